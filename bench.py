@@ -8,13 +8,19 @@ weight broadcast at load, no collectives in the step loop).
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Other BASELINE.json lines: --workload sd3-medium-1024 (configs[2]), --workload flux-dev-1024 --fp8 (configs[3]),
---batch 8 on 8 GPUs (configs[4]: 64 images per step over the node; --batch auto picks it when N > 1).  The default single-GPU run
-appends short legs of configs[2] and configs[3] to the same JSON line as "other_configs" (--no-other-configs skips them).
+--batch 8 on 8 GPUs (configs[4]: 64 images per step over the node; --batch auto picks it when N > 1).
+
+A plain run sets up, warms up, times the --steps steps, writes their outputs when --dump-outputs is given, and prints the line.
+Everything else the line can carry takes --full: the HIP-event replay behind "roofline", the CPU-port "cpu_baseline", and (single-GPU
+headline run) short legs of configs[2], configs[3] and the other workloads as "other_configs" (--no-roofline, --no-cpu-baseline and
+--no-other-configs drop single parts of it).
 
 A "step" is one pass of the hot path over one synthetic input per rank: the denoising steps (MMDiT
 forward + fused CFG/Euler update) followed by the VAE latent decode to a uint8 image.  Inputs
 (conditioning, weights) are resident in HBM before the timed region; the per-image noise draw is the
 reference's host numpy RNG (mlx/__init__.py:553-557) and its 1 MiB upload is inside the region.
+Inputs are seeded: the same arguments give the same inputs in every run.  --dump-outputs DIR writes what the last timed step
+returned to its caller (latents, float image, uint8 image) as DIR/<name>.npy in float32.
 Rank 0 prints ONE JSON line.
 """
 import argparse
@@ -30,6 +36,23 @@ sys.path.insert(0, ROOT)
 
 PEAK_BF16_TFLOPS = 2500.0  # /opt/skills/guides/MI355X_MICROARCH.md: dense bf16 MFMA peak
 PEAK_FP8_TFLOPS = 5000.0   # same table: dense fp8 (block-scaled K = 128 form)
+
+
+DUMP_BYTES = 60_000_000  # --dump-outputs: bytes of array data over all files and ranks (64 MB with room for the .npy headers)
+
+
+def dump_outputs(dump_dir, arrays, budget, suffix=""):
+    """--dump-outputs: each array as <dump_dir>/<name><suffix>.npy in float32.  A set larger than `budget` bytes keeps the same fraction
+    of every array, at flat positions drawn by a fixed seed (the same positions in every run of the same shapes), as a 1-D sample."""
+    import numpy as np
+    os.makedirs(dump_dir, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    frac = min(1.0, budget / max(sum(a.nbytes for a in host.values()), 1))
+    rng = np.random.default_rng(0)
+    for name, a in host.items():
+        if frac < 1.0:
+            a = a.reshape(-1)[np.sort(rng.integers(0, a.size, int(a.size * frac)))]
+        np.save(os.path.join(dump_dir, f"{name}{suffix}.npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def block_flops(S, h):
@@ -168,10 +191,12 @@ WORKLOAD_NAMES = {"flux-schnell-1024": "FLUX.1-schnell 1024x1024 4-step", "flux-
                   "tiny": "tiny"}
 
 
-def run_workload(ctx, workload, fp8, B, steps, warmup, guidance_embed=False, overlap_decode=False, want_roofline=True, max_replay=4, fp8_policy="quality", res=None):
+def run_workload(ctx, workload, fp8, B, steps, warmup, guidance_embed=False, overlap_decode=False, want_roofline=True, max_replay=4, fp8_policy="quality", res=None,
+                 dump_dir=None):
     """One bench leg: build the pipeline of `workload` on this rank, `warmup` untimed images, EXACTLY `steps` timed images
-    (each = the denoising steps + the VAE decode) bracketed by barrier + synchronize on both sides, max over ranks; then the
-    per-launch HIP-event replay for the roofline figures (rank 0).  Returns a dict of measurements (rank 0) or None."""
+    (each = the denoising steps + the VAE decode) bracketed by barrier + synchronize on both sides, max over ranks; the outputs of
+    the last timed image into `dump_dir` (when given); then the per-launch HIP-event replay for the roofline figures (rank 0).
+    Returns a dict of measurements (rank 0) or None."""
     from dataclasses import replace
 
     import numpy as np
@@ -254,11 +279,12 @@ def run_workload(ctx, workload, fp8, B, steps, warmup, guidance_embed=False, ove
         e1.record()
         if overlap_decode:
             pending.append(pipe.decode_async(lat))  # waited for in barrier(): every image is decoded inside the timed region
-            u8 = None
+            dec = pending[-1]
         else:
-            _, u8, _ = pipe.decoder.decode(lat)
+            img, u8, _ = pipe.decoder.decode(lat)
+            dec = (img, u8)
         e2.record()
-        return u8, (e0, e1, e2)
+        return (lat, dec), (e0, e1, e2)
 
     def barrier():
         while pending:
@@ -274,7 +300,7 @@ def run_workload(ctx, workload, fp8, B, steps, warmup, guidance_embed=False, ove
     t0 = time.perf_counter()
     evs = []
     for i in range(steps):
-        u8, ev = one_image(rank * 100000 + i)
+        out, ev = one_image(rank * 100000 + i)
         evs.append(ev)
     torch.cuda.synchronize()
     own = time.perf_counter() - t0  # this rank's own time (reported per rank; `elapsed` below is the contract's figure)
@@ -292,6 +318,11 @@ def run_workload(ctx, workload, fp8, B, steps, warmup, guidance_embed=False, ove
         allr = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
         per_rank = [float(t.item()) for t in allr]
+    if dump_dir:
+        lat, dec = out
+        img, u8 = dec.result() if overlap_decode else dec  # (a PendingDecode was waited for in barrier(): result() returns at once)
+        dump_outputs(dump_dir, {"latents": lat, "image": img, "image_u8": u8}, DUMP_BYTES // world,
+                     suffix=f"_rank{rank}" if world > 1 else "")
 
     # ---- roofline of the dominant kernel (the block Linears' MFMA GEMM), HIP events on the launch stream ----
     S_i = (latent[0] // cfg.patch_size) * (latent[1] // cfg.patch_size)
@@ -486,11 +517,17 @@ def main():
     ap.add_argument("--overlap-decode", action="store_true",
                     help="decode image i on a side stream while image i+1 is denoised (DiffusionPipeline.decode_async); the default, and the "
                          "headline, is the reference's order: denoise, then decode, image by image")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure more than the headline figure: the roofline replay, the CPU-port baseline and the `other_configs` legs "
+                         "(off: the run times the steps and prints the line, with those fields null)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (latents, float image, uint8 image) as DIR/<name>.npy "
+                         "in float32; at most 64 MB in all, a fixed seeded sample of each array beyond that (multi-GPU: <name>_rank<r>.npy)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU-port baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline replay")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short legs of BASELINE configs[2] (SD3-medium 1024x1024, 50 steps, CFG 5) and configs[3] (FLUX.1-dev, 50 steps, "
-                         "fp8 weights) that the default single-GPU headline run appends as `other_configs`")
+                    help="with --full: skip the short legs of BASELINE configs[2] (SD3-medium 1024x1024, 50 steps, CFG 5) and configs[3] (FLUX.1-dev, "
+                         "50 steps, fp8 weights) that a single-GPU headline run appends as `other_configs`")
     ap.add_argument("--res", type=int, default=None, metavar="PIXELS",
                     help="lab: run the chosen workload's model at PIXELS x PIXELS instead of its own resolution (a multiple of 16; dispatch sweeps, profiles/r06_res_sweep.md)")
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE",
@@ -501,6 +538,8 @@ def main():
                          "with the device work replaced by a sleep -- what tests/test_dist_cpu.py runs so that the first 8-GPU launch is not the "
                          "first time this code runs.  The line carries \"dry_run\": true and no roofline.")
     args = ap.parse_args()
+    if args.dry_run and args.dump_outputs:
+        ap.error("--dump-outputs needs device work: not with --dry-run")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args.gpus)
@@ -525,12 +564,13 @@ def main():
     ctx = {"rank": rank, "world": world, "dev": dev, "lib": lib}
 
     head = run_workload(ctx, args.workload, args.fp8, B, args.steps, args.warmup, guidance_embed=args.guidance_embed,
-                        overlap_decode=args.overlap_decode, want_roofline=not args.no_roofline, fp8_policy=args.fp8_policy, res=args.res)
+                        overlap_decode=args.overlap_decode, want_roofline=args.full and not args.no_roofline, fp8_policy=args.fp8_policy,
+                        res=args.res, dump_dir=args.dump_outputs)
 
     # ---- the other north-star configurations on the same driver-timed line (single-GPU headline runs only): short bounded legs,
     # same code path and timing contract as the headline (warm-up, barrier + synchronize brackets, decode inside the region) ----
     other = None
-    if world == 1 and args.workload == "flux-schnell-1024" and not args.fp8 and B == 1 and not args.no_other_configs and not args.tune and not args.res:
+    if args.full and world == 1 and args.workload == "flux-schnell-1024" and not args.fp8 and B == 1 and not args.no_other_configs and not args.tune and not args.res:
         other = {}
         for key, (wl, fp8, n_img, b_leg) in {
                 "sd3-medium-1024 (BASELINE configs[2])": ("sd3-medium-1024", False, 2, 1),
@@ -550,7 +590,7 @@ def main():
                           "roofline": {k: rf.get(k) for k in ("kernel", "achieved", "peak", "unit", "frac", "gemm_ms_per_image", "attention", "conv", "bf16_gemm") if k in rf}}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload != "tiny":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload != "tiny":
         cpu = cpu_baseline(head["cpu_workload"])
 
     if rank == 0:

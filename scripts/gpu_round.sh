@@ -9,7 +9,7 @@
 #   smoke            __graft_entry__.smoke()
 #   micro            scripts/microbench.py
 #   cpustep          scripts/cpu_flux_step.py, ALONE (round 4's first run shared the host with pytest: 250 s instead of ~170) -> cpu_flux_step.log
-#   bench[:name]     python bench.py $BENCH_<name> (default line when no name)          -> bench_<name>.json
+#   bench[:name]     python bench.py --full $BENCH_<name> (default line when no name)   -> bench_<name>.json
 #   prof[:name]      rocprofv3 --kernel-trace --stats over bench.py $BENCH_<name> $PROF_TAIL -> kernel_stats_<name>.md
 #   pmc[:name]       FETCH_SIZE / WRITE_SIZE / SQ passes (separate runs, kernel-trace only)  -> pmc_traffic_<name>.log, pmc_sq_<name>.log
 #   run:<script>     any other script of scripts/ (python or shell), logged                  -> <script>.log
@@ -53,7 +53,7 @@ for ST in $STAGES; do
     cpustep)
       timeout 900 python scripts/cpu_flux_step.py > $OUT/cpu_flux_step.log 2>&1; echo "cpustep exit $?" >> $OUT/cpu_flux_step.log; cat $OUT/cpu_flux_step.log ;;
     bench)
-      timeout 1200 python bench.py --gpus 1 $(bench_args $NAME) > $OUT/bench_$NAME.json 2> $OUT/bench_$NAME.err; echo "bench $NAME exit $?"
+      timeout 1200 python bench.py --gpus 1 --full $(bench_args $NAME) > $OUT/bench_$NAME.json 2> $OUT/bench_$NAME.err; echo "bench $NAME exit $?"
       python scripts/bench_line.py $OUT/bench_$NAME.json ;;
     prof)
       (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d $OLDPWD/$OUT/prof_$NAME -o run -- python $OLDPWD/bench.py --gpus 1 $(bench_args $NAME) $PROF_TAIL > $OLDPWD/$OUT/prof_$NAME.log 2>&1)

@@ -4,7 +4,7 @@
 OUT=${1:-gpurun_out/sweep}; mkdir -p $OUT
 run() {  # name, bench arguments
   local name=$1; shift
-  timeout 600 python bench.py --gpus 1 --no-cpu-baseline --no-other-configs "$@" > $OUT/$name.json 2> $OUT/$name.err
+  timeout 600 python bench.py --gpus 1 --full --no-cpu-baseline --no-other-configs "$@" > $OUT/$name.json 2> $OUT/$name.err
   python - "$name" $OUT/$name.json <<'PY'
 import json, sys
 name, path = sys.argv[1], sys.argv[2]

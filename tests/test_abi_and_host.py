@@ -186,3 +186,30 @@ def test_bench_cpu_sample_keeps_the_workload_width():
     cfg = tiny_sd3(depth=4)
     out = bench.cpu_baseline({"cfg": cfg, "latent": (8, 8), "num_steps": 2, "S_t": 24, "rows": 2}, threads=2)
     assert out["value"] > 0 and out["kind"] == "port" and out["cores"] == 2
+
+
+def test_bench_dump_outputs_budget(tmp_path):
+    """bench.py --dump-outputs: every array as <name>.npy in float32, whole while the set fits the budget; beyond it each array keeps
+    the same fraction of its values at seeded positions -- the same positions in every run, within 64 MB in all."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import numpy as np
+    import bench
+    assert bench.DUMP_BYTES <= 64_000_000 - 4096
+    g = torch.Generator().manual_seed(0)
+    lat, img = torch.randn(2, 8, 8, 16, generator=g), torch.rand(2, 64, 64, 3, generator=g)
+    arrays = {"latents": lat, "image": img, "image_u8": (img * 255).to(torch.uint8)}
+    bench.dump_outputs(str(tmp_path / "whole"), arrays, 10 ** 6)
+    for name, v in arrays.items():
+        a = np.load(tmp_path / "whole" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, v.float().numpy())
+    budget = lat.numel() + 2 * img.numel()  # bytes: a quarter of the set in float32
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays, budget, suffix="_rank0")
+    total = 0
+    for name, v in arrays.items():
+        a, b = (np.load(tmp_path / run / f"{name}_rank0.npy") for run in ("a", "b"))
+        assert a.dtype == np.float32 and a.ndim == 1 and a.size == v.numel() // 4 and np.array_equal(a, b)
+        assert np.isin(a, v.float().numpy().ravel()).all()
+        total += a.nbytes
+    assert total <= budget
