@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/dk_hip.h"
 #include "dk_common.h"
+#include "dk_ksplit.h"
 
 // ---- GEMM / implicit-GEMM conv ---------------------------------------------------------
 // C[m, n] = epi(alpha * sum_k A[m, k] * W[n, k] + bias[n])   (bf16 in, fp32 accumulate, bf16 out)
@@ -56,42 +57,67 @@ struct GemmParams {
   int qn_col0, qn_col1;
 };
 int dk_launch_gemm(const GemmParams& p, hipStream_t stream);
-// Plan mode (dk_gemm_plan / dk_gemm_pair_plan, host only): while g_dk_gemm_plan points at a record, the launchers fill it with what they WOULD launch and
-// return without touching the device -- the decision code is the launch code itself, so a CPU test can sweep shapes over the dispatch rules
-struct DkGemmPlan {
-  int kernel;      // 128: dk_gemm_bf16_kernel (128 x 128 tiles), 3: dk_gemm256v3_kernel (8 waves), 4: dk_gemm256v4_kernel (one wave per SIMD)
-  int tile_rows;   // 128 / 224 / 256
-  int tiles;       // output tiles of the launch (both problems of a grouped one)
-  int workgroups;  // grid size (tiles that are cut along K count once per piece)
-  int split_tiles; // tiles cut along K (0: none)
-  int k_pieces;    // pieces per cut tile
-  int ks;          // K-tile steps (64 elements each) of the finisher piece; whole tiles: K / 64
-  int n_cu;        // compute units the rules assumed
-  int launches;    // kernel launches the call expands to (a column split or a fused-norm fallback on the small kernel: 2)
-};
-extern thread_local DkGemmPlan* g_dk_gemm_plan;
-extern int g_dk_gemm_mode;
-extern int g_dk_v3_split;  // gemm256v3.hip: remainder-wave K split (-1 auto, 0 off, 1 whenever possible)
-extern int g_dk_pair_split_nk;  // gemm.hip: see dk_launch_gemm_pair
-extern int g_dk_v3_split_min;  // ... saved K-tile steps below which an all-remainder Linear stays whole (-1: default)
-extern int g_dk_v3_mf;     // gemm256v3.hip: wave-tile height in 16-row fragments (-1 auto, 8 = 256-row tiles, 7 = 224-row tiles)
-// workspace of the remainder-wave K split (fp32 slabs + flags; its last 4 KiB -- the flag region -- must be zero before the first
-// launch; the kernels leave it zero)
-size_t dk_gemm_split_workspace_bytes();
-bool dk_gemm256v3_eligible(const GemmParams& p);  // N % 128 == 0, K % 64 == 0, any M, any row-segment maps
-int dk_launch_gemm256v3(const GemmParams& p, const GemmParams* p2, hipStream_t stream);
-bool dk_gemm256v3_splits_whole_launch(const GemmParams& p, const GemmParams* p2);  // <= half a round of tiles, every tile cut along K (needs p.workspace)
-// gemm256v4.hip: one wave per SIMD, 256 accumulators in AGPRs, hand-scheduled asm body (N % 256 == 0, no conv / K split / half tiles)
-extern int g_dk_v4_auto;  // gemm.hip
-extern int g_dk_v4_skew;  // gemm256v4.hip
-bool dk_gemm256v4_eligible(const GemmParams& p);
-bool dk_gemm256v4_uniform_tiles(const GemmParams& p, int bm);
-int dk_gemm256v4_pick_mf(const GemmParams& p, const GemmParams* p2, int n_cu);
-int dk_launch_gemm256v4(const GemmParams& p, const GemmParams* p2, hipStream_t stream);
-int dk_launch_gemm256v3_raw(const GemmParams& p, const GemmParams& pb, int tiles_a, int tiles_b, hipStream_t stream);  // gemm256v3.hip (16x16x32 MFMA K loop)
 // two problems with the same N, K, epilogue in one launch (image + text stream of a double block); falls
 // back to two launches when the pair is not eligible for the grouped kernel
 int dk_launch_gemm_pair(const GemmParams& p0, const GemmParams& p1, hipStream_t stream);
+// dk_tune_set knobs of the routing (gemm.hip)
+extern int g_dk_gemm_mode;
+extern int g_dk_v3_split;       // remainder-wave K split (-1 auto, 0 off, 1 whenever possible)
+extern int g_dk_pair_split_nk;  // see route_pair
+extern int g_dk_v3_split_min;   // ... saved K-tile steps below which an all-remainder Linear stays whole (-1: default)
+extern int g_dk_v3_mf;          // wave-tile height in 16-row fragments (-1 auto, 8 = 256-row tiles, 7 = 224-row tiles)
+extern int g_dk_v4_auto;
+extern int g_dk_v4_skew;  // gemm256v4.hip
+
+// How the tiles beyond the last full wave of the CUs are cut along K (gemm256v3.hip's SplitArgs): n_dp whole tiles, then n_rem tiles in S
+// pieces each, the finisher's ks K-tiles first.  n_rem == 0: no split (S = 1, ks = all K-tiles).
+struct SplitPlan {
+  int n_dp, n_rem, S, ks;
+};
+// the split of `tiles` tiles of nk K-tiles each on n_cu CUs (gemm.hip; the fp8 kernel's split takes it too)
+SplitPlan dk_plan_split(int tiles, int nk, bool have_ws, int n_cu, bool linear);
+// the caller's K-split workspace is usable (never with the fused key QKNorm: a cut tile's finisher has no second pass over its row sums)
+template <class P>
+bool dk_ksplit_ws_ok(const P& p, const P* p2) {
+  return p.workspace != nullptr && p.workspace_bytes >= DK_KSPLIT_WS_BYTES && ((uintptr_t)p.workspace & 255) == 0 && p.kn_w == nullptr &&
+         (p2 == nullptr || p2->kn_w == nullptr);
+}
+
+// What one dk_launch_gemm / dk_launch_gemm_pair call launches: dk_gemm_route (gemm.hip) decides it from the problem(s), the CU count and the
+// tuning knobs alone; the launchers below take it as it is, and dk_gemm_plan reports it.
+struct GemmRoute {
+  // the call expands into two calls: the two problems of a pair one after the other, the two column ranges of a column split on the
+  // 128^2 kernel, or the projection without the fused key QKNorm followed by the stand-alone norm pass
+  enum { PAIR = -1, COLUMNS = -2, KNORM = -3 };
+  int kernel;     // 128: dk_gemm_bf16_kernel (128 x 128 tiles), 3: dk_gemm256v3_kernel (8 waves), 4: dk_gemm256v4_kernel (one wave per SIMD); or < 0
+  int tile_rows;  // 128 / 224 / 256
+  int tiles_a, tiles_b;  // output tiles of each problem (tiles_b: 0 without a second one)
+  int n_cu;       // compute units the rules assumed
+  SplitPlan split;  // kernel 3 only; otherwise {tiles, 0, 1, K / 64}
+};
+int dk_gemm_route(const GemmParams& p, const GemmParams* p2, int n_cu, GemmRoute& r);
+int dk_gemm_plan_call(const GemmParams& p, const GemmParams* p2, dk_gemm_plan_t& rec);  // dk_gemm_plan: records the routes, launches nothing
+
+// workspace of the remainder-wave K split (dk_ksplit.h: fp32 slabs + the flag region, which must be zero before the first launch; the kernels
+// leave it zero)
+size_t dk_gemm_split_workspace_bytes();
+bool dk_gemm256v3_eligible(const GemmParams& p);  // N % 128 == 0, K % 64 == 0, any M, any row-segment maps
+int dk_launch_gemm256v3(const GemmParams& p, const GemmParams* p2, const GemmRoute& r, hipStream_t stream);  // (16x16x32 MFMA K loop)
+// gemm256v4.hip: one wave per SIMD, 256 accumulators in AGPRs, hand-scheduled asm body (N % 256 == 0, no conv / K split / half tiles)
+bool dk_gemm256v4_eligible(const GemmParams& p);
+int dk_launch_gemm256v4(const GemmParams& p, const GemmParams* p2, const GemmRoute& r, hipStream_t stream);
+
+// fused key (and query) QKNorm + RoPE in the tail of a 256-column kernel (GemmParams / GemmF8Params kn_*, qn_*): whole 256-column tiles of 128- or
+// 64-column heads, bias-only first output
+template <class P>
+bool dk_qknorm_eligible(const P& p) {
+  if (p.kn_w == nullptr) return p.qn_w == nullptr;  // the query side rides on the key side's machinery
+  if (p.epi != DK_EPI_BIAS || (p.kn_D != 128 && p.kn_D != 64) || p.kn_seg_len <= 0 || p.kn_col0 % 256 != 0 || p.kn_col1 % 256 != 0 || p.kn_col0 >= p.kn_col1 ||
+      p.kn_col1 > (p.n_split > 0 ? p.n_split : p.N) || ((uintptr_t)p.kn_w & 15) != 0 || ((uintptr_t)p.kn_rope & 15) != 0)
+    return false;
+  return p.qn_w == nullptr || !(p.qn_col0 % 256 != 0 || p.qn_col1 % 256 != 0 || p.qn_col0 >= p.qn_col1 || p.qn_col1 > (p.n_split > 0 ? p.n_split : p.N) ||
+                                (p.qn_col0 < p.kn_col1 && p.kn_col0 < p.qn_col1) || ((uintptr_t)p.qn_w & 15) != 0);
+}
 
 // ---- fp8 GEMM (gemm256f8.hip): e4m3 weights with per-output-channel fp32 scales, MX-fp8 activations -------------------
 // C[m, n] = epi(wscale[n] * sum_k A[m, k] * 2^(SA[m, k / 32] - 127) * W[n, k] + bias[n]); same row-segment maps, epilogues,
@@ -129,7 +155,7 @@ struct GemmF8Params {
   float kn_eps;
   const bf16_t* qn_w;  // ... and of the query columns [qn_col0, qn_col1) (see GemmParams)
   int qn_col0, qn_col1;
-  // optional K-split scratch (dk_gemm_split_workspace_bytes(), the bf16 kernels' buffer: fp32 slabs + flags, flag region zero between launches):
+  // optional K-split scratch (dk_gemm_split_workspace_bytes(), the bf16 kernels' buffer: dk_ksplit.h, flag region zero between launches):
   // round 6 -- a launch of at most half a round of tiles with a long reduction is cut along K (FLUX below 1024 x 1024)
   void* workspace;
   size_t workspace_bytes;

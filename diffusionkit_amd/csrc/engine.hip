@@ -86,16 +86,8 @@ extern "C" int dk_gemm_bf16(const dk_gemm_desc* d, void* stream) {
 
 extern "C" int dk_gemm_plan(const dk_gemm_desc* d, const dk_gemm_desc* d2, dk_gemm_plan_t* plan) {
   DK_REQUIRE(d != nullptr && plan != nullptr, "null descriptor / plan");
-  static_assert(sizeof(dk_gemm_plan_t) == sizeof(DkGemmPlan), "the ABI record mirrors the launchers' record");
-  DkGemmPlan rec;
-  memset(&rec, 0, sizeof(rec));
-  struct Scope {  // (the launchers see the record only for the duration of this call, whatever path returns)
-    explicit Scope(DkGemmPlan* r) { g_dk_gemm_plan = r; }
-    ~Scope() { g_dk_gemm_plan = nullptr; }
-  } scope(&rec);
-  const int rc = d2 != nullptr ? dk_launch_gemm_pair(gemm_params_from_desc(d), gemm_params_from_desc(d2), nullptr) : dk_launch_gemm(gemm_params_from_desc(d), nullptr);
-  memcpy(plan, &rec, sizeof(rec));
-  return rc;
+  const GemmParams p2 = d2 != nullptr ? gemm_params_from_desc(d2) : GemmParams{};
+  return dk_gemm_plan_call(gemm_params_from_desc(d), d2 != nullptr ? &p2 : nullptr, *plan);
 }
 
 // workspace: optional K-split scratch (dk_gemm_split_workspace_bytes) for stages whose tiles fill only half the CUs
@@ -722,7 +714,7 @@ extern "C" int dk_mmdit_prepare(dk_mmdit* m, int32_t batch, int32_t latent_h, in
                                   (size_t)mh * m->h() * 2, (size_t)gw * m->h() * 2, gh, hipMemcpyDeviceToDevice, st));
   }
   // the flag region of the GEMM split workspace must be zero before the first launch (the kernels leave it zero)
-  DK_CHECK_HIP(hipMemsetAsync((char*)m->GWS + dk_gemm_split_workspace_bytes() - 4096, 0, 4096, st));
+  DK_CHECK_HIP(hipMemsetAsync((char*)m->GWS + DK_KSPLIT_FLAGS_OFF, 0, DK_KSPLIT_FLAG_BYTES, st));
   m->prepared = true;
   m->mod_ready = false;
   m->ctx_ready = false;
@@ -1385,7 +1377,7 @@ extern "C" int dk_vae_decode(dk_vae* v, const float* latent, int32_t batch, int3
   VaeRun R{v, S_(stream), batch};
   hipStream_t st = R.st;
   // the flag region of the GEMM split workspace must be zero before the first launch (the kernels leave it zero)
-  DK_CHECK_HIP(hipMemsetAsync((char*)v->GWS + dk_gemm_split_workspace_bytes() - 4096, 0, 4096, st));
+  DK_CHECK_HIP(hipMemsetAsync((char*)v->GWS + DK_KSPLIT_FLAGS_OFF, 0, DK_KSPLIT_FLAG_BYTES, st));
   LinearWsScope ws_scope(v->GWS);
   DK_CHECK_HIP(hipMemsetAsync(v->ZERO, 0, 256, st));
   int H = latent_h, W = latent_w;
@@ -1514,7 +1506,7 @@ extern "C" int dk_vae_encode(dk_vae* v, const float* image, int32_t batch, int32
   DK_REQUIRE(need_bytes <= workspace_bytes, "workspace too small");
   VaeRun R{v, S_(stream), batch};
   hipStream_t st = R.st;
-  DK_CHECK_HIP(hipMemsetAsync((char*)v->GWS + dk_gemm_split_workspace_bytes() - 4096, 0, 4096, st));
+  DK_CHECK_HIP(hipMemsetAsync((char*)v->GWS + DK_KSPLIT_FLAGS_OFF, 0, DK_KSPLIT_FLAG_BYTES, st));
   LinearWsScope ws_scope(v->GWS);
   DK_CHECK_HIP(hipMemsetAsync(v->ZERO, 0, 256, st));
   int H = image_h, W = image_w;

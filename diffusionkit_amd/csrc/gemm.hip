@@ -230,44 +230,188 @@ __global__ __launch_bounds__(256) void dk_gemm_bf16_kernel(GemmParams p) {
   }
 }
 
+// ---------------- routing: kernel, tile height and K split of one call (dk_gemm_route), read by the launches and by dk_gemm_plan ----------------
+
 // tuning knob (dk_tune_set("gemm", v)): -1 = automatic choice, 128 = always the 128^2-tile kernel of this file, 9 = the 256^2 kernel
 // (gemm256v3.hip) on every shape it accepts, 10 = the one-wave-per-SIMD 256^2 kernel (gemm256v4.hip) on every shape IT accepts (others: 9)
 int g_dk_gemm_mode = -1;
-thread_local DkGemmPlan* g_dk_gemm_plan = nullptr;
+int g_dk_pair_split_nk = -1;  // dk_tune_set("gemm_pair_nk", v): K-tile steps from which an image + text pair whose extra round is a small remainder is grouped and cut along K; -1: 24 (32 until the raw-accumulator exchange of round 6: profiles/r06_gemm_pair_nk.log)
+int g_dk_v4_auto = -1;  // dk_tune_set("gemm_v4", v): -1 (default) the rule in use_v4, 0 never in the automatic choice (A/B runs)
+// dk_tune_set("gemm_split", v): -1 (default) split a remainder wave of at most half the CUs into equal pieces when the
+// cost model below says it pays, 0 never, 1 whenever possible.  Kernel lab (profiles/archive/r01_gemm_lab.md): every workgroup
+// carries ~18 us of fixed cost (launch, first DMA, tail) and a CU runs its K-tiles ~20 % slower when all 256 CUs are busy
+// than when 192 are, so a remainder of MORE than half the CUs (finisher + several producer pieces in turn on the
+// spare CUs) loses on every shape but the longest-K one and is only taken when forced.
+int g_dk_v3_split = -1;
+int g_dk_v3_split_min = -1;  // dk_tune_set("gemm_split_min", v): saved K-tile steps below which a Linear that is ALL remainder stays whole; -1: 32 (see dk_plan_split)
+// dk_tune_set("gemm_mf", v): wave-tile height in 16-row fragments; -1 (default) = the height with the fewest rounds x height, 8 / 7 forced
+int g_dk_v3_mf = -1;
 
-// Which of the two 256^2 kernels takes a launch both accept.  gemm256v4.hip (one wave per SIMD, asm body) runs its K loop 5-7 % faster
-// (profiles/r05_gemm_v4_*.log: 8192^3 1587 against 1488 TF with cold weights, the model's linear1 / linear2 / fc1 / fc2 +4-5 %), but has no
+SplitPlan dk_plan_split(int tiles, int nk, bool have_ws, int n_cu, bool linear) {
+  SplitPlan none{tiles, 0, 1, nk};
+  if (!have_ws || g_dk_v3_split == 0 || n_cu < 16) return none;
+  const int G = n_cu & ~7;
+  const int T = tiles % G;
+  if (T == 0) return none;
+  const int E = G - T;
+  int S, ks, t_steps;  // t_steps: K-tile steps until the split wave is done
+  if (T > G / 2) {  // one producer piece per tile, c = ceil(T / E) of them in turn on each of the E spare CUs
+    if (g_dk_v3_split < 0) return none;
+    S = 2;
+    const int c = (T + E - 1) / E;
+    ks = (nk * c + c) / (c + 1);  // ~ nk * c / (c + 1), rounded up: the finishers must not end before the producers
+    if (ks > nk - 1) ks = nk - 1;
+    t_steps = ks > c * (nk - ks) ? ks : c * (nk - ks);
+  } else {  // S equal pieces per tile, one CU each
+    S = G / T < 4 ? G / T : 4;
+    ks = (nk + S - 1) / S;
+    t_steps = ks;
+  }
+  if (S < 2 || ks < 1 || nk - ks < S - 1 || T * (S - 1) > DK_KSPLIT_SLABS) return none;
+  // a K-tile step costs about 1.45 us; splitting costs a slab write + read and a flag round trip per tile
+  if (g_dk_v3_split < 0 && (nk - t_steps) * 1.45 < 25.0) return none;
+  // a Linear that is ALL remainder (round 6: FLUX / SD3 below 1024 x 1024, 60 - 120 tiles): every tile pays S - 1 slab round trips at once, and the few
+  // busy CUs run their K-tiles in ~1 us.  Measured (profiles/r06_gemm_small_m.log, r06_res_sweep.md): with the fp32-image exchange of rounds 1-5 FLUX's o_proj at
+  // 512 x 512 (K = 3072, four ranges: 36 steps saved) lost 16 us with the split and fc2 / linear2 (144 / 180 saved) gained 60 - 90; with the raw-accumulator
+  // exchange (gemm256v3.hip, round 6) the in-model sweep is flat from 0 to 48 saved steps and 1 % better at 24 - 36 than at 48: the rule cuts from 32
+  if (g_dk_v3_split < 0 && linear && tiles < G && nk - t_steps < (g_dk_v3_split_min >= 0 ? g_dk_v3_split_min : 32)) return none;
+  return SplitPlan{tiles - T, T, S, ks};
+}
+
+// a launch of `kernel` with bm x bn tiles over p (and p2), not split
+static GemmRoute tile_route(int kernel, int bm, int bn, const GemmParams& p, const GemmParams* p2, int n_cu) {
+  GemmRoute r;
+  r.kernel = kernel;
+  r.tile_rows = bm;
+  r.tiles_a = ((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn);
+  r.tiles_b = p2 ? ((p2->M + bm - 1) / bm) * ((p2->N + bn - 1) / bn) : 0;
+  r.n_cu = n_cu;
+  r.split = SplitPlan{r.tiles_a + r.tiles_b, 0, 1, p.K / BK};
+  return r;
+}
+static long tiles256(const GemmParams& p, const GemmParams* p2, int bm) {
+  long tiles = (long)((p.M + bm - 1) / bm) * ((p.N + 255) / 256);
+  if (p2) tiles += (long)((p2->M + bm - 1) / bm) * ((p2->N + 255) / 256);
+  return tiles;
+}
+
+// Tile height of the 256-column kernels.  Model: rounds of the CUs x rows per tile, over both problems of a grouped launch (same N).  Measured
+// (profiles/r02_gemm_tile_height.log): on the FLUX shapes 224-row tiles save 2.7 % of the GEMM time -- far less than the 12.5 %
+// the model promises, because a K-tile runs slower the more CUs are busy (the chip is power / fabric bound) -- and on
+// the short-K SD3 shapes the 15 % extra tiles (each with its fixed prologue + tail) cost more than the fuller round gives back.
+// So: 224-row tiles only for long reductions, and only when the model predicts at least 10 %.
+static int fewest_rounds_mf(const GemmParams& p, const GemmParams* p2, int n_cu) {
+  long cost[2];
+  for (int mf = 7; mf <= 8; ++mf) {
+    const int bm = 32 * mf;
+    cost[mf - 7] = ((tiles256(p, p2, bm) + n_cu - 1) / n_cu) * bm;
+  }
+  return cost[0] * 10 <= cost[1] * 9 ? 7 : 8;
+}
+
+// gemm256v3.hip: the tile height, then the K split of the remainder wave
+static GemmRoute route_v3(const GemmParams& p, const GemmParams* p2, int n_cu) {
+  const bool have_ws = dk_ksplit_ws_ok(p, p2);
+  const int nk = p.K / BK;
+  int mf = 8;
+  if (g_dk_v3_mf == 7 || g_dk_v3_mf == 8) {
+    mf = g_dk_v3_mf;
+  } else if (p.K >= 2048) {
+    // Small launches (round 6; the reference CLI's 512 x 512 default: FLUX's o_proj / fc2 / linear2 are 60 - 84 tiles for 256 CUs): when both
+    // heights leave at least half the CUs idle the launch is one split "remainder", and what a CU runs is the finisher piece: ks K-tiles of bm rows
+    const long t7 = tiles256(p, p2, 224), t8 = tiles256(p, p2, 256);
+    SplitPlan s7{}, s8{};
+    if (have_ws && !p.conv && (t7 < t8 ? t7 : t8) * 2 <= n_cu && t7 <= n_cu && t8 <= n_cu) {
+      s7 = dk_plan_split((int)t7, nk, true, n_cu, true);
+      s8 = dk_plan_split((int)t8, nk, true, n_cu, true);
+    }
+    if (s7.n_rem > 0 || s8.n_rem > 0)
+      mf = 224L * (s7.n_rem > 0 ? s7.ks : nk) < 256L * (s8.n_rem > 0 ? s8.ks : nk) ? 7 : 8;
+    else
+      mf = fewest_rounds_mf(p, p2, n_cu);
+  }
+  GemmRoute r = tile_route(3, 32 * mf, 256, p, p2, n_cu);
+  r.split = dk_plan_split(r.tiles_a + r.tiles_b, nk, have_ws, n_cu, !p.conv);
+  return r;
+}
+
+// gemm256v4.hip: every row tile of height bm lies inside one segment of every row map (its tile-uniform tail paths: FAST, or CUT for the last one)
+static bool uniform_tiles(const GemmParams& p, int bm) {
+  auto ok = [&](int len) { return len >= p.M || len % bm == 0; };
+  const bool res = p.epi == DK_EPI_GATE_RES || p.epi == DK_EPI_RES || (p.n_split > 0 && (p.epi2 == DK_EPI_GATE_RES || p.epi2 == DK_EPI_RES));
+  const bool gate = p.epi == DK_EPI_GATE_RES || (p.n_split > 0 && p.epi2 == DK_EPI_GATE_RES);
+  return ok(p.a_seg_len) && ok(p.c_seg_len) && (!res || ok(p.r_seg_len)) && (!gate || ok(p.gate_seg_len)) && (p.kn_w == nullptr || ok(p.kn_seg_len));
+}
+// gemm256v4.hip (both problems eligible): gemm256v3.hip's height rule without the K split, 256-row tiles where a 224-row tile would straddle a segment
+static GemmRoute route_v4(const GemmParams& p, const GemmParams* p2, int n_cu) {
+  int mf = 8;
+  if (g_dk_v3_mf == 7 || g_dk_v3_mf == 8)
+    mf = g_dk_v3_mf;
+  else if (p.K >= 2048 && uniform_tiles(p, 224) && (p2 == nullptr || uniform_tiles(*p2, 224)))  // (the per-row tail path is slow there)
+    mf = fewest_rounds_mf(p, p2, n_cu);
+  return tile_route(4, 32 * mf, 256, p, p2, n_cu);
+}
+
+// Which of the two 256^2 kernels takes a launch both accept (v3 / v4: its route on each).  gemm256v4.hip (one wave per SIMD, asm body) runs its K loop
+// 5-7 % faster (profiles/r05_gemm_v4_*.log: 8192^3 1587 against 1488 TF with cold weights, the model's linear1 / linear2 / fc1 / fc2 +4-5 %), but has no
 // remainder handling: gemm256v3.hip keeps the launches whose last round of the CUs is a small remainder (its 224-row tiles and the
 // remainder-wave K split fill those: the q / k / v projections at 2.25-2.4 rounds, the grouped image + text fc1 at 3.2).
-int g_dk_pair_split_nk = -1;  // dk_tune_set("gemm_pair_nk", v): K-tile steps from which an image + text pair whose extra round is a small remainder is grouped and cut along K; -1: 24 (32 until the raw-accumulator exchange of round 6: profiles/r06_gemm_pair_nk.log)
-int g_dk_v4_auto = -1;  // dk_tune_set("gemm_v4", v): -1 (default) the rule below, 0 never in the automatic choice (A/B runs)
-static bool dk_use_v4(const GemmParams& a, const GemmParams* b) {
+static bool use_v4(const GemmParams& p, const GemmParams* p2, const GemmRoute& v3, const GemmRoute& v4) {
   if (g_dk_gemm_mode != 10 && (g_dk_gemm_mode != -1 || g_dk_v4_auto == 0)) return false;
-  if (!dk_gemm256v4_eligible(a) || (b != nullptr && !dk_gemm256v4_eligible(*b))) return false;
   if (g_dk_gemm_mode == 10) return true;
+  const int n_cu = v3.n_cu;
   // Small launches (round 6): at most half a round of tiles, and gemm256v3.hip would cut every one of them along K -- FLUX at the reference CLI's
   // 512 x 512 default: o_proj / fc2 / linear2 are 60 - 84 tiles on 256 CUs, linear2 229 us on this kernel (profiles/r06_flux_512_kernel_stats_before.md)
-  if (g_dk_v4_auto != 2 && dk_gemm256v3_splits_whole_launch(a, b)) return false;
+  // (the one-wave-per-SIMD kernel has no K split, and 60 tiles on 256 CUs waste three quarters of the chip)
+  const bool v3_cuts_all = (long)(v3.tiles_a + v3.tiles_b) * 2 <= n_cu && v3.split.n_rem > 0 && v3.split.n_dp == 0;
+  if (g_dk_v4_auto != 2 && v3_cuts_all) return false;
   // launches with tiles that straddle row segments or short reductions with ragged rows stay on gemm256v3.hip: this kernel's per-row tail path
   // is slow (the lab's 1178 x 6144 x 1536 text fc1: 80 us here against 49 there) and its fixed cost per tile ~ 1 us higher (SD3-medium in the
   // model: every eligible launch 22.0 against 21.5 ms per step, whole-tile launches only 21.2; profiles/r05_gemm_v4_in_model.log).
   // ("gemm_v4" 2: lab, no such restriction)
-  const int n_cu = dk_device_cu_count();
-  const int mf = dk_gemm256v4_pick_mf(a, b, n_cu), bm = 32 * mf;
-  const bool uniform = dk_gemm256v4_uniform_tiles(a, bm) && (b == nullptr || dk_gemm256v4_uniform_tiles(*b, bm));
+  const int bm = v4.tile_rows;
+  const bool uniform = uniform_tiles(p, bm) && (p2 == nullptr || uniform_tiles(*p2, bm));
   // (K < 2048: the image stream's fc1 of SD3 alone on this kernel measured +1.1 % per step on one box and -0.9 % on another: short reductions stay
   //  on gemm256v3.hip)
-  if ((!uniform || a.K < 2048) && g_dk_v4_auto != 2) return false;
-  long tiles = (long)((a.M + bm - 1) / bm) * (a.N / 256);
-  if (b) tiles += (long)((b->M + bm - 1) / bm) * (b->N / 256);
+  if ((!uniform || p.K < 2048) && g_dk_v4_auto != 2) return false;
+  const long tiles = (long)v4.tiles_a + v4.tiles_b;
   // (the rounds test in units of the device's CUs: the constants were fitted on 256 CUs -- a last round more than 56 % full, or 8 rounds and more)
   const long frac = tiles % n_cu;
   return tiles <= n_cu || tiles >= 8L * n_cu || frac == 0 || frac * 16 > 9L * n_cu;
 }
 
-int dk_launch_gemm(const GemmParams& p_in, hipStream_t stream) {
-  GemmParams p = p_in;
-  if (p.ldw <= 0) p.ldw = p.K;
+// the grouped launch of an image + text pair (same N, K, epilogue), or PAIR: two launches
+static int route_pair(const GemmParams& a, const GemmParams& b, int n_cu, GemmRoute& r) {
+  r.kernel = GemmRoute::PAIR;
+  const bool same = a.N == b.N && a.K == b.K && a.epi == b.epi && a.alpha == b.alpha && a.n_split == 0 && b.n_split == 0;
+  if (!((g_dk_gemm_mode == -1 || g_dk_gemm_mode == 10) && same && (a.M >= 1024 || b.M >= 1024) && (a.N % 256 == 0 || a.N >= 1024) &&
+        dk_gemm256v3_eligible(a) && dk_gemm256v3_eligible(b)))
+    return 0;
+  // group only when the extra tiles do not open another wave of the CUs (kernel lab: a partial extra wave costs more
+  // than the small separate launch) ...
+  const long ta = (long)((a.M + 255) / 256) * ((a.N + 255) / 256), tb = (long)((b.M + 255) / 256) * ((b.N + 255) / 256);
+  const long nc = n_cu;  // (rounds in units of THIS device's CUs; the fractions below were fitted on 256)
+  // ... unless the kernel can cut that extra, small wave along K (remainder-wave split, needs the workspace)
+  const bool split_ok = g_dk_v3_split != 0 && a.workspace != nullptr && (ta + tb) % nc <= nc / 4 && a.K / 64 >= (g_dk_pair_split_nk >= 0 ? g_dk_pair_split_nk : 24);
+  const GemmRoute v3 = route_v3(a, &b, n_cu);
+  // (gemm256v4.hip: the same test at ITS tile height -- with 224-row tiles the image + text fc1 of FLUX is 912 + 96 tiles: both 4 rounds)
+  if (dk_gemm256v4_eligible(a) && dk_gemm256v4_eligible(b)) {
+    const GemmRoute v4 = route_v4(a, &b, n_cu);
+    const long ta4 = v4.tiles_a, tb4 = v4.tiles_b;
+    if ((ta4 + nc - 1) / nc == (ta4 + tb4 + nc - 1) / nc && use_v4(a, &b, v3, v4)) {
+      r = v4;
+      return 0;
+    }
+  }
+  if ((ta + nc - 1) / nc == (ta + tb + nc - 1) / nc || split_ok) {
+    DK_REQUIRE(!a.conv && !b.conv, "gemm256v3: no grouped convolutions");
+    r = v3;
+  }
+  return 0;
+}
+
+int dk_gemm_route(const GemmParams& p, const GemmParams* p2, int n_cu, GemmRoute& r) {
+  if (p2 != nullptr) return route_pair(p, *p2, n_cu, r);
   DK_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0, "empty GEMM");
   DK_REQUIRE(p.ldw >= p.K && p.ldw % 8 == 0, "ldw must be >= K and a multiple of 8 elements");
   // the 256^2 kernel (16x16x32 MFMA, LDS-DMA ring, any M and any row-segment map) takes every large-M shape it accepts; small M
@@ -279,39 +423,35 @@ int dk_launch_gemm(const GemmParams& p_in, hipStream_t stream) {
   const bool big = !p.conv && g_dk_gemm_mode != 128 && half_ok && dk_gemm256v3_eligible(p) &&
                    (p.M >= 1024 || g_dk_gemm_mode == 9 || (g_dk_gemm_mode == 10 && dk_gemm256v4_eligible(p)));
   if (g_dk_gemm_mode == 9 && !p.conv) DK_REQUIRE(big, "gemm256v3 forced but the shape does not allow it");
-  if (big && dk_use_v4(p, nullptr)) return dk_launch_gemm256v4(p, nullptr, stream);
-  if (big) return dk_launch_gemm256v3(p, nullptr, stream);
+  if (big) {
+    r = route_v3(p, nullptr, n_cu);
+    if (dk_gemm256v4_eligible(p)) {
+      const GemmRoute v4 = route_v4(p, nullptr, n_cu);
+      if (use_v4(p, nullptr, r, v4)) r = v4;
+    }
+    return 0;
+  }
+  // the fused key QKNorm + RoPE lives in the 256^2 kernel's tail: any other route runs the projection plain and the
+  // stand-alone pass over its key columns afterwards
   if (p.kn_w != nullptr) {
-    // the fused key QKNorm + RoPE lives in the 256^2 kernel's tail: any other route runs the projection plain and the
-    // stand-alone pass over its key columns afterwards
-    GemmParams plain = p;
-    plain.kn_w = nullptr;
-    plain.qn_w = nullptr;
-    const int rc = dk_launch_gemm(plain, stream);
-    if (rc) return rc;
-    DK_REQUIRE(p.c_seg_len == p.kn_seg_len || p.c_seg_len >= p.M, "fused key QKNorm: the output's row segments must be the sequences");
-    // (with the query side asked for as well -- qn_w -- the pass covers both column ranges: they hold the same number of heads)
-    DK_REQUIRE(p.qn_w == nullptr || p.qn_col1 - p.qn_col0 == p.kn_col1 - p.kn_col0, "fused QKNorm: query and key ranges must hold the same heads");
-    return dk_launch_qk_norm_rope(p.C, p.ldc, p.qn_w ? p.qn_col0 : 0, p.kn_col0, p.M, (p.kn_col1 - p.kn_col0) / p.kn_D, p.kn_D, p.qn_w ? p.qn_w : p.kn_w, p.kn_w,
-                                  p.kn_eps, p.kn_rope, p.kn_seg_len, p.c_seg_len == p.kn_seg_len ? p.c_seg_stride : p.kn_seg_len, p.kn_pos_off, 0,
-                                  stream, p.qn_w ? 0 : 1);
+    r.kernel = GemmRoute::KNORM;
+    return 0;
   }
   if (p.n_split > 0) {
     // column-split GEMM on the kernel without split support: two GEMMs over the two column ranges
     DK_REQUIRE(p.n_split < p.N && p.C2 != nullptr, "bad column split");
-    GemmParams a = p, b = p;
-    a.N = p.n_split; a.n_split = 0;
-    b.N = p.N - p.n_split; b.n_split = 0; b.W = p.W + (size_t)p.n_split * p.ldw; b.bias = p.bias ? p.bias + p.n_split : nullptr;
-    b.C = p.C2; b.ldc = p.ldc2; b.epi = p.epi2;
-    const int rc = dk_launch_gemm(a, stream);
-    return rc ? rc : dk_launch_gemm(b, stream);
+    r.kernel = GemmRoute::COLUMNS;
+    return 0;
   }
   if (p.conv && g_dk_gemm_mode != 128 && dk_gemm256v3_eligible(p)) {
     // implicit-GEMM convolutions with O % 256 == 0 ride the 256^2 kernel once their tiles fill most of the CUs (the VAE's 256^2-pixel
     // and larger stages); the 128^2-tile kernel below keeps the small stages and O = 128
     const long t256 = (long)((p.M + 255) / 256) * ((p.N + 255) / 256);
     // (with the K-split workspace a stage of about half the CUs' worth of tiles goes there too: its tiles are cut in two along K)
-    if (g_dk_gemm_mode == 9 || t256 >= 192 || (p.workspace != nullptr && t256 >= 96 && t256 <= 128)) return dk_launch_gemm256v3(p, nullptr, stream);
+    if (g_dk_gemm_mode == 9 || t256 >= 192 || (p.workspace != nullptr && t256 >= 96 && t256 <= 128)) {
+      r = route_v3(p, nullptr, n_cu);
+      return 0;
+    }
   }
   DK_REQUIRE(p.K % BK == 0, "K must be a multiple of 64");
   DK_REQUIRE(p.ldc % 4 == 0, "ldc must be a multiple of 4 elements");
@@ -323,20 +463,18 @@ int dk_launch_gemm(const GemmParams& p_in, hipStream_t stream) {
   }
   if (p.epi == DK_EPI_GATE_RES) DK_REQUIRE(p.gate && p.res, "gate/res missing");
   if (p.epi == DK_EPI_RES) DK_REQUIRE(p.res, "res missing");
-  const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
-  if (g_dk_gemm_plan != nullptr) {
-    DkGemmPlan& pl = *g_dk_gemm_plan;
-    pl.kernel = 128; pl.tile_rows = BM; pl.tiles = pl.workgroups = nbm * nbn; pl.split_tiles = 0; pl.k_pieces = 1; pl.ks = p.K / BK;
-    pl.n_cu = dk_device_cu_count(); pl.launches += 1;
-    return 0;
-  }
+  r = tile_route(128, BM, BN, p, nullptr, n_cu);
+  return 0;
+}
+
+static int launch_gemm128(const GemmParams& p, const GemmRoute& r, hipStream_t stream) {
   static DkDeviceOnce attr_once;
   if (attr_once.first()) {
     DK_CHECK_HIP(hipFuncSetAttribute((const void*)dk_gemm_bf16_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE_BYTES));
     DK_CHECK_HIP(hipFuncSetAttribute((const void*)dk_gemm_bf16_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE_BYTES));
     attr_once.mark();
   }
-  dim3 grid(nbm * nbn), block(256);
+  dim3 grid(r.tiles_a), block(256);
   dk_prof_begin(p.conv ? 1 : 0, 2.0 * (double)p.M * (double)p.N * (double)p.K, stream);
   if (p.conv)
     hipLaunchKernelGGL(dk_gemm_bf16_kernel<1>, grid, block, 2 * STAGE_BYTES, stream, p);
@@ -347,28 +485,59 @@ int dk_launch_gemm(const GemmParams& p_in, hipStream_t stream) {
   return 0;
 }
 
-int dk_launch_gemm_pair(const GemmParams& a_in, const GemmParams& b_in, hipStream_t stream) {
-  GemmParams a = a_in, b = b_in;
-  if (a.ldw <= 0) a.ldw = a.K;
-  if (b.ldw <= 0) b.ldw = b.K;
-  const bool same = a.N == b.N && a.K == b.K && a.epi == b.epi && a.alpha == b.alpha && a.n_split == 0 && b.n_split == 0;
-  if ((g_dk_gemm_mode == -1 || g_dk_gemm_mode == 10) && same && (a.M >= 1024 || b.M >= 1024) && (a.N % 256 == 0 || a.N >= 1024) &&
-      dk_gemm256v3_eligible(a) && dk_gemm256v3_eligible(b)) {
-    // group only when the extra tiles do not open another wave of the 256 CUs (kernel lab: a partial extra wave costs more
-    // than the small separate launch) ...
-    const long ta = (long)((a.M + 255) / 256) * ((a.N + 255) / 256), tb = (long)((b.M + 255) / 256) * ((b.N + 255) / 256);
-    const long n_cu = dk_device_cu_count();  // (rounds in units of THIS device's CUs; the fractions below were fitted on 256)
-    // ... unless the kernel can cut that extra, small wave along K (remainder-wave split, needs the workspace)
-    const bool split_ok = g_dk_v3_split != 0 && a.workspace != nullptr && (ta + tb) % n_cu <= n_cu / 4 && a.K / 64 >= (g_dk_pair_split_nk >= 0 ? g_dk_pair_split_nk : 24);
-    // (gemm256v4.hip: the same test at ITS tile height -- with 224-row tiles the image + text fc1 of FLUX is 912 + 96 tiles: both 4 rounds)
-    if (dk_gemm256v4_eligible(a) && dk_gemm256v4_eligible(b)) {
-      const int bm4 = 32 * dk_gemm256v4_pick_mf(a, &b, (int)n_cu);
-      const long ta4 = (long)((a.M + bm4 - 1) / bm4) * (a.N / 256), tb4 = (long)((b.M + bm4 - 1) / bm4) * (b.N / 256);
-      if ((ta4 + n_cu - 1) / n_cu == (ta4 + tb4 + n_cu - 1) / n_cu && dk_use_v4(a, &b)) return dk_launch_gemm256v4(a, &b, stream);
-    }
-    if ((ta + n_cu - 1) / n_cu == (ta + tb + n_cu - 1) / n_cu || split_ok) return dk_launch_gemm256v3(a, &b, stream);
-  }
-  int rc = dk_launch_gemm(a, stream);
+// One call: its route, then the launch -- or the calls an expansion is made of.  With `rec` (dk_gemm_plan) every launch is recorded instead:
+// `launches` counts them, the other fields describe the last GEMM launch.
+static int gemm_call(const GemmParams& p_in, const GemmParams* p2_in, hipStream_t stream, dk_gemm_plan_t* rec) {
+  GemmParams p = p_in, p2 = p2_in ? *p2_in : p_in;
+  if (p.ldw <= 0) p.ldw = p.K;
+  if (p2.ldw <= 0) p2.ldw = p2.K;
+  const GemmParams* second = p2_in ? &p2 : nullptr;
+  GemmRoute r;
+  const int rc = dk_gemm_route(p, second, dk_device_cu_count(), r);
   if (rc) return rc;
-  return dk_launch_gemm(b, stream);
+  if (r.kernel == GemmRoute::PAIR) {
+    const int rc1 = gemm_call(p, nullptr, stream, rec);
+    return rc1 ? rc1 : gemm_call(p2, nullptr, stream, rec);
+  }
+  if (r.kernel == GemmRoute::COLUMNS) {
+    GemmParams a = p, b = p;
+    a.N = p.n_split; a.n_split = 0;
+    b.N = p.N - p.n_split; b.n_split = 0; b.W = p.W + (size_t)p.n_split * p.ldw; b.bias = p.bias ? p.bias + p.n_split : nullptr;
+    b.C = p.C2; b.ldc = p.ldc2; b.epi = p.epi2;
+    const int rc1 = gemm_call(a, nullptr, stream, rec);
+    return rc1 ? rc1 : gemm_call(b, nullptr, stream, rec);
+  }
+  if (r.kernel == GemmRoute::KNORM) {
+    GemmParams plain = p;
+    plain.kn_w = nullptr;
+    plain.qn_w = nullptr;
+    const int rc1 = gemm_call(plain, nullptr, stream, rec);
+    if (rc1) return rc1;
+    DK_REQUIRE(p.c_seg_len == p.kn_seg_len || p.c_seg_len >= p.M, "fused key QKNorm: the output's row segments must be the sequences");
+    // (with the query side asked for as well -- qn_w -- the pass covers both column ranges: they hold the same number of heads)
+    DK_REQUIRE(p.qn_w == nullptr || p.qn_col1 - p.qn_col0 == p.kn_col1 - p.kn_col0, "fused QKNorm: query and key ranges must hold the same heads");
+    if (rec) {
+      rec->launches += 1;  // (the stand-alone pass)
+      return 0;
+    }
+    return dk_launch_qk_norm_rope(p.C, p.ldc, p.qn_w ? p.qn_col0 : 0, p.kn_col0, p.M, (p.kn_col1 - p.kn_col0) / p.kn_D, p.kn_D, p.qn_w ? p.qn_w : p.kn_w, p.kn_w,
+                                  p.kn_eps, p.kn_rope, p.kn_seg_len, p.c_seg_len == p.kn_seg_len ? p.c_seg_stride : p.kn_seg_len, p.kn_pos_off, 0,
+                                  stream, p.qn_w ? 0 : 1);
+  }
+  if (rec) {
+    rec->kernel = r.kernel; rec->tile_rows = r.tile_rows; rec->tiles = r.tiles_a + r.tiles_b;
+    rec->workgroups = r.split.n_dp + r.split.n_rem * r.split.S; rec->split_tiles = r.split.n_rem; rec->k_pieces = r.split.S; rec->ks = r.split.ks;
+    rec->n_cu = r.n_cu; rec->launches += 1;
+    return 0;
+  }
+  if (r.kernel == 3) return dk_launch_gemm256v3(p, second, r, stream);
+  if (r.kernel == 4) return dk_launch_gemm256v4(p, second, r, stream);
+  return launch_gemm128(p, r, stream);
+}
+
+int dk_launch_gemm(const GemmParams& p, hipStream_t stream) { return gemm_call(p, nullptr, stream, nullptr); }
+int dk_launch_gemm_pair(const GemmParams& a, const GemmParams& b, hipStream_t stream) { return gemm_call(a, &b, stream, nullptr); }
+int dk_gemm_plan_call(const GemmParams& p, const GemmParams* p2, dk_gemm_plan_t& rec) {
+  rec = dk_gemm_plan_t{};
+  return gemm_call(p, p2, nullptr, &rec);
 }

@@ -73,13 +73,12 @@ __device__ __forceinline__ int f8_xcd_contiguous(int bid, int count) {
 // equal K ranges, piece 0 = [0, ks) is the tile's finisher, pieces 1 .. S-1 share [ks, nk) and are producers (raw fp32 accumulators -> slab, flag).
 // Block order = dispatch order: the finishers first, then the producers; tiles * S <= #CU, so every workgroup is resident and a finisher's wait ends.
 struct F8Split {
-  float* slabs;     // [tiles * (S - 1)][512 threads x 32 accumulator quads] fp32, thread-linear (16 bytes per thread and quad: coalesced)
+  float* slabs;     // [tiles * (S - 1)][512 threads x 32 accumulator quads] fp32, thread-linear (dk_ksplit_store_acc)
   unsigned* flags;  // [tiles * (S - 1)], zero between launches (reset by the finisher)
   unsigned* error_word;
   int S;            // pieces per tile (0 / 1: no split)
   int ks;           // K-tiles of the finisher piece
 };
-#define F8_SLAB_FLOATS (256 * 256)
 
 __global__ __launch_bounds__(512, 2) void dk_gemm256f8_kernel(GemmF8Params pa, GemmF8Params pb, int tiles_a, int tiles_b, F8Split sp) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -373,51 +372,19 @@ __global__ __launch_bounds__(512, 2) void dk_gemm256f8_kernel(GemmF8Params pa, G
 #undef F8_DRAIN
 #undef F8_DRIVE
 
-  // ---------------- K split: producers hand their raw accumulators to the tile's finisher (gemm256v3.hip's protocol: write-through slab stores,
-  // vmcnt(0) in every wave, barrier, one relaxed agent-scope flag store; finisher: relaxed poll, one agent-scope acquire, barrier, plain loads).
+  // ---------------- K split: producers hand their raw accumulators to the tile's finisher (dk_ksplit.h, gemm256v3.hip's Linear form).
   // The MX scales were applied inside the MFMAs, the weight scale and the bias are applied once, by the finisher's tail: partial sums simply add.
   if (piece >= 0) {
     const int n_prod = sp.S - 1;
+    auto leader = [&] { return tid == 0; };
     if (piece >= 1) {
-      float* const slab = sp.slabs + (size_t)(tile * n_prod + piece - 1) * F8_SLAB_FLOATS + (size_t)tid * 4;
-#pragma unroll
-      for (int nf = 0; nf < 4; ++nf)
-#pragma unroll
-        for (int mf = 0; mf < 8; ++mf)
-          asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(slab + (size_t)(nf * 8 + mf) * 2048), "v"(acc[nf][mf]) : "memory");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every wave: its write-through stores have completed
-      __syncthreads();
-      if (tid == 0) __hip_atomic_store(sp.flags + tile * n_prod + piece - 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      dk_ksplit_store_acc<8>(sp.slabs + (size_t)(tile * n_prod + piece - 1) * DK_KSPLIT_SLAB_FLOATS + (size_t)tid * 4, 0u, acc);
+      dk_ksplit_publish(sp.flags, tile, n_prod, piece, leader);
       return;
     }
-    if (tid == 0) {
-      for (int pp = 0; pp < n_prod; ++pp) {
-        unsigned spins = 0;
-        while (__hip_atomic_load(sp.flags + tile * n_prod + pp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
-          __builtin_amdgcn_s_sleep(4);
-          if (++spins > (1u << 24)) {
-            __hip_atomic_store(sp.error_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            break;
-          }
-        }
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    }
-    __syncthreads();
-    for (int pp = 0; pp < n_prod; ++pp) {
-      const float* const slab = sp.slabs + (size_t)(tile * n_prod + pp) * F8_SLAB_FLOATS + (size_t)tid * 4;
-#pragma unroll
-      for (int nf = 0; nf < 4; ++nf)
-#pragma unroll
-        for (int mf = 0; mf < 8; ++mf) {
-          const f32x4 o = *(const f32x4*)(slab + (size_t)(nf * 8 + mf) * 2048);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) acc[nf][mf][e] += o[e];
-        }
-    }
-    __syncthreads();  // every wave has read the slabs
-    if (tid == 0)
-      for (int pp = 0; pp < n_prod; ++pp) __hip_atomic_store(sp.flags + tile * n_prod + pp, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    dk_ksplit_wait(sp.flags, tile, n_prod, sp.error_word, leader);
+    for (int pp = 0; pp < n_prod; ++pp) dk_ksplit_add_acc<8>(acc, sp.slabs + (size_t)(tile * n_prod + pp) * DK_KSPLIT_SLAB_FLOATS + (size_t)tid * 4, 0u);
+    dk_ksplit_release(sp.flags, tile, n_prod, leader);
   }
 
   // ---------------- tail: accumulators -> LDS (wave-private image) -> row-major ----------------
@@ -682,16 +649,7 @@ bool dk_gemm256f8_eligible(const GemmF8Params& p) {
   const bool res2 = p.n_split > 0 && (p.epi2 == DK_EPI_GATE_RES || p.epi2 == DK_EPI_RES);
   if ((res1 || res2) && (p.res == nullptr || p.r_seg_len <= 0 || p.ldr % 8 != 0)) return false;
   if ((p.epi == DK_EPI_GATE_RES || (p.n_split > 0 && p.epi2 == DK_EPI_GATE_RES)) && (p.gate == nullptr || p.gate_seg_len <= 0)) return false;
-  if (p.kn_w != nullptr) {  // fused key QKNorm + RoPE: whole 256-column tiles of 128- or 64-column heads, bias-only bf16 first output
-    if (p.epi != DK_EPI_BIAS || p.c_mx8 || (p.kn_D != 128 && p.kn_D != 64) || p.kn_seg_len <= 0 || p.kn_col0 % 256 != 0 || p.kn_col1 % 256 != 0 ||
-        p.kn_col0 >= p.kn_col1 || p.kn_col1 > (p.n_split > 0 ? p.n_split : p.N) || ((uintptr_t)p.kn_w & 15) != 0 || ((uintptr_t)p.kn_rope & 15) != 0)
-      return false;
-    if (p.qn_w != nullptr && (p.qn_col0 % 256 != 0 || p.qn_col1 % 256 != 0 || p.qn_col0 >= p.qn_col1 || p.qn_col1 > (p.n_split > 0 ? p.n_split : p.N) ||
-                              (p.qn_col0 < p.kn_col1 && p.kn_col0 < p.qn_col1) || ((uintptr_t)p.qn_w & 15) != 0))
-      return false;
-  } else if (p.qn_w != nullptr) {
-    return false;  // the query side rides on the key side's machinery
-  }
+  if ((p.kn_w != nullptr && p.c_mx8) || !dk_qknorm_eligible(p)) return false;  // (the fused QKNorm writes a bf16 first output)
   // outputs: bf16 rows of 16-byte stores, or MX-fp8 rows of 8-byte stores with the scale side array
   auto al = [](const void* q, int a) { return ((uintptr_t)q & (uintptr_t)(a - 1)) == 0; };
   if (p.c_mx8 ? (p.ldc % 8 != 0 || !al(p.C, 8)) : (p.ldc % 8 != 0 || !al(p.C, 16))) return false;
@@ -721,26 +679,18 @@ int dk_launch_gemm256f8(const GemmF8Params& p, const GemmF8Params* p2, hipStream
   }
   const int tiles_a = ((p.M + T256 - 1) / T256) * (p.N / T256);
   const int tiles_b = p2 ? ((p2->M + T256 - 1) / T256) * (p2->N / T256) : 0;
-  // K split (round 6): a launch of at most half a round of tiles whose reduction is long enough -- the bf16 rule (gemm256v3.hip: plan_split, measured
-  // break-even around 32 saved K-tile steps; an fp8 K-tile of 128 elements takes as long as a bf16 one of 64) -- FLUX's fc2 / linear2 below 1024 x 1024.
-  // Never with the fused key QKNorm (a cut tile's finisher has no second pass over its row sums) and never without the caller's workspace.
+  // K split (round 6): the bf16 rule (dk_plan_split; an fp8 K-tile of 128 elements takes as long as a bf16 one of 64) on a launch of at most half a
+  // round of tiles, where it cuts every tile -- FLUX's fc2 / linear2 below 1024 x 1024.  (This kernel has no remainder mode, n_dp == 0: its finishers
+  // come first and every workgroup is resident.)
   F8Split sp;
   memset(&sp, 0, sizeof(sp));
-  {
-    const int n_cu = dk_device_cu_count(), G = n_cu & ~7, tiles = tiles_a + tiles_b, nk = p.K / BKB;
-    const bool have_ws = p.workspace != nullptr && p.workspace_bytes >= dk_gemm_split_workspace_bytes() && ((uintptr_t)p.workspace & 255) == 0 &&
-                         p.kn_w == nullptr && (p2 == nullptr || p2->kn_w == nullptr);
-    if (have_ws && g_dk_v3_split != 0 && tiles > 0 && tiles * 2 <= G) {
-      const int S = G / tiles < 4 ? G / tiles : 4;
-      const int ks = (nk + S - 1) / S;
-      const int min_saved = g_dk_v3_split > 0 ? 1 : (g_dk_v3_split_min >= 0 ? g_dk_v3_split_min : 32);
-      if (S >= 2 && nk - ks >= S - 1 && nk - ks >= min_saved && tiles * (S - 1) <= 256) {
-        sp.S = S; sp.ks = ks;
-        sp.slabs = (float*)p.workspace;
-        sp.flags = (unsigned*)((char*)p.workspace + (size_t)256 * F8_SLAB_FLOATS * 4);
-        sp.error_word = sp.flags + 512;
-      }
-    }
+  const int n_cu = dk_device_cu_count(), tiles = tiles_a + tiles_b;
+  const SplitPlan pl = dk_plan_split(tiles, p.K / BKB, dk_ksplit_ws_ok(p, p2), n_cu, true);
+  if (tiles * 2 <= (n_cu & ~7) && pl.n_rem > 0) {
+    sp.S = pl.S; sp.ks = pl.ks;
+    sp.slabs = (float*)p.workspace;
+    sp.flags = (unsigned*)((char*)p.workspace + DK_KSPLIT_FLAGS_OFF);
+    sp.error_word = sp.flags + DK_KSPLIT_ERROR_WORD;
   }
   const int grid = (tiles_a + tiles_b) * (sp.S > 1 ? sp.S : 1);
   double work = 2.0 * (double)p.M * (double)p.N * (double)p.K;

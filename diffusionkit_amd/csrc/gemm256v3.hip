@@ -26,12 +26,12 @@
 //
 // Tail: accumulators -> wave-private LDS image (fp32, XOR-swizzled) -> row-major read-back, 8 columns per lane, one
 // 16-byte store per lane and row; bias / GELU (erfc polynomial) / SiLU / gate * x + residual on the way.
-// Remainder waves can be cut along K (SplitArgs, plan_split): finisher + producer pieces through fp32 slabs.
+// Remainder waves can be cut along K (SplitArgs, dk_plan_split): finisher + producer pieces through fp32 slabs (dk_ksplit.h).
 //
 // Tile height: template parameter MF = 16-row fragments per wave along m, 8 (256-row tiles) or 7 (224-row tiles).  The hot
 // shapes have M = 4352 / 4608 / 8192 rows and N / 256 = 12 .. 48 column tiles: with 256-row tiles the last round of the 256 CUs is
 // 20 % empty (N = 3072: 204 tiles, one round), with 224-row tiles the same work is 240 / 252 tiles of 7/8 the size -- one round
-// of 0.875 tile-times instead of 1.0.  The launcher takes the height that minimises rounds x height (dk_tune_set
+// of 0.875 tile-times instead of 1.0.  The route (dk_gemm_route) takes the height that minimises rounds x height (dk_tune_set
 // ("gemm_mf", 7 | 8) forces one).  The LDS image keeps its two 128-row A slots; a 224-row tile uses 112 rows of each.
 //
 // C / D layout of the swapped-operand MFMA (A-operand = W fragment, B-operand = activation fragment):
@@ -80,14 +80,14 @@ typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
 typedef __attribute__((address_space(3))) char lds_char;
 
-// Remainder split (dk_launch_gemm256v3): the tiles beyond the last full wave of the CUs -- n_rem < #CU of them --
+// Remainder split (SplitPlan, dk_plan_split in gemm.hip): the tiles beyond the last full wave of the CUs -- n_rem < #CU of them --
 // are cut along K into S pieces with the SAME cut points for every tile (so that the workgroups that run at the
 // same time still walk K in step and share A / W panels in L2): piece 0 = [0, ks) is the tile's finisher, pieces
-// 1 .. S-1 share [ks, nk) and are producers (fp32 partial tile -> slab, flag).  Block order = dispatch order:
+// 1 .. S-1 share [ks, nk) and are producers (partial tile -> slab, flag; dk_ksplit.h).  Block order = dispatch order:
 // full tiles, then the n_rem finishers, then the producers; a finisher only waits at its very end, and at least
 // #CU - n_rem CUs are never held by finishers, so producers always get to run.
 struct SplitArgs {
-  float* slabs;     // [n_rem * (S - 1)][256 * 256] fp32 row-major tile images
+  float* slabs;     // [n_rem * (S - 1)][256 * 256] fp32: raw accumulators (Linears) / row-major tile images (convolutions)
   unsigned* flags;  // [n_rem * (S - 1)], zero between launches (reset by the finisher)
   unsigned* error_word;
   int n_dp;         // full tiles (multiple of 8); 0 <= n_dp <= tiles
@@ -95,12 +95,6 @@ struct SplitArgs {
   int S;            // pieces per split tile
   int ks;           // K-tiles of the finisher piece
 };
-#define SLAB_FLOATS (256 * 256)
-
-// 16-byte write-through (sc1) store: the slab reaches memory without an agent-scope release fence
-__device__ __forceinline__ void v3_store_sc1_b128(float* ptr, f32x4 v) {
-  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(ptr), "v"(v) : "memory");
-}
 
 // position of block `bid` inside the XCD-contiguous order of the `count` blocks that start at block `base`
 // (hardware places block b on XCD b & 7): neighbouring positions share an XCD, hence an L2
@@ -496,33 +490,15 @@ __global__ __launch_bounds__(512, 2) void dk_gemm256v3_kernel(GemmParams pa, Gem
     int lane_x;
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_x));
     const unsigned toff = (unsigned)(wave * 64 + lane_x) * 4u;  // floats
+    auto leader = [wave, lane_x] { return wave == 0 && lane_x == 0; };
     if (piece >= 1) {
-      float* const slab = sp.slabs + (size_t)(rt * n_prod_x + piece - 1) * SLAB_FLOATS;  // (uniform base: scalar registers)
-#pragma unroll
-      for (int nf = 0; nf < 4; ++nf)
-#pragma unroll
-        for (int mf = 0; mf < MF; ++mf) v3_store_sc1_b128(slab + (size_t)(nf * 8 + mf) * 2048 + toff, acc[nf][mf]);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every wave: its write-through stores have completed
-      __syncthreads();
-      if (wave == 0 && lane_x == 0) __hip_atomic_store(sp.flags + rt * n_prod_x + piece - 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      dk_ksplit_store_acc<MF>(sp.slabs + (size_t)(rt * n_prod_x + piece - 1) * DK_KSPLIT_SLAB_FLOATS, toff, acc);  // (uniform base: scalar registers)
+      dk_ksplit_publish(sp.flags, rt, n_prod_x, piece, leader);
       return;
     }
-    if (wave == 0 && lane_x == 0) {
-      for (int pp = 0; pp < n_prod_x; ++pp) {
-        unsigned spins = 0;
-        while (__hip_atomic_load(sp.flags + rt * n_prod_x + pp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
-          __builtin_amdgcn_s_sleep(4);
-          if (++spins > (1u << 24)) {
-            __hip_atomic_store(sp.error_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            break;
-          }
-        }
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    }
-    __syncthreads();
+    dk_ksplit_wait(sp.flags, rt, n_prod_x, sp.error_word, leader);
     for (int pp = 0; pp < n_prod_x; ++pp) {
-      const float* const slab = sp.slabs + (size_t)(rt * n_prod_x + pp) * SLAB_FLOATS;
+      const float* const slab = sp.slabs + (size_t)(rt * n_prod_x + pp) * DK_KSPLIT_SLAB_FLOATS;
 #pragma unroll
       for (int nf = 0; nf < 4; ++nf)
 #pragma unroll
@@ -532,9 +508,7 @@ __global__ __launch_bounds__(512, 2) void dk_gemm256v3_kernel(GemmParams pa, Gem
           for (int e = 0; e < 4; ++e) acc[nf][mf][e] += o[e];
         }
     }
-    __syncthreads();  // every wave has read the slabs
-    if (wave == 0 && lane_x == 0)
-      for (int pp = 0; pp < n_prod_x; ++pp) __hip_atomic_store(sp.flags + rt * n_prod_x + pp, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    dk_ksplit_release(sp.flags, rt, n_prod_x, leader);
     piece = -1;  // from here on the finisher is a whole tile
   }
   if (!CONV) __builtin_assume(piece < 0);  // (no Linear tile reaches the fp32-image tail path below any more; convolutions still do)
@@ -562,27 +536,12 @@ __global__ __launch_bounds__(512, 2) void dk_gemm256v3_kernel(GemmParams pa, Gem
   // (16 rows x one chunk per 16 lanes) and for these reads (4 rows x 4 even / odd chunks per 16 lanes).
   const int rrow = lane >> 2, rc2 = (lane & 3) * 2;
 
-  // split tile: a producer stores its fp32 partial tile to its slab; the finisher first waits for every producer of
-  // the tile (hand-off per guide G16: write-through slab stores, vmcnt(0) in every wave, barrier, one relaxed
-  // agent-scope flag store; consumer: relaxed poll, one agent-scope acquire, barrier, plain loads)
+  // split tile (convolutions): a producer stores its fp32 partial tile image to its slab; the finisher first waits for every producer of
+  // the tile (dk_ksplit.h)
   const int n_prod = sp.S - 1;
-  float* const my_slab = piece >= 1 ? sp.slabs + (size_t)(rt * n_prod + piece - 1) * SLAB_FLOATS : nullptr;
-  if (piece == 0 && !(DK_V3_ABL & 16)) {
-    if (tid == 0) {
-      for (int pp = 0; pp < n_prod; ++pp) {
-        unsigned spins = 0;
-        while (__hip_atomic_load(sp.flags + rt * n_prod + pp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
-          __builtin_amdgcn_s_sleep(4);
-          if (++spins > (1u << 24)) {
-            __hip_atomic_store(sp.error_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            break;
-          }
-        }
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    }
-    __syncthreads();
-  }
+  float* const my_slab = piece >= 1 ? sp.slabs + (size_t)(rt * n_prod + piece - 1) * DK_KSPLIT_SLAB_FLOATS : nullptr;
+  auto leader = [&] { return tid == 0; };
+  if (piece == 0 && !(DK_V3_ABL & 16)) dk_ksplit_wait(sp.flags, rt, n_prod, sp.error_word, leader);
 
   auto unpack8 = [](const uint4 v, float* f) {
     unpack2bf(v.x, f[0], f[1]);
@@ -748,13 +707,13 @@ __global__ __launch_bounds__(512, 2) void dk_gemm256v3_kernel(GemmParams pa, Gem
           const size_t slab_idx = (size_t)(wm * HROWS + row) * 256 + wn * 64 + ni * 32 + rc2 * 4;
           if (piece >= 1) {
             if (!(DK_V3_ABL & 8)) {  // (lab: 8 = producers do not store)
-              v3_store_sc1_b128(my_slab + slab_idx, a0);
-              v3_store_sc1_b128(my_slab + slab_idx + 4, a1);
+              dk_ksplit_store_b128(my_slab + slab_idx, a0);
+              dk_ksplit_store_b128(my_slab + slab_idx + 4, a1);
             }
             continue;
           }
           for (int pp = 0; pp < ((DK_V3_ABL & 16) ? 0 : n_prod); ++pp) {  // (lab: 16 = finishers neither wait nor read)
-            const float* sl = sp.slabs + (size_t)(rt * n_prod + pp) * SLAB_FLOATS + slab_idx;
+            const float* sl = sp.slabs + (size_t)(rt * n_prod + pp) * DK_KSPLIT_SLAB_FLOATS + slab_idx;
             const f32x4 o0 = *(const f32x4*)sl, o1 = *(const f32x4*)(sl + 4);
 #pragma unroll
             for (int e = 0; e < 4; ++e) a0[e] += o0[e], a1[e] += o1[e];
@@ -866,15 +825,10 @@ __global__ __launch_bounds__(512, 2) void dk_gemm256v3_kernel(GemmParams pa, Gem
       tail_pass(std::integral_constant<int, 1>{}, std::true_type{}, std::true_type{});
     }
   }
-  if (piece >= 1) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every wave: its write-through stores have completed
-    __syncthreads();
-    if (tid == 0) __hip_atomic_store(sp.flags + rt * n_prod + piece - 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  } else if (piece == 0) {
-    __syncthreads();  // every wave has read the slabs
-    if (tid == 0)
-      for (int pp = 0; pp < n_prod; ++pp) __hip_atomic_store(sp.flags + rt * n_prod + pp, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  if (piece >= 1)
+    dk_ksplit_publish(sp.flags, rt, n_prod, piece, leader);
+  else if (piece == 0)
+    dk_ksplit_release(sp.flags, rt, n_prod, leader);
 }
 
 bool dk_gemm256v3_eligible(const GemmParams& p) {
@@ -891,16 +845,7 @@ bool dk_gemm256v3_eligible(const GemmParams& p) {
   const bool res2 = p.n_split > 0 && (p.epi2 == DK_EPI_GATE_RES || p.epi2 == DK_EPI_RES);
   if ((res1 || res2) && (p.res == nullptr || p.r_seg_len <= 0 || p.ldr % 8 != 0)) return false;
   if ((p.epi == DK_EPI_GATE_RES || (p.n_split > 0 && p.epi2 == DK_EPI_GATE_RES)) && (p.gate == nullptr || p.gate_seg_len <= 0)) return false;
-  if (p.kn_w != nullptr) {  // fused key QKNorm + RoPE: whole 256-column tiles of 128- or 64-column heads, bias-only first output
-    if (p.conv || p.epi != DK_EPI_BIAS || (p.kn_D != 128 && p.kn_D != 64) || p.kn_seg_len <= 0 || p.kn_col0 % 256 != 0 || p.kn_col1 % 256 != 0 || p.kn_col0 >= p.kn_col1 ||
-        p.kn_col1 > (p.n_split > 0 ? p.n_split : p.N) || ((uintptr_t)p.kn_w & 15) != 0 || ((uintptr_t)p.kn_rope & 15) != 0)
-      return false;
-    if (p.qn_w != nullptr && (p.qn_col0 % 256 != 0 || p.qn_col1 % 256 != 0 || p.qn_col0 >= p.qn_col1 || p.qn_col1 > (p.n_split > 0 ? p.n_split : p.N) ||
-                              (p.qn_col0 < p.kn_col1 && p.kn_col0 < p.qn_col1) || ((uintptr_t)p.qn_w & 15) != 0))
-      return false;
-  } else if (p.qn_w != nullptr) {
-    return false;  // the query side rides on the key side's machinery
-  }
+  if ((p.kn_w != nullptr && p.conv) || !dk_qknorm_eligible(p)) return false;
   // 16-byte accesses in the tail
   auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
   if (!al16(p.C) || !al16(p.C2) || !al16(p.res) || !al16(p.bias) || !al16(p.gate) || (p.gate != nullptr && p.gate_stride % 8 != 0)) return false;
@@ -909,118 +854,11 @@ bool dk_gemm256v3_eligible(const GemmParams& p) {
   return (p.conv || a_rows * (size_t)p.lda * 2 < (1ull << 32)) && (size_t)p.ldw * 2 * 8 < (1ull << 31);
 }
 
-// dk_tune_set("gemm_split", v): -1 (default) split a remainder wave of at most half the CUs into equal pieces when the
-// cost model below says it pays, 0 never, 1 whenever possible.  Kernel lab (profiles/archive/r01_gemm_lab.md): every workgroup
-// carries ~18 us of fixed cost (launch, first DMA, tail) and a CU runs its K-tiles ~20 % slower when all 256 CUs are busy
-// than when 192 are, so a remainder of MORE than half the CUs (finisher + several producer pieces in turn on the
-// spare CUs) loses on every shape but the longest-K one and is only taken when forced.
-int g_dk_v3_split = -1;
-int g_dk_v3_split_min = -1;  // dk_tune_set("gemm_split_min", v): saved K-tile steps below which a Linear that is ALL remainder stays whole; -1: 32 (see plan_split)
+size_t dk_gemm_split_workspace_bytes() { return DK_KSPLIT_WS_BYTES; }
 
-// 256 fp32 tile images + 4 KiB of flags (and the error word)
-size_t dk_gemm_split_workspace_bytes() { return (size_t)256 * SLAB_FLOATS * 4 + 4096; }
-
-// How the tiles beyond the last full wave of the CUs are cut along K (see SplitArgs).  n_rem == 0: no split.
-struct SplitPlan {
-  int n_dp, n_rem, S, ks;
-};
-static SplitPlan plan_split(int tiles, int nk, bool have_ws, int n_cu, bool linear = false) {
-  SplitPlan none{tiles, 0, 1, nk};
-  if (!have_ws || g_dk_v3_split == 0 || n_cu < 16) return none;
-  const int G = n_cu & ~7;
-  const int T = tiles % G;
-  if (T == 0) return none;
-  const int E = G - T;
-  int S, ks, t_steps;  // t_steps: K-tile steps until the split wave is done
-  if (T > G / 2) {  // one producer piece per tile, c = ceil(T / E) of them in turn on each of the E spare CUs
-    if (g_dk_v3_split < 0) return none;
-    S = 2;
-    const int c = (T + E - 1) / E;
-    ks = (nk * c + c) / (c + 1);  // ~ nk * c / (c + 1), rounded up: the finishers must not end before the producers
-    if (ks > nk - 1) ks = nk - 1;
-    t_steps = ks > c * (nk - ks) ? ks : c * (nk - ks);
-  } else {  // S equal pieces per tile, one CU each
-    S = G / T < 4 ? G / T : 4;
-    ks = (nk + S - 1) / S;
-    t_steps = ks;
-  }
-  if (S < 2 || ks < 1 || nk - ks < S - 1 || T * (S - 1) > 256) return none;
-  // a K-tile step costs about 1.45 us; splitting costs a slab write + read and a flag round trip per tile
-  if (g_dk_v3_split < 0 && (nk - t_steps) * 1.45 < 25.0) return none;
-  // a Linear that is ALL remainder (round 6: FLUX / SD3 below 1024 x 1024, 60 - 120 tiles): every tile pays S - 1 slab round trips at once, and the few
-  // busy CUs run their K-tiles in ~1 us.  Measured (profiles/r06_gemm_small_m.log, r06_res_sweep.md): with the fp32-image exchange of rounds 1-5 FLUX's o_proj at
-  // 512 x 512 (K = 3072, four ranges: 36 steps saved) lost 16 us with the split and fc2 / linear2 (144 / 180 saved) gained 60 - 90; with the raw-accumulator
-  // exchange (above, round 6) the in-model sweep is flat from 0 to 48 saved steps and 1 % better at 24 - 36 than at 48: the rule cuts from 32
-  if (g_dk_v3_split < 0 && linear && tiles < G && nk - t_steps < (g_dk_v3_split_min >= 0 ? g_dk_v3_split_min : 32)) return none;
-  return SplitPlan{tiles - T, T, S, ks};
-}
-
-// dk_tune_set("gemm_mf", v): wave-tile height in 16-row fragments; -1 (default) = the height with the fewest rounds x height, 8 / 7 forced
-int g_dk_v3_mf = -1;
-
-// Tile height for a launch.  Model: rounds of the CUs x rows per tile, over both problems of a grouped launch (same N).  Measured
-// (profiles/r02_gemm_tile_height.log): on the FLUX shapes 224-row tiles save 2.7 % of the GEMM time -- far less than the 12.5 %
-// the model promises, because a K-tile runs slower the more CUs are busy (the chip is power / fabric bound) -- and on
-// the short-K SD3 shapes the 15 % extra tiles (each with its fixed prologue + tail) cost more than the fuller round gives back.
-// So: 224-row tiles only for long reductions, and only when the model predicts at least 10 %.
-static long v3_tiles(const GemmParams& p, const GemmParams* p2, int bm) {
-  long tiles = (long)((p.M + bm - 1) / bm) * ((p.N + T256 - 1) / T256);
-  if (p2) tiles += (long)((p2->M + bm - 1) / bm) * ((p2->N + T256 - 1) / T256);
-  return tiles;
-}
-static bool v3_have_ws(const GemmParams& p, const GemmParams* p2) {
-  // (a launch with the fused key QKNorm is never split: a split tile's finisher has no second pass over its row sums)
-  return p.workspace != nullptr && p.workspace_bytes >= dk_gemm_split_workspace_bytes() && ((uintptr_t)p.workspace & 255) == 0 &&
-         p.kn_w == nullptr && (p2 == nullptr || p2->kn_w == nullptr);
-}
-static int pick_mf(const GemmParams& p, const GemmParams* p2, int n_cu, bool have_ws) {
-  if (g_dk_v3_mf == 7 || g_dk_v3_mf == 8) return g_dk_v3_mf;
-  if (p.K < 2048) return 8;
-  // Small launches (round 6; the reference CLI's 512 x 512 default: FLUX's o_proj / fc2 / linear2 are 60 - 84 tiles for 256 CUs): when both
-  // heights leave at least half the CUs idle the launch is one split "remainder", and what a CU runs is the finisher piece: ks K-tiles of bm rows
-  const long t7 = v3_tiles(p, p2, 224), t8 = v3_tiles(p, p2, 256);
-  if (have_ws && !p.conv && (t7 < t8 ? t7 : t8) * 2 <= n_cu && t7 <= n_cu && t8 <= n_cu) {
-    const int nk = p.K / BK;
-    const SplitPlan s7 = plan_split((int)t7, nk, true, n_cu, true), s8 = plan_split((int)t8, nk, true, n_cu, true);
-    if (s7.n_rem > 0 || s8.n_rem > 0) return 224L * (s7.n_rem > 0 ? s7.ks : nk) < 256L * (s8.n_rem > 0 ? s8.ks : nk) ? 7 : 8;
-  }
-  long cost[2];
-  for (int mf = 7; mf <= 8; ++mf) {
-    const int bm = 32 * mf;
-    cost[mf - 7] = ((v3_tiles(p, p2, bm) + n_cu - 1) / n_cu) * bm;
-  }
-  return cost[0] * 10 <= cost[1] * 9 ? 7 : 8;
-}
-
-// The whole launch is at most half a round of the CUs and this kernel would cut every tile along K (dk_use_v4 in gemm.hip leaves such
-// launches here: the one-wave-per-SIMD kernel has no K split, and 60 tiles on 256 CUs waste three quarters of the chip)
-bool dk_gemm256v3_splits_whole_launch(const GemmParams& p, const GemmParams* p2) {
-  if (p.conv || !dk_gemm256v3_eligible(p) || (p2 != nullptr && !dk_gemm256v3_eligible(*p2))) return false;
-  const int n_cu = dk_device_cu_count();
-  const bool have_ws = v3_have_ws(p, p2);
-  const int bm = 32 * pick_mf(p, p2, n_cu, have_ws);
-  const long tiles = v3_tiles(p, p2, bm);
-  if (tiles * 2 > n_cu) return false;
-  const SplitPlan pl = plan_split((int)tiles, p.K / BK, have_ws, n_cu, true);
-  return pl.n_rem > 0 && pl.n_dp == 0;
-}
-
-// `p2` null: one problem.  (tiles_a / tiles_b of older callers are recomputed here: they depend on the tile height)
-int dk_launch_gemm256v3_raw(const GemmParams& p, const GemmParams& pb, int /*tiles_a*/, int tiles_b_in, hipStream_t stream) {
-  const int n_cu = dk_device_cu_count();
-  const bool two = tiles_b_in > 0;
-  const bool have_ws = v3_have_ws(p, two ? &pb : nullptr);
-  const int mf = pick_mf(p, two ? &pb : nullptr, n_cu, have_ws);
-  const int bm = 32 * mf;
-  const int tiles_a = ((p.M + bm - 1) / bm) * ((p.N + T256 - 1) / T256);
-  const int tiles_b = two ? ((pb.M + bm - 1) / bm) * ((pb.N + T256 - 1) / T256) : 0;
-  const SplitPlan pl = plan_split(tiles_a + tiles_b, p.K / BK, have_ws, n_cu, !p.conv);
-  if (g_dk_gemm_plan != nullptr) {
-    DkGemmPlan& gp = *g_dk_gemm_plan;
-    gp.kernel = 3; gp.tile_rows = bm; gp.tiles = tiles_a + tiles_b; gp.workgroups = pl.n_dp + pl.n_rem * pl.S; gp.split_tiles = pl.n_rem;
-    gp.k_pieces = pl.n_rem > 0 ? pl.S : 1; gp.ks = pl.n_rem > 0 ? pl.ks : p.K / BK; gp.n_cu = n_cu; gp.launches += 1;
-    return 0;
-  }
+// tile-parallel launch of `p` and, optionally, a second problem `p2` with the same N, K, alpha and epilogue: tile height, tiles and K split
+// as routed (dk_gemm_route)
+int dk_launch_gemm256v3(const GemmParams& p, const GemmParams* p2, const GemmRoute& r, hipStream_t stream) {
   static DkDeviceOnce attr_once;
   if (attr_once.first()) {
     DK_CHECK_HIP(hipFuncSetAttribute((const void*)dk_gemm256v3_kernel<8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
@@ -1031,41 +869,27 @@ int dk_launch_gemm256v3_raw(const GemmParams& p, const GemmParams& pb, int /*til
   }
   SplitArgs sp;
   memset(&sp, 0, sizeof(sp));
-  sp.n_dp = pl.n_dp; sp.n_rem = pl.n_rem; sp.S = pl.S; sp.ks = pl.ks;
-  if (pl.n_rem > 0) {
+  sp.n_dp = r.split.n_dp; sp.n_rem = r.split.n_rem; sp.S = r.split.S; sp.ks = r.split.ks;
+  if (r.split.n_rem > 0) {
     sp.slabs = (float*)p.workspace;
-    sp.flags = (unsigned*)((char*)p.workspace + (size_t)256 * SLAB_FLOATS * 4);
-    sp.error_word = sp.flags + 512;
+    sp.flags = (unsigned*)((char*)p.workspace + DK_KSPLIT_FLAGS_OFF);
+    sp.error_word = sp.flags + DK_KSPLIT_ERROR_WORD;
   }
-  const int grid = pl.n_dp + pl.n_rem * pl.S;
-  if (p.conv) {
-    if (mf == 8)
-      hipLaunchKernelGGL((dk_gemm256v3_kernel<8, true>), dim3(grid), dim3(512), LDS_BYTES, stream, p, pb, tiles_a, tiles_b, sp);
-    else
-      hipLaunchKernelGGL((dk_gemm256v3_kernel<7, true>), dim3(grid), dim3(512), LDS_BYTES, stream, p, pb, tiles_a, tiles_b, sp);
-  } else if (mf == 8)
-    hipLaunchKernelGGL((dk_gemm256v3_kernel<8, false>), dim3(grid), dim3(512), LDS_BYTES, stream, p, pb, tiles_a, tiles_b, sp);
-  else
-    hipLaunchKernelGGL((dk_gemm256v3_kernel<7, false>), dim3(grid), dim3(512), LDS_BYTES, stream, p, pb, tiles_a, tiles_b, sp);
-  return 0;
-}
-
-// tile-parallel launch of `p` and, optionally, a second problem `p2` with the same N, K, alpha and epilogue
-int dk_launch_gemm256v3(const GemmParams& p, const GemmParams* p2, hipStream_t stream) {
-  DK_REQUIRE(dk_gemm256v3_eligible(p), "gemm256v3: shape / strides not eligible");
-  if (p2) {
-    DK_REQUIRE(!p.conv && !p2->conv, "gemm256v3: no grouped convolutions");
-    DK_REQUIRE(dk_gemm256v3_eligible(*p2), "gemm256v3: second problem not eligible");
-    DK_REQUIRE(p2->N == p.N && p2->K == p.K && p2->epi == p.epi && p2->alpha == p.alpha && p2->n_split == p.n_split &&
-                   (p.n_split == 0 || p2->epi2 == p.epi2),
-               "grouped GEMM: N, K, epilogue must match");
-  }
+  const GemmParams& pb = p2 ? *p2 : p;
+  const int grid = r.split.n_dp + r.split.n_rem * r.split.S;
   double work = 2.0 * (double)p.M * (double)p.N * (double)p.K;
   if (p2) work += 2.0 * (double)p2->M * (double)p2->N * (double)p2->K;
-  if (g_dk_gemm_plan != nullptr) return dk_launch_gemm256v3_raw(p, p2 ? *p2 : p, 0, p2 ? 1 : 0, stream);  // (plan mode: no device call)
   dk_prof_begin(p.conv ? 1 : 0, work, stream);
-  const int rc = dk_launch_gemm256v3_raw(p, p2 ? *p2 : p, 0, p2 ? 1 : 0, stream);
+  if (p.conv) {
+    if (r.tile_rows == 256)
+      hipLaunchKernelGGL((dk_gemm256v3_kernel<8, true>), dim3(grid), dim3(512), LDS_BYTES, stream, p, pb, r.tiles_a, r.tiles_b, sp);
+    else
+      hipLaunchKernelGGL((dk_gemm256v3_kernel<7, true>), dim3(grid), dim3(512), LDS_BYTES, stream, p, pb, r.tiles_a, r.tiles_b, sp);
+  } else if (r.tile_rows == 256)
+    hipLaunchKernelGGL((dk_gemm256v3_kernel<8, false>), dim3(grid), dim3(512), LDS_BYTES, stream, p, pb, r.tiles_a, r.tiles_b, sp);
+  else
+    hipLaunchKernelGGL((dk_gemm256v3_kernel<7, false>), dim3(grid), dim3(512), LDS_BYTES, stream, p, pb, r.tiles_a, r.tiles_b, sp);
   dk_prof_end(stream);
   DK_CHECK_HIP(hipGetLastError());
-  return rc;
+  return 0;
 }

@@ -432,33 +432,9 @@ __global__ __launch_bounds__(256, 1) void dk_gemm256v4_kernel(GemmParams pa, Gem
 #endif
 }
 
-// Tile height of a launch: gemm256v3.hip's rule (rounds of the CUs x rows per tile over both problems; 224-row tiles only for long reductions and
-// only when the model predicts at least 10 %; dk_tune_set("gemm_mf", 7 | 8) forces one)
-// every row tile of height bm lies inside one segment of every row map (tile-uniform tail paths: FAST, or CUT for the last one)
-bool dk_gemm256v4_uniform_tiles(const GemmParams& p, int bm) {
-  auto ok = [&](int len) { return len >= p.M || len % bm == 0; };
-  const bool res = p.epi == DK_EPI_GATE_RES || p.epi == DK_EPI_RES || (p.n_split > 0 && (p.epi2 == DK_EPI_GATE_RES || p.epi2 == DK_EPI_RES));
-  const bool gate = p.epi == DK_EPI_GATE_RES || (p.n_split > 0 && p.epi2 == DK_EPI_GATE_RES);
-  return ok(p.a_seg_len) && ok(p.c_seg_len) && (!res || ok(p.r_seg_len)) && (!gate || ok(p.gate_seg_len)) && (p.kn_w == nullptr || ok(p.kn_seg_len));
-}
-
-int dk_gemm256v4_pick_mf(const GemmParams& p, const GemmParams* p2, int n_cu) {
-  if (g_dk_v3_mf == 7 || g_dk_v3_mf == 8) return g_dk_v3_mf;
-  if (p.K < 2048) return 8;
-  if (!dk_gemm256v4_uniform_tiles(p, 224) || (p2 && !dk_gemm256v4_uniform_tiles(*p2, 224))) return 8;  // (the per-row tail path is slow here)
-  long cost[2];
-  for (int mf = 7; mf <= 8; ++mf) {
-    const int bm = 32 * mf;
-    long tiles = (long)((p.M + bm - 1) / bm) * (p.N / 256);
-    if (p2) tiles += (long)((p2->M + bm - 1) / bm) * (p2->N / 256);
-    cost[mf - 7] = ((tiles + n_cu - 1) / n_cu) * bm;
-  }
-  return cost[0] * 10 <= cost[1] * 9 ? 7 : 8;
-}
-
 int g_dk_v4_skew = -1;  // dk_tune_set("gemm_skew", v): start skew of multi-round launches in 0.25 us steps; -1 (default): none
 
-// dk_tune_set("gemm", 10) forces this kernel on every shape it accepts; -1 (automatic): see dk_launch_gemm / dk_launch_gemm_pair
+// dk_tune_set("gemm", 10) forces this kernel on every shape it accepts; -1 (automatic): see dk_gemm_route (gemm.hip)
 bool dk_gemm256v4_eligible(const GemmParams& p) {
   if (p.conv || !dk_gemm256v3_eligible(p)) return false;
   if (p.N % 256 != 0) return false;
@@ -466,25 +442,8 @@ bool dk_gemm256v4_eligible(const GemmParams& p) {
   return (size_t)p.ldw * 2 * 256 < (1ull << 31);
 }
 
-int dk_launch_gemm256v4(const GemmParams& p, const GemmParams* p2, hipStream_t stream) {
-  DK_REQUIRE(dk_gemm256v4_eligible(p), "gemm256v4: shape / strides not eligible");
-  if (p2) {
-    DK_REQUIRE(dk_gemm256v4_eligible(*p2), "gemm256v4: second problem not eligible");
-    DK_REQUIRE(p2->N == p.N && p2->K == p.K && p2->epi == p.epi && p2->alpha == p.alpha && p2->n_split == p.n_split &&
-                   (p.n_split == 0 || p2->epi2 == p.epi2),
-               "grouped GEMM: N, K, epilogue must match");
-  }
-  const int n_cu = dk_device_cu_count();
-  const int mf = dk_gemm256v4_pick_mf(p, p2, n_cu);
-  const int bm = 32 * mf;
-  const int tiles_a = ((p.M + bm - 1) / bm) * (p.N / 256);
-  const int tiles_b = p2 ? ((p2->M + bm - 1) / bm) * (p2->N / 256) : 0;
-  if (g_dk_gemm_plan != nullptr) {
-    DkGemmPlan& pl = *g_dk_gemm_plan;
-    pl.kernel = 4; pl.tile_rows = bm; pl.tiles = pl.workgroups = tiles_a + tiles_b; pl.split_tiles = 0; pl.k_pieces = 1; pl.ks = p.K / V4_BK;
-    pl.n_cu = n_cu; pl.launches += 1;
-    return 0;
-  }
+// tile height and tiles as routed (dk_gemm_route: gemm256v3.hip's height rule, 256-row tiles where 224-row ones would straddle a row segment)
+int dk_launch_gemm256v4(const GemmParams& p, const GemmParams* p2, const GemmRoute& r, hipStream_t stream) {
   static DkDeviceOnce attr_once;
   if (attr_once.first()) {
     DK_CHECK_HIP(hipFuncSetAttribute((const void*)dk_gemm256v4_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, V4_LDS_BYTES));
@@ -496,11 +455,12 @@ int dk_launch_gemm256v4(const GemmParams& p, const GemmParams* p2, hipStream_t s
   dk_prof_begin(0, work, stream);
   // ... in the lab with warm weights.  Inside the model (weights from HBM) the start skew is flat: 58.78 / 58.81 against 58.86 / 58.94 ms per FLUX
   // step (profiles/r05_gemm_v4_start_skew.log) -- the automatic choice keeps it off; dk_tune_set("gemm_skew", n) turns it on
-  const int skew = tiles_a + tiles_b <= n_cu || g_dk_v4_skew < 0 ? 0 : g_dk_v4_skew;
-  if (mf == 7)
-    hipLaunchKernelGGL(dk_gemm256v4_kernel<7>, dim3(tiles_a + tiles_b), dim3(256), V4_LDS_BYTES, stream, p, p2 ? *p2 : p, tiles_a, tiles_b, skew);
+  const int tiles = r.tiles_a + r.tiles_b;
+  const int skew = tiles <= r.n_cu || g_dk_v4_skew < 0 ? 0 : g_dk_v4_skew;
+  if (r.tile_rows == 224)
+    hipLaunchKernelGGL(dk_gemm256v4_kernel<7>, dim3(tiles), dim3(256), V4_LDS_BYTES, stream, p, p2 ? *p2 : p, r.tiles_a, r.tiles_b, skew);
   else
-    hipLaunchKernelGGL(dk_gemm256v4_kernel<8>, dim3(tiles_a + tiles_b), dim3(256), V4_LDS_BYTES, stream, p, p2 ? *p2 : p, tiles_a, tiles_b, skew);
+    hipLaunchKernelGGL(dk_gemm256v4_kernel<8>, dim3(tiles), dim3(256), V4_LDS_BYTES, stream, p, p2 ? *p2 : p, r.tiles_a, r.tiles_b, skew);
   dk_prof_end(stream);
   DK_CHECK_HIP(hipGetLastError());
   return 0;

@@ -82,7 +82,9 @@ int dk_gemm_bf16(const dk_gemm_desc* d, void* stream);
 /* What dk_gemm_bf16(d) -- or, with d2 != NULL, the grouped launch the engines issue for the image and text streams of a double block -- WOULD
  * launch on the current device (ABI 5, round 6).  Host only: no kernel runs, pointers in the descriptors are not dereferenced (only their alignment
  * is looked at; `workspace` non-NULL tells the rules that the K split is available), and without a GPU the rules assume 256 compute units.  The
- * decision code is the launch code itself, so tests/test_dispatch_plan.py sweeps shapes over the dispatch rules on the CPU. */
+ * record is read from the same route the launch takes (dk_gemm_route, gemm.hip), so tests/test_dispatch_plan.py sweeps shapes over the dispatch
+ * rules on the CPU.  A call that expands into several launches -- a pair that is not grouped runs as two -- reports their number in `launches`;
+ * the other fields describe the last of them. */
 typedef struct dk_gemm_plan_t {
   int32_t kernel;      /* 128: 128 x 128-tile kernel; 3: 256 x 256 tiles, 8 waves (gemm256v3.hip); 4: one wave per SIMD (gemm256v4.hip) */
   int32_t tile_rows;   /* 128 / 224 / 256 */

@@ -384,7 +384,7 @@ def test_gemm_v3_remainder_split(dev, M, N, K, epi, mf):
                                               (4352, 3072, 12288, "gate_res", False)])  # 1024 x 1024: a full round, untouched
 def test_gemm_small_launch_is_split_automatically(dev, M, N, K, epi, split):
     """Round 6 (the reference CLI's 512 x 512 default, generate_images.py:15-30): a block Linear of at most half a round of 256 x 256 tiles is cut
-    along K by the AUTOMATIC choice (gemm.hip: dk_use_v4 -> gemm256v3.hip's split) when the caller hands in the split workspace, as the engines do.
+    along K by the AUTOMATIC choice (gemm.hip: dk_gemm_route -> gemm256v3.hip's split) when the caller hands in the split workspace, as the engines do.
     Against the fp32 oracle, and against the same launch with the split switched off: bit-identical where the rule leaves the launch whole,
     equal up to the fp32 summation order where it is cut."""
     from diffusionkit_amd import ops
