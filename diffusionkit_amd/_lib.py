@@ -85,6 +85,31 @@ class dk_gemm_fp8_desc(C.Structure):
     ]
 
 
+_FUSED_TAIL = [
+    ("kn_w", C.c_void_p), ("kn_rope", C.c_void_p),
+    ("kn_col0", C.c_int32), ("kn_col1", C.c_int32), ("kn_D", C.c_int32), ("kn_pos_off", C.c_int32), ("kn_seg_len", C.c_int32),
+    ("kn_eps", C.c_float), ("qn_w", C.c_void_p), ("qn_col0", C.c_int32), ("qn_col1", C.c_int32),
+]
+
+
+class dk_gemm_side(C.Structure):
+    _fields_ = [("n_split", C.c_int32), ("C2", C.c_void_p), ("ldc2", C.c_int32), ("epi2", C.c_int32)] + _FUSED_TAIL
+
+
+class dk_gemm_fp8_side(C.Structure):
+    _fields_ = [("n_split", C.c_int32), ("C2", C.c_void_p), ("ldc2", C.c_int32), ("epi2", C.c_int32), ("c2_mx8", C.c_int32)] + _FUSED_TAIL
+
+
+class dk_attention_desc(C.Structure):
+    _fields_ = [
+        ("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("out", C.c_void_p),
+        ("B", C.c_int32), ("H", C.c_int32), ("S", C.c_int32), ("D", C.c_int32), ("ld", C.c_int32), ("ldo", C.c_int32),
+        ("scale", C.c_float), ("bias", C.c_void_p), ("bias_head_stride", C.c_int64), ("ldb", C.c_int32),
+        ("qn_a", C.c_void_p), ("qn_b", C.c_void_p), ("qn_split", C.c_int32), ("qn_eps", C.c_float), ("q_rope", C.c_void_p),
+        ("O8", C.c_void_p), ("O8_scales", C.c_void_p), ("o8_ld", C.c_int32), ("o8_rows", C.c_int64),
+    ]
+
+
 class dk_vae_config(C.Structure):
     _fields_ = [
         ("in_channels", C.c_int32), ("out_channels", C.c_int32), ("block_out_channels", C.c_int32 * 4),
@@ -108,6 +133,12 @@ SIGNATURES = {
     "dk_last_error": (C.c_char_p, []),
     "dk_gemm_bf16": (_i32, [C.POINTER(dk_gemm_desc), _vp]),
     "dk_gemm_plan": (_i32, [C.POINTER(dk_gemm_desc), C.POINTER(dk_gemm_desc), C.POINTER(dk_gemm_plan_t)]),
+    "dk_gemm_fused_bf16": (_i32, [C.POINTER(dk_gemm_desc), C.POINTER(dk_gemm_side), C.POINTER(dk_gemm_desc), C.POINTER(dk_gemm_side), _vp]),
+    "dk_gemm_fused_plan": (_i32, [C.POINTER(dk_gemm_desc), C.POINTER(dk_gemm_side), C.POINTER(dk_gemm_desc), C.POINTER(dk_gemm_side),
+                                  C.POINTER(dk_gemm_plan_t)]),
+    "dk_gemm_fp8_fused": (_i32, [C.POINTER(dk_gemm_fp8_desc), C.POINTER(dk_gemm_fp8_side), C.POINTER(dk_gemm_fp8_desc), C.POINTER(dk_gemm_fp8_side),
+                                 _vp]),
+    "dk_attention_desc_bf16": (_i32, [C.POINTER(dk_attention_desc), _vp]),
     "dk_gemm_workspace_bytes": (C.c_size_t, []),
     "dk_attention_workspace_bytes": (C.c_size_t, []),
     "dk_attention_set_workspace": (C.c_int, [C.c_void_p, C.c_size_t]),

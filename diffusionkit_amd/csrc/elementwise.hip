@@ -232,7 +232,7 @@ int dk_launch_qk_norm_rope(bf16_t* qkv, int ld, int q_off, int k_off, int rows, 
                            const bf16_t* kw, float eps, const float* rope, int row_seg_len, int row_seg_stride, int pos_off,
                            int S_pos, hipStream_t stream, int k_only) {
   (void)S_pos;
-  if (qw == nullptr && rope == nullptr) return 0;
+  if (qw == nullptr && kw == nullptr && rope == nullptr) return 0;  // (a key weight alone is work: dk_qk_norm_rope_bf16 with q_weight NULL, no table)
   QkJob a{qkv, qw, kw, rows, row_seg_len, row_seg_stride, pos_off}, none{nullptr, nullptr, nullptr, 0, 1, 0, 0};
   return launch_qk_jobs(a, none, ld, q_off, k_off, H, D, eps, rope, stream, k_only);
 }
@@ -240,7 +240,7 @@ int dk_launch_qk_norm_rope(bf16_t* qkv, int ld, int q_off, int k_off, int rows, 
 int dk_launch_qk_norm_rope2(bf16_t* qkv0, int rows0, const bf16_t* qw0, const bf16_t* kw0, int seg0, int pos0, bf16_t* qkv1, int rows1,
                             const bf16_t* qw1, const bf16_t* kw1, int seg1, int pos1, int ld, int q_off, int k_off, int H, int D,
                             float eps, const float* rope, int row_seg_stride, hipStream_t stream, int k_only) {
-  if (qw0 == nullptr && rope == nullptr) return 0;
+  if (qw0 == nullptr && kw0 == nullptr && qw1 == nullptr && kw1 == nullptr && rope == nullptr) return 0;
   QkJob a{qkv0, qw0, kw0, rows0, seg0, row_seg_stride, pos0}, b{qkv1, qw1, kw1, rows1, seg1, row_seg_stride, pos1};
   return launch_qk_jobs(a, b, ld, q_off, k_off, H, D, eps, rope, stream, k_only);
 }

@@ -90,6 +90,36 @@ extern "C" int dk_gemm_plan(const dk_gemm_desc* d, const dk_gemm_desc* d2, dk_ge
   return dk_gemm_plan_call(gemm_params_from_desc(d), d2 != nullptr ? &p2 : nullptr, *plan);
 }
 
+// the engine-only fields of GemmParams beside a descriptor (dk_gemm_side / dk_gemm_fp8_side: same names); null: nothing fused
+template <class P, class F>
+static void set_fused(P& p, const F* f) {
+  if (f == nullptr) return;
+  p.n_split = f->n_split; p.C2 = (decltype(p.C2))f->C2; p.ldc2 = f->ldc2; p.epi2 = f->epi2;
+  p.kn_w = (const bf16_t*)f->kn_w; p.kn_rope = f->kn_rope;
+  p.kn_col0 = f->kn_col0; p.kn_col1 = f->kn_col1; p.kn_D = f->kn_D; p.kn_pos_off = f->kn_pos_off; p.kn_seg_len = f->kn_seg_len; p.kn_eps = f->kn_eps;
+  p.qn_w = (const bf16_t*)f->qn_w; p.qn_col0 = f->qn_col0; p.qn_col1 = f->qn_col1;
+}
+
+// (no checks of their own: dk_gemm_route / the *_eligible functions decide what a form launches)
+extern "C" int dk_gemm_fused_bf16(const dk_gemm_desc* d, const dk_gemm_side* f, const dk_gemm_desc* d2, const dk_gemm_side* f2, void* stream) {
+  DK_REQUIRE(d != nullptr && (d2 != nullptr || f2 == nullptr), "null descriptor");
+  GemmParams p = gemm_params_from_desc(d);
+  set_fused(p, f);
+  if (d2 == nullptr) return dk_launch_gemm(p, S_(stream));
+  GemmParams p2 = gemm_params_from_desc(d2);
+  set_fused(p2, f2);
+  return dk_launch_gemm_pair(p, p2, S_(stream));
+}
+
+extern "C" int dk_gemm_fused_plan(const dk_gemm_desc* d, const dk_gemm_side* f, const dk_gemm_desc* d2, const dk_gemm_side* f2,
+                                  dk_gemm_plan_t* plan) {
+  DK_REQUIRE(d != nullptr && plan != nullptr && (d2 != nullptr || f2 == nullptr), "null descriptor / plan");
+  GemmParams p = gemm_params_from_desc(d), p2 = d2 != nullptr ? gemm_params_from_desc(d2) : GemmParams{};
+  set_fused(p, f);
+  if (d2 != nullptr) set_fused(p2, f2);
+  return dk_gemm_plan_call(p, d2 != nullptr ? &p2 : nullptr, *plan);
+}
+
 // workspace: optional K-split scratch (dk_gemm_split_workspace_bytes) for stages whose tiles fill only half the CUs
 static int conv3x3_launch(const dk_conv_desc* d, void* workspace, hipStream_t stream) {
   DK_REQUIRE(d != nullptr, "null descriptor");
@@ -137,6 +167,21 @@ extern "C" int dk_attention_bias_bf16(const void* q, const void* k, const void* 
   p.Q = (const bf16_t*)q; p.K = (const bf16_t*)k; p.V = (const bf16_t*)v; p.O = (bf16_t*)out;
   p.B = B; p.H = H; p.S = S; p.D = D; p.ld = ld; p.ldo = ldo; p.scale = scale;
   p.bias = (const bf16_t*)bias; p.bias_head_stride = (long)bias_head_stride; p.ldb = ldb;
+  return dk_launch_attention(p, S_(stream));
+}
+static int mx_nblk(long rows);
+extern "C" int dk_attention_desc_bf16(const dk_attention_desc* d, void* stream) {
+  DK_REQUIRE(d != nullptr, "null descriptor");
+  AttnParams p;
+  p.Q = (const bf16_t*)d->q; p.K = (const bf16_t*)d->k; p.V = (const bf16_t*)d->v; p.O = (bf16_t*)d->out;
+  p.B = d->B; p.H = d->H; p.S = d->S; p.D = d->D; p.ld = d->ld; p.ldo = d->ldo; p.scale = d->scale;
+  p.bias = (const bf16_t*)d->bias; p.bias_head_stride = (long)d->bias_head_stride; p.ldb = d->ldb;
+  p.qn_a = (const bf16_t*)d->qn_a; p.qn_b = (const bf16_t*)d->qn_b; p.qn_split = d->qn_split; p.qn_eps = d->qn_eps; p.q_rope = d->q_rope;
+  if (d->O8 != nullptr) {
+    DK_REQUIRE(d->O8_scales != nullptr && ((long)d->B * d->S) % 128 == 0 && d->o8_rows >= (int64_t)d->B * d->S && d->o8_ld >= d->H * d->D && d->o8_ld % 32 == 0,
+               "MX-fp8 output copy: scales, B * S a multiple of 128 rows inside the buffer, a row pitch of at least H * D bytes (multiple of 32)");
+    p.O8 = (unsigned char*)d->O8; p.O8_scales = (unsigned char*)d->O8_scales; p.o8_ld = d->o8_ld; p.o8_nblk = mx_nblk((long)d->o8_rows);
+  }
   return dk_launch_attention(p, S_(stream));
 }
 extern "C" int32_t dk_attention_d512_tp(int32_t T) { return (int32_t)align_up((size_t)(T > 0 ? T : 0), 64); }
@@ -194,9 +239,8 @@ extern "C" int32_t dk_weight_pitch_fp8(int32_t k) { return k >= g_dk_pitch_min_k
 static int mx_nblk(long rows) { return (int)((rows + 127) / 128 + 1); }
 extern "C" size_t dk_mx_scale_bytes(int64_t rows, int32_t k) { return (size_t)((k + 127) / 128) * (size_t)mx_nblk((long)rows) * 512; }
 
-extern "C" int dk_gemm_fp8(const dk_gemm_fp8_desc* d, void* stream) {
-  DK_REQUIRE(d != nullptr, "null descriptor");
-  GemmF8Params p;
+// mx8_out: the descriptor's C_scales / c_rows / c_row0 / c_col0 describe an MX-fp8 output (its own, or the second one of a column split)
+static int gemm_f8_params_from_desc(const dk_gemm_fp8_desc* d, bool mx8_out, GemmF8Params& p) {
   memset(&p, 0, sizeof(p));
   p.A = (const unsigned char*)d->A; p.SA = (const unsigned char*)d->A_scales; p.W = (const unsigned char*)d->W; p.wscale = d->w_scale;
   p.C = d->C; p.bias = (const bf16_t*)d->bias; p.gate = (const bf16_t*)d->gate; p.res = (const bf16_t*)d->res;
@@ -207,12 +251,33 @@ extern "C" int dk_gemm_fp8(const dk_gemm_fp8_desc* d, void* stream) {
   p.r_seg_len = d->r_seg_len > 0 ? d->r_seg_len : d->M; p.r_seg_stride = d->r_seg_stride;
   p.gate_seg_len = d->gate_seg_len > 0 ? d->gate_seg_len : d->M; p.gate_stride = d->gate_stride;
   p.epi = d->epilogue; p.c_mx8 = d->c_mx8;
-  if (d->c_mx8) {
+  if (mx8_out) {
     DK_REQUIRE(d->M % 256 == 0 && d->c_col0 % 32 == 0 && d->C_scales != nullptr, "MX-fp8 output: M a multiple of 256, column offset a multiple of 32");
     p.SC = (unsigned char*)d->C_scales; p.sc_nblk = mx_nblk(d->c_rows); p.c_row0 = d->c_row0; p.sc_kb0 = d->c_col0 / 32;
   }
   p.workspace = d->workspace; p.workspace_bytes = d->workspace_bytes;
+  return 0;
+}
+
+extern "C" int dk_gemm_fp8(const dk_gemm_fp8_desc* d, void* stream) {
+  DK_REQUIRE(d != nullptr, "null descriptor");
+  GemmF8Params p;
+  if (const int rc = gemm_f8_params_from_desc(d, d->c_mx8 != 0, p)) return rc;
   return dk_launch_gemm256f8(p, nullptr, S_(stream));
+}
+
+extern "C" int dk_gemm_fp8_fused(const dk_gemm_fp8_desc* d, const dk_gemm_fp8_side* f, const dk_gemm_fp8_desc* d2, const dk_gemm_fp8_side* f2,
+                                 void* stream) {
+  DK_REQUIRE(d != nullptr && (d2 != nullptr || f2 == nullptr), "null descriptor");
+  GemmF8Params p, p2;
+  if (const int rc = gemm_f8_params_from_desc(d, d->c_mx8 != 0 || (f != nullptr && f->c2_mx8 != 0), p)) return rc;
+  set_fused(p, f);
+  if (f != nullptr) p.c2_mx8 = f->c2_mx8;
+  if (d2 == nullptr) return dk_launch_gemm256f8(p, nullptr, S_(stream));
+  if (const int rc = gemm_f8_params_from_desc(d2, d2->c_mx8 != 0 || (f2 != nullptr && f2->c2_mx8 != 0), p2)) return rc;
+  set_fused(p2, f2);
+  if (f2 != nullptr) p2.c2_mx8 = f2->c2_mx8;
+  return dk_launch_gemm256f8(p, &p2, S_(stream));
 }
 static Mx8Out mx8_out(void* out, void* scales, int ldo, long rows, int row0, int seg_len, int seg_stride, int col0) {
   Mx8Out o;

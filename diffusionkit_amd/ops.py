@@ -71,6 +71,50 @@ def gemm_desc_call(**kw) -> None:
     _lib.check(lib.dk_gemm_bf16(C.byref(d), _stream()), "dk_gemm_bf16")
 
 
+def _fill(struct, fields):
+    """a ctypes struct from {field: value}; tensors become their device pointers, None a NULL struct pointer"""
+    if fields is None:
+        return None
+    s = struct()
+    for k, v in fields.items():
+        setattr(s, k, v.data_ptr() if isinstance(v, torch.Tensor) else v)
+    return s
+
+
+def _ref(s):
+    return C.byref(s) if s is not None else None
+
+
+def gemm_fused_call(d: dict, side: Optional[dict] = None, d2: Optional[dict] = None, side2: Optional[dict] = None) -> None:
+    """dk_gemm_fused_bf16: the launch forms of the engines -- column split, QKNorm + RoPE in the tile tail, an image + text pair.
+    ``d`` / ``d2``: dk_gemm_desc fields, ``side`` / ``side2``: dk_gemm_side fields (tensors are converted to pointers)."""
+    a, f, b, f2 = _fill(_lib.dk_gemm_desc, d), _fill(_lib.dk_gemm_side, side), _fill(_lib.dk_gemm_desc, d2), _fill(_lib.dk_gemm_side, side2)
+    _lib.check(_lib.load().dk_gemm_fused_bf16(_ref(a), _ref(f), _ref(b), _ref(f2), _stream()), "dk_gemm_fused_bf16")
+
+
+def gemm_fused_plan(d: dict, side: Optional[dict] = None, d2: Optional[dict] = None, side2: Optional[dict] = None):
+    """dk_gemm_fused_plan: what ``gemm_fused_call`` with these arguments would launch (host only; pointers may be made-up, aligned integers)."""
+    a, f, b, f2 = _fill(_lib.dk_gemm_desc, d), _fill(_lib.dk_gemm_side, side), _fill(_lib.dk_gemm_desc, d2), _fill(_lib.dk_gemm_side, side2)
+    plan = _lib.dk_gemm_plan_t()
+    _lib.check(_lib.load().dk_gemm_fused_plan(_ref(a), _ref(f), _ref(b), _ref(f2), C.byref(plan)), "dk_gemm_fused_plan")
+    return plan
+
+
+def gemm_fp8_fused_call(d: dict, side: Optional[dict] = None, d2: Optional[dict] = None, side2: Optional[dict] = None) -> None:
+    """dk_gemm_fp8_fused: the same forms on the fp8 GEMM (dk_gemm_fp8_desc / dk_gemm_fp8_side fields)."""
+    a, f = _fill(_lib.dk_gemm_fp8_desc, d), _fill(_lib.dk_gemm_fp8_side, side)
+    b, f2 = _fill(_lib.dk_gemm_fp8_desc, d2), _fill(_lib.dk_gemm_fp8_side, side2)
+    _lib.check(_lib.load().dk_gemm_fp8_fused(_ref(a), _ref(f), _ref(b), _ref(f2), _stream()), "dk_gemm_fp8_fused")
+
+
+def attention_desc_call(**kw) -> None:
+    """dk_attention_desc_bf16: attention with the query QKNorm + RoPE in the Q load and / or the MX-fp8 output copy; keyword names =
+    dk_attention_desc fields."""
+    _lib.ensure_attention_workspace(torch.cuda.current_device())
+    d = _fill(_lib.dk_attention_desc, kw)
+    _lib.check(_lib.load().dk_attention_desc_bf16(C.byref(d), _stream()), "dk_attention_desc_bf16")
+
+
 _zero_pages = {}
 
 

@@ -98,6 +98,34 @@ typedef struct dk_gemm_plan_t {
 } dk_gemm_plan_t;
 int dk_gemm_plan(const dk_gemm_desc* d, const dk_gemm_desc* d2, dk_gemm_plan_t* plan);
 
+/* The launch forms only the engines issue (dk_mmdit_forward: the q / k / v projections of the double blocks, linear1 of the single blocks), at the
+ * operator level, so that each can be compared with a reference of that operation alone (tests/test_gpu_fused_ops.py).  A dk_gemm_side rides beside a
+ * dk_gemm_desc and carries what the descriptor cannot say; all zero = the plain dk_gemm_bf16 call.
+ *   column split: output columns >= n_split (multiple of 256) go to C2 (row stride ldc2, C's row map, column index rebased to 0) with epilogue epi2 --
+ *     [q | k | v] and gelu(fc1) over one read of the activations (mmdit.py:693-751);
+ *   QKNorm + RoPE (mmdit.py:754-764, 934-942) in the tile tail: the columns [kn_col0, kn_col1) are heads of kn_D (128 / 64) columns, normalised with
+ *     kn_w [kn_D] and rotated by kn_rope (f32 [S_pos, kn_D / 2, 2], NULL: no rotation) at position kn_pos_off + row % kn_seg_len; qn_w: the columns
+ *     [qn_col0, qn_col1) the same way with their own weight (needs kn_w).  Same arithmetic and rounding points as dk_qk_norm_rope_bf16.
+ * With (d2, f2) the two problems are issued the way the engines issue the image and text stream of a double block: one grouped launch where the
+ * routing rules allow it (same N, K, epilogue), two launches otherwise.  A form a 256-column kernel cannot fuse is expanded into the equivalent
+ * sequence of launches (the column ranges one after the other; the projection, then the stand-alone norm pass): dk_gemm_fused_plan tells which. */
+typedef struct dk_gemm_side {
+  int32_t n_split;
+  void* C2;
+  int32_t ldc2;
+  int32_t epi2;
+  const void* kn_w;
+  const float* kn_rope;
+  int32_t kn_col0, kn_col1, kn_D, kn_pos_off, kn_seg_len;
+  float kn_eps;
+  const void* qn_w;
+  int32_t qn_col0, qn_col1;
+} dk_gemm_side;
+/* f / f2 may be NULL (nothing fused); d2 NULL: one problem */
+int dk_gemm_fused_bf16(const dk_gemm_desc* d, const dk_gemm_side* f, const dk_gemm_desc* d2, const dk_gemm_side* f2, void* stream);
+/* dk_gemm_plan of that call: launches == 1 -- fused / grouped in one 256-column kernel; 2 -- expanded */
+int dk_gemm_fused_plan(const dk_gemm_desc* d, const dk_gemm_side* f, const dk_gemm_desc* d2, const dk_gemm_side* f2, dk_gemm_plan_t* plan);
+
 typedef struct dk_conv_desc {
   const void* x;    /* NHWC bf16 [B, H(/2), W(/2), C]; C multiple of 64              */
   const void* w;    /* [O, 3, 3, C] bf16 (MLX nn.Conv2d weight layout)               */
@@ -153,6 +181,35 @@ int dk_groupnorm_table_bf16(const void* x, int32_t B, int64_t HW, int32_t C, int
  * q/k/v: row (b*S + s) at ptr + (b*S + s)*ld + head*D; out likewise with ldo.  D in {64,128}. */
 int dk_attention_bf16(const void* q, const void* k, const void* v, void* out, int32_t B, int32_t H,
                       int32_t S, int32_t D, int32_t ld, int32_t ldo, float scale, void* stream);
+
+/* The same by descriptor, with what the engines add to the launch (dk_mmdit_forward; tests/test_gpu_fused_ops.py):
+ *   bias (NULL: none): the additive score bias of dk_attention_bias_bf16;
+ *   QKNorm + RoPE of the QUERIES inside the kernel's Q load (the keys keep their own pass): token s < qn_split of every batch row is normalised with
+ *     qn_a [D], the others with qn_b (both NULL: no norm), eps qn_eps, and rotated by q_rope (f32 [S, D / 2, 2] indexed by s; NULL: no rotation);
+ *   O8 (NULL: none): an MX-fp8 copy of the output, row b * S + s at o8_ld bytes per row, head h at byte column h * D, E8M0 scales in O8_scales
+ *     (dk_mx_scale_bytes(o8_rows, o8_ld) bytes; B * S a multiple of 128) -- exactly dk_quantize_mx8 of the bf16 output.  The D = 128 kernels of
+ *     "attn" 9 / 10 write it from their accumulators INSTEAD of `out`, which they then leave untouched; the others write `out` and quantise it. */
+typedef struct dk_attention_desc {
+  const void* q;
+  const void* k;
+  const void* v;
+  void* out;
+  int32_t B, H, S, D, ld, ldo;
+  float scale;
+  const void* bias;
+  int64_t bias_head_stride;
+  int32_t ldb;
+  const void* qn_a;
+  const void* qn_b;
+  int32_t qn_split;
+  float qn_eps;
+  const float* q_rope;
+  void* O8;
+  void* O8_scales;
+  int32_t o8_ld;
+  int64_t o8_rows; /* rows of the buffer O8 points into (sizes its scale array) */
+} dk_attention_desc;
+int dk_attention_desc_bf16(const dk_attention_desc* d, void* stream);
 
 /* Workspace of the attention launches THIS host thread enqueues (256-byte aligned, dk_attention_workspace_bytes() bytes; NULL: none).
  * The one-wave-per-SIMD D = 128 kernel (attention5.hip) splits the query blocks of a launch's last, partial round of the CUs along the
@@ -227,6 +284,24 @@ typedef struct dk_gemm_fp8_desc {
   size_t workspace_bytes;
 } dk_gemm_fp8_desc;
 int dk_gemm_fp8(const dk_gemm_fp8_desc* d, void* stream);
+/* dk_gemm_side for the fp8 GEMM (the engines' fp8 blocks): the same fields, and c2_mx8 = 1: the second output of the column split leaves as MX-fp8
+ * (ldc2 in bytes) into the buffer the descriptor's C_scales / c_rows / c_row0 / c_col0 describe -- the descriptor's own output stays bf16 then
+ * (c_mx8 = 0).  With (d2, f2): one grouped launch of two problems with the same N, K, epilogues and split (an error otherwise: this kernel has no
+ * expansion).  The fused QKNorm needs a bf16 first output. */
+typedef struct dk_gemm_fp8_side {
+  int32_t n_split;
+  void* C2;
+  int32_t ldc2;
+  int32_t epi2;
+  int32_t c2_mx8;
+  const void* kn_w;
+  const float* kn_rope;
+  int32_t kn_col0, kn_col1, kn_D, kn_pos_off, kn_seg_len;
+  float kn_eps;
+  const void* qn_w;
+  int32_t qn_col0, qn_col1;
+} dk_gemm_fp8_side;
+int dk_gemm_fp8_fused(const dk_gemm_fp8_desc* d, const dk_gemm_fp8_side* f, const dk_gemm_fp8_desc* d2, const dk_gemm_fp8_side* f2, void* stream);
 size_t dk_mx_scale_bytes(int64_t rows, int32_t k);
 /* bf16 [M, h] (row stride ldx) -> MX-fp8 rows out_row0 .. of a [out_rows, ldo] e4m3 buffer at column out_col0 (multiple of 32) */
 int dk_quantize_mx8(const void* x, int32_t ldx, int32_t M, int32_t h, void* out, int32_t ldo, void* out_scales,

@@ -112,3 +112,124 @@ def test_plan_mode_leaves_no_state_behind():
     finally:
         lib.dk_tune_set(b"gemm_split", -1)
     assert plan(1280, 3072, 15360).split_tiles > 0
+
+
+# ---- the engine-only launch forms (dk_gemm_fused_plan): every case of tests/test_gpu_fused_ops.py takes the path it claims -----------------------
+from tests import _fused_cases as fc  # noqa: E402
+
+
+def fused_plan(call):
+    from diffusionkit_amd import ops
+    lib = _lib.load()
+    try:
+        for k, v in call.tune.items():
+            assert lib.dk_tune_set(k.encode(), v) == 0
+        return ops.gemm_fused_plan(*fc.resolve(call, fc.fake_address(call), lib.dk_gemm_workspace_bytes()))
+    finally:
+        for k in fc.TUNE_KEYS:
+            lib.dk_tune_set(k.encode(), -1)
+
+
+def check_expect(case, p):
+    launches, kernel = case["expect"]
+    assert p.launches == launches, (case["id"], p.launches, p.kernel)
+    if kernel is not None:
+        assert p.kernel == kernel, (case["id"], p.kernel)
+        if case.get("mf", -1) in (7, 8):
+            assert p.tile_rows == 32 * case["mf"], (case["id"], p.tile_rows)
+    else:
+        assert launches == 2  # an expansion names no single kernel
+
+
+@pytest.mark.parametrize("case", fc.SPLIT_CASES, ids=lambda c: c["id"])
+def test_column_split_cases_take_the_path_they_claim(case):
+    check_expect(case, fused_plan(fc.split_call(case)))
+    if case["expect"][0] == 1:  # ... and the two launches they are compared with run on the same kernel
+        for single in fc.split_single_calls(case):
+            p = fused_plan(single)
+            assert p.launches == 1 and p.kernel in (3, 4), (case["id"], p.kernel)
+
+
+@pytest.mark.parametrize("case", fc.PAIR_CASES, ids=lambda c: c["id"])
+def test_pair_cases_are_grouped(case):
+    p = fused_plan(fc.pair_call(case))
+    check_expect(case, p)
+    assert (p.split_tiles > 0) == bool(case.get("cut")), (case["id"], p.split_tiles)
+    if case.get("cut"):  # the rule the case names: a small extra share of a round, a long reduction
+        ta, tb = -(-case["B"] * case["S_i"] // 256) * (case["N"] // 256), -(-case["B"] * case["S_t"] // 256) * (case["N"] // 256)
+        assert (ta + tb) % p.n_cu <= p.n_cu // 4 and case["K"] // 64 >= 24
+    q = fused_plan(fc.pair_call(case, grouped=False))  # the comparison: two launches of gemm256v3.hip, whole tiles
+    assert (q.launches, q.kernel, q.split_tiles) == (2, 3, 0), (case["id"], q.launches, q.kernel)
+
+
+@pytest.mark.parametrize("case", fc.KNORM_CASES, ids=lambda c: c["id"])
+def test_qknorm_cases_take_the_path_they_claim(case):
+    check_expect(case, fused_plan(fc.knorm_call(case)))
+    if case["expect"][0] == 1:  # the plain projection of the second assertion: one launch of the same kernel
+        p = fused_plan(fc.knorm_call(case, fused=False))
+        assert (p.launches, p.kernel) == case["expect"], (case["id"], p.kernel)
+
+
+@pytest.mark.parametrize("case", fc.KNORM_PAIR_CASES, ids=lambda c: c["id"])
+def test_qknorm_pair_cases_are_grouped(case):
+    check_expect(case, fused_plan(fc.knorm_pair_call(case)))
+    q = fused_plan(fc.knorm_pair_call(case, fused=False, grouped=False))
+    assert (q.launches, q.kernel) == (2, 3)
+
+
+def test_ineligible_forms_expand():
+    """forms the 256-column kernels cannot fuse must run as the equivalent sequence of launches, never as a fused launch that ignores a field"""
+    for what, call, launches in fc.ineligible_calls():
+        assert fused_plan(call).launches == launches, what
+
+
+def test_fused_plan_without_a_side_struct_is_the_plain_plan():
+    a = plan(4352, 3072, 3072)
+    d = dict(M=4352, N=3072, K=3072, lda=3072, ldc=3072, ldr=3072, alpha=1.0, epilogue=0, workspace=FAKE_WS,
+             workspace_bytes=_lib.load().dk_gemm_workspace_bytes())
+    from diffusionkit_amd import ops
+    b = ops.gemm_fused_plan(d)
+    assert [getattr(a, f) for f, _ in a._fields_] == [getattr(b, f) for f, _ in b._fields_]
+
+
+@pytest.mark.parametrize("case", fc.KNORM_CASES, ids=lambda c: c["id"])
+def test_qknorm_cases_reach_the_tail_paths_they_name(case):
+    """dk_gemm_plan_t names kernel and tile height, not the tail path of a tile: the `fast` / `cut` arithmetic of the two kernels over the case's row
+    tiles (tests/_fused_cases.py: knorm_tail_paths) must give exactly the paths the table lists for it"""
+    if case["expect"][0] != 1:
+        assert case["id"] not in fc.KNORM_PATHS
+        return
+    p = fused_plan(fc.knorm_call(case))
+    assert fc.knorm_tail_paths(case, p.kernel, p.tile_rows) == fc.KNORM_PATHS[case["id"]], (case["id"], p.kernel, p.tile_rows)
+
+
+def test_qknorm_table_covers_every_tail_path_of_both_kernels():
+    seen = {3: set(), 4: set()}
+    for case in fc.KNORM_CASES:
+        if case["expect"][0] == 1:
+            seen[case["expect"][1]] |= fc.KNORM_PATHS[case["id"]]
+    assert seen[3] == {"fast", "wrap", "row"} and seen[4] == {"fast", "wrap", "cut", "row"}
+
+
+@pytest.mark.parametrize("case", fc.ATTN_Q_CASES + fc.ATTN_O8_CASES, ids=lambda c: c["id"])
+def test_attention_cases_run_the_kernel_they_name(case):
+    """dk_launch_attention turns mode 10 into 9 and 9 into the lean kernel without a word when a shape is not eligible, and attention5.hip's key split
+    needs 12 key tiles per range: the launchers' arithmetic (tests/_fused_cases.py: attn_path) against what the case's name claims"""
+    o8 = "in_kernel" in case
+    assert fc.attn_path(case, with_o8=o8) == fc.attn_claim(case), case["id"]
+    if o8:  # only the D = 128 kernels of modes 9 / 10 write the MX-fp8 copy themselves
+        assert case["in_kernel"] == (fc.attn_path(case, True)[0] in ("alt", "wave") and case["D"] == 128)
+        assert (case["B"] * case["S"]) % 128 == 0
+
+
+def test_attention_path_arithmetic_matches_the_launcher_source():
+    """attn_path restates constants of the launchers: fail when the source no longer holds them"""
+    import os
+    csrc = os.path.join(os.path.dirname(_lib.HEADER_PATH), "..", "diffusionkit_amd", "csrc")
+    a5 = open(os.path.join(csrc, "attention5.hip")).read()
+    assert "p.D == 128 && p.bias == nullptr && p.S % 256 == 0 && p.S >= 12 * 64" in a5
+    assert "if ((p.S / 256) / s < 3) break;" in a5 and "tail * s <= n_cu && tail * s * 10 >= n_cu * 6" in a5
+    assert "tail > 0 && p.O8 == nullptr && g_dk_attn5_split != 0" in a5
+    a = open(os.path.join(csrc, "attention.hip")).read()
+    assert "if (mode == 10 && !dk_attention5_eligible(p)) mode = 9;" in a
+    assert "rc = p.D == 128 ? dk_launch_attention4(p, stream) : dk_launch_attention2(p, 4, stream);" in a

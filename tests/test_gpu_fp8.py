@@ -260,3 +260,99 @@ def test_guidance_embedding(dev):
             ref[name] = taps["final"]
         yardstick_ok(outs[g], ref["emu"], ref["fp32"], f"guidance {g}")
     assert rel_l2(outs[3.5], outs[1.0]) > 1e-3
+
+
+# ---- the engine-only launch forms of the fp8 GEMM (dk_gemm_fp8_fused), each against the exact product of the dequantised operands --------------------
+def _fp8_desc(dev, qa, ea, qw, ws, bias, M, N, K, a_rows=None, a_row0=0):
+    """dk_gemm_fp8_desc fields of one problem over rows [a_row0, a_row0 + M) of an activation buffer (device tensors are kept alive by the caller)"""
+    keep = dict(a8=qa.to(dev), sa=f8.scales_to_array(ea, a_rows).to(dev), w8=qw.to(dev), ws=ws.to(dev), bias=bias.to(dev, BF))
+    d = dict(A=keep["a8"].data_ptr() + a_row0 * K, A_scales=keep["sa"], W=keep["w8"], w_scale=keep["ws"], bias=keep["bias"], M=M, N=N, K=K,
+             lda=K, ldw=qw.shape[1], a_row0=a_row0, a_rows=qa.shape[0], epilogue=DK_EPI_BIAS)
+    return d, keep
+
+
+def test_gemm_fp8_column_split_bf16_and_mx8_outputs(dev):
+    """linear1 of the single blocks on the fp8 path: [q | k | v] + bias -> bf16 C, gelu(fc1 + bias) -> MX-fp8 into a column window (offset 128: scale
+    blocks from sc_kb0 = 4) of a wider buffer whose other bytes must stay"""
+    from oracle.mmdit import gelu_erf
+    M, K, n1, n2, col0, ld8 = 512, 256, 768, 1024, 128, 128 + 1024 + 64
+    a, qa, ea, qw, ws, a_dq, w_dq = _fp8_problem(M, n1 + n2, K, seed=41)
+    bias = randn(n1 + n2, seed=42, scale=0.5)
+    d, keep = _fp8_desc(dev, qa, ea, qw, ws, bias, M, n1 + n2, K)
+    out = torch.full((M + 8, n1), 7.0, dtype=BF, device=dev)
+    buf8 = torch.full((M, ld8), 0xAB, dtype=torch.uint8, device=dev)
+    sc = torch.zeros(ops.mx_scale_bytes(M, ld8), dtype=torch.uint8, device=dev)
+    d.update(C=out, ldc=n1, C_scales=sc, c_rows=M, c_row0=0, c_col0=col0)
+    ops.gemm_fp8_fused_call(d, dict(n_split=n1, C2=buf8.data_ptr() + col0, ldc2=ld8, epi2=DK_EPI_BIAS_GELU, c2_mx8=1))
+    acc = a_dq @ w_dq.t() + bias
+    assert rel_l2(acc[:, :n1], out[:M].float()) < TOL_SINGLE_OP
+    assert bool((out[M:] == 7.0).all())
+    hid = gelu_erf(bf16r(acc[:, n1:]), Prec(BF))
+    want_q, want_e = o8.mx8_encode(hid)
+    got = f8.mx8_decode(buf8[:, col0:col0 + n2], f8.array_to_scales(sc, M, n2, rows=M, col0=col0))
+    r = rel_l2(f8.mx8_decode(want_q, want_e), got)
+    print(f"[fp8 column split] bf16 output rel_l2 {rel_l2(acc[:, :n1], out[:M].float()):.3e}, MX-fp8 output against the encoded oracle {r:.3e} (< 6e-3)")
+    assert r < 6e-3  # (as test_gemm_fp8_gelu_mx8_output_feeds_next_gemm: a bf16 ulp in front of the quantiser on a few elements)
+    assert bool((buf8[:, :col0] == 0xAB).all()) and bool((buf8[:, col0 + n2:] == 0xAB).all())
+
+
+@pytest.mark.parametrize("epi", ["bias", "gate_res"])
+def test_gemm_fp8_grouped_pair(dev, epi):
+    """image rows [0, Mi) and text rows [Mi, Mi + Mt) of one MX-fp8 activation buffer (one scale side array) in one launch, into the image / text rows of a
+    joint bf16 [B, S_t + S_i, N] buffer: own weights, weight scales, bias and gate per stream; gate + residual in place"""
+    B, S_t, S_i, N, K = 2, 128, 384, 512, 256
+    Mi, Mt, S = B * S_i, B * S_t, S_t + S_i
+    a, qa, ea, _, _, a_dq, _ = _fp8_problem(Mi + Mt, N, K, seed=51)
+    probs = []
+    for seed, row0, M in ((52, 0, Mi), (54, Mi, Mt)):
+        w = randn(N, K, seed=seed, scale=0.03).to(BF)
+        qw, ws = quantize_weight_e4m3(w)
+        probs.append((qw, ws, dequantize_weight_e4m3(qw, ws), randn(N, seed=seed + 1, scale=0.5), randn(B, N, seed=seed + 10), row0, M))
+    X = randn(B * S + 8, N, seed=60)
+    X[B * S:] = 7.0
+    Xd = X.to(dev, BF) if epi == "gate_res" else torch.full((B * S + 8, N), 7.0, dtype=BF, device=dev)
+    descs, keeps = [], []
+    for (qw, ws, w_dq, bias, gate, row0, M), (c_row0, seg) in zip(probs, ((S_t, S_i), (0, S_t))):
+        d, keep = _fp8_desc(dev, qa, ea, qw, ws, bias, M, N, K, a_row0=row0)
+        d.update(C=Xd.data_ptr() + c_row0 * N * 2, ldc=N, c_seg_len=seg, c_seg_stride=S)
+        if epi == "gate_res":
+            keep["gate"] = gate.to(dev, BF)
+            d.update(epilogue=DK_EPI_GATE_RES, res=d["C"], ldr=N, r_seg_len=seg, r_seg_stride=S, gate=keep["gate"], gate_seg_len=seg, gate_stride=N)
+        descs.append(d)
+        keeps.append(keep)
+    ops.gemm_fp8_fused_call(descs[0], None, descs[1], None)
+    got = Xd.float().cpu()
+    for (qw, ws, w_dq, bias, gate, row0, M), (c_row0, seg) in zip(probs, ((S_t, S_i), (0, S_t))):
+        m = torch.arange(M)
+        rows = c_row0 + (m // seg) * S + m % seg
+        lin = a_dq[row0:row0 + M] @ w_dq.t() + bias
+        ref = X[rows] + bf16r(gate.repeat_interleave(seg, 0) * bf16r(lin)) if epi == "gate_res" else lin
+        r = rel_l2(ref, got[rows])
+        print(f"[fp8 pair {epi}] problem at activation row {row0}: rel_l2 {r:.3e}")
+        assert r < TOL_SINGLE_OP
+    assert bool((got[B * S:] == 7.0).all())
+
+
+@pytest.mark.parametrize("D,table", [(128, "real"), (128, "ident"), (64, "angle")])
+def test_gemm_fp8_qknorm_rope_in_tail(dev, D, table):
+    """key AND query QKNorm + RoPE in the fp8 GEMM's tail (the fp8 path's default): the bounds of test_gpu_fused_ops.test_qknorm_rope_in_gemm_tail against
+    the oracle's rms_norm / rope_apply over the rounded exact product of the dequantised operands; two sequences of 384 rows, first position 16"""
+    from tests import _fused_cases as fc
+    from tests._fused_cases import norm_columns_ok, projection
+    h, K, n_seq, seg_len, pos_off = 256, 256, 2, 384, 16
+    M = n_seq * seg_len
+    a, qa, ea, qw, ws, a_dq, w_dq = _fp8_problem(M, 3 * h, K, seed=71)
+    case = dict(h=h, D=D, n_seq=n_seq, seg_len=seg_len, pos_off=pos_off, K=K, table=table, qn=True)
+    t = fc.knorm_inputs(case)
+    d, keep = _fp8_desc(dev, qa, ea, qw, ws, t["bias"][0], M, 3 * h, K)
+    out = torch.full((M + 8, 3 * h), 7.0, dtype=BF, device=dev)
+    kn, qn, rope = t["kn_w"].to(dev, BF), t["qn_w"].to(dev, BF), t["rope"].to(dev)
+    d.update(C=out, ldc=3 * h)
+    ops.gemm_fp8_fused_call(d, dict(kn_w=kn, kn_rope=rope, kn_col0=h, kn_col1=2 * h, kn_D=D, kn_pos_off=pos_off, kn_seg_len=seg_len, kn_eps=fc.KN_EPS,
+                                    qn_w=qn, qn_col0=0, qn_col1=h))
+    proj = projection(a_dq, w_dq, t["bias"])
+    ref = fc.knorm_oracle(case, t, proj, Prec(BF))
+    got = out.float().cpu()
+    norm_columns_ok(ref, got[:M], h, D, f"fp8 knorm D={D} {table}")
+    assert rel_l2(proj[:, 2 * h:], got[:M, 2 * h:]) < TOL_SINGLE_OP
+    assert bool((got[M:] == 7.0).all())

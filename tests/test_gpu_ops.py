@@ -677,6 +677,24 @@ def test_qk_norm_rope(dev, D, norm, rope):
     assert rel_l2(ref, got) < 2e-3
 
 
+@pytest.mark.parametrize("D", [128, 64])
+def test_qk_norm_rope_key_weight_alone(dev, D):
+    """include/dk_hip.h: "q_weight/k_weight NULL = no norm; rope_table NULL = no rotation" -- a key weight alone (q_weight NULL, no table) is work:
+    the keys are normalised, q and v stay as they are (the launcher used to return early whenever q_weight and the table were both NULL)"""
+    from diffusionkit_amd import ops
+    B, H, S = 2, 3, 29
+    h = H * D
+    qkv = randn(B, S, 3 * h, seed=53)
+    kw = bf16r(1 + randn(D, seed=54, scale=0.1))
+    d = g(qkv, dev)
+    ops.qk_norm_rope_(d, H, D, None, g(kw, dev), None)
+    k = om.rms_norm(qkv[..., h:2 * h].reshape(B, S, H, D), kw, 1e-6, Prec(BF)).reshape(B, S, h)
+    got = d.float().cpu()
+    assert torch.equal(got[..., :h], qkv[..., :h]) and torch.equal(got[..., 2 * h:], qkv[..., 2 * h:])  # q and v untouched
+    assert rel_l2(k, got[..., h:2 * h]) < 2e-3
+    assert not torch.equal(got[..., h:2 * h], qkv[..., h:2 * h])
+
+
 def test_timestep_embedding(dev):
     from diffusionkit_amd import ops
     from diffusionkit_amd.config import FLUX_SCHNELL, SD3_2b
