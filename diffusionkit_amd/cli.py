@@ -2,7 +2,8 @@
 pipelines.  Flags, defaults, the per-model height / width / shift tables, the FLUX "no CFG" rule, the benchmark-mode
 warm-up and the error behaviour follow python/src/diffusionkit/mlx/scripts/generate_images.py:15-187.
 
-There is no hub access on an MI355X box, so checkpoints are named explicitly: ``--local-ckpt`` is the MMDiT
+There is no hub access on an MI355X box, so checkpoints are named explicitly: ``--fp8 quality|speed`` selects the fp8 path (config.fp8_config)
+of the FLUX versions; ``--local-ckpt`` is the MMDiT
 ``.safetensors`` (as in the reference) and ``--ckpt KEY=PATH`` adds the other parts (``vae_decoder``, ``vae_encoder``, ``clip_l``,
 ``clip_g``, ``t5``, ``t5_tokenizer``; ``tokenizer_l`` / ``tokenizer_g`` take ``vocab.json,merges.txt``).  Parts that are not named
 run on seeded synthetic weights / synthetic conditioning and the log line says so -- useful for timing, not for pictures.
@@ -55,6 +56,9 @@ def build_parser(model_versions: Sequence[str]) -> argparse.ArgumentParser:
     p.add_argument("--ckpt", action="append", default=[], metavar="KEY=PATH",
                    help="Further local checkpoint parts (vae_decoder, vae_encoder, clip_l, clip_g, t5, t5_tokenizer, "
                         "tokenizer_l=vocab.json,merges.txt, tokenizer_g=...). Repeatable.")
+    p.add_argument("--fp8", choices=("quality", "speed"), default=None,
+                   help="Run the transformer blocks on the fp8 MFMA path (FLUX versions only). quality: the first double-stream "
+                        "blocks keep bf16 Linears; speed: every block Linear in fp8.")
     p.add_argument("--device", default=None, help="HIP device, e.g. cuda:0 (default: the current device)")
     return p
 
@@ -84,8 +88,13 @@ def resolve(args) -> dict:
     width = args.width or WIDTH[args.model_version]
     assert height % 16 == 0, f"Height must be divisible by 16 ({height}/16={height/16})"
     assert width % 16 == 0, f"Width must be divisible by 16 ({width}/16={width/16})"
-    return {"cfg": cfg, "shift": args.shift or SHIFT[args.model_version], "height": height, "width": width,
-            "flux": "FLUX" in args.model_version, "low_memory_mode": args.low_memory_mode and not args.benchmark_mode}
+    r = {"cfg": cfg, "shift": args.shift or SHIFT[args.model_version], "height": height, "width": width,
+         "flux": "FLUX" in args.model_version, "low_memory_mode": args.low_memory_mode and not args.benchmark_mode}
+    if getattr(args, "fp8", None):
+        # (config.fp8_config raises a ValueError for the SD3 geometries: head_dim 64)
+        from .config import MODEL_CONFIG, fp8_config
+        r["mmdit_config"] = fp8_config(MODEL_CONFIG[args.model_version], args.fp8)
+    return r
 
 
 def main(argv: Optional[Sequence[str]] = None, pipeline_overrides: Optional[dict] = None):
@@ -97,9 +106,13 @@ def main(argv: Optional[Sequence[str]] = None, pipeline_overrides: Optional[dict
     r = resolve(args)
     from .pipeline import DiffusionPipeline, FluxPipeline
     pipeline_class = FluxPipeline if r["flux"] else DiffusionPipeline
+    extra = dict(pipeline_overrides or {})
+    if args.fp8:  # (a config of the caller's is put on the fp8 path like the model version's own)
+        from .config import fp8_config
+        extra["mmdit_config"] = fp8_config(extra["mmdit_config"], args.fp8) if extra.get("mmdit_config") is not None else r["mmdit_config"]
     sd = pipeline_class(w16=True, shift=r["shift"], use_t5=args.t5, model_version=args.model_version,
                         low_memory_mode=r["low_memory_mode"], a16=True, local_ckpt=checkpoint_dict(args.local_ckpt, args.ckpt),
-                        device=args.device, **(pipeline_overrides or {}))
+                        device=args.device, **extra)
     logger.info(f"Output image resolution will be {r['height']}x{r['width']}")
     latent_size = (r["height"] // 8, r["width"] // 8)
     if args.benchmark_mode:

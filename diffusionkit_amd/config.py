@@ -47,7 +47,7 @@ class MMDiTConfig:
     dtype: str = "bfloat16"
     guidance_embed: bool = False
     # storage / MFMA dtype of the transformer blocks' Linear weights: "bfloat16", or "fp8_e4m3" (per-output-channel scales,
-    # MX-fp8 activations quantised on the fly; FLUX geometry only: head_dim 128, token counts multiples of 128)
+    # MX-fp8 activations quantised on the fly; FLUX geometry only: head_dim 128, text length a multiple of 128 -- any image token count)
     weight_dtype: str = "bfloat16"
     # fp8 precision policy (only read with weight_dtype = "fp8_e4m3"): the Linears of the first n double-stream blocks stay bf16 --
     # an error made in the first blocks travels through all the others (measured dB per block: DESIGN.md section 4)
@@ -133,7 +133,8 @@ def fp8_config(cfg: MMDiTConfig, policy: str = "quality") -> MMDiTConfig:
         raise ValueError(f"unknown fp8 policy {policy!r} (quality | speed)")
     # (reject here what dk_mmdit_create would only reject later -- the fp8 kernels are FLUX geometry: head_dim 128, width a multiple of 256)
     if cfg.head_dim != 128 or cfg.hidden_size % 256 != 0:
-        raise ValueError(f"fp8_config: the fp8 path needs head_dim 128 and hidden_size % 256 == 0 (got {cfg.head_dim}, {cfg.hidden_size})")
+        raise ValueError(f"fp8_config: the fp8 path needs head_dim 128 and hidden_size % 256 == 0 (got {cfg.head_dim}, {cfg.hidden_size}); "
+                         "at run time the text length must be a multiple of 128, the image size is free")
     n = min(FLUX_FP8_QUALITY_BLOCKS, cfg.depth_multimodal) if policy == "quality" else 0
     out = replace(cfg, weight_dtype="fp8_e4m3", fp8_bf16_double_blocks=n)
     validate_fp8_policy(out)

@@ -43,6 +43,10 @@ int dk_launch_attention(const AttnParams& p_in, hipStream_t stream) {
   const bool long5 = p.D == 128 && (p.S >= 2048 || (p.S >= 1024 && blocks5 * 4 >= 3L * dk_device_cu_count()));
   int mode = p.bias != nullptr ? 4 : g_dk_attn_mode < 0 ? (long5 ? 10 : 4) : g_dk_attn_mode;
   if (mode == 10 && !dk_attention5_eligible(p)) mode = 9;
+  if (p.O8 != nullptr && p.o8_split != 0) {
+    DK_REQUIRE(p.o8_split > 0 && p.o8_split < p.S && p.o8_txt_row0 >= p.B * (p.S - p.o8_split), "MX-fp8 copy: text rows behind the image rows");
+    if (mode == 10) mode = 9;  // (attention5.hip writes the joint row order only)
+  }
   dk_prof_begin(2, 4.0 * (double)p.B * p.H * (double)p.S * (double)p.S * p.D, stream);
   int rc = 0;
   switch (mode) {
@@ -58,6 +62,11 @@ int dk_launch_attention(const AttnParams& p_in, hipStream_t stream) {
   DK_CHECK_HIP(hipGetLastError());
   if (p.O8 != nullptr && !((mode == 9 || mode == 10) && p.D == 128)) {
     // only the D = 128 kernels write the MX-fp8 copy themselves: quantise the bf16 output behind the others
+    if (p.o8_split != 0) {  // text rows of every batch row -> [o8_txt_row0, ...), image rows -> [0, B * S_i)
+      const int S_t = p.o8_split, S_i = p.S - S_t;
+      Mx8Out o_txt{p.O8, p.O8_scales, p.o8_ld, p.o8_nblk, p.o8_txt_row0, p.B * S_t, 0, 0}, o_img{p.O8, p.O8_scales, p.o8_ld, p.o8_nblk, 0, p.B * S_i, 0, 0};
+      return dk_launch_quantize2_mx8(p.O + (size_t)S_t * p.ldo, S_i, p.B * S_i, o_img, p.O, S_t, p.B * S_t, o_txt, p.ldo, p.S, p.H * p.D, stream);
+    }
     Mx8Out o8{p.O8, p.O8_scales, p.o8_ld, p.o8_nblk, 0, p.B * p.S, 0, 0};
     return dk_launch_quantize_mx8(p.O, p.ldo, p.B * p.S, 0, p.B * p.S, p.H * p.D, o8, stream);
   }

@@ -116,6 +116,8 @@ __global__ __launch_bounds__(512, 2) void dk_attn4_fwd_kernel(AttnParams p) {
   for (int par = 0; par < 2; ++par)
     vr_off[par] = (unsigned)(x16 * 2048 + ((4 * (hi ^ x16) + (p16 >> 2)) ^ (2 * par + x16)) * 32 + (p16 & 3) * 8);
 
+  int b_tail = b;  // (the MX-fp8 store's copy of b waits in a VECTOR register: the tile loop leaves no scalar register free for it)
+  asm volatile("" : "+v"(b_tail));
   const bf16_t* Qb = p.Q + (size_t)b * S * p.ld + head * D;
   const char* Kb = (const char*)(p.K + (size_t)b * S * p.ld + head * D);  // wave-uniform bases
   const char* Vb = (const char*)(p.V + (size_t)b * S * p.ld + head * D);
@@ -399,7 +401,11 @@ __global__ __launch_bounds__(512, 2) void dk_attn4_fwd_kernel(AttnParams p) {
   const int q = q0 + l31;
   if (p.O8 != nullptr) {
     // MX-fp8 output: a 32-column block (one dt) of a query row lives in this lane and lane ^ 32 (16 values each)
-    const size_t orow = (size_t)b * S + min(q, S - 1);
+    // row of the copy (dk_kernels.h): text rows (s < o8_split) at o8_txt_row0 + b * S_t + s, image rows at b * (S - S_t) + s - S_t; o8_split == 0 is
+    // the joint stream's b * S + s
+    const int qc = min(q, S - 1);
+    const bool o8_txt = qc < p.o8_split;
+    const size_t orow = (size_t)(unsigned)(b_tail * (o8_txt ? p.o8_split : S - p.o8_split) + qc + (o8_txt ? p.o8_txt_row0 : -p.o8_split));
 #pragma unroll
     for (int dt = 0; dt < D / 32; ++dt) {
       float v[16], amax = 0.f;

@@ -171,6 +171,9 @@ struct Mx8Out {
   int ldo, n_blk128, row0, seg_len, seg_stride, col0;
 };
 int dk_launch_quantize_mx8(const bf16_t* x, int ldx, int x_seg_len, int x_seg_stride, int M, int h, const Mx8Out& o, hipStream_t stream);
+// two such jobs in one launch (the text and the image rows of a joint attention output): rows through (x_seg_len*, x_seg_stride) of x0 / x1
+int dk_launch_quantize2_mx8(const bf16_t* x0, int x_seg_len0, int M0, const Mx8Out& o0, const bf16_t* x1, int x_seg_len1, int M1, const Mx8Out& o1,
+                            int ldx, int x_seg_stride, int h, hipStream_t stream);
 int dk_launch_ln_modulate_mx8(const bf16_t* x, int ldx, int M, int h, const bf16_t* shift, const bf16_t* scale, int mod_stride, int seg_len,
                               int x_seg_len, int x_seg_stride, float eps, const Mx8Out& o, hipStream_t stream);
 int dk_launch_ln_modulate2_mx8(const bf16_t* x0, int M0, const bf16_t* shift0, const bf16_t* scale0, int seg0, const Mx8Out& o0,
@@ -212,6 +215,10 @@ struct AttnParams {
   unsigned char* O8 = nullptr;
   unsigned char* O8_scales = nullptr;
   int o8_ld = 0, o8_nblk = 0;
+  // row order of that copy.  o8_split == 0: row b*S + s, like O.  o8_split = S_t > 0 (the engine's double blocks with a ragged image token
+  // count): the image rows of all batch rows first, row b*(S - S_t) + (s - S_t), and the text rows behind them, row o8_txt_row0 + b*S_t + s --
+  // the two row ranges of the o-projections then start on 128-row scale blocks whatever S is (attention5.hip does not take such launches)
+  int o8_split = 0, o8_txt_row0 = 0;
   // attention5.hip, filled in by its launcher: workgroups 0 .. a5_whole - 1 take whole query blocks; the others one of a5_split key ranges of
   // a block of the last, partial round of the CUs and leave (O / l in bf16, offset, l) in a5_ws for dk_attn5_merge_kernel
   int a5_whole = 0, a5_split = 1;

@@ -178,8 +178,8 @@ extern "C" int dk_attention_desc_bf16(const dk_attention_desc* d, void* stream) 
   p.bias = (const bf16_t*)d->bias; p.bias_head_stride = (long)d->bias_head_stride; p.ldb = d->ldb;
   p.qn_a = (const bf16_t*)d->qn_a; p.qn_b = (const bf16_t*)d->qn_b; p.qn_split = d->qn_split; p.qn_eps = d->qn_eps; p.q_rope = d->q_rope;
   if (d->O8 != nullptr) {
-    DK_REQUIRE(d->O8_scales != nullptr && ((long)d->B * d->S) % 128 == 0 && d->o8_rows >= (int64_t)d->B * d->S && d->o8_ld >= d->H * d->D && d->o8_ld % 32 == 0,
-               "MX-fp8 output copy: scales, B * S a multiple of 128 rows inside the buffer, a row pitch of at least H * D bytes (multiple of 32)");
+    DK_REQUIRE(d->O8_scales != nullptr && d->o8_rows >= (int64_t)d->B * d->S && d->o8_ld >= d->H * d->D && d->o8_ld % 32 == 0,
+               "MX-fp8 output copy: scales, B * S rows inside the buffer, a row pitch of at least H * D bytes (multiple of 32)");
     p.O8 = (unsigned char*)d->O8; p.O8_scales = (unsigned char*)d->O8_scales; p.o8_ld = d->o8_ld; p.o8_nblk = mx_nblk((long)d->o8_rows);
   }
   return dk_launch_attention(p, S_(stream));
@@ -252,7 +252,7 @@ static int gemm_f8_params_from_desc(const dk_gemm_fp8_desc* d, bool mx8_out, Gem
   p.gate_seg_len = d->gate_seg_len > 0 ? d->gate_seg_len : d->M; p.gate_stride = d->gate_stride;
   p.epi = d->epilogue; p.c_mx8 = d->c_mx8;
   if (mx8_out) {
-    DK_REQUIRE(d->M % 256 == 0 && d->c_col0 % 32 == 0 && d->C_scales != nullptr, "MX-fp8 output: M a multiple of 256, column offset a multiple of 32");
+    DK_REQUIRE(d->c_col0 % 32 == 0 && d->C_scales != nullptr, "MX-fp8 output: scales, column offset a multiple of 32");
     p.SC = (unsigned char*)d->C_scales; p.sc_nblk = mx_nblk(d->c_rows); p.c_row0 = d->c_row0; p.sc_kb0 = d->c_col0 / 32;
   }
   p.workspace = d->workspace; p.workspace_bytes = d->workspace_bytes;
@@ -519,9 +519,13 @@ struct dk_mmdit {
   float guidance = 3.5f;
   bf16_t *gemb = nullptr, *g1 = nullptr, *gvec = nullptr;
   // fp8_linears: MX-fp8 activation buffers + their scale side arrays (layout dk_mx_scale_index)
-  unsigned char *XN8 = nullptr, *ATT8 = nullptr, *HC8 = nullptr;    // [BS, h], [BS, h], max([BS, ldh8], [BS, ldcat8])
+  unsigned char *XN8 = nullptr, *ATT8 = nullptr, *HC8 = nullptr;    // [rows8, h], [rows8, h], max([rows8, ldh8], [rows8, ldcat8])
   unsigned char *SXN = nullptr, *SATT = nullptr, *SHID = nullptr, *SCAT = nullptr;
   int ldh8 = 0, ldcat8 = 0, nblk = 0;
+  // row order of the double blocks' fp8 buffers: image rows of all batch rows [0, B * S_i), text rows from txt0_8 =
+  // ceil128(B * S_i) -- every row range an fp8 GEMM reads starts on a 128-row scale block; rows8 = txt0_8 + B * S_t >= B * S
+  int txt0_8 = 0;
+  long rows8 = 0;
   bool fp8() const { return cfg.fp8_linears != 0; }
   // precision policy: the first n_bf16() double-stream blocks keep bf16 Linears under fp8_linears (global block index = double-block index)
   int n_bf16() const { return fp8() ? (cfg.fp8_bf16_double_blocks < cfg.depth_multimodal ? cfg.fp8_bf16_double_blocks : cfg.depth_multimodal) : 0; }
@@ -709,15 +713,19 @@ static size_t mmdit_carve(dk_mmdit* m, Carver& c, int B, int Hl, int Wl, int S_t
     const int r = m->cfg.mlp_ratio;
     m->ldh8 = dk_weight_pitch_fp8(r * h);
     m->ldcat8 = dk_weight_pitch_fp8((1 + r) * h);
-    m->nblk = mx_nblk((long)BS);
-    m->XN8 = (unsigned char*)c.take(BS * h);
-    m->ATT8 = (unsigned char*)c.take(BS * h);
-    const size_t hid8 = BS * (size_t)m->ldh8, cat8 = m->cfg.depth_unified > 0 ? BS * (size_t)m->ldcat8 : 0;
+    // (a ragged image token count pads the image rows to the next scale block; aligned counts: rows8 == BS, the sizes they always had)
+    m->txt0_8 = (int)align_up((size_t)B * S_i, 128);
+    m->rows8 = (long)m->txt0_8 + (long)B * S_t;
+    const size_t R8 = (size_t)m->rows8;
+    m->nblk = mx_nblk(m->rows8);
+    m->XN8 = (unsigned char*)c.take(R8 * h);
+    m->ATT8 = (unsigned char*)c.take(R8 * h);
+    const size_t hid8 = R8 * (size_t)m->ldh8, cat8 = m->cfg.depth_unified > 0 ? R8 * (size_t)m->ldcat8 : 0;
     m->HC8 = (unsigned char*)c.take(cat8 > hid8 ? cat8 : hid8);
-    m->SXN = (unsigned char*)c.take(dk_mx_scale_bytes((long)BS, h));
-    m->SATT = (unsigned char*)c.take(dk_mx_scale_bytes((long)BS, h));
-    m->SHID = (unsigned char*)c.take(dk_mx_scale_bytes((long)BS, r * h));
-    m->SCAT = (unsigned char*)c.take(m->cfg.depth_unified > 0 ? dk_mx_scale_bytes((long)BS, (1 + r) * h) : 0);
+    m->SXN = (unsigned char*)c.take(dk_mx_scale_bytes(m->rows8, h));
+    m->SATT = (unsigned char*)c.take(dk_mx_scale_bytes(m->rows8, h));
+    m->SHID = (unsigned char*)c.take(dk_mx_scale_bytes(m->rows8, r * h));
+    m->SCAT = (unsigned char*)c.take(m->cfg.depth_unified > 0 ? dk_mx_scale_bytes(m->rows8, (1 + r) * h) : 0);
   }
   m->MOD = (bf16_t*)c.take((size_t)n_t * B * m->mod_rows() * h * 2);
   m->POS = (bf16_t*)c.take(m->cfg.use_pos_embed ? (size_t)S_i * h * 2 : 0);
@@ -755,11 +763,8 @@ extern "C" int dk_mmdit_prepare(dk_mmdit* m, int32_t batch, int32_t latent_h, in
   const int p = m->cfg.patch_size;
   DK_REQUIRE(latent_h % p == 0 && latent_w % p == 0, "latent size must be divisible by the patch size");
   DK_TRY(mmdit_resolve(m));
-  if (m->fp8()) {
-    const int S_i_ = (latent_h / p) * (latent_w / p);
-    DK_REQUIRE(text_len % 128 == 0 && S_i_ % 128 == 0,
-               "fp8_linears: text_len and the number of image tokens must be multiples of 128 (MX scale blocks of 128 rows)");
-  }
+  // (the image token count is free: a last, partial scale block is handled by the row order of the fp8 buffers, mmdit_carve)
+  if (m->fp8()) DK_REQUIRE(text_len % 128 == 0, "fp8_linears: only text lengths that are multiples of 128 are supported (MX scale blocks of 128 rows; the image token count is free)");
   DK_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
   Carver c(workspace, workspace_bytes);
   const size_t need_bytes = mmdit_carve(m, c, batch, latent_h, latent_w, text_len, n_timesteps);
@@ -870,7 +875,8 @@ static int mmdit_final_layer(dk_mmdit* m, const bf16_t* mod_step, bf16_t* tokens
 
 // ---- fp8_linears: the transformer blocks on the fp8 GEMM (gemm256f8.hip) -------------------------------------------------
 // A Linear over MX-fp8 activations.  abuf / sa: the fp8 activation buffer and its scale side array (pitch lda bytes); the GEMM
-// reads logical rows through (a_row0, a_seg_len, a_seg_stride) -- all multiples of 128 rows (checked in dk_mmdit_prepare).
+// reads logical rows through (a_row0, a_seg_len, a_seg_stride): a_row0 a multiple of 128 rows, and either one segment of any length or
+// segments of whole 128-row blocks (dk_gemm256f8_eligible; the row order of mmdit_carve provides it for every token count).
 static GemmF8Params f8_params(const dk_mmdit* m, const unsigned char* abuf, const unsigned char* sa, int lda, int a_row0, int a_seg_len,
                               int a_seg_stride, const unsigned char* W, int ldw, const float* ws, const bf16_t* bias, int M, int N, int K,
                               int epi) {
@@ -903,11 +909,15 @@ static int mmdit_blocks_fp8(dk_mmdit* m, const bf16_t* mod_step, int first, int 
   bf16_t* X_img = m->X + (size_t)S_t * h;
   bf16_t* X_txt = m->X;
   const int Mi = B * S_i, Mt = B * S_t;
-  const long BS = (long)B * S;
   const int ldh8 = m->ldh8, ldcat8 = m->ldcat8;
-  // XN8 / HID8 keep the bf16 path's row order: image rows [0, Mi), text rows [Mi, Mi + Mt); ATT8 / CAT8 are indexed like the
-  // joint stream (b * S + s)
-  const Mx8Out xn_img = mx8_out(m->XN8, m->SXN, h, BS, 0, Mi, 0, 0), xn_txt = mx8_out(m->XN8, m->SXN, h, BS, Mi, Mt, 0, 0);
+  // XN8 / HID8: image rows [0, Mi), text rows [T0, T0 + Mt) with T0 = ceil128(Mi) (= Mi, the bf16 path's row order, for aligned image token
+  // counts).  CAT8 is indexed like the joint stream (b * S + s); so is ATT8 while S_i is a multiple of 128 -- with a ragged S_i the image segment
+  // of batch row b >= 1 would start inside a scale block, and ATT8 takes the row order of XN8 instead (att_split: the attention launch maps
+  // (b, s) to it, the o-projections read two plain row ranges)
+  const int T0 = m->txt0_8;
+  const long R8 = m->rows8;
+  const bool att_split = S_i % 128 != 0;
+  const Mx8Out xn_img = mx8_out(m->XN8, m->SXN, h, R8, 0, Mi, 0, 0), xn_txt = mx8_out(m->XN8, m->SXN, h, R8, T0, Mt, 0, 0);
   for (int i = 0; i < c.depth_multimodal; ++i) {
     if (i < first || i >= first + count) continue;
     const bf16_t* mod_img = mod_step + (size_t)m->mod_offset(0, i) * h;
@@ -920,7 +930,7 @@ static int mmdit_blocks_fp8(dk_mmdit* m, const bf16_t* mod_step, int first, int 
                                       S, c.layer_norm_eps, st));
     {
       GemmF8Params qi = f8_params(m, m->XN8, m->SXN, h, 0, Mi, 0, wi.qkv_w8, h, wi.qkv_ws, wi.qkv_b, Mi, 3 * h, h, DK_EPI_BIAS);
-      GemmF8Params qt = f8_params(m, m->XN8, m->SXN, h, Mi, Mt, 0, wt.qkv_w8, h, wt.qkv_ws, wt.qkv_b, Mt, 3 * h, h, DK_EPI_BIAS);
+      GemmF8Params qt = f8_params(m, m->XN8, m->SXN, h, T0, Mt, 0, wt.qkv_w8, h, wt.qkv_ws, wt.qkv_b, Mt, 3 * h, h, DK_EPI_BIAS);
       f8_out_bf16(qi, m->QKV + (size_t)S_t * 3 * h, 3 * h, S_i, S);
       f8_out_bf16(qt, m->QKV, 3 * h, S_t, S);
       if (fuse_k(wi.kn) && fuse_k(wt.kn)) {
@@ -939,14 +949,17 @@ static int mmdit_blocks_fp8(dk_mmdit* m, const bf16_t* mod_step, int first, int 
     if (fuse_q() && !(fuse_k(wi.kn) && fuse_k(wt.kn) && fuse_qg(wi.qn, true) && fuse_qg(wt.qn, true))) { ap.qn_a = wt.qn; ap.qn_b = wi.qn; ap.qn_split = S_t; ap.q_rope = c.use_rope ? m->rope : nullptr; }
     // the o-projection's MX-fp8 operand comes out of the attention kernel (or out of a quantiser pass behind it: attention.hip)
     ap.O8 = m->ATT8; ap.O8_scales = m->SATT; ap.o8_ld = h; ap.o8_nblk = m->nblk;
+    if (att_split) { ap.o8_split = S_t; ap.o8_txt_row0 = T0; }
     DK_TRY(dk_launch_attention(ap, st));
     // post_sdpa (mmdit.py:537-548): residual += gate_attn * o_proj(attn)
     {
-      GemmF8Params oi = f8_params(m, m->ATT8, m->SATT, h, S_t, S_i, S, wi.o_w8, h, wi.o_ws, wi.o_b, Mi, h, h, DK_EPI_GATE_RES);
+      GemmF8Params oi = att_split ? f8_params(m, m->ATT8, m->SATT, h, 0, Mi, 0, wi.o_w8, h, wi.o_ws, wi.o_b, Mi, h, h, DK_EPI_GATE_RES)
+                                  : f8_params(m, m->ATT8, m->SATT, h, S_t, S_i, S, wi.o_w8, h, wi.o_ws, wi.o_b, Mi, h, h, DK_EPI_GATE_RES);
       f8_out_bf16(oi, X_img, h, S_i, S);
       f8_gate_res(oi, mod_img + 2 * h, S_i, mod_stride, X_img, h, S_i, S);
       if (txt_post) {
-        GemmF8Params ot = f8_params(m, m->ATT8, m->SATT, h, 0, S_t, S, wt.o_w8, h, wt.o_ws, wt.o_b, Mt, h, h, DK_EPI_GATE_RES);
+        GemmF8Params ot = att_split ? f8_params(m, m->ATT8, m->SATT, h, T0, Mt, 0, wt.o_w8, h, wt.o_ws, wt.o_b, Mt, h, h, DK_EPI_GATE_RES)
+                                    : f8_params(m, m->ATT8, m->SATT, h, 0, S_t, S, wt.o_w8, h, wt.o_ws, wt.o_b, Mt, h, h, DK_EPI_GATE_RES);
         f8_out_bf16(ot, X_txt, h, S_t, S);
         f8_gate_res(ot, mod_txt + 2 * h, S_t, mod_stride, X_txt, h, S_t, S);
         DK_TRY(f8_pair(oi, &ot, st));
@@ -968,10 +981,10 @@ static int mmdit_blocks_fp8(dk_mmdit* m, const bf16_t* mod_step, int first, int 
       f8_out_bf16(f2i, X_img, h, S_i, S);
       f8_gate_res(f2i, mod_img + 5 * h, S_i, mod_stride, X_img, h, S_i, S);
       if (txt_post) {
-        GemmF8Params f1t = f8_params(m, m->XN8, m->SXN, h, Mi, Mt, 0, wt.fc1_w8, h, wt.fc1_ws, wt.fc1_b, Mt, r * h, h, DK_EPI_BIAS_GELU);
-        f1t.C = m->HC8 + (size_t)Mi * ldh8; f1t.ldc = ldh8; f1t.c_seg_len = Mt; f1t.c_mx8 = 1; f1t.SC = m->SHID; f1t.sc_nblk = m->nblk; f1t.c_row0 = Mi;
+        GemmF8Params f1t = f8_params(m, m->XN8, m->SXN, h, T0, Mt, 0, wt.fc1_w8, h, wt.fc1_ws, wt.fc1_b, Mt, r * h, h, DK_EPI_BIAS_GELU);
+        f1t.C = m->HC8 + (size_t)T0 * ldh8; f1t.ldc = ldh8; f1t.c_seg_len = Mt; f1t.c_mx8 = 1; f1t.SC = m->SHID; f1t.sc_nblk = m->nblk; f1t.c_row0 = T0;
         f1t.sc_kb0 = 0; f1t.r_seg_len = Mt; f1t.gate_seg_len = Mt;
-        GemmF8Params f2t = f8_params(m, m->HC8, m->SHID, ldh8, Mi, Mt, 0, wt.fc2_w8, ldh8, wt.fc2_ws, wt.fc2_b, Mt, h, r * h, DK_EPI_GATE_RES);
+        GemmF8Params f2t = f8_params(m, m->HC8, m->SHID, ldh8, T0, Mt, 0, wt.fc2_w8, ldh8, wt.fc2_ws, wt.fc2_b, Mt, h, r * h, DK_EPI_GATE_RES);
         f8_out_bf16(f2t, X_txt, h, S_t, S);
         f8_gate_res(f2t, mod_txt + 5 * h, S_t, mod_stride, X_txt, h, S_t, S);
         DK_TRY(f8_pair(f1i, &f1t, st));
@@ -984,7 +997,7 @@ static int mmdit_blocks_fp8(dk_mmdit* m, const bf16_t* mod_step, int first, int 
   }
   // UnifiedTransformerBlock x depth_unified (mmdit.py:693-751)
   const int M = B * S;
-  const Mx8Out xn_all = mx8_out(m->XN8, m->SXN, h, BS, 0, M, 0, 0);
+  const Mx8Out xn_all = mx8_out(m->XN8, m->SXN, h, R8, 0, M, 0, 0);  // (single blocks: the joint stream from row 0, any M)
   for (int i = 0; i < c.depth_unified; ++i) {
     if (c.depth_multimodal + i < first || c.depth_multimodal + i >= first + count) continue;
     const StreamW& w = m->single[i];

@@ -150,6 +150,11 @@ static Mx8Job mx8_none() {
 int dk_launch_quantize_mx8(const bf16_t* x, int ldx, int x_seg_len, int x_seg_stride, int M, int h, const Mx8Out& o, hipStream_t stream) {
   return launch_mx8_jobs(mx8_job(x, ldx, M, nullptr, nullptr, 8, 1, x_seg_len > 0 ? x_seg_len : M, x_seg_stride, o), mx8_none(), h, 0.f, false, stream);
 }
+int dk_launch_quantize2_mx8(const bf16_t* x0, int x_seg_len0, int M0, const Mx8Out& o0, const bf16_t* x1, int x_seg_len1, int M1, const Mx8Out& o1,
+                            int ldx, int x_seg_stride, int h, hipStream_t stream) {
+  return launch_mx8_jobs(mx8_job(x0, ldx, M0, nullptr, nullptr, 8, 1, x_seg_len0, x_seg_stride, o0),
+                         mx8_job(x1, ldx, M1, nullptr, nullptr, 8, 1, x_seg_len1, x_seg_stride, o1), h, 0.f, false, stream);
+}
 int dk_launch_ln_modulate_mx8(const bf16_t* x, int ldx, int M, int h, const bf16_t* shift, const bf16_t* scale, int mod_stride, int seg_len,
                               int x_seg_len, int x_seg_stride, float eps, const Mx8Out& o, hipStream_t stream) {
   DK_REQUIRE(shift && scale, "shift / scale missing");

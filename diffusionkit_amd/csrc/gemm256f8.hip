@@ -176,7 +176,7 @@ __global__ __launch_bounds__(512, 2) void dk_gemm256f8_kernel(GemmF8Params pa, G
 
   // E8M0 scales of this wave's 128 A rows for one K-tile: 8 bytes per lane (byte mf = row mf * 16 + l15, block q), one
   // coalesced 512-byte read per wave (layout: dk_mx_scale_index).  The wave's rows must be one aligned 128-row block of the
-  // physical buffer (checked by the launcher: segments and offsets are multiples of 128 rows).
+  // physical buffer (checked by the launcher: every row range starts at a multiple of 128 rows; its last block may be partial).
   // (clamped to the last row block of M: the second wave row of a tile whose rows end at m0 + 128 owns no rows -- its results are
   //  masked -- and must not read scale bytes past the caller's side array)
   const int mrow0 = m0 + wm * 128;
@@ -643,8 +643,11 @@ bool dk_gemm256f8_eligible(const GemmF8Params& p) {
   if (p.A == nullptr || p.W == nullptr || p.SA == nullptr || p.wscale == nullptr || p.C == nullptr) return false;
   if (p.n_split % 256 != 0 || (p.n_split > 0 && (p.C2 == nullptr || p.n_split >= p.N))) return false;
   if (p.a_seg_len <= 0 || p.c_seg_len <= 0) return false;
-  // scale reads: every wave's 128 rows are one aligned 128-row block of the A buffer
-  if (p.a_seg_len % 128 != 0 || p.a_seg_stride % 128 != 0 || p.a_row0 % 128 != 0 || p.sa_nblk <= 0) return false;
+  // scale reads: every wave's 128 rows are one aligned 128-row block of the A buffer -- every row range starts on a physical row that is a
+  // multiple of 128.  A range may END inside a block (its last block is partial: the DMA clamps to row M - 1, the tail masks rows >= M), so a
+  // launch that stays inside its first segment takes any M; only a map of several segments needs whole blocks per segment.
+  const bool a_one_seg = p.M <= p.a_seg_len;
+  if (p.a_row0 % 128 != 0 || p.sa_nblk <= 0 || (!a_one_seg && (p.a_seg_len % 128 != 0 || p.a_seg_stride % 128 != 0))) return false;
   const bool res1 = p.epi == DK_EPI_GATE_RES || p.epi == DK_EPI_RES;
   const bool res2 = p.n_split > 0 && (p.epi2 == DK_EPI_GATE_RES || p.epi2 == DK_EPI_RES);
   if ((res1 || res2) && (p.res == nullptr || p.r_seg_len <= 0 || p.ldr % 8 != 0)) return false;
@@ -654,9 +657,17 @@ bool dk_gemm256f8_eligible(const GemmF8Params& p) {
   auto al = [](const void* q, int a) { return ((uintptr_t)q & (uintptr_t)(a - 1)) == 0; };
   if (p.c_mx8 ? (p.ldc % 8 != 0 || !al(p.C, 8)) : (p.ldc % 8 != 0 || !al(p.C, 16))) return false;
   if (p.n_split > 0 && (p.c2_mx8 ? (p.ldc2 % 8 != 0 || !al(p.C2, 8)) : (p.ldc2 % 8 != 0 || !al(p.C2, 16)))) return false;
+  const bool c_one_seg = p.M <= p.c_seg_len;
   if ((p.c_mx8 || (p.n_split > 0 && p.c2_mx8)) &&
-      (p.SC == nullptr || p.sc_nblk <= 0 || p.c_seg_len % 128 != 0 || p.c_seg_stride % 128 != 0 || p.c_row0 % 128 != 0))
-    return false;  // (the tail stores a 128-row block's eight scale bytes as one word)
+      (p.SC == nullptr || p.sc_nblk <= 0 || p.c_row0 % 128 != 0 || (!c_one_seg && (p.c_seg_len % 128 != 0 || p.c_seg_stride % 128 != 0))))
+    return false;  // (the tail stores a whole 128-row block's eight scale bytes as one word; the rows of a last, partial block byte by byte)
+  // nothing is read or written past the scale side arrays: the last row block a wave touches lies inside sa_nblk / sc_nblk blocks
+  const long a_last = (long)p.a_row0 + (long)((p.M - 1) / p.a_seg_len) * p.a_seg_stride + (p.M - 1) % p.a_seg_len;
+  if ((a_last >> 7) >= p.sa_nblk) return false;
+  if (p.c_mx8 || (p.n_split > 0 && p.c2_mx8)) {
+    const long c_last = (long)p.c_row0 + (long)((p.M - 1) / p.c_seg_len) * p.c_seg_stride + (p.M - 1) % p.c_seg_len;
+    if ((c_last >> 7) >= p.sc_nblk) return false;
+  }
   if (!al(p.res, 16) || !al(p.bias, 16) || !al(p.gate, 16) || !al(p.wscale, 16) || (p.gate != nullptr && p.gate_stride % 8 != 0)) return false;
   // 32-bit byte offsets on the DMA side
   const size_t a_rows = (size_t)((p.M - 1) / p.a_seg_len) * p.a_seg_stride + (size_t)((p.M - 1) % p.a_seg_len) + 1;

@@ -353,10 +353,13 @@ def ln_modulate_mx8(x: Tensor, shift: Tensor, scale: Tensor, mod_seg_len: int = 
 
 def gemm_fp8(a8: Tensor, a_scales: Tensor, w8: Tensor, w_scale: Tensor, bias: Optional[Tensor] = None, epilogue: int = DK_EPI_BIAS,
              gate: Optional[Tensor] = None, res: Optional[Tensor] = None, gate_seg_len: int = 0, M: Optional[int] = None,
-             k: Optional[int] = None, out_mx8: bool = False, workspace: Optional[Tensor] = None):
-    """dk_gemm_fp8 over the first M rows / k columns of an MX-fp8 activation buffer a8 [rows, lda] and an e4m3 weight w8 [N, ldw].
-    Returns bf16 [M, N], or with ``out_mx8`` (e4m3 bytes [M, N], scale side array).  ``workspace`` (ops.gemm_workspace): lets a launch of at most
-    half a round of tiles with a long reduction be cut along K, as the engines do."""
+             k: Optional[int] = None, out_mx8: bool = False, workspace: Optional[Tensor] = None, out: Optional[Tensor] = None,
+             out_scales: Optional[Tensor] = None):
+    """dk_gemm_fp8 over the first M rows / k columns of an MX-fp8 activation buffer a8 [rows, lda] and an e4m3 weight w8 [N, ldw]; any M >= 1 (the
+    last 128-row scale block of a8 may be partial).  Returns bf16 [M, N], or with ``out_mx8`` (e4m3 bytes [M, N], scale side array).  ``workspace``
+    (ops.gemm_workspace): lets a launch of at most half a round of tiles with a long reduction be cut along K, as the engines do.  ``out`` (and, with
+    ``out_mx8``, ``out_scales`` = a side array of ops.mx_scale_bytes(out rows, out pitch)): an output buffer of at least M rows to write rows
+    [0, M) of; the other rows are left alone."""
     lib = _lib.load()
     for n, t, dt in (("a8", a8, torch.uint8), ("a_scales", a_scales, torch.uint8), ("w8", w8, torch.uint8), ("w_scale", w_scale, torch.float32)):
         _require_cuda(t, n, dt)
@@ -375,13 +378,24 @@ def gemm_fp8(a8: Tensor, a_scales: Tensor, w8: Tensor, w_scale: Tensor, bias: Op
     d.epilogue = epilogue
     if workspace is not None:
         d.workspace, d.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    if out is not None:
+        _require_cuda(out, "out", torch.uint8 if out_mx8 else BF)
+        if out.dim() != 2 or out.shape[0] < M or out.shape[1] < N or out.stride(1) != 1:
+            raise ValueError(f"out must be a [>= {M}, >= {N}] matrix with contiguous rows")
     if out_mx8:
-        out = torch.zeros(M, N, dtype=torch.uint8, device=a8.device)
-        sc = torch.zeros(mx_scale_bytes(M, N), dtype=torch.uint8, device=a8.device)
-        d.C, d.ldc, d.c_mx8, d.C_scales, d.c_rows, d.c_row0, d.c_col0 = out.data_ptr(), N, 1, sc.data_ptr(), M, 0, 0
+        if out is None:
+            out = torch.zeros(M, N, dtype=torch.uint8, device=a8.device)
+        sc = out_scales
+        if sc is None:
+            sc = torch.zeros(mx_scale_bytes(out.shape[0], out.stride(0)), dtype=torch.uint8, device=a8.device)
+        _require_cuda(sc, "out_scales", torch.uint8)
+        if sc.numel() < mx_scale_bytes(out.shape[0], out.stride(0)):
+            raise ValueError("out_scales is smaller than ops.mx_scale_bytes(out rows, out pitch)")
+        d.C, d.ldc, d.c_mx8, d.C_scales, d.c_rows, d.c_row0, d.c_col0 = out.data_ptr(), out.stride(0), 1, sc.data_ptr(), out.shape[0], 0, 0
         _lib.check(lib.dk_gemm_fp8(C.byref(d), _stream()), "dk_gemm_fp8")
         return out, sc
-    out = torch.empty(M, N, dtype=BF, device=a8.device)
-    d.C, d.ldc = out.data_ptr(), N
+    if out is None:
+        out = torch.empty(M, N, dtype=BF, device=a8.device)
+    d.C, d.ldc = out.data_ptr(), out.stride(0)
     _lib.check(lib.dk_gemm_fp8(C.byref(d), _stream()), "dk_gemm_fp8")
     return out

@@ -187,7 +187,7 @@ int dk_attention_bf16(const void* q, const void* k, const void* v, void* out, in
  *   QKNorm + RoPE of the QUERIES inside the kernel's Q load (the keys keep their own pass): token s < qn_split of every batch row is normalised with
  *     qn_a [D], the others with qn_b (both NULL: no norm), eps qn_eps, and rotated by q_rope (f32 [S, D / 2, 2] indexed by s; NULL: no rotation);
  *   O8 (NULL: none): an MX-fp8 copy of the output, row b * S + s at o8_ld bytes per row, head h at byte column h * D, E8M0 scales in O8_scales
- *     (dk_mx_scale_bytes(o8_rows, o8_ld) bytes; B * S a multiple of 128) -- exactly dk_quantize_mx8 of the bf16 output.  The D = 128 kernels of
+ *     (dk_mx_scale_bytes(o8_rows, o8_ld) bytes; any B * S <= o8_rows) -- exactly dk_quantize_mx8 of the bf16 output.  The D = 128 kernels of
  *     "attn" 9 / 10 write it from their accumulators INSTEAD of `out`, which they then leave untouched; the others write `out` and quantise it. */
 typedef struct dk_attention_desc {
   const void* q;
@@ -268,14 +268,15 @@ typedef struct dk_gemm_fp8_desc {
   const void* res;
   int32_t M, N, K;      /* N % 256 == 0, K % 128 == 0                                                                    */
   int32_t lda, ldw, ldc, ldr;
-  int32_t a_seg_len, a_seg_stride; /* multiples of 128 rows                                                              */
-  int32_t a_row0;       /* physical row of its buffer that A points at (multiple of 128)                                 */
+  int32_t a_seg_len, a_seg_stride; /* M <= a_seg_len (one segment, 0: that): any M; several segments: multiples of 128  */
+  int32_t a_row0;       /* physical row of its buffer that A points at (multiple of 128: a row range starts on a scale  */
+                        /* block of 128 rows; it may end inside one)                                                     */
   int32_t a_rows;       /* rows of the buffer A points into (sizes its scale array)                                      */
   int32_t c_seg_len, c_seg_stride;
   int32_t r_seg_len, r_seg_stride;
   int32_t gate_seg_len, gate_stride;
   int32_t epilogue;     /* DK_EPI_*                                                                                      */
-  int32_t c_mx8;        /* 1: MX-fp8 output (M % 256 == 0)                                                               */
+  int32_t c_mx8;        /* 1: MX-fp8 output (any M; c_row0 % 128 == 0; c_seg_len, c_seg_stride as a_seg_len, a_seg_stride) */
   void* C_scales;
   int32_t c_rows, c_row0, c_col0; /* rows of the output buffer, physical row / column (multiple of 32) that C points at  */
   /* ABI 5: optional K-split scratch, the same buffer and rules as dk_gemm_desc.workspace (dk_gemm_workspace_bytes() bytes, 256-byte aligned, last
@@ -380,8 +381,8 @@ typedef struct dk_mmdit_config {
   /* 1: the Linear layers of the transformer blocks (q/k/v, o_proj, fc1, fc2, linear1, linear2) run on the fp8 MFMA with
    * e4m3 weights ("<name>.weight_fp8" uint8 [N, dk_weight_pitch_fp8(K)] + "<name>.wscale" f32 [N] instead of
    * "<name>.weight") and MX-fp8 activations quantised on the fly (BASELINE.json configs[3]; the reference's counterpart is
-   * its 4-bit nn.QuantizedLinear checkpoints, model_io.py:728-734,772-775).  Needs head_dim 128 and text / image token
-   * counts that are multiples of 128.  0: bf16 weights. */
+   * its 4-bit nn.QuantizedLinear checkpoints, model_io.py:728-734,772-775).  Needs head_dim 128 and a text length that is
+   * one of the multiples of 128; the image token count is free (dk_mmdit_prepare).  0: bf16 weights. */
   int32_t fp8_linears;
   /* fp8 precision policy (round 5; only read with fp8_linears): the Linears of the first fp8_bf16_double_blocks double-stream blocks
    * stay bf16 ("<name>.weight", bf16 activations, the bf16 GEMM): errors made in the first blocks travel through all 57 -- measured
