@@ -160,6 +160,17 @@ SIGNATURES = {
     "dk_ln_modulate_mx8": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _f32, _vp, _i32, _vp, _i64, _i32, _vp]),
     "dk_weight_pitch_fp8": (_i32, [_i32]),
     "dk_mmdit_set_guidance": (_i32, [_vp, _f32]),
+    # float16 element type (SD3 family): siblings of the bf16 operators, same descriptors
+    "dk_gemm_f16": (_i32, [C.POINTER(dk_gemm_desc), _vp]),
+    "dk_gemm_plan_f16": (_i32, [C.POINTER(dk_gemm_desc), C.POINTER(dk_gemm_desc), C.POINTER(dk_gemm_plan_t)]),
+    "dk_gemm_fused_f16": (_i32, [C.POINTER(dk_gemm_desc), C.POINTER(dk_gemm_side), C.POINTER(dk_gemm_desc), C.POINTER(dk_gemm_side), _vp]),
+    "dk_attention_desc_f16": (_i32, [C.POINTER(dk_attention_desc), _vp]),
+    "dk_ln_modulate_f16": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp]),
+    "dk_qk_norm_rope_f16": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _f32, _vp, _i32, _i32, _i32, _vp]),
+    "dk_timestep_embedding_f16": (_i32, [_vp, _i32, _i32, _f32, _i32, _vp, _vp]),
+    "dk_latent_to_tokens_f16": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "dk_euler_cfg_step_f16": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _vp]),
+    "dk_mmdit_set_activation_dtype": (_i32, [_vp, _i32]),
     "dk_ln_modulate_bf16": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp]),
     "dk_qk_norm_rope_bf16": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _f32, _vp, _i32, _i32, _i32, _vp]),
     "dk_rope_table_f32": (_i32, [_vp, _i32, _i32, _i32, C.POINTER(_i32), _i32, _f32, _vp]),

@@ -59,6 +59,9 @@ def build_parser(model_versions: Sequence[str]) -> argparse.ArgumentParser:
     p.add_argument("--fp8", choices=("quality", "speed"), default=None,
                    help="Run the transformer blocks on the fp8 MFMA path (FLUX versions only). quality: the first double-stream "
                         "blocks keep bf16 Linears; speed: every block Linear in fp8.")
+    p.add_argument("--activation-dtype", choices=("bfloat16", "float16"), default="bfloat16",
+                   help="Element type of the MMDiT's weights and activations. float16 is the reference's dtype for Stable Diffusion 3 "
+                        "(SD3 versions only); the text encoders and the VAE stay bfloat16.")
     p.add_argument("--device", default=None, help="HIP device, e.g. cuda:0 (default: the current device)")
     return p
 
@@ -94,6 +97,11 @@ def resolve(args) -> dict:
         # (config.fp8_config raises a ValueError for the SD3 geometries: head_dim 64)
         from .config import MODEL_CONFIG, fp8_config
         r["mmdit_config"] = fp8_config(MODEL_CONFIG[args.model_version], args.fp8)
+    if getattr(args, "activation_dtype", "bfloat16") != "bfloat16":
+        # (config.float16_config raises a ValueError for the FLUX geometries and together with --fp8)
+        from .config import MODEL_CONFIG, float16_config
+        float16_config(r.get("mmdit_config", MODEL_CONFIG[args.model_version]))
+        r["activation_dtype"] = args.activation_dtype
     return r
 
 
@@ -110,6 +118,8 @@ def main(argv: Optional[Sequence[str]] = None, pipeline_overrides: Optional[dict
     if args.fp8:  # (a config of the caller's is put on the fp8 path like the model version's own)
         from .config import fp8_config
         extra["mmdit_config"] = fp8_config(extra["mmdit_config"], args.fp8) if extra.get("mmdit_config") is not None else r["mmdit_config"]
+    if "activation_dtype" in r:
+        extra["activation_dtype"] = r["activation_dtype"]
     sd = pipeline_class(w16=True, shift=r["shift"], use_t5=args.t5, model_version=args.model_version,
                         low_memory_mode=r["low_memory_mode"], a16=True, local_ckpt=checkpoint_dict(args.local_ckpt, args.ckpt),
                         device=args.device, **extra)

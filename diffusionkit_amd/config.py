@@ -52,6 +52,9 @@ class MMDiTConfig:
     # fp8 precision policy (only read with weight_dtype = "fp8_e4m3"): the Linears of the first n double-stream blocks stay bf16 --
     # an error made in the first blocks travels through all the others (measured dB per block: DESIGN.md section 4)
     fp8_bf16_double_blocks: int = 0
+    # element type of the MMDiT's weights, activations and token / text / pooled I/O: "bfloat16", or "float16" -- the reference's dtype for
+    # Stable Diffusion 3 (config.py:77-79); SD3-family geometry only (validate_activation_dtype)
+    activation_dtype: str = "bfloat16"
 
     @property
     def hidden_size(self) -> int:
@@ -94,7 +97,7 @@ class MMDiTConfig:
         return n
 
 
-# reference config.py:78-80 (fp16 there; this build computes in bf16 on MI355X)
+# reference config.py:78-80 (fp16 there; bf16 here by default, float16_config(SD3_2b) runs it in the reference's dtype)
 SD3_2b = MMDiTConfig(depth_multimodal=24, num_heads=24, dtype="float16")
 
 # reference config.py:74-76
@@ -138,6 +141,28 @@ def fp8_config(cfg: MMDiTConfig, policy: str = "quality") -> MMDiTConfig:
     n = min(FLUX_FP8_QUALITY_BLOCKS, cfg.depth_multimodal) if policy == "quality" else 0
     out = replace(cfg, weight_dtype="fp8_e4m3", fp8_bf16_double_blocks=n)
     validate_fp8_policy(out)
+    return out
+
+
+def validate_activation_dtype(cfg: MMDiTConfig) -> None:
+    """``activation_dtype`` is "bfloat16" or "float16"; float16 is the SD3 family's: head_dim == 64, depth_unified == 0 and no fp8 Linears
+    (the rule dk_mmdit_set_activation_dtype enforces -- the D = 128 attention kernels, the single-stream blocks' fused launches and the fp8 path
+    are bf16 only)."""
+    if cfg.activation_dtype not in ("bfloat16", "float16"):
+        raise ValueError(f"unknown activation_dtype {cfg.activation_dtype!r} (bfloat16 | float16)")
+    if cfg.activation_dtype == "bfloat16":
+        return
+    if cfg.head_dim != 64 or cfg.depth_unified != 0:
+        raise ValueError(f"activation_dtype float16 needs SD3-family geometry: head_dim == 64 and depth_unified == 0 "
+                         f"(got head_dim {cfg.head_dim}, depth_unified {cfg.depth_unified})")
+    if cfg.weight_dtype == "fp8_e4m3":
+        raise ValueError("activation_dtype float16 cannot be combined with weight_dtype fp8_e4m3 (the fp8 path's activations are bf16 / MX-fp8)")
+
+
+def float16_config(cfg: MMDiTConfig) -> MMDiTConfig:
+    """``cfg`` with float16 weights and activations (the reference's dtype for SD3); raises ValueError for any other family."""
+    out = replace(cfg, activation_dtype="float16")
+    validate_activation_dtype(out)
     return out
 
 

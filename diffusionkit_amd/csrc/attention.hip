@@ -42,6 +42,10 @@ int dk_launch_attention(const AttnParams& p_in, hipStream_t stream) {
   const long blocks5 = (long)p.B * p.H * ((p.S + 255) / 256);
   const bool long5 = p.D == 128 && (p.S >= 2048 || (p.S >= 1024 && blocks5 * 4 >= 3L * dk_device_cu_count()));
   int mode = p.bias != nullptr ? 4 : g_dk_attn_mode < 0 ? (long5 ? 10 : 4) : g_dk_attn_mode;
+  if (p.dtype != DK_DTYPE_BF16) {  // fp16 (SD3 family): the lean kernel, whatever dk_tune_set("attn", 9 / 10) names -- those kernels are bf16 only
+    DK_REQUIRE(p.dtype == DK_DTYPE_F16 && p.D == 64 && p.bias == nullptr && p.O8 == nullptr, "fp16 attention: head_dim 64, no score bias, no MX-fp8 copy");
+    mode = 4;
+  }
   if (mode == 10 && !dk_attention5_eligible(p)) mode = 9;
   if (p.O8 != nullptr && p.o8_split != 0) {
     DK_REQUIRE(p.o8_split > 0 && p.o8_split < p.S && p.o8_txt_row0 >= p.B * (p.S - p.o8_split), "MX-fp8 copy: text rows behind the image rows");

@@ -72,12 +72,12 @@ __global__ __launch_bounds__(NW * 64, 2) void dk_attn2_fwd_kernel(AttnParams p) 
   const unsigned row_bytes = (unsigned)p.ld * 2u;
 
   // Q fragments (B operand of S^T = K Q^T): lane holds Q[q0 + l31][kk*16 + hi*8 .. +7]
-  bf16x8 qf[D / 16];
+  ex8 qf[D / 16];
   {
     const int qrow = min(q0 + l31, S - 1);
     const bf16_t* qp = Qb + (size_t)qrow * p.ld + hi * 8;
 #pragma unroll
-    for (int kk = 0; kk < D / 16; ++kk) qf[kk] = *(const bf16x8*)(qp + kk * 16);
+    for (int kk = 0; kk < D / 16; ++kk) qf[kk] = *(const ex8*)(qp + kk * 16);
     if (QFUSE) {
       // QKNorm + RoPE of this lane's query row on the fly (same fp32 arithmetic and bf16 rounding points as
       // dk_qk_norm_rope_kernel): the lane and its partner (lane ^ 32) hold the two halves of every 16-element group
@@ -97,9 +97,9 @@ __global__ __launch_bounds__(NW * 64, 2) void dk_attn2_fwd_kernel(AttnParams p) 
         const bf16_t* w = (qrow < p.qn_split ? p.qn_a : p.qn_b) + hi * 8;
 #pragma unroll
         for (int kk = 0; kk < D / 16; ++kk) {
-          const bf16x8 wv = *(const bf16x8*)(w + kk * 16);
+          const ex8 wv = *(const ex8*)(w + kk * 16);
 #pragma unroll
-          for (int e = 0; e < 8; ++e) v[kk][e] = round_bf16(v[kk][e] * r * (float)wv[e]);
+          for (int e = 0; e < 8; ++e) v[kk][e] = round_act(v[kk][e] * r * (float)wv[e]);
         }
       }
       if (p.q_rope != nullptr) {
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(NW * 64, 2) void dk_attn2_fwd_kernel(AttnParams p) 
 #pragma unroll
       for (int kk = 0; kk < D / 16; ++kk)
 #pragma unroll
-        for (int e = 0; e < 8; ++e) qf[kk][e] = (__bf16)v[kk][e];
+        for (int e = 0; e < 8; ++e) qf[kk][e] = (elem_s)v[kk][e];
     }
   }
 
@@ -205,10 +205,10 @@ __global__ __launch_bounds__(NW * 64, 2) void dk_attn2_fwd_kernel(AttnParams p) 
     _Pragma("unroll") for (int e = 0; e < 16; ++e) { s0[e] = 0.f; s1[e] = 0.f; }                           \
     __builtin_amdgcn_s_setprio(1);                                                                         \
     _Pragma("unroll") for (int kk = 0; kk < D / 16; ++kk) {                                                \
-      const bf16x8 k0 = *(const __attribute__((address_space(3))) bf16x8*)(lds + K_OFF + (BUF) * C::TILE_BYTES + kr_off[kk]); \
-      const bf16x8 k1 = *(const __attribute__((address_space(3))) bf16x8*)(lds + K_OFF + (BUF) * C::TILE_BYTES + 32 * C::ROWB + kr_off[kk]); \
-      s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k0, qf[kk], s0, 0, 0, 0);                               \
-      s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k1, qf[kk], s1, 0, 0, 0);                               \
+      const ex8 k0 = *(const __attribute__((address_space(3))) ex8*)(lds + K_OFF + (BUF) * C::TILE_BYTES + kr_off[kk]); \
+      const ex8 k1 = *(const __attribute__((address_space(3))) ex8*)(lds + K_OFF + (BUF) * C::TILE_BYTES + 32 * C::ROWB + kr_off[kk]); \
+      s0 = mfma_32x32x16(k0, qf[kk], s0);                               \
+      s1 = mfma_32x32x16(k1, qf[kk], s1);                               \
     }                                                                                                      \
     __builtin_amdgcn_s_setprio(0);                                                                         \
     if (j_ * 64 + 64 > S) {                                                                                \
@@ -224,8 +224,8 @@ __global__ __launch_bounds__(NW * 64, 2) void dk_attn2_fwd_kernel(AttnParams p) 
         const uint2 b0 = *(const uint2*)(bias_row + j_ * 64 + 8 * g4 + 4 * hi);                             \
         const uint2 b1 = *(const uint2*)(bias_row + j_ * 64 + 32 + 8 * g4 + 4 * hi);                        \
         float f0[4], f1[4];                                                                                \
-        unpack2bf(b0.x, f0[0], f0[1]); unpack2bf(b0.y, f0[2], f0[3]);                                      \
-        unpack2bf(b1.x, f1[0], f1[1]); unpack2bf(b1.y, f1[2], f1[3]);                                      \
+        unpack2(b0.x, f0[0], f0[1]); unpack2(b0.y, f0[2], f0[3]);                                      \
+        unpack2(b1.x, f1[0], f1[1]); unpack2(b1.y, f1[2], f1[3]);                                      \
         _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                                    \
           s0[4 * g4 + e] += f0[e] * inv_scale;                                                             \
           s1[4 * g4 + e] += f1[e] * inv_scale;                                                             \
@@ -253,14 +253,14 @@ __global__ __launch_bounds__(NW * 64, 2) void dk_attn2_fwd_kernel(AttnParams p) 
     __builtin_amdgcn_s_setprio(1);                                                                         \
     _Pragma("unroll") for (int u = 0; u < 2; ++u) {                                                        \
       _Pragma("unroll") for (int tt = 0; tt < 2; ++tt) {                                                   \
-        bf16x8 pf;                                                                                         \
-        _Pragma("unroll") for (int e = 0; e < 8; ++e) pf[e] = (__bf16)(u == 0 ? s0[8 * tt + e] : s1[8 * tt + e]); \
+        ex8 pf;                                                                                         \
+        _Pragma("unroll") for (int e = 0; e < 8; ++e) pf[e] = (elem_s)(u == 0 ? s0[8 * tt + e] : s1[8 * tt + e]); \
         _Pragma("unroll") for (int dt = 0; dt < D / 32; ++dt) {                                            \
           const int imm = V_OFF + (BUF) * C::TILE_BYTES + dt * 4096 + (32 * u + 16 * tt) * 32;             \
           const s16x4 vh0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(lds + imm + vr_off[dt & 1])); \
           const s16x4 vh1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(lds + imm + 256 + vr_off[dt & 1])); \
-          const bf16x8 vf = __builtin_bit_cast(bf16x8, __builtin_shufflevector(vh0, vh1, 0, 1, 2, 3, 4, 5, 6, 7)); \
-          o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, o[dt], 0, 0, 0);                         \
+          const ex8 vf = __builtin_bit_cast(ex8, __builtin_shufflevector(vh0, vh1, 0, 1, 2, 3, 4, 5, 6, 7)); \
+          o[dt] = mfma_32x32x16(vf, pf, o[dt]);                         \
         }                                                                                                  \
       }                                                                                                    \
     }                                                                                                      \
@@ -289,8 +289,8 @@ __global__ __launch_bounds__(NW * 64, 2) void dk_attn2_fwd_kernel(AttnParams p) 
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
         uint2 w;
-        w.x = pack2bf(o[dt][4 * g4 + 0] * inv, o[dt][4 * g4 + 1] * inv);
-        w.y = pack2bf(o[dt][4 * g4 + 2] * inv, o[dt][4 * g4 + 3] * inv);
+        w.x = pack2(o[dt][4 * g4 + 0] * inv, o[dt][4 * g4 + 1] * inv);
+        w.y = pack2(o[dt][4 * g4 + 2] * inv, o[dt][4 * g4 + 3] * inv);
         *(uint2*)(op + dt * 32 + 8 * g4 + 4 * hi) = w;
       }
   }
@@ -321,9 +321,22 @@ int dk_launch_attention2_d128(const AttnParams& p, hipStream_t stream) {  // (ar
   if (p.qn_a != nullptr || p.q_rope != nullptr) return launch_attn2<128, 4, false, true>(p, stream);
   return launch_attn2<128, 4>(p, stream);
 }
+#elif defined(DK_ELEM_F16)
+// attention2_f16.hip: this file compiled inside namespace dk_f16 -- the D = 64 forms on IEEE-half operands (scores, running maximum and sum in
+// fp32 as before; P rounded to fp16 for the P.V MFMA: P <= e^DK_RESCALE_THR under the deferred rescale, far inside fp16's range)
+int dk_launch_attention2(const AttnParams& p, int waves, hipStream_t stream) {
+  DK_REQUIRE((size_t)p.S * p.ld * 2 < (1ull << 32), "attention2: one batch row of QKV must span < 4 GiB");
+  DK_REQUIRE(p.D == 64 && p.bias == nullptr && p.O8 == nullptr && waves == 4, "attention2 (fp16): head_dim 64, no score bias, no MX-fp8 copy");
+  if (p.qn_a != nullptr || p.q_rope != nullptr) {
+    DK_REQUIRE(p.qn_a == nullptr || p.qn_b != nullptr, "qn_b missing (pass qn_a twice for one weight)");
+    return launch_attn2<64, 4, false, true>(p, stream);
+  }
+  return launch_attn2<64, 4>(p, stream);
+}
 #else
 int dk_launch_attention2_d128(const AttnParams& p, hipStream_t stream);  // attention2p.hip
 int dk_launch_attention2(const AttnParams& p, int waves, hipStream_t stream) {
+  if (p.dtype == DK_DTYPE_F16) return dk_f16::dk_launch_attention2(p, waves, stream);
   DK_REQUIRE((size_t)p.S * p.ld * 2 < (1ull << 32), "attention2: one batch row of QKV must span < 4 GiB");
   if (p.bias != nullptr) {  // text encoders: D = 64, short sequences
     DK_REQUIRE(p.ldb % 64 == 0 && p.ldb >= p.S && ((uintptr_t)p.bias & 7) == 0 && p.bias_head_stride % 4 == 0,

@@ -32,6 +32,44 @@ __device__ __forceinline__ void unpack2bf(uint32_t v, float& lo, float& hi) {
   hi = __uint_as_float(v & 0xffff0000u);
 }
 
+// ---- element-type layer ------------------------------------------------------------------------------------
+// The kernels on SD3's path (gemm.hip, gemm256v3.hip, attention2.hip, elementwise.hip) are written on these names instead of the bf16
+// helpers above: 16-bit storage (bf16_t is the raw halfword of either type), fp32 accumulation, one rounding per store.  At global scope
+// they ARE the bf16 helpers.  Inside namespace dk_f16 the same names mean IEEE half: the *_f16.hip translation units include a kernel's
+// source inside that namespace, so every kernel has one text and two instantiations, and the bf16 objects compile from the same tokens
+// as before.  An fp32 -> fp16 store that overflows gives +-inf (v_cvt_f16_f32, round to nearest even), as the reference's casts do.
+#define DK_DTYPE_BF16 0
+#define DK_DTYPE_F16 1
+typedef __bf16 elem_s;  // scalar element as the compiler's arithmetic type: (elem_s)x rounds an fp32 value to the element type
+typedef bf16x8 ex8;     // 8-wide MFMA operand
+__device__ __forceinline__ float to_f32(bf16_t v) { return bf2f(v); }
+__device__ __forceinline__ bf16_t from_f32(float f) { return f2bf(f); }
+__device__ __forceinline__ float round_act(float f) { return round_bf16(f); }
+__device__ __forceinline__ uint32_t pack2(float lo, float hi) { return pack2bf(lo, hi); }
+__device__ __forceinline__ void unpack2(uint32_t v, float& lo, float& hi) { unpack2bf(v, lo, hi); }
+__device__ __forceinline__ f32x16 mfma_32x32x16(ex8 a, ex8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ f32x4 mfma_16x16x32(ex8 a, ex8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+
+namespace dk_f16 {
+typedef _Float16 elem_s;
+typedef _Float16 ex8 __attribute__((ext_vector_type(8)));
+typedef _Float16 dk_f16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float to_f32(bf16_t v) { return (float)__builtin_bit_cast(_Float16, v); }
+__device__ __forceinline__ bf16_t from_f32(float f) { return __builtin_bit_cast(bf16_t, (_Float16)f); }
+__device__ __forceinline__ float round_act(float f) { return (float)(_Float16)f; }
+__device__ __forceinline__ uint32_t pack2(float lo, float hi) {
+  const dk_f16x2 v = {(_Float16)lo, (_Float16)hi};
+  return __builtin_bit_cast(uint32_t, v);
+}
+__device__ __forceinline__ void unpack2(uint32_t v, float& lo, float& hi) {
+  const dk_f16x2 h = __builtin_bit_cast(dk_f16x2, v);
+  lo = (float)h[0];
+  hi = (float)h[1];
+}
+__device__ __forceinline__ f32x16 mfma_32x32x16(ex8 a, ex8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ f32x4 mfma_16x16x32(ex8 a, ex8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
+}  // namespace dk_f16
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -1,0 +1,34 @@
+// Launchers that exist once per element type (dk_common.h, element-type layer): dk_kernels.h includes this file at global scope (bf16) and
+// again inside namespace dk_f16 (fp16) -- same signatures, 16-bit storage either way (bf16_t = the raw halfword).  No include guard.
+// The global gemm / attention launchers forward to their dk_f16 twin on GemmParams::dtype / AttnParams::dtype; the elementwise ones are
+// picked by the caller.
+int dk_launch_gemm128(const GemmParams& p, const GemmRoute& r, hipStream_t stream);  // gemm.hip: 128 x 128 tiles
+int dk_launch_gemm256v3(const GemmParams& p, const GemmParams* p2, const GemmRoute& r, hipStream_t stream);  // (16x16x32 MFMA K loop)
+int dk_launch_attention2(const AttnParams& p, int waves, hipStream_t stream);  // attention2.hip (VALU-lean variant)
+// out[m, :] = bf16( LN(x[m, :]) * bf16(1 + scale[b, :]) + shift[b, :] ), b = m / seg_len
+int dk_launch_ln_modulate(const bf16_t* x, int ldx, bf16_t* out, int ldo, int M, int h,
+                          const bf16_t* shift, const bf16_t* scale, int mod_stride, int seg_len,
+                          int x_seg_len, int x_seg_stride, float eps, hipStream_t stream);
+// in-place per-head RMSNorm (learned weight) + RoPE on the q and k column groups of a QKV buffer
+int dk_launch_qk_norm_rope(bf16_t* qkv, int ld, int q_off, int k_off, int rows, int H, int D,
+                           const bf16_t* qw, const bf16_t* kw, float eps, const float* rope,
+                           int row_seg_len, int row_seg_stride, int pos_off, int S_pos,
+                           hipStream_t stream, int k_only = 0);
+// two row sets (image / text stream of a double block) per launch
+int dk_launch_ln_modulate2(const bf16_t* x0, bf16_t* out0, int M0, const bf16_t* shift0, const bf16_t* scale0, int seg0, const bf16_t* x1,
+                           bf16_t* out1, int M1, const bf16_t* shift1, const bf16_t* scale1, int seg1, int ldx, int ldo, int h,
+                           int mod_stride, int x_seg_stride, float eps, hipStream_t stream);
+int dk_launch_qk_norm_rope2(bf16_t* qkv0, int rows0, const bf16_t* qw0, const bf16_t* kw0, int seg0, int pos0, bf16_t* qkv1, int rows1,
+                            const bf16_t* qw1, const bf16_t* kw1, int seg1, int pos1, int ld, int q_off, int k_off, int H, int D,
+                            float eps, const float* rope, int row_seg_stride, hipStream_t stream, int k_only = 0);
+int dk_launch_silu(const bf16_t* x, bf16_t* y, long n, hipStream_t stream);
+int dk_launch_add(const bf16_t* a, const bf16_t* b, int b_rows, bf16_t* y, int rows, int cols, hipStream_t stream);
+int dk_launch_timestep_embedding(const float* t, int n, int rep, int dim, float max_period, int embed_dtype,
+                                 bf16_t* out, hipStream_t stream);
+// latent [n_img, Hl, Wl, C] fp32 -> tokens [B, S_i, p*p*C] bf16 (B = n_img * dup)
+int dk_launch_latent_to_tokens(const float* x, bf16_t* tok, int n_img, int dup, int Hl, int Wl, int C, int p,
+                               int reshape_order, hipStream_t stream);
+// fused x0-prediction + CFG + Euler update (+ re-patchify for the next step)
+int dk_launch_euler_step(float* x, const bf16_t* model_out, int ld_out, bf16_t* tok, int n_img, int cfg_on,
+                         int Hl, int Wl, int C, int p, int reshape_order, float sigma, float sigma_next,
+                         float cfg_weight, hipStream_t stream);

@@ -55,6 +55,9 @@ struct GemmParams {
   // attention kernel then loads finished queries.  Needs kn_w; null qn_w: queries untouched
   const bf16_t* qn_w;
   int qn_col0, qn_col1;
+  // element type of A, W, C, bias, gate, res and the norm weights: DK_DTYPE_BF16 (0) or DK_DTYPE_F16 (1: Linears on the 128^2 kernel and
+  // gemm256v3.hip only -- the route never names gemm256v4.hip)
+  int dtype;
 };
 int dk_launch_gemm(const GemmParams& p, hipStream_t stream);
 // two problems with the same N, K, epilogue in one launch (image + text stream of a double block); falls
@@ -102,7 +105,6 @@ int dk_gemm_plan_call(const GemmParams& p, const GemmParams* p2, dk_gemm_plan_t&
 // leave it zero)
 size_t dk_gemm_split_workspace_bytes();
 bool dk_gemm256v3_eligible(const GemmParams& p);  // N % 128 == 0, K % 64 == 0, any M, any row-segment maps
-int dk_launch_gemm256v3(const GemmParams& p, const GemmParams* p2, const GemmRoute& r, hipStream_t stream);  // (16x16x32 MFMA K loop)
 // gemm256v4.hip: one wave per SIMD, 256 accumulators in AGPRs, hand-scheduled asm body (N % 256 == 0, no conv / K split / half tiles)
 bool dk_gemm256v4_eligible(const GemmParams& p);
 int dk_launch_gemm256v4(const GemmParams& p, const GemmParams* p2, const GemmRoute& r, hipStream_t stream);
@@ -223,13 +225,14 @@ struct AttnParams {
   // a block of the last, partial round of the CUs and leave (O / l in bf16, offset, l) in a5_ws for dk_attn5_merge_kernel
   int a5_whole = 0, a5_split = 1;
   void* a5_ws = nullptr;
+  // element type of Q, K, V, O and the query-norm weights: DK_DTYPE_BF16 (0) or DK_DTYPE_F16 (1: D = 64, the lean kernel)
+  int dtype = 0;
 };
 void dk_set_attention_workspace(void* ws, size_t bytes = 0);  // attention.hip: thread-local workspace, picked up by dk_launch_attention
 void* dk_get_attention_workspace();
 size_t dk_get_attention_workspace_bytes();
 extern int g_dk_attn_mode;
 int dk_launch_attention(const AttnParams& p, hipStream_t stream);
-int dk_launch_attention2(const AttnParams& p, int waves, hipStream_t stream);  // attention2.hip (VALU-lean variant)
 int dk_launch_attention4(const AttnParams& p, hipStream_t stream);             // attention4.hip (the waves of a SIMD in opposite phases; D = 128, no score bias)
 bool dk_attention5_eligible(const AttnParams& p);                              // attention5.hip (one wave per SIMD, asm tile loop; D = 128, S % 256 == 0, no score bias)
 int dk_launch_attention5(const AttnParams& p, hipStream_t stream);
@@ -255,37 +258,16 @@ int dk_launch_text_elementwise(const bf16_t* a, const bf16_t* b, bf16_t* y, floa
 int dk_launch_t5_bias(const bf16_t* emb, const int* rel_bucket, int H, int S, int ld, bf16_t* out, hipStream_t stream);
 
 // ---- elementwise / normalisation ---------------------------------------------------------
-// out[m, :] = bf16( LN(x[m, :]) * bf16(1 + scale[b, :]) + shift[b, :] ), b = m / seg_len
-int dk_launch_ln_modulate(const bf16_t* x, int ldx, bf16_t* out, int ldo, int M, int h,
-                          const bf16_t* shift, const bf16_t* scale, int mod_stride, int seg_len,
-                          int x_seg_len, int x_seg_stride, float eps, hipStream_t stream);
-// in-place per-head RMSNorm (learned weight) + RoPE on the q and k column groups of a QKV buffer
-int dk_launch_qk_norm_rope(bf16_t* qkv, int ld, int q_off, int k_off, int rows, int H, int D,
-                           const bf16_t* qw, const bf16_t* kw, float eps, const float* rope,
-                           int row_seg_len, int row_seg_stride, int pos_off, int S_pos,
-                           hipStream_t stream, int k_only = 0);
-// two row sets (image / text stream of a double block) per launch
-int dk_launch_ln_modulate2(const bf16_t* x0, bf16_t* out0, int M0, const bf16_t* shift0, const bf16_t* scale0, int seg0, const bf16_t* x1,
-                           bf16_t* out1, int M1, const bf16_t* shift1, const bf16_t* scale1, int seg1, int ldx, int ldo, int h,
-                           int mod_stride, int x_seg_stride, float eps, hipStream_t stream);
-int dk_launch_qk_norm_rope2(bf16_t* qkv0, int rows0, const bf16_t* qw0, const bf16_t* kw0, int seg0, int pos0, bf16_t* qkv1, int rows1,
-                            const bf16_t* qw1, const bf16_t* kw1, int seg1, int pos1, int ld, int q_off, int k_off, int H, int D,
-                            float eps, const float* rope, int row_seg_stride, hipStream_t stream, int k_only = 0);
-int dk_launch_silu(const bf16_t* x, bf16_t* y, long n, hipStream_t stream);
-int dk_launch_add(const bf16_t* a, const bf16_t* b, int b_rows, bf16_t* y, int rows, int cols, hipStream_t stream);
-int dk_launch_timestep_embedding(const float* t, int n, int rep, int dim, float max_period, int embed_dtype,
-                                 bf16_t* out, hipStream_t stream);
 int dk_launch_rope_table(float* table, int S_txt, int gh, int gw, const int* axes, int n_axes, float theta,
                          hipStream_t stream);
 int dk_launch_f32_to_bf16(const float* x, bf16_t* y, long n, hipStream_t stream);
 int dk_launch_affine_f32(const float* x, float* y, long n, float a, float b, hipStream_t stream);
-// latent [n_img, Hl, Wl, C] fp32 -> tokens [B, S_i, p*p*C] bf16 (B = n_img * dup)
-int dk_launch_latent_to_tokens(const float* x, bf16_t* tok, int n_img, int dup, int Hl, int Wl, int C, int p,
-                               int reshape_order, hipStream_t stream);
-// fused x0-prediction + CFG + Euler update (+ re-patchify for the next step)
-int dk_launch_euler_step(float* x, const bf16_t* model_out, int ld_out, bf16_t* tok, int n_img, int cfg_on,
-                         int Hl, int Wl, int C, int p, int reshape_order, float sigma, float sigma_next,
-                         float cfg_weight, hipStream_t stream);
+
+// ---- launchers per element type ------------------------------------------------------------------------------
+#include "dk_elem_launchers.h"
+namespace dk_f16 {
+#include "dk_elem_launchers.h"
+}
 
 // ---- 3x3 conv with LDS halo staging and the GroupNorm-apply + SiLU prologue (conv_halo.hip) ----------------------------------
 struct ConvHaloParams {

@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256) void dk_ln_modulate_kernel(LnJob ja, LnJob jb,
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float v0, v1;
-      unpack2bf(raw[i][e], v0, v1);
+      unpack2(raw[i][e], v0, v1);
       sum += v0 + v1;  // (zeros past the row end)
     }
   }
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256) void dk_ln_modulate_kernel(LnJob ja, LnJob jb,
     for (int e = 0; e < 4; ++e) {
       float v0, v1;
       asm volatile("" : "+v"(raw[i][e]));  // (opaque: else the unpacked row of pass 1 is kept live, 8 registers per chunk instead of 4)
-      unpack2bf(raw[i][e], v0, v1);
+      unpack2(raw[i][e], v0, v1);
       const float d0 = live ? v0 - mean : 0.f, d1 = live ? v1 - mean : 0.f;  // (masked before the product: sq += d * d stays one fma)
       sq += d0 * d0;
       sq += d1 * d1;
@@ -85,12 +85,12 @@ __global__ __launch_bounds__(256) void dk_ln_modulate_kernel(LnJob ja, LnJob jb,
     for (int e = 0; e < 4; ++e) {
       float v0, v1, s0, s1, c0, c1;
       asm volatile("" : "+v"(raw[i][e]));  // (and v - mean of pass 2 likewise)
-      unpack2bf(raw[i][e], v0, v1);
-      unpack2bf(rs[i][e], s0, s1);
-      unpack2bf(rc[i][e], c0, c1);
-      const float y0 = (v0 - mean) * rstd * round_bf16(1.0f + c0) + s0;
-      const float y1 = (v1 - mean) * rstd * round_bf16(1.0f + c1) + s1;
-      o[e] = pack2bf(y0, y1);
+      unpack2(raw[i][e], v0, v1);
+      unpack2(rs[i][e], s0, s1);
+      unpack2(rc[i][e], c0, c1);
+      const float y0 = (v0 - mean) * rstd * round_act(1.0f + c0) + s0;
+      const float y1 = (v1 - mean) * rstd * round_act(1.0f + c1) + s1;
+      o[e] = pack2(y0, y1);
     }
     __builtin_amdgcn_raw_buffer_store_b128(o, ro, (lane + 64 * i) * 16, 0, 0);
   }
@@ -176,7 +176,7 @@ __global__ __launch_bounds__(256) void dk_qk_norm_rope_kernel(QkJob ja, QkJob jb
   const u32x4 raw = *(const u32x4*)ptr;
   float v[8];
 #pragma unroll
-  for (int e = 0; e < 4; ++e) unpack2bf(raw[e], v[2 * e], v[2 * e + 1]);
+  for (int e = 0; e < 4; ++e) unpack2(raw[e], v[2 * e], v[2 * e + 1]);
   const bf16_t* w = which ? kw : qw;
   if (w != nullptr) {
     float ss = 0.f;
@@ -189,9 +189,9 @@ __global__ __launch_bounds__(256) void dk_qk_norm_rope_kernel(QkJob ja, QkJob jb
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float w0, w1;
-      unpack2bf(wr[e], w0, w1);
-      v[2 * e] = round_bf16(v[2 * e] * r * w0);
-      v[2 * e + 1] = round_bf16(v[2 * e + 1] * r * w1);
+      unpack2(wr[e], w0, w1);
+      v[2 * e] = round_act(v[2 * e] * r * w0);
+      v[2 * e + 1] = round_act(v[2 * e + 1] * r * w1);
     }
   }
   if (rope != nullptr) {
@@ -207,7 +207,7 @@ __global__ __launch_bounds__(256) void dk_qk_norm_rope_kernel(QkJob ja, QkJob jb
   if (active) {
     u32x4 o;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = pack2bf(v[2 * e], v[2 * e + 1]);
+    for (int e = 0; e < 4; ++e) o[e] = pack2(v[2 * e], v[2 * e + 1]);
     *(u32x4*)ptr = o;
   }
 }
@@ -250,7 +250,7 @@ int dk_launch_qk_norm_rope2(bf16_t* qkv0, int rows0, const bf16_t* qw0, const bf
 // ---------------------------------------------------------------------------------------------
 __global__ void dk_silu_kernel(const bf16_t* x, bf16_t* y, long n) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) y[i] = f2bf(silu_f(bf2f(x[i])));
+  if (i < n) y[i] = from_f32(silu_f(to_f32(x[i])));
 }
 int dk_launch_silu(const bf16_t* x, bf16_t* y, long n, hipStream_t stream) {
   hipLaunchKernelGGL(dk_silu_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, x, y, n);
@@ -264,7 +264,7 @@ __global__ void dk_add_kernel(const bf16_t* a, const bf16_t* b, int a_rows, int 
   if (i >= (long)rows * cols) return;
   const int r = (int)(i / cols), c = (int)(i % cols);
   // a is indexed by r % a_rows (batch row), b by r / a_rows (timestep row)
-  y[i] = f2bf(bf2f(a[(size_t)(r % a_rows) * cols + c]) + bf2f(b[(size_t)min(r / a_rows, b_rows - 1) * cols + c]));
+  y[i] = from_f32(to_f32(a[(size_t)(r % a_rows) * cols + c]) + to_f32(b[(size_t)min(r / a_rows, b_rows - 1) * cols + c]));
 }
 int dk_launch_add(const bf16_t* a, const bf16_t* b, int b_rows, bf16_t* y, int rows, int cols, hipStream_t stream) {
   const int a_rows = rows / b_rows;
@@ -288,8 +288,8 @@ __global__ void dk_timestep_embedding_kernel(const float* t, int n, int dim, flo
   const float ar = round_to((float)j, dt);
   const float freq = round_to(expf(-logf(max_period) * ar / (float)half), dt);
   const float arg = round_to(round_to(t[i], dt) * freq, dt);
-  out[(size_t)i * dim + j] = f2bf(round_to(cosf(arg), dt));
-  out[(size_t)i * dim + half + j] = f2bf(round_to(sinf(arg), dt));
+  out[(size_t)i * dim + j] = from_f32(round_to(cosf(arg), dt));
+  out[(size_t)i * dim + half + j] = from_f32(round_to(sinf(arg), dt));
 }
 int dk_launch_timestep_embedding(const float* t, int n, int rep, int dim, float max_period, int embed_dtype, bf16_t* out,
                                  hipStream_t stream) {
@@ -300,6 +300,7 @@ int dk_launch_timestep_embedding(const float* t, int n, int rep, int dim, float 
   return 0;
 }
 
+#ifndef DK_ELEM_F16  // (fp32 / bf16-only helpers: one copy)
 // RoPE cos/sin table [S, D/2, 2] for the joint [text, image] sequence
 // (python/src/diffusionkit/mlx/mmdit.py:865-911, quirk Q14).
 struct RopeAxes { int dim[4]; int n; };
@@ -357,6 +358,7 @@ int dk_launch_affine_f32(const float* x, float* y, long n, float a, float b, hip
   DK_CHECK_HIP(hipGetLastError());
   return 0;
 }
+#endif  // !DK_ELEM_F16
 
 // ---------------------------------------------------------------------------------------------
 // Patchify: latent [n_img, Hl, Wl, C] fp32 -> tokens [n_img*dup, S_i, p*p*C] bf16.
@@ -379,7 +381,7 @@ __global__ void dk_latent_to_tokens_kernel(const float* x, bf16_t* tok, int n_im
   const int gw = Wl / p, S_i = (Hl / p) * gw, F = p * p * C;
   const int t = (yy / p) * gw + (xx / p);
   const int f = patch_feature(c, yy % p, xx % p, C, p, reshape_order);
-  const bf16_t v = f2bf(x[i]);
+  const bf16_t v = from_f32(x[i]);
   for (int d = 0; d < dup; ++d) tok[((size_t)(d * n_img + img) * S_i + t) * F + f] = v;
 }
 int dk_launch_latent_to_tokens(const float* x, bf16_t* tok, int n_img, int dup, int Hl, int Wl, int C, int p, int reshape_order,
@@ -411,18 +413,18 @@ __global__ void dk_euler_step_kernel(float* x, const bf16_t* model_out, int ld_o
   const int t = (yy / p) * gw + (xx / p);
   const int f = patch_feature(c, yy % p, xx % p, C, p, reshape_order);
   const float xv = x[i];
-  const float xb = round_bf16(xv);  // the value the denoiser saw
-  const float o_text = bf2f(model_out[((size_t)img * S_i + t) * ld_out + f]);
+  const float xb = round_act(xv);  // the value the denoiser saw
+  const float o_text = to_f32(model_out[((size_t)img * S_i + t) * ld_out + f]);
   float den = xb - o_text * sigma;
   if (cfg_on) {
-    const float o_neg = bf2f(model_out[((size_t)(n_img + img) * S_i + t) * ld_out + f]);
+    const float o_neg = to_f32(model_out[((size_t)(n_img + img) * S_i + t) * ld_out + f]);
     const float den_neg = xb - o_neg * sigma;
     den = den_neg + cfg_weight * (den - den_neg);
   }
   const float d = (xv - den) / sigma;
   const float xn = xv + d * (sigma_next - sigma);
   x[i] = xn;
-  const bf16_t nb = f2bf(xn);
+  const bf16_t nb = from_f32(xn);
   tok[((size_t)img * S_i + t) * F + f] = nb;
   if (cfg_on) tok[((size_t)(n_img + img) * S_i + t) * F + f] = nb;
 }

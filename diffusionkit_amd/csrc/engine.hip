@@ -61,9 +61,21 @@ static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; 
 // ---------------------------------------------------------------------------------------------
 // operator-level wrappers
 // ---------------------------------------------------------------------------------------------
+// Element type of the launches an entry point builds: DK_DTYPE_BF16 unless an fp16 engine's call (MmditCallScope) or an *_f16 operator entry is
+// on the stack of this host thread (same discipline as g_linear_ws below: everything is enqueued before the call returns)
+static thread_local int g_elem_dtype = DK_DTYPE_BF16;
+struct ElemScope {
+  int prev;
+  explicit ElemScope(int dtype) : prev(g_elem_dtype) { g_elem_dtype = dtype; }
+  ~ElemScope() { g_elem_dtype = prev; }
+};
+// an elementwise launcher in the element type in force (dk_elem_launchers.h: same signature in both)
+#define DK_EL(fn) (g_elem_dtype == DK_DTYPE_F16 ? dk_f16::fn : fn)
+
 static GemmParams gemm_params_from_desc(const dk_gemm_desc* d) {
   GemmParams p;
   memset(&p, 0, sizeof(p));
+  p.dtype = g_elem_dtype;
   p.A = (const bf16_t*)d->A; p.W = (const bf16_t*)d->W; p.C = (bf16_t*)d->C;
   p.bias = (const bf16_t*)d->bias; p.gate = (const bf16_t*)d->gate; p.res = (const bf16_t*)d->res;
   p.M = d->M; p.N = d->N; p.K = d->K;
@@ -84,10 +96,20 @@ extern "C" int dk_gemm_bf16(const dk_gemm_desc* d, void* stream) {
   return dk_launch_gemm(gemm_params_from_desc(d), S_(stream));
 }
 
+extern "C" int dk_gemm_f16(const dk_gemm_desc* d, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_gemm_bf16(d, stream);
+}
+
 extern "C" int dk_gemm_plan(const dk_gemm_desc* d, const dk_gemm_desc* d2, dk_gemm_plan_t* plan) {
   DK_REQUIRE(d != nullptr && plan != nullptr, "null descriptor / plan");
   const GemmParams p2 = d2 != nullptr ? gemm_params_from_desc(d2) : GemmParams{};
   return dk_gemm_plan_call(gemm_params_from_desc(d), d2 != nullptr ? &p2 : nullptr, *plan);
+}
+
+extern "C" int dk_gemm_plan_f16(const dk_gemm_desc* d, const dk_gemm_desc* d2, dk_gemm_plan_t* plan) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_gemm_plan(d, d2, plan);
 }
 
 // the engine-only fields of GemmParams beside a descriptor (dk_gemm_side / dk_gemm_fp8_side: same names); null: nothing fused
@@ -109,6 +131,11 @@ extern "C" int dk_gemm_fused_bf16(const dk_gemm_desc* d, const dk_gemm_side* f, 
   GemmParams p2 = gemm_params_from_desc(d2);
   set_fused(p2, f2);
   return dk_launch_gemm_pair(p, p2, S_(stream));
+}
+
+extern "C" int dk_gemm_fused_f16(const dk_gemm_desc* d, const dk_gemm_side* f, const dk_gemm_desc* d2, const dk_gemm_side* f2, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_gemm_fused_bf16(d, f, d2, f2, stream);
 }
 
 extern "C" int dk_gemm_fused_plan(const dk_gemm_desc* d, const dk_gemm_side* f, const dk_gemm_desc* d2, const dk_gemm_side* f2,
@@ -177,12 +204,17 @@ extern "C" int dk_attention_desc_bf16(const dk_attention_desc* d, void* stream) 
   p.B = d->B; p.H = d->H; p.S = d->S; p.D = d->D; p.ld = d->ld; p.ldo = d->ldo; p.scale = d->scale;
   p.bias = (const bf16_t*)d->bias; p.bias_head_stride = (long)d->bias_head_stride; p.ldb = d->ldb;
   p.qn_a = (const bf16_t*)d->qn_a; p.qn_b = (const bf16_t*)d->qn_b; p.qn_split = d->qn_split; p.qn_eps = d->qn_eps; p.q_rope = d->q_rope;
+  p.dtype = g_elem_dtype;
   if (d->O8 != nullptr) {
     DK_REQUIRE(d->O8_scales != nullptr && d->o8_rows >= (int64_t)d->B * d->S && d->o8_ld >= d->H * d->D && d->o8_ld % 32 == 0,
                "MX-fp8 output copy: scales, B * S rows inside the buffer, a row pitch of at least H * D bytes (multiple of 32)");
     p.O8 = (unsigned char*)d->O8; p.O8_scales = (unsigned char*)d->O8_scales; p.o8_ld = d->o8_ld; p.o8_nblk = mx_nblk((long)d->o8_rows);
   }
   return dk_launch_attention(p, S_(stream));
+}
+extern "C" int dk_attention_desc_f16(const dk_attention_desc* d, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_attention_desc_bf16(d, stream);
 }
 extern "C" int32_t dk_attention_d512_tp(int32_t T) { return (int32_t)align_up((size_t)(T > 0 ? T : 0), 64); }
 // transpose of every image's V into [512, Tp] rows (zero-padded), then the flash kernel
@@ -230,9 +262,15 @@ extern "C" int dk_t5_bias_bf16(const void* emb, const int32_t* rel_bucket, int32
 extern "C" int dk_ln_modulate_bf16(const void* x, int32_t ldx, void* out, int32_t ldo, int32_t M, int32_t h, const void* shift,
                                    const void* scale, int32_t mod_stride, int32_t mod_seg_len, int32_t x_seg_len,
                                    int32_t x_seg_stride, float eps, void* stream) {
-  return dk_launch_ln_modulate((const bf16_t*)x, ldx, (bf16_t*)out, ldo, M, h, (const bf16_t*)shift, (const bf16_t*)scale,
-                               mod_stride, mod_seg_len > 0 ? mod_seg_len : M, x_seg_len > 0 ? x_seg_len : M, x_seg_stride,
-                               eps, S_(stream));
+  return DK_EL(dk_launch_ln_modulate)((const bf16_t*)x, ldx, (bf16_t*)out, ldo, M, h, (const bf16_t*)shift, (const bf16_t*)scale,
+                                      mod_stride, mod_seg_len > 0 ? mod_seg_len : M, x_seg_len > 0 ? x_seg_len : M, x_seg_stride,
+                                      eps, S_(stream));
+}
+extern "C" int dk_ln_modulate_f16(const void* x, int32_t ldx, void* out, int32_t ldo, int32_t M, int32_t h, const void* shift,
+                                  const void* scale, int32_t mod_stride, int32_t mod_seg_len, int32_t x_seg_len,
+                                  int32_t x_seg_stride, float eps, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_ln_modulate_bf16(x, ldx, out, ldo, M, h, shift, scale, mod_stride, mod_seg_len, x_seg_len, x_seg_stride, eps, stream);
 }
 
 extern "C" int32_t dk_weight_pitch_fp8(int32_t k) { return k >= g_dk_pitch_min_k ? k + 128 : k; }
@@ -306,8 +344,14 @@ extern "C" int dk_ln_modulate_mx8(const void* x, int32_t ldx, int32_t M, int32_t
 extern "C" int dk_qk_norm_rope_bf16(void* qkv, int32_t ld, int32_t q_off, int32_t k_off, int32_t rows, int32_t H, int32_t D,
                                     const void* q_weight, const void* k_weight, float eps, const float* rope_table,
                                     int32_t row_seg_len, int32_t row_seg_stride, int32_t pos_off, void* stream) {
-  return dk_launch_qk_norm_rope((bf16_t*)qkv, ld, q_off, k_off, rows, H, D, (const bf16_t*)q_weight, (const bf16_t*)k_weight,
-                                eps, rope_table, row_seg_len > 0 ? row_seg_len : rows, row_seg_stride, pos_off, 0, S_(stream));
+  return DK_EL(dk_launch_qk_norm_rope)((bf16_t*)qkv, ld, q_off, k_off, rows, H, D, (const bf16_t*)q_weight, (const bf16_t*)k_weight,
+                                       eps, rope_table, row_seg_len > 0 ? row_seg_len : rows, row_seg_stride, pos_off, 0, S_(stream), 0);
+}
+extern "C" int dk_qk_norm_rope_f16(void* qkv, int32_t ld, int32_t q_off, int32_t k_off, int32_t rows, int32_t H, int32_t D,
+                                   const void* q_weight, const void* k_weight, float eps, const float* rope_table,
+                                   int32_t row_seg_len, int32_t row_seg_stride, int32_t pos_off, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_qk_norm_rope_bf16(qkv, ld, q_off, k_off, rows, H, D, q_weight, k_weight, eps, rope_table, row_seg_len, row_seg_stride, pos_off, stream);
 }
 
 extern "C" int dk_rope_table_f32(float* table, int32_t S_txt, int32_t gh, int32_t gw, const int32_t* axes_dim, int32_t n_axes,
@@ -317,21 +361,37 @@ extern "C" int dk_rope_table_f32(float* table, int32_t S_txt, int32_t gh, int32_
 
 extern "C" int dk_timestep_embedding_bf16(const float* t_dev, int32_t n, int32_t dim, float max_period, int32_t embed_dtype,
                                           void* out, void* stream) {
-  return dk_launch_timestep_embedding(t_dev, n, 1, dim, max_period, embed_dtype, (bf16_t*)out, S_(stream));
+  return DK_EL(dk_launch_timestep_embedding)(t_dev, n, 1, dim, max_period, embed_dtype, (bf16_t*)out, S_(stream));
+}
+extern "C" int dk_timestep_embedding_f16(const float* t_dev, int32_t n, int32_t dim, float max_period, int32_t embed_dtype,
+                                         void* out, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_timestep_embedding_bf16(t_dev, n, dim, max_period, embed_dtype, out, stream);
 }
 
 extern "C" int dk_latent_to_tokens(const float* x, void* tokens, int32_t n_img, int32_t dup, int32_t Hl, int32_t Wl, int32_t C,
                                    int32_t p, int32_t reshape_order, void* stream) {
   DK_REQUIRE(Hl % p == 0 && Wl % p == 0, "latent size must be divisible by the patch size");
-  return dk_launch_latent_to_tokens(x, (bf16_t*)tokens, n_img, dup, Hl, Wl, C, p, reshape_order, S_(stream));
+  return DK_EL(dk_launch_latent_to_tokens)(x, (bf16_t*)tokens, n_img, dup, Hl, Wl, C, p, reshape_order, S_(stream));
+}
+extern "C" int dk_latent_to_tokens_f16(const float* x, void* tokens, int32_t n_img, int32_t dup, int32_t Hl, int32_t Wl, int32_t C,
+                                       int32_t p, int32_t reshape_order, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_latent_to_tokens(x, tokens, n_img, dup, Hl, Wl, C, p, reshape_order, stream);
 }
 
 extern "C" int dk_euler_cfg_step(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on,
                                  int32_t Hl, int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma,
                                  float sigma_next, float cfg_weight, void* stream) {
   DK_REQUIRE(sigma != 0.0f, "sigma must be non-zero");
-  return dk_launch_euler_step(x, (const bf16_t*)model_out, ld_out, (bf16_t*)tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order,
-                              sigma, sigma_next, cfg_weight, S_(stream));
+  return DK_EL(dk_launch_euler_step)(x, (const bf16_t*)model_out, ld_out, (bf16_t*)tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order,
+                                     sigma, sigma_next, cfg_weight, S_(stream));
+}
+extern "C" int dk_euler_cfg_step_f16(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on,
+                                     int32_t Hl, int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma,
+                                     float sigma_next, float cfg_weight, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_euler_cfg_step(x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight, stream);
 }
 
 extern "C" int dk_affine_f32(const float* x, float* y, int64_t n, float a, float b, void* stream) {
@@ -449,7 +509,7 @@ static GemmParams linear_params(const bf16_t* A, int lda, int a_seg_len, int a_s
   p.c_seg_len = c_seg_len; p.c_seg_stride = c_seg_stride;
   p.r_seg_len = r_seg_len > 0 ? r_seg_len : M; p.r_seg_stride = r_seg_stride;
   p.gate_seg_len = gate_seg_len > 0 ? gate_seg_len : M; p.gate_stride = gate_stride;
-  p.alpha = 1.0f; p.epi = epi;
+  p.alpha = 1.0f; p.epi = epi; p.dtype = g_elem_dtype;
   if (g_linear_ws) { p.workspace = g_linear_ws; p.workspace_bytes = dk_gemm_split_workspace_bytes(); }
   return p;
 }
@@ -466,7 +526,7 @@ static int linear_call(const bf16_t* A, int lda, int a_seg_len, int a_seg_stride
   p.c_seg_len = c_seg_len; p.c_seg_stride = c_seg_stride;
   p.r_seg_len = r_seg_len > 0 ? r_seg_len : M; p.r_seg_stride = r_seg_stride;
   p.gate_seg_len = gate_seg_len > 0 ? gate_seg_len : M; p.gate_stride = gate_stride;
-  p.alpha = 1.0f; p.epi = epi;
+  p.alpha = 1.0f; p.epi = epi; p.dtype = g_elem_dtype;
   return dk_launch_gemm(p, st);
 }
 // plain [M,K] x [N,K]^T -> [M,N]
@@ -526,6 +586,8 @@ struct dk_mmdit {
   // ceil128(B * S_i) -- every row range an fp8 GEMM reads starts on a 128-row scale block; rows8 = txt0_8 + B * S_t >= B * S
   int txt0_8 = 0;
   long rows8 = 0;
+  // element type of every bound tensor, activation buffer and of the token / text / pooled I/O (dk_mmdit_set_activation_dtype): sizes are the same
+  int dtype = DK_DTYPE_BF16;
   bool fp8() const { return cfg.fp8_linears != 0; }
   // precision policy: the first n_bf16() double-stream blocks keep bf16 Linears under fp8_linears (global block index = double-block index)
   int n_bf16() const { return fp8() ? (cfg.fp8_bf16_double_blocks < cfg.depth_multimodal ? cfg.fp8_bf16_double_blocks : cfg.depth_multimodal) : 0; }
@@ -582,6 +644,16 @@ extern "C" int dk_mmdit_set_guidance(dk_mmdit* m, float guidance) {
   DK_REQUIRE(m->cfg.guidance_embed, "this configuration has no guidance embedding (guidance_embed = 0)");
   m->guidance = guidance;
   m->mod_ready = false;
+  return 0;
+}
+extern "C" int dk_mmdit_set_activation_dtype(dk_mmdit* m, int32_t dtype) {
+  DK_REQUIRE(m != nullptr, "null handle");
+  DK_REQUIRE(dtype == DK_DTYPE_BF16 || dtype == DK_DTYPE_F16, "activation dtype: 0 bf16, 1 fp16");
+  DK_REQUIRE(m->named.empty() && !m->prepared, "dk_mmdit_set_activation_dtype must precede the first dk_mmdit_bind");
+  if (dtype == DK_DTYPE_F16)
+    DK_REQUIRE(m->D() == 64 && m->cfg.depth_unified == 0 && m->cfg.fp8_linears == 0,
+               "fp16 activations are the SD3 family's: head_dim == 64, depth_unified == 0, fp8_linears == 0");
+  m->dtype = dtype;
   return 0;
 }
 extern "C" void dk_mmdit_destroy(dk_mmdit* m) { delete m; }
@@ -798,9 +870,10 @@ extern "C" int dk_mmdit_cache_modulation_params(dk_mmdit* m, const void* pooled,
   DK_REQUIRE(n > 0 && n <= m->n_t, "more timesteps than the workspace was prepared for");
   hipStream_t st = S_(stream);
   LinearWsScope ws_scope(m->GWS);
+  ElemScope elem_scope(m->dtype);
   const int h = m->h(), B = m->B, P = m->cfg.pooled_text_embed_dim, Fq = m->cfg.frequency_embed_dim;
   DK_CHECK_HIP(hipMemcpyAsync(m->tdev, timesteps_host, (size_t)n * 4, hipMemcpyHostToDevice, st));
-  DK_TRY(dk_launch_timestep_embedding(m->tdev, n, 1, Fq, (float)m->cfg.max_period, m->cfg.embed_dtype, m->temb, st));
+  DK_TRY(DK_EL(dk_launch_timestep_embedding)(m->tdev, n, 1, Fq, (float)m->cfg.max_period, m->cfg.embed_dtype, m->temb, st));
   // t_embedder / y_embedder: Linear -> SiLU -> Linear (mmdit.py:352-392)
   DK_TRY(linear_plain(m->temb, m->t0_w, m->t0_b, m->t1, n, h, Fq, DK_EPI_BIAS_SILU, st));
   DK_TRY(linear_plain(m->t1, m->t2_w, m->t2_b, m->tvec, n, h, h, DK_EPI_BIAS, st));
@@ -811,14 +884,14 @@ extern "C" int dk_mmdit_cache_modulation_params(dk_mmdit* m, const void* pooled,
     // added to the pooled-text embedding of every batch row, hence to every modulation vector
     const float gt = 1000.0f * m->guidance;
     DK_CHECK_HIP(hipMemcpyAsync(m->tdev, &gt, 4, hipMemcpyHostToDevice, st));  // (tdev[0] was consumed by the launch above, same stream)
-    DK_TRY(dk_launch_timestep_embedding(m->tdev, 1, 1, Fq, (float)m->cfg.max_period, m->cfg.embed_dtype, m->gemb, st));
+    DK_TRY(DK_EL(dk_launch_timestep_embedding)(m->tdev, 1, 1, Fq, (float)m->cfg.max_period, m->cfg.embed_dtype, m->gemb, st));
     DK_TRY(linear_plain(m->gemb, m->g0_w, m->g0_b, m->g1, 1, h, Fq, DK_EPI_BIAS_SILU, st));
     DK_TRY(linear_plain(m->g1, m->g2_w, m->g2_b, m->gvec, 1, h, h, DK_EPI_BIAS, st));
-    DK_TRY(dk_launch_add(m->yvec, m->gvec, 1, m->yvec, B, h, st));  // y[b] += g
+    DK_TRY(DK_EL(dk_launch_add)(m->yvec, m->gvec, 1, m->yvec, B, h, st));  // y[b] += g
   }
   // vec[step*B + b] = silu(y[b] + t[step]); adaLN_modulation = SiLU -> Linear (mmdit.py:94-96,430-435)
-  DK_TRY(dk_launch_add(m->yvec, m->tvec, n, m->vec, n * B, h, st));
-  DK_TRY(dk_launch_silu(m->vec, m->vec, (long)n * B * h, st));
+  DK_TRY(DK_EL(dk_launch_add)(m->yvec, m->tvec, n, m->vec, n * B, h, st));
+  DK_TRY(DK_EL(dk_launch_silu)(m->vec, m->vec, (long)n * B * h, st));
   DK_TRY(linear_plain(m->vec, m->adaln_w, m->adaln_b, m->MOD, n * B, m->mod_rows() * h, h, DK_EPI_BIAS, st));
   m->mod_ready = true;
   return 0;
@@ -827,12 +900,12 @@ extern "C" int dk_mmdit_cache_modulation_params(dk_mmdit* m, const void* pooled,
 // one TransformerBlock.pre_sdpa (mmdit.py:440-519) on a row range of the joint stream
 static int pre_sdpa(dk_mmdit* m, const StreamW& w, int row_off, int S_s, const bf16_t* mod, int mod_stride, hipStream_t st) {
   const int h = m->h(), B = m->B, S = m->S, M = B * S_s;
-  DK_TRY(dk_launch_ln_modulate(m->X + (size_t)row_off * h, h, m->XN, h, M, h, mod, mod + h, mod_stride, S_s, S_s, S,
+  DK_TRY(DK_EL(dk_launch_ln_modulate)(m->X + (size_t)row_off * h, h, m->XN, h, M, h, mod, mod + h, mod_stride, S_s, S_s, S,
                                m->cfg.layer_norm_eps, st));
   DK_TRY(linear_call(m->XN, h, M, 0, w.qkv_w, w.qkv_b, m->QKV + (size_t)row_off * 3 * h, 3 * h, S_s, S, M, 3 * h, h,
                      DK_EPI_BIAS, nullptr, 0, 0, nullptr, 0, 0, 0, st));
-  DK_TRY(dk_launch_qk_norm_rope(m->QKV + (size_t)row_off * 3 * h, 3 * h, 0, h, M, m->cfg.num_heads, m->D(), w.qn, w.kn, 1e-6f,
-                                m->cfg.use_rope ? m->rope : nullptr, S_s, S, row_off, m->S, st));
+  DK_TRY(DK_EL(dk_launch_qk_norm_rope)(m->QKV + (size_t)row_off * 3 * h, 3 * h, 0, h, M, m->cfg.num_heads, m->D(), w.qn, w.kn, 1e-6f,
+                                m->cfg.use_rope ? m->rope : nullptr, S_s, S, row_off, m->S, st, 0));
   return 0;
 }
 
@@ -844,7 +917,7 @@ static int post_sdpa_seq(dk_mmdit* m, const StreamW& w, int row_off, int S_s, co
   DK_TRY(linear_call(m->ATT + (size_t)row_off * h, h, S_s, S, w.o_w, w.o_b, Xs, h, S_s, S, M, h, h, DK_EPI_GATE_RES, mod + 2 * h,
                      S_s, mod_stride, Xs, h, S_s, S, st));
   // residual += gate_mlp * fc2(gelu(fc1(LN-mod(residual))))
-  DK_TRY(dk_launch_ln_modulate(Xs, h, m->XN, h, M, h, mod + 3 * h, mod + 4 * h, mod_stride, S_s, S_s, S, m->cfg.layer_norm_eps, st));
+  DK_TRY(DK_EL(dk_launch_ln_modulate)(Xs, h, m->XN, h, M, h, mod + 3 * h, mod + 4 * h, mod_stride, S_s, S_s, S, m->cfg.layer_norm_eps, st));
   DK_TRY(linear_call(m->XN, h, M, 0, w.fc1_w, w.fc1_b, m->HID, m->ldh, M, 0, M, r * h, h, DK_EPI_BIAS_GELU, nullptr, 0, 0, nullptr,
                      0, 0, 0, st));
   DK_TRY(linear_call(m->HID, m->ldh, M, 0, w.fc2_w, w.fc2_b, Xs, h, S_s, S, M, h, r * h, DK_EPI_GATE_RES, mod + 5 * h, S_s,
@@ -855,6 +928,7 @@ static int post_sdpa_seq(dk_mmdit* m, const StreamW& w, int row_off, int S_s, co
 extern "C" int dk_mmdit_cache_context(dk_mmdit* m, const void* text, void* stream) {
   DK_REQUIRE(m && m->prepared && text, "prepare must precede cache_context");
   LinearWsScope ws_scope(m->GWS);
+  ElemScope elem_scope(m->dtype);
   const dk_mmdit_config& c = m->cfg;
   const int M = m->B * m->S_t;
   DK_TRY(linear_call((const bf16_t*)text, c.token_level_text_embed_dim, M, 0, m->ctx_w, m->ctx_b, m->CTXE, m->h(), M, 0, M, m->h(),
@@ -868,7 +942,7 @@ static int mmdit_final_layer(dk_mmdit* m, const bf16_t* mod_step, bf16_t* tokens
   const int h = m->h(), B = m->B, S = m->S, S_t = m->S_t, S_i = m->S_i, F = m->F();
   const int mod_stride = m->mod_rows() * h;
   const bf16_t* mod_fin = mod_step + (size_t)m->mod_offset(3, 0) * h;
-  DK_TRY(dk_launch_ln_modulate(m->X + (size_t)S_t * h, h, m->XN, h, B * S_i, h, mod_fin, mod_fin + h, mod_stride, S_i, S_i, S,
+  DK_TRY(DK_EL(dk_launch_ln_modulate)(m->X + (size_t)S_t * h, h, m->XN, h, B * S_i, h, mod_fin, mod_fin + h, mod_stride, S_i, S_i, S,
                                m->cfg.layer_norm_eps, st));
   return linear_plain(m->XN, m->final_w, m->final_b, tokens_out, B * S_i, F, h, DK_EPI_BIAS, st);
 }
@@ -1052,7 +1126,8 @@ struct AttnWsScope {  // an engine call's attention launches split through that 
 struct MmditCallScope {  // an engine call's GEMM and attention splits go through THAT engine's regions; the caller's settings come back
   LinearWsScope lin;
   AttnWsScope att;
-  explicit MmditCallScope(dk_mmdit* m) : lin(m->GWS), att(m->AWS, m->AWS_bytes) {}
+  ElemScope elem;
+  explicit MmditCallScope(dk_mmdit* m) : lin(m->GWS), att(m->AWS, m->AWS_bytes), elem(m->dtype) {}
 };
 
 // The transformer blocks [first, first + count) of the global order (double blocks 0 .. depth_multimodal - 1, then single blocks)
@@ -1082,7 +1157,7 @@ static int mmdit_blocks_bf16(dk_mmdit* m, const bf16_t* mod_step, int first, int
     const bool txt_post = !m->txt_skipped(i);
     // pre_sdpa (mmdit.py:440-519): LN-modulate, q/k/v projection, QK-norm (+ RoPE)
     // (image and text stream of each elementwise stage in ONE launch: the 256 text rows do not run alone on the chip)
-    DK_TRY(dk_launch_ln_modulate2(X_img, XN_img, Mi, mod_img, mod_img + h, S_i, X_txt, XN_txt, Mt, mod_txt, mod_txt + h, S_t, h, h, h,
+    DK_TRY(DK_EL(dk_launch_ln_modulate2)(X_img, XN_img, Mi, mod_img, mod_img + h, S_i, X_txt, XN_txt, Mt, mod_txt, mod_txt + h, S_t, h, h, h,
                                   mod_stride, S, c.layer_norm_eps, st));
     GemmParams qkv_img = linear_params(XN_img, h, Mi, 0, wi.qkv_w, wi.qkv_b, m->QKV + (size_t)S_t * 3 * h, 3 * h, S_i, S, Mi, 3 * h, h, DK_EPI_BIAS,
                                        nullptr, 0, 0, nullptr, 0, 0, 0);
@@ -1096,9 +1171,10 @@ static int mmdit_blocks_bf16(dk_mmdit* m, const bf16_t* mod_step, int first, int
     }
     DK_TRY(dk_launch_gemm_pair(qkv_img, qkv_txt, st));
     if (!kf)
-      DK_TRY(dk_launch_qk_norm_rope2(m->QKV + (size_t)S_t * 3 * h, Mi, wi.qn, wi.kn, S_i, S_t, m->QKV, Mt, wt.qn, wt.kn, S_t, 0, 3 * h, 0, h,
+      DK_TRY(DK_EL(dk_launch_qk_norm_rope2)(m->QKV + (size_t)S_t * 3 * h, Mi, wi.qn, wi.kn, S_i, S_t, m->QKV, Mt, wt.qn, wt.kn, S_t, 0, 3 * h, 0, h,
                                      c.num_heads, m->D(), 1e-6f, c.use_rope ? m->rope : nullptr, S, st, fuse_q()));
     AttnParams ap;
+    ap.dtype = m->dtype;
     ap.Q = m->QKV; ap.K = m->QKV + h; ap.V = m->QKV + 2 * h; ap.O = m->ATT;
     ap.B = B; ap.H = c.num_heads; ap.S = S; ap.D = m->D(); ap.ld = 3 * h; ap.ldo = h; ap.scale = scale;
     if (fuse_q() && !(kf && fuse_qg(wi.qn, false) && fuse_qg(wt.qn, false))) { ap.qn_a = wt.qn; ap.qn_b = wi.qn; ap.qn_split = S_t; ap.q_rope = c.use_rope ? m->rope : nullptr; }
@@ -1116,10 +1192,10 @@ static int mmdit_blocks_bf16(dk_mmdit* m, const bf16_t* mod_step, int first, int
     }
     // residual += gate_mlp * fc2(gelu(fc1(LN-mod(residual))))
     if (txt_post)
-      DK_TRY(dk_launch_ln_modulate2(X_img, XN_img, Mi, mod_img + 3 * h, mod_img + 4 * h, S_i, X_txt, XN_txt, Mt, mod_txt + 3 * h,
+      DK_TRY(DK_EL(dk_launch_ln_modulate2)(X_img, XN_img, Mi, mod_img + 3 * h, mod_img + 4 * h, S_i, X_txt, XN_txt, Mt, mod_txt + 3 * h,
                                     mod_txt + 4 * h, S_t, h, h, h, mod_stride, S, c.layer_norm_eps, st));
     else
-      DK_TRY(dk_launch_ln_modulate(X_img, h, XN_img, h, Mi, h, mod_img + 3 * h, mod_img + 4 * h, mod_stride, S_i, S_i, S, c.layer_norm_eps, st));
+      DK_TRY(DK_EL(dk_launch_ln_modulate)(X_img, h, XN_img, h, Mi, h, mod_img + 3 * h, mod_img + 4 * h, mod_stride, S_i, S_i, S, c.layer_norm_eps, st));
     const GemmParams fc1_img = linear_params(XN_img, h, Mi, 0, wi.fc1_w, wi.fc1_b, HID_img, ldh, Mi, 0, Mi, r * h, h, DK_EPI_BIAS_GELU,
                                              nullptr, 0, 0, nullptr, 0, 0, 0);
     const GemmParams fc2_img = linear_params(HID_img, ldh, Mi, 0, wi.fc2_w, wi.fc2_b, X_img, h, S_i, S, Mi, h, r * h, DK_EPI_GATE_RES,
@@ -1145,7 +1221,7 @@ static int mmdit_blocks_bf16(dk_mmdit* m, const bf16_t* mod_step, int first, int
     const StreamW& w = m->single[i];
     const bf16_t* mod = mod_step + (size_t)m->mod_offset(2, i) * h;
     const int M = B * S, ldcat = m->ldcat;
-    DK_TRY(dk_launch_ln_modulate(m->X, h, m->XN, h, M, h, mod, mod + h, mod_stride, S, M, 0, c.layer_norm_eps, st));
+    DK_TRY(DK_EL(dk_launch_ln_modulate)(m->X, h, m->XN, h, M, h, mod, mod + h, mod_stride, S, M, 0, c.layer_norm_eps, st));
     {  // linear1: [q|k|v] -> QKV, gelu(fc1) -> CAT[:, h:], one pass over the modulated activations
       GemmParams l1 = linear_params(m->XN, h, M, 0, w.qkv_w, w.qkv_b, m->QKV, 3 * h, M, 0, M, (3 + r) * h, h, DK_EPI_BIAS, nullptr, 0, 0,
                                     nullptr, 0, 0, 0);
@@ -1154,9 +1230,10 @@ static int mmdit_blocks_bf16(dk_mmdit* m, const bf16_t* mod_step, int first, int
       DK_TRY(dk_launch_gemm(l1, st));
     }
     if (!fuse_k(w.kn))
-      DK_TRY(dk_launch_qk_norm_rope(m->QKV, 3 * h, 0, h, M, c.num_heads, m->D(), w.qn, w.kn, 1e-6f, c.use_rope ? m->rope : nullptr,
+      DK_TRY(DK_EL(dk_launch_qk_norm_rope)(m->QKV, 3 * h, 0, h, M, c.num_heads, m->D(), w.qn, w.kn, 1e-6f, c.use_rope ? m->rope : nullptr,
                                     S, S, 0, S, st, fuse_q()));
     AttnParams ap;
+    ap.dtype = m->dtype;
     ap.Q = m->QKV; ap.K = m->QKV + h; ap.V = m->QKV + 2 * h; ap.O = m->CAT;
     ap.B = B; ap.H = c.num_heads; ap.S = S; ap.D = m->D(); ap.ld = 3 * h; ap.ldo = ldcat; ap.scale = scale;
     if (fuse_q() && !(fuse_k(w.kn) && fuse_qg(w.qn, false))) { ap.qn_a = ap.qn_b = w.qn; ap.qn_split = 0; ap.q_rope = c.use_rope ? m->rope : nullptr; }

@@ -138,17 +138,17 @@ __global__ __launch_bounds__(256) void dk_gemm_bf16_kernel(GemmParams p) {
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
       const int c = kk * 2 + hi;
-      bf16x8 wf[2], xf[2];
+      ex8 wf[2], xf[2];
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        wf[i] = *(const bf16x8*)(Bs + lds_row_off(wn * 64 + i * 32 + l31, c));
-        xf[i] = *(const bf16x8*)(As + lds_row_off(wm * 64 + i * 32 + l31, c));
+        wf[i] = *(const ex8*)(Bs + lds_row_off(wn * 64 + i * 32 + l31, c));
+        xf[i] = *(const ex8*)(As + lds_row_off(wm * 64 + i * 32 + l31, c));
       }
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi)
-          acc[ni][mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ni], xf[mi], acc[ni][mi], 0, 0, 0);
+          acc[ni][mi] = mfma_32x32x16(wf[ni], xf[mi], acc[ni][mi]);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -179,12 +179,12 @@ __global__ __launch_bounds__(256) void dk_gemm_bf16_kernel(GemmParams p) {
           if (p.bias) {
             const uint2 bb = *(const uint2*)(p.bias + nb);
             float b0, b1, b2, b3;
-            unpack2bf(bb.x, b0, b1);
-            unpack2bf(bb.y, b2, b3);
+            unpack2(bb.x, b0, b1);
+            unpack2(bb.y, b2, b3);
             v[0] += b0; v[1] += b1; v[2] += b2; v[3] += b3;
           }
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = round_bf16(v[e]);
+          for (int e = 0; e < 4; ++e) v[e] = round_act(v[e]);
           if (p.epi == DK_EPI_BIAS_GELU) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = gelu_erf_f(v[e]);
@@ -194,35 +194,35 @@ __global__ __launch_bounds__(256) void dk_gemm_bf16_kernel(GemmParams p) {
           } else if (p.epi == DK_EPI_GATE_RES || p.epi == DK_EPI_RES) {
             const uint2 rr = *(const uint2*)(p.res + rrow + nb);
             float r0, r1, r2, r3;
-            unpack2bf(rr.x, r0, r1);
-            unpack2bf(rr.y, r2, r3);
+            unpack2(rr.x, r0, r1);
+            unpack2(rr.y, r2, r3);
             if (p.epi == DK_EPI_GATE_RES) {
               const uint2 gg = *(const uint2*)(gate + nb);
               float g0, g1, g2, g3;
-              unpack2bf(gg.x, g0, g1);
-              unpack2bf(gg.y, g2, g3);
-              v[0] = r0 + round_bf16(g0 * v[0]);
-              v[1] = r1 + round_bf16(g1 * v[1]);
-              v[2] = r2 + round_bf16(g2 * v[2]);
-              v[3] = r3 + round_bf16(g3 * v[3]);
+              unpack2(gg.x, g0, g1);
+              unpack2(gg.y, g2, g3);
+              v[0] = r0 + round_act(g0 * v[0]);
+              v[1] = r1 + round_act(g1 * v[1]);
+              v[2] = r2 + round_act(g2 * v[2]);
+              v[3] = r3 + round_act(g3 * v[3]);
             } else {
               v[0] += r0; v[1] += r1; v[2] += r2; v[3] += r3;
             }
           }
           uint2 o;
-          o.x = pack2bf(v[0], v[1]);
-          o.y = pack2bf(v[2], v[3]);
+          o.x = pack2(v[0], v[1]);
+          o.y = pack2(v[2], v[3]);
           *(uint2*)(p.C + crow + nb) = o;
         } else {
           for (int e = 0; e < 4 && nb + e < p.N; ++e) {
             float x = v[e];
-            if (p.bias) x += bf2f(p.bias[nb + e]);
-            x = round_bf16(x);
+            if (p.bias) x += to_f32(p.bias[nb + e]);
+            x = round_act(x);
             if (p.epi == DK_EPI_BIAS_GELU) x = gelu_erf_f(x);
             else if (p.epi == DK_EPI_BIAS_SILU) x = silu_f(x);
-            else if (p.epi == DK_EPI_GATE_RES) x = bf2f(p.res[rrow + nb + e]) + round_bf16(bf2f(gate[nb + e]) * x);
-            else if (p.epi == DK_EPI_RES) x += bf2f(p.res[rrow + nb + e]);
-            p.C[crow + nb + e] = f2bf(x);
+            else if (p.epi == DK_EPI_GATE_RES) x = to_f32(p.res[rrow + nb + e]) + round_act(to_f32(gate[nb + e]) * x);
+            else if (p.epi == DK_EPI_RES) x += to_f32(p.res[rrow + nb + e]);
+            p.C[crow + nb + e] = from_f32(x);
           }
         }
       }
@@ -230,6 +230,7 @@ __global__ __launch_bounds__(256) void dk_gemm_bf16_kernel(GemmParams p) {
   }
 }
 
+#ifndef DK_ELEM_F16  // (gemm_f16.hip compiles the kernel above and its launcher below a second time, inside namespace dk_f16)
 // ---------------- routing: kernel, tile height and K split of one call (dk_gemm_route), read by the launches and by dk_gemm_plan ----------------
 
 // tuning knob (dk_tune_set("gemm", v)): -1 = automatic choice, 128 = always the 128^2-tile kernel of this file, 9 = the 256^2 kernel
@@ -352,6 +353,9 @@ static GemmRoute route_v4(const GemmParams& p, const GemmParams* p2, int n_cu) {
   return tile_route(4, 32 * mf, 256, p, p2, n_cu);
 }
 
+// gemm256v4.hip is a bf16 kernel (generated asm body): an fp16 launch never goes there, whatever dk_tune_set("gemm", 10) / ("gemm_v4", v) say
+static bool v4_ok(const GemmParams& p) { return p.dtype == DK_DTYPE_BF16 && dk_gemm256v4_eligible(p); }
+
 // Which of the two 256^2 kernels takes a launch both accept (v3 / v4: its route on each).  gemm256v4.hip (one wave per SIMD, asm body) runs its K loop
 // 5-7 % faster (profiles/r05_gemm_v4_*.log: 8192^3 1587 against 1488 TF with cold weights, the model's linear1 / linear2 / fc1 / fc2 +4-5 %), but has no
 // remainder handling: gemm256v3.hip keeps the launches whose last round of the CUs is a small remainder (its 224-row tiles and the
@@ -383,7 +387,7 @@ static bool use_v4(const GemmParams& p, const GemmParams* p2, const GemmRoute& v
 // the grouped launch of an image + text pair (same N, K, epilogue), or PAIR: two launches
 static int route_pair(const GemmParams& a, const GemmParams& b, int n_cu, GemmRoute& r) {
   r.kernel = GemmRoute::PAIR;
-  const bool same = a.N == b.N && a.K == b.K && a.epi == b.epi && a.alpha == b.alpha && a.n_split == 0 && b.n_split == 0;
+  const bool same = a.N == b.N && a.K == b.K && a.epi == b.epi && a.alpha == b.alpha && a.n_split == 0 && b.n_split == 0 && a.dtype == b.dtype;
   if (!((g_dk_gemm_mode == -1 || g_dk_gemm_mode == 10) && same && (a.M >= 1024 || b.M >= 1024) && (a.N % 256 == 0 || a.N >= 1024) &&
         dk_gemm256v3_eligible(a) && dk_gemm256v3_eligible(b)))
     return 0;
@@ -395,7 +399,7 @@ static int route_pair(const GemmParams& a, const GemmParams& b, int n_cu, GemmRo
   const bool split_ok = g_dk_v3_split != 0 && a.workspace != nullptr && (ta + tb) % nc <= nc / 4 && a.K / 64 >= (g_dk_pair_split_nk >= 0 ? g_dk_pair_split_nk : 24);
   const GemmRoute v3 = route_v3(a, &b, n_cu);
   // (gemm256v4.hip: the same test at ITS tile height -- with 224-row tiles the image + text fc1 of FLUX is 912 + 96 tiles: both 4 rounds)
-  if (dk_gemm256v4_eligible(a) && dk_gemm256v4_eligible(b)) {
+  if (v4_ok(a) && v4_ok(b)) {
     const GemmRoute v4 = route_v4(a, &b, n_cu);
     const long ta4 = v4.tiles_a, tb4 = v4.tiles_b;
     if ((ta4 + nc - 1) / nc == (ta4 + tb4 + nc - 1) / nc && use_v4(a, &b, v3, v4)) {
@@ -413,6 +417,7 @@ static int route_pair(const GemmParams& a, const GemmParams& b, int n_cu, GemmRo
 int dk_gemm_route(const GemmParams& p, const GemmParams* p2, int n_cu, GemmRoute& r) {
   if (p2 != nullptr) return route_pair(p, *p2, n_cu, r);
   DK_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0, "empty GEMM");
+  DK_REQUIRE(p.dtype == DK_DTYPE_BF16 || (p.dtype == DK_DTYPE_F16 && !p.conv), "element type: 0 bf16, 1 fp16 (Linears only: the convolutions are bf16)");
   DK_REQUIRE(p.ldw >= p.K && p.ldw % 8 == 0, "ldw must be >= K and a multiple of 8 elements");
   // the 256^2 kernel (16x16x32 MFMA, LDS-DMA ring, any M and any row-segment map) takes every large-M shape it accepts; small M
   // (modulation tables, embedders, a lone text stream) and N % 256 != 0 stay on the 128^2 tiles
@@ -421,11 +426,11 @@ int dk_gemm_route(const GemmParams& p, const GemmParams* p2, int n_cu, GemmRoute
   //  N such as the VAE's 128-channel shortcut Linear stays on the 128^2 tiles: ADVICE r4)
   const bool half_ok = p.N % 256 == 0 || p.N >= 1024 || g_dk_gemm_mode == 9;
   const bool big = !p.conv && g_dk_gemm_mode != 128 && half_ok && dk_gemm256v3_eligible(p) &&
-                   (p.M >= 1024 || g_dk_gemm_mode == 9 || (g_dk_gemm_mode == 10 && dk_gemm256v4_eligible(p)));
+                   (p.M >= 1024 || g_dk_gemm_mode == 9 || (g_dk_gemm_mode == 10 && v4_ok(p)));
   if (g_dk_gemm_mode == 9 && !p.conv) DK_REQUIRE(big, "gemm256v3 forced but the shape does not allow it");
   if (big) {
     r = route_v3(p, nullptr, n_cu);
-    if (dk_gemm256v4_eligible(p)) {
+    if (v4_ok(p)) {
       const GemmRoute v4 = route_v4(p, nullptr, n_cu);
       if (use_v4(p, nullptr, r, v4)) r = v4;
     }
@@ -467,23 +472,35 @@ int dk_gemm_route(const GemmParams& p, const GemmParams* p2, int n_cu, GemmRoute
   return 0;
 }
 
-static int launch_gemm128(const GemmParams& p, const GemmRoute& r, hipStream_t stream) {
+#endif  // !DK_ELEM_F16
+
+// the 128^2-tile kernel in this unit's element type (fp16: Linears only)
+int dk_launch_gemm128(const GemmParams& p, const GemmRoute& r, hipStream_t stream) {
+#ifndef DK_ELEM_F16
+  if (p.dtype == DK_DTYPE_F16) return dk_f16::dk_launch_gemm128(p, r, stream);
+#endif
   static DkDeviceOnce attr_once;
   if (attr_once.first()) {
     DK_CHECK_HIP(hipFuncSetAttribute((const void*)dk_gemm_bf16_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE_BYTES));
+#ifndef DK_ELEM_F16
     DK_CHECK_HIP(hipFuncSetAttribute((const void*)dk_gemm_bf16_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE_BYTES));
+#endif
     attr_once.mark();
   }
   dim3 grid(r.tiles_a), block(256);
   dk_prof_begin(p.conv ? 1 : 0, 2.0 * (double)p.M * (double)p.N * (double)p.K, stream);
+#ifndef DK_ELEM_F16
   if (p.conv)
     hipLaunchKernelGGL(dk_gemm_bf16_kernel<1>, grid, block, 2 * STAGE_BYTES, stream, p);
   else
+#endif
     hipLaunchKernelGGL(dk_gemm_bf16_kernel<0>, grid, block, 2 * STAGE_BYTES, stream, p);
   dk_prof_end(stream);
   DK_CHECK_HIP(hipGetLastError());
   return 0;
 }
+
+#ifndef DK_ELEM_F16
 
 // One call: its route, then the launch -- or the calls an expansion is made of.  With `rec` (dk_gemm_plan) every launch is recorded instead:
 // `launches` counts them, the other fields describe the last GEMM launch.
@@ -520,7 +537,7 @@ static int gemm_call(const GemmParams& p_in, const GemmParams* p2_in, hipStream_
       rec->launches += 1;  // (the stand-alone pass)
       return 0;
     }
-    return dk_launch_qk_norm_rope(p.C, p.ldc, p.qn_w ? p.qn_col0 : 0, p.kn_col0, p.M, (p.kn_col1 - p.kn_col0) / p.kn_D, p.kn_D, p.qn_w ? p.qn_w : p.kn_w, p.kn_w,
+    return (p.dtype == DK_DTYPE_F16 ? dk_f16::dk_launch_qk_norm_rope : dk_launch_qk_norm_rope)(p.C, p.ldc, p.qn_w ? p.qn_col0 : 0, p.kn_col0, p.M, (p.kn_col1 - p.kn_col0) / p.kn_D, p.kn_D, p.qn_w ? p.qn_w : p.kn_w, p.kn_w,
                                   p.kn_eps, p.kn_rope, p.kn_seg_len, p.c_seg_len == p.kn_seg_len ? p.c_seg_stride : p.kn_seg_len, p.kn_pos_off, 0,
                                   stream, p.qn_w ? 0 : 1);
   }
@@ -532,7 +549,7 @@ static int gemm_call(const GemmParams& p_in, const GemmParams* p2_in, hipStream_
   }
   if (r.kernel == 3) return dk_launch_gemm256v3(p, second, r, stream);
   if (r.kernel == 4) return dk_launch_gemm256v4(p, second, r, stream);
-  return launch_gemm128(p, r, stream);
+  return dk_launch_gemm128(p, r, stream);
 }
 
 int dk_launch_gemm(const GemmParams& p, hipStream_t stream) { return gemm_call(p, nullptr, stream, nullptr); }
@@ -541,3 +558,4 @@ int dk_gemm_plan_call(const GemmParams& p, const GemmParams* p2, dk_gemm_plan_t&
   rec = dk_gemm_plan_t{};
   return gemm_call(p, p2, nullptr, &rec);
 }
+#endif  // !DK_ELEM_F16

@@ -344,8 +344,8 @@ __global__ __launch_bounds__(512, 2) void dk_gemm256v3_kernel(GemmParams pa, Gem
     _Pragma("unroll") for (int e_ = (E0); e_ < (E1); ++e_) {                                                           \
       if (!(DK_V3_ABL & 1) && (NG) > 0 && (ON) && e_ >= (PH) && ((e_ - (PH)) % (NM)) == 0 && ((e_ - (PH)) / (NM)) < (NG)) \
         issue_piece((TILE), (G0) + ((e_ - (PH)) / (NM)));                                                         \
-      acc[e_ / (NM)][(MB) + (e_ % (NM))] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf##WSET[e_ / (NM)], xf##ASET[e_ % (NM)], \
-                                                                                   acc[e_ / (NM)][(MB) + (e_ % (NM))], 0, 0, 0); \
+      acc[e_ / (NM)][(MB) + (e_ % (NM))] = mfma_16x16x32(wf##WSET[e_ / (NM)], xf##ASET[e_ % (NM)], \
+                                                                                   acc[e_ / (NM)][(MB) + (e_ % (NM))]);          \
       __builtin_amdgcn_sched_barrier(0);                                                                          \
     }                                                                                                             \
   } while (0)
@@ -428,7 +428,7 @@ __global__ __launch_bounds__(512, 2) void dk_gemm256v3_kernel(GemmParams pa, Gem
   }
 
   {
-    bf16x8 wf0[4], wf1[4], xf0[4], xf1[4];
+    ex8 wf0[4], wf1[4], xf0[4], xf1[4];
     // prologue: K-tile 0, then K-tile 1 (the loop's first wait lets only its own four weight pieces, of K-tile 2, stay in flight)
 #pragma unroll
     for (int gidx = 0; gidx < 8; ++gidx) issue_piece_to(0, gidx, wo_cur);
@@ -544,10 +544,10 @@ __global__ __launch_bounds__(512, 2) void dk_gemm256v3_kernel(GemmParams pa, Gem
   if (piece == 0 && !(DK_V3_ABL & 16)) dk_ksplit_wait(sp.flags, rt, n_prod, sp.error_word, leader);
 
   auto unpack8 = [](const uint4 v, float* f) {
-    unpack2bf(v.x, f[0], f[1]);
-    unpack2bf(v.y, f[2], f[3]);
-    unpack2bf(v.z, f[4], f[5]);
-    unpack2bf(v.w, f[6], f[7]);
+    unpack2(v.x, f[0], f[1]);
+    unpack2(v.y, f[2], f[3]);
+    unpack2(v.z, f[4], f[5]);
+    unpack2(v.w, f[6], f[7]);
   };
 
   // whole tiles: the bias of this lane's 16 columns (4 per 16-column fragment), all loads up front -- one latency, not one per pass
@@ -570,11 +570,11 @@ __global__ __launch_bounds__(512, 2) void dk_gemm256v3_kernel(GemmParams pa, Gem
 #pragma unroll
       for (int nf = 0; nf < 4; ++nf) {
         float b4[4];
-        unpack2bf(bias_q[nf][0], b4[0], b4[1]);
-        unpack2bf(bias_q[nf][1], b4[2], b4[3]);
+        unpack2(bias_q[nf][0], b4[0], b4[1]);
+        unpack2(bias_q[nf][1], b4[2], b4[3]);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float v = round_bf16(acc[nf][mf][e] * p.alpha + b4[e]);
+          const float v = round_act(acc[nf][mf][e] * p.alpha + b4[e]);
           ss += v * v;
         }
       }
@@ -592,7 +592,7 @@ __global__ __launch_bounds__(512, 2) void dk_gemm256v3_kernel(GemmParams pa, Gem
     constexpr bool STAGE = decltype(stage_c)::value, EMIT = decltype(emit_c)::value;
     const unsigned reg0 = (unsigned)wave * 16384u + ((STAGE && EMIT) ? 0u : (unsigned)ni * 8192u);  // this pass's image
     // stage: lane owns row mf*16 + l15, columns (nf & 1)*16 + 4*q + {0..3} of this 32-column half.  A whole tile (no K split)
-    // stages round_bf16(alpha * acc + bias) -- what every epilogue starts from -- as bf16: half the LDS bytes of the fp32 image
+    // stages round_act(alpha * acc + bias) -- what every epilogue starts from -- as bf16: half the LDS bytes of the fp32 image
     // (64-byte rows, 16-byte chunk c at position c ^ ((row >> 2) & 3): conflict-free for these 8-byte writes and the 16-byte
     // read-back); split tiles stage the fp32 partial sums (128-byte rows)
     const bool bf_stage = piece < 0;
@@ -601,15 +601,15 @@ __global__ __launch_bounds__(512, 2) void dk_gemm256v3_kernel(GemmParams pa, Gem
 #pragma unroll
       for (int nf = 0; nf < 2; ++nf) {
         float b4[4];
-        unpack2bf(bias_q[ni * 2 + nf][0], b4[0], b4[1]);
-        unpack2bf(bias_q[ni * 2 + nf][1], b4[2], b4[3]);
+        unpack2(bias_q[ni * 2 + nf][0], b4[0], b4[1]);
+        unpack2(bias_q[ni * 2 + nf][1], b4[2], b4[3]);
 #pragma unroll
         for (int mf = 0; mf < MF; ++mf) {
           const int row = mf * 16 + l15;
           const f32x4 a = acc[ni * 2 + nf][mf];
           uint2 w;
-          w.x = pack2bf(a[0] * p.alpha + b4[0], a[1] * p.alpha + b4[1]);
-          w.y = pack2bf(a[2] * p.alpha + b4[2], a[3] * p.alpha + b4[3]);
+          w.x = pack2(a[0] * p.alpha + b4[0], a[1] * p.alpha + b4[1]);
+          w.y = pack2(a[2] * p.alpha + b4[2], a[3] * p.alpha + b4[3]);
           *(__attribute__((address_space(3))) u32x2*)((lds_char*)0 + reg0 + row * 64 + (((nf * 2 + (q >> 1)) ^ ((row >> 2) & 3)) << 4) + (q & 1) * 8) = u32x2{w.x, w.y};
         }
       }
@@ -722,8 +722,8 @@ __global__ __launch_bounds__(512, 2) void dk_gemm256v3_kernel(GemmParams pa, Gem
         if (!BF) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            vv[e] = round_bf16(a0[e] * p.alpha + bias8[e]);
-            vv[4 + e] = round_bf16(a1[e] * p.alpha + bias8[4 + e]);
+            vv[e] = round_act(a0[e] * p.alpha + bias8[e]);
+            vv[4 + e] = round_act(a1[e] * p.alpha + bias8[4 + e]);
           }
         }
         if (KF) {
@@ -731,7 +731,7 @@ __global__ __launch_bounds__(512, 2) void dk_gemm256v3_kernel(GemmParams pa, Gem
           if (p.kn_D == 128) ss += *(const __attribute__((address_space(3))) float*)((lds_char*)0 + XCH_OFF + ((wave ^ 1) * 128 + row) * 4);
           const float r = rsqrtf(ss / (float)p.kn_D + p.kn_eps);
 #pragma unroll
-          for (int e = 0; e < 8; ++e) vv[e] = round_bf16(vv[e] * r * kw8[e]);
+          for (int e = 0; e < 8; ++e) vv[e] = round_act(vv[e] * r * kw8[e]);
           if (p.kn_rope != nullptr) {
             const float* tab = p.kn_rope + ((size_t)(p.kn_pos_off + kpos) * (size_t)(p.kn_D / 2) + (size_t)(kcol >> 1)) * 2;
             f32x4 t0 = {1.f, 0.f, 1.f, 0.f}, t1 = {1.f, 0.f, 1.f, 0.f};
@@ -763,17 +763,17 @@ __global__ __launch_bounds__(512, 2) void dk_gemm256v3_kernel(GemmParams pa, Gem
           unpack8(rr, r8);
           if (ep == DK_EPI_GATE_RES) {
 #pragma unroll
-            for (int e = 0; e < 8; ++e) vv[e] = r8[e] + round_bf16(gate8[e] * vv[e]);
+            for (int e = 0; e < 8; ++e) vv[e] = r8[e] + round_act(gate8[e] * vv[e]);
           } else {
 #pragma unroll
             for (int e = 0; e < 8; ++e) vv[e] += r8[e];
           }
         }
         uint4 o4;
-        o4.x = pack2bf(vv[0], vv[1]);
-        o4.y = pack2bf(vv[2], vv[3]);
-        o4.z = pack2bf(vv[4], vv[5]);
-        o4.w = pack2bf(vv[6], vv[7]);
+        o4.x = pack2(vv[0], vv[1]);
+        o4.y = pack2(vv[2], vv[3]);
+        o4.z = pack2(vv[4], vv[5]);
+        o4.w = pack2(vv[6], vv[7]);
         // (lab: 32 = the C stores sit behind a condition that is false at run time -- the work stays, the traffic goes)
         if (((DK_V3_ABL & 32) ? p.alpha == -1234.5f : true) && (FAST || valid)) {
 #if DK_V3_NT_STORE
@@ -831,6 +831,7 @@ __global__ __launch_bounds__(512, 2) void dk_gemm256v3_kernel(GemmParams pa, Gem
     dk_ksplit_release(sp.flags, rt, n_prod, leader);
 }
 
+#ifndef DK_ELEM_F16  // (one copy: gemm256v3_f16.hip compiles this file a second time inside namespace dk_f16 for the kernel and its launcher)
 bool dk_gemm256v3_eligible(const GemmParams& p) {
   if (p.M <= 0 || p.N % 128 != 0 || p.K % BK != 0 || (!p.conv && p.lda % 8 != 0) || p.ldw % 8 != 0 || p.ldc % 8 != 0) return false;
   if (p.conv) {  // 3x3 / pad 1 / stride 1 (optionally over the nearest-x2 view); pixel packed as b:8 | y:12 | x:12, 31-bit byte offsets
@@ -855,16 +856,24 @@ bool dk_gemm256v3_eligible(const GemmParams& p) {
 }
 
 size_t dk_gemm_split_workspace_bytes() { return DK_KSPLIT_WS_BYTES; }
+#endif
 
 // tile-parallel launch of `p` and, optionally, a second problem `p2` with the same N, K, alpha and epilogue: tile height, tiles and K split
 // as routed (dk_gemm_route)
 int dk_launch_gemm256v3(const GemmParams& p, const GemmParams* p2, const GemmRoute& r, hipStream_t stream) {
+#ifndef DK_ELEM_F16
+  if (p.dtype == DK_DTYPE_F16) return dk_f16::dk_launch_gemm256v3(p, p2, r, stream);
+#else
+  DK_REQUIRE(!p.conv, "gemm256v3: the fp16 form takes Linears only");
+#endif
   static DkDeviceOnce attr_once;
   if (attr_once.first()) {
     DK_CHECK_HIP(hipFuncSetAttribute((const void*)dk_gemm256v3_kernel<8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
     DK_CHECK_HIP(hipFuncSetAttribute((const void*)dk_gemm256v3_kernel<7, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
+#ifndef DK_ELEM_F16
     DK_CHECK_HIP(hipFuncSetAttribute((const void*)dk_gemm256v3_kernel<8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
     DK_CHECK_HIP(hipFuncSetAttribute((const void*)dk_gemm256v3_kernel<7, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
+#endif
     attr_once.mark();
   }
   SplitArgs sp;
@@ -880,12 +889,15 @@ int dk_launch_gemm256v3(const GemmParams& p, const GemmParams* p2, const GemmRou
   double work = 2.0 * (double)p.M * (double)p.N * (double)p.K;
   if (p2) work += 2.0 * (double)p2->M * (double)p2->N * (double)p2->K;
   dk_prof_begin(p.conv ? 1 : 0, work, stream);
+#ifndef DK_ELEM_F16
   if (p.conv) {
     if (r.tile_rows == 256)
       hipLaunchKernelGGL((dk_gemm256v3_kernel<8, true>), dim3(grid), dim3(512), LDS_BYTES, stream, p, pb, r.tiles_a, r.tiles_b, sp);
     else
       hipLaunchKernelGGL((dk_gemm256v3_kernel<7, true>), dim3(grid), dim3(512), LDS_BYTES, stream, p, pb, r.tiles_a, r.tiles_b, sp);
-  } else if (r.tile_rows == 256)
+  } else
+#endif
+  if (r.tile_rows == 256)
     hipLaunchKernelGGL((dk_gemm256v3_kernel<8, false>), dim3(grid), dim3(512), LDS_BYTES, stream, p, pb, r.tiles_a, r.tiles_b, sp);
   else
     hipLaunchKernelGGL((dk_gemm256v3_kernel<7, false>), dim3(grid), dim3(512), LDS_BYTES, stream, p, pb, r.tiles_a, r.tiles_b, sp);

@@ -17,6 +17,7 @@ from .config import MMDiTConfig, PositionalEncoding, VAEDecoderConfig
 
 Tensor = torch.Tensor
 _EMBED_DTYPE = {"bfloat16": 0, "float16": 1, "float32": 2}
+_ACT_DTYPE = {"bfloat16": (0, torch.bfloat16), "float16": (1, torch.float16)}
 
 
 def _stream() -> int:
@@ -74,9 +75,17 @@ class MMDiTEngine:
         h = C.c_void_p()
         _lib.check(self.lib.dk_mmdit_create(C.byref(c), C.byref(h)), "dk_mmdit_create")
         self._h = h
+        from .config import validate_activation_dtype
+        try:
+            validate_activation_dtype(config)
+        except ValueError as e:
+            raise _lib.DkHipError(str(e)) from None
+        # element type of the weights and of tokens / text / pooled at this boundary (set before the first bind; 0 is the engine's default)
+        code, self.dtype = _ACT_DTYPE[config.activation_dtype]
+        _lib.check(self.lib.dk_mmdit_set_activation_dtype(self._h, code), "dk_mmdit_set_activation_dtype")
         self.weights = packed_weights  # keep the device tensors alive
         for name, t in packed_weights.items():
-            want = torch.uint8 if name.endswith(".weight_fp8") else torch.float32 if name.endswith(".wscale") else torch.bfloat16
+            want = torch.uint8 if name.endswith(".weight_fp8") else torch.float32 if name.endswith(".wscale") else self.dtype
             _require_cuda(t, name, want)
             _lib.check(self.lib.dk_mmdit_bind(self._h, name.encode(), t.data_ptr()), f"bind {name}")
         self.guidance = 3.5  # FLUX.1-dev's default distilled-guidance strength; only read when config.guidance_embed
@@ -139,7 +148,7 @@ class MMDiTEngine:
         already rounded to the activation dtype (quirk Q1)."""
         if self._shape is None:
             raise _lib.DkHipError("prepare() must be called before cache_modulation_params()")
-        pooled = pooled_text_embeddings.to(torch.bfloat16).contiguous()
+        pooled = pooled_text_embeddings.to(self.dtype).contiguous()
         _require_cuda(pooled, "pooled_text_embeddings")
         if pooled.shape != (self._shape[0], self.config.pooled_text_embed_dim):
             raise _lib.DkHipError(f"pooled_text_embeddings shape {tuple(pooled.shape)} != (batch, pooled_dim)")
@@ -155,7 +164,7 @@ class MMDiTEngine:
     def cache_context(self, text: Tensor) -> None:
         """Step-invariant hoist of ``context_embedder(text)`` (mmdit.py:195): embedded once here, ``forward_tokens(..., None, i)``
         then reuses it in every step (the reference recomputes the same values per call)."""
-        _require_cuda(text, "text", torch.bfloat16)
+        _require_cuda(text, "text", self.dtype)
         if tuple(text.shape) != (self._shape[0], self._shape[3], self.config.token_level_text_embed_dim):
             raise _lib.DkHipError(f"text shape {tuple(text.shape)} does not match the prepared problem")
         _lib.check(self.lib.dk_mmdit_cache_context(self._h, text.data_ptr(), _stream()), "dk_mmdit_cache_context")
@@ -163,14 +172,14 @@ class MMDiTEngine:
 
     def forward_tokens(self, tokens_in: Tensor, text: Optional[Tensor], step_index: int, tokens_out: Optional[Tensor] = None) -> Tensor:
         """MMDiT.__call__ between patchify and unpatchify (mmdit.py:188-252).  ``text=None`` uses ``cache_context``'s result."""
-        _require_cuda(tokens_in, "tokens_in", torch.bfloat16)
+        _require_cuda(tokens_in, "tokens_in", self.dtype)
         if tuple(tokens_in.shape) != self.tokens_shape():
             raise _lib.DkHipError(f"tokens_in shape {tuple(tokens_in.shape)} != {self.tokens_shape()}")
         if text is None:
             if not getattr(self, "_ctx_cached", False):
                 raise _lib.DkHipError("forward_tokens(text=None) needs cache_context(text) after prepare()")
         else:
-            _require_cuda(text, "text", torch.bfloat16)
+            _require_cuda(text, "text", self.dtype)
             if tuple(text.shape) != (self._shape[0], self._shape[3], self.config.token_level_text_embed_dim):
                 raise _lib.DkHipError(f"text shape {tuple(text.shape)} does not match the prepared problem")
         if not (0 <= step_index < self._n_cached):
@@ -185,7 +194,7 @@ class MMDiTEngine:
         """MultiModalTransformerBlock / UnifiedTransformerBlock.__call__ (mmdit.py:568-675, 693-751) on a caller-supplied joint
         residual stream ``x`` (bf16 [batch, S_t + S_i, h], text rows first): blocks ``first_block .. first_block + n_blocks - 1`` of
         the global order (double blocks, then single blocks) with the modulation cached for ``step_index``."""
-        _require_cuda(x, "x", torch.bfloat16)
+        _require_cuda(x, "x", self.dtype)
         b, hl, wl, s_t, _ = self._shape
         p = self.config.patch_size
         want = (b, s_t + (hl // p) * (wl // p), self.config.hidden_size)
@@ -203,8 +212,9 @@ class MMDiTEngine:
         _require_cuda(latent, "latent", torch.float32)
         n, hl, wl, c = latent.shape
         p = self.config.patch_size
-        tok = torch.empty(n * dup, (hl // p) * (wl // p), p * p * c, dtype=torch.bfloat16, device=latent.device)
-        _lib.check(self.lib.dk_latent_to_tokens(latent.data_ptr(), tok.data_ptr(), n, dup, hl, wl, c, p,
+        tok = torch.empty(n * dup, (hl // p) * (wl // p), p * p * c, dtype=self.dtype, device=latent.device)
+        fn = self.lib.dk_latent_to_tokens_f16 if self.dtype == torch.float16 else self.lib.dk_latent_to_tokens
+        _lib.check(fn(latent.data_ptr(), tok.data_ptr(), n, dup, hl, wl, c, p,
                                                 int(self.config.patchify_via_reshape), _stream()), "dk_latent_to_tokens")
         return tok
 
@@ -216,7 +226,7 @@ class MMDiTEngine:
         text = token_level_text_embeddings
         if text.dim() == 4:  # reference passes [B, S_t, 1, T]
             text = text.squeeze(2)
-        out = self.forward_tokens(tok, text.to(torch.bfloat16).contiguous(), step_index)
+        out = self.forward_tokens(tok, text.to(self.dtype).contiguous(), step_index)
         return unpatchify_tokens(out, self.config, lat.shape[1], lat.shape[2])
 
 

@@ -18,6 +18,16 @@ from .engine import _ptr, _require_cuda, _stream
 
 Tensor = torch.Tensor
 BF = torch.bfloat16
+F16 = torch.float16
+
+
+def _elem(dtype, what: str) -> str:
+    """suffix of the operator entry for an element type: the SD3-path operators exist as ``*_bf16`` and ``*_f16`` (include/dk_hip.h)"""
+    if dtype == BF:
+        return "bf16"
+    if dtype == F16:
+        return "f16"
+    raise _lib.DkHipError(f"{what}: element type must be torch.bfloat16 or torch.float16, got {dtype}")
 
 
 def tune(key: str, value: int) -> None:
@@ -39,14 +49,15 @@ def gemm_workspace(device) -> Tensor:
 def linear(x: Tensor, w: Tensor, bias: Optional[Tensor] = None, epilogue: int = DK_EPI_BIAS,
            gate: Optional[Tensor] = None, res: Optional[Tensor] = None, gate_seg_len: int = 0,
            alpha: float = 1.0, out: Optional[Tensor] = None, workspace: Optional[Tensor] = None) -> Tensor:
-    """nn.Linear (+ fused epilogue).  x: [M, K]; w: [N, K]; gate: [n_batch, N]; res: [M, N]."""
+    """nn.Linear (+ fused epilogue).  x: [M, K]; w: [N, K]; gate: [n_batch, N]; res: [M, N].  bf16 tensors, or all float16 (dk_gemm_f16)."""
     lib = _lib.load()
+    el = _elem(x.dtype, "linear")
     for n, t in (("x", x), ("w", w)):
-        _require_cuda(t, n, BF)
+        _require_cuda(t, n, x.dtype)
     M, K = x.shape
     N = w.shape[0]
     if out is None:
-        out = torch.empty(M, N, dtype=BF, device=x.device)
+        out = torch.empty(M, N, dtype=x.dtype, device=x.device)
     d = _lib.dk_gemm_desc()
     d.A, d.W, d.C = x.data_ptr(), w.data_ptr(), out.data_ptr()
     d.bias, d.gate, d.res = _ptr(bias), _ptr(gate), _ptr(res)
@@ -57,18 +68,28 @@ def linear(x: Tensor, w: Tensor, bias: Optional[Tensor] = None, epilogue: int = 
     d.alpha, d.epilogue = alpha, epilogue
     if workspace is not None:
         d.workspace, d.workspace_bytes = workspace.data_ptr(), workspace.numel()
-    _lib.check(lib.dk_gemm_bf16(C.byref(d), _stream()), "dk_gemm_bf16")
+    _lib.check(getattr(lib, "dk_gemm_" + el)(C.byref(d), _stream()), "dk_gemm_" + el)
     return out
 
 
-def gemm_desc_call(**kw) -> None:
+def gemm_desc_call(dtype=BF, **kw) -> None:
     """Raw descriptor call (segment mappings etc.); keyword names = dk_gemm_desc fields,
-    tensors are converted to pointers."""
+    tensors are converted to pointers.  ``dtype``: element type of every tensor named (bf16 | float16)."""
     lib = _lib.load()
+    el = _elem(dtype, "gemm_desc_call")
     d = _lib.dk_gemm_desc()
     for k, v in kw.items():
         setattr(d, k, v.data_ptr() if isinstance(v, torch.Tensor) else v)
-    _lib.check(lib.dk_gemm_bf16(C.byref(d), _stream()), "dk_gemm_bf16")
+    _lib.check(getattr(lib, "dk_gemm_" + el)(C.byref(d), _stream()), "dk_gemm_" + el)
+
+
+def gemm_plan(d: dict, d2: Optional[dict] = None, dtype=BF):
+    """dk_gemm_plan / dk_gemm_plan_f16: what the call would launch (host only; pointers may be made-up, aligned integers)."""
+    a, b = _fill(_lib.dk_gemm_desc, d), _fill(_lib.dk_gemm_desc, d2)
+    plan = _lib.dk_gemm_plan_t()
+    name = "dk_gemm_plan" if _elem(dtype, "gemm_plan") == "bf16" else "dk_gemm_plan_f16"
+    _lib.check(getattr(_lib.load(), name)(_ref(a), _ref(b), C.byref(plan)), name)
+    return plan
 
 
 def _fill(struct, fields):
@@ -85,11 +106,12 @@ def _ref(s):
     return C.byref(s) if s is not None else None
 
 
-def gemm_fused_call(d: dict, side: Optional[dict] = None, d2: Optional[dict] = None, side2: Optional[dict] = None) -> None:
-    """dk_gemm_fused_bf16: the launch forms of the engines -- column split, QKNorm + RoPE in the tile tail, an image + text pair.
+def gemm_fused_call(d: dict, side: Optional[dict] = None, d2: Optional[dict] = None, side2: Optional[dict] = None, dtype=BF) -> None:
+    """dk_gemm_fused_bf16 (``dtype`` float16: dk_gemm_fused_f16): the launch forms of the engines -- column split, QKNorm + RoPE in the tile tail, an image + text pair.
     ``d`` / ``d2``: dk_gemm_desc fields, ``side`` / ``side2``: dk_gemm_side fields (tensors are converted to pointers)."""
     a, f, b, f2 = _fill(_lib.dk_gemm_desc, d), _fill(_lib.dk_gemm_side, side), _fill(_lib.dk_gemm_desc, d2), _fill(_lib.dk_gemm_side, side2)
-    _lib.check(_lib.load().dk_gemm_fused_bf16(_ref(a), _ref(f), _ref(b), _ref(f2), _stream()), "dk_gemm_fused_bf16")
+    name = "dk_gemm_fused_" + _elem(dtype, "gemm_fused_call")
+    _lib.check(getattr(_lib.load(), name)(_ref(a), _ref(f), _ref(b), _ref(f2), _stream()), name)
 
 
 def gemm_fused_plan(d: dict, side: Optional[dict] = None, d2: Optional[dict] = None, side2: Optional[dict] = None):
@@ -107,12 +129,13 @@ def gemm_fp8_fused_call(d: dict, side: Optional[dict] = None, d2: Optional[dict]
     _lib.check(_lib.load().dk_gemm_fp8_fused(_ref(a), _ref(f), _ref(b), _ref(f2), _stream()), "dk_gemm_fp8_fused")
 
 
-def attention_desc_call(**kw) -> None:
-    """dk_attention_desc_bf16: attention with the query QKNorm + RoPE in the Q load and / or the MX-fp8 output copy; keyword names =
+def attention_desc_call(dtype=BF, **kw) -> None:
+    """dk_attention_desc_bf16 (``dtype`` float16: dk_attention_desc_f16, head_dim 64): attention with the query QKNorm + RoPE in the Q load and / or the MX-fp8 output copy; keyword names =
     dk_attention_desc fields."""
     _lib.ensure_attention_workspace(torch.cuda.current_device())
     d = _fill(_lib.dk_attention_desc, kw)
-    _lib.check(_lib.load().dk_attention_desc_bf16(C.byref(d), _stream()), "dk_attention_desc_bf16")
+    name = "dk_attention_desc_" + _elem(dtype, "attention_desc_call")
+    _lib.check(getattr(_lib.load(), name)(C.byref(d), _stream()), name)
 
 
 _zero_pages = {}
@@ -252,24 +275,32 @@ def attention(qkv: Tensor, H: int, D: int, scale: Optional[float] = None, worksp
 
 
 def ln_modulate(x: Tensor, shift: Tensor, scale: Tensor, eps: float = 1e-6) -> Tensor:
-    """x: [B, S, h]; shift/scale: [B, h] -> [B, S, h]."""
+    """x: [B, S, h]; shift/scale: [B, h] -> [B, S, h] (bf16, or all float16)."""
     lib = _lib.load()
-    _require_cuda(x, "x", BF)
+    name = "dk_ln_modulate_" + _elem(x.dtype, "ln_modulate")
+    _require_cuda(x, "x")
+    for n, t in (("shift", shift), ("scale", scale)):
+        if t.dtype != x.dtype:
+            raise _lib.DkHipError(f"{n} must be {x.dtype}, got {t.dtype}")
     B, S, h = x.shape
     out = torch.empty_like(x)
-    _lib.check(lib.dk_ln_modulate_bf16(x.data_ptr(), h, out.data_ptr(), h, B * S, h, shift.data_ptr(), scale.data_ptr(),
-                                       shift.stride(0), S, B * S, 0, eps, _stream()), "dk_ln_modulate_bf16")
+    _lib.check(getattr(lib, name)(x.data_ptr(), h, out.data_ptr(), h, B * S, h, shift.data_ptr(), scale.data_ptr(),
+                                  shift.stride(0), S, B * S, 0, eps, _stream()), name)
     return out
 
 
 def qk_norm_rope_(qkv: Tensor, H: int, D: int, qw: Optional[Tensor], kw: Optional[Tensor],
                   rope: Optional[Tensor], pos_off: int = 0, eps: float = 1e-6) -> Tensor:
-    """In place on qkv [B, S, 3*H*D]; rope: f32 [S_pos, D/2, 2]."""
+    """In place on qkv [B, S, 3*H*D] (bf16, or float16 with float16 weights); rope: f32 [S_pos, D/2, 2]."""
     lib = _lib.load()
-    _require_cuda(qkv, "qkv", BF)
+    name = "dk_qk_norm_rope_" + _elem(qkv.dtype, "qk_norm_rope_")
+    _require_cuda(qkv, "qkv")
+    for n, t in (("qw", qw), ("kw", kw)):
+        if t is not None and t.dtype != qkv.dtype:
+            raise _lib.DkHipError(f"{n} must be {qkv.dtype}, got {t.dtype}")
     B, S, ld = qkv.shape
-    _lib.check(lib.dk_qk_norm_rope_bf16(qkv.data_ptr(), ld, 0, H * D, B * S, H, D, _ptr(qw), _ptr(kw), eps, _ptr(rope),
-                                        S, S, pos_off, _stream()), "dk_qk_norm_rope_bf16")
+    _lib.check(getattr(lib, name)(qkv.data_ptr(), ld, 0, H * D, B * S, H, D, _ptr(qw), _ptr(kw), eps, _ptr(rope),
+                                  S, S, pos_off, _stream()), name)
     return qkv
 
 
@@ -282,13 +313,27 @@ def rope_table(S_txt: int, gh: int, gw: int, axes, theta: float, device) -> Tens
     return t
 
 
-def timestep_embedding(t: Tensor, dim: int, max_period: float, embed_dtype: int) -> Tensor:
+def timestep_embedding(t: Tensor, dim: int, max_period: float, embed_dtype: int, dtype=BF) -> Tensor:
+    """evaluated in ``embed_dtype`` (0 bf16, 1 fp16, 2 fp32), stored as ``dtype`` (bf16 | float16)"""
     lib = _lib.load()
     _require_cuda(t, "t", torch.float32)
-    out = torch.empty(t.numel(), dim, dtype=BF, device=t.device)
-    _lib.check(lib.dk_timestep_embedding_bf16(t.data_ptr(), t.numel(), dim, float(max_period), embed_dtype, out.data_ptr(),
-                                              _stream()), "dk_timestep_embedding_bf16")
+    name = "dk_timestep_embedding_" + _elem(dtype, "timestep_embedding")
+    out = torch.empty(t.numel(), dim, dtype=dtype, device=t.device)
+    _lib.check(getattr(lib, name)(t.data_ptr(), t.numel(), dim, float(max_period), embed_dtype, out.data_ptr(), _stream()), name)
     return out
+
+
+def euler_cfg_step(x: Tensor, model_out: Tensor, tokens: Tensor, n_img: int, cfg_on: bool, p: int, reshape_order: int, sigma: float,
+                   sigma_next: float, cfg_weight: float) -> None:
+    """dk_euler_cfg_step / _f16 by the dtype of ``model_out``: x f32 [n_img, Hl, Wl, C] updated in place, ``tokens`` (same dtype as
+    ``model_out``) receives the next step's patchified input."""
+    name = "dk_euler_cfg_step" + ("" if _elem(model_out.dtype, "euler_cfg_step") == "bf16" else "_f16")
+    _require_cuda(x, "x", torch.float32)
+    _require_cuda(model_out, "model_out")
+    _require_cuda(tokens, "tokens", model_out.dtype)
+    _, hl, wl, c = x.shape
+    _lib.check(getattr(_lib.load(), name)(x.data_ptr(), model_out.data_ptr(), model_out.shape[-1], tokens.data_ptr(), n_img, int(cfg_on), hl, wl, c,
+                                          p, reshape_order, float(sigma), float(sigma_next), float(cfg_weight), _stream()), name)
 
 
 def groupnorm(x: Tensor, gamma: Tensor, beta: Tensor, groups: int, eps: float, silu: bool) -> Tensor:

@@ -17,6 +17,7 @@ from __future__ import annotations
 import hashlib
 import logging
 import time
+from dataclasses import replace
 from typing import Callable, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -97,6 +98,7 @@ class DiffusionPipeline:
         weights_seed: int = 1234,
         text_len: Optional[int] = None,
         packed_weights: Optional[dict] = None,
+        activation_dtype: Optional[str] = None,
     ):
         _lib.load()  # fail loudly before anything else if the HIP extension is missing
         # The MI355X build computes in bf16 end to end (BASELINE.json configs); w16/a16 are
@@ -108,6 +110,15 @@ class DiffusionPipeline:
         self.float16_dtype = torch.bfloat16
         self.dtype = torch.bfloat16
         self.activation_dtype = torch.bfloat16
+        # activation_dtype="float16": the MMDiT engine, the conditioning hand-over, the CFG denoiser and the Euler loop run in the reference's
+        # dtype for Stable Diffusion 3 (fp16 weights and activations, mlx/__init__.py:76-79); the text encoders and the VAE stay bf16
+        # (DESIGN.md section 8).  None (default): bf16, exactly as before
+        if activation_dtype not in (None, "bfloat16", "float16"):
+            raise ValueError(f"unknown activation_dtype {activation_dtype!r} (bfloat16 | float16)")
+        if activation_dtype == "float16":
+            if self._IS_FLUX:
+                raise ValueError("activation_dtype float16 is the SD3 family's (head_dim 64, no single-stream blocks); FLUX runs in bfloat16")
+            self.float16_dtype = self.dtype = self.activation_dtype = torch.float16
         # The model timesteps are host floats rounded to the REFERENCE pipeline's 16-bit dtype (quirk Q1): mx.float16 for
         # DiffusionPipeline (mlx/__init__.py:76-79,683,770), mx.bfloat16 for FluxPipeline (:610-613) -- 857.69 -> 857.5 in
         # fp16, 856 in bf16; the adaLN table is computed on these values.
@@ -119,6 +130,12 @@ class DiffusionPipeline:
         self.local_ckpt = local_ckpt
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.mmdit_config = mmdit_config or MODEL_CONFIG[model_version]
+        if activation_dtype is not None:
+            from .config import validate_activation_dtype
+            self.mmdit_config = replace(self.mmdit_config, activation_dtype=activation_dtype)
+            validate_activation_dtype(self.mmdit_config)
+        elif self.mmdit_config.activation_dtype == "float16":  # a float16_config() passed as mmdit_config
+            self.float16_dtype = self.dtype = self.activation_dtype = torch.float16
         self.vae_config = vae_config or VAEDecoderConfig()
         self.vae_encoder_config = vae_encoder_config or VAEEncoderConfig()
         self.weights_seed = weights_seed
@@ -510,6 +527,8 @@ class CFGDenoiser:
         mm = self.model.mmdit
         cfg_on = cfg_weight > 0
         tok = mm.patchify(x_t.contiguous(), dup=2 if cfg_on else 1)
+        if mm.dtype == torch.float16:  # (bf16 -> fp16 of the encoders' output: exact in range)
+            conditioning = conditioning.to(torch.float16).contiguous()
         out = mm.forward_tokens(tok, conditioning, self.step_index(timestep))
         den = x_t.clone()
         _euler(self.model, den, out, tok, cfg_on, float(sigma), 0.0, float(cfg_weight))  # x + d*(0 - sigma) = x0
@@ -520,9 +539,10 @@ def _euler(pipe, x, model_out, tok, cfg_on, sigma, sigma_next, cfg_weight):
     cfg = pipe.mmdit_config
     n_img, hl, wl, c = x.shape
     lib = _lib.load()
-    _lib.check(lib.dk_euler_cfg_step(x.data_ptr(), model_out.data_ptr(), model_out.shape[-1], tok.data_ptr(), n_img,
-                                     int(cfg_on), hl, wl, c, cfg.patch_size, int(cfg.patchify_via_reshape),
-                                     sigma, sigma_next, cfg_weight, _stream()), "dk_euler_cfg_step")
+    fn = lib.dk_euler_cfg_step_f16 if model_out.dtype == torch.float16 else lib.dk_euler_cfg_step  # (tokens in the engine's element type)
+    _lib.check(fn(x.data_ptr(), model_out.data_ptr(), model_out.shape[-1], tok.data_ptr(), n_img,
+                  int(cfg_on), hl, wl, c, cfg.patch_size, int(cfg.patchify_via_reshape),
+                  sigma, sigma_next, cfg_weight, _stream()), "dk_euler_cfg_step")
 
 
 def append_dims(x, target_dims):
@@ -581,8 +601,9 @@ def sample_euler(model: CFGDenoiser, x: Tensor, sigmas, extra_args=None):
     conditioning, pooled = _tile_conditioning(conditioning, pooled, n_img, cfg_on, pipe._IS_FLUX)
     if conditioning.shape[0] != rows or pooled.shape[0] != rows:
         raise ValueError(f"conditioning batch {conditioning.shape[0]} does not match latent batch {rows}")
-    conditioning = conditioning.to(pipe.device, torch.bfloat16).contiguous()
-    pooled = pooled.to(pipe.device, torch.bfloat16).contiguous()
+    # (an fp16 engine: the bf16 -> fp16 cast of the encoders' output is exact in range)
+    conditioning = conditioning.to(pipe.device, mm.dtype).contiguous()
+    pooled = pooled.to(pipe.device, mm.dtype).contiguous()
 
     # model timesteps are sigma*1000 rounded to the reference pipeline's activation dtype (quirk Q1): fp16 for SD3, bf16 for FLUX
     timesteps = _round_to_dtype(pipe.sampler.timestep(sigmas), pipe.timestep_dtype)

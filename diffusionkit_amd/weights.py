@@ -234,12 +234,16 @@ BLOCK_LINEARS = (".attn.qkv", ".attn.o_proj", ".mlp.fc1", ".mlp.fc2", ".linear1"
 
 
 def pack_mmdit(cfg: MMDiTConfig, w: Dict[str, Tensor], device, consume: bool = False) -> Dict[str, Tensor]:
-    """Reference-named weights -> engine tensors (bf16, contiguous, on ``device``).
+    """Reference-named weights -> engine tensors (``cfg.activation_dtype``: bf16 by default; contiguous, on ``device``).
     ``consume=True`` pops source tensors as they are packed (halves peak memory at full size).
     With ``cfg.weight_dtype == "fp8_e4m3"`` the Linear matrices of the transformer blocks leave as
     "<name>.weight_fp8" (uint8 e4m3, rows at dk_weight_pitch_fp8) + "<name>.wscale" (fp32) instead of "<name>.weight"."""
     dev = torch.device(device)
-    bf = torch.bfloat16
+    # element type of every tensor the engine binds: cfg.activation_dtype.  float16: a value from an fp16 or fp32 source is rounded once to fp16,
+    # and an fp16 checkpoint tensor reaches the device bit for bit (same names, pitches and fusions)
+    from .config import validate_activation_dtype
+    validate_activation_dtype(cfg)
+    bf = torch.float16 if cfg.activation_dtype == "float16" else torch.bfloat16
     fp8 = cfg.weight_dtype == "fp8_e4m3"
     out: Dict[str, Tensor] = {}
     get = (lambda k: w.pop(k)) if consume else (lambda k: w[k])

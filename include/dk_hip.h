@@ -353,6 +353,35 @@ int dk_euler_cfg_step(float* x, const void* model_out, int32_t ld_out, void* tok
 /* LatentFormat.process_in/out, __init__.py:729-733: y = x * a + b (f32) */
 int dk_affine_f32(const float* x, float* y, int64_t n, float a, float b, void* stream);
 
+/* ---- float16 element type (the reference's dtype for Stable Diffusion 3, config.py:77-79) ----------------------------------
+ * Siblings of the *_bf16 operators above on IEEE-half tensors: same descriptors, strides in elements, 16-bit storage, fp32
+ * accumulation, the same rounding points with fp16 in place of bf16.  An fp32 -> fp16 store that overflows gives +-inf, as the
+ * reference's casts do (no clamp).  Every tensor a descriptor names (A, W, C, bias, gate, res, norm weights, q / k / v / out) is
+ * fp16; RoPE tables, the latent and timesteps stay fp32.
+ *  - GEMM: Linears only (no convolution); the route is the 128 x 128 kernel or the 256-column 8-wave kernel (generation 3) --
+ *    dk_gemm_plan_f16 never reports generation 4, and dk_tune_set("gemm", 10) / ("gemm_v4", v) have no effect on these launches.
+ *  - Attention: head_dim 64, no score bias, no MX-fp8 copy; always the lean kernel (dk_tune_set("attn", 9 / 10) have no effect).
+ *    Scores, running maximum and sum in fp32, P rounded to fp16 for the P.V product.
+ *  - dk_timestep_embedding_f16: evaluated in `embed_dtype` as before, stored as fp16.
+ *  - dk_euler_cfg_step_f16 / dk_latent_to_tokens_f16: model_out and tokens are fp16, the latent stays fp32. */
+int dk_gemm_f16(const dk_gemm_desc* d, void* stream);
+int dk_gemm_plan_f16(const dk_gemm_desc* d, const dk_gemm_desc* d2, dk_gemm_plan_t* plan);
+int dk_gemm_fused_f16(const dk_gemm_desc* d, const dk_gemm_side* f, const dk_gemm_desc* d2, const dk_gemm_side* f2, void* stream);
+int dk_attention_desc_f16(const dk_attention_desc* d, void* stream);
+int dk_ln_modulate_f16(const void* x, int32_t ldx, void* out, int32_t ldo, int32_t M, int32_t h,
+                       const void* shift, const void* scale, int32_t mod_stride, int32_t mod_seg_len,
+                       int32_t x_seg_len, int32_t x_seg_stride, float eps, void* stream);
+int dk_qk_norm_rope_f16(void* qkv, int32_t ld, int32_t q_off, int32_t k_off, int32_t rows, int32_t H,
+                        int32_t D, const void* q_weight, const void* k_weight, float eps, const float* rope_table,
+                        int32_t row_seg_len, int32_t row_seg_stride, int32_t pos_off, void* stream);
+int dk_timestep_embedding_f16(const float* t_dev, int32_t n, int32_t dim, float max_period,
+                              int32_t embed_dtype, void* out, void* stream);
+int dk_latent_to_tokens_f16(const float* x, void* tokens, int32_t n_img, int32_t dup, int32_t Hl, int32_t Wl,
+                            int32_t C, int32_t p, int32_t reshape_order, void* stream);
+int dk_euler_cfg_step_f16(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img,
+                          int32_t cfg_on, int32_t Hl, int32_t Wl, int32_t C, int32_t p, int32_t reshape_order,
+                          float sigma, float sigma_next, float cfg_weight, void* stream);
+
 /* nn.GroupNorm(pytorch_compatible=True) [+ nn.silu], vae.py:34,72,78,381,91,96,398.
  * x, y: NHWC bf16 [B, HW, C]; scratch_f32 needs dk_groupnorm_scratch_floats(B, G) floats. */
 size_t dk_groupnorm_scratch_floats(int32_t B, int32_t G);
@@ -421,6 +450,13 @@ int dk_mmdit_cache_modulation_params(dk_mmdit* m, const void* pooled, const floa
  * modulation vector -- the published FLUX.1-dev conditioning, which the reference's module tree declares (mmdit.py:31-36)
  * but whose call site (:219-220) it never reaches (quirk Q7). */
 int dk_mmdit_set_guidance(dk_mmdit* m, float guidance);
+
+/* Element type of the engine: 0 = bfloat16 (default), 1 = float16.  Call after dk_mmdit_create and before the first
+ * dk_mmdit_bind.  With 1 every bound weight / bias / table is fp16, every activation buffer holds fp16 (sizes unchanged), and
+ * tokens, text and pooled go in and come out as fp16; the modulation table, the context_embedder hoist and the final layer
+ * included.  Accepted only for SD3-family geometry -- head_dim == 64, depth_unified == 0, fp8_linears == 0 -- anything else
+ * returns an error that names the rule (dk_last_error). */
+int dk_mmdit_set_activation_dtype(dk_mmdit* m, int32_t dtype);
 
 /* Step-invariant hoist of `self.context_embedder(token_level_text_embeddings)` (mmdit.py:195, recomputed by the reference
  * in every MMDiT.__call__): embeds `text` (bf16 [batch, S_t, text_dim]) once into the engine's workspace; later
