@@ -202,6 +202,18 @@ SIGNATURES = {
     "dk_vae_encoder_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32]),
     "dk_vae_encode": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _sz, _vp]),
     "dk_latent_sample_f32": (_i32, [_vp, _i32, _vp, _vp, _i64, _i32, _vp]),
+    # float16 element type of the VAE halves and their operators
+    "dk_vae_set_dtype": (_i32, [_vp, _i32]),
+    "dk_latent_sample_f16": (_i32, [_vp, _i32, _vp, _vp, _i64, _i32, _vp]),
+    "dk_conv3x3_f16": (_i32, [C.POINTER(dk_conv_desc), _vp]),
+    "dk_conv3x3_plan": (_i32, [C.POINTER(dk_conv_desc), C.POINTER(dk_gemm_plan_t)]),
+    "dk_conv3x3_plan_f16": (_i32, [C.POINTER(dk_conv_desc), C.POINTER(dk_gemm_plan_t)]),
+    "dk_conv3x3_gn_f16": (_i32, [C.POINTER(dk_conv_gn_desc), _vp]),
+    "dk_groupnorm_table_f16": (_i32, [_vp, _i32, C.c_int64, _i32, _i32, _vp, _vp, C.c_float, _vp, _i32, _vp, _vp]),
+    "dk_groupnorm_f16": (_i32, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _f32, _i32, _vp, _vp]),
+    "dk_attention_d512_f16": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_float, _vp, _vp]),
+    "dk_softmax_rows_f16": (_i32, [_vp, _i32, _i32, _i32, _vp]),
+    "dk_transpose_f16": (_i32, [_vp, _vp, _i32, _i32, _vp]),
     "dk_profile_enable": (_i32, [_i32]),
     "dk_profile_read": (_i32, [_i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "dk_tune_set": (_i32, [C.c_char_p, _i32]),

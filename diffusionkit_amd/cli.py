@@ -61,7 +61,10 @@ def build_parser(model_versions: Sequence[str]) -> argparse.ArgumentParser:
                         "blocks keep bf16 Linears; speed: every block Linear in fp8.")
     p.add_argument("--activation-dtype", choices=("bfloat16", "float16"), default="bfloat16",
                    help="Element type of the MMDiT's weights and activations. float16 is the reference's dtype for Stable Diffusion 3 "
-                        "(SD3 versions only); the text encoders and the VAE stay bfloat16.")
+                        "(SD3 versions only); the text encoders stay bfloat16, the VAE has --vae-dtype.")
+    p.add_argument("--vae-dtype", choices=("bfloat16", "float16"), default=None,
+                   help="Element type of the VAE decoder and (img2img) encoder; default bfloat16. float16 is the reference's decoder dtype "
+                        "for Stable Diffusion 3 (not for FLUX); accepted for every model version.")
     p.add_argument("--device", default=None, help="HIP device, e.g. cuda:0 (default: the current device)")
     return p
 
@@ -102,6 +105,9 @@ def resolve(args) -> dict:
         from .config import MODEL_CONFIG, float16_config
         float16_config(r.get("mmdit_config", MODEL_CONFIG[args.model_version]))
         r["activation_dtype"] = args.activation_dtype
+    if getattr(args, "vae_dtype", None) is not None:  # (a key only when the flag is given)
+        from .config import validate_vae_dtype
+        r["vae_dtype"] = validate_vae_dtype(args.vae_dtype)
     return r
 
 
@@ -120,6 +126,8 @@ def main(argv: Optional[Sequence[str]] = None, pipeline_overrides: Optional[dict
         extra["mmdit_config"] = fp8_config(extra["mmdit_config"], args.fp8) if extra.get("mmdit_config") is not None else r["mmdit_config"]
     if "activation_dtype" in r:
         extra["activation_dtype"] = r["activation_dtype"]
+    if "vae_dtype" in r:
+        extra["vae_dtype"] = r["vae_dtype"]
     sd = pipeline_class(w16=True, shift=r["shift"], use_t5=args.t5, model_version=args.model_version,
                         low_memory_mode=r["low_memory_mode"], a16=True, local_ckpt=checkpoint_dict(args.local_ckpt, args.ckpt),
                         device=args.device, **extra)

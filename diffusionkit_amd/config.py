@@ -212,6 +212,9 @@ class VAEDecoderConfig:
     layers_per_block: int = 3
     resnet_groups: int = 32
     group_norm_eps: float = 1e-5  # MLX nn.GroupNorm default (vae.py:34,72,78,381)
+    # element type of the weights, the activations and the raw output: "bfloat16", or "float16" -- the reference's decoder dtype for Stable
+    # Diffusion 3 (mlx/__init__.py:108-113,483-484); see float16_vae_config
+    dtype: str = "bfloat16"
 
 
 @dataclass(frozen=True)
@@ -223,6 +226,27 @@ class VAEEncoderConfig:
     layers_per_block: int = 2
     resnet_groups: int = 32
     group_norm_eps: float = 1e-5
+    # element type of the weights, the activations and the 16-bit moments: "bfloat16" or "float16".  The reference keeps its encoder in fp32
+    # (load_vae_encoder(float16=False), mlx/__init__.py:116): float16 is the closer of the two 16-bit forms, not the reference's dtype
+    dtype: str = "bfloat16"
+
+
+VAE_DTYPES = ("bfloat16", "float16")
+
+
+def validate_vae_dtype(dtype: str) -> str:
+    """``dtype`` of a VAE half: "bfloat16" or "float16"; anything else raises ValueError."""
+    if dtype not in VAE_DTYPES:
+        raise ValueError(f"unknown VAE dtype {dtype!r} (bfloat16 | float16)")
+    return dtype
+
+
+def float16_vae_config(cfg, dtype: str = "float16"):
+    """``cfg`` (VAEDecoderConfig or VAEEncoderConfig) with float16 weights and activations -- or, with ``dtype``, in that element type;
+    unknown values raise ValueError.  Any channel plan: the VAE's fp16 kernels have no geometry rule."""
+    if not isinstance(cfg, (VAEDecoderConfig, VAEEncoderConfig)):
+        raise ValueError(f"float16_vae_config takes a VAEDecoderConfig or VAEEncoderConfig, got {type(cfg).__name__}")
+    return replace(cfg, dtype=validate_vae_dtype(dtype))
 
 
 def tiny_vae_encoder() -> VAEEncoderConfig:

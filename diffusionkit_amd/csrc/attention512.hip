@@ -87,9 +87,9 @@ __global__ __launch_bounds__(512, 2) void dk_attn512_fwd_kernel(Attn512Params p)
     // =========================== S role ===========================
     const int l15 = lane & 15, qq = lane >> 4;
     const int qrow = min(q0 + wave * 16 + l15, T - 1);
-    bf16x8 qf[16];  // B operand of S^T = K Q^T: lane (query l15, k block qq) holds Q[q][32 kk + 8 qq .. + 7]
+    ex8 qf[16];  // B operand of S^T = K Q^T: lane (query l15, k block qq) holds Q[q][32 kk + 8 qq .. + 7]
 #pragma unroll
-    for (int kk = 0; kk < 16; ++kk) qf[kk] = *(const bf16x8*)(Qb + (size_t)qrow * p.ld + kk * 32 + qq * 8);
+    for (int kk = 0; kk < 16; ++kk) qf[kk] = *(const ex8*)(Qb + (size_t)qrow * p.ld + kk * 32 + qq * 8);
     // K fragment of key block blk, K slice kk: key 16 blk + l15, chunk 4 kk + qq at position (4 kk + qq) ^ l15:
     // = (lane part for kk & 3) + 256 * (kk >> 2) -- the bits the XOR with l15 touches (6, 7 of the byte address) are those of kk & 3
     unsigned kbase[4];
@@ -103,10 +103,10 @@ __global__ __launch_bounds__(512, 2) void dk_attn512_fwd_kernel(Attn512Params p)
       f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int kk = 0; kk < 16; ++kk) {
-        const bf16x8 k0 = *(const __attribute__((address_space(3))) bf16x8*)(lds + ks + kbase[kk & 3] + (kk >> 2) * 256);
-        const bf16x8 k1 = *(const __attribute__((address_space(3))) bf16x8*)(lds + ks + 16 * 1024 + kbase[kk & 3] + (kk >> 2) * 256);
-        s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k0, qf[kk], s0, 0, 0, 0);
-        s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k1, qf[kk], s1, 0, 0, 0);
+        const ex8 k0 = *(const __attribute__((address_space(3))) ex8*)(lds + ks + kbase[kk & 3] + (kk >> 2) * 256);
+        const ex8 k1 = *(const __attribute__((address_space(3))) ex8*)(lds + ks + 16 * 1024 + kbase[kk & 3] + (kk >> 2) * 256);
+        s0 = mfma_16x16x32(k0, qf[kk], s0);
+        s1 = mfma_16x16x32(k1, qf[kk], s1);
       }
       // lane: query l15, keys t * 32 + 4 qq + e (s0) and + 16 (s1)
       if ((t + 1) * A5_KT > T) {
@@ -142,8 +142,8 @@ __global__ __launch_bounds__(512, 2) void dk_attn512_fwd_kernel(Attn512Params p)
       psum += __shfl_xor(psum, 32, 64);
       l_run += psum;
       const unsigned pw = (unsigned)(A5_P_OFF + (t & 1) * A5_P_SLOT + (wave * 16 + l15) * A5_P_ROWB + qq * 8);
-      *(__attribute__((address_space(3))) u32x2*)(lds + pw) = u32x2{pack2bf(s0[0], s0[1]), pack2bf(s0[2], s0[3])};
-      *(__attribute__((address_space(3))) u32x2*)(lds + pw + 32) = u32x2{pack2bf(s1[0], s1[1]), pack2bf(s1[2], s1[3])};
+      *(__attribute__((address_space(3))) u32x2*)(lds + pw) = u32x2{pack2(s0[0], s0[1]), pack2(s0[2], s0[3])};
+      *(__attribute__((address_space(3))) u32x2*)(lds + pw + 32) = u32x2{pack2(s1[0], s1[1]), pack2(s1[2], s1[3])};
       const unsigned aw = (unsigned)(A5_AL_OFF + (t & 1) * A5_AL_SLOT);
       if (qq == 0) *(__attribute__((address_space(3))) float*)(lds + aw + (wave * 16 + l15) * 4) = alpha;
       if (lane == 0) *(__attribute__((address_space(3))) unsigned*)(lds + aw + 256 + wave * 4) = grow ? 1u : 0u;
@@ -215,15 +215,15 @@ __global__ __launch_bounds__(512, 2) void dk_attn512_fwd_kernel(Attn512Params p)
       const unsigned vs = (unsigned)((t & 1) * A5_V_SLOT), ps = (unsigned)((t & 1) * A5_P_SLOT);
 #pragma unroll
       for (int st = 0; st < 2; ++st) {
-        bf16x8 pf[2], vf[4];
+        ex8 pf[2], vf[4];
 #pragma unroll
-        for (int qb = 0; qb < 2; ++qb) pf[qb] = *(const __attribute__((address_space(3))) bf16x8*)(lds + pa + ps + qb * 32 * A5_P_ROWB + st * 32);
+        for (int qb = 0; qb < 2; ++qb) pf[qb] = *(const __attribute__((address_space(3))) ex8*)(lds + pa + ps + qb * 32 * A5_P_ROWB + st * 32);
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt) vf[dt] = *(const __attribute__((address_space(3))) bf16x8*)(lds + va + vs + dt * 32 * A5_V_ROWB + st * 32);
+        for (int dt = 0; dt < 4; ++dt) vf[dt] = *(const __attribute__((address_space(3))) ex8*)(lds + va + vs + dt * 32 * A5_V_ROWB + st * 32);
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
-          for (int qb = 0; qb < 2; ++qb) o[dt][qb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[dt], pf[qb], o[dt][qb], 0, 0, 0);
+          for (int qb = 0; qb < 2; ++qb) o[dt][qb] = mfma_32x32x16(vf[dt], pf[qb], o[dt][qb]);
       }
       if (k2) store_k(t & 1);
       if (v1) store_v((t + 1) & 1);
@@ -242,8 +242,8 @@ __global__ __launch_bounds__(512, 2) void dk_attn512_fwd_kernel(Attn512Params p)
 #pragma unroll
           for (int g4 = 0; g4 < 4; ++g4) {
             uint2 w;
-            w.x = pack2bf(o[dt][qb][4 * g4 + 0] * inv, o[dt][qb][4 * g4 + 1] * inv);
-            w.y = pack2bf(o[dt][qb][4 * g4 + 2] * inv, o[dt][qb][4 * g4 + 3] * inv);
+            w.x = pack2(o[dt][qb][4 * g4 + 0] * inv, o[dt][qb][4 * g4 + 1] * inv);
+            w.y = pack2(o[dt][qb][4 * g4 + 2] * inv, o[dt][qb][4 * g4 + 3] * inv);
             *(uint2*)(op + dt * 32 + 8 * g4) = w;
           }
       }
@@ -252,6 +252,12 @@ __global__ __launch_bounds__(512, 2) void dk_attn512_fwd_kernel(Attn512Params p)
 }
 
 int dk_launch_attention512(const Attn512Params& p, hipStream_t stream) {
+#ifndef DK_ELEM_F16
+  DK_REQUIRE(p.dtype == DK_DTYPE_BF16 || p.dtype == DK_DTYPE_F16, "attention512: element type: 0 bf16, 1 fp16");
+  if (p.dtype == DK_DTYPE_F16) return dk_f16::dk_launch_attention512(p, stream);
+#else
+  DK_REQUIRE(p.dtype == DK_DTYPE_F16, "attention512: the fp16 form takes fp16 problems");
+#endif
   DK_REQUIRE(p.Q && p.K && p.Vt && p.O && p.T > 0 && p.B > 0, "attention512: null / empty argument");
   DK_REQUIRE(p.ld % 8 == 0 && p.ld >= A5_D && p.ldo % 4 == 0 && p.ldo >= A5_D, "attention512: row strides (16-byte aligned rows of >= 512 columns)");
   DK_REQUIRE(p.Tp % 8 == 0 && p.Tp >= (p.T + A5_KT - 1) / A5_KT * A5_KT, "attention512: V^T rows padded with zeros to a multiple of 32 keys");

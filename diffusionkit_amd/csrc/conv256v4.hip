@@ -263,6 +263,7 @@ int g_dk_conv_v4 = 1;  // dk_tune_set("conv_v4", v): 0 = conv_halo.hip for every
 static int conv4_nt(const ConvHaloParams& p) { return p.O % 256 == 0 ? 256 : 128; }
 
 bool dk_conv256v4_eligible(const ConvHaloParams& p) {
+  if (p.dtype != DK_DTYPE_BF16) return false;  // the generated asm body is bf16: an fp16 launch stays on conv_halo.hip, under every dk_tune_set("conv_v4", v)
   if (!dk_conv_halo_eligible(p, false)) return false;
   if (p.img || p.u8 || p.raw || p.x2) return false;
   if (p.O % 128 != 0 || p.C < 128) return false;

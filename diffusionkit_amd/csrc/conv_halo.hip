@@ -188,10 +188,10 @@ __global__ __launch_bounds__(512, 2) void dk_conv_halo_kernel(ConvHaloParams p) 
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           float a0, a1;
-          unpack2bf(hreg[i][e], a0, a1);
-          float g0 = round_bf16(a0 * sc[2 * e] + sh[2 * e]), g1 = round_bf16(a1 * sc[2 * e + 1] + sh[2 * e + 1]);
+          unpack2(hreg[i][e], a0, a1);
+          float g0 = round_act(a0 * sc[2 * e] + sh[2 * e]), g1 = round_act(a1 * sc[2 * e + 1] + sh[2 * e + 1]);
           if (p.gn_silu) g0 = silu_f(g0), g1 = silu_f(g1);
-          o[e] = pack2bf(g0, g1) & keep;
+          o[e] = pack2(g0, g1) & keep;
         }
       }
       const unsigned dst = ((inmask >> i) & 1u) ? lds_w0 + i * (64 * CH_ROWB) + slot * CH_A_SLOT : dummy_w;
@@ -231,18 +231,18 @@ __global__ __launch_bounds__(512, 2) void dk_conv_halo_kernel(ConvHaloParams p) 
   __syncthreads();
 
   // fragment sets: F0 = the K = 0..31 half of a K-tile, F1 = the K = 32..63 half
-  bf16x8 wf0[NF], af0[MF], wf1[NF], af1[MF];
+  ex8 wf0[NF], af0[MF], wf1[NF], af1[MF];
 #define CH_READ(WF, AF, WSLOT, ABASE, KK)                                                                                       \
   if (!((CH_ABL & 2) && in_loop)) do {                                                                                          \
     _Pragma("unroll") for (int nf = 0; nf < NF; ++nf)                                                                           \
-        WF[nf] = *(const __attribute__((address_space(3))) bf16x8*)(lds + w_lane[KK] + (WSLOT) * W_SLOT + nf * 2048);           \
+        WF[nf] = *(const __attribute__((address_space(3))) ex8*)(lds + w_lane[KK] + (WSLOT) * W_SLOT + nf * 2048);              \
     _Pragma("unroll") for (int mf = 0; mf < MF; ++mf)                                                                           \
-        AF[mf] = *(const __attribute__((address_space(3))) bf16x8*)(lds + (ABASE) + mf * (18 * CH_ROWB) + (KK) * 64);           \
+        AF[mf] = *(const __attribute__((address_space(3))) ex8*)(lds + (ABASE) + mf * (18 * CH_ROWB) + (KK) * 64);              \
   } while (0)
 #define CH_MMA(WF, AF)                                                                                                          \
   if (!(CH_ABL & 1)) do {                                                                                                       \
     _Pragma("unroll") for (int nf = 0; nf < NF; ++nf) _Pragma("unroll") for (int mf = 0; mf < MF; ++mf)                         \
-        acc[nf][mf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(WF[nf], AF[mf], acc[nf][mf], 0, 0, 0);                            \
+        acc[nf][mf] = mfma_16x16x32(WF[nf], AF[mf], acc[nf][mf]);                                                               \
   } while (0)
   // halo window of (chunk, tap): byte offset of halo row (dy * 18 + dx) in the chunk's slot
 #define CH_ABASE(CHUNK, DY, DX) (a_lane + (unsigned)(((CHUNK) & 1) * CH_A_SLOT + ((DY) * 18 + (DX)) * CH_ROWB))
@@ -369,20 +369,20 @@ __global__ __launch_bounds__(512, 2) void dk_conv_halo_kernel(ConvHaloParams p) 
     if (q == 0) {
       float b4[4] = {0.f, 0.f, 0.f, 0.f};
       for (int e = 0; e < 4; ++e)
-        if (e < p.out_channels) b4[e] = bf2f(p.bias[e]);
+        if (e < p.out_channels) b4[e] = to_f32(p.bias[e]);
 #pragma unroll
       for (int mf = 0; mf < MF; ++mf) {
         const size_t pix = ((size_t)b * p.H + py0 + wm * MF + mf) * p.W + px0 + l15;
         float v[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = e < p.out_channels ? round_bf16(acc[0][mf][e] + b4[e]) : 0.f;
-        if (p.raw) *(u32x2*)(p.raw + pix * 4) = u32x2{pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
+        for (int e = 0; e < 4; ++e) v[e] = e < p.out_channels ? round_act(acc[0][mf][e] + b4[e]) : 0.f;
+        if (p.raw) *(u32x2*)(p.raw + pix * 4) = u32x2{pack2(v[0], v[1]), pack2(v[2], v[3])};
         for (int e = 0; e < 3; ++e) {
           if (e >= p.out_channels) break;
           // the arithmetic of dk_image_post_kernel: bf16 products like the reference's (__init__.py:581-584; :525-526 truncation)
-          const float im = fminf(fmaxf(round_bf16(v[e] * 0.5f + 0.5f), 0.f), 1.f);
+          const float im = fminf(fmaxf(round_act(v[e] * 0.5f + 0.5f), 0.f), 1.f);
           if (p.img) p.img[pix * 3 + e] = im;
-          if (p.u8) p.u8[pix * 3 + e] = (unsigned char)round_bf16(im * 255.0f);
+          if (p.u8) p.u8[pix * 3 + e] = (unsigned char)round_act(im * 255.0f);
         }
       }
     }
@@ -396,13 +396,13 @@ __global__ __launch_bounds__(512, 2) void dk_conv_halo_kernel(ConvHaloParams p) 
       const int col = n0 + wn * 64 + nf * 16 + 4 * q;
       u32x2 bq = *(const u32x2*)(p.bias + col);
       float b4[4];
-      unpack2bf(bq[0], b4[0], b4[1]);
-      unpack2bf(bq[1], b4[2], b4[3]);
+      unpack2(bq[0], b4[0], b4[1]);
+      unpack2(bq[1], b4[2], b4[3]);
       if (p.bias2) {
         const u32x2 b2 = *(const u32x2*)(p.bias2 + col);
         float c4[4];
-        unpack2bf(b2[0], c4[0], c4[1]);
-        unpack2bf(b2[1], c4[2], c4[3]);
+        unpack2(b2[0], c4[0], c4[1]);
+        unpack2(b2[1], c4[2], c4[3]);
 #pragma unroll
         for (int e = 0; e < 4; ++e) b4[e] += c4[e];
       }
@@ -411,7 +411,7 @@ __global__ __launch_bounds__(512, 2) void dk_conv_halo_kernel(ConvHaloParams p) 
         const int row = mf * 16 + l15;
         const f32x4 a = acc[nf][mf];
         *(__attribute__((address_space(3))) u32x2*)(lds + img0 + row * 128 + (((nf * 2 + (q >> 1)) ^ (row & 7)) << 4) + (q & 1) * 8) =
-            u32x2{pack2bf(a[0] + b4[0], a[1] + b4[1]), pack2bf(a[2] + b4[2], a[3] + b4[3])};
+            u32x2{pack2(a[0] + b4[0], a[1] + b4[1]), pack2(a[2] + b4[2], a[3] + b4[3])};
       }
     }
     // (same wave writes and reads its image: program order + the compiler's lgkmcnt suffice)
@@ -441,9 +441,9 @@ __global__ __launch_bounds__(512, 2) void dk_conv_halo_kernel(ConvHaloParams p) 
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           float v0, v1, r0, r1;
-          unpack2bf(sv[e], v0, v1);
-          unpack2bf(rv[e], r0, r1);
-          sv[e] = pack2bf(v0 + r0, v1 + r1);
+          unpack2(sv[e], v0, v1);
+          unpack2(rv[e], r0, r1);
+          sv[e] = pack2(v0 + r0, v1 + r1);
         }
       }
       if (!(CH_ABL & 64) || p.ldy == -1) *(u32x4*)(p.y + pix * (size_t)p.ldy + ocol) = sv;
@@ -451,7 +451,7 @@ __global__ __launch_bounds__(512, 2) void dk_conv_halo_kernel(ConvHaloParams p) 
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           float v0, v1;
-          unpack2bf(sv[e], v0, v1);
+          unpack2(sv[e], v0, v1);
           ssum[2 * e] += v0, ssq[2 * e] += v0 * v0;
           ssum[2 * e + 1] += v1, ssq[2 * e + 1] += v1 * v1;
         }
@@ -497,6 +497,7 @@ __global__ __launch_bounds__(512, 2) void dk_conv_halo_kernel(ConvHaloParams p) 
   }
 }
 
+#ifndef DK_ELEM_F16  // (one copy: conv_halo_f16.hip compiles this file a second time inside namespace dk_f16 for the kernel and its launcher)
 bool dk_conv_halo_eligible(const ConvHaloParams& p, bool img) {
   if (p.B <= 0 || p.H % 16 != 0 || p.W % 16 != 0 || p.C % 64 != 0 || p.ups < 0 || p.ups > 1) return false;
   if (p.ups == 1 && (p.H % 2 != 0 || p.W % 2 != 0)) return false;
@@ -511,10 +512,18 @@ bool dk_conv_halo_eligible(const ConvHaloParams& p, bool img) {
   if (p.stats_out && (p.G_out <= 0 || p.O % p.G_out != 0 || 128 % (p.O / p.G_out) != 0 || (p.O / p.G_out) > 64)) return false;
   return true;
 }
+#endif
 
+// this unit's element type: the bf16 launcher hands an fp16 problem to its dk_f16 twin, which has no asm frame to route to
 int dk_launch_conv_halo(const ConvHaloParams& p, hipStream_t stream) {
   const bool img = p.img != nullptr || p.u8 != nullptr || p.raw != nullptr;
+#ifndef DK_ELEM_F16
+  DK_REQUIRE(p.dtype == DK_DTYPE_BF16 || p.dtype == DK_DTYPE_F16, "conv_halo: element type: 0 bf16, 1 fp16");
+  if (p.dtype == DK_DTYPE_F16) return dk_f16::dk_launch_conv_halo(p, stream);
   if (!img && dk_conv256v4_wanted(p)) return dk_launch_conv256v4(p, stream);  // the one-wave-per-SIMD frame (conv256v4.hip): 256-column tiles
+#else
+  DK_REQUIRE(p.dtype == DK_DTYPE_F16, "conv_halo: the fp16 form takes fp16 problems");
+#endif
   DK_REQUIRE(dk_conv_halo_eligible(p, img), "conv_halo: shape / alignment not supported (H, W multiples of 16; C multiple of 64; O multiple of 128, or <= 4 for the image tail)");
   static DkDeviceOnce attr_once;
   constexpr int LDS128 = 2 * CH_A_SLOT + 3 * 128 * 128 + 8192, LDS16 = 2 * CH_A_SLOT + 3 * 16 * 128 + 8192;  // (+ the dummy store zone)

@@ -33,8 +33,8 @@ __device__ __forceinline__ void unpack2bf(uint32_t v, float& lo, float& hi) {
 }
 
 // ---- element-type layer ------------------------------------------------------------------------------------
-// The kernels on SD3's path (gemm.hip, gemm256v3.hip, attention2.hip, elementwise.hip) are written on these names instead of the bf16
-// helpers above: 16-bit storage (bf16_t is the raw halfword of either type), fp32 accumulation, one rounding per store.  At global scope
+// The kernels on SD3's path (gemm.hip, gemm256v3.hip, attention2.hip, elementwise.hip) and the VAE's (conv_halo.hip, attention512.hip, vae_ops.hip)
+// are written on these names instead of the bf16 helpers above: 16-bit storage (bf16_t is the raw halfword of either type), fp32 accumulation, one rounding per store.  At global scope
 // they ARE the bf16 helpers.  Inside namespace dk_f16 the same names mean IEEE half: the *_f16.hip translation units include a kernel's
 // source inside that namespace, so every kernel has one text and two instantiations, and the bf16 objects compile from the same tokens
 // as before.  An fp32 -> fp16 store that overflows gives +-inf (v_cvt_f16_f32, round to nearest even), as the reference's casts do.

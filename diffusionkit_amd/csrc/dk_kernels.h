@@ -55,8 +55,8 @@ struct GemmParams {
   // attention kernel then loads finished queries.  Needs kn_w; null qn_w: queries untouched
   const bf16_t* qn_w;
   int qn_col0, qn_col1;
-  // element type of A, W, C, bias, gate, res and the norm weights: DK_DTYPE_BF16 (0) or DK_DTYPE_F16 (1: Linears on the 128^2 kernel and
-  // gemm256v3.hip only -- the route never names gemm256v4.hip)
+  // element type of A, W, C, bias, gate, res and the norm weights: DK_DTYPE_BF16 (0) or DK_DTYPE_F16 (1: Linears and the conv form on the 128^2
+  // kernel and gemm256v3.hip only -- the route never names gemm256v4.hip)
   int dtype;
 };
 int dk_launch_gemm(const GemmParams& p, hipStream_t stream);
@@ -246,8 +246,8 @@ struct Attn512Params {
   bf16_t* O;         // [B, T, ldo]
   int T, Tp, B, ld, ldo;
   float scale;
+  int dtype;  // element type of Q, K, Vt and O: DK_DTYPE_BF16 (0) or DK_DTYPE_F16 (1)
 };
-int dk_launch_attention512(const Attn512Params& p, hipStream_t stream);
 
 // ---- text-conditioning kernels (text_ops.hip) ---------------------------------------------------
 int dk_launch_embedding(const bf16_t* table, const int* ids, const bf16_t* pos, int pos_rows, bf16_t* out, float* out_f32, int n, int dim,
@@ -288,9 +288,11 @@ struct ConvHaloParams {
   bf16_t* raw;            // ... y itself, bf16 [npix, 4]
   int out_channels;
   int B, H, W, C, O, ups, ldw, ldy, ldr;
+  // element type of x, w, the biases, res, y, x2 and raw: DK_DTYPE_BF16 (0) or DK_DTYPE_F16 (1: conv_halo.hip only -- conv256v4.hip's asm body is
+  // bf16, dk_conv256v4_wanted is false for fp16 whatever dk_tune_set("conv_v4", v) says).  Last field: the asm kernel's argument offsets stay.
+  int dtype;
 };
 bool dk_conv_halo_eligible(const ConvHaloParams& p, bool img);
-int dk_launch_conv_halo(const ConvHaloParams& p, hipStream_t stream);
 // conv256v4.hip: the same contract in the one-wave-per-SIMD frame (16 x 16 pixels x 256 channels per workgroup, asm body); no shortcut
 // extension, no image tail.  dk_launch_conv_halo routes to it when dk_conv256v4_wanted (dk_tune_set("conv_v4", 0 | 1 | 2))
 extern int g_dk_conv_v4;
@@ -298,19 +300,10 @@ bool dk_conv256v4_eligible(const ConvHaloParams& p);
 bool dk_conv256v4_wanted(const ConvHaloParams& p);
 int dk_launch_conv256v4(const ConvHaloParams& p, hipStream_t stream);
 
-// ---- VAE ops -------------------------------------------------------------------------------
-// the second pass of the GroupNorm statistics alone: per (batch, group) the partials [B][nchunk][G][2] -> mean / rstd, and
-// (gamma given) the per-channel table scale_shift [B][2][C]: scale = rstd * gamma, shift = beta - mean * scale
-int dk_launch_groupnorm_finalize(const float* partial, int nchunk, int B, int G, double count, float eps, float* mean_rstd,
-                                 const bf16_t* gamma, const bf16_t* beta, int C, float* scale_shift, hipStream_t stream);
-int dk_launch_groupnorm_partials(const bf16_t* x, int B, long HW, int C, int G, float* partial, int nchunk, hipStream_t stream);
-int dk_launch_groupnorm_stats(const bf16_t* x, int B, long HW, int C, int G, float* partial, int nchunk,
-                              float* mean_rstd, float eps, hipStream_t stream);
-int dk_launch_groupnorm_apply(const bf16_t* x, bf16_t* y, int B, long HW, int C, int G, const float* mean_rstd,
-                              const bf16_t* gamma, const bf16_t* beta, int do_silu, hipStream_t stream);
-int dk_launch_softmax_rows(bf16_t* x, int rows, int cols, int ld, hipStream_t stream);
-int dk_launch_transpose(const bf16_t* x, bf16_t* y, int R, int Cc, hipStream_t stream, int ldy = 0);  // ldy > R: zero-padded rows
-int dk_launch_pad_channels(const float* x, bf16_t* y, long npix, int C, int Cpad, hipStream_t stream);
-int dk_launch_image_post(const bf16_t* x, int ldx, float* img, unsigned char* u8, long npix, hipStream_t stream);
-int dk_launch_latent_sample(const bf16_t* mom, int ldm, const float* noise, float* out, long npix, int L, hipStream_t stream);
-int dk_launch_bf16_rows_to_f32(const bf16_t* x, int ldx, float* y, long npix, int C, hipStream_t stream);
+// ---- VAE launchers per element type (conv_halo.hip, attention512.hip, vae_ops.hip) -------------------------------------------
+// dk_launch_conv_halo / dk_launch_attention512 at global scope forward to their dk_f16 twin on ConvHaloParams::dtype / Attn512Params::dtype;
+// the vae_ops.hip launchers are picked by the caller.
+#include "dk_vae_launchers.h"
+namespace dk_f16 {
+#include "dk_vae_launchers.h"
+}

@@ -147,11 +147,13 @@ extern "C" int dk_gemm_fused_plan(const dk_gemm_desc* d, const dk_gemm_side* f, 
   return dk_gemm_plan_call(p, d2 != nullptr ? &p2 : nullptr, *plan);
 }
 
-// workspace: optional K-split scratch (dk_gemm_split_workspace_bytes) for stages whose tiles fill only half the CUs
-static int conv3x3_launch(const dk_conv_desc* d, void* workspace, hipStream_t stream) {
+// workspace: optional K-split scratch (dk_gemm_split_workspace_bytes) for stages whose tiles fill only half the CUs; rec: record the route
+// instead of launching (dk_conv3x3_plan)
+static int conv3x3_launch(const dk_conv_desc* d, void* workspace, hipStream_t stream, dk_gemm_plan_t* rec = nullptr) {
   DK_REQUIRE(d != nullptr, "null descriptor");
   GemmParams p;
   memset(&p, 0, sizeof(p));
+  p.dtype = g_elem_dtype;
   p.A = (const bf16_t*)d->x; p.W = (const bf16_t*)d->w; p.C = (bf16_t*)d->y;
   p.bias = (const bf16_t*)d->bias; p.res = (const bf16_t*)d->res;
   p.M = d->B * d->H * d->W; p.N = d->O; p.K = 9 * d->C;
@@ -163,9 +165,22 @@ static int conv3x3_launch(const dk_conv_desc* d, void* workspace, hipStream_t st
   if (workspace) { p.workspace = workspace; p.workspace_bytes = dk_gemm_split_workspace_bytes(); }
   DK_REQUIRE(d->upsample >= 0 && d->upsample <= 2, "upsample: 0 plain, 1 nearest-x2 input view, 2 stride-2 (downsample)");
   if (d->upsample == 1) DK_REQUIRE(d->H % 2 == 0 && d->W % 2 == 0, "upsampled conv needs even output size");
+  if (rec != nullptr) return dk_gemm_plan_call(p, nullptr, *rec);
   return dk_launch_gemm(p, stream);
 }
 extern "C" int dk_conv3x3_bf16(const dk_conv_desc* d, void* stream) { return conv3x3_launch(d, nullptr, S_(stream)); }
+extern "C" int dk_conv3x3_f16(const dk_conv_desc* d, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_conv3x3_bf16(d, stream);
+}
+extern "C" int dk_conv3x3_plan(const dk_conv_desc* d, dk_gemm_plan_t* plan) {
+  DK_REQUIRE(plan != nullptr, "null plan");
+  return conv3x3_launch(d, nullptr, nullptr, plan);
+}
+extern "C" int dk_conv3x3_plan_f16(const dk_conv_desc* d, dk_gemm_plan_t* plan) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_conv3x3_plan(d, plan);
+}
 
 // Workspace of the attention launches of this host thread.  attention5.hip splits the query blocks of a launch's last, partial round of the
 // CUs along the keys (FLUX, one image: 408 blocks on 256 CUs -- 152 blocks in three key ranges each fill the second round to two thirds
@@ -223,11 +238,11 @@ static int attention_d512(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf1
   DK_REQUIRE(ld == 512, "attention_d512: q / k / v rows of exactly 512 columns (the transpose reads dense [T, 512] matrices)");
   const int Tp = dk_attention_d512_tp(T);
   for (int b = 0; b < B; ++b) {
-    const int rc = dk_launch_transpose(v + (size_t)b * T * ld, vt + (size_t)b * 512 * Tp, T, 512, st, Tp);
+    const int rc = DK_EL(dk_launch_transpose)(v + (size_t)b * T * ld, vt + (size_t)b * 512 * Tp, T, 512, st, Tp);
     if (rc) return rc;
   }
   Attn512Params a;
-  a.Q = q; a.K = k; a.Vt = vt; a.O = out; a.T = T; a.Tp = Tp; a.B = B; a.ld = ld; a.ldo = ldo; a.scale = scale;
+  a.Q = q; a.K = k; a.Vt = vt; a.O = out; a.T = T; a.Tp = Tp; a.B = B; a.ld = ld; a.ldo = ldo; a.scale = scale; a.dtype = g_elem_dtype;
   return dk_launch_attention512(a, st);
 }
 extern "C" int dk_attention_d512_bf16(const void* q, const void* k, const void* v, void* out, int32_t B, int32_t T, int32_t ld, int32_t ldo,
@@ -235,6 +250,11 @@ extern "C" int dk_attention_d512_bf16(const void* q, const void* k, const void* 
   DK_REQUIRE(q && k && v && out && vt_scratch && B > 0 && T > 0, "null / empty argument");
   return attention_d512((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)out, B, T, ld, ldo, scale, (bf16_t*)vt_scratch,
                         S_(stream));
+}
+extern "C" int dk_attention_d512_f16(const void* q, const void* k, const void* v, void* out, int32_t B, int32_t T, int32_t ld, int32_t ldo,
+                                     float scale, void* vt_scratch, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_attention_d512_bf16(q, k, v, out, B, T, ld, ldo, scale, vt_scratch, stream);
 }
 extern "C" int dk_embedding_bf16(const void* table, const int32_t* ids, const void* pos, int32_t pos_rows, void* out_bf16, float* out_f32,
                                  int32_t n, int32_t dim, int32_t vocab, void* stream) {
@@ -410,10 +430,15 @@ extern "C" int dk_groupnorm_bf16(const void* x, void* y, int32_t B, int64_t HW, 
                                  const void* beta, float eps, int32_t fuse_silu, float* scratch, void* stream) {
   const int nchunk = gn_nchunk((long)HW, C);
   float* mean_rstd = scratch + (size_t)B * 1024 * 2 * G;
-  int rc = dk_launch_groupnorm_stats((const bf16_t*)x, B, (long)HW, C, G, scratch, nchunk, mean_rstd, eps, S_(stream));
+  int rc = DK_EL(dk_launch_groupnorm_stats)((const bf16_t*)x, B, (long)HW, C, G, scratch, nchunk, mean_rstd, eps, S_(stream));
   if (rc) return rc;
-  return dk_launch_groupnorm_apply((const bf16_t*)x, (bf16_t*)y, B, (long)HW, C, G, mean_rstd, (const bf16_t*)gamma,
-                                   (const bf16_t*)beta, fuse_silu, S_(stream));
+  return DK_EL(dk_launch_groupnorm_apply)((const bf16_t*)x, (bf16_t*)y, B, (long)HW, C, G, mean_rstd, (const bf16_t*)gamma,
+                                          (const bf16_t*)beta, fuse_silu, S_(stream));
+}
+extern "C" int dk_groupnorm_f16(const void* x, void* y, int32_t B, int64_t HW, int32_t C, int32_t G, const void* gamma,
+                                const void* beta, float eps, int32_t fuse_silu, float* scratch, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_groupnorm_bf16(x, y, B, HW, C, G, gamma, beta, eps, fuse_silu, scratch, stream);
 }
 
 // scratch layout shared by dk_groupnorm_bf16 / dk_groupnorm_table_bf16: [partials: B * n * 2G][mean_rstd: B * G * 2], n = the
@@ -425,16 +450,22 @@ extern "C" int dk_groupnorm_table_bf16(const void* x, int32_t B, int64_t HW, int
   const int nchunk = x ? gn_nchunk((long)HW, C) : n_partial;
   float* mean_rstd = scratch + (size_t)B * (nchunk > 1024 ? nchunk : 1024) * 2 * G;
   if (x) {  // the partial sums only: the one finalisation below builds mean / rstd AND the table
-    const int rc = dk_launch_groupnorm_partials((const bf16_t*)x, B, (long)HW, C, G, scratch, nchunk, S_(stream));
+    const int rc = DK_EL(dk_launch_groupnorm_partials)((const bf16_t*)x, B, (long)HW, C, G, scratch, nchunk, S_(stream));
     if (rc) return rc;
   }
-  return dk_launch_groupnorm_finalize(scratch, nchunk, B, G, (double)HW * (double)(C / G), eps, mean_rstd, (const bf16_t*)gamma,
-                                      (const bf16_t*)beta, C, scale_shift, S_(stream));
+  return DK_EL(dk_launch_groupnorm_finalize)(scratch, nchunk, B, G, (double)HW * (double)(C / G), eps, mean_rstd, (const bf16_t*)gamma,
+                                             (const bf16_t*)beta, C, scale_shift, S_(stream));
+}
+extern "C" int dk_groupnorm_table_f16(const void* x, int32_t B, int64_t HW, int32_t C, int32_t G, const void* gamma, const void* beta,
+                                      float eps, float* scratch, int32_t n_partial, float* scale_shift, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_groupnorm_table_bf16(x, B, HW, C, G, gamma, beta, eps, scratch, n_partial, scale_shift, stream);
 }
 
 static ConvHaloParams conv_halo_params(const dk_conv_gn_desc* d) {
   ConvHaloParams p;
   memset(&p, 0, sizeof(p));
+  p.dtype = g_elem_dtype;
   p.x = (const bf16_t*)d->x; p.w = (const bf16_t*)d->w; p.bias = (const bf16_t*)d->bias; p.bias2 = (const bf16_t*)d->bias2;
   p.res = (const bf16_t*)d->res; p.y = (bf16_t*)d->y; p.gn_ss = d->gn_scale_shift; p.gn_silu = d->gn_silu;
   p.x2 = (const bf16_t*)d->x2; p.C2 = d->C2; p.stats_out = d->stats_partial; p.G_out = d->stats_groups;
@@ -448,12 +479,24 @@ extern "C" int dk_conv3x3_gn_bf16(const dk_conv_gn_desc* d, void* stream) {
   DK_REQUIRE(img || d->y, "no output");
   return dk_launch_conv_halo(conv_halo_params(d), S_(stream));
 }
+extern "C" int dk_conv3x3_gn_f16(const dk_conv_gn_desc* d, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_conv3x3_gn_bf16(d, stream);
+}
 
 extern "C" int dk_softmax_rows_bf16(void* x, int32_t rows, int32_t cols, int32_t ld, void* stream) {
-  return dk_launch_softmax_rows((bf16_t*)x, rows, cols, ld, S_(stream));
+  return DK_EL(dk_launch_softmax_rows)((bf16_t*)x, rows, cols, ld, S_(stream));
+}
+extern "C" int dk_softmax_rows_f16(void* x, int32_t rows, int32_t cols, int32_t ld, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_softmax_rows_bf16(x, rows, cols, ld, stream);
 }
 extern "C" int dk_transpose_bf16(const void* x, void* y, int32_t R, int32_t C, void* stream) {
-  return dk_launch_transpose((const bf16_t*)x, (bf16_t*)y, R, C, S_(stream));
+  return DK_EL(dk_launch_transpose)((const bf16_t*)x, (bf16_t*)y, R, C, S_(stream), 0);
+}
+extern "C" int dk_transpose_f16(const void* x, void* y, int32_t R, int32_t C, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_transpose_bf16(x, y, R, C, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1310,6 +1353,9 @@ struct dk_vae {
   float* gn;
   float *ss0, *ss1;  // GroupNorm (scale | shift) tables [B][2][C] of the fused norm -> silu -> conv stages
   void* GWS = nullptr;  // GEMM split workspace of this engine's launches (fp32 slabs + flags)
+  // element type of every bound tensor, activation buffer, of `raw` (decode) and of the 16-bit moments (encode): dk_vae_set_dtype; sizes are the same
+  int dtype = DK_DTYPE_BF16;
+  bool dtype_set = false;
 };
 
 extern "C" int dk_vae_create(const dk_vae_config* cfg, dk_vae** out) {
@@ -1322,6 +1368,15 @@ extern "C" int dk_vae_create(const dk_vae_config* cfg, dk_vae** out) {
   dk_vae* v = new dk_vae();
   v->cfg = *cfg;
   *out = v;
+  return 0;
+}
+extern "C" int dk_vae_set_dtype(dk_vae* v, int32_t dtype) {
+  DK_REQUIRE(v != nullptr, "null handle");
+  DK_REQUIRE(dtype == DK_DTYPE_BF16 || dtype == DK_DTYPE_F16, "VAE dtype: 0 bf16, 1 fp16");
+  if (v->dtype_set || !v->named.empty())
+    DK_REQUIRE(dtype == v->dtype, "dk_vae_set_dtype must precede the first dk_vae_bind; afterwards only the type already set is accepted");
+  v->dtype = dtype;
+  v->dtype_set = true;
   return 0;
 }
 extern "C" void dk_vae_destroy(dk_vae* v) { delete v; }
@@ -1440,6 +1495,7 @@ struct VaeRun {
     DK_TRY(gn_table(x, HW, Cin, p + ".norm1", v->ss0));
     ConvHaloParams c;
     memset(&c, 0, sizeof(c));
+    c.dtype = g_elem_dtype;
     c.x = x; c.w = W(p + ".conv1.weight"); c.bias = W(p + ".conv1.bias"); c.y = v->Y; c.gn_ss = v->ss0; c.gn_silu = 1;
     c.stats_out = v->gn; c.G_out = G;
     c.B = B; c.H = H; c.W = Wd; c.C = Cin; c.O = Cout; c.ldw = 9 * Cin; c.ldy = Cout;
@@ -1448,6 +1504,7 @@ struct VaeRun {
     n_part = tiles;
     DK_TRY(gn_table(v->Y, HW, Cout, p + ".norm2", v->ss1));
     memset(&c, 0, sizeof(c));
+    c.dtype = g_elem_dtype;
     c.x = v->Y; c.bias = W(p + ".conv2.bias"); c.y = out; c.gn_ss = v->ss1; c.gn_silu = 1;
     c.B = B; c.H = H; c.W = Wd; c.C = Cout; c.O = Cout; c.ldy = Cout; c.ldr = Cout;
     if (has(p + ".conv_shortcut.weight")) {
@@ -1509,10 +1566,10 @@ struct VaeRun {
       g.A = v->Qb + (size_t)b * T * C; g.W = v->Kb + (size_t)b * T * C; g.C = v->SCORES;
       g.M = T; g.N = T; g.K = C; g.lda = C; g.ldc = Tp;
       g.a_seg_len = g.c_seg_len = g.r_seg_len = g.gate_seg_len = T;
-      g.alpha = scale; g.epi = DK_EPI_BIAS;
+      g.alpha = scale; g.epi = DK_EPI_BIAS; g.dtype = g_elem_dtype;
       DK_TRY(dk_launch_gemm(g, st));
-      DK_TRY(dk_launch_softmax_rows(v->SCORES, T, T, Tp, st));  // columns [T, Tp) come out as zeros
-      DK_TRY(dk_launch_transpose(v->Vb + (size_t)b * T * C, v->Vt, T, C, st, Tp));
+      DK_TRY(DK_EL(dk_launch_softmax_rows)(v->SCORES, T, T, Tp, st));  // columns [T, Tp) come out as zeros
+      DK_TRY(DK_EL(dk_launch_transpose)(v->Vb + (size_t)b * T * C, v->Vt, T, C, st, Tp));
       // attn @ V: A = probs [T, Tp], W = V^T [C, Tp]; result into Y rows of this batch
       DK_TRY(linear_plain(v->SCORES, v->Vt, nullptr, v->Y + (size_t)b * T * C, T, C, Tp, DK_EPI_BIAS, st));
     }
@@ -1534,10 +1591,11 @@ extern "C" int dk_vae_decode(dk_vae* v, const float* latent, int32_t batch, int3
   // the flag region of the GEMM split workspace must be zero before the first launch (the kernels leave it zero)
   DK_CHECK_HIP(hipMemsetAsync((char*)v->GWS + DK_KSPLIT_FLAGS_OFF, 0, DK_KSPLIT_FLAG_BYTES, st));
   LinearWsScope ws_scope(v->GWS);
+  ElemScope elem_scope(v->dtype);
   DK_CHECK_HIP(hipMemsetAsync(v->ZERO, 0, 256, st));
   int H = latent_h, W = latent_w;
   const int Cm = cf.block_out_channels[cf.n_blocks - 1];
-  DK_TRY(dk_launch_pad_channels(latent, v->LAT, (long)batch * H * W, cf.in_channels, 64, st));
+  DK_TRY(DK_EL(dk_launch_pad_channels)(latent, v->LAT, (long)batch * H * W, cf.in_channels, 64, st));
   bf16_t *cur = v->bufA, *nxt = v->bufB;
   DK_TRY(R.conv(v->LAT, cur, H, W, 64, Cm, "conv_in", 0, nullptr, Cm));
   DK_TRY(R.resnet(cur, nxt, H, W, Cm, Cm, "mid_blocks.0")); std::swap(cur, nxt);
@@ -1563,6 +1621,7 @@ extern "C" int dk_vae_decode(dk_vae* v, const float* latent, int32_t batch, int3
         // front of it, and the statistics of its output for the next block's first GroupNorm
         ConvHaloParams c;
         memset(&c, 0, sizeof(c));
+        c.dtype = g_elem_dtype;
         c.x = cur; c.w = R.W(up + ".weight"); c.bias = R.W(up + ".bias"); c.y = nxt; c.stats_out = v->gn; c.G_out = cf.resnet_groups;
         c.B = batch; c.H = H; c.W = W; c.C = C; c.O = C; c.ups = 1; c.ldw = 9 * C; c.ldy = C;
         if (R.rc) return R.rc;
@@ -1579,6 +1638,7 @@ extern "C" int dk_vae_decode(dk_vae* v, const float* latent, int32_t batch, int3
     DK_TRY(R.gn_table(cur, (long)H * W, C, "conv_norm_out", v->ss0));
     ConvHaloParams c;
     memset(&c, 0, sizeof(c));
+    c.dtype = g_elem_dtype;
     c.x = cur; c.w = R.W("conv_out.weight"); c.bias = R.W("conv_out.bias"); c.gn_ss = v->ss0; c.gn_silu = 1;
     c.img = image_f32; c.u8 = image_u8; c.raw = raw_bf16 ? (bf16_t*)raw_bf16 : v->Y; c.out_channels = cf.out_channels;
     c.B = batch; c.H = H; c.W = W; c.C = C; c.O = cf.out_channels; c.ldw = 9 * C;
@@ -1589,7 +1649,7 @@ extern "C" int dk_vae_decode(dk_vae* v, const float* latent, int32_t batch, int3
   DK_TRY(R.gn(cur, v->T1, (long)H * W, C, "conv_norm_out", 1));
   bf16_t* raw = raw_bf16 ? (bf16_t*)raw_bf16 : v->Y;
   DK_TRY(R.conv(v->T1, raw, H, W, C, cf.out_channels, "conv_out", 0, nullptr, 4));
-  DK_TRY(dk_launch_image_post(raw, 4, image_f32, image_u8, (long)batch * H * W, st));
+  DK_TRY(DK_EL(dk_launch_image_post)(raw, 4, image_f32, image_u8, (long)batch * H * W, st));
   return R.rc;
 }
 
@@ -1663,9 +1723,10 @@ extern "C" int dk_vae_encode(dk_vae* v, const float* image, int32_t batch, int32
   hipStream_t st = R.st;
   DK_CHECK_HIP(hipMemsetAsync((char*)v->GWS + DK_KSPLIT_FLAGS_OFF, 0, DK_KSPLIT_FLAG_BYTES, st));
   LinearWsScope ws_scope(v->GWS);
+  ElemScope elem_scope(v->dtype);
   DK_CHECK_HIP(hipMemsetAsync(v->ZERO, 0, 256, st));
   int H = image_h, W = image_w;
-  DK_TRY(dk_launch_pad_channels(image, v->LAT, (long)batch * H * W, cf.in_channels, 64, st));
+  DK_TRY(DK_EL(dk_launch_pad_channels)(image, v->LAT, (long)batch * H * W, cf.in_channels, 64, st));
   bf16_t *cur = v->bufA, *nxt = v->bufB;
   int C = cf.block_out_channels[0];
   DK_TRY(R.conv(v->LAT, cur, H, W, 64, C, "conv_in", 0, nullptr, C));
@@ -1688,12 +1749,17 @@ extern "C" int dk_vae_encode(dk_vae* v, const float* image, int32_t batch, int32
   bf16_t* mom = moments_bf16 ? (bf16_t*)moments_bf16 : v->Y;
   const int ld = moments_bf16 ? ldm : ldo;
   DK_TRY(R.conv(v->T1, mom, H, W, C, cf.out_channels, "conv_out", 0, nullptr, ld));
-  if (moments_f32) DK_TRY(dk_launch_bf16_rows_to_f32(mom, ld, moments_f32, (long)batch * H * W, cf.out_channels, st));
+  if (moments_f32) DK_TRY(DK_EL(dk_launch_bf16_rows_to_f32)(mom, ld, moments_f32, (long)batch * H * W, cf.out_channels, st));
   return R.rc;
 }
 
 extern "C" int dk_latent_sample_f32(const void* moments_bf16, int32_t ldm, const float* noise, float* latent, int64_t n_pixels,
                                     int32_t latent_channels, void* stream) {
   DK_REQUIRE(moments_bf16 && noise && latent && n_pixels > 0 && latent_channels > 0 && ldm >= 2 * latent_channels, "bad argument");
-  return dk_launch_latent_sample((const bf16_t*)moments_bf16, ldm, noise, latent, (long)n_pixels, latent_channels, S_(stream));
+  return DK_EL(dk_launch_latent_sample)((const bf16_t*)moments_bf16, ldm, noise, latent, (long)n_pixels, latent_channels, S_(stream));
+}
+extern "C" int dk_latent_sample_f16(const void* moments_f16, int32_t ldm, const float* noise, float* latent, int64_t n_pixels,
+                                    int32_t latent_channels, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_latent_sample_f32(moments_f16, ldm, noise, latent, n_pixels, latent_channels, stream);
 }

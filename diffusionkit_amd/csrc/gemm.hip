@@ -417,7 +417,7 @@ static int route_pair(const GemmParams& a, const GemmParams& b, int n_cu, GemmRo
 int dk_gemm_route(const GemmParams& p, const GemmParams* p2, int n_cu, GemmRoute& r) {
   if (p2 != nullptr) return route_pair(p, *p2, n_cu, r);
   DK_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0, "empty GEMM");
-  DK_REQUIRE(p.dtype == DK_DTYPE_BF16 || (p.dtype == DK_DTYPE_F16 && !p.conv), "element type: 0 bf16, 1 fp16 (Linears only: the convolutions are bf16)");
+  DK_REQUIRE(p.dtype == DK_DTYPE_BF16 || p.dtype == DK_DTYPE_F16, "element type: 0 bf16, 1 fp16");
   DK_REQUIRE(p.ldw >= p.K && p.ldw % 8 == 0, "ldw must be >= K and a multiple of 8 elements");
   // the 256^2 kernel (16x16x32 MFMA, LDS-DMA ring, any M and any row-segment map) takes every large-M shape it accepts; small M
   // (modulation tables, embedders, a lone text stream) and N % 256 != 0 stay on the 128^2 tiles
@@ -474,7 +474,7 @@ int dk_gemm_route(const GemmParams& p, const GemmParams* p2, int n_cu, GemmRoute
 
 #endif  // !DK_ELEM_F16
 
-// the 128^2-tile kernel in this unit's element type (fp16: Linears only)
+// the 128^2-tile kernel in this unit's element type (Linears and the conv form)
 int dk_launch_gemm128(const GemmParams& p, const GemmRoute& r, hipStream_t stream) {
 #ifndef DK_ELEM_F16
   if (p.dtype == DK_DTYPE_F16) return dk_f16::dk_launch_gemm128(p, r, stream);
@@ -482,18 +482,14 @@ int dk_launch_gemm128(const GemmParams& p, const GemmRoute& r, hipStream_t strea
   static DkDeviceOnce attr_once;
   if (attr_once.first()) {
     DK_CHECK_HIP(hipFuncSetAttribute((const void*)dk_gemm_bf16_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE_BYTES));
-#ifndef DK_ELEM_F16
     DK_CHECK_HIP(hipFuncSetAttribute((const void*)dk_gemm_bf16_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE_BYTES));
-#endif
     attr_once.mark();
   }
   dim3 grid(r.tiles_a), block(256);
   dk_prof_begin(p.conv ? 1 : 0, 2.0 * (double)p.M * (double)p.N * (double)p.K, stream);
-#ifndef DK_ELEM_F16
   if (p.conv)
     hipLaunchKernelGGL(dk_gemm_bf16_kernel<1>, grid, block, 2 * STAGE_BYTES, stream, p);
   else
-#endif
     hipLaunchKernelGGL(dk_gemm_bf16_kernel<0>, grid, block, 2 * STAGE_BYTES, stream, p);
   dk_prof_end(stream);
   DK_CHECK_HIP(hipGetLastError());

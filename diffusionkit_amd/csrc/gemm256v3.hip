@@ -863,17 +863,13 @@ size_t dk_gemm_split_workspace_bytes() { return DK_KSPLIT_WS_BYTES; }
 int dk_launch_gemm256v3(const GemmParams& p, const GemmParams* p2, const GemmRoute& r, hipStream_t stream) {
 #ifndef DK_ELEM_F16
   if (p.dtype == DK_DTYPE_F16) return dk_f16::dk_launch_gemm256v3(p, p2, r, stream);
-#else
-  DK_REQUIRE(!p.conv, "gemm256v3: the fp16 form takes Linears only");
 #endif
   static DkDeviceOnce attr_once;
   if (attr_once.first()) {
     DK_CHECK_HIP(hipFuncSetAttribute((const void*)dk_gemm256v3_kernel<8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
     DK_CHECK_HIP(hipFuncSetAttribute((const void*)dk_gemm256v3_kernel<7, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-#ifndef DK_ELEM_F16
     DK_CHECK_HIP(hipFuncSetAttribute((const void*)dk_gemm256v3_kernel<8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
     DK_CHECK_HIP(hipFuncSetAttribute((const void*)dk_gemm256v3_kernel<7, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-#endif
     attr_once.mark();
   }
   SplitArgs sp;
@@ -889,15 +885,12 @@ int dk_launch_gemm256v3(const GemmParams& p, const GemmParams* p2, const GemmRou
   double work = 2.0 * (double)p.M * (double)p.N * (double)p.K;
   if (p2) work += 2.0 * (double)p2->M * (double)p2->N * (double)p2->K;
   dk_prof_begin(p.conv ? 1 : 0, work, stream);
-#ifndef DK_ELEM_F16
   if (p.conv) {
     if (r.tile_rows == 256)
       hipLaunchKernelGGL((dk_gemm256v3_kernel<8, true>), dim3(grid), dim3(512), LDS_BYTES, stream, p, pb, r.tiles_a, r.tiles_b, sp);
     else
       hipLaunchKernelGGL((dk_gemm256v3_kernel<7, true>), dim3(grid), dim3(512), LDS_BYTES, stream, p, pb, r.tiles_a, r.tiles_b, sp);
-  } else
-#endif
-  if (r.tile_rows == 256)
+  } else if (r.tile_rows == 256)
     hipLaunchKernelGGL((dk_gemm256v3_kernel<8, false>), dim3(grid), dim3(512), LDS_BYTES, stream, p, pb, r.tiles_a, r.tiles_b, sp);
   else
     hipLaunchKernelGGL((dk_gemm256v3_kernel<7, false>), dim3(grid), dim3(512), LDS_BYTES, stream, p, pb, r.tiles_a, r.tiles_b, sp);

@@ -31,7 +31,7 @@ __global__ __launch_bounds__(256) void dk_gn_partial_kernel(const bf16_t* __rest
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float a0, a1;
-      unpack2bf(raw[e], a0, a1);
+      unpack2(raw[e], a0, a1);
       s[2 * e] += a0; q[2 * e] += a0 * a0;
       s[2 * e + 1] += a1; q[2 * e + 1] += a1 * a1;
     }
@@ -97,9 +97,9 @@ __global__ __launch_bounds__(256) void dk_gn_finalize_kernel(const float* __rest
     const int cpg = C / G;
     for (int c = tid; c < cpg; c += 256) {
       const int ch = g * cpg + c;
-      const float sc = rf * bf2f(gamma[ch]);
+      const float sc = rf * to_f32(gamma[ch]);
       scale_shift[(size_t)b * 2 * C + ch] = sc;
-      scale_shift[(size_t)b * 2 * C + C + ch] = bf2f(beta[ch]) - mf * sc;
+      scale_shift[(size_t)b * 2 * C + C + ch] = to_f32(beta[ch]) - mf * sc;
     }
   }
 }
@@ -122,9 +122,10 @@ int dk_launch_groupnorm_partials(const bf16_t* x, int B, long HW, int C, int G, 
 }
 int dk_launch_groupnorm_stats(const bf16_t* x, int B, long HW, int C, int G, float* partial, int nchunk, float* mean_rstd,
                               float eps, hipStream_t stream) {
-  const int rc = dk_launch_groupnorm_partials(x, B, HW, C, G, partial, nchunk, stream);
+  // (names in parentheses: no argument-dependent lookup -- hipStream_t would bring the global-scope twin in beside this scope's own)
+  const int rc = (dk_launch_groupnorm_partials)(x, B, HW, C, G, partial, nchunk, stream);
   if (rc) return rc;
-  return dk_launch_groupnorm_finalize(partial, nchunk, B, G, (double)HW * (double)(C / G), eps, mean_rstd, nullptr, nullptr, C, nullptr, stream);
+  return (dk_launch_groupnorm_finalize)(partial, nchunk, B, G, (double)HW * (double)(C / G), eps, mean_rstd, nullptr, nullptr, C, nullptr, stream);
 }
 
 // y = [silu]( bf16( (x - mean) * rstd * gamma + beta ) ), evaluated as x * scale[c] + shift[c] with the per-channel
@@ -139,9 +140,9 @@ __global__ __launch_bounds__(256) void dk_gn_apply_kernel(const bf16_t* __restri
   const int cpg = C / G;
   for (int c = tid; c < C; c += 256) {
     const float* mr = mean_rstd + ((size_t)b * G + c / cpg) * 2;
-    const float sc = mr[1] * bf2f(gamma[c]);
+    const float sc = mr[1] * to_f32(gamma[c]);
     tab[c] = sc;
-    tab[C + c] = bf2f(beta[c]) - mr[0] * sc;
+    tab[C + c] = to_f32(beta[c]) - mr[0] * sc;
   }
   __syncthreads();
   const unsigned cpr = (unsigned)(C / 8);                      // 16-byte chunks per pixel
@@ -164,14 +165,14 @@ __global__ __launch_bounds__(256) void dk_gn_apply_kernel(const bf16_t* __restri
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float a0, a1;
-      unpack2bf(raw[u][e], a0, a1);
-      float y0 = round_bf16(a0 * tab[c0 + 2 * e] + tab[C + c0 + 2 * e]);
-      float y1 = round_bf16(a1 * tab[c0 + 2 * e + 1] + tab[C + c0 + 2 * e + 1]);
+      unpack2(raw[u][e], a0, a1);
+      float y0 = round_act(a0 * tab[c0 + 2 * e] + tab[C + c0 + 2 * e]);
+      float y1 = round_act(a1 * tab[c0 + 2 * e + 1] + tab[C + c0 + 2 * e + 1]);
       if (do_silu) {
         y0 = silu_f(y0);
         y1 = silu_f(y1);
       }
-      o[e] = pack2bf(y0, y1);
+      o[e] = pack2(y0, y1);
     }
     *(u32x4*)(yb + (size_t)i * 8) = o;
   }
@@ -206,7 +207,7 @@ __global__ __launch_bounds__(256) void dk_softmax_rows_kernel(bf16_t* __restrict
     if (c < nchunks) {
       const u32x4 raw = *(const u32x4*)(row + c * 8);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) unpack2bf(raw[e], v[i][2 * e], v[i][2 * e + 1]);
+      for (int e = 0; e < 4; ++e) unpack2(raw[e], v[i][2 * e], v[i][2 * e + 1]);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         if (c * 8 + e >= cols) v[i][e] = -3.0e38f;  // padding: by index, not by value
@@ -240,7 +241,7 @@ __global__ __launch_bounds__(256) void dk_softmax_rows_kernel(bf16_t* __restrict
     if (c < nchunks) {
       u32x4 o;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = pack2bf(v[i][2 * e] * inv, v[i][2 * e + 1] * inv);
+      for (int e = 0; e < 4; ++e) o[e] = pack2(v[i][2 * e] * inv, v[i][2 * e + 1] * inv);
       *(u32x4*)(row + c * 8) = o;
     }
   }
@@ -252,18 +253,18 @@ __global__ __launch_bounds__(256) void dk_softmax_long_rows_kernel(bf16_t* __res
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   bf16_t* row = x + (size_t)blockIdx.x * ld;
   float mx = -3.0e38f;
-  for (int c = tid; c < cols; c += 256) mx = fmaxf(mx, bf2f(row[c]));
+  for (int c = tid; c < cols; c += 256) mx = fmaxf(mx, to_f32(row[c]));
   mx = wave_max(mx);
   if (lane == 0) red[wave] = mx;
   __syncthreads();
   mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
   float sum = 0.f;
-  for (int c = tid; c < cols; c += 256) sum += __expf(bf2f(row[c]) - mx);
+  for (int c = tid; c < cols; c += 256) sum += __expf(to_f32(row[c]) - mx);
   sum = wave_sum(sum);
   if (lane == 0) red[4 + wave] = sum;
   __syncthreads();
   const float inv = 1.0f / (red[4] + red[5] + red[6] + red[7]);
-  for (int c = tid; c < ld; c += 256) row[c] = c < cols ? f2bf(__expf(bf2f(row[c]) - mx) * inv) : (bf16_t)0;
+  for (int c = tid; c < ld; c += 256) row[c] = c < cols ? from_f32(__expf(to_f32(row[c]) - mx) * inv) : (bf16_t)0;
 }
 int dk_launch_softmax_rows(bf16_t* x, int rows, int cols, int ld, hipStream_t stream) {
   DK_REQUIRE(cols >= 1 && cols <= ld && ld % 8 == 0, "softmax: 1 <= cols <= ld, ld a multiple of 8");
@@ -304,7 +305,7 @@ __global__ void dk_pad_channels_kernel(const float* x, bf16_t* y, long npix, int
   if (i >= npix * Cpad) return;
   const int c = (int)(i % Cpad);
   const long pix = i / Cpad;
-  y[i] = c < C ? f2bf(x[pix * C + c]) : (bf16_t)0;
+  y[i] = c < C ? from_f32(x[pix * C + c]) : (bf16_t)0;
 }
 int dk_launch_pad_channels(const float* x, bf16_t* y, long npix, int C, int Cpad, hipStream_t stream) {
   const long n = npix * Cpad;
@@ -320,10 +321,10 @@ __global__ void dk_image_post_kernel(const bf16_t* x, int ldx, float* img, unsig
   if (i >= npix * 3) return;
   const int c = (int)(i % 3);
   const long pix = i / 3;
-  float v = round_bf16(bf2f(x[pix * ldx + c]) * 0.5f + 0.5f);
+  float v = round_act(to_f32(x[pix * ldx + c]) * 0.5f + 0.5f);
   v = fminf(fmaxf(v, 0.f), 1.f);
   if (img) img[i] = v;
-  if (u8) u8[i] = (unsigned char)round_bf16(v * 255.0f);
+  if (u8) u8[i] = (unsigned char)round_act(v * 255.0f);
 }
 int dk_launch_image_post(const bf16_t* x, int ldx, float* img, unsigned char* u8, long npix, hipStream_t stream) {
   const long n = npix * 3;
@@ -339,8 +340,8 @@ __global__ void dk_latent_sample_kernel(const bf16_t* mom, int ldm, const float*
   if (i >= npix * L) return;
   const int c = (int)(i % L);
   const long pix = i / L;
-  const float mean = bf2f(mom[pix * ldm + c]);
-  const float logvar = fminf(fmaxf(bf2f(mom[pix * ldm + L + c]), -30.0f), 20.0f);
+  const float mean = to_f32(mom[pix * ldm + c]);
+  const float logvar = fminf(fmaxf(to_f32(mom[pix * ldm + L + c]), -30.0f), 20.0f);
   out[i] = mean + expf(0.5f * logvar) * noise[i];
 }
 int dk_launch_latent_sample(const bf16_t* mom, int ldm, const float* noise, float* out, long npix, int L, hipStream_t stream) {
@@ -354,7 +355,7 @@ int dk_launch_latent_sample(const bf16_t* mom, int ldm, const float* noise, floa
 __global__ void dk_bf16_rows_to_f32_kernel(const bf16_t* x, int ldx, float* y, long npix, int C) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= npix * C) return;
-  y[i] = bf2f(x[(i / C) * ldx + (i % C)]);
+  y[i] = to_f32(x[(i / C) * ldx + (i % C)]);
 }
 int dk_launch_bf16_rows_to_f32(const bf16_t* x, int ldx, float* y, long npix, int C, hipStream_t stream) {
   const long n = npix * C;

@@ -241,8 +241,20 @@ def unpatchify_tokens(tok: Tensor, cfg: MMDiTConfig, hl: int, wl: int) -> Tensor
     return tok.reshape(b, h, w, p, p, c).permute(0, 1, 3, 2, 4, 5).reshape(b, hl, wl, c)
 
 
+def _vae_set_dtype(lib, handle, config):
+    """element type of a VAE half from ``config.dtype`` ("bfloat16" default | "float16"), set on the handle before the first bind: the torch dtype
+    every bound tensor, ``raw`` (decoder) and the moments (encoder) then have"""
+    name = getattr(config, "dtype", "bfloat16")
+    if name not in _ACT_DTYPE:
+        raise _lib.DkHipError(f"unknown VAE dtype {name!r} (bfloat16 | float16)")
+    code, dt = _ACT_DTYPE[name]
+    _lib.check(lib.dk_vae_set_dtype(handle, code), "dk_vae_set_dtype")
+    return dt
+
+
 class VAEDecoderEngine:
-    """Drop-in for the reference ``VAEDecoder`` (+ the clip / uint8 tail)."""
+    """Drop-in for the reference ``VAEDecoder`` (+ the clip / uint8 tail).  ``config.dtype`` "float16": fp16 weights, activations and ``raw``
+    (the reference's decoder dtype for SD3); bf16 tensors are then refused."""
 
     def __init__(self, config: VAEDecoderConfig, packed_weights: Dict[str, Tensor]):
         self.lib = _lib.load()
@@ -257,9 +269,10 @@ class VAEDecoderEngine:
         h = C.c_void_p()
         _lib.check(self.lib.dk_vae_create(C.byref(c), C.byref(h)), "dk_vae_create")
         self._h = h
+        self.dtype = _vae_set_dtype(self.lib, h, config)
         self.weights = packed_weights
         for name, t in packed_weights.items():
-            _require_cuda(t, name, torch.bfloat16)
+            _require_cuda(t, name, self.dtype)
             _lib.check(self.lib.dk_vae_bind(self._h, name.encode(), t.data_ptr()), f"bind {name}")
         self._ws = None
 
@@ -269,7 +282,7 @@ class VAEDecoderEngine:
             self._h = None
 
     def decode(self, x: Tensor, want_raw: bool = False):
-        """x: f32 [B,h,w,16] -> (image f32 [B,8h,8w,3] in [0,1], uint8 image, raw bf16 or None)."""
+        """x: f32 [B,h,w,16] -> (image f32 [B,8h,8w,3] in [0,1], uint8 image, raw in ``self.dtype`` or None)."""
         x = x.to(torch.float32).contiguous()
         _require_cuda(x, "latent")
         b, h, w, _ = x.shape
@@ -280,7 +293,7 @@ class VAEDecoderEngine:
         scale = 2 ** (len(self.config.block_out_channels) - 1)
         img = torch.empty(b, h * scale, w * scale, 3, dtype=torch.float32, device=x.device)
         u8 = torch.empty(b, h * scale, w * scale, 3, dtype=torch.uint8, device=x.device)
-        raw = torch.empty(b, h * scale, w * scale, 4, dtype=torch.bfloat16, device=x.device) if want_raw else None
+        raw = torch.empty(b, h * scale, w * scale, 4, dtype=self.dtype, device=x.device) if want_raw else None
         _lib.check(self.lib.dk_vae_decode(self._h, x.data_ptr(), b, h, w, img.data_ptr(), u8.data_ptr(), _ptr(raw),
                                           self._ws.data_ptr(), self._ws.numel(), _stream()), "dk_vae_decode")
         return img, u8, raw
@@ -292,7 +305,8 @@ class VAEDecoderEngine:
 
 
 class VAEEncoderEngine:
-    """Drop-in for the reference ``VAEEncoder`` (vae.py:404-467): image in [-1, 1] -> moments."""
+    """Drop-in for the reference ``VAEEncoder`` (vae.py:404-467): image in [-1, 1] -> moments.  ``config.dtype`` "float16": fp16 weights,
+    activations and moments (the reference runs its encoder in fp32: fp16 is the closer 16-bit form, not its dtype)."""
 
     def __init__(self, config, packed_weights: Dict[str, Tensor]):
         self.lib = _lib.load()
@@ -307,9 +321,10 @@ class VAEEncoderEngine:
         h = C.c_void_p()
         _lib.check(self.lib.dk_vae_create(C.byref(c), C.byref(h)), "dk_vae_create")
         self._h = h
+        self.dtype = _vae_set_dtype(self.lib, h, config)
         self.weights = packed_weights
         for name, t in packed_weights.items():
-            _require_cuda(t, name, torch.bfloat16)
+            _require_cuda(t, name, self.dtype)
             _lib.check(self.lib.dk_vae_bind(self._h, name.encode(), t.data_ptr()), f"bind {name}")
         self._ws = None
 
@@ -319,7 +334,7 @@ class VAEEncoderEngine:
             self._h = None
 
     def encode(self, image: Tensor):
-        """image: f32 [B,H,W,3] in [-1,1] -> moments bf16 [B,H/8,W/8,ldm] (mean | logvar in the first
+        """image: f32 [B,H,W,3] in [-1,1] -> moments in ``self.dtype`` [B,H/8,W/8,ldm] (mean | logvar in the first
         ``out_channels`` columns)."""
         image = image.to(torch.float32).contiguous()
         _require_cuda(image, "image")
@@ -330,7 +345,7 @@ class VAEEncoderEngine:
             self._ws = torch.empty(nbytes, dtype=torch.uint8, device=image.device)
         down = 2 ** (len(self.config.block_out_channels) - 1)
         ldm = (self.config.out_channels + 3) // 4 * 4
-        mom = torch.empty(b, H // down, W // down, ldm, dtype=torch.bfloat16, device=image.device)
+        mom = torch.empty(b, H // down, W // down, ldm, dtype=self.dtype, device=image.device)
         _lib.check(self.lib.dk_vae_encode(self._h, image.data_ptr(), b, H, W, mom.data_ptr(), ldm, None,
                                           self._ws.data_ptr(), self._ws.numel(), _stream()), "dk_vae_encode")
         return mom
@@ -341,13 +356,13 @@ class VAEEncoderEngine:
 
     def sample(self, moments: Tensor, noise: Tensor) -> Tensor:
         """encode_image_to_latents tail (__init__.py:588-594): mean + exp(0.5 * clip(logvar)) * noise, f32."""
-        _require_cuda(moments, "moments", torch.bfloat16)
+        _require_cuda(moments, "moments", self.dtype)
         noise = noise.to(torch.float32).contiguous()
         _require_cuda(noise, "noise")
         L = self.config.out_channels // 2
         b, h, w, ldm = moments.shape
         assert noise.shape == (b, h, w, L), (noise.shape, (b, h, w, L))
         out = torch.empty(b, h, w, L, dtype=torch.float32, device=moments.device)
-        _lib.check(self.lib.dk_latent_sample_f32(moments.data_ptr(), ldm, noise.data_ptr(), out.data_ptr(), b * h * w, L,
-                                                 _stream()), "dk_latent_sample_f32")
+        name = "dk_latent_sample_f16" if self.dtype == torch.float16 else "dk_latent_sample_f32"
+        _lib.check(getattr(self.lib, name)(moments.data_ptr(), ldm, noise.data_ptr(), out.data_ptr(), b * h * w, L, _stream()), name)
         return out

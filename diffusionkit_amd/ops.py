@@ -30,6 +30,13 @@ def _elem(dtype, what: str) -> str:
     raise _lib.DkHipError(f"{what}: element type must be torch.bfloat16 or torch.float16, got {dtype}")
 
 
+def _same_elem(dt, what: str, **tensors) -> None:
+    """every optional tensor of an operator call is of the call's element type: mixed element types are refused"""
+    for n, t in tensors.items():
+        if t is not None and t.dtype != dt:
+            raise _lib.DkHipError(f"{what}: {n} must be {dt} like x, got {t.dtype} (mixed element types)")
+
+
 def tune(key: str, value: int) -> None:
     """dk_tune_set: kernel-variant knobs for A/B measurements and parity tests (-1 = automatic)."""
     _lib.check(_lib.load().dk_tune_set(key.encode(), int(value)), "dk_tune_set")
@@ -152,18 +159,20 @@ def conv3x3(x: Tensor, w: Tensor, bias: Optional[Tensor], upsample: bool = False
             downsample: bool = False) -> Tensor:
     """nn.Conv2d k3 on NHWC; w: [O,3,3,C] (or flattened [O, 9C]); C multiple of 64.  Default: stride 1, pad 1
     (``upsample``: over the nearest-x2 view of x); ``downsample``: stride 2 over x padded by one zero row /
-    column at the bottom / right (vae.py:141-143)."""
+    column at the bottom / right (vae.py:141-143).  bf16 tensors, or all float16 (dk_conv3x3_f16)."""
     assert not (upsample and downsample)
     lib = _lib.load()
-    _require_cuda(x, "x", BF)
-    _require_cuda(w, "w", BF)
+    el = _elem(x.dtype, "conv3x3")
+    _require_cuda(x, "x", x.dtype)
+    _require_cuda(w, "w", x.dtype)
+    _same_elem(x.dtype, "conv3x3", bias=bias, res=res)
     B, Hs, Ws, Cc = x.shape
     H, W_ = (Hs * 2, Ws * 2) if upsample else (Hs // 2, Ws // 2) if downsample else (Hs, Ws)
     if downsample:
         assert Hs % 2 == 0 and Ws % 2 == 0, "stride-2 conv needs even input sizes"
     O = w.shape[0]
     ldy = (O + 3) // 4 * 4
-    y = torch.empty(B, H, W_, ldy, dtype=BF, device=x.device)
+    y = torch.empty(B, H, W_, ldy, dtype=x.dtype, device=x.device)
     d = _lib.dk_conv_desc()
     d.x, d.w, d.y, d.bias, d.res = x.data_ptr(), w.data_ptr(), y.data_ptr(), _ptr(bias), _ptr(res)
     d.zeros = zero_page(x.device).data_ptr()
@@ -171,34 +180,53 @@ def conv3x3(x: Tensor, w: Tensor, bias: Optional[Tensor], upsample: bool = False
     d.ldy, d.ldr = ldy, (res.shape[-1] if res is not None else 0)
     d.upsample = 2 if downsample else int(upsample)
     d.epilogue = DK_EPI_RES if res is not None else DK_EPI_BIAS
-    _lib.check(lib.dk_conv3x3_bf16(C.byref(d), _stream()), "dk_conv3x3_bf16")
+    _lib.check(getattr(lib, "dk_conv3x3_" + el)(C.byref(d), _stream()), "dk_conv3x3_" + el)
     return y[..., :O]
 
 
+def conv3x3_plan(B: int, H: int, W: int, C_in: int, O: int, upsample: int = 0, dtype=BF, res: bool = False, workspace: int = 0):
+    """dk_conv3x3_plan / dk_conv3x3_plan_f16: the route a ``conv3x3`` call of this OUTPUT size would take (host only, nothing is launched;
+    the pointers are made-up, aligned integers)."""
+    d = _lib.dk_conv_desc()
+    d.x, d.w, d.y, d.bias, d.zeros = 0x10000, 0x20000, 0x30000, 0x40000, 0x50000
+    d.res = 0x60000 if res else None
+    d.B, d.H, d.W, d.C, d.O = B, H, W, C_in, O
+    d.ldy, d.ldr = (O + 3) // 4 * 4, (O if res else 0)
+    d.upsample = int(upsample)
+    d.epilogue = DK_EPI_RES if res else DK_EPI_BIAS
+    plan = _lib.dk_gemm_plan_t()
+    name = "dk_conv3x3_plan" if _elem(dtype, "conv3x3_plan") == "bf16" else "dk_conv3x3_plan_f16"
+    _lib.check(getattr(_lib.load(), name)(C.byref(d), C.byref(plan)), name)
+    return plan
+
+
 def attention_d512(q: Tensor, k: Tensor, v: Tensor, scale: Optional[float] = None) -> Tensor:
-    """single-head attention over head_dim 512 (VAE mid block, vae.py:28-57), flash-style; q / k / v: [B, T, 512] bf16."""
+    """single-head attention over head_dim 512 (VAE mid block, vae.py:28-57), flash-style; q / k / v: [B, T, 512] bf16, or all float16."""
     lib = _lib.load()
+    name = "dk_attention_d512_" + _elem(q.dtype, "attention_d512")
     for n, t in (("q", q), ("k", k), ("v", v)):
-        _require_cuda(t, n, BF)
+        _require_cuda(t, n, q.dtype)
     B, T, Cc = q.shape
     assert Cc == 512, f"attention_d512: head_dim {Cc}, the kernel is built for 512"
     for n, t in (("q", q), ("k", k), ("v", v)):
         assert t.shape == q.shape and t.is_contiguous(), f"attention_d512: {n} must be a dense [B, T, 512] tensor (row pitch 512)"
     out = torch.empty_like(q)
-    vt = torch.empty(B * 512 * lib.dk_attention_d512_tp(T), dtype=BF, device=q.device)
+    vt = torch.empty(B * 512 * lib.dk_attention_d512_tp(T), dtype=q.dtype, device=q.device)
     scale = scale if scale is not None else 1.0 / math.sqrt(Cc)
-    _lib.check(lib.dk_attention_d512_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, T, Cc, Cc, scale, vt.data_ptr(),
-                                          _stream()), "dk_attention_d512_bf16")
+    _lib.check(getattr(lib, name)(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, T, Cc, Cc, scale, vt.data_ptr(), _stream()), name)
     return out
 
 
 def groupnorm_table(x: Optional[Tensor], gamma: Tensor, beta: Tensor, groups: int, eps: float, partials: Optional[Tensor] = None,
                     shape=None) -> Tensor:
     """(scale | shift) table [B, 2, C] fp32 of nn.GroupNorm over NHWC ``x`` -- or over the tensor whose output-statistics
-    ``partials`` [B, n, G, 2] a ``conv3x3_gn`` launch produced (then ``shape`` = (B, H*W, C))."""
+    ``partials`` [B, n, G, 2] a ``conv3x3_gn`` launch produced (then ``shape`` = (B, H*W, C)).  The element type is ``gamma``'s
+    (bf16 | float16); ``beta`` and ``x`` must match it."""
     lib = _lib.load()
+    name = "dk_groupnorm_table_" + _elem(gamma.dtype, "groupnorm_table")
+    _same_elem(gamma.dtype, "groupnorm_table", beta=beta, x=x)
     if x is not None:
-        _require_cuda(x, "x", BF)
+        _require_cuda(x, "x", gamma.dtype)
         B, HW, Cc = x.shape[0], x.shape[1] * x.shape[2], x.shape[3]
         n_part = 0
         scratch = torch.empty(lib.dk_groupnorm_scratch_floats(B, groups), dtype=torch.float32, device=x.device)
@@ -208,8 +236,8 @@ def groupnorm_table(x: Optional[Tensor], gamma: Tensor, beta: Tensor, groups: in
         scratch = torch.empty(B * max(1024, n_part) * 2 * groups + B * groups * 2, dtype=torch.float32, device=partials.device)
         scratch[:partials.numel()] = partials.reshape(-1)
     ss = torch.empty(B, 2, Cc, dtype=torch.float32, device=gamma.device)
-    _lib.check(lib.dk_groupnorm_table_bf16(_ptr(x), B, HW, Cc, groups, gamma.data_ptr(), beta.data_ptr(), eps, scratch.data_ptr(),
-                                           n_part, ss.data_ptr(), _stream()), "dk_groupnorm_table_bf16")
+    _lib.check(getattr(lib, name)(_ptr(x), B, HW, Cc, groups, gamma.data_ptr(), beta.data_ptr(), eps, scratch.data_ptr(),
+                                  n_part, ss.data_ptr(), _stream()), name)
     return ss
 
 
@@ -217,10 +245,14 @@ def conv3x3_gn(x: Tensor, w: Tensor, bias: Tensor, gn_table: Optional[Tensor] = 
                x2: Optional[Tensor] = None, bias2: Optional[Tensor] = None, stats_groups: int = 0, upsample: bool = False,
                image: bool = False):
     """norm -> silu -> conv3x3 as one launch (csrc/conv_halo.hip): ``x`` raw NHWC, ``gn_table`` from ``groupnorm_table``;
-    ``w`` [O, 9 C (+ C2)] K-major.  Returns y, or (y, partials) with ``stats_groups``, or (image_f32, image_u8, raw) with ``image``."""
+    ``w`` [O, 9 C (+ C2)] K-major.  Returns y, or (y, partials) with ``stats_groups``, or (image_f32, image_u8, raw) with ``image``.
+    bf16 tensors, or all float16 (dk_conv3x3_gn_f16: always conv_halo.hip's kernel, whatever ``tune("conv_v4", v)`` says)."""
     lib = _lib.load()
-    _require_cuda(x, "x", BF)
-    _require_cuda(w, "w", BF)
+    dt = x.dtype
+    name = "dk_conv3x3_gn_" + _elem(dt, "conv3x3_gn")
+    _require_cuda(x, "x", dt)
+    _require_cuda(w, "w", dt)
+    _same_elem(dt, "conv3x3_gn", bias=bias, res=res, x2=x2, bias2=bias2)
     B, Hs, Ws, Cc = x.shape
     H, W_ = (Hs * 2, Ws * 2) if upsample else (Hs, Ws)
     O = w.shape[0]
@@ -235,18 +267,18 @@ def conv3x3_gn(x: Tensor, w: Tensor, bias: Tensor, gn_table: Optional[Tensor] = 
     if image:
         img = torch.empty(B, H, W_, 3, dtype=torch.float32, device=x.device)
         u8 = torch.empty(B, H, W_, 3, dtype=torch.uint8, device=x.device)
-        raw = torch.empty(B, H, W_, 4, dtype=BF, device=x.device)
+        raw = torch.empty(B, H, W_, 4, dtype=dt, device=x.device)
         d.image_f32, d.image_u8, d.raw_bf16 = img.data_ptr(), u8.data_ptr(), raw.data_ptr()
         out = (img, u8, raw)
     else:
-        y = torch.empty(B, H, W_, O, dtype=BF, device=x.device)
+        y = torch.empty(B, H, W_, O, dtype=dt, device=x.device)
         d.y, d.ldy, d.ldr = y.data_ptr(), O, (res.shape[-1] if res is not None else 0)
         out = y
         if stats_groups:
             part = torch.empty(B, (H // 16) * (W_ // 16), stats_groups, 2, dtype=torch.float32, device=x.device)
             d.stats_partial, d.stats_groups = part.data_ptr(), stats_groups
             out = (y, part)
-    _lib.check(lib.dk_conv3x3_gn_bf16(C.byref(d), _stream()), "dk_conv3x3_gn_bf16")
+    _lib.check(getattr(lib, name)(C.byref(d), _stream()), name)
     return out
 
 
@@ -337,14 +369,16 @@ def euler_cfg_step(x: Tensor, model_out: Tensor, tokens: Tensor, n_img: int, cfg
 
 
 def groupnorm(x: Tensor, gamma: Tensor, beta: Tensor, groups: int, eps: float, silu: bool) -> Tensor:
-    """x: NHWC bf16 [B,H,W,C]."""
+    """x: NHWC [B,H,W,C], bf16 or float16 (gamma / beta in the same type)."""
     lib = _lib.load()
-    _require_cuda(x, "x", BF)
+    name = "dk_groupnorm_" + _elem(x.dtype, "groupnorm")
+    _require_cuda(x, "x", x.dtype)
+    _same_elem(x.dtype, "groupnorm", gamma=gamma, beta=beta)
     B, H, W_, Cc = x.shape
     y = torch.empty_like(x)
     scratch = torch.empty(lib.dk_groupnorm_scratch_floats(B, groups), dtype=torch.float32, device=x.device)
-    _lib.check(lib.dk_groupnorm_bf16(x.data_ptr(), y.data_ptr(), B, H * W_, Cc, groups, gamma.data_ptr(), beta.data_ptr(), eps,
-                                     int(silu), scratch.data_ptr(), _stream()), "dk_groupnorm_bf16")
+    _lib.check(getattr(lib, name)(x.data_ptr(), y.data_ptr(), B, H * W_, Cc, groups, gamma.data_ptr(), beta.data_ptr(), eps,
+                                  int(silu), scratch.data_ptr(), _stream()), name)
     return y
 
 
@@ -352,17 +386,19 @@ def softmax_rows_(x: Tensor) -> Tensor:
     """In-place row softmax; ``x`` may be a column slice ``buf[:, :cols]`` of a wider row-major buffer, whose remaining
     columns are then written as zeros (row stride a multiple of 8)."""
     lib = _lib.load()
-    if not (x.is_cuda and x.dtype == BF and x.dim() == 2 and x.stride(1) == 1):
-        raise _lib.DkHipError("softmax_rows_: bf16 GPU matrix with unit column stride expected")
-    _lib.check(lib.dk_softmax_rows_bf16(x.data_ptr(), x.shape[0], x.shape[1], x.stride(0), _stream()), "dk_softmax_rows_bf16")
+    if not (x.is_cuda and x.dtype in (BF, F16) and x.dim() == 2 and x.stride(1) == 1):
+        raise _lib.DkHipError("softmax_rows_: bf16 / float16 GPU matrix with unit column stride expected")
+    name = "dk_softmax_rows_" + _elem(x.dtype, "softmax_rows_")
+    _lib.check(getattr(lib, name)(x.data_ptr(), x.shape[0], x.shape[1], x.stride(0), _stream()), name)
     return x
 
 
 def transpose(x: Tensor) -> Tensor:
     lib = _lib.load()
-    _require_cuda(x, "x", BF)
-    y = torch.empty(x.shape[1], x.shape[0], dtype=BF, device=x.device)
-    _lib.check(lib.dk_transpose_bf16(x.data_ptr(), y.data_ptr(), x.shape[0], x.shape[1], _stream()), "dk_transpose_bf16")
+    name = "dk_transpose_" + _elem(x.dtype, "transpose")
+    _require_cuda(x, "x", x.dtype)
+    y = torch.empty(x.shape[1], x.shape[0], dtype=x.dtype, device=x.device)
+    _lib.check(getattr(lib, name)(x.data_ptr(), y.data_ptr(), x.shape[0], x.shape[1], _stream()), name)
     return y
 
 

@@ -99,7 +99,14 @@ class DiffusionPipeline:
         text_len: Optional[int] = None,
         packed_weights: Optional[dict] = None,
         activation_dtype: Optional[str] = None,
+        vae_dtype: Optional[str] = None,
     ):
+        """``vae_dtype``: element type of the VAE decoder and (built on first use, img2img) encoder -- None or "bfloat16": bf16, today's
+        behaviour bit for bit, also together with ``activation_dtype="float16"``; "float16": fp16 weights, activations and image tail.  It is the
+        VAE's own switch and is accepted for every family: float16 is the reference's decoder dtype for Stable Diffusion 3
+        (mlx/__init__.py:108-113,483-484), not for FLUX (bf16 there); the reference's encoder runs in fp32, so the fp16 encoder is the closer
+        16-bit form, not its dtype.  ``packed_weights["vae_decoder"]`` / ``["vae_encoder"]`` must then hold float16 tensors (pack_vae with a
+        float16_vae_config)."""
         _lib.load()  # fail loudly before anything else if the HIP extension is missing
         # The MI355X build computes in bf16 end to end (BASELINE.json configs); w16/a16 are
         # accepted for signature compatibility.  The reference's defaults (w16 = a16 = False) mean fp32 weights / activations
@@ -111,8 +118,8 @@ class DiffusionPipeline:
         self.dtype = torch.bfloat16
         self.activation_dtype = torch.bfloat16
         # activation_dtype="float16": the MMDiT engine, the conditioning hand-over, the CFG denoiser and the Euler loop run in the reference's
-        # dtype for Stable Diffusion 3 (fp16 weights and activations, mlx/__init__.py:76-79); the text encoders and the VAE stay bf16
-        # (DESIGN.md section 8).  None (default): bf16, exactly as before
+        # dtype for Stable Diffusion 3 (fp16 weights and activations, mlx/__init__.py:76-79); the text encoders stay bf16, the VAE has its own
+        # switch, vae_dtype.  None (default): bf16, exactly as before
         if activation_dtype not in (None, "bfloat16", "float16"):
             raise ValueError(f"unknown activation_dtype {activation_dtype!r} (bfloat16 | float16)")
         if activation_dtype == "float16":
@@ -138,6 +145,10 @@ class DiffusionPipeline:
             self.float16_dtype = self.dtype = self.activation_dtype = torch.float16
         self.vae_config = vae_config or VAEDecoderConfig()
         self.vae_encoder_config = vae_encoder_config or VAEEncoderConfig()
+        if vae_dtype is not None:
+            from .config import float16_vae_config
+            self.vae_config = float16_vae_config(self.vae_config, vae_dtype)  # (ValueError for an unknown name)
+            self.vae_encoder_config = float16_vae_config(self.vae_encoder_config, vae_dtype)
         self.weights_seed = weights_seed
         self._text_len_override = text_len
         self._packed_weights = packed_weights  # {"mmdit": ..., "vae_decoder": ...} already in engine layout

@@ -343,7 +343,10 @@ def pack_mmdit(cfg: MMDiTConfig, w: Dict[str, Tensor], device, consume: bool = F
 
 
 def pack_vae(cfg, w: Dict[str, Tensor], device) -> Dict[str, Tensor]:
-    """Decoder or encoder half: conv weights [O,3,3,I] -> [O, 9*I] (conv_in zero-padded to I = 64)."""
+    """Decoder or encoder half: conv weights [O,3,3,I] -> [O, 9*I] (conv_in zero-padded to I = 64), in ``cfg.dtype`` (bfloat16 | float16):
+    one rounding from the source tensors."""
+    from .config import validate_vae_dtype
+    elem = getattr(torch, validate_vae_dtype(getattr(cfg, "dtype", "bfloat16")))
     dev = torch.device(device)
     out: Dict[str, Tensor] = {}
     for k, t in w.items():
@@ -355,7 +358,7 @@ def pack_vae(cfg, w: Dict[str, Tensor], device) -> Dict[str, Tensor]:
             t = tp
         if t.dim() == 4:
             t = t.reshape(t.shape[0], -1)
-        out[k] = t.to(torch.bfloat16).contiguous()
+        out[k] = t.to(elem).contiguous()
     # channel-changing resnets (vae.py:86-89,98-99): [conv2 | conv_shortcut] along the reduction, for the fused stage that runs the
     # 1x1 shortcut as extra K-tiles of conv2 (csrc/conv_halo.hip); the separate tensors stay for the unfused path
     for k in list(out):

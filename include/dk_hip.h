@@ -358,8 +358,9 @@ int dk_affine_f32(const float* x, float* y, int64_t n, float a, float b, void* s
  * accumulation, the same rounding points with fp16 in place of bf16.  An fp32 -> fp16 store that overflows gives +-inf, as the
  * reference's casts do (no clamp).  Every tensor a descriptor names (A, W, C, bias, gate, res, norm weights, q / k / v / out) is
  * fp16; RoPE tables, the latent and timesteps stay fp32.
- *  - GEMM: Linears only (no convolution); the route is the 128 x 128 kernel or the 256-column 8-wave kernel (generation 3) --
- *    dk_gemm_plan_f16 never reports generation 4, and dk_tune_set("gemm", 10) / ("gemm_v4", v) have no effect on these launches.
+ *  - GEMM: the route is the 128 x 128 kernel or the 256-column 8-wave kernel (generation 3) -- dk_gemm_plan_f16 never reports
+ *    generation 4, and dk_tune_set("gemm", 10) / ("gemm_v4", v) have no effect on these launches.  The implicit-GEMM convolution
+ *    (dk_conv3x3_f16) takes the same two kernels' conv forms; dk_conv3x3_plan_f16 reports its route.
  *  - Attention: head_dim 64, no score bias, no MX-fp8 copy; always the lean kernel (dk_tune_set("attn", 9 / 10) have no effect).
  *    Scores, running maximum and sum in fp32, P rounded to fp16 for the P.V product.
  *  - dk_timestep_embedding_f16: evaluated in `embed_dtype` as before, stored as fp16.
@@ -381,6 +382,27 @@ int dk_latent_to_tokens_f16(const float* x, void* tokens, int32_t n_img, int32_t
 int dk_euler_cfg_step_f16(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img,
                           int32_t cfg_on, int32_t Hl, int32_t Wl, int32_t C, int32_t p, int32_t reshape_order,
                           float sigma, float sigma_next, float cfg_weight, void* stream);
+
+/* The VAE's operators on IEEE-half tensors (the reference decodes SD3 latents with an fp16 decoder, mlx/__init__.py:108-113,483-484):
+ * same descriptors and scratch sizes as their *_bf16 siblings, every 16-bit tensor they name is fp16 (gamma / beta included), statistics, tables
+ * and accumulators stay fp32, the rounding points are the same with fp16 in place of bf16.
+ *  - dk_conv3x3_gn_f16: always conv_halo.hip's kernel -- the one-wave-per-SIMD frame (conv256v4.hip, generated asm body) is bf16 only, and
+ *    dk_tune_set("conv_v4", v) has no effect on fp16 launches.  Image tail: raw, raw / 2 + 0.5 and img * 255 are rounded to fp16
+ *    (uint8 image = truncation of the fp16 product, __init__.py:525-526).
+ *  - dk_attention_d512_f16: scores, running maximum and sum in fp32, P rounded to fp16 for the P.V product.
+ *  - dk_conv3x3_plan / dk_conv3x3_plan_f16: dk_gemm_plan of a dk_conv3x3_* call (host only, nothing is launched, pointers are not read). */
+int dk_conv3x3_f16(const dk_conv_desc* d, void* stream);
+int dk_conv3x3_plan(const dk_conv_desc* d, dk_gemm_plan_t* plan);
+int dk_conv3x3_plan_f16(const dk_conv_desc* d, dk_gemm_plan_t* plan);
+int dk_conv3x3_gn_f16(const dk_conv_gn_desc* d, void* stream);
+int dk_groupnorm_table_f16(const void* x, int32_t B, int64_t HW, int32_t C, int32_t G, const void* gamma, const void* beta,
+                           float eps, float* scratch, int32_t n_partial, float* scale_shift, void* stream);
+int dk_groupnorm_f16(const void* x, void* y, int32_t B, int64_t HW, int32_t C, int32_t G, const void* gamma,
+                     const void* beta, float eps, int32_t fuse_silu, float* scratch_f32, void* stream);
+int dk_attention_d512_f16(const void* q, const void* k, const void* v, void* out, int32_t B, int32_t T, int32_t ld, int32_t ldo,
+                          float scale, void* vt_scratch, void* stream);
+int dk_softmax_rows_f16(void* x, int32_t rows, int32_t cols, int32_t ld, void* stream);
+int dk_transpose_f16(const void* x, void* y, int32_t R, int32_t C, void* stream);
 
 /* nn.GroupNorm(pytorch_compatible=True) [+ nn.silu], vae.py:34,72,78,381,91,96,398.
  * x, y: NHWC bf16 [B, HW, C]; scratch_f32 needs dk_groupnorm_scratch_floats(B, G) floats. */
@@ -492,6 +514,12 @@ void dk_vae_destroy(dk_vae* v);
 /* names = reference module tree (vae.py / model_io.py:411-486), conv weights flattened to
  * [O, 9*I]; conv_in.weight zero-padded to I = 64 */
 int dk_vae_bind(dk_vae* v, const char* name, const void* dev_ptr);
+/* Element type of the handle (decoder or encoder): 0 = bfloat16 (the default) or 1 = float16; anything else is refused.  Call it
+ * before the first dk_vae_bind: every bound tensor is then of that type, and so are the activations, `raw_bf16` of dk_vae_decode and
+ * `moments_bf16` of dk_vae_encode (the f32 outputs stay f32).  A later call -- after a bind, or after an earlier dk_vae_set_dtype -- is
+ * refused unless it names the type already set.  fp16 is the reference's decoder dtype for Stable Diffusion 3 (mlx/__init__.py:108-113); its
+ * encoder runs in fp32 (:116), so the fp16 encoder is the closer of the two 16-bit forms, not the reference's dtype. */
+int dk_vae_set_dtype(dk_vae* v, int32_t dtype);
 size_t dk_vae_workspace_bytes(const dk_vae* v, int32_t batch, int32_t latent_h, int32_t latent_w);
 /* VAEDecoder.__call__ (vae.py:386-401) + decode_latents_to_image (__init__.py:581-584) +
  * uint8 conversion (__init__.py:525-526).  latent: f32 [B,h,w,16];
@@ -514,6 +542,8 @@ int dk_vae_encode(dk_vae* v, const float* image, int32_t batch, int32_t image_h,
  * latent = mean + exp(0.5 * clip(logvar, -30, 20)) * noise, f32 [n_pixels, latent_channels] */
 int dk_latent_sample_f32(const void* moments_bf16, int32_t ldm, const float* noise, float* latent,
                          int64_t n_pixels, int32_t latent_channels, void* stream);
+int dk_latent_sample_f16(const void* moments_f16, int32_t ldm, const float* noise, float* latent,
+                         int64_t n_pixels, int32_t latent_channels, void* stream);  /* the same on fp16 moments (an fp16 encoder's) */
 
 /* ------------------------------------------------------------------------------------------
  * Measurement hooks (no reference counterpart; the reference times phases with time.time(),
