@@ -211,7 +211,7 @@ __global__ __launch_bounds__(NW * 64, 2) void dk_attn2_fwd_kernel(AttnParams p) 
       s1 = mfma_32x32x16(k1, qf[kk], s1);                               \
     }                                                                                                      \
     __builtin_amdgcn_s_setprio(0);                                                                         \
-    if (j_ * 64 + 64 > S) {                                                                                \
+    if (!HAS_BIAS && j_ * 64 + 64 > S) {                                                                   \
       asm volatile("; tail tile" ::: "memory"); /* keeps hipcc from if-converting the mask into every tile */ \
       _Pragma("unroll") for (int e = 0; e < 16; ++e) {                                                     \
         const int key = j_ * 64 + (e & 3) + 8 * (e >> 2) + 4 * hi;                                         \
@@ -230,6 +230,13 @@ __global__ __launch_bounds__(NW * 64, 2) void dk_attn2_fwd_kernel(AttnParams p) 
           s0[4 * g4 + e] += f0[e] * inv_scale;                                                             \
           s1[4 * g4 + e] += f1[e] * inv_scale;                                                             \
         }                                                                                                  \
+      }                                                                                                    \
+    }                                                                                                      \
+    if (HAS_BIAS) { /* the mask comes AFTER the bias, as a select: whatever the pad columns S..ldb of a bias row hold never reaches a score */\
+      _Pragma("unroll") for (int e = 0; e < 16; ++e) {                                                     \
+        const int key = j_ * 64 + (e & 3) + 8 * (e >> 2) + 4 * hi;                                         \
+        s0[e] = key >= S ? -1e30f : s0[e];                                                                 \
+        s1[e] = key + 32 >= S ? -1e30f : s1[e];                                                            \
       }                                                                                                    \
     }                                                                                                      \
     float mloc = fmaxf(s0[0], s1[0]);                                                                      \
