@@ -1,0 +1,453 @@
+// C-ABI layer (include/dk_hip.h), part 1: the error string, dk_tune_set, the layout rules (dk_weight_pitch*, dk_mx_scale_bytes) and every
+// stand-alone operator entry.  The engines are mmdit_engine.hip and vae_engine.hip.  Host code only: no kernels are defined here.
+#include <cmath>
+#include <cstdio>
+
+#include "dk_engine.h"
+
+static thread_local std::string g_last_error;
+void dk_set_error(const std::string& msg) { g_last_error = msg; }
+
+extern "C" int dk_abi_version(void) { return DK_ABI_VERSION; }
+extern "C" const char* dk_last_error(void) { return g_last_error.c_str(); }
+
+// Rows of K >= g_dk_pitch_min_k elements (the [h, 5h] linear2 and [h, 4h] fc2 weights of FLUX and the activations they
+// multiply) are stored with 64 elements of padding: a 24-30 KB row stride makes the K-tile DMA of 256 rows camp on a few
+// memory channels (linear2 of FLUX: 369 -> 345 us with the padded pitch, profiles/archive/r01_gemm_lab_pitch.log).
+int g_dk_pitch_min_k = 8192;
+extern "C" int32_t dk_weight_pitch(int32_t k) { return k >= g_dk_pitch_min_k ? k + 64 : k; }
+extern "C" int32_t dk_weight_pitch_fp8(int32_t k) { return k >= g_dk_pitch_min_k ? k + 128 : k; }
+extern "C" size_t dk_mx_scale_bytes(int64_t rows, int32_t k) { return (size_t)((k + 127) / 128) * (size_t)mx_nblk((long)rows) * 512; }
+
+// every knob is defined, with its values and its default, in the file that reads it
+extern "C" int dk_tune_set(const char* key, int32_t value) {
+  static const struct { const char* key; int* knob; } knobs[] = {
+      {"gemm", &g_dk_gemm_mode}, {"gemm_v4", &g_dk_v4_auto}, {"gemm_skew", &g_dk_v4_skew}, {"gemm_mf", &g_dk_v3_mf},
+      {"gemm_split", &g_dk_v3_split}, {"gemm_split_min", &g_dk_v3_split_min}, {"gemm_pair_nk", &g_dk_pair_split_nk},
+      {"gemm_fuse_k", &g_dk_fuse_k}, {"gemm_fuse_q", &g_dk_fuse_qg}, {"attn", &g_dk_attn_mode}, {"attn_fuse_q", &g_dk_fuse_q},
+      {"attn_split", &g_dk_attn5_split}, {"pitch_min_k", &g_dk_pitch_min_k}, {"conv_halo", &g_dk_conv_halo}, {"conv_v4", &g_dk_conv_v4}};
+  DK_REQUIRE(key != nullptr, "null key");
+  for (const auto& k : knobs)
+    if (strcmp(key, k.key) == 0) { *k.knob = value; return 0; }
+  dk_set_error(std::string("unknown tuning key: ") + key);
+  return -1;
+}
+
+thread_local int g_elem_dtype = DK_DTYPE_BF16;  // (ElemScope, dk_engine.h)
+thread_local void* g_linear_ws = nullptr;       // (LinearWsScope, dk_engine.h)
+
+// ---------------------------------------------------------------------------------------------
+// operator-level wrappers
+// ---------------------------------------------------------------------------------------------
+static GemmParams gemm_params_from_desc(const dk_gemm_desc* d) {
+  GemmParams p;
+  memset(&p, 0, sizeof(p));
+  p.dtype = g_elem_dtype;
+  p.A = (const bf16_t*)d->A; p.W = (const bf16_t*)d->W; p.C = (bf16_t*)d->C;
+  p.bias = (const bf16_t*)d->bias; p.gate = (const bf16_t*)d->gate; p.res = (const bf16_t*)d->res;
+  p.M = d->M; p.N = d->N; p.K = d->K;
+  p.lda = d->lda; p.ldc = d->ldc; p.ldr = d->ldr;
+  p.a_seg_len = d->a_seg_len > 0 ? d->a_seg_len : d->M; p.a_seg_stride = d->a_seg_stride;
+  p.c_seg_len = d->c_seg_len > 0 ? d->c_seg_len : d->M; p.c_seg_stride = d->c_seg_stride;
+  p.r_seg_len = d->r_seg_len > 0 ? d->r_seg_len : d->M; p.r_seg_stride = d->r_seg_stride;
+  p.gate_seg_len = d->gate_seg_len > 0 ? d->gate_seg_len : d->M; p.gate_stride = d->gate_stride;
+  p.alpha = d->alpha; p.epi = d->epilogue; p.ldw = d->ldw;
+  p.workspace = d->workspace; p.workspace_bytes = d->workspace_bytes;
+  return p;
+}
+
+extern "C" size_t dk_gemm_workspace_bytes(void) { return dk_gemm_split_workspace_bytes(); }
+
+extern "C" int dk_gemm_bf16(const dk_gemm_desc* d, void* stream) {
+  DK_REQUIRE(d != nullptr, "null descriptor");
+  return dk_launch_gemm(gemm_params_from_desc(d), S_(stream));
+}
+
+extern "C" int dk_gemm_f16(const dk_gemm_desc* d, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_gemm_bf16(d, stream);
+}
+
+extern "C" int dk_gemm_plan(const dk_gemm_desc* d, const dk_gemm_desc* d2, dk_gemm_plan_t* plan) {
+  DK_REQUIRE(d != nullptr && plan != nullptr, "null descriptor / plan");
+  const GemmParams p2 = d2 != nullptr ? gemm_params_from_desc(d2) : GemmParams{};
+  return dk_gemm_plan_call(gemm_params_from_desc(d), d2 != nullptr ? &p2 : nullptr, *plan);
+}
+
+extern "C" int dk_gemm_plan_f16(const dk_gemm_desc* d, const dk_gemm_desc* d2, dk_gemm_plan_t* plan) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_gemm_plan(d, d2, plan);
+}
+
+// the engine-only fields of GemmParams beside a descriptor (dk_gemm_side / dk_gemm_fp8_side: same names); null: nothing fused
+template <class P, class F>
+static void set_fused(P& p, const F* f) {
+  if (f == nullptr) return;
+  p.n_split = f->n_split; p.C2 = (decltype(p.C2))f->C2; p.ldc2 = f->ldc2; p.epi2 = f->epi2;
+  p.kn_w = (const bf16_t*)f->kn_w; p.kn_rope = f->kn_rope;
+  p.kn_col0 = f->kn_col0; p.kn_col1 = f->kn_col1; p.kn_D = f->kn_D; p.kn_pos_off = f->kn_pos_off; p.kn_seg_len = f->kn_seg_len; p.kn_eps = f->kn_eps;
+  p.qn_w = (const bf16_t*)f->qn_w; p.qn_col0 = f->qn_col0; p.qn_col1 = f->qn_col1;
+}
+
+// (no checks of their own: dk_gemm_route / the *_eligible functions decide what a form launches)
+extern "C" int dk_gemm_fused_bf16(const dk_gemm_desc* d, const dk_gemm_side* f, const dk_gemm_desc* d2, const dk_gemm_side* f2, void* stream) {
+  DK_REQUIRE(d != nullptr && (d2 != nullptr || f2 == nullptr), "null descriptor");
+  GemmParams p = gemm_params_from_desc(d);
+  set_fused(p, f);
+  if (d2 == nullptr) return dk_launch_gemm(p, S_(stream));
+  GemmParams p2 = gemm_params_from_desc(d2);
+  set_fused(p2, f2);
+  return dk_launch_gemm_pair(p, p2, S_(stream));
+}
+
+extern "C" int dk_gemm_fused_f16(const dk_gemm_desc* d, const dk_gemm_side* f, const dk_gemm_desc* d2, const dk_gemm_side* f2, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_gemm_fused_bf16(d, f, d2, f2, stream);
+}
+
+extern "C" int dk_gemm_fused_plan(const dk_gemm_desc* d, const dk_gemm_side* f, const dk_gemm_desc* d2, const dk_gemm_side* f2,
+                                  dk_gemm_plan_t* plan) {
+  DK_REQUIRE(d != nullptr && plan != nullptr && (d2 != nullptr || f2 == nullptr), "null descriptor / plan");
+  GemmParams p = gemm_params_from_desc(d), p2 = d2 != nullptr ? gemm_params_from_desc(d2) : GemmParams{};
+  set_fused(p, f);
+  if (d2 != nullptr) set_fused(p2, f2);
+  return dk_gemm_plan_call(p, d2 != nullptr ? &p2 : nullptr, *plan);
+}
+
+int conv3x3_launch(const dk_conv_desc* d, void* workspace, hipStream_t stream, dk_gemm_plan_t* rec) {  // (dk_engine.h)
+  DK_REQUIRE(d != nullptr, "null descriptor");
+  GemmParams p;
+  memset(&p, 0, sizeof(p));
+  p.dtype = g_elem_dtype;
+  p.A = (const bf16_t*)d->x; p.W = (const bf16_t*)d->w; p.C = (bf16_t*)d->y;
+  p.bias = (const bf16_t*)d->bias; p.res = (const bf16_t*)d->res;
+  p.M = d->B * d->H * d->W; p.N = d->O; p.K = 9 * d->C;
+  p.lda = d->C; p.ldc = d->ldy; p.ldr = d->ldr;
+  p.a_seg_len = p.c_seg_len = p.r_seg_len = p.gate_seg_len = p.M;
+  p.alpha = 1.0f; p.epi = d->epilogue;
+  p.conv = 1; p.cB = d->B; p.cH = d->H; p.cW = d->W; p.cC = d->C; p.ups = d->upsample;
+  p.zeros = (const bf16_t*)d->zeros;
+  if (workspace) { p.workspace = workspace; p.workspace_bytes = dk_gemm_split_workspace_bytes(); }
+  DK_REQUIRE(d->upsample >= 0 && d->upsample <= 2, "upsample: 0 plain, 1 nearest-x2 input view, 2 stride-2 (downsample)");
+  if (d->upsample == 1) DK_REQUIRE(d->H % 2 == 0 && d->W % 2 == 0, "upsampled conv needs even output size");
+  if (rec != nullptr) return dk_gemm_plan_call(p, nullptr, *rec);
+  return dk_launch_gemm(p, stream);
+}
+extern "C" int dk_conv3x3_bf16(const dk_conv_desc* d, void* stream) { return conv3x3_launch(d, nullptr, S_(stream)); }
+extern "C" int dk_conv3x3_f16(const dk_conv_desc* d, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_conv3x3_bf16(d, stream);
+}
+extern "C" int dk_conv3x3_plan(const dk_conv_desc* d, dk_gemm_plan_t* plan) {
+  DK_REQUIRE(plan != nullptr, "null plan");
+  return conv3x3_launch(d, nullptr, nullptr, plan);
+}
+extern "C" int dk_conv3x3_plan_f16(const dk_conv_desc* d, dk_gemm_plan_t* plan) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_conv3x3_plan(d, plan);
+}
+
+// Workspace of the attention launches of this host thread.  attention5.hip splits the query blocks of a launch's last, partial round of the
+// CUs along the keys (FLUX, one image: 408 blocks on 256 CUs -- 152 blocks in three key ranges each fill the second round to two thirds
+// of a block's time); the partial results (bf16 O / l, offset, l per row) go through this buffer.  Without one (or with one too small for a
+// launch) the blocks are not split: same results up to the rounding of the partials, a longer last round.
+extern "C" size_t dk_attention_workspace_bytes(void) { return (size_t)1020 * (65536 + 2048); }  // <= 255 blocks x 4 key ranges
+extern "C" int dk_attention_set_workspace(void* workspace, size_t bytes) {
+  DK_REQUIRE(workspace == nullptr || ((uintptr_t)workspace & 255) == 0, "attention workspace: 256-byte aligned (or NULL)");
+  dk_set_attention_workspace(workspace, bytes);
+  return 0;
+}
+
+extern "C" int dk_attention_bf16(const void* q, const void* k, const void* v, void* out, int32_t B, int32_t H, int32_t S,
+                                 int32_t D, int32_t ld, int32_t ldo, float scale, void* stream) {
+  AttnParams p;
+  p.Q = (const bf16_t*)q; p.K = (const bf16_t*)k; p.V = (const bf16_t*)v; p.O = (bf16_t*)out;
+  p.B = B; p.H = H; p.S = S; p.D = D; p.ld = ld; p.ldo = ldo; p.scale = scale;
+  return dk_launch_attention(p, S_(stream));
+}
+
+extern "C" int dk_attention_bias_bf16(const void* q, const void* k, const void* v, void* out, int32_t B, int32_t H, int32_t S, int32_t D,
+                                      int32_t ld, int32_t ldo, float scale, const void* bias, int64_t bias_head_stride, int32_t ldb,
+                                      void* stream) {
+  DK_REQUIRE(bias != nullptr, "bias missing (use dk_attention_bf16 without one)");
+  AttnParams p;
+  p.Q = (const bf16_t*)q; p.K = (const bf16_t*)k; p.V = (const bf16_t*)v; p.O = (bf16_t*)out;
+  p.B = B; p.H = H; p.S = S; p.D = D; p.ld = ld; p.ldo = ldo; p.scale = scale;
+  p.bias = (const bf16_t*)bias; p.bias_head_stride = (long)bias_head_stride; p.ldb = ldb;
+  return dk_launch_attention(p, S_(stream));
+}
+extern "C" int dk_attention_desc_bf16(const dk_attention_desc* d, void* stream) {
+  DK_REQUIRE(d != nullptr, "null descriptor");
+  AttnParams p;
+  p.Q = (const bf16_t*)d->q; p.K = (const bf16_t*)d->k; p.V = (const bf16_t*)d->v; p.O = (bf16_t*)d->out;
+  p.B = d->B; p.H = d->H; p.S = d->S; p.D = d->D; p.ld = d->ld; p.ldo = d->ldo; p.scale = d->scale;
+  p.bias = (const bf16_t*)d->bias; p.bias_head_stride = (long)d->bias_head_stride; p.ldb = d->ldb;
+  p.qn_a = (const bf16_t*)d->qn_a; p.qn_b = (const bf16_t*)d->qn_b; p.qn_split = d->qn_split; p.qn_eps = d->qn_eps; p.q_rope = d->q_rope;
+  p.dtype = g_elem_dtype;
+  if (d->O8 != nullptr) {
+    DK_REQUIRE(d->O8_scales != nullptr && d->o8_rows >= (int64_t)d->B * d->S && d->o8_ld >= d->H * d->D && d->o8_ld % 32 == 0,
+               "MX-fp8 output copy: scales, B * S rows inside the buffer, a row pitch of at least H * D bytes (multiple of 32)");
+    p.O8 = (unsigned char*)d->O8; p.O8_scales = (unsigned char*)d->O8_scales; p.o8_ld = d->o8_ld; p.o8_nblk = mx_nblk((long)d->o8_rows);
+  }
+  return dk_launch_attention(p, S_(stream));
+}
+extern "C" int dk_attention_desc_f16(const dk_attention_desc* d, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_attention_desc_bf16(d, stream);
+}
+extern "C" int32_t dk_attention_d512_tp(int32_t T) { return (int32_t)align_up((size_t)(T > 0 ? T : 0), 64); }
+int attention_d512(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int B, int T, int ld, int ldo, float scale, bf16_t* vt,
+                   hipStream_t st) {  // (dk_engine.h)
+  DK_REQUIRE(ld == 512, "attention_d512: q / k / v rows of exactly 512 columns (the transpose reads dense [T, 512] matrices)");
+  const int Tp = dk_attention_d512_tp(T);
+  for (int b = 0; b < B; ++b) {
+    const int rc = DK_EL(dk_launch_transpose)(v + (size_t)b * T * ld, vt + (size_t)b * 512 * Tp, T, 512, st, Tp);
+    if (rc) return rc;
+  }
+  Attn512Params a;
+  a.Q = q; a.K = k; a.Vt = vt; a.O = out; a.T = T; a.Tp = Tp; a.B = B; a.ld = ld; a.ldo = ldo; a.scale = scale; a.dtype = g_elem_dtype;
+  return dk_launch_attention512(a, st);
+}
+extern "C" int dk_attention_d512_bf16(const void* q, const void* k, const void* v, void* out, int32_t B, int32_t T, int32_t ld, int32_t ldo,
+                                      float scale, void* vt_scratch, void* stream) {
+  DK_REQUIRE(q && k && v && out && vt_scratch && B > 0 && T > 0, "null / empty argument");
+  return attention_d512((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)out, B, T, ld, ldo, scale, (bf16_t*)vt_scratch,
+                        S_(stream));
+}
+extern "C" int dk_attention_d512_f16(const void* q, const void* k, const void* v, void* out, int32_t B, int32_t T, int32_t ld, int32_t ldo,
+                                     float scale, void* vt_scratch, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_attention_d512_bf16(q, k, v, out, B, T, ld, ldo, scale, vt_scratch, stream);
+}
+extern "C" int dk_embedding_bf16(const void* table, const int32_t* ids, const void* pos, int32_t pos_rows, void* out_bf16, float* out_f32,
+                                 int32_t n, int32_t dim, int32_t vocab, void* stream) {
+  DK_REQUIRE(table && ids && (out_bf16 || out_f32), "null argument");
+  return dk_launch_embedding((const bf16_t*)table, ids, (const bf16_t*)pos, pos_rows, (bf16_t*)out_bf16, out_f32, n, dim, vocab, S_(stream));
+}
+extern "C" int dk_layernorm_bf16(const void* x, void* out, int32_t M, int32_t h, const void* weight, const void* bias, float eps,
+                                 void* stream) {
+  DK_REQUIRE(x && out && weight && M > 0 && h > 0, "bad argument");
+  return dk_launch_layernorm((const bf16_t*)x, (bf16_t*)out, M, h, (const bf16_t*)weight, (const bf16_t*)bias, eps, S_(stream));
+}
+extern "C" int dk_t5_rmsnorm_bf16(const float* x, void* out, int32_t M, int32_t h, const void* weight, float eps, void* stream) {
+  DK_REQUIRE(x && out && weight && M > 0 && h > 0, "bad argument");
+  return dk_launch_t5_rmsnorm(x, (bf16_t*)out, M, h, (const bf16_t*)weight, eps, S_(stream));
+}
+extern "C" int dk_text_elementwise(const void* a, const void* b, void* y, float* r, int64_t n, int32_t op, void* stream) {
+  DK_REQUIRE(a && n > 0 && op >= 0 && op <= 2 && (op == 2 ? r != nullptr : y != nullptr) && (op != 1 || b != nullptr), "bad argument");
+  return dk_launch_text_elementwise((const bf16_t*)a, (const bf16_t*)b, (bf16_t*)y, r, (long)n, op, S_(stream));
+}
+extern "C" int dk_t5_bias_bf16(const void* emb, const int32_t* rel_bucket, int32_t H, int32_t S, int32_t ld, void* out, void* stream) {
+  DK_REQUIRE(emb && rel_bucket && out && H > 0 && S > 0 && ld >= S && ld % 64 == 0, "bad argument");
+  return dk_launch_t5_bias((const bf16_t*)emb, rel_bucket, H, S, ld, (bf16_t*)out, S_(stream));
+}
+
+extern "C" int dk_ln_modulate_bf16(const void* x, int32_t ldx, void* out, int32_t ldo, int32_t M, int32_t h, const void* shift,
+                                   const void* scale, int32_t mod_stride, int32_t mod_seg_len, int32_t x_seg_len,
+                                   int32_t x_seg_stride, float eps, void* stream) {
+  return DK_EL(dk_launch_ln_modulate)((const bf16_t*)x, ldx, (bf16_t*)out, ldo, M, h, (const bf16_t*)shift, (const bf16_t*)scale,
+                                      mod_stride, mod_seg_len > 0 ? mod_seg_len : M, x_seg_len > 0 ? x_seg_len : M, x_seg_stride,
+                                      eps, S_(stream));
+}
+extern "C" int dk_ln_modulate_f16(const void* x, int32_t ldx, void* out, int32_t ldo, int32_t M, int32_t h, const void* shift,
+                                  const void* scale, int32_t mod_stride, int32_t mod_seg_len, int32_t x_seg_len,
+                                  int32_t x_seg_stride, float eps, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_ln_modulate_bf16(x, ldx, out, ldo, M, h, shift, scale, mod_stride, mod_seg_len, x_seg_len, x_seg_stride, eps, stream);
+}
+
+// mx8_out: the descriptor's C_scales / c_rows / c_row0 / c_col0 describe an MX-fp8 output (its own, or the second one of a column split)
+static int gemm_f8_params_from_desc(const dk_gemm_fp8_desc* d, bool mx8_out, GemmF8Params& p) {
+  memset(&p, 0, sizeof(p));
+  p.A = (const unsigned char*)d->A; p.SA = (const unsigned char*)d->A_scales; p.W = (const unsigned char*)d->W; p.wscale = d->w_scale;
+  p.C = d->C; p.bias = (const bf16_t*)d->bias; p.gate = (const bf16_t*)d->gate; p.res = (const bf16_t*)d->res;
+  p.M = d->M; p.N = d->N; p.K = d->K; p.lda = d->lda; p.ldw = d->ldw; p.ldc = d->ldc; p.ldr = d->ldr;
+  p.a_seg_len = d->a_seg_len > 0 ? d->a_seg_len : (d->M + 127) / 128 * 128; p.a_seg_stride = d->a_seg_stride; p.a_row0 = d->a_row0;
+  p.sa_nblk = mx_nblk(d->a_rows);
+  p.c_seg_len = d->c_seg_len > 0 ? d->c_seg_len : d->M; p.c_seg_stride = d->c_seg_stride;
+  p.r_seg_len = d->r_seg_len > 0 ? d->r_seg_len : d->M; p.r_seg_stride = d->r_seg_stride;
+  p.gate_seg_len = d->gate_seg_len > 0 ? d->gate_seg_len : d->M; p.gate_stride = d->gate_stride;
+  p.epi = d->epilogue; p.c_mx8 = d->c_mx8;
+  if (mx8_out) {
+    DK_REQUIRE(d->c_col0 % 32 == 0 && d->C_scales != nullptr, "MX-fp8 output: scales, column offset a multiple of 32");
+    p.SC = (unsigned char*)d->C_scales; p.sc_nblk = mx_nblk(d->c_rows); p.c_row0 = d->c_row0; p.sc_kb0 = d->c_col0 / 32;
+  }
+  p.workspace = d->workspace; p.workspace_bytes = d->workspace_bytes;
+  return 0;
+}
+
+extern "C" int dk_gemm_fp8(const dk_gemm_fp8_desc* d, void* stream) {
+  DK_REQUIRE(d != nullptr, "null descriptor");
+  GemmF8Params p;
+  if (const int rc = gemm_f8_params_from_desc(d, d->c_mx8 != 0, p)) return rc;
+  return dk_launch_gemm256f8(p, nullptr, S_(stream));
+}
+
+extern "C" int dk_gemm_fp8_fused(const dk_gemm_fp8_desc* d, const dk_gemm_fp8_side* f, const dk_gemm_fp8_desc* d2, const dk_gemm_fp8_side* f2,
+                                 void* stream) {
+  DK_REQUIRE(d != nullptr && (d2 != nullptr || f2 == nullptr), "null descriptor");
+  GemmF8Params p, p2;
+  if (const int rc = gemm_f8_params_from_desc(d, d->c_mx8 != 0 || (f != nullptr && f->c2_mx8 != 0), p)) return rc;
+  set_fused(p, f);
+  if (f != nullptr) p.c2_mx8 = f->c2_mx8;
+  if (d2 == nullptr) return dk_launch_gemm256f8(p, nullptr, S_(stream));
+  if (const int rc = gemm_f8_params_from_desc(d2, d2->c_mx8 != 0 || (f2 != nullptr && f2->c2_mx8 != 0), p2)) return rc;
+  set_fused(p2, f2);
+  if (f2 != nullptr) p2.c2_mx8 = f2->c2_mx8;
+  return dk_launch_gemm256f8(p, &p2, S_(stream));
+}
+extern "C" int dk_quantize_mx8(const void* x, int32_t ldx, int32_t M, int32_t h, void* out, int32_t ldo, void* out_scales, int64_t out_rows,
+                               int32_t out_row0, int32_t out_col0, void* stream) {
+  DK_REQUIRE(x && out && out_scales && M > 0, "bad argument");
+  DK_REQUIRE(out_row0 >= 0 && (int64_t)out_row0 + M <= out_rows, "rows [out_row0, out_row0 + M) must lie inside the [out_rows, ldo] output");
+  DK_REQUIRE(out_col0 >= 0 && ldo >= out_col0 + h, "columns [out_col0, out_col0 + h) must lie inside a row of ldo bytes");
+  return dk_launch_quantize_mx8((const bf16_t*)x, ldx, M, 0, M, h, mx8_out(out, out_scales, ldo, (long)out_rows, out_row0, M, 0, out_col0), S_(stream));
+}
+extern "C" int dk_ln_modulate_mx8(const void* x, int32_t ldx, int32_t M, int32_t h, const void* shift, const void* scale, int32_t mod_stride,
+                                  int32_t mod_seg_len, float eps, void* out, int32_t ldo, void* out_scales, int64_t out_rows,
+                                  int32_t out_row0, void* stream) {
+  DK_REQUIRE(x && out && out_scales && M > 0, "bad argument");
+  DK_REQUIRE(out_row0 >= 0 && (int64_t)out_row0 + M <= out_rows, "rows [out_row0, out_row0 + M) must lie inside the [out_rows, ldo] output");
+  DK_REQUIRE(ldo >= h, "a row of the output holds h bytes");
+  return dk_launch_ln_modulate_mx8((const bf16_t*)x, ldx, M, h, (const bf16_t*)shift, (const bf16_t*)scale, mod_stride,
+                                   mod_seg_len > 0 ? mod_seg_len : M, M, 0, eps, mx8_out(out, out_scales, ldo, (long)out_rows, out_row0, M, 0, 0),
+                                   S_(stream));
+}
+
+extern "C" int dk_qk_norm_rope_bf16(void* qkv, int32_t ld, int32_t q_off, int32_t k_off, int32_t rows, int32_t H, int32_t D,
+                                    const void* q_weight, const void* k_weight, float eps, const float* rope_table,
+                                    int32_t row_seg_len, int32_t row_seg_stride, int32_t pos_off, void* stream) {
+  return DK_EL(dk_launch_qk_norm_rope)((bf16_t*)qkv, ld, q_off, k_off, rows, H, D, (const bf16_t*)q_weight, (const bf16_t*)k_weight,
+                                       eps, rope_table, row_seg_len > 0 ? row_seg_len : rows, row_seg_stride, pos_off, 0, S_(stream), 0);
+}
+extern "C" int dk_qk_norm_rope_f16(void* qkv, int32_t ld, int32_t q_off, int32_t k_off, int32_t rows, int32_t H, int32_t D,
+                                   const void* q_weight, const void* k_weight, float eps, const float* rope_table,
+                                   int32_t row_seg_len, int32_t row_seg_stride, int32_t pos_off, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_qk_norm_rope_bf16(qkv, ld, q_off, k_off, rows, H, D, q_weight, k_weight, eps, rope_table, row_seg_len, row_seg_stride, pos_off, stream);
+}
+
+extern "C" int dk_rope_table_f32(float* table, int32_t S_txt, int32_t gh, int32_t gw, const int32_t* axes_dim, int32_t n_axes,
+                                 float theta, void* stream) {
+  return dk_launch_rope_table(table, S_txt, gh, gw, axes_dim, n_axes, theta, S_(stream));
+}
+
+extern "C" int dk_timestep_embedding_bf16(const float* t_dev, int32_t n, int32_t dim, float max_period, int32_t embed_dtype,
+                                          void* out, void* stream) {
+  return DK_EL(dk_launch_timestep_embedding)(t_dev, n, 1, dim, max_period, embed_dtype, (bf16_t*)out, S_(stream));
+}
+extern "C" int dk_timestep_embedding_f16(const float* t_dev, int32_t n, int32_t dim, float max_period, int32_t embed_dtype,
+                                         void* out, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_timestep_embedding_bf16(t_dev, n, dim, max_period, embed_dtype, out, stream);
+}
+
+extern "C" int dk_latent_to_tokens(const float* x, void* tokens, int32_t n_img, int32_t dup, int32_t Hl, int32_t Wl, int32_t C,
+                                   int32_t p, int32_t reshape_order, void* stream) {
+  DK_REQUIRE(Hl % p == 0 && Wl % p == 0, "latent size must be divisible by the patch size");
+  return DK_EL(dk_launch_latent_to_tokens)(x, (bf16_t*)tokens, n_img, dup, Hl, Wl, C, p, reshape_order, S_(stream));
+}
+extern "C" int dk_latent_to_tokens_f16(const float* x, void* tokens, int32_t n_img, int32_t dup, int32_t Hl, int32_t Wl, int32_t C,
+                                       int32_t p, int32_t reshape_order, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_latent_to_tokens(x, tokens, n_img, dup, Hl, Wl, C, p, reshape_order, stream);
+}
+
+extern "C" int dk_euler_cfg_step(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on,
+                                 int32_t Hl, int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma,
+                                 float sigma_next, float cfg_weight, void* stream) {
+  DK_REQUIRE(sigma != 0.0f, "sigma must be non-zero");
+  return DK_EL(dk_launch_euler_step)(x, (const bf16_t*)model_out, ld_out, (bf16_t*)tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order,
+                                     sigma, sigma_next, cfg_weight, S_(stream));
+}
+extern "C" int dk_euler_cfg_step_f16(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on,
+                                     int32_t Hl, int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma,
+                                     float sigma_next, float cfg_weight, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_euler_cfg_step(x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight, stream);
+}
+
+extern "C" int dk_affine_f32(const float* x, float* y, int64_t n, float a, float b, void* stream) {
+  return dk_launch_affine_f32(x, y, (long)n, a, b, S_(stream));
+}
+
+static int gn_nchunk(long HW, int C) {
+  const long ppi = 256 / (C / 8);
+  long n = HW / (ppi * 8);
+  if (n < 1) n = 1;
+  if (n > 1024) n = 1024;
+  return (int)n;
+}
+extern "C" size_t dk_groupnorm_scratch_floats(int32_t B, int32_t G) { return (size_t)B * 1024 * 2 * G + (size_t)B * G * 2; }
+extern "C" int dk_groupnorm_bf16(const void* x, void* y, int32_t B, int64_t HW, int32_t C, int32_t G, const void* gamma,
+                                 const void* beta, float eps, int32_t fuse_silu, float* scratch, void* stream) {
+  const int nchunk = gn_nchunk((long)HW, C);
+  float* mean_rstd = scratch + (size_t)B * 1024 * 2 * G;
+  int rc = DK_EL(dk_launch_groupnorm_stats)((const bf16_t*)x, B, (long)HW, C, G, scratch, nchunk, mean_rstd, eps, S_(stream));
+  if (rc) return rc;
+  return DK_EL(dk_launch_groupnorm_apply)((const bf16_t*)x, (bf16_t*)y, B, (long)HW, C, G, mean_rstd, (const bf16_t*)gamma,
+                                          (const bf16_t*)beta, fuse_silu, S_(stream));
+}
+extern "C" int dk_groupnorm_f16(const void* x, void* y, int32_t B, int64_t HW, int32_t C, int32_t G, const void* gamma,
+                                const void* beta, float eps, int32_t fuse_silu, float* scratch, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_groupnorm_bf16(x, y, B, HW, C, G, gamma, beta, eps, fuse_silu, scratch, stream);
+}
+
+// scratch layout shared by dk_groupnorm_bf16 / dk_groupnorm_table_bf16: [partials: B * n * 2G][mean_rstd: B * G * 2], n = the
+// larger of 1024 and the caller's n_partial
+extern "C" int dk_groupnorm_table_bf16(const void* x, int32_t B, int64_t HW, int32_t C, int32_t G, const void* gamma, const void* beta,
+                                       float eps, float* scratch, int32_t n_partial, float* scale_shift, void* stream) {
+  DK_REQUIRE(gamma && beta && scratch && scale_shift && B > 0 && G > 0 && C % G == 0, "groupnorm table arguments");
+  DK_REQUIRE(x != nullptr || n_partial > 0, "either x or the number of partials a conv launch left in scratch");
+  const int nchunk = x ? gn_nchunk((long)HW, C) : n_partial;
+  float* mean_rstd = scratch + (size_t)B * (nchunk > 1024 ? nchunk : 1024) * 2 * G;
+  if (x) {  // the partial sums only: the one finalisation below builds mean / rstd AND the table
+    const int rc = DK_EL(dk_launch_groupnorm_partials)((const bf16_t*)x, B, (long)HW, C, G, scratch, nchunk, S_(stream));
+    if (rc) return rc;
+  }
+  return DK_EL(dk_launch_groupnorm_finalize)(scratch, nchunk, B, G, (double)HW * (double)(C / G), eps, mean_rstd, (const bf16_t*)gamma,
+                                             (const bf16_t*)beta, C, scale_shift, S_(stream));
+}
+extern "C" int dk_groupnorm_table_f16(const void* x, int32_t B, int64_t HW, int32_t C, int32_t G, const void* gamma, const void* beta,
+                                      float eps, float* scratch, int32_t n_partial, float* scale_shift, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_groupnorm_table_bf16(x, B, HW, C, G, gamma, beta, eps, scratch, n_partial, scale_shift, stream);
+}
+
+static ConvHaloParams conv_halo_params(const dk_conv_gn_desc* d) {
+  ConvHaloParams p;
+  memset(&p, 0, sizeof(p));
+  p.dtype = g_elem_dtype;
+  p.x = (const bf16_t*)d->x; p.w = (const bf16_t*)d->w; p.bias = (const bf16_t*)d->bias; p.bias2 = (const bf16_t*)d->bias2;
+  p.res = (const bf16_t*)d->res; p.y = (bf16_t*)d->y; p.gn_ss = d->gn_scale_shift; p.gn_silu = d->gn_silu;
+  p.x2 = (const bf16_t*)d->x2; p.C2 = d->C2; p.stats_out = d->stats_partial; p.G_out = d->stats_groups;
+  p.img = d->image_f32; p.u8 = d->image_u8; p.raw = (bf16_t*)d->raw_bf16; p.out_channels = d->O <= 4 ? d->O : 0;
+  p.B = d->B; p.H = d->H; p.W = d->W; p.C = d->C; p.O = d->O; p.ups = d->upsample; p.ldw = d->ldw; p.ldy = d->ldy; p.ldr = d->ldr;
+  return p;
+}
+extern "C" int dk_conv3x3_gn_bf16(const dk_conv_gn_desc* d, void* stream) {
+  DK_REQUIRE(d && d->x && d->w && d->bias, "null argument");
+  const bool img = d->image_f32 || d->image_u8 || d->raw_bf16;
+  DK_REQUIRE(img || d->y, "no output");
+  return dk_launch_conv_halo(conv_halo_params(d), S_(stream));
+}
+extern "C" int dk_conv3x3_gn_f16(const dk_conv_gn_desc* d, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_conv3x3_gn_bf16(d, stream);
+}
+
+extern "C" int dk_softmax_rows_bf16(void* x, int32_t rows, int32_t cols, int32_t ld, void* stream) {
+  return DK_EL(dk_launch_softmax_rows)((bf16_t*)x, rows, cols, ld, S_(stream));
+}
+extern "C" int dk_softmax_rows_f16(void* x, int32_t rows, int32_t cols, int32_t ld, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_softmax_rows_bf16(x, rows, cols, ld, stream);
+}
+extern "C" int dk_transpose_bf16(const void* x, void* y, int32_t R, int32_t C, void* stream) {
+  return DK_EL(dk_launch_transpose)((const bf16_t*)x, (bf16_t*)y, R, C, S_(stream), 0);
+}
+extern "C" int dk_transpose_f16(const void* x, void* y, int32_t R, int32_t C, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_transpose_bf16(x, y, R, C, stream);
+}

@@ -16,8 +16,8 @@
 // of the lean kernel, which is bound by VALU issue, profiles/r04_sd3_pmc.md).
 #include "dk_kernels.h"
 
-extern int g_dk_attn_mode;  // engine.hip; dk_tune_set("attn", v): -1 automatic; 4 = dk_attn2 (4 waves); 9 = dk_attn4 (8 waves, D = 128 only);
-                            // 10 = dk_attn5 (one wave per SIMD, asm tile loop; D = 128, S % 256 == 0: other shapes fall back to 9)
+int g_dk_attn_mode = -1;  // dk_tune_set("attn", v): -1 (default) automatic; 4 = dk_attn2 (4 waves); 9 = dk_attn4 (8 waves, D = 128 only);
+                          // 10 = dk_attn5 (one wave per SIMD, asm tile loop; D = 128, S % 256 == 0: other shapes fall back to 9)
 
 // workspace of the launches this host thread enqueues (dk_attention_set_workspace): the partial results of attention5.hip's key-split
 // workgroups; lab: the trace buffer of attention4.hip's DK4_TRACE builds (scripts/attn_trace.py)

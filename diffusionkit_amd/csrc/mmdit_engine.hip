@@ -1,0 +1,734 @@
+// C-ABI layer (include/dk_hip.h), part 2: the MMDiT engine (dk_mmdit_*), which sequences the gfx950 kernels of the transformer blocks.
+// Host code only: no kernels are defined here.
+#include <cmath>
+#include <type_traits>
+#include <vector>
+
+#include "dk_engine.h"
+
+int g_dk_fuse_k = 1;  // dk_tune_set("gemm_fuse_k", v): QKNorm + RoPE of the keys inside the q / k / v projection's tail (1, default) or as a separate pass (0)
+int g_dk_fuse_qg = -1;  // dk_tune_set("gemm_fuse_q", v): ... and of the QUERIES there too (1) instead of in the attention kernel's Q load (0); -1 (default): on
+                         // the fp8 path only -- measured in the model (profiles/r04_attention_qfuse_in_model.log): +1.0 % per step with fp8 weights, flat in bf16
+int g_dk_fuse_q = 1;  // dk_tune_set("attn_fuse_q", v): QKNorm + RoPE of the queries inside the attention kernel's Q load (1, default) or as a separate pass (0)
+
+// every attention kernel can normalise / rotate the queries in its Q load
+static int fuse_q() { return g_dk_fuse_q ? 1 : 0; }
+// the keys' QKNorm + RoPE rides in the q / k / v projection's tail (only together with the fused query side: the stand-alone pass
+// then has nothing left to do)
+static bool fuse_k(const bf16_t* kn) { return g_dk_fuse_k != 0 && fuse_q() && kn != nullptr; }
+// ... and the queries' with it (round 4): the attention kernel then loads finished queries
+static bool fuse_qg(const bf16_t* qn, bool f8) { return (g_dk_fuse_qg < 0 ? f8 : g_dk_fuse_qg != 0) && qn != nullptr; }
+template <typename P>
+static void set_key_norm(P& p, const bf16_t* kn, const bf16_t* qn, int h, int D, const float* rope, int pos_off, int seg_len) {
+  p.kn_w = kn; p.kn_rope = rope; p.kn_col0 = h; p.kn_col1 = 2 * h; p.kn_D = D; p.kn_pos_off = pos_off; p.kn_seg_len = seg_len; p.kn_eps = 1e-6f;
+  if (fuse_qg(qn, std::is_same<P, GemmF8Params>::value)) { p.qn_w = qn; p.qn_col0 = 0; p.qn_col1 = h; }
+}
+struct StreamW {  // one TransformerBlock's weights (mmdit.py:395-438)
+  const bf16_t *qkv_w = nullptr, *qkv_b = nullptr, *qn = nullptr, *kn = nullptr;
+  const bf16_t *o_w = nullptr, *o_b = nullptr, *fc1_w = nullptr, *fc1_b = nullptr, *fc2_w = nullptr, *fc2_b = nullptr;
+  const bf16_t *l2_w = nullptr, *l2_b = nullptr;  // single blocks: [h, 5h] = [o_proj | fc2]
+  // fp8_linears: e4m3 weights + per-output-channel scales instead of the bf16 matrices above (biases stay bf16)
+  const unsigned char *qkv_w8 = nullptr, *o_w8 = nullptr, *fc1_w8 = nullptr, *fc2_w8 = nullptr, *l2_w8 = nullptr;
+  const float *qkv_ws = nullptr, *o_ws = nullptr, *fc1_ws = nullptr, *fc2_ws = nullptr, *l2_ws = nullptr;
+};
+
+struct dk_mmdit {
+  dk_mmdit_config cfg;
+  std::unordered_map<std::string, const void*> named;
+  bool resolved = false;
+  // resolved weights
+  const bf16_t *xemb_w, *xemb_b, *pos_w, *ctx_w, *ctx_b, *y0_w, *y0_b, *y2_w, *y2_b, *t0_w, *t0_b, *t2_w, *t2_b;
+  const bf16_t *adaln_w, *adaln_b, *final_w, *final_b;
+  std::vector<StreamW> dimg, dtxt, single;
+  // shape
+  int B = 0, Hl = 0, Wl = 0, S_t = 0, S_i = 0, S = 0, n_t = 0;
+  bool prepared = false, mod_ready = false;
+  // workspace views
+  bf16_t *X, *XN, *QKV, *ATT, *CAT, *HID, *MOD, *POS;
+  bf16_t* CTXE = nullptr;  // context_embedder(text) [B, S_t, h], step-invariant (dk_mmdit_cache_context)
+  bool ctx_ready = false;
+  int ldh = 0, ldcat = 0;  // row pitch of HID / CAT (dk_weight_pitch of r*h / (1+r)*h at carve time; fc2 / linear2 weights use the same)
+  void* GWS = nullptr;  // GEMM split workspace (fp32 slabs + flags), dk_gemm_split_workspace_bytes()
+  void* AWS = nullptr;  // attention5.hip's key-split partial results of THIS engine's launches (dk_attention_workspace_bytes(); D = 128 only)
+  size_t AWS_bytes = 0;
+  bf16_t *temb, *t1, *tvec, *y1, *yvec, *vec;
+  float *rope, *tdev;
+  // guidance embedding (cfg.guidance_embed): MLPEmbedder weights, the value set by dk_mmdit_set_guidance, scratch rows
+  const bf16_t *g0_w = nullptr, *g0_b = nullptr, *g2_w = nullptr, *g2_b = nullptr;
+  float guidance = 3.5f;
+  bf16_t *gemb = nullptr, *g1 = nullptr, *gvec = nullptr;
+  // fp8_linears: MX-fp8 activation buffers + their scale side arrays (layout dk_mx_scale_index)
+  unsigned char *XN8 = nullptr, *ATT8 = nullptr, *HC8 = nullptr;    // [rows8, h], [rows8, h], max([rows8, ldh8], [rows8, ldcat8])
+  unsigned char *SXN = nullptr, *SATT = nullptr, *SHID = nullptr, *SCAT = nullptr;
+  int ldh8 = 0, ldcat8 = 0, nblk = 0;
+  // row order of the double blocks' fp8 buffers: image rows of all batch rows [0, B * S_i), text rows from txt0_8 =
+  // ceil128(B * S_i) -- every row range an fp8 GEMM reads starts on a 128-row scale block; rows8 = txt0_8 + B * S_t >= B * S
+  int txt0_8 = 0;
+  long rows8 = 0;
+  // element type of every bound tensor, activation buffer and of the token / text / pooled I/O (dk_mmdit_set_activation_dtype): sizes are the same
+  int dtype = DK_DTYPE_BF16;
+  bool fp8() const { return cfg.fp8_linears != 0; }
+  // precision policy: the first n_bf16() double-stream blocks keep bf16 Linears under fp8_linears (global block index = double-block index)
+  int n_bf16() const { return fp8() ? (cfg.fp8_bf16_double_blocks < cfg.depth_multimodal ? cfg.fp8_bf16_double_blocks : cfg.depth_multimodal) : 0; }
+
+  // row views of the joint-stream buffers [B, S, ld] (X, QKV, ATT; text rows first in every batch row): the image / the text rows of all batch
+  // rows.  XN, HID and CAT hold plain [M, ld] rows: dense(ptr, ld)
+  Rows img(bf16_t* buf, int ld) const { return Rows{buf + (size_t)S_t * ld, ld, S_i, S}; }
+  Rows txt(bf16_t* buf, int ld) const { return Rows{buf, ld, S_t, S}; }
+
+  int h() const { return cfg.hidden_size; }
+  int D() const { return cfg.hidden_size / cfg.num_heads; }
+  int F() const { return cfg.patch_size * cfg.patch_size * cfg.vae_latent_dim; }
+  bool txt_skipped(int i) const { return i == cfg.depth_multimodal - 1 && cfg.depth_unified < 1; }
+  int mod_rows() const {
+    int n = 0;
+    for (int i = 0; i < cfg.depth_multimodal; ++i) n += 6 + (txt_skipped(i) ? 2 : 6);
+    return n + 3 * cfg.depth_unified + 2;
+  }
+  int mod_offset(int kind, int index) const {
+    int n = 0;
+    for (int i = 0; i < cfg.depth_multimodal; ++i) {
+      if (kind == 0 && i == index) return n;
+      n += 6;
+      if (kind == 1 && i == index) return n;
+      n += txt_skipped(i) ? 2 : 6;
+    }
+    for (int i = 0; i < cfg.depth_unified; ++i) {
+      if (kind == 2 && i == index) return n;
+      n += 3;
+    }
+    if (kind == 3) return n;
+    return -1;
+  }
+};
+
+extern "C" int dk_mmdit_create(const dk_mmdit_config* cfg, dk_mmdit** out) {
+  DK_REQUIRE(cfg && out, "null argument");
+  DK_REQUIRE(cfg->hidden_size % cfg->num_heads == 0, "hidden_size must be divisible by num_heads");
+  const int D = cfg->hidden_size / cfg->num_heads;
+  DK_REQUIRE(D == 64 || D == 128, "head_dim must be 64 or 128");
+  DK_REQUIRE(cfg->hidden_size % 64 == 0, "hidden_size must be a multiple of 64");
+  DK_REQUIRE((cfg->patch_size * cfg->patch_size * cfg->vae_latent_dim) % 64 == 0, "patch feature size must be a multiple of 64");
+  DK_REQUIRE(cfg->token_level_text_embed_dim % 64 == 0 && cfg->pooled_text_embed_dim % 64 == 0 &&
+                 cfg->frequency_embed_dim % 64 == 0,
+             "embedding dims must be multiples of 64");
+  if (cfg->use_rope) {
+    int half = 0;
+    for (int i = 0; i < cfg->n_rope_axes; ++i) half += cfg->rope_axes_dim[i] / 2;
+    DK_REQUIRE(half * 2 == D, "rope axes must sum to head_dim");
+  }
+  if (cfg->fp8_linears) DK_REQUIRE(D == 128 && cfg->hidden_size % 256 == 0, "fp8_linears: head_dim 128 and hidden_size a multiple of 256");
+  dk_mmdit* m = new dk_mmdit();
+  m->cfg = *cfg;
+  *out = m;
+  return 0;
+}
+extern "C" int dk_mmdit_set_guidance(dk_mmdit* m, float guidance) {
+  DK_REQUIRE(m != nullptr, "null handle");
+  DK_REQUIRE(m->cfg.guidance_embed, "this configuration has no guidance embedding (guidance_embed = 0)");
+  m->guidance = guidance;
+  m->mod_ready = false;
+  return 0;
+}
+extern "C" int dk_mmdit_set_activation_dtype(dk_mmdit* m, int32_t dtype) {
+  DK_REQUIRE(m != nullptr, "null handle");
+  DK_REQUIRE(dtype == DK_DTYPE_BF16 || dtype == DK_DTYPE_F16, "activation dtype: 0 bf16, 1 fp16");
+  DK_REQUIRE(m->named.empty() && !m->prepared, "dk_mmdit_set_activation_dtype must precede the first dk_mmdit_bind");
+  if (dtype == DK_DTYPE_F16)
+    DK_REQUIRE(m->D() == 64 && m->cfg.depth_unified == 0 && m->cfg.fp8_linears == 0,
+               "fp16 activations are the SD3 family's: head_dim == 64, depth_unified == 0, fp8_linears == 0");
+  m->dtype = dtype;
+  return 0;
+}
+extern "C" void dk_mmdit_destroy(dk_mmdit* m) { delete m; }
+
+extern "C" int dk_mmdit_bind(dk_mmdit* m, const char* name, const void* dev_ptr) {
+  DK_REQUIRE(m && name && dev_ptr, "null argument");
+  m->named[name] = dev_ptr;
+  m->resolved = false;
+  return 0;
+}
+extern "C" int dk_mmdit_mod_rows(const dk_mmdit* m) { return m->mod_rows(); }
+extern "C" int dk_mmdit_mod_offset(const dk_mmdit* m, int32_t kind, int32_t index) { return m->mod_offset(kind, index); }
+
+// the matrix of one Linear: bf16 "<name>.weight", or (fp8_linears) e4m3 "<name>.weight_fp8" + f32 "<name>.wscale"
+static int need_matrix(dk_mmdit* m, bool f8, const std::string& name, const bf16_t** w, const unsigned char** w8, const float** ws) {
+  if (!f8) return need(m->named, name + ".weight", w);
+  const bf16_t *a = nullptr, *b = nullptr;
+  DK_TRY(need(m->named, name + ".weight_fp8", &a));
+  DK_TRY(need(m->named, name + ".wscale", &b));
+  *w8 = (const unsigned char*)a;
+  *ws = (const float*)b;
+  return 0;
+}
+static int resolve_stream(dk_mmdit* m, const std::string& p, StreamW& w, bool single, bool skip_post, bool f8) {
+  const auto& n = m->named;
+  if (single) {  // fused [q|k|v|fc1] matrix; fc1 views point into it
+    DK_TRY(need_matrix(m, f8, p + ".linear1", &w.qkv_w, &w.qkv_w8, &w.qkv_ws));
+    DK_TRY(need(n, p + ".linear1.bias", &w.qkv_b));
+    if (!f8) w.fc1_w = w.qkv_w + (size_t)3 * m->h() * m->h();
+    w.fc1_b = w.qkv_b + 3 * m->h();
+  } else {
+    DK_TRY(need_matrix(m, f8, p + ".attn.qkv", &w.qkv_w, &w.qkv_w8, &w.qkv_ws));
+    DK_TRY(need(n, p + ".attn.qkv.bias", &w.qkv_b));
+  }
+  if (m->cfg.use_qk_norm) {
+    DK_TRY(need(n, p + ".qk_norm.q_norm.weight", &w.qn));
+    DK_TRY(need(n, p + ".qk_norm.k_norm.weight", &w.kn));
+  }
+  if (skip_post) return 0;
+  if (!single) {
+    DK_TRY(need_matrix(m, f8, p + ".mlp.fc1", &w.fc1_w, &w.fc1_w8, &w.fc1_ws));
+    DK_TRY(need(n, p + ".mlp.fc1.bias", &w.fc1_b));
+  }
+  if (single) {
+    DK_TRY(need_matrix(m, f8, p + ".linear2", &w.l2_w, &w.l2_w8, &w.l2_ws));
+    DK_TRY(need(n, p + ".linear2.bias", &w.l2_b));
+  } else {
+    DK_TRY(need_matrix(m, f8, p + ".attn.o_proj", &w.o_w, &w.o_w8, &w.o_ws));
+    DK_TRY(need(n, p + ".attn.o_proj.bias", &w.o_b));
+    DK_TRY(need_matrix(m, f8, p + ".mlp.fc2", &w.fc2_w, &w.fc2_w8, &w.fc2_ws));
+    DK_TRY(need(n, p + ".mlp.fc2.bias", &w.fc2_b));
+  }
+  return 0;
+}
+
+static int mmdit_resolve(dk_mmdit* m) {
+  if (m->resolved) return 0;
+  const auto& n = m->named;
+  DK_TRY(need(n, "x_embedder.proj.weight", &m->xemb_w));
+  DK_TRY(need(n, "x_embedder.proj.bias", &m->xemb_b));
+  DK_TRY(need(n, "x_pos_embedder.pos_embed.weight", &m->pos_w, !m->cfg.use_pos_embed));
+  DK_TRY(need(n, "context_embedder.weight", &m->ctx_w));
+  DK_TRY(need(n, "context_embedder.bias", &m->ctx_b));
+  DK_TRY(need(n, "y_embedder.mlp.layers.0.weight", &m->y0_w));
+  DK_TRY(need(n, "y_embedder.mlp.layers.0.bias", &m->y0_b));
+  DK_TRY(need(n, "y_embedder.mlp.layers.2.weight", &m->y2_w));
+  DK_TRY(need(n, "y_embedder.mlp.layers.2.bias", &m->y2_b));
+  DK_TRY(need(n, "t_embedder.mlp.layers.0.weight", &m->t0_w));
+  DK_TRY(need(n, "t_embedder.mlp.layers.0.bias", &m->t0_b));
+  DK_TRY(need(n, "t_embedder.mlp.layers.2.weight", &m->t2_w));
+  DK_TRY(need(n, "t_embedder.mlp.layers.2.bias", &m->t2_b));
+  DK_TRY(need(n, "adaLN.weight", &m->adaln_w));
+  DK_TRY(need(n, "adaLN.bias", &m->adaln_b));
+  DK_TRY(need(n, "final_layer.linear.weight", &m->final_w));
+  DK_TRY(need(n, "final_layer.linear.bias", &m->final_b));
+  if (m->cfg.guidance_embed) {
+    DK_TRY(need(n, "guidance_in.mlp.layers.0.weight", &m->g0_w));
+    DK_TRY(need(n, "guidance_in.mlp.layers.0.bias", &m->g0_b));
+    DK_TRY(need(n, "guidance_in.mlp.layers.2.weight", &m->g2_w));
+    DK_TRY(need(n, "guidance_in.mlp.layers.2.bias", &m->g2_b));
+  }
+  m->dimg.assign(m->cfg.depth_multimodal, StreamW());
+  m->dtxt.assign(m->cfg.depth_multimodal, StreamW());
+  m->single.assign(m->cfg.depth_unified, StreamW());
+  for (int i = 0; i < m->cfg.depth_multimodal; ++i) {
+    const std::string b = "multimodal_transformer_blocks." + std::to_string(i);
+    const bool f8 = m->fp8() && i >= m->n_bf16();
+    DK_TRY(resolve_stream(m, b + ".image_transformer_block", m->dimg[i], false, false, f8));
+    DK_TRY(resolve_stream(m, b + ".text_transformer_block", m->dtxt[i], false, m->txt_skipped(i), f8));
+    // (the fused QKNorm decisions of a double block are taken per stream from these pointers and must agree: ADVICE r4)
+    DK_REQUIRE((m->dimg[i].qn == nullptr) == (m->dtxt[i].qn == nullptr) && (m->dimg[i].kn == nullptr) == (m->dtxt[i].kn == nullptr),
+               "QKNorm weights must be bound for both streams of a double block or for neither");
+  }
+  for (int i = 0; i < m->cfg.depth_unified; ++i)
+    DK_TRY(resolve_stream(m, "unified_transformer_blocks." + std::to_string(i) + ".transformer_block", m->single[i], true, false, m->fp8()));
+  m->resolved = true;
+  return 0;
+}
+
+static size_t mmdit_carve(dk_mmdit* m, Carver& c, int B, int Hl, int Wl, int S_t, int n_t) {
+  const int h = m->h(), p = m->cfg.patch_size;
+  const int S_i = (Hl / p) * (Wl / p), S = S_t + S_i;
+  const size_t BS = (size_t)B * S;
+  m->X = (bf16_t*)c.take(BS * h * 2);
+  m->XN = (bf16_t*)c.take(BS * h * 2);
+  m->QKV = (bf16_t*)c.take(BS * 3 * h * 2);
+  m->ATT = (bf16_t*)c.take(BS * h * 2);
+  m->ldh = dk_weight_pitch(m->cfg.mlp_ratio * h);
+  m->ldcat = dk_weight_pitch((1 + m->cfg.mlp_ratio) * h);
+  const size_t hid = BS * m->ldh * 2;  // MLP hidden of both streams of a double block (image rows first)
+  const size_t cat = m->cfg.depth_unified > 0 ? BS * (size_t)m->ldcat * 2 : 0;
+  // single blocks: [attn | gelu(fc1)]; double blocks: MLP hidden (fp8_linears: only the bf16 double blocks of the precision policy need it)
+  m->CAT = (bf16_t*)c.take(m->fp8() ? (m->n_bf16() > 0 ? hid : 0) : (cat > hid ? cat : hid));
+  m->HID = m->CAT;
+  if (m->fp8()) {  // the same buffers in MX-fp8 (the bf16 X, QKV, ATT above stay: residual stream, attention operands / output)
+    const int r = m->cfg.mlp_ratio;
+    m->ldh8 = dk_weight_pitch_fp8(r * h);
+    m->ldcat8 = dk_weight_pitch_fp8((1 + r) * h);
+    // (a ragged image token count pads the image rows to the next scale block; aligned counts: rows8 == BS, the sizes they always had)
+    m->txt0_8 = (int)align_up((size_t)B * S_i, 128);
+    m->rows8 = (long)m->txt0_8 + (long)B * S_t;
+    const size_t R8 = (size_t)m->rows8;
+    m->nblk = mx_nblk(m->rows8);
+    m->XN8 = (unsigned char*)c.take(R8 * h);
+    m->ATT8 = (unsigned char*)c.take(R8 * h);
+    const size_t hid8 = R8 * (size_t)m->ldh8, cat8 = m->cfg.depth_unified > 0 ? R8 * (size_t)m->ldcat8 : 0;
+    m->HC8 = (unsigned char*)c.take(cat8 > hid8 ? cat8 : hid8);
+    m->SXN = (unsigned char*)c.take(dk_mx_scale_bytes(m->rows8, h));
+    m->SATT = (unsigned char*)c.take(dk_mx_scale_bytes(m->rows8, h));
+    m->SHID = (unsigned char*)c.take(dk_mx_scale_bytes(m->rows8, r * h));
+    m->SCAT = (unsigned char*)c.take(m->cfg.depth_unified > 0 ? dk_mx_scale_bytes(m->rows8, (1 + r) * h) : 0);
+  }
+  m->MOD = (bf16_t*)c.take((size_t)n_t * B * m->mod_rows() * h * 2);
+  m->POS = (bf16_t*)c.take(m->cfg.use_pos_embed ? (size_t)S_i * h * 2 : 0);
+  m->CTXE = (bf16_t*)c.take((size_t)B * S_t * h * 2);
+  m->temb = (bf16_t*)c.take((size_t)n_t * m->cfg.frequency_embed_dim * 2);
+  m->t1 = (bf16_t*)c.take((size_t)n_t * h * 2);
+  m->tvec = (bf16_t*)c.take((size_t)n_t * h * 2);
+  m->y1 = (bf16_t*)c.take((size_t)B * h * 2);
+  m->yvec = (bf16_t*)c.take((size_t)B * h * 2);
+  m->vec = (bf16_t*)c.take((size_t)n_t * B * h * 2);
+  m->gemb = (bf16_t*)c.take(m->cfg.guidance_embed ? (size_t)m->cfg.frequency_embed_dim * 2 : 0);
+  m->g1 = (bf16_t*)c.take(m->cfg.guidance_embed ? (size_t)h * 2 : 0);
+  m->gvec = (bf16_t*)c.take(m->cfg.guidance_embed ? (size_t)h * 2 : 0);
+  m->rope = (float*)c.take(m->cfg.use_rope ? (size_t)S * m->D() * 4 : 0);
+  m->tdev = (float*)c.take((size_t)n_t * 4);
+  m->GWS = c.take(dk_gemm_split_workspace_bytes());
+  // this engine's own region for the key-split jobs of attention5.hip (two engines, or an engine and ops.attention, driven from one
+  // host thread on different streams must not share the partial results of their split launches)
+  m->AWS_bytes = m->D() == 128 ? dk_attention_workspace_bytes() : 0;
+  m->AWS = c.take(m->AWS_bytes);
+  return c.off;
+}
+
+extern "C" size_t dk_mmdit_workspace_bytes(const dk_mmdit* m, int32_t batch, int32_t latent_h, int32_t latent_w, int32_t text_len,
+                                           int32_t n_timesteps) {
+  dk_mmdit tmp = *m;
+  Carver c(nullptr, 0);
+  return mmdit_carve(&tmp, c, batch, latent_h, latent_w, text_len, n_timesteps) + 256;
+}
+
+extern "C" int dk_mmdit_prepare(dk_mmdit* m, int32_t batch, int32_t latent_h, int32_t latent_w, int32_t text_len,
+                                int32_t n_timesteps, void* workspace, size_t workspace_bytes, void* stream) {
+  DK_REQUIRE(m && workspace, "null argument");
+  DK_REQUIRE(batch > 0 && text_len > 0 && n_timesteps > 0, "empty problem");
+  const int p = m->cfg.patch_size;
+  DK_REQUIRE(latent_h % p == 0 && latent_w % p == 0, "latent size must be divisible by the patch size");
+  DK_TRY(mmdit_resolve(m));
+  // (the image token count is free: a last, partial scale block is handled by the row order of the fp8 buffers, mmdit_carve)
+  if (m->fp8()) DK_REQUIRE(text_len % 128 == 0, "fp8_linears: only text lengths that are multiples of 128 are supported (MX scale blocks of 128 rows; the image token count is free)");
+  DK_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
+  Carver c(workspace, workspace_bytes);
+  const size_t need_bytes = mmdit_carve(m, c, batch, latent_h, latent_w, text_len, n_timesteps);
+  DK_REQUIRE(need_bytes <= workspace_bytes, "workspace too small");
+  m->B = batch; m->Hl = latent_h; m->Wl = latent_w; m->S_t = text_len;
+  m->S_i = (latent_h / p) * (latent_w / p); m->S = m->S_t + m->S_i; m->n_t = n_timesteps;
+  hipStream_t st = S_(stream);
+  if (m->cfg.use_rope)
+    DK_TRY(dk_launch_rope_table(m->rope, m->S_t, latent_h / p, latent_w / p, m->cfg.rope_axes_dim, m->cfg.n_rope_axes,
+                                (float)m->cfg.rope_theta, st));
+  if (m->cfg.use_pos_embed) {
+    // centre crop of the learned table (mmdit.py:334-349): rows y0..y0+gh, cols x0..x0+gw
+    const int mh = m->cfg.max_latent_resolution, gh = latent_h / p, gw = latent_w / p;
+    DK_REQUIRE(gh <= mh && gw <= mh, "latent larger than the positional table");
+    const int y0 = (mh - gh) / 2, x0 = (mh - gw) / 2;
+    DK_CHECK_HIP(hipMemcpy2DAsync(m->POS, (size_t)gw * m->h() * 2, m->pos_w + ((size_t)y0 * mh + x0) * m->h(),
+                                  (size_t)mh * m->h() * 2, (size_t)gw * m->h() * 2, gh, hipMemcpyDeviceToDevice, st));
+  }
+  // the flag region of the GEMM split workspace must be zero before the first launch (the kernels leave it zero)
+  DK_CHECK_HIP(hipMemsetAsync((char*)m->GWS + DK_KSPLIT_FLAGS_OFF, 0, DK_KSPLIT_FLAG_BYTES, st));
+  m->prepared = true;
+  m->mod_ready = false;
+  m->ctx_ready = false;
+  return 0;
+}
+
+extern "C" int dk_mmdit_cache_modulation_params(dk_mmdit* m, const void* pooled, const float* timesteps_host, int32_t n,
+                                                void* stream) {
+  DK_REQUIRE(m && m->prepared, "dk_mmdit_prepare must be called first");
+  DK_REQUIRE(n > 0 && n <= m->n_t, "more timesteps than the workspace was prepared for");
+  hipStream_t st = S_(stream);
+  LinearWsScope ws_scope(m->GWS);
+  ElemScope elem_scope(m->dtype);
+  const int h = m->h(), B = m->B, P = m->cfg.pooled_text_embed_dim, Fq = m->cfg.frequency_embed_dim;
+  DK_CHECK_HIP(hipMemcpyAsync(m->tdev, timesteps_host, (size_t)n * 4, hipMemcpyHostToDevice, st));
+  DK_TRY(DK_EL(dk_launch_timestep_embedding)(m->tdev, n, 1, Fq, (float)m->cfg.max_period, m->cfg.embed_dtype, m->temb, st));
+  // t_embedder / y_embedder: Linear -> SiLU -> Linear (mmdit.py:352-392)
+  DK_TRY(dk_launch_gemm(Linear(dense(m->temb, Fq), m->t0_w, m->t0_b, dense(m->t1, h), n, h, Fq, DK_EPI_BIAS_SILU), st));
+  DK_TRY(dk_launch_gemm(Linear(dense(m->t1, h), m->t2_w, m->t2_b, dense(m->tvec, h), n, h, h, DK_EPI_BIAS), st));
+  DK_TRY(dk_launch_gemm(Linear(dense((const bf16_t*)pooled, P), m->y0_w, m->y0_b, dense(m->y1, h), B, h, P, DK_EPI_BIAS_SILU), st));
+  DK_TRY(dk_launch_gemm(Linear(dense(m->y1, h), m->y2_w, m->y2_b, dense(m->yvec, h), B, h, h, DK_EPI_BIAS), st));
+  if (m->cfg.guidance_embed) {
+    // FLUX.1-dev guidance embedding (MLPEmbedder, mmdit.py:31-36,945-955): g = guidance_in(timestep_embedding(1000 * guidance)),
+    // added to the pooled-text embedding of every batch row, hence to every modulation vector
+    const float gt = 1000.0f * m->guidance;
+    DK_CHECK_HIP(hipMemcpyAsync(m->tdev, &gt, 4, hipMemcpyHostToDevice, st));  // (tdev[0] was consumed by the launch above, same stream)
+    DK_TRY(DK_EL(dk_launch_timestep_embedding)(m->tdev, 1, 1, Fq, (float)m->cfg.max_period, m->cfg.embed_dtype, m->gemb, st));
+    DK_TRY(dk_launch_gemm(Linear(dense(m->gemb, Fq), m->g0_w, m->g0_b, dense(m->g1, h), 1, h, Fq, DK_EPI_BIAS_SILU), st));
+    DK_TRY(dk_launch_gemm(Linear(dense(m->g1, h), m->g2_w, m->g2_b, dense(m->gvec, h), 1, h, h, DK_EPI_BIAS), st));
+    DK_TRY(DK_EL(dk_launch_add)(m->yvec, m->gvec, 1, m->yvec, B, h, st));  // y[b] += g
+  }
+  // vec[step*B + b] = silu(y[b] + t[step]); adaLN_modulation = SiLU -> Linear (mmdit.py:94-96,430-435)
+  DK_TRY(DK_EL(dk_launch_add)(m->yvec, m->tvec, n, m->vec, n * B, h, st));
+  DK_TRY(DK_EL(dk_launch_silu)(m->vec, m->vec, (long)n * B * h, st));
+  const int Nmod = m->mod_rows() * h;
+  DK_TRY(dk_launch_gemm(Linear(dense(m->vec, h), m->adaln_w, m->adaln_b, dense(m->MOD, Nmod), n * B, Nmod, h, DK_EPI_BIAS), st));
+  m->mod_ready = true;
+  return 0;
+}
+
+extern "C" int dk_mmdit_cache_context(dk_mmdit* m, const void* text, void* stream) {
+  DK_REQUIRE(m && m->prepared && text, "prepare must precede cache_context");
+  LinearWsScope ws_scope(m->GWS);
+  ElemScope elem_scope(m->dtype);
+  const int M = m->B * m->S_t, T = m->cfg.token_level_text_embed_dim;
+  // (no split workspace: like the per-step form in dk_mmdit_forward, whose result it stands for)
+  DK_TRY(dk_launch_gemm(Linear(dense((const bf16_t*)text, T), m->ctx_w, m->ctx_b, dense(m->CTXE, m->h()), M, m->h(), T, DK_EPI_BIAS), S_(stream)));
+  m->ctx_ready = true;
+  return 0;
+}
+
+// FinalLayer (mmdit.py:767-796) on the image rows
+static int mmdit_final_layer(dk_mmdit* m, const bf16_t* mod_step, bf16_t* tokens_out, hipStream_t st) {
+  const int h = m->h(), B = m->B, S = m->S, S_t = m->S_t, S_i = m->S_i, F = m->F();
+  const int mod_stride = m->mod_rows() * h;
+  const bf16_t* mod_fin = mod_step + (size_t)m->mod_offset(3, 0) * h;
+  DK_TRY(DK_EL(dk_launch_ln_modulate)(m->X + (size_t)S_t * h, h, m->XN, h, B * S_i, h, mod_fin, mod_fin + h, mod_stride, S_i, S_i, S,
+                               m->cfg.layer_norm_eps, st));
+  return dk_launch_gemm(Linear(dense(m->XN, h), m->final_w, m->final_b, dense(tokens_out, F), B * S_i, F, h, DK_EPI_BIAS), st);
+}
+
+// ---- the transformer blocks -----------------------------------------------------------------------------------------------------
+// What every block of a call derives from the prepared shape, built once per call (mmdit_blocks)
+struct BlockCtx {
+  int h, B, S, S_t, S_i, Mi, Mt;  // Mi / Mt: image / text rows of all batch rows
+  int mod_stride;                 // modulation rows of one batch row
+  float scale;
+  const float* rope;
+  Rows X_img, X_txt;  // the two streams of the residual m->X
+  // fp8 row order.  XN8 / HID8: image rows [0, Mi), text rows [T0, T0 + Mt) with T0 = ceil128(Mi) (= Mi, the bf16 path's row order, for aligned
+  // image token counts).  CAT8 is indexed like the joint stream (b * S + s); so is ATT8 while S_i is a multiple of 128 -- with a ragged S_i the
+  // image segment of batch row b >= 1 would start inside a scale block, and ATT8 takes the row order of XN8 instead (att_split: the attention
+  // launch maps (b, s) to it, the o-projections read two plain row ranges)
+  int T0;
+  long R8;
+  bool att_split;
+  Mx8Out xn_img, xn_txt, xn_all;  // (xn_all -- single blocks: the joint stream from row 0, any M)
+};
+static BlockCtx block_ctx(const dk_mmdit* m) {
+  BlockCtx c;
+  memset(&c, 0, sizeof(c));
+  c.h = m->h(); c.B = m->B; c.S = m->S; c.S_t = m->S_t; c.S_i = m->S_i; c.Mi = m->B * m->S_i; c.Mt = m->B * m->S_t;
+  c.mod_stride = m->mod_rows() * c.h;
+  c.scale = 1.0f / sqrtf((float)m->D());
+  c.rope = m->cfg.use_rope ? m->rope : nullptr;
+  c.X_img = m->img(m->X, c.h); c.X_txt = m->txt(m->X, c.h);
+  if (m->fp8()) {
+    c.T0 = m->txt0_8; c.R8 = m->rows8; c.att_split = c.S_i % 128 != 0;
+    c.xn_img = mx8_out(m->XN8, m->SXN, c.h, c.R8, 0, c.Mi, 0, 0);
+    c.xn_txt = mx8_out(m->XN8, m->SXN, c.h, c.R8, c.T0, c.Mt, 0, 0);
+    c.xn_all = mx8_out(m->XN8, m->SXN, c.h, c.R8, 0, c.B * c.S, 0, 0);
+  }
+  return c;
+}
+// modulation rows of block `index` of `kind` (mod_offset) in the step's table
+static const bf16_t* block_mod(const dk_mmdit* m, const bf16_t* mod_step, int kind, int index) {
+  return mod_step + (size_t)m->mod_offset(kind, index) * m->h();
+}
+// QKNorm + RoPE: the keys in the projection's tail (or one pass over the buffer) -- for both streams of a double block or for neither
+static bool keys_in_tail(const StreamW& a, const StreamW* b) { return fuse_k(a.kn) && (b == nullptr || fuse_k(b->kn)); }
+// ... and the projection's tail finished the queries of every stream of the block too: the attention kernel loads them plain
+static bool queries_in_tail(const StreamW& a, const StreamW* b, bool f8) {
+  return keys_in_tail(a, b) && fuse_qg(a.qn, f8) && (b == nullptr || fuse_qg(b->qn, f8));
+}
+// Attention over the joint sequence of m->QKV into O (pitch ldo).  The queries that the projection's tail left raw are normalised / rotated
+// in the Q load: text rows with wt's weight, image rows with wi's (double block), or all rows with wt's (single block: wi null).
+// O8 / O8_scales / o8_ld: the MX-fp8 copy of the output the fp8 path's next Linear reads (it comes out of the attention kernel or out of a
+// quantiser pass behind it: attention.hip); null on the bf16 path
+static AttnParams joint_attention(const dk_mmdit* m, const BlockCtx& c, bf16_t* O, int ldo, const StreamW& wt, const StreamW* wi,
+                                  unsigned char* O8 = nullptr, unsigned char* O8_scales = nullptr, int o8_ld = 0) {
+  AttnParams ap;
+  ap.dtype = m->dtype;
+  ap.Q = m->QKV; ap.K = m->QKV + c.h; ap.V = m->QKV + 2 * c.h; ap.O = O;
+  ap.B = c.B; ap.H = m->cfg.num_heads; ap.S = c.S; ap.D = m->D(); ap.ld = 3 * c.h; ap.ldo = ldo; ap.scale = c.scale;
+  if (fuse_q() && !queries_in_tail(wt, wi, O8 != nullptr)) {
+    ap.qn_a = wt.qn; ap.qn_b = wi ? wi->qn : wt.qn; ap.qn_split = wi ? c.S_t : 0; ap.q_rope = c.rope;
+  }
+  if (O8 != nullptr) { ap.O8 = O8; ap.O8_scales = O8_scales; ap.o8_ld = o8_ld; ap.o8_nblk = m->nblk; }
+  return ap;
+}
+
+// MultiModalTransformerBlock i (mmdit.py:568-675), bf16 Linears.  The two streams run the same Linear shapes on different weights; their
+// GEMMs are issued as pairs so that the 256 x 256 kernel can place the text tiles in the same wave as the image tiles
+// (dk_launch_gemm_pair).  Every block Linear carries the engine's split workspace.
+static int double_block_bf16(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t* mod_step, hipStream_t st) {
+  const dk_mmdit_config& cf = m->cfg;
+  const int h = c.h, S = c.S, S_t = c.S_t, S_i = c.S_i, Mi = c.Mi, Mt = c.Mt, r = cf.mlp_ratio, ldh = m->ldh, mod_stride = c.mod_stride;
+  const bf16_t *mod_img = block_mod(m, mod_step, 0, i), *mod_txt = block_mod(m, mod_step, 1, i);
+  const StreamW &wi = m->dimg[i], &wt = m->dtxt[i];
+  const bool txt_post = !m->txt_skipped(i);
+  const Rows X_img = c.X_img, X_txt = c.X_txt;
+  const Rows XN_img = dense(m->XN, h), XN_txt = dense(m->XN + (size_t)Mi * h, h);              // (image rows first)
+  const Rows HID_img = dense(m->HID, ldh), HID_txt = dense(m->HID + (size_t)Mi * ldh, ldh);  // MLP hidden of both streams
+  // pre_sdpa (mmdit.py:440-519): LN-modulate, q/k/v projection, QK-norm (+ RoPE)
+  // (image and text stream of each elementwise stage in ONE launch: the 256 text rows do not run alone on the chip)
+  DK_TRY(DK_EL(dk_launch_ln_modulate2)(X_img.p, XN_img.p, Mi, mod_img, mod_img + h, S_i, X_txt.p, XN_txt.p, Mt, mod_txt, mod_txt + h, S_t, h, h, h,
+                                mod_stride, S, cf.layer_norm_eps, st));
+  Linear qkv_img = Linear(XN_img, wi.qkv_w, wi.qkv_b, m->img(m->QKV, 3 * h), Mi, 3 * h, h, DK_EPI_BIAS).split_ws();
+  Linear qkv_txt = Linear(XN_txt, wt.qkv_w, wt.qkv_b, m->txt(m->QKV, 3 * h), Mt, 3 * h, h, DK_EPI_BIAS).split_ws();
+  // QKNorm + RoPE: the keys in the projection's tail (or one pass over the buffer), the queries inside the attention kernel's Q load
+  const bool kf = keys_in_tail(wi, &wt);
+  if (kf) {
+    set_key_norm(qkv_img, wi.kn, wi.qn, h, m->D(), c.rope, S_t, S_i);
+    set_key_norm(qkv_txt, wt.kn, wt.qn, h, m->D(), c.rope, 0, S_t);
+  }
+  DK_TRY(dk_launch_gemm_pair(qkv_img, qkv_txt, st));
+  if (!kf)
+    DK_TRY(DK_EL(dk_launch_qk_norm_rope2)(m->QKV + (size_t)S_t * 3 * h, Mi, wi.qn, wi.kn, S_i, S_t, m->QKV, Mt, wt.qn, wt.kn, S_t, 0, 3 * h, 0, h,
+                                   cf.num_heads, m->D(), 1e-6f, c.rope, S, st, fuse_q()));
+  DK_TRY(dk_launch_attention(joint_attention(m, c, m->ATT, h, wt, &wi), st));
+  // post_sdpa, sequential form (mmdit.py:537-548): residual += gate_attn * o_proj(attn)
+  const Linear o_img = Linear(m->img(m->ATT, h), wi.o_w, wi.o_b, X_img, Mi, h, h, DK_EPI_GATE_RES)
+                           .gate_res(mod_img + 2 * h, S_i, mod_stride, X_img).split_ws();
+  if (txt_post) {
+    const Linear o_txt = Linear(m->txt(m->ATT, h), wt.o_w, wt.o_b, X_txt, Mt, h, h, DK_EPI_GATE_RES)
+                             .gate_res(mod_txt + 2 * h, S_t, mod_stride, X_txt).split_ws();
+    DK_TRY(dk_launch_gemm_pair(o_img, o_txt, st));
+  } else {
+    DK_TRY(dk_launch_gemm(o_img, st));
+  }
+  // residual += gate_mlp * fc2(gelu(fc1(LN-mod(residual))))
+  if (txt_post)
+    DK_TRY(DK_EL(dk_launch_ln_modulate2)(X_img.p, XN_img.p, Mi, mod_img + 3 * h, mod_img + 4 * h, S_i, X_txt.p, XN_txt.p, Mt, mod_txt + 3 * h,
+                                  mod_txt + 4 * h, S_t, h, h, h, mod_stride, S, cf.layer_norm_eps, st));
+  else
+    DK_TRY(DK_EL(dk_launch_ln_modulate)(X_img.p, h, XN_img.p, h, Mi, h, mod_img + 3 * h, mod_img + 4 * h, mod_stride, S_i, S_i, S, cf.layer_norm_eps, st));
+  const Linear fc1_img = Linear(XN_img, wi.fc1_w, wi.fc1_b, HID_img, Mi, r * h, h, DK_EPI_BIAS_GELU).split_ws();
+  const Linear fc2_img = Linear(HID_img, wi.fc2_w, wi.fc2_b, X_img, Mi, h, r * h, DK_EPI_GATE_RES, ldh)
+                             .gate_res(mod_img + 5 * h, S_i, mod_stride, X_img).split_ws();
+  if (txt_post) {
+    const Linear fc1_txt = Linear(XN_txt, wt.fc1_w, wt.fc1_b, HID_txt, Mt, r * h, h, DK_EPI_BIAS_GELU).split_ws();
+    const Linear fc2_txt = Linear(HID_txt, wt.fc2_w, wt.fc2_b, X_txt, Mt, h, r * h, DK_EPI_GATE_RES, ldh)
+                               .gate_res(mod_txt + 5 * h, S_t, mod_stride, X_txt).split_ws();
+    DK_TRY(dk_launch_gemm_pair(fc1_img, fc1_txt, st));
+    DK_TRY(dk_launch_gemm_pair(fc2_img, fc2_txt, st));
+  } else {
+    DK_TRY(dk_launch_gemm(fc1_img, st));
+    DK_TRY(dk_launch_gemm(fc2_img, st));
+  }
+  return 0;
+}
+
+// UnifiedTransformerBlock i (mmdit.py:693-751), bf16 Linears: parallel attention + MLP
+static int single_block_bf16(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t* mod_step, hipStream_t st) {
+  const dk_mmdit_config& cf = m->cfg;
+  const int h = c.h, S = c.S, M = c.B * c.S, r = cf.mlp_ratio, ldcat = m->ldcat;
+  const StreamW& w = m->single[i];
+  const bf16_t* mod = block_mod(m, mod_step, 2, i);
+  const Rows X = dense(m->X, h), CAT = dense(m->CAT, ldcat);
+  DK_TRY(DK_EL(dk_launch_ln_modulate)(m->X, h, m->XN, h, M, h, mod, mod + h, c.mod_stride, S, M, 0, cf.layer_norm_eps, st));
+  {  // linear1: [q|k|v] -> QKV, gelu(fc1) -> CAT[:, h:], one pass over the modulated activations
+    Linear l1 = Linear(dense(m->XN, h), w.qkv_w, w.qkv_b, dense(m->QKV, 3 * h), M, (3 + r) * h, h, DK_EPI_BIAS).split_ws();
+    l1.n_split = 3 * h; l1.C2 = m->CAT + h; l1.ldc2 = ldcat; l1.epi2 = DK_EPI_BIAS_GELU;
+    if (keys_in_tail(w, nullptr)) set_key_norm(l1, w.kn, w.qn, h, m->D(), c.rope, 0, S);
+    DK_TRY(dk_launch_gemm(l1, st));
+  }
+  if (!keys_in_tail(w, nullptr))
+    DK_TRY(DK_EL(dk_launch_qk_norm_rope)(m->QKV, 3 * h, 0, h, M, cf.num_heads, m->D(), w.qn, w.kn, 1e-6f, c.rope, S, S, 0, S, st, fuse_q()));
+  DK_TRY(dk_launch_attention(joint_attention(m, c, m->CAT, ldcat, w, nullptr), st));
+  // x += gate * ([attn | gelu] @ [o_proj | fc2]^T + bias)   (one bias: quirk Q8)
+  // (with the split workspace: below 1024 x 1024 the launch is a fraction of a round of the CUs and is cut along K)
+  const Linear l2 = Linear(CAT, w.l2_w, w.l2_b, X, M, h, (1 + r) * h, DK_EPI_GATE_RES, ldcat).gate_res(mod + 2 * h, S, c.mod_stride, X).split_ws();
+  return dk_launch_gemm(l2, st);
+}
+
+// ---- fp8_linears: the transformer blocks on the fp8 GEMM (gemm256f8.hip) -------------------------------------------------
+// A Linear over MX-fp8 activations.  abuf / sa: the fp8 activation buffer and its scale side array (pitch lda bytes); the GEMM
+// reads logical rows through (a_row0, a_seg_len, a_seg_stride): a_row0 a multiple of 128 rows, and either one segment of any length or
+// segments of whole 128-row blocks (dk_gemm256f8_eligible; the row order of mmdit_carve provides it for every token count).
+// Every one carries the engine's split workspace (the K split of small launches).
+static GemmF8Params f8_params(const dk_mmdit* m, const unsigned char* abuf, const unsigned char* sa, int lda, int a_row0, int a_seg_len,
+                              int a_seg_stride, const unsigned char* W, int ldw, const float* ws, const bf16_t* bias, int M, int N, int K,
+                              int epi) {
+  GemmF8Params p;
+  memset(&p, 0, sizeof(p));
+  p.A = abuf + (size_t)a_row0 * lda; p.SA = sa; p.W = W; p.wscale = ws; p.bias = bias;
+  p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = ldw;
+  p.a_seg_len = a_seg_len; p.a_seg_stride = a_seg_stride; p.a_row0 = a_row0; p.sa_nblk = m->nblk;
+  p.epi = epi;
+  if (g_linear_ws) { p.workspace = g_linear_ws; p.workspace_bytes = dk_gemm_split_workspace_bytes(); }
+  return p;
+}
+static void f8_out_bf16(GemmF8Params& p, Rows C) {
+  p.C = C.p; p.ldc = C.ld; p.c_seg_len = C.seg_len > 0 ? C.seg_len : p.M; p.c_seg_stride = C.seg_stride; p.c_mx8 = 0;
+  p.r_seg_len = p.M; p.gate_seg_len = p.M;
+}
+// the MX-fp8 output of fc1: rows [c_row0, c_row0 + M) of HC8 (pitch ldh8), scales in SHID
+static void f8_out_hid8(GemmF8Params& p, const dk_mmdit* m, int c_row0) {
+  p.C = m->HC8 + (size_t)c_row0 * m->ldh8; p.ldc = m->ldh8; p.c_seg_len = p.M; p.c_mx8 = 1;
+  p.SC = m->SHID; p.sc_nblk = m->nblk; p.c_row0 = c_row0; p.sc_kb0 = 0;
+  p.r_seg_len = p.M; p.gate_seg_len = p.M;
+}
+
+// MultiModalTransformerBlock i on the fp8 GEMM: the streams' Linears as pairs of one launch (dk_launch_gemm256f8)
+static int double_block_fp8(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t* mod_step, hipStream_t st) {
+  const dk_mmdit_config& cf = m->cfg;
+  const int h = c.h, S = c.S, S_t = c.S_t, S_i = c.S_i, Mi = c.Mi, Mt = c.Mt, T0 = c.T0, r = cf.mlp_ratio, ldh8 = m->ldh8, mod_stride = c.mod_stride;
+  const bf16_t *mod_img = block_mod(m, mod_step, 0, i), *mod_txt = block_mod(m, mod_step, 1, i);
+  const StreamW &wi = m->dimg[i], &wt = m->dtxt[i];
+  const bool txt_post = !m->txt_skipped(i);
+  const Rows X_img = c.X_img, X_txt = c.X_txt;
+  // pre_sdpa (mmdit.py:440-519): LN-modulate -> MX-fp8, q/k/v projection, QK-norm (+ RoPE)
+  DK_TRY(dk_launch_ln_modulate2_mx8(X_img.p, Mi, mod_img, mod_img + h, S_i, c.xn_img, X_txt.p, Mt, mod_txt, mod_txt + h, S_t, c.xn_txt, h, h, mod_stride,
+                                    S, cf.layer_norm_eps, st));
+  const bool kf = keys_in_tail(wi, &wt);
+  {
+    GemmF8Params qi = f8_params(m, m->XN8, m->SXN, h, 0, Mi, 0, wi.qkv_w8, h, wi.qkv_ws, wi.qkv_b, Mi, 3 * h, h, DK_EPI_BIAS);
+    GemmF8Params qt = f8_params(m, m->XN8, m->SXN, h, T0, Mt, 0, wt.qkv_w8, h, wt.qkv_ws, wt.qkv_b, Mt, 3 * h, h, DK_EPI_BIAS);
+    f8_out_bf16(qi, m->img(m->QKV, 3 * h));
+    f8_out_bf16(qt, m->txt(m->QKV, 3 * h));
+    if (kf) {
+      set_key_norm(qi, wi.kn, wi.qn, h, m->D(), c.rope, S_t, S_i);
+      set_key_norm(qt, wt.kn, wt.qn, h, m->D(), c.rope, 0, S_t);
+    }
+    DK_TRY(dk_launch_gemm256f8(qi, &qt, st));
+  }
+  if (!kf)
+    DK_TRY(dk_launch_qk_norm_rope2(m->QKV + (size_t)S_t * 3 * h, Mi, wi.qn, wi.kn, S_i, S_t, m->QKV, Mt, wt.qn, wt.kn, S_t, 0, 3 * h, 0, h,
+                                   cf.num_heads, m->D(), 1e-6f, c.rope, S, st, fuse_q()));
+  AttnParams ap = joint_attention(m, c, m->ATT, h, wt, &wi, m->ATT8, m->SATT, h);  // (ATT8: the o-projection's operand)
+  if (c.att_split) { ap.o8_split = S_t; ap.o8_txt_row0 = T0; }
+  DK_TRY(dk_launch_attention(ap, st));
+  // post_sdpa (mmdit.py:537-548): residual += gate_attn * o_proj(attn)
+  {
+    GemmF8Params oi = c.att_split ? f8_params(m, m->ATT8, m->SATT, h, 0, Mi, 0, wi.o_w8, h, wi.o_ws, wi.o_b, Mi, h, h, DK_EPI_GATE_RES)
+                                  : f8_params(m, m->ATT8, m->SATT, h, S_t, S_i, S, wi.o_w8, h, wi.o_ws, wi.o_b, Mi, h, h, DK_EPI_GATE_RES);
+    f8_out_bf16(oi, X_img);
+    set_gate_res(oi, mod_img + 2 * h, S_i, mod_stride, X_img);
+    GemmF8Params ot = c.att_split ? f8_params(m, m->ATT8, m->SATT, h, T0, Mt, 0, wt.o_w8, h, wt.o_ws, wt.o_b, Mt, h, h, DK_EPI_GATE_RES)
+                                  : f8_params(m, m->ATT8, m->SATT, h, 0, S_t, S, wt.o_w8, h, wt.o_ws, wt.o_b, Mt, h, h, DK_EPI_GATE_RES);
+    f8_out_bf16(ot, X_txt);
+    set_gate_res(ot, mod_txt + 2 * h, S_t, mod_stride, X_txt);
+    DK_TRY(dk_launch_gemm256f8(oi, txt_post ? &ot : nullptr, st));
+  }
+  // residual += gate_mlp * fc2(gelu(fc1(LN-mod(residual)))); the MLP hidden leaves fc1 as MX-fp8
+  if (txt_post)
+    DK_TRY(dk_launch_ln_modulate2_mx8(X_img.p, Mi, mod_img + 3 * h, mod_img + 4 * h, S_i, c.xn_img, X_txt.p, Mt, mod_txt + 3 * h, mod_txt + 4 * h, S_t,
+                                      c.xn_txt, h, h, mod_stride, S, cf.layer_norm_eps, st));
+  else
+    DK_TRY(dk_launch_ln_modulate_mx8(X_img.p, h, Mi, h, mod_img + 3 * h, mod_img + 4 * h, mod_stride, S_i, S_i, S, cf.layer_norm_eps, c.xn_img, st));
+  GemmF8Params f1i = f8_params(m, m->XN8, m->SXN, h, 0, Mi, 0, wi.fc1_w8, h, wi.fc1_ws, wi.fc1_b, Mi, r * h, h, DK_EPI_BIAS_GELU);
+  f8_out_hid8(f1i, m, 0);
+  GemmF8Params f2i = f8_params(m, m->HC8, m->SHID, ldh8, 0, Mi, 0, wi.fc2_w8, ldh8, wi.fc2_ws, wi.fc2_b, Mi, h, r * h, DK_EPI_GATE_RES);
+  f8_out_bf16(f2i, X_img);
+  set_gate_res(f2i, mod_img + 5 * h, S_i, mod_stride, X_img);
+  GemmF8Params f1t = f8_params(m, m->XN8, m->SXN, h, T0, Mt, 0, wt.fc1_w8, h, wt.fc1_ws, wt.fc1_b, Mt, r * h, h, DK_EPI_BIAS_GELU);
+  f8_out_hid8(f1t, m, T0);
+  GemmF8Params f2t = f8_params(m, m->HC8, m->SHID, ldh8, T0, Mt, 0, wt.fc2_w8, ldh8, wt.fc2_ws, wt.fc2_b, Mt, h, r * h, DK_EPI_GATE_RES);
+  f8_out_bf16(f2t, X_txt);
+  set_gate_res(f2t, mod_txt + 5 * h, S_t, mod_stride, X_txt);
+  DK_TRY(dk_launch_gemm256f8(f1i, txt_post ? &f1t : nullptr, st));
+  return dk_launch_gemm256f8(f2i, txt_post ? &f2t : nullptr, st);
+}
+
+// UnifiedTransformerBlock i on the fp8 GEMM
+static int single_block_fp8(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t* mod_step, hipStream_t st) {
+  const dk_mmdit_config& cf = m->cfg;
+  const int h = c.h, S = c.S, M = c.B * c.S, r = cf.mlp_ratio, ldcat8 = m->ldcat8;
+  const StreamW& w = m->single[i];
+  const bf16_t* mod = block_mod(m, mod_step, 2, i);
+  const Rows X = dense(m->X, h);
+  DK_TRY(dk_launch_ln_modulate_mx8(m->X, h, M, h, mod, mod + h, c.mod_stride, S, M, 0, cf.layer_norm_eps, c.xn_all, st));
+  {  // linear1: [q|k|v] -> QKV (bf16), gelu(fc1) -> CAT8[:, h:] (MX-fp8), one pass over the modulated activations
+    GemmF8Params l1 = f8_params(m, m->XN8, m->SXN, h, 0, M, 0, w.qkv_w8, h, w.qkv_ws, w.qkv_b, M, (3 + r) * h, h, DK_EPI_BIAS);
+    f8_out_bf16(l1, dense(m->QKV, 3 * h));
+    l1.n_split = 3 * h; l1.C2 = m->HC8 + h; l1.ldc2 = ldcat8; l1.epi2 = DK_EPI_BIAS_GELU; l1.c2_mx8 = 1;
+    l1.SC = m->SCAT; l1.sc_nblk = m->nblk; l1.c_row0 = 0; l1.sc_kb0 = h / 32;
+    if (keys_in_tail(w, nullptr)) set_key_norm(l1, w.kn, w.qn, h, m->D(), c.rope, 0, S);
+    DK_TRY(dk_launch_gemm256f8(l1, nullptr, st));
+  }
+  if (!keys_in_tail(w, nullptr))
+    DK_TRY(dk_launch_qk_norm_rope(m->QKV, 3 * h, 0, h, M, cf.num_heads, m->D(), w.qn, w.kn, 1e-6f, c.rope, S, S, 0, S, st, fuse_q()));
+  // (the MX-fp8 copy: the [attn | gelu] operand of linear2, columns [0, h))
+  DK_TRY(dk_launch_attention(joint_attention(m, c, m->ATT, h, w, nullptr, m->HC8, m->SCAT, ldcat8), st));
+  // x += gate * ([attn | gelu] @ [o_proj | fc2]^T + bias)   (one bias: quirk Q8)
+  GemmF8Params l2 = f8_params(m, m->HC8, m->SCAT, ldcat8, 0, M, 0, w.l2_w8, ldcat8, w.l2_ws, w.l2_b, M, h, (1 + r) * h, DK_EPI_GATE_RES);
+  f8_out_bf16(l2, X);
+  set_gate_res(l2, mod + 2 * h, S, c.mod_stride, X);
+  return dk_launch_gemm256f8(l2, nullptr, st);
+}
+
+// Blocks [first, first + count) of the global order (double blocks 0 .. depth_multimodal - 1, then single blocks) on the joint residual
+// stream m->X: the bf16 double blocks of the precision policy on the bf16 path, everything else on the model's own
+static int mmdit_blocks(dk_mmdit* m, const bf16_t* mod_step, int first, int count, hipStream_t st) {
+  const BlockCtx c = block_ctx(m);
+  const int n_double = m->cfg.depth_multimodal;
+  for (int g = first; g < first + count; ++g) {
+    const bool f8 = m->fp8() && g >= m->n_bf16();
+    if (g < n_double)
+      DK_TRY((f8 ? double_block_fp8 : double_block_bf16)(m, c, g, mod_step, st));
+    else
+      DK_TRY((f8 ? single_block_fp8 : single_block_bf16)(m, c, g - n_double, mod_step, st));
+  }
+  return 0;
+}
+
+struct AttnWsScope {  // an engine call's attention launches split through that engine's region; the host thread's own setting comes back
+  void* prev;
+  size_t prev_bytes;
+  AttnWsScope(void* ws, size_t bytes) : prev(dk_get_attention_workspace()), prev_bytes(dk_get_attention_workspace_bytes()) {
+    dk_set_attention_workspace(ws, bytes);  // (an engine without a region -- D = 64 -- runs unsplit: never the thread's buffer on another engine's stream)
+  }
+  ~AttnWsScope() { dk_set_attention_workspace(prev, prev_bytes); }
+};
+struct MmditCallScope {  // an engine call's GEMM and attention splits go through THAT engine's regions; the caller's settings come back
+  LinearWsScope lin;
+  AttnWsScope att;
+  ElemScope elem;
+  explicit MmditCallScope(dk_mmdit* m) : lin(m->GWS), att(m->AWS, m->AWS_bytes), elem(m->dtype) {}
+};
+
+extern "C" int dk_mmdit_forward(dk_mmdit* m, const void* tokens_in, const void* text, int32_t step_index, void* tokens_out,
+                                void* stream) {
+  DK_REQUIRE(m && m->prepared && m->mod_ready, "prepare + cache_modulation_params must precede forward");
+  DK_REQUIRE(step_index >= 0 && step_index < m->n_t, "step index out of range");
+  hipStream_t st = S_(stream);
+  MmditCallScope scope(m);
+  const dk_mmdit_config& c = m->cfg;
+  const int h = m->h(), B = m->B, S = m->S, S_t = m->S_t, S_i = m->S_i, F = m->F();
+  const bf16_t* mod_step = m->MOD + (size_t)step_index * B * m->mod_rows() * h;
+
+  // context_embedder (mmdit.py:195): text rows of the joint stream -- recomputed from `text`, or copied from the
+  // step-invariant result of dk_mmdit_cache_context when `text` is null
+  if (text != nullptr) {
+    const int T = c.token_level_text_embed_dim;  // (no split workspace)
+    DK_TRY(dk_launch_gemm(Linear(dense((const bf16_t*)text, T), m->ctx_w, m->ctx_b, m->txt(m->X, h), B * S_t, h, T, DK_EPI_BIAS), st));
+  } else {
+    DK_REQUIRE(m->ctx_ready, "forward without text needs dk_mmdit_cache_context first");
+    DK_CHECK_HIP(hipMemcpy2DAsync(m->X, (size_t)S * h * 2, m->CTXE, (size_t)S_t * h * 2, (size_t)S_t * h * 2, B, hipMemcpyDeviceToDevice, st));
+  }
+  // x_embedder (+ learned positional embedding) (mmdit.py:197-206): image rows
+  // (no split workspace; the positional rows repeat per image: one segment of S_i rows, stride 0)
+  DK_TRY(dk_launch_gemm(Linear(dense((const bf16_t*)tokens_in, F), m->xemb_w, m->xemb_b, m->img(m->X, h), B * S_i, h, F,
+                               c.use_pos_embed ? DK_EPI_RES : DK_EPI_BIAS)
+                            .gate_res(nullptr, 0, 0, Rows{c.use_pos_embed ? m->POS : nullptr, h, S_i, 0}),
+                        st));
+  const int n_blocks = c.depth_multimodal + c.depth_unified;
+  DK_TRY(mmdit_blocks(m, mod_step, 0, n_blocks, st));
+  return mmdit_final_layer(m, mod_step, (bf16_t*)tokens_out, st);
+}
+
+// Teacher-forced block range (include/dk_hip.h): x_in -> m->X, blocks [first, first + count), m->X -> x_out
+extern "C" int dk_mmdit_run_blocks(dk_mmdit* m, const void* x_in, void* x_out, int32_t step_index, int32_t first_block, int32_t n_blocks,
+                                   void* stream) {
+  DK_REQUIRE(m && m->prepared && m->mod_ready, "prepare + cache_modulation_params must precede run_blocks");
+  DK_REQUIRE(x_in && x_out, "null argument");
+  DK_REQUIRE(step_index >= 0 && step_index < m->n_t, "step index out of range");
+  const int total = m->cfg.depth_multimodal + m->cfg.depth_unified;
+  DK_REQUIRE(first_block >= 0 && n_blocks >= 1 && first_block + n_blocks <= total, "block range outside the model");
+  hipStream_t st = S_(stream);
+  MmditCallScope scope(m);
+  const size_t bytes = (size_t)m->B * m->S * m->h() * 2;
+  const bf16_t* mod_step = m->MOD + (size_t)step_index * m->B * m->mod_rows() * m->h();
+  DK_CHECK_HIP(hipMemcpyAsync(m->X, x_in, bytes, hipMemcpyDeviceToDevice, st));
+  DK_TRY(mmdit_blocks(m, mod_step, first_block, n_blocks, st));
+  DK_CHECK_HIP(hipMemcpyAsync(x_out, m->X, bytes, hipMemcpyDeviceToDevice, st));
+  return 0;
+}
+
+extern "C" const void* dk_mmdit_debug_buffer(const dk_mmdit* m, int32_t which) {
+  if (!m || !m->prepared) return nullptr;
+  return which == 0 ? (const void*)m->X : which == 1 ? (const void*)m->MOD : nullptr;
+}
+

@@ -3,7 +3,7 @@
     cd /tmp && rocprofv3 --kernel-trace -d <out> -o vae --output-format csv -- python scripts/vae_decode_bench.py     (N=3 is enough)
     python scripts/vae_stage_table.py <out>            -> markdown on stdout (profiles/r05_vae_by_stage.md)
 
-The decoder's launch order is fixed (vae.py:336-401; diffusionkit_amd/csrc/engine.hip: dk_vae_decode): conv_in, mid resnet, mid attention,
+The decoder's launch order is fixed (vae.py:336-401; diffusionkit_amd/csrc/vae_engine.hip: dk_vae_decode): conv_in, mid resnet, mid attention,
 mid resnet, then the up blocks from the deepest (3 resnets = 6 convs each; an upsampling conv behind all but the last), conv_out.  The
 fused stages run dk_conv_halo_kernel<128> (GroupNorm-apply + SiLU on the way into the LDS halo tile; the 1x1 shortcut of a
 channel-changing resnet rides in its conv2 as extra K-tiles) or, with >= 256 output channels where one image fills the CUs,

@@ -171,6 +171,76 @@ def test_tune_keys_and_workspace_sizes():
     assert lib.dk_attention_set_workspace(None, 0) == 0
 
 
+def _mmdit_handle(lib, cfg):
+    """a handle whose config is filled the way MMDiTEngine fills it (the fields the workspace layout reads)"""
+    from diffusionkit_amd.config import PositionalEncoding
+    c = _lib.dk_mmdit_config()
+    c.num_heads, c.depth_multimodal, c.depth_unified = cfg.num_heads, cfg.depth_multimodal, cfg.depth_unified
+    c.hidden_size, c.mlp_ratio = cfg.hidden_size, cfg.mlp_ratio
+    c.vae_latent_dim, c.patch_size = cfg.vae_latent_dim, cfg.patch_size
+    c.use_qk_norm = int(cfg.use_qk_norm)
+    c.use_rope = int(cfg.pos_embed_type == PositionalEncoding.PreSDPARope)
+    axes = list(cfg.rope_axes_dim or ())
+    for i, a in enumerate(axes):
+        c.rope_axes_dim[i] = a
+    c.n_rope_axes, c.rope_theta = len(axes), cfg.rope_theta
+    c.use_pos_embed = int(cfg.pos_embed_type == PositionalEncoding.LearnedInputEmbedding)
+    c.max_latent_resolution = cfg.max_latent_resolution
+    c.pooled_text_embed_dim, c.token_level_text_embed_dim = cfg.pooled_text_embed_dim, cfg.token_level_text_embed_dim
+    c.frequency_embed_dim, c.max_period = cfg.frequency_embed_dim, cfg.max_period
+    c.layer_norm_eps = cfg.layer_norm_eps
+    c.guidance_embed = int(cfg.guidance_embed)
+    c.fp8_linears = int(cfg.weight_dtype == "fp8_e4m3")
+    c.fp8_bf16_double_blocks = int(cfg.fp8_bf16_double_blocks) if c.fp8_linears else 0
+    h = ctypes.c_void_p()
+    assert lib.dk_mmdit_create(ctypes.byref(c), ctypes.byref(h)) == 0, lib.dk_last_error()
+    return h
+
+
+def _vae_handle(lib, cfg):
+    c = _lib.dk_vae_config()
+    c.in_channels, c.out_channels = cfg.in_channels, cfg.out_channels
+    for i, ch in enumerate(cfg.block_out_channels):
+        c.block_out_channels[i] = ch
+    c.n_blocks = len(cfg.block_out_channels)
+    c.layers_per_block, c.resnet_groups = cfg.layers_per_block, cfg.resnet_groups
+    c.group_norm_eps = cfg.group_norm_eps
+    h = ctypes.c_void_p()
+    assert lib.dk_vae_create(ctypes.byref(c), ctypes.byref(h)) == 0, lib.dk_last_error()
+    return h
+
+
+def test_workspace_sizes_are_pinned():
+    """The workspace layout of the three engines is observable through its size: a reordered, resized or dropped buffer of mmdit_carve /
+    vae_carve moves one of these numbers (every buffer starts on a 256-byte boundary, so the order matters too)."""
+    from diffusionkit_amd.config import FLUX_DEV, SD3_8b, VAEDecoderConfig, VAEEncoderConfig, fp8_config, tiny_vae_encoder
+    lib = _lib.load()
+    mmdit = [(tiny_flux(), (1, 8, 8, 16, 3), 136310272),
+             (tiny_sd3(), (2, 8, 8, 16, 3), 67543040),
+             (FLUX_SCHNELL, (1, 128, 128, 256, 4), 443075072),
+             (fp8_config(FLUX_DEV), (2, 104, 104, 512, 50), 900880384),  # precision policy, ragged: 2 x 2704 image tokens
+             (fp8_config(FLUX_DEV, "speed"), (1, 128, 128, 512, 50), 522754048),
+             (SD3_2b, (2, 128, 128, 589, 50), 459673088),
+             (SD3_8b, (2, 64, 64, 589, 28), 359390464)]
+    for cfg, args, want in mmdit:
+        h = _mmdit_handle(lib, cfg)
+        got = lib.dk_mmdit_workspace_bytes(h, *args)
+        lib.dk_mmdit_destroy(h)
+        assert got == want, (args, got, want)
+    vae = [(lib.dk_vae_workspace_bytes, tiny_vae(), (1, 8, 8), 70081280),
+           (lib.dk_vae_workspace_bytes, tiny_vae(), (2, 6, 10), 72705536),
+           (lib.dk_vae_workspace_bytes, VAEDecoderConfig(), (1, 128, 128), 2821731072),
+           (lib.dk_vae_workspace_bytes, VAEDecoderConfig(), (2, 64, 64), 1444434944),
+           (lib.dk_vae_encoder_workspace_bytes, tiny_vae_encoder(), (1, 64, 64), 70597376),
+           (lib.dk_vae_encoder_workspace_bytes, tiny_vae_encoder(), (2, 128, 64), 80520192),
+           (lib.dk_vae_encoder_workspace_bytes, VAEEncoderConfig(), (1, 1024, 1024), 1611674368)]
+    for fn, cfg, args, want in vae:
+        h = _vae_handle(lib, cfg)
+        got = fn(h, *args)
+        lib.dk_vae_destroy(h)
+        assert got == want, (args, got, want)
+
+
 def test_bench_cpu_sample_keeps_the_workload_width():
     """bench.py's bounded CPU sample (`cpu_sample_config`) is the workload's model with 1/f of its blocks: same width and head size
     (SD3 derives its width from the depth, 64 x depth_multimodal -- the sample must not shrink it), block ratio kept; and

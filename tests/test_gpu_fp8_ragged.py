@@ -17,7 +17,7 @@ import torch
 
 from diffusionkit_amd import ops
 from diffusionkit_amd._lib import DK_EPI_BIAS, DK_EPI_BIAS_GELU, DK_EPI_GATE_RES
-from diffusionkit_amd.config import tiny_flux
+from diffusionkit_amd.config import tiny_flux, tiny_sd3
 from diffusionkit_amd.weights import dequantize_weight_e4m3, quantize_weight_e4m3
 from tests import _fp8 as f8
 from tests._util import BF, TOL_SINGLE_OP, bf16r, psnr, randn, rel_l2
@@ -199,3 +199,42 @@ def test_attention_mx8_copy_ragged_rows(dev, mode):
     assert bool((o8b[M:] == 0xAB).all()), "rows behind B * S were written"
     if mode == 9:
         assert bool((out == SENTINEL).all()), "O written although the kernel owns the MX-fp8 copy"
+
+
+def _splits(n, nb):
+    """chained splits of [0, n): in two at every interior boundary (the policy boundary nb among them) and into single blocks"""
+    out = [[(0, k), (k, n - k)] for k in range(1, n)]
+    out.append([(i, 1) for i in range(n)])
+    assert nb == 0 or [(0, nb), (nb, n - nb)] in out
+    return out
+
+
+_T22 = tiny_flux(depth_multimodal=2, depth_unified=2, heads=2)
+# (config, B, latent h, latent w, text length): fp8 with the first double block in bf16 at aligned and at ragged (2 x 360) image token counts, the
+# bf16 path of FLUX, and SD3 (its last double block skips the text stream's post-attention half)
+COMPOSE_CASES = [(replace(_T22, weight_dtype="fp8_e4m3", fp8_bf16_double_blocks=1), 1, 32, 32, 128),
+                 (replace(_T22, weight_dtype="fp8_e4m3", fp8_bf16_double_blocks=1), 2, 40, 36, 128),
+                 (_T22, 2, 8, 8, 16),
+                 (tiny_sd3(), 2, 8, 8, 16)]
+
+
+@pytest.mark.parametrize("cfg,B,Hl,Wl,S_t", COMPOSE_CASES, ids=["fp8-policy", "fp8-policy-ragged", "flux-bf16", "sd3-bf16"])
+def test_block_ranges_compose(dev, cfg, B, Hl, Wl, S_t):
+    """run_blocks over [0, n) is bit for bit every chain of run_blocks over the parts of a split of [0, n): a block's launches do not depend on
+    the range it is issued in, on either side of the precision-policy boundary or across it"""
+    from diffusionkit_amd.engine import MMDiTEngine
+    from diffusionkit_amd.weights import pack_mmdit, synth_mmdit_weights
+    eng = MMDiTEngine(cfg, pack_mmdit(cfg, synth_mmdit_weights(cfg, seed=1234), dev))
+    eng.prepare(B, (Hl, Wl), S_t, 3)
+    eng.cache_modulation_params(randn(B, cfg.pooled_text_embed_dim, seed=4).to(dev), [1000.0, 752.0, 500.0])
+    n = cfg.depth_multimodal + cfg.depth_unified
+    nb = cfg.fp8_bf16_double_blocks if cfg.weight_dtype == "fp8_e4m3" else 0
+    S = S_t + (Hl // cfg.patch_size) * (Wl // cfg.patch_size)
+    x = randn(B, S, cfg.hidden_size, seed=840).to(dev, BF)
+    whole = eng.run_blocks(x, 1, 0, n)
+    assert bool(torch.isfinite(whole.float()).all()) and not torch.equal(whole, x)
+    for split in _splits(n, nb):
+        y = x
+        for first, count in split:
+            y = eng.run_blocks(y, 1, first, count)
+        assert torch.equal(y, whole), f"blocks [0, {n}) differ from the chain {split}"
