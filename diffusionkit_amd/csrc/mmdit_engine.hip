@@ -729,6 +729,6 @@ extern "C" int dk_mmdit_run_blocks(dk_mmdit* m, const void* x_in, void* x_out, i
 
 extern "C" const void* dk_mmdit_debug_buffer(const dk_mmdit* m, int32_t which) {
   if (!m || !m->prepared) return nullptr;
-  return which == 0 ? (const void*)m->X : which == 1 ? (const void*)m->MOD : nullptr;
+  return which == 0 ? (const void*)m->X : which == 1 ? (const void*)m->MOD : which == 2 ? (const void*)m->GWS : nullptr;
 }
 

@@ -501,7 +501,8 @@ int dk_mmdit_forward(dk_mmdit* m, const void* tokens_in, const void* text, int32
 int dk_mmdit_run_blocks(dk_mmdit* m, const void* x_in, void* x_out, int32_t step_index, int32_t first_block,
                         int32_t n_blocks, void* stream);
 /* read-only view of an internal buffer for parity taps: 0 = joint residual stream [B,S,h],
- * 1 = modulation table [n*B, rows*h] */
+ * 1 = modulation table [n*B, rows*h], 2 = base of the engine's GEMM K-split workspace (dk_gemm_workspace_bytes() bytes:
+ * the fp32 slabs, then the 4096-byte flag region, which is zero between launches) */
 const void* dk_mmdit_debug_buffer(const dk_mmdit* m, int32_t which);
 
 typedef struct dk_vae_config {
