@@ -13,7 +13,7 @@ from ._lib import DkHipError  # noqa: F401
 def __getattr__(name):
     # pipeline classes import torch lazily so that `import diffusionkit_amd` stays cheap
     if name in ("DiffusionPipeline", "FluxPipeline", "CFGDenoiser", "sample_euler", "LatentFormat",
-                "SD3LatentFormat", "FluxLatentFormat", "to_d", "append_dims"):
+                "SD3LatentFormat", "FluxLatentFormat", "to_d", "append_dims", "read_mask"):
         from . import pipeline
         return getattr(pipeline, name)
     if name in ("MMDiTEngine", "VAEDecoderEngine"):

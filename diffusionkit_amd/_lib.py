@@ -177,6 +177,12 @@ SIGNATURES = {
     "dk_timestep_embedding_bf16": (_i32, [_vp, _i32, _i32, _f32, _i32, _vp, _vp]),
     "dk_latent_to_tokens": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "dk_euler_cfg_step": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _vp]),
+    # inpainting: the masked step (bf16 / fp16 tokens), the mask's pixels -> latent cells, the paste-back of the kept pixels
+    "dk_euler_cfg_step_masked": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _vp, _vp, _vp, _i32, _vp]),
+    "dk_euler_cfg_step_masked_f16": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _vp, _vp, _vp, _i32,
+                                            _vp]),
+    "dk_mask_to_latent_f32": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "dk_image_composite_u8": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "dk_affine_f32": (_i32, [_vp, _vp, _i64, _f32, _f32, _vp]),
     "dk_groupnorm_scratch_floats": (_sz, [_i32, _i32]),
     "dk_groupnorm_bf16": (_i32, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _f32, _i32, _vp, _vp]),

@@ -52,6 +52,10 @@ def build_parser(model_versions: Sequence[str]) -> argparse.ArgumentParser:
     p.add_argument("--benchmark-mode", action="store_true", help="Warm the kernels up with a one-step run first.")
     p.add_argument("--denoise", type=float, default=0.0,
                    help="Denoising factor when an input image is provided. (between 0.0 and 1.0)")
+    p.add_argument("--mask-path", type=str, default=None,
+                   help="Inpainting mask for --image-path (first channel; 255 = repaint, 0 = keep; resized to the image with NEAREST).")
+    p.add_argument("--no-composite", action="store_true",
+                   help="With --mask-path: do not paste the kept pixels of the input image back over the decoded image.")
     p.add_argument("--local-ckpt", default=None, type=str, help="Path to the local mmdit checkpoint.")
     p.add_argument("--ckpt", action="append", default=[], metavar="KEY=PATH",
                    help="Further local checkpoint parts (vae_decoder, vae_encoder, clip_l, clip_g, t5, t5_tokenizer, "
@@ -108,6 +112,12 @@ def resolve(args) -> dict:
     if getattr(args, "vae_dtype", None) is not None:  # (a key only when the flag is given)
         from .config import validate_vae_dtype
         r["vae_dtype"] = validate_vae_dtype(args.vae_dtype)
+    if getattr(args, "mask_path", None) is not None:  # (keys only when the flags are given)
+        if args.image_path is None:
+            raise ValueError("--mask-path needs --image-path")
+        r["mask_path"] = args.mask_path
+    if getattr(args, "no_composite", False):
+        r["composite"] = False
     return r
 
 
@@ -140,7 +150,8 @@ def main(argv: Optional[Sequence[str]] = None, pipeline_overrides: Optional[dict
         logger.info("Benchmark mode: Warming up the models done.")
     image, log = sd.generate_image(args.prompt, cfg_weight=r["cfg"], num_steps=args.steps, seed=args.seed,
                                    negative_text=args.negative_prompt, latent_size=latent_size, image_path=args.image_path,
-                                   denoise=args.denoise, verbose=args.verbose)
+                                   denoise=args.denoise, verbose=args.verbose, mask_path=r.get("mask_path"),
+                                   composite=r.get("composite", True))
     if log["text_encoding"].get("synthetic"):
         logger.warning("no text-encoder checkpoints were named (--ckpt clip_l=... t5=...): the conditioning is synthetic")
     image.save(args.output_path)

@@ -367,6 +367,41 @@ extern "C" int dk_euler_cfg_step_f16(float* x, const void* model_out, int32_t ld
   return dk_euler_cfg_step(x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight, stream);
 }
 
+extern "C" int dk_euler_cfg_step_masked(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on,
+                                        int32_t Hl, int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma,
+                                        float sigma_next, float cfg_weight, const float* x_orig, const float* noise, const float* mask,
+                                        int32_t mask_per_image, void* stream) {
+  DK_REQUIRE(sigma != 0.0f, "sigma must be non-zero");
+  DK_REQUIRE(p > 0 && Hl % p == 0 && Wl % p == 0, "latent size must be divisible by the patch size");
+  DK_REQUIRE(x && model_out && tokens && x_orig && noise && mask, "null argument");
+  DK_REQUIRE(n_img > 0, "n_img must be positive");
+  return DK_EL(dk_launch_euler_step_masked)(x, (const bf16_t*)model_out, ld_out, (bf16_t*)tokens, n_img, cfg_on, Hl, Wl, C, p,
+                                            reshape_order, sigma, sigma_next, cfg_weight, x_orig, noise, mask, mask_per_image != 0,
+                                            S_(stream));
+}
+extern "C" int dk_euler_cfg_step_masked_f16(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on,
+                                            int32_t Hl, int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma,
+                                            float sigma_next, float cfg_weight, const float* x_orig, const float* noise,
+                                            const float* mask, int32_t mask_per_image, void* stream) {
+  ElemScope f16(DK_DTYPE_F16);
+  return dk_euler_cfg_step_masked(x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight,
+                                  x_orig, noise, mask, mask_per_image, stream);
+}
+
+extern "C" int dk_mask_to_latent_f32(const uint8_t* mask, float* out, int32_t n_mask, int32_t H, int32_t W, int32_t f, void* stream) {
+  DK_REQUIRE(mask && out, "null argument");
+  DK_REQUIRE(n_mask > 0, "n_mask must be positive");
+  DK_REQUIRE(f > 0 && f <= 64 && H > 0 && W > 0 && H % f == 0 && W % f == 0, "mask size must be divisible by the factor (1..64)");
+  return dk_launch_mask_to_latent(mask, out, n_mask, H, W, f, S_(stream));
+}
+
+extern "C" int dk_image_composite_u8(const uint8_t* dec, const uint8_t* orig, const uint8_t* mask, uint8_t* out, int32_t B, int32_t H,
+                                     int32_t W, int32_t orig_per_image, int32_t mask_per_image, void* stream) {
+  DK_REQUIRE(dec && orig && mask && out, "null argument");
+  DK_REQUIRE(B > 0 && H > 0 && W > 0, "B, H and W must be positive");
+  return dk_launch_image_composite_u8(dec, orig, mask, out, B, H, W, orig_per_image != 0, mask_per_image != 0, S_(stream));
+}
+
 extern "C" int dk_affine_f32(const float* x, float* y, int64_t n, float a, float b, void* stream) {
   return dk_launch_affine_f32(x, y, (long)n, a, b, S_(stream));
 }

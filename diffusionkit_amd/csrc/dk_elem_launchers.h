@@ -32,3 +32,9 @@ int dk_launch_latent_to_tokens(const float* x, bf16_t* tok, int n_img, int dup, 
 int dk_launch_euler_step(float* x, const bf16_t* model_out, int ld_out, bf16_t* tok, int n_img, int cfg_on,
                          int Hl, int Wl, int C, int p, int reshape_order, float sigma, float sigma_next,
                          float cfg_weight, hipStream_t stream);
+// ... followed by the inpainting blend x = m * x_new + (1 - m) * (sigma_next * noise + (1 - sigma_next) * x_orig); x_orig, noise: f32 like x,
+// mask: f32 [n_img or 1, Hl, Wl]
+int dk_launch_euler_step_masked(float* x, const bf16_t* model_out, int ld_out, bf16_t* tok, int n_img, int cfg_on,
+                                int Hl, int Wl, int C, int p, int reshape_order, float sigma, float sigma_next,
+                                float cfg_weight, const float* x_orig, const float* noise, const float* mask,
+                                int mask_per_image, hipStream_t stream);

@@ -262,6 +262,10 @@ int dk_launch_rope_table(float* table, int S_txt, int gh, int gw, const int* axe
                          hipStream_t stream);
 int dk_launch_f32_to_bf16(const float* x, bf16_t* y, long n, hipStream_t stream);
 int dk_launch_affine_f32(const float* x, float* y, long n, float a, float b, hipStream_t stream);
+// inpainting: mask u8 [n_mask, H, W] -> f32 [n_mask, H / f, W / f] (box sum / (f * f * 255)); paste-back of the kept pixels
+int dk_launch_mask_to_latent(const unsigned char* mask, float* out, int n_mask, int H, int W, int f, hipStream_t stream);
+int dk_launch_image_composite_u8(const unsigned char* dec, const unsigned char* orig, const unsigned char* mask, unsigned char* out, int B,
+                                 int H, int W, int orig_per_image, int mask_per_image, hipStream_t stream);
 
 // ---- launchers per element type ------------------------------------------------------------------------------
 #include "dk_elem_launchers.h"

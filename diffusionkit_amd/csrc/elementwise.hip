@@ -358,6 +358,48 @@ int dk_launch_affine_f32(const float* x, float* y, long n, float a, float b, hip
   DK_CHECK_HIP(hipGetLastError());
   return 0;
 }
+
+// Inpainting mask, pixels -> latent cells: u8 [n_mask, H, W] (255 = repaint, 0 = keep) -> f32 [n_mask, H / f, W / f], the integer sum of
+// an f x f block over f * f * 255 by a true division: an all-0 block is exactly 0.0f, an all-255 block exactly 1.0f.
+__global__ void dk_mask_to_latent_kernel(const unsigned char* mask, float* out, int n_mask, int H, int W, int f) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int Hl = H / f, Wl = W / f;
+  if (i >= (long)n_mask * Hl * Wl) return;
+  const int xx = (int)(i % Wl), yy = (int)(i / Wl % Hl), n = (int)(i / ((long)Hl * Wl));
+  const unsigned char* blk = mask + ((size_t)n * H + (size_t)yy * f) * W + (size_t)xx * f;
+  int sum = 0;
+  for (int r = 0; r < f; ++r)
+    for (int c = 0; c < f; ++c) sum += blk[(size_t)r * W + c];
+  out[i] = (float)sum / (float)(f * f * 255);
+}
+int dk_launch_mask_to_latent(const unsigned char* mask, float* out, int n_mask, int H, int W, int f, hipStream_t stream) {
+  const long n = (long)n_mask * (H / f) * (W / f);
+  hipLaunchKernelGGL(dk_mask_to_latent_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, mask, out, n_mask, H, W, f);
+  DK_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// Inpainting paste-back in pixel space: out = (uint8)(w * dec + (1 - w) * orig + 0.5f), w = mask / 255.0f, one thread per pixel.
+// w == 1 gives the decoder's byte, w == 0 the original's.  Contraction is off so that the bytes are those of the plain fp32 expression
+// (a fused multiply-add rounds once less and can land on the other side of a truncation boundary).
+__global__ void dk_image_composite_u8_kernel(const unsigned char* dec, const unsigned char* orig, const unsigned char* mask,
+                                             unsigned char* out, int B, long HW, int orig_per_image, int mask_per_image) {
+#pragma clang fp contract(off)
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= HW * B) return;
+  const long pix = i % HW;
+  const float w = (float)mask[mask_per_image ? i : pix] / 255.0f;
+  const unsigned char* o = orig + (orig_per_image ? i : pix) * 3;
+  for (int c = 0; c < 3; ++c) out[i * 3 + c] = (unsigned char)(w * (float)dec[i * 3 + c] + (1.0f - w) * (float)o[c] + 0.5f);
+}
+int dk_launch_image_composite_u8(const unsigned char* dec, const unsigned char* orig, const unsigned char* mask, unsigned char* out, int B,
+                                 int H, int W, int orig_per_image, int mask_per_image, hipStream_t stream) {
+  const long HW = (long)H * W;
+  hipLaunchKernelGGL(dk_image_composite_u8_kernel, dim3((unsigned)((HW * B + 255) / 256)), dim3(256), 0, stream, dec, orig, mask, out, B,
+                     HW, orig_per_image, mask_per_image);
+  DK_CHECK_HIP(hipGetLastError());
+  return 0;
+}
 #endif  // !DK_ELEM_F16
 
 // ---------------------------------------------------------------------------------------------
@@ -398,9 +440,17 @@ int dk_launch_latent_to_tokens(const float* x, bf16_t* tok, int n_img, int dup, 
 // reference: CFGDenoiser.__call__ python/src/diffusionkit/mlx/__init__.py:691-719
 // (x_bf16 - out*sigma in fp32; neg + w*(text - neg)), to_d :756, sample_euler :778-781;
 // unpack/unpatchify mmdit.py:304-321, 975-988.  x stays fp32 (quirk Q6).
+// MASKED (inpainting, no reference counterpart): the updated latent is blended with the known region re-noised to sigma_next,
+//   known = sigma_next * noise + (1 - sigma_next) * x_orig,  x = m * x_new + (1 - m) * known,
+// m = mask[img or 0][yy][xx] in [0, 1], the same for the C channels of a cell.  The two-product form is exact at both ends whatever
+// is contracted into FMAs: m == 1 gives x_new, m == 0 gives known, and sigma_next == 0 makes known = x_orig, bit for bit for finite inputs -- but
+// for the sign of a zero: the vanishing product is +-0, and -0 + (+0) = +0, so a value of -0.0f at an exact end may come out as +0.0f.
+// The tokens are the rounding of the blended value.  MASKED = false: the mask operands are not read, same arithmetic as before.
 // ---------------------------------------------------------------------------------------------
+template <bool MASKED>
 __global__ void dk_euler_step_kernel(float* x, const bf16_t* model_out, int ld_out, bf16_t* tok, int n_img, int cfg_on, int Hl,
-                                     int Wl, int C, int p, int reshape_order, float sigma, float sigma_next, float cfg_weight) {
+                                     int Wl, int C, int p, int reshape_order, float sigma, float sigma_next, float cfg_weight,
+                                     const float* x_orig, const float* noise, const float* mask, int mask_per_image) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long per_img = (long)Hl * Wl * C;
   if (i >= per_img * n_img) return;
@@ -422,7 +472,12 @@ __global__ void dk_euler_step_kernel(float* x, const bf16_t* model_out, int ld_o
     den = den_neg + cfg_weight * (den - den_neg);
   }
   const float d = (xv - den) / sigma;
-  const float xn = xv + d * (sigma_next - sigma);
+  float xn = xv + d * (sigma_next - sigma);
+  if constexpr (MASKED) {
+    const float m = mask[(mask_per_image ? (long)img * Hl * Wl : 0) + (long)yy * Wl + xx];
+    const float known = sigma_next * noise[i] + (1.0f - sigma_next) * x_orig[i];
+    xn = m * xn + (1.0f - m) * known;
+  }
   x[i] = xn;
   const bf16_t nb = from_f32(xn);
   tok[((size_t)img * S_i + t) * F + f] = nb;
@@ -431,8 +486,17 @@ __global__ void dk_euler_step_kernel(float* x, const bf16_t* model_out, int ld_o
 int dk_launch_euler_step(float* x, const bf16_t* model_out, int ld_out, bf16_t* tok, int n_img, int cfg_on, int Hl, int Wl, int C,
                          int p, int reshape_order, float sigma, float sigma_next, float cfg_weight, hipStream_t stream) {
   const long n = (long)n_img * Hl * Wl * C;
-  hipLaunchKernelGGL(dk_euler_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, x, model_out, ld_out, tok,
-                     n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight);
+  hipLaunchKernelGGL(dk_euler_step_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, x, model_out, ld_out, tok,
+                     n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight, nullptr, nullptr, nullptr, 0);
+  DK_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+int dk_launch_euler_step_masked(float* x, const bf16_t* model_out, int ld_out, bf16_t* tok, int n_img, int cfg_on, int Hl, int Wl,
+                                int C, int p, int reshape_order, float sigma, float sigma_next, float cfg_weight, const float* x_orig,
+                                const float* noise, const float* mask, int mask_per_image, hipStream_t stream) {
+  const long n = (long)n_img * Hl * Wl * C;
+  hipLaunchKernelGGL(dk_euler_step_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, x, model_out, ld_out, tok,
+                     n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight, x_orig, noise, mask, mask_per_image);
   DK_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -368,6 +368,66 @@ def euler_cfg_step(x: Tensor, model_out: Tensor, tokens: Tensor, n_img: int, cfg
                                           p, reshape_order, float(sigma), float(sigma_next), float(cfg_weight), _stream()), name)
 
 
+def _mask_per_image(n: int, per_image: int, n_img: int, what: str) -> int:
+    """0: one mask of ``per_image`` elements for all images, 1: one per image"""
+    if n == per_image:
+        return 0
+    if n == per_image * n_img:
+        return 1
+    raise ValueError(f"{what}: the mask holds {n} elements, expected {per_image} (shared) or {n_img} x {per_image} (per image)")
+
+
+def euler_cfg_step_masked(x: Tensor, model_out: Tensor, tokens: Tensor, n_img: int, cfg_on: bool, p: int, reshape_order: int, sigma: float,
+                          sigma_next: float, cfg_weight: float, x_orig: Tensor, noise: Tensor, mask: Tensor) -> None:
+    """dk_euler_cfg_step_masked / _f16 by the dtype of ``model_out``: ``euler_cfg_step``, then x = m * x_new + (1 - m) * (sigma_next * noise +
+    (1 - sigma_next) * x_orig) in the same launch.  ``x_orig``, ``noise``: f32 like x; ``mask``: f32 [Hl, Wl] (shared) or [n_img, Hl, Wl]."""
+    name = "dk_euler_cfg_step_masked" + ("" if _elem(model_out.dtype, "euler_cfg_step_masked") == "bf16" else "_f16")
+    _require_cuda(x, "x", torch.float32)
+    _require_cuda(model_out, "model_out")
+    _require_cuda(tokens, "tokens", model_out.dtype)
+    for n, t in (("x_orig", x_orig), ("noise", noise), ("mask", mask)):
+        _require_cuda(t, n, torch.float32)
+    _, hl, wl, c = x.shape
+    if x_orig.shape != x.shape or noise.shape != x.shape:
+        raise ValueError(f"x_orig {tuple(x_orig.shape)} and noise {tuple(noise.shape)} must have the latent's shape {tuple(x.shape)}")
+    if tuple(mask.shape[-2:]) != (hl, wl):
+        raise ValueError(f"mask {tuple(mask.shape)} does not end in the latent size {(hl, wl)}")
+    per_image = _mask_per_image(mask.numel(), hl * wl, n_img, "euler_cfg_step_masked")
+    _lib.check(getattr(_lib.load(), name)(x.data_ptr(), model_out.data_ptr(), model_out.shape[-1], tokens.data_ptr(), n_img, int(cfg_on), hl, wl, c,
+                                          p, reshape_order, float(sigma), float(sigma_next), float(cfg_weight), x_orig.data_ptr(),
+                                          noise.data_ptr(), mask.data_ptr(), per_image, _stream()), name)
+
+
+def mask_to_latent(mask: Tensor, factor: int = 8) -> Tensor:
+    """dk_mask_to_latent_f32: uint8 [n_mask, H, W] (or [H, W]) -> f32 [n_mask, H / factor, W / factor], box sum / (factor^2 * 255)."""
+    _require_cuda(mask, "mask", torch.uint8)
+    if mask.dim() not in (2, 3):
+        raise ValueError(f"mask must be [H, W] or [n_mask, H, W], got {tuple(mask.shape)}")
+    H, W = mask.shape[-2:]
+    n = mask.shape[0] if mask.dim() == 3 else 1
+    out = torch.empty(n, H // factor, W // factor, dtype=torch.float32, device=mask.device)
+    _lib.check(_lib.load().dk_mask_to_latent_f32(mask.data_ptr(), out.data_ptr(), n, H, W, int(factor), _stream()), "dk_mask_to_latent_f32")
+    return out
+
+
+def image_composite(dec: Tensor, orig: Tensor, mask: Tensor) -> Tensor:
+    """dk_image_composite_u8: dec uint8 [B, H, W, 3], orig uint8 [H, W, 3] / [1 or B, H, W, 3], mask uint8 [H, W] / [1 or B, H, W] ->
+    uint8 [B, H, W, 3]: the decoder's bytes where mask == 255, the original's where mask == 0."""
+    for n, t in (("dec", dec), ("orig", orig), ("mask", mask)):
+        _require_cuda(t, n, torch.uint8)
+    if dec.dim() != 4 or dec.shape[-1] != 3:
+        raise ValueError(f"dec must be [B, H, W, 3], got {tuple(dec.shape)}")
+    B, H, W, _ = dec.shape
+    if tuple(orig.shape[-3:]) != (H, W, 3) or tuple(mask.shape[-2:]) != (H, W):
+        raise ValueError(f"orig {tuple(orig.shape)} / mask {tuple(mask.shape)} do not match the image {(H, W, 3)}")
+    orig_pi = _mask_per_image(orig.numel(), H * W * 3, B, "image_composite (orig)")
+    mask_pi = _mask_per_image(mask.numel(), H * W, B, "image_composite")
+    out = torch.empty_like(dec)
+    _lib.check(_lib.load().dk_image_composite_u8(dec.data_ptr(), orig.data_ptr(), mask.data_ptr(), out.data_ptr(), B, H, W, orig_pi, mask_pi,
+                                                 _stream()), "dk_image_composite_u8")
+    return out
+
+
 def groupnorm(x: Tensor, gamma: Tensor, beta: Tensor, groups: int, eps: float, silu: bool) -> Tensor:
     """x: NHWC [B,H,W,C], bf16 or float16 (gamma / beta in the same type)."""
     lib = _lib.load()

@@ -3,10 +3,15 @@
 Signatures, defaults, return values and error behaviour follow
 python/src/diffusionkit/mlx/__init__.py:64-594 (DiffusionPipeline), :597-671 (FluxPipeline),
 :674-719 (CFGDenoiser), :722-747 (LatentFormat), :750-788 (append_dims, to_d, sample_euler).
-Only the denoising hot path (step loop + MMDiT + latent-decode VAE) is implemented; the text
-encoders (CLIP / T5), img2img and checkpoint download are outside this build's scope
- -- ``encode_text`` uses a pluggable encoder and otherwise deterministic
-synthetic conditioning so that ``generate_image`` stays callable end to end.
+Text-to-image and img2img (``image_path=``, ``denoise=``: VAE encoder, posterior sample per seed, truncated schedule) run as in the
+reference; the text encoders (CLIP / T5, diffusionkit_amd.text) are built from the checkpoints ``local_ckpt`` names, and without
+them ``encode_text`` falls back to deterministic synthetic conditioning so that ``generate_image`` stays callable end to end.
+Checkpoint download is not offered (no hub access).
+
+Inpainting (``mask_path=``, keyword-only, no reference counterpart) is latent blending on top of img2img: the mask (255 = repaint,
+0 = keep) becomes one weight per latent cell, every Euler step re-imposes the known region re-noised to the step's sigma inside the
+step's own launch (dk_euler_cfg_step_masked), and ``generate_image`` pastes the kept pixels of the input back over the decoded image
+(``composite=``).  Kept latent cells come out as the encoded image bit for bit, kept pixels as the input's bytes.
 
 All arithmetic runs in libdk_hip.so on the current HIP stream; numpy is used exactly where the
 reference uses it (the seeded noise draw, __init__.py:553-557) and for O(num_steps) schedule
@@ -68,6 +73,66 @@ class FluxLatentFormat(LatentFormat):
         super().__init__()
         self.scale_factor = 0.3611
         self.shift_factor = 0.1159
+
+
+def _open_image(image):
+    """a path, a PIL image or a uint8 array -> PIL image"""
+    from PIL import Image
+    if isinstance(image, np.ndarray):
+        return Image.fromarray(image)
+    if isinstance(image, Image.Image):
+        return image
+    return Image.open(image)
+
+
+def read_image_u8(image_path) -> np.ndarray:
+    """The pixels ``DiffusionPipeline.read_image`` settles on (mlx/__init__.py:536-551), as HWC uint8 RGB: sizes are cut down to a multiple
+    of 64 with a LANCZOS resize.  ``image_path`` may also be a PIL image or an HWC uint8 array.  Needs no GPU."""
+    from PIL import Image
+    img = _open_image(image_path)
+    W, H = (dim - dim % 64 for dim in (img.width, img.height))
+    if W != img.width or H != img.height:
+        logger.warning(f"Warning: image shape is not divisible by 64, downsampling to {W}x{H}")
+        img = img.resize((W, H), Image.LANCZOS)
+    arr = np.array(img)
+    if arr.ndim == 2:
+        arr = np.repeat(arr[:, :, None], 3, axis=2)
+    return arr[:, :, :3]
+
+
+def read_mask(mask, size) -> np.ndarray:
+    """Inpainting mask -> uint8 [H, W] with ``size`` = (H, W), the size ``read_image`` settled on: 255 = repaint, 0 = keep, values between
+    blend.  ``mask`` is a path, a PIL image or an array ([H, W] or [H, W, channels], uint8 or bool); only the first channel is taken, and a
+    mask of another size is resized with NEAREST, so that a {0, 255} mask stays one.  Needs no GPU."""
+    from PIL import Image
+    if isinstance(mask, np.ndarray):
+        arr = mask
+    else:
+        img = _open_image(mask)
+        if img.mode not in ("L", "RGB", "RGBA", "1"):
+            img = img.convert("L")
+        arr = np.array(img)
+    if arr.ndim == 3:
+        arr = arr[:, :, 0]
+    if arr.ndim != 2:
+        raise ValueError(f"mask must be [H, W] or [H, W, channels], got shape {arr.shape}")
+    if arr.dtype == np.bool_:
+        arr = arr.astype(np.uint8) * 255
+    if arr.dtype != np.uint8:
+        raise ValueError(f"mask must be uint8 (255 = repaint, 0 = keep) or bool, got {arr.dtype}")
+    H, W = int(size[0]), int(size[1])
+    if arr.shape != (H, W):
+        arr = np.array(Image.fromarray(np.ascontiguousarray(arr)).resize((W, H), Image.NEAREST))
+    return np.ascontiguousarray(arr)
+
+
+def _read_masks(mask, size, n_img: int) -> np.ndarray:
+    """uint8 [1, H, W] (one mask for all images) or, for a list / tuple of ``n_img`` masks, [n_img, H, W]"""
+    if isinstance(mask, (list, tuple)):
+        if len(mask) != n_img:
+            raise ValueError(f"{len(mask)} masks for {n_img} images: give one mask, or one per image")
+        return np.stack([read_mask(m, size) for m in mask], 0)
+    return read_mask(mask, size)[None]
 
 
 def _affine(x: Tensor, a: float, b: float) -> Tensor:
@@ -280,9 +345,15 @@ class DiffusionPipeline:
         seed=None,
         image_path: Optional[str] = None,
         denoise: float = 1.0,
+        *,
+        mask_path=None,
     ):
         """mlx/__init__.py:253-292.  ``seed`` may be a list: one image per seed is denoised in a
-        single batched step loop (data-parallel sharding hands each rank a list)."""
+        single batched step loop (data-parallel sharding hands each rank a list).
+        ``mask_path`` (inpainting; a path, a PIL image or an array as ``read_mask`` takes them, or a list with one per seed): repaint where the
+        mask is 255, keep ``image_path``'s content where it is 0 -- kept latent cells equal the encoded image bit for bit."""
+        if mask_path is not None and image_path is None:
+            raise ValueError("mask_path needs image_path: the mask says which part of that image to keep")
         seed = int(time.time()) if seed is None else seed
         seeds = list(seed) if isinstance(seed, (list, tuple)) else [seed]
         logger.info(f"Seed: {seeds}")
@@ -292,8 +363,8 @@ class DiffusionPipeline:
             x_T = np.repeat(x_T, len(seeds), axis=0) if len(seeds) > 1 else x_T
         else:
             # img2img (mlx/__init__.py:270-277): the encoded image, one posterior sample per seed
-            x_T = torch.cat([self.latent_format.process_in(self.encode_image_to_latents(image_path, seed=s)) for s in seeds], 0)
-            x_T = x_T.cpu().numpy()
+            x_orig = torch.cat([self.latent_format.process_in(self.encode_image_to_latents(image_path, seed=s)) for s in seeds], 0)
+            x_T = x_orig.cpu().numpy()
         noise = np.concatenate([self.get_noise(s, x_T[:1]) for s in seeds], axis=0)
         sigmas = self.get_sigmas(self.sampler, num_steps)
         sigmas = sigmas[int(num_steps * (1 - denoise)):]
@@ -302,6 +373,13 @@ class DiffusionPipeline:
             "cfg_weight": cfg_weight,
             "pooled_conditioning": pooled_conditioning,
         }
+        if mask_path is not None:
+            from . import ops
+            hl, wl = x_T.shape[1:3]
+            masks = _read_masks(mask_path, (hl * 8, wl * 8), len(seeds))
+            extra_args["mask"] = ops.mask_to_latent(torch.from_numpy(masks).to(self.device), 8)
+            extra_args["x_orig"] = x_orig
+            extra_args["noise"] = torch.from_numpy(np.ascontiguousarray(noise, dtype=np.float32)).to(self.device)
         noise_scaled = self.sampler.noise_scaling(np.float32(sigmas[0]), noise, x_T, self.max_denoise(sigmas))
         x0 = torch.from_numpy(np.ascontiguousarray(noise_scaled, dtype=np.float32)).to(self.device)
         latent, iter_time = sample_euler(CFGDenoiser(self), x0, sigmas, extra_args=extra_args)
@@ -319,8 +397,14 @@ class DiffusionPipeline:
         verbose: bool = True,
         image_path: Optional[str] = None,
         denoise: float = 1.0,
+        *,
+        mask_path=None,
+        composite: bool = True,
     ):
-        """mlx/__init__.py:294-534: returns (PIL.Image, log)."""
+        """mlx/__init__.py:294-534: returns (PIL.Image, log).  ``mask_path``: inpainting, see ``denoise_latents``; with ``composite`` the pixels
+        the mask keeps are pasted back from the input image after decoding (the VAE round trip alone does not reproduce them)."""
+        if mask_path is not None and image_path is None:
+            raise ValueError("mask_path needs image_path: the mask says which part of that image to keep")
         assert latent_size[0] % 2 == 0, f"Height must be divisible by 16 ({latent_size[0]*8}/16={latent_size[0]/2})"
         assert latent_size[1] % 2 == 0, f"Width must be divisible by 16 ({latent_size[1]*8}/16={latent_size[1]/2})"
         self.check_and_load_models()
@@ -350,7 +434,7 @@ class DiffusionPipeline:
         log["denoising"]["pre"] = mem()
         latents, iter_time = self.denoise_latents(
             conditioning, pooled_conditioning, num_steps=num_steps, cfg_weight=cfg_weight,
-            latent_size=latent_size, seed=seed, image_path=image_path, denoise=denoise)
+            latent_size=latent_size, seed=seed, image_path=image_path, denoise=denoise, mask_path=mask_path)
         torch.cuda.synchronize(dev)
         log["denoising"]["post"] = mem()
         log["peak_memory"] = max(log["peak_memory"], log["denoising"]["post"]["peak_memory"])
@@ -361,6 +445,8 @@ class DiffusionPipeline:
         t0 = time.time()
         log["decoding"]["pre"] = mem()
         _, u8, _ = self.decoder.decode(latents)
+        if mask_path is not None and composite:
+            u8 = self.composite_image(u8, image_path, mask_path)
         torch.cuda.synchronize(dev)
         log["decoding"]["post"] = mem()
         log["peak_memory"] = max(log["peak_memory"], log["decoding"]["post"]["peak_memory"])
@@ -392,22 +478,20 @@ class DiffusionPipeline:
     def read_image(self, image_path):
         """mlx/__init__.py:536-551: RGB in [-1, 1], NHWC float32 [1,H,W,3]; sizes are cut down to a
         multiple of 64 with a LANCZOS resize.  ``image_path`` may also be a PIL image or an HWC uint8 array."""
-        from PIL import Image
-        if isinstance(image_path, np.ndarray):
-            img = Image.fromarray(image_path)
-        elif isinstance(image_path, Image.Image):
-            img = image_path
-        else:
-            img = Image.open(image_path)
-        W, H = (dim - dim % 64 for dim in (img.width, img.height))
-        if W != img.width or H != img.height:
-            logger.warning(f"Warning: image shape is not divisible by 64, downsampling to {W}x{H}")
-            img = img.resize((W, H), Image.LANCZOS)
-        arr = np.array(img)
-        if arr.ndim == 2:
-            arr = np.repeat(arr[:, :, None], 3, axis=2)
-        arr = (arr[:, :, :3].astype(np.float32) / 255) * 2 - 1.0
+        arr = (read_image_u8(image_path).astype(np.float32) / 255) * 2 - 1.0
         return torch.from_numpy(np.ascontiguousarray(arr[None])).to(self.device)
+
+    def composite_image(self, u8: Tensor, image, mask) -> Tensor:
+        """Inpainting paste-back (no reference counterpart): ``u8`` = decoded images uint8 [B, H, W, 3] on the GPU (``decoder.decode`` /
+        ``decode_async``), ``image`` / ``mask`` as ``generate_image`` takes them -> uint8 [B, H, W, 3] with the input image's bytes where the
+        mask is 0, the decoder's where it is 255 and the rounded blend between."""
+        from . import ops
+        orig = read_image_u8(image)
+        if orig.shape != tuple(u8.shape[1:]):
+            raise ValueError(f"the image is {orig.shape[0]}x{orig.shape[1]} after read_image, the decoded images {u8.shape[1]}x{u8.shape[2]}")
+        masks = _read_masks(mask, orig.shape[:2], u8.shape[0])
+        return ops.image_composite(u8.contiguous(), torch.from_numpy(np.ascontiguousarray(orig)).to(u8.device),
+                                   torch.from_numpy(masks).to(u8.device))
 
     def encode_image_to_latents(self, image_path, seed):
         """mlx/__init__.py:586-594: mean + std * noise of the VAE posterior, NHWC float32 on the device."""
@@ -596,7 +680,10 @@ def _tile_conditioning(conditioning: Tensor, pooled: Tensor, n_img: int, cfg_on:
 def sample_euler(model: CFGDenoiser, x: Tensor, sigmas, extra_args=None):
     """mlx/__init__.py:761-788.  x: fp32 [n_img,h,w,16] on the GPU (updated copy is returned);
     sigmas: host float32 array.  One device synchronisation per step (the reference's
-    mx.eval(x)) provides iter_time."""
+    mx.eval(x)) provides iter_time.
+    Inpainting: ``extra_args["mask"]`` (f32 [1 or n_img, h, w], 1 = repaint) together with ``"x_orig"`` and ``"noise"`` (f32 like x: the
+    encoded image after process_in and the draw of the start state) makes every step end in the blend of dk_euler_cfg_step_masked --
+    still one launch per step."""
     extra_args = {} if extra_args is None else dict(extra_args)
     pipe = model.model
     mm = pipe.mmdit
@@ -623,13 +710,25 @@ def sample_euler(model: CFGDenoiser, x: Tensor, sigmas, extra_args=None):
     mm.cache_context(conditioning)  # context_embedder is step-invariant (the reference recomputes it in every call, mmdit.py:195)
 
     x = x.to(torch.float32).contiguous().clone()
+    mask = extra_args.get("mask")
+    if mask is not None:
+        from . import ops
+        pcfg = pipe.mmdit_config
+        mask, x_orig, noise = (t.to(pipe.device, torch.float32).contiguous() for t in (mask, extra_args["x_orig"], extra_args["noise"]))
+        if x_orig.shape != x.shape or noise.shape != x.shape or mask.shape[1:] != x.shape[1:3] or mask.shape[0] not in (1, n_img):
+            raise ValueError(f"inpainting operands do not match the latent {tuple(x.shape)}: x_orig {tuple(x_orig.shape)}, "
+                             f"noise {tuple(noise.shape)}, mask {tuple(mask.shape)}")
     tok = mm.patchify(x, dup=2 if cfg_on else 1)
     out = torch.empty_like(tok)
     iter_time = []
     for i in range(len(sigmas) - 1):
         t0 = time.perf_counter()
         mm.forward_tokens(tok, None, i, tokens_out=out)
-        _euler(pipe, x, out, tok, cfg_on, float(sigmas[i]), float(sigmas[i + 1]), cfg_weight)
+        if mask is None:
+            _euler(pipe, x, out, tok, cfg_on, float(sigmas[i]), float(sigmas[i + 1]), cfg_weight)
+        else:
+            ops.euler_cfg_step_masked(x, out, tok, n_img, cfg_on, pcfg.patch_size, int(pcfg.patchify_via_reshape), float(sigmas[i]),
+                                      float(sigmas[i + 1]), cfg_weight, x_orig, noise, mask)
         torch.cuda.synchronize(pipe.device)
         iter_time.append(round(time.perf_counter() - t0, 3))
     model.clear_cache()

@@ -350,6 +350,33 @@ int dk_euler_cfg_step(float* x, const void* model_out, int32_t ld_out, void* tok
                       int32_t cfg_on, int32_t Hl, int32_t Wl, int32_t C, int32_t p, int32_t reshape_order,
                       float sigma, float sigma_next, float cfg_weight, void* stream);
 
+/* Inpainting (latent blending; no reference counterpart): dk_euler_cfg_step followed, in the same launch, by
+ *   known = sigma_next * noise + (1 - sigma_next) * x_orig;  x = m * x_new + (1 - m) * known
+ * x_orig (process_in of the encoded image) and noise (the draw of the start state): f32 [n_img,Hl,Wl,C] like x;
+ * mask: f32 [Hl,Wl] for all images (mask_per_image = 0) or [n_img,Hl,Wl] (1), 1 = repaint, 0 = keep, the same for the C channels
+ * of a cell.  Exact ends for finite inputs: m == 1 leaves dk_euler_cfg_step's bits, m == 0 gives known, and with
+ * sigma_next == 0 known is x_orig (a value of -0.0f there may come out as +0.0f: the vanishing product is added as a signed zero).  tokens: the rounding of the blended value, in both CFG copies.
+ * dk_euler_cfg_step_masked_f16: model_out and tokens are fp16. */
+int dk_euler_cfg_step_masked(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img,
+                             int32_t cfg_on, int32_t Hl, int32_t Wl, int32_t C, int32_t p, int32_t reshape_order,
+                             float sigma, float sigma_next, float cfg_weight, const float* x_orig, const float* noise,
+                             const float* mask, int32_t mask_per_image, void* stream);
+int dk_euler_cfg_step_masked_f16(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img,
+                                 int32_t cfg_on, int32_t Hl, int32_t Wl, int32_t C, int32_t p, int32_t reshape_order,
+                                 float sigma, float sigma_next, float cfg_weight, const float* x_orig, const float* noise,
+                                 const float* mask, int32_t mask_per_image, void* stream);
+
+/* Inpainting mask, pixels -> latent cells: mask u8 [n_mask,H,W] (255 = repaint, 0 = keep) -> f32 [n_mask,H/f,W/f],
+ * (integer sum of the f x f block) / (f * f * 255) by a true division: an all-0 block gives 0.0f, an all-255 block 1.0f.
+ * H and W must be multiples of f (the pipeline passes the VAE's factor, 8). */
+int dk_mask_to_latent_f32(const uint8_t* mask, float* out, int32_t n_mask, int32_t H, int32_t W, int32_t f, void* stream);
+
+/* Inpainting paste-back: out = (uint8)(w * dec + (1 - w) * orig + 0.5f), w = mask / 255.0f, in plain fp32 (nothing fused):
+ * the decoder's bytes where mask == 255, the original's where mask == 0.  dec, out: u8 [B,H,W,3]; orig: u8 [H,W,3]
+ * (orig_per_image = 0) or [B,H,W,3] (1); mask: u8 [H,W] (mask_per_image = 0) or [B,H,W] (1). */
+int dk_image_composite_u8(const uint8_t* dec, const uint8_t* orig, const uint8_t* mask, uint8_t* out, int32_t B,
+                          int32_t H, int32_t W, int32_t orig_per_image, int32_t mask_per_image, void* stream);
+
 /* LatentFormat.process_in/out, __init__.py:729-733: y = x * a + b (f32) */
 int dk_affine_f32(const float* x, float* y, int64_t n, float a, float b, void* stream);
 
