@@ -5,7 +5,10 @@
 
 #include "dk_engine.h"
 
+// The library's two thread-local objects: the last error, and the attention workspace of the stand-alone dk_attention_* entries below
+// (dk_attention_set_workspace; the engines pass their own region and never consult it)
 static thread_local std::string g_last_error;
+static thread_local AttnWs g_attn_ws;
 void dk_set_error(const std::string& msg) { g_last_error = msg; }
 
 extern "C" int dk_abi_version(void) { return DK_ABI_VERSION; }
@@ -33,16 +36,13 @@ extern "C" int dk_tune_set(const char* key, int32_t value) {
   return -1;
 }
 
-thread_local int g_elem_dtype = DK_DTYPE_BF16;  // (ElemScope, dk_engine.h)
-thread_local void* g_linear_ws = nullptr;       // (LinearWsScope, dk_engine.h)
-
 // ---------------------------------------------------------------------------------------------
-// operator-level wrappers
+// operator-level wrappers: one implementation per operator, which takes the element type; the *_bf16 / *_f16 entries name theirs
 // ---------------------------------------------------------------------------------------------
-static GemmParams gemm_params_from_desc(const dk_gemm_desc* d) {
+static GemmParams gemm_params_from_desc(int dtype, const dk_gemm_desc* d) {
   GemmParams p;
   memset(&p, 0, sizeof(p));
-  p.dtype = g_elem_dtype;
+  p.dtype = dtype;
   p.A = (const bf16_t*)d->A; p.W = (const bf16_t*)d->W; p.C = (bf16_t*)d->C;
   p.bias = (const bf16_t*)d->bias; p.gate = (const bf16_t*)d->gate; p.res = (const bf16_t*)d->res;
   p.M = d->M; p.N = d->N; p.K = d->K;
@@ -58,26 +58,20 @@ static GemmParams gemm_params_from_desc(const dk_gemm_desc* d) {
 
 extern "C" size_t dk_gemm_workspace_bytes(void) { return dk_gemm_split_workspace_bytes(); }
 
-extern "C" int dk_gemm_bf16(const dk_gemm_desc* d, void* stream) {
+static int gemm(int dtype, const dk_gemm_desc* d, void* stream) {
   DK_REQUIRE(d != nullptr, "null descriptor");
-  return dk_launch_gemm(gemm_params_from_desc(d), S_(stream));
+  return dk_launch_gemm(gemm_params_from_desc(dtype, d), S_(stream));
 }
+extern "C" int dk_gemm_bf16(const dk_gemm_desc* d, void* stream) { return gemm(DK_DTYPE_BF16, d, stream); }
+extern "C" int dk_gemm_f16(const dk_gemm_desc* d, void* stream) { return gemm(DK_DTYPE_F16, d, stream); }
 
-extern "C" int dk_gemm_f16(const dk_gemm_desc* d, void* stream) {
-  ElemScope f16(DK_DTYPE_F16);
-  return dk_gemm_bf16(d, stream);
-}
-
-extern "C" int dk_gemm_plan(const dk_gemm_desc* d, const dk_gemm_desc* d2, dk_gemm_plan_t* plan) {
+static int gemm_plan(int dtype, const dk_gemm_desc* d, const dk_gemm_desc* d2, dk_gemm_plan_t* plan) {
   DK_REQUIRE(d != nullptr && plan != nullptr, "null descriptor / plan");
-  const GemmParams p2 = d2 != nullptr ? gemm_params_from_desc(d2) : GemmParams{};
-  return dk_gemm_plan_call(gemm_params_from_desc(d), d2 != nullptr ? &p2 : nullptr, *plan);
+  const GemmParams p2 = d2 != nullptr ? gemm_params_from_desc(dtype, d2) : GemmParams{};
+  return dk_gemm_plan_call(gemm_params_from_desc(dtype, d), d2 != nullptr ? &p2 : nullptr, *plan);
 }
-
-extern "C" int dk_gemm_plan_f16(const dk_gemm_desc* d, const dk_gemm_desc* d2, dk_gemm_plan_t* plan) {
-  ElemScope f16(DK_DTYPE_F16);
-  return dk_gemm_plan(d, d2, plan);
-}
+extern "C" int dk_gemm_plan(const dk_gemm_desc* d, const dk_gemm_desc* d2, dk_gemm_plan_t* plan) { return gemm_plan(DK_DTYPE_BF16, d, d2, plan); }
+extern "C" int dk_gemm_plan_f16(const dk_gemm_desc* d, const dk_gemm_desc* d2, dk_gemm_plan_t* plan) { return gemm_plan(DK_DTYPE_F16, d, d2, plan); }
 
 // the engine-only fields of GemmParams beside a descriptor (dk_gemm_side / dk_gemm_fp8_side: same names); null: nothing fused
 template <class P, class F>
@@ -90,35 +84,36 @@ static void set_fused(P& p, const F* f) {
 }
 
 // (no checks of their own: dk_gemm_route / the *_eligible functions decide what a form launches)
-extern "C" int dk_gemm_fused_bf16(const dk_gemm_desc* d, const dk_gemm_side* f, const dk_gemm_desc* d2, const dk_gemm_side* f2, void* stream) {
+static int gemm_fused(int dtype, const dk_gemm_desc* d, const dk_gemm_side* f, const dk_gemm_desc* d2, const dk_gemm_side* f2, void* stream) {
   DK_REQUIRE(d != nullptr && (d2 != nullptr || f2 == nullptr), "null descriptor");
-  GemmParams p = gemm_params_from_desc(d);
+  GemmParams p = gemm_params_from_desc(dtype, d);
   set_fused(p, f);
   if (d2 == nullptr) return dk_launch_gemm(p, S_(stream));
-  GemmParams p2 = gemm_params_from_desc(d2);
+  GemmParams p2 = gemm_params_from_desc(dtype, d2);
   set_fused(p2, f2);
   return dk_launch_gemm_pair(p, p2, S_(stream));
 }
-
+extern "C" int dk_gemm_fused_bf16(const dk_gemm_desc* d, const dk_gemm_side* f, const dk_gemm_desc* d2, const dk_gemm_side* f2, void* stream) {
+  return gemm_fused(DK_DTYPE_BF16, d, f, d2, f2, stream);
+}
 extern "C" int dk_gemm_fused_f16(const dk_gemm_desc* d, const dk_gemm_side* f, const dk_gemm_desc* d2, const dk_gemm_side* f2, void* stream) {
-  ElemScope f16(DK_DTYPE_F16);
-  return dk_gemm_fused_bf16(d, f, d2, f2, stream);
+  return gemm_fused(DK_DTYPE_F16, d, f, d2, f2, stream);
 }
 
 extern "C" int dk_gemm_fused_plan(const dk_gemm_desc* d, const dk_gemm_side* f, const dk_gemm_desc* d2, const dk_gemm_side* f2,
                                   dk_gemm_plan_t* plan) {
   DK_REQUIRE(d != nullptr && plan != nullptr && (d2 != nullptr || f2 == nullptr), "null descriptor / plan");
-  GemmParams p = gemm_params_from_desc(d), p2 = d2 != nullptr ? gemm_params_from_desc(d2) : GemmParams{};
+  GemmParams p = gemm_params_from_desc(DK_DTYPE_BF16, d), p2 = d2 != nullptr ? gemm_params_from_desc(DK_DTYPE_BF16, d2) : GemmParams{};
   set_fused(p, f);
   if (d2 != nullptr) set_fused(p2, f2);
   return dk_gemm_plan_call(p, d2 != nullptr ? &p2 : nullptr, *plan);
 }
 
-int conv3x3_launch(const dk_conv_desc* d, void* workspace, hipStream_t stream, dk_gemm_plan_t* rec) {  // (dk_engine.h)
+int conv3x3_launch(int dtype, const dk_conv_desc* d, void* workspace, hipStream_t stream, dk_gemm_plan_t* rec) {  // (dk_engine.h)
   DK_REQUIRE(d != nullptr, "null descriptor");
   GemmParams p;
   memset(&p, 0, sizeof(p));
-  p.dtype = g_elem_dtype;
+  p.dtype = dtype;
   p.A = (const bf16_t*)d->x; p.W = (const bf16_t*)d->w; p.C = (bf16_t*)d->y;
   p.bias = (const bf16_t*)d->bias; p.res = (const bf16_t*)d->res;
   p.M = d->B * d->H * d->W; p.N = d->O; p.K = 9 * d->C;
@@ -133,28 +128,23 @@ int conv3x3_launch(const dk_conv_desc* d, void* workspace, hipStream_t stream, d
   if (rec != nullptr) return dk_gemm_plan_call(p, nullptr, *rec);
   return dk_launch_gemm(p, stream);
 }
-extern "C" int dk_conv3x3_bf16(const dk_conv_desc* d, void* stream) { return conv3x3_launch(d, nullptr, S_(stream)); }
-extern "C" int dk_conv3x3_f16(const dk_conv_desc* d, void* stream) {
-  ElemScope f16(DK_DTYPE_F16);
-  return dk_conv3x3_bf16(d, stream);
-}
-extern "C" int dk_conv3x3_plan(const dk_conv_desc* d, dk_gemm_plan_t* plan) {
+extern "C" int dk_conv3x3_bf16(const dk_conv_desc* d, void* stream) { return conv3x3_launch(DK_DTYPE_BF16, d, nullptr, S_(stream)); }
+extern "C" int dk_conv3x3_f16(const dk_conv_desc* d, void* stream) { return conv3x3_launch(DK_DTYPE_F16, d, nullptr, S_(stream)); }
+static int conv3x3_plan(int dtype, const dk_conv_desc* d, dk_gemm_plan_t* plan) {
   DK_REQUIRE(plan != nullptr, "null plan");
-  return conv3x3_launch(d, nullptr, nullptr, plan);
+  return conv3x3_launch(dtype, d, nullptr, nullptr, plan);
 }
-extern "C" int dk_conv3x3_plan_f16(const dk_conv_desc* d, dk_gemm_plan_t* plan) {
-  ElemScope f16(DK_DTYPE_F16);
-  return dk_conv3x3_plan(d, plan);
-}
+extern "C" int dk_conv3x3_plan(const dk_conv_desc* d, dk_gemm_plan_t* plan) { return conv3x3_plan(DK_DTYPE_BF16, d, plan); }
+extern "C" int dk_conv3x3_plan_f16(const dk_conv_desc* d, dk_gemm_plan_t* plan) { return conv3x3_plan(DK_DTYPE_F16, d, plan); }
 
-// Workspace of the attention launches of this host thread.  attention5.hip splits the query blocks of a launch's last, partial round of the
+// Workspace of the stand-alone attention launches (dk_attention_*) of this host thread.  attention5.hip splits the query blocks of a launch's last, partial round of the
 // CUs along the keys (FLUX, one image: 408 blocks on 256 CUs -- 152 blocks in three key ranges each fill the second round to two thirds
 // of a block's time); the partial results (bf16 O / l, offset, l per row) go through this buffer.  Without one (or with one too small for a
 // launch) the blocks are not split: same results up to the rounding of the partials, a longer last round.
 extern "C" size_t dk_attention_workspace_bytes(void) { return (size_t)1020 * (65536 + 2048); }  // <= 255 blocks x 4 key ranges
 extern "C" int dk_attention_set_workspace(void* workspace, size_t bytes) {
   DK_REQUIRE(workspace == nullptr || ((uintptr_t)workspace & 255) == 0, "attention workspace: 256-byte aligned (or NULL)");
-  dk_set_attention_workspace(workspace, bytes);
+  g_attn_ws = AttnWs{workspace, workspace ? bytes : 0};
   return 0;
 }
 
@@ -163,7 +153,7 @@ extern "C" int dk_attention_bf16(const void* q, const void* k, const void* v, vo
   AttnParams p;
   p.Q = (const bf16_t*)q; p.K = (const bf16_t*)k; p.V = (const bf16_t*)v; p.O = (bf16_t*)out;
   p.B = B; p.H = H; p.S = S; p.D = D; p.ld = ld; p.ldo = ldo; p.scale = scale;
-  return dk_launch_attention(p, S_(stream));
+  return dk_launch_attention(p, g_attn_ws, S_(stream));
 }
 
 extern "C" int dk_attention_bias_bf16(const void* q, const void* k, const void* v, void* out, int32_t B, int32_t H, int32_t S, int32_t D,
@@ -174,50 +164,51 @@ extern "C" int dk_attention_bias_bf16(const void* q, const void* k, const void* 
   p.Q = (const bf16_t*)q; p.K = (const bf16_t*)k; p.V = (const bf16_t*)v; p.O = (bf16_t*)out;
   p.B = B; p.H = H; p.S = S; p.D = D; p.ld = ld; p.ldo = ldo; p.scale = scale;
   p.bias = (const bf16_t*)bias; p.bias_head_stride = (long)bias_head_stride; p.ldb = ldb;
-  return dk_launch_attention(p, S_(stream));
+  return dk_launch_attention(p, g_attn_ws, S_(stream));
 }
-extern "C" int dk_attention_desc_bf16(const dk_attention_desc* d, void* stream) {
+static int attention_desc(int dtype, const dk_attention_desc* d, void* stream) {
   DK_REQUIRE(d != nullptr, "null descriptor");
   AttnParams p;
   p.Q = (const bf16_t*)d->q; p.K = (const bf16_t*)d->k; p.V = (const bf16_t*)d->v; p.O = (bf16_t*)d->out;
   p.B = d->B; p.H = d->H; p.S = d->S; p.D = d->D; p.ld = d->ld; p.ldo = d->ldo; p.scale = d->scale;
   p.bias = (const bf16_t*)d->bias; p.bias_head_stride = (long)d->bias_head_stride; p.ldb = d->ldb;
   p.qn_a = (const bf16_t*)d->qn_a; p.qn_b = (const bf16_t*)d->qn_b; p.qn_split = d->qn_split; p.qn_eps = d->qn_eps; p.q_rope = d->q_rope;
-  p.dtype = g_elem_dtype;
+  p.dtype = dtype;
   if (d->O8 != nullptr) {
     DK_REQUIRE(d->O8_scales != nullptr && d->o8_rows >= (int64_t)d->B * d->S && d->o8_ld >= d->H * d->D && d->o8_ld % 32 == 0,
                "MX-fp8 output copy: scales, B * S rows inside the buffer, a row pitch of at least H * D bytes (multiple of 32)");
     p.O8 = (unsigned char*)d->O8; p.O8_scales = (unsigned char*)d->O8_scales; p.o8_ld = d->o8_ld; p.o8_nblk = mx_nblk((long)d->o8_rows);
   }
-  return dk_launch_attention(p, S_(stream));
+  return dk_launch_attention(p, g_attn_ws, S_(stream));
 }
-extern "C" int dk_attention_desc_f16(const dk_attention_desc* d, void* stream) {
-  ElemScope f16(DK_DTYPE_F16);
-  return dk_attention_desc_bf16(d, stream);
-}
+extern "C" int dk_attention_desc_bf16(const dk_attention_desc* d, void* stream) { return attention_desc(DK_DTYPE_BF16, d, stream); }
+extern "C" int dk_attention_desc_f16(const dk_attention_desc* d, void* stream) { return attention_desc(DK_DTYPE_F16, d, stream); }
 extern "C" int32_t dk_attention_d512_tp(int32_t T) { return (int32_t)align_up((size_t)(T > 0 ? T : 0), 64); }
-int attention_d512(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int B, int T, int ld, int ldo, float scale, bf16_t* vt,
-                   hipStream_t st) {  // (dk_engine.h)
+int attention_d512(int dtype, const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int B, int T, int ld, int ldo, float scale,
+                   bf16_t* vt, hipStream_t st) {  // (dk_engine.h)
   DK_REQUIRE(ld == 512, "attention_d512: q / k / v rows of exactly 512 columns (the transpose reads dense [T, 512] matrices)");
   const int Tp = dk_attention_d512_tp(T);
   for (int b = 0; b < B; ++b) {
-    const int rc = DK_EL(dk_launch_transpose)(v + (size_t)b * T * ld, vt + (size_t)b * 512 * Tp, T, 512, st, Tp);
+    const int rc = DK_EL(dtype, dk_launch_transpose)(v + (size_t)b * T * ld, vt + (size_t)b * 512 * Tp, T, 512, st, Tp);
     if (rc) return rc;
   }
   Attn512Params a;
-  a.Q = q; a.K = k; a.Vt = vt; a.O = out; a.T = T; a.Tp = Tp; a.B = B; a.ld = ld; a.ldo = ldo; a.scale = scale; a.dtype = g_elem_dtype;
+  a.Q = q; a.K = k; a.Vt = vt; a.O = out; a.T = T; a.Tp = Tp; a.B = B; a.ld = ld; a.ldo = ldo; a.scale = scale; a.dtype = dtype;
   return dk_launch_attention512(a, st);
+}
+static int attention_d512_checked(int dtype, const void* q, const void* k, const void* v, void* out, int B, int T, int ld, int ldo, float scale,
+                                  void* vt_scratch, void* stream) {
+  DK_REQUIRE(q && k && v && out && vt_scratch && B > 0 && T > 0, "null / empty argument");
+  return attention_d512(dtype, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)out, B, T, ld, ldo, scale, (bf16_t*)vt_scratch,
+                        S_(stream));
 }
 extern "C" int dk_attention_d512_bf16(const void* q, const void* k, const void* v, void* out, int32_t B, int32_t T, int32_t ld, int32_t ldo,
                                       float scale, void* vt_scratch, void* stream) {
-  DK_REQUIRE(q && k && v && out && vt_scratch && B > 0 && T > 0, "null / empty argument");
-  return attention_d512((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)out, B, T, ld, ldo, scale, (bf16_t*)vt_scratch,
-                        S_(stream));
+  return attention_d512_checked(DK_DTYPE_BF16, q, k, v, out, B, T, ld, ldo, scale, vt_scratch, stream);
 }
 extern "C" int dk_attention_d512_f16(const void* q, const void* k, const void* v, void* out, int32_t B, int32_t T, int32_t ld, int32_t ldo,
                                      float scale, void* vt_scratch, void* stream) {
-  ElemScope f16(DK_DTYPE_F16);
-  return dk_attention_d512_bf16(q, k, v, out, B, T, ld, ldo, scale, vt_scratch, stream);
+  return attention_d512_checked(DK_DTYPE_F16, q, k, v, out, B, T, ld, ldo, scale, vt_scratch, stream);
 }
 extern "C" int dk_embedding_bf16(const void* table, const int32_t* ids, const void* pos, int32_t pos_rows, void* out_bf16, float* out_f32,
                                  int32_t n, int32_t dim, int32_t vocab, void* stream) {
@@ -242,18 +233,21 @@ extern "C" int dk_t5_bias_bf16(const void* emb, const int32_t* rel_bucket, int32
   return dk_launch_t5_bias((const bf16_t*)emb, rel_bucket, H, S, ld, (bf16_t*)out, S_(stream));
 }
 
+static int ln_modulate(int dtype, const void* x, int ldx, void* out, int ldo, int M, int h, const void* shift, const void* scale, int mod_stride,
+                       int mod_seg_len, int x_seg_len, int x_seg_stride, float eps, void* stream) {
+  return DK_EL(dtype, dk_launch_ln_modulate)((const bf16_t*)x, ldx, (bf16_t*)out, ldo, M, h, (const bf16_t*)shift, (const bf16_t*)scale,
+                                             mod_stride, mod_seg_len > 0 ? mod_seg_len : M, x_seg_len > 0 ? x_seg_len : M, x_seg_stride,
+                                             eps, S_(stream));
+}
 extern "C" int dk_ln_modulate_bf16(const void* x, int32_t ldx, void* out, int32_t ldo, int32_t M, int32_t h, const void* shift,
                                    const void* scale, int32_t mod_stride, int32_t mod_seg_len, int32_t x_seg_len,
                                    int32_t x_seg_stride, float eps, void* stream) {
-  return DK_EL(dk_launch_ln_modulate)((const bf16_t*)x, ldx, (bf16_t*)out, ldo, M, h, (const bf16_t*)shift, (const bf16_t*)scale,
-                                      mod_stride, mod_seg_len > 0 ? mod_seg_len : M, x_seg_len > 0 ? x_seg_len : M, x_seg_stride,
-                                      eps, S_(stream));
+  return ln_modulate(DK_DTYPE_BF16, x, ldx, out, ldo, M, h, shift, scale, mod_stride, mod_seg_len, x_seg_len, x_seg_stride, eps, stream);
 }
 extern "C" int dk_ln_modulate_f16(const void* x, int32_t ldx, void* out, int32_t ldo, int32_t M, int32_t h, const void* shift,
                                   const void* scale, int32_t mod_stride, int32_t mod_seg_len, int32_t x_seg_len,
                                   int32_t x_seg_stride, float eps, void* stream) {
-  ElemScope f16(DK_DTYPE_F16);
-  return dk_ln_modulate_bf16(x, ldx, out, ldo, M, h, shift, scale, mod_stride, mod_seg_len, x_seg_len, x_seg_stride, eps, stream);
+  return ln_modulate(DK_DTYPE_F16, x, ldx, out, ldo, M, h, shift, scale, mod_stride, mod_seg_len, x_seg_len, x_seg_stride, eps, stream);
 }
 
 // mx8_out: the descriptor's C_scales / c_rows / c_row0 / c_col0 describe an MX-fp8 output (its own, or the second one of a column split)
@@ -314,17 +308,20 @@ extern "C" int dk_ln_modulate_mx8(const void* x, int32_t ldx, int32_t M, int32_t
                                    S_(stream));
 }
 
+static int qk_norm_rope(int dtype, void* qkv, int ld, int q_off, int k_off, int rows, int H, int D, const void* q_weight, const void* k_weight,
+                        float eps, const float* rope_table, int row_seg_len, int row_seg_stride, int pos_off, void* stream) {
+  return DK_EL(dtype, dk_launch_qk_norm_rope)((bf16_t*)qkv, ld, q_off, k_off, rows, H, D, (const bf16_t*)q_weight, (const bf16_t*)k_weight, eps,
+                                              rope_table, row_seg_len > 0 ? row_seg_len : rows, row_seg_stride, pos_off, 0, S_(stream), 0);
+}
 extern "C" int dk_qk_norm_rope_bf16(void* qkv, int32_t ld, int32_t q_off, int32_t k_off, int32_t rows, int32_t H, int32_t D,
                                     const void* q_weight, const void* k_weight, float eps, const float* rope_table,
                                     int32_t row_seg_len, int32_t row_seg_stride, int32_t pos_off, void* stream) {
-  return DK_EL(dk_launch_qk_norm_rope)((bf16_t*)qkv, ld, q_off, k_off, rows, H, D, (const bf16_t*)q_weight, (const bf16_t*)k_weight,
-                                       eps, rope_table, row_seg_len > 0 ? row_seg_len : rows, row_seg_stride, pos_off, 0, S_(stream), 0);
+  return qk_norm_rope(DK_DTYPE_BF16, qkv, ld, q_off, k_off, rows, H, D, q_weight, k_weight, eps, rope_table, row_seg_len, row_seg_stride, pos_off, stream);
 }
 extern "C" int dk_qk_norm_rope_f16(void* qkv, int32_t ld, int32_t q_off, int32_t k_off, int32_t rows, int32_t H, int32_t D,
                                    const void* q_weight, const void* k_weight, float eps, const float* rope_table,
                                    int32_t row_seg_len, int32_t row_seg_stride, int32_t pos_off, void* stream) {
-  ElemScope f16(DK_DTYPE_F16);
-  return dk_qk_norm_rope_bf16(qkv, ld, q_off, k_off, rows, H, D, q_weight, k_weight, eps, rope_table, row_seg_len, row_seg_stride, pos_off, stream);
+  return qk_norm_rope(DK_DTYPE_F16, qkv, ld, q_off, k_off, rows, H, D, q_weight, k_weight, eps, rope_table, row_seg_len, row_seg_stride, pos_off, stream);
 }
 
 extern "C" int dk_rope_table_f32(float* table, int32_t S_txt, int32_t gh, int32_t gw, const int32_t* axes_dim, int32_t n_axes,
@@ -332,60 +329,73 @@ extern "C" int dk_rope_table_f32(float* table, int32_t S_txt, int32_t gh, int32_
   return dk_launch_rope_table(table, S_txt, gh, gw, axes_dim, n_axes, theta, S_(stream));
 }
 
+static int timestep_embedding(int dtype, const float* t_dev, int n, int dim, float max_period, int embed_dtype, void* out, void* stream) {
+  return DK_EL(dtype, dk_launch_timestep_embedding)(t_dev, n, 1, dim, max_period, embed_dtype, (bf16_t*)out, S_(stream));
+}
 extern "C" int dk_timestep_embedding_bf16(const float* t_dev, int32_t n, int32_t dim, float max_period, int32_t embed_dtype,
                                           void* out, void* stream) {
-  return DK_EL(dk_launch_timestep_embedding)(t_dev, n, 1, dim, max_period, embed_dtype, (bf16_t*)out, S_(stream));
+  return timestep_embedding(DK_DTYPE_BF16, t_dev, n, dim, max_period, embed_dtype, out, stream);
 }
 extern "C" int dk_timestep_embedding_f16(const float* t_dev, int32_t n, int32_t dim, float max_period, int32_t embed_dtype,
                                          void* out, void* stream) {
-  ElemScope f16(DK_DTYPE_F16);
-  return dk_timestep_embedding_bf16(t_dev, n, dim, max_period, embed_dtype, out, stream);
+  return timestep_embedding(DK_DTYPE_F16, t_dev, n, dim, max_period, embed_dtype, out, stream);
 }
 
+static int latent_to_tokens(int dtype, const float* x, void* tokens, int n_img, int dup, int Hl, int Wl, int C, int p, int reshape_order,
+                            void* stream) {
+  DK_REQUIRE(Hl % p == 0 && Wl % p == 0, "latent size must be divisible by the patch size");
+  return DK_EL(dtype, dk_launch_latent_to_tokens)(x, (bf16_t*)tokens, n_img, dup, Hl, Wl, C, p, reshape_order, S_(stream));
+}
 extern "C" int dk_latent_to_tokens(const float* x, void* tokens, int32_t n_img, int32_t dup, int32_t Hl, int32_t Wl, int32_t C,
                                    int32_t p, int32_t reshape_order, void* stream) {
-  DK_REQUIRE(Hl % p == 0 && Wl % p == 0, "latent size must be divisible by the patch size");
-  return DK_EL(dk_launch_latent_to_tokens)(x, (bf16_t*)tokens, n_img, dup, Hl, Wl, C, p, reshape_order, S_(stream));
+  return latent_to_tokens(DK_DTYPE_BF16, x, tokens, n_img, dup, Hl, Wl, C, p, reshape_order, stream);
 }
 extern "C" int dk_latent_to_tokens_f16(const float* x, void* tokens, int32_t n_img, int32_t dup, int32_t Hl, int32_t Wl, int32_t C,
                                        int32_t p, int32_t reshape_order, void* stream) {
-  ElemScope f16(DK_DTYPE_F16);
-  return dk_latent_to_tokens(x, tokens, n_img, dup, Hl, Wl, C, p, reshape_order, stream);
+  return latent_to_tokens(DK_DTYPE_F16, x, tokens, n_img, dup, Hl, Wl, C, p, reshape_order, stream);
 }
 
+static int euler_cfg_step(int dtype, float* x, const void* model_out, int ld_out, void* tokens, int n_img, int cfg_on, int Hl, int Wl, int C, int p,
+                          int reshape_order, float sigma, float sigma_next, float cfg_weight, void* stream) {
+  DK_REQUIRE(sigma != 0.0f, "sigma must be non-zero");
+  return DK_EL(dtype, dk_launch_euler_step)(x, (const bf16_t*)model_out, ld_out, (bf16_t*)tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order,
+                                            sigma, sigma_next, cfg_weight, S_(stream));
+}
 extern "C" int dk_euler_cfg_step(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on,
                                  int32_t Hl, int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma,
                                  float sigma_next, float cfg_weight, void* stream) {
-  DK_REQUIRE(sigma != 0.0f, "sigma must be non-zero");
-  return DK_EL(dk_launch_euler_step)(x, (const bf16_t*)model_out, ld_out, (bf16_t*)tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order,
-                                     sigma, sigma_next, cfg_weight, S_(stream));
+  return euler_cfg_step(DK_DTYPE_BF16, x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight, stream);
 }
 extern "C" int dk_euler_cfg_step_f16(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on,
                                      int32_t Hl, int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma,
                                      float sigma_next, float cfg_weight, void* stream) {
-  ElemScope f16(DK_DTYPE_F16);
-  return dk_euler_cfg_step(x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight, stream);
+  return euler_cfg_step(DK_DTYPE_F16, x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight, stream);
 }
 
-extern "C" int dk_euler_cfg_step_masked(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on,
-                                        int32_t Hl, int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma,
-                                        float sigma_next, float cfg_weight, const float* x_orig, const float* noise, const float* mask,
-                                        int32_t mask_per_image, void* stream) {
+static int euler_cfg_step_masked(int dtype, float* x, const void* model_out, int ld_out, void* tokens, int n_img, int cfg_on, int Hl, int Wl, int C,
+                                 int p, int reshape_order, float sigma, float sigma_next, float cfg_weight, const float* x_orig,
+                                 const float* noise, const float* mask, int mask_per_image, void* stream) {
   DK_REQUIRE(sigma != 0.0f, "sigma must be non-zero");
   DK_REQUIRE(p > 0 && Hl % p == 0 && Wl % p == 0, "latent size must be divisible by the patch size");
   DK_REQUIRE(x && model_out && tokens && x_orig && noise && mask, "null argument");
   DK_REQUIRE(n_img > 0, "n_img must be positive");
-  return DK_EL(dk_launch_euler_step_masked)(x, (const bf16_t*)model_out, ld_out, (bf16_t*)tokens, n_img, cfg_on, Hl, Wl, C, p,
-                                            reshape_order, sigma, sigma_next, cfg_weight, x_orig, noise, mask, mask_per_image != 0,
-                                            S_(stream));
+  return DK_EL(dtype, dk_launch_euler_step_masked)(x, (const bf16_t*)model_out, ld_out, (bf16_t*)tokens, n_img, cfg_on, Hl, Wl, C, p,
+                                                   reshape_order, sigma, sigma_next, cfg_weight, x_orig, noise, mask, mask_per_image != 0,
+                                                   S_(stream));
+}
+extern "C" int dk_euler_cfg_step_masked(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on,
+                                        int32_t Hl, int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma,
+                                        float sigma_next, float cfg_weight, const float* x_orig, const float* noise, const float* mask,
+                                        int32_t mask_per_image, void* stream) {
+  return euler_cfg_step_masked(DK_DTYPE_BF16, x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next,
+                               cfg_weight, x_orig, noise, mask, mask_per_image, stream);
 }
 extern "C" int dk_euler_cfg_step_masked_f16(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on,
                                             int32_t Hl, int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma,
                                             float sigma_next, float cfg_weight, const float* x_orig, const float* noise,
                                             const float* mask, int32_t mask_per_image, void* stream) {
-  ElemScope f16(DK_DTYPE_F16);
-  return dk_euler_cfg_step_masked(x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight,
-                                  x_orig, noise, mask, mask_per_image, stream);
+  return euler_cfg_step_masked(DK_DTYPE_F16, x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next,
+                               cfg_weight, x_orig, noise, mask, mask_per_image, stream);
 }
 
 extern "C" int dk_mask_to_latent_f32(const uint8_t* mask, float* out, int32_t n_mask, int32_t H, int32_t W, int32_t f, void* stream) {
@@ -414,46 +424,50 @@ static int gn_nchunk(long HW, int C) {
   return (int)n;
 }
 extern "C" size_t dk_groupnorm_scratch_floats(int32_t B, int32_t G) { return (size_t)B * 1024 * 2 * G + (size_t)B * G * 2; }
+int groupnorm_launch(int dtype, const void* x, void* y, int B, long HW, int C, int G, const void* gamma, const void* beta, float eps,
+                     int fuse_silu, float* scratch, hipStream_t st) {  // (dk_engine.h)
+  const int nchunk = gn_nchunk(HW, C);
+  float* mean_rstd = scratch + (size_t)B * 1024 * 2 * G;
+  int rc = DK_EL(dtype, dk_launch_groupnorm_stats)((const bf16_t*)x, B, HW, C, G, scratch, nchunk, mean_rstd, eps, st);
+  if (rc) return rc;
+  return DK_EL(dtype, dk_launch_groupnorm_apply)((const bf16_t*)x, (bf16_t*)y, B, HW, C, G, mean_rstd, (const bf16_t*)gamma, (const bf16_t*)beta,
+                                                 fuse_silu, st);
+}
 extern "C" int dk_groupnorm_bf16(const void* x, void* y, int32_t B, int64_t HW, int32_t C, int32_t G, const void* gamma,
                                  const void* beta, float eps, int32_t fuse_silu, float* scratch, void* stream) {
-  const int nchunk = gn_nchunk((long)HW, C);
-  float* mean_rstd = scratch + (size_t)B * 1024 * 2 * G;
-  int rc = DK_EL(dk_launch_groupnorm_stats)((const bf16_t*)x, B, (long)HW, C, G, scratch, nchunk, mean_rstd, eps, S_(stream));
-  if (rc) return rc;
-  return DK_EL(dk_launch_groupnorm_apply)((const bf16_t*)x, (bf16_t*)y, B, (long)HW, C, G, mean_rstd, (const bf16_t*)gamma,
-                                          (const bf16_t*)beta, fuse_silu, S_(stream));
+  return groupnorm_launch(DK_DTYPE_BF16, x, y, B, (long)HW, C, G, gamma, beta, eps, fuse_silu, scratch, S_(stream));
 }
 extern "C" int dk_groupnorm_f16(const void* x, void* y, int32_t B, int64_t HW, int32_t C, int32_t G, const void* gamma,
                                 const void* beta, float eps, int32_t fuse_silu, float* scratch, void* stream) {
-  ElemScope f16(DK_DTYPE_F16);
-  return dk_groupnorm_bf16(x, y, B, HW, C, G, gamma, beta, eps, fuse_silu, scratch, stream);
+  return groupnorm_launch(DK_DTYPE_F16, x, y, B, (long)HW, C, G, gamma, beta, eps, fuse_silu, scratch, S_(stream));
 }
 
-// scratch layout shared by dk_groupnorm_bf16 / dk_groupnorm_table_bf16: [partials: B * n * 2G][mean_rstd: B * G * 2], n = the
-// larger of 1024 and the caller's n_partial
-extern "C" int dk_groupnorm_table_bf16(const void* x, int32_t B, int64_t HW, int32_t C, int32_t G, const void* gamma, const void* beta,
-                                       float eps, float* scratch, int32_t n_partial, float* scale_shift, void* stream) {
+int groupnorm_table_launch(int dtype, const void* x, int B, long HW, int C, int G, const void* gamma, const void* beta, float eps,
+                           float* scratch, int n_partial, float* scale_shift, hipStream_t st) {  // (dk_engine.h)
   DK_REQUIRE(gamma && beta && scratch && scale_shift && B > 0 && G > 0 && C % G == 0, "groupnorm table arguments");
   DK_REQUIRE(x != nullptr || n_partial > 0, "either x or the number of partials a conv launch left in scratch");
-  const int nchunk = x ? gn_nchunk((long)HW, C) : n_partial;
+  const int nchunk = x ? gn_nchunk(HW, C) : n_partial;
   float* mean_rstd = scratch + (size_t)B * (nchunk > 1024 ? nchunk : 1024) * 2 * G;
   if (x) {  // the partial sums only: the one finalisation below builds mean / rstd AND the table
-    const int rc = DK_EL(dk_launch_groupnorm_partials)((const bf16_t*)x, B, (long)HW, C, G, scratch, nchunk, S_(stream));
+    const int rc = DK_EL(dtype, dk_launch_groupnorm_partials)((const bf16_t*)x, B, HW, C, G, scratch, nchunk, st);
     if (rc) return rc;
   }
-  return DK_EL(dk_launch_groupnorm_finalize)(scratch, nchunk, B, G, (double)HW * (double)(C / G), eps, mean_rstd, (const bf16_t*)gamma,
-                                             (const bf16_t*)beta, C, scale_shift, S_(stream));
+  return DK_EL(dtype, dk_launch_groupnorm_finalize)(scratch, nchunk, B, G, (double)HW * (double)(C / G), eps, mean_rstd, (const bf16_t*)gamma,
+                                                    (const bf16_t*)beta, C, scale_shift, st);
+}
+extern "C" int dk_groupnorm_table_bf16(const void* x, int32_t B, int64_t HW, int32_t C, int32_t G, const void* gamma, const void* beta,
+                                       float eps, float* scratch, int32_t n_partial, float* scale_shift, void* stream) {
+  return groupnorm_table_launch(DK_DTYPE_BF16, x, B, (long)HW, C, G, gamma, beta, eps, scratch, n_partial, scale_shift, S_(stream));
 }
 extern "C" int dk_groupnorm_table_f16(const void* x, int32_t B, int64_t HW, int32_t C, int32_t G, const void* gamma, const void* beta,
                                       float eps, float* scratch, int32_t n_partial, float* scale_shift, void* stream) {
-  ElemScope f16(DK_DTYPE_F16);
-  return dk_groupnorm_table_bf16(x, B, HW, C, G, gamma, beta, eps, scratch, n_partial, scale_shift, stream);
+  return groupnorm_table_launch(DK_DTYPE_F16, x, B, (long)HW, C, G, gamma, beta, eps, scratch, n_partial, scale_shift, S_(stream));
 }
 
-static ConvHaloParams conv_halo_params(const dk_conv_gn_desc* d) {
+static ConvHaloParams conv_halo_params(int dtype, const dk_conv_gn_desc* d) {
   ConvHaloParams p;
   memset(&p, 0, sizeof(p));
-  p.dtype = g_elem_dtype;
+  p.dtype = dtype;
   p.x = (const bf16_t*)d->x; p.w = (const bf16_t*)d->w; p.bias = (const bf16_t*)d->bias; p.bias2 = (const bf16_t*)d->bias2;
   p.res = (const bf16_t*)d->res; p.y = (bf16_t*)d->y; p.gn_ss = d->gn_scale_shift; p.gn_silu = d->gn_silu;
   p.x2 = (const bf16_t*)d->x2; p.C2 = d->C2; p.stats_out = d->stats_partial; p.G_out = d->stats_groups;
@@ -461,28 +475,22 @@ static ConvHaloParams conv_halo_params(const dk_conv_gn_desc* d) {
   p.B = d->B; p.H = d->H; p.W = d->W; p.C = d->C; p.O = d->O; p.ups = d->upsample; p.ldw = d->ldw; p.ldy = d->ldy; p.ldr = d->ldr;
   return p;
 }
-extern "C" int dk_conv3x3_gn_bf16(const dk_conv_gn_desc* d, void* stream) {
+static int conv3x3_gn(int dtype, const dk_conv_gn_desc* d, void* stream) {
   DK_REQUIRE(d && d->x && d->w && d->bias, "null argument");
   const bool img = d->image_f32 || d->image_u8 || d->raw_bf16;
   DK_REQUIRE(img || d->y, "no output");
-  return dk_launch_conv_halo(conv_halo_params(d), S_(stream));
+  return dk_launch_conv_halo(conv_halo_params(dtype, d), S_(stream));
 }
-extern "C" int dk_conv3x3_gn_f16(const dk_conv_gn_desc* d, void* stream) {
-  ElemScope f16(DK_DTYPE_F16);
-  return dk_conv3x3_gn_bf16(d, stream);
-}
+extern "C" int dk_conv3x3_gn_bf16(const dk_conv_gn_desc* d, void* stream) { return conv3x3_gn(DK_DTYPE_BF16, d, stream); }
+extern "C" int dk_conv3x3_gn_f16(const dk_conv_gn_desc* d, void* stream) { return conv3x3_gn(DK_DTYPE_F16, d, stream); }
 
-extern "C" int dk_softmax_rows_bf16(void* x, int32_t rows, int32_t cols, int32_t ld, void* stream) {
-  return DK_EL(dk_launch_softmax_rows)((bf16_t*)x, rows, cols, ld, S_(stream));
+static int softmax_rows(int dtype, void* x, int rows, int cols, int ld, void* stream) {
+  return DK_EL(dtype, dk_launch_softmax_rows)((bf16_t*)x, rows, cols, ld, S_(stream));
 }
-extern "C" int dk_softmax_rows_f16(void* x, int32_t rows, int32_t cols, int32_t ld, void* stream) {
-  ElemScope f16(DK_DTYPE_F16);
-  return dk_softmax_rows_bf16(x, rows, cols, ld, stream);
+extern "C" int dk_softmax_rows_bf16(void* x, int32_t rows, int32_t cols, int32_t ld, void* stream) { return softmax_rows(DK_DTYPE_BF16, x, rows, cols, ld, stream); }
+extern "C" int dk_softmax_rows_f16(void* x, int32_t rows, int32_t cols, int32_t ld, void* stream) { return softmax_rows(DK_DTYPE_F16, x, rows, cols, ld, stream); }
+static int transpose(int dtype, const void* x, void* y, int R, int C, void* stream) {
+  return DK_EL(dtype, dk_launch_transpose)((const bf16_t*)x, (bf16_t*)y, R, C, S_(stream), 0);
 }
-extern "C" int dk_transpose_bf16(const void* x, void* y, int32_t R, int32_t C, void* stream) {
-  return DK_EL(dk_launch_transpose)((const bf16_t*)x, (bf16_t*)y, R, C, S_(stream), 0);
-}
-extern "C" int dk_transpose_f16(const void* x, void* y, int32_t R, int32_t C, void* stream) {
-  ElemScope f16(DK_DTYPE_F16);
-  return dk_transpose_bf16(x, y, R, C, stream);
-}
+extern "C" int dk_transpose_bf16(const void* x, void* y, int32_t R, int32_t C, void* stream) { return transpose(DK_DTYPE_BF16, x, y, R, C, stream); }
+extern "C" int dk_transpose_f16(const void* x, void* y, int32_t R, int32_t C, void* stream) { return transpose(DK_DTYPE_F16, x, y, R, C, stream); }

@@ -19,17 +19,10 @@
 int g_dk_attn_mode = -1;  // dk_tune_set("attn", v): -1 (default) automatic; 4 = dk_attn2 (4 waves); 9 = dk_attn4 (8 waves, D = 128 only);
                           // 10 = dk_attn5 (one wave per SIMD, asm tile loop; D = 128, S % 256 == 0: other shapes fall back to 9)
 
-// workspace of the launches this host thread enqueues (dk_attention_set_workspace): the partial results of attention5.hip's key-split
-// workgroups; lab: the trace buffer of attention4.hip's DK4_TRACE builds (scripts/attn_trace.py)
-static thread_local void* g_attn_ws = nullptr;
-static thread_local size_t g_attn_ws_bytes = 0;
-void dk_set_attention_workspace(void* ws, size_t bytes) { g_attn_ws = ws, g_attn_ws_bytes = ws ? bytes : 0; }
-void* dk_get_attention_workspace() { return g_attn_ws; }
-size_t dk_get_attention_workspace_bytes() { return g_attn_ws_bytes; }
-
-int dk_launch_attention(const AttnParams& p_in, hipStream_t stream) {
+// ws: the caller's region for the partial results of attention5.hip's key-split workgroups (AttnWs, dk_kernels.h)
+int dk_launch_attention(const AttnParams& p_in, AttnWs ws, hipStream_t stream) {
   AttnParams p = p_in;
-  if (p.bal_ws == nullptr) p.bal_ws = g_attn_ws;
+  if (p.bal_ws == nullptr) p.bal_ws = ws.p;
   DK_REQUIRE(p.D == 128 || p.D == 64, "head_dim must be 64 or 128");
   DK_REQUIRE(p.S > 0 && p.B > 0 && p.H > 0, "empty attention");
   DK_REQUIRE(p.ld % 8 == 0 && p.ldo % 4 == 0, "row strides must keep 16-byte alignment");
@@ -58,7 +51,7 @@ int dk_launch_attention(const AttnParams& p_in, hipStream_t stream) {
     case 9:  // phase-alternating kernel (attention4.hip); D = 128 only
       rc = p.D == 128 ? dk_launch_attention4(p, stream) : dk_launch_attention2(p, 4, stream);
       break;
-    case 10: rc = dk_launch_attention5(p, stream); break;  // one wave per SIMD (attention5.hip)
+    case 10: rc = dk_launch_attention5(p, ws, stream); break;  // one wave per SIMD (attention5.hip)
     default: DK_REQUIRE(false, "unknown attention variant (4: lean kernel, 9: phase-alternating kernel, 10: one-wave-per-SIMD kernel)");
   }
   dk_prof_end(stream);

@@ -299,7 +299,7 @@ bool dk_attention5_eligible(const AttnParams& p) {
   return p.D == 128 && p.bias == nullptr && p.S % 256 == 0 && p.S >= 12 * 64 && (size_t)p.S * p.ld * 2 < (1ull << 32);
 }
 
-int dk_launch_attention5(const AttnParams& p_in, hipStream_t stream) {
+int dk_launch_attention5(const AttnParams& p_in, AttnWs ws, hipStream_t stream) {
   DK_REQUIRE(dk_attention5_eligible(p_in), "attention5: head_dim 128, no score bias, S a multiple of 256 and >= 768");
   AttnParams p = p_in;
   const bool qfuse = p.qn_a != nullptr || p.q_rope != nullptr;
@@ -319,9 +319,8 @@ int dk_launch_attention5(const AttnParams& p_in, hipStream_t stream) {
       if ((p.S / 256) / s < 3) break;  // >= 12 tiles per range
       if (g_dk_attn5_split > 0 ? s == g_dk_attn5_split : (tail * s <= n_cu && tail * s * 10 >= n_cu * 6)) split = s;
     }
-    void* ws = dk_get_attention_workspace();
-    if (split > 1 && (ws == nullptr || dk_get_attention_workspace_bytes() < (size_t)tail * split * (65536 + 2048))) split = 1;
-    p.a5_ws = ws;
+    if (split > 1 && (ws.p == nullptr || ws.bytes < (size_t)tail * split * (65536 + 2048))) split = 1;
+    p.a5_ws = ws.p;
   }
   p.a5_split = split;
   p.a5_whole = split > 1 ? nb - tail : nb;

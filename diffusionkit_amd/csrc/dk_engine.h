@@ -37,28 +37,17 @@ struct Carver {
   }
 };
 
-// Element type of the launches an entry point builds: DK_DTYPE_BF16 unless an fp16 engine's call (MmditCallScope) or an *_f16 operator entry is
-// on the stack of this host thread (same discipline as g_linear_ws below: everything is enqueued before the call returns)
-extern thread_local int g_elem_dtype;  // abi_ops.hip
-struct ElemScope {
-  int prev;
-  explicit ElemScope(int dtype) : prev(g_elem_dtype) { g_elem_dtype = dtype; }
-  ~ElemScope() { g_elem_dtype = prev; }
+// What an entry point knows about the launches it builds and hands down to whatever builds one: plain arguments, no state outside the call.
+// Two engines, on one host thread in turn or on two threads / streams at once, therefore never share an element type or a split region.  (A
+// single engine must not be driven from two streams concurrently: its activations live in one workspace anyway.)
+struct LaunchCtx {
+  hipStream_t st;
+  int dtype;            // element type of every launch: DK_DTYPE_BF16 / DK_DTYPE_F16
+  void* kws = nullptr;  // the caller's K-split region (fp32 slabs + flags, dk_gemm_split_workspace_bytes()) for Linear::split_ws, or null
+  AttnWs aws;           // ... and its attention key-split region for dk_launch_attention (empty: no launch is split)
 };
-// an elementwise launcher in the element type in force (dk_elem_launchers.h: same signature in both)
-#define DK_EL(fn) (g_elem_dtype == DK_DTYPE_F16 ? dk_f16::fn : fn)
-
-// Split workspace (fp32 slabs + flags) handed to the GEMMs an engine call builds: every dk_mmdit_* entry point sets it to ITS
-// engine's region (carved from that engine's workspace) before it enqueues anything and all launches of the call are
-// enqueued before it returns, so two engines -- on one host thread in turn, or on two threads / streams at once
-// (thread_local) -- never share a flag region.  A single engine must not be driven from two streams concurrently (its
-// activations live in one workspace anyway).
-extern thread_local void* g_linear_ws;  // abi_ops.hip
-struct LinearWsScope {  // an engine call's GEMMs split through that engine's region; the previous setting comes back afterwards
-  void* prev;
-  explicit LinearWsScope(void* ws) : prev(g_linear_ws) { g_linear_ws = ws; }
-  ~LinearWsScope() { g_linear_ws = prev; }
-};
+// an elementwise launcher in element type dtype (dk_elem_launchers.h: same signature in both)
+#define DK_EL(dtype, fn) ((dtype) == DK_DTYPE_F16 ? dk_f16::fn : fn)
 
 inline int need(const std::unordered_map<std::string, const void*>& named, const std::string& name, const bf16_t** out, bool optional = false) {
   auto it = named.find(name);
@@ -96,33 +85,38 @@ inline void set_gate_res(P& p, const bf16_t* gate, int gate_seg_len, int gate_st
   p.res = res.p; p.ldr = res.ld; p.r_seg_len = res.seg_len > 0 ? res.seg_len : p.M; p.r_seg_stride = res.seg_stride;
 }
 
-// C = epi(A @ W^T + bias): W [N, ldw >= K] (0: K), element type of the call in force.  Launch with dk_launch_gemm / dk_launch_gemm_pair.
+// C = epi(A @ W^T + bias) in element type dtype_: W [N, ldw >= K] (0: K).  Launch with dk_launch_gemm / dk_launch_gemm_pair.
 struct Linear : GemmParams {
-  Linear(Rows A_, const bf16_t* W_, const bf16_t* bias_, Rows C_, int M_, int N_, int K_, int epi_, int ldw_ = 0) {
+  Linear(int dtype_, Rows A_, const bf16_t* W_, const bf16_t* bias_, Rows C_, int M_, int N_, int K_, int epi_, int ldw_ = 0) {
     memset(static_cast<GemmParams*>(this), 0, sizeof(GemmParams));
     A = A_.p; W = W_; C = C_.p; bias = bias_;
     M = M_; N = N_; K = K_; lda = A_.ld; ldc = C_.ld; ldw = ldw_;
     a_seg_len = A_.seg_len > 0 ? A_.seg_len : M; a_seg_stride = A_.seg_stride;
     c_seg_len = C_.seg_len > 0 ? C_.seg_len : M; c_seg_stride = C_.seg_stride;
     r_seg_len = gate_seg_len = M;
-    alpha = 1.0f; epi = epi_; dtype = g_elem_dtype;
+    alpha = 1.0f; epi = epi_; dtype = dtype_;
   }
   Linear& gate_res(const bf16_t* gate_, int gate_seg_len_, int gate_stride_, Rows res_) {
     set_gate_res(*this, gate_, gate_seg_len_, gate_stride_, res_);
     return *this;
   }
-  // with the calling engine's K-split workspace: dk_gemm_route may then cut a launch that fills a fraction of a round of the CUs along K
-  // (another summation order) -- which launches carry it is part of their results
-  Linear& split_ws() {
-    if (g_linear_ws) { workspace = g_linear_ws; workspace_bytes = dk_gemm_split_workspace_bytes(); }
+  // with the calling engine's K-split region (LaunchCtx::kws): dk_gemm_route may then cut a launch that fills a fraction of a round of the CUs
+  // along K (another summation order) -- which launches carry it is part of their results
+  Linear& split_ws(void* kws) {
+    if (kws) { workspace = kws; workspace_bytes = dk_gemm_split_workspace_bytes(); }
     return *this;
   }
 };
 
-// ---- abi_ops.hip, used by the engines -------------------------------------------------------------------------------------------
+// ---- abi_ops.hip, used by the engines: the typed implementations behind the exported *_bf16 / *_f16 operator entries --------------------
 // workspace: optional K-split scratch (dk_gemm_split_workspace_bytes) for stages whose tiles fill only half the CUs; rec: record the route
 // instead of launching (dk_conv3x3_plan)
-int conv3x3_launch(const dk_conv_desc* d, void* workspace, hipStream_t stream, dk_gemm_plan_t* rec = nullptr);
+int conv3x3_launch(int dtype, const dk_conv_desc* d, void* workspace, hipStream_t stream, dk_gemm_plan_t* rec = nullptr);
 // transpose of every image's V into [512, Tp] rows (zero-padded), then the flash kernel
-int attention_d512(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int B, int T, int ld, int ldo, float scale, bf16_t* vt,
-                   hipStream_t st);
+int attention_d512(int dtype, const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int B, int T, int ld, int ldo, float scale,
+                   bf16_t* vt, hipStream_t st);
+// scratch layout shared by the two: [partials: B * n * 2G][mean_rstd: B * G * 2], n = the larger of 1024 and the caller's n_partial
+int groupnorm_launch(int dtype, const void* x, void* y, int B, long HW, int C, int G, const void* gamma, const void* beta, float eps,
+                     int fuse_silu, float* scratch, hipStream_t st);
+int groupnorm_table_launch(int dtype, const void* x, int B, long HW, int C, int G, const void* gamma, const void* beta, float eps,
+                           float* scratch, int n_partial, float* scale_shift, hipStream_t st);

@@ -208,7 +208,8 @@ struct AttnParams {
   int qn_split = 0;
   float qn_eps = 1e-6f;
   const float* q_rope = nullptr;
-  // lab only: trace buffer of attention4.hip's DK4_TRACE builds (scripts/attn_trace.py)
+  // the caller's workspace region, filled in by dk_launch_attention when null; no shipped kernel reads it: attention4.hip's DK4_TRACE lab
+  // builds stamp their trace into it (scripts/attn_trace.py)
   void* bal_ws = nullptr;
   // optional MX-fp8 copy of the output (fp8_linears: the o-projection's activation operand): row (b*S + s) of O8 at o8_ld bytes
   // per row, head h at byte column h*D; E8M0 scales of 32-column blocks in O8_scales (dk_mx_scale_index over o8_nblk 128-row
@@ -228,14 +229,17 @@ struct AttnParams {
   // element type of Q, K, V, O and the query-norm weights: DK_DTYPE_BF16 (0) or DK_DTYPE_F16 (1: D = 64, the lean kernel)
   int dtype = 0;
 };
-void dk_set_attention_workspace(void* ws, size_t bytes = 0);  // attention.hip: thread-local workspace, picked up by dk_launch_attention
-void* dk_get_attention_workspace();
-size_t dk_get_attention_workspace_bytes();
+// the region the key-split workgroups of attention5.hip leave their partial results in (dk_attention_workspace_bytes(); 256-byte aligned): the
+// caller's own -- an engine's carve, or what dk_attention_set_workspace gave the stand-alone entries.  Empty, or too small for a launch: no split
+struct AttnWs {
+  void* p = nullptr;
+  size_t bytes = 0;
+};
 extern int g_dk_attn_mode;
-int dk_launch_attention(const AttnParams& p, hipStream_t stream);
+int dk_launch_attention(const AttnParams& p, AttnWs ws, hipStream_t stream);
 int dk_launch_attention4(const AttnParams& p, hipStream_t stream);             // attention4.hip (the waves of a SIMD in opposite phases; D = 128, no score bias)
 bool dk_attention5_eligible(const AttnParams& p);                              // attention5.hip (one wave per SIMD, asm tile loop; D = 128, S % 256 == 0, no score bias)
-int dk_launch_attention5(const AttnParams& p, hipStream_t stream);
+int dk_launch_attention5(const AttnParams& p, AttnWs ws, hipStream_t stream);
 extern int g_dk_attn5_split;
 
 // ---- single-head D = 512 attention of the VAE's mid block (attention512.hip) -------------------------------

@@ -67,6 +67,8 @@ struct dk_mmdit {
   long rows8 = 0;
   // element type of every bound tensor, activation buffer and of the token / text / pooled I/O (dk_mmdit_set_activation_dtype): sizes are the same
   int dtype = DK_DTYPE_BF16;
+  // what a call on `stream` hands its launches: this engine's element type and ITS regions (for D = 64 no attention region: unsplit launches)
+  LaunchCtx ctx(void* stream) const { return LaunchCtx{S_(stream), dtype, GWS, AttnWs{AWS, AWS_bytes}}; }
   bool fp8() const { return cfg.fp8_linears != 0; }
   // precision policy: the first n_bf16() double-stream blocks keep bf16 Linears under fp8_linears (global block index = double-block index)
   int n_bf16() const { return fp8() ? (cfg.fp8_bf16_double_blocks < cfg.depth_multimodal ? cfg.fp8_bf16_double_blocks : cfg.depth_multimodal) : 0; }
@@ -339,54 +341,52 @@ extern "C" int dk_mmdit_cache_modulation_params(dk_mmdit* m, const void* pooled,
   DK_REQUIRE(m && m->prepared, "dk_mmdit_prepare must be called first");
   DK_REQUIRE(n > 0 && n <= m->n_t, "more timesteps than the workspace was prepared for");
   hipStream_t st = S_(stream);
-  LinearWsScope ws_scope(m->GWS);
-  ElemScope elem_scope(m->dtype);
+  const int dt = m->dtype;
   const int h = m->h(), B = m->B, P = m->cfg.pooled_text_embed_dim, Fq = m->cfg.frequency_embed_dim;
   DK_CHECK_HIP(hipMemcpyAsync(m->tdev, timesteps_host, (size_t)n * 4, hipMemcpyHostToDevice, st));
-  DK_TRY(DK_EL(dk_launch_timestep_embedding)(m->tdev, n, 1, Fq, (float)m->cfg.max_period, m->cfg.embed_dtype, m->temb, st));
+  DK_TRY(DK_EL(dt, dk_launch_timestep_embedding)(m->tdev, n, 1, Fq, (float)m->cfg.max_period, m->cfg.embed_dtype, m->temb, st));
   // t_embedder / y_embedder: Linear -> SiLU -> Linear (mmdit.py:352-392)
-  DK_TRY(dk_launch_gemm(Linear(dense(m->temb, Fq), m->t0_w, m->t0_b, dense(m->t1, h), n, h, Fq, DK_EPI_BIAS_SILU), st));
-  DK_TRY(dk_launch_gemm(Linear(dense(m->t1, h), m->t2_w, m->t2_b, dense(m->tvec, h), n, h, h, DK_EPI_BIAS), st));
-  DK_TRY(dk_launch_gemm(Linear(dense((const bf16_t*)pooled, P), m->y0_w, m->y0_b, dense(m->y1, h), B, h, P, DK_EPI_BIAS_SILU), st));
-  DK_TRY(dk_launch_gemm(Linear(dense(m->y1, h), m->y2_w, m->y2_b, dense(m->yvec, h), B, h, h, DK_EPI_BIAS), st));
+  DK_TRY(dk_launch_gemm(Linear(dt, dense(m->temb, Fq), m->t0_w, m->t0_b, dense(m->t1, h), n, h, Fq, DK_EPI_BIAS_SILU), st));
+  DK_TRY(dk_launch_gemm(Linear(dt, dense(m->t1, h), m->t2_w, m->t2_b, dense(m->tvec, h), n, h, h, DK_EPI_BIAS), st));
+  DK_TRY(dk_launch_gemm(Linear(dt, dense((const bf16_t*)pooled, P), m->y0_w, m->y0_b, dense(m->y1, h), B, h, P, DK_EPI_BIAS_SILU), st));
+  DK_TRY(dk_launch_gemm(Linear(dt, dense(m->y1, h), m->y2_w, m->y2_b, dense(m->yvec, h), B, h, h, DK_EPI_BIAS), st));
   if (m->cfg.guidance_embed) {
     // FLUX.1-dev guidance embedding (MLPEmbedder, mmdit.py:31-36,945-955): g = guidance_in(timestep_embedding(1000 * guidance)),
     // added to the pooled-text embedding of every batch row, hence to every modulation vector
     const float gt = 1000.0f * m->guidance;
     DK_CHECK_HIP(hipMemcpyAsync(m->tdev, &gt, 4, hipMemcpyHostToDevice, st));  // (tdev[0] was consumed by the launch above, same stream)
-    DK_TRY(DK_EL(dk_launch_timestep_embedding)(m->tdev, 1, 1, Fq, (float)m->cfg.max_period, m->cfg.embed_dtype, m->gemb, st));
-    DK_TRY(dk_launch_gemm(Linear(dense(m->gemb, Fq), m->g0_w, m->g0_b, dense(m->g1, h), 1, h, Fq, DK_EPI_BIAS_SILU), st));
-    DK_TRY(dk_launch_gemm(Linear(dense(m->g1, h), m->g2_w, m->g2_b, dense(m->gvec, h), 1, h, h, DK_EPI_BIAS), st));
-    DK_TRY(DK_EL(dk_launch_add)(m->yvec, m->gvec, 1, m->yvec, B, h, st));  // y[b] += g
+    DK_TRY(DK_EL(dt, dk_launch_timestep_embedding)(m->tdev, 1, 1, Fq, (float)m->cfg.max_period, m->cfg.embed_dtype, m->gemb, st));
+    DK_TRY(dk_launch_gemm(Linear(dt, dense(m->gemb, Fq), m->g0_w, m->g0_b, dense(m->g1, h), 1, h, Fq, DK_EPI_BIAS_SILU), st));
+    DK_TRY(dk_launch_gemm(Linear(dt, dense(m->g1, h), m->g2_w, m->g2_b, dense(m->gvec, h), 1, h, h, DK_EPI_BIAS), st));
+    DK_TRY(DK_EL(dt, dk_launch_add)(m->yvec, m->gvec, 1, m->yvec, B, h, st));  // y[b] += g
   }
   // vec[step*B + b] = silu(y[b] + t[step]); adaLN_modulation = SiLU -> Linear (mmdit.py:94-96,430-435)
-  DK_TRY(DK_EL(dk_launch_add)(m->yvec, m->tvec, n, m->vec, n * B, h, st));
-  DK_TRY(DK_EL(dk_launch_silu)(m->vec, m->vec, (long)n * B * h, st));
+  DK_TRY(DK_EL(dt, dk_launch_add)(m->yvec, m->tvec, n, m->vec, n * B, h, st));
+  DK_TRY(DK_EL(dt, dk_launch_silu)(m->vec, m->vec, (long)n * B * h, st));
   const int Nmod = m->mod_rows() * h;
-  DK_TRY(dk_launch_gemm(Linear(dense(m->vec, h), m->adaln_w, m->adaln_b, dense(m->MOD, Nmod), n * B, Nmod, h, DK_EPI_BIAS), st));
+  DK_TRY(dk_launch_gemm(Linear(dt, dense(m->vec, h), m->adaln_w, m->adaln_b, dense(m->MOD, Nmod), n * B, Nmod, h, DK_EPI_BIAS), st));
   m->mod_ready = true;
   return 0;
 }
 
 extern "C" int dk_mmdit_cache_context(dk_mmdit* m, const void* text, void* stream) {
   DK_REQUIRE(m && m->prepared && text, "prepare must precede cache_context");
-  LinearWsScope ws_scope(m->GWS);
-  ElemScope elem_scope(m->dtype);
   const int M = m->B * m->S_t, T = m->cfg.token_level_text_embed_dim;
   // (no split workspace: like the per-step form in dk_mmdit_forward, whose result it stands for)
-  DK_TRY(dk_launch_gemm(Linear(dense((const bf16_t*)text, T), m->ctx_w, m->ctx_b, dense(m->CTXE, m->h()), M, m->h(), T, DK_EPI_BIAS), S_(stream)));
+  DK_TRY(dk_launch_gemm(Linear(m->dtype, dense((const bf16_t*)text, T), m->ctx_w, m->ctx_b, dense(m->CTXE, m->h()), M, m->h(), T, DK_EPI_BIAS), S_(stream)));
   m->ctx_ready = true;
   return 0;
 }
 
 // FinalLayer (mmdit.py:767-796) on the image rows
-static int mmdit_final_layer(dk_mmdit* m, const bf16_t* mod_step, bf16_t* tokens_out, hipStream_t st) {
+static int mmdit_final_layer(dk_mmdit* m, const bf16_t* mod_step, bf16_t* tokens_out, const LaunchCtx& L) {
+  const hipStream_t st = L.st;
   const int h = m->h(), B = m->B, S = m->S, S_t = m->S_t, S_i = m->S_i, F = m->F();
   const int mod_stride = m->mod_rows() * h;
   const bf16_t* mod_fin = mod_step + (size_t)m->mod_offset(3, 0) * h;
-  DK_TRY(DK_EL(dk_launch_ln_modulate)(m->X + (size_t)S_t * h, h, m->XN, h, B * S_i, h, mod_fin, mod_fin + h, mod_stride, S_i, S_i, S,
+  DK_TRY(DK_EL(L.dtype, dk_launch_ln_modulate)(m->X + (size_t)S_t * h, h, m->XN, h, B * S_i, h, mod_fin, mod_fin + h, mod_stride, S_i, S_i, S,
                                m->cfg.layer_norm_eps, st));
-  return dk_launch_gemm(Linear(dense(m->XN, h), m->final_w, m->final_b, dense(tokens_out, F), B * S_i, F, h, DK_EPI_BIAS), st);
+  return dk_launch_gemm(Linear(L.dtype, dense(m->XN, h), m->final_w, m->final_b, dense(tokens_out, F), B * S_i, F, h, DK_EPI_BIAS), st);
 }
 
 // ---- the transformer blocks -----------------------------------------------------------------------------------------------------
@@ -452,7 +452,8 @@ static AttnParams joint_attention(const dk_mmdit* m, const BlockCtx& c, bf16_t* 
 // MultiModalTransformerBlock i (mmdit.py:568-675), bf16 Linears.  The two streams run the same Linear shapes on different weights; their
 // GEMMs are issued as pairs so that the 256 x 256 kernel can place the text tiles in the same wave as the image tiles
 // (dk_launch_gemm_pair).  Every block Linear carries the engine's split workspace.
-static int double_block_bf16(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t* mod_step, hipStream_t st) {
+static int double_block_bf16(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t* mod_step, const LaunchCtx& L) {
+  const hipStream_t st = L.st;
   const dk_mmdit_config& cf = m->cfg;
   const int h = c.h, S = c.S, S_t = c.S_t, S_i = c.S_i, Mi = c.Mi, Mt = c.Mt, r = cf.mlp_ratio, ldh = m->ldh, mod_stride = c.mod_stride;
   const bf16_t *mod_img = block_mod(m, mod_step, 0, i), *mod_txt = block_mod(m, mod_step, 1, i);
@@ -463,10 +464,10 @@ static int double_block_bf16(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t
   const Rows HID_img = dense(m->HID, ldh), HID_txt = dense(m->HID + (size_t)Mi * ldh, ldh);  // MLP hidden of both streams
   // pre_sdpa (mmdit.py:440-519): LN-modulate, q/k/v projection, QK-norm (+ RoPE)
   // (image and text stream of each elementwise stage in ONE launch: the 256 text rows do not run alone on the chip)
-  DK_TRY(DK_EL(dk_launch_ln_modulate2)(X_img.p, XN_img.p, Mi, mod_img, mod_img + h, S_i, X_txt.p, XN_txt.p, Mt, mod_txt, mod_txt + h, S_t, h, h, h,
+  DK_TRY(DK_EL(L.dtype, dk_launch_ln_modulate2)(X_img.p, XN_img.p, Mi, mod_img, mod_img + h, S_i, X_txt.p, XN_txt.p, Mt, mod_txt, mod_txt + h, S_t, h, h, h,
                                 mod_stride, S, cf.layer_norm_eps, st));
-  Linear qkv_img = Linear(XN_img, wi.qkv_w, wi.qkv_b, m->img(m->QKV, 3 * h), Mi, 3 * h, h, DK_EPI_BIAS).split_ws();
-  Linear qkv_txt = Linear(XN_txt, wt.qkv_w, wt.qkv_b, m->txt(m->QKV, 3 * h), Mt, 3 * h, h, DK_EPI_BIAS).split_ws();
+  Linear qkv_img = Linear(L.dtype, XN_img, wi.qkv_w, wi.qkv_b, m->img(m->QKV, 3 * h), Mi, 3 * h, h, DK_EPI_BIAS).split_ws(L.kws);
+  Linear qkv_txt = Linear(L.dtype, XN_txt, wt.qkv_w, wt.qkv_b, m->txt(m->QKV, 3 * h), Mt, 3 * h, h, DK_EPI_BIAS).split_ws(L.kws);
   // QKNorm + RoPE: the keys in the projection's tail (or one pass over the buffer), the queries inside the attention kernel's Q load
   const bool kf = keys_in_tail(wi, &wt);
   if (kf) {
@@ -475,32 +476,32 @@ static int double_block_bf16(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t
   }
   DK_TRY(dk_launch_gemm_pair(qkv_img, qkv_txt, st));
   if (!kf)
-    DK_TRY(DK_EL(dk_launch_qk_norm_rope2)(m->QKV + (size_t)S_t * 3 * h, Mi, wi.qn, wi.kn, S_i, S_t, m->QKV, Mt, wt.qn, wt.kn, S_t, 0, 3 * h, 0, h,
+    DK_TRY(DK_EL(L.dtype, dk_launch_qk_norm_rope2)(m->QKV + (size_t)S_t * 3 * h, Mi, wi.qn, wi.kn, S_i, S_t, m->QKV, Mt, wt.qn, wt.kn, S_t, 0, 3 * h, 0, h,
                                    cf.num_heads, m->D(), 1e-6f, c.rope, S, st, fuse_q()));
-  DK_TRY(dk_launch_attention(joint_attention(m, c, m->ATT, h, wt, &wi), st));
+  DK_TRY(dk_launch_attention(joint_attention(m, c, m->ATT, h, wt, &wi), L.aws, st));
   // post_sdpa, sequential form (mmdit.py:537-548): residual += gate_attn * o_proj(attn)
-  const Linear o_img = Linear(m->img(m->ATT, h), wi.o_w, wi.o_b, X_img, Mi, h, h, DK_EPI_GATE_RES)
-                           .gate_res(mod_img + 2 * h, S_i, mod_stride, X_img).split_ws();
+  const Linear o_img = Linear(L.dtype, m->img(m->ATT, h), wi.o_w, wi.o_b, X_img, Mi, h, h, DK_EPI_GATE_RES)
+                           .gate_res(mod_img + 2 * h, S_i, mod_stride, X_img).split_ws(L.kws);
   if (txt_post) {
-    const Linear o_txt = Linear(m->txt(m->ATT, h), wt.o_w, wt.o_b, X_txt, Mt, h, h, DK_EPI_GATE_RES)
-                             .gate_res(mod_txt + 2 * h, S_t, mod_stride, X_txt).split_ws();
+    const Linear o_txt = Linear(L.dtype, m->txt(m->ATT, h), wt.o_w, wt.o_b, X_txt, Mt, h, h, DK_EPI_GATE_RES)
+                             .gate_res(mod_txt + 2 * h, S_t, mod_stride, X_txt).split_ws(L.kws);
     DK_TRY(dk_launch_gemm_pair(o_img, o_txt, st));
   } else {
     DK_TRY(dk_launch_gemm(o_img, st));
   }
   // residual += gate_mlp * fc2(gelu(fc1(LN-mod(residual))))
   if (txt_post)
-    DK_TRY(DK_EL(dk_launch_ln_modulate2)(X_img.p, XN_img.p, Mi, mod_img + 3 * h, mod_img + 4 * h, S_i, X_txt.p, XN_txt.p, Mt, mod_txt + 3 * h,
+    DK_TRY(DK_EL(L.dtype, dk_launch_ln_modulate2)(X_img.p, XN_img.p, Mi, mod_img + 3 * h, mod_img + 4 * h, S_i, X_txt.p, XN_txt.p, Mt, mod_txt + 3 * h,
                                   mod_txt + 4 * h, S_t, h, h, h, mod_stride, S, cf.layer_norm_eps, st));
   else
-    DK_TRY(DK_EL(dk_launch_ln_modulate)(X_img.p, h, XN_img.p, h, Mi, h, mod_img + 3 * h, mod_img + 4 * h, mod_stride, S_i, S_i, S, cf.layer_norm_eps, st));
-  const Linear fc1_img = Linear(XN_img, wi.fc1_w, wi.fc1_b, HID_img, Mi, r * h, h, DK_EPI_BIAS_GELU).split_ws();
-  const Linear fc2_img = Linear(HID_img, wi.fc2_w, wi.fc2_b, X_img, Mi, h, r * h, DK_EPI_GATE_RES, ldh)
-                             .gate_res(mod_img + 5 * h, S_i, mod_stride, X_img).split_ws();
+    DK_TRY(DK_EL(L.dtype, dk_launch_ln_modulate)(X_img.p, h, XN_img.p, h, Mi, h, mod_img + 3 * h, mod_img + 4 * h, mod_stride, S_i, S_i, S, cf.layer_norm_eps, st));
+  const Linear fc1_img = Linear(L.dtype, XN_img, wi.fc1_w, wi.fc1_b, HID_img, Mi, r * h, h, DK_EPI_BIAS_GELU).split_ws(L.kws);
+  const Linear fc2_img = Linear(L.dtype, HID_img, wi.fc2_w, wi.fc2_b, X_img, Mi, h, r * h, DK_EPI_GATE_RES, ldh)
+                             .gate_res(mod_img + 5 * h, S_i, mod_stride, X_img).split_ws(L.kws);
   if (txt_post) {
-    const Linear fc1_txt = Linear(XN_txt, wt.fc1_w, wt.fc1_b, HID_txt, Mt, r * h, h, DK_EPI_BIAS_GELU).split_ws();
-    const Linear fc2_txt = Linear(HID_txt, wt.fc2_w, wt.fc2_b, X_txt, Mt, h, r * h, DK_EPI_GATE_RES, ldh)
-                               .gate_res(mod_txt + 5 * h, S_t, mod_stride, X_txt).split_ws();
+    const Linear fc1_txt = Linear(L.dtype, XN_txt, wt.fc1_w, wt.fc1_b, HID_txt, Mt, r * h, h, DK_EPI_BIAS_GELU).split_ws(L.kws);
+    const Linear fc2_txt = Linear(L.dtype, HID_txt, wt.fc2_w, wt.fc2_b, X_txt, Mt, h, r * h, DK_EPI_GATE_RES, ldh)
+                               .gate_res(mod_txt + 5 * h, S_t, mod_stride, X_txt).split_ws(L.kws);
     DK_TRY(dk_launch_gemm_pair(fc1_img, fc1_txt, st));
     DK_TRY(dk_launch_gemm_pair(fc2_img, fc2_txt, st));
   } else {
@@ -511,25 +512,26 @@ static int double_block_bf16(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t
 }
 
 // UnifiedTransformerBlock i (mmdit.py:693-751), bf16 Linears: parallel attention + MLP
-static int single_block_bf16(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t* mod_step, hipStream_t st) {
+static int single_block_bf16(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t* mod_step, const LaunchCtx& L) {
+  const hipStream_t st = L.st;
   const dk_mmdit_config& cf = m->cfg;
   const int h = c.h, S = c.S, M = c.B * c.S, r = cf.mlp_ratio, ldcat = m->ldcat;
   const StreamW& w = m->single[i];
   const bf16_t* mod = block_mod(m, mod_step, 2, i);
   const Rows X = dense(m->X, h), CAT = dense(m->CAT, ldcat);
-  DK_TRY(DK_EL(dk_launch_ln_modulate)(m->X, h, m->XN, h, M, h, mod, mod + h, c.mod_stride, S, M, 0, cf.layer_norm_eps, st));
+  DK_TRY(DK_EL(L.dtype, dk_launch_ln_modulate)(m->X, h, m->XN, h, M, h, mod, mod + h, c.mod_stride, S, M, 0, cf.layer_norm_eps, st));
   {  // linear1: [q|k|v] -> QKV, gelu(fc1) -> CAT[:, h:], one pass over the modulated activations
-    Linear l1 = Linear(dense(m->XN, h), w.qkv_w, w.qkv_b, dense(m->QKV, 3 * h), M, (3 + r) * h, h, DK_EPI_BIAS).split_ws();
+    Linear l1 = Linear(L.dtype, dense(m->XN, h), w.qkv_w, w.qkv_b, dense(m->QKV, 3 * h), M, (3 + r) * h, h, DK_EPI_BIAS).split_ws(L.kws);
     l1.n_split = 3 * h; l1.C2 = m->CAT + h; l1.ldc2 = ldcat; l1.epi2 = DK_EPI_BIAS_GELU;
     if (keys_in_tail(w, nullptr)) set_key_norm(l1, w.kn, w.qn, h, m->D(), c.rope, 0, S);
     DK_TRY(dk_launch_gemm(l1, st));
   }
   if (!keys_in_tail(w, nullptr))
-    DK_TRY(DK_EL(dk_launch_qk_norm_rope)(m->QKV, 3 * h, 0, h, M, cf.num_heads, m->D(), w.qn, w.kn, 1e-6f, c.rope, S, S, 0, S, st, fuse_q()));
-  DK_TRY(dk_launch_attention(joint_attention(m, c, m->CAT, ldcat, w, nullptr), st));
+    DK_TRY(DK_EL(L.dtype, dk_launch_qk_norm_rope)(m->QKV, 3 * h, 0, h, M, cf.num_heads, m->D(), w.qn, w.kn, 1e-6f, c.rope, S, S, 0, S, st, fuse_q()));
+  DK_TRY(dk_launch_attention(joint_attention(m, c, m->CAT, ldcat, w, nullptr), L.aws, st));
   // x += gate * ([attn | gelu] @ [o_proj | fc2]^T + bias)   (one bias: quirk Q8)
   // (with the split workspace: below 1024 x 1024 the launch is a fraction of a round of the CUs and is cut along K)
-  const Linear l2 = Linear(CAT, w.l2_w, w.l2_b, X, M, h, (1 + r) * h, DK_EPI_GATE_RES, ldcat).gate_res(mod + 2 * h, S, c.mod_stride, X).split_ws();
+  const Linear l2 = Linear(L.dtype, CAT, w.l2_w, w.l2_b, X, M, h, (1 + r) * h, DK_EPI_GATE_RES, ldcat).gate_res(mod + 2 * h, S, c.mod_stride, X).split_ws(L.kws);
   return dk_launch_gemm(l2, st);
 }
 
@@ -547,7 +549,7 @@ static GemmF8Params f8_params(const dk_mmdit* m, const unsigned char* abuf, cons
   p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = ldw;
   p.a_seg_len = a_seg_len; p.a_seg_stride = a_seg_stride; p.a_row0 = a_row0; p.sa_nblk = m->nblk;
   p.epi = epi;
-  if (g_linear_ws) { p.workspace = g_linear_ws; p.workspace_bytes = dk_gemm_split_workspace_bytes(); }
+  if (m->GWS) { p.workspace = m->GWS; p.workspace_bytes = dk_gemm_split_workspace_bytes(); }
   return p;
 }
 static void f8_out_bf16(GemmF8Params& p, Rows C) {
@@ -562,7 +564,8 @@ static void f8_out_hid8(GemmF8Params& p, const dk_mmdit* m, int c_row0) {
 }
 
 // MultiModalTransformerBlock i on the fp8 GEMM: the streams' Linears as pairs of one launch (dk_launch_gemm256f8)
-static int double_block_fp8(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t* mod_step, hipStream_t st) {
+static int double_block_fp8(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t* mod_step, const LaunchCtx& L) {
+  const hipStream_t st = L.st;
   const dk_mmdit_config& cf = m->cfg;
   const int h = c.h, S = c.S, S_t = c.S_t, S_i = c.S_i, Mi = c.Mi, Mt = c.Mt, T0 = c.T0, r = cf.mlp_ratio, ldh8 = m->ldh8, mod_stride = c.mod_stride;
   const bf16_t *mod_img = block_mod(m, mod_step, 0, i), *mod_txt = block_mod(m, mod_step, 1, i);
@@ -589,7 +592,7 @@ static int double_block_fp8(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t*
                                    cf.num_heads, m->D(), 1e-6f, c.rope, S, st, fuse_q()));
   AttnParams ap = joint_attention(m, c, m->ATT, h, wt, &wi, m->ATT8, m->SATT, h);  // (ATT8: the o-projection's operand)
   if (c.att_split) { ap.o8_split = S_t; ap.o8_txt_row0 = T0; }
-  DK_TRY(dk_launch_attention(ap, st));
+  DK_TRY(dk_launch_attention(ap, L.aws, st));
   // post_sdpa (mmdit.py:537-548): residual += gate_attn * o_proj(attn)
   {
     GemmF8Params oi = c.att_split ? f8_params(m, m->ATT8, m->SATT, h, 0, Mi, 0, wi.o_w8, h, wi.o_ws, wi.o_b, Mi, h, h, DK_EPI_GATE_RES)
@@ -623,7 +626,8 @@ static int double_block_fp8(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t*
 }
 
 // UnifiedTransformerBlock i on the fp8 GEMM
-static int single_block_fp8(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t* mod_step, hipStream_t st) {
+static int single_block_fp8(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t* mod_step, const LaunchCtx& L) {
+  const hipStream_t st = L.st;
   const dk_mmdit_config& cf = m->cfg;
   const int h = c.h, S = c.S, M = c.B * c.S, r = cf.mlp_ratio, ldcat8 = m->ldcat8;
   const StreamW& w = m->single[i];
@@ -641,7 +645,7 @@ static int single_block_fp8(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t*
   if (!keys_in_tail(w, nullptr))
     DK_TRY(dk_launch_qk_norm_rope(m->QKV, 3 * h, 0, h, M, cf.num_heads, m->D(), w.qn, w.kn, 1e-6f, c.rope, S, S, 0, S, st, fuse_q()));
   // (the MX-fp8 copy: the [attn | gelu] operand of linear2, columns [0, h))
-  DK_TRY(dk_launch_attention(joint_attention(m, c, m->ATT, h, w, nullptr, m->HC8, m->SCAT, ldcat8), st));
+  DK_TRY(dk_launch_attention(joint_attention(m, c, m->ATT, h, w, nullptr, m->HC8, m->SCAT, ldcat8), L.aws, st));
   // x += gate * ([attn | gelu] @ [o_proj | fc2]^T + bias)   (one bias: quirk Q8)
   GemmF8Params l2 = f8_params(m, m->HC8, m->SCAT, ldcat8, 0, M, 0, w.l2_w8, ldcat8, w.l2_ws, w.l2_b, M, h, (1 + r) * h, DK_EPI_GATE_RES);
   f8_out_bf16(l2, X);
@@ -651,40 +655,25 @@ static int single_block_fp8(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t*
 
 // Blocks [first, first + count) of the global order (double blocks 0 .. depth_multimodal - 1, then single blocks) on the joint residual
 // stream m->X: the bf16 double blocks of the precision policy on the bf16 path, everything else on the model's own
-static int mmdit_blocks(dk_mmdit* m, const bf16_t* mod_step, int first, int count, hipStream_t st) {
+static int mmdit_blocks(dk_mmdit* m, const bf16_t* mod_step, int first, int count, const LaunchCtx& L) {
   const BlockCtx c = block_ctx(m);
   const int n_double = m->cfg.depth_multimodal;
   for (int g = first; g < first + count; ++g) {
     const bool f8 = m->fp8() && g >= m->n_bf16();
     if (g < n_double)
-      DK_TRY((f8 ? double_block_fp8 : double_block_bf16)(m, c, g, mod_step, st));
+      DK_TRY((f8 ? double_block_fp8 : double_block_bf16)(m, c, g, mod_step, L));
     else
-      DK_TRY((f8 ? single_block_fp8 : single_block_bf16)(m, c, g - n_double, mod_step, st));
+      DK_TRY((f8 ? single_block_fp8 : single_block_bf16)(m, c, g - n_double, mod_step, L));
   }
   return 0;
 }
-
-struct AttnWsScope {  // an engine call's attention launches split through that engine's region; the host thread's own setting comes back
-  void* prev;
-  size_t prev_bytes;
-  AttnWsScope(void* ws, size_t bytes) : prev(dk_get_attention_workspace()), prev_bytes(dk_get_attention_workspace_bytes()) {
-    dk_set_attention_workspace(ws, bytes);  // (an engine without a region -- D = 64 -- runs unsplit: never the thread's buffer on another engine's stream)
-  }
-  ~AttnWsScope() { dk_set_attention_workspace(prev, prev_bytes); }
-};
-struct MmditCallScope {  // an engine call's GEMM and attention splits go through THAT engine's regions; the caller's settings come back
-  LinearWsScope lin;
-  AttnWsScope att;
-  ElemScope elem;
-  explicit MmditCallScope(dk_mmdit* m) : lin(m->GWS), att(m->AWS, m->AWS_bytes), elem(m->dtype) {}
-};
 
 extern "C" int dk_mmdit_forward(dk_mmdit* m, const void* tokens_in, const void* text, int32_t step_index, void* tokens_out,
                                 void* stream) {
   DK_REQUIRE(m && m->prepared && m->mod_ready, "prepare + cache_modulation_params must precede forward");
   DK_REQUIRE(step_index >= 0 && step_index < m->n_t, "step index out of range");
-  hipStream_t st = S_(stream);
-  MmditCallScope scope(m);
+  const LaunchCtx L = m->ctx(stream);
+  const hipStream_t st = L.st;
   const dk_mmdit_config& c = m->cfg;
   const int h = m->h(), B = m->B, S = m->S, S_t = m->S_t, S_i = m->S_i, F = m->F();
   const bf16_t* mod_step = m->MOD + (size_t)step_index * B * m->mod_rows() * h;
@@ -693,20 +682,20 @@ extern "C" int dk_mmdit_forward(dk_mmdit* m, const void* tokens_in, const void* 
   // step-invariant result of dk_mmdit_cache_context when `text` is null
   if (text != nullptr) {
     const int T = c.token_level_text_embed_dim;  // (no split workspace)
-    DK_TRY(dk_launch_gemm(Linear(dense((const bf16_t*)text, T), m->ctx_w, m->ctx_b, m->txt(m->X, h), B * S_t, h, T, DK_EPI_BIAS), st));
+    DK_TRY(dk_launch_gemm(Linear(L.dtype, dense((const bf16_t*)text, T), m->ctx_w, m->ctx_b, m->txt(m->X, h), B * S_t, h, T, DK_EPI_BIAS), st));
   } else {
     DK_REQUIRE(m->ctx_ready, "forward without text needs dk_mmdit_cache_context first");
     DK_CHECK_HIP(hipMemcpy2DAsync(m->X, (size_t)S * h * 2, m->CTXE, (size_t)S_t * h * 2, (size_t)S_t * h * 2, B, hipMemcpyDeviceToDevice, st));
   }
   // x_embedder (+ learned positional embedding) (mmdit.py:197-206): image rows
   // (no split workspace; the positional rows repeat per image: one segment of S_i rows, stride 0)
-  DK_TRY(dk_launch_gemm(Linear(dense((const bf16_t*)tokens_in, F), m->xemb_w, m->xemb_b, m->img(m->X, h), B * S_i, h, F,
+  DK_TRY(dk_launch_gemm(Linear(L.dtype, dense((const bf16_t*)tokens_in, F), m->xemb_w, m->xemb_b, m->img(m->X, h), B * S_i, h, F,
                                c.use_pos_embed ? DK_EPI_RES : DK_EPI_BIAS)
                             .gate_res(nullptr, 0, 0, Rows{c.use_pos_embed ? m->POS : nullptr, h, S_i, 0}),
                         st));
   const int n_blocks = c.depth_multimodal + c.depth_unified;
-  DK_TRY(mmdit_blocks(m, mod_step, 0, n_blocks, st));
-  return mmdit_final_layer(m, mod_step, (bf16_t*)tokens_out, st);
+  DK_TRY(mmdit_blocks(m, mod_step, 0, n_blocks, L));
+  return mmdit_final_layer(m, mod_step, (bf16_t*)tokens_out, L);
 }
 
 // Teacher-forced block range (include/dk_hip.h): x_in -> m->X, blocks [first, first + count), m->X -> x_out
@@ -717,12 +706,12 @@ extern "C" int dk_mmdit_run_blocks(dk_mmdit* m, const void* x_in, void* x_out, i
   DK_REQUIRE(step_index >= 0 && step_index < m->n_t, "step index out of range");
   const int total = m->cfg.depth_multimodal + m->cfg.depth_unified;
   DK_REQUIRE(first_block >= 0 && n_blocks >= 1 && first_block + n_blocks <= total, "block range outside the model");
-  hipStream_t st = S_(stream);
-  MmditCallScope scope(m);
+  const LaunchCtx L = m->ctx(stream);
+  const hipStream_t st = L.st;
   const size_t bytes = (size_t)m->B * m->S * m->h() * 2;
   const bf16_t* mod_step = m->MOD + (size_t)step_index * m->B * m->mod_rows() * m->h();
   DK_CHECK_HIP(hipMemcpyAsync(m->X, x_in, bytes, hipMemcpyDeviceToDevice, st));
-  DK_TRY(mmdit_blocks(m, mod_step, first_block, n_blocks, st));
+  DK_TRY(mmdit_blocks(m, mod_step, first_block, n_blocks, L));
   DK_CHECK_HIP(hipMemcpyAsync(x_out, m->X, bytes, hipMemcpyDeviceToDevice, st));
   return 0;
 }

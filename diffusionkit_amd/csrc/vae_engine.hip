@@ -129,9 +129,8 @@ extern "C" size_t dk_vae_workspace_bytes(const dk_vae* v, int32_t batch, int32_t
   return vae_carve(&tmp, c, batch, decoder_extents(tmp.cfg, batch, latent_h, latent_w)) + 256;
 }
 
-struct VaeRun {
+struct VaeRun : LaunchCtx {  // (st, dtype; kws: the 3x3 convs' split region; no attention region)
   dk_vae* v;
-  hipStream_t st;
   int B;
   int rc = 0;
   const bf16_t* W(const std::string& name) {
@@ -143,7 +142,7 @@ struct VaeRun {
   int gn(const bf16_t* x, bf16_t* y, long HW, int C, const std::string& name, int silu) {
     const bf16_t *g = W(name + ".weight"), *b = W(name + ".bias");
     if (rc) return rc;
-    return dk_groupnorm_bf16(x, y, B, HW, C, v->cfg.resnet_groups, g, b, v->cfg.group_norm_eps, silu, v->gn, st);
+    return groupnorm_launch(dtype, x, y, B, HW, C, v->cfg.resnet_groups, g, b, v->cfg.group_norm_eps, silu, v->gn, st);
   }
   int conv(const bf16_t* x, bf16_t* y, int H, int Wd, int C, int O, const std::string& name, int ups, const bf16_t* res, int ldy) {
     dk_conv_desc d;
@@ -152,7 +151,7 @@ struct VaeRun {
     if (rc) return rc;
     d.B = B; d.H = H; d.W = Wd; d.C = C; d.O = O; d.ldy = ldy; d.ldr = O; d.upsample = ups;
     d.epilogue = res ? DK_EPI_RES : DK_EPI_BIAS;
-    return conv3x3_launch(&d, v->GWS, st);
+    return conv3x3_launch(dtype, &d, kws, st);
   }
   // ---- fused norm -> silu -> conv stages (conv_halo.hip) ----
   int n_part = 0;  // > 0: v->gn holds the output-statistics partials [B][n_part][G][2] of the tensor the last fused conv wrote
@@ -171,14 +170,14 @@ struct VaeRun {
     if (rc) return rc;
     const int np = n_part;
     n_part = 0;
-    return dk_groupnorm_table_bf16(np > 0 ? nullptr : x, B, HW, C, v->cfg.resnet_groups, g, b, v->cfg.group_norm_eps, v->gn, np, ss, st);
+    return groupnorm_table_launch(dtype, np > 0 ? nullptr : x, B, HW, C, v->cfg.resnet_groups, g, b, v->cfg.group_norm_eps, v->gn, np, ss, st);
   }
   // a conv_halo.hip launch of this run: the fields all of them set (ldw: row pitch of the weight, ldy: of y -- 0 for the image tail);
   // operands, norm table, statistics and outputs stay at the call site
   ConvHaloParams halo_conv(int H, int Wd, int C, int O, int ldw, int ldy) const {
     ConvHaloParams c;
     memset(&c, 0, sizeof(c));
-    c.dtype = g_elem_dtype;
+    c.dtype = dtype;
     c.B = B; c.H = H; c.W = Wd; c.C = C; c.O = O; c.ldw = ldw; c.ldy = ldy;
     return c;
   }
@@ -224,7 +223,7 @@ struct VaeRun {
     if (has(p + ".conv_shortcut.weight")) {
       const bf16_t *sw = W(p + ".conv_shortcut.weight"), *sb = W(p + ".conv_shortcut.bias");
       if (rc) return rc;
-      DK_TRY(dk_launch_gemm(Linear(dense(x, Cin), sw, sb, dense(v->SC, Cout), (int)(B * HW), Cout, Cin, DK_EPI_BIAS), st));
+      DK_TRY(dk_launch_gemm(Linear(dtype, dense(x, Cin), sw, sb, dense(v->SC, Cout), (int)(B * HW), Cout, Cin, DK_EPI_BIAS), st));
       res = v->SC;
     } else {
       DK_REQUIRE(Cin == Cout, "resnet without shortcut must keep the channel count");
@@ -244,24 +243,24 @@ struct VaeRun {
     const bf16_t *vw = W(p + ".value_proj.weight"), *vb = W(p + ".value_proj.bias");
     const bf16_t *ow = W(p + ".out_proj.weight"), *ob = W(p + ".out_proj.bias");
     if (rc) return rc;
-    DK_TRY(dk_launch_gemm(Linear(dense(v->T1, C), qw, qb, dense(v->Qb, C), B * T, C, C, DK_EPI_BIAS), st));
-    DK_TRY(dk_launch_gemm(Linear(dense(v->T1, C), kw, kb, dense(v->Kb, C), B * T, C, C, DK_EPI_BIAS), st));
-    DK_TRY(dk_launch_gemm(Linear(dense(v->T1, C), vw, vb, dense(v->Vb, C), B * T, C, C, DK_EPI_BIAS), st));
+    DK_TRY(dk_launch_gemm(Linear(dtype, dense(v->T1, C), qw, qb, dense(v->Qb, C), B * T, C, C, DK_EPI_BIAS), st));
+    DK_TRY(dk_launch_gemm(Linear(dtype, dense(v->T1, C), kw, kb, dense(v->Kb, C), B * T, C, C, DK_EPI_BIAS), st));
+    DK_TRY(dk_launch_gemm(Linear(dtype, dense(v->T1, C), vw, vb, dense(v->Vb, C), B * T, C, C, DK_EPI_BIAS), st));
     const float scale = 1.0f / sqrtf((float)C);
     // flash form (attention512.hip): no [T, T] score matrix
-    if (C == 512) DK_TRY(attention_d512(v->Qb, v->Kb, v->Vb, v->Y, B, T, C, C, scale, v->Vt, st));
+    if (C == 512) DK_TRY(attention_d512(dtype, v->Qb, v->Kb, v->Vb, v->Y, B, T, C, C, scale, v->Vt, st));
     else
       for (int b = 0; b < B; ++b) {
-        Linear g(dense(v->Qb + (size_t)b * T * C, C), v->Kb + (size_t)b * T * C, nullptr, dense(v->SCORES, Tp), T, T, C, DK_EPI_BIAS);
+        Linear g(dtype, dense(v->Qb + (size_t)b * T * C, C), v->Kb + (size_t)b * T * C, nullptr, dense(v->SCORES, Tp), T, T, C, DK_EPI_BIAS);
         g.alpha = scale;  // scores = scale * q @ k^T
         DK_TRY(dk_launch_gemm(g, st));
-        DK_TRY(DK_EL(dk_launch_softmax_rows)(v->SCORES, T, T, Tp, st));  // columns [T, Tp) come out as zeros
-        DK_TRY(DK_EL(dk_launch_transpose)(v->Vb + (size_t)b * T * C, v->Vt, T, C, st, Tp));
+        DK_TRY(DK_EL(dtype, dk_launch_softmax_rows)(v->SCORES, T, T, Tp, st));  // columns [T, Tp) come out as zeros
+        DK_TRY(DK_EL(dtype, dk_launch_transpose)(v->Vb + (size_t)b * T * C, v->Vt, T, C, st, Tp));
         // attn @ V: A = probs [T, Tp], W = V^T [C, Tp]; result into Y rows of this batch
-        DK_TRY(dk_launch_gemm(Linear(dense(v->SCORES, Tp), v->Vt, nullptr, dense(v->Y + (size_t)b * T * C, C), T, C, Tp, DK_EPI_BIAS), st));
+        DK_TRY(dk_launch_gemm(Linear(dtype, dense(v->SCORES, Tp), v->Vt, nullptr, dense(v->Y + (size_t)b * T * C, C), T, C, Tp, DK_EPI_BIAS), st));
       }
     // out_proj + residual
-    return dk_launch_gemm(Linear(dense(v->Y, C), ow, ob, dense(out, C), B * T, C, C, DK_EPI_RES).gate_res(nullptr, 0, 0, dense(x, C)), st);
+    return dk_launch_gemm(Linear(dtype, dense(v->Y, C), ow, ob, dense(out, C), B * T, C, C, DK_EPI_RES).gate_res(nullptr, 0, 0, dense(x, C)), st);
   }
 };
 
@@ -273,16 +272,14 @@ extern "C" int dk_vae_decode(dk_vae* v, const float* latent, int32_t batch, int3
   const size_t need_bytes = vae_carve(v, c, batch, decoder_extents(v->cfg, batch, latent_h, latent_w));
   DK_REQUIRE(need_bytes <= workspace_bytes, "workspace too small");
   const dk_vae_config& cf = v->cfg;
-  VaeRun R{v, S_(stream), batch};
+  VaeRun R{{S_(stream), v->dtype, v->GWS}, v, batch};
   hipStream_t st = R.st;
   // the flag region of the GEMM split workspace must be zero before the first launch (the kernels leave it zero)
   DK_CHECK_HIP(hipMemsetAsync((char*)v->GWS + DK_KSPLIT_FLAGS_OFF, 0, DK_KSPLIT_FLAG_BYTES, st));
-  LinearWsScope ws_scope(v->GWS);
-  ElemScope elem_scope(v->dtype);
   DK_CHECK_HIP(hipMemsetAsync(v->ZERO, 0, 256, st));
   int H = latent_h, W = latent_w;
   const int Cm = cf.block_out_channels[cf.n_blocks - 1];
-  DK_TRY(DK_EL(dk_launch_pad_channels)(latent, v->LAT, (long)batch * H * W, cf.in_channels, 64, st));
+  DK_TRY(DK_EL(v->dtype, dk_launch_pad_channels)(latent, v->LAT, (long)batch * H * W, cf.in_channels, 64, st));
   bf16_t *cur = v->bufA, *nxt = v->bufB;
   DK_TRY(R.conv(v->LAT, cur, H, W, 64, Cm, "conv_in", 0, nullptr, Cm));
   DK_TRY(R.resnet(cur, nxt, H, W, Cm, Cm, "mid_blocks.0")); std::swap(cur, nxt);
@@ -331,7 +328,7 @@ extern "C" int dk_vae_decode(dk_vae* v, const float* latent, int32_t batch, int3
   DK_TRY(R.gn(cur, v->T1, (long)H * W, C, "conv_norm_out", 1));
   bf16_t* raw = raw_bf16 ? (bf16_t*)raw_bf16 : v->Y;
   DK_TRY(R.conv(v->T1, raw, H, W, C, cf.out_channels, "conv_out", 0, nullptr, 4));
-  DK_TRY(DK_EL(dk_launch_image_post)(raw, 4, image_f32, image_u8, (long)batch * H * W, st));
+  DK_TRY(DK_EL(v->dtype, dk_launch_image_post)(raw, 4, image_f32, image_u8, (long)batch * H * W, st));
   return R.rc;
 }
 
@@ -359,14 +356,12 @@ extern "C" int dk_vae_encode(dk_vae* v, const float* image, int32_t batch, int32
   Carver c(workspace, workspace_bytes);
   const size_t need_bytes = vae_carve(v, c, batch, encoder_extents(v->cfg, batch, image_h, image_w));
   DK_REQUIRE(need_bytes <= workspace_bytes, "workspace too small");
-  VaeRun R{v, S_(stream), batch};
+  VaeRun R{{S_(stream), v->dtype, v->GWS}, v, batch};
   hipStream_t st = R.st;
   DK_CHECK_HIP(hipMemsetAsync((char*)v->GWS + DK_KSPLIT_FLAGS_OFF, 0, DK_KSPLIT_FLAG_BYTES, st));
-  LinearWsScope ws_scope(v->GWS);
-  ElemScope elem_scope(v->dtype);
   DK_CHECK_HIP(hipMemsetAsync(v->ZERO, 0, 256, st));
   int H = image_h, W = image_w;
-  DK_TRY(DK_EL(dk_launch_pad_channels)(image, v->LAT, (long)batch * H * W, cf.in_channels, 64, st));
+  DK_TRY(DK_EL(v->dtype, dk_launch_pad_channels)(image, v->LAT, (long)batch * H * W, cf.in_channels, 64, st));
   bf16_t *cur = v->bufA, *nxt = v->bufB;
   int C = cf.block_out_channels[0];
   DK_TRY(R.conv(v->LAT, cur, H, W, 64, C, "conv_in", 0, nullptr, C));
@@ -389,17 +384,19 @@ extern "C" int dk_vae_encode(dk_vae* v, const float* image, int32_t batch, int32
   bf16_t* mom = moments_bf16 ? (bf16_t*)moments_bf16 : v->Y;
   const int ld = moments_bf16 ? ldm : ldo;
   DK_TRY(R.conv(v->T1, mom, H, W, C, cf.out_channels, "conv_out", 0, nullptr, ld));
-  if (moments_f32) DK_TRY(DK_EL(dk_launch_bf16_rows_to_f32)(mom, ld, moments_f32, (long)batch * H * W, cf.out_channels, st));
+  if (moments_f32) DK_TRY(DK_EL(v->dtype, dk_launch_bf16_rows_to_f32)(mom, ld, moments_f32, (long)batch * H * W, cf.out_channels, st));
   return R.rc;
 }
 
+static int latent_sample(int dtype, const void* moments, int ldm, const float* noise, float* latent, long n_pixels, int latent_channels, void* stream) {
+  DK_REQUIRE(moments && noise && latent && n_pixels > 0 && latent_channels > 0 && ldm >= 2 * latent_channels, "bad argument");
+  return DK_EL(dtype, dk_launch_latent_sample)((const bf16_t*)moments, ldm, noise, latent, n_pixels, latent_channels, S_(stream));
+}
 extern "C" int dk_latent_sample_f32(const void* moments_bf16, int32_t ldm, const float* noise, float* latent, int64_t n_pixels,
                                     int32_t latent_channels, void* stream) {
-  DK_REQUIRE(moments_bf16 && noise && latent && n_pixels > 0 && latent_channels > 0 && ldm >= 2 * latent_channels, "bad argument");
-  return DK_EL(dk_launch_latent_sample)((const bf16_t*)moments_bf16, ldm, noise, latent, (long)n_pixels, latent_channels, S_(stream));
+  return latent_sample(DK_DTYPE_BF16, moments_bf16, ldm, noise, latent, (long)n_pixels, latent_channels, stream);
 }
 extern "C" int dk_latent_sample_f16(const void* moments_f16, int32_t ldm, const float* noise, float* latent, int64_t n_pixels,
                                     int32_t latent_channels, void* stream) {
-  ElemScope f16(DK_DTYPE_F16);
-  return dk_latent_sample_f32(moments_f16, ldm, noise, latent, n_pixels, latent_channels, stream);
+  return latent_sample(DK_DTYPE_F16, moments_f16, ldm, noise, latent, (long)n_pixels, latent_channels, stream);
 }

@@ -216,8 +216,9 @@ int dk_attention_desc_bf16(const dk_attention_desc* d, void* stream);
  * keys and merges the partial results through it.  Optional: without a workspace nothing is split (same results up to the bf16
  * rounding of the partials; FLUX 1024^2, one image: ~10 % longer attention launches).  ONE split launch at a time may use a given
  * workspace: launches that share it must be ordered on one stream.  The pointer is per host thread, not per device -- a thread that
- * moves to another device installs that device's buffer again.  dk_mmdit_* calls do not use this buffer: every engine carves its own
- * region from its workspace and installs it for the duration of the call (two engines on two streams never share partial results). */
+ * moves to another device installs that device's buffer again.  Only the stand-alone dk_attention_* entries read it.  dk_mmdit_* calls
+ * neither use nor move it: every engine carves its own region from its workspace and hands it to its attention launches (two engines on two
+ * streams never share partial results). */
 size_t dk_attention_workspace_bytes(void);
 int dk_attention_set_workspace(void* workspace, size_t bytes);
 

@@ -4,6 +4,8 @@ and the host classes refuse to run without a GPU instead of falling back."""
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 import torch
@@ -28,6 +30,20 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, s), f"{s} declared in include/dk_hip.h but not exported"
     assert sorted(_lib.SIGNATURES) == syms
     assert lib.dk_abi_version() == 5
+
+
+READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
+
+
+@pytest.mark.skipif(not (os.path.exists(_lib.LIB_PATH) and shutil.which(READELF)), reason="needs the built library and the ROCm LLVM tools")
+def test_library_keeps_exactly_two_thread_local_objects():
+    """No launch learns its element type or a workspace from per-thread state: the library's thread-local objects are the last-error string and
+    the attention workspace (pointer, bytes) of the stand-alone dk_attention_* entries, both in csrc/abi_ops.hip.  (__tls_guard / __tls_init are
+    the compiler's own: the string's lazy construction.)"""
+    out = subprocess.check_output([READELF, "--symbols", "--wide", _lib.LIB_PATH], text=True)
+    tls = {ln.split()[7] for ln in out.splitlines() if len(ln.split()) >= 8 and ln.split()[3] == "TLS"}
+    tls = sorted(t for t in tls if not t.startswith("__tls_"))
+    assert len(tls) == 2 and all(any(name in t for t in tls) for name in ("g_last_error", "g_attn_ws")), tls
 
 
 def test_mod_table_layout_matches_config():

@@ -68,19 +68,24 @@ def mmdit_inputs(cfg, dev, B, Hl, Wl, S_t, seed0=0):
                 lat=randn(B, Hl, Wl, 16, seed=seed0 + 5).to(dev), x=randn(B, S, cfg.hidden_size, seed=seed0 + 840).to(dev, dt))
 
 
-def mmdit_sequence(eng, shape, inp, ts, before_forward=None):
-    """prepare -> cache_modulation_params -> forward_tokens at every cached step -> run_blocks over the whole range; nothing refills the workspace
-    in between (prepare writes the RoPE table, the cropped positional table and the K-split flags)"""
+def mmdit_prepared_steps(eng, shape, inp, ts, before_forward=None):
+    """prepare -> cache_modulation_params, then one thunk per output of mmdit_sequence (the interleaving tests call them in turn with other work)"""
     B, Hl, Wl, S_t = shape
     eng.prepare(B, (Hl, Wl), S_t, len(ts))
     eng.cache_modulation_params(inp["pooled"], ts)
     if before_forward is not None:
         before_forward(eng)
     tok = eng.patchify(inp["lat"])
-    outs = [eng.forward_tokens(tok, inp["text"], i) for i in range(len(ts))]
-    outs.append(eng.run_blocks(inp["x"], len(ts) - 1, 0, eng.config.depth_multimodal + eng.config.depth_unified))
+    steps = [lambda i=i: eng.forward_tokens(tok, inp["text"], i) for i in range(len(ts))]
+    return steps + [lambda: eng.run_blocks(inp["x"], len(ts) - 1, 0, eng.config.depth_multimodal + eng.config.depth_unified)]
+
+
+def mmdit_sequence(eng, shape, inp, ts, before_forward=None):
+    """prepare -> cache_modulation_params -> forward_tokens at every cached step -> run_blocks over the whole range; nothing refills the workspace
+    in between (prepare writes the RoPE table, the cropped positional table and the K-split flags)"""
+    outs = tuple(step() for step in mmdit_prepared_steps(eng, shape, inp, ts, before_forward))
     torch.cuda.synchronize()
-    return tuple(outs)
+    return outs
 
 
 def mmdit_contents_case(dev, cfg, packed, shape, big, ts, what, after_run=None, before_forward=None):
@@ -275,6 +280,40 @@ def test_flux_width_attention5_key_split(dev, packed_for):
     assert rel_l2(whole[1].float(), outs["zero"][1].float()) < 4e-3  # (tests/test_gpu_model.py::test_attention_kernels_agree_inside_the_model's bound)
 
 
+def test_flux_width_interleaved_workspaces(dev, packed_for):
+    """Two engines of one width on one host thread and stream, forwards alternating: engine 1 at B = 2, latent 64 x 96 (attention5's key split goes
+    through ITS attention region: test_flux_width_attention5_key_split), engine 2 at B = 1, latent 64 x 64 (fc2 / linear2 are cut along K through ITS
+    K-split region: test_flux_width_k_split_flags).  Each launch gets its regions as arguments from the engine that builds it, so every output
+    equals that engine's solo sequence, the idle engine's whole workspace is byte for byte the same before and after the other one's call, and both
+    pairs of margins are intact."""
+    from diffusionkit_amd.engine import MMDiTEngine
+    _, packed = packed_for(FLUX_W)
+    shapes = [(2, 64, 96, 256), (1, 64, 64, 256)]
+    inps = [mmdit_inputs(FLUX_W, dev, *s, seed0=50 * i) for i, s in enumerate(shapes)]
+    solo = [mmdit_sequence(MMDiTEngine(FLUX_W, packed), s, inp, TS2) for s, inp in zip(shapes, inps)]
+    engs = [MMDiTEngine(FLUX_W, packed) for _ in shapes]
+    nbytes = [e.lib.dk_mmdit_workspace_bytes(e._h, *s, len(TS2)) for e, s in zip(engs, shapes)]
+    wss = [es.GuardedWorkspace(n, dev) for n in nbytes]
+    for e, ws, n in zip(engs, wss, nbytes):
+        ws.fill(es.FILL_NAN)
+        es.lend(e, ws, n)
+    steps = [mmdit_prepared_steps(e, s, inp, TS2) for e, s, inp in zip(engs, shapes, inps)]
+    torch.cuda.synchronize()
+    got = [[], []]
+    for k in range(len(steps[0])):
+        for a, idle in ((0, 1), (1, 0)):
+            before = wss[idle].interior(nbytes[idle]).clone()
+            got[a].append(steps[a][k]())
+            torch.cuda.synchronize()
+            d = wss[idle].interior(nbytes[idle]) != before
+            assert not bool(d.any()), (f"call {k} of engine {a + 1} changed the idle engine {idle + 1}'s workspace, first at byte "
+                                       f"{int(torch.nonzero(d)[0])} of {nbytes[idle]}")
+    for i, (e, ws, n) in enumerate(zip(engs, wss, nbytes)):
+        assert e._ws.data_ptr() == ws.interior(n).data_ptr() and e._ws.numel() == n
+        ws.check(n, f"interleaved flux width, engine {i + 1} {shapes[i]}", fill=es.FILL_NAN)
+        es.assert_identical({"solo": solo[i], "interleaved": tuple(got[i])}, f"interleaved flux width, engine {i + 1} {shapes[i]}")
+
+
 def test_flux_width_fp8_ragged_rows(dev, packed_for):
     """the fp8 configuration at width, B = 2, latent 104 x 104: 5408 image rows, pad rows up to 5504 in front of the text rows of XN8 / ATT8 / HC8"""
     cfg = replace(FLUX_W, weight_dtype="fp8_e4m3")
@@ -421,6 +460,51 @@ def test_vae_encoder_production_contents_and_bounds(dev, f16):
     _, _, make = _encoder(dev, True, f16)
     vae_contents_case(dev, make, _encoder_bytes, _encode, _image(1, 80, 112, seed=3), _image(1, 96, 128, seed=4),
                       f"vae encoder production 80 x 112 {'float16' if f16 else 'bf16'}")
+
+
+# ---- interleaved element types: bf16 and float16 engines and stand-alone operators in turn on one host thread and stream ---------------------------
+def test_interleaved_element_types_one_thread(dev, packed_for):
+    """A bf16 and a float16 tiny SD3 engine and the tiny VAE decoder in both element types, stepped round-robin; between two engine steps one
+    stand-alone float16 ops.linear and one bf16 ops.attention.  The element type of a launch is an argument of whatever builds it: every engine
+    output equals the same engine's solo run, every stand-alone result the same call made before any of these engines existed.
+    The attention (D = 128, S = 2048, 96 query blocks on 256 compute units) is cut into two key ranges through the host thread's own attention
+    workspace, which no engine call consults or moves."""
+    from diffusionkit_amd import ops
+    from diffusionkit_amd.engine import MMDiTEngine
+    x, w, b = randn(154, 256, seed=60).to(dev, F16), randn(384, 256, seed=61, scale=0.08).to(dev, F16), randn(384, seed=62, scale=0.1).to(dev, F16)
+    qkv = randn(1, 2048, 3 * 12 * 128, seed=63).to(dev, BF)
+    standalone = lambda: (ops.linear(x, w, b), ops.attention(qkv, 12, 128))
+    alone = standalone()
+    try:
+        ops.tune("attn_split", 0)
+        whole = ops.attention(qkv, 12, 128)
+    finally:
+        ops.tune("attn_split", -1)
+    assert not torch.equal(whole, alone[1]), "the key split did not engage: the stand-alone attention does not reach the thread's workspace"
+
+    shape, z = (2, 8, 12, 20), _latent(2, 6, 10).to(dev)
+    cfgs = [tiny_sd3(), float16_config(tiny_sd3())]
+    mm = [(cfg, packed_for(cfg)[1], mmdit_inputs(cfg, dev, *shape)) for cfg in cfgs]
+    makes = [_decoder(dev, False, f16)[2] for f16 in (False, True)]
+    solo = [mmdit_sequence(MMDiTEngine(cfg, packed), shape, inp, TS) for cfg, packed, inp in mm] + [_decode(make(), z) for make in makes]
+    torch.cuda.synchronize()
+
+    steps = [mmdit_prepared_steps(MMDiTEngine(cfg, packed), shape, inp, TS) for cfg, packed, inp in mm]
+    decoders = [make() for make in makes]
+    got, between = [[], [], [], []], []
+    for r in range(len(TS) + 1):
+        for j in range(4):
+            got[j].append(steps[j][r]() if j < 2 else _decode(decoders[j - 2], z))
+            between.append(standalone())
+    torch.cuda.synchronize()
+    for j, name in enumerate(("tiny sd3 bf16", "tiny sd3 float16")):
+        assert got[j][0].dtype == dtype_of(cfgs[j])
+        es.assert_identical({"solo": solo[j], "interleaved": tuple(got[j])}, f"interleaved element types, {name}")
+    for j, name in ((2, "vae decoder bf16"), (3, "vae decoder float16")):
+        for r, out in enumerate(got[j]):
+            es.assert_identical({"solo": solo[j], "interleaved": out}, f"interleaved element types, {name}, round {r + 1}")
+    for i, out in enumerate(between):
+        es.assert_identical({"no engine alive": alone, "between engine steps": out}, f"stand-alone linear / attention behind engine step {i + 1}")
 
 
 # ---- 2b. reuse: one object through a sequence of problems against fresh objects -----------------------------------------------------------------
