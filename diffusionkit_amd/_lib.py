@@ -129,6 +129,10 @@ class dk_gemm_plan_t(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("kernel", "tile_rows", "tiles", "workgroups", "split_tiles", "k_pieces", "ks", "n_cu", "launches")]
 
 
+class dk_attention_plan_t(C.Structure):  # (o8_split is read by dk_attention_plan, the other fields are written)
+    _fields_ = [(n, C.c_int32) for n in ("kernel", "qfuse", "blocks", "whole", "split", "jobs", "merge", "quantize", "launches", "n_cu", "o8_split")]
+
+
 SIGNATURES = {
     "dk_abi_version": (_i32, []),
     "dk_last_error": (C.c_char_p, []),
@@ -140,6 +144,7 @@ SIGNATURES = {
     "dk_gemm_fp8_fused": (_i32, [C.POINTER(dk_gemm_fp8_desc), C.POINTER(dk_gemm_fp8_side), C.POINTER(dk_gemm_fp8_desc), C.POINTER(dk_gemm_fp8_side),
                                  _vp]),
     "dk_attention_desc_bf16": (_i32, [C.POINTER(dk_attention_desc), _vp]),
+    "dk_attention_plan": (_i32, [C.POINTER(dk_attention_desc), _sz, C.POINTER(dk_attention_plan_t)]),
     "dk_gemm_workspace_bytes": (C.c_size_t, []),
     "dk_attention_workspace_bytes": (C.c_size_t, []),
     "dk_attention_set_workspace": (C.c_int, [C.c_void_p, C.c_size_t]),
@@ -166,6 +171,7 @@ SIGNATURES = {
     "dk_gemm_plan_f16": (_i32, [C.POINTER(dk_gemm_desc), C.POINTER(dk_gemm_desc), C.POINTER(dk_gemm_plan_t)]),
     "dk_gemm_fused_f16": (_i32, [C.POINTER(dk_gemm_desc), C.POINTER(dk_gemm_side), C.POINTER(dk_gemm_desc), C.POINTER(dk_gemm_side), _vp]),
     "dk_attention_desc_f16": (_i32, [C.POINTER(dk_attention_desc), _vp]),
+    "dk_attention_plan_f16": (_i32, [C.POINTER(dk_attention_desc), _sz, C.POINTER(dk_attention_plan_t)]),
     "dk_ln_modulate_f16": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp]),
     "dk_qk_norm_rope_f16": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _f32, _vp, _i32, _i32, _i32, _vp]),
     "dk_timestep_embedding_f16": (_i32, [_vp, _i32, _i32, _f32, _i32, _vp, _vp]),

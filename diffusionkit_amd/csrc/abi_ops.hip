@@ -138,10 +138,11 @@ extern "C" int dk_conv3x3_plan(const dk_conv_desc* d, dk_gemm_plan_t* plan) { re
 extern "C" int dk_conv3x3_plan_f16(const dk_conv_desc* d, dk_gemm_plan_t* plan) { return conv3x3_plan(DK_DTYPE_F16, d, plan); }
 
 // Workspace of the stand-alone attention launches (dk_attention_*) of this host thread.  attention5.hip splits the query blocks of a launch's last, partial round of the
-// CUs along the keys (FLUX, one image: 408 blocks on 256 CUs -- 152 blocks in three key ranges each fill the second round to two thirds
-// of a block's time); the partial results (bf16 O / l, offset, l per row) go through this buffer.  Without one (or with one too small for a
-// launch) the blocks are not split: same results up to the rounding of the partials, a longer last round.
-extern "C" size_t dk_attention_workspace_bytes(void) { return (size_t)1020 * (65536 + 2048); }  // <= 255 blocks x 4 key ranges
+// CUs along the keys where that shortens the round (dk_attention_route, attention.hip: FLUX 1024 x 1024 with four images, 1632 blocks on 256 CUs -- the
+// 96 blocks of the seventh round in two key ranges each; with one image the 152 blocks of the second round stay whole); the partial results (bf16
+// O / l, offset, l per row) go through this buffer.  Without one (or with one too small for a launch) the blocks are not split: same results up
+// to the rounding of the partials, a longer last round.
+extern "C" size_t dk_attention_workspace_bytes(void) { return (size_t)1020 * DK_ATTN5_JOB_BYTES; }  // <= 255 blocks x 4 key ranges
 extern "C" int dk_attention_set_workspace(void* workspace, size_t bytes) {
   DK_REQUIRE(workspace == nullptr || ((uintptr_t)workspace & 255) == 0, "attention workspace: 256-byte aligned (or NULL)");
   g_attn_ws = AttnWs{workspace, workspace ? bytes : 0};
@@ -166,9 +167,8 @@ extern "C" int dk_attention_bias_bf16(const void* q, const void* k, const void* 
   p.bias = (const bf16_t*)bias; p.bias_head_stride = (long)bias_head_stride; p.ldb = ldb;
   return dk_launch_attention(p, g_attn_ws, S_(stream));
 }
-static int attention_desc(int dtype, const dk_attention_desc* d, void* stream) {
+static int attn_params_from_desc(int dtype, const dk_attention_desc* d, AttnParams& p) {
   DK_REQUIRE(d != nullptr, "null descriptor");
-  AttnParams p;
   p.Q = (const bf16_t*)d->q; p.K = (const bf16_t*)d->k; p.V = (const bf16_t*)d->v; p.O = (bf16_t*)d->out;
   p.B = d->B; p.H = d->H; p.S = d->S; p.D = d->D; p.ld = d->ld; p.ldo = d->ldo; p.scale = d->scale;
   p.bias = (const bf16_t*)d->bias; p.bias_head_stride = (long)d->bias_head_stride; p.ldb = d->ldb;
@@ -179,10 +179,35 @@ static int attention_desc(int dtype, const dk_attention_desc* d, void* stream) {
                "MX-fp8 output copy: scales, B * S rows inside the buffer, a row pitch of at least H * D bytes (multiple of 32)");
     p.O8 = (unsigned char*)d->O8; p.O8_scales = (unsigned char*)d->O8_scales; p.o8_ld = d->o8_ld; p.o8_nblk = mx_nblk((long)d->o8_rows);
   }
+  return 0;
+}
+static int attention_desc(int dtype, const dk_attention_desc* d, void* stream) {
+  AttnParams p;
+  if (const int rc = attn_params_from_desc(dtype, d, p)) return rc;
   return dk_launch_attention(p, g_attn_ws, S_(stream));
 }
 extern "C" int dk_attention_desc_bf16(const dk_attention_desc* d, void* stream) { return attention_desc(DK_DTYPE_BF16, d, stream); }
 extern "C" int dk_attention_desc_f16(const dk_attention_desc* d, void* stream) { return attention_desc(DK_DTYPE_F16, d, stream); }
+// the route of that call with a region of workspace_bytes bytes; plan->o8_split is read (dk_hip.h), every other field written
+static int attention_plan(int dtype, const dk_attention_desc* d, size_t workspace_bytes, dk_attention_plan_t* plan) {
+  DK_REQUIRE(plan != nullptr, "null plan");
+  AttnParams p;
+  if (const int rc = attn_params_from_desc(dtype, d, p)) return rc;
+  if (p.O8 != nullptr) {
+    p.o8_split = plan->o8_split;
+    p.o8_txt_row0 = p.B * (p.S - p.o8_split);  // (the text rows right behind the image rows)
+  }
+  AttnRoute r;
+  if (const int rc = dk_attention_route(p, workspace_bytes, dk_device_cu_count(), r)) return rc;
+  *plan = dk_attention_plan_t{r.kernel, r.qfuse, r.blocks, r.whole, r.split, r.jobs, r.jobs > 0, r.quantize, r.launches, r.n_cu, p.o8_split};
+  return 0;
+}
+extern "C" int dk_attention_plan(const dk_attention_desc* d, size_t workspace_bytes, dk_attention_plan_t* plan) {
+  return attention_plan(DK_DTYPE_BF16, d, workspace_bytes, plan);
+}
+extern "C" int dk_attention_plan_f16(const dk_attention_desc* d, size_t workspace_bytes, dk_attention_plan_t* plan) {
+  return attention_plan(DK_DTYPE_F16, d, workspace_bytes, plan);
+}
 extern "C" int32_t dk_attention_d512_tp(int32_t T) { return (int32_t)align_up((size_t)(T > 0 ? T : 0), 64); }
 int attention_d512(int dtype, const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int B, int T, int ld, int ldo, float scale,
                    bf16_t* vt, hipStream_t st) {  // (dk_engine.h)

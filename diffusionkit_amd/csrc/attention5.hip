@@ -35,7 +35,7 @@ __global__ __launch_bounds__(256, 1) void dk_attn5_fwd_kernel(AttnParams p) {
   const int S = p.S;
   const int nq = (S + 255) / 256;
   // Jobs: workgroups 0 .. a5_whole - 1 take whole query blocks; the others key range `part` of a5_split of one of the remaining blocks (the
-  // launch's last, partial round of the CUs -- dk_launch_attention5).  Inside each class the blocks follow each other on an XCD.
+  // launch's last, partial round of the CUs -- dk_attention_route).  Inside each class the blocks follow each other on an XCD.
   auto xcd_contiguous = [](int bid, int nwg) {
     const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
@@ -293,48 +293,27 @@ __global__ __launch_bounds__(256) void dk_attn5_merge_kernel(AttnParams p, int n
   }
 }
 
-int g_dk_attn5_split = -1;  // dk_tune_set("attn_split", v): -1 automatic (needs the workspace), 0 never, 2 .. 4 that many key ranges for the last round's blocks
-
 bool dk_attention5_eligible(const AttnParams& p) {
   return p.D == 128 && p.bias == nullptr && p.S % 256 == 0 && p.S >= 12 * 64 && (size_t)p.S * p.ld * 2 < (1ull << 32);
 }
 
-int dk_launch_attention5(const AttnParams& p_in, AttnWs ws, hipStream_t stream) {
+// r: the call's route (dk_attention_route, attention.hip: whole blocks, key ranges and split jobs as given); ws: the region of the split jobs' partials
+int dk_launch_attention5(const AttnParams& p_in, const AttnRoute& r, void* ws, hipStream_t stream) {
   DK_REQUIRE(dk_attention5_eligible(p_in), "attention5: head_dim 128, no score bias, S a multiple of 256 and >= 768");
   AttnParams p = p_in;
-  const bool qfuse = p.qn_a != nullptr || p.q_rope != nullptr;
-  if (qfuse) DK_REQUIRE(p.qn_a == nullptr || p.qn_b != nullptr, "qn_b missing (pass qn_a twice for one weight)");
-  const int n_cu = dk_device_cu_count();
-  // One workgroup per CU: a launch of nb blocks runs in ceil(nb / n_cu) rounds, the last one with nb % n_cu blocks.  Those blocks are split
-  // into s key ranges each (every range a multiple of four tiles, at least twelve) when that shortens the last round: it then takes
-  // ceil(tail * s / n_cu) / s of a block's time.  The partial results go through the workspace and dk_attn5_merge_kernel.
-  const int nb = ((p.S + 255) / 256) * p.H * p.B;
-  const int tail = nb % n_cu;
-  int split = 1;
-  if (tail > 0 && p.O8 == nullptr && g_dk_attn5_split != 0) {
-    // (measured, profiles/r05_attention5_lab.log: a workgroup costs ~14 us + 1.66 us per tile, and a last round on 152 of 256 CUs runs faster
-    //  than a full one -- FLUX, one image, gains nothing from three ranges in two sub-rounds; a tail that fits the CUs in ONE sub-round does:
-    //  batch 4: 96 blocks x 2)
-    for (int s = 2; s <= 4 && split == 1; ++s) {
-      if ((p.S / 256) / s < 3) break;  // >= 12 tiles per range
-      if (g_dk_attn5_split > 0 ? s == g_dk_attn5_split : (tail * s <= n_cu && tail * s * 10 >= n_cu * 6)) split = s;
-    }
-    if (split > 1 && (ws.p == nullptr || ws.bytes < (size_t)tail * split * (65536 + 2048))) split = 1;
-    p.a5_ws = ws.p;
-  }
-  p.a5_split = split;
-  p.a5_whole = split > 1 ? nb - tail : nb;
-  const int njobs = split > 1 ? tail * split : 0;
+  p.a5_split = r.split;
+  p.a5_whole = r.whole;
+  p.a5_ws = r.jobs > 0 ? ws : nullptr;
   static DkDeviceOnce attr_once;
   if (attr_once.first()) {
     DK_CHECK_HIP(hipFuncSetAttribute((const void*)dk_attn5_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, A5_LDS_BYTES));
     DK_CHECK_HIP(hipFuncSetAttribute((const void*)dk_attn5_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, A5_LDS_BYTES));
     attr_once.mark();
   }
-  if (qfuse)
-    hipLaunchKernelGGL((dk_attn5_fwd_kernel<true>), dim3((unsigned)(p.a5_whole + njobs)), dim3(256), A5_LDS_BYTES, stream, p);
+  if (r.qfuse)
+    hipLaunchKernelGGL((dk_attn5_fwd_kernel<true>), dim3((unsigned)(r.whole + r.jobs)), dim3(256), A5_LDS_BYTES, stream, p);
   else
-    hipLaunchKernelGGL((dk_attn5_fwd_kernel<false>), dim3((unsigned)(p.a5_whole + njobs)), dim3(256), A5_LDS_BYTES, stream, p);
-  if (njobs > 0) hipLaunchKernelGGL(dk_attn5_merge_kernel, dim3((unsigned)(tail * 16)), dim3(256), 0, stream, p, njobs);
+    hipLaunchKernelGGL((dk_attn5_fwd_kernel<false>), dim3((unsigned)(r.whole + r.jobs)), dim3(256), A5_LDS_BYTES, stream, p);
+  if (r.jobs > 0) hipLaunchKernelGGL(dk_attn5_merge_kernel, dim3((unsigned)((r.blocks - r.whole) * 16)), dim3(256), 0, stream, p, r.jobs);
   return 0;
 }

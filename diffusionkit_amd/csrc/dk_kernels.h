@@ -235,12 +235,32 @@ struct AttnWs {
   void* p = nullptr;
   size_t bytes = 0;
 };
-extern int g_dk_attn_mode;
+// bytes one key-split job leaves in that region: 256 rows x 128 bf16 of O / l, then 256 x (exponent offset, l) in fp32 (attention5.hip's indexing
+// keeps the two sizes as literals)
+constexpr size_t DK_ATTN5_JOB_BYTES = 65536 + 2048;
+
+// What one dk_launch_attention call launches: dk_attention_route (attention.hip) decides it -- and makes every argument check -- from the problem,
+// the bytes of the caller's region, the CU count and the knobs "attn" / "attn_split" alone; the launchers take it as it is, and
+// dk_attention_plan reports it.  A key split changes the summation order: the route is part of the results.
+struct AttnRoute {
+  int kernel;     // in the knob's codes: 4 lean (attention2.hip), 9 phase-alternating (attention4.hip), 10 one wave per SIMD (attention5.hip)
+  bool qfuse;     // QKNorm / RoPE of the queries inside the Q load
+  int blocks;     // query blocks of 256 rows, B * H * ceil(S / 256): what the automatic choice counts and kernels 9 and 10 launch per workgroup
+  // kernel 10 (otherwise whole = blocks, split = 1, jobs = 0): workgroups 0 .. whole - 1 take whole blocks; each of the blocks - whole others,
+  // the launch's last, partial round of the CUs, is cut into `split` key ranges -- jobs = (blocks - whole) * split workgroups more, and a
+  // dk_attn5_merge_kernel launch behind them when jobs > 0
+  int whole, split, jobs;
+  int quantize;   // MX-fp8 copy: 0 none, or the kernel writes it; 1 a quantiser pass follows; 2 the same as two row ranges (o8_split)
+  int launches;   // kernel launches of the call
+  int n_cu;       // compute units the rules assumed
+};
+extern int g_dk_attn_mode, g_dk_attn5_split;  // attention.hip
+int dk_attention_route(const AttnParams& p, size_t ws_bytes, int n_cu, AttnRoute& r);
 int dk_launch_attention(const AttnParams& p, AttnWs ws, hipStream_t stream);
+// the kernels' launchers: arguments checked, kernel and split chosen by dk_attention_route
 int dk_launch_attention4(const AttnParams& p, hipStream_t stream);             // attention4.hip (the waves of a SIMD in opposite phases; D = 128, no score bias)
 bool dk_attention5_eligible(const AttnParams& p);                              // attention5.hip (one wave per SIMD, asm tile loop; D = 128, S % 256 == 0, no score bias)
-int dk_launch_attention5(const AttnParams& p, AttnWs ws, hipStream_t stream);
-extern int g_dk_attn5_split;
+int dk_launch_attention5(const AttnParams& p, const AttnRoute& r, void* ws, hipStream_t stream);
 
 // ---- single-head D = 512 attention of the VAE's mid block (attention512.hip) -------------------------------
 struct Attn512Params {

@@ -145,6 +145,15 @@ def attention_desc_call(dtype=BF, **kw) -> None:
     _lib.check(getattr(_lib.load(), name)(C.byref(d), _stream()), name)
 
 
+def attention_plan(dtype=BF, workspace_bytes=0, o8_split=0, **kw):
+    """dk_attention_plan / dk_attention_plan_f16: what ``attention_desc_call`` with these dk_attention_desc fields and a workspace of ``workspace_bytes``
+    bytes would launch (host only; pointers may be made-up, aligned integers).  ``o8_split``: the engines' row order of the MX-fp8 copy."""
+    d, plan = _fill(_lib.dk_attention_desc, kw), _lib.dk_attention_plan_t(o8_split=o8_split)
+    name = "dk_attention_plan" if _elem(dtype, "attention_plan") == "bf16" else "dk_attention_plan_f16"
+    _lib.check(getattr(_lib.load(), name)(C.byref(d), workspace_bytes, C.byref(plan)), name)
+    return plan
+
+
 _zero_pages = {}
 
 

@@ -222,6 +222,29 @@ int dk_attention_desc_bf16(const dk_attention_desc* d, void* stream);
 size_t dk_attention_workspace_bytes(void);
 int dk_attention_set_workspace(void* workspace, size_t bytes);
 
+/* What dk_attention_desc_bf16(d) WOULD launch on the current device with a workspace of workspace_bytes bytes (0: none) -- additive in ABI 5.
+ * Host only, like dk_gemm_plan: no kernel runs, pointers are not dereferenced (only NULL-ness and alignment are looked at), the arguments are
+ * checked as the launch checks them (same refusals, same dk_last_error() text), and without a GPU the rules assume 256 compute units.  The
+ * record is read from the route the launch takes (dk_attention_route, attention.hip).  A key split changes the summation order, so `split` is
+ * part of the results.
+ * One field is an INPUT: o8_split, the engines' row order of the MX-fp8 copy, which no descriptor can name (ragged image token counts of the
+ * double blocks: image rows of all batch rows first, the S_t = o8_split text rows of each behind them).  Zero it -- or the whole record -- before
+ * the call for the plain order of dk_attention_desc_bf16; it is read only when d->O8 is set. */
+typedef struct dk_attention_plan_t {
+  int32_t kernel;    /* in the codes of dk_tune_set("attn", .): 4 lean kernel, 9 phase-alternating, 10 one wave per SIMD */
+  int32_t qfuse;     /* QKNorm / RoPE of the queries inside the kernel's Q load */
+  int32_t blocks;    /* query blocks of 256 rows: B * H * ceil(S / 256) */
+  int32_t whole;     /* kernel 10: blocks that run whole (the others: the launch's last, partial round of the CUs); otherwise = blocks */
+  int32_t split;     /* key ranges each of the other blocks is cut into (1: none) */
+  int32_t jobs;      /* workgroups of those ranges: (blocks - whole) * split, 0 without a split */
+  int32_t merge;     /* a merge launch follows (jobs > 0) */
+  int32_t quantize;  /* MX-fp8 copy: 0 none, or the kernel writes it; 1 a quantiser pass follows; 2 the same as two row ranges (o8_split) */
+  int32_t launches;  /* kernel launches the call expands to */
+  int32_t n_cu;      /* compute units the rules assumed */
+  int32_t o8_split;  /* INPUT, see above */
+} dk_attention_plan_t;
+int dk_attention_plan(const dk_attention_desc* d, size_t workspace_bytes, dk_attention_plan_t* plan);
+
 /* Single-head attention over head_dim 512: the VAE mid block's Attention (vae.py:28-57: softmax((q / sqrt 512) k^T) v over all
  * H * W tokens), flash-style -- the [T, T] score matrix of the reference (537 MB at T = 16384) is never written.  q / k / v / out:
  * bf16 [B, T, ld] with ld == 512 EXACTLY (dense rows: the transposed copy of v is taken from a dense [T, 512] matrix; any other row
@@ -389,7 +412,8 @@ int dk_affine_f32(const float* x, float* y, int64_t n, float a, float b, void* s
  *  - GEMM: the route is the 128 x 128 kernel or the 256-column 8-wave kernel (generation 3) -- dk_gemm_plan_f16 never reports
  *    generation 4, and dk_tune_set("gemm", 10) / ("gemm_v4", v) have no effect on these launches.  The implicit-GEMM convolution
  *    (dk_conv3x3_f16) takes the same two kernels' conv forms; dk_conv3x3_plan_f16 reports its route.
- *  - Attention: head_dim 64, no score bias, no MX-fp8 copy; always the lean kernel (dk_tune_set("attn", 9 / 10) have no effect).
+ *  - Attention: head_dim 64, no score bias, no MX-fp8 copy; always the lean kernel (dk_tune_set("attn", 9 / 10) have no effect;
+ *    dk_attention_plan_f16 reports the route and refuses what the launch refuses).
  *    Scores, running maximum and sum in fp32, P rounded to fp16 for the P.V product.
  *  - dk_timestep_embedding_f16: evaluated in `embed_dtype` as before, stored as fp16.
  *  - dk_euler_cfg_step_f16 / dk_latent_to_tokens_f16: model_out and tokens are fp16, the latent stays fp32. */
@@ -397,6 +421,7 @@ int dk_gemm_f16(const dk_gemm_desc* d, void* stream);
 int dk_gemm_plan_f16(const dk_gemm_desc* d, const dk_gemm_desc* d2, dk_gemm_plan_t* plan);
 int dk_gemm_fused_f16(const dk_gemm_desc* d, const dk_gemm_side* f, const dk_gemm_desc* d2, const dk_gemm_side* f2, void* stream);
 int dk_attention_desc_f16(const dk_attention_desc* d, void* stream);
+int dk_attention_plan_f16(const dk_attention_desc* d, size_t workspace_bytes, dk_attention_plan_t* plan);
 int dk_ln_modulate_f16(const void* x, int32_t ldx, void* out, int32_t ldo, int32_t M, int32_t h,
                        const void* shift, const void* scale, int32_t mod_stride, int32_t mod_seg_len,
                        int32_t x_seg_len, int32_t x_seg_stride, float eps, void* stream);

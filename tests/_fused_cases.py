@@ -316,31 +316,27 @@ ATTN_Q_CASES = [
     # attention5.hip's key-split jobs (a range holds at least 12 key tiles: two ranges from S = 1536, four from 3072) load the same fused queries
     dict(id="wave_key_split_2", mode=10, attn_split=2, B=2, H=2, S=1536, D=128, split=300, norm=True, rope=True),
     dict(id="wave_key_split_4", mode=10, attn_split=4, B=1, H=2, S=3072, D=128, split=256, norm=True, rope=True),
+    # ... and the smallest shape at which the AUTOMATIC rule cuts: 96 blocks, all in the last round, two ranges on 256 CUs
+    dict(id="wave_auto_key_split_2", mode=10, B=1, H=16, S=1536, D=128, split=300, norm=True, rope=True),
 ]
 
-N_CU = 256  # compute units of the MI355X (what the launchers' rules see there)
+
+def attn_plan_desc(c):
+    """the dk_attention_desc fields of an ATTN_Q_CASES / ATTN_O8_CASES launch for dk_attention_plan: made-up aligned addresses (nothing is
+    dereferenced), q | k | v in one [B * S, 3h] buffer"""
+    B, H, S, D = c["B"], c["H"], c["S"], c["D"]
+    h, qkv, w = H * D, 0x10000000, 0x30000000
+    d = dict(q=qkv, k=qkv + 2 * h, v=qkv + 4 * h, out=0x20000000, B=B, H=H, S=S, D=D, ld=3 * h, ldo=h, scale=D ** -0.5)
+    if c.get("norm"):
+        d.update(qn_a=w, qn_b=w + 2 * D, qn_split=c["split"], qn_eps=KN_EPS)
+    if c.get("rope"):
+        d.update(q_rope=w + 4 * D)
+    if "in_kernel" in c:
+        d.update(O8=0x40000000, O8_scales=0x50000000, o8_ld=h, o8_rows=B * S)
+    return d
 
 
-def attn_path(c, with_o8=False):
-    """(kernel, key ranges) a case's launch takes: the arithmetic of dk_launch_attention (attention.hip) and dk_launch_attention5 (attention5.hip)
-    for a forced "attn" mode without score bias -- 10 falls back to 9 unless D = 128, S % 256 == 0, S >= 768; 9 to the lean kernel unless D = 128; the
-    one-wave-per-SIMD kernel cuts the blocks of its last, partial round of the CUs into "attn_split" key ranges of at least 12 tiles (never with O8)"""
-    mode, D, S = c["mode"], c["D"], c["S"]
-    if mode == 10 and not (D == 128 and S % 256 == 0 and S >= 768):
-        mode = 9
-    if mode == 9 and D != 128:
-        mode = 4
-    kernel = {4: "lean", 9: "alt", 10: "wave"}[mode]
-    ranges, want = 1, c.get("attn_split", -1)
-    tail = ((S + 255) // 256 * c["H"] * c["B"]) % N_CU
-    if kernel == "wave" and tail > 0 and not with_o8 and want != 0:
-        for s_ in (2, 3, 4):
-            if (S // 256) // s_ < 3:
-                break
-            if (s_ == want) if want > 0 else (tail * s_ <= N_CU and tail * s_ * 10 >= N_CU * 6):
-                ranges = s_
-                break
-    return kernel, ranges
+ATTN_KERNEL_NAMES = {4: "lean", 9: "alt", 10: "wave"}  # dk_attention_plan_t.kernel -> the prefix of a case's id
 
 
 def attn_claim(c):

@@ -211,25 +211,101 @@ def test_qknorm_table_covers_every_tail_path_of_both_kernels():
     assert seen[3] == {"fast", "wrap", "row"} and seen[4] == {"fast", "wrap", "cut", "row"}
 
 
+# ---- attention: dk_attention_plan asks dk_attention_route, the function the launchers take their kernel and key split from --------------------------
+def attn_plan(desc=None, ws=True, dtype=None, o8_split=0, attn=-1, attn_split=-1, **shape):
+    """the plan of a launch under the knobs "attn" / "attn_split" (reset afterwards); ``shape``: B, H, S, D of a dense q | k | v buffer instead of
+    ``desc``; ws: a workspace of dk_attention_workspace_bytes(), or none"""
+    from diffusionkit_amd import ops
+    lib = _lib.load()
+    if desc is None:
+        desc = fc.attn_plan_desc(shape)
+    try:
+        assert lib.dk_tune_set(b"attn", attn) == 0 and lib.dk_tune_set(b"attn_split", attn_split) == 0
+        return ops.attention_plan(dtype=dtype or ops.BF, workspace_bytes=lib.dk_attention_workspace_bytes() if ws else 0, o8_split=o8_split, **desc)
+    finally:
+        lib.dk_tune_set(b"attn", -1)
+        lib.dk_tune_set(b"attn_split", -1)
+
+
+def fields(p):
+    return [getattr(p, f) for f, _ in p._fields_]
+
+
 @pytest.mark.parametrize("case", fc.ATTN_Q_CASES + fc.ATTN_O8_CASES, ids=lambda c: c["id"])
 def test_attention_cases_run_the_kernel_they_name(case):
-    """dk_launch_attention turns mode 10 into 9 and 9 into the lean kernel without a word when a shape is not eligible, and attention5.hip's key split
-    needs 12 key tiles per range: the launchers' arithmetic (tests/_fused_cases.py: attn_path) against what the case's name claims"""
-    o8 = "in_kernel" in case
-    assert fc.attn_path(case, with_o8=o8) == fc.attn_claim(case), case["id"]
-    if o8:  # only the D = 128 kernels of modes 9 / 10 write the MX-fp8 copy themselves
-        assert case["in_kernel"] == (fc.attn_path(case, True)[0] in ("alt", "wave") and case["D"] == 128)
+    """dk_attention_route turns mode 10 into 9 and 9 into the lean kernel without a word when a shape is not eligible, and attention5.hip's key split
+    needs 12 key tiles per range: what the route answers for the case's knobs against what the case's name claims"""
+    p = attn_plan(fc.attn_plan_desc(case), attn=case["mode"], attn_split=case.get("attn_split", -1))
+    assert (fc.ATTN_KERNEL_NAMES[p.kernel], p.split) == fc.attn_claim(case), (case["id"], p.kernel, p.split)
+    assert p.merge == (p.split > 1) and p.jobs == (p.blocks - p.whole) * p.split * p.merge
+    if "in_kernel" in case:  # only the D = 128 kernels of modes 9 / 10 write the MX-fp8 copy themselves: a quantiser pass follows the others
+        assert case["in_kernel"] == (p.kernel in (9, 10) and case["D"] == 128)
+        assert p.quantize == (0 if case["in_kernel"] else 1) and p.launches == 1 + p.quantize
         assert (case["B"] * case["S"]) % 128 == 0
+    else:
+        assert p.qfuse == 1 and p.quantize == 0 and p.launches == 1 + p.merge
 
 
-def test_attention_path_arithmetic_matches_the_launcher_source():
-    """attn_path restates constants of the launchers: fail when the source no longer holds them"""
-    import os
-    csrc = os.path.join(os.path.dirname(_lib.HEADER_PATH), "..", "diffusionkit_amd", "csrc")
-    a5 = open(os.path.join(csrc, "attention5.hip")).read()
-    assert "p.D == 128 && p.bias == nullptr && p.S % 256 == 0 && p.S >= 12 * 64" in a5
-    assert "if ((p.S / 256) / s < 3) break;" in a5 and "tail * s <= n_cu && tail * s * 10 >= n_cu * 6" in a5
-    assert "tail > 0 && p.O8 == nullptr && g_dk_attn5_split != 0" in a5
-    a = open(os.path.join(csrc, "attention.hip")).read()
-    assert "if (mode == 10 && !dk_attention5_eligible(p)) mode = 9;" in a
-    assert "rc = p.D == 128 ? dk_launch_attention4(p, stream) : dk_launch_attention2(p, 4, stream);" in a
+FLUX = dict(H=24, D=128)
+
+
+def test_attention_headline_shapes_keep_their_measured_choices():
+    """the automatic choices the profiles were taken on (256 CUs, the workspace of dk_attention_workspace_bytes()); the expected values are worked out
+    by hand from the rules: FLUX 1024 x 1024 is S = 4352 = 17 blocks per head"""
+    assert attn_plan(B=1, S=4352, **FLUX).n_cu == 256
+    p = attn_plan(B=1, S=4352, **FLUX)  # 408 blocks: one round + 152, which no number of ranges fits into one sub-round
+    assert (p.kernel, p.blocks, p.whole, p.split, p.jobs, p.merge, p.launches) == (10, 408, 408, 1, 0, 0, 1)
+    p = attn_plan(B=2, S=4352, **FLUX)  # 816 = 3 rounds + 48: four ranges fill 192 CUs
+    assert (p.kernel, p.blocks - p.whole, p.split, p.jobs, p.merge, p.launches) == (10, 48, 4, 192, 1, 2)
+    p = attn_plan(B=4, S=4352, **FLUX)  # 1632 = 6 rounds + 96
+    assert (p.kernel, p.blocks - p.whole, p.split, p.jobs, p.whole) == (10, 96, 2, 192, 1536)
+    p = attn_plan(B=1, S=4608, **FLUX)  # FLUX-dev, S_t = 512: 432 = one round + 176
+    assert (p.kernel, p.split, p.whole) == (10, 1, 432)
+    p = attn_plan(B=1, S=2560, **FLUX)  # 768 x 768: 240 blocks in one round; two or three ranges overflow it, four would hold 8 tiles each
+    assert (p.kernel, p.blocks, p.split) == (10, 240, 1)
+    p = attn_plan(B=1, S=1280, **FLUX)  # 512 x 512: 120 blocks are less than three quarters of a round
+    assert (p.kernel, p.blocks, p.split, p.launches) == (4, 120, 1, 1)
+    p = attn_plan(B=2, S=1280, **FLUX)  # ... 240 are not; five tiles of 256 keys do not make two ranges
+    assert (p.kernel, p.split) == (10, 1)
+    assert attn_plan(B=1, S=4225, **FLUX).kernel == 9  # ragged: the one-wave-per-SIMD kernel wants S % 256 == 0
+    p = attn_plan(fc.attn_plan_desc(dict(B=1, S=4352, in_kernel=True, **FLUX)), o8_split=256)
+    assert (p.kernel, p.quantize, p.launches) == (9, 0, 1)  # the engines' row order of the MX-fp8 copy: attention5.hip does not write it
+    assert attn_plan(fc.attn_plan_desc(dict(B=1, S=1280, in_kernel=True, **FLUX)), o8_split=256).quantize == 2  # (the lean kernel: two-range pass)
+
+
+def test_attention_head_dim_64_and_score_bias_take_the_lean_kernel():
+    from diffusionkit_amd import ops
+    for H, S_txt in ((24, 589), (38, 333)):  # SD3-medium, SD3.5-large
+        for res in (512, 1024):
+            for dtype in (ops.BF, ops.F16):
+                for attn in (-1, 9, 10):
+                    p = attn_plan(B=2, H=H, S=S_txt + (res // 16) ** 2, D=64, dtype=dtype, attn=attn)
+                    assert (p.kernel, p.split, p.launches) == (4, 1, 1), (H, res, dtype, attn)
+    d = dict(fc.attn_plan_desc(dict(B=1, S=4352, **FLUX)), bias=0x60000000, bias_head_stride=4352 * 4352, ldb=4352)
+    for attn in (-1, 9, 10):  # a score bias: only the lean kernel has the form, whatever the knob says
+        assert attn_plan(d, attn=attn).kernel == 4
+    with pytest.raises(_lib.DkHipError, match="fp16 attention: head_dim 64"):
+        attn_plan(B=1, S=4352, dtype=ops.F16, **FLUX)
+
+
+def test_attention_plan_without_a_workspace_never_splits():
+    """workspace_bytes = 0 turns every split into 1 and changes nothing else; so does a workspace one job short"""
+    from diffusionkit_amd import ops
+    job = _lib.load().dk_attention_workspace_bytes() // 1020  # (the workspace holds 255 blocks x 4 ranges)
+    for B, S in ((1, 4352), (2, 4352), (4, 4352), (1, 4608), (1, 2560), (2, 1280), (1, 1280), (1, 4225)):
+        a, b = attn_plan(B=B, S=S, **FLUX), attn_plan(B=B, S=S, ws=False, **FLUX)
+        want = dict(zip([f for f, _ in a._fields_], fields(a)), split=1, whole=a.blocks, jobs=0, merge=0, launches=a.launches - a.merge)
+        assert fields(b) == list(want.values()), (B, S)
+        if a.split > 1:
+            d = fc.attn_plan_desc(dict(B=B, S=S, **FLUX))
+            assert ops.attention_plan(workspace_bytes=a.jobs * job, **d).split == a.split
+            assert fields(ops.attention_plan(workspace_bytes=a.jobs * job - 1, **d)) == fields(b)
+
+
+def test_attention_plan_mode_leaves_no_state_behind():
+    """two plans of one shape agree; a forced "attn_split" shows in the plan and is gone after the reset"""
+    assert fields(attn_plan(B=4, S=4352, **FLUX)) == fields(attn_plan(B=4, S=4352, **FLUX))
+    p = attn_plan(B=1, S=4352, attn_split=3, **FLUX)
+    assert (p.split, p.jobs, p.whole, p.merge) == (3, 456, 256, 1)
+    assert attn_plan(B=4, S=4352, attn_split=0, **FLUX).split == 1
+    assert attn_plan(B=1, S=4352, **FLUX).split == 1 and attn_plan(B=4, S=4352, **FLUX).split == 2

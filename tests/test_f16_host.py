@@ -15,7 +15,7 @@ import torch.multiprocessing as mp
 from diffusionkit_amd import _lib, cli
 from diffusionkit_amd.config import MMDIT_CKPT, SD3_2b, SD3_8b, MMDiTConfig, tiny_flux, tiny_sd3
 
-F16_SYMBOLS = ("dk_mmdit_set_activation_dtype", "dk_gemm_f16", "dk_gemm_plan_f16", "dk_gemm_fused_f16", "dk_attention_desc_f16", "dk_ln_modulate_f16",
+F16_SYMBOLS = ("dk_mmdit_set_activation_dtype", "dk_gemm_f16", "dk_gemm_plan_f16", "dk_gemm_fused_f16", "dk_attention_desc_f16", "dk_attention_plan_f16", "dk_ln_modulate_f16",
                "dk_qk_norm_rope_f16", "dk_timestep_embedding_f16", "dk_latent_to_tokens_f16", "dk_euler_cfg_step_f16")
 
 

@@ -293,7 +293,7 @@ def test_query_norm_rope_in_attention_q_load(dev, case):
     row s of the table (s, not b * S + s).  Reference: the oracle's rms_norm + rope_apply on q (Prec(BF)), then its sdpa.  Second assertion: the
     stand-alone pass over the q columns (k and v restored) + plain attention on the same kernel; the fused launch may be no further from it than
     twice that path's own distance from the oracle."""
-    from diffusionkit_amd import ops
+    from diffusionkit_amd import _lib, ops
     B, H, S, D, split = case["B"], case["H"], case["S"], case["D"], case["split"]
     h = H * D
     qkv = randn(B, S, 3 * h, seed=120)
@@ -309,6 +309,9 @@ def test_query_norm_rope_in_attention_q_load(dev, case):
         desc = dict(q=base, k=base + 2 * h, v=base + 4 * h, out=out, B=B, H=H, S=S, D=D, ld=3 * h, ldo=h, scale=scale,
                     qn_a=d_qa if case["norm"] else None, qn_b=d_qb if case["norm"] else None, qn_split=split, qn_eps=fc.KN_EPS, q_rope=d_tab)
         ops.attention_desc_call(**desc)
+        claim = fc.attn_claim(case)  # ... on the kernel and in the key ranges the case names, on THIS device
+        plan = ops.attention_plan(workspace_bytes=_lib.load().dk_attention_workspace_bytes(), **desc)
+        assert (fc.ATTN_KERNEL_NAMES[plan.kernel], plan.split) == claim, (case["id"], plan.kernel, plan.split, plan.n_cu)
         # the separate path: stand-alone pass over the rows of each side of the split, k / v restored, plain attention
         sep = d_qkv.clone()
         for s0, n, w in ((0, split, d_qa), (split, S - split, d_qb)):
@@ -318,7 +321,7 @@ def test_query_norm_rope_in_attention_q_load(dev, case):
         sep[..., h:] = d_qkv[..., h:]
         y_sep = ops.attention(sep, H, D)
         y_whole = None
-        if fc.attn_claim(case)[1] > 1:  # the key-split jobs: the same fused launch with whole blocks must differ in bits (bf16-rounded partials)
+        if claim[1] > 1:  # the key-split jobs: the same fused launch with whole blocks must differ in bits (bf16-rounded partials)
             ops.tune("attn_split", 0)
             y_whole = torch.empty_like(out)
             ops.attention_desc_call(**dict(desc, out=y_whole))
