@@ -207,6 +207,15 @@ SIGNATURES = {
     "dk_mmdit_cache_context": (_i32, [_vp, _vp, _vp]),
     "dk_mmdit_run_blocks": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "dk_mmdit_debug_buffer": (_vp, [_vp, _i32]),
+    # first-block cache: the engine's head / tail entries and the two kernels stand-alone
+    "dk_mmdit_set_block_cache": (_i32, [_vp, _i32]),
+    "dk_mmdit_reset_block_cache": (_i32, [_vp]),
+    "dk_mmdit_forward_head": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp]),
+    "dk_mmdit_forward_tail": (_i32, [_vp, _i32, _i32, _vp, _vp]),
+    "dk_block_probe_bf16": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "dk_block_probe_f16": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "dk_block_residual_bf16": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
+    "dk_block_residual_f16": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
     "dk_vae_create": (_i32, [C.POINTER(dk_vae_config), C.POINTER(_vp)]),
     "dk_vae_destroy": (None, [_vp]),
     "dk_vae_bind": (_i32, [_vp, C.c_char_p, _vp]),

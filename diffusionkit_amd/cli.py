@@ -56,6 +56,10 @@ def build_parser(model_versions: Sequence[str]) -> argparse.ArgumentParser:
                    help="Inpainting mask for --image-path (first channel; 255 = repaint, 0 = keep; resized to the image with NEAREST).")
     p.add_argument("--no-composite", action="store_true",
                    help="With --mask-path: do not paste the kept pixels of the input image back over the decoded image.")
+    p.add_argument("--block-cache", type=float, default=None, metavar="THRESHOLD",
+                   help="First-block cache: skip the blocks behind block 0 in steps where block 0's effect moved by less than THRESHOLD "
+                        "(a float >= 0, relative to the last computed step). Published implementations use about 0.1 for FLUX; no value "
+                        "has been validated here on a real checkpoint.")
     p.add_argument("--local-ckpt", default=None, type=str, help="Path to the local mmdit checkpoint.")
     p.add_argument("--ckpt", action="append", default=[], metavar="KEY=PATH",
                    help="Further local checkpoint parts (vae_decoder, vae_encoder, clip_l, clip_g, t5, t5_tokenizer, "
@@ -118,6 +122,10 @@ def resolve(args) -> dict:
         r["mask_path"] = args.mask_path
     if getattr(args, "no_composite", False):
         r["composite"] = False
+    if getattr(args, "block_cache", None) is not None:  # (a key only when the flag is given)
+        if not args.block_cache >= 0.0:
+            raise ValueError("Block cache threshold must be a float >= 0")
+        r["block_cache"] = args.block_cache
     return r
 
 
@@ -151,7 +159,7 @@ def main(argv: Optional[Sequence[str]] = None, pipeline_overrides: Optional[dict
     image, log = sd.generate_image(args.prompt, cfg_weight=r["cfg"], num_steps=args.steps, seed=args.seed,
                                    negative_text=args.negative_prompt, latent_size=latent_size, image_path=args.image_path,
                                    denoise=args.denoise, verbose=args.verbose, mask_path=r.get("mask_path"),
-                                   composite=r.get("composite", True))
+                                   composite=r.get("composite", True), block_cache=r.get("block_cache"))
     if log["text_encoding"].get("synthetic"):
         logger.warning("no text-encoder checkpoints were named (--ckpt clip_l=... t5=...): the conditioning is synthetic")
     image.save(args.output_path)

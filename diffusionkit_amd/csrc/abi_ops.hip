@@ -275,6 +275,31 @@ extern "C" int dk_ln_modulate_f16(const void* x, int32_t ldx, void* out, int32_t
   return ln_modulate(DK_DTYPE_F16, x, ldx, out, ldo, M, h, shift, scale, mod_stride, mod_seg_len, x_seg_len, x_seg_stride, eps, stream);
 }
 
+static int block_probe(int dtype, const void* x, int ldx, int x_seg_len, int x_seg_stride, void* d, const void* d_ref, float* row_partials,
+                       float* probe, int M, int h, int rows_per_batch, void* stream) {
+  return DK_EL(dtype, dk_launch_block_probe)((const bf16_t*)x, ldx, x_seg_len, x_seg_stride, (bf16_t*)d, (const bf16_t*)d_ref, row_partials, probe, M, h,
+                                             rows_per_batch, S_(stream));
+}
+extern "C" int dk_block_probe_bf16(const void* x, int32_t ldx, int32_t x_seg_len, int32_t x_seg_stride, void* d, const void* d_ref,
+                                   float* row_partials, float* probe, int32_t M, int32_t h, int32_t rows_per_batch, void* stream) {
+  return block_probe(DK_DTYPE_BF16, x, ldx, x_seg_len, x_seg_stride, d, d_ref, row_partials, probe, M, h, rows_per_batch, stream);
+}
+extern "C" int dk_block_probe_f16(const void* x, int32_t ldx, int32_t x_seg_len, int32_t x_seg_stride, void* d, const void* d_ref,
+                                  float* row_partials, float* probe, int32_t M, int32_t h, int32_t rows_per_batch, void* stream) {
+  return block_probe(DK_DTYPE_F16, x, ldx, x_seg_len, x_seg_stride, d, d_ref, row_partials, probe, M, h, rows_per_batch, stream);
+}
+static int block_residual(int dtype, void* x, int ldx, int x_seg_len, int x_seg_stride, void* r, int M, int h, int reuse, void* stream) {
+  return DK_EL(dtype, dk_launch_block_residual)((bf16_t*)x, ldx, x_seg_len, x_seg_stride, (bf16_t*)r, M, h, reuse != 0, S_(stream));
+}
+extern "C" int dk_block_residual_bf16(void* x, int32_t ldx, int32_t x_seg_len, int32_t x_seg_stride, void* r, int32_t M, int32_t h,
+                                      int32_t reuse, void* stream) {
+  return block_residual(DK_DTYPE_BF16, x, ldx, x_seg_len, x_seg_stride, r, M, h, reuse, stream);
+}
+extern "C" int dk_block_residual_f16(void* x, int32_t ldx, int32_t x_seg_len, int32_t x_seg_stride, void* r, int32_t M, int32_t h,
+                                     int32_t reuse, void* stream) {
+  return block_residual(DK_DTYPE_F16, x, ldx, x_seg_len, x_seg_stride, r, M, h, reuse, stream);
+}
+
 // mx8_out: the descriptor's C_scales / c_rows / c_row0 / c_col0 describe an MX-fp8 output (its own, or the second one of a column split)
 static int gemm_f8_params_from_desc(const dk_gemm_fp8_desc* d, bool mx8_out, GemmF8Params& p) {
   memset(&p, 0, sizeof(p));

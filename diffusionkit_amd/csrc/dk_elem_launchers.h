@@ -38,3 +38,9 @@ int dk_launch_euler_step_masked(float* x, const bf16_t* model_out, int ld_out, b
                                 int Hl, int Wl, int C, int p, int reshape_order, float sigma, float sigma_next,
                                 float cfg_weight, const float* x_orig, const float* noise, const float* mask,
                                 int mask_per_image, hipStream_t stream);
+// first-block cache (include/dk_hip.h): d = round(x - d) over M rows of x through the row map, (num, den) = (sum |d - d_ref|, sum |d_ref|) per
+// row into row_partials [M][2], then per rows_per_batch rows in a fixed order into probe [M / rows_per_batch][2]; d_ref null: read as zeros
+int dk_launch_block_probe(const bf16_t* x, int ldx, int x_seg_len, int x_seg_stride, bf16_t* d, const bf16_t* d_ref, float* row_partials,
+                          float* probe, int M, int h, int rows_per_batch, hipStream_t stream);
+// reuse false: r = round(x - r); true: x = round(x + r)
+int dk_launch_block_residual(bf16_t* x, int ldx, int x_seg_len, int x_seg_stride, bf16_t* r, int M, int h, bool reuse, hipStream_t stream);

@@ -500,3 +500,148 @@ int dk_launch_euler_step_masked(float* x, const bf16_t* model_out, int ld_out, b
   DK_CHECK_HIP(hipGetLastError());
   return 0;
 }
+
+// ---------------------------------------------------------------------------------------------
+// First-block cache (include/dk_hip.h; no reference counterpart): what block 0 did to the image rows of the joint stream, compared
+// with what it did in the last computed step, and the cached effect of the blocks behind it.  fp32 arithmetic, one rounding to the
+// element type per stored value.
+// Probe: one wave per image row, 4 rows per workgroup, the row's three operands loaded up front as in dk_ln_modulate_kernel (buffer
+// loads whose resource spans one row: lanes past the row end read zeros, their stores are dropped).  d holds X0's row on entry and
+// D_cur = round(x - d) on return; (num, den) = (sum |D_cur - D_ref|, sum |D_ref|) of the row: each lane adds its elements in index order,
+// wave_sum folds the lanes in a fixed butterfly -- no atomics, the same bits on every run.  A null d_ref is a resource of zero bytes: it
+// reads as zeros, den = 0.
+// ---------------------------------------------------------------------------------------------
+template <int NCH>
+__global__ __launch_bounds__(256) void dk_block_probe_kernel(const bf16_t* x, int ldx, int x_seg_len, int x_seg_stride, bf16_t* d,
+                                                             const bf16_t* d_ref, float* row_partials, int M, int h) {
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int m = (int)blockIdx.x * 4 + wave;
+  if (m >= M) return;
+  const size_t xrow = (size_t)((m / x_seg_len) * x_seg_stride + (m % x_seg_len)) * ldx;
+  bf16_t* drow = d + (size_t)m * h;
+  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(x + xrow), 0, h * 2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc((void*)drow, 0, h * 2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rr =
+      __builtin_amdgcn_make_buffer_rsrc(d_ref ? (void*)(d_ref + (size_t)m * h) : (void*)drow, 0, d_ref ? h * 2 : 0, 0x00020000);
+  u32x4 a[NCH], p[NCH], r[NCH];
+#pragma unroll
+  for (int i = 0; i < NCH; ++i) a[i] = __builtin_amdgcn_raw_buffer_load_b128(rx, (lane + 64 * i) * 16, 0, 0);
+#pragma unroll
+  for (int i = 0; i < NCH; ++i) {
+    p[i] = __builtin_amdgcn_raw_buffer_load_b128(rd, (lane + 64 * i) * 16, 0, 0);
+    r[i] = __builtin_amdgcn_raw_buffer_load_b128(rr, (lane + 64 * i) * 16, 0, 0);
+  }
+  __builtin_amdgcn_sched_barrier(0);  // (without it the scheduler sinks some of the loads of d below the first stores to it)
+  float num = 0.f, den = 0.f;
+#pragma unroll
+  for (int i = 0; i < NCH; ++i) {
+    u32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float a0, a1, p0, p1, r0, r1, d0, d1;
+      unpack2(a[i][e], a0, a1);
+      unpack2(p[i][e], p0, p1);
+      unpack2(r[i][e], r0, r1);
+      o[e] = pack2(a0 - p0, a1 - p1);
+      unpack2(o[e], d0, d1);  // (the stored, rounded difference is what is compared)
+      num += fabsf(d0 - r0);
+      num += fabsf(d1 - r1);
+      den += fabsf(r0);
+      den += fabsf(r1);
+    }
+    __builtin_amdgcn_raw_buffer_store_b128(o, rd, (lane + 64 * i) * 16, 0, 0);
+  }
+  num = wave_sum(num);
+  den = wave_sum(den);
+  if (lane == 0) {
+    row_partials[2 * (size_t)m] = num;
+    row_partials[2 * (size_t)m + 1] = den;
+  }
+}
+// ... and the rows of one batch row: one wave per batch row, lane l adds rows l, l + 64, ... in that order, wave_sum folds the lanes
+__global__ __launch_bounds__(64) void dk_block_probe_fold_kernel(const float* row_partials, float* probe, int rows_per_batch) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const float* p = row_partials + 2 * (size_t)b * rows_per_batch;
+  float num = 0.f, den = 0.f;
+  int r = lane;
+  for (; r + 7 * 64 < rows_per_batch; r += 8 * 64) {  // (eight independent loads in flight, the additions in the same order as one by one)
+    float2 v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = *(const float2*)(p + 2 * (size_t)(r + 64 * u));
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      num += v[u].x;
+      den += v[u].y;
+    }
+  }
+  for (; r < rows_per_batch; r += 64) {
+    num += p[2 * (size_t)r];
+    den += p[2 * (size_t)r + 1];
+  }
+  num = wave_sum(num);
+  den = wave_sum(den);
+  if (lane == 0) {
+    probe[2 * b] = num;
+    probe[2 * b + 1] = den;
+  }
+}
+static int check_block_rows(const void* x, int ldx, int x_seg_len, const void* dense, int M, int h) {
+  DK_REQUIRE(h > 0 && h % 8 == 0 && h <= 4096, "hidden size must be a multiple of 8 (rows move as 16-byte vectors) and <= 4096");
+  DK_REQUIRE(x != nullptr && dense != nullptr && M > 0 && x_seg_len > 0, "null / empty argument");
+  DK_REQUIRE(ldx % 8 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)dense & 15) == 0, "rows must keep 16-byte alignment");
+  return 0;
+}
+int dk_launch_block_probe(const bf16_t* x, int ldx, int x_seg_len, int x_seg_stride, bf16_t* d, const bf16_t* d_ref, float* row_partials,
+                          float* probe, int M, int h, int rows_per_batch, hipStream_t stream) {
+  if (const int rc = check_block_rows(x, ldx, x_seg_len, d, M, h)) return rc;
+  DK_REQUIRE(row_partials != nullptr && probe != nullptr && ((uintptr_t)d_ref & 15) == 0 && ((uintptr_t)row_partials & 7) == 0,
+             "null / misaligned argument");
+  DK_REQUIRE(rows_per_batch > 0 && M % rows_per_batch == 0, "the rows must be whole batch rows of rows_per_batch rows");
+  dim3 grid((M + 3) / 4), block(256);
+#define PROBE_CASE(N)                                                                                                                   \
+  case N:                                                                                                                               \
+    hipLaunchKernelGGL(dk_block_probe_kernel<N>, grid, block, 0, stream, x, ldx, x_seg_len, x_seg_stride, d, d_ref, row_partials, M, h); \
+    break;
+  switch ((h / 8 + 63) / 64) {
+    PROBE_CASE(1) PROBE_CASE(2) PROBE_CASE(3) PROBE_CASE(4) PROBE_CASE(5) PROBE_CASE(6) PROBE_CASE(7) PROBE_CASE(8)
+    default: DK_REQUIRE(false, "unsupported hidden size");
+  }
+#undef PROBE_CASE
+  DK_CHECK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(dk_block_probe_fold_kernel, dim3(M / rows_per_batch), dim3(64), 0, stream, row_partials, probe, rows_per_batch);
+  DK_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// REUSE false: r = round(x - r), in place over the saved X1 (x is read only); true: x = round(x + r).  One 16-byte chunk per thread;
+// x through the row map, r dense [M, h].
+template <bool REUSE>
+__global__ __launch_bounds__(256) void dk_block_residual_kernel(bf16_t* x, int ldx, int x_seg_len, int x_seg_stride, bf16_t* r, int M, int cpr) {
+  const unsigned gid = blockIdx.x * 256u + threadIdx.x;  // (32-bit: M * cpr < 2^31, checked by the launcher)
+  if (gid >= (unsigned)M * (unsigned)cpr) return;
+  const int m = (int)(gid / (unsigned)cpr), c = (int)(gid - (unsigned)m * (unsigned)cpr);
+  bf16_t* xp = x + (size_t)((m / x_seg_len) * x_seg_stride + (m % x_seg_len)) * ldx + c * 8;
+  bf16_t* rp = r + ((size_t)m * cpr + c) * 8;
+  const u32x4 a = *(const u32x4*)xp, b = *(const u32x4*)rp;
+  u32x4 o;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    float a0, a1, b0, b1;
+    unpack2(a[e], a0, a1);
+    unpack2(b[e], b0, b1);
+    o[e] = REUSE ? pack2(a0 + b0, a1 + b1) : pack2(a0 - b0, a1 - b1);
+  }
+  *(u32x4*)(REUSE ? xp : rp) = o;
+}
+int dk_launch_block_residual(bf16_t* x, int ldx, int x_seg_len, int x_seg_stride, bf16_t* r, int M, int h, bool reuse, hipStream_t stream) {
+  if (const int rc = check_block_rows(x, ldx, x_seg_len, r, M, h)) return rc;
+  const int cpr = h / 8;
+  DK_REQUIRE((long)M * cpr < (1L << 31) - 256, "block_residual: rows * h / 8 must stay below 2^31");
+  dim3 grid((unsigned)(((long)M * cpr + 255) / 256)), block(256);
+  if (reuse)
+    hipLaunchKernelGGL(dk_block_residual_kernel<true>, grid, block, 0, stream, x, ldx, x_seg_len, x_seg_stride, r, M, cpr);
+  else
+    hipLaunchKernelGGL(dk_block_residual_kernel<false>, grid, block, 0, stream, x, ldx, x_seg_len, x_seg_stride, r, M, cpr);
+  DK_CHECK_HIP(hipGetLastError());
+  return 0;
+}

@@ -67,6 +67,15 @@ struct dk_mmdit {
   long rows8 = 0;
   // element type of every bound tensor, activation buffer and of the token / text / pooled I/O (dk_mmdit_set_activation_dtype): sizes are the same
   int dtype = DK_DTYPE_BF16;
+  // first-block cache (dk_mmdit_set_block_cache; include/dk_hip.h): image rows [B * S_i, h] each.  BC_R: X1 at the start of a compute tail, R
+  // behind it.  BC_D[bc_cur]: X0 before block 0, D_cur behind the probe; BC_D[1 - bc_cur]: D_ref -- a compute tail swaps the two.
+  // BC_ROWS: the probe's (num, den) per image row.  bc_valid: R / D_ref come from a computed step since the last reset; bc_pending: the step
+  // whose head ran last and waits for its tail, or -1
+  bool bc_on = false, bc_valid = false;
+  int bc_cur = 0, bc_pending = -1;
+  bf16_t *BC_R = nullptr, *BC_D[2] = {nullptr, nullptr};
+  float* BC_ROWS = nullptr;
+  void bc_reset() { bc_valid = false; bc_pending = -1; }
   // what a call on `stream` hands its launches: this engine's element type and ITS regions (for D = 64 no attention region: unsplit launches)
   LaunchCtx ctx(void* stream) const { return LaunchCtx{S_(stream), dtype, GWS, AttnWs{AWS, AWS_bytes}}; }
   bool fp8() const { return cfg.fp8_linears != 0; }
@@ -291,6 +300,13 @@ static size_t mmdit_carve(dk_mmdit* m, Carver& c, int B, int Hl, int Wl, int S_t
   // host thread on different streams must not share the partial results of their split launches)
   m->AWS_bytes = m->D() == 128 ? dk_attention_workspace_bytes() : 0;
   m->AWS = c.take(m->AWS_bytes);
+  if (m->bc_on) {  // (behind everything else: with the cache off the carve is what it was)
+    const size_t img = (size_t)B * S_i * h * 2;
+    m->BC_R = (bf16_t*)c.take(img);
+    m->BC_D[0] = (bf16_t*)c.take(img);
+    m->BC_D[1] = (bf16_t*)c.take(img);
+    m->BC_ROWS = (float*)c.take((size_t)B * S_i * 2 * 4);
+  }
   return c.off;
 }
 
@@ -333,6 +349,7 @@ extern "C" int dk_mmdit_prepare(dk_mmdit* m, int32_t batch, int32_t latent_h, in
   m->prepared = true;
   m->mod_ready = false;
   m->ctx_ready = false;
+  m->bc_reset();
   return 0;
 }
 
@@ -366,6 +383,7 @@ extern "C" int dk_mmdit_cache_modulation_params(dk_mmdit* m, const void* pooled,
   const int Nmod = m->mod_rows() * h;
   DK_TRY(dk_launch_gemm(Linear(dt, dense(m->vec, h), m->adaln_w, m->adaln_b, dense(m->MOD, Nmod), n * B, Nmod, h, DK_EPI_BIAS), st));
   m->mod_ready = true;
+  m->bc_reset();  // (R and D_ref belong to the conditioning they were computed under)
   return 0;
 }
 
@@ -668,16 +686,11 @@ static int mmdit_blocks(dk_mmdit* m, const bf16_t* mod_step, int first, int coun
   return 0;
 }
 
-extern "C" int dk_mmdit_forward(dk_mmdit* m, const void* tokens_in, const void* text, int32_t step_index, void* tokens_out,
-                                void* stream) {
-  DK_REQUIRE(m && m->prepared && m->mod_ready, "prepare + cache_modulation_params must precede forward");
-  DK_REQUIRE(step_index >= 0 && step_index < m->n_t, "step index out of range");
-  const LaunchCtx L = m->ctx(stream);
+// the embedders of a forward call: text rows and image rows of the joint stream m->X
+static int mmdit_embed(dk_mmdit* m, const void* tokens_in, const void* text, const LaunchCtx& L) {
   const hipStream_t st = L.st;
   const dk_mmdit_config& c = m->cfg;
   const int h = m->h(), B = m->B, S = m->S, S_t = m->S_t, S_i = m->S_i, F = m->F();
-  const bf16_t* mod_step = m->MOD + (size_t)step_index * B * m->mod_rows() * h;
-
   // context_embedder (mmdit.py:195): text rows of the joint stream -- recomputed from `text`, or copied from the
   // step-invariant result of dk_mmdit_cache_context when `text` is null
   if (text != nullptr) {
@@ -693,9 +706,81 @@ extern "C" int dk_mmdit_forward(dk_mmdit* m, const void* tokens_in, const void* 
                                c.use_pos_embed ? DK_EPI_RES : DK_EPI_BIAS)
                             .gate_res(nullptr, 0, 0, Rows{c.use_pos_embed ? m->POS : nullptr, h, S_i, 0}),
                         st));
-  const int n_blocks = c.depth_multimodal + c.depth_unified;
-  DK_TRY(mmdit_blocks(m, mod_step, 0, n_blocks, L));
+  return 0;
+}
+
+extern "C" int dk_mmdit_forward(dk_mmdit* m, const void* tokens_in, const void* text, int32_t step_index, void* tokens_out,
+                                void* stream) {
+  DK_REQUIRE(m && m->prepared && m->mod_ready, "prepare + cache_modulation_params must precede forward");
+  DK_REQUIRE(step_index >= 0 && step_index < m->n_t, "step index out of range");
+  const LaunchCtx L = m->ctx(stream);
+  const bf16_t* mod_step = m->MOD + (size_t)step_index * m->B * m->mod_rows() * m->h();
+  m->bc_pending = -1;  // (a head without its tail is dropped: this call overwrites the stream it left; R / D_ref stay)
+  DK_TRY(mmdit_embed(m, tokens_in, text, L));
+  DK_TRY(mmdit_blocks(m, mod_step, 0, m->cfg.depth_multimodal + m->cfg.depth_unified, L));
   return mmdit_final_layer(m, mod_step, (bf16_t*)tokens_out, L);
+}
+
+// ---- first-block cache (include/dk_hip.h) -----------------------------------------------------------------------------------------
+extern "C" int dk_mmdit_set_block_cache(dk_mmdit* m, int32_t on) {
+  DK_REQUIRE(m != nullptr, "null handle");
+  if (m->bc_on != (on != 0)) m->prepared = false;  // (another carve: dk_mmdit_prepare must follow)
+  m->bc_on = on != 0;
+  m->bc_reset();
+  return 0;
+}
+extern "C" int dk_mmdit_reset_block_cache(dk_mmdit* m) {
+  DK_REQUIRE(m != nullptr, "null handle");
+  m->bc_reset();
+  return 0;
+}
+// image rows of the stream <-> a dense [B * S_i, h] buffer
+static int bc_save_img(const dk_mmdit* m, bf16_t* dst, hipStream_t st) {
+  const size_t row = (size_t)m->S_i * m->h() * 2;
+  DK_CHECK_HIP(hipMemcpy2DAsync(dst, row, m->X + (size_t)m->S_t * m->h(), (size_t)m->S * m->h() * 2, row, m->B, hipMemcpyDeviceToDevice, st));
+  return 0;
+}
+extern "C" int dk_mmdit_forward_head(dk_mmdit* m, const void* tokens_in, const void* text, int32_t step_index, float* probe_out, void* stream) {
+  DK_REQUIRE(m && m->prepared && m->mod_ready, "prepare + cache_modulation_params must precede forward_head");
+  DK_REQUIRE(m->bc_on, "forward_head needs the block cache: dk_mmdit_set_block_cache(m, 1) before dk_mmdit_prepare");
+  DK_REQUIRE(probe_out != nullptr, "null argument");
+  DK_REQUIRE(step_index >= 0 && step_index < m->n_t, "step index out of range");
+  const LaunchCtx L = m->ctx(stream);
+  const int h = m->h();
+  const bf16_t* mod_step = m->MOD + (size_t)step_index * m->B * m->mod_rows() * h;
+  m->bc_pending = -1;
+  DK_TRY(mmdit_embed(m, tokens_in, text, L));
+  bf16_t* dcur = m->BC_D[m->bc_cur];
+  DK_TRY(bc_save_img(m, dcur, L.st));  // X0
+  DK_TRY(mmdit_blocks(m, mod_step, 0, 1, L));
+  DK_TRY(DK_EL(L.dtype, dk_launch_block_probe)(m->X + (size_t)m->S_t * h, h, m->S_i, m->S, dcur, m->bc_valid ? m->BC_D[1 - m->bc_cur] : nullptr,
+                                               m->BC_ROWS, probe_out, m->B * m->S_i, h, m->S_i, L.st));
+  m->bc_pending = step_index;
+  return 0;
+}
+extern "C" int dk_mmdit_forward_tail(dk_mmdit* m, int32_t step_index, int32_t reuse, void* tokens_out, void* stream) {
+  DK_REQUIRE(m && m->prepared && m->mod_ready, "prepare + cache_modulation_params must precede forward_tail");
+  DK_REQUIRE(m->bc_on && tokens_out != nullptr, "forward_tail needs the block cache and an output");
+  DK_REQUIRE(m->bc_pending >= 0, "forward_tail needs a pending head: dk_mmdit_forward_head of this step must run first");
+  DK_REQUIRE(m->bc_pending == step_index, "forward_tail must be of the same step as the pending head");
+  if (reuse) DK_REQUIRE(m->bc_valid, "forward_tail(reuse = 1) needs a valid cache: a computed step since the last prepare / cache_modulation_params / reset");
+  const LaunchCtx L = m->ctx(stream);
+  const int h = m->h(), Mi = m->B * m->S_i;
+  const bf16_t* mod_step = m->MOD + (size_t)step_index * m->B * m->mod_rows() * h;
+  bf16_t* x_img = m->X + (size_t)m->S_t * h;
+  m->bc_pending = -1;
+  if (reuse) {
+    DK_TRY(DK_EL(L.dtype, dk_launch_block_residual)(x_img, h, m->S_i, m->S, m->BC_R, Mi, h, true, L.st));
+    return mmdit_final_layer(m, mod_step, (bf16_t*)tokens_out, L);
+  }
+  m->bc_valid = false;  // (R is being rewritten; valid again once every launch of this tail is queued)
+  DK_TRY(bc_save_img(m, m->BC_R, L.st));  // X1
+  DK_TRY(mmdit_blocks(m, mod_step, 1, m->cfg.depth_multimodal + m->cfg.depth_unified - 1, L));
+  DK_TRY(mmdit_final_layer(m, mod_step, (bf16_t*)tokens_out, L));
+  DK_TRY(DK_EL(L.dtype, dk_launch_block_residual)(x_img, h, m->S_i, m->S, m->BC_R, Mi, h, false, L.st));
+  m->bc_cur = 1 - m->bc_cur;  // D_ref <- D_cur
+  m->bc_valid = true;
+  return 0;
 }
 
 // Teacher-forced block range (include/dk_hip.h): x_in -> m->X, blocks [first, first + count), m->X -> x_out
@@ -718,6 +803,8 @@ extern "C" int dk_mmdit_run_blocks(dk_mmdit* m, const void* x_in, void* x_out, i
 
 extern "C" const void* dk_mmdit_debug_buffer(const dk_mmdit* m, int32_t which) {
   if (!m || !m->prepared) return nullptr;
+  if (which >= 3 && which <= 5)  // R, D_ref, D_cur (5: the probe's output between a head and its tail; a compute tail makes that buffer D_ref)
+    return !m->bc_on ? nullptr : which == 3 ? (const void*)m->BC_R : (const void*)m->BC_D[which == 4 ? 1 - m->bc_cur : m->bc_cur];
   return which == 0 ? (const void*)m->X : which == 1 ? (const void*)m->MOD : which == 2 ? (const void*)m->GWS : nullptr;
 }
 

@@ -92,6 +92,7 @@ class MMDiTEngine:
         self._shape = None
         self._ws = None
         self._n_cached = 0
+        self.block_cache = False
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -172,6 +173,14 @@ class MMDiTEngine:
 
     def forward_tokens(self, tokens_in: Tensor, text: Optional[Tensor], step_index: int, tokens_out: Optional[Tensor] = None) -> Tensor:
         """MMDiT.__call__ between patchify and unpatchify (mmdit.py:188-252).  ``text=None`` uses ``cache_context``'s result."""
+        self._check_forward_args(tokens_in, text, step_index)
+        if tokens_out is None:
+            tokens_out = torch.empty_like(tokens_in)
+        _lib.check(self.lib.dk_mmdit_forward(self._h, tokens_in.data_ptr(), None if text is None else text.data_ptr(), step_index,
+                                             tokens_out.data_ptr(), _stream()), "dk_mmdit_forward")
+        return tokens_out
+
+    def _check_forward_args(self, tokens_in: Tensor, text: Optional[Tensor], step_index: int) -> None:
         _require_cuda(tokens_in, "tokens_in", self.dtype)
         if tuple(tokens_in.shape) != self.tokens_shape():
             raise _lib.DkHipError(f"tokens_in shape {tuple(tokens_in.shape)} != {self.tokens_shape()}")
@@ -184,10 +193,44 @@ class MMDiTEngine:
                 raise _lib.DkHipError(f"text shape {tuple(text.shape)} does not match the prepared problem")
         if not (0 <= step_index < self._n_cached):
             raise KeyError(f"no cached modulation parameters for step {step_index}")  # reference: dict KeyError
+
+    # -- first-block cache (include/dk_hip.h; no reference counterpart) ----------------------------------------------------
+    def enable_block_cache(self, on: bool = True) -> None:
+        """Turn the first-block cache on or off.  The workspace layout changes with it, so the next ``prepare`` carves again (and the
+        modulation parameters and the context must be cached again)."""
+        if bool(on) == self.block_cache:
+            return
+        _lib.check(self.lib.dk_mmdit_set_block_cache(self._h, int(bool(on))), "dk_mmdit_set_block_cache")
+        self.block_cache = bool(on)
+        self._shape = None
+        self._n_cached = 0
+        self._ctx_cached = False
+
+    def reset_block_cache(self) -> None:
+        _lib.check(self.lib.dk_mmdit_reset_block_cache(self._h), "dk_mmdit_reset_block_cache")
+
+    def forward_head(self, tokens_in: Tensor, text: Optional[Tensor], step_index: int) -> Tensor:
+        """Embedders, block 0 and the probe of step ``step_index``: returns f32 [batch, 2] on the device, (num, den) per batch row =
+        (sum |D_cur - D_ref|, sum |D_ref|) over the image rows (den = 0 before any computed step).  Nothing synchronises: read it
+        (``.cpu()``) to decide, then call ``forward_tail`` for the same step."""
+        self._check_forward_args(tokens_in, text, step_index)
+        probe = torch.empty(self._shape[0], 2, dtype=torch.float32, device=tokens_in.device)
+        _lib.check(self.lib.dk_mmdit_forward_head(self._h, tokens_in.data_ptr(), None if text is None else text.data_ptr(), step_index,
+                                                  probe.data_ptr(), _stream()), "dk_mmdit_forward_head")
+        return probe
+
+    def forward_tail(self, step_index: int, reuse: bool, tokens_out: Optional[Tensor] = None) -> Tensor:
+        """The rest of the step whose head ran last.  ``reuse`` False: blocks 1 .. L-1 and the final layer, and their effect on the
+        image rows is cached; True: that cached effect is added instead and only the final layer runs."""
+        if self._shape is None:
+            raise _lib.DkHipError("prepare() must be called before forward_tail()")
         if tokens_out is None:
-            tokens_out = torch.empty_like(tokens_in)
-        _lib.check(self.lib.dk_mmdit_forward(self._h, tokens_in.data_ptr(), None if text is None else text.data_ptr(), step_index,
-                                             tokens_out.data_ptr(), _stream()), "dk_mmdit_forward")
+            tokens_out = torch.empty(self.tokens_shape(), dtype=self.dtype, device=self._ws.device)
+        _require_cuda(tokens_out, "tokens_out", self.dtype)
+        if tuple(tokens_out.shape) != self.tokens_shape():
+            raise _lib.DkHipError(f"tokens_out shape {tuple(tokens_out.shape)} != {self.tokens_shape()}")
+        _lib.check(self.lib.dk_mmdit_forward_tail(self._h, step_index, int(bool(reuse)), tokens_out.data_ptr(), _stream()),
+                   "dk_mmdit_forward_tail")
         return tokens_out
 
     def run_blocks(self, x: Tensor, step_index: int, first_block: int, n_blocks: int = 1) -> Tensor:

@@ -330,6 +330,43 @@ def ln_modulate(x: Tensor, shift: Tensor, scale: Tensor, eps: float = 1e-6) -> T
     return out
 
 
+def block_probe(x: Tensor, s_t: int, d: Tensor, d_ref: Optional[Tensor] = None):
+    """First-block-cache probe (dk_block_probe_*).  x: the joint stream [B, S, h] behind block 0 (text rows first, ``s_t`` of them per
+    batch row; only the image rows are read); d: [B, S - s_t, h], X0's image rows on entry, D_cur = round(x - d) on return; d_ref: the
+    same shape, or None (den = 0).  Returns (d, probe) with probe f32 [B, 2] = (sum |D_cur - D_ref|, sum |D_ref|) per batch row."""
+    lib = _lib.load()
+    name = "dk_block_probe_" + _elem(x.dtype, "block_probe")
+    _require_cuda(x, "x")
+    _require_cuda(d, "d", x.dtype)
+    if d_ref is not None:
+        _require_cuda(d_ref, "d_ref", x.dtype)
+    B, S, h = x.shape
+    s_i = S - s_t
+    for n, t in (("d", d), ("d_ref", d_ref)):
+        if t is not None and tuple(t.shape) != (B, s_i, h):
+            raise _lib.DkHipError(f"{n} shape {tuple(t.shape)} != {(B, s_i, h)}")
+    rows = torch.empty(B * s_i, 2, dtype=torch.float32, device=x.device)
+    probe = torch.empty(B, 2, dtype=torch.float32, device=x.device)
+    _lib.check(getattr(lib, name)(x.data_ptr() + s_t * h * x.element_size(), h, s_i, S, d.data_ptr(), _ptr(d_ref), rows.data_ptr(),
+                                  probe.data_ptr(), B * s_i, h, s_i, _stream()), name)
+    return d, probe
+
+
+def block_residual(x: Tensor, s_t: int, r: Tensor, reuse: bool) -> Tensor:
+    """dk_block_residual_* on the image rows of the joint stream x [B, S, h] and r [B, S - s_t, h].  reuse False: r = round(x - r) in place
+    (r held X1's image rows), returns r; True: x's image rows = round(x + r) in place, returns x."""
+    lib = _lib.load()
+    name = "dk_block_residual_" + _elem(x.dtype, "block_residual")
+    _require_cuda(x, "x")
+    _require_cuda(r, "r", x.dtype)
+    B, S, h = x.shape
+    if tuple(r.shape) != (B, S - s_t, h):
+        raise _lib.DkHipError(f"r shape {tuple(r.shape)} != {(B, S - s_t, h)}")
+    _lib.check(getattr(lib, name)(x.data_ptr() + s_t * h * x.element_size(), h, S - s_t, S, r.data_ptr(), B * (S - s_t), h, int(bool(reuse)),
+                                  _stream()), name)
+    return x if reuse else r
+
+
 def qk_norm_rope_(qkv: Tensor, H: int, D: int, qw: Optional[Tensor], kw: Optional[Tensor],
                   rope: Optional[Tensor], pos_off: int = 0, eps: float = 1e-6) -> Tensor:
     """In place on qkv [B, S, 3*H*D] (bf16, or float16 with float16 weights); rope: f32 [S_pos, D/2, 2]."""

@@ -347,11 +347,18 @@ class DiffusionPipeline:
         denoise: float = 1.0,
         *,
         mask_path=None,
+        block_cache=None,
     ):
         """mlx/__init__.py:253-292.  ``seed`` may be a list: one image per seed is denoised in a
         single batched step loop (data-parallel sharding hands each rank a list).
         ``mask_path`` (inpainting; a path, a PIL image or an array as ``read_mask`` takes them, or a list with one per seed): repaint where the
-        mask is 255, keep ``image_path``'s content where it is 0 -- kept latent cells equal the encoded image bit for bit."""
+        mask is 255, keep ``image_path``'s content where it is 0 -- kept latent cells equal the encoded image bit for bit.
+        ``block_cache`` (first-block cache; a float threshold >= 0 or a policy object with ``decide(step, n_steps, rel)``, see
+        ``sampler.BlockCachePolicy``): every step runs block 0, and where its effect on the image rows moved by less than the threshold,
+        relative to the last computed step, the cached effect of the other blocks is reused instead of running them.  One decision per launch:
+        the images of a seed list and the two CFG rows share it through the maximum of their changes, so a cached batch equals the single
+        runs only where their decisions coincide.  What was decided is kept in ``self.last_block_cache`` (threshold, computed and skipped
+        steps, rel per step; None without the option).  No threshold has been validated on a real checkpoint here."""
         if mask_path is not None and image_path is None:
             raise ValueError("mask_path needs image_path: the mask says which part of that image to keep")
         seed = int(time.time()) if seed is None else seed
@@ -380,9 +387,13 @@ class DiffusionPipeline:
             extra_args["mask"] = ops.mask_to_latent(torch.from_numpy(masks).to(self.device), 8)
             extra_args["x_orig"] = x_orig
             extra_args["noise"] = torch.from_numpy(np.ascontiguousarray(noise, dtype=np.float32)).to(self.device)
+        if block_cache is not None:
+            extra_args["block_cache"] = block_cache
         noise_scaled = self.sampler.noise_scaling(np.float32(sigmas[0]), noise, x_T, self.max_denoise(sigmas))
         x0 = torch.from_numpy(np.ascontiguousarray(noise_scaled, dtype=np.float32)).to(self.device)
-        latent, iter_time = sample_euler(CFGDenoiser(self), x0, sigmas, extra_args=extra_args)
+        denoiser = CFGDenoiser(self)
+        latent, iter_time = sample_euler(denoiser, x0, sigmas, extra_args=extra_args)
+        self.last_block_cache = denoiser.block_cache_record
         latent = self.latent_format.process_out(latent)
         return latent, iter_time
 
@@ -400,9 +411,11 @@ class DiffusionPipeline:
         *,
         mask_path=None,
         composite: bool = True,
+        block_cache=None,
     ):
         """mlx/__init__.py:294-534: returns (PIL.Image, log).  ``mask_path``: inpainting, see ``denoise_latents``; with ``composite`` the pixels
-        the mask keeps are pasted back from the input image after decoding (the VAE round trip alone does not reproduce them)."""
+        the mask keeps are pasted back from the input image after decoding (the VAE round trip alone does not reproduce them).
+        ``block_cache``: first-block cache, see ``denoise_latents``; its record goes to ``log["denoising"]["block_cache"]``."""
         if mask_path is not None and image_path is None:
             raise ValueError("mask_path needs image_path: the mask says which part of that image to keep")
         assert latent_size[0] % 2 == 0, f"Height must be divisible by 16 ({latent_size[0]*8}/16={latent_size[0]/2})"
@@ -434,12 +447,14 @@ class DiffusionPipeline:
         log["denoising"]["pre"] = mem()
         latents, iter_time = self.denoise_latents(
             conditioning, pooled_conditioning, num_steps=num_steps, cfg_weight=cfg_weight,
-            latent_size=latent_size, seed=seed, image_path=image_path, denoise=denoise, mask_path=mask_path)
+            latent_size=latent_size, seed=seed, image_path=image_path, denoise=denoise, mask_path=mask_path, block_cache=block_cache)
         torch.cuda.synchronize(dev)
         log["denoising"]["post"] = mem()
         log["peak_memory"] = max(log["peak_memory"], log["denoising"]["post"]["peak_memory"])
         log["denoising"]["time"] = round(time.time() - t0, 3)
         log["denoising"]["iter_time"] = iter_time
+        if block_cache is not None:
+            log["denoising"]["block_cache"] = self.last_block_cache
 
         torch.cuda.reset_peak_memory_stats(dev)
         t0 = time.time()
@@ -604,6 +619,7 @@ class CFGDenoiser:
     def __init__(self, model: DiffusionPipeline):
         self.model = model
         self._timesteps: List[float] = []
+        self.block_cache_record = None  # what sample_euler decided per step under extra_args["block_cache"]
 
     def cache_modulation_params(self, pooled_text_embeddings, timesteps):
         self._timesteps = [float(t) for t in timesteps]
@@ -683,7 +699,10 @@ def sample_euler(model: CFGDenoiser, x: Tensor, sigmas, extra_args=None):
     mx.eval(x)) provides iter_time.
     Inpainting: ``extra_args["mask"]`` (f32 [1 or n_img, h, w], 1 = repaint) together with ``"x_orig"`` and ``"noise"`` (f32 like x: the
     encoded image after process_in and the draw of the start state) makes every step end in the blend of dk_euler_cfg_step_masked --
-    still one launch per step."""
+    still one launch per step.
+    First-block cache: ``extra_args["block_cache"]`` (a float threshold or a policy object, ``sampler.BlockCachePolicy``) turns a step into
+    the engine's head, the read of its probe (the step's decision needs it on the host: a synchronisation), and the tail the policy chose;
+    the record of the decisions goes to ``model.block_cache_record``."""
     extra_args = {} if extra_args is None else dict(extra_args)
     pipe = model.model
     mm = pipe.mmdit
@@ -705,6 +724,11 @@ def sample_euler(model: CFGDenoiser, x: Tensor, sigmas, extra_args=None):
 
     # model timesteps are sigma*1000 rounded to the reference pipeline's activation dtype (quirk Q1): fp16 for SD3, bf16 for FLUX
     timesteps = _round_to_dtype(pipe.sampler.timestep(sigmas), pipe.timestep_dtype)
+    policy = extra_args.get("block_cache")
+    if policy is not None and not hasattr(policy, "decide"):
+        from .sampler import BlockCachePolicy
+        policy = BlockCachePolicy(policy)
+    mm.enable_block_cache(policy is not None)  # (off: the engine's workspace and launches are what they are without the feature)
     mm.prepare(rows, x.shape[1:3], conditioning.shape[1], len(timesteps))
     model.cache_modulation_params(pooled, timesteps)
     mm.cache_context(conditioning)  # context_embedder is step-invariant (the reference recomputes it in every call, mmdit.py:195)
@@ -721,6 +745,27 @@ def sample_euler(model: CFGDenoiser, x: Tensor, sigmas, extra_args=None):
     tok = mm.patchify(x, dup=2 if cfg_on else 1)
     out = torch.empty_like(tok)
     iter_time = []
+    if policy is not None:
+        from .sampler import block_cache_rel
+        n_steps = len(sigmas) - 1
+        record = {"threshold": getattr(policy, "threshold", None), "computed": [], "skipped": [], "rel": []}
+        for i in range(n_steps):
+            t0 = time.perf_counter()
+            rel = block_cache_rel(mm.forward_head(tok, None, i).cpu().tolist())  # (.cpu(): the step's synchronisation point)
+            skip = bool(policy.decide(i, n_steps, rel))
+            mm.forward_tail(i, skip, tokens_out=out)
+            record["skipped" if skip else "computed"].append(i)
+            record["rel"].append(rel)
+            if mask is None:
+                _euler(pipe, x, out, tok, cfg_on, float(sigmas[i]), float(sigmas[i + 1]), cfg_weight)
+            else:
+                ops.euler_cfg_step_masked(x, out, tok, n_img, cfg_on, pcfg.patch_size, int(pcfg.patchify_via_reshape), float(sigmas[i]),
+                                          float(sigmas[i + 1]), cfg_weight, x_orig, noise, mask)
+            torch.cuda.synchronize(pipe.device)
+            iter_time.append(round(time.perf_counter() - t0, 3))
+        model.block_cache_record = record
+        model.clear_cache()
+        return x, iter_time
     for i in range(len(sigmas) - 1):
         t0 = time.perf_counter()
         mm.forward_tokens(tok, None, i, tokens_out=out)

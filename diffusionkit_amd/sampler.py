@@ -88,3 +88,53 @@ def max_denoise(sampler, sigmas) -> bool:
     max_sigma = float(sampler.sigma_max)
     sigma = float(sigmas[0])
     return math.isclose(max_sigma, sigma, rel_tol=1e-05) or sigma > max_sigma
+
+
+# ---- first-block cache: which steps compute and which reuse (host policy; no reference counterpart) -------------------------
+def block_cache_rel(probe) -> float:
+    """``probe``: (num, den) per batch row as ``MMDiTEngine.forward_head`` returns them, on the host -> the relative change of block 0's
+    effect on the image rows, the maximum over the batch rows of num / den.  den == 0 (no computed step to compare with) gives inf."""
+    rel = 0.0
+    for num, den in probe:
+        num, den = float(num), float(den)
+        r = num / den if den > 0.0 else math.inf
+        rel = r if (r > rel or r != r) else rel  # (a NaN row is kept: it compares False with every threshold, the step computes)
+    return rel
+
+
+class BlockCachePolicy:
+    """Skip a step iff ``rel < threshold``; the first and the last step always compute, and after ``max_consecutive_skips`` skipped
+    steps in a row (None: no cap) the next one computes.  threshold 0 never skips, inf skips every step in between (``rel`` = inf,
+    the answer before any computed step, is never below a threshold).  ``decide`` is called once per step, in order."""
+
+    def __init__(self, threshold: float, max_consecutive_skips=None):
+        threshold = float(threshold)
+        if not threshold >= 0.0:
+            raise ValueError(f"block cache threshold must be a float >= 0, got {threshold}")
+        if max_consecutive_skips is not None and int(max_consecutive_skips) < 0:
+            raise ValueError("max_consecutive_skips must be None or >= 0")
+        self.threshold = threshold
+        self.max_consecutive_skips = None if max_consecutive_skips is None else int(max_consecutive_skips)
+        self._run = 0
+
+    def decide(self, step: int, n_steps: int, rel: float) -> bool:
+        """True: reuse the cached blocks in this step."""
+        if step == 0:
+            self._run = 0
+        capped = self.max_consecutive_skips is not None and self._run >= self.max_consecutive_skips
+        skip = 0 < step < n_steps - 1 and not capped and rel < self.threshold
+        self._run = self._run + 1 if skip else 0
+        return skip
+
+
+class FixedSchedule:
+    """The same interface with the decisions written down: skip exactly the steps in ``skip`` (never the first or the last one),
+    whatever ``rel`` says -- for runs that must take the same decisions regardless of rounding."""
+
+    threshold = None
+
+    def __init__(self, skip):
+        self.skip = frozenset(int(s) for s in skip)
+
+    def decide(self, step: int, n_steps: int, rel: float) -> bool:
+        return 0 < step < n_steps - 1 and step in self.skip

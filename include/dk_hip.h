@@ -555,8 +555,51 @@ int dk_mmdit_run_blocks(dk_mmdit* m, const void* x_in, void* x_out, int32_t step
                         int32_t n_blocks, void* stream);
 /* read-only view of an internal buffer for parity taps: 0 = joint residual stream [B,S,h],
  * 1 = modulation table [n*B, rows*h], 2 = base of the engine's GEMM K-split workspace (dk_gemm_workspace_bytes() bytes:
- * the fp32 slabs, then the 4096-byte flag region, which is zero between launches) */
+ * the fp32 slabs, then the 4096-byte flag region, which is zero between launches); with the first-block cache on, image rows only
+ * [B * S_i, h]: 3 = R, 4 = D_ref, 5 = D_cur (the probe's output, between a head and its tail; a compute tail makes it D_ref); NULL with the cache off */
 const void* dk_mmdit_debug_buffer(const dk_mmdit* m, int32_t which);
+
+/* ---- first-block cache (opt-in; no reference counterpart) -------------------------------------------------------------------
+ * A step is split into a head -- embedders, block 0, a probe of what block 0 did to the image rows -- and a tail that either
+ * computes blocks 1 .. L-1 or reuses their cached effect.  All of it acts on the image rows of the joint stream X [B, S, h], in
+ * the engine's element type E, fp32 arithmetic with one round-to-nearest-even to E per stored value.  With X0 the stream behind
+ * the embedders, X1 behind block 0 and X_L behind the last block:
+ *   D_cur = round_E(X1 - X0);  num[b] = sum |D_cur - D_ref|,  den[b] = sum |D_ref|  over the S_i * h image elements of batch row b,
+ *   with D_ref the D_cur of the last COMPUTED step since the cache was reset.  The sums are fp32, built without atomics in a
+ *   fixed order (per lane, per wave, per batch row): the same bits on every run and every CU count.
+ *   compute tail: blocks 1 .. L-1 and the final layer as in dk_mmdit_forward; R = round_E(X_L - X1); D_ref <- D_cur.
+ *   reuse tail:   image rows X <- round_E(X1 + R), text rows as block 0 left them, then the final layer; D_ref and R stay.
+ * A model whose block 0 is its only block is accepted: the compute tail's block range is empty and R is all +0.
+ *
+ * dk_mmdit_set_block_cache: call before dk_mmdit_prepare (a prepared engine must be prepared again).  on != 0 adds three image-row
+ * buffers [B * S_i, h] and the probe's per-row partial sums behind everything else in the workspace; with 0 (the default)
+ * dk_mmdit_workspace_bytes, the carve and every launch of dk_mmdit_forward are what they are without the feature.
+ * dk_mmdit_forward keeps working on a cache-enabled engine: it drops a pending head and leaves R / D_ref alone.
+ * dk_mmdit_prepare, dk_mmdit_cache_modulation_params and dk_mmdit_reset_block_cache invalidate the cache (and a pending head).
+ * None of these entries synchronises: probe_out is valid in stream order, the caller reads it. */
+int dk_mmdit_set_block_cache(dk_mmdit* m, int32_t on);
+int dk_mmdit_reset_block_cache(dk_mmdit* m);
+/* Head of step `step_index`: dk_mmdit_forward's embedder launches, block 0 and the probe.  probe_out: device float [batch][2] =
+ * (num, den) per batch row; before any computed step den is 0 (and num = sum |D_cur|).  Records a pending head for step_index. */
+int dk_mmdit_forward_head(dk_mmdit* m, const void* tokens_in, const void* text, int32_t step_index, float* probe_out, void* stream);
+/* Tail of the pending head, which must be of the same step_index; reuse = 1 additionally needs a valid cache (a computed step since
+ * the last reset).  Either violation is an error that names the rule, never a launch. */
+int dk_mmdit_forward_tail(dk_mmdit* m, int32_t step_index, int32_t reuse, void* tokens_out, void* stream);
+/* The two kernels behind it, stand-alone.  x: first image row of a joint stream; logical row m of M is physical row
+ * (m / x_seg_len) * x_seg_stride + m % x_seg_len at ldx elements per row (the engine: x = X + S_t * h, x_seg_len = S_i, x_seg_stride = S).
+ * h % 8 == 0, h <= 4096; ldx % 8 == 0; 16-byte aligned pointers.
+ * dk_block_probe_*: d [M, h] dense holds X0's rows on entry and D_cur = round_E(x - d) on return; d_ref [M, h] dense or NULL (read as
+ * zeros: den = 0); row_partials: float [M][2] scratch, (num, den) per row; probe: float [M / rows_per_batch][2].
+ * dk_block_residual_*: reuse == 0: r [M, h] dense holds X1's rows on entry and R = round_E(x - r) on return (x is read only);
+ * reuse != 0: x = round_E(x + r) (r is read only). */
+int dk_block_probe_bf16(const void* x, int32_t ldx, int32_t x_seg_len, int32_t x_seg_stride, void* d, const void* d_ref,
+                        float* row_partials, float* probe, int32_t M, int32_t h, int32_t rows_per_batch, void* stream);
+int dk_block_probe_f16(const void* x, int32_t ldx, int32_t x_seg_len, int32_t x_seg_stride, void* d, const void* d_ref,
+                       float* row_partials, float* probe, int32_t M, int32_t h, int32_t rows_per_batch, void* stream);
+int dk_block_residual_bf16(void* x, int32_t ldx, int32_t x_seg_len, int32_t x_seg_stride, void* r, int32_t M, int32_t h, int32_t reuse,
+                           void* stream);
+int dk_block_residual_f16(void* x, int32_t ldx, int32_t x_seg_len, int32_t x_seg_stride, void* r, int32_t M, int32_t h, int32_t reuse,
+                          void* stream);
 
 typedef struct dk_vae_config {
   int32_t in_channels, out_channels, block_out_channels[4], n_blocks, layers_per_block, resnet_groups;
