@@ -133,6 +133,9 @@ class dk_attention_plan_t(C.Structure):  # (o8_split is read by dk_attention_pla
     _fields_ = [(n, C.c_int32) for n in ("kernel", "qfuse", "blocks", "whole", "split", "jobs", "merge", "quantize", "launches", "n_cu", "o8_split")]
 
 
+# dk_lms_cfg_step*: x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, cfg_weight, hist, the five coefficients,
+# sigma_next, reads_h, writes_h (then the mask operands of the masked entries, then the stream)
+_LMS_ARGS = [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _i32]
 SIGNATURES = {
     "dk_abi_version": (_i32, []),
     "dk_last_error": (C.c_char_p, []),
@@ -188,6 +191,11 @@ SIGNATURES = {
     "dk_euler_cfg_step_masked": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _vp, _vp, _vp, _i32, _vp]),
     "dk_euler_cfg_step_masked_f16": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _vp, _vp, _vp, _i32,
                                             _vp]),
+    # second-order samplers: the step as a coefficient row over a history buffer, plain and masked
+    "dk_lms_cfg_step": (_i32, _LMS_ARGS + [_vp]),
+    "dk_lms_cfg_step_f16": (_i32, _LMS_ARGS + [_vp]),
+    "dk_lms_cfg_step_masked": (_i32, _LMS_ARGS + [_vp, _vp, _vp, _i32, _vp]),
+    "dk_lms_cfg_step_masked_f16": (_i32, _LMS_ARGS + [_vp, _vp, _vp, _i32, _vp]),
     "dk_mask_to_latent_f32": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "dk_image_composite_u8": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "dk_affine_f32": (_i32, [_vp, _vp, _i64, _f32, _f32, _vp]),

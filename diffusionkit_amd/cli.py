@@ -60,6 +60,10 @@ def build_parser(model_versions: Sequence[str]) -> argparse.ArgumentParser:
                    help="First-block cache: skip the blocks behind block 0 in steps where block 0's effect moved by less than THRESHOLD "
                         "(a float >= 0, relative to the last computed step). Published implementations use about 0.1 for FLUX; no value "
                         "has been validated here on a real checkpoint.")
+    p.add_argument("--sampler", choices=("euler", "heun", "ab2"), default=None,
+                   help="Integrator of the step loop. euler (default): first order, one model evaluation per step. heun: second order, two "
+                        "evaluations per step but the last (not together with --block-cache). ab2: second order, one evaluation per step. "
+                        "The orders are checked on an analytic problem, not on a trained checkpoint.")
     p.add_argument("--local-ckpt", default=None, type=str, help="Path to the local mmdit checkpoint.")
     p.add_argument("--ckpt", action="append", default=[], metavar="KEY=PATH",
                    help="Further local checkpoint parts (vae_decoder, vae_encoder, clip_l, clip_g, t5, t5_tokenizer, "
@@ -126,6 +130,11 @@ def resolve(args) -> dict:
         if not args.block_cache >= 0.0:
             raise ValueError("Block cache threshold must be a float >= 0")
         r["block_cache"] = args.block_cache
+    if getattr(args, "sampler", None) is not None:  # (a key only when the flag is given)
+        if args.sampler == "heun" and "block_cache" in r:
+            raise ValueError("--sampler heun cannot run together with --block-cache (two model evaluations per step have no cache policy yet); "
+                             "use --sampler ab2")
+        r["sampler"] = args.sampler
     return r
 
 
@@ -159,7 +168,7 @@ def main(argv: Optional[Sequence[str]] = None, pipeline_overrides: Optional[dict
     image, log = sd.generate_image(args.prompt, cfg_weight=r["cfg"], num_steps=args.steps, seed=args.seed,
                                    negative_text=args.negative_prompt, latent_size=latent_size, image_path=args.image_path,
                                    denoise=args.denoise, verbose=args.verbose, mask_path=r.get("mask_path"),
-                                   composite=r.get("composite", True), block_cache=r.get("block_cache"))
+                                   composite=r.get("composite", True), block_cache=r.get("block_cache"), sampler=r.get("sampler"))
     if log["text_encoding"].get("synthetic"):
         logger.warning("no text-encoder checkpoints were named (--ckpt clip_l=... t5=...): the conditioning is synthetic")
     image.save(args.output_path)

@@ -448,6 +448,51 @@ extern "C" int dk_euler_cfg_step_masked_f16(float* x, const void* model_out, int
                                cfg_weight, x_orig, noise, mask, mask_per_image, stream);
 }
 
+// second-order samplers: the step as a coefficient row (x' = cx x + cd d + ch H, H' = hx x + hd d); masked = the inpainting blend behind it
+static int lms_cfg_step(int dtype, bool masked, float* x, const void* model_out, int ld_out, void* tokens, int n_img, int cfg_on, int Hl, int Wl,
+                        int C, int p, int reshape_order, float sigma, float cfg_weight, float* hist, float cx, float cd, float ch, float hx,
+                        float hd, float sigma_next, int reads_h, int writes_h, const float* x_orig, const float* noise, const float* mask,
+                        int mask_per_image, void* stream) {
+  DK_REQUIRE(sigma != 0.0f, "sigma must be non-zero");
+  DK_REQUIRE(p > 0 && Hl % p == 0 && Wl % p == 0, "latent size must be divisible by the patch size");
+  DK_REQUIRE(x && model_out && tokens, "null argument");
+  DK_REQUIRE(n_img > 0, "n_img must be positive");
+  DK_REQUIRE(hist || !(reads_h || writes_h), "hist is null while the row reads or writes the history");
+  const float coef[5] = {cx, cd, ch, hx, hd};
+  for (float v : coef) DK_REQUIRE(std::isfinite(v), "the coefficients of the row must be finite");
+  DK_REQUIRE(std::isfinite(sigma) && std::isfinite(sigma_next), "sigma and sigma_next must be finite");
+  if (masked) DK_REQUIRE(x_orig && noise && mask, "null argument");
+  return DK_EL(dtype, dk_launch_lms_step)(x, (const bf16_t*)model_out, ld_out, (bf16_t*)tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma,
+                                          sigma_next, cfg_weight, hist, coef, reads_h != 0, writes_h != 0, masked ? x_orig : nullptr,
+                                          masked ? noise : nullptr, masked ? mask : nullptr, mask_per_image != 0, S_(stream));
+}
+extern "C" int dk_lms_cfg_step(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on, int32_t Hl, int32_t Wl,
+                               int32_t C, int32_t p, int32_t reshape_order, float sigma, float cfg_weight, float* hist, float cx, float cd,
+                               float ch, float hx, float hd, float sigma_next, int32_t reads_h, int32_t writes_h, void* stream) {
+  return lms_cfg_step(DK_DTYPE_BF16, false, x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, cfg_weight, hist, cx, cd,
+                      ch, hx, hd, sigma_next, reads_h, writes_h, nullptr, nullptr, nullptr, 0, stream);
+}
+extern "C" int dk_lms_cfg_step_f16(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on, int32_t Hl,
+                                   int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma, float cfg_weight, float* hist, float cx,
+                                   float cd, float ch, float hx, float hd, float sigma_next, int32_t reads_h, int32_t writes_h, void* stream) {
+  return lms_cfg_step(DK_DTYPE_F16, false, x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, cfg_weight, hist, cx, cd,
+                      ch, hx, hd, sigma_next, reads_h, writes_h, nullptr, nullptr, nullptr, 0, stream);
+}
+extern "C" int dk_lms_cfg_step_masked(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on, int32_t Hl,
+                                      int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma, float cfg_weight, float* hist,
+                                      float cx, float cd, float ch, float hx, float hd, float sigma_next, int32_t reads_h, int32_t writes_h,
+                                      const float* x_orig, const float* noise, const float* mask, int32_t mask_per_image, void* stream) {
+  return lms_cfg_step(DK_DTYPE_BF16, true, x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, cfg_weight, hist, cx, cd,
+                      ch, hx, hd, sigma_next, reads_h, writes_h, x_orig, noise, mask, mask_per_image, stream);
+}
+extern "C" int dk_lms_cfg_step_masked_f16(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on, int32_t Hl,
+                                          int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma, float cfg_weight, float* hist,
+                                          float cx, float cd, float ch, float hx, float hd, float sigma_next, int32_t reads_h, int32_t writes_h,
+                                          const float* x_orig, const float* noise, const float* mask, int32_t mask_per_image, void* stream) {
+  return lms_cfg_step(DK_DTYPE_F16, true, x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, cfg_weight, hist, cx, cd,
+                      ch, hx, hd, sigma_next, reads_h, writes_h, x_orig, noise, mask, mask_per_image, stream);
+}
+
 extern "C" int dk_mask_to_latent_f32(const uint8_t* mask, float* out, int32_t n_mask, int32_t H, int32_t W, int32_t f, void* stream) {
   DK_REQUIRE(mask && out, "null argument");
   DK_REQUIRE(n_mask > 0, "n_mask must be positive");

@@ -38,6 +38,12 @@ int dk_launch_euler_step_masked(float* x, const bf16_t* model_out, int ld_out, b
                                 int Hl, int Wl, int C, int p, int reshape_order, float sigma, float sigma_next,
                                 float cfg_weight, const float* x_orig, const float* noise, const float* mask,
                                 int mask_per_image, hipStream_t stream);
+// the same tail with the update as a coefficient row over the fp32 history buffer hist (second-order samplers): d = (x - den) / sigma,
+// x' = coef[0] * x + coef[1] * d + coef[2] * hist (hist read only under reads_h), hist' = coef[3] * x + coef[4] * d (written only under
+// writes_h); mask non-null: followed by the inpainting blend at sigma_next
+int dk_launch_lms_step(float* x, const bf16_t* model_out, int ld_out, bf16_t* tok, int n_img, int cfg_on, int Hl, int Wl, int C, int p,
+                       int reshape_order, float sigma, float sigma_next, float cfg_weight, float* hist, const float* coef, int reads_h,
+                       int writes_h, const float* x_orig, const float* noise, const float* mask, int mask_per_image, hipStream_t stream);
 // first-block cache (include/dk_hip.h): d = round(x - d) over M rows of x through the row map, (num, den) = (sum |d - d_ref|, sum |d_ref|) per
 // row into row_partials [M][2], then per rows_per_batch rows in a fixed order into probe [M / rows_per_batch][2]; d_ref null: read as zeros
 int dk_launch_block_probe(const bf16_t* x, int ldx, int x_seg_len, int x_seg_stride, bf16_t* d, const bf16_t* d_ref, float* row_partials,

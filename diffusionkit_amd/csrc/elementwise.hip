@@ -502,6 +502,82 @@ int dk_launch_euler_step_masked(float* x, const bf16_t* model_out, int ld_out, b
 }
 
 // ---------------------------------------------------------------------------------------------
+// Second-order samplers (Heun, Adams-Bashforth 2; no reference counterpart): the step-loop tail above with the update written as a
+// coefficient row over one fp32 history buffer H shaped like the latent,
+//   d = (x - den) / sigma,    x' = cx * x + cd * d + ch * H,    H' = hx * x + hd * d,
+// den formed exactly as dk_euler_step_kernel forms it (same round_act, CFG combine, addressing and rounding points).  The host writes
+// the rows (sampler.step_plan); sigma is the sigma the model was evaluated at, sigma_next the one the row's result lives at (only the
+// blend reads it).  reads_h == 0: H is not read (the caller never initialises it) and ch is ignored; writes_h == 0: H is not written.
+// A first-order row -- reads_h == 0 and cx == 1 -- is evaluated as the Euler expression itself, x + d * cd: with cd = sigma_next - sigma
+// (the fp32 difference dk_euler_step_kernel takes on the device) it is that kernel's statement on that kernel's operands, so x and the
+// tokens are its bits whether or not the compiler contracts the product into the sum; cx * x + d * cd would depend on which of the two
+// products a contraction swallows.  H' is taken from x BEFORE the update.
+// MASKED: dk_euler_step_kernel's two-product blend behind the update, known at sigma_next, with the same exact ends.
+// ---------------------------------------------------------------------------------------------
+struct LmsRow {
+  float cx, cd, ch, hx, hd;
+  int reads_h, writes_h;
+};
+template <bool MASKED>
+__global__ void dk_lms_step_kernel(float* x, const bf16_t* model_out, int ld_out, bf16_t* tok, int n_img, int cfg_on, int Hl, int Wl,
+                                   int C, int p, int reshape_order, float sigma, float sigma_next, float cfg_weight, float* hist,
+                                   LmsRow row, const float* x_orig, const float* noise, const float* mask, int mask_per_image) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long per_img = (long)Hl * Wl * C;
+  if (i >= per_img * n_img) return;
+  const int img = (int)(i / per_img);
+  long r = i % per_img;
+  const int c = (int)(r % C);
+  r /= C;
+  const int xx = (int)(r % Wl), yy = (int)(r / Wl);
+  const int gw = Wl / p, S_i = (Hl / p) * gw, F = p * p * C;
+  const int t = (yy / p) * gw + (xx / p);
+  const int f = patch_feature(c, yy % p, xx % p, C, p, reshape_order);
+  const float xv = x[i];
+  const float xb = round_act(xv);  // the value the denoiser saw
+  const float o_text = to_f32(model_out[((size_t)img * S_i + t) * ld_out + f]);
+  float den = xb - o_text * sigma;
+  if (cfg_on) {
+    const float o_neg = to_f32(model_out[((size_t)(n_img + img) * S_i + t) * ld_out + f]);
+    const float den_neg = xb - o_neg * sigma;
+    den = den_neg + cfg_weight * (den - den_neg);
+  }
+  const float d = (xv - den) / sigma;
+  float xn;
+  if (row.reads_h)
+    xn = row.cx * xv + row.cd * d + row.ch * hist[i];
+  else if (row.cx == 1.0f)
+    xn = xv + d * row.cd;
+  else
+    xn = row.cx * xv + d * row.cd;
+  if (row.writes_h) hist[i] = row.hx * xv + row.hd * d;
+  if constexpr (MASKED) {
+    const float m = mask[(mask_per_image ? (long)img * Hl * Wl : 0) + (long)yy * Wl + xx];
+    const float known = sigma_next * noise[i] + (1.0f - sigma_next) * x_orig[i];
+    xn = m * xn + (1.0f - m) * known;
+  }
+  x[i] = xn;
+  const bf16_t nb = from_f32(xn);
+  tok[((size_t)img * S_i + t) * F + f] = nb;
+  if (cfg_on) tok[((size_t)(n_img + img) * S_i + t) * F + f] = nb;
+}
+int dk_launch_lms_step(float* x, const bf16_t* model_out, int ld_out, bf16_t* tok, int n_img, int cfg_on, int Hl, int Wl, int C, int p,
+                       int reshape_order, float sigma, float sigma_next, float cfg_weight, float* hist, const float* coef, int reads_h,
+                       int writes_h, const float* x_orig, const float* noise, const float* mask, int mask_per_image, hipStream_t stream) {
+  const long n = (long)n_img * Hl * Wl * C;
+  const LmsRow row = {coef[0], coef[1], coef[2], coef[3], coef[4], reads_h, writes_h};
+  const dim3 grid((unsigned)((n + 255) / 256));
+  if (mask)
+    hipLaunchKernelGGL(dk_lms_step_kernel<true>, grid, dim3(256), 0, stream, x, model_out, ld_out, tok, n_img, cfg_on, Hl, Wl, C, p,
+                       reshape_order, sigma, sigma_next, cfg_weight, hist, row, x_orig, noise, mask, mask_per_image);
+  else
+    hipLaunchKernelGGL(dk_lms_step_kernel<false>, grid, dim3(256), 0, stream, x, model_out, ld_out, tok, n_img, cfg_on, Hl, Wl, C, p,
+                       reshape_order, sigma, sigma_next, cfg_weight, hist, row, nullptr, nullptr, nullptr, 0);
+  DK_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
 // First-block cache (include/dk_hip.h; no reference counterpart): what block 0 did to the image rows of the joint stream, compared
 // with what it did in the last computed step, and the cached effect of the blocks behind it.  fp32 arithmetic, one rounding to the
 // element type per stored value.

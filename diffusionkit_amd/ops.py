@@ -444,6 +444,49 @@ def euler_cfg_step_masked(x: Tensor, model_out: Tensor, tokens: Tensor, n_img: i
                                           noise.data_ptr(), mask.data_ptr(), per_image, _stream()), name)
 
 
+def _lms_args(x: Tensor, model_out: Tensor, tokens: Tensor, n_img: int, cfg_on: bool, p: int, reshape_order: int, sigma: float, sigma_next: float,
+              cfg_weight: float, hist: Optional[Tensor], coef, reads_h: bool, writes_h: bool):
+    _require_cuda(x, "x", torch.float32)
+    _require_cuda(model_out, "model_out")
+    _require_cuda(tokens, "tokens", model_out.dtype)
+    if hist is not None:
+        _require_cuda(hist, "hist", torch.float32)
+        if hist.shape != x.shape:
+            raise _lib.DkHipError(f"hist {tuple(hist.shape)} must have the latent's shape {tuple(x.shape)}")
+    cx, cd, ch, hx, hd = (float(v) for v in coef)
+    _, hl, wl, c = x.shape
+    return (x.data_ptr(), model_out.data_ptr(), model_out.shape[-1], tokens.data_ptr(), n_img, int(cfg_on), hl, wl, c, p, reshape_order, float(sigma),
+            float(cfg_weight), _ptr(hist), cx, cd, ch, hx, hd, float(sigma_next), int(bool(reads_h)), int(bool(writes_h)))
+
+
+def lms_cfg_step(x: Tensor, model_out: Tensor, tokens: Tensor, n_img: int, cfg_on: bool, p: int, reshape_order: int, sigma: float,
+                 sigma_next: float, cfg_weight: float, hist: Optional[Tensor], coef, reads_h: bool, writes_h: bool) -> None:
+    """dk_lms_cfg_step / _f16 by the dtype of ``model_out``: ``euler_cfg_step`` with the update as a coefficient row, ``coef`` = (cx, cd, ch, hx, hd):
+    d = (x - den) / sigma, x = cx x + cd d + ch hist, hist = hx x + hd d.  ``hist``: f32 like x, read only under ``reads_h``, written only under
+    ``writes_h`` (None when neither); the rows come from ``sampler.step_plan``."""
+    name = "dk_lms_cfg_step" + ("" if _elem(model_out.dtype, "lms_cfg_step") == "bf16" else "_f16")
+    args = _lms_args(x, model_out, tokens, n_img, cfg_on, p, reshape_order, sigma, sigma_next, cfg_weight, hist, coef, reads_h, writes_h)
+    _lib.check(getattr(_lib.load(), name)(*args, _stream()), name)
+
+
+def lms_cfg_step_masked(x: Tensor, model_out: Tensor, tokens: Tensor, n_img: int, cfg_on: bool, p: int, reshape_order: int, sigma: float,
+                        sigma_next: float, cfg_weight: float, hist: Optional[Tensor], coef, reads_h: bool, writes_h: bool, x_orig: Tensor,
+                        noise: Tensor, mask: Tensor) -> None:
+    """dk_lms_cfg_step_masked / _f16: ``lms_cfg_step``, then the blend of ``euler_cfg_step_masked`` with the known region re-noised to
+    ``sigma_next``, in the same launch."""
+    name = "dk_lms_cfg_step_masked" + ("" if _elem(model_out.dtype, "lms_cfg_step_masked") == "bf16" else "_f16")
+    args = _lms_args(x, model_out, tokens, n_img, cfg_on, p, reshape_order, sigma, sigma_next, cfg_weight, hist, coef, reads_h, writes_h)
+    for n, t in (("x_orig", x_orig), ("noise", noise), ("mask", mask)):
+        _require_cuda(t, n, torch.float32)
+    _, hl, wl, _ = x.shape
+    if x_orig.shape != x.shape or noise.shape != x.shape:
+        raise _lib.DkHipError(f"x_orig {tuple(x_orig.shape)} and noise {tuple(noise.shape)} must have the latent's shape {tuple(x.shape)}")
+    if tuple(mask.shape[-2:]) != (hl, wl) or mask.numel() not in (hl * wl, n_img * hl * wl):
+        raise _lib.DkHipError(f"lms_cfg_step_masked: mask {tuple(mask.shape)} is neither [{hl}, {wl}] (shared) nor [{n_img}, {hl}, {wl}] (per image)")
+    per_image = _mask_per_image(mask.numel(), hl * wl, n_img, "lms_cfg_step_masked")
+    _lib.check(getattr(_lib.load(), name)(*args, x_orig.data_ptr(), noise.data_ptr(), mask.data_ptr(), per_image, _stream()), name)
+
+
 def mask_to_latent(mask: Tensor, factor: int = 8) -> Tensor:
     """dk_mask_to_latent_f32: uint8 [n_mask, H, W] (or [H, W]) -> f32 [n_mask, H / factor, W / factor], box sum / (factor^2 * 255)."""
     _require_cuda(mask, "mask", torch.uint8)

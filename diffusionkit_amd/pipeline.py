@@ -13,6 +13,9 @@ Inpainting (``mask_path=``, keyword-only, no reference counterpart) is latent bl
 step's own launch (dk_euler_cfg_step_masked), and ``generate_image`` pastes the kept pixels of the input back over the decoded image
 (``composite=``).  Kept latent cells come out as the encoded image bit for bit, kept pixels as the input's bytes.
 
+Samplers (``sampler=``, keyword-only, no reference counterpart): "euler" (default: the reference's loop, ``sample_euler``), "heun" and "ab2" run
+``sample_steps`` over the rows of ``sampler.step_plan`` -- one launch of dk_lms_cfg_step (or its masked form) behind every model evaluation.
+
 All arithmetic runs in libdk_hip.so on the current HIP stream; numpy is used exactly where the
 reference uses it (the seeded noise draw, __init__.py:553-557) and for O(num_steps) schedule
 scalars.
@@ -23,7 +26,7 @@ import hashlib
 import logging
 import time
 from dataclasses import replace
-from typing import Callable, List, Optional, Sequence, Tuple, Union
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -31,7 +34,7 @@ import torch
 from . import _lib
 from .config import (MMDIT_CKPT, MODEL_CONFIG, T5_MAX_LENGTH, MMDiTConfig, VAEDecoderConfig, VAEEncoderConfig)
 from .engine import MMDiTEngine, VAEDecoderEngine, VAEEncoderEngine, _stream
-from .sampler import FluxSampler, ModelSamplingDiscreteFlow, get_sigmas, max_denoise
+from .sampler import FluxSampler, ModelSamplingDiscreteFlow, check_sampler, get_sigmas, max_denoise, step_plan
 from .weights import pack_mmdit, pack_vae, synth_mmdit_weights, synth_vae_encoder_weights, synth_vae_weights
 
 logger = logging.getLogger(__name__)
@@ -348,6 +351,7 @@ class DiffusionPipeline:
         *,
         mask_path=None,
         block_cache=None,
+        sampler=None,
     ):
         """mlx/__init__.py:253-292.  ``seed`` may be a list: one image per seed is denoised in a
         single batched step loop (data-parallel sharding hands each rank a list).
@@ -358,9 +362,16 @@ class DiffusionPipeline:
         relative to the last computed step, the cached effect of the other blocks is reused instead of running them.  One decision per launch:
         the images of a seed list and the two CFG rows share it through the maximum of their changes, so a cached batch equals the single
         runs only where their decisions coincide.  What was decided is kept in ``self.last_block_cache`` (threshold, computed and skipped
-        steps, rel per step; None without the option).  No threshold has been validated on a real checkpoint here."""
+        steps, rel per step; None without the option).  No threshold has been validated on a real checkpoint here.
+        ``sampler``: None or "euler" (the reference's first-order loop, today's launches and bits), "heun" (second order, two model evaluations
+        per step but the last) or "ab2" (second order, one evaluation per step, the previous step's direction kept in an fp32 buffer); every
+        composition above works with them, except that "heun" refuses ``block_cache`` (see ``sample_steps``).  ``self.last_sampler`` says what
+        ran: {"sampler", "model_evals"}.  Their order is checked on an analytic problem (profiles/samplers.md), not on a trained checkpoint."""
         if mask_path is not None and image_path is None:
             raise ValueError("mask_path needs image_path: the mask says which part of that image to keep")
+        sampler = check_sampler(sampler)
+        if sampler == "heun" and block_cache is not None:
+            raise ValueError(_HEUN_BLOCK_CACHE)
         seed = int(time.time()) if seed is None else seed
         seeds = list(seed) if isinstance(seed, (list, tuple)) else [seed]
         logger.info(f"Seed: {seeds}")
@@ -392,7 +403,14 @@ class DiffusionPipeline:
         noise_scaled = self.sampler.noise_scaling(np.float32(sigmas[0]), noise, x_T, self.max_denoise(sigmas))
         x0 = torch.from_numpy(np.ascontiguousarray(noise_scaled, dtype=np.float32)).to(self.device)
         denoiser = CFGDenoiser(self)
-        latent, iter_time = sample_euler(denoiser, x0, sigmas, extra_args=extra_args)
+        if sampler == "euler":
+            latent, iter_time = sample_euler(denoiser, x0, sigmas, extra_args=extra_args)
+            evals = len(iter_time)
+        else:
+            plan = step_plan(sampler, sigmas)
+            latent, iter_time = sample_steps(denoiser, x0, sigmas, plan, extra_args=extra_args)
+            evals = len(plan)
+        self.last_sampler = {"sampler": sampler, "model_evals": evals}
         self.last_block_cache = denoiser.block_cache_record
         latent = self.latent_format.process_out(latent)
         return latent, iter_time
@@ -412,10 +430,12 @@ class DiffusionPipeline:
         mask_path=None,
         composite: bool = True,
         block_cache=None,
+        sampler=None,
     ):
         """mlx/__init__.py:294-534: returns (PIL.Image, log).  ``mask_path``: inpainting, see ``denoise_latents``; with ``composite`` the pixels
         the mask keeps are pasted back from the input image after decoding (the VAE round trip alone does not reproduce them).
-        ``block_cache``: first-block cache, see ``denoise_latents``; its record goes to ``log["denoising"]["block_cache"]``."""
+        ``block_cache``: first-block cache, see ``denoise_latents``; its record goes to ``log["denoising"]["block_cache"]``.
+        ``sampler``: "euler" (default) | "heun" | "ab2", see ``denoise_latents``; ``log["denoising"]["sampler"]`` and ``["model_evals"]`` say what ran."""
         if mask_path is not None and image_path is None:
             raise ValueError("mask_path needs image_path: the mask says which part of that image to keep")
         assert latent_size[0] % 2 == 0, f"Height must be divisible by 16 ({latent_size[0]*8}/16={latent_size[0]/2})"
@@ -447,12 +467,14 @@ class DiffusionPipeline:
         log["denoising"]["pre"] = mem()
         latents, iter_time = self.denoise_latents(
             conditioning, pooled_conditioning, num_steps=num_steps, cfg_weight=cfg_weight,
-            latent_size=latent_size, seed=seed, image_path=image_path, denoise=denoise, mask_path=mask_path, block_cache=block_cache)
+            latent_size=latent_size, seed=seed, image_path=image_path, denoise=denoise, mask_path=mask_path, block_cache=block_cache,
+            sampler=sampler)
         torch.cuda.synchronize(dev)
         log["denoising"]["post"] = mem()
         log["peak_memory"] = max(log["peak_memory"], log["denoising"]["post"]["peak_memory"])
         log["denoising"]["time"] = round(time.time() - t0, 3)
         log["denoising"]["iter_time"] = iter_time
+        log["denoising"].update(self.last_sampler)
         if block_cache is not None:
             log["denoising"]["block_cache"] = self.last_block_cache
 
@@ -693,16 +715,30 @@ def _tile_conditioning(conditioning: Tensor, pooled: Tensor, n_img: int, cfg_on:
     return conditioning, pooled
 
 
-def sample_euler(model: CFGDenoiser, x: Tensor, sigmas, extra_args=None):
-    """mlx/__init__.py:761-788.  x: fp32 [n_img,h,w,16] on the GPU (updated copy is returned);
-    sigmas: host float32 array.  One device synchronisation per step (the reference's
-    mx.eval(x)) provides iter_time.
-    Inpainting: ``extra_args["mask"]`` (f32 [1 or n_img, h, w], 1 = repaint) together with ``"x_orig"`` and ``"noise"`` (f32 like x: the
-    encoded image after process_in and the draw of the start state) makes every step end in the blend of dk_euler_cfg_step_masked --
-    still one launch per step.
-    First-block cache: ``extra_args["block_cache"]`` (a float threshold or a policy object, ``sampler.BlockCachePolicy``) turns a step into
-    the engine's head, the read of its probe (the step's decision needs it on the host: a synchronisation), and the tail the policy chose;
-    the record of the decisions goes to ``model.block_cache_record``."""
+_HEUN_BLOCK_CACHE = ("sampler 'heun' cannot run together with block_cache: its two model evaluations per step do not map onto the policy's "
+                     "decide(step, n_steps, rel); a policy for two-evaluation steps is out of scope -- use sampler 'ab2' (one evaluation per step)")
+
+
+class _Loop(NamedTuple):
+    """what a step loop works on once the engine is prepared (``_loop_setup``)"""
+    pipe: object
+    mm: object
+    sigmas: np.ndarray
+    cfg_weight: float
+    cfg_on: bool
+    n_img: int
+    policy: object
+    x: Tensor
+    mask: Optional[Tensor]
+    x_orig: Optional[Tensor]
+    noise: Optional[Tensor]
+    tok: Tensor
+    out: Tensor
+
+
+def _loop_setup(model: "CFGDenoiser", x: Tensor, sigmas, extra_args) -> _Loop:
+    """The part of a step loop in front of its first step: conditioning rows in the engine's batch layout, timesteps, the engine prepared with its
+    modulation table and cached context, the fp32 copy of the latent, the inpainting operands and the first patchified tokens."""
     extra_args = {} if extra_args is None else dict(extra_args)
     pipe = model.model
     mm = pipe.mmdit
@@ -736,14 +772,30 @@ def sample_euler(model: CFGDenoiser, x: Tensor, sigmas, extra_args=None):
     x = x.to(torch.float32).contiguous().clone()
     mask = extra_args.get("mask")
     if mask is not None:
-        from . import ops
-        pcfg = pipe.mmdit_config
         mask, x_orig, noise = (t.to(pipe.device, torch.float32).contiguous() for t in (mask, extra_args["x_orig"], extra_args["noise"]))
         if x_orig.shape != x.shape or noise.shape != x.shape or mask.shape[1:] != x.shape[1:3] or mask.shape[0] not in (1, n_img):
             raise ValueError(f"inpainting operands do not match the latent {tuple(x.shape)}: x_orig {tuple(x_orig.shape)}, "
                              f"noise {tuple(noise.shape)}, mask {tuple(mask.shape)}")
+    else:
+        x_orig = noise = None
     tok = mm.patchify(x, dup=2 if cfg_on else 1)
-    out = torch.empty_like(tok)
+    return _Loop(pipe, mm, sigmas, cfg_weight, cfg_on, n_img, policy, x, mask, x_orig, noise, tok, torch.empty_like(tok))
+
+
+def sample_euler(model: CFGDenoiser, x: Tensor, sigmas, extra_args=None):
+    """mlx/__init__.py:761-788.  x: fp32 [n_img,h,w,16] on the GPU (updated copy is returned);
+    sigmas: host float32 array.  One device synchronisation per step (the reference's
+    mx.eval(x)) provides iter_time.
+    Inpainting: ``extra_args["mask"]`` (f32 [1 or n_img, h, w], 1 = repaint) together with ``"x_orig"`` and ``"noise"`` (f32 like x: the
+    encoded image after process_in and the draw of the start state) makes every step end in the blend of dk_euler_cfg_step_masked --
+    still one launch per step.
+    First-block cache: ``extra_args["block_cache"]`` (a float threshold or a policy object, ``sampler.BlockCachePolicy``) turns a step into
+    the engine's head, the read of its probe (the step's decision needs it on the host: a synchronisation), and the tail the policy chose;
+    the record of the decisions goes to ``model.block_cache_record``."""
+    pipe, mm, sigmas, cfg_weight, cfg_on, n_img, policy, x, mask, x_orig, noise, tok, out = _loop_setup(model, x, sigmas, extra_args)
+    if mask is not None:
+        from . import ops
+        pcfg = pipe.mmdit_config
     iter_time = []
     if policy is not None:
         from .sampler import block_cache_rel
@@ -776,5 +828,53 @@ def sample_euler(model: CFGDenoiser, x: Tensor, sigmas, extra_args=None):
                                       float(sigmas[i + 1]), cfg_weight, x_orig, noise, mask)
         torch.cuda.synchronize(pipe.device)
         iter_time.append(round(time.perf_counter() - t0, 3))
+    model.clear_cache()
+    return x, iter_time
+
+
+def sample_steps(model: CFGDenoiser, x: Tensor, sigmas, plan, extra_args=None):
+    """``sample_euler`` for the second-order samplers (no reference counterpart): ``plan`` = the rows of ``sampler.step_plan(name, sigmas)``, one model
+    evaluation each (at the row's entry of the schedule, which is also its row of the cached modulation table -- Heun's corrector reuses the next
+    step's), followed by one launch of dk_lms_cfg_step that applies the row's coefficients to x and to the fp32 history buffer allocated here.
+    Same operands and ``extra_args`` as ``sample_euler``, inpainting and the first-block cache included: the masked launch blends at the row's
+    sigma_next (on Heun's predictor row too, so that the corrector's evaluation sees the re-imposed region), and a plan of one evaluation per
+    step (ab2) hands the policy the same step indices as the Euler loop.  A plan with two evaluations in a step (heun) refuses ``block_cache``.
+    ``iter_time`` has one entry per step -- a Heun step's covers both evaluations -- with one device synchronisation per step."""
+    from . import ops
+    from .sampler import block_cache_rel
+    plan = list(plan)
+    pipe, mm, sigmas, cfg_weight, cfg_on, n_img, policy, x, mask, x_orig, noise, tok, out = _loop_setup(model, x, sigmas, extra_args)
+    if policy is not None and not all(r.ends_step for r in plan):
+        raise ValueError(_HEUN_BLOCK_CACHE)
+    if any(not 0 <= r.index < len(sigmas) - 1 for r in plan):
+        raise ValueError("the plan evaluates the model outside the schedule (or at its last entry): build it with sampler.step_plan on these sigmas")
+    pcfg = pipe.mmdit_config
+    hist = torch.empty_like(x) if any(r.reads_h or r.writes_h for r in plan) else None  # (never initialised: no row reads it before one wrote it)
+    n_steps = sum(r.ends_step for r in plan)
+    record = {"threshold": getattr(policy, "threshold", None), "computed": [], "skipped": [], "rel": []}
+    iter_time = []
+    step, t0 = 0, None
+    for r in plan:
+        t0 = time.perf_counter() if t0 is None else t0
+        if policy is None:
+            mm.forward_tokens(tok, None, r.index, tokens_out=out)
+        else:
+            rel = block_cache_rel(mm.forward_head(tok, None, r.index).cpu().tolist())  # (.cpu(): the step's synchronisation point)
+            skip = bool(policy.decide(step, n_steps, rel))
+            mm.forward_tail(r.index, skip, tokens_out=out)
+            record["skipped" if skip else "computed"].append(step)
+            record["rel"].append(rel)
+        args = (x, out, tok, n_img, cfg_on, pcfg.patch_size, int(pcfg.patchify_via_reshape), r.sigma, r.sigma_next, cfg_weight, hist,
+                (r.cx, r.cd, r.ch, r.hx, r.hd), r.reads_h, r.writes_h)
+        if mask is None:
+            ops.lms_cfg_step(*args)
+        else:
+            ops.lms_cfg_step_masked(*args, x_orig, noise, mask)
+        if r.ends_step:
+            torch.cuda.synchronize(pipe.device)
+            iter_time.append(round(time.perf_counter() - t0, 3))
+            step, t0 = step + 1, None
+    if policy is not None:
+        model.block_cache_record = record
     model.clear_cache()
     return x, iter_time

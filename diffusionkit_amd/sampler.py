@@ -9,6 +9,7 @@ numpy float32 so that the values agree with the reference's MLX float32 arrays.
 from __future__ import annotations
 
 import math
+from typing import List, NamedTuple
 
 import numpy as np
 
@@ -88,6 +89,74 @@ def max_denoise(sampler, sigmas) -> bool:
     max_sigma = float(sampler.sigma_max)
     sigma = float(sigmas[0])
     return math.isclose(max_sigma, sigma, rel_tol=1e-05) or sigma > max_sigma
+
+
+# ---- step plans: the update of every model evaluation as a coefficient row (host; no reference counterpart) --------------------------------
+SAMPLERS = ("euler", "heun", "ab2")
+
+
+def check_sampler(name) -> str:
+    """None -> "euler"; an unknown name raises a ValueError that lists the valid ones"""
+    if name is None:
+        return "euler"
+    if name not in SAMPLERS:
+        raise ValueError(f"unknown sampler {name!r}: valid samplers are {', '.join(SAMPLERS)}")
+    return name
+
+
+class StepRow(NamedTuple):
+    """One model evaluation and the update behind it (dk_lms_cfg_step):  d = (x - den) / sigma,  x' = cx x + cd d + ch H,  H' = hx x + hd d.
+    ``index``: which entry of the schedule the model is evaluated at (also the row of the cached modulation table); ``sigma`` = sigmas[index];
+    ``sigma_next``: the sigma x' lives at (the masked blend re-noises the known region to it); ``reads_h`` / ``writes_h``: whether the row takes
+    the history buffer / leaves one for a later row; ``ends_step``: x' is the state at the next entry of the schedule."""
+    index: int
+    sigma: float
+    sigma_next: float
+    cx: float
+    cd: float
+    ch: float
+    hx: float
+    hd: float
+    reads_h: bool
+    writes_h: bool
+    ends_step: bool
+
+
+def _row(index, sigma, sigma_next, cd, ch=0.0, reads_h=False, writes_h=False, ends_step=True) -> StepRow:
+    # (every method here keeps cx = 1 and H' = d; the coefficients are rounded to the kernel's float32 once, here)
+    f = lambda v: float(_F(v))  # noqa: E731
+    return StepRow(int(index), f(sigma), f(sigma_next), 1.0, f(cd), f(ch) if reads_h else 0.0, 0.0, 1.0 if writes_h else 0.0, bool(reads_h),
+                   bool(writes_h), bool(ends_step))
+
+
+def step_plan(name, sigmas) -> List[StepRow]:
+    """The ordered rows that take x from sigmas[0] to sigmas[-1], computed in float64 from the float32 schedule, with h = sigmas[i+1] - sigmas[i]:
+    euler  one row (1, h, 0) per step -- h is exact in float64, so its rounding is the float32 difference dk_euler_cfg_step takes;
+    heun   the trapezoid rule: the predictor (1, h, 0) at sigmas[i] leaves H = d, the corrector at sigmas[i+1], evaluated on the predicted
+           state, is (1, h/2, -h/2): x + (h/2)(d1 + d2).  The model is never evaluated at sigma = 0: a step that ends there is its Euler row;
+    ab2    variable-step Adams-Bashforth 2: the first row is Euler and leaves H = d; later ones are (1, h(1 + w), -h w), w = h / (2 h_prev),
+           H = d; a step that ends at sigma = 0 is its Euler row here too.
+    A row writes H only if the next row reads it.  A schedule cut by ``denoise`` starts at its first remaining entry, first-order."""
+    name = check_sampler(name)
+    s = [float(v) for v in np.asarray(sigmas, dtype=_F)]
+    n = len(s) - 1
+    rows: List[StepRow] = []
+    for i in range(n):
+        h = s[i + 1] - s[i]
+        last = s[i + 1] == 0.0
+        if name == "euler" or last and name == "heun":
+            rows.append(_row(i, s[i], s[i + 1], h))
+        elif name == "heun":
+            rows.append(_row(i, s[i], s[i + 1], h, writes_h=True, ends_step=False))
+            rows.append(_row(i + 1, s[i + 1], s[i + 1], h / 2, -h / 2, reads_h=True))
+        else:
+            feeds = i + 1 < n and s[i + 2] != 0.0  # (the next row reads H)
+            if i == 0 or last:
+                rows.append(_row(i, s[i], s[i + 1], h, writes_h=feeds))
+            else:
+                w = h / (2.0 * (s[i] - s[i - 1]))
+                rows.append(_row(i, s[i], s[i + 1], h * (1.0 + w), -h * w, reads_h=True, writes_h=feeds))
+    return rows
 
 
 # ---- first-block cache: which steps compute and which reuse (host policy; no reference counterpart) -------------------------

@@ -390,6 +390,35 @@ int dk_euler_cfg_step_masked_f16(float* x, const void* model_out, int32_t ld_out
                                  float sigma, float sigma_next, float cfg_weight, const float* x_orig, const float* noise,
                                  const float* mask, int32_t mask_per_image, void* stream);
 
+/* Second-order samplers (Heun, Adams-Bashforth 2; no reference counterpart): dk_euler_cfg_step with the update as a coefficient row over
+ * one caller-owned history buffer hist (f32, shaped like x).  den is formed as dk_euler_cfg_step forms it; then
+ *   d = (x - den) / sigma;   x' = cx * x + cd * d + ch * hist;   hist' = hx * x + hd * d   (x before the update)
+ * sigma: the sigma of the model evaluation; sigma_next: the sigma x' lives at (read by the masked entries' blend only).
+ * reads_h == 0: hist is not read (it may be uninitialised) and ch is ignored; writes_h == 0: hist is not written; hist may be null when
+ * both are 0.  A row with reads_h == 0, cx == 1 and cd = sigma_next - sigma (taken in fp32) gives dk_euler_cfg_step's x and tokens bit
+ * for bit.  The host computes the rows (diffusionkit_amd/sampler.py: step_plan).  Refused with a dk_last_error() text: sigma == 0, a null
+ * hist under a set flag, a non-finite coefficient or sigma.
+ * _masked: followed in the same launch by dk_euler_cfg_step_masked's blend with known taken at sigma_next (same operands, same exact ends).
+ * _f16: model_out and tokens are fp16. */
+int dk_lms_cfg_step(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on,
+                    int32_t Hl, int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma, float cfg_weight,
+                    float* hist, float cx, float cd, float ch, float hx, float hd, float sigma_next, int32_t reads_h,
+                    int32_t writes_h, void* stream);
+int dk_lms_cfg_step_f16(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on,
+                        int32_t Hl, int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma, float cfg_weight,
+                        float* hist, float cx, float cd, float ch, float hx, float hd, float sigma_next, int32_t reads_h,
+                        int32_t writes_h, void* stream);
+int dk_lms_cfg_step_masked(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on,
+                           int32_t Hl, int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma, float cfg_weight,
+                           float* hist, float cx, float cd, float ch, float hx, float hd, float sigma_next, int32_t reads_h,
+                           int32_t writes_h, const float* x_orig, const float* noise, const float* mask,
+                           int32_t mask_per_image, void* stream);
+int dk_lms_cfg_step_masked_f16(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on,
+                               int32_t Hl, int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma, float cfg_weight,
+                               float* hist, float cx, float cd, float ch, float hx, float hd, float sigma_next, int32_t reads_h,
+                               int32_t writes_h, const float* x_orig, const float* noise, const float* mask,
+                               int32_t mask_per_image, void* stream);
+
 /* Inpainting mask, pixels -> latent cells: mask u8 [n_mask,H,W] (255 = repaint, 0 = keep) -> f32 [n_mask,H/f,W/f],
  * (integer sum of the f x f block) / (f * f * 255) by a true division: an all-0 block gives 0.0f, an all-255 block 1.0f.
  * H and W must be multiples of f (the pipeline passes the VAE's factor, 8). */
