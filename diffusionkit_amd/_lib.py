@@ -196,6 +196,10 @@ SIGNATURES = {
     "dk_lms_cfg_step_f16": (_i32, _LMS_ARGS + [_vp]),
     "dk_lms_cfg_step_masked": (_i32, _LMS_ARGS + [_vp, _vp, _vp, _i32, _vp]),
     "dk_lms_cfg_step_masked_f16": (_i32, _LMS_ARGS + [_vp, _vp, _vp, _i32, _vp]),
+    # guidance modes: dk_lms_cfg_step's list, the (nullable) mask operands, then mode, phi, eta, r, beta, reads_m, writes_m, m, workspace, its bytes
+    "dk_guidance_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "dk_guided_cfg_step": (_i32, _LMS_ARGS + [_vp, _vp, _vp, _i32, _i32, _f32, _f32, _f32, _f32, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "dk_guided_cfg_step_f16": (_i32, _LMS_ARGS + [_vp, _vp, _vp, _i32, _i32, _f32, _f32, _f32, _f32, _i32, _i32, _vp, _vp, _sz, _vp]),
     "dk_mask_to_latent_f32": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "dk_image_composite_u8": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "dk_affine_f32": (_i32, [_vp, _vp, _i64, _f32, _f32, _vp]),

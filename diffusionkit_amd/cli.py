@@ -64,6 +64,19 @@ def build_parser(model_versions: Sequence[str]) -> argparse.ArgumentParser:
                    help="Integrator of the step loop. euler (default): first order, one model evaluation per step. heun: second order, two "
                         "evaluations per step but the last (not together with --block-cache). ab2: second order, one evaluation per step. "
                         "The orders are checked on an analytic problem, not on a trained checkpoint.")
+    p.add_argument("--guidance", choices=("cfg", "rescale", "apg"), default=None,
+                   help="How the prompt and the negative prediction are combined (models with --cfg > 0 only). cfg (default): neg + w (pos - neg). "
+                        "rescale: the same, scaled towards the prompt prediction's standard deviation (--guidance-rescale). apg: adaptive "
+                        "projected guidance (--apg-eta, --apg-norm-threshold, --apg-momentum). Verified as arithmetic only: no setting has "
+                        "been validated on a trained checkpoint here.")
+    p.add_argument("--guidance-rescale", type=float, default=None, metavar="PHI", help="rescale: blend factor in [0, 1] (default 0.7).")
+    p.add_argument("--apg-eta", type=float, default=None, metavar="ETA", help="apg: weight of the component parallel to the prediction (default 0).")
+    p.add_argument("--apg-norm-threshold", type=float, default=None, metavar="R",
+                   help="apg: clip the norm of the guidance direction to R per image (default 0 = off).")
+    p.add_argument("--apg-momentum", type=float, default=None, metavar="BETA",
+                   help="apg: momentum of the guidance direction over the guided evaluations (default 0; the paper uses -0.5).")
+    p.add_argument("--guidance-interval", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                   help="Guide only the model evaluations whose sigma lies in [LO, HI]; the others run on the prompt alone, at half the batch.")
     p.add_argument("--local-ckpt", default=None, type=str, help="Path to the local mmdit checkpoint.")
     p.add_argument("--ckpt", action="append", default=[], metavar="KEY=PATH",
                    help="Further local checkpoint parts (vae_decoder, vae_encoder, clip_l, clip_g, t5, t5_tokenizer, "
@@ -135,7 +148,22 @@ def resolve(args) -> dict:
             raise ValueError("--sampler heun cannot run together with --block-cache (two model evaluations per step have no cache policy yet); "
                              "use --sampler ab2")
         r["sampler"] = args.sampler
+    for flag, key in GUIDANCE_FLAGS.items():  # (keys only when the flags are given)
+        v = getattr(args, flag, None)
+        if v is not None:
+            if cfg <= 0.0:
+                raise ValueError(f"--{flag.replace('_', '-')} needs classifier-free guidance (--cfg > 0), which {args.model_version} runs without")
+            r[key] = tuple(v) if flag == "guidance_interval" else v
+    if "guidance_rescale" in r and not 0.0 <= r["guidance_rescale"] <= 1.0:
+        raise ValueError("--guidance-rescale must lie in [0, 1]")
+    if "guidance_interval" in r and not r["guidance_interval"][0] <= r["guidance_interval"][1]:
+        raise ValueError("--guidance-interval expects LO <= HI")
     return r
+
+
+# argparse destination -> keyword of generate_image
+GUIDANCE_FLAGS = {"guidance": "guidance", "guidance_rescale": "guidance_rescale", "apg_eta": "apg_eta", "apg_norm_threshold": "apg_norm_threshold",
+                  "apg_momentum": "apg_momentum", "guidance_interval": "guidance_interval"}
 
 
 def main(argv: Optional[Sequence[str]] = None, pipeline_overrides: Optional[dict] = None):
@@ -168,7 +196,8 @@ def main(argv: Optional[Sequence[str]] = None, pipeline_overrides: Optional[dict
     image, log = sd.generate_image(args.prompt, cfg_weight=r["cfg"], num_steps=args.steps, seed=args.seed,
                                    negative_text=args.negative_prompt, latent_size=latent_size, image_path=args.image_path,
                                    denoise=args.denoise, verbose=args.verbose, mask_path=r.get("mask_path"),
-                                   composite=r.get("composite", True), block_cache=r.get("block_cache"), sampler=r.get("sampler"))
+                                   composite=r.get("composite", True), block_cache=r.get("block_cache"), sampler=r.get("sampler"),
+                                   **{key: r[key] for key in GUIDANCE_FLAGS.values() if key in r})
     if log["text_encoding"].get("synthetic"):
         logger.warning("no text-encoder checkpoints were named (--ckpt clip_l=... t5=...): the conditioning is synthetic")
     image.save(args.output_path)

@@ -493,6 +493,65 @@ extern "C" int dk_lms_cfg_step_masked_f16(float* x, const void* model_out, int32
                       ch, hx, hd, sigma_next, reads_h, writes_h, x_orig, noise, mask, mask_per_image, stream);
 }
 
+// guidance modes: the coefficient-row step behind the per-image moments of the two predictions (mode 0: dk_lms_cfg_step itself)
+extern "C" size_t dk_guidance_workspace_bytes(int32_t n_img, int32_t Hl, int32_t Wl, int32_t C) {
+  if (n_img <= 0 || Hl <= 0 || Wl <= 0 || C <= 0) return 0;
+  return dk_guidance_workspace_size(n_img, Hl, Wl, C);
+}
+static int guided_cfg_step(int dtype, float* x, const void* model_out, int ld_out, void* tokens, int n_img, int cfg_on, int Hl, int Wl, int C, int p,
+                           int reshape_order, float sigma, float cfg_weight, float* hist, float cx, float cd, float ch, float hx, float hd,
+                           float sigma_next, int reads_h, int writes_h, const float* x_orig, const float* noise, const float* mask,
+                           int mask_per_image, int mode, float phi, float eta, float r, float beta, int reads_m, int writes_m, float* m,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+  DK_REQUIRE(cfg_on != 0, "guidance modes combine two predictions: cfg_on must be set (an unguided row is dk_lms_cfg_step with cfg_on = 0)");
+  DK_REQUIRE(mode >= 0 && mode <= 2, "unknown guidance mode (0 cfg, 1 rescale, 2 apg)");
+  DK_REQUIRE(std::isfinite(phi) && std::isfinite(eta) && std::isfinite(r) && std::isfinite(beta) && std::isfinite(cfg_weight),
+             "the guidance parameters must be finite");
+  DK_REQUIRE(phi >= 0.0f && phi <= 1.0f, "the rescale factor phi must lie in [0, 1]");
+  DK_REQUIRE(C > 0 && Hl > 0 && Wl > 0, "the latent size must be positive");
+  const bool masked = x_orig || noise || mask;
+  if (mode == 0)
+    return lms_cfg_step(dtype, masked, x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, cfg_weight, hist, cx, cd, ch,
+                        hx, hd, sigma_next, reads_h, writes_h, x_orig, noise, mask, mask_per_image, stream);
+  DK_REQUIRE(sigma != 0.0f, "sigma must be non-zero");
+  DK_REQUIRE(p > 0 && Hl % p == 0 && Wl % p == 0, "latent size must be divisible by the patch size");
+  DK_REQUIRE(x && model_out && tokens, "null argument");
+  DK_REQUIRE(n_img > 0, "n_img must be positive");
+  DK_REQUIRE(hist || !(reads_h || writes_h), "hist is null while the row reads or writes the history");
+  const float coef[5] = {cx, cd, ch, hx, hd};
+  for (float v : coef) DK_REQUIRE(std::isfinite(v), "the coefficients of the row must be finite");
+  DK_REQUIRE(std::isfinite(sigma) && std::isfinite(sigma_next), "sigma and sigma_next must be finite");
+  if (masked) DK_REQUIRE(x_orig && noise && mask, "null argument");
+  if (mode != 2) reads_m = writes_m = 0;
+  DK_REQUIRE(m || !(reads_m || writes_m), "the momentum buffer M is null while the row reads or writes it");
+  DK_REQUIRE(workspace && workspace_bytes >= dk_guidance_workspace_size(n_img, Hl, Wl, C),
+             "the guidance workspace is null or shorter than dk_guidance_workspace_bytes");
+  const float gpar[4] = {phi, eta, r, beta};
+  return DK_EL(dtype, dk_launch_guided_step)(x, (const bf16_t*)model_out, ld_out, (bf16_t*)tokens, n_img, Hl, Wl, C, p, reshape_order, sigma,
+                                             sigma_next, cfg_weight, hist, coef, reads_h != 0, writes_h != 0, x_orig, noise, mask,
+                                             mask_per_image != 0, mode, gpar, reads_m != 0, writes_m != 0, m, workspace, S_(stream));
+}
+extern "C" int dk_guided_cfg_step(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on, int32_t Hl, int32_t Wl,
+                                  int32_t C, int32_t p, int32_t reshape_order, float sigma, float cfg_weight, float* hist, float cx, float cd,
+                                  float ch, float hx, float hd, float sigma_next, int32_t reads_h, int32_t writes_h, const float* x_orig,
+                                  const float* noise, const float* mask, int32_t mask_per_image, int32_t mode, float phi, float eta, float r,
+                                  float beta, int32_t reads_m, int32_t writes_m, float* m, void* workspace, size_t workspace_bytes,
+                                  void* stream) {
+  return guided_cfg_step(DK_DTYPE_BF16, x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, cfg_weight, hist, cx, cd, ch,
+                         hx, hd, sigma_next, reads_h, writes_h, x_orig, noise, mask, mask_per_image, mode, phi, eta, r, beta, reads_m, writes_m, m,
+                         workspace, workspace_bytes, stream);
+}
+extern "C" int dk_guided_cfg_step_f16(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on, int32_t Hl,
+                                      int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma, float cfg_weight, float* hist, float cx,
+                                      float cd, float ch, float hx, float hd, float sigma_next, int32_t reads_h, int32_t writes_h,
+                                      const float* x_orig, const float* noise, const float* mask, int32_t mask_per_image, int32_t mode, float phi,
+                                      float eta, float r, float beta, int32_t reads_m, int32_t writes_m, float* m, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+  return guided_cfg_step(DK_DTYPE_F16, x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, cfg_weight, hist, cx, cd, ch,
+                         hx, hd, sigma_next, reads_h, writes_h, x_orig, noise, mask, mask_per_image, mode, phi, eta, r, beta, reads_m, writes_m, m,
+                         workspace, workspace_bytes, stream);
+}
+
 extern "C" int dk_mask_to_latent_f32(const uint8_t* mask, float* out, int32_t n_mask, int32_t H, int32_t W, int32_t f, void* stream) {
   DK_REQUIRE(mask && out, "null argument");
   DK_REQUIRE(n_mask > 0, "n_mask must be positive");

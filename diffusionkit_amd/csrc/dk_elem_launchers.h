@@ -44,6 +44,15 @@ int dk_launch_euler_step_masked(float* x, const bf16_t* model_out, int ld_out, b
 int dk_launch_lms_step(float* x, const bf16_t* model_out, int ld_out, bf16_t* tok, int n_img, int cfg_on, int Hl, int Wl, int C, int p,
                        int reshape_order, float sigma, float sigma_next, float cfg_weight, float* hist, const float* coef, int reads_h,
                        int writes_h, const float* x_orig, const float* noise, const float* mask, int mask_per_image, hipStream_t stream);
+// guidance modes (include/dk_hip.h): the per-image moments of the two predictions (two launches: partial sums per workgroup, then one wave
+// per image folds them in fp64 into the scalars), then the coefficient-row step with den = g * s (mode 1, rescale) or c + (w - 1)(a D - b c)
+// (mode 2, APG; m: the fp32 momentum buffer, read under reads_m, written under writes_m).  gpar = (phi, eta, r, beta); workspace: at least
+// dk_guidance_workspace_size bytes, 8-byte aligned.  CFG is on by definition.
+size_t dk_guidance_workspace_size(int n_img, int Hl, int Wl, int C);
+int dk_launch_guided_step(float* x, const bf16_t* model_out, int ld_out, bf16_t* tok, int n_img, int Hl, int Wl, int C, int p,
+                          int reshape_order, float sigma, float sigma_next, float cfg_weight, float* hist, const float* coef, int reads_h,
+                          int writes_h, const float* x_orig, const float* noise, const float* mask, int mask_per_image, int mode,
+                          const float* gpar, int reads_m, int writes_m, float* m, void* workspace, hipStream_t stream);
 // first-block cache (include/dk_hip.h): d = round(x - d) over M rows of x through the row map, (num, den) = (sum |d - d_ref|, sum |d_ref|) per
 // row into row_partials [M][2], then per rows_per_batch rows in a fixed order into probe [M / rows_per_batch][2]; d_ref null: read as zeros
 int dk_launch_block_probe(const bf16_t* x, int ldx, int x_seg_len, int x_seg_stride, bf16_t* d, const bf16_t* d_ref, float* row_partials,

@@ -518,10 +518,24 @@ struct LmsRow {
   float cx, cd, ch, hx, hd;
   int reads_h, writes_h;
 };
-template <bool MASKED>
+// Guidance modes (include/dk_hip.h; no reference counterpart).  GMODE = DK_GUIDE_CFG is the kernel as it was: gd is not read.  With c = den
+// of the prompt row and u = den of the negative row, formed as above:
+//   RESCALE  g = u + w (c - u),  den = g * s                      s = scal[2 img]               (s == 1.0f: the CFG step bit for bit)
+//   APG      D = (c - u) [+ beta * M],  den = c + (w - 1)(a D - b c)   (a, b) = scal[2 img], scal[2 img + 1]
+// The per-image scalars come from the moments pass below, which forms c, u, g and D by the same expressions.  M (fp32, shaped like the latent)
+// follows hist's discipline: read only under reads_m, written (M' = D) only under writes_m, each element by the thread that read it.
+enum { DK_GUIDE_CFG = 0, DK_GUIDE_RESCALE = 1, DK_GUIDE_APG = 2 };
+struct GuideArgs {
+  const float* scal;
+  float* m;
+  float beta;
+  int reads_m, writes_m;
+};
+template <bool MASKED, int GMODE = DK_GUIDE_CFG>
 __global__ void dk_lms_step_kernel(float* x, const bf16_t* model_out, int ld_out, bf16_t* tok, int n_img, int cfg_on, int Hl, int Wl,
                                    int C, int p, int reshape_order, float sigma, float sigma_next, float cfg_weight, float* hist,
-                                   LmsRow row, const float* x_orig, const float* noise, const float* mask, int mask_per_image) {
+                                   LmsRow row, const float* x_orig, const float* noise, const float* mask, int mask_per_image,
+                                   GuideArgs gd) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long per_img = (long)Hl * Wl * C;
   if (i >= per_img * n_img) return;
@@ -537,10 +551,25 @@ __global__ void dk_lms_step_kernel(float* x, const bf16_t* model_out, int ld_out
   const float xb = round_act(xv);  // the value the denoiser saw
   const float o_text = to_f32(model_out[((size_t)img * S_i + t) * ld_out + f]);
   float den = xb - o_text * sigma;
-  if (cfg_on) {
+  if constexpr (GMODE == DK_GUIDE_CFG) {
+    if (cfg_on) {
+      const float o_neg = to_f32(model_out[((size_t)(n_img + img) * S_i + t) * ld_out + f]);
+      const float den_neg = xb - o_neg * sigma;
+      den = den_neg + cfg_weight * (den - den_neg);
+    }
+  } else {  // (the launcher passes cfg_on = 1)
     const float o_neg = to_f32(model_out[((size_t)(n_img + img) * S_i + t) * ld_out + f]);
     const float den_neg = xb - o_neg * sigma;
-    den = den_neg + cfg_weight * (den - den_neg);
+    if constexpr (GMODE == DK_GUIDE_RESCALE) {
+      const float g = den_neg + cfg_weight * (den - den_neg);
+      den = g * gd.scal[2 * img];
+    } else {
+      float dl = den - den_neg;
+      if (gd.reads_m) dl = dl + gd.beta * gd.m[i];
+      if (gd.writes_m) gd.m[i] = dl;
+      const float a = gd.scal[2 * img], b = gd.scal[2 * img + 1];
+      den = den + (cfg_weight - 1.0f) * (a * dl - b * den);
+    }
   }
   const float d = (xv - den) / sigma;
   float xn;
@@ -567,12 +596,163 @@ int dk_launch_lms_step(float* x, const bf16_t* model_out, int ld_out, bf16_t* to
   const long n = (long)n_img * Hl * Wl * C;
   const LmsRow row = {coef[0], coef[1], coef[2], coef[3], coef[4], reads_h, writes_h};
   const dim3 grid((unsigned)((n + 255) / 256));
+  const GuideArgs none = {nullptr, nullptr, 0.f, 0, 0};
   if (mask)
     hipLaunchKernelGGL(dk_lms_step_kernel<true>, grid, dim3(256), 0, stream, x, model_out, ld_out, tok, n_img, cfg_on, Hl, Wl, C, p,
-                       reshape_order, sigma, sigma_next, cfg_weight, hist, row, x_orig, noise, mask, mask_per_image);
+                       reshape_order, sigma, sigma_next, cfg_weight, hist, row, x_orig, noise, mask, mask_per_image, none);
   else
     hipLaunchKernelGGL(dk_lms_step_kernel<false>, grid, dim3(256), 0, stream, x, model_out, ld_out, tok, n_img, cfg_on, Hl, Wl, C, p,
-                       reshape_order, sigma, sigma_next, cfg_weight, hist, row, nullptr, nullptr, nullptr, 0);
+                       reshape_order, sigma, sigma_next, cfg_weight, hist, row, nullptr, nullptr, nullptr, 0, none);
+  DK_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Guidance moments (no reference counterpart): the per-image sums the guided step needs, and the scalars they end in.
+// Pass 1: grid (nb, n_img), 256 threads -- a workgroup never leaves its image.  Thread t of block b takes the elements b * 256 + t,
+// + nb * 256, ... of the image, in that order, forms c, u and g or D as dk_lms_step_kernel does and adds its terms in fp32; wave_sum
+// folds the lanes in a fixed butterfly; the four wave partials go through LDS and thread 0 adds them in fp64, in wave order, into
+// part[img][b][4].  RESCALE: (sum c, sum g, sum c^2, sum g^2); APG: (sum D^2, sum D c, sum c^2, 0).
+// Pass 2: one wave per image, lane l adds blocks l, l + 64, ... in that order in fp64, a fixed butterfly folds the lanes, lane 0 writes
+//   RESCALE  s = phi * std(c) / std(g) + (1 - phi)   (std(g) == 0: s = 1; phi == 0: s = 1.0f exactly)
+//   APG      a = min(1, r / |D|) (r <= 0 or |D| == 0: 1),   b = (1 - eta) a <D, c> / <c, c>  (<c, c> == 0: 0)
+// as scal[2 img], scal[2 img + 1].  No atomics: the same bits on every run.  The workspace: part (fp64) [n_img][nb][4], then scal (fp32)
+// [n_img][2]; every element read is written first.
+// ---------------------------------------------------------------------------------------------
+static inline int guide_blocks(long per_img) {
+  const long nb = (per_img + 1023) / 1024;
+  return (int)(nb < 1 ? 1 : nb > 1024 ? 1024 : nb);
+}
+size_t dk_guidance_workspace_size(int n_img, int Hl, int Wl, int C) {
+  const long per_img = (long)Hl * Wl * C;
+  return (size_t)n_img * guide_blocks(per_img) * 4 * sizeof(double) + (size_t)n_img * 2 * sizeof(float);
+}
+template <int GMODE>
+__global__ __launch_bounds__(256) void dk_guide_moments_kernel(const float* x, const bf16_t* model_out, int ld_out, int n_img, int Hl, int Wl,
+                                                               int C, int p, int reshape_order, float sigma, float cfg_weight,
+                                                               const float* m, float beta, int reads_m, double* part) {
+  __shared__ float wpart[4][4];
+  const int img = blockIdx.y, nb = gridDim.x;
+  const int per_img = Hl * Wl * C;  // (< 2^31: checked by the launcher)
+  const int gw = Wl / p, S_i = (Hl / p) * gw;
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+  for (int j = (int)blockIdx.x * 256 + (int)threadIdx.x; j < per_img; j += nb * 256) {
+    const long i = (long)img * per_img + j;
+    int r = j;
+    const int c = r % C;
+    r /= C;
+    const int xx = r % Wl, yy = r / Wl;
+    const int t = (yy / p) * gw + (xx / p);
+    const int f = patch_feature(c, yy % p, xx % p, C, p, reshape_order);
+    const float xb = round_act(x[i]);
+    const float o_text = to_f32(model_out[((size_t)img * S_i + t) * ld_out + f]);
+    const float o_neg = to_f32(model_out[((size_t)(n_img + img) * S_i + t) * ld_out + f]);
+    const float den = xb - o_text * sigma;
+    const float den_neg = xb - o_neg * sigma;
+    if constexpr (GMODE == DK_GUIDE_RESCALE) {
+      const float g = den_neg + cfg_weight * (den - den_neg);
+      s0 += den;
+      s1 += g;
+      s2 += den * den;
+      s3 += g * g;
+    } else {
+      float dl = den - den_neg;
+      if (reads_m) dl = dl + beta * m[i];
+      s0 += dl * dl;
+      s1 += dl * den;
+      s2 += den * den;
+    }
+  }
+  s0 = wave_sum(s0);
+  s1 = wave_sum(s1);
+  s2 = wave_sum(s2);
+  s3 = wave_sum(s3);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    wpart[wave][0] = s0;
+    wpart[wave][1] = s1;
+    wpart[wave][2] = s2;
+    wpart[wave][3] = s3;
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    const int k = threadIdx.x;
+    double acc = (double)wpart[0][k];
+    for (int w = 1; w < 4; ++w) acc += (double)wpart[w][k];
+    part[((size_t)img * nb + blockIdx.x) * 4 + k] = acc;
+  }
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+template <int GMODE>
+__global__ __launch_bounds__(64) void dk_guide_fold_kernel(const double* part, float* scal, int nb, double n_elem, float phi, float eta,
+                                                           float thr) {
+  const int img = blockIdx.x, lane = threadIdx.x;
+  const double* pp = part + (size_t)img * nb * 4;
+  double s[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int b = lane; b < nb; b += 64) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s[k] += pp[(size_t)b * 4 + k];
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) s[k] = wave_sum_f64(s[k]);
+  if (lane != 0) return;
+  float o0, o1 = 0.f;
+  if constexpr (GMODE == DK_GUIDE_RESCALE) {
+    const double mc = s[0] / n_elem, mg = s[1] / n_elem;
+    double vc = s[2] / n_elem - mc * mc, vg = s[3] / n_elem - mg * mg;
+    vc = vc > 0.0 ? vc : 0.0;
+    vg = vg > 0.0 ? vg : 0.0;
+    o0 = (phi == 0.f || !(vg > 0.0)) ? 1.0f : (float)((double)phi * sqrt(vc / vg) + (1.0 - (double)phi));
+  } else {
+    const double nd = sqrt(s[0]);
+    const double a = (thr > 0.f && nd > 0.0 && (double)thr < nd) ? (double)thr / nd : 1.0;
+    o0 = (float)a;
+    o1 = s[2] > 0.0 ? (float)((1.0 - (double)eta) * a * s[1] / s[2]) : 0.0f;
+  }
+  *(float2*)(scal + 2 * img) = make_float2(o0, o1);
+}
+int dk_launch_guided_step(float* x, const bf16_t* model_out, int ld_out, bf16_t* tok, int n_img, int Hl, int Wl, int C, int p,
+                          int reshape_order, float sigma, float sigma_next, float cfg_weight, float* hist, const float* coef, int reads_h,
+                          int writes_h, const float* x_orig, const float* noise, const float* mask, int mask_per_image, int mode,
+                          const float* gpar, int reads_m, int writes_m, float* m, void* workspace, hipStream_t stream) {
+  const long per_img = (long)Hl * Wl * C;
+  const long n = (long)n_img * per_img;
+  DK_REQUIRE(per_img < (1L << 31) - 1024L * 256, "the latent of one image must hold fewer than 2^31 elements");
+  DK_REQUIRE(((uintptr_t)workspace & 7) == 0, "the guidance workspace must be 8-byte aligned");
+  const int nb = guide_blocks(per_img);
+  double* part = (double*)workspace;
+  float* scal = (float*)(part + (size_t)n_img * nb * 4);
+  const float phi = gpar[0], eta = gpar[1], thr = gpar[2], beta = gpar[3];
+  const dim3 mgrid((unsigned)nb, (unsigned)n_img);
+  if (mode == DK_GUIDE_RESCALE) {
+    hipLaunchKernelGGL(dk_guide_moments_kernel<DK_GUIDE_RESCALE>, mgrid, dim3(256), 0, stream, x, model_out, ld_out, n_img, Hl, Wl, C, p,
+                       reshape_order, sigma, cfg_weight, nullptr, 0.f, 0, part);
+    DK_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(dk_guide_fold_kernel<DK_GUIDE_RESCALE>, dim3(n_img), dim3(64), 0, stream, part, scal, nb, (double)per_img, phi, eta,
+                       thr);
+  } else {
+    hipLaunchKernelGGL(dk_guide_moments_kernel<DK_GUIDE_APG>, mgrid, dim3(256), 0, stream, x, model_out, ld_out, n_img, Hl, Wl, C, p,
+                       reshape_order, sigma, cfg_weight, m, beta, reads_m, part);
+    DK_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(dk_guide_fold_kernel<DK_GUIDE_APG>, dim3(n_img), dim3(64), 0, stream, part, scal, nb, (double)per_img, phi, eta, thr);
+  }
+  DK_CHECK_HIP(hipGetLastError());
+  const LmsRow row = {coef[0], coef[1], coef[2], coef[3], coef[4], reads_h, writes_h};
+  const GuideArgs gd = {scal, m, beta, reads_m, writes_m};
+  const dim3 grid((unsigned)((n + 255) / 256));
+#define GUIDED_STEP(MASKED, GMODE)                                                                                                          \
+  hipLaunchKernelGGL((dk_lms_step_kernel<MASKED, GMODE>), grid, dim3(256), 0, stream, x, model_out, ld_out, tok, n_img, 1, Hl, Wl, C, p,     \
+                     reshape_order, sigma, sigma_next, cfg_weight, hist, row, x_orig, noise, mask, mask_per_image, gd)
+  if (mode == DK_GUIDE_RESCALE) {
+    if (mask) GUIDED_STEP(true, DK_GUIDE_RESCALE); else GUIDED_STEP(false, DK_GUIDE_RESCALE);
+  } else {
+    if (mask) GUIDED_STEP(true, DK_GUIDE_APG); else GUIDED_STEP(false, DK_GUIDE_APG);
+  }
+#undef GUIDED_STEP
   DK_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -487,6 +487,53 @@ def lms_cfg_step_masked(x: Tensor, model_out: Tensor, tokens: Tensor, n_img: int
     _lib.check(getattr(_lib.load(), name)(*args, x_orig.data_ptr(), noise.data_ptr(), mask.data_ptr(), per_image, _stream()), name)
 
 
+GUIDANCE_MODES = {"cfg": 0, "rescale": 1, "apg": 2}
+
+
+def guidance_workspace_bytes(n_img: int, hl: int, wl: int, c: int) -> int:
+    """dk_guidance_workspace_bytes: what ``guided_cfg_step`` needs as ``workspace`` for a latent [n_img, hl, wl, c]"""
+    return int(_lib.load().dk_guidance_workspace_bytes(int(n_img), int(hl), int(wl), int(c)))
+
+
+def guided_cfg_step(x: Tensor, model_out: Tensor, tokens: Tensor, n_img: int, cfg_on: bool, p: int, reshape_order: int, sigma: float,
+                    sigma_next: float, cfg_weight: float, hist: Optional[Tensor], coef, reads_h: bool, writes_h: bool, *, mode: str,
+                    workspace: Optional[Tensor], rescale: float = 0.0, eta: float = 0.0, norm_threshold: float = 0.0, momentum: float = 0.0,
+                    reads_m: bool = False, writes_m: bool = False, m: Optional[Tensor] = None, x_orig: Optional[Tensor] = None,
+                    noise: Optional[Tensor] = None, mask: Optional[Tensor] = None) -> None:
+    """dk_guided_cfg_step / _f16 by the dtype of ``model_out``: ``lms_cfg_step`` (with ``x_orig``, ``noise`` and ``mask``: ``lms_cfg_step_masked``)
+    with the two predictions combined by ``mode``: "cfg", "rescale" (``rescale`` = phi in [0, 1]) or "apg" (``eta``, ``norm_threshold`` r,
+    ``momentum`` beta, and the momentum buffer ``m``, f32 like x, read only under ``reads_m`` and written only under ``writes_m``); the definitions
+    are ``sampler.guide_reference``'s.  ``workspace``: a device tensor of at least ``guidance_workspace_bytes(...)`` bytes, 8-byte aligned, never
+    initialised by the caller (None for "cfg", which launches nothing else)."""
+    name = "dk_guided_cfg_step" + ("" if _elem(model_out.dtype, "guided_cfg_step") == "bf16" else "_f16")
+    if mode not in GUIDANCE_MODES:
+        raise ValueError(f"unknown guidance mode {mode!r}: valid modes are {', '.join(GUIDANCE_MODES)}")
+    args = _lms_args(x, model_out, tokens, n_img, cfg_on, p, reshape_order, sigma, sigma_next, cfg_weight, hist, coef, reads_h, writes_h)
+    _, hl, wl, _ = x.shape
+    per_image = 0
+    if x_orig is not None or noise is not None or mask is not None:
+        for n, t in (("x_orig", x_orig), ("noise", noise), ("mask", mask)):
+            if t is None:
+                raise _lib.DkHipError(f"guided_cfg_step: {n} is None while another mask operand is given")
+            _require_cuda(t, n, torch.float32)
+        if x_orig.shape != x.shape or noise.shape != x.shape:
+            raise _lib.DkHipError(f"x_orig {tuple(x_orig.shape)} and noise {tuple(noise.shape)} must have the latent's shape {tuple(x.shape)}")
+        if tuple(mask.shape[-2:]) != (hl, wl) or mask.numel() not in (hl * wl, n_img * hl * wl):
+            raise _lib.DkHipError(f"guided_cfg_step: mask {tuple(mask.shape)} is neither [{hl}, {wl}] (shared) nor [{n_img}, {hl}, {wl}] (per image)")
+        per_image = _mask_per_image(mask.numel(), hl * wl, n_img, "guided_cfg_step")
+    if m is not None:
+        _require_cuda(m, "m", torch.float32)
+        if m.shape != x.shape:
+            raise _lib.DkHipError(f"m {tuple(m.shape)} must have the latent's shape {tuple(x.shape)}")
+    ws_bytes = 0
+    if workspace is not None:
+        _require_cuda(workspace, "workspace")
+        ws_bytes = workspace.numel() * workspace.element_size()
+    _lib.check(getattr(_lib.load(), name)(*args, _ptr(x_orig), _ptr(noise), _ptr(mask), per_image, GUIDANCE_MODES[mode], float(rescale), float(eta),
+                                          float(norm_threshold), float(momentum), int(bool(reads_m)), int(bool(writes_m)), _ptr(m),
+                                          _ptr(workspace), ws_bytes, _stream()), name)
+
+
 def mask_to_latent(mask: Tensor, factor: int = 8) -> Tensor:
     """dk_mask_to_latent_f32: uint8 [n_mask, H, W] (or [H, W]) -> f32 [n_mask, H / factor, W / factor], box sum / (factor^2 * 255)."""
     _require_cuda(mask, "mask", torch.uint8)

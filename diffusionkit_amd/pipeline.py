@@ -16,6 +16,10 @@ step's own launch (dk_euler_cfg_step_masked), and ``generate_image`` pastes the 
 Samplers (``sampler=``, keyword-only, no reference counterpart): "euler" (default: the reference's loop, ``sample_euler``), "heun" and "ab2" run
 ``sample_steps`` over the rows of ``sampler.step_plan`` -- one launch of dk_lms_cfg_step (or its masked form) behind every model evaluation.
 
+Guidance (``guidance=``, ``guidance_interval=`` and the mode parameters, keyword-only, no reference counterpart; models that run with CFG): "cfg"
+(default: today's combine), "rescale" and "apg" replace the step launch of ``sample_steps`` by dk_guided_cfg_step, and an interval runs the evaluations
+outside it on the prompt rows alone (``_set_rows``).  The definitions are ``sampler.guide_reference``'s.
+
 All arithmetic runs in libdk_hip.so on the current HIP stream; numpy is used exactly where the
 reference uses it (the seeded noise draw, __init__.py:553-557) and for O(num_steps) schedule
 scalars.
@@ -34,7 +38,8 @@ import torch
 from . import _lib
 from .config import (MMDIT_CKPT, MODEL_CONFIG, T5_MAX_LENGTH, MMDiTConfig, VAEDecoderConfig, VAEEncoderConfig)
 from .engine import MMDiTEngine, VAEDecoderEngine, VAEEncoderEngine, _stream
-from .sampler import FluxSampler, ModelSamplingDiscreteFlow, check_sampler, get_sigmas, max_denoise, step_plan
+from .sampler import (FluxSampler, ModelSamplingDiscreteFlow, check_guidance, check_interval, check_sampler, get_sigmas, guidance_rows, max_denoise,
+                      step_plan)
 from .weights import pack_mmdit, pack_vae, synth_mmdit_weights, synth_vae_encoder_weights, synth_vae_weights
 
 logger = logging.getLogger(__name__)
@@ -352,6 +357,12 @@ class DiffusionPipeline:
         mask_path=None,
         block_cache=None,
         sampler=None,
+        guidance=None,
+        guidance_rescale: float = 0.7,
+        apg_eta: float = 0.0,
+        apg_norm_threshold: float = 0.0,
+        apg_momentum: float = 0.0,
+        guidance_interval=None,
     ):
         """mlx/__init__.py:253-292.  ``seed`` may be a list: one image per seed is denoised in a
         single batched step loop (data-parallel sharding hands each rank a list).
@@ -366,7 +377,16 @@ class DiffusionPipeline:
         ``sampler``: None or "euler" (the reference's first-order loop, today's launches and bits), "heun" (second order, two model evaluations
         per step but the last) or "ab2" (second order, one evaluation per step, the previous step's direction kept in an fp32 buffer); every
         composition above works with them, except that "heun" refuses ``block_cache`` (see ``sample_steps``).  ``self.last_sampler`` says what
-        ran: {"sampler", "model_evals"}.  Their order is checked on an analytic problem (profiles/samplers.md), not on a trained checkpoint."""
+        ran: {"sampler", "model_evals"}.  Their order is checked on an analytic problem (profiles/samplers.md), not on a trained checkpoint.
+        ``guidance`` (models with ``cfg_weight > 0``): None or "cfg" (neg + w (pos - neg), today's launches and bits), "rescale" (the same, scaled by
+        ``guidance_rescale`` * std(pos) / std(cfg) + 1 - ``guidance_rescale`` per image) or "apg" (adaptive projected guidance on the x0 predictions:
+        ``apg_eta`` weighs the component parallel to the prompt prediction, ``apg_norm_threshold`` > 0 clips the norm of the direction per image,
+        ``apg_momentum`` carries it over the guided evaluations in an fp32 buffer); the definitions are ``sampler.guide_reference``'s.
+        ``guidance_interval`` = (lo, hi): only evaluations with lo <= sigma <= hi are guided; the others run the prompt rows alone, the engine
+        re-prepared for half the batch at every change.  Any of these options goes through ``sample_steps`` (Euler as its plan) and raises with
+        ``cfg_weight <= 0``.  ``self.last_guidance`` says what ran: the mode, its parameters, the interval and the guided / unguided evaluation
+        counts.  The modes are verified as arithmetic only: no setting has been validated on a trained checkpoint here."""
+        guide = _guidance_options(guidance, guidance_rescale, apg_eta, apg_norm_threshold, apg_momentum, guidance_interval, cfg_weight)
         if mask_path is not None and image_path is None:
             raise ValueError("mask_path needs image_path: the mask says which part of that image to keep")
         sampler = check_sampler(sampler)
@@ -400,10 +420,12 @@ class DiffusionPipeline:
             extra_args["noise"] = torch.from_numpy(np.ascontiguousarray(noise, dtype=np.float32)).to(self.device)
         if block_cache is not None:
             extra_args["block_cache"] = block_cache
+        if guide is not None:
+            extra_args["guidance"] = guide
         noise_scaled = self.sampler.noise_scaling(np.float32(sigmas[0]), noise, x_T, self.max_denoise(sigmas))
         x0 = torch.from_numpy(np.ascontiguousarray(noise_scaled, dtype=np.float32)).to(self.device)
         denoiser = CFGDenoiser(self)
-        if sampler == "euler":
+        if sampler == "euler" and guide is None:
             latent, iter_time = sample_euler(denoiser, x0, sigmas, extra_args=extra_args)
             evals = len(iter_time)
         else:
@@ -412,6 +434,8 @@ class DiffusionPipeline:
             evals = len(plan)
         self.last_sampler = {"sampler": sampler, "model_evals": evals}
         self.last_block_cache = denoiser.block_cache_record
+        self.last_guidance = denoiser.guidance_record or dict(_DEFAULT_GUIDANCE, guided_evals=evals if cfg_weight > 0 else 0,
+                                                              unguided_evals=0 if cfg_weight > 0 else evals)
         latent = self.latent_format.process_out(latent)
         return latent, iter_time
 
@@ -431,11 +455,19 @@ class DiffusionPipeline:
         composite: bool = True,
         block_cache=None,
         sampler=None,
+        guidance=None,
+        guidance_rescale: float = 0.7,
+        apg_eta: float = 0.0,
+        apg_norm_threshold: float = 0.0,
+        apg_momentum: float = 0.0,
+        guidance_interval=None,
     ):
         """mlx/__init__.py:294-534: returns (PIL.Image, log).  ``mask_path``: inpainting, see ``denoise_latents``; with ``composite`` the pixels
         the mask keeps are pasted back from the input image after decoding (the VAE round trip alone does not reproduce them).
         ``block_cache``: first-block cache, see ``denoise_latents``; its record goes to ``log["denoising"]["block_cache"]``.
-        ``sampler``: "euler" (default) | "heun" | "ab2", see ``denoise_latents``; ``log["denoising"]["sampler"]`` and ``["model_evals"]`` say what ran."""
+        ``sampler``: "euler" (default) | "heun" | "ab2", see ``denoise_latents``; ``log["denoising"]["sampler"]`` and ``["model_evals"]`` say what ran.
+        ``guidance``, ``guidance_rescale``, ``apg_eta``, ``apg_norm_threshold``, ``apg_momentum``, ``guidance_interval``: see ``denoise_latents``; with any
+        of them set, ``log["denoising"]["guidance"]`` is ``self.last_guidance``."""
         if mask_path is not None and image_path is None:
             raise ValueError("mask_path needs image_path: the mask says which part of that image to keep")
         assert latent_size[0] % 2 == 0, f"Height must be divisible by 16 ({latent_size[0]*8}/16={latent_size[0]/2})"
@@ -468,7 +500,8 @@ class DiffusionPipeline:
         latents, iter_time = self.denoise_latents(
             conditioning, pooled_conditioning, num_steps=num_steps, cfg_weight=cfg_weight,
             latent_size=latent_size, seed=seed, image_path=image_path, denoise=denoise, mask_path=mask_path, block_cache=block_cache,
-            sampler=sampler)
+            sampler=sampler, guidance=guidance, guidance_rescale=guidance_rescale, apg_eta=apg_eta, apg_norm_threshold=apg_norm_threshold,
+            apg_momentum=apg_momentum, guidance_interval=guidance_interval)
         torch.cuda.synchronize(dev)
         log["denoising"]["post"] = mem()
         log["peak_memory"] = max(log["peak_memory"], log["denoising"]["post"]["peak_memory"])
@@ -477,6 +510,8 @@ class DiffusionPipeline:
         log["denoising"].update(self.last_sampler)
         if block_cache is not None:
             log["denoising"]["block_cache"] = self.last_block_cache
+        if any(self.last_guidance[k] != v for k, v in _DEFAULT_GUIDANCE.items()):  # (a key only when an option is set)
+            log["denoising"]["guidance"] = self.last_guidance
 
         torch.cuda.reset_peak_memory_stats(dev)
         t0 = time.time()
@@ -642,6 +677,7 @@ class CFGDenoiser:
         self.model = model
         self._timesteps: List[float] = []
         self.block_cache_record = None  # what sample_euler decided per step under extra_args["block_cache"]
+        self.guidance_record = None  # what sample_steps ran under extra_args["guidance"]
 
     def cache_modulation_params(self, pooled_text_embeddings, timesteps):
         self._timesteps = [float(t) for t in timesteps]
@@ -719,6 +755,28 @@ _HEUN_BLOCK_CACHE = ("sampler 'heun' cannot run together with block_cache: its t
                      "decide(step, n_steps, rel); a policy for two-evaluation steps is out of scope -- use sampler 'ab2' (one evaluation per step)")
 
 
+_DEFAULT_GUIDANCE = {"mode": "cfg", "guidance_rescale": 0.7, "apg_eta": 0.0, "apg_norm_threshold": 0.0, "apg_momentum": 0.0, "interval": None}
+
+
+def _guidance_options(guidance, rescale, eta, norm_threshold, momentum, interval, cfg_weight):
+    """The guidance keywords of ``denoise_latents`` -> None when they are all at their defaults (the loops run as they always did), else the dict
+    ``sample_steps`` takes as ``extra_args["guidance"]``.  Refused: an unknown mode, a parameter that is not finite, a rescale factor outside
+    [0, 1], an interval that is not lo <= hi, and any non-default option without classifier-free guidance (``cfg_weight <= 0``: FLUX)."""
+    opts = {"mode": check_guidance(guidance), "guidance_rescale": float(rescale), "apg_eta": float(eta), "apg_norm_threshold": float(norm_threshold),
+            "apg_momentum": float(momentum), "interval": None if interval is None else check_interval(interval)}
+    for k in ("guidance_rescale", "apg_eta", "apg_norm_threshold", "apg_momentum"):
+        if not np.isfinite(opts[k]):
+            raise ValueError(f"{k} must be finite, got {opts[k]}")
+    if not 0.0 <= opts["guidance_rescale"] <= 1.0:
+        raise ValueError(f"guidance_rescale must lie in [0, 1], got {opts['guidance_rescale']}")
+    if opts == _DEFAULT_GUIDANCE:
+        return None
+    if not cfg_weight > 0:
+        raise ValueError("the guidance options (guidance, guidance_rescale, apg_*, guidance_interval) need classifier-free guidance: cfg_weight is "
+                         f"{cfg_weight}, so there is no negative prediction to combine (FLUX runs without one)")
+    return opts
+
+
 class _Loop(NamedTuple):
     """what a step loop works on once the engine is prepared (``_loop_setup``)"""
     pipe: object
@@ -734,11 +792,15 @@ class _Loop(NamedTuple):
     noise: Optional[Tensor]
     tok: Tensor
     out: Tensor
+    conditioning: Tensor
+    pooled: Tensor
+    timesteps: object
 
 
-def _loop_setup(model: "CFGDenoiser", x: Tensor, sigmas, extra_args) -> _Loop:
+def _loop_setup(model: "CFGDenoiser", x: Tensor, sigmas, extra_args, guided: bool = True) -> _Loop:
     """The part of a step loop in front of its first step: conditioning rows in the engine's batch layout, timesteps, the engine prepared with its
-    modulation table and cached context, the fp32 copy of the latent, the inpainting operands and the first patchified tokens."""
+    modulation table and cached context, the fp32 copy of the latent, the inpainting operands and the first patchified tokens.
+    ``guided`` False (a guidance interval that leaves out the first evaluation): the engine starts on the prompt rows alone, ``_set_rows``'s state."""
     extra_args = {} if extra_args is None else dict(extra_args)
     pipe = model.model
     mm = pipe.mmdit
@@ -765,9 +827,10 @@ def _loop_setup(model: "CFGDenoiser", x: Tensor, sigmas, extra_args) -> _Loop:
         from .sampler import BlockCachePolicy
         policy = BlockCachePolicy(policy)
     mm.enable_block_cache(policy is not None)  # (off: the engine's workspace and launches are what they are without the feature)
-    mm.prepare(rows, x.shape[1:3], conditioning.shape[1], len(timesteps))
-    model.cache_modulation_params(pooled, timesteps)
-    mm.cache_context(conditioning)  # context_embedder is step-invariant (the reference recomputes it in every call, mmdit.py:195)
+    now = rows if guided else n_img  # ([prompt x n_img, negative x n_img]: the prompt rows come first)
+    mm.prepare(now, x.shape[1:3], conditioning.shape[1], len(timesteps))
+    model.cache_modulation_params(pooled[:now], timesteps)
+    mm.cache_context(conditioning[:now])  # context_embedder is step-invariant (the reference recomputes it in every call, mmdit.py:195)
 
     x = x.to(torch.float32).contiguous().clone()
     mask = extra_args.get("mask")
@@ -778,8 +841,19 @@ def _loop_setup(model: "CFGDenoiser", x: Tensor, sigmas, extra_args) -> _Loop:
                              f"noise {tuple(noise.shape)}, mask {tuple(mask.shape)}")
     else:
         x_orig = noise = None
-    tok = mm.patchify(x, dup=2 if cfg_on else 1)
-    return _Loop(pipe, mm, sigmas, cfg_weight, cfg_on, n_img, policy, x, mask, x_orig, noise, tok, torch.empty_like(tok))
+    tok = mm.patchify(x, dup=2 if cfg_on and guided else 1)
+    return _Loop(pipe, mm, sigmas, cfg_weight, cfg_on, n_img, policy, x, mask, x_orig, noise, tok, torch.empty_like(tok), conditioning, pooled, timesteps)
+
+
+def _set_rows(model: "CFGDenoiser", lp: _Loop, guided: bool):
+    """A guidance interval begins or ends: the engine re-prepared for both CFG rows of every image or for the prompt rows alone, its modulation table
+    and context cached again for those rows, x patchified with the matching ``dup`` -> (tok, out)."""
+    now = lp.n_img * (2 if guided else 1)
+    lp.mm.prepare(now, lp.x.shape[1:3], lp.conditioning.shape[1], len(lp.timesteps))
+    model.cache_modulation_params(lp.pooled[:now].contiguous(), lp.timesteps)
+    lp.mm.cache_context(lp.conditioning[:now].contiguous())
+    tok = lp.mm.patchify(lp.x, dup=2 if guided else 1)
+    return tok, torch.empty_like(tok)
 
 
 def sample_euler(model: CFGDenoiser, x: Tensor, sigmas, extra_args=None):
@@ -792,7 +866,7 @@ def sample_euler(model: CFGDenoiser, x: Tensor, sigmas, extra_args=None):
     First-block cache: ``extra_args["block_cache"]`` (a float threshold or a policy object, ``sampler.BlockCachePolicy``) turns a step into
     the engine's head, the read of its probe (the step's decision needs it on the host: a synchronisation), and the tail the policy chose;
     the record of the decisions goes to ``model.block_cache_record``."""
-    pipe, mm, sigmas, cfg_weight, cfg_on, n_img, policy, x, mask, x_orig, noise, tok, out = _loop_setup(model, x, sigmas, extra_args)
+    pipe, mm, sigmas, cfg_weight, cfg_on, n_img, policy, x, mask, x_orig, noise, tok, out = _loop_setup(model, x, sigmas, extra_args)[:13]
     if mask is not None:
         from . import ops
         pcfg = pipe.mmdit_config
@@ -839,34 +913,66 @@ def sample_steps(model: CFGDenoiser, x: Tensor, sigmas, plan, extra_args=None):
     Same operands and ``extra_args`` as ``sample_euler``, inpainting and the first-block cache included: the masked launch blends at the row's
     sigma_next (on Heun's predictor row too, so that the corrector's evaluation sees the re-imposed region), and a plan of one evaluation per
     step (ab2) hands the policy the same step indices as the Euler loop.  A plan with two evaluations in a step (heun) refuses ``block_cache``.
-    ``iter_time`` has one entry per step -- a Heun step's covers both evaluations -- with one device synchronisation per step."""
+    ``iter_time`` has one entry per step -- a Heun step's covers both evaluations -- with one device synchronisation per step.
+    Guidance: ``extra_args["guidance"]`` (the dict of ``_guidance_options``) replaces the step launch of a guided evaluation by dk_guided_cfg_step
+    (two small launches for the per-image moments, then the step) for "rescale" and "apg", and under an interval runs the evaluations outside it
+    on the prompt rows alone: where the guidedness changes, ``_set_rows`` re-prepares the engine, the first-block cache (if on) is reset and that
+    evaluation computes whatever the policy says, and the update is dk_lms_cfg_step with cfg_on = 0 on the first n_img token rows.  APG's momentum
+    buffer is allocated here and never initialised: the first guided evaluation of a stretch does not read it.  What ran goes to
+    ``model.guidance_record``."""
     from . import ops
     from .sampler import block_cache_rel
     plan = list(plan)
-    pipe, mm, sigmas, cfg_weight, cfg_on, n_img, policy, x, mask, x_orig, noise, tok, out = _loop_setup(model, x, sigmas, extra_args)
+    guide = None if extra_args is None else extra_args.get("guidance")
+    grows = guidance_rows(plan, None if guide is None else guide["interval"])
+    lp = _loop_setup(model, x, sigmas, extra_args, guided=grows[0].guided if grows else True)
+    pipe, mm, sigmas, cfg_weight, cfg_on, n_img, policy, x, mask, x_orig, noise, tok, out = lp[:13]
+    if guide is not None and not cfg_on:
+        raise ValueError("extra_args['guidance'] needs classifier-free guidance (cfg_weight > 0)")
     if policy is not None and not all(r.ends_step for r in plan):
         raise ValueError(_HEUN_BLOCK_CACHE)
     if any(not 0 <= r.index < len(sigmas) - 1 for r in plan):
         raise ValueError("the plan evaluates the model outside the schedule (or at its last entry): build it with sampler.step_plan on these sigmas")
     pcfg = pipe.mmdit_config
     hist = torch.empty_like(x) if any(r.reads_h or r.writes_h for r in plan) else None  # (never initialised: no row reads it before one wrote it)
+    mode = "cfg" if guide is None else guide["mode"]
+    beta = 0.0 if guide is None else guide["apg_momentum"]
+    gws = mbuf = None
+    if mode != "cfg" and any(g.guided for g in grows):  # (the moments' partials and scalars: caller-owned, never initialised)
+        gws = torch.empty(ops.guidance_workspace_bytes(*x.shape), dtype=torch.uint8, device=x.device)
+    if mode == "apg" and beta != 0.0 and any(g.feeds for g in grows):
+        mbuf = torch.empty_like(x)  # (never initialised: the first guided row of a stretch does not read it)
     n_steps = sum(r.ends_step for r in plan)
     record = {"threshold": getattr(policy, "threshold", None), "computed": [], "skipped": [], "rel": []}
     iter_time = []
     step, t0 = 0, None
-    for r in plan:
+    on = cfg_on and (grows[0].guided if grows else True)  # whether the engine holds both CFG rows of every image
+    fresh = False  # the engine was re-prepared: the first-block cache holds nothing to reuse
+    for r, g in zip(plan, grows):
         t0 = time.perf_counter() if t0 is None else t0
+        if cfg_on and g.guided != on:
+            on = g.guided
+            tok, out = _set_rows(model, lp, on)
+            if policy is not None:
+                mm.reset_block_cache()
+                fresh = True
         if policy is None:
             mm.forward_tokens(tok, None, r.index, tokens_out=out)
         else:
             rel = block_cache_rel(mm.forward_head(tok, None, r.index).cpu().tolist())  # (.cpu(): the step's synchronisation point)
-            skip = bool(policy.decide(step, n_steps, rel))
+            skip = bool(policy.decide(step, n_steps, rel)) and not fresh
+            fresh = False
             mm.forward_tail(r.index, skip, tokens_out=out)
             record["skipped" if skip else "computed"].append(step)
             record["rel"].append(rel)
-        args = (x, out, tok, n_img, cfg_on, pcfg.patch_size, int(pcfg.patchify_via_reshape), r.sigma, r.sigma_next, cfg_weight, hist,
+        args = (x, out, tok, n_img, on, pcfg.patch_size, int(pcfg.patchify_via_reshape), r.sigma, r.sigma_next, cfg_weight, hist,
                 (r.cx, r.cd, r.ch, r.hx, r.hd), r.reads_h, r.writes_h)
-        if mask is None:
+        if on and mode != "cfg":
+            kw = {} if mask is None else dict(x_orig=x_orig, noise=noise, mask=mask)
+            ops.guided_cfg_step(*args, mode=mode, workspace=gws, rescale=guide["guidance_rescale"], eta=guide["apg_eta"],
+                                norm_threshold=guide["apg_norm_threshold"], momentum=beta, reads_m=mbuf is not None and not g.first,
+                                writes_m=mbuf is not None and g.feeds, m=mbuf, **kw)
+        elif mask is None:
             ops.lms_cfg_step(*args)
         else:
             ops.lms_cfg_step_masked(*args, x_orig, noise, mask)
@@ -876,5 +982,8 @@ def sample_steps(model: CFGDenoiser, x: Tensor, sigmas, plan, extra_args=None):
             step, t0 = step + 1, None
     if policy is not None:
         model.block_cache_record = record
+    if guide is not None:
+        n_g = sum(g.guided for g in grows)
+        model.guidance_record = dict(guide, guided_evals=n_g, unguided_evals=len(grows) - n_g)
     model.clear_cache()
     return x, iter_time

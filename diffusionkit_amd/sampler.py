@@ -159,6 +159,77 @@ def step_plan(name, sigmas) -> List[StepRow]:
     return rows
 
 
+# ---- guidance modes: how the two predictions of a guided evaluation are combined (no reference counterpart) ---------------------------------
+GUIDANCE = ("cfg", "rescale", "apg")
+
+
+def check_guidance(name) -> str:
+    """None -> "cfg"; an unknown name raises a ValueError that lists the valid ones"""
+    if name is None:
+        return "cfg"
+    if name not in GUIDANCE:
+        raise ValueError(f"unknown guidance mode {name!r}: valid modes are {', '.join(GUIDANCE)}")
+    return name
+
+
+def check_interval(interval):
+    """None -> (0, inf), which guides every evaluation; otherwise (lo, hi) with lo <= hi, neither NaN, as float32 values"""
+    if interval is None:
+        return 0.0, math.inf
+    lo, hi = (float(_F(v)) for v in interval)
+    if not lo <= hi:
+        raise ValueError(f"guidance_interval must be (lo, hi) with lo <= hi, got ({lo}, {hi})")
+    return lo, hi
+
+
+def guide_reference(c, u, w, mode="cfg", *, rescale=0.7, eta=0.0, norm_threshold=0.0, momentum=0.0, m=None, reads_m=False, writes_m=False):
+    """The statement of the guidance modes, in float64 numpy: ``c`` and ``u`` [n_img, ...] are the x0 predictions of the prompt and the negative
+    row, w the guidance weight; every mean, norm and inner product is taken per image, over all of its elements.  Returns (den, m').
+      cfg      den = u + w (c - u)
+      rescale  g = u + w (c - u);  s = phi std(c) / std(g) + (1 - phi), s = 1 if std(g) == 0;  den = g s       (Lin et al. 2023, section 3.4)
+      apg      D = (c - u) + beta m under ``reads_m``, else c - u;  m' = D under ``writes_m``;  a = min(1, r / |D|), a = 1 if r <= 0 or |D| == 0;
+               b = (1 - eta) a <D, c> / <c, c>, b = 0 if <c, c> == 0;  den = c + (w - 1)(a D - b c)               (Sadat et al. 2024)
+    phi = ``rescale``, r = ``norm_threshold``, beta = ``momentum``.  m' is ``m`` itself (None allowed) where the row does not write it."""
+    mode = check_guidance(mode)
+    c, u, w = np.asarray(c, dtype=np.float64), np.asarray(u, dtype=np.float64), float(w)
+    ax = tuple(range(1, c.ndim))
+    per = lambda v: np.asarray(v, dtype=np.float64).reshape((-1,) + (1,) * (c.ndim - 1))  # noqa: E731
+    if mode == "cfg":
+        return u + w * (c - u), m
+    if mode == "rescale":
+        phi = float(rescale)
+        g = u + w * (c - u)
+        sc, sg = c.std(axis=ax), g.std(axis=ax)
+        s = np.where(sg == 0.0, 1.0, phi * sc / np.where(sg == 0.0, 1.0, sg) + (1.0 - phi))
+        return g * per(s), m
+    delta = c - u
+    if reads_m:
+        delta = delta + float(momentum) * np.asarray(m, dtype=np.float64)
+    m_new = delta.copy() if writes_m else m
+    nd = np.sqrt((delta * delta).sum(axis=ax))
+    r = float(norm_threshold)
+    a = np.where((nd == 0.0) | (r <= 0.0), 1.0, np.minimum(1.0, r / np.where(nd == 0.0, 1.0, nd)))
+    cc = (c * c).sum(axis=ax)
+    b = np.where(cc == 0.0, 0.0, (1.0 - float(eta)) * a * (delta * c).sum(axis=ax) / np.where(cc == 0.0, 1.0, cc))
+    return c + (w - 1.0) * (per(a) * delta - per(b) * c), m_new
+
+
+class GuidedRow(NamedTuple):
+    """``guided``: the evaluation runs both rows and combines them; ``first``: it is the first guided evaluation of its stretch (it does not read
+    the momentum buffer); ``feeds``: the next evaluation is guided too (this one leaves the momentum buffer for it)"""
+    guided: bool
+    first: bool
+    feeds: bool
+
+
+def guidance_rows(plan, interval=None) -> List[GuidedRow]:
+    """One entry per row of a ``step_plan``: guided iff lo <= sigma <= hi, compared in float32 on the sigma the row's model evaluation runs at
+    (Heun's corrector: its own).  None guides every row."""
+    lo, hi = check_interval(interval)
+    g = [bool(_F(lo) <= _F(r.sigma) <= _F(hi)) for r in plan]
+    return [GuidedRow(g[k], g[k] and (k == 0 or not g[k - 1]), g[k] and k + 1 < len(g) and g[k + 1]) for k in range(len(g))]
+
+
 # ---- first-block cache: which steps compute and which reuse (host policy; no reference counterpart) -------------------------
 def block_cache_rel(probe) -> float:
     """``probe``: (num, den) per batch row as ``MMDiTEngine.forward_head`` returns them, on the host -> the relative change of block 0's

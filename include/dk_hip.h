@@ -419,6 +419,40 @@ int dk_lms_cfg_step_masked_f16(float* x, const void* model_out, int32_t ld_out, 
                                int32_t writes_h, const float* x_orig, const float* noise, const float* mask,
                                int32_t mask_per_image, void* stream);
 
+/* Guidance modes (no reference counterpart): dk_lms_cfg_step with the combination of the two predictions chosen by mode.  With
+ * c = xb - o_text * sigma and u = xb - o_neg * sigma formed as dk_lms_cfg_step forms them (fp32), w = cfg_weight, every sum and norm
+ * taken per image over its Hl * Wl * C elements:
+ *   mode 0 (cfg)      den = u + w (c - u): dk_lms_cfg_step / _masked itself, no other launch; workspace and m are not touched.
+ *   mode 1 (rescale)  g = u + w (c - u);  s = phi * std(c) / std(g) + (1 - phi)  (s = 1 if std(g) == 0);  den = g * s.
+ *                     phi == 0 gives s == 1.0f and the bits of mode 0.
+ *   mode 2 (apg)      D = (c - u) + beta * m under reads_m, else c - u;  m' = D under writes_m;
+ *                     a = min(1, r / |D|)  (a = 1 if r <= 0 or |D| == 0);  b = (1 - eta) a <D, c> / <c, c>  (b = 0 if <c, c> == 0);
+ *                     den = c + (w - 1)(a D - b c).
+ * Everything behind den is dk_lms_cfg_step's: d = (x - den) / sigma, the coefficient row, hist, the blend, the tokens in both copies.
+ * x_orig, noise, mask: all null (no blend) or all set (dk_lms_cfg_step_masked's blend).
+ * m: f32 shaped like x, caller-owned; read only under reads_m (it may be uninitialised otherwise), written only under writes_m, may be
+ * null when both are 0; modes 0 and 1 ignore it and both flags.
+ * Modes 1 and 2 run two small launches in front of the step: per-workgroup partial sums (fp32 in the lanes, a fixed butterfly over the
+ * wave, fp64 from there on; a workgroup never spans two images), then one wave per image that folds them in a fixed order into the
+ * scalars s or (a, b) -- no floating-point atomics, the same bits on every run.  Partials and scalars live in workspace: caller-owned
+ * device memory of at least dk_guidance_workspace_bytes(n_img, Hl, Wl, C) bytes, 8-byte aligned, which need not be initialised.
+ * Refused with a dk_last_error() text, nothing written: cfg_on == 0, an unknown mode, phi outside [0, 1], a non-finite phi / eta / r /
+ * beta / cfg_weight, a null m under a set flag (mode 2), a null or short workspace (modes 1 and 2), and whatever dk_lms_cfg_step refuses.
+ * _f16: model_out and tokens are fp16. */
+size_t dk_guidance_workspace_bytes(int32_t n_img, int32_t Hl, int32_t Wl, int32_t C);
+int dk_guided_cfg_step(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on, int32_t Hl,
+                       int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma, float cfg_weight, float* hist, float cx,
+                       float cd, float ch, float hx, float hd, float sigma_next, int32_t reads_h, int32_t writes_h,
+                       const float* x_orig, const float* noise, const float* mask, int32_t mask_per_image, int32_t mode, float phi,
+                       float eta, float r, float beta, int32_t reads_m, int32_t writes_m, float* m, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int dk_guided_cfg_step_f16(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on, int32_t Hl,
+                           int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma, float cfg_weight, float* hist,
+                           float cx, float cd, float ch, float hx, float hd, float sigma_next, int32_t reads_h, int32_t writes_h,
+                           const float* x_orig, const float* noise, const float* mask, int32_t mask_per_image, int32_t mode,
+                           float phi, float eta, float r, float beta, int32_t reads_m, int32_t writes_m, float* m, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 /* Inpainting mask, pixels -> latent cells: mask u8 [n_mask,H,W] (255 = repaint, 0 = keep) -> f32 [n_mask,H/f,W/f],
  * (integer sum of the f x f block) / (f * f * 255) by a true division: an all-0 block gives 0.0f, an all-255 block 1.0f.
  * H and W must be multiples of f (the pipeline passes the VAE's factor, 8). */
