@@ -133,9 +133,16 @@ class dk_attention_plan_t(C.Structure):  # (o8_split is read by dk_attention_pla
     _fields_ = [(n, C.c_int32) for n in ("kernel", "qfuse", "blocks", "whole", "split", "jobs", "merge", "quantize", "launches", "n_cu", "o8_split")]
 
 
-# dk_lms_cfg_step*: x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, cfg_weight, hist, the five coefficients,
-# sigma_next, reads_h, writes_h (then the mask operands of the masked entries, then the stream)
-_LMS_ARGS = [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _i32]
+# the step entries (dk_euler / dk_lms / dk_guided _cfg_step, their masked and _f16 forms), composed: x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl,
+# C, p, reshape_order, sigma; then Euler's sigma_next, cfg_weight, or the row's cfg_weight, hist, five coefficients, sigma_next, reads_h, writes_h; then
+# the mask operands x_orig, noise, mask, mask_per_image; then mode, phi, eta, r, beta, reads_m, writes_m, m, workspace, its bytes; then the stream
+_STEP_HEAD = [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32]
+_STEP_EULER = _STEP_HEAD + [_f32, _f32]
+_STEP_ROW = _STEP_HEAD + [_f32, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _i32]
+_STEP_MASK = [_vp, _vp, _vp, _i32]
+_STEP_GUIDE = [_i32, _f32, _f32, _f32, _f32, _i32, _i32, _vp, _vp, _sz]
+_STEP_ENTRIES = {"dk_euler_cfg_step": _STEP_EULER, "dk_euler_cfg_step_masked": _STEP_EULER + _STEP_MASK, "dk_lms_cfg_step": _STEP_ROW,
+                 "dk_lms_cfg_step_masked": _STEP_ROW + _STEP_MASK, "dk_guided_cfg_step": _STEP_ROW + _STEP_MASK + _STEP_GUIDE}
 SIGNATURES = {
     "dk_abi_version": (_i32, []),
     "dk_last_error": (C.c_char_p, []),
@@ -179,27 +186,16 @@ SIGNATURES = {
     "dk_qk_norm_rope_f16": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _f32, _vp, _i32, _i32, _i32, _vp]),
     "dk_timestep_embedding_f16": (_i32, [_vp, _i32, _i32, _f32, _i32, _vp, _vp]),
     "dk_latent_to_tokens_f16": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
-    "dk_euler_cfg_step_f16": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _vp]),
     "dk_mmdit_set_activation_dtype": (_i32, [_vp, _i32]),
     "dk_ln_modulate_bf16": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp]),
     "dk_qk_norm_rope_bf16": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _f32, _vp, _i32, _i32, _i32, _vp]),
     "dk_rope_table_f32": (_i32, [_vp, _i32, _i32, _i32, C.POINTER(_i32), _i32, _f32, _vp]),
     "dk_timestep_embedding_bf16": (_i32, [_vp, _i32, _i32, _f32, _i32, _vp, _vp]),
     "dk_latent_to_tokens": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
-    "dk_euler_cfg_step": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _vp]),
-    # inpainting: the masked step (bf16 / fp16 tokens), the mask's pixels -> latent cells, the paste-back of the kept pixels
-    "dk_euler_cfg_step_masked": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _vp, _vp, _vp, _i32, _vp]),
-    "dk_euler_cfg_step_masked_f16": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _vp, _vp, _vp, _i32,
-                                            _vp]),
-    # second-order samplers: the step as a coefficient row over a history buffer, plain and masked
-    "dk_lms_cfg_step": (_i32, _LMS_ARGS + [_vp]),
-    "dk_lms_cfg_step_f16": (_i32, _LMS_ARGS + [_vp]),
-    "dk_lms_cfg_step_masked": (_i32, _LMS_ARGS + [_vp, _vp, _vp, _i32, _vp]),
-    "dk_lms_cfg_step_masked_f16": (_i32, _LMS_ARGS + [_vp, _vp, _vp, _i32, _vp]),
-    # guidance modes: dk_lms_cfg_step's list, the (nullable) mask operands, then mode, phi, eta, r, beta, reads_m, writes_m, m, workspace, its bytes
+    # the step tail: Euler, the coefficient row of the second-order samplers, the guidance modes (mask operands nullable); plain / masked, bf16 / fp16
+    **{name + f16: (_i32, args + [_vp]) for name, args in _STEP_ENTRIES.items() for f16 in ("", "_f16")},
     "dk_guidance_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
-    "dk_guided_cfg_step": (_i32, _LMS_ARGS + [_vp, _vp, _vp, _i32, _i32, _f32, _f32, _f32, _f32, _i32, _i32, _vp, _vp, _sz, _vp]),
-    "dk_guided_cfg_step_f16": (_i32, _LMS_ARGS + [_vp, _vp, _vp, _i32, _i32, _f32, _f32, _f32, _f32, _i32, _i32, _vp, _vp, _sz, _vp]),
+    # inpainting: the mask's pixels -> latent cells, the paste-back of the kept pixels
     "dk_mask_to_latent_f32": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "dk_image_composite_u8": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "dk_affine_f32": (_i32, [_vp, _vp, _i64, _f32, _f32, _vp]),

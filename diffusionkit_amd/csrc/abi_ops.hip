@@ -405,131 +405,127 @@ extern "C" int dk_latent_to_tokens_f16(const float* x, void* tokens, int32_t n_i
   return latent_to_tokens(DK_DTYPE_F16, x, tokens, n_img, dup, Hl, Wl, C, p, reshape_order, stream);
 }
 
-static int euler_cfg_step(int dtype, float* x, const void* model_out, int ld_out, void* tokens, int n_img, int cfg_on, int Hl, int Wl, int C, int p,
-                          int reshape_order, float sigma, float sigma_next, float cfg_weight, void* stream) {
+// ---- the step tail: ten entries (Euler, coefficient row, guided; plain and masked; bf16 and fp16) over one parameter block, one check, one launcher
+// Every requirement of a step launch.  The guided entries' own come first, then the common ones, so that a call that breaks one rule is told what it
+// always was; the structured binding gives the fields the names the messages quote.
+static int check_step(const StepParams& s) {
+  const auto& [x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight, has_row, cx, cd, ch, hx, hd,
+               hist, reads_h, writes_h, masked, x_orig, noise, mask, mask_per_image, guided, mode, phi, eta, r, beta, m, reads_m, writes_m, workspace,
+               workspace_bytes] = s;
+  if (guided) {
+    DK_REQUIRE(cfg_on != 0, "guidance modes combine two predictions: cfg_on must be set (an unguided row is dk_lms_cfg_step with cfg_on = 0)");
+    DK_REQUIRE(mode >= 0 && mode <= 2, "unknown guidance mode (0 cfg, 1 rescale, 2 apg)");
+    DK_REQUIRE(std::isfinite(phi) && std::isfinite(eta) && std::isfinite(r) && std::isfinite(beta) && std::isfinite(cfg_weight),
+               "the guidance parameters must be finite");
+    DK_REQUIRE(phi >= 0.0f && phi <= 1.0f, "the rescale factor phi must lie in [0, 1]");
+    DK_REQUIRE(C > 0 && Hl > 0 && Wl > 0, "the latent size must be positive");
+  }
   DK_REQUIRE(sigma != 0.0f, "sigma must be non-zero");
-  return DK_EL(dtype, dk_launch_euler_step)(x, (const bf16_t*)model_out, ld_out, (bf16_t*)tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order,
-                                            sigma, sigma_next, cfg_weight, S_(stream));
+  DK_REQUIRE(p > 0 && Hl % p == 0 && Wl % p == 0, "latent size must be divisible by the patch size");
+  if (!has_row && masked) DK_REQUIRE(x && model_out && tokens && x_orig && noise && mask, "null argument");  // (dk_euler_cfg_step_masked's wording)
+  DK_REQUIRE(x && model_out && tokens, "null argument");
+  DK_REQUIRE(n_img > 0, "n_img must be positive");
+  if (has_row) {
+    DK_REQUIRE(hist || !(reads_h || writes_h), "hist is null while the row reads or writes the history");
+    const float coef[5] = {cx, cd, ch, hx, hd};
+    for (float v : coef) DK_REQUIRE(std::isfinite(v), "the coefficients of the row must be finite");
+    DK_REQUIRE(std::isfinite(sigma) && std::isfinite(sigma_next), "sigma and sigma_next must be finite");
+  }
+  if (masked) DK_REQUIRE(x_orig && noise && mask, "null argument");
+  if (mode != 0) {
+    DK_REQUIRE(m || !(reads_m || writes_m), "the momentum buffer M is null while the row reads or writes it");
+    DK_REQUIRE(workspace && workspace_bytes >= dk_guidance_workspace_size(n_img, Hl, Wl, C),
+               "the guidance workspace is null or shorter than dk_guidance_workspace_bytes");
+  }
+  return 0;
+}
+static int step(int dtype, const StepParams& s, void* stream) {
+  const int rc = check_step(s);
+  return rc ? rc : DK_EL(dtype, dk_launch_step)(s, S_(stream));
+}
+// the fields the entries' arguments name, group by group (StepParams, dk_elem_launchers.h); whatever an entry does not name stays zero
+static StepParams step_operands(float* x, const void* model_out, int ld_out, void* tokens, int n_img, int cfg_on, int Hl, int Wl, int C, int p,
+                                int reshape_order, float sigma, float sigma_next, float cfg_weight) {
+  StepParams s = {};
+  s.x = x, s.model_out = (const bf16_t*)model_out, s.ld_out = ld_out, s.tok = (bf16_t*)tokens, s.n_img = n_img, s.cfg_on = cfg_on;
+  s.Hl = Hl, s.Wl = Wl, s.C = C, s.p = p, s.reshape_order = reshape_order, s.sigma = sigma, s.sigma_next = sigma_next, s.cfg_weight = cfg_weight;
+  return s;
+}
+static StepParams with_row(StepParams s, float* hist, float cx, float cd, float ch, float hx, float hd, int reads_h, int writes_h) {
+  s.has_row = true, s.hist = hist, s.cx = cx, s.cd = cd, s.ch = ch, s.hx = hx, s.hd = hd, s.reads_h = reads_h != 0, s.writes_h = writes_h != 0;
+  return s;
+}
+static StepParams with_blend(StepParams s, bool masked, const float* x_orig, const float* noise, const float* mask, int mask_per_image) {
+  s.masked = masked, s.x_orig = x_orig, s.noise = noise, s.mask = mask, s.mask_per_image = mask_per_image != 0;
+  return s;
+}
+// (the momentum flags count under APG alone)
+static StepParams with_guidance(StepParams s, int mode, float phi, float eta, float r, float beta, int reads_m, int writes_m, float* m, void* workspace,
+                                size_t workspace_bytes) {
+  s.guided = true, s.mode = mode, s.phi = phi, s.eta = eta, s.r = r, s.beta = beta, s.m = m, s.workspace = workspace, s.workspace_bytes = workspace_bytes;
+  s.reads_m = mode == 2 && reads_m != 0, s.writes_m = mode == 2 && writes_m != 0;
+  return s;
 }
 extern "C" int dk_euler_cfg_step(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on,
                                  int32_t Hl, int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma,
                                  float sigma_next, float cfg_weight, void* stream) {
-  return euler_cfg_step(DK_DTYPE_BF16, x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight, stream);
+  return step(DK_DTYPE_BF16, step_operands(x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight),
+              stream);
 }
 extern "C" int dk_euler_cfg_step_f16(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on,
                                      int32_t Hl, int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma,
                                      float sigma_next, float cfg_weight, void* stream) {
-  return euler_cfg_step(DK_DTYPE_F16, x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight, stream);
-}
-
-static int euler_cfg_step_masked(int dtype, float* x, const void* model_out, int ld_out, void* tokens, int n_img, int cfg_on, int Hl, int Wl, int C,
-                                 int p, int reshape_order, float sigma, float sigma_next, float cfg_weight, const float* x_orig,
-                                 const float* noise, const float* mask, int mask_per_image, void* stream) {
-  DK_REQUIRE(sigma != 0.0f, "sigma must be non-zero");
-  DK_REQUIRE(p > 0 && Hl % p == 0 && Wl % p == 0, "latent size must be divisible by the patch size");
-  DK_REQUIRE(x && model_out && tokens && x_orig && noise && mask, "null argument");
-  DK_REQUIRE(n_img > 0, "n_img must be positive");
-  return DK_EL(dtype, dk_launch_euler_step_masked)(x, (const bf16_t*)model_out, ld_out, (bf16_t*)tokens, n_img, cfg_on, Hl, Wl, C, p,
-                                                   reshape_order, sigma, sigma_next, cfg_weight, x_orig, noise, mask, mask_per_image != 0,
-                                                   S_(stream));
+  return step(DK_DTYPE_F16, step_operands(x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight),
+              stream);
 }
 extern "C" int dk_euler_cfg_step_masked(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on,
                                         int32_t Hl, int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma,
                                         float sigma_next, float cfg_weight, const float* x_orig, const float* noise, const float* mask,
                                         int32_t mask_per_image, void* stream) {
-  return euler_cfg_step_masked(DK_DTYPE_BF16, x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next,
-                               cfg_weight, x_orig, noise, mask, mask_per_image, stream);
+  const StepParams s = step_operands(x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight);
+  return step(DK_DTYPE_BF16, with_blend(s, true, x_orig, noise, mask, mask_per_image), stream);
 }
 extern "C" int dk_euler_cfg_step_masked_f16(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on,
                                             int32_t Hl, int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma,
                                             float sigma_next, float cfg_weight, const float* x_orig, const float* noise,
                                             const float* mask, int32_t mask_per_image, void* stream) {
-  return euler_cfg_step_masked(DK_DTYPE_F16, x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next,
-                               cfg_weight, x_orig, noise, mask, mask_per_image, stream);
+  const StepParams s = step_operands(x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight);
+  return step(DK_DTYPE_F16, with_blend(s, true, x_orig, noise, mask, mask_per_image), stream);
 }
 
 // second-order samplers: the step as a coefficient row (x' = cx x + cd d + ch H, H' = hx x + hd d); masked = the inpainting blend behind it
-static int lms_cfg_step(int dtype, bool masked, float* x, const void* model_out, int ld_out, void* tokens, int n_img, int cfg_on, int Hl, int Wl,
-                        int C, int p, int reshape_order, float sigma, float cfg_weight, float* hist, float cx, float cd, float ch, float hx,
-                        float hd, float sigma_next, int reads_h, int writes_h, const float* x_orig, const float* noise, const float* mask,
-                        int mask_per_image, void* stream) {
-  DK_REQUIRE(sigma != 0.0f, "sigma must be non-zero");
-  DK_REQUIRE(p > 0 && Hl % p == 0 && Wl % p == 0, "latent size must be divisible by the patch size");
-  DK_REQUIRE(x && model_out && tokens, "null argument");
-  DK_REQUIRE(n_img > 0, "n_img must be positive");
-  DK_REQUIRE(hist || !(reads_h || writes_h), "hist is null while the row reads or writes the history");
-  const float coef[5] = {cx, cd, ch, hx, hd};
-  for (float v : coef) DK_REQUIRE(std::isfinite(v), "the coefficients of the row must be finite");
-  DK_REQUIRE(std::isfinite(sigma) && std::isfinite(sigma_next), "sigma and sigma_next must be finite");
-  if (masked) DK_REQUIRE(x_orig && noise && mask, "null argument");
-  return DK_EL(dtype, dk_launch_lms_step)(x, (const bf16_t*)model_out, ld_out, (bf16_t*)tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma,
-                                          sigma_next, cfg_weight, hist, coef, reads_h != 0, writes_h != 0, masked ? x_orig : nullptr,
-                                          masked ? noise : nullptr, masked ? mask : nullptr, mask_per_image != 0, S_(stream));
-}
 extern "C" int dk_lms_cfg_step(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on, int32_t Hl, int32_t Wl,
                                int32_t C, int32_t p, int32_t reshape_order, float sigma, float cfg_weight, float* hist, float cx, float cd,
                                float ch, float hx, float hd, float sigma_next, int32_t reads_h, int32_t writes_h, void* stream) {
-  return lms_cfg_step(DK_DTYPE_BF16, false, x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, cfg_weight, hist, cx, cd,
-                      ch, hx, hd, sigma_next, reads_h, writes_h, nullptr, nullptr, nullptr, 0, stream);
+  const StepParams s = step_operands(x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight);
+  return step(DK_DTYPE_BF16, with_row(s, hist, cx, cd, ch, hx, hd, reads_h, writes_h), stream);
 }
 extern "C" int dk_lms_cfg_step_f16(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on, int32_t Hl,
                                    int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma, float cfg_weight, float* hist, float cx,
                                    float cd, float ch, float hx, float hd, float sigma_next, int32_t reads_h, int32_t writes_h, void* stream) {
-  return lms_cfg_step(DK_DTYPE_F16, false, x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, cfg_weight, hist, cx, cd,
-                      ch, hx, hd, sigma_next, reads_h, writes_h, nullptr, nullptr, nullptr, 0, stream);
+  const StepParams s = step_operands(x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight);
+  return step(DK_DTYPE_F16, with_row(s, hist, cx, cd, ch, hx, hd, reads_h, writes_h), stream);
 }
 extern "C" int dk_lms_cfg_step_masked(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on, int32_t Hl,
                                       int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma, float cfg_weight, float* hist,
                                       float cx, float cd, float ch, float hx, float hd, float sigma_next, int32_t reads_h, int32_t writes_h,
                                       const float* x_orig, const float* noise, const float* mask, int32_t mask_per_image, void* stream) {
-  return lms_cfg_step(DK_DTYPE_BF16, true, x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, cfg_weight, hist, cx, cd,
-                      ch, hx, hd, sigma_next, reads_h, writes_h, x_orig, noise, mask, mask_per_image, stream);
+  const StepParams s = step_operands(x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight);
+  return step(DK_DTYPE_BF16, with_blend(with_row(s, hist, cx, cd, ch, hx, hd, reads_h, writes_h), true, x_orig, noise, mask, mask_per_image), stream);
 }
 extern "C" int dk_lms_cfg_step_masked_f16(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on, int32_t Hl,
                                           int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma, float cfg_weight, float* hist,
                                           float cx, float cd, float ch, float hx, float hd, float sigma_next, int32_t reads_h, int32_t writes_h,
                                           const float* x_orig, const float* noise, const float* mask, int32_t mask_per_image, void* stream) {
-  return lms_cfg_step(DK_DTYPE_F16, true, x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, cfg_weight, hist, cx, cd,
-                      ch, hx, hd, sigma_next, reads_h, writes_h, x_orig, noise, mask, mask_per_image, stream);
+  const StepParams s = step_operands(x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight);
+  return step(DK_DTYPE_F16, with_blend(with_row(s, hist, cx, cd, ch, hx, hd, reads_h, writes_h), true, x_orig, noise, mask, mask_per_image), stream);
 }
 
-// guidance modes: the coefficient-row step behind the per-image moments of the two predictions (mode 0: dk_lms_cfg_step itself)
+// guidance modes: the coefficient-row step behind the per-image moments of the two predictions (mode 0: dk_lms_cfg_step itself); masked iff a
+// mask operand is given
 extern "C" size_t dk_guidance_workspace_bytes(int32_t n_img, int32_t Hl, int32_t Wl, int32_t C) {
   if (n_img <= 0 || Hl <= 0 || Wl <= 0 || C <= 0) return 0;
   return dk_guidance_workspace_size(n_img, Hl, Wl, C);
-}
-static int guided_cfg_step(int dtype, float* x, const void* model_out, int ld_out, void* tokens, int n_img, int cfg_on, int Hl, int Wl, int C, int p,
-                           int reshape_order, float sigma, float cfg_weight, float* hist, float cx, float cd, float ch, float hx, float hd,
-                           float sigma_next, int reads_h, int writes_h, const float* x_orig, const float* noise, const float* mask,
-                           int mask_per_image, int mode, float phi, float eta, float r, float beta, int reads_m, int writes_m, float* m,
-                           void* workspace, size_t workspace_bytes, void* stream) {
-  DK_REQUIRE(cfg_on != 0, "guidance modes combine two predictions: cfg_on must be set (an unguided row is dk_lms_cfg_step with cfg_on = 0)");
-  DK_REQUIRE(mode >= 0 && mode <= 2, "unknown guidance mode (0 cfg, 1 rescale, 2 apg)");
-  DK_REQUIRE(std::isfinite(phi) && std::isfinite(eta) && std::isfinite(r) && std::isfinite(beta) && std::isfinite(cfg_weight),
-             "the guidance parameters must be finite");
-  DK_REQUIRE(phi >= 0.0f && phi <= 1.0f, "the rescale factor phi must lie in [0, 1]");
-  DK_REQUIRE(C > 0 && Hl > 0 && Wl > 0, "the latent size must be positive");
-  const bool masked = x_orig || noise || mask;
-  if (mode == 0)
-    return lms_cfg_step(dtype, masked, x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, cfg_weight, hist, cx, cd, ch,
-                        hx, hd, sigma_next, reads_h, writes_h, x_orig, noise, mask, mask_per_image, stream);
-  DK_REQUIRE(sigma != 0.0f, "sigma must be non-zero");
-  DK_REQUIRE(p > 0 && Hl % p == 0 && Wl % p == 0, "latent size must be divisible by the patch size");
-  DK_REQUIRE(x && model_out && tokens, "null argument");
-  DK_REQUIRE(n_img > 0, "n_img must be positive");
-  DK_REQUIRE(hist || !(reads_h || writes_h), "hist is null while the row reads or writes the history");
-  const float coef[5] = {cx, cd, ch, hx, hd};
-  for (float v : coef) DK_REQUIRE(std::isfinite(v), "the coefficients of the row must be finite");
-  DK_REQUIRE(std::isfinite(sigma) && std::isfinite(sigma_next), "sigma and sigma_next must be finite");
-  if (masked) DK_REQUIRE(x_orig && noise && mask, "null argument");
-  if (mode != 2) reads_m = writes_m = 0;
-  DK_REQUIRE(m || !(reads_m || writes_m), "the momentum buffer M is null while the row reads or writes it");
-  DK_REQUIRE(workspace && workspace_bytes >= dk_guidance_workspace_size(n_img, Hl, Wl, C),
-             "the guidance workspace is null or shorter than dk_guidance_workspace_bytes");
-  const float gpar[4] = {phi, eta, r, beta};
-  return DK_EL(dtype, dk_launch_guided_step)(x, (const bf16_t*)model_out, ld_out, (bf16_t*)tokens, n_img, Hl, Wl, C, p, reshape_order, sigma,
-                                             sigma_next, cfg_weight, hist, coef, reads_h != 0, writes_h != 0, x_orig, noise, mask,
-                                             mask_per_image != 0, mode, gpar, reads_m != 0, writes_m != 0, m, workspace, S_(stream));
 }
 extern "C" int dk_guided_cfg_step(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on, int32_t Hl, int32_t Wl,
                                   int32_t C, int32_t p, int32_t reshape_order, float sigma, float cfg_weight, float* hist, float cx, float cd,
@@ -537,9 +533,9 @@ extern "C" int dk_guided_cfg_step(float* x, const void* model_out, int32_t ld_ou
                                   const float* noise, const float* mask, int32_t mask_per_image, int32_t mode, float phi, float eta, float r,
                                   float beta, int32_t reads_m, int32_t writes_m, float* m, void* workspace, size_t workspace_bytes,
                                   void* stream) {
-  return guided_cfg_step(DK_DTYPE_BF16, x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, cfg_weight, hist, cx, cd, ch,
-                         hx, hd, sigma_next, reads_h, writes_h, x_orig, noise, mask, mask_per_image, mode, phi, eta, r, beta, reads_m, writes_m, m,
-                         workspace, workspace_bytes, stream);
+  const StepParams s = step_operands(x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight);
+  const StepParams b = with_blend(with_row(s, hist, cx, cd, ch, hx, hd, reads_h, writes_h), x_orig || noise || mask, x_orig, noise, mask, mask_per_image);
+  return step(DK_DTYPE_BF16, with_guidance(b, mode, phi, eta, r, beta, reads_m, writes_m, m, workspace, workspace_bytes), stream);
 }
 extern "C" int dk_guided_cfg_step_f16(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on, int32_t Hl,
                                       int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma, float cfg_weight, float* hist, float cx,
@@ -547,9 +543,9 @@ extern "C" int dk_guided_cfg_step_f16(float* x, const void* model_out, int32_t l
                                       const float* x_orig, const float* noise, const float* mask, int32_t mask_per_image, int32_t mode, float phi,
                                       float eta, float r, float beta, int32_t reads_m, int32_t writes_m, float* m, void* workspace,
                                       size_t workspace_bytes, void* stream) {
-  return guided_cfg_step(DK_DTYPE_F16, x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, cfg_weight, hist, cx, cd, ch,
-                         hx, hd, sigma_next, reads_h, writes_h, x_orig, noise, mask, mask_per_image, mode, phi, eta, r, beta, reads_m, writes_m, m,
-                         workspace, workspace_bytes, stream);
+  const StepParams s = step_operands(x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight);
+  const StepParams b = with_blend(with_row(s, hist, cx, cd, ch, hx, hd, reads_h, writes_h), x_orig || noise || mask, x_orig, noise, mask, mask_per_image);
+  return step(DK_DTYPE_F16, with_guidance(b, mode, phi, eta, r, beta, reads_m, writes_m, m, workspace, workspace_bytes), stream);
 }
 
 extern "C" int dk_mask_to_latent_f32(const uint8_t* mask, float* out, int32_t n_mask, int32_t H, int32_t W, int32_t f, void* stream) {

@@ -28,31 +28,45 @@ int dk_launch_timestep_embedding(const float* t, int n, int rep, int dim, float 
 // latent [n_img, Hl, Wl, C] fp32 -> tokens [B, S_i, p*p*C] bf16 (B = n_img * dup)
 int dk_launch_latent_to_tokens(const float* x, bf16_t* tok, int n_img, int dup, int Hl, int Wl, int C, int p,
                                int reshape_order, hipStream_t stream);
-// fused x0-prediction + CFG + Euler update (+ re-patchify for the next step)
-int dk_launch_euler_step(float* x, const bf16_t* model_out, int ld_out, bf16_t* tok, int n_img, int cfg_on,
-                         int Hl, int Wl, int C, int p, int reshape_order, float sigma, float sigma_next,
-                         float cfg_weight, hipStream_t stream);
-// ... followed by the inpainting blend x = m * x_new + (1 - m) * (sigma_next * noise + (1 - sigma_next) * x_orig); x_orig, noise: f32 like x,
-// mask: f32 [n_img or 1, Hl, Wl]
-int dk_launch_euler_step_masked(float* x, const bf16_t* model_out, int ld_out, bf16_t* tok, int n_img, int cfg_on,
-                                int Hl, int Wl, int C, int p, int reshape_order, float sigma, float sigma_next,
-                                float cfg_weight, const float* x_orig, const float* noise, const float* mask,
-                                int mask_per_image, hipStream_t stream);
-// the same tail with the update as a coefficient row over the fp32 history buffer hist (second-order samplers): d = (x - den) / sigma,
-// x' = coef[0] * x + coef[1] * d + coef[2] * hist (hist read only under reads_h), hist' = coef[3] * x + coef[4] * d (written only under
-// writes_h); mask non-null: followed by the inpainting blend at sigma_next
-int dk_launch_lms_step(float* x, const bf16_t* model_out, int ld_out, bf16_t* tok, int n_img, int cfg_on, int Hl, int Wl, int C, int p,
-                       int reshape_order, float sigma, float sigma_next, float cfg_weight, float* hist, const float* coef, int reads_h,
-                       int writes_h, const float* x_orig, const float* noise, const float* mask, int mask_per_image, hipStream_t stream);
-// guidance modes (include/dk_hip.h): the per-image moments of the two predictions (two launches: partial sums per workgroup, then one wave
-// per image folds them in fp64 into the scalars), then the coefficient-row step with den = g * s (mode 1, rescale) or c + (w - 1)(a D - b c)
-// (mode 2, APG; m: the fp32 momentum buffer, read under reads_m, written under writes_m).  gpar = (phi, eta, r, beta); workspace: at least
-// dk_guidance_workspace_size bytes, 8-byte aligned.  CFG is on by definition.
+// The step-loop tail: x0 prediction + CFG + update of x (+ re-patchify for the next step), one launch -- behind two small ones under a guidance
+// mode.  All zeros but the operands = the plain Euler step with the CFG combine.  (One struct for both element types: the second inclusion
+// finds it at global scope.)
+#ifndef DK_STEP_PARAMS
+#define DK_STEP_PARAMS
+struct StepParams {
+  // operands: x f32 [n_img, Hl, Wl, C], the model's output and the tokens of the next step in the element type
+  float* x;
+  const bf16_t* model_out;
+  int ld_out;
+  bf16_t* tok;
+  int n_img, cfg_on, Hl, Wl, C, p, reshape_order;
+  float sigma, sigma_next, cfg_weight;
+  // update.  has_row false: x' = x + d (sigma_next - sigma), dk_euler_step_kernel.  True: dk_lms_step_kernel with d = (x - den) / sigma,
+  // x' = cx x + cd d + ch hist (hist, fp32 like x, read only under reads_h), hist' = hx x + hd d (written only under writes_h)
+  bool has_row;
+  float cx, cd, ch, hx, hd;
+  float* hist;
+  bool reads_h, writes_h;
+  // blend (masked; the entry says whether it promises one): x = m x' + (1 - m)(sigma_next noise + (1 - sigma_next) x_orig); x_orig, noise: f32
+  // like x, mask: f32 [n_img or 1, Hl, Wl]
+  bool masked;
+  const float *x_orig, *noise, *mask;
+  bool mask_per_image;
+  // guidance (include/dk_hip.h; guided: a dk_guided_* call, whose mode and parameters are checked and which needs cfg_on).  Mode 0 is the
+  // launch above.  Modes 1 / 2: the per-image moments of the two predictions in front (partial sums per workgroup, then one wave per image folds
+  // them in fp64 into the scalars), then the row step with den = g * s (1, rescale) or c + (w - 1)(a D - b c) (2, APG; m: the fp32 momentum
+  // buffer, read under reads_m, written under writes_m).  workspace: at least dk_guidance_workspace_size bytes, 8-byte aligned.
+  bool guided;
+  int mode;
+  float phi, eta, r, beta;
+  float* m;
+  bool reads_m, writes_m;
+  void* workspace;
+  size_t workspace_bytes;
+};
+#endif
 size_t dk_guidance_workspace_size(int n_img, int Hl, int Wl, int C);
-int dk_launch_guided_step(float* x, const bf16_t* model_out, int ld_out, bf16_t* tok, int n_img, int Hl, int Wl, int C, int p,
-                          int reshape_order, float sigma, float sigma_next, float cfg_weight, float* hist, const float* coef, int reads_h,
-                          int writes_h, const float* x_orig, const float* noise, const float* mask, int mask_per_image, int mode,
-                          const float* gpar, int reads_m, int writes_m, float* m, void* workspace, hipStream_t stream);
+int dk_launch_step(const StepParams& s, hipStream_t stream);
 // first-block cache (include/dk_hip.h): d = round(x - d) over M rows of x through the row map, (num, den) = (sum |d - d_ref|, sum |d_ref|) per
 // row into row_partials [M][2], then per rows_per_batch rows in a fixed order into probe [M / rows_per_batch][2]; d_ref null: read as zeros
 int dk_launch_block_probe(const bf16_t* x, int ldx, int x_seg_len, int x_seg_stride, bf16_t* d, const bf16_t* d_ref, float* row_partials,

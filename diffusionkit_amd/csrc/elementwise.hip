@@ -410,21 +410,52 @@ int dk_launch_image_composite_u8(const unsigned char* dec, const unsigned char* 
 __device__ __forceinline__ int patch_feature(int c, int ph, int pw, int C, int p, int reshape_order) {
   return reshape_order ? (c * p * p + ph * p + pw) : ((ph * p + pw) * C + c);
 }
+// The statements the patchify and step kernels share, written once.  The index r of an element inside its image's latent (long, or int where
+// the caller has checked the range) -> its cell, token and feature, and the token grid's sizes ...
+struct StepCell {
+  int img, yy, xx, t, f, S_i, F;
+};
+template <class I>
+__device__ __forceinline__ StepCell step_cell(int img, I r, int Hl, int Wl, int C, int p, int reshape_order) {
+  StepCell k;
+  k.img = img;
+  const int c = (int)(r % C);
+  r /= C;
+  k.xx = (int)(r % Wl), k.yy = (int)(r / Wl);
+  const int gw = Wl / p;
+  k.S_i = (Hl / p) * gw, k.F = p * p * C;
+  k.t = (k.yy / p) * gw + (k.xx / p);
+  k.f = patch_feature(c, k.yy % p, k.xx % p, C, p, reshape_order);
+  return k;
+}
+// ... the x0 prediction of batch row `row` at the element's token and feature: the value the denoiser saw minus sigma times the model's output
+// (this one and the blend take the cell's fields one by one: handed the StepCell, the moments kernel and the masked step kernels come out of
+// the compiler with their instructions in another order, and the objects' .text is held byte for byte, scripts/device_code_diff.py) ...
+__device__ __forceinline__ float step_den(const bf16_t* model_out, int ld_out, int row, int S_i, int t, int f, float xb, float sigma) {
+  return xb - to_f32(model_out[((size_t)row * S_i + t) * ld_out + f]) * sigma;
+}
+// ... the inpainting blend of the updated value with the known region re-noised to sigma_next (dk_euler_step_kernel's comment) ...
+__device__ __forceinline__ float step_blend(float xn, long i, int img, int yy, int xx, int Hl, int Wl, float sigma_next, const float* x_orig,
+                                            const float* noise, const float* mask, int mask_per_image) {
+  const float m = mask[(mask_per_image ? (long)img * Hl * Wl : 0) + (long)yy * Wl + xx];
+  const float known = sigma_next * noise[i] + (1.0f - sigma_next) * x_orig[i];
+  return m * xn + (1.0f - m) * known;
+}
+// ... and the store of the updated value: x in fp32, its rounding into the tokens of the prompt row and, under CFG, of the negative row.
+__device__ __forceinline__ void step_store(float* x, bf16_t* tok, long i, float xn, const StepCell& k, int n_img, int cfg_on) {
+  x[i] = xn;
+  const bf16_t nb = from_f32(xn);
+  tok[((size_t)k.img * k.S_i + k.t) * k.F + k.f] = nb;
+  if (cfg_on) tok[((size_t)(n_img + k.img) * k.S_i + k.t) * k.F + k.f] = nb;
+}
 __global__ void dk_latent_to_tokens_kernel(const float* x, bf16_t* tok, int n_img, int dup, int Hl, int Wl, int C, int p,
                                            int reshape_order) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long per_img = (long)Hl * Wl * C;
   if (i >= per_img * n_img) return;
-  const int img = (int)(i / per_img);
-  long r = i % per_img;
-  const int c = (int)(r % C);
-  r /= C;
-  const int xx = (int)(r % Wl), yy = (int)(r / Wl);
-  const int gw = Wl / p, S_i = (Hl / p) * gw, F = p * p * C;
-  const int t = (yy / p) * gw + (xx / p);
-  const int f = patch_feature(c, yy % p, xx % p, C, p, reshape_order);
+  const StepCell k = step_cell((int)(i / per_img), i % per_img, Hl, Wl, C, p, reshape_order);
   const bf16_t v = from_f32(x[i]);
-  for (int d = 0; d < dup; ++d) tok[((size_t)(d * n_img + img) * S_i + t) * F + f] = v;
+  for (int d = 0; d < dup; ++d) tok[((size_t)(d * n_img + k.img) * k.S_i + k.t) * k.F + k.f] = v;
 }
 int dk_launch_latent_to_tokens(const float* x, bf16_t* tok, int n_img, int dup, int Hl, int Wl, int C, int p, int reshape_order,
                                hipStream_t stream) {
@@ -454,65 +485,34 @@ __global__ void dk_euler_step_kernel(float* x, const bf16_t* model_out, int ld_o
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long per_img = (long)Hl * Wl * C;
   if (i >= per_img * n_img) return;
-  const int img = (int)(i / per_img);
-  long r = i % per_img;
-  const int c = (int)(r % C);
-  r /= C;
-  const int xx = (int)(r % Wl), yy = (int)(r / Wl);
-  const int gw = Wl / p, S_i = (Hl / p) * gw, F = p * p * C;
-  const int t = (yy / p) * gw + (xx / p);
-  const int f = patch_feature(c, yy % p, xx % p, C, p, reshape_order);
+  const StepCell k = step_cell((int)(i / per_img), i % per_img, Hl, Wl, C, p, reshape_order);
   const float xv = x[i];
   const float xb = round_act(xv);  // the value the denoiser saw
-  const float o_text = to_f32(model_out[((size_t)img * S_i + t) * ld_out + f]);
-  float den = xb - o_text * sigma;
+  float den = step_den(model_out, ld_out, k.img, k.S_i, k.t, k.f, xb, sigma);
   if (cfg_on) {
-    const float o_neg = to_f32(model_out[((size_t)(n_img + img) * S_i + t) * ld_out + f]);
-    const float den_neg = xb - o_neg * sigma;
+    const float den_neg = step_den(model_out, ld_out, n_img + k.img, k.S_i, k.t, k.f, xb, sigma);
     den = den_neg + cfg_weight * (den - den_neg);
   }
   const float d = (xv - den) / sigma;
   float xn = xv + d * (sigma_next - sigma);
   if constexpr (MASKED) {
-    const float m = mask[(mask_per_image ? (long)img * Hl * Wl : 0) + (long)yy * Wl + xx];
-    const float known = sigma_next * noise[i] + (1.0f - sigma_next) * x_orig[i];
-    xn = m * xn + (1.0f - m) * known;
+    xn = step_blend(xn, i, k.img, k.yy, k.xx, Hl, Wl, sigma_next, x_orig, noise, mask, mask_per_image);
   }
-  x[i] = xn;
-  const bf16_t nb = from_f32(xn);
-  tok[((size_t)img * S_i + t) * F + f] = nb;
-  if (cfg_on) tok[((size_t)(n_img + img) * S_i + t) * F + f] = nb;
-}
-int dk_launch_euler_step(float* x, const bf16_t* model_out, int ld_out, bf16_t* tok, int n_img, int cfg_on, int Hl, int Wl, int C,
-                         int p, int reshape_order, float sigma, float sigma_next, float cfg_weight, hipStream_t stream) {
-  const long n = (long)n_img * Hl * Wl * C;
-  hipLaunchKernelGGL(dk_euler_step_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, x, model_out, ld_out, tok,
-                     n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight, nullptr, nullptr, nullptr, 0);
-  DK_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-int dk_launch_euler_step_masked(float* x, const bf16_t* model_out, int ld_out, bf16_t* tok, int n_img, int cfg_on, int Hl, int Wl,
-                                int C, int p, int reshape_order, float sigma, float sigma_next, float cfg_weight, const float* x_orig,
-                                const float* noise, const float* mask, int mask_per_image, hipStream_t stream) {
-  const long n = (long)n_img * Hl * Wl * C;
-  hipLaunchKernelGGL(dk_euler_step_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, x, model_out, ld_out, tok,
-                     n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight, x_orig, noise, mask, mask_per_image);
-  DK_CHECK_HIP(hipGetLastError());
-  return 0;
+  step_store(x, tok, i, xn, k, n_img, cfg_on);
 }
 
 // ---------------------------------------------------------------------------------------------
 // Second-order samplers (Heun, Adams-Bashforth 2; no reference counterpart): the step-loop tail above with the update written as a
 // coefficient row over one fp32 history buffer H shaped like the latent,
 //   d = (x - den) / sigma,    x' = cx * x + cd * d + ch * H,    H' = hx * x + hd * d,
-// den formed exactly as dk_euler_step_kernel forms it (same round_act, CFG combine, addressing and rounding points).  The host writes
+// den formed as dk_euler_step_kernel forms it (step_den on the same round_act; the same CFG combine and rounding points).  The host writes
 // the rows (sampler.step_plan); sigma is the sigma the model was evaluated at, sigma_next the one the row's result lives at (only the
 // blend reads it).  reads_h == 0: H is not read (the caller never initialises it) and ch is ignored; writes_h == 0: H is not written.
 // A first-order row -- reads_h == 0 and cx == 1 -- is evaluated as the Euler expression itself, x + d * cd: with cd = sigma_next - sigma
 // (the fp32 difference dk_euler_step_kernel takes on the device) it is that kernel's statement on that kernel's operands, so x and the
 // tokens are its bits whether or not the compiler contracts the product into the sum; cx * x + d * cd would depend on which of the two
 // products a contraction swallows.  H' is taken from x BEFORE the update.
-// MASKED: dk_euler_step_kernel's two-product blend behind the update, known at sigma_next, with the same exact ends.
+// MASKED: dk_euler_step_kernel's two-product blend (step_blend) behind the update, known at sigma_next, with the same exact ends.
 // ---------------------------------------------------------------------------------------------
 struct LmsRow {
   float cx, cd, ch, hx, hd;
@@ -539,35 +539,25 @@ __global__ void dk_lms_step_kernel(float* x, const bf16_t* model_out, int ld_out
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long per_img = (long)Hl * Wl * C;
   if (i >= per_img * n_img) return;
-  const int img = (int)(i / per_img);
-  long r = i % per_img;
-  const int c = (int)(r % C);
-  r /= C;
-  const int xx = (int)(r % Wl), yy = (int)(r / Wl);
-  const int gw = Wl / p, S_i = (Hl / p) * gw, F = p * p * C;
-  const int t = (yy / p) * gw + (xx / p);
-  const int f = patch_feature(c, yy % p, xx % p, C, p, reshape_order);
+  const StepCell k = step_cell((int)(i / per_img), i % per_img, Hl, Wl, C, p, reshape_order);
   const float xv = x[i];
   const float xb = round_act(xv);  // the value the denoiser saw
-  const float o_text = to_f32(model_out[((size_t)img * S_i + t) * ld_out + f]);
-  float den = xb - o_text * sigma;
+  float den = step_den(model_out, ld_out, k.img, k.S_i, k.t, k.f, xb, sigma);
   if constexpr (GMODE == DK_GUIDE_CFG) {
     if (cfg_on) {
-      const float o_neg = to_f32(model_out[((size_t)(n_img + img) * S_i + t) * ld_out + f]);
-      const float den_neg = xb - o_neg * sigma;
+      const float den_neg = step_den(model_out, ld_out, n_img + k.img, k.S_i, k.t, k.f, xb, sigma);
       den = den_neg + cfg_weight * (den - den_neg);
     }
-  } else {  // (the launcher passes cfg_on = 1)
-    const float o_neg = to_f32(model_out[((size_t)(n_img + img) * S_i + t) * ld_out + f]);
-    const float den_neg = xb - o_neg * sigma;
+  } else {  // (cfg_on != 0: check_step)
+    const float den_neg = step_den(model_out, ld_out, n_img + k.img, k.S_i, k.t, k.f, xb, sigma);
     if constexpr (GMODE == DK_GUIDE_RESCALE) {
       const float g = den_neg + cfg_weight * (den - den_neg);
-      den = g * gd.scal[2 * img];
+      den = g * gd.scal[2 * k.img];
     } else {
       float dl = den - den_neg;
       if (gd.reads_m) dl = dl + gd.beta * gd.m[i];
       if (gd.writes_m) gd.m[i] = dl;
-      const float a = gd.scal[2 * img], b = gd.scal[2 * img + 1];
+      const float a = gd.scal[2 * k.img], b = gd.scal[2 * k.img + 1];
       den = den + (cfg_weight - 1.0f) * (a * dl - b * den);
     }
   }
@@ -581,36 +571,15 @@ __global__ void dk_lms_step_kernel(float* x, const bf16_t* model_out, int ld_out
     xn = row.cx * xv + d * row.cd;
   if (row.writes_h) hist[i] = row.hx * xv + row.hd * d;
   if constexpr (MASKED) {
-    const float m = mask[(mask_per_image ? (long)img * Hl * Wl : 0) + (long)yy * Wl + xx];
-    const float known = sigma_next * noise[i] + (1.0f - sigma_next) * x_orig[i];
-    xn = m * xn + (1.0f - m) * known;
+    xn = step_blend(xn, i, k.img, k.yy, k.xx, Hl, Wl, sigma_next, x_orig, noise, mask, mask_per_image);
   }
-  x[i] = xn;
-  const bf16_t nb = from_f32(xn);
-  tok[((size_t)img * S_i + t) * F + f] = nb;
-  if (cfg_on) tok[((size_t)(n_img + img) * S_i + t) * F + f] = nb;
-}
-int dk_launch_lms_step(float* x, const bf16_t* model_out, int ld_out, bf16_t* tok, int n_img, int cfg_on, int Hl, int Wl, int C, int p,
-                       int reshape_order, float sigma, float sigma_next, float cfg_weight, float* hist, const float* coef, int reads_h,
-                       int writes_h, const float* x_orig, const float* noise, const float* mask, int mask_per_image, hipStream_t stream) {
-  const long n = (long)n_img * Hl * Wl * C;
-  const LmsRow row = {coef[0], coef[1], coef[2], coef[3], coef[4], reads_h, writes_h};
-  const dim3 grid((unsigned)((n + 255) / 256));
-  const GuideArgs none = {nullptr, nullptr, 0.f, 0, 0};
-  if (mask)
-    hipLaunchKernelGGL(dk_lms_step_kernel<true>, grid, dim3(256), 0, stream, x, model_out, ld_out, tok, n_img, cfg_on, Hl, Wl, C, p,
-                       reshape_order, sigma, sigma_next, cfg_weight, hist, row, x_orig, noise, mask, mask_per_image, none);
-  else
-    hipLaunchKernelGGL(dk_lms_step_kernel<false>, grid, dim3(256), 0, stream, x, model_out, ld_out, tok, n_img, cfg_on, Hl, Wl, C, p,
-                       reshape_order, sigma, sigma_next, cfg_weight, hist, row, nullptr, nullptr, nullptr, 0, none);
-  DK_CHECK_HIP(hipGetLastError());
-  return 0;
+  step_store(x, tok, i, xn, k, n_img, cfg_on);
 }
 
 // ---------------------------------------------------------------------------------------------
 // Guidance moments (no reference counterpart): the per-image sums the guided step needs, and the scalars they end in.
 // Pass 1: grid (nb, n_img), 256 threads -- a workgroup never leaves its image.  Thread t of block b takes the elements b * 256 + t,
-// + nb * 256, ... of the image, in that order, forms c, u and g or D as dk_lms_step_kernel does and adds its terms in fp32; wave_sum
+// + nb * 256, ... of the image, in that order, forms c and u by step_den, g or D as dk_lms_step_kernel does, and adds its terms in fp32; wave_sum
 // folds the lanes in a fixed butterfly; the four wave partials go through LDS and thread 0 adds them in fp64, in wave order, into
 // part[img][b][4].  RESCALE: (sum c, sum g, sum c^2, sum g^2); APG: (sum D^2, sum D c, sum c^2, 0).
 // Pass 2: one wave per image, lane l adds blocks l, l + 64, ... in that order in fp64, a fixed butterfly folds the lanes, lane 0 writes
@@ -634,21 +603,14 @@ __global__ __launch_bounds__(256) void dk_guide_moments_kernel(const float* x, c
   __shared__ float wpart[4][4];
   const int img = blockIdx.y, nb = gridDim.x;
   const int per_img = Hl * Wl * C;  // (< 2^31: checked by the launcher)
-  const int gw = Wl / p, S_i = (Hl / p) * gw;
+  const int gw = Wl / p, S_i = (Hl / p) * gw;  // (step_cell's S_i, taken in front of the loop: inside it the instructions move)
   float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
   for (int j = (int)blockIdx.x * 256 + (int)threadIdx.x; j < per_img; j += nb * 256) {
     const long i = (long)img * per_img + j;
-    int r = j;
-    const int c = r % C;
-    r /= C;
-    const int xx = r % Wl, yy = r / Wl;
-    const int t = (yy / p) * gw + (xx / p);
-    const int f = patch_feature(c, yy % p, xx % p, C, p, reshape_order);
+    const StepCell k = step_cell(img, j, Hl, Wl, C, p, reshape_order);
     const float xb = round_act(x[i]);
-    const float o_text = to_f32(model_out[((size_t)img * S_i + t) * ld_out + f]);
-    const float o_neg = to_f32(model_out[((size_t)(n_img + img) * S_i + t) * ld_out + f]);
-    const float den = xb - o_text * sigma;
-    const float den_neg = xb - o_neg * sigma;
+    const float den = step_den(model_out, ld_out, img, S_i, k.t, k.f, xb, sigma);
+    const float den_neg = step_den(model_out, ld_out, n_img + img, S_i, k.t, k.f, xb, sigma);
     if constexpr (GMODE == DK_GUIDE_RESCALE) {
       const float g = den_neg + cfg_weight * (den - den_neg);
       s0 += den;
@@ -715,44 +677,49 @@ __global__ __launch_bounds__(64) void dk_guide_fold_kernel(const double* part, f
   }
   *(float2*)(scal + 2 * img) = make_float2(o0, o1);
 }
-int dk_launch_guided_step(float* x, const bf16_t* model_out, int ld_out, bf16_t* tok, int n_img, int Hl, int Wl, int C, int p,
-                          int reshape_order, float sigma, float sigma_next, float cfg_weight, float* hist, const float* coef, int reads_h,
-                          int writes_h, const float* x_orig, const float* noise, const float* mask, int mask_per_image, int mode,
-                          const float* gpar, int reads_m, int writes_m, float* m, void* workspace, hipStream_t stream) {
-  const long per_img = (long)Hl * Wl * C;
-  const long n = (long)n_img * per_img;
-  DK_REQUIRE(per_img < (1L << 31) - 1024L * 256, "the latent of one image must hold fewer than 2^31 elements");
-  DK_REQUIRE(((uintptr_t)workspace & 7) == 0, "the guidance workspace must be 8-byte aligned");
-  const int nb = guide_blocks(per_img);
-  double* part = (double*)workspace;
-  float* scal = (float*)(part + (size_t)n_img * nb * 4);
-  const float phi = gpar[0], eta = gpar[1], thr = gpar[2], beta = gpar[3];
-  const dim3 mgrid((unsigned)nb, (unsigned)n_img);
-  if (mode == DK_GUIDE_RESCALE) {
-    hipLaunchKernelGGL(dk_guide_moments_kernel<DK_GUIDE_RESCALE>, mgrid, dim3(256), 0, stream, x, model_out, ld_out, n_img, Hl, Wl, C, p,
-                       reshape_order, sigma, cfg_weight, nullptr, 0.f, 0, part);
-    DK_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(dk_guide_fold_kernel<DK_GUIDE_RESCALE>, dim3(n_img), dim3(64), 0, stream, part, scal, nb, (double)per_img, phi, eta,
-                       thr);
-  } else {
-    hipLaunchKernelGGL(dk_guide_moments_kernel<DK_GUIDE_APG>, mgrid, dim3(256), 0, stream, x, model_out, ld_out, n_img, Hl, Wl, C, p,
-                       reshape_order, sigma, cfg_weight, m, beta, reads_m, part);
-    DK_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(dk_guide_fold_kernel<DK_GUIDE_APG>, dim3(n_img), dim3(64), 0, stream, part, scal, nb, (double)per_img, phi, eta, thr);
-  }
-  DK_CHECK_HIP(hipGetLastError());
-  const LmsRow row = {coef[0], coef[1], coef[2], coef[3], coef[4], reads_h, writes_h};
-  const GuideArgs gd = {scal, m, beta, reads_m, writes_m};
+// The one launcher of the step tail (StepParams, dk_elem_launchers.h): the Euler kernel without a row, else the row kernel of the block's
+// (masked, mode), behind the two moments launches under modes 1 and 2.  What an instantiation does not read (the blend operands unmasked, gd
+// under mode 0) is passed as the block holds it.  The instantiations are named in the order the object has always held them: its .text is
+// compared byte for byte across host-only changes (scripts/device_code_diff.py).
+int dk_launch_step(const StepParams& s, hipStream_t stream) {
+  const long per_img = (long)s.Hl * s.Wl * s.C;
+  const long n = (long)s.n_img * per_img;
   const dim3 grid((unsigned)((n + 255) / 256));
-#define GUIDED_STEP(MASKED, GMODE)                                                                                                          \
-  hipLaunchKernelGGL((dk_lms_step_kernel<MASKED, GMODE>), grid, dim3(256), 0, stream, x, model_out, ld_out, tok, n_img, 1, Hl, Wl, C, p,     \
-                     reshape_order, sigma, sigma_next, cfg_weight, hist, row, x_orig, noise, mask, mask_per_image, gd)
-  if (mode == DK_GUIDE_RESCALE) {
-    if (mask) GUIDED_STEP(true, DK_GUIDE_RESCALE); else GUIDED_STEP(false, DK_GUIDE_RESCALE);
-  } else {
-    if (mask) GUIDED_STEP(true, DK_GUIDE_APG); else GUIDED_STEP(false, DK_GUIDE_APG);
+  if (!s.has_row) {
+    const auto kernel = !s.masked ? dk_euler_step_kernel<false> : dk_euler_step_kernel<true>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, s.x, s.model_out, s.ld_out, s.tok, s.n_img, s.cfg_on, s.Hl, s.Wl, s.C, s.p,
+                       s.reshape_order, s.sigma, s.sigma_next, s.cfg_weight, s.x_orig, s.noise, s.mask, (int)s.mask_per_image);
+    DK_CHECK_HIP(hipGetLastError());
+    return 0;
   }
-#undef GUIDED_STEP
+  auto kernel = s.masked ? dk_lms_step_kernel<true> : dk_lms_step_kernel<false>;
+  float* scal = nullptr;
+  if (s.mode != DK_GUIDE_CFG) {
+    void* const workspace = s.workspace;
+    DK_REQUIRE(per_img < (1L << 31) - 1024L * 256, "the latent of one image must hold fewer than 2^31 elements");
+    DK_REQUIRE(((uintptr_t)workspace & 7) == 0, "the guidance workspace must be 8-byte aligned");
+    const int nb = guide_blocks(per_img);
+    double* part = (double*)workspace;
+    scal = (float*)(part + (size_t)s.n_img * nb * 4);
+    const dim3 mgrid((unsigned)nb, (unsigned)s.n_img);
+    const bool rescale = s.mode == DK_GUIDE_RESCALE;
+    auto moments = dk_guide_moments_kernel<DK_GUIDE_RESCALE>;
+    auto fold = dk_guide_fold_kernel<DK_GUIDE_RESCALE>;
+    if (!rescale) moments = dk_guide_moments_kernel<DK_GUIDE_APG>, fold = dk_guide_fold_kernel<DK_GUIDE_APG>;
+    if (rescale)
+      kernel = s.masked ? dk_lms_step_kernel<true, DK_GUIDE_RESCALE> : dk_lms_step_kernel<false, DK_GUIDE_RESCALE>;
+    else
+      kernel = s.masked ? dk_lms_step_kernel<true, DK_GUIDE_APG> : dk_lms_step_kernel<false, DK_GUIDE_APG>;
+    hipLaunchKernelGGL(moments, mgrid, dim3(256), 0, stream, s.x, s.model_out, s.ld_out, s.n_img, s.Hl, s.Wl, s.C, s.p, s.reshape_order, s.sigma,
+                       s.cfg_weight, s.m, s.beta, (int)s.reads_m, part);
+    DK_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(fold, dim3(s.n_img), dim3(64), 0, stream, part, scal, nb, (double)per_img, s.phi, s.eta, s.r);
+    DK_CHECK_HIP(hipGetLastError());
+  }
+  const LmsRow row = {s.cx, s.cd, s.ch, s.hx, s.hd, s.reads_h, s.writes_h};
+  const GuideArgs gd = {scal, s.m, s.beta, s.reads_m, s.writes_m};
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, s.x, s.model_out, s.ld_out, s.tok, s.n_img, s.cfg_on, s.Hl, s.Wl, s.C, s.p, s.reshape_order,
+                     s.sigma, s.sigma_next, s.cfg_weight, s.hist, row, s.x_orig, s.noise, s.mask, (int)s.mask_per_image, gd);
   DK_CHECK_HIP(hipGetLastError());
   return 0;
 }

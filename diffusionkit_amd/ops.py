@@ -401,19 +401,6 @@ def timestep_embedding(t: Tensor, dim: int, max_period: float, embed_dtype: int,
     return out
 
 
-def euler_cfg_step(x: Tensor, model_out: Tensor, tokens: Tensor, n_img: int, cfg_on: bool, p: int, reshape_order: int, sigma: float,
-                   sigma_next: float, cfg_weight: float) -> None:
-    """dk_euler_cfg_step / _f16 by the dtype of ``model_out``: x f32 [n_img, Hl, Wl, C] updated in place, ``tokens`` (same dtype as
-    ``model_out``) receives the next step's patchified input."""
-    name = "dk_euler_cfg_step" + ("" if _elem(model_out.dtype, "euler_cfg_step") == "bf16" else "_f16")
-    _require_cuda(x, "x", torch.float32)
-    _require_cuda(model_out, "model_out")
-    _require_cuda(tokens, "tokens", model_out.dtype)
-    _, hl, wl, c = x.shape
-    _lib.check(getattr(_lib.load(), name)(x.data_ptr(), model_out.data_ptr(), model_out.shape[-1], tokens.data_ptr(), n_img, int(cfg_on), hl, wl, c,
-                                          p, reshape_order, float(sigma), float(sigma_next), float(cfg_weight), _stream()), name)
-
-
 def _mask_per_image(n: int, per_image: int, n_img: int, what: str) -> int:
     """0: one mask of ``per_image`` elements for all images, 1: one per image"""
     if n == per_image:
@@ -423,40 +410,77 @@ def _mask_per_image(n: int, per_image: int, n_img: int, what: str) -> int:
     raise ValueError(f"{what}: the mask holds {n} elements, expected {per_image} (shared) or {n_img} x {per_image} (per image)")
 
 
+GUIDANCE_MODES = {"cfg": 0, "rescale": 1, "apg": 2}
+
+
+def _step(what, x, model_out, tokens, n_img, cfg_on, p, reshape_order, sigma, sigma_next, cfg_weight, row=None, blend=None, blend_error=_lib.DkHipError,
+          guide=None) -> None:
+    """The one call of a step entry, dk_<what> / _f16 by the dtype of ``model_out`` (the argument groups of ``_lib._STEP_ENTRIES``): the operands, then
+    ``row`` = (hist, coef, reads_h, writes_h), ``blend`` = (x_orig, noise, mask) and ``guide`` = (mode, phi, eta, r, beta, reads_m, writes_m, m,
+    workspace) where the entry has them, each validated here.  ``blend_error``: what a mask operand of the wrong shape raises -- the Euler wrapper
+    says ValueError, in its own words, where the others say DkHipError."""
+    name = "dk_" + what + ("" if _elem(model_out.dtype, what) == "bf16" else "_f16")
+    if guide is not None and guide[0] not in GUIDANCE_MODES:
+        raise ValueError(f"unknown guidance mode {guide[0]!r}: valid modes are {', '.join(GUIDANCE_MODES)}")
+    _require_cuda(x, "x", torch.float32)
+    _require_cuda(model_out, "model_out")
+    _require_cuda(tokens, "tokens", model_out.dtype)
+    _, hl, wl, c = x.shape
+    if row is None:
+        tail = (float(sigma_next), float(cfg_weight))
+    else:
+        hist, coef, reads_h, writes_h = row
+        if hist is not None:
+            _require_cuda(hist, "hist", torch.float32)
+            if hist.shape != x.shape:
+                raise _lib.DkHipError(f"hist {tuple(hist.shape)} must have the latent's shape {tuple(x.shape)}")
+        cx, cd, ch, hx, hd = (float(v) for v in coef)
+        tail = (float(cfg_weight), _ptr(hist), cx, cd, ch, hx, hd, float(sigma_next), int(bool(reads_h)), int(bool(writes_h)))
+    if blend is not None:
+        x_orig, noise, mask = blend
+        for n, t in (("x_orig", x_orig), ("noise", noise), ("mask", mask)):
+            if t is None and guide is not None:  # (the only entry whose mask operands may be left out)
+                raise _lib.DkHipError(f"{what}: {n} is None while another mask operand is given")
+            _require_cuda(t, n, torch.float32)
+        if x_orig.shape != x.shape or noise.shape != x.shape:
+            raise blend_error(f"x_orig {tuple(x_orig.shape)} and noise {tuple(noise.shape)} must have the latent's shape {tuple(x.shape)}")
+        if blend_error is ValueError:  # (a mask of the wrong element count is ``_mask_per_image``'s ValueError)
+            if tuple(mask.shape[-2:]) != (hl, wl):
+                raise ValueError(f"mask {tuple(mask.shape)} does not end in the latent size {(hl, wl)}")
+        elif tuple(mask.shape[-2:]) != (hl, wl) or mask.numel() not in (hl * wl, n_img * hl * wl):
+            raise blend_error(f"{what}: mask {tuple(mask.shape)} is neither [{hl}, {wl}] (shared) nor [{n_img}, {hl}, {wl}] (per image)")
+        tail += (x_orig.data_ptr(), noise.data_ptr(), mask.data_ptr(), _mask_per_image(mask.numel(), hl * wl, n_img, what))
+    elif guide is not None:
+        tail += (None, None, None, 0)
+    if guide is not None:
+        mode, phi, eta, r, beta, reads_m, writes_m, m, workspace = guide
+        if m is not None:
+            _require_cuda(m, "m", torch.float32)
+            if m.shape != x.shape:
+                raise _lib.DkHipError(f"m {tuple(m.shape)} must have the latent's shape {tuple(x.shape)}")
+        ws_bytes = 0
+        if workspace is not None:
+            _require_cuda(workspace, "workspace")
+            ws_bytes = workspace.numel() * workspace.element_size()
+        tail += (GUIDANCE_MODES[mode], float(phi), float(eta), float(r), float(beta), int(bool(reads_m)), int(bool(writes_m)), _ptr(m),
+                 _ptr(workspace), ws_bytes)
+    _lib.check(getattr(_lib.load(), name)(x.data_ptr(), model_out.data_ptr(), model_out.shape[-1], tokens.data_ptr(), n_img, int(cfg_on), hl, wl, c, p,
+                                          reshape_order, float(sigma), *tail, _stream()), name)
+
+
+def euler_cfg_step(x: Tensor, model_out: Tensor, tokens: Tensor, n_img: int, cfg_on: bool, p: int, reshape_order: int, sigma: float,
+                   sigma_next: float, cfg_weight: float) -> None:
+    """dk_euler_cfg_step / _f16 by the dtype of ``model_out``: x f32 [n_img, Hl, Wl, C] updated in place, ``tokens`` (same dtype as
+    ``model_out``) receives the next step's patchified input."""
+    _step("euler_cfg_step", x, model_out, tokens, n_img, cfg_on, p, reshape_order, sigma, sigma_next, cfg_weight)
+
+
 def euler_cfg_step_masked(x: Tensor, model_out: Tensor, tokens: Tensor, n_img: int, cfg_on: bool, p: int, reshape_order: int, sigma: float,
                           sigma_next: float, cfg_weight: float, x_orig: Tensor, noise: Tensor, mask: Tensor) -> None:
     """dk_euler_cfg_step_masked / _f16 by the dtype of ``model_out``: ``euler_cfg_step``, then x = m * x_new + (1 - m) * (sigma_next * noise +
     (1 - sigma_next) * x_orig) in the same launch.  ``x_orig``, ``noise``: f32 like x; ``mask``: f32 [Hl, Wl] (shared) or [n_img, Hl, Wl]."""
-    name = "dk_euler_cfg_step_masked" + ("" if _elem(model_out.dtype, "euler_cfg_step_masked") == "bf16" else "_f16")
-    _require_cuda(x, "x", torch.float32)
-    _require_cuda(model_out, "model_out")
-    _require_cuda(tokens, "tokens", model_out.dtype)
-    for n, t in (("x_orig", x_orig), ("noise", noise), ("mask", mask)):
-        _require_cuda(t, n, torch.float32)
-    _, hl, wl, c = x.shape
-    if x_orig.shape != x.shape or noise.shape != x.shape:
-        raise ValueError(f"x_orig {tuple(x_orig.shape)} and noise {tuple(noise.shape)} must have the latent's shape {tuple(x.shape)}")
-    if tuple(mask.shape[-2:]) != (hl, wl):
-        raise ValueError(f"mask {tuple(mask.shape)} does not end in the latent size {(hl, wl)}")
-    per_image = _mask_per_image(mask.numel(), hl * wl, n_img, "euler_cfg_step_masked")
-    _lib.check(getattr(_lib.load(), name)(x.data_ptr(), model_out.data_ptr(), model_out.shape[-1], tokens.data_ptr(), n_img, int(cfg_on), hl, wl, c,
-                                          p, reshape_order, float(sigma), float(sigma_next), float(cfg_weight), x_orig.data_ptr(),
-                                          noise.data_ptr(), mask.data_ptr(), per_image, _stream()), name)
-
-
-def _lms_args(x: Tensor, model_out: Tensor, tokens: Tensor, n_img: int, cfg_on: bool, p: int, reshape_order: int, sigma: float, sigma_next: float,
-              cfg_weight: float, hist: Optional[Tensor], coef, reads_h: bool, writes_h: bool):
-    _require_cuda(x, "x", torch.float32)
-    _require_cuda(model_out, "model_out")
-    _require_cuda(tokens, "tokens", model_out.dtype)
-    if hist is not None:
-        _require_cuda(hist, "hist", torch.float32)
-        if hist.shape != x.shape:
-            raise _lib.DkHipError(f"hist {tuple(hist.shape)} must have the latent's shape {tuple(x.shape)}")
-    cx, cd, ch, hx, hd = (float(v) for v in coef)
-    _, hl, wl, c = x.shape
-    return (x.data_ptr(), model_out.data_ptr(), model_out.shape[-1], tokens.data_ptr(), n_img, int(cfg_on), hl, wl, c, p, reshape_order, float(sigma),
-            float(cfg_weight), _ptr(hist), cx, cd, ch, hx, hd, float(sigma_next), int(bool(reads_h)), int(bool(writes_h)))
+    _step("euler_cfg_step_masked", x, model_out, tokens, n_img, cfg_on, p, reshape_order, sigma, sigma_next, cfg_weight,
+          blend=(x_orig, noise, mask), blend_error=ValueError)
 
 
 def lms_cfg_step(x: Tensor, model_out: Tensor, tokens: Tensor, n_img: int, cfg_on: bool, p: int, reshape_order: int, sigma: float,
@@ -464,9 +488,7 @@ def lms_cfg_step(x: Tensor, model_out: Tensor, tokens: Tensor, n_img: int, cfg_o
     """dk_lms_cfg_step / _f16 by the dtype of ``model_out``: ``euler_cfg_step`` with the update as a coefficient row, ``coef`` = (cx, cd, ch, hx, hd):
     d = (x - den) / sigma, x = cx x + cd d + ch hist, hist = hx x + hd d.  ``hist``: f32 like x, read only under ``reads_h``, written only under
     ``writes_h`` (None when neither); the rows come from ``sampler.step_plan``."""
-    name = "dk_lms_cfg_step" + ("" if _elem(model_out.dtype, "lms_cfg_step") == "bf16" else "_f16")
-    args = _lms_args(x, model_out, tokens, n_img, cfg_on, p, reshape_order, sigma, sigma_next, cfg_weight, hist, coef, reads_h, writes_h)
-    _lib.check(getattr(_lib.load(), name)(*args, _stream()), name)
+    _step("lms_cfg_step", x, model_out, tokens, n_img, cfg_on, p, reshape_order, sigma, sigma_next, cfg_weight, row=(hist, coef, reads_h, writes_h))
 
 
 def lms_cfg_step_masked(x: Tensor, model_out: Tensor, tokens: Tensor, n_img: int, cfg_on: bool, p: int, reshape_order: int, sigma: float,
@@ -474,20 +496,8 @@ def lms_cfg_step_masked(x: Tensor, model_out: Tensor, tokens: Tensor, n_img: int
                         noise: Tensor, mask: Tensor) -> None:
     """dk_lms_cfg_step_masked / _f16: ``lms_cfg_step``, then the blend of ``euler_cfg_step_masked`` with the known region re-noised to
     ``sigma_next``, in the same launch."""
-    name = "dk_lms_cfg_step_masked" + ("" if _elem(model_out.dtype, "lms_cfg_step_masked") == "bf16" else "_f16")
-    args = _lms_args(x, model_out, tokens, n_img, cfg_on, p, reshape_order, sigma, sigma_next, cfg_weight, hist, coef, reads_h, writes_h)
-    for n, t in (("x_orig", x_orig), ("noise", noise), ("mask", mask)):
-        _require_cuda(t, n, torch.float32)
-    _, hl, wl, _ = x.shape
-    if x_orig.shape != x.shape or noise.shape != x.shape:
-        raise _lib.DkHipError(f"x_orig {tuple(x_orig.shape)} and noise {tuple(noise.shape)} must have the latent's shape {tuple(x.shape)}")
-    if tuple(mask.shape[-2:]) != (hl, wl) or mask.numel() not in (hl * wl, n_img * hl * wl):
-        raise _lib.DkHipError(f"lms_cfg_step_masked: mask {tuple(mask.shape)} is neither [{hl}, {wl}] (shared) nor [{n_img}, {hl}, {wl}] (per image)")
-    per_image = _mask_per_image(mask.numel(), hl * wl, n_img, "lms_cfg_step_masked")
-    _lib.check(getattr(_lib.load(), name)(*args, x_orig.data_ptr(), noise.data_ptr(), mask.data_ptr(), per_image, _stream()), name)
-
-
-GUIDANCE_MODES = {"cfg": 0, "rescale": 1, "apg": 2}
+    _step("lms_cfg_step_masked", x, model_out, tokens, n_img, cfg_on, p, reshape_order, sigma, sigma_next, cfg_weight,
+          row=(hist, coef, reads_h, writes_h), blend=(x_orig, noise, mask))
 
 
 def guidance_workspace_bytes(n_img: int, hl: int, wl: int, c: int) -> int:
@@ -505,33 +515,9 @@ def guided_cfg_step(x: Tensor, model_out: Tensor, tokens: Tensor, n_img: int, cf
     ``momentum`` beta, and the momentum buffer ``m``, f32 like x, read only under ``reads_m`` and written only under ``writes_m``); the definitions
     are ``sampler.guide_reference``'s.  ``workspace``: a device tensor of at least ``guidance_workspace_bytes(...)`` bytes, 8-byte aligned, never
     initialised by the caller (None for "cfg", which launches nothing else)."""
-    name = "dk_guided_cfg_step" + ("" if _elem(model_out.dtype, "guided_cfg_step") == "bf16" else "_f16")
-    if mode not in GUIDANCE_MODES:
-        raise ValueError(f"unknown guidance mode {mode!r}: valid modes are {', '.join(GUIDANCE_MODES)}")
-    args = _lms_args(x, model_out, tokens, n_img, cfg_on, p, reshape_order, sigma, sigma_next, cfg_weight, hist, coef, reads_h, writes_h)
-    _, hl, wl, _ = x.shape
-    per_image = 0
-    if x_orig is not None or noise is not None or mask is not None:
-        for n, t in (("x_orig", x_orig), ("noise", noise), ("mask", mask)):
-            if t is None:
-                raise _lib.DkHipError(f"guided_cfg_step: {n} is None while another mask operand is given")
-            _require_cuda(t, n, torch.float32)
-        if x_orig.shape != x.shape or noise.shape != x.shape:
-            raise _lib.DkHipError(f"x_orig {tuple(x_orig.shape)} and noise {tuple(noise.shape)} must have the latent's shape {tuple(x.shape)}")
-        if tuple(mask.shape[-2:]) != (hl, wl) or mask.numel() not in (hl * wl, n_img * hl * wl):
-            raise _lib.DkHipError(f"guided_cfg_step: mask {tuple(mask.shape)} is neither [{hl}, {wl}] (shared) nor [{n_img}, {hl}, {wl}] (per image)")
-        per_image = _mask_per_image(mask.numel(), hl * wl, n_img, "guided_cfg_step")
-    if m is not None:
-        _require_cuda(m, "m", torch.float32)
-        if m.shape != x.shape:
-            raise _lib.DkHipError(f"m {tuple(m.shape)} must have the latent's shape {tuple(x.shape)}")
-    ws_bytes = 0
-    if workspace is not None:
-        _require_cuda(workspace, "workspace")
-        ws_bytes = workspace.numel() * workspace.element_size()
-    _lib.check(getattr(_lib.load(), name)(*args, _ptr(x_orig), _ptr(noise), _ptr(mask), per_image, GUIDANCE_MODES[mode], float(rescale), float(eta),
-                                          float(norm_threshold), float(momentum), int(bool(reads_m)), int(bool(writes_m)), _ptr(m),
-                                          _ptr(workspace), ws_bytes, _stream()), name)
+    blend = None if x_orig is None and noise is None and mask is None else (x_orig, noise, mask)
+    _step("guided_cfg_step", x, model_out, tokens, n_img, cfg_on, p, reshape_order, sigma, sigma_next, cfg_weight,
+          row=(hist, coef, reads_h, writes_h), blend=blend, guide=(mode, rescale, eta, norm_threshold, momentum, reads_m, writes_m, m, workspace))
 
 
 def mask_to_latent(mask: Tensor, factor: int = 8) -> Tensor:

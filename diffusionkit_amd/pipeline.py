@@ -693,25 +693,17 @@ class CFGDenoiser:
 
     def __call__(self, x_t, timestep, sigma, conditioning, cfg_weight: float = 7.5, pooled_conditioning=None):
         """Returns the (CFG-combined) x0 prediction, fp32, same shape as x_t."""
-        mm = self.model.mmdit
+        from . import ops
+        mm, cfg = self.model.mmdit, self.model.mmdit_config
         cfg_on = cfg_weight > 0
         tok = mm.patchify(x_t.contiguous(), dup=2 if cfg_on else 1)
         if mm.dtype == torch.float16:  # (bf16 -> fp16 of the encoders' output: exact in range)
             conditioning = conditioning.to(torch.float16).contiguous()
         out = mm.forward_tokens(tok, conditioning, self.step_index(timestep))
         den = x_t.clone()
-        _euler(self.model, den, out, tok, cfg_on, float(sigma), 0.0, float(cfg_weight))  # x + d*(0 - sigma) = x0
+        ops.euler_cfg_step(den, out, tok, den.shape[0], cfg_on, cfg.patch_size, int(cfg.patchify_via_reshape), float(sigma), 0.0,
+                           float(cfg_weight))  # x + d*(0 - sigma) = x0
         return den
-
-
-def _euler(pipe, x, model_out, tok, cfg_on, sigma, sigma_next, cfg_weight):
-    cfg = pipe.mmdit_config
-    n_img, hl, wl, c = x.shape
-    lib = _lib.load()
-    fn = lib.dk_euler_cfg_step_f16 if model_out.dtype == torch.float16 else lib.dk_euler_cfg_step  # (tokens in the engine's element type)
-    _lib.check(fn(x.data_ptr(), model_out.data_ptr(), model_out.shape[-1], tok.data_ptr(), n_img,
-                  int(cfg_on), hl, wl, c, cfg.patch_size, int(cfg.patchify_via_reshape),
-                  sigma, sigma_next, cfg_weight, _stream()), "dk_euler_cfg_step")
 
 
 def append_dims(x, target_dims):
@@ -856,83 +848,14 @@ def _set_rows(model: "CFGDenoiser", lp: _Loop, guided: bool):
     return tok, torch.empty_like(tok)
 
 
-def sample_euler(model: CFGDenoiser, x: Tensor, sigmas, extra_args=None):
-    """mlx/__init__.py:761-788.  x: fp32 [n_img,h,w,16] on the GPU (updated copy is returned);
-    sigmas: host float32 array.  One device synchronisation per step (the reference's
-    mx.eval(x)) provides iter_time.
-    Inpainting: ``extra_args["mask"]`` (f32 [1 or n_img, h, w], 1 = repaint) together with ``"x_orig"`` and ``"noise"`` (f32 like x: the
-    encoded image after process_in and the draw of the start state) makes every step end in the blend of dk_euler_cfg_step_masked --
-    still one launch per step.
-    First-block cache: ``extra_args["block_cache"]`` (a float threshold or a policy object, ``sampler.BlockCachePolicy``) turns a step into
-    the engine's head, the read of its probe (the step's decision needs it on the host: a synchronisation), and the tail the policy chose;
-    the record of the decisions goes to ``model.block_cache_record``."""
-    pipe, mm, sigmas, cfg_weight, cfg_on, n_img, policy, x, mask, x_orig, noise, tok, out = _loop_setup(model, x, sigmas, extra_args)[:13]
-    if mask is not None:
-        from . import ops
-        pcfg = pipe.mmdit_config
-    iter_time = []
-    if policy is not None:
-        from .sampler import block_cache_rel
-        n_steps = len(sigmas) - 1
-        record = {"threshold": getattr(policy, "threshold", None), "computed": [], "skipped": [], "rel": []}
-        for i in range(n_steps):
-            t0 = time.perf_counter()
-            rel = block_cache_rel(mm.forward_head(tok, None, i).cpu().tolist())  # (.cpu(): the step's synchronisation point)
-            skip = bool(policy.decide(i, n_steps, rel))
-            mm.forward_tail(i, skip, tokens_out=out)
-            record["skipped" if skip else "computed"].append(i)
-            record["rel"].append(rel)
-            if mask is None:
-                _euler(pipe, x, out, tok, cfg_on, float(sigmas[i]), float(sigmas[i + 1]), cfg_weight)
-            else:
-                ops.euler_cfg_step_masked(x, out, tok, n_img, cfg_on, pcfg.patch_size, int(pcfg.patchify_via_reshape), float(sigmas[i]),
-                                          float(sigmas[i + 1]), cfg_weight, x_orig, noise, mask)
-            torch.cuda.synchronize(pipe.device)
-            iter_time.append(round(time.perf_counter() - t0, 3))
-        model.block_cache_record = record
-        model.clear_cache()
-        return x, iter_time
-    for i in range(len(sigmas) - 1):
-        t0 = time.perf_counter()
-        mm.forward_tokens(tok, None, i, tokens_out=out)
-        if mask is None:
-            _euler(pipe, x, out, tok, cfg_on, float(sigmas[i]), float(sigmas[i + 1]), cfg_weight)
-        else:
-            ops.euler_cfg_step_masked(x, out, tok, n_img, cfg_on, pcfg.patch_size, int(pcfg.patchify_via_reshape), float(sigmas[i]),
-                                      float(sigmas[i + 1]), cfg_weight, x_orig, noise, mask)
-        torch.cuda.synchronize(pipe.device)
-        iter_time.append(round(time.perf_counter() - t0, 3))
-    model.clear_cache()
-    return x, iter_time
-
-
-def sample_steps(model: CFGDenoiser, x: Tensor, sigmas, plan, extra_args=None):
-    """``sample_euler`` for the second-order samplers (no reference counterpart): ``plan`` = the rows of ``sampler.step_plan(name, sigmas)``, one model
-    evaluation each (at the row's entry of the schedule, which is also its row of the cached modulation table -- Heun's corrector reuses the next
-    step's), followed by one launch of dk_lms_cfg_step that applies the row's coefficients to x and to the fp32 history buffer allocated here.
-    Same operands and ``extra_args`` as ``sample_euler``, inpainting and the first-block cache included: the masked launch blends at the row's
-    sigma_next (on Heun's predictor row too, so that the corrector's evaluation sees the re-imposed region), and a plan of one evaluation per
-    step (ab2) hands the policy the same step indices as the Euler loop.  A plan with two evaluations in a step (heun) refuses ``block_cache``.
-    ``iter_time`` has one entry per step -- a Heun step's covers both evaluations -- with one device synchronisation per step.
-    Guidance: ``extra_args["guidance"]`` (the dict of ``_guidance_options``) replaces the step launch of a guided evaluation by dk_guided_cfg_step
-    (two small launches for the per-image moments, then the step) for "rescale" and "apg", and under an interval runs the evaluations outside it
-    on the prompt rows alone: where the guidedness changes, ``_set_rows`` re-prepares the engine, the first-block cache (if on) is reset and that
-    evaluation computes whatever the policy says, and the update is dk_lms_cfg_step with cfg_on = 0 on the first n_img token rows.  APG's momentum
-    buffer is allocated here and never initialised: the first guided evaluation of a stretch does not read it.  What ran goes to
-    ``model.guidance_record``."""
+def _step_loop(model: "CFGDenoiser", lp: _Loop, plan, grows, guide=None, euler: bool = False):
+    """The host loop behind ``sample_euler`` and ``sample_steps``: per (row, guidance row) one model evaluation -- the engine's head, the policy's
+    decision and the chosen tail under the first-block cache -- and one launch of the update, with one device synchronisation per step (the
+    reference's mx.eval(x)), which provides iter_time.  ``euler``: the rows are the schedule's Euler rows and the update is dk_euler_cfg_step, the
+    reference's statement, instead of the coefficient-row entry.  The operators are looked up on ``ops`` at every call."""
     from . import ops
     from .sampler import block_cache_rel
-    plan = list(plan)
-    guide = None if extra_args is None else extra_args.get("guidance")
-    grows = guidance_rows(plan, None if guide is None else guide["interval"])
-    lp = _loop_setup(model, x, sigmas, extra_args, guided=grows[0].guided if grows else True)
-    pipe, mm, sigmas, cfg_weight, cfg_on, n_img, policy, x, mask, x_orig, noise, tok, out = lp[:13]
-    if guide is not None and not cfg_on:
-        raise ValueError("extra_args['guidance'] needs classifier-free guidance (cfg_weight > 0)")
-    if policy is not None and not all(r.ends_step for r in plan):
-        raise ValueError(_HEUN_BLOCK_CACHE)
-    if any(not 0 <= r.index < len(sigmas) - 1 for r in plan):
-        raise ValueError("the plan evaluates the model outside the schedule (or at its last entry): build it with sampler.step_plan on these sigmas")
+    pipe, mm, _, cfg_weight, cfg_on, n_img, policy, x, mask, x_orig, noise, tok, out = lp[:13]
     pcfg = pipe.mmdit_config
     hist = torch.empty_like(x) if any(r.reads_h or r.writes_h for r in plan) else None  # (never initialised: no row reads it before one wrote it)
     mode = "cfg" if guide is None else guide["mode"]
@@ -942,6 +865,7 @@ def sample_steps(model: CFGDenoiser, x: Tensor, sigmas, plan, extra_args=None):
         gws = torch.empty(ops.guidance_workspace_bytes(*x.shape), dtype=torch.uint8, device=x.device)
     if mode == "apg" and beta != 0.0 and any(g.feeds for g in grows):
         mbuf = torch.empty_like(x)  # (never initialised: the first guided row of a stretch does not read it)
+    blend = () if mask is None else (x_orig, noise, mask)
     n_steps = sum(r.ends_step for r in plan)
     record = {"threshold": getattr(policy, "threshold", None), "computed": [], "skipped": [], "rel": []}
     iter_time = []
@@ -965,17 +889,15 @@ def sample_steps(model: CFGDenoiser, x: Tensor, sigmas, plan, extra_args=None):
             mm.forward_tail(r.index, skip, tokens_out=out)
             record["skipped" if skip else "computed"].append(step)
             record["rel"].append(rel)
-        args = (x, out, tok, n_img, on, pcfg.patch_size, int(pcfg.patchify_via_reshape), r.sigma, r.sigma_next, cfg_weight, hist,
-                (r.cx, r.cd, r.ch, r.hx, r.hd), r.reads_h, r.writes_h)
+        args = (x, out, tok, n_img, on, pcfg.patch_size, int(pcfg.patchify_via_reshape), r.sigma, r.sigma_next, cfg_weight)
+        if not euler:
+            args += (hist, (r.cx, r.cd, r.ch, r.hx, r.hd), r.reads_h, r.writes_h)
         if on and mode != "cfg":
-            kw = {} if mask is None else dict(x_orig=x_orig, noise=noise, mask=mask)
             ops.guided_cfg_step(*args, mode=mode, workspace=gws, rescale=guide["guidance_rescale"], eta=guide["apg_eta"],
                                 norm_threshold=guide["apg_norm_threshold"], momentum=beta, reads_m=mbuf is not None and not g.first,
-                                writes_m=mbuf is not None and g.feeds, m=mbuf, **kw)
-        elif mask is None:
-            ops.lms_cfg_step(*args)
+                                writes_m=mbuf is not None and g.feeds, m=mbuf, **dict(zip(("x_orig", "noise", "mask"), blend)))
         else:
-            ops.lms_cfg_step_masked(*args, x_orig, noise, mask)
+            getattr(ops, ("euler" if euler else "lms") + "_cfg_step" + ("_masked" if blend else ""))(*args, *blend)
         if r.ends_step:
             torch.cuda.synchronize(pipe.device)
             iter_time.append(round(time.perf_counter() - t0, 3))
@@ -987,3 +909,45 @@ def sample_steps(model: CFGDenoiser, x: Tensor, sigmas, plan, extra_args=None):
         model.guidance_record = dict(guide, guided_evals=n_g, unguided_evals=len(grows) - n_g)
     model.clear_cache()
     return x, iter_time
+
+
+def sample_euler(model: CFGDenoiser, x: Tensor, sigmas, extra_args=None):
+    """mlx/__init__.py:761-788.  x: fp32 [n_img,h,w,16] on the GPU (updated copy is returned);
+    sigmas: host float32 array.  One device synchronisation per step (the reference's
+    mx.eval(x)) provides iter_time.
+    Inpainting: ``extra_args["mask"]`` (f32 [1 or n_img, h, w], 1 = repaint) together with ``"x_orig"`` and ``"noise"`` (f32 like x: the
+    encoded image after process_in and the draw of the start state) makes every step end in the blend of dk_euler_cfg_step_masked --
+    still one launch per step.
+    First-block cache: ``extra_args["block_cache"]`` (a float threshold or a policy object, ``sampler.BlockCachePolicy``) turns a step into
+    the engine's head, the read of its probe (the step's decision needs it on the host: a synchronisation), and the tail the policy chose;
+    the record of the decisions goes to ``model.block_cache_record``."""
+    lp = _loop_setup(model, x, sigmas, extra_args)
+    plan = step_plan("euler", lp.sigmas)  # (one row per step; its sigma and sigma_next are the schedule's float32 entries)
+    return _step_loop(model, lp, plan, guidance_rows(plan), euler=True)
+
+
+def sample_steps(model: CFGDenoiser, x: Tensor, sigmas, plan, extra_args=None):
+    """``sample_euler`` for the second-order samplers (no reference counterpart): ``plan`` = the rows of ``sampler.step_plan(name, sigmas)``, one model
+    evaluation each (at the row's entry of the schedule, which is also its row of the cached modulation table -- Heun's corrector reuses the next
+    step's), followed by one launch of dk_lms_cfg_step that applies the row's coefficients to x and to the fp32 history buffer allocated here.
+    Same operands and ``extra_args`` as ``sample_euler``, inpainting and the first-block cache included: the masked launch blends at the row's
+    sigma_next (on Heun's predictor row too, so that the corrector's evaluation sees the re-imposed region), and a plan of one evaluation per
+    step (ab2) hands the policy the same step indices as the Euler loop.  A plan with two evaluations in a step (heun) refuses ``block_cache``.
+    ``iter_time`` has one entry per step -- a Heun step's covers both evaluations -- with one device synchronisation per step.
+    Guidance: ``extra_args["guidance"]`` (the dict of ``_guidance_options``) replaces the step launch of a guided evaluation by dk_guided_cfg_step
+    (two small launches for the per-image moments, then the step) for "rescale" and "apg", and under an interval runs the evaluations outside it
+    on the prompt rows alone: where the guidedness changes, ``_set_rows`` re-prepares the engine, the first-block cache (if on) is reset and that
+    evaluation computes whatever the policy says, and the update is dk_lms_cfg_step with cfg_on = 0 on the first n_img token rows.  APG's momentum
+    buffer is allocated here and never initialised: the first guided evaluation of a stretch does not read it.  What ran goes to
+    ``model.guidance_record``."""
+    plan = list(plan)
+    guide = None if extra_args is None else extra_args.get("guidance")
+    grows = guidance_rows(plan, None if guide is None else guide["interval"])
+    lp = _loop_setup(model, x, sigmas, extra_args, guided=grows[0].guided if grows else True)
+    if guide is not None and not lp.cfg_on:
+        raise ValueError("extra_args['guidance'] needs classifier-free guidance (cfg_weight > 0)")
+    if lp.policy is not None and not all(r.ends_step for r in plan):
+        raise ValueError(_HEUN_BLOCK_CACHE)
+    if any(not 0 <= r.index < len(lp.sigmas) - 1 for r in plan):
+        raise ValueError("the plan evaluates the model outside the schedule (or at its last entry): build it with sampler.step_plan on these sigmas")
+    return _step_loop(model, lp, plan, grows, guide)
