@@ -224,6 +224,10 @@ SIGNATURES = {
     "dk_block_probe_f16": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "dk_block_residual_bf16": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
     "dk_block_residual_f16": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
+    # reference-image conditioning: the engine's grid / hoist entries and the RoPE table for several grids
+    "dk_mmdit_set_reference_grid": (_i32, [_vp, _i32, _i32]),
+    "dk_mmdit_cache_reference": (_i32, [_vp, _vp, _i32, _vp]),
+    "dk_rope_table_segments_f32": (_i32, [_vp, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), _i32, _f32, _vp]),
     "dk_vae_create": (_i32, [C.POINTER(dk_vae_config), C.POINTER(_vp)]),
     "dk_vae_destroy": (None, [_vp]),
     "dk_vae_bind": (_i32, [_vp, C.c_char_p, _vp]),

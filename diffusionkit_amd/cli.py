@@ -56,6 +56,10 @@ def build_parser(model_versions: Sequence[str]) -> argparse.ArgumentParser:
                    help="Inpainting mask for --image-path (first channel; 255 = repaint, 0 = keep; resized to the image with NEAREST).")
     p.add_argument("--no-composite", action="store_true",
                    help="With --mask-path: do not paste the kept pixels of the input image back over the decoded image.")
+    p.add_argument("--reference-image-path", type=str, default=None,
+                   help="Reference-image conditioning in FLUX.1 Kontext's token layout (FLUX versions only): the image is VAE-encoded and its "
+                        "tokens ride behind the image tokens at RoPE index 1. Sides must be multiples of 16 pixels; it is not resized. "
+                        "Verified as arithmetic only: no Kontext checkpoint has been run here.")
     p.add_argument("--block-cache", type=float, default=None, metavar="THRESHOLD",
                    help="First-block cache: skip the blocks behind block 0 in steps where block 0's effect moved by less than THRESHOLD "
                         "(a float >= 0, relative to the last computed step). Published implementations use about 0.1 for FLUX; no value "
@@ -139,6 +143,10 @@ def resolve(args) -> dict:
         r["mask_path"] = args.mask_path
     if getattr(args, "no_composite", False):
         r["composite"] = False
+    if getattr(args, "reference_image_path", None) is not None:  # (a key only when the flag is given)
+        if "FLUX" not in args.model_version:
+            raise ValueError(f"--reference-image-path needs a FLUX model version (RoPE positions tell the reference from the image), not {args.model_version}")
+        r["reference_image_path"] = args.reference_image_path
     if getattr(args, "block_cache", None) is not None:  # (a key only when the flag is given)
         if not args.block_cache >= 0.0:
             raise ValueError("Block cache threshold must be a float >= 0")
@@ -197,7 +205,7 @@ def main(argv: Optional[Sequence[str]] = None, pipeline_overrides: Optional[dict
                                    negative_text=args.negative_prompt, latent_size=latent_size, image_path=args.image_path,
                                    denoise=args.denoise, verbose=args.verbose, mask_path=r.get("mask_path"),
                                    composite=r.get("composite", True), block_cache=r.get("block_cache"), sampler=r.get("sampler"),
-                                   **{key: r[key] for key in GUIDANCE_FLAGS.values() if key in r})
+                                   **{key: r[key] for key in (*GUIDANCE_FLAGS.values(), "reference_image_path") if key in r})
     if log["text_encoding"].get("synthetic"):
         logger.warning("no text-encoder checkpoints were named (--ckpt clip_l=... t5=...): the conditioning is synthetic")
     image.save(args.output_path)

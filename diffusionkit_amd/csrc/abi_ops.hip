@@ -378,6 +378,10 @@ extern "C" int dk_rope_table_f32(float* table, int32_t S_txt, int32_t gh, int32_
                                  float theta, void* stream) {
   return dk_launch_rope_table(table, S_txt, gh, gw, axes_dim, n_axes, theta, S_(stream));
 }
+extern "C" int dk_rope_table_segments_f32(float* table, int32_t S_txt, int32_t n_seg, const int32_t* seg, const int32_t* axes_dim,
+                                          int32_t n_axes, float theta, void* stream) {
+  return dk_launch_rope_table_segments(table, S_txt, n_seg, seg, axes_dim, n_axes, theta, S_(stream));
+}
 
 static int timestep_embedding(int dtype, const float* t_dev, int n, int dim, float max_period, int embed_dtype, void* out, void* stream) {
   return DK_EL(dtype, dk_launch_timestep_embedding)(t_dev, n, 1, dim, max_period, embed_dtype, (bf16_t*)out, S_(stream));

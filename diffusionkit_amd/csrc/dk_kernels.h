@@ -284,6 +284,9 @@ int dk_launch_t5_bias(const bf16_t* emb, const int* rel_bucket, int H, int S, in
 // ---- elementwise / normalisation ---------------------------------------------------------
 int dk_launch_rope_table(float* table, int S_txt, int gh, int gw, const int* axes, int n_axes, float theta,
                          hipStream_t stream);
+// seg: [n_seg][3] = (gh, gw, index) on the host; the one-grid form above is this with the segment (gh, gw, 0)
+int dk_launch_rope_table_segments(float* table, int S_txt, int n_seg, const int* seg, const int* axes, int n_axes, float theta,
+                                  hipStream_t stream);
 int dk_launch_f32_to_bf16(const float* x, bf16_t* y, long n, hipStream_t stream);
 int dk_launch_affine_f32(const float* x, float* y, long n, float a, float b, hipStream_t stream);
 // inpainting: mask u8 [n_mask, H, W] -> f32 [n_mask, H / f, W / f] (box sum / (f * f * 255)); paste-back of the kept pixels

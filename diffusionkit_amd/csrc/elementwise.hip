@@ -304,14 +304,23 @@ int dk_launch_timestep_embedding(const float* t, int n, int rep, int dim, float 
 // RoPE cos/sin table [S, D/2, 2] for the joint [text, image] sequence
 // (python/src/diffusionkit/mlx/mmdit.py:865-911, quirk Q14).
 struct RopeAxes { int dim[4]; int n; };
-__global__ void dk_rope_table_kernel(float* table, int S_txt, int gh, int gw, RopeAxes ax, float theta, int half) {
+// the grids behind the text rows: segment i holds gh[i] * gw[i] rows at positions (index[i], row, col), rows and columns counted from 0 in
+// every segment (one segment at index 0: the image; FLUX.1 Kontext's reference image is a second one at index 1)
+#define DK_ROPE_MAX_SEG 4
+struct RopeSegs { int gh[DK_ROPE_MAX_SEG], gw[DK_ROPE_MAX_SEG], index[DK_ROPE_MAX_SEG]; int n; };
+__global__ void dk_rope_table_kernel(float* table, int S_txt, RopeSegs sg, RopeAxes ax, float theta, int half) {
   const int s = blockIdx.x, pi = threadIdx.x;
   if (pi >= half) return;
   float pos[4] = {0.f, 0.f, 0.f, 0.f};
   if (s >= S_txt) {
-    const int idx = s - S_txt;
-    pos[1] = (float)(idx / gw);
-    pos[2] = (float)(idx % gw);
+    int idx = s - S_txt, g = 0;
+    while (g < sg.n - 1 && idx >= sg.gh[g] * sg.gw[g]) {
+      idx -= sg.gh[g] * sg.gw[g];
+      ++g;
+    }
+    pos[0] = (float)sg.index[g];
+    pos[1] = (float)(idx / sg.gw[g]);
+    pos[2] = (float)(idx % sg.gw[g]);
   }
   int a = 0, local = pi;
   while (a < ax.n - 1 && local >= ax.dim[a] / 2) {
@@ -324,20 +333,37 @@ __global__ void dk_rope_table_kernel(float* table, int S_txt, int gh, int gw, Ro
   table[((size_t)s * half + pi) * 2 + 0] = cosf(ang);
   table[((size_t)s * half + pi) * 2 + 1] = sinf(ang);
 }
-int dk_launch_rope_table(float* table, int S_txt, int gh, int gw, const int* axes, int n_axes, float theta, hipStream_t stream) {
+int dk_launch_rope_table_segments(float* table, int S_txt, int n_seg, const int* seg, const int* axes, int n_axes, float theta,
+                                  hipStream_t stream) {
+  DK_REQUIRE(table != nullptr && seg != nullptr && axes != nullptr, "null argument");
   DK_REQUIRE(n_axes >= 1 && n_axes <= 4, "rope axes");
+  DK_REQUIRE(n_seg >= 1 && n_seg <= DK_ROPE_MAX_SEG, "rope table: 1 to 4 grid segments");
+  DK_REQUIRE(S_txt >= 0, "rope table: negative text length");
   RopeAxes ax;
+  RopeSegs sg;
   int half = 0;
+  long S = S_txt;
   for (int i = 0; i < 4; ++i) ax.dim[i] = 0;
   for (int i = 0; i < n_axes; ++i) {
     ax.dim[i] = axes[i];
     half += axes[i] / 2;
   }
   ax.n = n_axes;
-  const int S = S_txt + gh * gw;
-  hipLaunchKernelGGL(dk_rope_table_kernel, dim3(S), dim3(((half + 63) / 64) * 64), 0, stream, table, S_txt, gh, gw, ax, theta, half);
+  for (int i = 0; i < DK_ROPE_MAX_SEG; ++i) sg.gh[i] = sg.gw[i] = sg.index[i] = 0;
+  for (int i = 0; i < n_seg; ++i) {
+    DK_REQUIRE(seg[3 * i] > 0 && seg[3 * i + 1] > 0, "rope table: every grid segment needs positive sides");
+    sg.gh[i] = seg[3 * i]; sg.gw[i] = seg[3 * i + 1]; sg.index[i] = seg[3 * i + 2];
+    S += (long)sg.gh[i] * sg.gw[i];
+  }
+  sg.n = n_seg;
+  DK_REQUIRE(half >= 1 && half <= 1024 && S >= 1 && S <= 0x7fffffffL, "rope table: size");
+  hipLaunchKernelGGL(dk_rope_table_kernel, dim3((unsigned)S), dim3(((half + 63) / 64) * 64), 0, stream, table, S_txt, sg, ax, theta, half);
   DK_CHECK_HIP(hipGetLastError());
   return 0;
+}
+int dk_launch_rope_table(float* table, int S_txt, int gh, int gw, const int* axes, int n_axes, float theta, hipStream_t stream) {
+  const int seg[3] = {gh, gw, 0};
+  return dk_launch_rope_table_segments(table, S_txt, 1, seg, axes, n_axes, theta, stream);
 }
 
 __global__ void dk_f32_to_bf16_kernel(const float* x, bf16_t* y, long n) {

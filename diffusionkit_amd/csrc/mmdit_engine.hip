@@ -41,7 +41,14 @@ struct dk_mmdit {
   const bf16_t *adaln_w, *adaln_b, *final_w, *final_b;
   std::vector<StreamW> dimg, dtxt, single;
   // shape
-  int B = 0, Hl = 0, Wl = 0, S_t = 0, S_i = 0, S = 0, n_t = 0;
+  // S_i: the rows the model predicts (tokens_in / tokens_out, the final layer, the first-block cache's buffers).  S_x: the rows of the
+  // image stream inside the blocks = S_i + S_r, with S_r the reference image's rows behind the image rows (dk_mmdit_set_reference_grid;
+  // 0 without one: S_x == S_i).  S = S_t + S_x
+  int B = 0, Hl = 0, Wl = 0, S_t = 0, S_i = 0, S_r = 0, S_x = 0, S = 0, n_t = 0;
+  int ref_h = 0, ref_w = 0;  // the reference latent's sides (0, 0: off)
+  bf16_t* REFE = nullptr;    // x_embedder(reference tokens) [B, S_r, h], step-invariant (dk_mmdit_cache_reference)
+  bool ref_ready = false;
+  int ref_rows(int p) const { return (ref_h / p) * (ref_w / p); }
   bool prepared = false, mod_ready = false;
   // workspace views
   bf16_t *X, *XN, *QKV, *ATT, *CAT, *HID, *MOD, *POS;
@@ -83,8 +90,10 @@ struct dk_mmdit {
   int n_bf16() const { return fp8() ? (cfg.fp8_bf16_double_blocks < cfg.depth_multimodal ? cfg.fp8_bf16_double_blocks : cfg.depth_multimodal) : 0; }
 
   // row views of the joint-stream buffers [B, S, ld] (X, QKV, ATT; text rows first in every batch row): the image / the text rows of all batch
-  // rows.  XN, HID and CAT hold plain [M, ld] rows: dense(ptr, ld)
-  Rows img(bf16_t* buf, int ld) const { return Rows{buf + (size_t)S_t * ld, ld, S_i, S}; }
+  // rows.  XN, HID and CAT hold plain [M, ld] rows: dense(ptr, ld).  img: the image STREAM (reference rows included); own: the S_i image
+  // rows alone
+  Rows img(bf16_t* buf, int ld) const { return Rows{buf + (size_t)S_t * ld, ld, S_x, S}; }
+  Rows own(bf16_t* buf, int ld) const { return Rows{buf + (size_t)S_t * ld, ld, S_i, S}; }
   Rows txt(bf16_t* buf, int ld) const { return Rows{buf, ld, S_t, S}; }
 
   int h() const { return cfg.hidden_size; }
@@ -250,7 +259,7 @@ static int mmdit_resolve(dk_mmdit* m) {
 
 static size_t mmdit_carve(dk_mmdit* m, Carver& c, int B, int Hl, int Wl, int S_t, int n_t) {
   const int h = m->h(), p = m->cfg.patch_size;
-  const int S_i = (Hl / p) * (Wl / p), S = S_t + S_i;
+  const int S_i = (Hl / p) * (Wl / p), S_r = m->ref_rows(p), S_x = S_i + S_r, S = S_t + S_x;
   const size_t BS = (size_t)B * S;
   m->X = (bf16_t*)c.take(BS * h * 2);
   m->XN = (bf16_t*)c.take(BS * h * 2);
@@ -268,7 +277,7 @@ static size_t mmdit_carve(dk_mmdit* m, Carver& c, int B, int Hl, int Wl, int S_t
     m->ldh8 = dk_weight_pitch_fp8(r * h);
     m->ldcat8 = dk_weight_pitch_fp8((1 + r) * h);
     // (a ragged image token count pads the image rows to the next scale block; aligned counts: rows8 == BS, the sizes they always had)
-    m->txt0_8 = (int)align_up((size_t)B * S_i, 128);
+    m->txt0_8 = (int)align_up((size_t)B * S_x, 128);
     m->rows8 = (long)m->txt0_8 + (long)B * S_t;
     const size_t R8 = (size_t)m->rows8;
     m->nblk = mx_nblk(m->rows8);
@@ -307,6 +316,8 @@ static size_t mmdit_carve(dk_mmdit* m, Carver& c, int B, int Hl, int Wl, int S_t
     m->BC_D[1] = (bf16_t*)c.take(img);
     m->BC_ROWS = (float*)c.take((size_t)B * S_i * 2 * 4);
   }
+  m->REFE = nullptr;
+  if (S_r > 0) m->REFE = (bf16_t*)c.take((size_t)B * S_r * h * 2);  // (behind everything else, and no take at all without a reference)
   return c.off;
 }
 
@@ -331,11 +342,13 @@ extern "C" int dk_mmdit_prepare(dk_mmdit* m, int32_t batch, int32_t latent_h, in
   const size_t need_bytes = mmdit_carve(m, c, batch, latent_h, latent_w, text_len, n_timesteps);
   DK_REQUIRE(need_bytes <= workspace_bytes, "workspace too small");
   m->B = batch; m->Hl = latent_h; m->Wl = latent_w; m->S_t = text_len;
-  m->S_i = (latent_h / p) * (latent_w / p); m->S = m->S_t + m->S_i; m->n_t = n_timesteps;
+  m->S_i = (latent_h / p) * (latent_w / p); m->S_r = m->ref_rows(p); m->S_x = m->S_i + m->S_r; m->S = m->S_t + m->S_x; m->n_t = n_timesteps;
   hipStream_t st = S_(stream);
-  if (m->cfg.use_rope)
-    DK_TRY(dk_launch_rope_table(m->rope, m->S_t, latent_h / p, latent_w / p, m->cfg.rope_axes_dim, m->cfg.n_rope_axes,
-                                (float)m->cfg.rope_theta, st));
+  if (m->cfg.use_rope) {  // the image at index 0 and, behind it, the reference image's own grid at index 1
+    const int seg[6] = {latent_h / p, latent_w / p, 0, m->ref_h / p, m->ref_w / p, 1};
+    DK_TRY(dk_launch_rope_table_segments(m->rope, m->S_t, m->S_r > 0 ? 2 : 1, seg, m->cfg.rope_axes_dim, m->cfg.n_rope_axes,
+                                         (float)m->cfg.rope_theta, st));
+  }
   if (m->cfg.use_pos_embed) {
     // centre crop of the learned table (mmdit.py:334-349): rows y0..y0+gh, cols x0..x0+gw
     const int mh = m->cfg.max_latent_resolution, gh = latent_h / p, gw = latent_w / p;
@@ -349,7 +362,44 @@ extern "C" int dk_mmdit_prepare(dk_mmdit* m, int32_t batch, int32_t latent_h, in
   m->prepared = true;
   m->mod_ready = false;
   m->ctx_ready = false;
+  m->ref_ready = false;
   m->bc_reset();
+  return 0;
+}
+
+// ---- reference-image conditioning (include/dk_hip.h) --------------------------------------------------------------------------------
+extern "C" int dk_mmdit_set_reference_grid(dk_mmdit* m, int32_t ref_latent_h, int32_t ref_latent_w) {
+  DK_REQUIRE(m != nullptr, "null handle");
+  if (ref_latent_h != 0 || ref_latent_w != 0) {
+    const int p = m->cfg.patch_size;
+    DK_REQUIRE(m->cfg.use_rope, "a reference grid needs RoPE (use_rope = 1, the FLUX family): the reference rows are told from the image rows by their position index");
+    DK_REQUIRE(ref_latent_h > 0 && ref_latent_w > 0 && ref_latent_h % p == 0 && ref_latent_w % p == 0,
+               "reference latent sides must both be positive multiples of the patch size, or both 0 (off)");
+    DK_REQUIRE((long)(ref_latent_h / p) * (ref_latent_w / p) <= (1L << 24), "reference grid too large");
+  }
+  if (m->ref_h != ref_latent_h || m->ref_w != ref_latent_w) m->prepared = false;  // (another carve: dk_mmdit_prepare must follow)
+  m->ref_h = ref_latent_h; m->ref_w = ref_latent_w;
+  m->ref_ready = false;
+  m->bc_reset();
+  return 0;
+}
+extern "C" int dk_mmdit_cache_reference(dk_mmdit* m, const void* ref_tokens, int32_t per_image, void* stream) {
+  DK_REQUIRE(m && m->prepared && ref_tokens, "prepare must precede cache_reference");
+  DK_REQUIRE(m->S_r > 0, "cache_reference needs a reference grid: dk_mmdit_set_reference_grid before dk_mmdit_prepare");
+  const int h = m->h(), F = m->F(), S_r = m->S_r;
+  // x_embedder as in mmdit_embed (no split workspace), one launch per batch row: a shared reference gives every batch row the bits a
+  // per-image copy of it would
+  for (int b = 0; b < m->B; ++b) {
+    const bf16_t* src = (const bf16_t*)ref_tokens + (per_image ? (size_t)b * S_r * F : 0);
+    DK_TRY(dk_launch_gemm(Linear(m->dtype, dense(src, F), m->xemb_w, m->xemb_b, dense(m->REFE + (size_t)b * S_r * h, h), S_r, h, F, DK_EPI_BIAS), S_(stream)));
+  }
+  m->ref_ready = true;
+  m->bc_reset();  // (R and D_ref belong to the conditioning they were computed under)
+  return 0;
+}
+// what every entry that runs blocks asks of an engine with a reference grid
+static int need_reference(const dk_mmdit* m) {
+  DK_REQUIRE(m->S_r == 0 || m->ref_ready, "an engine with a reference grid needs dk_mmdit_cache_reference after dk_mmdit_prepare");
   return 0;
 }
 
@@ -410,7 +460,8 @@ static int mmdit_final_layer(dk_mmdit* m, const bf16_t* mod_step, bf16_t* tokens
 // ---- the transformer blocks -----------------------------------------------------------------------------------------------------
 // What every block of a call derives from the prepared shape, built once per call (mmdit_blocks)
 struct BlockCtx {
-  int h, B, S, S_t, S_i, Mi, Mt;  // Mi / Mt: image / text rows of all batch rows
+  int h, B, S, S_t, S_i, Mi, Mt;  // S_i: rows of the image STREAM per batch row (dk_mmdit::S_x: a reference image's rows included -- to a
+                                  // block they are image rows); Mi / Mt: image-stream / text rows of all batch rows
   int mod_stride;                 // modulation rows of one batch row
   float scale;
   const float* rope;
@@ -427,7 +478,7 @@ struct BlockCtx {
 static BlockCtx block_ctx(const dk_mmdit* m) {
   BlockCtx c;
   memset(&c, 0, sizeof(c));
-  c.h = m->h(); c.B = m->B; c.S = m->S; c.S_t = m->S_t; c.S_i = m->S_i; c.Mi = m->B * m->S_i; c.Mt = m->B * m->S_t;
+  c.h = m->h(); c.B = m->B; c.S = m->S; c.S_t = m->S_t; c.S_i = m->S_x; c.Mi = m->B * m->S_x; c.Mt = m->B * m->S_t;
   c.mod_stride = m->mod_rows() * c.h;
   c.scale = 1.0f / sqrtf((float)m->D());
   c.rope = m->cfg.use_rope ? m->rope : nullptr;
@@ -691,6 +742,7 @@ static int mmdit_embed(dk_mmdit* m, const void* tokens_in, const void* text, con
   const hipStream_t st = L.st;
   const dk_mmdit_config& c = m->cfg;
   const int h = m->h(), B = m->B, S = m->S, S_t = m->S_t, S_i = m->S_i, F = m->F();
+  DK_TRY(need_reference(m));
   // context_embedder (mmdit.py:195): text rows of the joint stream -- recomputed from `text`, or copied from the
   // step-invariant result of dk_mmdit_cache_context when `text` is null
   if (text != nullptr) {
@@ -702,10 +754,14 @@ static int mmdit_embed(dk_mmdit* m, const void* tokens_in, const void* text, con
   }
   // x_embedder (+ learned positional embedding) (mmdit.py:197-206): image rows
   // (no split workspace; the positional rows repeat per image: one segment of S_i rows, stride 0)
-  DK_TRY(dk_launch_gemm(Linear(L.dtype, dense((const bf16_t*)tokens_in, F), m->xemb_w, m->xemb_b, m->img(m->X, h), B * S_i, h, F,
+  DK_TRY(dk_launch_gemm(Linear(L.dtype, dense((const bf16_t*)tokens_in, F), m->xemb_w, m->xemb_b, m->own(m->X, h), B * S_i, h, F,
                                c.use_pos_embed ? DK_EPI_RES : DK_EPI_BIAS)
                             .gate_res(nullptr, 0, 0, Rows{c.use_pos_embed ? m->POS : nullptr, h, S_i, 0}),
                         st));
+  // the reference image's rows behind them: the step-invariant result of dk_mmdit_cache_reference
+  if (m->S_r > 0)
+    DK_CHECK_HIP(hipMemcpy2DAsync(m->X + (size_t)(S_t + S_i) * h, (size_t)S * h * 2, m->REFE, (size_t)m->S_r * h * 2, (size_t)m->S_r * h * 2, B,
+                                  hipMemcpyDeviceToDevice, st));
   return 0;
 }
 
@@ -791,6 +847,7 @@ extern "C" int dk_mmdit_run_blocks(dk_mmdit* m, const void* x_in, void* x_out, i
   DK_REQUIRE(step_index >= 0 && step_index < m->n_t, "step index out of range");
   const int total = m->cfg.depth_multimodal + m->cfg.depth_unified;
   DK_REQUIRE(first_block >= 0 && n_blocks >= 1 && first_block + n_blocks <= total, "block range outside the model");
+  DK_TRY(need_reference(m));
   const LaunchCtx L = m->ctx(stream);
   const hipStream_t st = L.st;
   const size_t bytes = (size_t)m->B * m->S * m->h() * 2;

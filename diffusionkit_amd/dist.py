@@ -44,6 +44,29 @@ def shard_seeds(seeds: Sequence[int], rank: int, world: int) -> List[int]:
     return list(seeds[lo:hi])
 
 
+def shard_per_image(value, n_seeds: int, rank: int, world: int):
+    """A per-image keyword of ``generate_image`` / ``denoise_latents`` for this rank's seeds: the list form (one entry per seed, as
+    ``mask_path=`` and ``reference_image_path=`` take it) is cut like ``shard_seeds`` cuts the seeds, anything else (None, one path / image /
+    array for all images) is passed through."""
+    if isinstance(value, (list, tuple)):
+        if len(value) != n_seeds:
+            raise ValueError(f"{len(value)} per-image entries for {n_seeds} seeds: give one entry, or one per seed")
+        return shard_seeds(value, rank, world)
+    return value
+
+
+def generate_sharded(pipe, text: str, seeds: Sequence[int], rank: int, world: int, *, mask_path=None, reference_image_path=None, **kw):
+    """``pipe.generate_image`` on this rank's share of ``seeds``; ``mask_path`` and ``reference_image_path`` in their list form are cut
+    the same way, and are only passed on when set.  Returns None for a rank without seeds."""
+    mine = shard_seeds(seeds, rank, world)
+    if not mine:
+        return None
+    for key, value in (("mask_path", mask_path), ("reference_image_path", reference_image_path)):
+        if value is not None:
+            kw[key] = shard_per_image(value, len(seeds), rank, world)
+    return pipe.generate_image(text, seed=mine, **kw)
+
+
 def broadcast_weights(packed: Optional[Dict[str, torch.Tensor]], device, src: int = 0,
                       chunk_elems: int = _CHUNK_ELEMS, force: bool = False) -> Dict[str, torch.Tensor]:
     """Root packs its engine tensors into one byte blob; every rank receives blob + index and

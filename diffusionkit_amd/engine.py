@@ -93,6 +93,8 @@ class MMDiTEngine:
         self._ws = None
         self._n_cached = 0
         self.block_cache = False
+        self.reference_size = (0, 0)  # latent cells of the reference image (prepare(reference_size=...)); (0, 0): none
+        self._ref_cached = False
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -113,8 +115,16 @@ class MMDiTEngine:
                                       f"{pitch} (was the weight packed under a different pitch_min_k?)")
 
     # -- shape / workspace ---------------------------------------------------------------
-    def prepare(self, batch: int, latent_size: Sequence[int], text_len: int, n_timesteps: int) -> None:
+    def prepare(self, batch: int, latent_size: Sequence[int], text_len: int, n_timesteps: int,
+                reference_size: Optional[Sequence[int]] = None) -> None:
+        """``reference_size``: the (h, w) latent cells of a reference image (``cache_reference``), or None for no reference rows."""
         shape = (batch, int(latent_size[0]), int(latent_size[1]), text_len, n_timesteps)
+        ref = (0, 0) if reference_size is None else (int(reference_size[0]), int(reference_size[1]))
+        if ref != self.reference_size:
+            _lib.check(self.lib.dk_mmdit_set_reference_grid(self._h, *ref), "dk_mmdit_set_reference_grid")
+            self.reference_size = ref
+            self._shape = None
+            self._ref_cached = False
         if self._shape == shape:
             return
         self._check_pitched_weights()
@@ -127,6 +137,7 @@ class MMDiTEngine:
         self._shape = shape
         self._n_cached = 0
         self._ctx_cached = False
+        self._ref_cached = False
 
     @property
     def batch(self):
@@ -170,6 +181,30 @@ class MMDiTEngine:
             raise _lib.DkHipError(f"text shape {tuple(text.shape)} does not match the prepared problem")
         _lib.check(self.lib.dk_mmdit_cache_context(self._h, text.data_ptr(), _stream()), "dk_mmdit_cache_context")
         self._ctx_cached = True
+
+    def reference_tokens(self) -> int:
+        """S_r: rows of the reference image behind the image rows of every batch row (0 without one)."""
+        p = self.config.patch_size
+        return (self.reference_size[0] // p) * (self.reference_size[1] // p)
+
+    def cache_reference(self, latent_or_tokens: Tensor, per_image: bool = False) -> None:
+        """Reference-image conditioning (FLUX.1 Kontext's token layout, include/dk_hip.h): embeds the reference once; every later
+        forward carries its rows behind the image rows.  ``latent_or_tokens``: the reference latent, f32 NHWC [n, rh, rw, C] with
+        (rh, rw) the ``reference_size`` given to ``prepare``, or its tokens in the engine's dtype [n, S_r, p*p*C]; n = batch with
+        ``per_image``, else 1 (one reference for every batch row)."""
+        if self._shape is None or self.reference_size == (0, 0):
+            raise _lib.DkHipError("cache_reference() needs prepare(..., reference_size=(h, w)) first")
+        t = latent_or_tokens
+        if t.dim() == 4:
+            if tuple(t.shape[1:3]) != self.reference_size:
+                raise _lib.DkHipError(f"reference latent {tuple(t.shape[1:3])} != the prepared reference_size {self.reference_size}")
+            t = self.patchify(t.to(torch.float32).contiguous())
+        _require_cuda(t, "reference tokens", self.dtype)
+        want = (self._shape[0] if per_image else 1, self.reference_tokens(), self.config.patch_dim)
+        if tuple(t.shape) != want:
+            raise _lib.DkHipError(f"reference tokens shape {tuple(t.shape)} != {want}")
+        _lib.check(self.lib.dk_mmdit_cache_reference(self._h, t.data_ptr(), int(bool(per_image)), _stream()), "dk_mmdit_cache_reference")
+        self._ref_cached = True
 
     def forward_tokens(self, tokens_in: Tensor, text: Optional[Tensor], step_index: int, tokens_out: Optional[Tensor] = None) -> Tensor:
         """MMDiT.__call__ between patchify and unpatchify (mmdit.py:188-252).  ``text=None`` uses ``cache_context``'s result."""
@@ -235,12 +270,12 @@ class MMDiTEngine:
 
     def run_blocks(self, x: Tensor, step_index: int, first_block: int, n_blocks: int = 1) -> Tensor:
         """MultiModalTransformerBlock / UnifiedTransformerBlock.__call__ (mmdit.py:568-675, 693-751) on a caller-supplied joint
-        residual stream ``x`` (bf16 [batch, S_t + S_i, h], text rows first): blocks ``first_block .. first_block + n_blocks - 1`` of
+        residual stream ``x`` (bf16 [batch, S_t + S_i (+ S_r), h], text rows first): blocks ``first_block .. first_block + n_blocks - 1`` of
         the global order (double blocks, then single blocks) with the modulation cached for ``step_index``."""
         _require_cuda(x, "x", self.dtype)
         b, hl, wl, s_t, _ = self._shape
         p = self.config.patch_size
-        want = (b, s_t + (hl // p) * (wl // p), self.config.hidden_size)
+        want = (b, s_t + (hl // p) * (wl // p) + self.reference_tokens(), self.config.hidden_size)
         if tuple(x.shape) != want:
             raise _lib.DkHipError(f"x shape {tuple(x.shape)} != {want}")
         if not (0 <= step_index < self._n_cached):

@@ -391,6 +391,22 @@ def rope_table(S_txt: int, gh: int, gw: int, axes, theta: float, device) -> Tens
     return t
 
 
+def rope_table_segments(S_txt: int, segments, axes, theta: float, device) -> Tensor:
+    """The table for several grids behind the text rows: ``segments`` = [(gh, gw, index), ...], rows at (index, row, col), rows and
+    columns counted from 0 in every segment.  [(gh, gw, 0)] is ``rope_table`` bit for bit."""
+    lib = _lib.load()
+    segments = [tuple(int(v) for v in s) for s in segments]
+    if not segments or any(len(s) != 3 or s[0] < 1 or s[1] < 1 for s in segments):
+        raise _lib.DkHipError("segments: a non-empty list of (gh, gw, index) with positive sides")
+    half = sum(a // 2 for a in axes)
+    t = torch.empty(S_txt + sum(s[0] * s[1] for s in segments), half, 2, dtype=torch.float32, device=device)
+    arr = (C.c_int32 * len(axes))(*axes)
+    seg = (C.c_int32 * (3 * len(segments)))(*[v for s in segments for v in s])
+    _lib.check(lib.dk_rope_table_segments_f32(t.data_ptr(), S_txt, len(segments), seg, arr, len(axes), float(theta), _stream()),
+               "dk_rope_table_segments_f32")
+    return t
+
+
 def timestep_embedding(t: Tensor, dim: int, max_period: float, embed_dtype: int, dtype=BF) -> Tensor:
     """evaluated in ``embed_dtype`` (0 bf16, 1 fp16, 2 fp32), stored as ``dtype`` (bf16 | float16)"""
     lib = _lib.load()

@@ -143,6 +143,35 @@ def _read_masks(mask, size, n_img: int) -> np.ndarray:
     return read_mask(mask, size)[None]
 
 
+def read_reference_u8(image) -> np.ndarray:
+    """A reference image (``reference_image_path=``) as HWC uint8 RGB: a path, a PIL image or an array, as ``read_image_u8`` takes them, but
+    never resized -- sides that are not multiples of 16 pixels (one 2 x 2 patch of 8-pixel latent cells) raise.  Needs no GPU."""
+    arr = np.array(_open_image(image))
+    if arr.ndim == 2:
+        arr = np.repeat(arr[:, :, None], 3, axis=2)
+    arr = arr[:, :, :3]
+    H, W = arr.shape[:2]
+    if H < 16 or W < 16 or H % 16 or W % 16:
+        raise ValueError(f"the reference image is {H}x{W}: both sides must be multiples of 16 pixels (it is not resized here)")
+    return np.ascontiguousarray(arr)
+
+
+def _read_references(reference, n_img: int) -> np.ndarray:
+    """uint8 [1, H, W, 3] (one reference for all images) or, for a list / tuple of ``n_img`` references of one size, [n_img, H, W, 3]"""
+    if isinstance(reference, (list, tuple)):
+        if len(reference) != n_img:
+            raise ValueError(f"{len(reference)} reference images for {n_img} images: give one reference, or one per image")
+        refs = [read_reference_u8(r) for r in reference]
+        if any(r.shape != refs[0].shape for r in refs):
+            raise ValueError("the reference images of one call must have one size: " + ", ".join(f"{r.shape[0]}x{r.shape[1]}" for r in refs))
+        return np.stack(refs, 0)
+    return read_reference_u8(reference)[None]
+
+
+_REFERENCE_NEEDS_ROPE = ("reference_image_path needs a FLUX-family pipeline: the reference image's tokens are told from the image's by their RoPE "
+                         "position index, and the SD3 family has no RoPE")
+
+
 def _affine(x: Tensor, a: float, b: float) -> Tensor:
     x = x.contiguous()
     y = torch.empty_like(x)
@@ -363,6 +392,7 @@ class DiffusionPipeline:
         apg_norm_threshold: float = 0.0,
         apg_momentum: float = 0.0,
         guidance_interval=None,
+        reference_image_path=None,
     ):
         """mlx/__init__.py:253-292.  ``seed`` may be a list: one image per seed is denoised in a
         single batched step loop (data-parallel sharding hands each rank a list).
@@ -385,7 +415,14 @@ class DiffusionPipeline:
         ``guidance_interval`` = (lo, hi): only evaluations with lo <= sigma <= hi are guided; the others run the prompt rows alone, the engine
         re-prepared for half the batch at every change.  Any of these options goes through ``sample_steps`` (Euler as its plan) and raises with
         ``cfg_weight <= 0``.  ``self.last_guidance`` says what ran: the mode, its parameters, the interval and the guided / unguided evaluation
-        counts.  The modes are verified as arithmetic only: no setting has been validated on a trained checkpoint here."""
+        counts.  The modes are verified as arithmetic only: no setting has been validated on a trained checkpoint here.
+        ``reference_image_path`` (reference-image conditioning in FLUX.1 Kontext's token layout, FLUX family only; a path, a PIL image or an array,
+        or a list with one per seed; sides multiples of 16 pixels, never resized): the image is encoded to the VAE posterior's mean, goes through
+        ``latent_format.process_in`` and rides behind the image tokens of every model evaluation at RoPE index 1 (``MMDiTEngine.cache_reference``,
+        embedded once per call).  It composes with every option above.  ``self.last_reference`` = {"size": (H, W), "tokens": S_r}, or None
+        without the option.  Verified as arithmetic only: no Kontext checkpoint has been run here."""
+        if reference_image_path is not None and not self._IS_FLUX:
+            raise ValueError(_REFERENCE_NEEDS_ROPE)
         guide = _guidance_options(guidance, guidance_rescale, apg_eta, apg_norm_threshold, apg_momentum, guidance_interval, cfg_weight)
         if mask_path is not None and image_path is None:
             raise ValueError("mask_path needs image_path: the mask says which part of that image to keep")
@@ -395,6 +432,7 @@ class DiffusionPipeline:
         seed = int(time.time()) if seed is None else seed
         seeds = list(seed) if isinstance(seed, (list, tuple)) else [seed]
         logger.info(f"Seed: {seeds}")
+        refs = None if reference_image_path is None else _read_references(reference_image_path, len(seeds))  # (raises before any GPU work)
         x_T = self.get_empty_latent(*latent_size)
         if image_path is None:
             denoise = 1.0
@@ -422,6 +460,11 @@ class DiffusionPipeline:
             extra_args["block_cache"] = block_cache
         if guide is not None:
             extra_args["guidance"] = guide
+        self.last_reference = None
+        if refs is not None:
+            extra_args["reference"] = self.latent_format.process_in(self.encode_reference_to_latents(refs))
+            p = self.mmdit_config.patch_size
+            self.last_reference = {"size": tuple(refs.shape[1:3]), "tokens": (refs.shape[1] // (8 * p)) * (refs.shape[2] // (8 * p))}
         noise_scaled = self.sampler.noise_scaling(np.float32(sigmas[0]), noise, x_T, self.max_denoise(sigmas))
         x0 = torch.from_numpy(np.ascontiguousarray(noise_scaled, dtype=np.float32)).to(self.device)
         denoiser = CFGDenoiser(self)
@@ -461,13 +504,16 @@ class DiffusionPipeline:
         apg_norm_threshold: float = 0.0,
         apg_momentum: float = 0.0,
         guidance_interval=None,
+        reference_image_path=None,
     ):
         """mlx/__init__.py:294-534: returns (PIL.Image, log).  ``mask_path``: inpainting, see ``denoise_latents``; with ``composite`` the pixels
         the mask keeps are pasted back from the input image after decoding (the VAE round trip alone does not reproduce them).
         ``block_cache``: first-block cache, see ``denoise_latents``; its record goes to ``log["denoising"]["block_cache"]``.
         ``sampler``: "euler" (default) | "heun" | "ab2", see ``denoise_latents``; ``log["denoising"]["sampler"]`` and ``["model_evals"]`` say what ran.
         ``guidance``, ``guidance_rescale``, ``apg_eta``, ``apg_norm_threshold``, ``apg_momentum``, ``guidance_interval``: see ``denoise_latents``; with any
-        of them set, ``log["denoising"]["guidance"]`` is ``self.last_guidance``."""
+        of them set, ``log["denoising"]["guidance"]`` is ``self.last_guidance``.
+        ``reference_image_path``: reference-image conditioning, see ``denoise_latents``; with it set, ``log["denoising"]["reference"]`` is
+        ``self.last_reference``."""
         if mask_path is not None and image_path is None:
             raise ValueError("mask_path needs image_path: the mask says which part of that image to keep")
         assert latent_size[0] % 2 == 0, f"Height must be divisible by 16 ({latent_size[0]*8}/16={latent_size[0]/2})"
@@ -501,7 +547,8 @@ class DiffusionPipeline:
             conditioning, pooled_conditioning, num_steps=num_steps, cfg_weight=cfg_weight,
             latent_size=latent_size, seed=seed, image_path=image_path, denoise=denoise, mask_path=mask_path, block_cache=block_cache,
             sampler=sampler, guidance=guidance, guidance_rescale=guidance_rescale, apg_eta=apg_eta, apg_norm_threshold=apg_norm_threshold,
-            apg_momentum=apg_momentum, guidance_interval=guidance_interval)
+            apg_momentum=apg_momentum, guidance_interval=guidance_interval,
+            **({} if reference_image_path is None else {"reference_image_path": reference_image_path}))
         torch.cuda.synchronize(dev)
         log["denoising"]["post"] = mem()
         log["peak_memory"] = max(log["peak_memory"], log["denoising"]["post"]["peak_memory"])
@@ -512,6 +559,8 @@ class DiffusionPipeline:
             log["denoising"]["block_cache"] = self.last_block_cache
         if any(self.last_guidance[k] != v for k, v in _DEFAULT_GUIDANCE.items()):  # (a key only when an option is set)
             log["denoising"]["guidance"] = self.last_guidance
+        if reference_image_path is not None:
+            log["denoising"]["reference"] = self.last_reference
 
         torch.cuda.reset_peak_memory_stats(dev)
         t0 = time.time()
@@ -574,6 +623,16 @@ class DiffusionPipeline:
         mean_like = np.empty((b, h, w, self.vae_encoder_config.out_channels // 2), dtype=np.float32)
         noise = torch.from_numpy(self.get_noise(seed, mean_like)).to(self.device)
         return self.encoder.sample(moments, noise)
+
+    def encode_reference_to_latents(self, refs: np.ndarray) -> Tensor:
+        """Reference images uint8 [n, H, W, 3] (``_read_references``) -> the MEAN of the VAE posterior, NHWC float32 [n, H/8, W/8, L] on the device:
+        the encoder's ``sample`` with a zero noise tensor, so the same reference gives the same conditioning whatever the seed."""
+        self.load_vae_encoder()
+        image = torch.from_numpy((refs.astype(np.float32) / 255) * 2 - 1.0).to(self.device)
+        moments = self.encoder.encode(image)
+        b, h, w, _ = moments.shape
+        zeros = torch.zeros(b, h, w, self.vae_encoder_config.out_channels // 2, dtype=torch.float32, device=self.device)
+        return self.encoder.sample(moments, zeros)
 
     def get_empty_latent(self, *shape):
         return np.ones([1, *shape, 16], dtype=np.float32) * np.float32(0.0609)
@@ -787,6 +846,27 @@ class _Loop(NamedTuple):
     conditioning: Tensor
     pooled: Tensor
     timesteps: object
+    reference: Optional[Tensor] = None  # the reference latent f32 [1 or n_img, rh, rw, C] behind ``extra_args["reference"]``, or None
+
+
+def _prepare_rows(mm, now: int, latent_hw, text_len: int, n_t: int, reference: Optional[Tensor]) -> None:
+    """``MMDiTEngine.prepare`` for ``now`` batch rows, with the reference latent's grid when there is one (none: the engine's grid is turned off)"""
+    if reference is None:
+        mm.prepare(now, latent_hw, text_len, n_t)  # (the call as it always was)
+    else:
+        mm.prepare(now, latent_hw, text_len, n_t, reference_size=tuple(reference.shape[1:3]))
+
+
+def _cache_reference(mm, reference: Optional[Tensor], now: int, n_img: int) -> None:
+    """Behind ``_prepare_rows``: the reference embedded once for those rows: one shared reference is broadcast, per-image ones follow the engine's
+    batch layout ([prompt x n_img, negative x n_img] with CFG)."""
+    if reference is None:
+        return
+    if reference.shape[0] == 1:
+        mm.cache_reference(reference, per_image=False)
+    else:
+        tok = mm.patchify(reference.to(torch.float32).contiguous())
+        mm.cache_reference(tok.repeat(now // n_img, 1, 1).contiguous(), per_image=True)
 
 
 def _loop_setup(model: "CFGDenoiser", x: Tensor, sigmas, extra_args, guided: bool = True) -> _Loop:
@@ -820,7 +900,13 @@ def _loop_setup(model: "CFGDenoiser", x: Tensor, sigmas, extra_args, guided: boo
         policy = BlockCachePolicy(policy)
     mm.enable_block_cache(policy is not None)  # (off: the engine's workspace and launches are what they are without the feature)
     now = rows if guided else n_img  # ([prompt x n_img, negative x n_img]: the prompt rows come first)
-    mm.prepare(now, x.shape[1:3], conditioning.shape[1], len(timesteps))
+    reference = extra_args.get("reference")
+    if reference is not None:
+        reference = reference.to(pipe.device, torch.float32).contiguous()
+        if reference.dim() != 4 or reference.shape[0] not in (1, n_img) or reference.shape[3] != x.shape[3]:
+            raise ValueError(f"the reference latent {tuple(reference.shape)} does not match the latent {tuple(x.shape)}: [1 or n_img, rh, rw, C]")
+    _prepare_rows(mm, now, x.shape[1:3], conditioning.shape[1], len(timesteps), reference)
+    _cache_reference(mm, reference, now, n_img)
     model.cache_modulation_params(pooled[:now], timesteps)
     mm.cache_context(conditioning[:now])  # context_embedder is step-invariant (the reference recomputes it in every call, mmdit.py:195)
 
@@ -834,14 +920,16 @@ def _loop_setup(model: "CFGDenoiser", x: Tensor, sigmas, extra_args, guided: boo
     else:
         x_orig = noise = None
     tok = mm.patchify(x, dup=2 if cfg_on and guided else 1)
-    return _Loop(pipe, mm, sigmas, cfg_weight, cfg_on, n_img, policy, x, mask, x_orig, noise, tok, torch.empty_like(tok), conditioning, pooled, timesteps)
+    return _Loop(pipe, mm, sigmas, cfg_weight, cfg_on, n_img, policy, x, mask, x_orig, noise, tok, torch.empty_like(tok), conditioning, pooled, timesteps,
+                 reference)
 
 
 def _set_rows(model: "CFGDenoiser", lp: _Loop, guided: bool):
     """A guidance interval begins or ends: the engine re-prepared for both CFG rows of every image or for the prompt rows alone, its modulation table
     and context cached again for those rows, x patchified with the matching ``dup`` -> (tok, out)."""
     now = lp.n_img * (2 if guided else 1)
-    lp.mm.prepare(now, lp.x.shape[1:3], lp.conditioning.shape[1], len(lp.timesteps))
+    _prepare_rows(lp.mm, now, lp.x.shape[1:3], lp.conditioning.shape[1], len(lp.timesteps), lp.reference)
+    _cache_reference(lp.mm, lp.reference, now, lp.n_img)
     model.cache_modulation_params(lp.pooled[:now].contiguous(), lp.timesteps)
     lp.mm.cache_context(lp.conditioning[:now].contiguous())
     tok = lp.mm.patchify(lp.x, dup=2 if guided else 1)

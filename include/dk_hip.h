@@ -355,6 +355,13 @@ int dk_qk_norm_rope_bf16(void* qkv, int32_t ld, int32_t q_off, int32_t k_off, in
 /* RoPE.rope / _get_positions, mmdit.py:865-911: table f32 [S_txt + gh*gw, sum(axes)/2, 2] */
 int dk_rope_table_f32(float* table, int32_t S_txt, int32_t gh, int32_t gw, const int32_t* axes_dim,
                       int32_t n_axes, float theta, void* stream);
+/* The same table for several grids behind the text rows.  seg: host int32 [n_seg][3] = (gh, gw, index), 1 <= n_seg <= 4, positive
+ * sides.  Rows: S_txt rows at position (0, 0, 0), then the gh * gw rows of every segment in order at (index, row, col), rows and
+ * columns counted from 0 in each segment: table f32 [S_txt + sum gh*gw, sum(axes)/2, 2].  One segment (gh, gw, 0) is
+ * dk_rope_table_f32 bit for bit (one kernel behind both).  FLUX.1 Kontext's layout is the image at index 0 and the reference image
+ * at index 1 (published sampling code: prepare_kontext). */
+int dk_rope_table_segments_f32(float* table, int32_t S_txt, int32_t n_seg, const int32_t* seg, const int32_t* axes_dim,
+                               int32_t n_axes, float theta, void* stream);
 
 /* TimestepAdapter.timestep_embedding, mmdit.py:379-389 (quirk Q2). embed_dtype: 0 bf16, 1 fp16, 2 fp32 */
 int dk_timestep_embedding_bf16(const float* t_dev, int32_t n, int32_t dim, float max_period,
@@ -642,6 +649,30 @@ const void* dk_mmdit_debug_buffer(const dk_mmdit* m, int32_t which);
  * None of these entries synchronises: probe_out is valid in stream order, the caller reads it. */
 int dk_mmdit_set_block_cache(dk_mmdit* m, int32_t on);
 int dk_mmdit_reset_block_cache(dk_mmdit* m);
+
+/* ---- reference-image conditioning (opt-in; FLUX.1 Kontext's token layout, no counterpart in the reference) ---------------------
+ * The joint sequence of every batch row becomes [text (S_t) | image (S_i) | reference (S_r)], S_r = (ref_latent_h / p) *
+ * (ref_latent_w / p): the VAE-encoded reference image rides behind the image rows as extra rows of the IMAGE stream (published
+ * Kontext sampling code: img = cat(img, img_cond), pred[:, :S_i]).  Inside the blocks the reference rows are image-stream rows --
+ * image weights and modulation in double blocks, the one stream of single blocks, queries / keys / values of the joint attention --
+ * at RoPE positions (1, row, col) of their own grid (dk_rope_table_segments_f32).  The final layer, tokens_in / tokens_out, the
+ * first-block cache's probe / R / D_ref / D_cur buffers keep covering the S_i image rows only; debug buffer 0 is [B, S, h] with
+ * S = S_t + S_i + S_r.
+ * Verified against an fp32 / bf16-emulating oracle of this layout with synthetic weights (arithmetic parity); no Kontext checkpoint
+ * has been run through it.
+ *
+ * dk_mmdit_set_reference_grid: call before dk_mmdit_prepare (a prepared engine must be prepared again).  (0, 0), the default, turns
+ * the feature off: dk_mmdit_workspace_bytes, the carve and every launch of every entry are then what they are without it.  Refused,
+ * with no state changed: a configuration without RoPE (use_rope == 0: the SD3 family has no position index to tell the reference
+ * from the image), sides that are not positive multiples of patch_size, one side zero and the other not.
+ * dk_mmdit_cache_reference: ref_tokens in the engine's element type, [batch, S_r, p*p*C] (per_image != 0) or [1, S_r, p*p*C]
+ * (per_image == 0: one reference for every batch row), as dk_latent_to_tokens_* makes them from the reference latent.  Runs
+ * x_embedder on them once into the workspace (step-invariant, like dk_mmdit_cache_context); every later forward / head copies the
+ * result behind the image rows of every batch row.  Invalidated by dk_mmdit_prepare.  dk_mmdit_forward, dk_mmdit_forward_head and
+ * dk_mmdit_run_blocks on an engine with a reference grid but no cached reference return an error that names the rule, never
+ * launch. */
+int dk_mmdit_set_reference_grid(dk_mmdit* m, int32_t ref_latent_h, int32_t ref_latent_w);
+int dk_mmdit_cache_reference(dk_mmdit* m, const void* ref_tokens, int32_t per_image, void* stream);
 /* Head of step `step_index`: dk_mmdit_forward's embedder launches, block 0 and the probe.  probe_out: device float [batch][2] =
  * (num, den) per batch row; before any computed step den is 0 (and num = sum |D_cur|).  Records a pending head for step_index. */
 int dk_mmdit_forward_head(dk_mmdit* m, const void* tokens_in, const void* text, int32_t step_index, float* probe_out, void* stream);
