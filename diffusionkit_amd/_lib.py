@@ -228,6 +228,11 @@ SIGNATURES = {
     "dk_mmdit_set_reference_grid": (_i32, [_vp, _i32, _i32]),
     "dk_mmdit_cache_reference": (_i32, [_vp, _vp, _i32, _vp]),
     "dk_rope_table_segments_f32": (_i32, [_vp, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), _i32, _f32, _vp]),
+    # channel-concatenated conditioning (FLUX.1 Fill / Canny / Depth): the engine's width / hoist entries and the two operators
+    "dk_mmdit_set_condition_width": (_i32, [_vp, _i32]),
+    "dk_mmdit_cache_condition": (_i32, [_vp, _vp, _i32, _vp]),
+    "dk_image_mask_out_f32": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "dk_fill_condition_tokens": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "dk_vae_create": (_i32, [C.POINTER(dk_vae_config), C.POINTER(_vp)]),
     "dk_vae_destroy": (None, [_vp]),
     "dk_vae_bind": (_i32, [_vp, C.c_char_p, _vp]),

@@ -60,6 +60,17 @@ def build_parser(model_versions: Sequence[str]) -> argparse.ArgumentParser:
                    help="Reference-image conditioning in FLUX.1 Kontext's token layout (FLUX versions only): the image is VAE-encoded and its "
                         "tokens ride behind the image tokens at RoPE index 1. Sides must be multiples of 16 pixels; it is not resized. "
                         "Verified as arithmetic only: no Kontext checkpoint has been run here.")
+    p.add_argument("--condition", choices=("fill", "control"), default=None,
+                   help="Channel-concatenated conditioning (FLUX versions only): 'fill' is FLUX.1 Fill's layout (the masked image's latent and the "
+                        "mask ride into every model evaluation; needs --condition-image-path and --condition-mask-path), 'control' FLUX.1 Canny / "
+                        "Depth's (a prepared control image; --condition-image-path). The checkpoint's img_in must be 384 / 128 columns wide. "
+                        "Verified as arithmetic only: no such checkpoint has been run here.")
+    p.add_argument("--condition-image-path", type=str, default=None,
+                   help="With --condition: the image to fill in, or the prepared control image (edges, depth). Its sides must equal "
+                        "--height / --width; it is not resized.")
+    p.add_argument("--condition-mask-path", type=str, default=None,
+                   help="With --condition fill: the mask (first channel; 255 = repaint, 0 = keep, values between are passed on as they are). "
+                        "Same size as the image; not resized.")
     p.add_argument("--block-cache", type=float, default=None, metavar="THRESHOLD",
                    help="First-block cache: skip the blocks behind block 0 in steps where block 0's effect moved by less than THRESHOLD "
                         "(a float >= 0, relative to the last computed step). Published implementations use about 0.1 for FLUX; no value "
@@ -147,6 +158,15 @@ def resolve(args) -> dict:
         if "FLUX" not in args.model_version:
             raise ValueError(f"--reference-image-path needs a FLUX model version (RoPE positions tell the reference from the image), not {args.model_version}")
         r["reference_image_path"] = args.reference_image_path
+    kind = getattr(args, "condition", None)
+    cond_image, cond_mask = getattr(args, "condition_image_path", None), getattr(args, "condition_mask_path", None)
+    if kind is not None or cond_image is not None or cond_mask is not None:  # (keys only when the flags are given)
+        from .pipeline import check_condition_args
+        check_condition_args(kind, cond_image, cond_mask, r.get("reference_image_path"), "FLUX" in args.model_version)
+        r["condition"] = kind
+        r["condition_image_path"] = cond_image
+        if cond_mask is not None:
+            r["condition_mask_path"] = cond_mask
     if getattr(args, "block_cache", None) is not None:  # (a key only when the flag is given)
         if not args.block_cache >= 0.0:
             raise ValueError("Block cache threshold must be a float >= 0")
@@ -191,6 +211,9 @@ def main(argv: Optional[Sequence[str]] = None, pipeline_overrides: Optional[dict
         extra["activation_dtype"] = r["activation_dtype"]
     if "vae_dtype" in r:
         extra["vae_dtype"] = r["vae_dtype"]
+    if "condition" in r:
+        extra["condition"] = r["condition"]
+    cond_kw = {key: r[key] for key in ("condition_image_path", "condition_mask_path") if key in r}
     sd = pipeline_class(w16=True, shift=r["shift"], use_t5=args.t5, model_version=args.model_version,
                         low_memory_mode=r["low_memory_mode"], a16=True, local_ckpt=checkpoint_dict(args.local_ckpt, args.ckpt),
                         device=args.device, **extra)
@@ -199,13 +222,13 @@ def main(argv: Optional[Sequence[str]] = None, pipeline_overrides: Optional[dict
     if args.benchmark_mode:
         logger.info("Running in benchmark mode. Warming up the models. (generated latents will be discarded)")
         sd.generate_image(args.prompt, cfg_weight=r["cfg"], num_steps=1, seed=args.seed, negative_text=args.negative_prompt,
-                          latent_size=latent_size, verbose=False)
+                          latent_size=latent_size, verbose=False, **cond_kw)
         logger.info("Benchmark mode: Warming up the models done.")
     image, log = sd.generate_image(args.prompt, cfg_weight=r["cfg"], num_steps=args.steps, seed=args.seed,
                                    negative_text=args.negative_prompt, latent_size=latent_size, image_path=args.image_path,
                                    denoise=args.denoise, verbose=args.verbose, mask_path=r.get("mask_path"),
                                    composite=r.get("composite", True), block_cache=r.get("block_cache"), sampler=r.get("sampler"),
-                                   **{key: r[key] for key in (*GUIDANCE_FLAGS.values(), "reference_image_path") if key in r})
+                                   **{key: r[key] for key in (*GUIDANCE_FLAGS.values(), "reference_image_path") if key in r}, **cond_kw)
     if log["text_encoding"].get("synthetic"):
         logger.warning("no text-encoder checkpoints were named (--ckpt clip_l=... t5=...): the conditioning is synthetic")
     image.save(args.output_path)

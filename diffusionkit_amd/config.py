@@ -55,6 +55,9 @@ class MMDiTConfig:
     # element type of the MMDiT's weights, activations and token / text / pooled I/O: "bfloat16", or "float16" -- the reference's dtype for
     # Stable Diffusion 3 (config.py:77-79); SD3-family geometry only (validate_activation_dtype)
     activation_dtype: str = "bfloat16"
+    # channel-concatenated conditioning (FLUX.1 Fill: 320, Canny / Depth: 64; 0: none): x_embedder.proj.weight has patch_dim + condition_features
+    # columns, and a condition token row of that width rides into every model evaluation (MMDiTEngine.cache_condition); FLUX family only
+    condition_features: int = 0
 
     @property
     def hidden_size(self) -> int:
@@ -122,6 +125,24 @@ FLUX_SCHNELL = MMDiTConfig(
 # reference config.py:97-111 (declared there, never selected: quirk Q7)
 FLUX_DEV = replace(FLUX_SCHNELL, guidance_embed=True)
 
+# FLUX.1 Fill / Canny / Depth (no reference counterpart): FLUX.1-dev by keys and widths but for img_in, [3072, 64 + 320] / [3072, 64 + 64] -- the
+# condition latent's 64 patch features (Fill: + the 8 x 8-unshuffled mask's 256) concatenated to the latent's on the feature axis
+FLUX_FILL_DEV = replace(FLUX_DEV, condition_features=320)
+FLUX_CONTROL_DEV = replace(FLUX_DEV, condition_features=64)
+
+
+def validate_condition_features(cfg: MMDiTConfig) -> None:
+    """0, or a positive multiple of 64 on a configuration without the learned positional table and with bf16 activations (the rule
+    dk_mmdit_set_condition_width enforces)."""
+    n = cfg.condition_features
+    if n == 0:
+        return
+    if n < 0 or n % 64 != 0:
+        raise ValueError(f"condition_features = {n}: must be 0 or a positive multiple of 64")
+    if cfg.pos_embed_type == PositionalEncoding.LearnedInputEmbedding or cfg.activation_dtype != "bfloat16":
+        raise ValueError("condition_features needs the FLUX family: no learned positional table (the x_embedder launch's residual operand carries "
+                         "the condition's share) and bfloat16 activations")
+
 
 # fp8 precision policy of the FLUX family, measured at full depth on MI355X (scripts/fp8_policy_gpu.py, profiles/r05_fp8_policy_gpu.log:
 # Euler direction of teacher-forced steps 1 / 2 / 49 / 50 against the fp32 oracle): every double-stream block kept in bf16 buys ~0.27 dB and
@@ -175,7 +196,7 @@ def validate_fp8_policy(cfg: MMDiTConfig) -> None:
 
 
 def tiny_flux(depth_multimodal: int = 2, depth_unified: int = 2, heads: int = 2,
-              head_dim: int = 128, text_dim: int = 256, pooled: int = 64) -> MMDiTConfig:
+              head_dim: int = 128, text_dim: int = 256, pooled: int = 64, condition_features: int = 0) -> MMDiTConfig:
     """FLUX-shaped config small enough for the CPU oracle (head_dim stays 128 so the
     RoPE axes (16,56,56) and the D=128 attention kernel are the production ones)."""
     return replace(
@@ -186,6 +207,7 @@ def tiny_flux(depth_multimodal: int = 2, depth_unified: int = 2, heads: int = 2,
         hidden_size_override=heads * head_dim,
         token_level_text_embed_dim=text_dim,
         pooled_text_embed_dim=pooled,
+        condition_features=condition_features,
     )
 
 

@@ -566,6 +566,24 @@ extern "C" int dk_image_composite_u8(const uint8_t* dec, const uint8_t* orig, co
   return dk_launch_image_composite_u8(dec, orig, mask, out, B, H, W, orig_per_image != 0, mask_per_image != 0, S_(stream));
 }
 
+extern "C" int dk_image_mask_out_f32(const uint8_t* image, const uint8_t* mask, float* out, int32_t n, int32_t n_mask, int32_t H, int32_t W,
+                                     void* stream) {
+  DK_REQUIRE(image && mask && out, "null argument");
+  DK_REQUIRE(n > 0 && H > 0 && W > 0, "n, H and W must be positive");
+  DK_REQUIRE(n_mask == 1 || n_mask == n, "n_mask must be 1 (one mask for every image) or n");
+  return dk_launch_image_mask_out_f32(image, mask, out, n, H, W, n_mask == n && n > 1, S_(stream));
+}
+
+extern "C" int dk_fill_condition_tokens(const float* z, const uint8_t* mask, void* tokens, int32_t n, int32_t n_mask, int32_t Hl, int32_t Wl,
+                                        int32_t C, int32_t patch, void* stream) {
+  DK_REQUIRE(z && tokens, "null argument");
+  DK_REQUIRE(n > 0 && C > 0 && patch > 0 && patch <= 16, "n, C and patch (1..16) must be positive");
+  DK_REQUIRE(Hl > 0 && Wl > 0 && Hl % patch == 0 && Wl % patch == 0, "latent sides must be positive multiples of the patch size");
+  DK_REQUIRE(Hl <= (1 << 20) && Wl <= (1 << 20), "latent sides too large");
+  if (mask) DK_REQUIRE(n_mask == 1 || n_mask == n, "n_mask must be 1 (one mask for every image) or n");
+  return dk_launch_fill_condition_tokens(z, mask, (bf16_t*)tokens, n, mask != nullptr && n_mask == n && n > 1, Hl, Wl, C, patch, S_(stream));
+}
+
 extern "C" int dk_affine_f32(const float* x, float* y, int64_t n, float a, float b, void* stream) {
   return dk_launch_affine_f32(x, y, (long)n, a, b, S_(stream));
 }

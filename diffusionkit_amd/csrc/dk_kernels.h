@@ -293,6 +293,12 @@ int dk_launch_affine_f32(const float* x, float* y, long n, float a, float b, hip
 int dk_launch_mask_to_latent(const unsigned char* mask, float* out, int n_mask, int H, int W, int f, hipStream_t stream);
 int dk_launch_image_composite_u8(const unsigned char* dec, const unsigned char* orig, const unsigned char* mask, unsigned char* out, int B,
                                  int H, int W, int orig_per_image, int mask_per_image, hipStream_t stream);
+// channel-concatenated conditioning (FLUX.1 Fill / Canny / Depth): the masked-out image in [-1, 1], and the bf16 condition token rows
+// [n, S_i, p*p*C (+ 64*p*p with a mask)] from its latent and the mask (null: the latent columns only)
+int dk_launch_image_mask_out_f32(const unsigned char* image, const unsigned char* mask, float* out, int n, int H, int W, int mask_per_image,
+                                 hipStream_t stream);
+int dk_launch_fill_condition_tokens(const float* z, const unsigned char* mask, bf16_t* tok, int n, int mask_per_image, int Hl, int Wl, int C,
+                                    int p, hipStream_t stream);
 
 // ---- launchers per element type ------------------------------------------------------------------------------
 #include "dk_elem_launchers.h"

@@ -426,6 +426,63 @@ int dk_launch_image_composite_u8(const unsigned char* dec, const unsigned char* 
   DK_CHECK_HIP(hipGetLastError());
   return 0;
 }
+
+// Channel-concatenated conditioning (FLUX.1 Fill): the image the model may look at, out = a * (1 - m) with a = u8 / 255 * 2 - 1 (read_image's
+// statement) and m = mask / 255, one thread per element.  Contraction is off: every operation rounds on its own, as numpy's float32 does.
+__global__ void dk_image_mask_out_f32_kernel(const unsigned char* image, const unsigned char* mask, float* out, long n_elem, long HW,
+                                             int mask_per_image) {
+#pragma clang fp contract(off)
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_elem) return;
+  const long pix = i / 3;
+  const float a = (float)image[i] / 255.0f * 2.0f - 1.0f;
+  const float m = (float)mask[mask_per_image ? pix : pix % HW] / 255.0f;
+  out[i] = a * (1.0f - m);
+}
+int dk_launch_image_mask_out_f32(const unsigned char* image, const unsigned char* mask, float* out, int n, int H, int W, int mask_per_image,
+                                 hipStream_t stream) {
+  const long HW = (long)H * W, n_elem = HW * 3 * n;
+  DK_REQUIRE(n_elem > 0 && (n_elem + 255) / 256 <= 0x7fffffffL, "image_mask_out: size");
+  hipLaunchKernelGGL(dk_image_mask_out_f32_kernel, dim3((unsigned)((n_elem + 255) / 256)), dim3(256), 0, stream, image, mask, out, n_elem, HW,
+                     mask_per_image);
+  DK_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// ... and its token rows: z f32 [n, Hl, Wl, C] (+ mask u8 [n_mask, 8 Hl, 8 Wl]) -> bf16 [n, S_i, p*p*C (+ 64*p*p)], one thread per output
+// element, consecutive threads along the feature axis.  Columns [0, p*p*C): the latent's patch, features (c, ph, pw) -- dk_latent_to_tokens'
+// FLUX order and rounding.  Columns behind them: the mask's 8 x 8 pixel-unshuffle to 64 channels at latent resolution (channel 8 * py + px),
+// through the same patchify: column p*p*C + (8 * py + px) * p*p + ph * p + pw of token (ti, tj) = bf16(mask[(ti*p + ph) * 8 + py,
+// (tj*p + pw) * 8 + px] / 255).  A null mask writes the latent columns only (FLUX.1 Canny / Depth).
+__global__ void dk_fill_condition_tokens_kernel(const float* z, const unsigned char* mask, bf16_t* tok, long n_out, int mask_per_image, int Hl,
+                                                int Wl, int C, int p, int Fo) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_out) return;
+  const int gw = Wl / p, S_i = (Hl / p) * gw, pp = p * p, Fz = pp * C;
+  const int f = (int)(i % Fo);
+  const long row = i / Fo;
+  const int t = (int)(row % S_i), img = (int)(row / S_i);
+  const int g = f < Fz ? f : f - Fz;  // (channel, ph, pw) of the latent, or of the unshuffled mask
+  const int ch = g / pp, yy = (t / gw) * p + (g / p) % p, xx = (t % gw) * p + g % p;
+  float v;
+  if (f < Fz) {
+    v = z[(((size_t)img * Hl + yy) * Wl + xx) * C + ch];
+  } else {
+    const size_t W8 = (size_t)Wl * 8;
+    v = (float)mask[((size_t)(mask_per_image ? img : 0) * Hl * 8 + (size_t)yy * 8 + ch / 8) * W8 + (size_t)xx * 8 + ch % 8] / 255.0f;
+  }
+  tok[i] = f2bf(v);
+}
+int dk_launch_fill_condition_tokens(const float* z, const unsigned char* mask, bf16_t* tok, int n, int mask_per_image, int Hl, int Wl, int C,
+                                    int p, hipStream_t stream) {
+  const int Fo = p * p * C + (mask ? 64 * p * p : 0);
+  const long n_out = (long)n * (Hl / p) * (Wl / p) * Fo;
+  DK_REQUIRE(n_out > 0 && (n_out + 255) / 256 <= 0x7fffffffL, "fill_condition_tokens: size");
+  hipLaunchKernelGGL(dk_fill_condition_tokens_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, stream, z, mask, tok, n_out,
+                     mask_per_image, Hl, Wl, C, p, Fo);
+  DK_CHECK_HIP(hipGetLastError());
+  return 0;
+}
 #endif  // !DK_ELEM_F16
 
 // ---------------------------------------------------------------------------------------------

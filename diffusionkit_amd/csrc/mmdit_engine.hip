@@ -49,6 +49,11 @@ struct dk_mmdit {
   bf16_t* REFE = nullptr;    // x_embedder(reference tokens) [B, S_r, h], step-invariant (dk_mmdit_cache_reference)
   bool ref_ready = false;
   int ref_rows(int p) const { return (ref_h / p) * (ref_w / p); }
+  // channel-concatenated conditioning (dk_mmdit_set_condition_width): x_embedder.proj.weight is [h, F + cond_f]; the condition's share of the
+  // sum is step-invariant and kept in CONDE [B, S_i, h] (dk_mmdit_cache_condition), the residual operand of the x_embedder launch
+  int cond_f = 0;
+  bf16_t* CONDE = nullptr;
+  bool cond_ready = false;
   bool prepared = false, mod_ready = false;
   // workspace views
   bf16_t *X, *XN, *QKV, *ATT, *CAT, *HID, *MOD, *POS;
@@ -318,6 +323,8 @@ static size_t mmdit_carve(dk_mmdit* m, Carver& c, int B, int Hl, int Wl, int S_t
   }
   m->REFE = nullptr;
   if (S_r > 0) m->REFE = (bf16_t*)c.take((size_t)B * S_r * h * 2);  // (behind everything else, and no take at all without a reference)
+  m->CONDE = nullptr;
+  if (m->cond_f > 0) m->CONDE = (bf16_t*)c.take((size_t)B * S_i * h * 2);  // (the same: no take with the width off)
   return c.off;
 }
 
@@ -363,6 +370,7 @@ extern "C" int dk_mmdit_prepare(dk_mmdit* m, int32_t batch, int32_t latent_h, in
   m->mod_ready = false;
   m->ctx_ready = false;
   m->ref_ready = false;
+  m->cond_ready = false;
   m->bc_reset();
   return 0;
 }
@@ -372,6 +380,7 @@ extern "C" int dk_mmdit_set_reference_grid(dk_mmdit* m, int32_t ref_latent_h, in
   DK_REQUIRE(m != nullptr, "null handle");
   if (ref_latent_h != 0 || ref_latent_w != 0) {
     const int p = m->cfg.patch_size;
+    DK_REQUIRE(m->cond_f == 0, "a reference grid and a condition width cannot be set at the same time");
     DK_REQUIRE(m->cfg.use_rope, "a reference grid needs RoPE (use_rope = 1, the FLUX family): the reference rows are told from the image rows by their position index");
     DK_REQUIRE(ref_latent_h > 0 && ref_latent_w > 0 && ref_latent_h % p == 0 && ref_latent_w % p == 0,
                "reference latent sides must both be positive multiples of the patch size, or both 0 (off)");
@@ -400,6 +409,42 @@ extern "C" int dk_mmdit_cache_reference(dk_mmdit* m, const void* ref_tokens, int
 // what every entry that runs blocks asks of an engine with a reference grid
 static int need_reference(const dk_mmdit* m) {
   DK_REQUIRE(m->S_r == 0 || m->ref_ready, "an engine with a reference grid needs dk_mmdit_cache_reference after dk_mmdit_prepare");
+  return 0;
+}
+
+// ---- channel-concatenated conditioning (include/dk_hip.h) ---------------------------------------------------------------------------
+extern "C" int dk_mmdit_set_condition_width(dk_mmdit* m, int32_t cond_features) {
+  DK_REQUIRE(m != nullptr, "null handle");
+  if (cond_features != 0) {
+    DK_REQUIRE(cond_features > 0 && cond_features % 64 == 0 && cond_features <= (1 << 16), "the condition width must be a positive multiple of 64, or 0 (off)");
+    DK_REQUIRE(m->cfg.use_pos_embed == 0, "a condition width needs use_pos_embed == 0 (the FLUX family): the residual operand of the x_embedder launch carries the condition's share");
+    DK_REQUIRE(m->ref_h == 0 && m->ref_w == 0, "a condition width and a reference grid cannot be set at the same time");
+    DK_REQUIRE(m->dtype == DK_DTYPE_BF16, "a condition width needs bf16 activations");
+  }
+  if (m->cond_f != cond_features) m->prepared = false;  // (another carve: dk_mmdit_prepare must follow)
+  m->cond_f = cond_features;
+  m->cond_ready = false;
+  m->bc_reset();
+  return 0;
+}
+extern "C" int dk_mmdit_cache_condition(dk_mmdit* m, const void* cond_tokens, int32_t per_image, void* stream) {
+  DK_REQUIRE(m && m->prepared && cond_tokens, "prepare must precede cache_condition");
+  DK_REQUIRE(m->cond_f > 0, "cache_condition needs a condition width: dk_mmdit_set_condition_width before dk_mmdit_prepare");
+  const int h = m->h(), F = m->F(), Fc = m->cond_f, S_i = m->S_i;
+  // the condition columns of x_embedder's weight, W[:, F:], without the bias (the x_embedder launch of every evaluation adds it once); one
+  // launch per batch row: a shared condition gives every batch row the bits a per-image copy of it would
+  for (int b = 0; b < m->B; ++b) {
+    const bf16_t* src = (const bf16_t*)cond_tokens + (per_image ? (size_t)b * S_i * Fc : 0);
+    DK_TRY(dk_launch_gemm(Linear(m->dtype, dense(src, Fc), m->xemb_w + F, nullptr, dense(m->CONDE + (size_t)b * S_i * h, h), S_i, h, Fc, DK_EPI_BIAS, F + Fc),
+                          S_(stream)));
+  }
+  m->cond_ready = true;
+  m->bc_reset();  // (R and D_ref belong to the conditioning they were computed under)
+  return 0;
+}
+// what every entry that runs blocks asks of an engine with a condition width
+static int need_condition(const dk_mmdit* m) {
+  DK_REQUIRE(m->cond_f == 0 || m->cond_ready, "an engine with a condition width needs dk_mmdit_cache_condition after dk_mmdit_prepare");
   return 0;
 }
 
@@ -743,6 +788,7 @@ static int mmdit_embed(dk_mmdit* m, const void* tokens_in, const void* text, con
   const dk_mmdit_config& c = m->cfg;
   const int h = m->h(), B = m->B, S = m->S, S_t = m->S_t, S_i = m->S_i, F = m->F();
   DK_TRY(need_reference(m));
+  DK_TRY(need_condition(m));
   // context_embedder (mmdit.py:195): text rows of the joint stream -- recomputed from `text`, or copied from the
   // step-invariant result of dk_mmdit_cache_context when `text` is null
   if (text != nullptr) {
@@ -754,9 +800,13 @@ static int mmdit_embed(dk_mmdit* m, const void* tokens_in, const void* text, con
   }
   // x_embedder (+ learned positional embedding) (mmdit.py:197-206): image rows
   // (no split workspace; the positional rows repeat per image: one segment of S_i rows, stride 0)
+  // (with a condition width: the latent columns of the [h, F + cond_f] weight, and the condition's step-invariant share, CONDE, in the
+  // residual slot the positional table leaves free -- one segment per batch row)
+  const bool cond = m->cond_f > 0;
+  const Rows res = cond ? Rows{m->CONDE, h, S_i, S_i} : Rows{c.use_pos_embed ? m->POS : nullptr, h, S_i, 0};
   DK_TRY(dk_launch_gemm(Linear(L.dtype, dense((const bf16_t*)tokens_in, F), m->xemb_w, m->xemb_b, m->own(m->X, h), B * S_i, h, F,
-                               c.use_pos_embed ? DK_EPI_RES : DK_EPI_BIAS)
-                            .gate_res(nullptr, 0, 0, Rows{c.use_pos_embed ? m->POS : nullptr, h, S_i, 0}),
+                               cond || c.use_pos_embed ? DK_EPI_RES : DK_EPI_BIAS, cond ? F + m->cond_f : 0)
+                            .gate_res(nullptr, 0, 0, res),
                         st));
   // the reference image's rows behind them: the step-invariant result of dk_mmdit_cache_reference
   if (m->S_r > 0)
@@ -848,6 +898,7 @@ extern "C" int dk_mmdit_run_blocks(dk_mmdit* m, const void* x_in, void* x_out, i
   const int total = m->cfg.depth_multimodal + m->cfg.depth_unified;
   DK_REQUIRE(first_block >= 0 && n_blocks >= 1 && first_block + n_blocks <= total, "block range outside the model");
   DK_TRY(need_reference(m));
+  DK_TRY(need_condition(m));
   const LaunchCtx L = m->ctx(stream);
   const hipStream_t st = L.st;
   const size_t bytes = (size_t)m->B * m->S * m->h() * 2;
@@ -862,6 +913,7 @@ extern "C" const void* dk_mmdit_debug_buffer(const dk_mmdit* m, int32_t which) {
   if (!m || !m->prepared) return nullptr;
   if (which >= 3 && which <= 5)  // R, D_ref, D_cur (5: the probe's output between a head and its tail; a compute tail makes that buffer D_ref)
     return !m->bc_on ? nullptr : which == 3 ? (const void*)m->BC_R : (const void*)m->BC_D[which == 4 ? 1 - m->bc_cur : m->bc_cur];
+  if (which == 6) return (const void*)m->CONDE;  // x_embedder's condition share [B, S_i, h] (null with the width off)
   return which == 0 ? (const void*)m->X : which == 1 ? (const void*)m->MOD : which == 2 ? (const void*)m->GWS : nullptr;
 }
 

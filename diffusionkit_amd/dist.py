@@ -55,13 +55,15 @@ def shard_per_image(value, n_seeds: int, rank: int, world: int):
     return value
 
 
-def generate_sharded(pipe, text: str, seeds: Sequence[int], rank: int, world: int, *, mask_path=None, reference_image_path=None, **kw):
-    """``pipe.generate_image`` on this rank's share of ``seeds``; ``mask_path`` and ``reference_image_path`` in their list form are cut
-    the same way, and are only passed on when set.  Returns None for a rank without seeds."""
+def generate_sharded(pipe, text: str, seeds: Sequence[int], rank: int, world: int, *, mask_path=None, reference_image_path=None,
+                     condition_image_path=None, condition_mask_path=None, **kw):
+    """``pipe.generate_image`` on this rank's share of ``seeds``; ``mask_path``, ``reference_image_path``, ``condition_image_path`` and
+    ``condition_mask_path`` in their list form are cut the same way, and are only passed on when set.  Returns None for a rank without seeds."""
     mine = shard_seeds(seeds, rank, world)
     if not mine:
         return None
-    for key, value in (("mask_path", mask_path), ("reference_image_path", reference_image_path)):
+    for key, value in (("mask_path", mask_path), ("reference_image_path", reference_image_path), ("condition_image_path", condition_image_path),
+                       ("condition_mask_path", condition_mask_path)):
         if value is not None:
             kw[key] = shard_per_image(value, len(seeds), rank, world)
     return pipe.generate_image(text, seed=mine, **kw)

@@ -83,6 +83,21 @@ class MMDiTEngine:
         # element type of the weights and of tokens / text / pooled at this boundary (set before the first bind; 0 is the engine's default)
         code, self.dtype = _ACT_DTYPE[config.activation_dtype]
         _lib.check(self.lib.dk_mmdit_set_activation_dtype(self._h, code), "dk_mmdit_set_activation_dtype")
+        # channel-concatenated conditioning: x_embedder's weight is read as [h, patch_dim + condition_features]; dk_mmdit_bind sees a bare
+        # pointer, so the column count is checked here, before anything is bound (a narrower weight would be read out of bounds)
+        from .config import validate_condition_features
+        try:
+            validate_condition_features(config)
+        except ValueError as e:
+            raise _lib.DkHipError(str(e)) from None
+        self.condition_features = int(config.condition_features)
+        xw = packed_weights.get("x_embedder.proj.weight")
+        if xw is not None and (xw.dim() != 2 or xw.shape[1] != config.patch_dim + self.condition_features):
+            raise _lib.DkHipError(f"x_embedder.proj.weight is {tuple(xw.shape)}: the configuration (patch_dim {config.patch_dim}, condition_features "
+                                  f"{self.condition_features}) needs {config.patch_dim + self.condition_features} columns")
+        if self.condition_features:
+            _lib.check(self.lib.dk_mmdit_set_condition_width(self._h, self.condition_features), "dk_mmdit_set_condition_width")
+        self._cond_cached = False
         self.weights = packed_weights  # keep the device tensors alive
         for name, t in packed_weights.items():
             want = torch.uint8 if name.endswith(".weight_fp8") else torch.float32 if name.endswith(".wscale") else self.dtype
@@ -138,6 +153,7 @@ class MMDiTEngine:
         self._n_cached = 0
         self._ctx_cached = False
         self._ref_cached = False
+        self._cond_cached = False
 
     @property
     def batch(self):
@@ -205,6 +221,19 @@ class MMDiTEngine:
             raise _lib.DkHipError(f"reference tokens shape {tuple(t.shape)} != {want}")
         _lib.check(self.lib.dk_mmdit_cache_reference(self._h, t.data_ptr(), int(bool(per_image)), _stream()), "dk_mmdit_cache_reference")
         self._ref_cached = True
+
+    def cache_condition(self, tokens: Tensor, per_image: bool = False) -> None:
+        """Channel-concatenated conditioning (FLUX.1 Fill / Canny / Depth, include/dk_hip.h): the condition token rows
+        (``ops.fill_condition_tokens``), bf16 [n, S_i, condition_features]; n = batch with ``per_image``, else 1 (one condition for every
+        batch row).  Their share of x_embedder is computed once here and added in every later forward."""
+        if self._shape is None or not self.condition_features:
+            raise _lib.DkHipError("cache_condition() needs a configuration with condition_features > 0 and prepare() first")
+        _require_cuda(tokens, "condition tokens", self.dtype)
+        want = (self._shape[0] if per_image else 1, self.tokens_shape()[1], self.condition_features)
+        if tuple(tokens.shape) != want:
+            raise _lib.DkHipError(f"condition tokens shape {tuple(tokens.shape)} != {want}")
+        _lib.check(self.lib.dk_mmdit_cache_condition(self._h, tokens.data_ptr(), int(bool(per_image)), _stream()), "dk_mmdit_cache_condition")
+        self._cond_cached = True
 
     def forward_tokens(self, tokens_in: Tensor, text: Optional[Tensor], step_index: int, tokens_out: Optional[Tensor] = None) -> Tensor:
         """MMDiT.__call__ between patchify and unpatchify (mmdit.py:188-252).  ``text=None`` uses ``cache_context``'s result."""

@@ -134,7 +134,12 @@ def flux_checkpoint_to_reference(sd: StateDict, cfg: MMDiTConfig) -> StateDict:
     w = out.get("x_embedder.proj.weight")
     if w is None:
         raise CheckpointError("img_in.weight missing")
-    out["x_embedder.proj.weight"] = w.reshape(w.shape[0], 1, 1, w.shape[1])  # Linear 64->h as a 1x1 conv (:306-308)
+    if w.dim() != 2 or w.shape[1] != cfg.patch_dim + cfg.condition_features:
+        # FLUX.1 Fill / Canny / Depth widen img_in by the condition's features (config.FLUX_FILL_DEV / FLUX_CONTROL_DEV)
+        raise CheckpointError(f"img_in.weight has {tuple(w.shape)[-1]} input columns = {cfg.patch_dim} + a condition width of "
+                              f"{tuple(w.shape)[-1] - cfg.patch_dim}, but the configuration's condition_features is {cfg.condition_features} "
+                              f"(it expects {cfg.patch_dim + cfg.condition_features} columns)")
+    out["x_embedder.proj.weight"] = w.reshape(w.shape[0], 1, 1, w.shape[1])  # Linear 64 (+ condition_features) -> h as a 1x1 conv (:306-308)
     _check_mmdit_complete(out, cfg)
     return out
 

@@ -566,6 +566,44 @@ def image_composite(dec: Tensor, orig: Tensor, mask: Tensor) -> Tensor:
     return out
 
 
+def image_mask_out(image: Tensor, mask: Tensor) -> Tensor:
+    """dk_image_mask_out_f32: image uint8 [n, H, W, 3], mask uint8 [H, W] / [1 or n, H, W] (255 = repaint) -> f32 [n, H, W, 3] =
+    (image / 255 * 2 - 1) * (1 - mask / 255), the bits of that numpy float32 expression: the image FLUX.1 Fill's encoder may look at."""
+    _require_cuda(image, "image", torch.uint8)
+    _require_cuda(mask, "mask", torch.uint8)
+    if image.dim() != 4 or image.shape[-1] != 3:
+        raise ValueError(f"image must be [n, H, W, 3], got {tuple(image.shape)}")
+    n, H, W, _ = image.shape
+    if mask.dim() not in (2, 3) or tuple(mask.shape[-2:]) != (H, W) or (mask.dim() == 3 and mask.shape[0] not in (1, n)):
+        raise ValueError(f"mask {tuple(mask.shape)} does not match the images {tuple(image.shape)}: [H, W] or [1 or n, H, W]")
+    n_mask = mask.shape[0] if mask.dim() == 3 else 1
+    out = torch.empty(n, H, W, 3, dtype=torch.float32, device=image.device)
+    _lib.check(_lib.load().dk_image_mask_out_f32(image.data_ptr(), mask.data_ptr(), out.data_ptr(), n, n_mask, H, W, _stream()),
+               "dk_image_mask_out_f32")
+    return out
+
+
+def fill_condition_tokens(z: Tensor, mask: Optional[Tensor] = None, patch: int = 2) -> Tensor:
+    """dk_fill_condition_tokens: the condition latent z f32 [n, Hl, Wl, C] (+ mask uint8 [8 Hl, 8 Wl] / [1 or n, 8 Hl, 8 Wl]) -> bf16
+    [n, S_i, patch^2 C (+ 64 patch^2)]: the latent's patch features in (c, ph, pw) order, then (FLUX.1 Fill) the mask / 255 in its 8 x 8
+    pixel-unshuffled, patchified order (include/dk_hip.h).  No mask: FLUX.1 Canny / Depth's layout."""
+    _require_cuda(z, "z", torch.float32)
+    if z.dim() != 4 or z.shape[1] % patch or z.shape[2] % patch:
+        raise ValueError(f"z must be [n, Hl, Wl, C] with sides divisible by the patch size {patch}, got {tuple(z.shape)}")
+    n, Hl, Wl, Cc = z.shape
+    n_mask = 0
+    if mask is not None:
+        _require_cuda(mask, "mask", torch.uint8)
+        if mask.dim() not in (2, 3) or tuple(mask.shape[-2:]) != (8 * Hl, 8 * Wl) or (mask.dim() == 3 and mask.shape[0] not in (1, n)):
+            raise ValueError(f"mask {tuple(mask.shape)} does not match the latent {tuple(z.shape)}: [8 Hl, 8 Wl] or [1 or n, 8 Hl, 8 Wl]")
+        n_mask = mask.shape[0] if mask.dim() == 3 else 1
+    width = patch * patch * Cc + (64 * patch * patch if mask is not None else 0)
+    out = torch.empty(n, (Hl // patch) * (Wl // patch), width, dtype=BF, device=z.device)
+    _lib.check(_lib.load().dk_fill_condition_tokens(z.data_ptr(), None if mask is None else mask.data_ptr(), out.data_ptr(), n, n_mask, Hl, Wl,
+                                                    Cc, int(patch), _stream()), "dk_fill_condition_tokens")
+    return out
+
+
 def groupnorm(x: Tensor, gamma: Tensor, beta: Tensor, groups: int, eps: float, silu: bool) -> Tensor:
     """x: NHWC [B,H,W,C], bf16 or float16 (gamma / beta in the same type)."""
     lib = _lib.load()

@@ -172,6 +172,85 @@ _REFERENCE_NEEDS_ROPE = ("reference_image_path needs a FLUX-family pipeline: the
                          "position index, and the SD3 family has no RoPE")
 
 
+CONDITION_FEATURES = {"fill": 320, "control": 64}  # condition= of FluxPipeline -> MMDiTConfig.condition_features (FLUX_FILL_DEV / FLUX_CONTROL_DEV)
+
+
+_CONDITION_NEEDS_FLUX = ("channel-concatenated conditioning (condition / condition_image_path / condition_mask_path) needs a FLUX-family pipeline: "
+                         "FLUX.1 Fill / Canny / Depth are FLUX.1-dev checkpoints, and the SD3 family's x_embedder has no condition columns")
+
+
+def check_condition_kind(kind, is_flux: bool) -> None:
+    """``condition=`` of a pipeline's constructor: None, or "fill" / "control" on the FLUX family.  Needs no GPU."""
+    if kind is None:
+        return
+    if not is_flux:
+        raise ValueError(_CONDITION_NEEDS_FLUX)
+    if kind not in CONDITION_FEATURES:
+        raise ValueError(f"unknown condition {kind!r} (fill | control)")
+
+
+def check_condition_args(kind, condition_image, condition_mask, reference, is_flux: bool) -> None:
+    """The rules of channel-concatenated conditioning (``FluxPipeline(condition=)``, ``condition_image_path=`` / ``condition_mask_path=``), checked
+    before any GPU work; ``kind`` is the pipeline's ``condition``.  Needs no GPU."""
+    if kind is None and condition_image is None and condition_mask is None:
+        return
+    if not is_flux:
+        raise ValueError(_CONDITION_NEEDS_FLUX)
+    if kind is None:
+        raise ValueError("condition_image_path / condition_mask_path need a pipeline built with condition='fill' or condition='control' "
+                         "(its x_embedder weight carries the condition's columns)")
+    check_condition_kind(kind, is_flux)
+    if condition_image is None:
+        raise ValueError(f"a pipeline built with condition={kind!r} needs condition_image_path in every call: the model was trained to see it")
+    if kind == "fill" and condition_mask is None:
+        raise ValueError("condition='fill' needs condition_mask_path: the mask says where to repaint (255) and what to keep (0)")
+    if kind == "control" and condition_mask is not None:
+        raise ValueError("condition='control' takes no condition_mask_path: the control image (edges, depth) conditions the whole picture")
+    if reference is not None:
+        raise ValueError("reference_image_path cannot be combined with condition_image_path: the engine carries one kind of image conditioning at a time")
+
+
+def _mask_hw(mask):
+    """(H, W) of a mask as ``read_mask`` takes it, without resizing anything"""
+    if isinstance(mask, np.ndarray):
+        return tuple(mask.shape[:2])
+    img = _open_image(mask)
+    return (img.height, img.width)
+
+
+def read_condition_images(image, mask, size, n_img: int):
+    """``condition_image_path`` / ``condition_mask_path`` -> (uint8 [1 or n_img, H, W, 3], uint8 [1 or n_img, H, W] or None): a path, a PIL image or an
+    array each, or a list with one per image.  ``size`` = (H, W) of the output; nothing is resized, any other size raises.  Needs no GPU."""
+    H, W = int(size[0]), int(size[1])
+
+    def many(value, what):
+        if isinstance(value, (list, tuple)):
+            if len(value) != n_img:
+                raise ValueError(f"{len(value)} condition {what}s for {n_img} images: give one, or one per image")
+            return list(value)
+        return [value]
+
+    def one_image(v):
+        arr = np.array(_open_image(v))
+        if arr.ndim == 2:
+            arr = np.repeat(arr[:, :, None], 3, axis=2)
+        arr = arr[:, :, :3]
+        if arr.dtype != np.uint8 or arr.shape != (H, W, 3):
+            raise ValueError(f"the condition image is {arr.shape[0]}x{arr.shape[1]} ({arr.dtype}), the output {H}x{W}: it must be uint8 RGB of the "
+                             "output's size (it is not resized here)")
+        return np.ascontiguousarray(arr)
+
+    def one_mask(v):
+        if _mask_hw(v) != (H, W):
+            raise ValueError(f"the condition mask is {_mask_hw(v)[0]}x{_mask_hw(v)[1]}, the output {H}x{W}: it must have the output's size (it is not "
+                             "resized here)")
+        return read_mask(v, (H, W))
+
+    images = np.stack([one_image(v) for v in many(image, "image")], 0)
+    masks = None if mask is None else np.stack([one_mask(v) for v in many(mask, "mask")], 0)
+    return images, masks
+
+
 def _affine(x: Tensor, a: float, b: float) -> Tensor:
     x = x.contiguous()
     y = torch.empty_like(x)
@@ -202,13 +281,19 @@ class DiffusionPipeline:
         packed_weights: Optional[dict] = None,
         activation_dtype: Optional[str] = None,
         vae_dtype: Optional[str] = None,
+        condition: Optional[str] = None,
     ):
-        """``vae_dtype``: element type of the VAE decoder and (built on first use, img2img) encoder -- None or "bfloat16": bf16, today's
+        """``condition`` (FluxPipeline only): None, "fill" (FLUX.1 Fill) or "control" (FLUX.1 Canny / Depth) -- channel-concatenated conditioning: the
+        model's x_embedder is 64 + 320 / 64 + 64 columns wide (``config.FLUX_FILL_DEV`` / ``FLUX_CONTROL_DEV``; a ``mmdit_config`` of the caller's
+        gets that width), and every call must name its ``condition_image_path`` (see ``denoise_latents``).
+        ``vae_dtype``: element type of the VAE decoder and (built on first use, img2img) encoder -- None or "bfloat16": bf16, today's
         behaviour bit for bit, also together with ``activation_dtype="float16"``; "float16": fp16 weights, activations and image tail.  It is the
         VAE's own switch and is accepted for every family: float16 is the reference's decoder dtype for Stable Diffusion 3
         (mlx/__init__.py:108-113,483-484), not for FLUX (bf16 there); the reference's encoder runs in fp32, so the fp16 encoder is the closer
         16-bit form, not its dtype.  ``packed_weights["vae_decoder"]`` / ``["vae_encoder"]`` must then hold float16 tensors (pack_vae with a
         float16_vae_config)."""
+        check_condition_kind(condition, self._IS_FLUX)  # (before anything is loaded)
+        self.condition = condition
         _lib.load()  # fail loudly before anything else if the HIP extension is missing
         # The MI355X build computes in bf16 end to end (BASELINE.json configs); w16/a16 are
         # accepted for signature compatibility.  The reference's defaults (w16 = a16 = False) mean fp32 weights / activations
@@ -239,6 +324,10 @@ class DiffusionPipeline:
         self.local_ckpt = local_ckpt
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.mmdit_config = mmdit_config or MODEL_CONFIG[model_version]
+        if condition is not None:
+            from .config import FLUX_CONTROL_DEV, FLUX_FILL_DEV
+            preset = FLUX_FILL_DEV if condition == "fill" else FLUX_CONTROL_DEV
+            self.mmdit_config = preset if mmdit_config is None else replace(mmdit_config, condition_features=preset.condition_features)
         if activation_dtype is not None:
             from .config import validate_activation_dtype
             self.mmdit_config = replace(self.mmdit_config, activation_dtype=activation_dtype)
@@ -393,6 +482,8 @@ class DiffusionPipeline:
         apg_momentum: float = 0.0,
         guidance_interval=None,
         reference_image_path=None,
+        condition_image_path=None,
+        condition_mask_path=None,
     ):
         """mlx/__init__.py:253-292.  ``seed`` may be a list: one image per seed is denoised in a
         single batched step loop (data-parallel sharding hands each rank a list).
@@ -420,7 +511,18 @@ class DiffusionPipeline:
         or a list with one per seed; sides multiples of 16 pixels, never resized): the image is encoded to the VAE posterior's mean, goes through
         ``latent_format.process_in`` and rides behind the image tokens of every model evaluation at RoPE index 1 (``MMDiTEngine.cache_reference``,
         embedded once per call).  It composes with every option above.  ``self.last_reference`` = {"size": (H, W), "tokens": S_r}, or None
-        without the option.  Verified as arithmetic only: no Kontext checkpoint has been run here."""
+        without the option.  Verified as arithmetic only: no Kontext checkpoint has been run here.
+        ``condition_image_path`` / ``condition_mask_path`` (channel-concatenated conditioning, ``FluxPipeline(condition="fill" | "control")``; a path, a
+        PIL image or an array, or a list with one per seed; sides equal to the output's, never resized): the published FLUX sampling code's
+        ``prepare_fill`` / ``prepare_control``.  "control": the prepared control image (edges, depth) is VAE-encoded, goes through ``process_in`` and
+        its 64 patch features are concatenated to the latent's in every model evaluation.  "fill": the image times (1 - mask / 255) is encoded the same
+        way, and 256 more columns carry the mask itself (not binarised; 255 = repaint).  The encoder's posterior MEAN is taken where the published code
+        samples, so the same inputs give the same conditioning whatever the seed.  The condition's share of x_embedder is computed once per call
+        (``MMDiTEngine.cache_condition``); the step loop and every option above are untouched.  Refused before any GPU work: the keywords on a
+        pipeline without ``condition``, a ``condition`` pipeline without them, "fill" without a mask, "control" with one, a reference image at the same
+        time, the SD3 family.  ``self.last_condition`` = {"kind", "features"}, or None.  Verified as arithmetic only: no Fill / Canny / Depth checkpoint
+        has been run here."""
+        check_condition_args(getattr(self, "condition", None), condition_image_path, condition_mask_path, reference_image_path, self._IS_FLUX)
         if reference_image_path is not None and not self._IS_FLUX:
             raise ValueError(_REFERENCE_NEEDS_ROPE)
         guide = _guidance_options(guidance, guidance_rescale, apg_eta, apg_norm_threshold, apg_momentum, guidance_interval, cfg_weight)
@@ -433,6 +535,10 @@ class DiffusionPipeline:
         seeds = list(seed) if isinstance(seed, (list, tuple)) else [seed]
         logger.info(f"Seed: {seeds}")
         refs = None if reference_image_path is None else _read_references(reference_image_path, len(seeds))  # (raises before any GPU work)
+        cond_px = None
+        if condition_image_path is not None:  # (the same)
+            out_hw = (latent_size[0] * 8, latent_size[1] * 8) if image_path is None else read_image_u8(image_path).shape[:2]  # (img2img: the image's)
+            cond_px = read_condition_images(condition_image_path, condition_mask_path, out_hw, len(seeds))
         x_T = self.get_empty_latent(*latent_size)
         if image_path is None:
             denoise = 1.0
@@ -465,6 +571,11 @@ class DiffusionPipeline:
             extra_args["reference"] = self.latent_format.process_in(self.encode_reference_to_latents(refs))
             p = self.mmdit_config.patch_size
             self.last_reference = {"size": tuple(refs.shape[1:3]), "tokens": (refs.shape[1] // (8 * p)) * (refs.shape[2] // (8 * p))}
+        self.last_condition, self._condition_pixels = None, None
+        if cond_px is not None:
+            extra_args["condition"] = self.condition_tokens(*cond_px)
+            self.last_condition = {"kind": self.condition, "features": int(extra_args["condition"].shape[-1])}
+            self._condition_pixels = cond_px
         noise_scaled = self.sampler.noise_scaling(np.float32(sigmas[0]), noise, x_T, self.max_denoise(sigmas))
         x0 = torch.from_numpy(np.ascontiguousarray(noise_scaled, dtype=np.float32)).to(self.device)
         denoiser = CFGDenoiser(self)
@@ -505,6 +616,8 @@ class DiffusionPipeline:
         apg_momentum: float = 0.0,
         guidance_interval=None,
         reference_image_path=None,
+        condition_image_path=None,
+        condition_mask_path=None,
     ):
         """mlx/__init__.py:294-534: returns (PIL.Image, log).  ``mask_path``: inpainting, see ``denoise_latents``; with ``composite`` the pixels
         the mask keeps are pasted back from the input image after decoding (the VAE round trip alone does not reproduce them).
@@ -513,7 +626,10 @@ class DiffusionPipeline:
         ``guidance``, ``guidance_rescale``, ``apg_eta``, ``apg_norm_threshold``, ``apg_momentum``, ``guidance_interval``: see ``denoise_latents``; with any
         of them set, ``log["denoising"]["guidance"]`` is ``self.last_guidance``.
         ``reference_image_path``: reference-image conditioning, see ``denoise_latents``; with it set, ``log["denoising"]["reference"]`` is
-        ``self.last_reference``."""
+        ``self.last_reference``.
+        ``condition_image_path`` / ``condition_mask_path``: channel-concatenated conditioning, see ``denoise_latents``; ``log["denoising"]["condition"]`` is
+        ``self.last_condition``.  With ``composite`` and no ``mask_path``, the pixels a fill mask keeps are pasted back from the condition image."""
+        check_condition_args(getattr(self, "condition", None), condition_image_path, condition_mask_path, reference_image_path, self._IS_FLUX)
         if mask_path is not None and image_path is None:
             raise ValueError("mask_path needs image_path: the mask says which part of that image to keep")
         assert latent_size[0] % 2 == 0, f"Height must be divisible by 16 ({latent_size[0]*8}/16={latent_size[0]/2})"
@@ -548,7 +664,8 @@ class DiffusionPipeline:
             latent_size=latent_size, seed=seed, image_path=image_path, denoise=denoise, mask_path=mask_path, block_cache=block_cache,
             sampler=sampler, guidance=guidance, guidance_rescale=guidance_rescale, apg_eta=apg_eta, apg_norm_threshold=apg_norm_threshold,
             apg_momentum=apg_momentum, guidance_interval=guidance_interval,
-            **({} if reference_image_path is None else {"reference_image_path": reference_image_path}))
+            **({} if reference_image_path is None else {"reference_image_path": reference_image_path}),
+            **({} if condition_image_path is None else {"condition_image_path": condition_image_path, "condition_mask_path": condition_mask_path}))
         torch.cuda.synchronize(dev)
         log["denoising"]["post"] = mem()
         log["peak_memory"] = max(log["peak_memory"], log["denoising"]["post"]["peak_memory"])
@@ -561,6 +678,8 @@ class DiffusionPipeline:
             log["denoising"]["guidance"] = self.last_guidance
         if reference_image_path is not None:
             log["denoising"]["reference"] = self.last_reference
+        if condition_image_path is not None:
+            log["denoising"]["condition"] = self.last_condition
 
         torch.cuda.reset_peak_memory_stats(dev)
         t0 = time.time()
@@ -568,6 +687,10 @@ class DiffusionPipeline:
         _, u8, _ = self.decoder.decode(latents)
         if mask_path is not None and composite:
             u8 = self.composite_image(u8, image_path, mask_path)
+        elif condition_mask_path is not None and composite:  # (fill: the kept pixels of the condition image, at the size they came in)
+            from . import ops
+            px, masks = self._condition_pixels
+            u8 = ops.image_composite(u8.contiguous(), torch.from_numpy(px).to(u8.device), torch.from_numpy(masks).to(u8.device))
         torch.cuda.synchronize(dev)
         log["decoding"]["post"] = mem()
         log["peak_memory"] = max(log["peak_memory"], log["decoding"]["post"]["peak_memory"])
@@ -624,11 +747,27 @@ class DiffusionPipeline:
         noise = torch.from_numpy(self.get_noise(seed, mean_like)).to(self.device)
         return self.encoder.sample(moments, noise)
 
+    def condition_tokens(self, images: np.ndarray, masks: Optional[np.ndarray]) -> Tensor:
+        """``read_condition_images``' arrays -> the condition token rows bf16 [1 or n, S_i, condition_features] on the device (published FLUX sampling
+        code: prepare_fill / prepare_control, with the posterior's mean in place of a sample).  No masks: the control layout."""
+        from . import ops
+        if masks is None:
+            image = torch.from_numpy((images.astype(np.float32) / 255) * 2 - 1.0).to(self.device)
+            return ops.fill_condition_tokens(self.latent_format.process_in(self.encode_mean_latents(image)), None, self.mmdit_config.patch_size)
+        n = max(images.shape[0], masks.shape[0])
+        px = torch.from_numpy(np.array(np.broadcast_to(images, (n, *images.shape[1:])))).to(self.device)  # (a copy: one image for several masks)
+        m = torch.from_numpy(masks).to(self.device)
+        z = self.latent_format.process_in(self.encode_mean_latents(ops.image_mask_out(px, m)))
+        return ops.fill_condition_tokens(z, m, self.mmdit_config.patch_size)
+
     def encode_reference_to_latents(self, refs: np.ndarray) -> Tensor:
         """Reference images uint8 [n, H, W, 3] (``_read_references``) -> the MEAN of the VAE posterior, NHWC float32 [n, H/8, W/8, L] on the device:
         the encoder's ``sample`` with a zero noise tensor, so the same reference gives the same conditioning whatever the seed."""
+        return self.encode_mean_latents(torch.from_numpy((refs.astype(np.float32) / 255) * 2 - 1.0).to(self.device))
+
+    def encode_mean_latents(self, image: Tensor) -> Tensor:
+        """``image``: f32 [n, H, W, 3] in [-1, 1] on the device -> the MEAN of the VAE posterior, NHWC float32 [n, H/8, W/8, L]"""
         self.load_vae_encoder()
-        image = torch.from_numpy((refs.astype(np.float32) / 255) * 2 - 1.0).to(self.device)
         moments = self.encoder.encode(image)
         b, h, w, _ = moments.shape
         zeros = torch.zeros(b, h, w, self.vae_encoder_config.out_channels // 2, dtype=torch.float32, device=self.device)
@@ -847,6 +986,17 @@ class _Loop(NamedTuple):
     pooled: Tensor
     timesteps: object
     reference: Optional[Tensor] = None  # the reference latent f32 [1 or n_img, rh, rw, C] behind ``extra_args["reference"]``, or None
+    condition: Optional[Tensor] = None  # the condition token rows bf16 [1 or n_img, S_i, condition_features] behind ``extra_args["condition"]``, or None
+
+
+def _cache_condition(mm, condition: Optional[Tensor], now: int, n_img: int) -> None:
+    """Behind ``_prepare_rows``: the condition's share of x_embedder computed once for those rows, shared or per image like ``_cache_reference``"""
+    if condition is None:
+        return
+    if condition.shape[0] == 1:
+        mm.cache_condition(condition, per_image=False)
+    else:
+        mm.cache_condition(condition.repeat(now // n_img, 1, 1).contiguous(), per_image=True)
 
 
 def _prepare_rows(mm, now: int, latent_hw, text_len: int, n_t: int, reference: Optional[Tensor]) -> None:
@@ -907,6 +1057,10 @@ def _loop_setup(model: "CFGDenoiser", x: Tensor, sigmas, extra_args, guided: boo
             raise ValueError(f"the reference latent {tuple(reference.shape)} does not match the latent {tuple(x.shape)}: [1 or n_img, rh, rw, C]")
     _prepare_rows(mm, now, x.shape[1:3], conditioning.shape[1], len(timesteps), reference)
     _cache_reference(mm, reference, now, n_img)
+    condition = extra_args.get("condition")
+    if condition is not None and (condition.dim() != 3 or condition.shape[0] not in (1, n_img)):
+        raise ValueError(f"the condition tokens {tuple(condition.shape)} do not match {n_img} images: [1 or n_img, S_i, condition_features]")
+    _cache_condition(mm, condition, now, n_img)
     model.cache_modulation_params(pooled[:now], timesteps)
     mm.cache_context(conditioning[:now])  # context_embedder is step-invariant (the reference recomputes it in every call, mmdit.py:195)
 
@@ -921,7 +1075,7 @@ def _loop_setup(model: "CFGDenoiser", x: Tensor, sigmas, extra_args, guided: boo
         x_orig = noise = None
     tok = mm.patchify(x, dup=2 if cfg_on and guided else 1)
     return _Loop(pipe, mm, sigmas, cfg_weight, cfg_on, n_img, policy, x, mask, x_orig, noise, tok, torch.empty_like(tok), conditioning, pooled, timesteps,
-                 reference)
+                 reference, condition)
 
 
 def _set_rows(model: "CFGDenoiser", lp: _Loop, guided: bool):
@@ -930,6 +1084,7 @@ def _set_rows(model: "CFGDenoiser", lp: _Loop, guided: bool):
     now = lp.n_img * (2 if guided else 1)
     _prepare_rows(lp.mm, now, lp.x.shape[1:3], lp.conditioning.shape[1], len(lp.timesteps), lp.reference)
     _cache_reference(lp.mm, lp.reference, now, lp.n_img)
+    _cache_condition(lp.mm, lp.condition, now, lp.n_img)
     model.cache_modulation_params(lp.pooled[:now].contiguous(), lp.timesteps)
     lp.mm.cache_context(lp.conditioning[:now].contiguous())
     tok = lp.mm.patchify(lp.x, dup=2 if guided else 1)

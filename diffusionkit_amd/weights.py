@@ -71,7 +71,7 @@ def synth_mmdit_weights(cfg: MMDiTConfig, seed: int = 1234, device="cpu", dtype=
     h, D, r = cfg.hidden_size, cfg.head_dim, cfg.mlp_ratio
     p = cfg.patch_size
     if cfg.patchify_via_reshape:
-        I.normal("x_embedder.proj.weight", (h, 1, 1, cfg.patch_dim))
+        I.normal("x_embedder.proj.weight", (h, 1, 1, cfg.patch_dim + cfg.condition_features))  # (width 0: the stream it always drew)
     else:
         I.normal("x_embedder.proj.weight", (h, p, p, cfg.vae_latent_dim))
     I.normal("x_embedder.proj.bias", (h,))

@@ -471,6 +471,21 @@ int dk_mask_to_latent_f32(const uint8_t* mask, float* out, int32_t n_mask, int32
 int dk_image_composite_u8(const uint8_t* dec, const uint8_t* orig, const uint8_t* mask, uint8_t* out, int32_t B,
                           int32_t H, int32_t W, int32_t orig_per_image, int32_t mask_per_image, void* stream);
 
+/* Channel-concatenated conditioning (FLUX.1 Fill; published sampling code: prepare_fill), the image the model may look at:
+ * out = a * (1 - m) with a = u8 / 255 * 2 - 1 and m = mask / 255 (not binarised; 1 = repaint), every operation rounded to fp32 on its
+ * own, nothing fused: the bits of the same numpy float32 expression.  image: u8 [n,H,W,3]; mask: u8 [n_mask,H,W], n_mask = 1 (one
+ * mask for every image) or n; out: f32 [n,H,W,3]. */
+int dk_image_mask_out_f32(const uint8_t* image, const uint8_t* mask, float* out, int32_t n, int32_t n_mask, int32_t H, int32_t W,
+                          void* stream);
+/* ... and the condition's token rows (prepare_fill / prepare_control), one launch: z f32 [n,Hl,Wl,C] (the encoded, process_in'ed
+ * condition latent), mask u8 [n_mask,8*Hl,8*Wl] or NULL -> tokens bf16 [n, S_i, p*p*C (+ 64*p*p with a mask)], S_i = (Hl/p)*(Wl/p).
+ * Columns [0, p*p*C): the bits dk_latent_to_tokens(reshape_order = 1) writes for z, features (c, ph, pw).  Columns behind them (Fill):
+ * the mask's 8 x 8 pixel-unshuffle to 64 channels at latent resolution (channel 8*py + px) through the same patchify: for token (i, j),
+ * column p*p*C + p*p*(8*py + px) + p*ph + pw = bf16(mask[8*(p*i + ph) + py, 8*(p*j + pw) + px] / 255).  NULL mask: the control layout
+ * (FLUX.1 Canny / Depth), the latent columns only; n_mask is then ignored. */
+int dk_fill_condition_tokens(const float* z, const uint8_t* mask, void* tokens, int32_t n, int32_t n_mask, int32_t Hl, int32_t Wl,
+                             int32_t C, int32_t patch, void* stream);
+
 /* LatentFormat.process_in/out, __init__.py:729-733: y = x * a + b (f32) */
 int dk_affine_f32(const float* x, float* y, int64_t n, float a, float b, void* stream);
 
@@ -626,7 +641,8 @@ int dk_mmdit_run_blocks(dk_mmdit* m, const void* x_in, void* x_out, int32_t step
 /* read-only view of an internal buffer for parity taps: 0 = joint residual stream [B,S,h],
  * 1 = modulation table [n*B, rows*h], 2 = base of the engine's GEMM K-split workspace (dk_gemm_workspace_bytes() bytes:
  * the fp32 slabs, then the 4096-byte flag region, which is zero between launches); with the first-block cache on, image rows only
- * [B * S_i, h]: 3 = R, 4 = D_ref, 5 = D_cur (the probe's output, between a head and its tail; a compute tail makes it D_ref); NULL with the cache off */
+ * [B * S_i, h]: 3 = R, 4 = D_ref, 5 = D_cur (the probe's output, between a head and its tail; a compute tail makes it D_ref); NULL with the cache off;
+ * 6 = CONDE [B, S_i, h], x_embedder's condition share (dk_mmdit_cache_condition); NULL without a condition width */
 const void* dk_mmdit_debug_buffer(const dk_mmdit* m, int32_t which);
 
 /* ---- first-block cache (opt-in; no reference counterpart) -------------------------------------------------------------------
@@ -673,6 +689,30 @@ int dk_mmdit_reset_block_cache(dk_mmdit* m);
  * launch. */
 int dk_mmdit_set_reference_grid(dk_mmdit* m, int32_t ref_latent_h, int32_t ref_latent_w);
 int dk_mmdit_cache_reference(dk_mmdit* m, const void* ref_tokens, int32_t per_image, void* stream);
+
+/* ---- channel-concatenated conditioning (opt-in; FLUX.1 Fill / Canny / Depth, no counterpart in the reference) ---------------------
+ * These checkpoints are FLUX.1-dev with a wider img_in: x_embedder.proj.weight is [h, F + cond_features] row-major (F = p*p*C), and
+ * every model evaluation embeds cat(tokens, cond_tokens) on the feature axis (published sampling code: prepare_fill / prepare_control);
+ * the model still predicts F features per token.  The condition is step-invariant, so its share of the sum is computed once,
+ * CONDE[b] = cond[b] . W[:, F:]^T (no bias, rounded to bf16), and the x_embedder launch of every evaluation becomes
+ * Linear(tokens [.., F], W with row stride F + cond_features, bias, DK_EPI_RES, residual = CONDE): bf16(bf16(tokens . W[:, :F]^T + bias)
+ * + CONDE).  tokens_in / tokens_out, the step kernels and every other buffer keep their widths.
+ * Verified against an fp32 / bf16-emulating oracle of this layout with synthetic weights (arithmetic parity); no Fill / Canny / Depth
+ * checkpoint has been run through it.
+ *
+ * dk_mmdit_set_condition_width: call before dk_mmdit_prepare (a prepared engine must be prepared again: CONDE is one more carve).  0,
+ * the default, turns the feature off: dk_mmdit_workspace_bytes, the carve and every launch are then what they are without it.
+ * Refused, with no state changed: a width that is not a positive multiple of 64, a configuration with use_pos_embed != 0 (its
+ * positional table holds the residual slot of the x_embedder launch), fp16 activations, a reference grid set at the same time
+ * (dk_mmdit_set_reference_grid refuses the other way round).  dk_mmdit_bind cannot see sizes: the caller must make sure that the bound
+ * x_embedder.proj.weight holds F + cond_features columns (MMDiTEngine checks it before binding).
+ * dk_mmdit_cache_condition: cond_tokens bf16 [batch, S_i, cond_features] (per_image != 0) or [1, S_i, cond_features] (per_image == 0:
+ * one condition for every batch row; one launch per batch row either way, so the bits are those of a repeated condition), as
+ * dk_fill_condition_tokens makes them.  Resets the first-block cache; invalidated by dk_mmdit_prepare.  dk_mmdit_forward,
+ * dk_mmdit_forward_head and dk_mmdit_run_blocks on an engine with a condition width but no cached condition return an error that
+ * names the rule, never launch. */
+int dk_mmdit_set_condition_width(dk_mmdit* m, int32_t cond_features);
+int dk_mmdit_cache_condition(dk_mmdit* m, const void* cond_tokens, int32_t per_image, void* stream);
 /* Head of step `step_index`: dk_mmdit_forward's embedder launches, block 0 and the probe.  probe_out: device float [batch][2] =
  * (num, den) per batch row; before any computed step den is 0 (and num = sum |D_cur|).  Records a pending head for step_index. */
 int dk_mmdit_forward_head(dk_mmdit* m, const void* tokens_in, const void* text, int32_t step_index, float* probe_out, void* stream);
