@@ -121,6 +121,20 @@ bool dk_qknorm_eligible(const P& p) {
                                 (p.qn_col0 < p.kn_col1 && p.kn_col0 < p.qn_col1) || ((uintptr_t)p.qn_w & 15) != 0);
 }
 
+// the operands the shared tail of the 256-column kernels reads beside the accumulators (dk_gemm_tail.h; GemmParams / GemmF8Params): a column
+// split on a tile boundary with its second output, residual and gate where an epilogue of either output reads them, rows of whole 16-byte
+// pieces, 16-byte aligned.  (The outputs' own alignment depends on their kind: the callers check it.)
+template <class P>
+bool dk_gemm_tail_operands_ok(const P& p) {
+  if (p.n_split % 256 != 0 || (p.n_split > 0 && (p.C2 == nullptr || p.n_split >= p.N))) return false;
+  const bool res1 = p.epi == DK_EPI_GATE_RES || p.epi == DK_EPI_RES;
+  const bool res2 = p.n_split > 0 && (p.epi2 == DK_EPI_GATE_RES || p.epi2 == DK_EPI_RES);
+  if ((res1 || res2) && (p.res == nullptr || p.r_seg_len <= 0 || p.ldr % 8 != 0)) return false;
+  if ((p.epi == DK_EPI_GATE_RES || (p.n_split > 0 && p.epi2 == DK_EPI_GATE_RES)) && (p.gate == nullptr || p.gate_seg_len <= 0)) return false;
+  auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
+  return al16(p.res) && al16(p.bias) && al16(p.gate) && (p.gate == nullptr || p.gate_stride % 8 == 0);
+}
+
 // ---- fp8 GEMM (gemm256f8.hip): e4m3 weights with per-output-channel fp32 scales, MX-fp8 activations -------------------
 // C[m, n] = epi(wscale[n] * sum_k A[m, k] * 2^(SA[m, k / 32] - 127) * W[n, k] + bias[n]); same row-segment maps, epilogues,
 // grouped launch and column split as GemmParams.  Strides of A / W and of an MX-fp8 output are in BYTES (= elements).

@@ -38,6 +38,7 @@
 #include <type_traits>
 
 #include "dk_kernels.h"
+#include "dk_gemm_tail.h"
 
 #ifndef DK_F8_ABL
 #define DK_F8_ABL 0  // lab only (timing ablations, results wrong): 1 no scale loads in the K loop, 2 no DMA in it, 4 no fragment reads in it
@@ -387,32 +388,10 @@ __global__ __launch_bounds__(512, 2) void dk_gemm256f8_kernel(GemmF8Params pa, G
     dk_ksplit_release(sp.flags, tile, n_prod, leader);
   }
 
-  // ---------------- tail: accumulators -> LDS (wave-private image) -> row-major ----------------
+  // ---------------- tail: accumulators -> LDS (wave-private image) -> row-major (dk_gemm_tail.h) ----------------
   // All waves passed the last loop barrier after their final ds_read of live data, so the ring is free.
-  const bool out2 = p.n_split > 0 && n0 >= p.n_split;  // tile-uniform: second output of a column-split GEMM
-  void* const Cb = out2 ? p.C2 : p.C;
-  const int ldcb = out2 ? p.ldc2 : p_ldc;
-  const int epi = out2 ? p.epi2 : p.epi;
-  const bool out_mx8 = out2 ? p.c2_mx8 != 0 : p.c_mx8 != 0;
-  const int ncol0 = out2 ? n0 - p.n_split : n0;
-  const bool has_res = epi == DK_EPI_GATE_RES || epi == DK_EPI_RES;
-  auto inside = [&](int len) { return m0 / len == (m0 + T256 - 1) / len; };
-  const bool fast = m0 + T256 <= p_M && inside(p_c_seg_len) && (!has_res || inside(p.r_seg_len)) &&
-                    (epi != DK_EPI_GATE_RES || inside(p.gate_seg_len));
-  const size_t physC0 = (size_t)((m0 / p_c_seg_len) * p.c_seg_stride + (m0 % p_c_seg_len)) + wm * 128;
-  const size_t physR0 = has_res ? (size_t)((m0 / p.r_seg_len) * p.r_seg_stride + (m0 % p.r_seg_len)) + wm * 128 : 0;
-  const bf16_t* gate_row = epi == DK_EPI_GATE_RES ? p.gate + (size_t)(m0 / p.gate_seg_len) * p.gate_stride : nullptr;
-  const unsigned reg0 = (unsigned)wave * 16384u;  // this wave's 16 KiB staging image
-  const int rrow = lane >> 2, rc2 = (lane & 3) * 2;
-
-  auto unpack8 = [](const uint4 v, float* f) {
-    unpack2bf(v.x, f[0], f[1]);
-    unpack2bf(v.y, f[2], f[3]);
-    unpack2bf(v.z, f[4], f[5]);
-    unpack2bf(v.w, f[6], f[7]);
-  };
-
-  // the weight scales and the bias of this lane's 16 columns (4 per 16-column fragment), all loads up front
+  // the weight scales and the bias of this lane's 16 columns (4 per 16-column fragment), all loads up front, in front of the tile set-up (its chain of scalar loads and divisions covers
+  // their latency)
   f32x4 ws_q[4];
   u32x2 bias_q[4] = {u32x2{0u, 0u}, u32x2{0u, 0u}, u32x2{0u, 0u}, u32x2{0u, 0u}};
 #pragma unroll
@@ -420,40 +399,20 @@ __global__ __launch_bounds__(512, 2) void dk_gemm256f8_kernel(GemmF8Params pa, G
     ws_q[nf] = *(const f32x4*)(p.wscale + n0 + wn * 64 + nf * 16 + 4 * q);
     if (p.bias) bias_q[nf] = *(const u32x2*)(p.bias + n0 + wn * 64 + nf * 16 + 4 * q);
   }
-  // Key tile of a q / k / v projection with the fused QKNorm + RoPE (gemm256v3.hip has the bf16 twin): the sum of squares of every
-  // row over its head's columns -- this wave's 64 columns from the accumulators, for 128-column heads plus the partner wave's
-  // through LDS (behind the staging images)
-  const bool qtile = p.qn_w != nullptr && !out2 && n0 >= p.qn_col0 && n0 < p.qn_col1;  // query tile (round 4)
-  const bool kfuse = p.kn_w != nullptr && !out2 && ((n0 >= p.kn_col0 && n0 < p.kn_col1) || qtile);  // tile-uniform
-  const bf16_t* const nw = qtile ? p.qn_w : p.kn_w;
-  constexpr unsigned XCH_OFF = 8u * 16384u;
-  if (kfuse) {
-#pragma unroll
-    for (int mf = 0; mf < 8; ++mf) {
-      float ss = 0.f;
-#pragma unroll
-      for (int nf = 0; nf < 4; ++nf) {
-        float b4[4];
-        unpack2bf(bias_q[nf][0], b4[0], b4[1]);
-        unpack2bf(bias_q[nf][1], b4[2], b4[3]);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float v = round_bf16(acc[nf][mf][e] * ws_q[nf][e] + b4[e]);
-          ss += v * v;
-        }
-      }
-      ss += __shfl_xor(ss, 16, 64);
-      ss += __shfl_xor(ss, 32, 64);
-      if (q == 0) *(__attribute__((address_space(3))) float*)((lds_char*)0 + XCH_OFF + (wave * 128 + mf * 16 + l15) * 4) = ss;
-    }
-    __syncthreads();
-  }
+  DkTailTile t = dk_tail_tile<false>(p, m0, n0, T256, wm * 128, p_M, p_ldc, p_c_seg_len, p_ldr);
+  dk_tail_first_rows<-1>(p, t);
+  const bool out_mx8 = (p.n_split > 0 && n0 >= p.n_split) ? p.c2_mx8 != 0 : p.c_mx8 != 0;
+  const unsigned reg0 = (unsigned)wave * 16384u;  // this wave's 16 KiB staging image
+  const int rrow = lane >> 2;
+
+  // Key tile of a q / k / v projection with the fused QKNorm + RoPE: the sum of squares of every row over its head's columns, from the
+  // accumulators
+  if (t.kfuse) dk_tail_sumsq_exchange<8>(acc, bias_q, [&](int nf, int e) { return ws_q[nf][e]; }, wave, l15, q);
   // the two 32-column halves of the wave tile (compile-time index: the accumulators must stay in registers)
   auto tail_pass = [&](auto ni_c) {
     constexpr int ni = decltype(ni_c)::value;
     // stage round_bf16(wscale * acc + bias) -- what every epilogue starts from -- as bf16: lane owns row mf*16 + l15, columns
-    // (nf & 1)*16 + 4*q + {0..3} of this 32-column half; 64-byte rows, 16-byte chunk c at position c ^ ((row >> 2) & 3)
-    // (conflict-free for these 8-byte writes and the 16-byte read-back)
+    // (nf & 1)*16 + 4*q + {0..3} of this 32-column half
 #pragma unroll
     for (int nf = 0; nf < 2; ++nf) {
       float b4[4];
@@ -462,126 +421,26 @@ __global__ __launch_bounds__(512, 2) void dk_gemm256f8_kernel(GemmF8Params pa, G
       const f32x4 w4 = ws_q[ni * 2 + nf];
 #pragma unroll
       for (int mf = 0; mf < 8; ++mf) {
-        const int row = mf * 16 + l15;
         const f32x4 a = acc[ni * 2 + nf][mf];
         const unsigned lo = pack2bf(a[0] * w4[0] + b4[0], a[1] * w4[1] + b4[1]), hi = pack2bf(a[2] * w4[2] + b4[2], a[3] * w4[3] + b4[3]);
-        *(__attribute__((address_space(3))) u32x2*)((lds_char*)0 + reg0 + row * 64 + (((nf * 2 + (q >> 1)) ^ ((row >> 2) & 3)) << 4) + (q & 1) * 8) = u32x2{lo, hi};
+        *(__attribute__((address_space(3))) u32x2*)((lds_char*)0 + reg0 + dk_tail_stage_off(mf * 16 + l15, nf, q)) = u32x2{lo, hi};
       }
     }
-    const int col = n0 + wn * 64 + ni * 32 + rc2 * 4;      // first of this lane's 8 columns of the GEMM (gate, residual)
-    const int ocol = ncol0 + wn * 64 + ni * 32 + rc2 * 4;  // the same inside the output it goes to
-    float gate8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    // the shared row loop, one pass per call; this kernel's own: the MX-fp8 output
     auto rows = [&](auto fast_c, auto ek_c, auto mx_c, auto kf_c) {
       constexpr bool FAST = decltype(fast_c)::value;
       constexpr bool KF = decltype(kf_c)::value;  // key tile with the fused QKNorm + RoPE (bias-only epilogue, bf16 out)
-      float kw8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      const int kcol = KF ? col % p.kn_D : 0;  // first of this lane's 8 columns inside its head (the ranges start at multiples of 256)
-      if (KF) unpack8(*(const uint4*)(nw + kcol), kw8);
-      constexpr int EK = decltype(ek_c)::value;  // the epilogue as a compile-time constant (straight-line row loop), or -1: `epi`
-      constexpr int MX = decltype(mx_c)::value;  // output: 1 MX-fp8, 0 bf16, -1: `out_mx8`
-      const int ep = EK >= 0 ? EK : epi;
-      const bool hres = EK >= 0 ? (EK == DK_EPI_GATE_RES || EK == DK_EPI_RES) : has_res;
+      constexpr int EK = decltype(ek_c)::value;   // the epilogue as a compile-time constant (straight-line row loop), or -1: `epi`
+      constexpr int MX = decltype(mx_c)::value;   // output: 1 MX-fp8, 0 bf16, -1: `out_mx8`
       const bool omx = MX >= 0 ? MX == 1 : out_mx8;
-      if (FAST && ep == DK_EPI_GATE_RES) unpack8(*(const uint4*)(gate_row + col), gate8);
-      int c_seg = 0, c_rem = 0, r_seg = 0, r_rem = 0, g_seg = 0, g_rem = 0;
-      if (!FAST) {
-        const int ms = mrow0 + rrow;
-        c_seg = ms / p_c_seg_len, c_rem = ms % p_c_seg_len;
-        if (hres) r_seg = ms / p.r_seg_len, r_rem = ms % p.r_seg_len;
-        if (ep == DK_EPI_GATE_RES) g_seg = ms / p.gate_seg_len, g_rem = ms % p.gate_seg_len;
-      }
       // MX-fp8 output on a tile-uniform row map: a lane's eight rows (itr) are the eight 16-row fragments of its 128-row block, and
       // their scale bytes are the eight consecutive bytes of ONE word of the side array (dk_mx_scale_index: byte (r / 16) % 8) --
       // collected in two registers over the (fully unrolled) loop, stored once per lane quad and 32-column half
       unsigned sc_lo = 0u, sc_hi = 0u;
-      // FAST tiles: the residual rows (updated in place: the compiler may not move a row's load above the previous row's store) and the
-      // cos / sin entries of a key tile are fetched BEFORE the row loop -- one memory round trip per pass instead of one per row (round 4,
-      // gemm256v3.hip)
-      constexpr bool PRE_RES = FAST && (EK == DK_EPI_GATE_RES || EK == DK_EPI_RES);
-      constexpr bool PRE_ROPE = FAST && KF;
-      uint4 res_pre[PRE_RES ? 8 : 1];
-      f32x4 rope_pre[PRE_ROPE ? 16 : 1];
-      if (PRE_RES) {
-#pragma unroll
-        for (int itr = 0; itr < 8; ++itr) res_pre[itr] = *(const uint4*)(p.res + (physR0 + itr * 16 + rrow) * (size_t)p_ldr + col);
-      }
-      if (PRE_ROPE) {
-        if (p.kn_rope != nullptr) {
-#pragma unroll
-          for (int itr = 0; itr < 8; ++itr) {
-            const int kpos_ = (mrow0 + itr * 16 + rrow) % p.kn_seg_len;
-            const float* tab = p.kn_rope + ((size_t)(p.kn_pos_off + kpos_) * (size_t)(p.kn_D / 2) + (size_t)(kcol >> 1)) * 2;
-            rope_pre[2 * itr] = *(const f32x4*)tab, rope_pre[2 * itr + 1] = *(const f32x4*)(tab + 4);
-          }
-        }
-      }
-#pragma unroll
-      for (int itr = 0; itr < 8; ++itr) {
-        const int row = itr * 16 + rrow;  // row inside the wave's 128-row block
-        size_t crow = physC0 + row, rrow_phys = physR0 + row;
-        bool valid = true;
-        if (!FAST) {
-          valid = mrow0 + row < p_M;
-          crow = (size_t)c_seg * p.c_seg_stride + c_rem;
-          rrow_phys = (size_t)r_seg * p.r_seg_stride + r_rem;
-          if (ep == DK_EPI_GATE_RES && valid) unpack8(*(const uint4*)(p.gate + (size_t)g_seg * p.gate_stride + col), gate8);
-          for (c_rem += 16; c_rem >= p_c_seg_len; c_rem -= p_c_seg_len) ++c_seg;
-          if (hres)
-            for (r_rem += 16; r_rem >= p.r_seg_len; r_rem -= p.r_seg_len) ++r_seg;
-          if (ep == DK_EPI_GATE_RES)
-            for (g_rem += 16; g_rem >= p.gate_seg_len; g_rem -= p.gate_seg_len) ++g_seg;
-        }
-        const u32x4 sv = *(const __attribute__((address_space(3))) u32x4*)((lds_char*)0 + reg0 + row * 64 + ((((unsigned)rc2 >> 1) ^ ((unsigned)(row >> 2) & 3u)) << 4));
-        if (EK == DK_EPI_BIAS && MX == 0 && !KF) {  // bias only, bf16 out: the staged values ARE the output
-          if (FAST || valid) *(u32x4*)((bf16_t*)Cb + crow * (size_t)ldcb + ocol) = sv;
-          continue;
-        }
-        float vv[8];
-        unpack8(make_uint4(sv[0], sv[1], sv[2], sv[3]), vv);
-        if (KF) {
-          const int kpos = (mrow0 + row) % p.kn_seg_len;  // the row's position inside its sequence
-          float ss = *(const __attribute__((address_space(3))) float*)((lds_char*)0 + XCH_OFF + (wave * 128 + row) * 4);
-          if (p.kn_D == 128) ss += *(const __attribute__((address_space(3))) float*)((lds_char*)0 + XCH_OFF + ((wave ^ 1) * 128 + row) * 4);
-          const float r = rsqrtf(ss / (float)p.kn_D + p.kn_eps);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) vv[e] = round_bf16(vv[e] * r * kw8[e]);
-          if (p.kn_rope != nullptr) {
-            const float* tab = p.kn_rope + ((size_t)(p.kn_pos_off + kpos) * (size_t)(p.kn_D / 2) + (size_t)(kcol >> 1)) * 2;
-            f32x4 t0 = {1.f, 0.f, 1.f, 0.f}, t1 = {1.f, 0.f, 1.f, 0.f};
-            if (PRE_ROPE) t0 = rope_pre[2 * itr], t1 = rope_pre[2 * itr + 1];
-            else if (valid) t0 = *(const f32x4*)tab, t1 = *(const f32x4*)(tab + 4);
-            const float cs[8] = {t0[0], t0[1], t0[2], t0[3], t1[0], t1[1], t1[2], t1[3]};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-              const float c = cs[2 * i], sn = cs[2 * i + 1], xe = vv[2 * i], xo = vv[2 * i + 1];
-              vv[2 * i] = c * xe - sn * xo;
-              vv[2 * i + 1] = sn * xe + c * xo;
-            }
-          }
-        }
-        if (ep == DK_EPI_BIAS_GELU) {
-#pragma unroll
-          for (int e = 0; e < 8; e += 2) {
-            const f32x2 g2 = gelu_erf_f2(f32x2{vv[e], vv[e + 1]});
-            vv[e] = g2[0], vv[e + 1] = g2[1];
-          }
-        } else if (ep == DK_EPI_BIAS_SILU) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) vv[e] = silu_f(vv[e]);
-        } else if (hres) {
-          uint4 rr = make_uint4(0u, 0u, 0u, 0u);
-          if (PRE_RES) rr = res_pre[itr];
-          else if (FAST || valid) rr = *(const uint4*)(p.res + rrow_phys * (size_t)p_ldr + col);
-          float r8[8];
-          unpack8(rr, r8);
-          if (ep == DK_EPI_GATE_RES) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) vv[e] = r8[e] + round_bf16(gate8[e] * vv[e]);
-          } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) vv[e] += r8[e];
-          }
-        }
+      auto store_raw = [&](size_t crow, int ocol, bool ok, u32x4 sv) {
+        if (ok) *(u32x4*)(t.Cb + crow * (size_t)t.ldcb + ocol) = sv;
+      };
+      auto store = [&](int itr, size_t crow, int ocol, bool ok, float* vv) {
         if (omx) {
           // MX-fp8 output: the four lanes of a row hold one 32-column block; values are rounded to bf16 first (what the bf16
           // path would have stored), then quantised -- 8 bytes per lane, one scale byte per block
@@ -589,38 +448,38 @@ __global__ __launch_bounds__(512, 2) void dk_gemm256f8_kernel(GemmF8Params pa, G
           for (int e = 0; e < 8; ++e) vv[e] = round_bf16(vv[e]);
           unsigned e8;
           const uint2 q8 = dk_mx8_quantize8(vv, e8);
-          if (FAST || valid) *(uint2*)((unsigned char*)Cb + crow * (size_t)ldcb + ocol) = q8;
+          if (ok) *(uint2*)((unsigned char*)t.Cb + crow * (size_t)t.ldcb + ocol) = q8;
           if (FAST) {
             if (itr < 4) sc_lo |= e8 << (8 * (itr & 3));
             else sc_hi |= e8 << (8 * (itr & 3));
-          } else if (valid && (lane & 3) == 0) {
+          } else if (ok && (lane & 3) == 0) {
             p.SC[dk_mx_scale_index((unsigned)crow + (unsigned)p.c_row0, (unsigned)(p.sc_kb0 + (ocol >> 5)), (unsigned)p.sc_nblk)] = (unsigned char)e8;
           }
         } else {
-          uint4 o4;
-          o4.x = pack2bf(vv[0], vv[1]);
-          o4.y = pack2bf(vv[2], vv[3]);
-          o4.z = pack2bf(vv[4], vv[5]);
-          o4.w = pack2bf(vv[6], vv[7]);
-          if (FAST || valid) *(uint4*)((bf16_t*)Cb + crow * (size_t)ldcb + ocol) = o4;
+          const uint4 o4 = dk_tail_pack8(vv);
+          store_raw(crow, ocol, ok, u32x4{o4.x, o4.y, o4.z, o4.w});
         }
-      }
+      };
+      dk_tail_rows<FAST, EK, KF, 8, false, 1, MX == 0>(
+          p, t, lane, [&](int) { return DkTailPass{reg0, wn * 64 + ni * 32}; }, [&](int, int, int row) { return dk_tail_sumsq_read(wave, row, p.kn_D); },
+          store, store_raw);
       if (FAST && omx && (lane & 3) == 0) {
         // rows physC0 + c_row0 + rrow + 16 * {0..7}: one aligned 128-row block (the launcher checks the alignment), bytes 0..7
-        const unsigned r0 = (unsigned)physC0 + (unsigned)p.c_row0 + (unsigned)rrow;
-        const unsigned kb = (unsigned)(p.sc_kb0 + (ocol >> 5));
+        const unsigned r0 = (unsigned)t.physC0 + (unsigned)p.c_row0 + (unsigned)rrow;
+        const unsigned kb = (unsigned)(p.sc_kb0 + ((t.ncol0 + wn * 64 + ni * 32) >> 5));
         *(uint2*)(p.SC + dk_mx_scale_index(r0, kb, (unsigned)p.sc_nblk)) = make_uint2(sc_lo, sc_hi);
       }
     };
     using Run = std::integral_constant<int, -1>;
     using No = std::false_type;
     using Yes = std::true_type;
-    if (kfuse) {  // (bias-only epilogue, bf16 out -- checked by the launcher)
-      if (fast)
+    const int epi = t.epi;
+    if (t.kfuse) {  // (bias-only epilogue, bf16 out -- checked by the launcher)
+      if (t.fast)
         rows(Yes{}, std::integral_constant<int, DK_EPI_BIAS>{}, std::integral_constant<int, 0>{}, Yes{});
       else
         rows(No{}, std::integral_constant<int, DK_EPI_BIAS>{}, std::integral_constant<int, 0>{}, Yes{});
-    } else if (fast) {
+    } else if (t.fast) {
       // the model's combinations with epilogue and output kind folded at compile time (no scalar branches inside the row loop)
       if (epi == DK_EPI_BIAS && !out_mx8)
         rows(Yes{}, std::integral_constant<int, DK_EPI_BIAS>{}, std::integral_constant<int, 0>{}, No{});
@@ -641,17 +500,12 @@ __global__ __launch_bounds__(512, 2) void dk_gemm256f8_kernel(GemmF8Params pa, G
 bool dk_gemm256f8_eligible(const GemmF8Params& p) {
   if (p.M <= 0 || p.N % 256 != 0 || p.K % BKB != 0 || p.lda % 16 != 0 || p.ldw % 16 != 0 || p.lda < p.K || p.ldw < p.K) return false;
   if (p.A == nullptr || p.W == nullptr || p.SA == nullptr || p.wscale == nullptr || p.C == nullptr) return false;
-  if (p.n_split % 256 != 0 || (p.n_split > 0 && (p.C2 == nullptr || p.n_split >= p.N))) return false;
-  if (p.a_seg_len <= 0 || p.c_seg_len <= 0) return false;
+  if (!dk_gemm_tail_operands_ok(p) || p.a_seg_len <= 0 || p.c_seg_len <= 0) return false;
   // scale reads: every wave's 128 rows are one aligned 128-row block of the A buffer -- every row range starts on a physical row that is a
   // multiple of 128.  A range may END inside a block (its last block is partial: the DMA clamps to row M - 1, the tail masks rows >= M), so a
   // launch that stays inside its first segment takes any M; only a map of several segments needs whole blocks per segment.
   const bool a_one_seg = p.M <= p.a_seg_len;
   if (p.a_row0 % 128 != 0 || p.sa_nblk <= 0 || (!a_one_seg && (p.a_seg_len % 128 != 0 || p.a_seg_stride % 128 != 0))) return false;
-  const bool res1 = p.epi == DK_EPI_GATE_RES || p.epi == DK_EPI_RES;
-  const bool res2 = p.n_split > 0 && (p.epi2 == DK_EPI_GATE_RES || p.epi2 == DK_EPI_RES);
-  if ((res1 || res2) && (p.res == nullptr || p.r_seg_len <= 0 || p.ldr % 8 != 0)) return false;
-  if ((p.epi == DK_EPI_GATE_RES || (p.n_split > 0 && p.epi2 == DK_EPI_GATE_RES)) && (p.gate == nullptr || p.gate_seg_len <= 0)) return false;
   if ((p.kn_w != nullptr && p.c_mx8) || !dk_qknorm_eligible(p)) return false;  // (the fused QKNorm writes a bf16 first output)
   // outputs: bf16 rows of 16-byte stores, or MX-fp8 rows of 8-byte stores with the scale side array
   auto al = [](const void* q, int a) { return ((uintptr_t)q & (uintptr_t)(a - 1)) == 0; };
@@ -668,7 +522,7 @@ bool dk_gemm256f8_eligible(const GemmF8Params& p) {
     const long c_last = (long)p.c_row0 + (long)((p.M - 1) / p.c_seg_len) * p.c_seg_stride + (p.M - 1) % p.c_seg_len;
     if ((c_last >> 7) >= p.sc_nblk) return false;
   }
-  if (!al(p.res, 16) || !al(p.bias, 16) || !al(p.gate, 16) || !al(p.wscale, 16) || (p.gate != nullptr && p.gate_stride % 8 != 0)) return false;
+  if (!al(p.wscale, 16)) return false;
   // 32-bit byte offsets on the DMA side
   const size_t a_rows = (size_t)((p.M - 1) / p.a_seg_len) * p.a_seg_stride + (size_t)((p.M - 1) % p.a_seg_len) + 1;
   return a_rows * (size_t)p.lda < (1ull << 32) && (size_t)p.ldw * 8 < (1ull << 31);

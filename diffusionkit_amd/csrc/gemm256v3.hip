@@ -40,6 +40,7 @@
 #include <type_traits>
 
 #include "dk_kernels.h"
+#include "dk_gemm_tail.h"
 
 #ifndef DK_V3_ABL
 #define DK_V3_ABL 0  // lab only (scripts/build_lab.sh ABL=n), bit mask: 1 no DMA inside the K loop, 2 no fragment reads inside it, 4 no tile
@@ -513,28 +514,19 @@ __global__ __launch_bounds__(512, 2) void dk_gemm256v3_kernel(GemmParams pa, Gem
   }
   if (!CONV) __builtin_assume(piece < 0);  // (no Linear tile reaches the fp32-image tail path below any more; convolutions still do)
 
-  // ---------------- tail: accumulators -> LDS (wave-private image) -> row-major ----------------
+  // ---------------- tail: accumulators -> LDS (wave-private image) -> row-major (dk_gemm_tail.h) ----------------
   // All waves passed the last loop barrier after their final ds_read, so the ring is free.
-  const bool out2 = p.n_split > 0 && n0 >= p.n_split;  // tile-uniform: second output of a column-split GEMM
-  bf16_t* const Cb = out2 ? p.C2 : p.C;
-  const int ldcb = out2 ? p.ldc2 : p.ldc;
-  const int epi = out2 ? p.epi2 : p.epi;
-  const int ncol0 = out2 ? n0 - p.n_split : n0;
-  const bool has_res = epi == DK_EPI_GATE_RES || epi == DK_EPI_RES;
-  // a tile that lies inside one row segment of every map and inside M evaluates the maps once (scalar unit);
-  // otherwise each lane walks its rows through the maps (fast == false)
-  auto inside = [&](int len) { return m0 / len == (m0 + BM - 1) / len; };
-  const bool fast = m0 + BM <= p.M && inside(p.c_seg_len) && (!has_res || inside(p.r_seg_len)) &&
-                    (epi != DK_EPI_GATE_RES || inside(p.gate_seg_len));
-  const int mrow0 = m0 + wm * HROWS;  // first GEMM row of this wave's block
-  const size_t physC0 = (size_t)((m0 / p.c_seg_len) * p.c_seg_stride + (m0 % p.c_seg_len)) + wm * HROWS;
-  const size_t physR0 = has_res ? (size_t)((m0 / p.r_seg_len) * p.r_seg_stride + (m0 % p.r_seg_len)) + wm * HROWS : 0;
-  const bf16_t* gate_row = epi == DK_EPI_GATE_RES ? p.gate + (size_t)(m0 / p.gate_seg_len) * p.gate_stride : nullptr;
-  // read-back: a lane takes 8 consecutive columns (two 16-byte chunks) of one row, 4 lanes a 32-column row of the
-  // image, 16 rows per step -- one 16-byte global store per lane and step (8-byte stores are issue-bound: half as
-  // many instructions, guide T21).  Image swizzle chunk ^ ((row >> 1) & 7): conflict-free for the staging writes
-  // (16 rows x one chunk per 16 lanes) and for these reads (4 rows x 4 even / odd chunks per 16 lanes).
-  const int rrow = lane >> 2, rc2 = (lane & 3) * 2;
+  // whole tiles: the bias of this lane's 16 columns (4 per 16-column fragment), all loads up front -- one latency, not one per pass,
+  // and in front of the tile set-up, whose chain of scalar loads and divisions covers it
+  u32x2 bias_q[4] = {u32x2{0u, 0u}, u32x2{0u, 0u}, u32x2{0u, 0u}, u32x2{0u, 0u}};
+  if (piece < 0 && p.bias && col_ok) {
+#pragma unroll
+    for (int nf = 0; nf < 4; ++nf) bias_q[nf] = *(const u32x2*)(p.bias + n0 + wn * 64 + nf * 16 + 4 * q);
+  }
+  DkTailTile t = dk_tail_tile<false>(p, m0, n0, BM, wm * HROWS, p.M, p.ldc, p.c_seg_len, p.ldr);
+  dk_tail_first_rows<-1>(p, t);
+  t.kfuse = !CONV && piece < 0 && t.kfuse;  // (a whole Linear tile)
+  const int rrow = lane >> 2, rc2 = (lane & 3) * 2;  // read-back: this lane's row of a 16-row step and its first 16-byte chunk of an fp32 image row
 
   // split tile (convolutions): a producer stores its fp32 partial tile image to its slab; the finisher first waits for every producer of
   // the tile (dk_ksplit.h)
@@ -543,47 +535,23 @@ __global__ __launch_bounds__(512, 2) void dk_gemm256v3_kernel(GemmParams pa, Gem
   auto leader = [&] { return tid == 0; };
   if (piece == 0 && !(DK_V3_ABL & 16)) dk_ksplit_wait(sp.flags, rt, n_prod, sp.error_word, leader);
 
-  auto unpack8 = [](const uint4 v, float* f) {
-    unpack2(v.x, f[0], f[1]);
-    unpack2(v.y, f[2], f[3]);
-    unpack2(v.z, f[4], f[5]);
-    unpack2(v.w, f[6], f[7]);
+  // Key tile of a q / k / v projection with the fused QKNorm + RoPE: the sum of squares of every row over its head's columns, from the
+  // accumulators
+  if (t.kfuse) dk_tail_sumsq_exchange<MF>(acc, bias_q, [&](int, int) { return p.alpha; }, wave, l15, q);
+  // how a finished row leaves
+  auto store_raw = [&](size_t crow, int ocol, bool ok, u32x4 sv) {
+    // (lab: 32 = the C stores sit behind a condition that is false at run time -- the work stays, the traffic goes)
+    if (((DK_V3_ABL & 32) ? p.alpha == -1234.5f : true) && ok) *(u32x4*)(t.Cb + crow * (size_t)t.ldcb + ocol) = sv;
   };
-
-  // whole tiles: the bias of this lane's 16 columns (4 per 16-column fragment), all loads up front -- one latency, not one per pass
-  u32x2 bias_q[4] = {u32x2{0u, 0u}, u32x2{0u, 0u}, u32x2{0u, 0u}, u32x2{0u, 0u}};
-  if (piece < 0 && p.bias && col_ok) {
-#pragma unroll
-    for (int nf = 0; nf < 4; ++nf) bias_q[nf] = *(const u32x2*)(p.bias + n0 + wn * 64 + nf * 16 + 4 * q);
-  }
-  // Key tile of a q / k / v projection with the fused QKNorm + RoPE: the sum of squares of every row over its head's columns --
-  // this wave's 64 columns from the accumulators (same bf16-rounded values that get staged), for 128-column heads plus the
-  // partner wave's 64 through LDS (behind the staging images)
-  const bool qtile = !CONV && p.qn_w != nullptr && n0 >= p.qn_col0 && n0 < p.qn_col1;  // query tile (round 4): same treatment, own weight
-  const bool kfuse = !CONV && p.kn_w != nullptr && piece < 0 && ((n0 >= p.kn_col0 && n0 < p.kn_col1) || qtile);  // tile-uniform
-  const bf16_t* const nw = qtile ? p.qn_w : p.kn_w;
-  constexpr unsigned XCH_OFF = 8u * 16384u;
-  if (kfuse) {
-#pragma unroll
-    for (int mf = 0; mf < MF; ++mf) {
-      float ss = 0.f;
-#pragma unroll
-      for (int nf = 0; nf < 4; ++nf) {
-        float b4[4];
-        unpack2(bias_q[nf][0], b4[0], b4[1]);
-        unpack2(bias_q[nf][1], b4[2], b4[3]);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float v = round_act(acc[nf][mf][e] * p.alpha + b4[e]);
-          ss += v * v;
-        }
-      }
-      ss += __shfl_xor(ss, 16, 64);
-      ss += __shfl_xor(ss, 32, 64);
-      if (q == 0) *(__attribute__((address_space(3))) float*)((lds_char*)0 + XCH_OFF + (wave * 128 + mf * 16 + l15) * 4) = ss;
-    }
-    __syncthreads();
-  }
+  auto store = [&](int, size_t crow, int ocol, bool ok, const float* vv) {
+    const uint4 o4 = dk_tail_pack8(vv);
+    const u32x4 ov = {o4.x, o4.y, o4.z, o4.w};
+#if DK_V3_NT_STORE
+    if (((DK_V3_ABL & 32) ? p.alpha == -1234.5f : true) && ok) __builtin_nontemporal_store(ov, (u32x4*)(t.Cb + crow * (size_t)t.ldcb + ocol));
+#else
+    store_raw(crow, ocol, ok, ov);
+#endif
+  };
   // the two 32-column halves of the wave tile (compile-time index: the accumulators must stay in registers)
   // (STAGE / EMIT: a whole tile stages BOTH halves -- two 8 KiB bf16 images per wave -- before it reads the first one back: one
   //  LDS round trip of latency per tile instead of two; a split tile's 16 KiB fp32 image holds one half at a time)
@@ -592,9 +560,8 @@ __global__ __launch_bounds__(512, 2) void dk_gemm256v3_kernel(GemmParams pa, Gem
     constexpr bool STAGE = decltype(stage_c)::value, EMIT = decltype(emit_c)::value;
     const unsigned reg0 = (unsigned)wave * 16384u + ((STAGE && EMIT) ? 0u : (unsigned)ni * 8192u);  // this pass's image
     // stage: lane owns row mf*16 + l15, columns (nf & 1)*16 + 4*q + {0..3} of this 32-column half.  A whole tile (no K split)
-    // stages round_act(alpha * acc + bias) -- what every epilogue starts from -- as bf16: half the LDS bytes of the fp32 image
-    // (64-byte rows, 16-byte chunk c at position c ^ ((row >> 2) & 3): conflict-free for these 8-byte writes and the 16-byte
-    // read-back); split tiles stage the fp32 partial sums (128-byte rows)
+    // stages round_act(alpha * acc + bias) -- what every epilogue starts from -- as bf16: half the LDS bytes of the fp32 image;
+    // split tiles stage the fp32 partial sums (128-byte rows, 16-byte chunk c at position c ^ ((row >> 1) & 7))
     const bool bf_stage = piece < 0;
     if (!STAGE) {
     } else if (bf_stage) {
@@ -605,12 +572,11 @@ __global__ __launch_bounds__(512, 2) void dk_gemm256v3_kernel(GemmParams pa, Gem
         unpack2(bias_q[ni * 2 + nf][1], b4[2], b4[3]);
 #pragma unroll
         for (int mf = 0; mf < MF; ++mf) {
-          const int row = mf * 16 + l15;
           const f32x4 a = acc[ni * 2 + nf][mf];
           uint2 w;
           w.x = pack2(a[0] * p.alpha + b4[0], a[1] * p.alpha + b4[1]);
           w.y = pack2(a[2] * p.alpha + b4[2], a[3] * p.alpha + b4[3]);
-          *(__attribute__((address_space(3))) u32x2*)((lds_char*)0 + reg0 + row * 64 + (((nf * 2 + (q >> 1)) ^ ((row >> 2) & 3)) << 4) + (q & 1) * 8) = u32x2{w.x, w.y};
+          *(__attribute__((address_space(3))) u32x2*)((lds_char*)0 + reg0 + dk_tail_stage_off(mf * 16 + l15, nf, q)) = u32x2{w.x, w.y};
         }
       }
     } else {
@@ -624,194 +590,91 @@ __global__ __launch_bounds__(512, 2) void dk_gemm256v3_kernel(GemmParams pa, Gem
     }
     // (same wave writes and reads the image: program order + the compiler's lgkmcnt suffice)
     if (!EMIT || !col_ok) return;
-    const int col = n0 + wn * 64 + ni * 32 + rc2 * 4;      // first of this lane's 8 columns of the GEMM (bias, gate, residual)
-    const int ocol = ncol0 + wn * 64 + ni * 32 + rc2 * 4;  // the same inside the output it goes to
-    float bias8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, gate8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (p.bias && piece == 0) unpack8(*(const uint4*)(p.bias + col), bias8);  // (whole tiles: the bias went in before staging)
-    // the row loop is instantiated twice -- tile-uniform maps (FAST) or a per-lane walk through the maps -- so that
-    // the common case keeps its short body (one v_add per address, batched loads)
-    auto rows = [&](auto fast_c, auto bf_c, auto ek_c, auto kf_c) {
+    const int coff = wn * 64 + ni * 32;  // first of this pass's 32 columns inside the tile
+    // whole tile: the shared row loop, one pass per call.  It is instantiated per form -- tile-uniform maps (FAST) or a per-lane walk through
+    // the maps -- so that the common case keeps its short body (one v_add per address, batched loads)
+    auto rows = [&](auto fast_c, auto ek_c, auto kf_c) {
+      dk_tail_rows<decltype(fast_c)::value, decltype(ek_c)::value, decltype(kf_c)::value, MF, false, 1, true>(
+          p, t, lane, [&](int) { return DkTailPass{reg0, coff}; }, [&](int, int, int row) { return dk_tail_sumsq_read(wave, row, p.kn_D); }, store, store_raw);
+    };
+    // split tile (convolutions): the fp32 image keeps a row loop of its own on the shared per-row pieces -- a producer stores its rows to its
+    // slab and is done; the finisher adds the slabs, and the bias goes in after the sum (run-time epilogue, no fused norm)
+    auto split_rows = [&](auto fast_c) {
       constexpr bool FAST = decltype(fast_c)::value;
-      constexpr bool KF = decltype(kf_c)::value;  // key tile with the fused QKNorm + RoPE (bf16 image, bias-only epilogue)
-      constexpr bool BF = decltype(bf_c)::value;  // bf16 image of a whole tile / fp32 image of a split tile
-      constexpr int EK = decltype(ek_c)::value;   // the epilogue as a compile-time constant (straight-line row loop), or -1: `epi`
-      constexpr bool PLAIN = BF && EK == DK_EPI_BIAS && !KF;  // a bias-only epilogue on a bf16 image: the staged values ARE the output
-      float kw8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      const int kcol = KF ? col % p.kn_D : 0;  // first of this lane's 8 columns inside its head (the ranges start at multiples of 256)
-      if (KF) unpack8(*(const uint4*)(nw + kcol), kw8);
-      const int ep = EK >= 0 ? EK : epi;
-      const bool hres = EK >= 0 ? (EK == DK_EPI_GATE_RES || EK == DK_EPI_RES) : has_res;
-      if (FAST && ep == DK_EPI_GATE_RES) unpack8(*(const uint4*)(gate_row + col), gate8);
-      // row walk of the slow path: (segment, row inside it) of this lane's current row in each map; 16 rows per step
-      int c_seg = 0, c_rem = 0, r_seg = 0, r_rem = 0, g_seg = 0, g_rem = 0;
-      if (!FAST) {
-        const int ms = mrow0 + rrow;
-        c_seg = ms / p.c_seg_len, c_rem = ms % p.c_seg_len;
-        if (hres) r_seg = ms / p.r_seg_len, r_rem = ms % p.r_seg_len;
-        if (ep == DK_EPI_GATE_RES) g_seg = ms / p.gate_seg_len, g_rem = ms % p.gate_seg_len;
-      }
-      // FAST tiles: everything the rows read from memory is fetched BEFORE the row loop (round 4).  The residual is updated in place
-      // (C == res), so the compiler may not move a row's load above the previous row's store: as written before, every row of every
-      // pass was its own dependent memory round trip (16 per wave and tile; with the fused key norm two more loads per row for the cos /
-      // sin entries) -- the tail's latency chain.  One round trip per pass now; values and their order unchanged.
-      constexpr bool PRE_RES = FAST && BF && (EK == DK_EPI_GATE_RES || EK == DK_EPI_RES);
-      constexpr bool PRE_ROPE = FAST && KF;
-      uint4 res_pre[PRE_RES ? MF : 1];
-      f32x4 rope_pre[PRE_ROPE ? 2 * MF : 1];
-      if (PRE_RES) {
-#pragma unroll
-        for (int itr = 0; itr < MF; ++itr) res_pre[itr] = *(const uint4*)(p.res + (physR0 + itr * 16 + rrow) * (size_t)p.ldr + col);
-      }
-      if (PRE_ROPE) {
-        if (p.kn_rope != nullptr) {
-#pragma unroll
-          for (int itr = 0; itr < MF; ++itr) {
-            const int kpos_ = (mrow0 + itr * 16 + rrow) % p.kn_seg_len;
-            const float* tab = p.kn_rope + ((size_t)(p.kn_pos_off + kpos_) * (size_t)(p.kn_D / 2) + (size_t)(kcol >> 1)) * 2;
-            rope_pre[2 * itr] = *(const f32x4*)tab, rope_pre[2 * itr + 1] = *(const f32x4*)(tab + 4);
-          }
-        }
-      }
+      const int col = t.n0 + coff + rc2 * 4, ocol = t.ncol0 + coff + rc2 * 4;
+      const bool gated = t.epi == DK_EPI_GATE_RES;
+      float bias8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, gate8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      if (p.bias && piece == 0) dk_tail_unpack8(*(const uint4*)(p.bias + col), bias8);
+      if (FAST && gated) dk_tail_unpack8(*(const uint4*)(t.gate_row + col), gate8);
+      DkTailWalk w;
+      if (!FAST) w.start(p, p.c_seg_len, t.mrow0 + rrow, t.has_res, gated);
 #pragma unroll
       for (int itr = 0; itr < MF; ++itr) {
         const int row = itr * 16 + rrow;  // row inside the wave's block of HROWS rows
-        size_t crow = physC0 + row, rrow_phys = physR0 + row;
+        size_t crow = t.physC0 + row, rrow_phys = t.physR0 + row;
         bool valid = true;
-        const int kpos = KF ? (mrow0 + row) % p.kn_seg_len : 0;  // the row's position inside its sequence
         if (!FAST) {
-          valid = mrow0 + row < p.M;
-          crow = (size_t)c_seg * p.c_seg_stride + c_rem;
-          rrow_phys = (size_t)r_seg * p.r_seg_stride + r_rem;
-          if (ep == DK_EPI_GATE_RES && valid) unpack8(*(const uint4*)(p.gate + (size_t)g_seg * p.gate_stride + col), gate8);
-          for (c_rem += 16; c_rem >= p.c_seg_len; c_rem -= p.c_seg_len) ++c_seg;
-          if (hres)
-            for (r_rem += 16; r_rem >= p.r_seg_len; r_rem -= p.r_seg_len) ++r_seg;
-          if (ep == DK_EPI_GATE_RES)
-            for (g_rem += 16; g_rem >= p.gate_seg_len; g_rem -= p.gate_seg_len) ++g_seg;
+          valid = t.mrow0 + row < p.M;
+          crow = w.crow(p);
+          rrow_phys = w.rrow(p);
+          if (gated && valid) dk_tail_unpack8(*(const uint4*)(w.gate(p) + col), gate8);
+          w.step(p, p.c_seg_len, t.has_res, gated);
+        }
+        const unsigned sw = (unsigned)((row >> 1) & 7);
+        f32x4 a0 = *(const __attribute__((address_space(3))) f32x4*)((lds_char*)0 + reg0 + row * 128 + (((unsigned)rc2 ^ sw) << 4));
+        f32x4 a1 = *(const __attribute__((address_space(3))) f32x4*)((lds_char*)0 + reg0 + row * 128 + (((unsigned)(rc2 + 1) ^ sw) << 4));
+        const size_t slab_idx = (size_t)(wm * HROWS + row) * 256 + coff + rc2 * 4;
+        if (piece >= 1) {
+          if (!(DK_V3_ABL & 8)) {  // (lab: 8 = producers do not store)
+            dk_ksplit_store_b128(my_slab + slab_idx, a0);
+            dk_ksplit_store_b128(my_slab + slab_idx + 4, a1);
+          }
+          continue;
+        }
+        for (int pp = 0; pp < ((DK_V3_ABL & 16) ? 0 : n_prod); ++pp) {  // (lab: 16 = finishers neither wait nor read)
+          const float* sl = sp.slabs + (size_t)(rt * n_prod + pp) * DK_KSPLIT_SLAB_FLOATS + slab_idx;
+          const f32x4 o0 = *(const f32x4*)sl, o1 = *(const f32x4*)(sl + 4);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) a0[e] += o0[e], a1[e] += o1[e];
         }
         float vv[8];
-        f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
-        if (BF) {
-          const u32x4 sv = *(const __attribute__((address_space(3))) u32x4*)((lds_char*)0 + reg0 + row * 64 + ((((unsigned)rc2 >> 1) ^ ((unsigned)(row >> 2) & 3u)) << 4));
-          if (PLAIN) {
-            if (((DK_V3_ABL & 32) ? p.alpha == -1234.5f : true) && (FAST || valid)) *(u32x4*)(Cb + crow * (size_t)ldcb + ocol) = sv;
-            continue;
-          }
-          unpack8(make_uint4(sv[0], sv[1], sv[2], sv[3]), vv);
-        } else {
-          const unsigned sw = (unsigned)((row >> 1) & 7);
-          a0 = *(const __attribute__((address_space(3))) f32x4*)((lds_char*)0 + reg0 + row * 128 + (((unsigned)rc2 ^ sw) << 4));
-          a1 = *(const __attribute__((address_space(3))) f32x4*)((lds_char*)0 + reg0 + row * 128 + (((unsigned)(rc2 + 1) ^ sw) << 4));
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          vv[e] = round_act(a0[e] * p.alpha + bias8[e]);
+          vv[4 + e] = round_act(a1[e] * p.alpha + bias8[4 + e]);
         }
-        if (!BF) {  // split tile
-          const size_t slab_idx = (size_t)(wm * HROWS + row) * 256 + wn * 64 + ni * 32 + rc2 * 4;
-          if (piece >= 1) {
-            if (!(DK_V3_ABL & 8)) {  // (lab: 8 = producers do not store)
-              dk_ksplit_store_b128(my_slab + slab_idx, a0);
-              dk_ksplit_store_b128(my_slab + slab_idx + 4, a1);
-            }
-            continue;
-          }
-          for (int pp = 0; pp < ((DK_V3_ABL & 16) ? 0 : n_prod); ++pp) {  // (lab: 16 = finishers neither wait nor read)
-            const float* sl = sp.slabs + (size_t)(rt * n_prod + pp) * DK_KSPLIT_SLAB_FLOATS + slab_idx;
-            const f32x4 o0 = *(const f32x4*)sl, o1 = *(const f32x4*)(sl + 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) a0[e] += o0[e], a1[e] += o1[e];
-          }
-        }
-        if (!BF) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            vv[e] = round_act(a0[e] * p.alpha + bias8[e]);
-            vv[4 + e] = round_act(a1[e] * p.alpha + bias8[4 + e]);
-          }
-        }
-        if (KF) {
-          float ss = *(const __attribute__((address_space(3))) float*)((lds_char*)0 + XCH_OFF + (wave * 128 + row) * 4);
-          if (p.kn_D == 128) ss += *(const __attribute__((address_space(3))) float*)((lds_char*)0 + XCH_OFF + ((wave ^ 1) * 128 + row) * 4);
-          const float r = rsqrtf(ss / (float)p.kn_D + p.kn_eps);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) vv[e] = round_act(vv[e] * r * kw8[e]);
-          if (p.kn_rope != nullptr) {
-            const float* tab = p.kn_rope + ((size_t)(p.kn_pos_off + kpos) * (size_t)(p.kn_D / 2) + (size_t)(kcol >> 1)) * 2;
-            f32x4 t0 = {1.f, 0.f, 1.f, 0.f}, t1 = {1.f, 0.f, 1.f, 0.f};
-            if (PRE_ROPE) t0 = rope_pre[2 * itr], t1 = rope_pre[2 * itr + 1];
-            else if (valid) t0 = *(const f32x4*)tab, t1 = *(const f32x4*)(tab + 4);
-            const float cs[8] = {t0[0], t0[1], t0[2], t0[3], t1[0], t1[1], t1[2], t1[3]};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-              const float c = cs[2 * i], sn = cs[2 * i + 1], xe = vv[2 * i], xo = vv[2 * i + 1];
-              vv[2 * i] = c * xe - sn * xo;
-              vv[2 * i + 1] = sn * xe + c * xo;
-            }
-          }
-        }
-        if (ep == DK_EPI_BIAS_GELU) {
-#pragma unroll
-          for (int e = 0; e < 8; e += 2) {
-            const f32x2 g2 = gelu_erf_f2(f32x2{vv[e], vv[e + 1]});
-            vv[e] = g2[0], vv[e + 1] = g2[1];
-          }
-        } else if (ep == DK_EPI_BIAS_SILU) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) vv[e] = silu_f(vv[e]);
-        } else if (hres) {
-          uint4 rr = make_uint4(0u, 0u, 0u, 0u);
-          if (PRE_RES) rr = res_pre[itr];
-          else if (FAST || valid) rr = *(const uint4*)(p.res + rrow_phys * (size_t)p.ldr + col);
-          float r8[8];
-          unpack8(rr, r8);
-          if (ep == DK_EPI_GATE_RES) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) vv[e] = r8[e] + round_act(gate8[e] * vv[e]);
-          } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) vv[e] += r8[e];
-          }
-        }
-        uint4 o4;
-        o4.x = pack2(vv[0], vv[1]);
-        o4.y = pack2(vv[2], vv[3]);
-        o4.z = pack2(vv[4], vv[5]);
-        o4.w = pack2(vv[6], vv[7]);
-        // (lab: 32 = the C stores sit behind a condition that is false at run time -- the work stays, the traffic goes)
-        if (((DK_V3_ABL & 32) ? p.alpha == -1234.5f : true) && (FAST || valid)) {
-#if DK_V3_NT_STORE
-          const u32x4 ov = {o4.x, o4.y, o4.z, o4.w};
-          __builtin_nontemporal_store(ov, (u32x4*)(Cb + crow * (size_t)ldcb + ocol));
-#else
-          *(uint4*)(Cb + crow * (size_t)ldcb + ocol) = o4;
-#endif
-        }
+        auto res = [&] { return (FAST || valid) ? *(const uint4*)(p.res + rrow_phys * (size_t)p.ldr + col) : make_uint4(0u, 0u, 0u, 0u); };
+        dk_tail_epilogue8(vv, t.epi, t.has_res, res, gate8);
+        store(itr, crow, ocol, FAST || valid, vv);
       }
     };
     using EkRun = std::integral_constant<int, -1>;
     using No = std::false_type;
     using Yes = std::true_type;
-    if (kfuse) {  // (whole tile, bias-only epilogue -- checked by the launcher)
-      if (fast)
-        rows(Yes{}, Yes{}, std::integral_constant<int, DK_EPI_BIAS>{}, Yes{});
+    const int epi = t.epi;
+    if (t.kfuse) {  // (whole tile, bias-only epilogue -- checked by the launcher)
+      if (t.fast)
+        rows(Yes{}, std::integral_constant<int, DK_EPI_BIAS>{}, Yes{});
       else
-        rows(No{}, Yes{}, std::integral_constant<int, DK_EPI_BIAS>{}, Yes{});
-    } else if (bf_stage && fast) {
+        rows(No{}, std::integral_constant<int, DK_EPI_BIAS>{}, Yes{});
+    } else if (bf_stage && t.fast) {
       // the common epilogues with the epilogue folded at compile time (no scalar branches inside the row loop)
       if (epi == DK_EPI_BIAS)
-        rows(Yes{}, Yes{}, std::integral_constant<int, DK_EPI_BIAS>{}, No{});
+        rows(Yes{}, std::integral_constant<int, DK_EPI_BIAS>{}, No{});
       else if (epi == DK_EPI_BIAS_GELU)
-        rows(Yes{}, Yes{}, std::integral_constant<int, DK_EPI_BIAS_GELU>{}, No{});
+        rows(Yes{}, std::integral_constant<int, DK_EPI_BIAS_GELU>{}, No{});
       else if (epi == DK_EPI_GATE_RES)
-        rows(Yes{}, Yes{}, std::integral_constant<int, DK_EPI_GATE_RES>{}, No{});
+        rows(Yes{}, std::integral_constant<int, DK_EPI_GATE_RES>{}, No{});
       else if (epi == DK_EPI_RES)
-        rows(Yes{}, Yes{}, std::integral_constant<int, DK_EPI_RES>{}, No{});
+        rows(Yes{}, std::integral_constant<int, DK_EPI_RES>{}, No{});
       else
-        rows(Yes{}, Yes{}, EkRun{}, No{});
+        rows(Yes{}, EkRun{}, No{});
     } else if (bf_stage) {
-      rows(No{}, Yes{}, EkRun{}, No{});
+      rows(No{}, EkRun{}, No{});
+    } else if (t.fast) {
+      split_rows(Yes{});
     } else {
-      if (fast)
-        rows(Yes{}, No{}, EkRun{}, No{});
-      else
-        rows(No{}, No{}, EkRun{}, No{});
+      split_rows(No{});
     }
   };
   if (!((DK_V3_ABL & 64) && p.alpha != -1234.5f)) {  // (lab: 64 = no tail at run time)
@@ -840,16 +703,11 @@ bool dk_gemm256v3_eligible(const GemmParams& p) {
     if (p.cB > 256 || p.cH > 4096 || p.cW > 4096 || (p.ups == 1 && (p.cH % 2 != 0 || p.cW % 2 != 0))) return false;
     if ((size_t)p.cB * (p.cH >> p.ups) * (p.cW >> p.ups) * p.cC * 2 >= (1ull << 31) || ((uintptr_t)p.A & 15) != 0) return false;
   }
-  if (p.n_split % 256 != 0 || (p.n_split > 0 && (p.C2 == nullptr || p.ldc2 % 8 != 0 || p.n_split >= p.N))) return false;
+  if (!dk_gemm_tail_operands_ok(p) || (p.n_split > 0 && p.ldc2 % 8 != 0)) return false;
   if (p.a_seg_len <= 0 || p.c_seg_len <= 0) return false;
-  const bool res1 = p.epi == DK_EPI_GATE_RES || p.epi == DK_EPI_RES;
-  const bool res2 = p.n_split > 0 && (p.epi2 == DK_EPI_GATE_RES || p.epi2 == DK_EPI_RES);
-  if ((res1 || res2) && (p.res == nullptr || p.r_seg_len <= 0 || p.ldr % 8 != 0)) return false;
-  if ((p.epi == DK_EPI_GATE_RES || (p.n_split > 0 && p.epi2 == DK_EPI_GATE_RES)) && (p.gate == nullptr || p.gate_seg_len <= 0)) return false;
   if ((p.kn_w != nullptr && p.conv) || !dk_qknorm_eligible(p)) return false;
-  // 16-byte accesses in the tail
-  auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
-  if (!al16(p.C) || !al16(p.C2) || !al16(p.res) || !al16(p.bias) || !al16(p.gate) || (p.gate != nullptr && p.gate_stride % 8 != 0)) return false;
+  // 16-byte stores in the tail
+  if (((uintptr_t)p.C & 15) != 0 || ((uintptr_t)p.C2 & 15) != 0) return false;
   // 32-bit byte offsets on the DMA side: the A rows this problem touches and 8 rows of W
   const size_t a_rows = (size_t)((p.M - 1) / p.a_seg_len) * p.a_seg_stride + (size_t)((p.M - 1) % p.a_seg_len) + 1;
   return (p.conv || a_rows * (size_t)p.lda * 2 < (1ull << 32)) && (size_t)p.ldw * 2 * 8 < (1ull << 31);

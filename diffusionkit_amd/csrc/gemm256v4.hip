@@ -17,13 +17,14 @@
 // those).  C / D layout as in gemm256v3.hip: lane holds row m = mf*16 + (lane & 15), columns n = nf*16 + 4*(lane >> 4) + {0..3}.
 //
 // Tail: the asm block leaves round_bf16(alpha * acc + bias) in the LDS image gemm256v3.hip's tail stages (eight wave-private 16 KiB
-// regions; a wave of this kernel owns two of them), so the read-back below is that kernel's: 8 columns per lane, one 16-byte store
-// per lane and row, epilogues folded at compile time.  The fused QKNorm + RoPE of key / query tiles takes its row sums from the
-// staged image (a wave's 128 columns hold whole heads: no exchange between waves).
+// regions; a wave of this kernel owns two of them), so the read-back is the one all three 256 x 256 kernels share (dk_gemm_tail.h): 8 columns
+// per lane, one 16-byte store per lane and row, epilogues folded at compile time.  The fused QKNorm + RoPE of key / query tiles takes its
+// row sums from the staged image (a wave's 128 columns hold whole heads: no exchange between waves).
 #include <cstring>
 #include <type_traits>
 
 #include "dk_kernels.h"
+#include "dk_gemm_tail.h"
 
 #define V4_T 256
 #define V4_BK 64
@@ -54,42 +55,16 @@ __device__ __forceinline__ void v4_store16(bf16_t* ptr, u32x4 v) {
 #endif
 }
 
-struct V4Tail {
-  const GemmParams __attribute__((address_space(4))) * p;
-  bf16_t* Cb;
-  int ldcb, epi, n0, ncol0, m0, wm, wn2, lane;
-  bool has_res;
-  const bf16_t* nw;  // QKNorm weight of this tile (key or query), or null
-};
-
-// read-back of the staged tile: see gemm256v3.hip (rows lambda); FAST: tile-uniform row maps; EK: epilogue folded at compile time (-1: run time);
-// KF: key / query tile with the fused QKNorm + RoPE
-// CUT (with FAST): the tile lies inside one segment of every map but M ends inside it (the last row tile: 4352 rows in 224-row tiles) -- the
-// tile-uniform addressing of FAST with a row limit: rows past it are neither stored nor (residual) loaded from their own address
-template <bool FAST, int EK, bool KF, int MF, bool CUT = false>
-__device__ __forceinline__ void v4_rows(const V4Tail& t) {
-  static_assert(FAST || !CUT, "CUT is a form of FAST");
-  constexpr int HROWS = 16 * MF;  // rows of a wave's block (the LDS image keeps 128-row regions; a 224-row tile uses 112 of each)
-  const auto& p = *t.p;
-  constexpr bool PLAIN = EK == DK_EPI_BIAS && !KF;
-  const int lane = t.lane;
-  const int rrow = lane >> 2, rc2 = (lane & 3) * 2;
-  const int mrow0 = t.m0 + t.wm * HROWS;
-  const int row_lim = CUT ? t.p->M - 1 - mrow0 : HROWS;  // last valid row of this wave's block
-  if (CUT && row_lim < 0) return;                        // (the whole block lies past M)
-  const int ep = EK >= 0 ? EK : t.epi;
-  const bool hres = EK >= 0 ? (EK == DK_EPI_GATE_RES || EK == DK_EPI_RES) : t.has_res;
-  const size_t physC0 = (size_t)((t.m0 / p.c_seg_len) * p.c_seg_stride + (t.m0 % p.c_seg_len)) + t.wm * HROWS;
-  const size_t physR0 = hres ? (size_t)((t.m0 / p.r_seg_len) * p.r_seg_stride + (t.m0 % p.r_seg_len)) + t.wm * HROWS : 0;
-  const bf16_t* gate_row = ep == DK_EPI_GATE_RES ? p.gate + (size_t)(t.m0 / p.gate_seg_len) * p.gate_stride : nullptr;
-  auto unpack8 = [](const uint4 v, float* f) {
-    unpack2bf(v.x, f[0], f[1]);
-    unpack2bf(v.y, f[2], f[3]);
-    unpack2bf(v.z, f[4], f[5]);
-    unpack2bf(v.w, f[6], f[7]);
-  };
+// read-back of the staged tile: the shared row loop (dk_gemm_tail.h) in this kernel's frame -- a wave owns a 128 x 128 block of the tile, two of
+// the 16 KiB image regions of each of its two row halves: four 32-column passes, every load of all four in front of the first store (a lone
+// wave has nothing else to cover a memory round trip).  FAST / EK / KF / CUT: see dk_tail_rows
+template <bool FAST, int EK, bool KF, int MF, bool CUT = false, class P>
+__device__ __forceinline__ void v4_rows(const P& p, const DkTailTile& tile, int wm, int wn2, int lane) {
+  DkTailTile t = tile;
+  dk_tail_first_rows<EK>(p, t);
   // KF: sum of squares of every row over its head's columns, from the staged (bf16-rounded) values: this lane's 8 rows, per head
-  // (kn_D = 128: the wave's 128 columns are one head; 64: two heads = the two virtual waves)
+  // (kn_D = 128: the wave's 128 columns are one head; 64: two heads = the two virtual waves).  This order of summation is this kernel's own:
+  // gemm256v3.hip sums the accumulators (dk_tail_sumsq_exchange), so key tiles of the two agree within rounding, not bit for bit
   float ss[2][MF];
   if (KF) {
 #pragma unroll
@@ -97,13 +72,12 @@ __device__ __forceinline__ void v4_rows(const V4Tail& t) {
 #pragma unroll
       for (int itr = 0; itr < MF; ++itr) ss[vwn][itr] = 0.f;
       for (int ni = 0; ni < 2; ++ni) {
-        const unsigned reg0 = (unsigned)((t.wm * 4 + 2 * t.wn2 + vwn) * 16384 + ni * 8192);
+        const unsigned reg0 = (unsigned)((wm * 4 + 2 * wn2 + vwn) * 16384 + ni * 8192);
 #pragma unroll
         for (int itr = 0; itr < MF; ++itr) {
-          const int row = itr * 16 + rrow;
-          const u32x4 sv = *(const __attribute__((address_space(3))) u32x4*)((v4_lds_char*)0 + reg0 + row * 64 + ((((unsigned)rc2 >> 1) ^ ((unsigned)(row >> 2) & 3u)) << 4));
+          const u32x4 sv = dk_tail_read(reg0, itr * 16 + (lane >> 2), lane & 3);
           float vv[8];
-          unpack8(make_uint4(sv[0], sv[1], sv[2], sv[3]), vv);
+          dk_tail_unpack8(make_uint4(sv[0], sv[1], sv[2], sv[3]), vv);
 #pragma unroll
           for (int e = 0; e < 8; ++e) ss[vwn][itr] += vv[e] * vv[e];
         }
@@ -119,132 +93,19 @@ __device__ __forceinline__ void v4_rows(const V4Tail& t) {
       for (int itr = 0; itr < MF; ++itr) ss[0][itr] = ss[1][itr] = ss[0][itr] + ss[1][itr];
     }
   }
-  // FAST tiles: everything the rows read from memory is fetched before the first store -- for all four passes at once (the residual is
-  // updated in place, C == res: behind a store the compiler may not move a load up, and a lone wave has nothing else to cover the
-  // round trip; gemm256v3.hip round 4 did this per pass)
-  constexpr bool PRE_RES = FAST && (EK == DK_EPI_GATE_RES || EK == DK_EPI_RES);
-  constexpr bool PRE_ROPE = FAST && KF;
-  uint4 res_pre[PRE_RES ? 4 : 1][PRE_RES ? MF : 1];
-  f32x4 rope_pre[PRE_ROPE ? 4 : 1][PRE_ROPE ? 2 * MF : 1];
-  float gate_pre[(FAST && EK == DK_EPI_GATE_RES) ? 4 : 1][8];
-#pragma unroll
-  for (int pass = 0; pass < 4; ++pass) {
-    const int wn = 2 * t.wn2 + (pass >> 1), ni = pass & 1;
-    const int col = t.n0 + wn * 64 + ni * 32 + rc2 * 4;
-    if (PRE_RES) {
-#pragma unroll
-      for (int itr = 0; itr < MF; ++itr) res_pre[pass][itr] = *(const uint4*)(p.res + (physR0 + (CUT ? min(itr * 16 + rrow, row_lim) : itr * 16 + rrow)) * (size_t)p.ldr + col);
-    }
-    if (FAST && EK == DK_EPI_GATE_RES) unpack8(*(const uint4*)(gate_row + col), gate_pre[pass]);
-    if (PRE_ROPE) {
-      if (p.kn_rope != nullptr) {
-        const int kcol = col % p.kn_D;
-#pragma unroll
-        for (int itr = 0; itr < MF; ++itr) {
-          const int kpos_ = (mrow0 + itr * 16 + rrow) % p.kn_seg_len;
-          const float* tab = p.kn_rope + ((size_t)(p.kn_pos_off + kpos_) * (size_t)(p.kn_D / 2) + (size_t)(kcol >> 1)) * 2;
-          rope_pre[pass][2 * itr] = *(const f32x4*)tab, rope_pre[pass][2 * itr + 1] = *(const f32x4*)(tab + 4);
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int pass = 0; pass < 4; ++pass) {
-    const int vwn = pass >> 1, ni = pass & 1;
-    const int wn = 2 * t.wn2 + vwn;
-    const unsigned reg0 = (unsigned)((t.wm * 4 + wn) * 16384 + ni * 8192);
-    const int col = t.n0 + wn * 64 + ni * 32 + rc2 * 4;      // first of this lane's 8 columns of the GEMM (gate, residual)
-    const int ocol = t.ncol0 + wn * 64 + ni * 32 + rc2 * 4;  // the same inside the output it goes to
-    float gate8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    float kw8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const int kcol = KF ? col % p.kn_D : 0;
-    if (KF) unpack8(*(const uint4*)(t.nw + kcol), kw8);
-    if (FAST && EK == DK_EPI_GATE_RES) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) gate8[e] = gate_pre[pass][e];
-    } else if (FAST && ep == DK_EPI_GATE_RES) {
-      unpack8(*(const uint4*)(gate_row + col), gate8);
-    }
-    int c_seg = 0, c_rem = 0, r_seg = 0, r_rem = 0, g_seg = 0, g_rem = 0;
-    if (!FAST) {
-      const int ms = mrow0 + rrow;
-      c_seg = ms / p.c_seg_len, c_rem = ms % p.c_seg_len;
-      if (hres) r_seg = ms / p.r_seg_len, r_rem = ms % p.r_seg_len;
-      if (ep == DK_EPI_GATE_RES) g_seg = ms / p.gate_seg_len, g_rem = ms % p.gate_seg_len;
-    }
-#pragma unroll
-    for (int itr = 0; itr < MF; ++itr) {
-      const int row = itr * 16 + rrow;  // row inside the wave's block of 128 rows
-      size_t crow = physC0 + row, rrow_phys = physR0 + row;
-      bool valid = !CUT || row <= row_lim;
-      const int kpos = KF ? (mrow0 + row) % p.kn_seg_len : 0;
-      if (!FAST) {
-        valid = mrow0 + row < p.M;
-        crow = (size_t)c_seg * p.c_seg_stride + c_rem;
-        rrow_phys = (size_t)r_seg * p.r_seg_stride + r_rem;
-        if (ep == DK_EPI_GATE_RES && valid) unpack8(*(const uint4*)(p.gate + (size_t)g_seg * p.gate_stride + col), gate8);
-        for (c_rem += 16; c_rem >= p.c_seg_len; c_rem -= p.c_seg_len) ++c_seg;
-        if (hres)
-          for (r_rem += 16; r_rem >= p.r_seg_len; r_rem -= p.r_seg_len) ++r_seg;
-        if (ep == DK_EPI_GATE_RES)
-          for (g_rem += 16; g_rem >= p.gate_seg_len; g_rem -= p.gate_seg_len) ++g_seg;
-      }
-      const u32x4 sv = *(const __attribute__((address_space(3))) u32x4*)((v4_lds_char*)0 + reg0 + row * 64 + ((((unsigned)rc2 >> 1) ^ ((unsigned)(row >> 2) & 3u)) << 4));
-      if (PLAIN) {
-        if ((FAST && !CUT) || valid) v4_store16(t.Cb + crow * (size_t)t.ldcb + ocol, sv);
-        continue;
-      }
-      float vv[8];
-      unpack8(make_uint4(sv[0], sv[1], sv[2], sv[3]), vv);
-      if (KF) {
-        const float r = rsqrtf(ss[vwn][itr] / (float)p.kn_D + p.kn_eps);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) vv[e] = round_bf16(vv[e] * r * kw8[e]);
-        if (p.kn_rope != nullptr) {
-          const float* tab = p.kn_rope + ((size_t)(p.kn_pos_off + kpos) * (size_t)(p.kn_D / 2) + (size_t)(kcol >> 1)) * 2;
-          f32x4 t0 = {1.f, 0.f, 1.f, 0.f}, t1 = {1.f, 0.f, 1.f, 0.f};
-          if (PRE_ROPE) t0 = rope_pre[pass][2 * itr], t1 = rope_pre[pass][2 * itr + 1];
-          else if (valid) t0 = *(const f32x4*)tab, t1 = *(const f32x4*)(tab + 4);
-          const float cs[8] = {t0[0], t0[1], t0[2], t0[3], t1[0], t1[1], t1[2], t1[3]};
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const float c = cs[2 * i], sn = cs[2 * i + 1], xe = vv[2 * i], xo = vv[2 * i + 1];
-            vv[2 * i] = c * xe - sn * xo;
-            vv[2 * i + 1] = sn * xe + c * xo;
-          }
-        }
-      }
-      if (ep == DK_EPI_BIAS_GELU) {
-#pragma unroll
-        for (int e = 0; e < 8; e += 2) {
-          const f32x2 g2 = gelu_erf_f2(f32x2{vv[e], vv[e + 1]});
-          vv[e] = g2[0], vv[e + 1] = g2[1];
-        }
-      } else if (ep == DK_EPI_BIAS_SILU) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) vv[e] = silu_f(vv[e]);
-      } else if (hres) {
-        uint4 rr = make_uint4(0u, 0u, 0u, 0u);
-        if (PRE_RES) rr = res_pre[pass][itr];
-        else if (FAST || valid) rr = *(const uint4*)(p.res + rrow_phys * (size_t)p.ldr + col);
-        float r8[8];
-        unpack8(rr, r8);
-        if (ep == DK_EPI_GATE_RES) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) vv[e] = r8[e] + round_bf16(gate8[e] * vv[e]);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) vv[e] += r8[e];
-        }
-      }
-      uint4 o4;
-      o4.x = pack2bf(vv[0], vv[1]);
-      o4.y = pack2bf(vv[2], vv[3]);
-      o4.z = pack2bf(vv[4], vv[5]);
-      o4.w = pack2bf(vv[6], vv[7]);
-      if ((FAST && !CUT) || valid) v4_store16(t.Cb + crow * (size_t)t.ldcb + ocol, u32x4{o4.x, o4.y, o4.z, o4.w});
-    }
-  }
+  auto pass_of = [&](int pass) {
+    const int wn = 2 * wn2 + (pass >> 1), ni = pass & 1;
+    return DkTailPass{(unsigned)((wm * 4 + wn) * 16384 + ni * 8192), wn * 64 + ni * 32};
+  };
+  auto ss_of = [&](int pass, int itr, int) { return ss[pass >> 1][itr]; };
+  auto store_raw = [&](size_t crow, int ocol, bool ok, u32x4 sv) {
+    if (ok) v4_store16(t.Cb + crow * (size_t)t.ldcb + ocol, sv);
+  };
+  auto store = [&](int, size_t crow, int ocol, bool ok, const float* vv) {
+    const uint4 o4 = dk_tail_pack8(vv);
+    store_raw(crow, ocol, ok, u32x4{o4.x, o4.y, o4.z, o4.w});
+  };
+  dk_tail_rows<FAST, EK, KF, MF, CUT, 4, true>(p, t, lane, pass_of, ss_of, store, store_raw);
 }
 
 // MF: 16-row activation fragments per wave: 8 = 256-row tiles, 7 = 224-row tiles (the launcher takes the height with the fewest rounds x height,
@@ -326,7 +187,7 @@ __global__ __launch_bounds__(256, 1) void dk_gemm256v4_kernel(GemmParams pa, Gem
     rd[2 + kk] = 65536 + wn2 * 16384 + offk;
   }
   u32x2 dr;
-  dr[0] = (unsigned)((wm * 4 + 2 * wn2) * 16384 + l15 * 64 + (q & 1) * 8 + (((q >> 1) ^ ((l15 >> 2) & 3)) << 4));
+  dr[0] = (unsigned)((wm * 4 + 2 * wn2) * 16384) + dk_tail_stage_off(l15, 0, q);
   dr[1] = dr[0] ^ 32u;
   // bias of this lane's 32 columns (4 per 16-column fragment)
   f32x8 bq[4];
@@ -386,42 +247,25 @@ __global__ __launch_bounds__(256, 1) void dk_gemm256v4_kernel(GemmParams pa, Gem
 #endif
 
   // ---------------- tail: staged bf16 image -> row-major, epilogues on the way ----------------
-  const bool out2 = p.n_split > 0 && n0 >= p.n_split;  // tile-uniform: second output of a column-split GEMM
-  V4Tail t;
-  t.p = &p;
-  t.Cb = out2 ? p.C2 : p.C;
-  t.ldcb = out2 ? p.ldc2 : p.ldc;
-  t.epi = out2 ? p.epi2 : p.epi;
-  t.n0 = n0;
-  t.ncol0 = out2 ? n0 - p.n_split : n0;
-  t.m0 = m0, t.wm = wm, t.wn2 = wn2, t.lane = lane;
-  t.has_res = t.epi == DK_EPI_GATE_RES || t.epi == DK_EPI_RES;
-  auto inside = [&](int len) { return m0 / len == (m0 + BM - 1) / len; };
-  const bool fast = m0 + BM <= p.M && inside(p.c_seg_len) && (!t.has_res || inside(p.r_seg_len)) && (t.epi != DK_EPI_GATE_RES || inside(p.gate_seg_len));
-  const bool qtile = p.qn_w != nullptr && n0 >= p.qn_col0 && n0 < p.qn_col1;
-  const bool kfuse = p.kn_w != nullptr && ((n0 >= p.kn_col0 && n0 < p.kn_col1) || qtile);
-  t.nw = qtile ? p.qn_w : p.kn_w;
-  // the last row tile of a single-segment problem: tile-uniform maps, M ends inside it
-  auto inside_cut = [&](int len) { return m0 / len == (p.M - 1) / len; };
-  const bool cut = !fast && m0 + BM > p.M && inside_cut(p.c_seg_len) && (!t.has_res || inside_cut(p.r_seg_len)) &&
-                   (t.epi != DK_EPI_GATE_RES || inside_cut(p.gate_seg_len));
-  if (kfuse) {  // (bias-only epilogue -- checked by the launcher)
-    if (fast) v4_rows<true, DK_EPI_BIAS, true, MF>(t);
-    else if (cut) v4_rows<true, DK_EPI_BIAS, true, MF, true>(t);
-    else v4_rows<false, DK_EPI_BIAS, true, MF>(t);
+  const DkTailTile t = dk_tail_tile<true>(p, m0, n0, BM, wm * HROWS, p.M, p.ldc, p.c_seg_len, p.ldr);
+  const bool fast = t.fast, cut = t.cut;
+  if (t.kfuse) {  // (bias-only epilogue -- checked by the launcher)
+    if (fast) v4_rows<true, DK_EPI_BIAS, true, MF>(p, t, wm, wn2, lane);
+    else if (cut) v4_rows<true, DK_EPI_BIAS, true, MF, true>(p, t, wm, wn2, lane);
+    else v4_rows<false, DK_EPI_BIAS, true, MF>(p, t, wm, wn2, lane);
   } else if (cut) {
-    if (t.epi == DK_EPI_BIAS) v4_rows<true, DK_EPI_BIAS, false, MF, true>(t);
-    else if (t.epi == DK_EPI_BIAS_GELU) v4_rows<true, DK_EPI_BIAS_GELU, false, MF, true>(t);
-    else if (t.epi == DK_EPI_GATE_RES) v4_rows<true, DK_EPI_GATE_RES, false, MF, true>(t);
-    else v4_rows<false, -1, false, MF>(t);
+    if (t.epi == DK_EPI_BIAS) v4_rows<true, DK_EPI_BIAS, false, MF, true>(p, t, wm, wn2, lane);
+    else if (t.epi == DK_EPI_BIAS_GELU) v4_rows<true, DK_EPI_BIAS_GELU, false, MF, true>(p, t, wm, wn2, lane);
+    else if (t.epi == DK_EPI_GATE_RES) v4_rows<true, DK_EPI_GATE_RES, false, MF, true>(p, t, wm, wn2, lane);
+    else v4_rows<false, -1, false, MF>(p, t, wm, wn2, lane);
   } else if (fast) {
-    if (t.epi == DK_EPI_BIAS) v4_rows<true, DK_EPI_BIAS, false, MF>(t);
-    else if (t.epi == DK_EPI_BIAS_GELU) v4_rows<true, DK_EPI_BIAS_GELU, false, MF>(t);
-    else if (t.epi == DK_EPI_GATE_RES) v4_rows<true, DK_EPI_GATE_RES, false, MF>(t);
-    else if (t.epi == DK_EPI_RES) v4_rows<true, DK_EPI_RES, false, MF>(t);
-    else v4_rows<true, -1, false, MF>(t);
+    if (t.epi == DK_EPI_BIAS) v4_rows<true, DK_EPI_BIAS, false, MF>(p, t, wm, wn2, lane);
+    else if (t.epi == DK_EPI_BIAS_GELU) v4_rows<true, DK_EPI_BIAS_GELU, false, MF>(p, t, wm, wn2, lane);
+    else if (t.epi == DK_EPI_GATE_RES) v4_rows<true, DK_EPI_GATE_RES, false, MF>(p, t, wm, wn2, lane);
+    else if (t.epi == DK_EPI_RES) v4_rows<true, DK_EPI_RES, false, MF>(p, t, wm, wn2, lane);
+    else v4_rows<true, -1, false, MF>(p, t, wm, wn2, lane);
   } else {
-    v4_rows<false, -1, false, MF>(t);
+    v4_rows<false, -1, false, MF>(p, t, wm, wn2, lane);
   }
 #ifdef V4_TRACE
   if (p.workspace != nullptr && wave == 0 && lane == 0 && (blockIdx.x == 0 || blockIdx.x == gridDim.x - 1)) {

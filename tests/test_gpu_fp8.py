@@ -356,3 +356,78 @@ def test_gemm_fp8_qknorm_rope_in_tail(dev, D, table):
     norm_columns_ok(ref, got[:M], h, D, f"fp8 knorm D={D} {table}")
     assert rel_l2(proj[:, 2 * h:], got[:M, 2 * h:]) < TOL_SINGLE_OP
     assert bool((got[M:] == 7.0).all())
+
+
+# ---- the fp8 kernel's tail is the bf16 kernels' tail (dk_gemm_tail.h) -----------------------------------------------------------------------------
+_TAIL_N, _TAIL_K = 512, 128
+_TAIL_CASES = {"whole": (256, 256, 1),      # one whole row tile: tile-uniform maps (FAST)
+               "ragged": (300, 300, 1),     # a ragged last tile: gemm256v3 / gemm256f8 walk it row by row, gemm256v4 takes its CUT form
+               "straddle": (300, 200, 2)}   # tile 0 straddles a gate segment: every kernel walks it row by row
+_tail_cache = {}
+
+
+def _tail_inputs(M):
+    """Operands on which all three 256 x 256 kernels hold the SAME fp32 accumulators: integer A in [-4, 4] (exact in MX-fp8) and W in [-2, 2] (exact in
+    e4m3 with weight scale 1 and in bf16), K = 128, so |acc| <= 1024, and a bias of multiples of 0.25: acc + bias is exact in fp32 whatever the order of
+    summation or the contraction.  What differs between the kernels' outputs can then only come from their tails."""
+    if M not in _tail_cache:
+        gen = torch.Generator().manual_seed(900 + M)
+        a = torch.randint(-4, 5, (M, _TAIL_K), generator=gen).float()
+        w = torch.randint(-2, 3, (_TAIL_N, _TAIL_K), generator=gen).float()
+        bias = torch.randint(-8, 9, (_TAIL_N,), generator=gen).float() * 0.25
+        qa, ea = o8.mx8_encode(a)
+        assert torch.equal(f8.mx8_decode(qa, ea), a), "the MX-fp8 encoding of A is exact"
+        qw = w.to(torch.float8_e4m3fn)
+        assert torch.equal(qw.float(), w)
+        _tail_cache[M] = dict(a=a, w=w, bias=bias, qa=qa, ea=ea, qw=qw.view(torch.uint8), res=randn(M, _TAIL_N, seed=901), gate=randn(2, _TAIL_N, seed=902),
+                              acc=bf16r(a @ w.t() + bias))
+    return _tail_cache[M]
+
+
+@pytest.mark.parametrize("epi", ["bias", "gelu", "gate_res", "res"])
+@pytest.mark.parametrize("case", list(_TAIL_CASES))
+def test_gemm_fp8_tail_equals_bf16_tail(dev, case, epi):
+    """gemm256f8.hip, gemm256v3.hip (mode 9) and gemm256v4.hip (mode 10) finish a tile with one shared read-back (dk_gemm_tail.h): on operands that give all
+    three the same accumulators the outputs are the same BITS, on whole tiles, on a ragged last tile and on a tile that straddles a gate segment, for
+    every epilogue the models use; with GELU and an MX-fp8 output the fp8 kernel's bytes and scales are the encoding of the bf16 kernel's output.  Key /
+    query tiles are left out: gemm256v4.hip sums a head's squares in another order by design (tests/test_gpu_fused_ops.py bounds them)."""
+    from oracle.mmdit import gelu_erf
+    from diffusionkit_amd._lib import DK_EPI_RES
+    M, gate_seg, n_gate = _TAIL_CASES[case]
+    t = _tail_inputs(M)
+    gate, res, acc = t["gate"][:n_gate], t["res"], t["acc"]
+    to = lambda x: x.to(dev, BF)
+    kw = {}
+    if epi == "gelu":
+        kw, ref = dict(epilogue=DK_EPI_BIAS_GELU), gelu_erf(acc, Prec(BF))
+    elif epi == "gate_res":
+        kw = dict(epilogue=DK_EPI_GATE_RES, gate=to(gate), res=to(res), gate_seg_len=gate_seg)
+        ref = res + bf16r(gate.repeat_interleave(gate_seg, 0)[:M] * acc)
+    elif epi == "res":
+        kw, ref = dict(epilogue=DK_EPI_RES, res=to(res)), res + acc
+    else:
+        ref = acc
+    rows = (M + 127) // 128 * 128
+    a8 = torch.zeros(rows, _TAIL_K, dtype=torch.uint8)
+    a8[:M] = t["qa"]
+    f8_args = (a8.to(dev), f8.scales_to_array(t["ea"], rows).to(dev), t["qw"].to(dev), torch.ones(_TAIL_N, device=dev))
+    out8 = ops.gemm_fp8(*f8_args, bias=to(t["bias"]), M=M, **kw)
+    outs = {}
+    for mode in (9, 10):
+        try:
+            ops.tune("gemm", mode)
+            ops.tune("gemm_split", 0)
+            outs[mode] = ops.linear(to(t["a"]), to(t["w"]), to(t["bias"]), **kw)
+        finally:
+            ops.tune("gemm", -1)
+            ops.tune("gemm_split", -1)
+    for name, y in (("fp8", out8), ("mode 9", outs[9]), ("mode 10", outs[10])):
+        r = rel_l2(ref, y.float())
+        print(f"[tail {case} {epi}] {name}: rel_l2 against the oracle {r:.3e}; elements that differ from mode 9: {int((y != outs[9]).sum())}")
+        assert r < TOL_SINGLE_OP
+    assert torch.equal(outs[9], outs[10])
+    assert torch.equal(out8, outs[9])
+    if epi == "gelu":
+        q8, sc = ops.gemm_fp8(*f8_args, bias=to(t["bias"]), M=M, out_mx8=True, **kw)
+        want_q, want_e = o8.mx8_encode(outs[9].float().cpu())
+        assert torch.equal(q8.cpu(), want_q) and torch.equal(f8.array_to_scales(sc, M, _TAIL_N), want_e)
