@@ -231,6 +231,10 @@ SIGNATURES = {
     # channel-concatenated conditioning (FLUX.1 Fill / Canny / Depth): the engine's width / hoist entries and the two operators
     "dk_mmdit_set_condition_width": (_i32, [_vp, _i32]),
     "dk_mmdit_cache_condition": (_i32, [_vp, _vp, _i32, _vp]),
+    # MMDiT-X dual-attention blocks (Stable Diffusion 3.5 medium): the engine's setter and the LayerNorm pass with two modulated outputs
+    "dk_mmdit_set_dual_attention": (_i32, [_vp, _i32]),
+    **{"dk_ln_modulate_dual_" + el: (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
+                                            _i32, _f32, _vp]) for el in ("bf16", "f16")},
     "dk_image_mask_out_f32": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "dk_fill_condition_tokens": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "dk_vae_create": (_i32, [C.POINTER(dk_vae_config), C.POINTER(_vp)]),

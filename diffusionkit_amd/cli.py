@@ -24,6 +24,7 @@ HEIGHT = {
     "argmaxinc/mlx-FLUX.1-schnell": 512,
     "argmaxinc/mlx-FLUX.1-schnell-4bit-quantized": 512,
     "argmaxinc/mlx-FLUX.1-dev": 512,
+    "stabilityai/stable-diffusion-3.5-medium": 1024,  # (no reference counterpart; runs from --local-ckpt)
 }
 WIDTH = dict(HEIGHT)
 SHIFT = {k: (1.0 if "FLUX" in k else 3.0) for k in HEIGHT}

@@ -58,6 +58,10 @@ class MMDiTConfig:
     # channel-concatenated conditioning (FLUX.1 Fill: 320, Canny / Depth: 64; 0: none): x_embedder.proj.weight has patch_dim + condition_features
     # columns, and a condition token row of that width rides into every model evaluation (MMDiTEngine.cache_condition); FLUX family only
     condition_features: int = 0
+    # MMDiT-X (Stable Diffusion 3.5 medium; no reference counterpart): the first n double blocks carry a second self-attention over the image
+    # tokens alone (x_block.attn2), fed by a second modulation of the block's LayerNorm and gated by a ninth adaLN row; SD3 family only
+    # (validate_dual_attention)
+    dual_attention_blocks: int = 0
 
     @property
     def hidden_size(self) -> int:
@@ -76,11 +80,12 @@ class MMDiTConfig:
         return self.depth_unified > 0
 
     def param_count(self) -> int:
-        """Approximate parameter count (linear weights only): 12 h^2 per stream / single block plus
-        the adaLN Linears."""
+        """Approximate parameter count (linear weights only): 12 h^2 per stream / single block (+ 4 h^2 for the second attention of a
+        dual block) plus the adaLN Linears."""
         h = self.hidden_size
         per_stream = (4 + 2 * self.mlp_ratio) * h * h
         n = (2 * self.depth_multimodal + self.depth_unified) * per_stream
+        n += self.dual_attention_blocks * 4 * h * h
         n += self.num_modulation_rows() * h * h
         n += (self.token_level_text_embed_dim + self.pooled_text_embed_dim + self.frequency_embed_dim + 2 * h) * h
         return n
@@ -88,13 +93,13 @@ class MMDiTConfig:
     def num_modulation_rows(self) -> int:
         """Number of hidden-size rows of adaLN output per (timestep, batch row).
 
-        double block: 6 (image) + 6 (text); the last SD3 block's text stream has 2
+        double block: 6 (image; 9 for a dual-attention block) + 6 (text); the last SD3 block's text stream has 2
         (reference mmdit.py:64-65,424-427); single block: 3; final layer: 2.
         """
         n = 0
         for i in range(self.depth_multimodal):
             skip_txt = (i == self.depth_multimodal - 1) and self.depth_unified < 1
-            n += 6 + (2 if skip_txt else 6)
+            n += (9 if i < self.dual_attention_blocks else 6) + (2 if skip_txt else 6)
         n += 3 * self.depth_unified
         n += 2
         return n
@@ -105,6 +110,21 @@ SD3_2b = MMDiTConfig(depth_multimodal=24, num_heads=24, dtype="float16")
 
 # reference config.py:74-76
 SD3_8b = MMDiTConfig(depth_multimodal=38, num_heads=38, use_qk_norm=True)
+
+# Stable Diffusion 3.5 medium (no reference counterpart; published model definition: MMDiT-X, depth 24, 384^2 position table, QK-RMSNorm, the
+# first 13 joint blocks with a second, image-only attention)
+SD3_5_MEDIUM = MMDiTConfig(depth_multimodal=24, num_heads=24, use_qk_norm=True, max_latent_resolution=384, dual_attention_blocks=13)
+
+
+def validate_dual_attention(cfg: MMDiTConfig) -> None:
+    """0 <= dual_attention_blocks <= depth_multimodal, and above 0 only on the SD3 family with bf16 / fp16 Linears: depth_unified == 0, no
+    fp8 weights (the rule dk_mmdit_set_dual_attention enforces)."""
+    n = cfg.dual_attention_blocks
+    if not (0 <= n <= cfg.depth_multimodal):
+        raise ValueError(f"dual_attention_blocks = {n}: must lie in [0, depth_multimodal = {cfg.depth_multimodal}]")
+    if n > 0 and (cfg.depth_unified != 0 or cfg.weight_dtype == "fp8_e4m3"):
+        raise ValueError("dual_attention_blocks needs the SD3 family (MMDiT-X): depth_unified == 0 and no fp8 Linears")
+
 
 # reference config.py:82-95
 FLUX_SCHNELL = MMDiTConfig(
@@ -225,6 +245,21 @@ def tiny_sd3(depth: int = 2, heads: int = 4, text_dim: int = 256, pooled: int = 
     )
 
 
+def tiny_sd35m(depth: int = 3, heads: int = 4, dual: int = 2, text_dim: int = 256, pooled: int = 64, max_res: int = 24) -> MMDiTConfig:
+    """SD3.5-medium-shaped config (MMDiT-X: head_dim 64, QK-RMSNorm, learned pos-emb, the first ``dual`` blocks with the second attention; the
+    defaults put a plain block and the text-skipping last block behind the dual ones)."""
+    return replace(
+        SD3_5_MEDIUM,
+        num_heads=heads,
+        depth_multimodal=depth,
+        dual_attention_blocks=dual,
+        hidden_size_override=heads * 64,
+        token_level_text_embed_dim=text_dim,
+        pooled_text_embed_dim=pooled,
+        max_latent_resolution=max_res,
+    )
+
+
 @dataclass(frozen=True)
 class VAEDecoderConfig:
     """reference config.py:126-132"""
@@ -287,6 +322,7 @@ MMDIT_CKPT = {
     "argmaxinc/mlx-FLUX.1-schnell": "argmaxinc/mlx-FLUX.1-schnell",
     "argmaxinc/mlx-FLUX.1-schnell-4bit-quantized": "argmaxinc/mlx-FLUX.1-schnell-4bit-quantized",
     "argmaxinc/mlx-FLUX.1-dev": "argmaxinc/mlx-FLUX.1-dev",
+    "stabilityai/stable-diffusion-3.5-medium": "stabilityai/stable-diffusion-3.5-medium",  # (no reference counterpart: local checkpoints only)
 }
 
 T5_MAX_LENGTH = {
@@ -296,6 +332,7 @@ T5_MAX_LENGTH = {
     "argmaxinc/mlx-FLUX.1-schnell": 256,
     "argmaxinc/mlx-FLUX.1-schnell-4bit-quantized": 256,
     "argmaxinc/mlx-FLUX.1-dev": 512,
+    "stabilityai/stable-diffusion-3.5-medium": 512,
 }
 
 # reference model_io.py:104-111 (_CONFIG): which MMDiT preset a model_version selects
@@ -306,4 +343,5 @@ MODEL_CONFIG = {
     "argmaxinc/mlx-FLUX.1-dev": FLUX_SCHNELL,  # quirk Q7: dev runs without guidance embedding
     "argmaxinc/mlx-stable-diffusion-3.5-large": SD3_8b,
     "argmaxinc/mlx-stable-diffusion-3.5-large-4bit-quantized": SD3_8b,
+    "stabilityai/stable-diffusion-3.5-medium": SD3_5_MEDIUM,
 }

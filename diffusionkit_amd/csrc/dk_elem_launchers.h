@@ -18,6 +18,11 @@ int dk_launch_qk_norm_rope(bf16_t* qkv, int ld, int q_off, int k_off, int rows, 
 int dk_launch_ln_modulate2(const bf16_t* x0, bf16_t* out0, int M0, const bf16_t* shift0, const bf16_t* scale0, int seg0, const bf16_t* x1,
                            bf16_t* out1, int M1, const bf16_t* shift1, const bf16_t* scale1, int seg1, int ldx, int ldo, int h,
                            int mod_stride, int x_seg_stride, float eps, hipStream_t stream);
+// ... the first of which leaves twice, under two modulations (MMDiT-X: the image stream of a dual-attention block); M1 == 0: one row set
+int dk_launch_ln_modulate2x(const bf16_t* x0, bf16_t* out0, bf16_t* out0b, int M0, const bf16_t* shift0, const bf16_t* scale0,
+                            const bf16_t* shift0b, const bf16_t* scale0b, int seg0, const bf16_t* x1, bf16_t* out1, int M1,
+                            const bf16_t* shift1, const bf16_t* scale1, int seg1, int ldx, int ldo, int h, int mod_stride, int x_seg_stride,
+                            int x_seg_stride1, float eps, hipStream_t stream);
 int dk_launch_qk_norm_rope2(bf16_t* qkv0, int rows0, const bf16_t* qw0, const bf16_t* kw0, int seg0, int pos0, bf16_t* qkv1, int rows1,
                             const bf16_t* qw1, const bf16_t* kw1, int seg1, int pos1, int ld, int q_off, int k_off, int H, int D,
                             float eps, const float* rope, int row_seg_stride, hipStream_t stream, int k_only = 0);

@@ -24,13 +24,25 @@ struct LnJob {
 // are dropped, one 32-bit offset register serves all three arrays, and the row stays in its packed bf16 form (unpacked again
 // in each pass) so the kernel holds 12 * NCH data registers.
 static_assert(sizeof(LnJob) % 8 == 0 && alignof(LnJob) == 8, "job b follows job a without padding in the kernarg segment");
-template <int NCH>
-__global__ __launch_bounds__(256) void dk_ln_modulate_kernel(LnJob ja, LnJob jb, int blocks_a, int h, float eps) {
+// DUAL (MMDiT-X, the image stream of a dual-attention block): a job carries a second (shift, scale, out) triple, and the row -- loaded and
+// reduced once -- leaves twice, out2 = bf16( LN(x) * bf16(1 + scale2[b]) + shift2[b] ) from the same registers with the same expression and
+// rounding.  A job without one (the text stream riding in the same launch) has out2 null and shift2 / scale2 = its first pair: the loads
+// stay unconditional, the second store is skipped on a wave-uniform test.  The plain instantiations do not see any of this.
+struct LnJob2 : LnJob {
+  bf16_t* out2;
+  const bf16_t *shift2, *scale2;
+};
+static_assert(sizeof(LnJob2) % 8 == 0 && alignof(LnJob2) == 8, "job b follows job a without padding in the kernarg segment");
+template <bool DUAL> struct LnJobOf { typedef LnJob type; };
+template <> struct LnJobOf<true> { typedef LnJob2 type; };
+template <int NCH, bool DUAL = false>
+__global__ __launch_bounds__(256) void dk_ln_modulate_kernel(typename LnJobOf<DUAL>::type ja, typename LnJobOf<DUAL>::type jb, int blocks_a, int h, float eps) {
+  typedef typename LnJobOf<DUAL>::type Job;
   const bool first = (int)blockIdx.x < blocks_a;
   // one scalar base pointer into the kernarg segment (`first ? ja : jb` copies both jobs to scratch, see gemm256v3.hip)
-  typedef const __attribute__((address_space(4))) LnJob karg_job_t;
+  typedef const __attribute__((address_space(4))) Job karg_job_t;
   const __attribute__((address_space(4))) char* kbase = (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
-  karg_job_t& j = *(karg_job_t*)(kbase + (first ? 0 : sizeof(LnJob)));
+  karg_job_t& j = *(karg_job_t*)(kbase + (first ? 0 : sizeof(Job)));
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (uniform: row bases live in SGPRs)
   const int m = ((int)blockIdx.x - (first ? 0 : blocks_a)) * 4 + wave;
   if (m >= j.M) return;
@@ -48,6 +60,23 @@ __global__ __launch_bounds__(256) void dk_ln_modulate_kernel(LnJob ja, LnJob jb,
   for (int i = 0; i < NCH; ++i) {
     rs[i] = __builtin_amdgcn_raw_buffer_load_b128(rsh, (lane + 64 * i) * 16, 0, 0);
     rc[i] = __builtin_amdgcn_raw_buffer_load_b128(rsc, (lane + 64 * i) * 16, 0, 0);
+  }
+  // the second triple (DUAL): its loads join the same round trip; a plain kernel keeps one register of each array, never touched
+  constexpr int NCH2 = DUAL ? NCH : 1;
+  u32x4 rs2[NCH2], rc2[NCH2];
+  __amdgpu_buffer_rsrc_t ro2 = ro;
+  bool second = false;
+  if constexpr (DUAL) {
+    const __amdgpu_buffer_rsrc_t rsh2 = __builtin_amdgcn_make_buffer_rsrc((void*)(j.shift2 + mod), 0, h * 2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsc2 = __builtin_amdgcn_make_buffer_rsrc((void*)(j.scale2 + mod), 0, h * 2, 0x00020000);
+    second = j.out2 != nullptr;
+    // (a job without a second output: a resource of zero bytes at the first output's row -- nothing can be stored through it)
+    ro2 = __builtin_amdgcn_make_buffer_rsrc((void*)((second ? j.out2 : j.out) + (size_t)m * j.ldo), 0, second ? h * 2 : 0, 0x00020000);
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+      rs2[i] = __builtin_amdgcn_raw_buffer_load_b128(rsh2, (lane + 64 * i) * 16, 0, 0);
+      rc2[i] = __builtin_amdgcn_raw_buffer_load_b128(rsc2, (lane + 64 * i) * 16, 0, 0);
+    }
   }
   __builtin_amdgcn_sched_barrier(0);  // (without it the scheduler sinks the shift / scale loads below the two reductions)
   float sum = 0.f;
@@ -93,6 +122,22 @@ __global__ __launch_bounds__(256) void dk_ln_modulate_kernel(LnJob ja, LnJob jb,
       o[e] = pack2(y0, y1);
     }
     __builtin_amdgcn_raw_buffer_store_b128(o, ro, (lane + 64 * i) * 16, 0, 0);
+    if constexpr (DUAL) {
+      if (second) {  // (wave-uniform)
+        u32x4 o2;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float v0, v1, s0, s1, c0, c1;
+          unpack2(raw[i][e], v0, v1);
+          unpack2(rs2[i][e], s0, s1);
+          unpack2(rc2[i][e], c0, c1);
+          const float y0 = (v0 - mean) * rstd * round_act(1.0f + c0) + s0;
+          const float y1 = (v1 - mean) * rstd * round_act(1.0f + c1) + s1;
+          o2[e] = pack2(y0, y1);
+        }
+        __builtin_amdgcn_raw_buffer_store_b128(o2, ro2, (lane + 64 * i) * 16, 0, 0);
+      }
+    }
   }
 }
 
@@ -127,6 +172,45 @@ int dk_launch_ln_modulate(const bf16_t* x, int ldx, bf16_t* out, int ldo, int M,
                           hipStream_t stream) {
   LnJob none = ln_job(nullptr, 8, nullptr, 8, 0, nullptr, nullptr, 8, 1, 1, 0);
   return launch_ln_jobs(ln_job(x, ldx, out, ldo, M, shift, scale, mod_stride, seg_len, x_seg_len, x_seg_stride), none, h, eps, stream);
+}
+// the DUAL instantiations: job a with its two triples, job b plain (M == 0: absent)
+static int launch_ln_jobs_dual(const LnJob2& a, const LnJob2& b, int h, float eps, hipStream_t stream) {
+  DK_REQUIRE(h % 8 == 0 && h <= 4096, "hidden size must be a multiple of 8 and <= 4096");
+  for (const LnJob2* j : {&a, &b})
+    DK_REQUIRE(j->M == 0 || (j->ldx % 8 == 0 && j->ldo % 8 == 0 && j->mod_stride % 8 == 0), "strides must keep 16-byte alignment");
+  const int blocks_a = (a.M + 3) / 4, blocks_b = (b.M + 3) / 4;
+  dim3 grid(blocks_a + blocks_b), block(256);
+  const int nch = (h / 8 + 63) / 64;
+#define LN_CASE(N)                                                                                               \
+  case N:                                                                                                        \
+    hipLaunchKernelGGL((dk_ln_modulate_kernel<N, true>), grid, block, 0, stream, a, b, blocks_a, h, eps);        \
+    break;
+  switch (nch) {
+    LN_CASE(1) LN_CASE(2) LN_CASE(3) LN_CASE(4) LN_CASE(5) LN_CASE(6) LN_CASE(7) LN_CASE(8)
+    default: DK_REQUIRE(false, "unsupported hidden size");
+  }
+#undef LN_CASE
+  DK_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+static LnJob2 ln_job2(const LnJob& j, bf16_t* out2, const bf16_t* shift2, const bf16_t* scale2) {
+  LnJob2 d;
+  static_cast<LnJob&>(d) = j;
+  d.out2 = out2; d.shift2 = out2 ? shift2 : j.shift; d.scale2 = out2 ? scale2 : j.scale;
+  return d;
+}
+// ... of which the first leaves twice (MMDiT-X dual-attention block: out0 under (shift0, scale0), out0b under (shift0b, scale0b)); M1 == 0:
+// no second row set (x_seg_stride1: its own segment stride -- the engine's two streams share one, S)
+int dk_launch_ln_modulate2x(const bf16_t* x0, bf16_t* out0, bf16_t* out0b, int M0, const bf16_t* shift0, const bf16_t* scale0,
+                            const bf16_t* shift0b, const bf16_t* scale0b, int seg0, const bf16_t* x1, bf16_t* out1, int M1,
+                            const bf16_t* shift1, const bf16_t* scale1, int seg1, int ldx, int ldo, int h, int mod_stride, int x_seg_stride,
+                            int x_seg_stride1, float eps, hipStream_t stream) {
+  DK_REQUIRE(x0 && out0 && out0b && shift0 && scale0 && shift0b && scale0b && M0 > 0 && seg0 > 0, "ln_modulate2x: the dual job needs both triples");
+  DK_REQUIRE(M1 == 0 || (x1 && out1 && shift1 && scale1 && seg1 > 0), "ln_modulate2x: bad second row set");
+  const LnJob b = M1 > 0 ? ln_job(x1, ldx, out1, ldo, M1, shift1, scale1, mod_stride, seg1, seg1, x_seg_stride1)
+                         : ln_job(nullptr, 8, nullptr, 8, 0, nullptr, nullptr, 8, 1, 1, 0);
+  return launch_ln_jobs_dual(ln_job2(ln_job(x0, ldx, out0, ldo, M0, shift0, scale0, mod_stride, seg0, seg0, x_seg_stride), out0b, shift0b, scale0b),
+                             ln_job2(b, nullptr, nullptr, nullptr), h, eps, stream);
 }
 // two row sets (image / text stream) of the same hidden size in one launch
 int dk_launch_ln_modulate2(const bf16_t* x0, bf16_t* out0, int M0, const bf16_t* shift0, const bf16_t* scale0, int seg0, const bf16_t* x1,

@@ -30,6 +30,9 @@ struct StreamW {  // one TransformerBlock's weights (mmdit.py:395-438)
   // fp8_linears: e4m3 weights + per-output-channel scales instead of the bf16 matrices above (biases stay bf16)
   const unsigned char *qkv_w8 = nullptr, *o_w8 = nullptr, *fc1_w8 = nullptr, *fc2_w8 = nullptr, *l2_w8 = nullptr;
   const float *qkv_ws = nullptr, *o_ws = nullptr, *fc1_ws = nullptr, *fc2_ws = nullptr, *l2_ws = nullptr;
+  // MMDiT-X (dk_mmdit_set_dual_attention), image stream of a dual block: the second attention's q | k | v matrix with its FULL bias (attn2's
+  // k_proj keeps its bias), its own QKNorm weights and its output projection
+  const bf16_t *qkv2_w = nullptr, *qkv2_b = nullptr, *qn2 = nullptr, *kn2 = nullptr, *o2_w = nullptr, *o2_b = nullptr;
 };
 
 struct dk_mmdit {
@@ -79,6 +82,11 @@ struct dk_mmdit {
   long rows8 = 0;
   // element type of every bound tensor, activation buffer and of the token / text / pooled I/O (dk_mmdit_set_activation_dtype): sizes are the same
   int dtype = DK_DTYPE_BF16;
+  // MMDiT-X dual attention (dk_mmdit_set_dual_attention): double blocks [0, n_dual) run a second attention over the image stream alone, from a
+  // second modulation of the block's LayerNorm (XN2 [B S_x, h]) through QKV2 [B S_x, 3h] into ATT2 [B S_x, h]; their image modules have 9 rows
+  int n_dual = 0;
+  bf16_t *XN2 = nullptr, *QKV2 = nullptr, *ATT2 = nullptr;
+  int img_rows(int i) const { return i < n_dual ? 9 : 6; }
   // first-block cache (dk_mmdit_set_block_cache; include/dk_hip.h): image rows [B * S_i, h] each.  BC_R: X1 at the start of a compute tail, R
   // behind it.  BC_D[bc_cur]: X0 before block 0, D_cur behind the probe; BC_D[1 - bc_cur]: D_ref -- a compute tail swaps the two.
   // BC_ROWS: the probe's (num, den) per image row.  bc_valid: R / D_ref come from a computed step since the last reset; bc_pending: the step
@@ -107,14 +115,14 @@ struct dk_mmdit {
   bool txt_skipped(int i) const { return i == cfg.depth_multimodal - 1 && cfg.depth_unified < 1; }
   int mod_rows() const {
     int n = 0;
-    for (int i = 0; i < cfg.depth_multimodal; ++i) n += 6 + (txt_skipped(i) ? 2 : 6);
+    for (int i = 0; i < cfg.depth_multimodal; ++i) n += img_rows(i) + (txt_skipped(i) ? 2 : 6);
     return n + 3 * cfg.depth_unified + 2;
   }
   int mod_offset(int kind, int index) const {
     int n = 0;
     for (int i = 0; i < cfg.depth_multimodal; ++i) {
       if (kind == 0 && i == index) return n;
-      n += 6;
+      n += img_rows(i);
       if (kind == 1 && i == index) return n;
       n += txt_skipped(i) ? 2 : 6;
     }
@@ -163,6 +171,17 @@ extern "C" int dk_mmdit_set_activation_dtype(dk_mmdit* m, int32_t dtype) {
     DK_REQUIRE(m->D() == 64 && m->cfg.depth_unified == 0 && m->cfg.fp8_linears == 0,
                "fp16 activations are the SD3 family's: head_dim == 64, depth_unified == 0, fp8_linears == 0");
   m->dtype = dtype;
+  return 0;
+}
+extern "C" int dk_mmdit_set_dual_attention(dk_mmdit* m, int32_t n_blocks) {
+  DK_REQUIRE(m != nullptr, "null handle");
+  DK_REQUIRE(!m->resolved && !m->prepared, "dk_mmdit_set_dual_attention is legal only before the weights are resolved (the first dk_mmdit_prepare)");
+  DK_REQUIRE(n_blocks >= 0 && n_blocks <= m->cfg.depth_multimodal, "dual attention blocks must lie in [0, depth_multimodal]");
+  if (n_blocks > 0)
+    DK_REQUIRE(m->cfg.depth_unified == 0 && m->cfg.fp8_linears == 0,
+               "dual attention blocks are the SD3 family's (MMDiT-X): depth_unified == 0 and fp8_linears == 0");
+  m->n_dual = n_blocks;
+  m->mod_ready = false;
   return 0;
 }
 extern "C" void dk_mmdit_destroy(dk_mmdit* m) { delete m; }
@@ -218,6 +237,31 @@ static int resolve_stream(dk_mmdit* m, const std::string& p, StreamW& w, bool si
   return 0;
 }
 
+// the second attention of an MMDiT-X image stream: required inside the dual range, refused outside it (a checkpoint with attn2 tensors on an
+// engine that would ignore them is a configuration error, not something to run)
+static int resolve_attn2(dk_mmdit* m, const std::string& p, StreamW& w, bool dual) {
+  const auto& n = m->named;
+  static const char* const kNames[] = {".attn2.qkv.weight", ".attn2.qkv.bias", ".attn2.o_proj.weight", ".attn2.o_proj.bias", ".qk_norm2.q_norm.weight",
+                                       ".qk_norm2.k_norm.weight"};
+  if (!dual) {
+    for (const char* s : kNames)
+      if (n.find(p + s) != n.end()) {
+        dk_set_error("weight bound outside the dual attention range (dk_mmdit_set_dual_attention): " + p + s);
+        return -3;
+      }
+    return 0;
+  }
+  DK_TRY(need(n, p + ".attn2.qkv.weight", &w.qkv2_w));
+  DK_TRY(need(n, p + ".attn2.qkv.bias", &w.qkv2_b));
+  DK_TRY(need(n, p + ".attn2.o_proj.weight", &w.o2_w));
+  DK_TRY(need(n, p + ".attn2.o_proj.bias", &w.o2_b));
+  if (m->cfg.use_qk_norm) {
+    DK_TRY(need(n, p + ".qk_norm2.q_norm.weight", &w.qn2));
+    DK_TRY(need(n, p + ".qk_norm2.k_norm.weight", &w.kn2));
+  }
+  return 0;
+}
+
 static int mmdit_resolve(dk_mmdit* m) {
   if (m->resolved) return 0;
   const auto& n = m->named;
@@ -255,6 +299,7 @@ static int mmdit_resolve(dk_mmdit* m) {
     // (the fused QKNorm decisions of a double block are taken per stream from these pointers and must agree: ADVICE r4)
     DK_REQUIRE((m->dimg[i].qn == nullptr) == (m->dtxt[i].qn == nullptr) && (m->dimg[i].kn == nullptr) == (m->dtxt[i].kn == nullptr),
                "QKNorm weights must be bound for both streams of a double block or for neither");
+    DK_TRY(resolve_attn2(m, b + ".image_transformer_block", m->dimg[i], i < m->n_dual));
   }
   for (int i = 0; i < m->cfg.depth_unified; ++i)
     DK_TRY(resolve_stream(m, "unified_transformer_blocks." + std::to_string(i) + ".transformer_block", m->single[i], true, false, m->fp8()));
@@ -325,6 +370,13 @@ static size_t mmdit_carve(dk_mmdit* m, Carver& c, int B, int Hl, int Wl, int S_t
   if (S_r > 0) m->REFE = (bf16_t*)c.take((size_t)B * S_r * h * 2);  // (behind everything else, and no take at all without a reference)
   m->CONDE = nullptr;
   if (m->cond_f > 0) m->CONDE = (bf16_t*)c.take((size_t)B * S_i * h * 2);  // (the same: no take with the width off)
+  m->XN2 = m->QKV2 = m->ATT2 = nullptr;
+  if (m->n_dual > 0) {  // (the same: no take without dual blocks)
+    const size_t Mi = (size_t)B * S_x;
+    m->XN2 = (bf16_t*)c.take(Mi * h * 2);
+    m->QKV2 = (bf16_t*)c.take(Mi * 3 * h * 2);
+    m->ATT2 = (bf16_t*)c.take(Mi * h * 2);
+  }
   return c.off;
 }
 
@@ -578,8 +630,14 @@ static int double_block_bf16(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t
   const Rows HID_img = dense(m->HID, ldh), HID_txt = dense(m->HID + (size_t)Mi * ldh, ldh);  // MLP hidden of both streams
   // pre_sdpa (mmdit.py:440-519): LN-modulate, q/k/v projection, QK-norm (+ RoPE)
   // (image and text stream of each elementwise stage in ONE launch: the 256 text rows do not run alone on the chip)
-  DK_TRY(DK_EL(L.dtype, dk_launch_ln_modulate2)(X_img.p, XN_img.p, Mi, mod_img, mod_img + h, S_i, X_txt.p, XN_txt.p, Mt, mod_txt, mod_txt + h, S_t, h, h, h,
-                                mod_stride, S, cf.layer_norm_eps, st));
+  // (MMDiT-X dual block: the image rows leave the same pass a second time, under shift_msa2 / scale_msa2 -- rows 6 and 7 of the 9 -- into XN2)
+  const bool dual = i < m->n_dual;
+  if (dual)
+    DK_TRY(DK_EL(L.dtype, dk_launch_ln_modulate2x)(X_img.p, XN_img.p, m->XN2, Mi, mod_img, mod_img + h, mod_img + 6 * h, mod_img + 7 * h, S_i, X_txt.p,
+                                                   XN_txt.p, Mt, mod_txt, mod_txt + h, S_t, h, h, h, mod_stride, S, S, cf.layer_norm_eps, st));
+  else
+    DK_TRY(DK_EL(L.dtype, dk_launch_ln_modulate2)(X_img.p, XN_img.p, Mi, mod_img, mod_img + h, S_i, X_txt.p, XN_txt.p, Mt, mod_txt, mod_txt + h, S_t, h, h, h,
+                                                  mod_stride, S, cf.layer_norm_eps, st));
   Linear qkv_img = Linear(L.dtype, XN_img, wi.qkv_w, wi.qkv_b, m->img(m->QKV, 3 * h), Mi, 3 * h, h, DK_EPI_BIAS).split_ws(L.kws);
   Linear qkv_txt = Linear(L.dtype, XN_txt, wt.qkv_w, wt.qkv_b, m->txt(m->QKV, 3 * h), Mt, 3 * h, h, DK_EPI_BIAS).split_ws(L.kws);
   // QKNorm + RoPE: the keys in the projection's tail (or one pass over the buffer), the queries inside the attention kernel's Q load
@@ -592,7 +650,25 @@ static int double_block_bf16(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t
   if (!kf)
     DK_TRY(DK_EL(L.dtype, dk_launch_qk_norm_rope2)(m->QKV + (size_t)S_t * 3 * h, Mi, wi.qn, wi.kn, S_i, S_t, m->QKV, Mt, wt.qn, wt.kn, S_t, 0, 3 * h, 0, h,
                                    cf.num_heads, m->D(), 1e-6f, c.rope, S, st, fuse_q()));
+  // attn2's projection on the second modulation, a launch of its own: it has the image job's M and fills the chip as that one does, and the
+  // pair above stays the launch of a plain block.  Its QKNorm follows the same switches as the main attention's, without a RoPE table
+  const bool kf2 = dual && fuse_k(wi.kn2);
+  if (dual) {
+    Linear qkv2 = Linear(L.dtype, dense(m->XN2, h), wi.qkv2_w, wi.qkv2_b, dense(m->QKV2, 3 * h), Mi, 3 * h, h, DK_EPI_BIAS).split_ws(L.kws);
+    if (kf2) set_key_norm(qkv2, wi.kn2, wi.qn2, h, m->D(), nullptr, 0, S_i);
+    DK_TRY(dk_launch_gemm(qkv2, st));
+    if (!kf2)
+      DK_TRY(DK_EL(L.dtype, dk_launch_qk_norm_rope)(m->QKV2, 3 * h, 0, h, Mi, cf.num_heads, m->D(), wi.qn2, wi.kn2, 1e-6f, nullptr, S_i, S_i, 0, S_i, st, fuse_q()));
+  }
   DK_TRY(dk_launch_attention(joint_attention(m, c, m->ATT, h, wt, &wi), L.aws, st));
+  if (dual) {  // the image stream alone: [B, S_i] dense rows of QKV2, no text rows, no RoPE
+    AttnParams ap;
+    ap.dtype = m->dtype;
+    ap.Q = m->QKV2; ap.K = m->QKV2 + h; ap.V = m->QKV2 + 2 * h; ap.O = m->ATT2;
+    ap.B = c.B; ap.H = cf.num_heads; ap.S = S_i; ap.D = m->D(); ap.ld = 3 * h; ap.ldo = h; ap.scale = c.scale;
+    if (fuse_q() && !(kf2 && fuse_qg(wi.qn2, false))) { ap.qn_a = wi.qn2; ap.qn_b = wi.qn2; ap.qn_split = 0; }
+    DK_TRY(dk_launch_attention(ap, L.aws, st));
+  }
   // post_sdpa, sequential form (mmdit.py:537-548): residual += gate_attn * o_proj(attn)
   const Linear o_img = Linear(L.dtype, m->img(m->ATT, h), wi.o_w, wi.o_b, X_img, Mi, h, h, DK_EPI_GATE_RES)
                            .gate_res(mod_img + 2 * h, S_i, mod_stride, X_img).split_ws(L.kws);
@@ -603,6 +679,10 @@ static int double_block_bf16(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t
   } else {
     DK_TRY(dk_launch_gemm(o_img, st));
   }
+  // ... += gate_msa2 * attn2.o_proj(a2) (row 8 of the 9): behind o_proj, both write X_img in place
+  if (dual)
+    DK_TRY(dk_launch_gemm(Linear(L.dtype, dense(m->ATT2, h), wi.o2_w, wi.o2_b, X_img, Mi, h, h, DK_EPI_GATE_RES)
+                              .gate_res(mod_img + 8 * h, S_i, mod_stride, X_img).split_ws(L.kws), st));
   // residual += gate_mlp * fc2(gelu(fc1(LN-mod(residual))))
   if (txt_post)
     DK_TRY(DK_EL(L.dtype, dk_launch_ln_modulate2)(X_img.p, XN_img.p, Mi, mod_img + 3 * h, mod_img + 4 * h, S_i, X_txt.p, XN_txt.p, Mt, mod_txt + 3 * h,

@@ -98,6 +98,14 @@ class MMDiTEngine:
         if self.condition_features:
             _lib.check(self.lib.dk_mmdit_set_condition_width(self._h, self.condition_features), "dk_mmdit_set_condition_width")
         self._cond_cached = False
+        # MMDiT-X dual-attention blocks: the 9-row image modules and the attn2 weights of the first n blocks (before anything is bound)
+        from .config import validate_dual_attention
+        try:
+            validate_dual_attention(config)
+        except ValueError as e:
+            raise _lib.DkHipError(str(e)) from None
+        if config.dual_attention_blocks:
+            _lib.check(self.lib.dk_mmdit_set_dual_attention(self._h, int(config.dual_attention_blocks)), "dk_mmdit_set_dual_attention")
         self.weights = packed_weights  # keep the device tensors alive
         for name, t in packed_weights.items():
             want = torch.uint8 if name.endswith(".weight_fp8") else torch.float32 if name.endswith(".wscale") else self.dtype

@@ -13,7 +13,9 @@ key, plus the four tensor transformations the reference performs:
     quirk Q8, so only one bias is kept);
   * conv weights OIHW -> OHWI (:398-400, :455-484), 1x1 convs (VAE attention q/k/v/proj_out,
     nin_shortcut) -> Linear weights;
-  * SD3 ``pos_embed`` [1, T, h] -> ``x_pos_embedder.pos_embed.weight`` [T, h] (:392-396).
+  * SD3 ``pos_embed`` [1, T, h] -> ``x_pos_embedder.pos_embed.weight`` [T, h] (:392-396);
+  * SD3.5 medium (MMDiT-X, no reference counterpart): ``x_block.attn2.qkv`` -> ``attn2.{q,k,v}_proj`` WITH the k bias,
+    ``attn2.proj`` -> ``attn2.o_proj``, ``attn2.ln_q|ln_k`` -> ``qk_norm2.{q,k}_norm``, and a 9h-row ``adaLN_modulation.1``.
 
 The result is the dict ``diffusionkit_amd.weights.pack_mmdit`` / ``pack_vae`` consume, i.e. exactly
 what ``synth_mmdit_weights`` / ``synth_vae_weights`` produce for the benchmarks.  FLUX.1-dev's
@@ -188,6 +190,20 @@ def sd3_checkpoint_to_reference(sd: StateDict, cfg: MMDiTConfig, prefix: str = "
                 out[f"{base}.attn.o_proj.{leaf}"] = t
             elif part in ("attn.ln_q", "attn.ln_k"):
                 out[f"{base}.qk_norm.{part[-1]}_norm.{leaf}"] = t
+            elif part.startswith("attn2."):
+                # MMDiT-X (SD3.5 medium): the image stream's second attention, blocks [0, dual_attention_blocks) only; its k_proj keeps the bias
+                if m2.group(2) != "x_block" or int(m2.group(1)) >= cfg.dual_attention_blocks:
+                    raise CheckpointError(f"{k0}: an attn2 tensor outside the image streams of blocks [0, dual_attention_blocks = "
+                                          f"{cfg.dual_attention_blocks}) of the configuration")
+                if part == "attn2.qkv":
+                    for n, piece in zip("qkv", torch.chunk(t, 3, dim=0)):
+                        out[f"{base}.attn2.{n}_proj.{leaf}"] = piece
+                elif part == "attn2.proj":
+                    out[f"{base}.attn2.o_proj.{leaf}"] = t
+                elif part in ("attn2.ln_q", "attn2.ln_k"):
+                    out[f"{base}.qk_norm2.{part[-1]}_norm.{leaf}"] = t
+                else:
+                    raise CheckpointError(f"unknown SD3 block tensor: {k0}")
             elif part in ("mlp.fc1", "mlp.fc2"):
                 out[f"{base}.{part}.{leaf}"] = t
             elif part == "adaLN_modulation.1":
@@ -205,6 +221,9 @@ def _check_mmdit_complete(out: StateDict, cfg: MMDiTConfig) -> None:
     missing = sorted(set(want) - set(out))
     if missing:
         raise CheckpointError(f"checkpoint lacks {len(missing)} tensors, first: {missing[:3]}")
+    extra2 = sorted(k for k in set(out) - set(want) if ".attn2." in k or ".qk_norm2." in k)
+    if extra2:
+        raise CheckpointError(f"{extra2[0]}: an attn2 tensor outside blocks [0, dual_attention_blocks = {cfg.dual_attention_blocks})")
     for k, shp in want.items():
         if tuple(out[k].shape) != shp:
             raise CheckpointError(f"{k}: shape {tuple(out[k].shape)} != expected {shp}")

@@ -330,6 +330,36 @@ def ln_modulate(x: Tensor, shift: Tensor, scale: Tensor, eps: float = 1e-6) -> T
     return out
 
 
+def ln_modulate_dual(x: Tensor, shift_a: Tensor, scale_a: Tensor, shift_b: Tensor, scale_b: Tensor, text=None, eps: float = 1e-6):
+    """One LayerNorm pass, two modulated outputs (dk_ln_modulate_dual_*, the first launch of an MMDiT-X dual-attention block).
+    x: [B, S, h]; shift_* / scale_*: [B, h] views of ONE modulation table (equal row strides) -> (out_a, out_b), each what ``ln_modulate`` gives
+    for its pair.  ``text``: optionally (x1 [B, S1, h], shift1, scale1), a plain second row set in the same launch -> (out_a, out_b, out1)."""
+    lib = _lib.load()
+    name = "dk_ln_modulate_dual_" + _elem(x.dtype, "ln_modulate_dual")
+    _require_cuda(x, "x")
+    mods = [("shift_a", shift_a), ("scale_a", scale_a), ("shift_b", shift_b), ("scale_b", scale_b)]
+    x1 = None
+    if text is not None:
+        x1, shift1, scale1 = text
+        _require_cuda(x1, "text x")
+        mods += [("text shift", shift1), ("text scale", scale1)]
+    B, S, h = x.shape
+    for n, t in mods:
+        if t.dtype != x.dtype or t.stride(0) != shift_a.stride(0) or tuple(t.shape) != (B, h) or t.stride(1) != 1:
+            raise _lib.DkHipError(f"{n} must be a [{B}, {h}] {x.dtype} view with the row stride of shift_a")
+    out_a, out_b = torch.empty_like(x), torch.empty_like(x)
+    if x1 is not None:
+        if x1.dtype != x.dtype or x1.shape[0] != B or x1.shape[2] != h:
+            raise _lib.DkHipError("text x must be [B, S1, h] in x's dtype")
+        out1, S1 = torch.empty_like(x1), x1.shape[1]
+        args1 = (x1.data_ptr(), out1.data_ptr(), B * S1, mods[4][1].data_ptr(), mods[5][1].data_ptr(), S1)
+    else:
+        args1 = (None, None, 0, None, None, 0)
+    _lib.check(getattr(lib, name)(x.data_ptr(), out_a.data_ptr(), out_b.data_ptr(), B * S, shift_a.data_ptr(), scale_a.data_ptr(),
+                                  shift_b.data_ptr(), scale_b.data_ptr(), S, *args1, h, h, h, shift_a.stride(0), S, args1[5], eps, _stream()), name)
+    return (out_a, out_b) if x1 is None else (out_a, out_b, out1)
+
+
 def block_probe(x: Tensor, s_t: int, d: Tensor, d_ref: Optional[Tensor] = None):
     """First-block-cache probe (dk_block_probe_*).  x: the joint stream [B, S, h] behind block 0 (text rows first, ``s_t`` of them per
     batch row; only the image rows are read); d: [B, S - s_t, h], X0's image rows on entry, D_cur = round(x - d) on return; d_ref: the

@@ -11,7 +11,8 @@ so a real checkpoint loader ("next" row f1) only has to produce the same dict.
 engine binds by name:
   * q/k/v projections -> one [3h, h] matrix, bias [3h] with a zero k part (quirk Q9);
   * single blocks: q|k|v|fc1 -> linear1 [7h, h]; o_proj | fc2 -> linear2 [h, 5h] with ONE bias (quirk Q8);
-  * all adaLN_modulation Linears -> one [rows*h, h] matrix in the engine's row order;
+  * all adaLN_modulation Linears -> one [rows*h, h] matrix in the engine's row order (the image module of an MMDiT-X
+    dual-attention block contributes 9h rows); such a block's attn2 q/k/v -> one [3h, h] matrix with a FULL bias;
   * conv weights [O,3,3,I] -> [O, 9*I] (already K-major in the MLX layout), conv_in padded to I=64.
 """
 from __future__ import annotations
@@ -106,6 +107,22 @@ def synth_mmdit_weights(cfg: MMDiTConfig, seed: int = 1234, device="cpu", dtype=
         block(f"unified_transformer_blocks.{i}.transformer_block", 3, parallel=True)
     I.linear("final_layer.linear", cfg.patch_dim, h)
     I.linear("final_layer.adaLN_modulation.layers.1", 2 * h, h)
+    # MMDiT-X dual-attention blocks (cfg.dual_attention_blocks): the second attention of the image stream -- k_proj WITH its bias -- and rows
+    # 6h .. 9h of its adaLN Linear (shift / scale / gate of attn2), appended to the six drawn above.  Drawn behind everything else: a
+    # configuration without dual blocks gets the random stream it always got, and one with them the same first six rows
+    for i in range(cfg.dual_attention_blocks):
+        prefix = f"multimodal_transformer_blocks.{i}.image_transformer_block"
+        for n in "qkv":
+            I.linear(f"{prefix}.attn2.{n}_proj", h, h)
+        if cfg.use_qk_norm:
+            I.normal(prefix + ".qk_norm2.q_norm.weight", (D,), mean=1.0)
+            I.normal(prefix + ".qk_norm2.k_norm.weight", (D,), mean=1.0)
+        I.linear(prefix + ".attn2.o_proj", h, h)
+        for leaf, shape in ((".weight", (3 * h, h)), (".bias", (3 * h,))):
+            name = prefix + ".adaLN_modulation.layers.1" + leaf
+            I.normal(name + ".msa2", shape)
+            rows = I.out.pop(name + ".msa2")
+            I.out[name] = (9 * h,) + tuple(shape[1:]) if shapes_only else torch.cat([I.out[name], rows], dim=0)  # (the key keeps its place)
     return I.out
 
 
@@ -241,8 +258,9 @@ def pack_mmdit(cfg: MMDiTConfig, w: Dict[str, Tensor], device, consume: bool = F
     dev = torch.device(device)
     # element type of every tensor the engine binds: cfg.activation_dtype.  float16: a value from an fp16 or fp32 source is rounded once to fp16,
     # and an fp16 checkpoint tensor reaches the device bit for bit (same names, pitches and fusions)
-    from .config import validate_activation_dtype
+    from .config import validate_activation_dtype, validate_dual_attention
     validate_activation_dtype(cfg)
+    validate_dual_attention(cfg)
     bf = torch.float16 if cfg.activation_dtype == "float16" else torch.bfloat16
     fp8 = cfg.weight_dtype == "fp8_e4m3"
     out: Dict[str, Tensor] = {}
@@ -333,9 +351,22 @@ def pack_mmdit(cfg: MMDiTConfig, w: Dict[str, Tensor], device, consume: bool = F
             put_pitched(f"{prefix}.mlp.fc2.weight", get(f"{prefix}.mlp.fc2.weight"))
             put(f"{prefix}.mlp.fc2.bias", get(f"{prefix}.mlp.fc2.bias"))
 
+    def attn2(prefix):
+        """the second attention of an MMDiT-X image stream: q | k | v with the full bias (attn2.k_proj keeps its bias: quirk Q9 is the reference's
+        ``attn``), the output projection and its own QKNorm weights, under the names dk_mmdit_set_dual_attention documents"""
+        put(prefix + ".attn2.qkv.weight", torch.cat([get(f"{prefix}.attn2.{n}_proj.weight").to(dev) for n in "qkv"], dim=0))
+        put(prefix + ".attn2.qkv.bias", torch.cat([get(f"{prefix}.attn2.{n}_proj.bias").to(dev) for n in "qkv"], dim=0))
+        if cfg.use_qk_norm:
+            put(prefix + ".qk_norm2.q_norm.weight", get(prefix + ".qk_norm2.q_norm.weight"))
+            put(prefix + ".qk_norm2.k_norm.weight", get(prefix + ".qk_norm2.k_norm.weight"))
+        put(prefix + ".attn2.o_proj.weight", get(prefix + ".attn2.o_proj.weight"))
+        put(prefix + ".attn2.o_proj.bias", get(prefix + ".attn2.o_proj.bias"))
+
     for i in range(cfg.depth_multimodal):
         skip_txt = (i == cfg.depth_multimodal - 1) and cfg.depth_unified < 1
         stream(f"multimodal_transformer_blocks.{i}.image_transformer_block")
+        if i < cfg.dual_attention_blocks:
+            attn2(f"multimodal_transformer_blocks.{i}.image_transformer_block")
         stream(f"multimodal_transformer_blocks.{i}.text_transformer_block", skip_post=skip_txt)
     for i in range(cfg.depth_unified):
         stream(f"unified_transformer_blocks.{i}.transformer_block", single=True)

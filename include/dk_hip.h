@@ -343,6 +343,15 @@ int32_t dk_weight_pitch_fp8(int32_t k);
 int dk_ln_modulate_bf16(const void* x, int32_t ldx, void* out, int32_t ldo, int32_t M, int32_t h,
                         const void* shift, const void* scale, int32_t mod_stride, int32_t mod_seg_len,
                         int32_t x_seg_len, int32_t x_seg_stride, float eps, void* stream);
+/* One LayerNorm pass with two modulated outputs (MMDiT-X dual-attention blocks, see dk_mmdit_set_dual_attention): the M rows of x are
+ * loaded and reduced once and leave twice, out_a under (shift_a, scale_a) and out_b under (shift_b, scale_b) -- each bit-identical to a
+ * dk_ln_modulate_bf16 call with the same operands.  Logical row m of x is physical row (m / mod_seg_len) * x_seg_stride + m % mod_seg_len;
+ * the outputs are dense [M, ldo]; modulation row b = m / mod_seg_len at b * mod_stride.  A second, plain row set (x1, out1, M1, shift1,
+ * scale1, mod_seg_len1, x_seg_stride1; same ldx / ldo / mod_stride) rides in the same launch as in the engine's double blocks; M1 == 0: none. */
+int dk_ln_modulate_dual_bf16(const void* x, void* out_a, void* out_b, int32_t M, const void* shift_a, const void* scale_a,
+                             const void* shift_b, const void* scale_b, int32_t mod_seg_len, const void* x1, void* out1, int32_t M1,
+                             const void* shift1, const void* scale1, int32_t mod_seg_len1, int32_t ldx, int32_t ldo, int32_t h,
+                             int32_t mod_stride, int32_t x_seg_stride, int32_t x_seg_stride1, float eps, void* stream);
 
 /* QKNorm (mmdit.py:754-764) + RoPE.apply (mmdit.py:934-942), in place on the q / k column groups
  * of a token-major QKV buffer.  q_weight/k_weight NULL = no norm; rope_table NULL = no rotation.
@@ -510,6 +519,10 @@ int dk_attention_plan_f16(const dk_attention_desc* d, size_t workspace_bytes, dk
 int dk_ln_modulate_f16(const void* x, int32_t ldx, void* out, int32_t ldo, int32_t M, int32_t h,
                        const void* shift, const void* scale, int32_t mod_stride, int32_t mod_seg_len,
                        int32_t x_seg_len, int32_t x_seg_stride, float eps, void* stream);
+int dk_ln_modulate_dual_f16(const void* x, void* out_a, void* out_b, int32_t M, const void* shift_a, const void* scale_a,
+                            const void* shift_b, const void* scale_b, int32_t mod_seg_len, const void* x1, void* out1, int32_t M1,
+                            const void* shift1, const void* scale1, int32_t mod_seg_len1, int32_t ldx, int32_t ldo, int32_t h,
+                            int32_t mod_stride, int32_t x_seg_stride, int32_t x_seg_stride1, float eps, void* stream);
 int dk_qk_norm_rope_f16(void* qkv, int32_t ld, int32_t q_off, int32_t k_off, int32_t rows, int32_t H,
                         int32_t D, const void* q_weight, const void* k_weight, float eps, const float* rope_table,
                         int32_t row_seg_len, int32_t row_seg_stride, int32_t pos_off, void* stream);
@@ -713,6 +726,33 @@ int dk_mmdit_cache_reference(dk_mmdit* m, const void* ref_tokens, int32_t per_im
  * names the rule, never launch. */
 int dk_mmdit_set_condition_width(dk_mmdit* m, int32_t cond_features);
 int dk_mmdit_cache_condition(dk_mmdit* m, const void* cond_tokens, int32_t per_image, void* stream);
+
+/* ---- MMDiT-X dual-attention blocks (opt-in; Stable Diffusion 3.5 medium, no counterpart in the reference) ---------------------------
+ * The first n_blocks double blocks carry a second self-attention over the image-stream rows alone (published model definition:
+ * Stability's mmditx.py x_block.attn2, diffusers' JointTransformerBlock(use_dual_attention=True)).  The image module of such a block has
+ * NINE modulation rows -- shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp, shift_msa2, scale_msa2, gate_msa2: the first six
+ * are the row order of every other block -- and the block computes, with n = LN(x) taken once,
+ *   m1 = n (1 + scale_msa) + shift_msa  -> attn.qkv  -> the joint attention with the text stream, as in every double block
+ *   m2 = n (1 + scale_msa2) + shift_msa2 -> attn2.qkv -> QK-RMSNorm (attn2's own weights, eps 1e-6) -> SDPA over the image rows of each
+ *        batch row alone (same heads, head_dim and 1 / sqrt(D) scale; no text rows, no RoPE)
+ *   x += gate_msa * attn.o_proj(joint attention's image rows);  x += gate_msa2 * attn2.o_proj(a2);  then the MLP half, unchanged.
+ * One rounding per Linear output, modulate, norm and gated add, as in the existing block.  The text stream of a dual block and the
+ * blocks i >= n_blocks are what they are without the feature.
+ * Bound names, required for image streams i < n_blocks and refused (at resolve time, naming the tensor) for the others:
+ *   <image block>.attn2.qkv.{weight,bias}     [3h, h] / [3h], q | k | v; the bias is FULL: attn2.k_proj keeps its bias (quirk Q9 is a
+ *                                             property of the reference's `attn`; behind an RMSNorm a key bias is not a no-op)
+ *   <image block>.attn2.o_proj.{weight,bias}  [h, h] / [h]
+ *   <image block>.qk_norm2.{q,k}_norm.weight  [head_dim] (with use_qk_norm)
+ * and adaLN.{weight,bias} holds 9 h rows for these image modules (dk_mmdit_mod_rows / dk_mmdit_mod_offset count them).
+ * Verified against an fp32 / bf16-emulating oracle of this block form with synthetic weights (arithmetic parity); no SD3.5-medium
+ * checkpoint has been run through it.
+ *
+ * dk_mmdit_set_dual_attention: legal until the weights are resolved (the first dk_mmdit_prepare).  0, the default, is the feature off:
+ * the modulation table, dk_mmdit_workspace_bytes, the carve and every launch are then what they are without it; n_blocks > 0 adds XN2
+ * [B S_x, h], QKV2 [B S_x, 3h] and ATT2 [B S_x, h] behind everything else in the workspace.  Refused, with no state changed and an
+ * error that names the rule: n_blocks outside [0, depth_multimodal], a configuration with depth_unified > 0 or fp8_linears, an engine
+ * whose weights are resolved. */
+int dk_mmdit_set_dual_attention(dk_mmdit* m, int32_t n_blocks);
 /* Head of step `step_index`: dk_mmdit_forward's embedder launches, block 0 and the probe.  probe_out: device float [batch][2] =
  * (num, den) per batch row; before any computed step den is 0 (and num = sum |D_cur|).  Records a pending head for step_index. */
 int dk_mmdit_forward_head(dk_mmdit* m, const void* tokens_in, const void* text, int32_t step_index, float* probe_out, void* stream);
