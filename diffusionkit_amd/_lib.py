@@ -135,14 +135,16 @@ class dk_attention_plan_t(C.Structure):  # (o8_split is read by dk_attention_pla
 
 # the step entries (dk_euler / dk_lms / dk_guided _cfg_step, their masked and _f16 forms), composed: x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl,
 # C, p, reshape_order, sigma; then Euler's sigma_next, cfg_weight, or the row's cfg_weight, hist, five coefficients, sigma_next, reads_h, writes_h; then
-# the mask operands x_orig, noise, mask, mask_per_image; then mode, phi, eta, r, beta, reads_m, writes_m, m, workspace, its bytes; then the stream
+# the mask operands x_orig, noise, mask, mask_per_image; then mode, phi, eta, r, beta, reads_m, writes_m, m, workspace, its bytes; then (dk_slg_cfg_step)
+# slg_scale; then the stream
 _STEP_HEAD = [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32]
 _STEP_EULER = _STEP_HEAD + [_f32, _f32]
 _STEP_ROW = _STEP_HEAD + [_f32, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _i32]
 _STEP_MASK = [_vp, _vp, _vp, _i32]
 _STEP_GUIDE = [_i32, _f32, _f32, _f32, _f32, _i32, _i32, _vp, _vp, _sz]
 _STEP_ENTRIES = {"dk_euler_cfg_step": _STEP_EULER, "dk_euler_cfg_step_masked": _STEP_EULER + _STEP_MASK, "dk_lms_cfg_step": _STEP_ROW,
-                 "dk_lms_cfg_step_masked": _STEP_ROW + _STEP_MASK, "dk_guided_cfg_step": _STEP_ROW + _STEP_MASK + _STEP_GUIDE}
+                 "dk_lms_cfg_step_masked": _STEP_ROW + _STEP_MASK, "dk_guided_cfg_step": _STEP_ROW + _STEP_MASK + _STEP_GUIDE,
+                 "dk_slg_cfg_step": _STEP_ROW + _STEP_MASK + _STEP_GUIDE + [_f32]}
 SIGNATURES = {
     "dk_abi_version": (_i32, []),
     "dk_last_error": (C.c_char_p, []),
@@ -233,6 +235,8 @@ SIGNATURES = {
     "dk_mmdit_cache_condition": (_i32, [_vp, _vp, _i32, _vp]),
     # MMDiT-X dual-attention blocks (Stable Diffusion 3.5 medium): the engine's setter and the LayerNorm pass with two modulated outputs
     "dk_mmdit_set_dual_attention": (_i32, [_vp, _i32]),
+    # skip-layer guidance: the engine's forked row group (the step entry is dk_slg_cfg_step above)
+    "dk_mmdit_set_skip_layers": (_i32, [_vp, C.POINTER(_i32), _i32, _i32]),
     **{"dk_ln_modulate_dual_" + el: (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
                                             _i32, _f32, _vp]) for el in ("bf16", "f16")},
     "dk_image_mask_out_f32": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),

@@ -345,3 +345,10 @@ MODEL_CONFIG = {
     "argmaxinc/mlx-stable-diffusion-3.5-large-4bit-quantized": SD3_8b,
     "stabilityai/stable-diffusion-3.5-medium": SD3_5_MEDIUM,
 }
+
+# Skip-layer guidance: the sampling recipe published with a model version (Stability's sd3_infer.py and diffusers' StableDiffusion3Pipeline run
+# SD3.5-medium with it): the double blocks the third evaluation skips, the scale of its term and the (start, stop) fractions of the schedule.
+# Every other SD3 version must name its layers (pipeline ``skip_layers=``).  Arithmetic only: no SD3.5-medium checkpoint has been run here.
+SKIP_LAYER_GUIDANCE = {
+    "stabilityai/stable-diffusion-3.5-medium": {"layers": (7, 8, 9), "scale": 2.5, "interval": (0.01, 0.2)},
+}

@@ -433,13 +433,17 @@ extern "C" int dk_latent_to_tokens_f16(const float* x, void* tokens, int32_t n_i
   return latent_to_tokens(DK_DTYPE_F16, x, tokens, n_img, dup, Hl, Wl, C, p, reshape_order, stream);
 }
 
-// ---- the step tail: ten entries (Euler, coefficient row, guided; plain and masked; bf16 and fp16) over one parameter block, one check, one launcher
+// ---- the step tail: twelve entries (Euler, coefficient row, guided, skip-layer; plain and masked; bf16 and fp16) over one parameter block, one check, one launcher
 // Every requirement of a step launch.  The guided entries' own come first, then the common ones, so that a call that breaks one rule is told what it
 // always was; the structured binding gives the fields the names the messages quote.
 static int check_step(const StepParams& s) {
   const auto& [x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight, has_row, cx, cd, ch, hx, hd,
                hist, reads_h, writes_h, masked, x_orig, noise, mask, mask_per_image, guided, mode, phi, eta, r, beta, m, reads_m, writes_m, workspace,
-               workspace_bytes] = s;
+               workspace_bytes, slg, slg_scale] = s;
+  if (slg) {
+    DK_REQUIRE(cfg_on != 0, "skip-layer guidance adds its term to a guided prediction: cfg_on must be set");
+    DK_REQUIRE(std::isfinite(slg_scale), "slg_scale must be finite");
+  }
   if (guided) {
     DK_REQUIRE(cfg_on != 0, "guidance modes combine two predictions: cfg_on must be set (an unguided row is dk_lms_cfg_step with cfg_on = 0)");
     DK_REQUIRE(mode >= 0 && mode <= 2, "unknown guidance mode (0 cfg, 1 rescale, 2 apg)");
@@ -574,6 +578,33 @@ extern "C" int dk_guided_cfg_step_f16(float* x, const void* model_out, int32_t l
   const StepParams s = step_operands(x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight);
   const StepParams b = with_blend(with_row(s, hist, cx, cd, ch, hx, hd, reads_h, writes_h), x_orig || noise || mask, x_orig, noise, mask, mask_per_image);
   return step(DK_DTYPE_F16, with_guidance(b, mode, phi, eta, r, beta, reads_m, writes_m, m, workspace, workspace_bytes), stream);
+}
+
+// skip-layer guidance: the guided step on three row groups, den + slg_scale (c - k)
+static StepParams with_skip_layers(StepParams s, float slg_scale) {
+  s.slg = true, s.slg_scale = slg_scale;
+  return s;
+}
+extern "C" int dk_slg_cfg_step(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on, int32_t Hl, int32_t Wl,
+                               int32_t C, int32_t p, int32_t reshape_order, float sigma, float cfg_weight, float* hist, float cx, float cd, float ch,
+                               float hx, float hd, float sigma_next, int32_t reads_h, int32_t writes_h, const float* x_orig, const float* noise,
+                               const float* mask, int32_t mask_per_image, int32_t mode, float phi, float eta, float r, float beta, int32_t reads_m,
+                               int32_t writes_m, float* m, void* workspace, size_t workspace_bytes, float slg_scale, void* stream) {
+  const StepParams s = step_operands(x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight);
+  const StepParams b = with_blend(with_row(s, hist, cx, cd, ch, hx, hd, reads_h, writes_h), x_orig || noise || mask, x_orig, noise, mask, mask_per_image);
+  return step(DK_DTYPE_BF16, with_skip_layers(with_guidance(b, mode, phi, eta, r, beta, reads_m, writes_m, m, workspace, workspace_bytes), slg_scale),
+              stream);
+}
+extern "C" int dk_slg_cfg_step_f16(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on, int32_t Hl,
+                                   int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma, float cfg_weight, float* hist, float cx,
+                                   float cd, float ch, float hx, float hd, float sigma_next, int32_t reads_h, int32_t writes_h, const float* x_orig,
+                                   const float* noise, const float* mask, int32_t mask_per_image, int32_t mode, float phi, float eta, float r,
+                                   float beta, int32_t reads_m, int32_t writes_m, float* m, void* workspace, size_t workspace_bytes, float slg_scale,
+                                   void* stream) {
+  const StepParams s = step_operands(x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight);
+  const StepParams b = with_blend(with_row(s, hist, cx, cd, ch, hx, hd, reads_h, writes_h), x_orig || noise || mask, x_orig, noise, mask, mask_per_image);
+  return step(DK_DTYPE_F16, with_skip_layers(with_guidance(b, mode, phi, eta, r, beta, reads_m, writes_m, m, workspace, workspace_bytes), slg_scale),
+              stream);
 }
 
 extern "C" int dk_mask_to_latent_f32(const uint8_t* mask, float* out, int32_t n_mask, int32_t H, int32_t W, int32_t f, void* stream) {

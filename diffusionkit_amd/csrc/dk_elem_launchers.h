@@ -68,6 +68,10 @@ struct StepParams {
   bool reads_m, writes_m;
   void* workspace;
   size_t workspace_bytes;
+  // skip-layer guidance (slg: a dk_slg_* call, which needs cfg_on): model_out holds a third row group [2 n_img, 3 n_img), and den takes
+  // slg_scale (c - k) with k its x0 prediction; the tokens keep their two copies
+  bool slg;
+  float slg_scale;
 };
 #endif
 size_t dk_guidance_workspace_size(int n_img, int Hl, int Wl, int C);

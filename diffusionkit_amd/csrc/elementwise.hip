@@ -691,14 +691,18 @@ struct LmsRow {
 //   APG      D = (c - u) [+ beta * M],  den = c + (w - 1)(a D - b c)   (a, b) = scal[2 img], scal[2 img + 1]
 // The per-image scalars come from the moments pass below, which forms c, u, g and D by the same expressions.  M (fp32, shaped like the latent)
 // follows hist's discipline: read only under reads_m, written (M' = D) only under writes_m, each element by the thread that read it.
+// Skip-layer guidance (SLG, include/dk_hip.h: dk_slg_cfg_step): model_out holds a third row group [2 n_img, 3 n_img), the evaluation with blocks
+// skipped; with k its x0 prediction, formed by step_den like c and u, the mode's den takes one more term, den + slg_scale * (c - k).  The tokens
+// are stored as ever, in the two live copies.  SLG = false is the kernel as it was: the third group and slg_scale are not read.
 enum { DK_GUIDE_CFG = 0, DK_GUIDE_RESCALE = 1, DK_GUIDE_APG = 2 };
 struct GuideArgs {
   const float* scal;
   float* m;
   float beta;
   int reads_m, writes_m;
+  float slg_scale;  // (in the struct's tail padding: the argument layout of every instantiation stays)
 };
-template <bool MASKED, int GMODE = DK_GUIDE_CFG>
+template <bool MASKED, int GMODE = DK_GUIDE_CFG, bool SLG = false>
 __global__ void dk_lms_step_kernel(float* x, const bf16_t* model_out, int ld_out, bf16_t* tok, int n_img, int cfg_on, int Hl, int Wl,
                                    int C, int p, int reshape_order, float sigma, float sigma_next, float cfg_weight, float* hist,
                                    LmsRow row, const float* x_orig, const float* noise, const float* mask, int mask_per_image,
@@ -710,6 +714,10 @@ __global__ void dk_lms_step_kernel(float* x, const bf16_t* model_out, int ld_out
   const float xv = x[i];
   const float xb = round_act(xv);  // the value the denoiser saw
   float den = step_den(model_out, ld_out, k.img, k.S_i, k.t, k.f, xb, sigma);
+  float slg = 0.0f;
+  if constexpr (SLG) {  // (cfg_on != 0: check_step)
+    slg = gd.slg_scale * (den - step_den(model_out, ld_out, 2 * n_img + k.img, k.S_i, k.t, k.f, xb, sigma));
+  }
   if constexpr (GMODE == DK_GUIDE_CFG) {
     if (cfg_on) {
       const float den_neg = step_den(model_out, ld_out, n_img + k.img, k.S_i, k.t, k.f, xb, sigma);
@@ -728,7 +736,12 @@ __global__ void dk_lms_step_kernel(float* x, const bf16_t* model_out, int ld_out
       den = den + (cfg_weight - 1.0f) * (a * dl - b * den);
     }
   }
-  const float d = (xv - den) / sigma;
+  float num = xv - den;
+  if constexpr (SLG) {
+    num = num - slg;  // x - (den + slg), taken behind the difference: a product that forms den may be contracted into it, and with slg_scale == 0 the
+                      // exact zero then leaves the bits of the mode's own step
+  }
+  const float d = num / sigma;
   float xn;
   if (row.reads_h)
     xn = row.cx * xv + row.cd * d + row.ch * hist[i];
@@ -847,7 +860,7 @@ __global__ __launch_bounds__(64) void dk_guide_fold_kernel(const double* part, f
 // The one launcher of the step tail (StepParams, dk_elem_launchers.h): the Euler kernel without a row, else the row kernel of the block's
 // (masked, mode), behind the two moments launches under modes 1 and 2.  What an instantiation does not read (the blend operands unmasked, gd
 // under mode 0) is passed as the block holds it.  The instantiations are named in the order the object has always held them: its .text is
-// compared byte for byte across host-only changes (scripts/device_code_diff.py).
+// compared byte for byte across host-only changes (scripts/device_code_diff.py).  The skip-layer forms of the row kernel come behind them.
 int dk_launch_step(const StepParams& s, hipStream_t stream) {
   const long per_img = (long)s.Hl * s.Wl * s.C;
   const long n = (long)s.n_img * per_img;
@@ -883,8 +896,16 @@ int dk_launch_step(const StepParams& s, hipStream_t stream) {
     hipLaunchKernelGGL(fold, dim3(s.n_img), dim3(64), 0, stream, part, scal, nb, (double)per_img, s.phi, s.eta, s.r);
     DK_CHECK_HIP(hipGetLastError());
   }
+  if (s.slg) {  // (the moments above read rows [0, 2 n_img) and are the mode's own)
+    if (s.mode == DK_GUIDE_CFG)
+      kernel = s.masked ? dk_lms_step_kernel<true, DK_GUIDE_CFG, true> : dk_lms_step_kernel<false, DK_GUIDE_CFG, true>;
+    else if (s.mode == DK_GUIDE_RESCALE)
+      kernel = s.masked ? dk_lms_step_kernel<true, DK_GUIDE_RESCALE, true> : dk_lms_step_kernel<false, DK_GUIDE_RESCALE, true>;
+    else
+      kernel = s.masked ? dk_lms_step_kernel<true, DK_GUIDE_APG, true> : dk_lms_step_kernel<false, DK_GUIDE_APG, true>;
+  }
   const LmsRow row = {s.cx, s.cd, s.ch, s.hx, s.hd, s.reads_h, s.writes_h};
-  const GuideArgs gd = {scal, s.m, s.beta, s.reads_m, s.writes_m};
+  const GuideArgs gd = {scal, s.m, s.beta, s.reads_m, s.writes_m, s.slg_scale};
   hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, s.x, s.model_out, s.ld_out, s.tok, s.n_img, s.cfg_on, s.Hl, s.Wl, s.C, s.p, s.reshape_order,
                      s.sigma, s.sigma_next, s.cfg_weight, s.hist, row, s.x_orig, s.noise, s.mask, (int)s.mask_per_image, gd);
   DK_CHECK_HIP(hipGetLastError());

@@ -1,5 +1,6 @@
 // C-ABI layer (include/dk_hip.h), part 2: the MMDiT engine (dk_mmdit_*), which sequences the gfx950 kernels of the transformer blocks.
 // Host code only: no kernels are defined here.
+#include <algorithm>
 #include <cmath>
 #include <type_traits>
 #include <vector>
@@ -87,6 +88,12 @@ struct dk_mmdit {
   int n_dual = 0;
   bf16_t *XN2 = nullptr, *QKV2 = nullptr, *ATT2 = nullptr;
   int img_rows(int i) const { return i < n_dual ? 9 : 6; }
+  // skip-layer guidance (dk_mmdit_set_skip_layers): the last fork_rows batch rows are a copy of the first fork_rows that joins in front of double
+  // block min(skip) and sits out the blocks in skip (sorted, distinct).  Empty / 0: off
+  std::vector<int32_t> skip;
+  int fork_rows = 0;
+  bool slg() const { return !skip.empty(); }
+  bool skipped(int g) const { return std::find(skip.begin(), skip.end(), g) != skip.end(); }
   // first-block cache (dk_mmdit_set_block_cache; include/dk_hip.h): image rows [B * S_i, h] each.  BC_R: X1 at the start of a compute tail, R
   // behind it.  BC_D[bc_cur]: X0 before block 0, D_cur behind the probe; BC_D[1 - bc_cur]: D_ref -- a compute tail swaps the two.
   // BC_ROWS: the probe's (num, den) per image row.  bc_valid: R / D_ref come from a computed step since the last reset; bc_pending: the step
@@ -572,10 +579,11 @@ struct BlockCtx {
   bool att_split;
   Mx8Out xn_img, xn_txt, xn_all;  // (xn_all -- single blocks: the joint stream from row 0, any M)
 };
-static BlockCtx block_ctx(const dk_mmdit* m) {
+// (B: the batch rows [0, B) the blocks run on -- the prepared batch, or its live rows while a forked row group sits out, dk_mmdit_set_skip_layers)
+static BlockCtx block_ctx(const dk_mmdit* m, int B) {
   BlockCtx c;
   memset(&c, 0, sizeof(c));
-  c.h = m->h(); c.B = m->B; c.S = m->S; c.S_t = m->S_t; c.S_i = m->S_x; c.Mi = m->B * m->S_x; c.Mt = m->B * m->S_t;
+  c.h = m->h(); c.B = B; c.S = m->S; c.S_t = m->S_t; c.S_i = m->S_x; c.Mi = B * m->S_x; c.Mt = B * m->S_t;
   c.mod_stride = m->mod_rows() * c.h;
   c.scale = 1.0f / sqrtf((float)m->D());
   c.rope = m->cfg.use_rope ? m->rope : nullptr;
@@ -848,9 +856,10 @@ static int single_block_fp8(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t*
 }
 
 // Blocks [first, first + count) of the global order (double blocks 0 .. depth_multimodal - 1, then single blocks) on the joint residual
-// stream m->X: the bf16 double blocks of the precision policy on the bf16 path, everything else on the model's own
-static int mmdit_blocks(dk_mmdit* m, const bf16_t* mod_step, int first, int count, const LaunchCtx& L) {
-  const BlockCtx c = block_ctx(m);
+// stream m->X: the bf16 double blocks of the precision policy on the bf16 path, everything else on the model's own.  rows: the batch rows
+// [0, rows) they run on, the launches of a batch of that size on the same buffers (0: the prepared batch)
+static int mmdit_blocks(dk_mmdit* m, const bf16_t* mod_step, int first, int count, const LaunchCtx& L, int rows = 0) {
+  const BlockCtx c = block_ctx(m, rows > 0 ? rows : m->B);
   const int n_double = m->cfg.depth_multimodal;
   for (int g = first; g < first + count; ++g) {
     const bool f8 = m->fp8() && g >= m->n_bf16();
@@ -862,11 +871,12 @@ static int mmdit_blocks(dk_mmdit* m, const bf16_t* mod_step, int first, int coun
   return 0;
 }
 
-// the embedders of a forward call: text rows and image rows of the joint stream m->X
-static int mmdit_embed(dk_mmdit* m, const void* tokens_in, const void* text, const LaunchCtx& L) {
+// the embedders of a forward call: text rows and image rows of the joint stream m->X (rows: as in mmdit_blocks -- the operands' rows behind
+// them are not read)
+static int mmdit_embed(dk_mmdit* m, const void* tokens_in, const void* text, const LaunchCtx& L, int rows = 0) {
   const hipStream_t st = L.st;
   const dk_mmdit_config& c = m->cfg;
-  const int h = m->h(), B = m->B, S = m->S, S_t = m->S_t, S_i = m->S_i, F = m->F();
+  const int h = m->h(), B = rows > 0 ? rows : m->B, S = m->S, S_t = m->S_t, S_i = m->S_i, F = m->F();
   DK_TRY(need_reference(m));
   DK_TRY(need_condition(m));
   // context_embedder (mmdit.py:195): text rows of the joint stream -- recomputed from `text`, or copied from the
@@ -895,6 +905,49 @@ static int mmdit_embed(dk_mmdit* m, const void* tokens_in, const void* text, con
   return 0;
 }
 
+// ---- skip-layer guidance (include/dk_hip.h) -----------------------------------------------------------------------------------------
+extern "C" int dk_mmdit_set_skip_layers(dk_mmdit* m, const int32_t* blocks, int32_t n_blocks, int32_t fork_rows) {
+  DK_REQUIRE(m != nullptr, "null handle");
+  DK_REQUIRE(n_blocks >= 0 && fork_rows >= 0, "skip layers: n_blocks and fork_rows must not be negative");
+  DK_REQUIRE((n_blocks == 0) == (fork_rows == 0), "skip layers: n_blocks and fork_rows are both zero (off) or both positive");
+  if (n_blocks == 0) {
+    m->skip.clear();
+    m->fork_rows = 0;
+    return 0;
+  }
+  DK_REQUIRE(blocks != nullptr, "null argument");
+  DK_REQUIRE(m->cfg.depth_unified == 0, "skip layers are the SD3 family's: depth_unified must be 0");
+  DK_REQUIRE(m->cfg.fp8_linears == 0, "skip layers cannot be set on an engine with fp8_linears");
+  DK_REQUIRE(m->ref_h == 0 && m->ref_w == 0 && m->cond_f == 0, "skip layers cannot be set while a reference grid or a condition width is set");
+  std::vector<int32_t> v(blocks, blocks + n_blocks);
+  std::sort(v.begin(), v.end());
+  DK_REQUIRE(v.front() >= 0 && v.back() < m->cfg.depth_multimodal, "skip layers: every block must lie in [0, depth_multimodal)");
+  DK_REQUIRE(std::adjacent_find(v.begin(), v.end()) == v.end(), "skip layers: a block is named twice (duplicate)");
+  m->skip = v;
+  m->fork_rows = fork_rows;
+  return 0;
+}
+static int no_skip_layers(const dk_mmdit* m, const char* entry) {
+  if (!m->slg()) return 0;
+  dk_set_error(std::string(entry) + " cannot run while skip layers are set (dk_mmdit_set_skip_layers): only dk_mmdit_forward forks the row group");
+  return -1;
+}
+// dk_mmdit_forward with skip layers set: rows [0, live) alone up to the first skipped block, there the fork rows become a copy of rows
+// [0, fork_rows), and from there on they run every block but the skipped ones -- each group of launches is the driver's for its row count
+static int mmdit_forward_forked(dk_mmdit* m, const void* tokens_in, const void* text, const bf16_t* mod_step, bf16_t* tokens_out, const LaunchCtx& L) {
+  const int B = m->B, fork = m->fork_rows, live = B - fork, depth = m->cfg.depth_multimodal;
+  DK_REQUIRE(2 * fork <= B, "skip layers: 2 * fork_rows must not exceed the prepared batch (the fork rows copy rows [0, fork_rows))");
+  DK_REQUIRE(m->S_r == 0 && m->cond_f == 0 && m->cfg.depth_unified == 0 && !m->fp8(),
+             "skip layers cannot run with a reference grid, a condition width, single blocks or fp8_linears");
+  const int first = m->skip.front();
+  DK_TRY(mmdit_embed(m, tokens_in, text, L, live));
+  if (first > 0) DK_TRY(mmdit_blocks(m, mod_step, 0, first, L, live));
+  const size_t row = (size_t)m->S * m->h() * 2;
+  DK_CHECK_HIP(hipMemcpyAsync(m->X + (size_t)live * m->S * m->h(), m->X, (size_t)fork * row, hipMemcpyDeviceToDevice, L.st));
+  for (int g = first; g < depth; ++g) DK_TRY(mmdit_blocks(m, mod_step, g, 1, L, m->skipped(g) ? live : B));
+  return mmdit_final_layer(m, mod_step, tokens_out, L);
+}
+
 extern "C" int dk_mmdit_forward(dk_mmdit* m, const void* tokens_in, const void* text, int32_t step_index, void* tokens_out,
                                 void* stream) {
   DK_REQUIRE(m && m->prepared && m->mod_ready, "prepare + cache_modulation_params must precede forward");
@@ -902,6 +955,7 @@ extern "C" int dk_mmdit_forward(dk_mmdit* m, const void* tokens_in, const void* 
   const LaunchCtx L = m->ctx(stream);
   const bf16_t* mod_step = m->MOD + (size_t)step_index * m->B * m->mod_rows() * m->h();
   m->bc_pending = -1;  // (a head without its tail is dropped: this call overwrites the stream it left; R / D_ref stay)
+  if (m->slg()) return mmdit_forward_forked(m, tokens_in, text, mod_step, (bf16_t*)tokens_out, L);
   DK_TRY(mmdit_embed(m, tokens_in, text, L));
   DK_TRY(mmdit_blocks(m, mod_step, 0, m->cfg.depth_multimodal + m->cfg.depth_unified, L));
   return mmdit_final_layer(m, mod_step, (bf16_t*)tokens_out, L);
@@ -930,6 +984,7 @@ extern "C" int dk_mmdit_forward_head(dk_mmdit* m, const void* tokens_in, const v
   DK_REQUIRE(m && m->prepared && m->mod_ready, "prepare + cache_modulation_params must precede forward_head");
   DK_REQUIRE(m->bc_on, "forward_head needs the block cache: dk_mmdit_set_block_cache(m, 1) before dk_mmdit_prepare");
   DK_REQUIRE(probe_out != nullptr, "null argument");
+  DK_TRY(no_skip_layers(m, "dk_mmdit_forward_head"));
   DK_REQUIRE(step_index >= 0 && step_index < m->n_t, "step index out of range");
   const LaunchCtx L = m->ctx(stream);
   const int h = m->h();
@@ -947,6 +1002,7 @@ extern "C" int dk_mmdit_forward_head(dk_mmdit* m, const void* tokens_in, const v
 extern "C" int dk_mmdit_forward_tail(dk_mmdit* m, int32_t step_index, int32_t reuse, void* tokens_out, void* stream) {
   DK_REQUIRE(m && m->prepared && m->mod_ready, "prepare + cache_modulation_params must precede forward_tail");
   DK_REQUIRE(m->bc_on && tokens_out != nullptr, "forward_tail needs the block cache and an output");
+  DK_TRY(no_skip_layers(m, "dk_mmdit_forward_tail"));
   DK_REQUIRE(m->bc_pending >= 0, "forward_tail needs a pending head: dk_mmdit_forward_head of this step must run first");
   DK_REQUIRE(m->bc_pending == step_index, "forward_tail must be of the same step as the pending head");
   if (reuse) DK_REQUIRE(m->bc_valid, "forward_tail(reuse = 1) needs a valid cache: a computed step since the last prepare / cache_modulation_params / reset");
@@ -974,6 +1030,7 @@ extern "C" int dk_mmdit_run_blocks(dk_mmdit* m, const void* x_in, void* x_out, i
                                    void* stream) {
   DK_REQUIRE(m && m->prepared && m->mod_ready, "prepare + cache_modulation_params must precede run_blocks");
   DK_REQUIRE(x_in && x_out, "null argument");
+  DK_TRY(no_skip_layers(m, "dk_mmdit_run_blocks"));
   DK_REQUIRE(step_index >= 0 && step_index < m->n_t, "step index out of range");
   const int total = m->cfg.depth_multimodal + m->cfg.depth_unified;
   DK_REQUIRE(first_block >= 0 && n_blocks >= 1 && first_block + n_blocks <= total, "block range outside the model");

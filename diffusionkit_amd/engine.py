@@ -118,11 +118,22 @@ class MMDiTEngine:
         self.block_cache = False
         self.reference_size = (0, 0)  # latent cells of the reference image (prepare(reference_size=...)); (0, 0): none
         self._ref_cached = False
+        self.skip_layers, self.fork_rows = (), 0  # ``set_skip_layers``; ((), 0): off
 
     def __del__(self):
         if getattr(self, "_h", None):
             self.lib.dk_mmdit_destroy(self._h)
             self._h = None
+
+    def set_skip_layers(self, blocks=None, fork_rows: int = 0) -> None:
+        """dk_mmdit_set_skip_layers (skip-layer guidance, include/dk_hip.h): the last ``fork_rows`` batch rows of every later ``forward_tokens``
+        become a copy of the first ``fork_rows`` that joins in front of double block min(``blocks``) and sits out the blocks named; their rows of
+        ``tokens_in``, of ``text`` and of the cached context are never read, and the caller repeats the pooled rows for them.  ``(None, 0)``: off.
+        Takes effect at the next forward; nothing is re-prepared.  ``forward_head`` / ``forward_tail`` / ``run_blocks`` are refused while set."""
+        blocks = [] if blocks is None else [int(b) for b in blocks]
+        arr = (C.c_int32 * len(blocks))(*blocks) if blocks else None
+        _lib.check(self.lib.dk_mmdit_set_skip_layers(self._h, arr, len(blocks), int(fork_rows)), "dk_mmdit_set_skip_layers")
+        self.skip_layers, self.fork_rows = tuple(sorted(blocks)), int(fork_rows)
 
     def _check_pitched_weights(self) -> None:
         """The engine reads the long-reduction weights at ``dk_weight_pitch`` elements per row (include/dk_hip.h); the C ABI

@@ -460,10 +460,10 @@ GUIDANCE_MODES = {"cfg": 0, "rescale": 1, "apg": 2}
 
 
 def _step(what, x, model_out, tokens, n_img, cfg_on, p, reshape_order, sigma, sigma_next, cfg_weight, row=None, blend=None, blend_error=_lib.DkHipError,
-          guide=None) -> None:
+          guide=None, slg_scale=None) -> None:
     """The one call of a step entry, dk_<what> / _f16 by the dtype of ``model_out`` (the argument groups of ``_lib._STEP_ENTRIES``): the operands, then
     ``row`` = (hist, coef, reads_h, writes_h), ``blend`` = (x_orig, noise, mask) and ``guide`` = (mode, phi, eta, r, beta, reads_m, writes_m, m,
-    workspace) where the entry has them, each validated here.  ``blend_error``: what a mask operand of the wrong shape raises -- the Euler wrapper
+    workspace) and ``slg_scale`` where the entry has them, each validated here.  ``blend_error``: what a mask operand of the wrong shape raises -- the Euler wrapper
     says ValueError, in its own words, where the others say DkHipError."""
     name = "dk_" + what + ("" if _elem(model_out.dtype, what) == "bf16" else "_f16")
     if guide is not None and guide[0] not in GUIDANCE_MODES:
@@ -510,6 +510,8 @@ def _step(what, x, model_out, tokens, n_img, cfg_on, p, reshape_order, sigma, si
             ws_bytes = workspace.numel() * workspace.element_size()
         tail += (GUIDANCE_MODES[mode], float(phi), float(eta), float(r), float(beta), int(bool(reads_m)), int(bool(writes_m)), _ptr(m),
                  _ptr(workspace), ws_bytes)
+    if slg_scale is not None:
+        tail += (float(slg_scale),)
     _lib.check(getattr(_lib.load(), name)(x.data_ptr(), model_out.data_ptr(), model_out.shape[-1], tokens.data_ptr(), n_img, int(cfg_on), hl, wl, c, p,
                                           reshape_order, float(sigma), *tail, _stream()), name)
 
@@ -564,6 +566,25 @@ def guided_cfg_step(x: Tensor, model_out: Tensor, tokens: Tensor, n_img: int, cf
     blend = None if x_orig is None and noise is None and mask is None else (x_orig, noise, mask)
     _step("guided_cfg_step", x, model_out, tokens, n_img, cfg_on, p, reshape_order, sigma, sigma_next, cfg_weight,
           row=(hist, coef, reads_h, writes_h), blend=blend, guide=(mode, rescale, eta, norm_threshold, momentum, reads_m, writes_m, m, workspace))
+
+
+def slg_cfg_step(x: Tensor, model_out: Tensor, tokens: Tensor, n_img: int, cfg_on: bool, p: int, reshape_order: int, sigma: float,
+                 sigma_next: float, cfg_weight: float, hist: Optional[Tensor], coef, reads_h: bool, writes_h: bool, *, slg_scale: float,
+                 mode: str = "cfg", workspace: Optional[Tensor] = None, rescale: float = 0.0, eta: float = 0.0, norm_threshold: float = 0.0,
+                 momentum: float = 0.0, reads_m: bool = False, writes_m: bool = False, m: Optional[Tensor] = None, x_orig: Optional[Tensor] = None,
+                 noise: Optional[Tensor] = None, mask: Optional[Tensor] = None) -> None:
+    """dk_slg_cfg_step / _f16 by the dtype of ``model_out``: ``guided_cfg_step`` with skip-layer guidance.  ``model_out`` holds three row groups,
+    [3 * n_img, S_i, ld]: the prompt rows, the negative rows and the prompt rows evaluated with blocks skipped (``MMDiTEngine.set_skip_layers``);
+    den = G(c, u) + ``slg_scale`` * (c - k), G the mode's combination and k the x0 prediction of the third group (``sampler.slg_reference``).
+    ``tokens`` are written in their first 2 * n_img rows only.  ``slg_scale`` 0 gives ``guided_cfg_step``'s bits."""
+    if model_out.dim() == 3 and model_out.shape[0] != 3 * n_img:
+        raise _lib.DkHipError(f"slg_cfg_step: model_out holds {model_out.shape[0]} rows, expected 3 * n_img = {3 * n_img}")
+    if tokens.dim() == 3 and tokens.shape[0] < 2 * n_img:
+        raise _lib.DkHipError(f"slg_cfg_step: tokens hold {tokens.shape[0]} rows, expected at least 2 * n_img = {2 * n_img}")
+    blend = None if x_orig is None and noise is None and mask is None else (x_orig, noise, mask)
+    _step("slg_cfg_step", x, model_out, tokens, n_img, cfg_on, p, reshape_order, sigma, sigma_next, cfg_weight,
+          row=(hist, coef, reads_h, writes_h), blend=blend, guide=(mode, rescale, eta, norm_threshold, momentum, reads_m, writes_m, m, workspace),
+          slg_scale=slg_scale)
 
 
 def mask_to_latent(mask: Tensor, factor: int = 8) -> Tensor:

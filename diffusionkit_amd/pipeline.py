@@ -20,6 +20,11 @@ Guidance (``guidance=``, ``guidance_interval=`` and the mode parameters, keyword
 (default: today's combine), "rescale" and "apg" replace the step launch of ``sample_steps`` by dk_guided_cfg_step, and an interval runs the evaluations
 outside it on the prompt rows alone (``_set_rows``).  The definitions are ``sampler.guide_reference``'s.
 
+Skip-layer guidance (``skip_layer_guidance=``, ``skip_layers=``, ``skip_layer_interval=``, keyword-only, no reference counterpart; the recipe published with
+Stable Diffusion 3.5 medium): in the steps of its window the engine carries a third row group, a copy of the prompt rows that joins in front of the first
+skipped block and sits out the skipped ones (``MMDiTEngine.set_skip_layers``), and the step launch is dk_slg_cfg_step, which adds scale (c - k) to the
+mode's prediction.  The definition is ``sampler.slg_reference``'s.  Arithmetic only, on synthetic weights: no SD3.5-medium checkpoint has been run here.
+
 All arithmetic runs in libdk_hip.so on the current HIP stream; numpy is used exactly where the
 reference uses it (the seeded noise draw, __init__.py:553-557) and for O(num_steps) schedule
 scalars.
@@ -36,10 +41,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .config import (MMDIT_CKPT, MODEL_CONFIG, T5_MAX_LENGTH, MMDiTConfig, VAEDecoderConfig, VAEEncoderConfig)
+from .config import (MMDIT_CKPT, MODEL_CONFIG, SKIP_LAYER_GUIDANCE, T5_MAX_LENGTH, MMDiTConfig, VAEDecoderConfig, VAEEncoderConfig)
 from .engine import MMDiTEngine, VAEDecoderEngine, VAEEncoderEngine, _stream
-from .sampler import (FluxSampler, ModelSamplingDiscreteFlow, check_guidance, check_interval, check_sampler, get_sigmas, guidance_rows, max_denoise,
-                      step_plan)
+from .sampler import (FluxSampler, ModelSamplingDiscreteFlow, check_guidance, check_interval, check_sampler, check_skip_layer_guidance, get_sigmas,
+                      guidance_rows, max_denoise, slg_rows, step_plan)
 from .weights import pack_mmdit, pack_vae, synth_mmdit_weights, synth_vae_encoder_weights, synth_vae_weights
 
 logger = logging.getLogger(__name__)
@@ -484,6 +489,9 @@ class DiffusionPipeline:
         reference_image_path=None,
         condition_image_path=None,
         condition_mask_path=None,
+        skip_layer_guidance=None,
+        skip_layers=None,
+        skip_layer_interval=None,
     ):
         """mlx/__init__.py:253-292.  ``seed`` may be a list: one image per seed is denoised in a
         single batched step loop (data-parallel sharding hands each rank a list).
@@ -521,10 +529,25 @@ class DiffusionPipeline:
         (``MMDiTEngine.cache_condition``); the step loop and every option above are untouched.  Refused before any GPU work: the keywords on a
         pipeline without ``condition``, a ``condition`` pipeline without them, "fill" without a mask, "control" with one, a reference image at the same
         time, the SD3 family.  ``self.last_condition`` = {"kind", "features"}, or None.  Verified as arithmetic only: no Fill / Canny / Depth checkpoint
-        has been run here."""
+        has been run here.
+        ``skip_layer_guidance`` (skip-layer guidance, SD3 family with ``cfg_weight > 0``; None: off): the scale s of a third evaluation per step, the
+        prompt rows through a model that skips the double blocks ``skip_layers``: den = G(pos, neg) + s (pos - skip), G the guidance mode's combination
+        (``sampler.slg_reference``).  Step i of n takes the term iff n start < i < n stop, ``skip_layer_interval`` = (start, stop), and only in
+        evaluations a ``guidance_interval`` leaves guided.  The third evaluation rides as a third row group of the same launches: it joins in front
+        of the first skipped block and sits out the skipped ones, so it costs the blocks it runs; the engine is re-prepared where the group count
+        changes (twice for one window).  ``skip_layers`` / ``skip_layer_interval`` None take the defaults published with the model version
+        (``config.SKIP_LAYER_GUIDANCE``: SD3.5-medium (7, 8, 9) and (0.01, 0.2); ``skip_layer_guidance=True`` takes its scale, 2.5, too); any other
+        version must name its layers, and its interval defaults to (0, 1).  Composes with seed lists, every sampler and guidance mode, img2img,
+        inpainting and float16.  Raises on FLUX, ``cfg_weight <= 0``, ``block_cache`` (no cache policy for a forked row group yet) and a layer outside
+        the model.  ``self.last_skip_layer_guidance`` = {"layers", "scale", "interval", "evals"} (evaluations with the term), or None.  Verified as
+        arithmetic only, on synthetic weights: no SD3.5-medium checkpoint has been run here."""
         check_condition_args(getattr(self, "condition", None), condition_image_path, condition_mask_path, reference_image_path, self._IS_FLUX)
         if reference_image_path is not None and not self._IS_FLUX:
             raise ValueError(_REFERENCE_NEEDS_ROPE)
+        slg = None
+        if skip_layer_guidance is not None or skip_layers is not None or skip_layer_interval is not None:
+            slg = _skip_layer_options(skip_layer_guidance, skip_layers, skip_layer_interval, self.model_version, self.mmdit_config, self._IS_FLUX,
+                                      cfg_weight, block_cache)
         guide = _guidance_options(guidance, guidance_rescale, apg_eta, apg_norm_threshold, apg_momentum, guidance_interval, cfg_weight)
         if mask_path is not None and image_path is None:
             raise ValueError("mask_path needs image_path: the mask says which part of that image to keep")
@@ -566,6 +589,8 @@ class DiffusionPipeline:
             extra_args["block_cache"] = block_cache
         if guide is not None:
             extra_args["guidance"] = guide
+        if slg is not None:
+            extra_args["skip_layer_guidance"] = slg
         self.last_reference = None
         if refs is not None:
             extra_args["reference"] = self.latent_format.process_in(self.encode_reference_to_latents(refs))
@@ -579,7 +604,7 @@ class DiffusionPipeline:
         noise_scaled = self.sampler.noise_scaling(np.float32(sigmas[0]), noise, x_T, self.max_denoise(sigmas))
         x0 = torch.from_numpy(np.ascontiguousarray(noise_scaled, dtype=np.float32)).to(self.device)
         denoiser = CFGDenoiser(self)
-        if sampler == "euler" and guide is None:
+        if sampler == "euler" and guide is None and slg is None:
             latent, iter_time = sample_euler(denoiser, x0, sigmas, extra_args=extra_args)
             evals = len(iter_time)
         else:
@@ -590,6 +615,7 @@ class DiffusionPipeline:
         self.last_block_cache = denoiser.block_cache_record
         self.last_guidance = denoiser.guidance_record or dict(_DEFAULT_GUIDANCE, guided_evals=evals if cfg_weight > 0 else 0,
                                                               unguided_evals=0 if cfg_weight > 0 else evals)
+        self.last_skip_layer_guidance = denoiser.skip_layer_record
         latent = self.latent_format.process_out(latent)
         return latent, iter_time
 
@@ -618,6 +644,9 @@ class DiffusionPipeline:
         reference_image_path=None,
         condition_image_path=None,
         condition_mask_path=None,
+        skip_layer_guidance=None,
+        skip_layers=None,
+        skip_layer_interval=None,
     ):
         """mlx/__init__.py:294-534: returns (PIL.Image, log).  ``mask_path``: inpainting, see ``denoise_latents``; with ``composite`` the pixels
         the mask keeps are pasted back from the input image after decoding (the VAE round trip alone does not reproduce them).
@@ -628,7 +657,9 @@ class DiffusionPipeline:
         ``reference_image_path``: reference-image conditioning, see ``denoise_latents``; with it set, ``log["denoising"]["reference"]`` is
         ``self.last_reference``.
         ``condition_image_path`` / ``condition_mask_path``: channel-concatenated conditioning, see ``denoise_latents``; ``log["denoising"]["condition"]`` is
-        ``self.last_condition``.  With ``composite`` and no ``mask_path``, the pixels a fill mask keeps are pasted back from the condition image."""
+        ``self.last_condition``.  With ``composite`` and no ``mask_path``, the pixels a fill mask keeps are pasted back from the condition image.
+        ``skip_layer_guidance``, ``skip_layers``, ``skip_layer_interval``: skip-layer guidance, see ``denoise_latents``; with it on,
+        ``log["denoising"]["skip_layer_guidance"]`` is ``self.last_skip_layer_guidance``."""
         check_condition_args(getattr(self, "condition", None), condition_image_path, condition_mask_path, reference_image_path, self._IS_FLUX)
         if mask_path is not None and image_path is None:
             raise ValueError("mask_path needs image_path: the mask says which part of that image to keep")
@@ -665,7 +696,9 @@ class DiffusionPipeline:
             sampler=sampler, guidance=guidance, guidance_rescale=guidance_rescale, apg_eta=apg_eta, apg_norm_threshold=apg_norm_threshold,
             apg_momentum=apg_momentum, guidance_interval=guidance_interval,
             **({} if reference_image_path is None else {"reference_image_path": reference_image_path}),
-            **({} if condition_image_path is None else {"condition_image_path": condition_image_path, "condition_mask_path": condition_mask_path}))
+            **({} if condition_image_path is None else {"condition_image_path": condition_image_path, "condition_mask_path": condition_mask_path}),
+            **({} if skip_layer_guidance is None and skip_layers is None and skip_layer_interval is None else
+               {"skip_layer_guidance": skip_layer_guidance, "skip_layers": skip_layers, "skip_layer_interval": skip_layer_interval}))
         torch.cuda.synchronize(dev)
         log["denoising"]["post"] = mem()
         log["peak_memory"] = max(log["peak_memory"], log["denoising"]["post"]["peak_memory"])
@@ -680,6 +713,8 @@ class DiffusionPipeline:
             log["denoising"]["reference"] = self.last_reference
         if condition_image_path is not None:
             log["denoising"]["condition"] = self.last_condition
+        if self.last_skip_layer_guidance is not None:
+            log["denoising"]["skip_layer_guidance"] = self.last_skip_layer_guidance
 
         torch.cuda.reset_peak_memory_stats(dev)
         t0 = time.time()
@@ -876,6 +911,7 @@ class CFGDenoiser:
         self._timesteps: List[float] = []
         self.block_cache_record = None  # what sample_euler decided per step under extra_args["block_cache"]
         self.guidance_record = None  # what sample_steps ran under extra_args["guidance"]
+        self.skip_layer_record = None  # what sample_steps ran under extra_args["skip_layer_guidance"]
 
     def cache_modulation_params(self, pooled_text_embeddings, timesteps):
         self._timesteps = [float(t) for t in timesteps]
@@ -967,6 +1003,37 @@ def _guidance_options(guidance, rescale, eta, norm_threshold, momentum, interval
     return opts
 
 
+def _skip_layer_options(scale, layers, interval, model_version, mmdit_config, is_flux, cfg_weight, block_cache):
+    """The skip-layer keywords of ``denoise_latents`` -> None when the feature is off (``scale`` None, the loops run as they always did), else the dict
+    ``sample_steps`` takes as ``extra_args["skip_layer_guidance"]``: {"scale", "layers", "interval"}.  What the caller leaves None comes from the
+    model version's published recipe (``config.SKIP_LAYER_GUIDANCE``); ``scale`` True asks for its scale as well.  Refused: layers or an interval
+    without a scale, FLUX, ``cfg_weight <= 0``, ``block_cache``, a version without a recipe that names no layers, and whatever
+    ``sampler.check_skip_layer_guidance`` refuses."""
+    if scale is None:
+        if layers is not None or interval is not None:
+            raise ValueError("skip_layers / skip_layer_interval need skip_layer_guidance (the scale of the term; None is off)")
+        return None
+    if is_flux:
+        raise ValueError("skip-layer guidance is the SD3 family's: FLUX runs without classifier-free guidance and its single blocks have no skip form")
+    if not cfg_weight > 0:
+        raise ValueError(f"skip-layer guidance needs classifier-free guidance: cfg_weight is {cfg_weight}, so there is no guided prediction to add to")
+    if block_cache is not None:
+        raise ValueError("skip-layer guidance cannot run together with block_cache: there is no cache policy for a forked row group yet")
+    recipe = SKIP_LAYER_GUIDANCE.get(model_version, {})
+    if scale is True:
+        if "scale" not in recipe:
+            raise ValueError(f"skip_layer_guidance=True takes the scale published with the model version, and {model_version} has none: name a scale")
+        scale = recipe["scale"]
+    if layers is None:
+        if "layers" not in recipe:
+            raise ValueError(f"no skip layers are published for {model_version}: name them (skip_layers=...)")
+        layers = recipe["layers"]
+    if interval is None:
+        interval = recipe.get("interval")
+    scale, layers, interval = check_skip_layer_guidance(scale, layers, interval, mmdit_config.depth_multimodal)
+    return {"scale": scale, "layers": layers, "interval": interval}
+
+
 class _Loop(NamedTuple):
     """what a step loop works on once the engine is prepared (``_loop_setup``)"""
     pipe: object
@@ -987,6 +1054,7 @@ class _Loop(NamedTuple):
     timesteps: object
     reference: Optional[Tensor] = None  # the reference latent f32 [1 or n_img, rh, rw, C] behind ``extra_args["reference"]``, or None
     condition: Optional[Tensor] = None  # the condition token rows bf16 [1 or n_img, S_i, condition_features] behind ``extra_args["condition"]``, or None
+    slg: Optional[dict] = None  # ``extra_args["skip_layer_guidance"]`` (``_skip_layer_options``), or None
 
 
 def _cache_condition(mm, condition: Optional[Tensor], now: int, n_img: int) -> None:
@@ -1075,27 +1143,34 @@ def _loop_setup(model: "CFGDenoiser", x: Tensor, sigmas, extra_args, guided: boo
         x_orig = noise = None
     tok = mm.patchify(x, dup=2 if cfg_on and guided else 1)
     return _Loop(pipe, mm, sigmas, cfg_weight, cfg_on, n_img, policy, x, mask, x_orig, noise, tok, torch.empty_like(tok), conditioning, pooled, timesteps,
-                 reference, condition)
+                 reference, condition, extra_args.get("skip_layer_guidance"))
 
 
-def _set_rows(model: "CFGDenoiser", lp: _Loop, guided: bool):
-    """A guidance interval begins or ends: the engine re-prepared for both CFG rows of every image or for the prompt rows alone, its modulation table
-    and context cached again for those rows, x patchified with the matching ``dup`` -> (tok, out)."""
-    now = lp.n_img * (2 if guided else 1)
+def _set_rows(model: "CFGDenoiser", lp: _Loop, guided: bool, fork: bool = False):
+    """The number of row groups changes -- a guidance interval or the window of skip-layer guidance begins or ends: the engine re-prepared for one
+    group (the prompt rows alone), two (both CFG rows of every image) or, with ``fork``, three ([prompt x n | negative x n | skip x n], the third a forked
+    copy of the first: ``MMDiTEngine.set_skip_layers(layers, n_img)``), its modulation table and context cached again for those rows -- the fork rows
+    repeat the prompt's pooled rows; their context and token rows are never read -- and x patchified with the matching ``dup`` -> (tok, out)."""
+    live = lp.n_img * (2 if guided else 1)
+    now = live + (lp.n_img if fork else 0)
+    rows = (lambda t: torch.cat([t[:live], t[:lp.n_img]], 0)) if fork else (lambda t: t[:live])
     _prepare_rows(lp.mm, now, lp.x.shape[1:3], lp.conditioning.shape[1], len(lp.timesteps), lp.reference)
     _cache_reference(lp.mm, lp.reference, now, lp.n_img)
     _cache_condition(lp.mm, lp.condition, now, lp.n_img)
-    model.cache_modulation_params(lp.pooled[:now].contiguous(), lp.timesteps)
-    lp.mm.cache_context(lp.conditioning[:now].contiguous())
-    tok = lp.mm.patchify(lp.x, dup=2 if guided else 1)
+    model.cache_modulation_params(rows(lp.pooled).contiguous(), lp.timesteps)
+    lp.mm.cache_context(rows(lp.conditioning).contiguous())
+    if lp.slg is not None:  # (without the option the engine is never told: its calls are what they were)
+        lp.mm.set_skip_layers(lp.slg["layers"] if fork else None, lp.n_img if fork else 0)
+    tok = lp.mm.patchify(lp.x, dup=now // lp.n_img)
     return tok, torch.empty_like(tok)
 
 
-def _step_loop(model: "CFGDenoiser", lp: _Loop, plan, grows, guide=None, euler: bool = False):
+def _step_loop(model: "CFGDenoiser", lp: _Loop, plan, grows, guide=None, euler: bool = False, srows=None):
     """The host loop behind ``sample_euler`` and ``sample_steps``: per (row, guidance row) one model evaluation -- the engine's head, the policy's
     decision and the chosen tail under the first-block cache -- and one launch of the update, with one device synchronisation per step (the
     reference's mx.eval(x)), which provides iter_time.  ``euler``: the rows are the schedule's Euler rows and the update is dk_euler_cfg_step, the
-    reference's statement, instead of the coefficient-row entry.  The operators are looked up on ``ops`` at every call."""
+    reference's statement, instead of the coefficient-row entry.  ``srows`` (``sampler.slg_rows``; None: no row): the evaluations that carry the forked
+    third row group and end in dk_slg_cfg_step.  The operators are looked up on ``ops`` at every call."""
     from . import ops
     from .sampler import block_cache_rel
     pipe, mm, _, cfg_weight, cfg_on, n_img, policy, x, mask, x_orig, noise, tok, out = lp[:13]
@@ -1115,11 +1190,13 @@ def _step_loop(model: "CFGDenoiser", lp: _Loop, plan, grows, guide=None, euler: 
     step, t0 = 0, None
     on = cfg_on and (grows[0].guided if grows else True)  # whether the engine holds both CFG rows of every image
     fresh = False  # the engine was re-prepared: the first-block cache holds nothing to reuse
-    for r, g in zip(plan, grows):
+    fork = False  # whether it holds the forked third row group of skip-layer guidance
+    srows = [False] * len(plan) if srows is None else srows
+    for r, g, sl in zip(plan, grows, srows):
         t0 = time.perf_counter() if t0 is None else t0
-        if cfg_on and g.guided != on:
-            on = g.guided
-            tok, out = _set_rows(model, lp, on)
+        if cfg_on and (g.guided != on or sl != fork):
+            on, fork = g.guided, sl
+            tok, out = _set_rows(model, lp, on, fork) if lp.slg is not None else _set_rows(model, lp, on)
             if policy is not None:
                 mm.reset_block_cache()
                 fresh = True
@@ -1135,7 +1212,11 @@ def _step_loop(model: "CFGDenoiser", lp: _Loop, plan, grows, guide=None, euler: 
         args = (x, out, tok, n_img, on, pcfg.patch_size, int(pcfg.patchify_via_reshape), r.sigma, r.sigma_next, cfg_weight)
         if not euler:
             args += (hist, (r.cx, r.cd, r.ch, r.hx, r.hd), r.reads_h, r.writes_h)
-        if on and mode != "cfg":
+        if fork:
+            ops.slg_cfg_step(*args, slg_scale=lp.slg["scale"], mode=mode, workspace=gws, **({} if guide is None else dict(
+                rescale=guide["guidance_rescale"], eta=guide["apg_eta"], norm_threshold=guide["apg_norm_threshold"])), momentum=beta,
+                reads_m=mbuf is not None and not g.first, writes_m=mbuf is not None and g.feeds, m=mbuf, **dict(zip(("x_orig", "noise", "mask"), blend)))
+        elif on and mode != "cfg":
             ops.guided_cfg_step(*args, mode=mode, workspace=gws, rescale=guide["guidance_rescale"], eta=guide["apg_eta"],
                                 norm_threshold=guide["apg_norm_threshold"], momentum=beta, reads_m=mbuf is not None and not g.first,
                                 writes_m=mbuf is not None and g.feeds, m=mbuf, **dict(zip(("x_orig", "noise", "mask"), blend)))
@@ -1150,6 +1231,8 @@ def _step_loop(model: "CFGDenoiser", lp: _Loop, plan, grows, guide=None, euler: 
     if guide is not None:
         n_g = sum(g.guided for g in grows)
         model.guidance_record = dict(guide, guided_evals=n_g, unguided_evals=len(grows) - n_g)
+    if lp.slg is not None:
+        model.skip_layer_record = dict(lp.slg, evals=sum(bool(v) for v in srows))
     model.clear_cache()
     return x, iter_time
 
@@ -1182,15 +1265,28 @@ def sample_steps(model: CFGDenoiser, x: Tensor, sigmas, plan, extra_args=None):
     on the prompt rows alone: where the guidedness changes, ``_set_rows`` re-prepares the engine, the first-block cache (if on) is reset and that
     evaluation computes whatever the policy says, and the update is dk_lms_cfg_step with cfg_on = 0 on the first n_img token rows.  APG's momentum
     buffer is allocated here and never initialised: the first guided evaluation of a stretch does not read it.  What ran goes to
-    ``model.guidance_record``."""
+    ``model.guidance_record``.
+    Skip-layer guidance: ``extra_args["skip_layer_guidance"]`` ({"scale", "layers", "interval"}, ``_skip_layer_options``) gives the evaluations of
+    ``sampler.slg_rows`` a third row group, forked inside the engine, and dk_slg_cfg_step as their update; ``_set_rows`` re-prepares the engine where the
+    window begins and ends, and the engine's skip layers are off again when the loop returns or raises.  What ran goes to ``model.skip_layer_record``."""
     plan = list(plan)
     guide = None if extra_args is None else extra_args.get("guidance")
+    slg = None if extra_args is None else extra_args.get("skip_layer_guidance")
     grows = guidance_rows(plan, None if guide is None else guide["interval"])
     lp = _loop_setup(model, x, sigmas, extra_args, guided=grows[0].guided if grows else True)
     if guide is not None and not lp.cfg_on:
         raise ValueError("extra_args['guidance'] needs classifier-free guidance (cfg_weight > 0)")
+    if slg is not None and not lp.cfg_on:
+        raise ValueError("extra_args['skip_layer_guidance'] needs classifier-free guidance (cfg_weight > 0)")
+    if slg is not None and lp.policy is not None:
+        raise ValueError("skip-layer guidance cannot run together with block_cache: there is no cache policy for a forked row group yet")
     if lp.policy is not None and not all(r.ends_step for r in plan):
         raise ValueError(_HEUN_BLOCK_CACHE)
     if any(not 0 <= r.index < len(lp.sigmas) - 1 for r in plan):
         raise ValueError("the plan evaluates the model outside the schedule (or at its last entry): build it with sampler.step_plan on these sigmas")
-    return _step_loop(model, lp, plan, grows, guide)
+    if slg is None:
+        return _step_loop(model, lp, plan, grows, guide)
+    try:
+        return _step_loop(model, lp, plan, grows, guide, srows=slg_rows(plan, grows, *slg["interval"]))
+    finally:
+        lp.mm.set_skip_layers(None, 0)

@@ -230,6 +230,53 @@ def guidance_rows(plan, interval=None) -> List[GuidedRow]:
     return [GuidedRow(g[k], g[k] and (k == 0 or not g[k - 1]), g[k] and k + 1 < len(g) and g[k + 1]) for k in range(len(g))]
 
 
+# ---- skip-layer guidance: a third evaluation with blocks skipped, and the steps that take its term (no reference counterpart) ---------------
+def check_skip_layer_guidance(scale, layers, interval, depth):
+    """The options of skip-layer guidance -> (scale, layers, (start, stop)): a finite float; the sorted tuple of distinct block indices, at least
+    one, each in [0, depth); fractions of the schedule with 0 <= start <= stop <= 1 (None: (0, 1), every step but the first).  Anything else raises a
+    ValueError that names the rule."""
+    try:
+        scale = float(scale)
+    except (TypeError, ValueError):
+        raise ValueError(f"skip_layer_guidance must be a float (the scale), got {scale!r}") from None
+    if not math.isfinite(scale):
+        raise ValueError(f"skip_layer_guidance (the scale) must be finite, got {scale}")
+    if layers is None or isinstance(layers, (str, bytes)) or len(tuple(layers)) == 0:
+        raise ValueError("skip_layers must name at least one block")
+    raw = tuple(layers)
+    if any(isinstance(b, bool) or int(b) != b for b in raw):
+        raise ValueError(f"skip_layers must be block indices (integers), got {raw}")
+    out = tuple(sorted(int(b) for b in raw))
+    if len(set(out)) != len(out):
+        raise ValueError(f"skip_layers names a block twice: {raw}")
+    if out[0] < 0 or out[-1] >= int(depth):
+        raise ValueError(f"skip_layers {raw}: every block must lie in [0, {int(depth)}), the model's double blocks")
+    start, stop = (0.0, 1.0) if interval is None else (float(v) for v in interval)
+    if not 0.0 <= start <= stop <= 1.0:
+        raise ValueError(f"skip_layer_interval must be (start, stop) with 0 <= start <= stop <= 1, got ({start}, {stop})")
+    return scale, out, (start, stop)
+
+
+def slg_rows(plan, guided_rows, start, stop) -> List[bool]:
+    """One bool per row of a ``step_plan``: whether its evaluation takes the skip-layer term.  Step i (0-based) of the plan's n steps takes it iff
+    n start < i < n stop, strict on both sides (diffusers' rule for skip_layer_guidance_start / _stop); the rows of a step -- Heun's predictor and
+    corrector -- share their step's decision, and a row that ``guided_rows`` (``guidance_rows`` of the same plan) leaves unguided takes no term."""
+    n = sum(bool(r.ends_step) for r in plan)
+    out, i = [], 0
+    for r, g in zip(plan, guided_rows):
+        out.append(bool(g.guided and n * float(start) < i < n * float(stop)))
+        i += bool(r.ends_step)
+    return out
+
+
+def slg_reference(c, u, k, w, scale, mode="cfg", **kw):
+    """``guide_reference`` with the skip-layer term, float64 numpy: ``k`` is the x0 prediction of the prompt rows evaluated with blocks skipped;
+    den = G(c, u) + scale (c - k), G the mode's combination.  Returns (den, m') like ``guide_reference``, whose keywords ``kw`` are."""
+    den, m_new = guide_reference(c, u, w, mode, **kw)
+    c, k = np.asarray(c, dtype=np.float64), np.asarray(k, dtype=np.float64)
+    return den + float(scale) * (c - k), m_new
+
+
 # ---- first-block cache: which steps compute and which reuse (host policy; no reference counterpart) -------------------------
 def block_cache_rel(probe) -> float:
     """``probe``: (num, den) per batch row as ``MMDiTEngine.forward_head`` returns them, on the host -> the relative change of block 0's

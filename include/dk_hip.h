@@ -469,6 +469,30 @@ int dk_guided_cfg_step_f16(float* x, const void* model_out, int32_t ld_out, void
                            float phi, float eta, float r, float beta, int32_t reads_m, int32_t writes_m, float* m, void* workspace,
                            size_t workspace_bytes, void* stream);
 
+/* Skip-layer guidance (no reference counterpart; the sampling recipe published with Stable Diffusion 3.5 medium: diffusers'
+ * noise_pred += scale * (noise_pred_text - noise_pred_skip_layers), Stability's SkipLayerCFGDenoiser, restated on x0 predictions):
+ * dk_guided_cfg_step on THREE row groups.  model_out is [3 * n_img, S_i, ld_out]: rows [2 n_img, 3 n_img) are the evaluation of the prompt
+ * rows with blocks skipped (dk_mmdit_set_skip_layers).  With k = xb - o_skip * sigma formed like c and u (fp32) and G the mode's
+ * combination of c and u exactly as above,
+ *   den = G(c, u) + slg_scale * (c - k).
+ * Everything else is dk_guided_cfg_step's, argument for argument: the moments launches of modes 1 and 2 read rows [0, 2 n_img), the
+ * coefficient row, hist, the blend.  tokens are written in the two live copies [0, 2 n_img) only: the engine never reads the third.
+ * slg_scale == 0 is accepted and gives dk_guided_cfg_step's bits in every mode for finite predictions (the term is an exact zero).
+ * Refused with a dk_last_error() text, nothing written: cfg_on == 0, a non-finite slg_scale, and whatever dk_guided_cfg_step refuses.
+ * Verified as arithmetic only, on synthetic weights: no SD3.5-medium checkpoint has been run here.  _f16: model_out and tokens are fp16. */
+int dk_slg_cfg_step(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on, int32_t Hl, int32_t Wl,
+                    int32_t C, int32_t p, int32_t reshape_order, float sigma, float cfg_weight, float* hist, float cx, float cd,
+                    float ch, float hx, float hd, float sigma_next, int32_t reads_h, int32_t writes_h, const float* x_orig,
+                    const float* noise, const float* mask, int32_t mask_per_image, int32_t mode, float phi, float eta, float r,
+                    float beta, int32_t reads_m, int32_t writes_m, float* m, void* workspace, size_t workspace_bytes, float slg_scale,
+                    void* stream);
+int dk_slg_cfg_step_f16(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on, int32_t Hl,
+                        int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma, float cfg_weight, float* hist, float cx,
+                        float cd, float ch, float hx, float hd, float sigma_next, int32_t reads_h, int32_t writes_h,
+                        const float* x_orig, const float* noise, const float* mask, int32_t mask_per_image, int32_t mode, float phi,
+                        float eta, float r, float beta, int32_t reads_m, int32_t writes_m, float* m, void* workspace,
+                        size_t workspace_bytes, float slg_scale, void* stream);
+
 /* Inpainting mask, pixels -> latent cells: mask u8 [n_mask,H,W] (255 = repaint, 0 = keep) -> f32 [n_mask,H/f,W/f],
  * (integer sum of the f x f block) / (f * f * 255) by a true division: an all-0 block gives 0.0f, an all-255 block 1.0f.
  * H and W must be multiples of f (the pipeline passes the VAE's factor, 8). */
@@ -753,6 +777,24 @@ int dk_mmdit_cache_condition(dk_mmdit* m, const void* cond_tokens, int32_t per_i
  * error that names the rule: n_blocks outside [0, depth_multimodal], a configuration with depth_unified > 0 or fp8_linears, an engine
  * whose weights are resolved. */
 int dk_mmdit_set_dual_attention(dk_mmdit* m, int32_t n_blocks);
+
+/* ---- Skip layers: a forked row group that sits out some double blocks (opt-in; skip-layer guidance, see dk_slg_cfg_step) ----------------
+ * With B prepared batch rows, live = B - fork_rows and f = min(blocks), dk_mmdit_forward runs
+ *   the embedders and the blocks g < f     on rows [0, live): rows >= live of tokens_in, of text and of the cached context are never read;
+ *   the fork, in front of block f          X[live + j] = X[j] for j < fork_rows, text and image rows, one device copy in stream order;
+ *   the blocks of the set                  on rows [0, live);
+ *   every other block >= f, the final layer on all B rows;   tokens_out is [B, S_i, F].
+ * "On rows [0, live)" is the launch sequence of a batch of `live` on the same buffers.  The modulation table is cached for B rows as
+ * ever: the caller repeats the pooled rows of rows [0, fork_rows) for the fork rows.  So the fork rows are the evaluation of rows
+ * [0, fork_rows) by a model that passes both streams unchanged through the blocks of the set, at the cost of the blocks they run.
+ * May be called at any time after dk_mmdit_create and takes effect at the next forward; workspace size and carve do not change.
+ * (NULL, 0, 0) is off, the default: every launch and every bit is then what it is without the feature.
+ * Refused, with no state changed and an error that names the rule: exactly one of n_blocks and fork_rows zero (or either negative), a
+ * block outside [0, depth_multimodal) or named twice, depth_unified > 0, fp8_linears, a reference grid or a condition width that is set.
+ * Refused at the call, never launched: a forward with 2 * fork_rows > B, and dk_mmdit_forward_head, dk_mmdit_forward_tail and
+ * dk_mmdit_run_blocks while skip layers are set.  Both element types.
+ * Verified against an fp32 / emulating oracle with synthetic weights (arithmetic parity); no SD3.5-medium checkpoint has been run. */
+int dk_mmdit_set_skip_layers(dk_mmdit* m, const int32_t* blocks, int32_t n_blocks, int32_t fork_rows);
 /* Head of step `step_index`: dk_mmdit_forward's embedder launches, block 0 and the probe.  probe_out: device float [batch][2] =
  * (num, den) per batch row; before any computed step den is 0 (and num = sum |D_cur|).  Records a pending head for step_index. */
 int dk_mmdit_forward_head(dk_mmdit* m, const void* tokens_in, const void* text, int32_t step_index, float* probe_out, void* stream);
