@@ -157,6 +157,10 @@ SIGNATURES = {
                                  _vp]),
     "dk_attention_desc_bf16": (_i32, [C.POINTER(dk_attention_desc), _vp]),
     "dk_attention_plan": (_i32, [C.POINTER(dk_attention_desc), _sz, C.POINTER(dk_attention_plan_t)]),
+    # identity attention (perturbed-attention guidance): the descriptor, ident_from, then the stream -- or f16 and the plan
+    "dk_attention_identity_bf16": (_i32, [C.POINTER(dk_attention_desc), _i32, _vp]),
+    "dk_attention_identity_f16": (_i32, [C.POINTER(dk_attention_desc), _i32, _vp]),
+    "dk_attention_identity_plan": (_i32, [C.POINTER(dk_attention_desc), _i32, _i32, C.POINTER(dk_attention_plan_t)]),
     "dk_gemm_workspace_bytes": (C.c_size_t, []),
     "dk_attention_workspace_bytes": (C.c_size_t, []),
     "dk_attention_set_workspace": (C.c_int, [C.c_void_p, C.c_size_t]),
@@ -237,6 +241,8 @@ SIGNATURES = {
     "dk_mmdit_set_dual_attention": (_i32, [_vp, _i32]),
     # skip-layer guidance: the engine's forked row group (the step entry is dk_slg_cfg_step above)
     "dk_mmdit_set_skip_layers": (_i32, [_vp, C.POINTER(_i32), _i32, _i32]),
+    # perturbed-attention guidance: the same fork with identity attention in the blocks named
+    "dk_mmdit_set_perturbed_attention": (_i32, [_vp, C.POINTER(_i32), _i32, _i32]),
     **{"dk_ln_modulate_dual_" + el: (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
                                             _i32, _f32, _vp]) for el in ("bf16", "f16")},
     "dk_image_mask_out_f32": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),

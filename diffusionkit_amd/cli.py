@@ -103,6 +103,13 @@ def build_parser(model_versions: Sequence[str]) -> argparse.ArgumentParser:
     p.add_argument("--slg-interval", type=float, nargs=2, default=None, metavar=("START", "STOP"),
                    help="With --slg-scale: step i of n takes the term iff n START < i < n STOP (default: the model version's published 0.01 0.2, "
                         "else 0 1).")
+    p.add_argument("--pag-scale", type=float, default=None, metavar="S",
+                   help="Perturbed-attention guidance (SD3 versions with --cfg > 0): add S times (prompt prediction - prediction with the attention "
+                        "of --pag-layers perturbed: image queries see the text and themselves only). Needs --pag-layers. Not together with "
+                        "--slg-scale or --block-cache. Verified as arithmetic only: no checkpoint has been run here.")
+    p.add_argument("--pag-layers", type=int, nargs="+", default=None, metavar="BLOCK", help="With --pag-scale: the double blocks whose attention is perturbed.")
+    p.add_argument("--pag-interval", type=float, nargs=2, default=None, metavar=("START", "STOP"),
+                   help="With --pag-scale: step i of n takes the term iff n START < i < n STOP (default: every guided step).")
     p.add_argument("--local-ckpt", default=None, type=str, help="Path to the local mmdit checkpoint.")
     p.add_argument("--ckpt", action="append", default=[], metavar="KEY=PATH",
                    help="Further local checkpoint parts (vae_decoder, vae_encoder, clip_l, clip_g, t5, t5_tokenizer, "
@@ -204,10 +211,19 @@ def resolve(args) -> dict:
         opts = _skip_layer_options(scale, layers, window, args.model_version, r.get("mmdit_config", MODEL_CONFIG[args.model_version]),
                                    "FLUX" in args.model_version, cfg, r.get("block_cache"))
         r.update(skip_layer_guidance=opts["scale"], skip_layers=opts["layers"], skip_layer_interval=opts["interval"])
+    pag = tuple(getattr(args, k, None) for k in ("pag_scale", "pag_layers", "pag_interval"))
+    if any(v is not None for v in pag):  # (keys only when the flags are given)
+        from .config import MODEL_CONFIG
+        from .pipeline import _perturbed_attention_options
+        mcfg = r.get("mmdit_config", MODEL_CONFIG[args.model_version])
+        opts = _perturbed_attention_options(*pag, mcfg, "FLUX" in args.model_version, cfg, r.get("block_cache"), r.get("reference_image_path"),
+                                            r.get("condition"), r.get("skip_layer_guidance"))
+        r.update(pag_scale=opts["scale"], pag_layers=opts["layers"], pag_interval=opts["interval"])
     return r
 
 
 SKIP_LAYER_KEYS = ("skip_layer_guidance", "skip_layers", "skip_layer_interval")  # keywords of generate_image that ``resolve`` sets together
+PAG_KEYS = ("pag_scale", "pag_layers", "pag_interval")  # the same, perturbed-attention guidance
 # argparse destination -> keyword of generate_image
 GUIDANCE_FLAGS = {"guidance": "guidance", "guidance_rescale": "guidance_rescale", "apg_eta": "apg_eta", "apg_norm_threshold": "apg_norm_threshold",
                   "apg_momentum": "apg_momentum", "guidance_interval": "guidance_interval"}
@@ -247,7 +263,7 @@ def main(argv: Optional[Sequence[str]] = None, pipeline_overrides: Optional[dict
                                    negative_text=args.negative_prompt, latent_size=latent_size, image_path=args.image_path,
                                    denoise=args.denoise, verbose=args.verbose, mask_path=r.get("mask_path"),
                                    composite=r.get("composite", True), block_cache=r.get("block_cache"), sampler=r.get("sampler"),
-                                   **{key: r[key] for key in (*GUIDANCE_FLAGS.values(), "reference_image_path", *SKIP_LAYER_KEYS) if key in r},
+                                   **{key: r[key] for key in (*GUIDANCE_FLAGS.values(), "reference_image_path", *SKIP_LAYER_KEYS, *PAG_KEYS) if key in r},
                                    **cond_kw)
     if log["text_encoding"].get("synthetic"):
         logger.warning("no text-encoder checkpoints were named (--ckpt clip_l=... t5=...): the conditioning is synthetic")

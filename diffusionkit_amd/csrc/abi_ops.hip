@@ -208,6 +208,28 @@ extern "C" int dk_attention_plan(const dk_attention_desc* d, size_t workspace_by
 extern "C" int dk_attention_plan_f16(const dk_attention_desc* d, size_t workspace_bytes, dk_attention_plan_t* plan) {
   return attention_plan(DK_DTYPE_F16, d, workspace_bytes, plan);
 }
+// identity attention (include/dk_hip.h): the descriptor's launch with AttnParams::ident_from set; every check is dk_attention_route's
+static int attention_identity(int dtype, const dk_attention_desc* d, int32_t ident_from, void* stream, dk_attention_plan_t* plan) {
+  AttnParams p;
+  if (const int rc = attn_params_from_desc(dtype, d, p)) return rc;
+  DK_REQUIRE(ident_from != 0, "identity attention: 1 <= ident_from < S");  // (0 is the plain launch's value of the field)
+  p.ident_from = ident_from;
+  if (plan == nullptr) return dk_launch_attention(p, g_attn_ws, S_(stream));
+  AttnRoute r;
+  if (const int rc = dk_attention_route(p, 0, dk_device_cu_count(), r)) return rc;
+  *plan = dk_attention_plan_t{r.kernel, r.qfuse, r.blocks, r.whole, r.split, r.jobs, r.jobs > 0, r.quantize, r.launches, r.n_cu, 0};
+  return 0;
+}
+extern "C" int dk_attention_identity_bf16(const dk_attention_desc* d, int32_t ident_from, void* stream) {
+  return attention_identity(DK_DTYPE_BF16, d, ident_from, stream, nullptr);
+}
+extern "C" int dk_attention_identity_f16(const dk_attention_desc* d, int32_t ident_from, void* stream) {
+  return attention_identity(DK_DTYPE_F16, d, ident_from, stream, nullptr);
+}
+extern "C" int dk_attention_identity_plan(const dk_attention_desc* d, int32_t ident_from, int32_t f16, dk_attention_plan_t* plan) {
+  DK_REQUIRE(plan != nullptr, "null plan");
+  return attention_identity(f16 ? DK_DTYPE_F16 : DK_DTYPE_BF16, d, ident_from, nullptr, plan);
+}
 extern "C" int32_t dk_attention_d512_tp(int32_t T) { return (int32_t)align_up((size_t)(T > 0 ? T : 0), 64); }
 int attention_d512(int dtype, const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int B, int T, int ld, int ldo, float scale,
                    bf16_t* vt, hipStream_t st) {  // (dk_engine.h)

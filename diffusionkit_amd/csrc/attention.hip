@@ -27,6 +27,12 @@ int dk_attention_route(const AttnParams& p, size_t ws_bytes, int n_cu, AttnRoute
   DK_REQUIRE(p.S > 0 && p.B > 0 && p.H > 0, "empty attention");
   DK_REQUIRE(p.ld % 8 == 0 && p.ldo % 4 == 0, "row strides must keep 16-byte alignment");
   DK_REQUIRE(n_cu > 0, "compute unit count");
+  if (p.ident_from != 0) {  // identity attention (AttnParams::ident_from): attention2.hip's IDENT case, bf16 and fp16
+    DK_REQUIRE(p.D == 64, "identity attention: head_dim must be 64");
+    DK_REQUIRE(p.bias == nullptr, "identity attention: no score bias");
+    DK_REQUIRE(p.O8 == nullptr, "identity attention: no MX-fp8 copy of the output");
+    DK_REQUIRE(p.ident_from >= 1 && p.ident_from < p.S, "identity attention: 1 <= ident_from < S");
+  }
   // automatic choice (kernel lab, profiles/archive/r01_attention_lab.md, r02_attn_bench.log, r03_attention_phase_alternating.md): D = 128 on
   // long sequences: the phase-alternating kernel; otherwise the VALU-lean kernel with 4 waves (D = 64: 842 TF against 773 / 823 for the
   // pipelined forms).  A score bias (text encoders) is only implemented by the lean kernel
@@ -40,6 +46,7 @@ int dk_attention_route(const AttnParams& p, size_t ws_bytes, int n_cu, AttnRoute
     DK_REQUIRE(p.dtype == DK_DTYPE_F16 && p.D == 64 && p.bias == nullptr && p.O8 == nullptr, "fp16 attention: head_dim 64, no score bias, no MX-fp8 copy");
     mode = 4;
   }
+  if (p.ident_from != 0) mode = 4;  // identity attention: the lean kernel's template case, whatever the "attn" knob says
   if (mode == 10 && !dk_attention5_eligible(p)) mode = 9;
   if (p.O8 != nullptr && p.o8_split != 0) {
     DK_REQUIRE(p.o8_split > 0 && p.o8_split < p.S && p.o8_txt_row0 >= p.B * (p.S - p.o8_split), "MX-fp8 copy: text rows behind the image rows");
@@ -85,7 +92,16 @@ int dk_launch_attention(const AttnParams& p_in, AttnWs ws, hipStream_t stream) {
   if (const int rc = dk_attention_route(p_in, ws.p != nullptr ? ws.bytes : 0, dk_device_cu_count(), r)) return rc;
   AttnParams p = p_in;
   if (p.bal_ws == nullptr) p.bal_ws = ws.p;
-  dk_prof_begin(2, 4.0 * (double)p.B * p.H * (double)p.S * (double)p.S * p.D, stream);
+  double work = 4.0 * (double)p.B * p.H * (double)p.S * (double)p.S * p.D;
+  if (p.ident_from != 0) {  // the tiles the query blocks walk (dk_ident_walk): 128 queries x 64 keys each
+    long tiles = 0;
+    for (int q0 = 0; q0 < p.S; q0 += 128) {
+      const IdentWalk w = dk_ident_walk(q0, p.S, p.ident_from);
+      tiles += w.n_lo + w.n_hi;
+    }
+    work = 4.0 * (double)p.B * p.H * (double)tiles * 128.0 * 64.0 * p.D;
+  }
+  dk_prof_begin(2, work, stream);
   const int rc = r.kernel == 10 ? dk_launch_attention5(p, r, ws.p, stream) : r.kernel == 9 ? dk_launch_attention4(p, stream) : dk_launch_attention2(p, 4, stream);
   dk_prof_end(stream);
   if (rc) return rc;

@@ -16,6 +16,27 @@
 //     e^THR instead of 1, which fp32 accumulation and bf16 P tolerate (guide T13; the safe order is
 //     kept: the decision precedes the exponentials of the tile it covers, nothing else is pending);
 //   * the two 32-key score chains of a tile are interleaved (two independent accumulators).
+//
+// IDENT (identity attention, AttnParams::ident_from = F; D = 64; perturbed-attention guidance): a query s >= F sees the keys [0, F) and its
+// own key only.  A template case of the same kernel: with IDENT false every addition below folds away.  A query block that lies wholly in the
+// image range walks the ceil(F / 64) text tiles and then the (at most two) tiles of its own 128 rows (dk_ident_walk); a block with a text
+// query walks every tile, so its text rows take the plain kernel's tiles in the plain kernel's order.  The element mask
+// `query < F || key < F || key == query` is a select to -1e30 in front of the running maximum, in the tiles that hold a key >= F, for the
+// waves that hold an image query; tiles wholly below F and waves wholly of text take the unmasked body.  The hazards:
+//   * a fully masked tile.  A wave whose 32 queries see no key of a tile (wave-uniform: no text query, no text key, not the wave's own rows)
+//     skips the tile's arithmetic, so (m, l, O) are untouched.  Inside a wave that does run, a lane may still find all its keys masked; its
+//     scores are the finite -1e30, never -inf.  Every walk starts at tile 0, which holds key 0 < F, so every query's maximum is finite
+//     before it meets a masked tile: mloc - m_run is then about -1e30, the lane never votes for the rescale, and its probabilities are
+//     exp2(-1e30 c - m c) = 0 exactly -- l and O gain exact zeros.  No exp(-inf - (-inf)) can form;
+//   * barriers.  The tile list, the loads, the LDS stores and the barriers depend on the query block alone (scalars): workgroup-uniform.
+//     Only the arithmetic between them is skipped per wave;
+//   * the ragged last key tile.  load_tile clamps the rows of whatever tile it is given exactly as before, and the tail mask `key >= S`
+//     still follows the identity mask (a lane whose query lies beyond S must not unmask the key of the same index);
+//   * the fused Q load (QFUSE) is in front of the tile loop and unchanged: it composes with IDENT as a second template flag.
+//   * the launch's critical path.  A block with a text query is as long as a plain one: those blocks take the first workgroup ids.
+// In the one wave that straddles F the text lanes share the deferred-rescale vote with image lanes whose maxima differ from the plain
+// kernel's, so those (at most 31) text rows may rescale at other tiles than the plain launch does: equal to rounding, not bit for bit.
+// Text rows of waves wholly below F are the plain kernel's bits.
 #include "dk_kernels.h"
 
 #define DK_RESCALE_THR 4.0f  // natural-log units of the scaled scores
@@ -39,7 +60,7 @@ __device__ __forceinline__ int k2_swz(int r) { return D == 128 ? (r & 15) : ((r 
 
 typedef __attribute__((address_space(3))) char lds_char;
 
-template <int D, int NW, bool HAS_BIAS = false, bool QFUSE = false>
+template <int D, int NW, bool HAS_BIAS = false, bool QFUSE = false, bool IDENT = false>
 __global__ __launch_bounds__(NW * 64, 2) void dk_attn2_fwd_kernel(AttnParams p) {
   using C = Attn2Cfg<D, NW>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -63,7 +84,16 @@ __global__ __launch_bounds__(NW * 64, 2) void dk_attn2_fwd_kernel(AttnParams p) 
     const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
     t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
   }
-  const int qb = t % nq, head = (t / nq) % p.H, b = t / (nq * p.H);
+  int qb = t % nq, head = (t / nq) % p.H, b = t / (nq * p.H);
+  if (IDENT) {
+    // The query blocks that hold a text query walk every tile, the others five or so: the long ones are the launch's critical path, so they take
+    // the first workgroup ids (dispatched first, in plain blockIdx order: round-robin over the XCDs) and the short ones fill in behind them
+    const int n_long = min((p.ident_from + C::QB - 1) / C::QB, nq), bid = blockIdx.x, first = n_long * p.H * p.B;
+    int bh;
+    if (bid < first) qb = bid % n_long, bh = bid / n_long;
+    else qb = n_long + (bid - first) % (nq - n_long), bh = (bid - first) / (nq - n_long);
+    head = bh % p.H, b = bh / p.H;
+  }
   const int q0 = qb * C::QB + wave * 32;
 
   const bf16_t* Qb = p.Q + (size_t)b * S * p.ld + head * D;
@@ -154,6 +184,19 @@ __global__ __launch_bounds__(NW * 64, 2) void dk_attn2_fwd_kernel(AttnParams p) 
 
   u32x4 kreg[C::NCH], vreg[C::NCH];
   const int ntiles = (S + 63) / 64;
+  // IDENT: the tiles this workgroup walks (dk_ident_walk, dk_kernels.h), chosen per query block from scalars alone; step i of nsteps is tile
+  // tile_of(i).  Otherwise step i is tile i of ntiles
+  const int F = IDENT ? p.ident_from : 0;
+  const IdentWalk walk = IDENT ? dk_ident_walk(qb * C::QB, S, F) : IdentWalk{ntiles, ntiles, 0};
+  const int nsteps = IDENT ? walk.n_lo + walk.n_hi : ntiles;
+  const int n_lo = walk.n_lo, hi_d = walk.hi0 - walk.n_lo;
+  auto tile_of = [&](int i) { return IDENT && i >= n_lo ? i + hi_d : i; };
+  // (IDENT) per wave, in tiles: the wave computes the tiles below n_act (all of them when it holds a text query, else those with a text key)
+  // and tile j_own, which holds its 32 rows; it masks from tile f_mask on (never, when it holds no image query).  Per lane: the query,
+  // unclamped (a lane beyond S owns no key), and the first key index it does not see unless it is its own (a text query sees all)
+  const int n_act = q0 < F ? 0x7fffffff : (F + 63) / 64, j_own = q0 >> 6;
+  const int f_mask = q0 + 32 > F ? F / 64 : 0x7fffffff;
+  const int qself = q0 + l31, qlim = qself < F ? 0x7fffffff : F;
   auto load_tile = [&](int j) {
     const char* kb = Kb + (size_t)j * 64 * row_bytes;
     const char* vb = Vb + (size_t)j * 64 * row_bytes;
@@ -193,14 +236,17 @@ __global__ __launch_bounds__(NW * 64, 2) void dk_attn2_fwd_kernel(AttnParams p) 
   const float inv_scale = 1.0f / p.scale;
   const bf16_t* bias_row = HAS_BIAS ? p.bias + (size_t)head * p.bias_head_stride + (size_t)min(q0 + l31, S - 1) * p.ldb : nullptr;
 
-  load_tile(0);
+  load_tile(0);  // (IDENT: tile 0 holds key 0 < F, so it is the first tile of every walk)
   DK2_STORE_TILE(0)
   __syncthreads();
 
-#define DK2_TILE(BUF, J)                                                                                   \
+#define DK2_TILE(BUF, I)                                                                                   \
   do {                                                                                                     \
-    const int j_ = (J);                                                                                    \
-    if (j_ + 1 < ntiles) load_tile(j_ + 1);                                                                \
+    const int i_ = (I), j_ = tile_of(i_);                                                                  \
+    if (i_ + 1 < nsteps) load_tile(tile_of(i_ + 1));                                                       \
+    /* IDENT: a wave none of whose 32 queries sees a key of this tile -- no text query, no text key, not its own rows -- skips the tile's */ \
+    /* arithmetic: (m, l, O) stay as they are.  It still takes the loads, the stores and the barrier, which are the workgroup's */ \
+    if (!IDENT || j_ < n_act || j_ == j_own) {                                                             \
     f32x16 s0, s1;                                                                                         \
     _Pragma("unroll") for (int e = 0; e < 16; ++e) { s0[e] = 0.f; s1[e] = 0.f; }                           \
     __builtin_amdgcn_s_setprio(1);                                                                         \
@@ -211,6 +257,16 @@ __global__ __launch_bounds__(NW * 64, 2) void dk_attn2_fwd_kernel(AttnParams p) 
       s1 = mfma_32x32x16(k1, qf[kk], s1);                               \
     }                                                                                                      \
     __builtin_amdgcn_s_setprio(0);                                                                         \
+    if (IDENT && j_ >= f_mask) { /* a tile with keys >= F, a wave with image queries */                    \
+      asm volatile("; identity mask" ::: "memory");                                                        \
+      _Pragma("unroll") for (int e = 0; e < 16; ++e) {                                                     \
+        const int key = j_ * 64 + (e & 3) + 8 * (e >> 2) + 4 * hi;                                         \
+        if (!(key < qlim || key == qself)) s0[e] = -1e30f;                                                 \
+        if (!(key + 32 < qlim || key + 32 == qself)) s1[e] = -1e30f;                                       \
+        /* (every compare leaves a lane mask in a scalar pair: keep the scheduler from gathering all 64 in front of the selects) */ \
+        if ((e & 3) == 3) __builtin_amdgcn_sched_barrier(0);                                               \
+      }                                                                                                    \
+    }                                                                                                      \
     if (!HAS_BIAS && j_ * 64 + 64 > S) {                                                                   \
       asm volatile("; tail tile" ::: "memory"); /* keeps hipcc from if-converting the mask into every tile */ \
       _Pragma("unroll") for (int e = 0; e < 16; ++e) {                                                     \
@@ -272,16 +328,17 @@ __global__ __launch_bounds__(NW * 64, 2) void dk_attn2_fwd_kernel(AttnParams p) 
       }                                                                                                    \
     }                                                                                                      \
     __builtin_amdgcn_s_setprio(0);                                                                         \
-    if (j_ + 1 < ntiles) { DK2_STORE_TILE((BUF) ^ 1) }                                                     \
+    }                                                                                                      \
+    if (i_ + 1 < nsteps) { DK2_STORE_TILE((BUF) ^ 1) }                                                     \
     __syncthreads();                                                                                       \
   } while (0)
 
   int j = 0;
-  for (; j + 1 < ntiles; j += 2) {
+  for (; j + 1 < nsteps; j += 2) {
     DK2_TILE(0, j);
     DK2_TILE(1, j + 1);
   }
-  if (j < ntiles) DK2_TILE(0, j);
+  if (j < nsteps) DK2_TILE(0, j);
 #undef DK2_TILE
 #undef DK2_STORE_TILE
 
@@ -303,17 +360,17 @@ __global__ __launch_bounds__(NW * 64, 2) void dk_attn2_fwd_kernel(AttnParams p) 
   }
 }
 
-template <int D, int NW, bool HAS_BIAS = false, bool QFUSE = false>
+template <int D, int NW, bool HAS_BIAS = false, bool QFUSE = false, bool IDENT = false>
 static int launch_attn2(const AttnParams& p, hipStream_t stream) {
   using C = Attn2Cfg<D, NW>;
   static DkDeviceOnce attr_once;
   if (attr_once.first()) {
-    DK_CHECK_HIP(hipFuncSetAttribute((const void*)dk_attn2_fwd_kernel<D, NW, HAS_BIAS, QFUSE>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    DK_CHECK_HIP(hipFuncSetAttribute((const void*)dk_attn2_fwd_kernel<D, NW, HAS_BIAS, QFUSE, IDENT>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      C::LDS_BYTES));
     attr_once.mark();
   }
   const int nq = (p.S + C::QB - 1) / C::QB;
-  hipLaunchKernelGGL((dk_attn2_fwd_kernel<D, NW, HAS_BIAS, QFUSE>), dim3(nq * p.H * p.B), dim3(C::NT), C::LDS_BYTES, stream, p);
+  hipLaunchKernelGGL((dk_attn2_fwd_kernel<D, NW, HAS_BIAS, QFUSE, IDENT>), dim3(nq * p.H * p.B), dim3(C::NT), C::LDS_BYTES, stream, p);
   return 0;
 }
 
@@ -333,6 +390,8 @@ int dk_launch_attention2_d128(const AttnParams& p, hipStream_t stream) {  // (ar
 // fp32 as before; P rounded to fp16 for the P.V MFMA: P <= e^DK_RESCALE_THR under the deferred rescale, far inside fp16's range)
 int dk_launch_attention2(const AttnParams& p, int waves, hipStream_t stream) {  // (arguments checked by dk_attention_route)
   DK_REQUIRE(p.D == 64 && p.bias == nullptr && p.O8 == nullptr && waves == 4, "attention2 (fp16): head_dim 64, no score bias, no MX-fp8 copy");
+  if (p.ident_from != 0)
+    return p.qn_a != nullptr || p.q_rope != nullptr ? launch_attn2<64, 4, false, true, true>(p, stream) : launch_attn2<64, 4, false, false, true>(p, stream);
   if (p.qn_a != nullptr || p.q_rope != nullptr) return launch_attn2<64, 4, false, true>(p, stream);
   return launch_attn2<64, 4>(p, stream);
 }
@@ -341,6 +400,10 @@ int dk_launch_attention2_d128(const AttnParams& p, hipStream_t stream);  // atte
 int dk_launch_attention2(const AttnParams& p, int waves, hipStream_t stream) {  // (arguments checked by dk_attention_route)
   if (p.dtype == DK_DTYPE_F16) return dk_f16::dk_launch_attention2(p, waves, stream);
   DK_REQUIRE(waves == 4, "attention2: 4 waves per workgroup (the 8- and 7-wave forms were pruned in round 3)");
+  if (p.ident_from != 0) {  // identity attention: D = 64, no score bias (dk_attention_route)
+    DK_REQUIRE(p.D == 64 && p.bias == nullptr, "attention2 (identity): head_dim 64, no score bias");
+    return p.qn_a != nullptr || p.q_rope != nullptr ? launch_attn2<64, 4, false, true, true>(p, stream) : launch_attn2<64, 4, false, false, true>(p, stream);
+  }
   if (p.bias != nullptr)  // text encoders: D = 64, short sequences
     return p.D == 128 ? dk_launch_attention2_d128(p, stream) : launch_attn2<64, 4, true>(p, stream);
   if (p.qn_a != nullptr || p.q_rope != nullptr)  // query-side QKNorm / RoPE fused into the Q load (MMDiT call sites)

@@ -242,7 +242,23 @@ struct AttnParams {
   void* a5_ws = nullptr;
   // element type of Q, K, V, O and the query-norm weights: DK_DTYPE_BF16 (0) or DK_DTYPE_F16 (1: D = 64, the lean kernel)
   int dtype = 0;
+  // identity attention (perturbed-attention guidance; the lean kernel, D = 64): 0 off.  F = ident_from, 1 <= F < S: a query s < F (text) sees
+  // every key; a query s >= F (image) sees the keys [0, F) and its own key s, nothing else
+  int ident_from = 0;
 };
+// The 64-key tiles a 128-query block of identity attention walks, in order: tiles [0, n_lo), then [hi0, hi0 + n_hi).  A block that lies wholly
+// in the image range (q0 >= F) takes the ceil(F / 64) tiles that hold text keys and the tiles that hold its own rows, cut at the end of the
+// sequence -- never the same tile twice: q0 >= F is a multiple of 64, so q0 / 64 >= ceil(F / 64).  A block with a text query walks every tile.
+// Shared by the kernel (attention2.hip) and the FLOP count of the launch (attention.hip).
+struct IdentWalk {
+  int n_lo, hi0, n_hi;
+};
+__host__ __device__ inline IdentWalk dk_ident_walk(int q0, int S, int F) {
+  const int ntiles = (S + 63) / 64;
+  if (q0 < F) return IdentWalk{ntiles, ntiles, 0};
+  const int hi0 = q0 / 64;
+  return IdentWalk{(F + 63) / 64, hi0, ntiles - hi0 < 2 ? ntiles - hi0 : 2};
+}
 // the region the key-split workgroups of attention5.hip leave their partial results in (dk_attention_workspace_bytes(); 256-byte aligned): the
 // caller's own -- an engine's carve, or what dk_attention_set_workspace gave the stand-alone entries.  Empty, or too small for a launch: no split
 struct AttnWs {

@@ -94,6 +94,11 @@ struct dk_mmdit {
   int fork_rows = 0;
   bool slg() const { return !skip.empty(); }
   bool skipped(int g) const { return std::find(skip.begin(), skip.end(), g) != skip.end(); }
+  // perturbed-attention guidance (dk_mmdit_set_perturbed_attention): the same fork (fork_rows is shared: one of the two features at a time), joining in
+  // front of double block min(pag); in the blocks of pag (sorted, distinct) the fork rows' main attention is the identity launch.  Empty: off
+  std::vector<int32_t> pag;
+  bool perturbed() const { return !pag.empty(); }
+  bool perturbed(int g) const { return std::find(pag.begin(), pag.end(), g) != pag.end(); }
   // first-block cache (dk_mmdit_set_block_cache; include/dk_hip.h): image rows [B * S_i, h] each.  BC_R: X1 at the start of a compute tail, R
   // behind it.  BC_D[bc_cur]: X0 before block 0, D_cur behind the probe; BC_D[1 - bc_cur]: D_ref -- a compute tail swaps the two.
   // BC_ROWS: the probe's (num, den) per image row.  bc_valid: R / D_ref come from a computed step since the last reset; bc_pending: the step
@@ -668,7 +673,19 @@ static int double_block_bf16(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t
     if (!kf2)
       DK_TRY(DK_EL(L.dtype, dk_launch_qk_norm_rope)(m->QKV2, 3 * h, 0, h, Mi, cf.num_heads, m->D(), wi.qn2, wi.kn2, 1e-6f, nullptr, S_i, S_i, 0, S_i, st, fuse_q()));
   }
-  DK_TRY(dk_launch_attention(joint_attention(m, c, m->ATT, h, wt, &wi), L.aws, st));
+  // perturbed attention (dk_mmdit_set_perturbed_attention): in a block of the set, run on the whole batch, the fork rows [live, B) take the identity
+  // launch -- the same operands advanced by `live` batch rows, image queries seeing the text keys and their own -- and the live rows the plain one
+  const int ident_rows = m->perturbed(i) && c.B == m->B ? m->fork_rows : 0;
+  AttnParams att = joint_attention(m, c, m->ATT, h, wt, &wi);
+  att.B = c.B - ident_rows;
+  DK_TRY(dk_launch_attention(att, L.aws, st));
+  if (ident_rows > 0) {
+    const size_t rows = (size_t)att.B * S;
+    att.Q += rows * 3 * h; att.K += rows * 3 * h; att.V += rows * 3 * h; att.O += rows * h;
+    att.B = ident_rows;
+    att.ident_from = S_t;
+    DK_TRY(dk_launch_attention(att, L.aws, st));
+  }
   if (dual) {  // the image stream alone: [B, S_i] dense rows of QKV2, no text rows, no RoPE
     AttnParams ap;
     ap.dtype = m->dtype;
@@ -912,13 +929,14 @@ extern "C" int dk_mmdit_set_skip_layers(dk_mmdit* m, const int32_t* blocks, int3
   DK_REQUIRE((n_blocks == 0) == (fork_rows == 0), "skip layers: n_blocks and fork_rows are both zero (off) or both positive");
   if (n_blocks == 0) {
     m->skip.clear();
-    m->fork_rows = 0;
+    if (!m->perturbed()) m->fork_rows = 0;  // (the fork is shared: switching this feature off leaves the other's rows alone)
     return 0;
   }
   DK_REQUIRE(blocks != nullptr, "null argument");
   DK_REQUIRE(m->cfg.depth_unified == 0, "skip layers are the SD3 family's: depth_unified must be 0");
   DK_REQUIRE(m->cfg.fp8_linears == 0, "skip layers cannot be set on an engine with fp8_linears");
   DK_REQUIRE(m->ref_h == 0 && m->ref_w == 0 && m->cond_f == 0, "skip layers cannot be set while a reference grid or a condition width is set");
+  DK_REQUIRE(!m->perturbed(), "skip layers cannot be set while perturbed attention is set (dk_mmdit_set_perturbed_attention): there is one fork");
   std::vector<int32_t> v(blocks, blocks + n_blocks);
   std::sort(v.begin(), v.end());
   DK_REQUIRE(v.front() >= 0 && v.back() < m->cfg.depth_multimodal, "skip layers: every block must lie in [0, depth_multimodal)");
@@ -927,25 +945,65 @@ extern "C" int dk_mmdit_set_skip_layers(dk_mmdit* m, const int32_t* blocks, int3
   m->fork_rows = fork_rows;
   return 0;
 }
+extern "C" int dk_mmdit_set_perturbed_attention(dk_mmdit* m, const int32_t* blocks, int32_t n_blocks, int32_t fork_rows) {
+  DK_REQUIRE(m != nullptr, "null handle");
+  DK_REQUIRE(n_blocks >= 0 && fork_rows >= 0, "perturbed attention: n_blocks and fork_rows must not be negative");
+  DK_REQUIRE((n_blocks == 0) == (fork_rows == 0), "perturbed attention: n_blocks and fork_rows are both zero (off) or both positive");
+  if (n_blocks == 0) {
+    if (m->perturbed()) m->fork_rows = 0;
+    m->pag.clear();
+    return 0;
+  }
+  DK_REQUIRE(blocks != nullptr, "null argument");
+  DK_REQUIRE(m->cfg.depth_unified == 0, "perturbed attention is the SD3 family's: depth_unified must be 0");
+  DK_REQUIRE(m->cfg.fp8_linears == 0, "perturbed attention cannot be set on an engine with fp8_linears");
+  DK_REQUIRE(m->ref_h == 0 && m->ref_w == 0 && m->cond_f == 0, "perturbed attention cannot be set while a reference grid or a condition width is set");
+  DK_REQUIRE(!m->slg(), "perturbed attention cannot be set while skip layers are set (dk_mmdit_set_skip_layers): there is one fork");
+  std::vector<int32_t> v(blocks, blocks + n_blocks);
+  std::sort(v.begin(), v.end());
+  DK_REQUIRE(v.front() >= 0 && v.back() < m->cfg.depth_multimodal, "perturbed attention: every block must lie in [0, depth_multimodal)");
+  DK_REQUIRE(std::adjacent_find(v.begin(), v.end()) == v.end(), "perturbed attention: a block is named twice (duplicate)");
+  m->pag = v;
+  m->fork_rows = fork_rows;
+  return 0;
+}
 static int no_skip_layers(const dk_mmdit* m, const char* entry) {
-  if (!m->slg()) return 0;
-  dk_set_error(std::string(entry) + " cannot run while skip layers are set (dk_mmdit_set_skip_layers): only dk_mmdit_forward forks the row group");
+  if (!m->slg() && !m->perturbed()) return 0;
+  dk_set_error(std::string(entry) + (m->slg() ? " cannot run while skip layers are set (dk_mmdit_set_skip_layers)" :
+                                                " cannot run while perturbed attention is set (dk_mmdit_set_perturbed_attention)") +
+               ": only dk_mmdit_forward forks the row group");
   return -1;
 }
-// dk_mmdit_forward with skip layers set: rows [0, live) alone up to the first skipped block, there the fork rows become a copy of rows
-// [0, fork_rows), and from there on they run every block but the skipped ones -- each group of launches is the driver's for its row count
-static int mmdit_forward_forked(dk_mmdit* m, const void* tokens_in, const void* text, const bf16_t* mod_step, bf16_t* tokens_out, const LaunchCtx& L) {
-  const int B = m->B, fork = m->fork_rows, live = B - fork, depth = m->cfg.depth_multimodal;
-  DK_REQUIRE(2 * fork <= B, "skip layers: 2 * fork_rows must not exceed the prepared batch (the fork rows copy rows [0, fork_rows))");
-  DK_REQUIRE(m->S_r == 0 && m->cond_f == 0 && m->cfg.depth_unified == 0 && !m->fp8(),
-             "skip layers cannot run with a reference grid, a condition width, single blocks or fp8_linears");
-  const int first = m->skip.front();
+// The fork of both features: rows [0, live) alone up to block `first`, there the fork rows become a copy of rows [0, fork_rows), and from there on
+// block g runs on the rows [0, rows_of(g)) -- each group of launches is the driver's for its row count
+template <class RowsOf>
+static int mmdit_forward_fork(dk_mmdit* m, const void* tokens_in, const void* text, const bf16_t* mod_step, bf16_t* tokens_out, const LaunchCtx& L,
+                              int first, RowsOf rows_of) {
+  const int fork = m->fork_rows, live = m->B - fork, depth = m->cfg.depth_multimodal;
   DK_TRY(mmdit_embed(m, tokens_in, text, L, live));
   if (first > 0) DK_TRY(mmdit_blocks(m, mod_step, 0, first, L, live));
   const size_t row = (size_t)m->S * m->h() * 2;
   DK_CHECK_HIP(hipMemcpyAsync(m->X + (size_t)live * m->S * m->h(), m->X, (size_t)fork * row, hipMemcpyDeviceToDevice, L.st));
-  for (int g = first; g < depth; ++g) DK_TRY(mmdit_blocks(m, mod_step, g, 1, L, m->skipped(g) ? live : B));
+  for (int g = first; g < depth; ++g) DK_TRY(mmdit_blocks(m, mod_step, g, 1, L, rows_of(g)));
   return mmdit_final_layer(m, mod_step, tokens_out, L);
+}
+// dk_mmdit_forward with skip layers set: the fork in front of the first skipped block; the fork rows run every block behind it but the skipped ones
+static int mmdit_forward_forked(dk_mmdit* m, const void* tokens_in, const void* text, const bf16_t* mod_step, bf16_t* tokens_out, const LaunchCtx& L) {
+  const int B = m->B, live = B - m->fork_rows;
+  DK_REQUIRE(2 * m->fork_rows <= B, "skip layers: 2 * fork_rows must not exceed the prepared batch (the fork rows copy rows [0, fork_rows))");
+  DK_REQUIRE(m->S_r == 0 && m->cond_f == 0 && m->cfg.depth_unified == 0 && !m->fp8(),
+             "skip layers cannot run with a reference grid, a condition width, single blocks or fp8_linears");
+  return mmdit_forward_fork(m, tokens_in, text, mod_step, tokens_out, L, m->skip.front(), [&](int g) { return m->skipped(g) ? live : B; });
+}
+// ... with perturbed attention set: the fork in front of the first block of the set; every block behind it runs on all rows, and the blocks of the
+// set give the fork rows the identity launch (double_block_bf16)
+static int mmdit_forward_perturbed(dk_mmdit* m, const void* tokens_in, const void* text, const bf16_t* mod_step, bf16_t* tokens_out, const LaunchCtx& L) {
+  const int B = m->B;
+  DK_REQUIRE(2 * m->fork_rows <= B, "perturbed attention: 2 * fork_rows must not exceed the prepared batch (the fork rows copy rows [0, fork_rows))");
+  DK_REQUIRE(m->S_r == 0 && m->cond_f == 0 && m->cfg.depth_unified == 0 && !m->fp8(),
+             "perturbed attention cannot run with a reference grid, a condition width, single blocks or fp8_linears");
+  DK_REQUIRE(m->D() == 64, "perturbed attention: the identity attention kernel is built for head_dim 64");
+  return mmdit_forward_fork(m, tokens_in, text, mod_step, tokens_out, L, m->pag.front(), [&](int) { return B; });
 }
 
 extern "C" int dk_mmdit_forward(dk_mmdit* m, const void* tokens_in, const void* text, int32_t step_index, void* tokens_out,
@@ -956,6 +1014,7 @@ extern "C" int dk_mmdit_forward(dk_mmdit* m, const void* tokens_in, const void* 
   const bf16_t* mod_step = m->MOD + (size_t)step_index * m->B * m->mod_rows() * m->h();
   m->bc_pending = -1;  // (a head without its tail is dropped: this call overwrites the stream it left; R / D_ref stay)
   if (m->slg()) return mmdit_forward_forked(m, tokens_in, text, mod_step, (bf16_t*)tokens_out, L);
+  if (m->perturbed()) return mmdit_forward_perturbed(m, tokens_in, text, mod_step, (bf16_t*)tokens_out, L);
   DK_TRY(mmdit_embed(m, tokens_in, text, L));
   DK_TRY(mmdit_blocks(m, mod_step, 0, m->cfg.depth_multimodal + m->cfg.depth_unified, L));
   return mmdit_final_layer(m, mod_step, (bf16_t*)tokens_out, L);

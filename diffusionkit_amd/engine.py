@@ -119,6 +119,7 @@ class MMDiTEngine:
         self.reference_size = (0, 0)  # latent cells of the reference image (prepare(reference_size=...)); (0, 0): none
         self._ref_cached = False
         self.skip_layers, self.fork_rows = (), 0  # ``set_skip_layers``; ((), 0): off
+        self.perturbed_attention = ()  # ``set_perturbed_attention``: the blocks; (): off (it shares ``fork_rows``: one of the two at a time)
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -134,6 +135,20 @@ class MMDiTEngine:
         arr = (C.c_int32 * len(blocks))(*blocks) if blocks else None
         _lib.check(self.lib.dk_mmdit_set_skip_layers(self._h, arr, len(blocks), int(fork_rows)), "dk_mmdit_set_skip_layers")
         self.skip_layers, self.fork_rows = tuple(sorted(blocks)), int(fork_rows)
+
+    def set_perturbed_attention(self, blocks=None, fork_rows: int = 0) -> None:
+        """dk_mmdit_set_perturbed_attention (perturbed-attention guidance, include/dk_hip.h): the last ``fork_rows`` batch rows of every later
+        ``forward_tokens`` become a copy of the first ``fork_rows`` that joins in front of double block min(``blocks``); in the blocks named their
+        image queries attend to the text keys and to their own key only (one identity-attention launch beside the plain one).  Their rows of
+        ``tokens_in``, of ``text`` and of the cached context are never read, and the caller repeats the pooled rows for them.  ``(None, 0)``:
+        off.  Takes effect at the next forward; nothing is re-prepared.  Refused while skip layers are set, and ``forward_head`` /
+        ``forward_tail`` / ``run_blocks`` are refused while this is."""
+        blocks = [] if blocks is None else [int(b) for b in blocks]
+        arr = (C.c_int32 * len(blocks))(*blocks) if blocks else None
+        _lib.check(self.lib.dk_mmdit_set_perturbed_attention(self._h, arr, len(blocks), int(fork_rows)), "dk_mmdit_set_perturbed_attention")
+        if blocks or self.perturbed_attention:
+            self.fork_rows = int(fork_rows)
+        self.perturbed_attention = tuple(sorted(blocks))
 
     def _check_pitched_weights(self) -> None:
         """The engine reads the long-reduction weights at ``dk_weight_pitch`` elements per row (include/dk_hip.h); the C ABI

@@ -315,6 +315,35 @@ def attention(qkv: Tensor, H: int, D: int, scale: Optional[float] = None, worksp
     return out
 
 
+def attention_identity(qkv: Tensor, H: int, D: int, ident_from: int, scale: Optional[float] = None, qn=None) -> Tensor:
+    """dk_attention_identity_bf16 / _f16 by the dtype of ``qkv``: ``attention`` over a token-major [B, S, 3*H*D] buffer in which a query
+    s >= ``ident_from`` sees the keys [0, ident_from) and its own key only (perturbed-attention guidance; head_dim 64).  ``qn``: optionally
+    (qn_a, qn_b, qn_split[, q_rope]), the query QKNorm (+ RoPE) of the kernel's Q load, as ``attention_desc_call`` names them."""
+    el = _elem(qkv.dtype, "attention_identity")
+    _require_cuda(qkv, "qkv", qkv.dtype)
+    B, S, ld = qkv.shape
+    h = H * D
+    out = torch.empty(B, S, h, dtype=qkv.dtype, device=qkv.device)
+    kw = dict(q=qkv, k=qkv[:, :, h:], v=qkv[:, :, 2 * h:], out=out, B=B, H=H, S=S, D=D, ld=ld, ldo=h,
+              scale=scale if scale is not None else 1.0 / math.sqrt(D))
+    if qn is not None:
+        _same_elem(qkv.dtype, "attention_identity", qn_a=qn[0], qn_b=qn[1])
+        kw.update(qn_a=qn[0], qn_b=qn[1], qn_split=int(qn[2]), qn_eps=1e-6, q_rope=qn[3] if len(qn) > 3 else None)
+    d = _fill(_lib.dk_attention_desc, kw)
+    name = "dk_attention_identity_" + el
+    _lib.check(getattr(_lib.load(), name)(C.byref(d), int(ident_from), _stream()), name)
+    return out
+
+
+def attention_identity_plan(ident_from: int, dtype=BF, **kw):
+    """dk_attention_identity_plan: what ``attention_identity`` with these dk_attention_desc fields would launch (host only; pointers may be
+    made-up, aligned integers), and every refusal of the launch."""
+    d, plan = _fill(_lib.dk_attention_desc, kw), _lib.dk_attention_plan_t()
+    f16 = int(_elem(dtype, "attention_identity_plan") != "bf16")
+    _lib.check(_lib.load().dk_attention_identity_plan(C.byref(d), int(ident_from), f16, C.byref(plan)), "dk_attention_identity_plan")
+    return plan
+
+
 def ln_modulate(x: Tensor, shift: Tensor, scale: Tensor, eps: float = 1e-6) -> Tensor:
     """x: [B, S, h]; shift/scale: [B, h] -> [B, S, h] (bf16, or all float16)."""
     lib = _lib.load()

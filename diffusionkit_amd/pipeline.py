@@ -25,6 +25,11 @@ Stable Diffusion 3.5 medium): in the steps of its window the engine carries a th
 skipped block and sits out the skipped ones (``MMDiTEngine.set_skip_layers``), and the step launch is dk_slg_cfg_step, which adds scale (c - k) to the
 mode's prediction.  The definition is ``sampler.slg_reference``'s.  Arithmetic only, on synthetic weights: no SD3.5-medium checkpoint has been run here.
 
+Perturbed-attention guidance (``pag_scale=``, ``pag_layers=``, ``pag_interval=``, keyword-only, no reference counterpart; diffusers'
+StableDiffusion3PAGPipeline): the same third row group and the same step launch, but the fork rows run every block, and in the named ones their image
+queries attend to the text keys and to their own key only (``MMDiTEngine.set_perturbed_attention``, dk_attention_identity_*).  One loop serves both
+features (``_Loop.forked``); they cannot be combined: the engine forks one row group.  Arithmetic only, on synthetic weights.
+
 All arithmetic runs in libdk_hip.so on the current HIP stream; numpy is used exactly where the
 reference uses it (the seeded noise draw, __init__.py:553-557) and for O(num_steps) schedule
 scalars.
@@ -43,7 +48,8 @@ import torch
 from . import _lib
 from .config import (MMDIT_CKPT, MODEL_CONFIG, SKIP_LAYER_GUIDANCE, T5_MAX_LENGTH, MMDiTConfig, VAEDecoderConfig, VAEEncoderConfig)
 from .engine import MMDiTEngine, VAEDecoderEngine, VAEEncoderEngine, _stream
-from .sampler import (FluxSampler, ModelSamplingDiscreteFlow, check_guidance, check_interval, check_sampler, check_skip_layer_guidance, get_sigmas,
+from .sampler import (FluxSampler, ModelSamplingDiscreteFlow, check_guidance, check_interval, check_perturbed_attention_guidance, check_sampler,
+                      check_skip_layer_guidance, get_sigmas,
                       guidance_rows, max_denoise, slg_rows, step_plan)
 from .weights import pack_mmdit, pack_vae, synth_mmdit_weights, synth_vae_encoder_weights, synth_vae_weights
 
@@ -492,6 +498,9 @@ class DiffusionPipeline:
         skip_layer_guidance=None,
         skip_layers=None,
         skip_layer_interval=None,
+        pag_scale=None,
+        pag_layers=None,
+        pag_interval=None,
     ):
         """mlx/__init__.py:253-292.  ``seed`` may be a list: one image per seed is denoised in a
         single batched step loop (data-parallel sharding hands each rank a list).
@@ -540,7 +549,16 @@ class DiffusionPipeline:
         version must name its layers, and its interval defaults to (0, 1).  Composes with seed lists, every sampler and guidance mode, img2img,
         inpainting and float16.  Raises on FLUX, ``cfg_weight <= 0``, ``block_cache`` (no cache policy for a forked row group yet) and a layer outside
         the model.  ``self.last_skip_layer_guidance`` = {"layers", "scale", "interval", "evals"} (evaluations with the term), or None.  Verified as
-        arithmetic only, on synthetic weights: no SD3.5-medium checkpoint has been run here."""
+        arithmetic only, on synthetic weights: no SD3.5-medium checkpoint has been run here.
+        ``pag_scale`` (perturbed-attention guidance, diffusers' StableDiffusion3PAGPipeline; SD3 family with ``cfg_weight > 0``; None: off): the scale
+        s of a third evaluation, the prompt rows through a model whose double blocks ``pag_layers`` run their attention perturbed -- image queries
+        attend to the text keys and to their own key only: den = G(pos, neg) + s (pos - perturbed), the same term and the same step launch as
+        skip-layer guidance.  ``pag_interval`` None: every guided evaluation carries it; (start, stop): step i of n iff n start < i < n stop.  There
+        is no published recipe: scale and layers come together.  The third row group is forked inside the engine
+        (``MMDiTEngine.set_perturbed_attention``).  Composes with seed lists, every sampler and guidance mode, ``guidance_interval``, img2img,
+        inpainting and float16.  Raises on FLUX, ``cfg_weight <= 0``, ``block_cache``, an fp8 engine, a reference image, a condition and together
+        with skip-layer guidance (there is one fork).  ``self.last_perturbed_attention_guidance`` = {"layers", "scale", "interval", "evals"}, or
+        None.  Verified as arithmetic only, on synthetic weights: no checkpoint has been run here."""
         check_condition_args(getattr(self, "condition", None), condition_image_path, condition_mask_path, reference_image_path, self._IS_FLUX)
         if reference_image_path is not None and not self._IS_FLUX:
             raise ValueError(_REFERENCE_NEEDS_ROPE)
@@ -548,6 +566,10 @@ class DiffusionPipeline:
         if skip_layer_guidance is not None or skip_layers is not None or skip_layer_interval is not None:
             slg = _skip_layer_options(skip_layer_guidance, skip_layers, skip_layer_interval, self.model_version, self.mmdit_config, self._IS_FLUX,
                                       cfg_weight, block_cache)
+        pag = None
+        if pag_scale is not None or pag_layers is not None or pag_interval is not None:
+            pag = _perturbed_attention_options(pag_scale, pag_layers, pag_interval, self.mmdit_config, self._IS_FLUX, cfg_weight, block_cache,
+                                               reference_image_path, getattr(self, "condition", None) or condition_image_path, slg)
         guide = _guidance_options(guidance, guidance_rescale, apg_eta, apg_norm_threshold, apg_momentum, guidance_interval, cfg_weight)
         if mask_path is not None and image_path is None:
             raise ValueError("mask_path needs image_path: the mask says which part of that image to keep")
@@ -591,6 +613,8 @@ class DiffusionPipeline:
             extra_args["guidance"] = guide
         if slg is not None:
             extra_args["skip_layer_guidance"] = slg
+        if pag is not None:
+            extra_args["perturbed_attention_guidance"] = pag
         self.last_reference = None
         if refs is not None:
             extra_args["reference"] = self.latent_format.process_in(self.encode_reference_to_latents(refs))
@@ -604,7 +628,7 @@ class DiffusionPipeline:
         noise_scaled = self.sampler.noise_scaling(np.float32(sigmas[0]), noise, x_T, self.max_denoise(sigmas))
         x0 = torch.from_numpy(np.ascontiguousarray(noise_scaled, dtype=np.float32)).to(self.device)
         denoiser = CFGDenoiser(self)
-        if sampler == "euler" and guide is None and slg is None:
+        if sampler == "euler" and guide is None and slg is None and pag is None:
             latent, iter_time = sample_euler(denoiser, x0, sigmas, extra_args=extra_args)
             evals = len(iter_time)
         else:
@@ -616,6 +640,7 @@ class DiffusionPipeline:
         self.last_guidance = denoiser.guidance_record or dict(_DEFAULT_GUIDANCE, guided_evals=evals if cfg_weight > 0 else 0,
                                                               unguided_evals=0 if cfg_weight > 0 else evals)
         self.last_skip_layer_guidance = denoiser.skip_layer_record
+        self.last_perturbed_attention_guidance = denoiser.perturbed_attention_record
         latent = self.latent_format.process_out(latent)
         return latent, iter_time
 
@@ -647,6 +672,9 @@ class DiffusionPipeline:
         skip_layer_guidance=None,
         skip_layers=None,
         skip_layer_interval=None,
+        pag_scale=None,
+        pag_layers=None,
+        pag_interval=None,
     ):
         """mlx/__init__.py:294-534: returns (PIL.Image, log).  ``mask_path``: inpainting, see ``denoise_latents``; with ``composite`` the pixels
         the mask keeps are pasted back from the input image after decoding (the VAE round trip alone does not reproduce them).
@@ -659,7 +687,9 @@ class DiffusionPipeline:
         ``condition_image_path`` / ``condition_mask_path``: channel-concatenated conditioning, see ``denoise_latents``; ``log["denoising"]["condition"]`` is
         ``self.last_condition``.  With ``composite`` and no ``mask_path``, the pixels a fill mask keeps are pasted back from the condition image.
         ``skip_layer_guidance``, ``skip_layers``, ``skip_layer_interval``: skip-layer guidance, see ``denoise_latents``; with it on,
-        ``log["denoising"]["skip_layer_guidance"]`` is ``self.last_skip_layer_guidance``."""
+        ``log["denoising"]["skip_layer_guidance"]`` is ``self.last_skip_layer_guidance``.
+        ``pag_scale``, ``pag_layers``, ``pag_interval``: perturbed-attention guidance, see ``denoise_latents``; with it on,
+        ``log["denoising"]["perturbed_attention_guidance"]`` is ``self.last_perturbed_attention_guidance``."""
         check_condition_args(getattr(self, "condition", None), condition_image_path, condition_mask_path, reference_image_path, self._IS_FLUX)
         if mask_path is not None and image_path is None:
             raise ValueError("mask_path needs image_path: the mask says which part of that image to keep")
@@ -698,7 +728,9 @@ class DiffusionPipeline:
             **({} if reference_image_path is None else {"reference_image_path": reference_image_path}),
             **({} if condition_image_path is None else {"condition_image_path": condition_image_path, "condition_mask_path": condition_mask_path}),
             **({} if skip_layer_guidance is None and skip_layers is None and skip_layer_interval is None else
-               {"skip_layer_guidance": skip_layer_guidance, "skip_layers": skip_layers, "skip_layer_interval": skip_layer_interval}))
+               {"skip_layer_guidance": skip_layer_guidance, "skip_layers": skip_layers, "skip_layer_interval": skip_layer_interval}),
+            **({} if pag_scale is None and pag_layers is None and pag_interval is None else
+               {"pag_scale": pag_scale, "pag_layers": pag_layers, "pag_interval": pag_interval}))
         torch.cuda.synchronize(dev)
         log["denoising"]["post"] = mem()
         log["peak_memory"] = max(log["peak_memory"], log["denoising"]["post"]["peak_memory"])
@@ -715,6 +747,8 @@ class DiffusionPipeline:
             log["denoising"]["condition"] = self.last_condition
         if self.last_skip_layer_guidance is not None:
             log["denoising"]["skip_layer_guidance"] = self.last_skip_layer_guidance
+        if self.last_perturbed_attention_guidance is not None:
+            log["denoising"]["perturbed_attention_guidance"] = self.last_perturbed_attention_guidance
 
         torch.cuda.reset_peak_memory_stats(dev)
         t0 = time.time()
@@ -912,6 +946,7 @@ class CFGDenoiser:
         self.block_cache_record = None  # what sample_euler decided per step under extra_args["block_cache"]
         self.guidance_record = None  # what sample_steps ran under extra_args["guidance"]
         self.skip_layer_record = None  # what sample_steps ran under extra_args["skip_layer_guidance"]
+        self.perturbed_attention_record = None  # ... under extra_args["perturbed_attention_guidance"]
 
     def cache_modulation_params(self, pooled_text_embeddings, timesteps):
         self._timesteps = [float(t) for t in timesteps]
@@ -1034,6 +1069,37 @@ def _skip_layer_options(scale, layers, interval, model_version, mmdit_config, is
     return {"scale": scale, "layers": layers, "interval": interval}
 
 
+def _perturbed_attention_options(scale, layers, interval, mmdit_config, is_flux, cfg_weight, block_cache, reference, condition, slg):
+    """The perturbed-attention keywords of ``denoise_latents`` -> None when the feature is off (all None), else the dict ``sample_steps`` takes as
+    ``extra_args["perturbed_attention_guidance"]``: {"scale", "layers", "interval"} (interval None: every guided row).  There is no published recipe:
+    a scale without layers and layers (or an interval) without a scale are refused, and so are FLUX, ``cfg_weight <= 0``, ``block_cache``, an fp8
+    engine, a reference image, a condition, skip-layer guidance in the same call, and whatever ``sampler.check_perturbed_attention_guidance``
+    refuses."""
+    if scale is None and layers is None and interval is None:
+        return None
+    if scale is None:
+        raise ValueError("pag_layers / pag_interval need pag_scale (the scale of the term; None is off)")
+    if layers is None:
+        raise ValueError("pag_scale needs pag_layers: no layers are published for perturbed-attention guidance, name them")
+    if is_flux:
+        raise ValueError("perturbed-attention guidance is the SD3 family's: FLUX runs without classifier-free guidance and its blocks have no perturbed form")
+    if not cfg_weight > 0:
+        raise ValueError(f"perturbed-attention guidance needs classifier-free guidance: cfg_weight is {cfg_weight}, and the step entry combines both "
+                         "CFG rows (PAG without CFG is not built)")
+    if block_cache is not None:
+        raise ValueError("perturbed-attention guidance cannot run together with block_cache: there is no cache policy for a forked row group yet")
+    if mmdit_config.weight_dtype == "fp8_e4m3":
+        raise ValueError("perturbed-attention guidance cannot run on an fp8 engine: the identity attention has no MX-fp8 output copy")
+    if reference is not None:
+        raise ValueError("perturbed-attention guidance cannot run with a reference image: the forked row group has no reference grid")
+    if condition is not None:
+        raise ValueError("perturbed-attention guidance cannot run with a condition: the forked row group has no condition width")
+    if slg is not None:
+        raise ValueError("perturbed-attention guidance cannot run together with skip-layer guidance: the engine forks one row group")
+    scale, layers, interval = check_perturbed_attention_guidance(scale, layers, interval, mmdit_config.depth_multimodal)
+    return {"scale": scale, "layers": layers, "interval": interval}
+
+
 class _Loop(NamedTuple):
     """what a step loop works on once the engine is prepared (``_loop_setup``)"""
     pipe: object
@@ -1055,6 +1121,17 @@ class _Loop(NamedTuple):
     reference: Optional[Tensor] = None  # the reference latent f32 [1 or n_img, rh, rw, C] behind ``extra_args["reference"]``, or None
     condition: Optional[Tensor] = None  # the condition token rows bf16 [1 or n_img, S_i, condition_features] behind ``extra_args["condition"]``, or None
     slg: Optional[dict] = None  # ``extra_args["skip_layer_guidance"]`` (``_skip_layer_options``), or None
+    pag: Optional[dict] = None  # ``extra_args["perturbed_attention_guidance"]`` (``_perturbed_attention_options``), or None: never both
+
+    @property
+    def forked(self) -> Optional[dict]:
+        """the options of the feature that forks a third row group, skip-layer or perturbed-attention guidance: {"scale", "layers", ...}, or None"""
+        return self.slg if self.slg is not None else self.pag
+
+    def set_fork(self, on: bool) -> None:
+        """the engine's setter of that feature: its layers on ``n_img`` fork rows, or off"""
+        setter = self.mm.set_skip_layers if self.slg is not None else self.mm.set_perturbed_attention
+        setter(self.forked["layers"] if on else None, self.n_img if on else 0)
 
 
 def _cache_condition(mm, condition: Optional[Tensor], now: int, n_img: int) -> None:
@@ -1143,7 +1220,7 @@ def _loop_setup(model: "CFGDenoiser", x: Tensor, sigmas, extra_args, guided: boo
         x_orig = noise = None
     tok = mm.patchify(x, dup=2 if cfg_on and guided else 1)
     return _Loop(pipe, mm, sigmas, cfg_weight, cfg_on, n_img, policy, x, mask, x_orig, noise, tok, torch.empty_like(tok), conditioning, pooled, timesteps,
-                 reference, condition, extra_args.get("skip_layer_guidance"))
+                 reference, condition, extra_args.get("skip_layer_guidance"), extra_args.get("perturbed_attention_guidance"))
 
 
 def _set_rows(model: "CFGDenoiser", lp: _Loop, guided: bool, fork: bool = False):
@@ -1159,8 +1236,8 @@ def _set_rows(model: "CFGDenoiser", lp: _Loop, guided: bool, fork: bool = False)
     _cache_condition(lp.mm, lp.condition, now, lp.n_img)
     model.cache_modulation_params(rows(lp.pooled).contiguous(), lp.timesteps)
     lp.mm.cache_context(rows(lp.conditioning).contiguous())
-    if lp.slg is not None:  # (without the option the engine is never told: its calls are what they were)
-        lp.mm.set_skip_layers(lp.slg["layers"] if fork else None, lp.n_img if fork else 0)
+    if lp.forked is not None:  # (without the options the engine is never told: its calls are what they were)
+        lp.set_fork(fork)
     tok = lp.mm.patchify(lp.x, dup=now // lp.n_img)
     return tok, torch.empty_like(tok)
 
@@ -1196,7 +1273,7 @@ def _step_loop(model: "CFGDenoiser", lp: _Loop, plan, grows, guide=None, euler: 
         t0 = time.perf_counter() if t0 is None else t0
         if cfg_on and (g.guided != on or sl != fork):
             on, fork = g.guided, sl
-            tok, out = _set_rows(model, lp, on, fork) if lp.slg is not None else _set_rows(model, lp, on)
+            tok, out = _set_rows(model, lp, on, fork) if lp.forked is not None else _set_rows(model, lp, on)
             if policy is not None:
                 mm.reset_block_cache()
                 fresh = True
@@ -1213,7 +1290,7 @@ def _step_loop(model: "CFGDenoiser", lp: _Loop, plan, grows, guide=None, euler: 
         if not euler:
             args += (hist, (r.cx, r.cd, r.ch, r.hx, r.hd), r.reads_h, r.writes_h)
         if fork:
-            ops.slg_cfg_step(*args, slg_scale=lp.slg["scale"], mode=mode, workspace=gws, **({} if guide is None else dict(
+            ops.slg_cfg_step(*args, slg_scale=lp.forked["scale"], mode=mode, workspace=gws, **({} if guide is None else dict(
                 rescale=guide["guidance_rescale"], eta=guide["apg_eta"], norm_threshold=guide["apg_norm_threshold"])), momentum=beta,
                 reads_m=mbuf is not None and not g.first, writes_m=mbuf is not None and g.feeds, m=mbuf, **dict(zip(("x_orig", "noise", "mask"), blend)))
         elif on and mode != "cfg":
@@ -1233,6 +1310,8 @@ def _step_loop(model: "CFGDenoiser", lp: _Loop, plan, grows, guide=None, euler: 
         model.guidance_record = dict(guide, guided_evals=n_g, unguided_evals=len(grows) - n_g)
     if lp.slg is not None:
         model.skip_layer_record = dict(lp.slg, evals=sum(bool(v) for v in srows))
+    if lp.pag is not None:
+        model.perturbed_attention_record = dict(lp.pag, evals=sum(bool(v) for v in srows))
     model.clear_cache()
     return x, iter_time
 
@@ -1278,15 +1357,23 @@ def sample_steps(model: CFGDenoiser, x: Tensor, sigmas, plan, extra_args=None):
         raise ValueError("extra_args['guidance'] needs classifier-free guidance (cfg_weight > 0)")
     if slg is not None and not lp.cfg_on:
         raise ValueError("extra_args['skip_layer_guidance'] needs classifier-free guidance (cfg_weight > 0)")
-    if slg is not None and lp.policy is not None:
-        raise ValueError("skip-layer guidance cannot run together with block_cache: there is no cache policy for a forked row group yet")
+    pag = None if extra_args is None else extra_args.get("perturbed_attention_guidance")
+    if pag is not None and slg is not None:
+        raise ValueError("extra_args holds both 'skip_layer_guidance' and 'perturbed_attention_guidance': the engine forks one row group")
+    if pag is not None and not lp.cfg_on:
+        raise ValueError("extra_args['perturbed_attention_guidance'] needs classifier-free guidance (cfg_weight > 0)")
+    if (slg is not None or pag is not None) and lp.policy is not None:
+        raise ValueError(("skip-layer" if slg is not None else "perturbed-attention") +
+                         " guidance cannot run together with block_cache: there is no cache policy for a forked row group yet")
     if lp.policy is not None and not all(r.ends_step for r in plan):
         raise ValueError(_HEUN_BLOCK_CACHE)
     if any(not 0 <= r.index < len(lp.sigmas) - 1 for r in plan):
         raise ValueError("the plan evaluates the model outside the schedule (or at its last entry): build it with sampler.step_plan on these sigmas")
-    if slg is None:
+    if lp.forked is None:
         return _step_loop(model, lp, plan, grows, guide)
+    window = lp.forked["interval"]  # (None, perturbed-attention guidance only: every guided row)
+    srows = [bool(g.guided) for g in grows] if window is None else slg_rows(plan, grows, *window)
     try:
-        return _step_loop(model, lp, plan, grows, guide, srows=slg_rows(plan, grows, *slg["interval"]))
+        return _step_loop(model, lp, plan, grows, guide, srows=srows)
     finally:
-        lp.mm.set_skip_layers(None, 0)
+        lp.set_fork(False)

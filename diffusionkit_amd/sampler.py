@@ -277,6 +277,39 @@ def slg_reference(c, u, k, w, scale, mode="cfg", **kw):
     return den + float(scale) * (c - k), m_new
 
 
+# ---- perturbed-attention guidance: the same third evaluation, through blocks whose image queries attend to the text keys and to themselves -----
+def check_perturbed_attention_guidance(scale, layers, interval, depth):
+    """The options of perturbed-attention guidance -> (scale, layers, interval): a finite float >= 0; the sorted tuple of distinct block indices, at
+    least one, each in [0, depth); None (every guided row carries the term) or fractions of the schedule (start, stop) with 0 <= start <= stop <= 1,
+    read by ``slg_rows``.  The term itself is ``slg_reference``'s, with k the perturbed model's prediction.  Anything else raises a ValueError that
+    names the rule."""
+    try:
+        scale = float(scale)
+    except (TypeError, ValueError):
+        raise ValueError(f"pag_scale must be a float, got {scale!r}") from None
+    if not math.isfinite(scale) or scale < 0.0:
+        raise ValueError(f"pag_scale must be finite and >= 0, got {scale}")
+    if layers is None or isinstance(layers, (str, bytes)) or len(tuple(layers)) == 0:
+        raise ValueError("pag_layers must name at least one block")
+    raw = tuple(layers)
+    if any(isinstance(b, bool) or int(b) != b for b in raw):
+        raise ValueError(f"pag_layers must be block indices (integers), got {raw}")
+    out = tuple(sorted(int(b) for b in raw))
+    if len(set(out)) != len(out):
+        raise ValueError(f"pag_layers names a block twice: {raw}")
+    if out[0] < 0 or out[-1] >= int(depth):
+        raise ValueError(f"pag_layers {raw}: every block must lie in [0, {int(depth)}), the model's double blocks")
+    if interval is not None:
+        try:
+            start, stop = (float(v) for v in interval)
+        except (TypeError, ValueError):
+            raise ValueError(f"pag_interval must be None or (start, stop), got {interval!r}") from None
+        if not 0.0 <= start <= stop <= 1.0:
+            raise ValueError(f"pag_interval must be (start, stop) with 0 <= start <= stop <= 1, got ({start}, {stop})")
+        interval = (start, stop)
+    return scale, out, interval
+
+
 # ---- first-block cache: which steps compute and which reuse (host policy; no reference counterpart) -------------------------
 def block_cache_rel(probe) -> float:
     """``probe``: (num, den) per batch row as ``MMDiTEngine.forward_head`` returns them, on the host -> the relative change of block 0's

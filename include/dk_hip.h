@@ -245,6 +245,22 @@ typedef struct dk_attention_plan_t {
 } dk_attention_plan_t;
 int dk_attention_plan(const dk_attention_desc* d, size_t workspace_bytes, dk_attention_plan_t* plan);
 
+/* Identity attention (additive in ABI 5; no reference counterpart -- the perturbation of perturbed-attention guidance, Ahn et al. 2024,
+ * diffusers' PAGJointAttnProcessor2_0): the descriptor's attention in which, per batch row and head, with F = ident_from,
+ *   a query s <  F (text)   sees every key in [0, S), as in dk_attention_desc_bf16;
+ *   a query s >= F (image)  sees the keys [0, F) and its own key s, and nothing else.
+ * Softmax and P.V are the plain kernel's; a masked key contributes an exact zero.  No [S, S] mask exists: the lean D = 64 kernel
+ * (attention2.hip) walks, for a block of 128 image queries, the ceil(F / 64) key tiles that hold text keys and the two tiles that hold
+ * the block's own rows -- 5 tiles instead of 67 at S = 154 + 4096; a block that holds a text query walks every tile.  The fused query
+ * load (qn_a / qn_b / qn_split / q_rope) works as in the plain launch.  Text rows below the last multiple of 32 that is <= F are the
+ * plain launch's bits; the other text rows (they share a wave with image rows) equal it to rounding.
+ * Refused, nothing launched, dk_last_error() names the rule: D != 64; a score bias; an MX-fp8 copy (O8); ident_from outside [1, S).
+ * The route is kernel 4 whatever dk_tune_set("attn", .) says.  _f16: fp16 elements.  dk_attention_identity_plan: host only, the same
+ * checks and the record dk_attention_plan gives (f16 != 0: of the _f16 entry); plan->o8_split is not read. */
+int dk_attention_identity_bf16(const dk_attention_desc* d, int32_t ident_from, void* stream);
+int dk_attention_identity_f16(const dk_attention_desc* d, int32_t ident_from, void* stream);
+int dk_attention_identity_plan(const dk_attention_desc* d, int32_t ident_from, int32_t f16, dk_attention_plan_t* plan);
+
 /* Single-head attention over head_dim 512: the VAE mid block's Attention (vae.py:28-57: softmax((q / sqrt 512) k^T) v over all
  * H * W tokens), flash-style -- the [T, T] score matrix of the reference (537 MB at T = 16384) is never written.  q / k / v / out:
  * bf16 [B, T, ld] with ld == 512 EXACTLY (dense rows: the transposed copy of v is taken from a dense [T, 512] matrix; any other row
@@ -795,6 +811,29 @@ int dk_mmdit_set_dual_attention(dk_mmdit* m, int32_t n_blocks);
  * dk_mmdit_run_blocks while skip layers are set.  Both element types.
  * Verified against an fp32 / emulating oracle with synthetic weights (arithmetic parity); no SD3.5-medium checkpoint has been run. */
 int dk_mmdit_set_skip_layers(dk_mmdit* m, const int32_t* blocks, int32_t n_blocks, int32_t fork_rows);
+
+/* ---- Perturbed attention: the forked row group with identity attention in some double blocks (opt-in; perturbed-attention guidance,
+ * diffusers' StableDiffusion3PAGPipeline; the step entry is dk_slg_cfg_step, whose slg_scale is then the PAG scale) -------------------
+ * The fork is dk_mmdit_set_skip_layers' (one function drives both).  With B prepared batch rows, live = B - fork_rows and f = min(blocks),
+ * dk_mmdit_forward runs
+ *   the embedders and the blocks g < f     on rows [0, live): rows >= live of tokens_in, of text and of the cached context are never read;
+ *   the fork, in front of block f          X[live + j] = X[j] for j < fork_rows, one device copy in stream order;
+ *   every block >= f, the final layer      on all B rows;   tokens_out is [B, S_i, F].
+ * In a block of the set only the main attention differs: the plain launch runs on rows [0, live), and dk_attention_identity_* with
+ * ident_from = S_t on rows [live, B) -- the same QKV / ATT buffers, base pointers advanced by `live` batch rows; one launch more per
+ * perturbed block.  LN-modulate, the q/k/v projections, the key norm, the attn2 path of an MMDiT-X dual block (diffusers perturbs attn
+ * only), both o-projections and the MLP stay one launch over B rows.  So the fork rows are the evaluation of rows [0, fork_rows) by a
+ * model whose image queries, in the blocks of the set, attend to the text keys and to their own key.  The caller repeats the pooled rows
+ * of rows [0, fork_rows) for the fork rows.  May be called at any time after dk_mmdit_create and takes effect at the next forward;
+ * workspace size and carve do not change.  (NULL, 0, 0) is off, the default: every launch and every bit is then what it is without the
+ * feature.
+ * Refused, with no state changed and an error that names the rule: exactly one of n_blocks and fork_rows zero (or either negative), a
+ * block outside [0, depth_multimodal) or named twice, depth_unified > 0, fp8_linears, a reference grid or a condition width that is
+ * set, skip layers that are set (there is one fork; dk_mmdit_set_skip_layers likewise refuses while perturbed attention is set).
+ * Refused at the call, never launched: a forward with 2 * fork_rows > B or a head_dim other than 64, and dk_mmdit_forward_head,
+ * dk_mmdit_forward_tail and dk_mmdit_run_blocks while perturbed attention is set.  Both element types.
+ * Verified against an fp32 / emulating oracle with synthetic weights (arithmetic parity); no checkpoint has been run. */
+int dk_mmdit_set_perturbed_attention(dk_mmdit* m, const int32_t* blocks, int32_t n_blocks, int32_t fork_rows);
 /* Head of step `step_index`: dk_mmdit_forward's embedder launches, block 0 and the probe.  probe_out: device float [batch][2] =
  * (num, den) per batch row; before any computed step den is 0 (and num = sum |D_cur|).  Records a pending head for step_index. */
 int dk_mmdit_forward_head(dk_mmdit* m, const void* tokens_in, const void* text, int32_t step_index, float* probe_out, void* stream);
