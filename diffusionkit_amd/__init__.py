@@ -6,7 +6,7 @@ python/src/diffusionkit/mlx/__init__.py): ``DiffusionPipeline``, ``FluxPipeline`
 Importing this package does not load the HIP library; constructing a pipeline or an engine
 does, and raises ``DkHipError`` if it is missing (there is no CPU fallback).
 """
-from .config import MMDIT_CKPT, T5_MAX_LENGTH, MMDiTConfig, VAEDecoderConfig, SD3_2b, SD3_8b, FLUX_SCHNELL  # noqa: F401
+from .config import MMDIT_CKPT, T5_MAX_LENGTH, MMDiTConfig, VAEDecoderConfig, SD3_2b, SD3_8b, FLUX_SCHNELL, SD3_CONTROLNET_6  # noqa: F401
 from ._lib import DkHipError  # noqa: F401
 
 

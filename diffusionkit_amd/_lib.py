@@ -245,6 +245,13 @@ SIGNATURES = {
     "dk_mmdit_set_perturbed_attention": (_i32, [_vp, C.POINTER(_i32), _i32, _i32]),
     **{"dk_ln_modulate_dual_" + el: (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
                                             _i32, _f32, _vp]) for el in ("bf16", "f16")},
+    # SD3 ControlNet: the control-net engine's setter / hoist / forward, the main engine's taps, and the LayerNorm pass with a residual tap in front
+    "dk_mmdit_set_control_net": (_i32, [_vp, _i32]),
+    "dk_mmdit_cache_control_image": (_i32, [_vp, _vp, _i32, _vp]),
+    "dk_mmdit_control_forward": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp]),
+    "dk_mmdit_set_control_taps": (_i32, [_vp, _vp, _i32, _f32]),
+    **{"dk_ln_modulate_add_" + el: (_i32, [_vp, _vp, _i32, _f32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
+                                           _i32, _f32, _vp]) for el in ("bf16", "f16")},
     "dk_image_mask_out_f32": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "dk_fill_condition_tokens": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "dk_vae_create": (_i32, [C.POINTER(dk_vae_config), C.POINTER(_vp)]),

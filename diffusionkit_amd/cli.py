@@ -110,6 +110,15 @@ def build_parser(model_versions: Sequence[str]) -> argparse.ArgumentParser:
     p.add_argument("--pag-layers", type=int, nargs="+", default=None, metavar="BLOCK", help="With --pag-scale: the double blocks whose attention is perturbed.")
     p.add_argument("--pag-interval", type=float, nargs=2, default=None, metavar=("START", "STOP"),
                    help="With --pag-scale: step i of n takes the term iff n START < i < n STOP (default: every guided step).")
+    p.add_argument("--controlnet", type=str, default=None, metavar="PATH",
+                   help="An SD3 ControlNet in the layout of diffusers' SD3ControlNetModel (the InstantX SD3-medium Canny / Pose / Tile files; SD3 "
+                        "versions only, not Stable Diffusion 3.5 medium): a .safetensors file. Needs --controlnet-image-path. Not together with "
+                        "--block-cache, --slg-scale, --pag-scale or --fp8. Verified as arithmetic only: the key table has not been run against a real file.")
+    p.add_argument("--controlnet-image-path", type=str, default=None, metavar="IMG",
+                   help="With --controlnet: the prepared control image (edges, pose, ...). Its sides must equal --height / --width: it is not resized.")
+    p.add_argument("--controlnet-scale", type=float, default=None, metavar="S", help="With --controlnet: the scale of the ControlNet's residuals (default 1.0).")
+    p.add_argument("--controlnet-interval", type=float, nargs=2, default=None, metavar=("START", "STOP"),
+                   help="With --controlnet: step i of n is controlled iff i / n >= START and (i + 1) / n <= STOP (default: every step).")
     p.add_argument("--local-ckpt", default=None, type=str, help="Path to the local mmdit checkpoint.")
     p.add_argument("--ckpt", action="append", default=[], metavar="KEY=PATH",
                    help="Further local checkpoint parts (vae_decoder, vae_encoder, clip_l, clip_g, t5, t5_tokenizer, "
@@ -219,11 +228,37 @@ def resolve(args) -> dict:
         opts = _perturbed_attention_options(*pag, mcfg, "FLUX" in args.model_version, cfg, r.get("block_cache"), r.get("reference_image_path"),
                                             r.get("condition"), r.get("skip_layer_guidance"))
         r.update(pag_scale=opts["scale"], pag_layers=opts["layers"], pag_interval=opts["interval"])
+    cn = {k: getattr(args, k, None) for k in ("controlnet", "controlnet_image_path", "controlnet_scale", "controlnet_interval")}
+    if any(v is not None for v in cn.values()):  # (keys only when the flags are given)
+        from .config import MODEL_CONFIG
+        mcfg = r.get("mmdit_config", MODEL_CONFIG[args.model_version])
+        if cn["controlnet"] is None:
+            raise ValueError("--controlnet-image-path / --controlnet-scale / --controlnet-interval need --controlnet")
+        if cn["controlnet_image_path"] is None:
+            raise ValueError("--controlnet needs --controlnet-image-path: the ControlNet was trained to see a control image")
+        if "FLUX" in args.model_version:
+            raise ValueError(f"--controlnet needs an SD3 model version (diffusers' SD3ControlNetModel), not {args.model_version}")
+        if mcfg.dual_attention_blocks > 0:
+            raise ValueError(f"--controlnet cannot run with {args.model_version}: its dual attention blocks have no tap form")
+        if getattr(args, "fp8", None):
+            raise ValueError("--controlnet cannot run together with --fp8")
+        for key, flag in (("block_cache", "--block-cache"), ("skip_layer_guidance", "--slg-scale"), ("pag_scale", "--pag-scale")):
+            if r.get(key) is not None:
+                raise ValueError(f"--controlnet cannot run together with {flag}")
+        if cn["controlnet_interval"] is not None and not cn["controlnet_interval"][0] <= cn["controlnet_interval"][1]:
+            raise ValueError("--controlnet-interval expects START <= STOP")
+        r["controlnet_ckpt"] = cn["controlnet"]
+        r["controlnet_image_path"] = cn["controlnet_image_path"]
+        if cn["controlnet_scale"] is not None:
+            r["controlnet_scale"] = cn["controlnet_scale"]
+        if cn["controlnet_interval"] is not None:
+            r["controlnet_interval"] = tuple(cn["controlnet_interval"])
     return r
 
 
 SKIP_LAYER_KEYS = ("skip_layer_guidance", "skip_layers", "skip_layer_interval")  # keywords of generate_image that ``resolve`` sets together
 PAG_KEYS = ("pag_scale", "pag_layers", "pag_interval")  # the same, perturbed-attention guidance
+CONTROLNET_KEYS = ("controlnet_image_path", "controlnet_scale", "controlnet_interval")  # the same, SD3 ControlNet (the constructor takes controlnet_ckpt)
 # argparse destination -> keyword of generate_image
 GUIDANCE_FLAGS = {"guidance": "guidance", "guidance_rescale": "guidance_rescale", "apg_eta": "apg_eta", "apg_norm_threshold": "apg_norm_threshold",
                   "apg_momentum": "apg_momentum", "guidance_interval": "guidance_interval"}
@@ -248,7 +283,9 @@ def main(argv: Optional[Sequence[str]] = None, pipeline_overrides: Optional[dict
         extra["vae_dtype"] = r["vae_dtype"]
     if "condition" in r:
         extra["condition"] = r["condition"]
-    cond_kw = {key: r[key] for key in ("condition_image_path", "condition_mask_path") if key in r}
+    if "controlnet_ckpt" in r:
+        extra["controlnet_ckpt"] = r["controlnet_ckpt"]
+    cond_kw = {key: r[key] for key in ("condition_image_path", "condition_mask_path", *CONTROLNET_KEYS) if key in r}
     sd = pipeline_class(w16=True, shift=r["shift"], use_t5=args.t5, model_version=args.model_version,
                         low_memory_mode=r["low_memory_mode"], a16=True, local_ckpt=checkpoint_dict(args.local_ckpt, args.ckpt),
                         device=args.device, **extra)

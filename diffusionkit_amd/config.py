@@ -62,6 +62,10 @@ class MMDiTConfig:
     # tokens alone (x_block.attn2), fed by a second modulation of the block's LayerNorm and gated by a ninth adaLN row; SD3 family only
     # (validate_dual_attention)
     dual_attention_blocks: int = 0
+    # SD3 ControlNet (the layout of diffusers' SD3ControlNetModel; no reference counterpart): this configuration is the ControlNet, not a model --
+    # ``depth_multimodal`` joint blocks with their own embedders, a second patch embedder for the control image (pos_embed_input) and one
+    # Linear(h, h) per block (controlnet_blocks), no final layer; SD3 family only (validate_control_net)
+    control_net: bool = False
 
     @property
     def hidden_size(self) -> int:
@@ -101,7 +105,7 @@ class MMDiTConfig:
             skip_txt = (i == self.depth_multimodal - 1) and self.depth_unified < 1
             n += (9 if i < self.dual_attention_blocks else 6) + (2 if skip_txt else 6)
         n += 3 * self.depth_unified
-        n += 2
+        n += 0 if self.control_net else 2  # (a ControlNet has no final layer)
         return n
 
 
@@ -124,6 +128,22 @@ def validate_dual_attention(cfg: MMDiTConfig) -> None:
         raise ValueError(f"dual_attention_blocks = {n}: must lie in [0, depth_multimodal = {cfg.depth_multimodal}]")
     if n > 0 and (cfg.depth_unified != 0 or cfg.weight_dtype == "fp8_e4m3"):
         raise ValueError("dual_attention_blocks needs the SD3 family (MMDiT-X): depth_unified == 0 and no fp8 Linears")
+
+
+# The InstantX SD3-medium ControlNets (Canny / Pose / Tile; diffusers' SD3ControlNetModel): six joint blocks of SD3-medium's width.  The width is
+# the MODEL's (24 * 64), not 64 * depth
+SD3_CONTROLNET_6 = replace(SD3_2b, depth_multimodal=6, hidden_size_override=SD3_2b.hidden_size, control_net=True)
+
+
+def validate_control_net(cfg: MMDiTConfig) -> None:
+    """``control_net`` needs SD3 geometry: the learned positional table, depth_unified == 0, no fp8 Linears, no dual attention blocks, no
+    condition width (the rule dk_mmdit_set_control_net enforces)."""
+    if not cfg.control_net:
+        return
+    if (cfg.pos_embed_type != PositionalEncoding.LearnedInputEmbedding or cfg.depth_unified != 0 or cfg.weight_dtype == "fp8_e4m3"
+            or cfg.dual_attention_blocks != 0 or cfg.condition_features != 0):
+        raise ValueError("control_net needs the SD3 family: the learned positional table, depth_unified == 0, no fp8 Linears, no dual attention "
+                         "blocks and no condition width")
 
 
 # reference config.py:82-95
@@ -243,6 +263,11 @@ def tiny_sd3(depth: int = 2, heads: int = 4, text_dim: int = 256, pooled: int = 
         pooled_text_embed_dim=pooled,
         max_latent_resolution=max_res,
     )
+
+
+def tiny_sd3_controlnet(depth: int = 2, heads: int = 4, text_dim: int = 256, pooled: int = 64, max_res: int = 24) -> MMDiTConfig:
+    """SD3-ControlNet-shaped config for a ``tiny_sd3`` model of the same ``heads`` (the widths must agree: the taps are added to its stream)."""
+    return replace(tiny_sd3(depth, heads, text_dim, pooled, max_res), control_net=True)
 
 
 def tiny_sd35m(depth: int = 3, heads: int = 4, dual: int = 2, text_dim: int = 256, pooled: int = 64, max_res: int = 24) -> MMDiTConfig:

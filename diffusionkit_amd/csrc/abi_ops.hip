@@ -321,6 +321,30 @@ extern "C" int dk_ln_modulate_dual_f16(const void* x, void* out_a, void* out_b, 
                           ldx, ldo, h, mod_stride, x_seg_stride, x_seg_stride1, eps, stream);
 }
 
+static int ln_modulate_add(int dtype, void* x, const void* tap, int ldt, float s, void* out, int M, const void* shift, const void* scale, int seg,
+                           const void* x1, void* out1, int M1, const void* shift1, const void* scale1, int seg1, int ldx, int ldo, int h,
+                           int mod_stride, int x_seg_stride, int x_seg_stride1, float eps, void* stream) {
+  DK_REQUIRE(M > 0 && M1 >= 0 && h > 0, "bad argument");
+  return DK_EL(dtype, dk_launch_ln_modulate2_add)((bf16_t*)x, (const bf16_t*)tap, ldt, s, (bf16_t*)out, M, (const bf16_t*)shift, (const bf16_t*)scale,
+                                                  seg > 0 ? seg : M, (const bf16_t*)x1, (bf16_t*)out1, M1, (const bf16_t*)shift1, (const bf16_t*)scale1,
+                                                  seg1 > 0 ? seg1 : (M1 > 0 ? M1 : 1), ldx, ldo, h, mod_stride, x_seg_stride, x_seg_stride1, eps,
+                                                  S_(stream));
+}
+extern "C" int dk_ln_modulate_add_bf16(void* x, const void* tap, int32_t ldt, float s, void* out, int32_t M, const void* shift, const void* scale,
+                                       int32_t mod_seg_len, const void* x1, void* out1, int32_t M1, const void* shift1, const void* scale1,
+                                       int32_t mod_seg_len1, int32_t ldx, int32_t ldo, int32_t h, int32_t mod_stride, int32_t x_seg_stride,
+                                       int32_t x_seg_stride1, float eps, void* stream) {
+  return ln_modulate_add(DK_DTYPE_BF16, x, tap, ldt, s, out, M, shift, scale, mod_seg_len, x1, out1, M1, shift1, scale1, mod_seg_len1, ldx, ldo, h,
+                         mod_stride, x_seg_stride, x_seg_stride1, eps, stream);
+}
+extern "C" int dk_ln_modulate_add_f16(void* x, const void* tap, int32_t ldt, float s, void* out, int32_t M, const void* shift, const void* scale,
+                                      int32_t mod_seg_len, const void* x1, void* out1, int32_t M1, const void* shift1, const void* scale1,
+                                      int32_t mod_seg_len1, int32_t ldx, int32_t ldo, int32_t h, int32_t mod_stride, int32_t x_seg_stride,
+                                      int32_t x_seg_stride1, float eps, void* stream) {
+  return ln_modulate_add(DK_DTYPE_F16, x, tap, ldt, s, out, M, shift, scale, mod_seg_len, x1, out1, M1, shift1, scale1, mod_seg_len1, ldx, ldo, h,
+                         mod_stride, x_seg_stride, x_seg_stride1, eps, stream);
+}
+
 static int block_probe(int dtype, const void* x, int ldx, int x_seg_len, int x_seg_stride, void* d, const void* d_ref, float* row_partials,
                        float* probe, int M, int h, int rows_per_batch, void* stream) {
   return DK_EL(dtype, dk_launch_block_probe)((const bf16_t*)x, ldx, x_seg_len, x_seg_stride, (bf16_t*)d, (const bf16_t*)d_ref, row_partials, probe, M, h,

@@ -23,6 +23,10 @@ int dk_launch_ln_modulate2x(const bf16_t* x0, bf16_t* out0, bf16_t* out0b, int M
                             const bf16_t* shift0b, const bf16_t* scale0b, int seg0, const bf16_t* x1, bf16_t* out1, int M1,
                             const bf16_t* shift1, const bf16_t* scale1, int seg1, int ldx, int ldo, int h, int mod_stride, int x_seg_stride,
                             int x_seg_stride1, float eps, hipStream_t stream);
+// ... or takes a residual first (ControlNet taps): x0 <- round(fmaf(s, tap, x0)) in place (tap: dense [M0, ldt]), out0 from the new rows
+int dk_launch_ln_modulate2_add(bf16_t* x0, const bf16_t* tap, int ldt, float s, bf16_t* out0, int M0, const bf16_t* shift0, const bf16_t* scale0,
+                               int seg0, const bf16_t* x1, bf16_t* out1, int M1, const bf16_t* shift1, const bf16_t* scale1, int seg1, int ldx,
+                               int ldo, int h, int mod_stride, int x_seg_stride, int x_seg_stride1, float eps, hipStream_t stream);
 int dk_launch_qk_norm_rope2(bf16_t* qkv0, int rows0, const bf16_t* qw0, const bf16_t* kw0, int seg0, int pos0, bf16_t* qkv1, int rows1,
                             const bf16_t* qw1, const bf16_t* kw1, int seg1, int pos1, int ld, int q_off, int k_off, int H, int D,
                             float eps, const float* rope, int row_seg_stride, hipStream_t stream, int k_only = 0);

@@ -33,11 +33,24 @@ struct LnJob2 : LnJob {
   const bf16_t *shift2, *scale2;
 };
 static_assert(sizeof(LnJob2) % 8 == 0 && alignof(LnJob2) == 8, "job b follows job a without padding in the kernarg segment");
-template <bool DUAL> struct LnJobOf { typedef LnJob type; };
-template <> struct LnJobOf<true> { typedef LnJob2 type; };
-template <int NCH, bool DUAL = false>
-__global__ __launch_bounds__(256) void dk_ln_modulate_kernel(typename LnJobOf<DUAL>::type ja, typename LnJobOf<DUAL>::type jb, int blocks_a, int h, float eps) {
-  typedef typename LnJobOf<DUAL>::type Job;
+// ADD (ControlNet residuals, dk_mmdit_set_control_taps): a job carries a tap t, [M, ldt] dense rows in the element type, and an fp32 scalar s.  Row
+// m becomes x' = round( fmaf(s, t[m], x) ) -- fp32, one rounding to the element type -- BEFORE anything else: the tap chunks are loaded in the
+// row's round trip, x' goes back over x through the row's own resource, and the two reductions and the modulated store run on x' from the
+// same registers.  A job without a tap (the text stream riding in the same launch) has t null: a tap resource of zero bytes, and the add
+// and the write-back are skipped on a wave-uniform test.  The plain and the DUAL instantiations do not see any of this.
+struct LnJobT : LnJob {
+  const bf16_t* t;
+  float s;
+  int ldt;
+};
+static_assert(sizeof(LnJobT) % 8 == 0 && alignof(LnJobT) == 8, "job b follows job a without padding in the kernarg segment");
+template <bool DUAL, bool ADD = false> struct LnJobOf { typedef LnJob type; };
+template <> struct LnJobOf<true, false> { typedef LnJob2 type; };
+template <> struct LnJobOf<false, true> { typedef LnJobT type; };
+template <int NCH, bool DUAL = false, bool ADD = false>
+__global__ __launch_bounds__(256) void dk_ln_modulate_kernel(typename LnJobOf<DUAL, ADD>::type ja, typename LnJobOf<DUAL, ADD>::type jb, int blocks_a, int h, float eps) {
+  static_assert(!(DUAL && ADD), "one of the two cases at a time");
+  typedef typename LnJobOf<DUAL, ADD>::type Job;
   const bool first = (int)blockIdx.x < blocks_a;
   // one scalar base pointer into the kernarg segment (`first ? ja : jb` copies both jobs to scratch, see gemm256v3.hip)
   typedef const __attribute__((address_space(4))) Job karg_job_t;
@@ -56,6 +69,18 @@ __global__ __launch_bounds__(256) void dk_ln_modulate_kernel(typename LnJobOf<DU
   u32x4 raw[NCH], rs[NCH], rc[NCH];
 #pragma unroll
   for (int i = 0; i < NCH; ++i) raw[i] = __builtin_amdgcn_raw_buffer_load_b128(rx, (lane + 64 * i) * 16, 0, 0);
+  // the tap (ADD): its loads follow the row's, ahead of shift / scale -- the add needs only these two; a plain kernel keeps one register
+  constexpr int NCHT = ADD ? NCH : 1;
+  u32x4 rt[NCHT];
+  bool tapped = false;
+  if constexpr (ADD) {
+    tapped = j.t != nullptr;
+    // (a job without a tap: a resource of zero bytes at the row -- every lane reads zeros)
+    const __amdgpu_buffer_rsrc_t rtap =
+        __builtin_amdgcn_make_buffer_rsrc((void*)(tapped ? j.t + (size_t)m * j.ldt : j.x + xrow), 0, tapped ? h * 2 : 0, 0x00020000);
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) rt[i] = __builtin_amdgcn_raw_buffer_load_b128(rtap, (lane + 64 * i) * 16, 0, 0);
+  }
 #pragma unroll
   for (int i = 0; i < NCH; ++i) {
     rs[i] = __builtin_amdgcn_raw_buffer_load_b128(rsh, (lane + 64 * i) * 16, 0, 0);
@@ -79,6 +104,23 @@ __global__ __launch_bounds__(256) void dk_ln_modulate_kernel(typename LnJobOf<DU
     }
   }
   __builtin_amdgcn_sched_barrier(0);  // (without it the scheduler sinks the shift / scale loads below the two reductions)
+  if constexpr (ADD) {
+    if (tapped) {  // (wave-uniform)
+      const float s = j.s;
+#pragma unroll
+      for (int i = 0; i < NCH; ++i) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float v0, v1, t0, t1;
+          unpack2(raw[i][e], v0, v1);
+          unpack2(rt[i][e], t0, t1);
+          raw[i][e] = pack2(__builtin_fmaf(s, t0, v0), __builtin_fmaf(s, t1, v1));  // (zeros past the row end stay zeros)
+        }
+        __builtin_amdgcn_raw_buffer_store_b128(raw[i], rx, (lane + 64 * i) * 16, 0, 0);  // (past the row end: dropped)
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
   float sum = 0.f;
 #pragma unroll
   for (int i = 0; i < NCH; ++i) {
@@ -211,6 +253,45 @@ int dk_launch_ln_modulate2x(const bf16_t* x0, bf16_t* out0, bf16_t* out0b, int M
                          : ln_job(nullptr, 8, nullptr, 8, 0, nullptr, nullptr, 8, 1, 1, 0);
   return launch_ln_jobs_dual(ln_job2(ln_job(x0, ldx, out0, ldo, M0, shift0, scale0, mod_stride, seg0, seg0, x_seg_stride), out0b, shift0b, scale0b),
                              ln_job2(b, nullptr, nullptr, nullptr), h, eps, stream);
+}
+// the ADD instantiations: job a with its tap, job b plain (M == 0: absent)
+static int launch_ln_jobs_add(const LnJobT& a, const LnJobT& b, int h, float eps, hipStream_t stream) {
+  DK_REQUIRE(h % 8 == 0 && h <= 4096, "hidden size must be a multiple of 8 and <= 4096");
+  for (const LnJobT* j : {&a, &b})
+    DK_REQUIRE(j->M == 0 || (j->ldx % 8 == 0 && j->ldo % 8 == 0 && j->mod_stride % 8 == 0), "strides must keep 16-byte alignment");
+  const int blocks_a = (a.M + 3) / 4, blocks_b = (b.M + 3) / 4;
+  dim3 grid(blocks_a + blocks_b), block(256);
+  const int nch = (h / 8 + 63) / 64;
+#define LN_CASE(N)                                                                                                      \
+  case N:                                                                                                               \
+    hipLaunchKernelGGL((dk_ln_modulate_kernel<N, false, true>), grid, block, 0, stream, a, b, blocks_a, h, eps);        \
+    break;
+  switch (nch) {
+    LN_CASE(1) LN_CASE(2) LN_CASE(3) LN_CASE(4) LN_CASE(5) LN_CASE(6) LN_CASE(7) LN_CASE(8)
+    default: DK_REQUIRE(false, "unsupported hidden size");
+  }
+#undef LN_CASE
+  DK_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+static LnJobT ln_job_tap(const LnJob& j, const bf16_t* t, int ldt, float s) {
+  LnJobT d;
+  static_cast<LnJob&>(d) = j;
+  d.t = t; d.s = t ? s : 0.f; d.ldt = t ? ldt : 8;
+  return d;
+}
+// ... of which the first takes a residual first (ControlNet taps): x0 <- round(x0 + s * tap) in place, row m of the dense [M0, ldt] tap onto
+// logical row m of x0, and out0 is the modulated LayerNorm of the new rows; the second row set is plain (M1 == 0: none)
+int dk_launch_ln_modulate2_add(bf16_t* x0, const bf16_t* tap, int ldt, float s, bf16_t* out0, int M0, const bf16_t* shift0, const bf16_t* scale0,
+                               int seg0, const bf16_t* x1, bf16_t* out1, int M1, const bf16_t* shift1, const bf16_t* scale1, int seg1, int ldx,
+                               int ldo, int h, int mod_stride, int x_seg_stride, int x_seg_stride1, float eps, hipStream_t stream) {
+  DK_REQUIRE(x0 && tap && out0 && shift0 && scale0 && M0 > 0 && seg0 > 0, "ln_modulate2_add: the first row set needs its tap");
+  DK_REQUIRE(ldt >= h && ldt % 8 == 0 && ((uintptr_t)tap & 15) == 0, "ln_modulate2_add: the tap's rows must be 16-byte aligned and hold h elements");
+  DK_REQUIRE(M1 == 0 || (x1 && out1 && shift1 && scale1 && seg1 > 0), "ln_modulate2_add: bad second row set");
+  const LnJob b = M1 > 0 ? ln_job(x1, ldx, out1, ldo, M1, shift1, scale1, mod_stride, seg1, seg1, x_seg_stride1)
+                         : ln_job(nullptr, 8, nullptr, 8, 0, nullptr, nullptr, 8, 1, 1, 0);
+  return launch_ln_jobs_add(ln_job_tap(ln_job(x0, ldx, out0, ldo, M0, shift0, scale0, mod_stride, seg0, seg0, x_seg_stride), tap, ldt, s),
+                            ln_job_tap(b, nullptr, 0, 0.f), h, eps, stream);
 }
 // two row sets (image / text stream) of the same hidden size in one launch
 int dk_launch_ln_modulate2(const bf16_t* x0, bf16_t* out0, int M0, const bf16_t* shift0, const bf16_t* scale0, int seg0, const bf16_t* x1,

@@ -108,6 +108,17 @@ struct dk_mmdit {
   bf16_t *BC_R = nullptr, *BC_D[2] = {nullptr, nullptr};
   float* BC_ROWS = nullptr;
   void bc_reset() { bc_valid = false; bc_pending = -1; }
+  // SD3 ControlNet (include/dk_hip.h).  control_net (dk_mmdit_set_control_net): this engine IS the ControlNet -- no final layer, a second
+  // patch embedder whose step-invariant share POS + pos_embed_input(control tokens) sits in CONDE (dk_mmdit_cache_control_image), one tap
+  // Linear per block.  taps (dk_mmdit_set_control_taps): this engine is the MAIN model and adds tap_scale * taps[tap_of(g)] behind block g
+  bool control_net = false, ctrl_ready = false;
+  const bf16_t *cin_w = nullptr, *cin_b = nullptr;
+  std::vector<const bf16_t*> tap_w, tap_b;
+  const bf16_t* taps = nullptr;  // [n_taps, B, S_i, h], the caller's
+  int n_taps = 0;
+  float tap_scale = 0.f;
+  bool tapped() const { return n_taps > 0; }
+  int tap_of(int g) const { return (int)((long)g * n_taps / cfg.depth_multimodal); }
   // what a call on `stream` hands its launches: this engine's element type and ITS regions (for D = 64 no attention region: unsplit launches)
   LaunchCtx ctx(void* stream) const { return LaunchCtx{S_(stream), dtype, GWS, AttnWs{AWS, AWS_bytes}}; }
   bool fp8() const { return cfg.fp8_linears != 0; }
@@ -128,7 +139,7 @@ struct dk_mmdit {
   int mod_rows() const {
     int n = 0;
     for (int i = 0; i < cfg.depth_multimodal; ++i) n += img_rows(i) + (txt_skipped(i) ? 2 : 6);
-    return n + 3 * cfg.depth_unified + 2;
+    return n + 3 * cfg.depth_unified + (control_net ? 0 : 2);  // (a control-net engine has no final layer, and no rows for one)
   }
   int mod_offset(int kind, int index) const {
     int n = 0;
@@ -189,9 +200,11 @@ extern "C" int dk_mmdit_set_dual_attention(dk_mmdit* m, int32_t n_blocks) {
   DK_REQUIRE(m != nullptr, "null handle");
   DK_REQUIRE(!m->resolved && !m->prepared, "dk_mmdit_set_dual_attention is legal only before the weights are resolved (the first dk_mmdit_prepare)");
   DK_REQUIRE(n_blocks >= 0 && n_blocks <= m->cfg.depth_multimodal, "dual attention blocks must lie in [0, depth_multimodal]");
-  if (n_blocks > 0)
+  if (n_blocks > 0) {
     DK_REQUIRE(m->cfg.depth_unified == 0 && m->cfg.fp8_linears == 0,
                "dual attention blocks are the SD3 family's (MMDiT-X): depth_unified == 0 and fp8_linears == 0");
+    DK_REQUIRE(!m->control_net && !m->tapped(), "dual attention blocks cannot be set on a control-net engine or while control taps are set");
+  }
   m->n_dual = n_blocks;
   m->mod_ready = false;
   return 0;
@@ -292,8 +305,18 @@ static int mmdit_resolve(dk_mmdit* m) {
   DK_TRY(need(n, "t_embedder.mlp.layers.2.bias", &m->t2_b));
   DK_TRY(need(n, "adaLN.weight", &m->adaln_w));
   DK_TRY(need(n, "adaLN.bias", &m->adaln_b));
-  DK_TRY(need(n, "final_layer.linear.weight", &m->final_w));
-  DK_TRY(need(n, "final_layer.linear.bias", &m->final_b));
+  DK_TRY(need(n, "final_layer.linear.weight", &m->final_w, m->control_net));
+  DK_TRY(need(n, "final_layer.linear.bias", &m->final_b, m->control_net));
+  if (m->control_net) {
+    DK_TRY(need(n, "pos_embed_input.proj.weight", &m->cin_w));
+    DK_TRY(need(n, "pos_embed_input.proj.bias", &m->cin_b));
+    m->tap_w.assign(m->cfg.depth_multimodal, nullptr);
+    m->tap_b.assign(m->cfg.depth_multimodal, nullptr);
+    for (int i = 0; i < m->cfg.depth_multimodal; ++i) {
+      DK_TRY(need(n, "controlnet_blocks." + std::to_string(i) + ".weight", &m->tap_w[i]));
+      DK_TRY(need(n, "controlnet_blocks." + std::to_string(i) + ".bias", &m->tap_b[i]));
+    }
+  }
   if (m->cfg.guidance_embed) {
     DK_TRY(need(n, "guidance_in.mlp.layers.0.weight", &m->g0_w));
     DK_TRY(need(n, "guidance_in.mlp.layers.0.bias", &m->g0_b));
@@ -381,7 +404,7 @@ static size_t mmdit_carve(dk_mmdit* m, Carver& c, int B, int Hl, int Wl, int S_t
   m->REFE = nullptr;
   if (S_r > 0) m->REFE = (bf16_t*)c.take((size_t)B * S_r * h * 2);  // (behind everything else, and no take at all without a reference)
   m->CONDE = nullptr;
-  if (m->cond_f > 0) m->CONDE = (bf16_t*)c.take((size_t)B * S_i * h * 2);  // (the same: no take with the width off)
+  if (m->cond_f > 0 || m->control_net) m->CONDE = (bf16_t*)c.take((size_t)B * S_i * h * 2);  // (the same: no take with both off)
   m->XN2 = m->QKV2 = m->ATT2 = nullptr;
   if (m->n_dual > 0) {  // (the same: no take without dual blocks)
     const size_t Mi = (size_t)B * S_x;
@@ -435,6 +458,8 @@ extern "C" int dk_mmdit_prepare(dk_mmdit* m, int32_t batch, int32_t latent_h, in
   m->ctx_ready = false;
   m->ref_ready = false;
   m->cond_ready = false;
+  m->ctrl_ready = false;
+  m->taps = nullptr; m->n_taps = 0; m->tap_scale = 0.f;  // (the caller's taps had the previous problem's shape: set again after prepare)
   m->bc_reset();
   return 0;
 }
@@ -445,6 +470,7 @@ extern "C" int dk_mmdit_set_reference_grid(dk_mmdit* m, int32_t ref_latent_h, in
   if (ref_latent_h != 0 || ref_latent_w != 0) {
     const int p = m->cfg.patch_size;
     DK_REQUIRE(m->cond_f == 0, "a reference grid and a condition width cannot be set at the same time");
+    DK_REQUIRE(!m->control_net && !m->tapped(), "a reference grid cannot be set on a control-net engine or while control taps are set");
     DK_REQUIRE(m->cfg.use_rope, "a reference grid needs RoPE (use_rope = 1, the FLUX family): the reference rows are told from the image rows by their position index");
     DK_REQUIRE(ref_latent_h > 0 && ref_latent_w > 0 && ref_latent_h % p == 0 && ref_latent_w % p == 0,
                "reference latent sides must both be positive multiples of the patch size, or both 0 (off)");
@@ -484,6 +510,7 @@ extern "C" int dk_mmdit_set_condition_width(dk_mmdit* m, int32_t cond_features) 
     DK_REQUIRE(m->cfg.use_pos_embed == 0, "a condition width needs use_pos_embed == 0 (the FLUX family): the residual operand of the x_embedder launch carries the condition's share");
     DK_REQUIRE(m->ref_h == 0 && m->ref_w == 0, "a condition width and a reference grid cannot be set at the same time");
     DK_REQUIRE(m->dtype == DK_DTYPE_BF16, "a condition width needs bf16 activations");
+    DK_REQUIRE(!m->control_net && !m->tapped(), "a condition width cannot be set on a control-net engine or while control taps are set");
   }
   if (m->cond_f != cond_features) m->prepared = false;  // (another carve: dk_mmdit_prepare must follow)
   m->cond_f = cond_features;
@@ -648,6 +675,12 @@ static int double_block_bf16(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t
   if (dual)
     DK_TRY(DK_EL(L.dtype, dk_launch_ln_modulate2x)(X_img.p, XN_img.p, m->XN2, Mi, mod_img, mod_img + h, mod_img + 6 * h, mod_img + 7 * h, S_i, X_txt.p,
                                                    XN_txt.p, Mt, mod_txt, mod_txt + h, S_t, h, h, h, mod_stride, S, S, cf.layer_norm_eps, st));
+  else if (m->tapped() && i > 0)
+    // ControlNet taps (dk_mmdit_set_control_taps): the residual behind block i - 1 is added here, in front of block i -- the same stream state --
+    // in the pass that reads every image row anyway; the image rows are rewritten in place, the text job is the plain one
+    DK_TRY(DK_EL(L.dtype, dk_launch_ln_modulate2_add)(X_img.p, m->taps + (size_t)m->tap_of(i - 1) * Mi * h, h, m->tap_scale, XN_img.p, Mi, mod_img,
+                                                      mod_img + h, S_i, X_txt.p, XN_txt.p, Mt, mod_txt, mod_txt + h, S_t, h, h, h, mod_stride, S, S,
+                                                      cf.layer_norm_eps, st));
   else
     DK_TRY(DK_EL(L.dtype, dk_launch_ln_modulate2)(X_img.p, XN_img.p, Mi, mod_img, mod_img + h, S_i, X_txt.p, XN_txt.p, Mt, mod_txt, mod_txt + h, S_t, h, h, h,
                                                   mod_stride, S, cf.layer_norm_eps, st));
@@ -909,8 +942,10 @@ static int mmdit_embed(dk_mmdit* m, const void* tokens_in, const void* text, con
   // (no split workspace; the positional rows repeat per image: one segment of S_i rows, stride 0)
   // (with a condition width: the latent columns of the [h, F + cond_f] weight, and the condition's step-invariant share, CONDE, in the
   // residual slot the positional table leaves free -- one segment per batch row)
+  // (a control-net engine: CONDE = POS + pos_embed_input(control tokens) in the slot of POS -- x_embedder's own [h, F] weight, pitch F)
   const bool cond = m->cond_f > 0;
-  const Rows res = cond ? Rows{m->CONDE, h, S_i, S_i} : Rows{c.use_pos_embed ? m->POS : nullptr, h, S_i, 0};
+  DK_REQUIRE(!m->control_net || m->ctrl_ready, "a control-net engine needs dk_mmdit_cache_control_image after dk_mmdit_prepare");
+  const Rows res = cond || m->control_net ? Rows{m->CONDE, h, S_i, S_i} : Rows{c.use_pos_embed ? m->POS : nullptr, h, S_i, 0};
   DK_TRY(dk_launch_gemm(Linear(L.dtype, dense((const bf16_t*)tokens_in, F), m->xemb_w, m->xemb_b, m->own(m->X, h), B * S_i, h, F,
                                cond || c.use_pos_embed ? DK_EPI_RES : DK_EPI_BIAS, cond ? F + m->cond_f : 0)
                             .gate_res(nullptr, 0, 0, res),
@@ -937,6 +972,7 @@ extern "C" int dk_mmdit_set_skip_layers(dk_mmdit* m, const int32_t* blocks, int3
   DK_REQUIRE(m->cfg.fp8_linears == 0, "skip layers cannot be set on an engine with fp8_linears");
   DK_REQUIRE(m->ref_h == 0 && m->ref_w == 0 && m->cond_f == 0, "skip layers cannot be set while a reference grid or a condition width is set");
   DK_REQUIRE(!m->perturbed(), "skip layers cannot be set while perturbed attention is set (dk_mmdit_set_perturbed_attention): there is one fork");
+  DK_REQUIRE(!m->control_net && !m->tapped(), "skip layers cannot be set on a control-net engine or while control taps are set: the fork rows would need taps of their own");
   std::vector<int32_t> v(blocks, blocks + n_blocks);
   std::sort(v.begin(), v.end());
   DK_REQUIRE(v.front() >= 0 && v.back() < m->cfg.depth_multimodal, "skip layers: every block must lie in [0, depth_multimodal)");
@@ -959,6 +995,7 @@ extern "C" int dk_mmdit_set_perturbed_attention(dk_mmdit* m, const int32_t* bloc
   DK_REQUIRE(m->cfg.fp8_linears == 0, "perturbed attention cannot be set on an engine with fp8_linears");
   DK_REQUIRE(m->ref_h == 0 && m->ref_w == 0 && m->cond_f == 0, "perturbed attention cannot be set while a reference grid or a condition width is set");
   DK_REQUIRE(!m->slg(), "perturbed attention cannot be set while skip layers are set (dk_mmdit_set_skip_layers): there is one fork");
+  DK_REQUIRE(!m->control_net && !m->tapped(), "perturbed attention cannot be set on a control-net engine or while control taps are set: the fork rows would need taps of their own");
   std::vector<int32_t> v(blocks, blocks + n_blocks);
   std::sort(v.begin(), v.end());
   DK_REQUIRE(v.front() >= 0 && v.back() < m->cfg.depth_multimodal, "perturbed attention: every block must lie in [0, depth_multimodal)");
@@ -974,6 +1011,89 @@ static int no_skip_layers(const dk_mmdit* m, const char* entry) {
                ": only dk_mmdit_forward forks the row group");
   return -1;
 }
+
+// ---- SD3 ControlNet (include/dk_hip.h) --------------------------------------------------------------------------------------------------
+static bool sd3_geometry(const dk_mmdit* m) { return m->cfg.use_pos_embed != 0 && m->cfg.depth_unified == 0 && m->cfg.fp8_linears == 0; }
+extern "C" int dk_mmdit_set_control_net(dk_mmdit* m, int32_t on) {
+  DK_REQUIRE(m != nullptr, "null handle");
+  DK_REQUIRE(m->named.empty() && !m->prepared, "dk_mmdit_set_control_net must precede the first dk_mmdit_bind");
+  if (on) {
+    DK_REQUIRE(sd3_geometry(m), "a control-net engine is the SD3 family's: use_pos_embed != 0, depth_unified == 0 and fp8_linears == 0");
+    DK_REQUIRE(m->n_dual == 0 && m->ref_h == 0 && m->ref_w == 0 && m->cond_f == 0,
+               "a control-net engine cannot have dual attention blocks, a reference grid or a condition width");
+    DK_REQUIRE(!m->bc_on && !m->slg() && !m->perturbed() && !m->tapped(),
+               "a control-net engine cannot have a block cache, skip layers, perturbed attention or control taps of its own");
+  }
+  m->control_net = on != 0;
+  m->ctrl_ready = false;
+  return 0;
+}
+extern "C" int dk_mmdit_cache_control_image(dk_mmdit* m, const void* ctrl_tokens, int32_t per_image, void* stream) {
+  DK_REQUIRE(m && m->prepared && ctrl_tokens, "prepare must precede cache_control_image");
+  DK_REQUIRE(m->control_net, "cache_control_image needs a control-net engine: dk_mmdit_set_control_net before the first dk_mmdit_bind");
+  const int h = m->h(), F = m->F(), S_i = m->S_i;
+  // pos_embed_input as x_embedder in mmdit_embed (no split workspace) with the positional rows as residual, one launch per batch row: a shared
+  // control image gives every batch row the bits a per-image copy of it would
+  for (int b = 0; b < m->B; ++b) {
+    const bf16_t* src = (const bf16_t*)ctrl_tokens + (per_image ? (size_t)b * S_i * F : 0);
+    DK_TRY(dk_launch_gemm(Linear(m->dtype, dense(src, F), m->cin_w, m->cin_b, dense(m->CONDE + (size_t)b * S_i * h, h), S_i, h, F, DK_EPI_RES)
+                              .gate_res(nullptr, 0, 0, Rows{m->POS, h, S_i, 0}),
+                          S_(stream)));
+  }
+  m->ctrl_ready = true;
+  return 0;
+}
+extern "C" int dk_mmdit_set_control_taps(dk_mmdit* m, const void* taps, int32_t n_taps, float scale) {
+  DK_REQUIRE(m != nullptr, "null handle");
+  if (taps == nullptr || n_taps == 0) {
+    m->taps = nullptr; m->n_taps = 0; m->tap_scale = 0.f;
+    return 0;
+  }
+  DK_REQUIRE(sd3_geometry(m), "control taps are the SD3 family's: use_pos_embed != 0, depth_unified == 0 and fp8_linears == 0");
+  DK_REQUIRE(!m->control_net, "control taps cannot be set on a control-net engine (dk_mmdit_set_control_net): it writes taps, the main engine reads them");
+  DK_REQUIRE(n_taps >= 1 && n_taps <= m->cfg.depth_multimodal, "control taps: n_taps must lie in [1, depth_multimodal]");
+  DK_REQUIRE(((uintptr_t)taps & 15) == 0, "control taps must be 16-byte aligned");
+  DK_REQUIRE(m->n_dual == 0, "control taps cannot be set on an engine with dual attention blocks");
+  DK_REQUIRE(!m->bc_on, "control taps cannot be set while the block cache is on (dk_mmdit_set_block_cache)");
+  DK_REQUIRE(!m->slg() && !m->perturbed(), "control taps cannot be set while skip layers or perturbed attention are set: the fork rows would need taps of their own");
+  DK_REQUIRE(m->ref_h == 0 && m->ref_w == 0 && m->cond_f == 0, "control taps cannot be set while a reference grid or a condition width is set");
+  // diffusers' rule in integers: floor(g n / depth) must be int(g / (depth / n)) in double for every block that takes a tap
+  const int depth = m->cfg.depth_multimodal;
+  const double interval = (double)depth / (double)n_taps;
+  for (int g = 0; g + 1 < depth; ++g)
+    DK_REQUIRE((int)((long)g * n_taps / depth) == (int)((double)g / interval), "control taps: the integer tap index disagrees with int(g / (depth / n_taps))");
+  m->taps = (const bf16_t*)taps; m->n_taps = n_taps; m->tap_scale = scale;
+  return 0;
+}
+// what the entries other than dk_mmdit_forward answer while taps are set, and the forward entries on a control-net engine
+static int no_control_taps(const dk_mmdit* m, const char* entry) {
+  if (!m->tapped()) return 0;
+  dk_set_error(std::string(entry) + " cannot run while control taps are set (dk_mmdit_set_control_taps): only dk_mmdit_forward adds them");
+  return -1;
+}
+static int no_control_net(const dk_mmdit* m, const char* entry) {
+  if (!m->control_net) return 0;
+  dk_set_error(std::string(entry) + " cannot run on a control-net engine (dk_mmdit_set_control_net): it has no final layer, use dk_mmdit_control_forward");
+  return -1;
+}
+extern "C" int dk_mmdit_control_forward(dk_mmdit* m, const void* tokens_in, const void* text, int32_t step_index, void* taps_out, void* stream) {
+  DK_REQUIRE(m && m->prepared && m->mod_ready, "prepare + cache_modulation_params must precede control_forward");
+  DK_REQUIRE(m->control_net, "control_forward needs a control-net engine: dk_mmdit_set_control_net before the first dk_mmdit_bind");
+  DK_REQUIRE(tokens_in && taps_out, "null argument");
+  DK_REQUIRE(step_index >= 0 && step_index < m->n_t, "step index out of range");
+  const LaunchCtx L = m->ctx(stream);
+  const int h = m->h(), Mi = m->B * m->S_i;
+  const bf16_t* mod_step = m->MOD + (size_t)step_index * m->B * m->mod_rows() * h;
+  DK_TRY(mmdit_embed(m, tokens_in, text, L, 0));
+  for (int j = 0; j < m->cfg.depth_multimodal; ++j) {
+    DK_TRY(mmdit_blocks(m, mod_step, j, 1, L));
+    // taps_out[j] = controlnet_blocks.j(image rows): the segmented rows of the stream in, dense [B S_i, h] out
+    DK_TRY(dk_launch_gemm(Linear(L.dtype, m->own(m->X, h), m->tap_w[j], m->tap_b[j], dense((bf16_t*)taps_out + (size_t)j * Mi * h, h), Mi, h, h, DK_EPI_BIAS)
+                              .split_ws(L.kws), L.st));
+  }
+  return 0;
+}
+
 // The fork of both features: rows [0, live) alone up to block `first`, there the fork rows become a copy of rows [0, fork_rows), and from there on
 // block g runs on the rows [0, rows_of(g)) -- each group of launches is the driver's for its row count
 template <class RowsOf>
@@ -1012,6 +1132,7 @@ extern "C" int dk_mmdit_forward(dk_mmdit* m, const void* tokens_in, const void* 
   DK_REQUIRE(step_index >= 0 && step_index < m->n_t, "step index out of range");
   const LaunchCtx L = m->ctx(stream);
   const bf16_t* mod_step = m->MOD + (size_t)step_index * m->B * m->mod_rows() * m->h();
+  DK_TRY(no_control_net(m, "dk_mmdit_forward"));
   m->bc_pending = -1;  // (a head without its tail is dropped: this call overwrites the stream it left; R / D_ref stay)
   if (m->slg()) return mmdit_forward_forked(m, tokens_in, text, mod_step, (bf16_t*)tokens_out, L);
   if (m->perturbed()) return mmdit_forward_perturbed(m, tokens_in, text, mod_step, (bf16_t*)tokens_out, L);
@@ -1023,6 +1144,7 @@ extern "C" int dk_mmdit_forward(dk_mmdit* m, const void* tokens_in, const void* 
 // ---- first-block cache (include/dk_hip.h) -----------------------------------------------------------------------------------------
 extern "C" int dk_mmdit_set_block_cache(dk_mmdit* m, int32_t on) {
   DK_REQUIRE(m != nullptr, "null handle");
+  if (on) DK_REQUIRE(!m->control_net && !m->tapped(), "the block cache cannot be switched on on a control-net engine or while control taps are set");
   if (m->bc_on != (on != 0)) m->prepared = false;  // (another carve: dk_mmdit_prepare must follow)
   m->bc_on = on != 0;
   m->bc_reset();
@@ -1044,6 +1166,8 @@ extern "C" int dk_mmdit_forward_head(dk_mmdit* m, const void* tokens_in, const v
   DK_REQUIRE(m->bc_on, "forward_head needs the block cache: dk_mmdit_set_block_cache(m, 1) before dk_mmdit_prepare");
   DK_REQUIRE(probe_out != nullptr, "null argument");
   DK_TRY(no_skip_layers(m, "dk_mmdit_forward_head"));
+  DK_TRY(no_control_net(m, "dk_mmdit_forward_head"));
+  DK_TRY(no_control_taps(m, "dk_mmdit_forward_head"));
   DK_REQUIRE(step_index >= 0 && step_index < m->n_t, "step index out of range");
   const LaunchCtx L = m->ctx(stream);
   const int h = m->h();
@@ -1062,6 +1186,8 @@ extern "C" int dk_mmdit_forward_tail(dk_mmdit* m, int32_t step_index, int32_t re
   DK_REQUIRE(m && m->prepared && m->mod_ready, "prepare + cache_modulation_params must precede forward_tail");
   DK_REQUIRE(m->bc_on && tokens_out != nullptr, "forward_tail needs the block cache and an output");
   DK_TRY(no_skip_layers(m, "dk_mmdit_forward_tail"));
+  DK_TRY(no_control_net(m, "dk_mmdit_forward_tail"));
+  DK_TRY(no_control_taps(m, "dk_mmdit_forward_tail"));
   DK_REQUIRE(m->bc_pending >= 0, "forward_tail needs a pending head: dk_mmdit_forward_head of this step must run first");
   DK_REQUIRE(m->bc_pending == step_index, "forward_tail must be of the same step as the pending head");
   if (reuse) DK_REQUIRE(m->bc_valid, "forward_tail(reuse = 1) needs a valid cache: a computed step since the last prepare / cache_modulation_params / reset");
@@ -1090,6 +1216,7 @@ extern "C" int dk_mmdit_run_blocks(dk_mmdit* m, const void* x_in, void* x_out, i
   DK_REQUIRE(m && m->prepared && m->mod_ready, "prepare + cache_modulation_params must precede run_blocks");
   DK_REQUIRE(x_in && x_out, "null argument");
   DK_TRY(no_skip_layers(m, "dk_mmdit_run_blocks"));
+  DK_TRY(no_control_taps(m, "dk_mmdit_run_blocks"));
   DK_REQUIRE(step_index >= 0 && step_index < m->n_t, "step index out of range");
   const int total = m->cfg.depth_multimodal + m->cfg.depth_unified;
   DK_REQUIRE(first_block >= 0 && n_blocks >= 1 && first_block + n_blocks <= total, "block range outside the model");

@@ -106,6 +106,23 @@ class MMDiTEngine:
             raise _lib.DkHipError(str(e)) from None
         if config.dual_attention_blocks:
             _lib.check(self.lib.dk_mmdit_set_dual_attention(self._h, int(config.dual_attention_blocks)), "dk_mmdit_set_dual_attention")
+        # SD3 ControlNet: this engine is the ControlNet (no final layer, a second patch embedder, one tap Linear per block); set before the first bind
+        from .config import validate_control_net
+        try:
+            validate_control_net(config)
+        except ValueError as e:
+            raise _lib.DkHipError(str(e)) from None
+        self.control_net = bool(config.control_net)
+        if self.control_net:
+            _lib.check(self.lib.dk_mmdit_set_control_net(self._h, 1), "dk_mmdit_set_control_net")
+            for name, cols in [("pos_embed_input.proj.weight", config.patch_dim)] + [(f"controlnet_blocks.{i}.weight", config.hidden_size)
+                                                                                      for i in range(config.depth_multimodal)]:
+                t = packed_weights.get(name)  # (dk_mmdit_bind sees bare pointers: the shapes are checked here)
+                if t is None or tuple(t.shape) != (config.hidden_size, cols):
+                    raise _lib.DkHipError(f"{name}: a control-net engine needs a [{config.hidden_size}, {cols}] tensor, got "
+                                          f"{None if t is None else tuple(t.shape)}")
+        self._ctrl_cached = False
+        self.control_taps = None  # ``set_control_taps``: (taps tensor, scale), kept alive while the engine reads it; None: off
         self.weights = packed_weights  # keep the device tensors alive
         for name, t in packed_weights.items():
             want = torch.uint8 if name.endswith(".weight_fp8") else torch.float32 if name.endswith(".wscale") else self.dtype
@@ -188,6 +205,8 @@ class MMDiTEngine:
         self._ctx_cached = False
         self._ref_cached = False
         self._cond_cached = False
+        self._ctrl_cached = False
+        self.control_taps = None  # (dk_mmdit_prepare switches taps off: their shape was the previous problem's)
 
     @property
     def batch(self):
@@ -268,6 +287,65 @@ class MMDiTEngine:
             raise _lib.DkHipError(f"condition tokens shape {tuple(tokens.shape)} != {want}")
         _lib.check(self.lib.dk_mmdit_cache_condition(self._h, tokens.data_ptr(), int(bool(per_image)), _stream()), "dk_mmdit_cache_condition")
         self._cond_cached = True
+
+    # -- SD3 ControlNet (include/dk_hip.h; no reference counterpart) ---------------------------------------------------------
+    def taps_shape(self):
+        """[N_c, batch, S_i, h]: what ``control_forward`` of this (control-net) engine writes."""
+        b, s_i, _ = self.tokens_shape()
+        return (self.config.depth_multimodal, b, s_i, self.config.hidden_size)
+
+    def cache_control_image(self, latent_or_tokens: Tensor, per_image: bool = False) -> None:
+        """dk_mmdit_cache_control_image: the VAE-encoded control image, f32 NHWC latent [n, Hl, Wl, C] of the prepared size or its tokens in the
+        engine's dtype [n, S_i, p*p*C]; n = batch with ``per_image``, else 1 (one control image for every batch row).  Its share of the patch
+        embedding (with the positional rows) is computed once here and added in every later ``control_forward``."""
+        if self._shape is None or not self.control_net:
+            raise _lib.DkHipError("cache_control_image() needs a configuration with control_net = True and prepare() first")
+        t = latent_or_tokens
+        if t.dim() == 4:
+            if tuple(t.shape[1:3]) != tuple(self._shape[1:3]):
+                raise _lib.DkHipError(f"control latent {tuple(t.shape[1:3])} != the prepared latent size {tuple(self._shape[1:3])}")
+            t = self.patchify(t.to(torch.float32).contiguous())
+        _require_cuda(t, "control tokens", self.dtype)
+        want = (self._shape[0] if per_image else 1,) + self.tokens_shape()[1:]
+        if tuple(t.shape) != want:
+            raise _lib.DkHipError(f"control tokens shape {tuple(t.shape)} != {want}")
+        _lib.check(self.lib.dk_mmdit_cache_control_image(self._h, t.data_ptr(), int(bool(per_image)), _stream()), "dk_mmdit_cache_control_image")
+        self._ctrl_cached = True
+
+    def control_forward(self, tokens_in: Tensor, text: Optional[Tensor], step_index: int, taps_out: Optional[Tensor] = None) -> Tensor:
+        """dk_mmdit_control_forward: the ControlNet on ``tokens_in`` (the main model's tokens of this evaluation) -> taps [N_c, batch, S_i, h]
+        for the main engine's ``set_control_taps``.  ``text=None`` uses ``cache_context``'s result."""
+        if not self.control_net:
+            raise _lib.DkHipError("control_forward() needs a configuration with control_net = True")
+        self._check_forward_args(tokens_in, text, step_index)
+        if not self._ctrl_cached:
+            raise _lib.DkHipError("control_forward() needs cache_control_image() after prepare()")
+        if taps_out is None:
+            taps_out = torch.empty(self.taps_shape(), dtype=self.dtype, device=tokens_in.device)
+        _require_cuda(taps_out, "taps_out", self.dtype)
+        if tuple(taps_out.shape) != self.taps_shape():
+            raise _lib.DkHipError(f"taps_out shape {tuple(taps_out.shape)} != {self.taps_shape()}")
+        _lib.check(self.lib.dk_mmdit_control_forward(self._h, tokens_in.data_ptr(), None if text is None else text.data_ptr(), step_index,
+                                                     taps_out.data_ptr(), _stream()), "dk_mmdit_control_forward")
+        return taps_out
+
+    def set_control_taps(self, taps: Optional[Tensor] = None, scale: float = 1.0) -> None:
+        """dk_mmdit_set_control_taps on the MAIN engine: every later ``forward_tokens`` adds ``scale * taps[floor(g * n / depth)]`` to the image
+        stream behind block g (g < depth - 1), inside the next block's first LayerNorm launch.  ``taps``: [n, batch, S_i, h] in the engine's
+        dtype, read in stream order at every forward (the caller may rewrite it between forwards); None: off.  Nothing is re-prepared.
+        ``forward_head`` / ``forward_tail`` / ``run_blocks`` are refused while set."""
+        if taps is None:
+            _lib.check(self.lib.dk_mmdit_set_control_taps(self._h, None, 0, 0.0), "dk_mmdit_set_control_taps")
+            self.control_taps = None
+            return
+        if self._shape is None:
+            raise _lib.DkHipError("set_control_taps() needs prepare() first: the taps' shape is the prepared problem's")
+        _require_cuda(taps, "taps", self.dtype)
+        b, s_i, _ = self.tokens_shape()
+        if taps.dim() != 4 or tuple(taps.shape[1:]) != (b, s_i, self.config.hidden_size):
+            raise _lib.DkHipError(f"taps shape {tuple(taps.shape)} != (n, {b}, {s_i}, {self.config.hidden_size})")
+        _lib.check(self.lib.dk_mmdit_set_control_taps(self._h, taps.data_ptr(), int(taps.shape[0]), float(scale)), "dk_mmdit_set_control_taps")
+        self.control_taps = (taps, float(scale))
 
     def forward_tokens(self, tokens_in: Tensor, text: Optional[Tensor], step_index: int, tokens_out: Optional[Tensor] = None) -> Tensor:
         """MMDiT.__call__ between patchify and unpatchify (mmdit.py:188-252).  ``text=None`` uses ``cache_context``'s result."""

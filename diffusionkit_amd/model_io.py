@@ -214,6 +214,87 @@ def sd3_checkpoint_to_reference(sd: StateDict, cfg: MMDiTConfig, prefix: str = "
     return out
 
 
+_CN_TOP = {"context_embedder": "context_embedder",
+           "time_text_embed.timestep_embedder.linear_1": "t_embedder.mlp.layers.0", "time_text_embed.timestep_embedder.linear_2": "t_embedder.mlp.layers.2",
+           "time_text_embed.text_embedder.linear_1": "y_embedder.mlp.layers.0", "time_text_embed.text_embedder.linear_2": "y_embedder.mlp.layers.2"}
+_CN_BLOCK = {"attn.to_q": ("image", "attn.q_proj"), "attn.to_k": ("image", "attn.k_proj"), "attn.to_v": ("image", "attn.v_proj"),
+             "attn.to_out.0": ("image", "attn.o_proj"), "attn.add_q_proj": ("text", "attn.q_proj"), "attn.add_k_proj": ("text", "attn.k_proj"),
+             "attn.add_v_proj": ("text", "attn.v_proj"), "attn.to_add_out": ("text", "attn.o_proj"), "ff.net.0.proj": ("image", "mlp.fc1"),
+             "ff.net.2": ("image", "mlp.fc2"), "ff_context.net.0.proj": ("text", "mlp.fc1"), "ff_context.net.2": ("text", "mlp.fc2"),
+             "norm1.linear": ("image", "adaLN_modulation.layers.1"), "norm1_context.linear": ("text", "adaLN_modulation.layers.1")}
+
+
+def sd3_controlnet_checkpoint_to_reference(sd: StateDict, cfg: MMDiTConfig) -> StateDict:
+    """The layout of diffusers' ``SD3ControlNetModel`` (the InstantX SD3-medium Canny / Pose / Tile files) -> the names of
+    ``weights.synth_mmdit_weights`` for a control-net configuration.  Written from the published model definition, NOT verified against a real
+    file: no checkpoint and no diffusers installation exist where this was developed.
+      pos_embed.proj / pos_embed.pos_embed -> x_embedder.proj (OIHW -> OHWI) / the positional table;  pos_embed_input.proj -> the control image's
+      patch embedder;  time_text_embed.{timestep,text}_embedder.linear_{1,2} -> t_embedder / y_embedder;  context_embedder;
+      transformer_blocks.i.norm1.linear / norm1_context.linear -> the adaLN Linears (6h rows: shift, scale, gate of attention, then of the MLP --
+      the engine's row order);  attn.{to_q,to_k,to_v,to_out.0} / attn.{add_q_proj,add_k_proj,add_v_proj,to_add_out} -> the image / text
+      q, k, v, o projections (the k bias is dropped, as the SD3 loader does);  ff / ff_context .net.{0.proj,2} -> mlp.fc1 / fc2;
+      controlnet_blocks.i -> the tap Linears.
+    The published model runs the last block's text stream through its post-attention half, and nothing reads the result: its to_add_out and
+    ff_context are dropped here and its norm1_context keeps the first 2h rows (shift_msa, scale_msa).
+    Refused: a missing or mis-shaped tensor, an unknown key, pos_embed_input with other than p*p*C input features (extra_conditioning_channels),
+    a file without joint blocks (Stability's SD3.5-large ControlNets: another block form), controlnet_blocks count != block count."""
+    if not getattr(cfg, "control_net", False):
+        raise CheckpointError("sd3_controlnet_checkpoint_to_reference needs a control-net configuration (control_net=True)")
+    h, depth = cfg.hidden_size, cfg.depth_multimodal
+    if not any(k.startswith("transformer_blocks.") and ".attn.add_q_proj." in k for k in sd):
+        raise CheckpointError("no joint blocks (transformer_blocks.N.attn.add_q_proj) in the ControlNet checkpoint: Stability's SD3.5-large ControlNets "
+                              "have a single-stream block form that is not built")
+    n_taps = len({k.split(".")[1] for k in sd if k.startswith("controlnet_blocks.")})
+    n_blocks = len({k.split(".")[1] for k in sd if k.startswith("transformer_blocks.")})
+    if n_taps != n_blocks or n_blocks != depth:
+        raise CheckpointError(f"the ControlNet checkpoint holds {n_blocks} blocks and {n_taps} controlnet_blocks, the configuration {depth} of each")
+    out: StateDict = {}
+    for k0, t in sd.items():
+        if k0 == "pos_embed.pos_embed":
+            out["x_pos_embedder.pos_embed.weight"] = t[0]
+            continue
+        m = re.fullmatch(r"(.+)\.(weight|bias)", k0)
+        if not m:
+            raise CheckpointError(f"unknown SD3 ControlNet checkpoint key: {k0}")
+        stem, leaf = m.group(1), m.group(2)
+        if stem in ("pos_embed.proj", "pos_embed_input.proj"):
+            name = "x_embedder.proj" if stem == "pos_embed.proj" else "pos_embed_input.proj"
+            if leaf == "weight" and (t.dim() != 4 or t.shape[1] != cfg.vae_latent_dim):
+                raise CheckpointError(f"{k0}: shape {tuple(t.shape)}: {cfg.vae_latent_dim} input channels expected (a ControlNet with "
+                                      "extra_conditioning_channels is not supported)")
+            out[f"{name}.{leaf}"] = t.permute(0, 2, 3, 1).contiguous() if leaf == "weight" else t
+        elif stem in _CN_TOP:
+            out[f"{_CN_TOP[stem]}.{leaf}"] = t
+        elif (m2 := re.fullmatch(r"controlnet_blocks\.(\d+)", stem)):
+            out[f"controlnet_blocks.{m2.group(1)}.{leaf}"] = t
+        elif (m2 := re.fullmatch(r"transformer_blocks\.(\d+)\.(.+)", stem)) and m2.group(2) in _CN_BLOCK:
+            i = int(m2.group(1))
+            stream, part = _CN_BLOCK[m2.group(2)]
+            if part == "attn.k_proj" and leaf == "bias":
+                continue  # (softmax is invariant to it: the reference's model has no k bias, quirk Q9)
+            last_txt = stream == "text" and i == depth - 1
+            if last_txt and part in ("attn.o_proj", "mlp.fc1", "mlp.fc2"):
+                continue  # (the last text stream's post-attention half: nothing reads its result)
+            if last_txt and part == "adaLN_modulation.layers.1":
+                if t.shape[0] != 6 * h:
+                    raise CheckpointError(f"{k0}: shape {tuple(t.shape)}: {6 * h} rows expected")
+                t = t[:2 * h]
+            out[f"multimodal_transformer_blocks.{i}.{stream}_transformer_block.{part}.{leaf}"] = t
+        else:
+            raise CheckpointError(f"unknown SD3 ControlNet checkpoint key: {k0}")
+    _check_mmdit_complete(out, cfg)
+    return out
+
+
+def load_controlnet_checkpoint(src, cfg: MMDiTConfig) -> StateDict:
+    """``src``: a dict already in reference names, a state dict in the diffusers SD3ControlNetModel layout, or a .safetensors path of one."""
+    sd = load_safetensors(src) if isinstance(src, str) else dict(src)
+    if any(k.startswith("multimodal_transformer_blocks.") for k in sd):
+        _check_mmdit_complete(sd, cfg)
+        return sd
+    return sd3_controlnet_checkpoint_to_reference(sd, cfg)
+
+
 def _check_mmdit_complete(out: StateDict, cfg: MMDiTConfig) -> None:
     """Every tensor pack_mmdit needs must be present with the right shape (fail loudly, name the key)."""
     from .weights import mmdit_weight_shapes

@@ -389,6 +389,49 @@ def ln_modulate_dual(x: Tensor, shift_a: Tensor, scale_a: Tensor, shift_b: Tenso
     return (out_a, out_b) if x1 is None else (out_a, out_b, out1)
 
 
+def ln_modulate_add(x: Tensor, tap: Tensor, s: float, shift: Tensor, scale: Tensor, text=None, eps: float = 1e-6):
+    """The LayerNorm pass with a residual tap in front (dk_ln_modulate_add_*, the first launch of a main-model block behind a ControlNet tap):
+    x <- round(fmaf(s, tap, x)) IN PLACE, fp32 with one rounding to x's dtype, and out = ``ln_modulate`` of the new rows -- one read of x.
+    x: [B, S, h], contiguous or the row range of a joint buffer (a view ``joint[:, a:b]`` with unit inner stride); tap: [B, S, h] contiguous;
+    shift / scale: [B, h] views of one modulation table.  ``text``: optionally (x1 [B, S1, h], shift1, scale1), a plain second row set of the same
+    row pitch in the same launch, read only.  Returns (x, out) or (x, out, out1)."""
+    lib = _lib.load()
+    name = "dk_ln_modulate_add_" + _elem(x.dtype, "ln_modulate_add")
+    if not x.is_cuda or x.dim() != 3:
+        raise _lib.DkHipError("x must be a [B, S, h] tensor on the GPU; there is no CPU path")
+    B, S, h = x.shape
+    ldx = x.stride(1)
+    if x.stride(2) != 1 or (B > 1 and x.stride(0) % ldx != 0):
+        raise _lib.DkHipError("x must have unit inner stride and a batch stride that is a whole number of rows")
+    _require_cuda(tap, "tap", x.dtype)
+    if tuple(tap.shape) != (B, S, h):
+        raise _lib.DkHipError(f"tap shape {tuple(tap.shape)} != {(B, S, h)}")
+    mods = [("shift", shift), ("scale", scale)]
+    x1 = None
+    if text is not None:
+        x1, shift1, scale1 = text
+        mods += [("text shift", shift1), ("text scale", scale1)]
+    for n, t in mods:
+        if t.dtype != x.dtype or t.stride(0) != shift.stride(0) or tuple(t.shape) != (B, h) or t.stride(1) != 1:
+            raise _lib.DkHipError(f"{n} must be a [{B}, {h}] {x.dtype} view with the row stride of shift")
+    out = torch.empty(B, S, h, dtype=x.dtype, device=x.device)
+    if x1 is not None:
+        if not x1.is_cuda or x1.dtype != x.dtype or x1.dim() != 3 or x1.shape[0] != B or x1.shape[2] != h:
+            raise _lib.DkHipError("text x must be [B, S1, h] in x's dtype on the GPU")
+        if x1.stride(2) != 1 or x1.stride(1) != ldx or (B > 1 and x1.stride(0) % ldx != 0):
+            raise _lib.DkHipError("text x must have x's row pitch, unit inner stride and a batch stride that is a whole number of rows")
+        S1 = x1.shape[1]
+        out1 = torch.empty(B, S1, h, dtype=x.dtype, device=x.device)
+        args1 = (x1.data_ptr(), out1.data_ptr(), B * S1, mods[2][1].data_ptr(), mods[3][1].data_ptr(), S1)
+        xss1 = x1.stride(0) // ldx if B > 1 else S1
+    else:
+        args1, xss1 = (None, None, 0, None, None, 0), 0
+    xss = x.stride(0) // ldx if B > 1 else S
+    _lib.check(getattr(lib, name)(x.data_ptr(), tap.data_ptr(), h, float(s), out.data_ptr(), B * S, shift.data_ptr(), scale.data_ptr(), S, *args1,
+                                  ldx, h, h, shift.stride(0), xss, xss1, eps, _stream()), name)
+    return (x, out) if x1 is None else (x, out, out1)
+
+
 def block_probe(x: Tensor, s_t: int, d: Tensor, d_ref: Optional[Tensor] = None):
     """First-block-cache probe (dk_block_probe_*).  x: the joint stream [B, S, h] behind block 0 (text rows first, ``s_t`` of them per
     batch row; only the image rows are read); d: [B, S - s_t, h], X0's image rows on entry, D_cur = round(x - d) on return; d_ref: the

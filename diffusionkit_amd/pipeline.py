@@ -293,8 +293,15 @@ class DiffusionPipeline:
         activation_dtype: Optional[str] = None,
         vae_dtype: Optional[str] = None,
         condition: Optional[str] = None,
+        controlnet_ckpt=None,
+        controlnet_config: Optional[MMDiTConfig] = None,
     ):
-        """``condition`` (FluxPipeline only): None, "fill" (FLUX.1 Fill) or "control" (FLUX.1 Canny / Depth) -- channel-concatenated conditioning: the
+        """``controlnet_ckpt`` (SD3 family only): an SD3 ControlNet in the layout of diffusers' SD3ControlNetModel -- a .safetensors path or a state
+        dict in that layout, or a dict of reference-named tensors (``weights.synth_mmdit_weights`` of a control-net config) -- built into a second
+        ``MMDiTEngine``, ``self.controlnet``; ``controlnet_config``: its configuration (default ``config.SD3_CONTROLNET_6``, in the model's element
+        type).  Every call must then name its ``controlnet_image_path`` (see ``denoise_latents``).  Refused on FLUX, on a model with dual attention
+        blocks (SD3.5-medium) and on an fp8 engine.  Arithmetic parity on synthetic weights only: no ControlNet checkpoint has been run.
+        ``condition`` (FluxPipeline only): None, "fill" (FLUX.1 Fill) or "control" (FLUX.1 Canny / Depth) -- channel-concatenated conditioning: the
         model's x_embedder is 64 + 320 / 64 + 64 columns wide (``config.FLUX_FILL_DEV`` / ``FLUX_CONTROL_DEV``; a ``mmdit_config`` of the caller's
         gets that width), and every call must name its ``condition_image_path`` (see ``denoise_latents``).
         ``vae_dtype``: element type of the VAE decoder and (built on first use, img2img) encoder -- None or "bfloat16": bf16, today's
@@ -356,7 +363,40 @@ class DiffusionPipeline:
         self._packed_weights = packed_weights  # {"mmdit": ..., "vae_decoder": ...} already in engine layout
         self._text_encoder: Optional[Callable] = None
         self._init_sampler(shift)
+        self.controlnet = None
+        if controlnet_ckpt is None and controlnet_config is not None:
+            raise ValueError("controlnet_config needs controlnet_ckpt: there is no ControlNet to configure")
+        if controlnet_ckpt is not None:
+            self._check_controlnet_config(controlnet_config)  # (before anything is loaded)
         self.check_and_load_models()
+        if controlnet_ckpt is not None:
+            self.load_controlnet(controlnet_ckpt)
+
+    def _check_controlnet_config(self, controlnet_config) -> None:
+        from .config import SD3_CONTROLNET_6, validate_control_net
+        cfg = self.mmdit_config
+        if self._IS_FLUX or cfg.depth_unified > 0:
+            raise ValueError("controlnet_ckpt is the SD3 family's (diffusers' SD3ControlNetModel): FLUX ControlNets have single-block taps and are not built")
+        if cfg.dual_attention_blocks > 0:
+            raise ValueError("controlnet_ckpt cannot be combined with dual attention blocks (SD3.5-medium): the engine adds taps in a plain block's "
+                             "LayerNorm launch only")
+        if cfg.weight_dtype == "fp8_e4m3":
+            raise ValueError("controlnet_ckpt cannot be combined with an fp8 engine: the taps are added on the bf16 / fp16 path only")
+        ccfg = replace(controlnet_config or SD3_CONTROLNET_6, activation_dtype=cfg.activation_dtype)
+        if not ccfg.control_net:
+            raise ValueError("controlnet_config must be a control-net configuration (control_net=True, e.g. config.SD3_CONTROLNET_6)")
+        validate_control_net(ccfg)
+        if ccfg.hidden_size != cfg.hidden_size or ccfg.patch_dim != cfg.patch_dim or ccfg.depth_multimodal > cfg.depth_multimodal:
+            raise ValueError(f"the ControlNet (hidden {ccfg.hidden_size}, patch_dim {ccfg.patch_dim}, {ccfg.depth_multimodal} blocks) does not fit the model "
+                             f"(hidden {cfg.hidden_size}, patch_dim {cfg.patch_dim}, {cfg.depth_multimodal} blocks): the taps are added to its stream")
+        self.controlnet_config = ccfg
+
+    def load_controlnet(self, ckpt) -> None:
+        """Builds ``self.controlnet``, the ControlNet's engine, from a path / state dict in the diffusers layout or reference-named tensors"""
+        from .model_io import load_controlnet_checkpoint
+        ccfg = self.controlnet_config
+        named = dict(load_controlnet_checkpoint(ckpt, ccfg))
+        self.controlnet = MMDiTEngine(ccfg, pack_mmdit(ccfg, named, self.device, consume=True))
 
     def _init_sampler(self, shift):
         self.sampler = ModelSamplingDiscreteFlow(shift=shift)
@@ -501,8 +541,20 @@ class DiffusionPipeline:
         pag_scale=None,
         pag_layers=None,
         pag_interval=None,
+        controlnet_image_path=None,
+        controlnet_scale: float = 1.0,
+        controlnet_interval=None,
     ):
-        """mlx/__init__.py:253-292.  ``seed`` may be a list: one image per seed is denoised in a
+        """``controlnet_image_path`` (a pipeline built with ``controlnet_ckpt``; a path, a PIL image or an array, or a list with one per seed): the
+        prepared control image (edges, pose, ...) at the OUTPUT size -- never resized, sides multiples of 16 -- VAE-encoded to the posterior's mean (the
+        published pipeline samples), put through the latent format's ``process_in`` and patchified.  Every model evaluation of a controlled step first
+        runs the ControlNet's engine on the same tokens, both CFG rows included, and the main engine adds ``controlnet_scale`` times its taps
+        (``MMDiTEngine.set_control_taps``).  ``controlnet_interval`` = (start, stop): step i of n is controlled iff i / n >= start and
+        (i + 1) / n <= stop (diffusers' control_guidance_start / _end; Heun's two evaluations share their step's decision); outside it the ControlNet
+        is not run and the launches are the plain ones.  Composes with seed lists, every sampler and guidance mode, ``guidance_interval`` (both
+        engines are re-prepared together), img2img, inpainting and float16.  Raises on ``block_cache``, skip-layer and perturbed-attention guidance,
+        on these keywords without a ControlNet and on their absence with one.  ``self.last_controlnet`` = {"scale", "interval", "evals"}, or None.
+        mlx/__init__.py:253-292.  ``seed`` may be a list: one image per seed is denoised in a
         single batched step loop (data-parallel sharding hands each rank a list).
         ``mask_path`` (inpainting; a path, a PIL image or an array as ``read_mask`` takes them, or a list with one per seed): repaint where the
         mask is 255, keep ``image_path``'s content where it is 0 -- kept latent cells equal the encoded image bit for bit.
@@ -573,6 +625,10 @@ class DiffusionPipeline:
         guide = _guidance_options(guidance, guidance_rescale, apg_eta, apg_norm_threshold, apg_momentum, guidance_interval, cfg_weight)
         if mask_path is not None and image_path is None:
             raise ValueError("mask_path needs image_path: the mask says which part of that image to keep")
+        n_seeds = len(seed) if isinstance(seed, (list, tuple)) else 1
+        control = _controlnet_options(self, controlnet_image_path, controlnet_scale, controlnet_interval, n_seeds,
+                                      (latent_size[0] * 8, latent_size[1] * 8) if image_path is None else read_image_u8(image_path).shape[:2],
+                                      block_cache, slg, pag)  # (raises before any GPU work)
         sampler = check_sampler(sampler)
         if sampler == "heun" and block_cache is not None:
             raise ValueError(_HEUN_BLOCK_CACHE)
@@ -615,6 +671,10 @@ class DiffusionPipeline:
             extra_args["skip_layer_guidance"] = slg
         if pag is not None:
             extra_args["perturbed_attention_guidance"] = pag
+        if control is not None:
+            z = self.latent_format.process_in(self.encode_reference_to_latents(control["pixels"]))
+            extra_args["controlnet"] = {"engine": self.controlnet, "tokens": self.controlnet.patchify(z.to(torch.float32).contiguous()),
+                                        "scale": control["scale"], "interval": control["interval"]}
         self.last_reference = None
         if refs is not None:
             extra_args["reference"] = self.latent_format.process_in(self.encode_reference_to_latents(refs))
@@ -641,6 +701,7 @@ class DiffusionPipeline:
                                                               unguided_evals=0 if cfg_weight > 0 else evals)
         self.last_skip_layer_guidance = denoiser.skip_layer_record
         self.last_perturbed_attention_guidance = denoiser.perturbed_attention_record
+        self.last_controlnet = denoiser.controlnet_record
         latent = self.latent_format.process_out(latent)
         return latent, iter_time
 
@@ -675,8 +736,13 @@ class DiffusionPipeline:
         pag_scale=None,
         pag_layers=None,
         pag_interval=None,
+        controlnet_image_path=None,
+        controlnet_scale: float = 1.0,
+        controlnet_interval=None,
     ):
-        """mlx/__init__.py:294-534: returns (PIL.Image, log).  ``mask_path``: inpainting, see ``denoise_latents``; with ``composite`` the pixels
+        """``controlnet_image_path``, ``controlnet_scale``, ``controlnet_interval``: SD3 ControlNet, see ``denoise_latents``; with a ControlNet,
+        ``log["denoising"]["controlnet"]`` is ``self.last_controlnet``.
+        mlx/__init__.py:294-534: returns (PIL.Image, log).  ``mask_path``: inpainting, see ``denoise_latents``; with ``composite`` the pixels
         the mask keeps are pasted back from the input image after decoding (the VAE round trip alone does not reproduce them).
         ``block_cache``: first-block cache, see ``denoise_latents``; its record goes to ``log["denoising"]["block_cache"]``.
         ``sampler``: "euler" (default) | "heun" | "ab2", see ``denoise_latents``; ``log["denoising"]["sampler"]`` and ``["model_evals"]`` say what ran.
@@ -730,7 +796,9 @@ class DiffusionPipeline:
             **({} if skip_layer_guidance is None and skip_layers is None and skip_layer_interval is None else
                {"skip_layer_guidance": skip_layer_guidance, "skip_layers": skip_layers, "skip_layer_interval": skip_layer_interval}),
             **({} if pag_scale is None and pag_layers is None and pag_interval is None else
-               {"pag_scale": pag_scale, "pag_layers": pag_layers, "pag_interval": pag_interval}))
+               {"pag_scale": pag_scale, "pag_layers": pag_layers, "pag_interval": pag_interval}),
+            **({} if controlnet_image_path is None and controlnet_interval is None and controlnet_scale == 1.0 and getattr(self, "controlnet", None) is None
+               else {"controlnet_image_path": controlnet_image_path, "controlnet_scale": controlnet_scale, "controlnet_interval": controlnet_interval}))
         torch.cuda.synchronize(dev)
         log["denoising"]["post"] = mem()
         log["peak_memory"] = max(log["peak_memory"], log["denoising"]["post"]["peak_memory"])
@@ -749,6 +817,8 @@ class DiffusionPipeline:
             log["denoising"]["skip_layer_guidance"] = self.last_skip_layer_guidance
         if self.last_perturbed_attention_guidance is not None:
             log["denoising"]["perturbed_attention_guidance"] = self.last_perturbed_attention_guidance
+        if self.last_controlnet is not None:
+            log["denoising"]["controlnet"] = self.last_controlnet
 
         torch.cuda.reset_peak_memory_stats(dev)
         t0 = time.time()
@@ -947,6 +1017,7 @@ class CFGDenoiser:
         self.guidance_record = None  # what sample_steps ran under extra_args["guidance"]
         self.skip_layer_record = None  # what sample_steps ran under extra_args["skip_layer_guidance"]
         self.perturbed_attention_record = None  # ... under extra_args["perturbed_attention_guidance"]
+        self.controlnet_record = None  # ... under extra_args["controlnet"]
 
     def cache_modulation_params(self, pooled_text_embeddings, timesteps):
         self._timesteps = [float(t) for t in timesteps]
@@ -1100,6 +1171,60 @@ def _perturbed_attention_options(scale, layers, interval, mmdit_config, is_flux,
     return {"scale": scale, "layers": layers, "interval": interval}
 
 
+def controlnet_step_active(i: int, n: int, interval) -> bool:
+    """whether step ``i`` of ``n`` runs with the ControlNet under ``interval`` = (start, stop) fractions of the schedule: diffusers'
+    control_guidance_start / _end rule, i / n >= start and (i + 1) / n <= stop.  None: every step"""
+    if interval is None:
+        return True
+    start, stop = interval
+    return i / n >= start and (i + 1) / n <= stop
+
+
+def _controlnet_options(pipe, image, scale, interval, n_img, out_hw, block_cache, slg, pag):
+    """The ControlNet keywords of one call -> None (a pipeline without a ControlNet and no keyword) or {"pixels": uint8 [1 or n_img, H, W, 3],
+    "scale", "interval"}.  Refused, each naming its rule: the keywords on a pipeline built without a ControlNet and their absence on one built
+    with it, ``block_cache``, skip-layer and perturbed-attention guidance, a control image of another size than the output."""
+    has = getattr(pipe, "controlnet", None) is not None
+    if not has:
+        if image is not None or interval is not None or float(scale) != 1.0:
+            raise ValueError("controlnet_image_path / controlnet_scale / controlnet_interval need a pipeline built with a ControlNet (controlnet_ckpt=)")
+        return None
+    if image is None:
+        raise ValueError("a pipeline built with a ControlNet needs controlnet_image_path in every call: the ControlNet was trained to see a control image")
+    if block_cache is not None:
+        raise ValueError("a ControlNet cannot run together with block_cache: the cached effect of blocks 1 .. L-1 would hold another step's taps")
+    if slg is not None or pag is not None:
+        raise ValueError("a ControlNet cannot run together with skip-layer or perturbed-attention guidance: the forked row group would need taps of its own")
+    scale = float(scale)
+    if not np.isfinite(scale):
+        raise ValueError(f"controlnet_scale must be finite, got {scale}")
+    if interval is not None:
+        interval = tuple(float(v) for v in interval)
+        if len(interval) != 2 or not all(np.isfinite(v) for v in interval):
+            raise ValueError(f"controlnet_interval must be (start, stop), two finite fractions of the schedule, got {interval}")
+    px = _read_references(image, n_img)  # (a path, a PIL image or an array, or one per seed; sides that are multiples of 16; never resized)
+    if tuple(px.shape[1:3]) != tuple(out_hw):
+        raise ValueError(f"the control image is {px.shape[1]}x{px.shape[2]}, the output {out_hw[0]}x{out_hw[1]}: it must have the output's size "
+                         "(it is not resized here)")
+    return {"pixels": px, "scale": scale, "interval": interval}
+
+
+def _prepare_control(lp_control: Optional[dict], now: int, n_img: int, latent_hw, conditioning: Tensor, pooled: Tensor, timesteps) -> None:
+    """Behind ``_prepare_rows``: the ControlNet engine prepared for the same rows as the main engine, with its own modulation table, context and
+    control-image share, and a taps tensor of that shape"""
+    if lp_control is None:
+        return
+    cn, tok = lp_control["engine"], lp_control["tokens"]
+    cn.prepare(now, latent_hw, conditioning.shape[1], len(timesteps))
+    cn.cache_modulation_params(pooled, [float(t) for t in timesteps])
+    cn.cache_context(conditioning)
+    if tok.shape[0] == 1:
+        cn.cache_control_image(tok, per_image=False)
+    else:
+        cn.cache_control_image(tok.repeat(now // n_img, 1, 1).contiguous(), per_image=True)
+    lp_control["taps"] = torch.empty(cn.taps_shape(), dtype=cn.dtype, device=tok.device)
+
+
 class _Loop(NamedTuple):
     """what a step loop works on once the engine is prepared (``_loop_setup``)"""
     pipe: object
@@ -1122,6 +1247,9 @@ class _Loop(NamedTuple):
     condition: Optional[Tensor] = None  # the condition token rows bf16 [1 or n_img, S_i, condition_features] behind ``extra_args["condition"]``, or None
     slg: Optional[dict] = None  # ``extra_args["skip_layer_guidance"]`` (``_skip_layer_options``), or None
     pag: Optional[dict] = None  # ``extra_args["perturbed_attention_guidance"]`` (``_perturbed_attention_options``), or None: never both
+    # ``extra_args["controlnet"]``: {"engine": the ControlNet's MMDiTEngine, "tokens": the control image's tokens [1 or n_img, S_i, p*p*C], "scale",
+    # "interval"} plus "taps", the tensor ``_prepare_control`` allocates for the rows the engines hold; or None
+    control: Optional[dict] = None
 
     @property
     def forked(self) -> Optional[dict]:
@@ -1208,6 +1336,14 @@ def _loop_setup(model: "CFGDenoiser", x: Tensor, sigmas, extra_args, guided: boo
     _cache_condition(mm, condition, now, n_img)
     model.cache_modulation_params(pooled[:now], timesteps)
     mm.cache_context(conditioning[:now])  # context_embedder is step-invariant (the reference recomputes it in every call, mmdit.py:195)
+    control = extra_args.get("controlnet")
+    if control is not None:
+        control = dict(control)
+        if policy is not None or extra_args.get("skip_layer_guidance") is not None or extra_args.get("perturbed_attention_guidance") is not None:
+            raise ValueError("extra_args['controlnet'] cannot run together with block_cache, skip-layer or perturbed-attention guidance")
+        if control["tokens"].dim() != 3 or control["tokens"].shape[0] not in (1, n_img):
+            raise ValueError(f"the control tokens {tuple(control['tokens'].shape)} do not match {n_img} images: [1 or n_img, S_i, patch_dim]")
+        _prepare_control(control, now, n_img, x.shape[1:3], conditioning[:now], pooled[:now], timesteps)
 
     x = x.to(torch.float32).contiguous().clone()
     mask = extra_args.get("mask")
@@ -1220,7 +1356,7 @@ def _loop_setup(model: "CFGDenoiser", x: Tensor, sigmas, extra_args, guided: boo
         x_orig = noise = None
     tok = mm.patchify(x, dup=2 if cfg_on and guided else 1)
     return _Loop(pipe, mm, sigmas, cfg_weight, cfg_on, n_img, policy, x, mask, x_orig, noise, tok, torch.empty_like(tok), conditioning, pooled, timesteps,
-                 reference, condition, extra_args.get("skip_layer_guidance"), extra_args.get("perturbed_attention_guidance"))
+                 reference, condition, extra_args.get("skip_layer_guidance"), extra_args.get("perturbed_attention_guidance"), control)
 
 
 def _set_rows(model: "CFGDenoiser", lp: _Loop, guided: bool, fork: bool = False):
@@ -1238,6 +1374,7 @@ def _set_rows(model: "CFGDenoiser", lp: _Loop, guided: bool, fork: bool = False)
     lp.mm.cache_context(rows(lp.conditioning).contiguous())
     if lp.forked is not None:  # (without the options the engine is never told: its calls are what they were)
         lp.set_fork(fork)
+    _prepare_control(lp.control, now, lp.n_img, lp.x.shape[1:3], rows(lp.conditioning).contiguous(), rows(lp.pooled).contiguous(), lp.timesteps)
     tok = lp.mm.patchify(lp.x, dup=now // lp.n_img)
     return tok, torch.empty_like(tok)
 
@@ -1269,6 +1406,7 @@ def _step_loop(model: "CFGDenoiser", lp: _Loop, plan, grows, guide=None, euler: 
     fresh = False  # the engine was re-prepared: the first-block cache holds nothing to reuse
     fork = False  # whether it holds the forked third row group of skip-layer guidance
     srows = [False] * len(plan) if srows is None else srows
+    control_evals = 0
     for r, g, sl in zip(plan, grows, srows):
         t0 = time.perf_counter() if t0 is None else t0
         if cfg_on and (g.guided != on or sl != fork):
@@ -1277,6 +1415,16 @@ def _step_loop(model: "CFGDenoiser", lp: _Loop, plan, grows, guide=None, euler: 
             if policy is not None:
                 mm.reset_block_cache()
                 fresh = True
+        if lp.control is not None:
+            # the ControlNet in front of the main forward, on the same stream and the same tokens; a step outside the interval runs without it and
+            # with the taps off: the plain launches (Heun's two rows share their step's decision)
+            if controlnet_step_active(step, n_steps, lp.control["interval"]):
+                lp.control["engine"].control_forward(tok, None, r.index, taps_out=lp.control["taps"])
+                if mm.control_taps is None or mm.control_taps[0] is not lp.control["taps"]:
+                    mm.set_control_taps(lp.control["taps"], lp.control["scale"])
+                control_evals += 1
+            elif mm.control_taps is not None:
+                mm.set_control_taps(None)
         if policy is None:
             mm.forward_tokens(tok, None, r.index, tokens_out=out)
         else:
@@ -1312,6 +1460,8 @@ def _step_loop(model: "CFGDenoiser", lp: _Loop, plan, grows, guide=None, euler: 
         model.skip_layer_record = dict(lp.slg, evals=sum(bool(v) for v in srows))
     if lp.pag is not None:
         model.perturbed_attention_record = dict(lp.pag, evals=sum(bool(v) for v in srows))
+    if lp.control is not None:
+        model.controlnet_record = {"scale": lp.control["scale"], "interval": lp.control["interval"], "evals": control_evals}
     model.clear_cache()
     return x, iter_time
 
@@ -1328,7 +1478,11 @@ def sample_euler(model: CFGDenoiser, x: Tensor, sigmas, extra_args=None):
     the record of the decisions goes to ``model.block_cache_record``."""
     lp = _loop_setup(model, x, sigmas, extra_args)
     plan = step_plan("euler", lp.sigmas)  # (one row per step; its sigma and sigma_next are the schedule's float32 entries)
-    return _step_loop(model, lp, plan, guidance_rows(plan), euler=True)
+    try:
+        return _step_loop(model, lp, plan, guidance_rows(plan), euler=True)
+    finally:
+        if lp.control is not None:  # (the main engine's taps are off again when the loop returns or raises)
+            lp.mm.set_control_taps(None)
 
 
 def sample_steps(model: CFGDenoiser, x: Tensor, sigmas, plan, extra_args=None):
@@ -1370,7 +1524,11 @@ def sample_steps(model: CFGDenoiser, x: Tensor, sigmas, plan, extra_args=None):
     if any(not 0 <= r.index < len(lp.sigmas) - 1 for r in plan):
         raise ValueError("the plan evaluates the model outside the schedule (or at its last entry): build it with sampler.step_plan on these sigmas")
     if lp.forked is None:
-        return _step_loop(model, lp, plan, grows, guide)
+        try:
+            return _step_loop(model, lp, plan, grows, guide)
+        finally:
+            if lp.control is not None:  # (the main engine's taps are off again when the loop returns or raises)
+                lp.mm.set_control_taps(None)
     window = lp.forked["interval"]  # (None, perturbed-attention guidance only: every guided row)
     srows = [bool(g.guided) for g in grows] if window is None else slg_rows(plan, grows, *window)
     try:

@@ -105,6 +105,14 @@ def synth_mmdit_weights(cfg: MMDiTConfig, seed: int = 1234, device="cpu", dtype=
         block(f"multimodal_transformer_blocks.{i}.text_transformer_block", 2 if skip_txt else 6, skip_post=skip_txt)
     for i in range(cfg.depth_unified):
         block(f"unified_transformer_blocks.{i}.transformer_block", 3, parallel=True)
+    if getattr(cfg, "control_net", False):
+        # SD3 ControlNet: no final layer; the second patch embedder (the control image's) and one Linear per block.  Zero-initialised in a fresh
+        # ControlNet, trained in a published one: drawn like every other Linear, or nothing downstream of them would be exercised
+        I.normal("pos_embed_input.proj.weight", (h, p, p, cfg.vae_latent_dim))
+        I.normal("pos_embed_input.proj.bias", (h,))
+        for i in range(cfg.depth_multimodal):
+            I.linear(f"controlnet_blocks.{i}", h, h)
+        return I.out
     I.linear("final_layer.linear", cfg.patch_dim, h)
     I.linear("final_layer.adaLN_modulation.layers.1", 2 * h, h)
     # MMDiT-X dual-attention blocks (cfg.dual_attention_blocks): the second attention of the image stream -- k_proj WITH its bias -- and rows
@@ -223,7 +231,8 @@ def adaln_order(cfg: MMDiTConfig):
         names.append(f"multimodal_transformer_blocks.{i}.text_transformer_block")
     for i in range(cfg.depth_unified):
         names.append(f"unified_transformer_blocks.{i}.transformer_block")
-    names.append("final_layer")
+    if not getattr(cfg, "control_net", False):  # (a ControlNet has no final layer)
+        names.append("final_layer")
     return names
 
 
@@ -258,9 +267,11 @@ def pack_mmdit(cfg: MMDiTConfig, w: Dict[str, Tensor], device, consume: bool = F
     dev = torch.device(device)
     # element type of every tensor the engine binds: cfg.activation_dtype.  float16: a value from an fp16 or fp32 source is rounded once to fp16,
     # and an fp16 checkpoint tensor reaches the device bit for bit (same names, pitches and fusions)
-    from .config import validate_activation_dtype, validate_dual_attention
+    from .config import validate_activation_dtype, validate_control_net, validate_dual_attention
     validate_activation_dtype(cfg)
     validate_dual_attention(cfg)
+    validate_control_net(cfg)
+    control_net = bool(getattr(cfg, "control_net", False))
     bf = torch.float16 if cfg.activation_dtype == "float16" else torch.bfloat16
     fp8 = cfg.weight_dtype == "fp8_e4m3"
     out: Dict[str, Tensor] = {}
@@ -311,9 +322,19 @@ def pack_mmdit(cfg: MMDiTConfig, w: Dict[str, Tensor], device, consume: bool = F
               "y_embedder.mlp.layers.0.weight", "y_embedder.mlp.layers.0.bias",
               "y_embedder.mlp.layers.2.weight", "y_embedder.mlp.layers.2.bias",
               "t_embedder.mlp.layers.0.weight", "t_embedder.mlp.layers.0.bias",
-              "t_embedder.mlp.layers.2.weight", "t_embedder.mlp.layers.2.bias",
-              "final_layer.linear.weight", "final_layer.linear.bias"):
+              "t_embedder.mlp.layers.2.weight", "t_embedder.mlp.layers.2.bias") + (
+                  () if control_net else ("final_layer.linear.weight", "final_layer.linear.bias")):
         put(k, get(k))
+    if control_net:  # the control image's patch embedder, packed as x_embedder is, and the tap Linears (dk_mmdit_set_control_net)
+        cw = get("pos_embed_input.proj.weight")
+        if cw.reshape(cw.shape[0], -1).shape[1] != cfg.patch_dim:
+            raise ValueError(f"pos_embed_input.proj.weight {tuple(cw.shape)}: {cfg.patch_dim} input features expected (extra conditioning channels "
+                             "are not supported)")
+        put("pos_embed_input.proj.weight", cw.reshape(cw.shape[0], -1))
+        put("pos_embed_input.proj.bias", get("pos_embed_input.proj.bias"))
+        for i in range(cfg.depth_multimodal):
+            put(f"controlnet_blocks.{i}.weight", get(f"controlnet_blocks.{i}.weight"))
+            put(f"controlnet_blocks.{i}.bias", get(f"controlnet_blocks.{i}.bias"))
     if cfg.guidance_embed:
         for k in ("guidance_in.mlp.layers.0.weight", "guidance_in.mlp.layers.0.bias", "guidance_in.mlp.layers.2.weight",
                   "guidance_in.mlp.layers.2.bias"):

@@ -368,6 +368,16 @@ int dk_ln_modulate_dual_bf16(const void* x, void* out_a, void* out_b, int32_t M,
                              const void* shift_b, const void* scale_b, int32_t mod_seg_len, const void* x1, void* out1, int32_t M1,
                              const void* shift1, const void* scale1, int32_t mod_seg_len1, int32_t ldx, int32_t ldo, int32_t h,
                              int32_t mod_stride, int32_t x_seg_stride, int32_t x_seg_stride1, float eps, void* stream);
+/* The LayerNorm pass with a residual tap in front (ControlNet taps, see dk_mmdit_set_control_taps): for each of the M rows of x,
+ *   x'[m, :] = round_E( fmaf(s, tap[m, :], x[m, :]) )   fp32 arithmetic, one rounding to the element type E,
+ * is stored back over x (in place) and out[m, :] is what dk_ln_modulate_bf16 gives for x' -- bit for bit; the tap is loaded with the row
+ * and the row is read once.  tap: [M, ldt] dense rows of E, 16-byte aligned, ldt >= h and ldt % 8 == 0; row m of the tap goes with
+ * LOGICAL row m of x (the row map of dk_ln_modulate_dual_bf16).  The second row set (x1 ..., M1 == 0: none) is plain: no tap, and x1 is
+ * read only. */
+int dk_ln_modulate_add_bf16(void* x, const void* tap, int32_t ldt, float s, void* out, int32_t M, const void* shift, const void* scale,
+                            int32_t mod_seg_len, const void* x1, void* out1, int32_t M1, const void* shift1, const void* scale1,
+                            int32_t mod_seg_len1, int32_t ldx, int32_t ldo, int32_t h, int32_t mod_stride, int32_t x_seg_stride,
+                            int32_t x_seg_stride1, float eps, void* stream);
 
 /* QKNorm (mmdit.py:754-764) + RoPE.apply (mmdit.py:934-942), in place on the q / k column groups
  * of a token-major QKV buffer.  q_weight/k_weight NULL = no norm; rope_table NULL = no rotation.
@@ -563,6 +573,10 @@ int dk_ln_modulate_dual_f16(const void* x, void* out_a, void* out_b, int32_t M, 
                             const void* shift_b, const void* scale_b, int32_t mod_seg_len, const void* x1, void* out1, int32_t M1,
                             const void* shift1, const void* scale1, int32_t mod_seg_len1, int32_t ldx, int32_t ldo, int32_t h,
                             int32_t mod_stride, int32_t x_seg_stride, int32_t x_seg_stride1, float eps, void* stream);
+int dk_ln_modulate_add_f16(void* x, const void* tap, int32_t ldt, float s, void* out, int32_t M, const void* shift, const void* scale,
+                           int32_t mod_seg_len, const void* x1, void* out1, int32_t M1, const void* shift1, const void* scale1,
+                           int32_t mod_seg_len1, int32_t ldx, int32_t ldo, int32_t h, int32_t mod_stride, int32_t x_seg_stride,
+                           int32_t x_seg_stride1, float eps, void* stream);
 int dk_qk_norm_rope_f16(void* qkv, int32_t ld, int32_t q_off, int32_t k_off, int32_t rows, int32_t H,
                         int32_t D, const void* q_weight, const void* k_weight, float eps, const float* rope_table,
                         int32_t row_seg_len, int32_t row_seg_stride, int32_t pos_off, void* stream);
@@ -834,6 +848,43 @@ int dk_mmdit_set_skip_layers(dk_mmdit* m, const int32_t* blocks, int32_t n_block
  * dk_mmdit_forward_tail and dk_mmdit_run_blocks while perturbed attention is set.  Both element types.
  * Verified against an fp32 / emulating oracle with synthetic weights (arithmetic parity); no checkpoint has been run. */
 int dk_mmdit_set_perturbed_attention(dk_mmdit* m, const int32_t* blocks, int32_t n_blocks, int32_t fork_rows);
+
+/* ---- SD3 ControlNet (opt-in; the layout of diffusers' SD3ControlNetModel, no counterpart in the reference) ---------------------------
+ * Two engines.  The CONTROL-NET engine is an SD3 engine of N_c blocks without a final layer, with a second patch embedder for the
+ * VAE-encoded control image and one Linear(h, h) per block; it writes N_c taps, [N_c, B, S_i, h] in the element type.  The MAIN engine
+ * adds them to its image stream: with n taps and depth blocks, s * tap[floor(g * n / depth)] behind block g for g = 0 .. depth - 2 (diffusers'
+ * rule, interval_control = depth / n and index int(g / interval_control), restated in integers; nothing behind the last block, whose text
+ * stream is pre-only).  "Behind block g" is "in front of block g + 1": block g + 1's first LayerNorm launch becomes
+ * dk_ln_modulate_add_* -- x' = round_E(fmaf(s, tap, x)), ONE rounding where the published code rounds s * tap and the sum -- and no
+ * launch is added.
+ * Verified against an fp32 / emulating oracle with synthetic weights (arithmetic parity); no ControlNet checkpoint has been run.
+ *
+ * dk_mmdit_set_control_net(m, on): legal before the first dk_mmdit_bind.  Refused unless the geometry is SD3's: use_pos_embed,
+ * depth_unified == 0, no fp8_linears, no dual attention, no reference grid, no condition width.  Such an engine additionally binds
+ *   pos_embed_input.proj.{weight,bias}   [h, p*p*C] / [h], packed as x_embedder.proj is
+ *   controlnet_blocks.<j>.{weight,bias}  [h, h] / [h], j < depth_multimodal
+ * and needs no final_layer.*; every other tensor is what an SD3 engine of that depth binds (the last block's text stream is pre-only as
+ * ever: the published model runs its post-attention half, and nothing reads the result).
+ * dk_mmdit_cache_control_image: after dk_mmdit_prepare.  ctrl_tokens in the element type, [batch, S_i, p*p*C] (per_image != 0) or
+ * [1, S_i, p*p*C] (one control image for every batch row: one launch per batch row either way, the bits of a repeated image).  Computes
+ * CONDE[b] = POS + pos_embed_input(ctrl_tokens[b]) once; every later dk_mmdit_control_forward's x_embedder launch takes CONDE in its
+ * residual slot instead of POS.  Invalidated by dk_mmdit_prepare.
+ * dk_mmdit_control_forward: the embedders, then blocks 0 .. N_c - 1, and behind block j one GEMM taps_out[j] = controlnet_blocks.<j>(
+ * image rows) into the caller's taps_out [N_c, B, S_i, h].  dk_mmdit_forward, dk_mmdit_forward_head and dk_mmdit_forward_tail on a
+ * control-net engine are refused with an error that names dk_mmdit_control_forward; dk_mmdit_run_blocks stays.
+ *
+ * dk_mmdit_set_control_taps(m, taps, n_taps, scale) on the MAIN engine: taps [n_taps, B, S_i, h] dense in the element type, 16-byte
+ * aligned, owned by the caller and read by every later dk_mmdit_forward in stream order.  (NULL, 0, any) is off, the default: every launch
+ * and every bit is then what it is without the feature.  Takes effect at the next forward; workspace size and carve do not change.
+ * dk_mmdit_prepare switches the taps off (their shape was the previous problem's): set them again behind it.
+ * Refused, with no state changed and an error that names the rule: a geometry other than SD3's (use_pos_embed, depth_unified == 0),
+ * n_taps outside [1, depth_multimodal], fp8_linears, dual attention, a block cache, skip layers, perturbed attention, a reference grid or
+ * a condition width that is set, a control-net engine.  dk_mmdit_forward_head, dk_mmdit_forward_tail and dk_mmdit_run_blocks are refused
+ * while taps are set; dk_mmdit_set_block_cache(1), dk_mmdit_set_skip_layers and dk_mmdit_set_perturbed_attention likewise. */
+int dk_mmdit_set_control_net(dk_mmdit* m, int32_t on);
+int dk_mmdit_cache_control_image(dk_mmdit* m, const void* ctrl_tokens, int32_t per_image, void* stream);
+int dk_mmdit_control_forward(dk_mmdit* m, const void* tokens_in, const void* text, int32_t step_index, void* taps_out, void* stream);
+int dk_mmdit_set_control_taps(dk_mmdit* m, const void* taps, int32_t n_taps, float scale);
 /* Head of step `step_index`: dk_mmdit_forward's embedder launches, block 0 and the probe.  probe_out: device float [batch][2] =
  * (num, den) per batch row; before any computed step den is 0 (and num = sum |D_cur|).  Records a pending head for step_index. */
 int dk_mmdit_forward_head(dk_mmdit* m, const void* tokens_in, const void* text, int32_t step_index, float* probe_out, void* stream);
