@@ -136,7 +136,7 @@ class dk_attention_plan_t(C.Structure):  # (o8_split is read by dk_attention_pla
 # the step entries (dk_euler / dk_lms / dk_guided _cfg_step, their masked and _f16 forms), composed: x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl,
 # C, p, reshape_order, sigma; then Euler's sigma_next, cfg_weight, or the row's cfg_weight, hist, five coefficients, sigma_next, reads_h, writes_h; then
 # the mask operands x_orig, noise, mask, mask_per_image; then mode, phi, eta, r, beta, reads_m, writes_m, m, workspace, its bytes; then (dk_slg_cfg_step)
-# slg_scale; then the stream
+# slg_scale; then (dk_noisy_cfg_step) guided, slg, cn, seeds, draw; then the stream
 _STEP_HEAD = [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32]
 _STEP_EULER = _STEP_HEAD + [_f32, _f32]
 _STEP_ROW = _STEP_HEAD + [_f32, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _i32]
@@ -144,7 +144,8 @@ _STEP_MASK = [_vp, _vp, _vp, _i32]
 _STEP_GUIDE = [_i32, _f32, _f32, _f32, _f32, _i32, _i32, _vp, _vp, _sz]
 _STEP_ENTRIES = {"dk_euler_cfg_step": _STEP_EULER, "dk_euler_cfg_step_masked": _STEP_EULER + _STEP_MASK, "dk_lms_cfg_step": _STEP_ROW,
                  "dk_lms_cfg_step_masked": _STEP_ROW + _STEP_MASK, "dk_guided_cfg_step": _STEP_ROW + _STEP_MASK + _STEP_GUIDE,
-                 "dk_slg_cfg_step": _STEP_ROW + _STEP_MASK + _STEP_GUIDE + [_f32]}
+                 "dk_slg_cfg_step": _STEP_ROW + _STEP_MASK + _STEP_GUIDE + [_f32],
+                 "dk_noisy_cfg_step": _STEP_ROW + _STEP_MASK + _STEP_GUIDE + [_f32] + [_i32, _i32, _f32, _vp, _i32]}
 SIGNATURES = {
     "dk_abi_version": (_i32, []),
     "dk_last_error": (C.c_char_p, []),
@@ -201,6 +202,9 @@ SIGNATURES = {
     # the step tail: Euler, the coefficient row of the second-order samplers, the guidance modes (mask operands nullable); plain / masked, bf16 / fp16
     **{name + f16: (_i32, args + [_vp]) for name, args in _STEP_ENTRIES.items() for f16 in ("", "_f16")},
     "dk_guidance_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    # stochastic samplers: the generator as an operator (out, seeds u64 [n_img], n_img, n_per_img, draw, stream tag, quad_offset; the step entry is
+    # dk_noisy_cfg_step above)
+    "dk_philox_normal_f32": (_i32, [_vp, _vp, _i32, _i64, _i32, _i32, C.c_uint64, _vp]),
     # inpainting: the mask's pixels -> latent cells, the paste-back of the kept pixels
     "dk_mask_to_latent_f32": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "dk_image_composite_u8": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),

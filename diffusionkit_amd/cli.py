@@ -76,10 +76,15 @@ def build_parser(model_versions: Sequence[str]) -> argparse.ArgumentParser:
                    help="First-block cache: skip the blocks behind block 0 in steps where block 0's effect moved by less than THRESHOLD "
                         "(a float >= 0, relative to the last computed step). Published implementations use about 0.1 for FLUX; no value "
                         "has been validated here on a real checkpoint.")
-    p.add_argument("--sampler", choices=("euler", "heun", "ab2"), default=None,
+    p.add_argument("--sampler", choices=("euler", "heun", "ab2", "euler_a", "sde"), default=None,
                    help="Integrator of the step loop. euler (default): first order, one model evaluation per step. heun: second order, two "
                         "evaluations per step but the last (not together with --block-cache). ab2: second order, one evaluation per step. "
-                        "The orders are checked on an analytic problem, not on a trained checkpoint.")
+                        "The orders are checked on an analytic problem, not on a trained checkpoint. euler_a: ancestral Euler for rectified flows "
+                        "(k-diffusion's sample_euler_ancestral_RF), first order, re-noises a share --sampler-eta of every step. sde: diffusers' "
+                        "stochastic_sampling, which re-draws all of the noise every step; offered as the published definition and nothing more. Both "
+                        "draw their noise on the GPU from the image's seed; neither has been run on a trained checkpoint here.")
+    p.add_argument("--sampler-eta", type=float, default=None, metavar="ETA",
+                   help="With --sampler euler_a: the share of each step that is re-noised, in [0, 1] (default 1; 0 is euler).")
     p.add_argument("--guidance", choices=("cfg", "rescale", "apg"), default=None,
                    help="How the prompt and the negative prediction are combined (models with --cfg > 0 only). cfg (default): neg + w (pos - neg). "
                         "rescale: the same, scaled towards the prompt prediction's standard deviation (--guidance-rescale). apg: adaptive "
@@ -203,6 +208,12 @@ def resolve(args) -> dict:
             raise ValueError("--sampler heun cannot run together with --block-cache (two model evaluations per step have no cache policy yet); "
                              "use --sampler ab2")
         r["sampler"] = args.sampler
+    if getattr(args, "sampler_eta", None) is not None:  # (a key only when the flag is given)
+        if r.get("sampler") != "euler_a":
+            raise ValueError("--sampler-eta belongs to --sampler euler_a")
+        if not 0.0 <= args.sampler_eta <= 1.0:
+            raise ValueError("--sampler-eta must lie in [0, 1]")
+        r["sampler_eta"] = args.sampler_eta
     for flag, key in GUIDANCE_FLAGS.items():  # (keys only when the flags are given)
         v = getattr(args, flag, None)
         if v is not None:
@@ -300,7 +311,8 @@ def main(argv: Optional[Sequence[str]] = None, pipeline_overrides: Optional[dict
                                    negative_text=args.negative_prompt, latent_size=latent_size, image_path=args.image_path,
                                    denoise=args.denoise, verbose=args.verbose, mask_path=r.get("mask_path"),
                                    composite=r.get("composite", True), block_cache=r.get("block_cache"), sampler=r.get("sampler"),
-                                   **{key: r[key] for key in (*GUIDANCE_FLAGS.values(), "reference_image_path", *SKIP_LAYER_KEYS, *PAG_KEYS) if key in r},
+                                   **{key: r[key] for key in (*GUIDANCE_FLAGS.values(), "reference_image_path", *SKIP_LAYER_KEYS, *PAG_KEYS, "sampler_eta")
+                                      if key in r},
                                    **cond_kw)
     if log["text_encoding"].get("synthetic"):
         logger.warning("no text-encoder checkpoints were named (--ckpt clip_l=... t5=...): the conditioning is synthetic")

@@ -479,13 +479,19 @@ extern "C" int dk_latent_to_tokens_f16(const float* x, void* tokens, int32_t n_i
   return latent_to_tokens(DK_DTYPE_F16, x, tokens, n_img, dup, Hl, Wl, C, p, reshape_order, stream);
 }
 
-// ---- the step tail: twelve entries (Euler, coefficient row, guided, skip-layer; plain and masked; bf16 and fp16) over one parameter block, one check, one launcher
+// ---- the step tail: fourteen entries (Euler, coefficient row, guided, skip-layer, noisy; plain and masked; bf16 and fp16) over one parameter block, one check, one launcher
 // Every requirement of a step launch.  The guided entries' own come first, then the common ones, so that a call that breaks one rule is told what it
 // always was; the structured binding gives the fields the names the messages quote.
 static int check_step(const StepParams& s) {
   const auto& [x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight, has_row, cx, cd, ch, hx, hd,
                hist, reads_h, writes_h, masked, x_orig, noise, mask, mask_per_image, guided, mode, phi, eta, r, beta, m, reads_m, writes_m, workspace,
-               workspace_bytes, slg, slg_scale] = s;
+               workspace_bytes, slg, slg_scale, noisy, cn, seeds, draw] = s;
+  if (noisy) {
+    DK_REQUIRE(std::isfinite(cn), "cn must be finite");
+    DK_REQUIRE(seeds || cn == 0.0f, "seeds is null while the row carries a noise term (cn != 0)");
+    DK_REQUIRE(draw >= 0 || cn == 0.0f, "draw must not be negative where the row carries a noise term (cn != 0)");
+    DK_REQUIRE(((long)Hl * Wl * C) % 4 == 0, "the latent of one image must hold a multiple of 4 elements (Hl * Wl * C % 4 == 0): a Philox block is four normals");
+  }
   if (slg) {
     DK_REQUIRE(cfg_on != 0, "skip-layer guidance adds its term to a guided prediction: cfg_on must be set");
     DK_REQUIRE(std::isfinite(slg_scale), "slg_scale must be finite");
@@ -651,6 +657,56 @@ extern "C" int dk_slg_cfg_step_f16(float* x, const void* model_out, int32_t ld_o
   const StepParams b = with_blend(with_row(s, hist, cx, cd, ch, hx, hd, reads_h, writes_h), x_orig || noise || mask, x_orig, noise, mask, mask_per_image);
   return step(DK_DTYPE_F16, with_skip_layers(with_guidance(b, mode, phi, eta, r, beta, reads_m, writes_m, m, workspace, workspace_bytes), slg_scale),
               stream);
+}
+
+// stochastic samplers: dk_slg_cfg_step's row with the flags `guided` and `slg` spelled out (0: the group is left out, and an unguided row runs with
+// cfg_on = 0) and one more term, cn xi(seeds[img], draw), drawn in the launch
+static StepParams with_noise(StepParams s, float cn, const uint64_t* seeds, int draw) {
+  s.noisy = true, s.cn = cn, s.seeds = (const unsigned long long*)seeds, s.draw = draw;
+  return s;
+}
+static int noisy_step(int dtype, float* x, const void* model_out, int ld_out, void* tokens, int n_img, int cfg_on, int Hl, int Wl, int C, int p,
+                      int reshape_order, float sigma, float cfg_weight, float* hist, float cx, float cd, float ch, float hx, float hd, float sigma_next,
+                      int reads_h, int writes_h, const float* x_orig, const float* noise, const float* mask, int mask_per_image, int guided, int mode,
+                      float phi, float eta, float r, float beta, int reads_m, int writes_m, float* m, void* workspace, size_t workspace_bytes, int slg,
+                      float slg_scale, float cn, const uint64_t* seeds, int draw, void* stream) {
+  DK_REQUIRE(guided != 0 || mode == 0, "a row without the guidance group (guided = 0) takes mode 0");
+  const StepParams s = step_operands(x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, sigma_next, cfg_weight);
+  StepParams b = with_blend(with_row(s, hist, cx, cd, ch, hx, hd, reads_h, writes_h), x_orig || noise || mask, x_orig, noise, mask, mask_per_image);
+  if (guided) b = with_guidance(b, mode, phi, eta, r, beta, reads_m, writes_m, m, workspace, workspace_bytes);
+  if (slg) b = with_skip_layers(b, slg_scale);
+  return step(dtype, with_noise(b, cn, seeds, draw), stream);
+}
+extern "C" int dk_noisy_cfg_step(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on, int32_t Hl, int32_t Wl,
+                                 int32_t C, int32_t p, int32_t reshape_order, float sigma, float cfg_weight, float* hist, float cx, float cd, float ch,
+                                 float hx, float hd, float sigma_next, int32_t reads_h, int32_t writes_h, const float* x_orig, const float* noise,
+                                 const float* mask, int32_t mask_per_image, int32_t mode, float phi, float eta, float r, float beta, int32_t reads_m,
+                                 int32_t writes_m, float* m, void* workspace, size_t workspace_bytes, float slg_scale, int32_t guided, int32_t slg,
+                                 float cn, const uint64_t* seeds, int32_t draw, void* stream) {
+  return noisy_step(DK_DTYPE_BF16, x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, cfg_weight, hist, cx, cd, ch, hx, hd,
+                    sigma_next, reads_h, writes_h, x_orig, noise, mask, mask_per_image, guided, mode, phi, eta, r, beta, reads_m, writes_m, m, workspace,
+                    workspace_bytes, slg, slg_scale, cn, seeds, draw, stream);
+}
+extern "C" int dk_noisy_cfg_step_f16(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on, int32_t Hl,
+                                     int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma, float cfg_weight, float* hist, float cx,
+                                     float cd, float ch, float hx, float hd, float sigma_next, int32_t reads_h, int32_t writes_h, const float* x_orig,
+                                     const float* noise, const float* mask, int32_t mask_per_image, int32_t mode, float phi, float eta, float r,
+                                     float beta, int32_t reads_m, int32_t writes_m, float* m, void* workspace, size_t workspace_bytes, float slg_scale,
+                                     int32_t guided, int32_t slg, float cn, const uint64_t* seeds, int32_t draw, void* stream) {
+  return noisy_step(DK_DTYPE_F16, x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl, C, p, reshape_order, sigma, cfg_weight, hist, cx, cd, ch, hx, hd,
+                    sigma_next, reads_h, writes_h, x_orig, noise, mask, mask_per_image, guided, mode, phi, eta, r, beta, reads_m, writes_m, m, workspace,
+                    workspace_bytes, slg, slg_scale, cn, seeds, draw, stream);
+}
+// the generator where tests can reach it: out f32 [n_img, n_per_img], row j from seeds[j] (u64 on the device), quads quad_offset, quad_offset + 1, ...
+extern "C" int dk_philox_normal_f32(float* out, const uint64_t* seeds, int32_t n_img, int64_t n_per_img, int32_t draw, int32_t stream_tag,
+                                    uint64_t quad_offset, void* stream) {
+  DK_REQUIRE(out && seeds, "null argument");
+  DK_REQUIRE(n_img > 0 && n_per_img > 0, "n_img and n_per_img must be positive");
+  DK_REQUIRE(n_per_img % 4 == 0, "n_per_img must be a multiple of 4: a Philox block is four normals");
+  DK_REQUIRE(draw >= 0 && stream_tag >= 0, "draw and stream must not be negative");
+  DK_REQUIRE(quad_offset <= ~0ull - (uint64_t)(n_per_img / 4), "quad_offset + n_per_img / 4 must stay below 2^64");
+  return dk_launch_philox_normal(out, (const unsigned long long*)seeds, n_img, (long)n_per_img, (unsigned)draw, (unsigned)stream_tag,
+                                 (unsigned long long)quad_offset, S_(stream));
 }
 
 extern "C" int dk_mask_to_latent_f32(const uint8_t* mask, float* out, int32_t n_mask, int32_t H, int32_t W, int32_t f, void* stream) {

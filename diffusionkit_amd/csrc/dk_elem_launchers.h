@@ -76,6 +76,13 @@ struct StepParams {
   // slg_scale (c - k) with k its x0 prediction; the tokens keep their two copies
   bool slg;
   float slg_scale;
+  // stochastic samplers (noisy: a dk_noisy_* call, whose latent must hold a multiple of 4 elements per image): x' takes cn xi behind the update and
+  // in front of the blend, xi the standard normals of draw `draw` of seeds[img] (u64 [n_img] on the device; read only where cn != 0), formed in the
+  // launch.  cn == 0: the launches above, bit for bit
+  bool noisy;
+  float cn;
+  const unsigned long long* seeds;
+  int draw;
 };
 #endif
 size_t dk_guidance_workspace_size(int n_img, int Hl, int Wl, int C);

@@ -329,6 +329,9 @@ int dk_launch_image_mask_out_f32(const unsigned char* image, const unsigned char
                                  hipStream_t stream);
 int dk_launch_fill_condition_tokens(const float* z, const unsigned char* mask, bf16_t* tok, int n, int mask_per_image, int Hl, int Wl, int C,
                                     int p, hipStream_t stream);
+// stochastic samplers: out f32 [n_img, n_per_img], row j the standard normals of seeds[j] (Philox4x32-10 + Box-Muller, include/dk_hip.h)
+int dk_launch_philox_normal(float* out, const unsigned long long* seeds, int n_img, long n_per_img, unsigned draw, unsigned stream,
+                            unsigned long long quad_offset, hipStream_t st);
 
 // ---- launchers per element type ------------------------------------------------------------------------------
 #include "dk_elem_launchers.h"

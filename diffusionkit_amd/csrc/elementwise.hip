@@ -465,7 +465,50 @@ int dk_launch_timestep_embedding(const float* t, int n, int rep, int dim, float 
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------------
+// The noise of the stochastic samplers (no reference counterpart; the definition is sampler.philox4x32_10 / philox_normal_reference).
+// Philox4x32-10 (Salmon et al., SC'11), counter (q & 0xffffffff, q >> 32, draw, stream), key (seed & 0xffffffff, seed >> 32); a block
+// (o0, o1, o2, o3) gives four normals by Box-Muller on 24-bit uniforms, pairs (o0, o1) -> z0, z1 and (o2, o3) -> z2, z3, and element r of an image
+// takes z[r % 4] of quad q = r / 4.  Every thread runs the ten rounds of its own quad and keeps one of the four normals: the four threads of a quad
+// repeat each other's block (about forty 32-bit multiplies each) instead of exchanging it, so that a value depends on (seed, q, draw, stream, r % 4)
+// alone -- not on which lanes of a wave are live, nor on the launch that asks -- and the operator and the step kernel share this one function.
+// u = ((o_a >> 8) + 1) 2^-24 is exact in fp32 and never 0; the angle is taken in half turns, 2 (o_b >> 8) 2^-24, exact too, through sinpif / cospif.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ float philox_normal(unsigned long long seed, unsigned long long q, unsigned draw, unsigned stream, int k) {
+  unsigned c0 = (unsigned)q, c1 = (unsigned)(q >> 32), c2 = draw, c3 = stream;
+  unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+#pragma unroll
+  for (int round = 0; round < 10; ++round) {
+    const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+    const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    c0 = h1 ^ c1 ^ k0, c1 = l1, c2 = h0 ^ c3 ^ k1, c3 = l0;
+    k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
+  }
+  const unsigned oa = (k & 2) ? c2 : c0, ob = (k & 2) ? c3 : c1;
+  const float u = (float)((oa >> 8) + 1u) * 0x1p-24f;
+  const float turns = (float)(ob >> 8) * 0x1p-23f;
+  const float rad = sqrtf(-2.0f * logf(u));
+  return rad * ((k & 1) ? sinpif(turns) : cospif(turns));
+}
+
 #ifndef DK_ELEM_F16  // (fp32 / bf16-only helpers: one copy)
+// out f32 [n_img, n_per_img]: row j holds the normals of seeds[j] from quad quad_offset on (dk_philox_normal_f32; n_per_img % 4 == 0)
+__global__ void dk_philox_normal_kernel(float* out, const unsigned long long* seeds, long n_img, long n_per_img, unsigned draw, unsigned stream,
+                                        unsigned long long quad_offset) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_img * n_per_img) return;
+  const long img = i / n_per_img, r = i % n_per_img;
+  out[i] = philox_normal(seeds[img], quad_offset + (unsigned long long)(r >> 2), draw, stream, (int)(r & 3));
+}
+int dk_launch_philox_normal(float* out, const unsigned long long* seeds, int n_img, long n_per_img, unsigned draw, unsigned stream,
+                            unsigned long long quad_offset, hipStream_t st) {
+  const long n = (long)n_img * n_per_img;
+  DK_REQUIRE(n > 0 && (n + 255) / 256 <= 0x7fffffffL, "philox_normal: size");
+  hipLaunchKernelGGL(dk_philox_normal_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, out, seeds, (long)n_img, n_per_img, draw, stream,
+                     quad_offset);
+  DK_CHECK_HIP(hipGetLastError());
+  return 0;
+}
 // RoPE cos/sin table [S, D/2, 2] for the joint [text, image] sequence
 // (python/src/diffusionkit/mlx/mmdit.py:865-911, quirk Q14).
 struct RopeAxes { int dim[4]; int n; };
@@ -783,58 +826,31 @@ struct GuideArgs {
   int reads_m, writes_m;
   float slg_scale;  // (in the struct's tail padding: the argument layout of every instantiation stays)
 };
+// Stochastic samplers (include/dk_hip.h: dk_noisy_cfg_step): behind the update and in front of the blend, x' takes cn * xi, xi =
+// philox_normal(seeds[img], r / 4, draw, 0, r % 4) with r the element's index inside its image -- the operator's function on the operator's
+// arguments, formed in registers: no noise buffer is read or written.  The term lives in kernels of its own, dk_lms_noisy_step_kernel, whose body is
+// the text of dk_lms_step_kernel's (lms_step_body.inc): the argument layout and the instructions of that kernel's instantiations stay.
+struct NoiseArgs {
+  float cn;
+  const unsigned long long* seeds;
+  unsigned draw;
+};
 template <bool MASKED, int GMODE = DK_GUIDE_CFG, bool SLG = false>
 __global__ void dk_lms_step_kernel(float* x, const bf16_t* model_out, int ld_out, bf16_t* tok, int n_img, int cfg_on, int Hl, int Wl,
                                    int C, int p, int reshape_order, float sigma, float sigma_next, float cfg_weight, float* hist,
                                    LmsRow row, const float* x_orig, const float* noise, const float* mask, int mask_per_image,
                                    GuideArgs gd) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long per_img = (long)Hl * Wl * C;
-  if (i >= per_img * n_img) return;
-  const StepCell k = step_cell((int)(i / per_img), i % per_img, Hl, Wl, C, p, reshape_order);
-  const float xv = x[i];
-  const float xb = round_act(xv);  // the value the denoiser saw
-  float den = step_den(model_out, ld_out, k.img, k.S_i, k.t, k.f, xb, sigma);
-  float slg = 0.0f;
-  if constexpr (SLG) {  // (cfg_on != 0: check_step)
-    slg = gd.slg_scale * (den - step_den(model_out, ld_out, 2 * n_img + k.img, k.S_i, k.t, k.f, xb, sigma));
-  }
-  if constexpr (GMODE == DK_GUIDE_CFG) {
-    if (cfg_on) {
-      const float den_neg = step_den(model_out, ld_out, n_img + k.img, k.S_i, k.t, k.f, xb, sigma);
-      den = den_neg + cfg_weight * (den - den_neg);
-    }
-  } else {  // (cfg_on != 0: check_step)
-    const float den_neg = step_den(model_out, ld_out, n_img + k.img, k.S_i, k.t, k.f, xb, sigma);
-    if constexpr (GMODE == DK_GUIDE_RESCALE) {
-      const float g = den_neg + cfg_weight * (den - den_neg);
-      den = g * gd.scal[2 * k.img];
-    } else {
-      float dl = den - den_neg;
-      if (gd.reads_m) dl = dl + gd.beta * gd.m[i];
-      if (gd.writes_m) gd.m[i] = dl;
-      const float a = gd.scal[2 * k.img], b = gd.scal[2 * k.img + 1];
-      den = den + (cfg_weight - 1.0f) * (a * dl - b * den);
-    }
-  }
-  float num = xv - den;
-  if constexpr (SLG) {
-    num = num - slg;  // x - (den + slg), taken behind the difference: a product that forms den may be contracted into it, and with slg_scale == 0 the
-                      // exact zero then leaves the bits of the mode's own step
-  }
-  const float d = num / sigma;
-  float xn;
-  if (row.reads_h)
-    xn = row.cx * xv + row.cd * d + row.ch * hist[i];
-  else if (row.cx == 1.0f)
-    xn = xv + d * row.cd;
-  else
-    xn = row.cx * xv + d * row.cd;
-  if (row.writes_h) hist[i] = row.hx * xv + row.hd * d;
-  if constexpr (MASKED) {
-    xn = step_blend(xn, i, k.img, k.yy, k.xx, Hl, Wl, sigma_next, x_orig, noise, mask, mask_per_image);
-  }
-  step_store(x, tok, i, xn, k, n_img, cfg_on);
+  constexpr bool NOISY = false;
+  constexpr NoiseArgs nz = {};  // (named by the included text, never read)
+#include "lms_step_body.inc"
+}
+template <bool MASKED, int GMODE, bool SLG>
+__global__ void dk_lms_noisy_step_kernel(float* x, const bf16_t* model_out, int ld_out, bf16_t* tok, int n_img, int cfg_on, int Hl, int Wl,
+                                         int C, int p, int reshape_order, float sigma, float sigma_next, float cfg_weight, float* hist,
+                                         LmsRow row, const float* x_orig, const float* noise, const float* mask, int mask_per_image,
+                                         GuideArgs gd, NoiseArgs nz) {
+  constexpr bool NOISY = true;
+#include "lms_step_body.inc"
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -941,7 +957,8 @@ __global__ __launch_bounds__(64) void dk_guide_fold_kernel(const double* part, f
 // The one launcher of the step tail (StepParams, dk_elem_launchers.h): the Euler kernel without a row, else the row kernel of the block's
 // (masked, mode), behind the two moments launches under modes 1 and 2.  What an instantiation does not read (the blend operands unmasked, gd
 // under mode 0) is passed as the block holds it.  The instantiations are named in the order the object has always held them: its .text is
-// compared byte for byte across host-only changes (scripts/device_code_diff.py).  The skip-layer forms of the row kernel come behind them.
+// compared byte for byte across host-only changes (scripts/device_code_diff.py).  The skip-layer forms of the row kernel come behind them, and the
+// noisy kernel's twelve (masked x mode x skip-layer) behind those.
 int dk_launch_step(const StepParams& s, hipStream_t stream) {
   const long per_img = (long)s.Hl * s.Wl * s.C;
   const long n = (long)s.n_img * per_img;
@@ -987,6 +1004,18 @@ int dk_launch_step(const StepParams& s, hipStream_t stream) {
   }
   const LmsRow row = {s.cx, s.cd, s.ch, s.hx, s.hd, s.reads_h, s.writes_h};
   const GuideArgs gd = {scal, s.m, s.beta, s.reads_m, s.writes_m, s.slg_scale};
+  if (s.cn != 0.0f) {  // (the row carries a noise term: the same case of the noisy kernel, behind the same moments; cn == 0 is the launch below)
+#define DK_NOISY(MODE) {{dk_lms_noisy_step_kernel<false, MODE, false>, dk_lms_noisy_step_kernel<false, MODE, true>}, \
+                        {dk_lms_noisy_step_kernel<true, MODE, false>, dk_lms_noisy_step_kernel<true, MODE, true>}}
+    static const decltype(&dk_lms_noisy_step_kernel<false, DK_GUIDE_CFG, false>) noisy[3][2][2] = {DK_NOISY(DK_GUIDE_CFG), DK_NOISY(DK_GUIDE_RESCALE),
+                                                                                                  DK_NOISY(DK_GUIDE_APG)};
+#undef DK_NOISY
+    const NoiseArgs nz = {s.cn, s.seeds, (unsigned)s.draw};
+    hipLaunchKernelGGL(noisy[s.mode][s.masked][s.slg], grid, dim3(256), 0, stream, s.x, s.model_out, s.ld_out, s.tok, s.n_img, s.cfg_on, s.Hl, s.Wl, s.C,
+                       s.p, s.reshape_order, s.sigma, s.sigma_next, s.cfg_weight, s.hist, row, s.x_orig, s.noise, s.mask, (int)s.mask_per_image, gd, nz);
+    DK_CHECK_HIP(hipGetLastError());
+    return 0;
+  }
   hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, s.x, s.model_out, s.ld_out, s.tok, s.n_img, s.cfg_on, s.Hl, s.Wl, s.C, s.p, s.reshape_order,
                      s.sigma, s.sigma_next, s.cfg_weight, s.hist, row, s.x_orig, s.noise, s.mask, (int)s.mask_per_image, gd);
   DK_CHECK_HIP(hipGetLastError());

@@ -532,10 +532,11 @@ GUIDANCE_MODES = {"cfg": 0, "rescale": 1, "apg": 2}
 
 
 def _step(what, x, model_out, tokens, n_img, cfg_on, p, reshape_order, sigma, sigma_next, cfg_weight, row=None, blend=None, blend_error=_lib.DkHipError,
-          guide=None, slg_scale=None) -> None:
+          guide=None, slg_scale=None, noise_term=None) -> None:
     """The one call of a step entry, dk_<what> / _f16 by the dtype of ``model_out`` (the argument groups of ``_lib._STEP_ENTRIES``): the operands, then
     ``row`` = (hist, coef, reads_h, writes_h), ``blend`` = (x_orig, noise, mask) and ``guide`` = (mode, phi, eta, r, beta, reads_m, writes_m, m,
-    workspace) and ``slg_scale`` where the entry has them, each validated here.  ``blend_error``: what a mask operand of the wrong shape raises -- the Euler wrapper
+    workspace) and ``slg_scale`` where the entry has them, each validated here; ``noise_term`` = (guided, slg, cn, seeds, draw), dk_noisy_cfg_step's
+    tail.  ``blend_error``: what a mask operand of the wrong shape raises -- the Euler wrapper
     says ValueError, in its own words, where the others say DkHipError."""
     name = "dk_" + what + ("" if _elem(model_out.dtype, what) == "bf16" else "_f16")
     if guide is not None and guide[0] not in GUIDANCE_MODES:
@@ -584,6 +585,11 @@ def _step(what, x, model_out, tokens, n_img, cfg_on, p, reshape_order, sigma, si
                  _ptr(workspace), ws_bytes)
     if slg_scale is not None:
         tail += (float(slg_scale),)
+    if noise_term is not None:
+        guided, slg, cn, seeds, draw = noise_term
+        if seeds is not None:
+            _require_seeds(seeds, n_img, what)
+        tail += (int(bool(guided)), int(bool(slg)), float(cn), _ptr(seeds), int(draw))
     _lib.check(getattr(_lib.load(), name)(x.data_ptr(), model_out.data_ptr(), model_out.shape[-1], tokens.data_ptr(), n_img, int(cfg_on), hl, wl, c, p,
                                           reshape_order, float(sigma), *tail, _stream()), name)
 
@@ -657,6 +663,56 @@ def slg_cfg_step(x: Tensor, model_out: Tensor, tokens: Tensor, n_img: int, cfg_o
     _step("slg_cfg_step", x, model_out, tokens, n_img, cfg_on, p, reshape_order, sigma, sigma_next, cfg_weight,
           row=(hist, coef, reads_h, writes_h), blend=blend, guide=(mode, rescale, eta, norm_threshold, momentum, reads_m, writes_m, m, workspace),
           slg_scale=slg_scale)
+
+
+def seed_tensor(seeds, device) -> Tensor:
+    """The per-image seeds of the stochastic samplers on the device: Python ints in [0, 2^64) -> int64 [n] holding their 64 bits (the library reads
+    them as u64)"""
+    seeds = [int(v) for v in seeds]
+    if any(not 0 <= v < 1 << 64 for v in seeds):
+        raise ValueError(f"seeds must lie in [0, 2^64), got {seeds}")
+    import numpy as np
+    return torch.from_numpy(np.asarray(seeds, dtype=np.uint64).view(np.int64).copy()).to(device)
+
+
+def _require_seeds(seeds: Tensor, n_img: int, what: str) -> None:
+    _require_cuda(seeds, "seeds")
+    if seeds.dtype not in (torch.int64, torch.uint64) or seeds.numel() != n_img:
+        raise _lib.DkHipError(f"{what}: seeds must hold one 64-bit integer per image ({n_img}; ``seed_tensor``), got {seeds.dtype} {tuple(seeds.shape)}")
+
+
+def philox_normal(seeds: Tensor, n_per_img: int, draw: int, stream: int = 0, quad_offset: int = 0) -> Tensor:
+    """dk_philox_normal_f32: f32 [n_img, n_per_img], row j = the standard normals of ``seeds[j]`` (``seed_tensor``) for draw ``draw`` of use
+    ``stream``, from quad ``quad_offset`` on -- ``sampler.philox_normal_reference`` on the GPU, the noise the stochastic step forms in registers.
+    ``n_per_img`` must be a multiple of 4."""
+    n_img = int(seeds.numel())
+    _require_seeds(seeds, n_img, "philox_normal")
+    out = torch.empty(n_img, int(n_per_img), dtype=torch.float32, device=seeds.device)
+    _lib.check(_lib.load().dk_philox_normal_f32(out.data_ptr(), seeds.data_ptr(), n_img, int(n_per_img), int(draw), int(stream), int(quad_offset),
+                                                _stream()), "dk_philox_normal_f32")
+    return out
+
+
+def noisy_cfg_step(x: Tensor, model_out: Tensor, tokens: Tensor, n_img: int, cfg_on: bool, p: int, reshape_order: int, sigma: float,
+                   sigma_next: float, cfg_weight: float, hist: Optional[Tensor], coef, reads_h: bool, writes_h: bool, *, cn: float,
+                   seeds: Optional[Tensor], draw: int, guided: bool = False, slg_scale: Optional[float] = None, mode: str = "cfg",
+                   workspace: Optional[Tensor] = None, rescale: float = 0.0, eta: float = 0.0, norm_threshold: float = 0.0, momentum: float = 0.0,
+                   reads_m: bool = False, writes_m: bool = False, m: Optional[Tensor] = None, x_orig: Optional[Tensor] = None,
+                   noise: Optional[Tensor] = None, mask: Optional[Tensor] = None) -> None:
+    """dk_noisy_cfg_step / _f16 by the dtype of ``model_out``: the coefficient-row step of a stochastic sampler, x = cx x + cd d + ch hist +
+    ``cn`` xi, xi the standard normals of draw ``draw`` of ``seeds[img]`` (``seed_tensor``; ``philox_normal``'s values), formed inside the launch in
+    front of the blend.  ``guided``: the guidance group of ``guided_cfg_step`` is read (needs ``cfg_on``); ``slg_scale`` not None: ``slg_cfg_step``'s
+    third row group.  Without either the call is ``lms_cfg_step`` (with the mask operands: ``lms_cfg_step_masked``) plus the term.  ``cn`` 0 gives
+    the bits of those entries and reads neither ``seeds`` nor ``draw``.  The latent of one image must hold a multiple of 4 elements."""
+    if slg_scale is not None:
+        if model_out.dim() == 3 and model_out.shape[0] != 3 * n_img:
+            raise _lib.DkHipError(f"noisy_cfg_step: model_out holds {model_out.shape[0]} rows, expected 3 * n_img = {3 * n_img}")
+        if tokens.dim() == 3 and tokens.shape[0] < 2 * n_img:
+            raise _lib.DkHipError(f"noisy_cfg_step: tokens hold {tokens.shape[0]} rows, expected at least 2 * n_img = {2 * n_img}")
+    blend = None if x_orig is None and noise is None and mask is None else (x_orig, noise, mask)
+    _step("noisy_cfg_step", x, model_out, tokens, n_img, cfg_on, p, reshape_order, sigma, sigma_next, cfg_weight,
+          row=(hist, coef, reads_h, writes_h), blend=blend, guide=(mode, rescale, eta, norm_threshold, momentum, reads_m, writes_m, m, workspace),
+          slg_scale=0.0 if slg_scale is None else slg_scale, noise_term=(guided, slg_scale is not None, cn, seeds, draw))
 
 
 def mask_to_latent(mask: Tensor, factor: int = 8) -> Tensor:

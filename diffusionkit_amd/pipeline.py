@@ -15,6 +15,8 @@ step's own launch (dk_euler_cfg_step_masked), and ``generate_image`` pastes the 
 
 Samplers (``sampler=``, keyword-only, no reference counterpart): "euler" (default: the reference's loop, ``sample_euler``), "heun" and "ab2" run
 ``sample_steps`` over the rows of ``sampler.step_plan`` -- one launch of dk_lms_cfg_step (or its masked form) behind every model evaluation.
+The stochastic samplers "euler_a" (``sampler_eta=``) and "sde" are rows with one more term, cn xi: their launch is dk_noisy_cfg_step, which draws xi
+inside the launch from a counter (Philox4x32-10 keyed by the image's own seed), so no noise is drawn on the host, uploaded or stored per step.
 
 Guidance (``guidance=``, ``guidance_interval=`` and the mode parameters, keyword-only, no reference counterpart; models that run with CFG): "cfg"
 (default: today's combine), "rescale" and "apg" replace the step launch of ``sample_steps`` by dk_guided_cfg_step, and an interval runs the evaluations
@@ -48,8 +50,8 @@ import torch
 from . import _lib
 from .config import (MMDIT_CKPT, MODEL_CONFIG, SKIP_LAYER_GUIDANCE, T5_MAX_LENGTH, MMDiTConfig, VAEDecoderConfig, VAEEncoderConfig)
 from .engine import MMDiTEngine, VAEDecoderEngine, VAEEncoderEngine, _stream
-from .sampler import (FluxSampler, ModelSamplingDiscreteFlow, check_guidance, check_interval, check_perturbed_attention_guidance, check_sampler,
-                      check_skip_layer_guidance, get_sigmas,
+from .sampler import (STOCHASTIC_SAMPLERS, FluxSampler, ModelSamplingDiscreteFlow, check_guidance, check_interval, check_perturbed_attention_guidance,
+                      check_sampler, check_sampler_eta, check_skip_layer_guidance, get_sigmas,
                       guidance_rows, max_denoise, slg_rows, step_plan)
 from .weights import pack_mmdit, pack_vae, synth_mmdit_weights, synth_vae_encoder_weights, synth_vae_weights
 
@@ -526,6 +528,7 @@ class DiffusionPipeline:
         mask_path=None,
         block_cache=None,
         sampler=None,
+        sampler_eta=None,
         guidance=None,
         guidance_rescale: float = 0.7,
         apg_eta: float = 0.0,
@@ -568,6 +571,17 @@ class DiffusionPipeline:
         per step but the last) or "ab2" (second order, one evaluation per step, the previous step's direction kept in an fp32 buffer); every
         composition above works with them, except that "heun" refuses ``block_cache`` (see ``sample_steps``).  ``self.last_sampler`` says what
         ran: {"sampler", "model_evals"}.  Their order is checked on an analytic problem (profiles/samplers.md), not on a trained checkpoint.
+        Stochastic samplers: "euler_a" (k-diffusion's sample_euler_ancestral_RF; ``sampler_eta`` in [0, 1], default 1, the share of the step that is
+        re-noised: 0 is "euler", its launches and its bits) and "sde" (diffusers' FlowMatchEulerDiscreteScheduler(stochastic_sampling=True): x' =
+        (1 - sigma') den + sigma' xi, all of the noise re-drawn every step -- offered as the published definition and nothing more: at a finite number
+        of steps it does not preserve the marginals of a mean-predicting denoiser, profiles/stochastic_samplers.md).  First order, one evaluation per
+        step.  The noise is drawn inside the step launch (dk_noisy_cfg_step) from a counter: Philox4x32-10 keyed by the image's own seed -- the one its
+        start noise was drawn with; with ``seed=None`` the one picked and logged here -- at the schedule index of the step, so an image's result depends
+        on its seed alone, not on its place in a seed list, the batch size, CFG or the element type; a schedule cut by ``denoise`` keeps the draws of
+        the entries it keeps.  The seeds are uploaded once per call.  The rows go through the same loop as every plan, so the compositions above hold
+        (inpainting: the blend still re-noises the known region with the start draw).  ``sampler_eta`` with any other sampler raises.
+        ``self.last_sampler`` then also holds "eta" (None under "sde") and "noise_draws", the number of launches that drew noise.  Arithmetic only, on
+        synthetic weights: nothing here says anything about image quality on a trained checkpoint.
         ``guidance`` (models with ``cfg_weight > 0``): None or "cfg" (neg + w (pos - neg), today's launches and bits), "rescale" (the same, scaled by
         ``guidance_rescale`` * std(pos) / std(cfg) + 1 - ``guidance_rescale`` per image) or "apg" (adaptive projected guidance on the x0 predictions:
         ``apg_eta`` weighs the component parallel to the prompt prediction, ``apg_norm_threshold`` > 0 clips the norm of the direction per image,
@@ -630,6 +644,7 @@ class DiffusionPipeline:
                                       (latent_size[0] * 8, latent_size[1] * 8) if image_path is None else read_image_u8(image_path).shape[:2],
                                       block_cache, slg, pag)  # (raises before any GPU work)
         sampler = check_sampler(sampler)
+        eta = check_sampler_eta(sampler, sampler_eta)
         if sampler == "heun" and block_cache is not None:
             raise ValueError(_HEUN_BLOCK_CACHE)
         seed = int(time.time()) if seed is None else seed
@@ -650,7 +665,8 @@ class DiffusionPipeline:
             x_T = x_orig.cpu().numpy()
         noise = np.concatenate([self.get_noise(s, x_T[:1]) for s in seeds], axis=0)
         sigmas = self.get_sigmas(self.sampler, num_steps)
-        sigmas = sigmas[int(num_steps * (1 - denoise)):]
+        cut = int(num_steps * (1 - denoise))
+        sigmas = sigmas[cut:]
         extra_args = {
             "conditioning": conditioning,
             "cfg_weight": cfg_weight,
@@ -688,14 +704,21 @@ class DiffusionPipeline:
         noise_scaled = self.sampler.noise_scaling(np.float32(sigmas[0]), noise, x_T, self.max_denoise(sigmas))
         x0 = torch.from_numpy(np.ascontiguousarray(noise_scaled, dtype=np.float32)).to(self.device)
         denoiser = CFGDenoiser(self)
-        if sampler == "euler" and guide is None and slg is None and pag is None:
+        stochastic = sampler in STOCHASTIC_SAMPLERS
+        rows = "euler" if sampler == "euler_a" and eta == 0.0 else sampler  # (eta = 0: euler's rows, and so euler's launches)
+        if rows == "euler" and guide is None and slg is None and pag is None:
             latent, iter_time = sample_euler(denoiser, x0, sigmas, extra_args=extra_args)
-            evals = len(iter_time)
+            evals, draws = len(iter_time), 0
         else:
-            plan = step_plan(sampler, sigmas)
+            plan = step_plan(rows, sigmas, eta if rows == "euler_a" else None, first_draw=cut)
+            draws = sum(r.cn != 0.0 for r in plan)
+            if draws:  # (the seeds the start noise was drawn with, one per image)
+                extra_args["noise_seeds"] = [int(s) for s in seeds]
             latent, iter_time = sample_steps(denoiser, x0, sigmas, plan, extra_args=extra_args)
             evals = len(plan)
         self.last_sampler = {"sampler": sampler, "model_evals": evals}
+        if stochastic:  # (keys of the stochastic samplers alone)
+            self.last_sampler.update(eta=eta if sampler == "euler_a" else None, noise_draws=draws)
         self.last_block_cache = denoiser.block_cache_record
         self.last_guidance = denoiser.guidance_record or dict(_DEFAULT_GUIDANCE, guided_evals=evals if cfg_weight > 0 else 0,
                                                               unguided_evals=0 if cfg_weight > 0 else evals)
@@ -721,6 +744,7 @@ class DiffusionPipeline:
         composite: bool = True,
         block_cache=None,
         sampler=None,
+        sampler_eta=None,
         guidance=None,
         guidance_rescale: float = 0.7,
         apg_eta: float = 0.0,
@@ -745,7 +769,8 @@ class DiffusionPipeline:
         mlx/__init__.py:294-534: returns (PIL.Image, log).  ``mask_path``: inpainting, see ``denoise_latents``; with ``composite`` the pixels
         the mask keeps are pasted back from the input image after decoding (the VAE round trip alone does not reproduce them).
         ``block_cache``: first-block cache, see ``denoise_latents``; its record goes to ``log["denoising"]["block_cache"]``.
-        ``sampler``: "euler" (default) | "heun" | "ab2", see ``denoise_latents``; ``log["denoising"]["sampler"]`` and ``["model_evals"]`` say what ran.
+        ``sampler``: "euler" (default) | "heun" | "ab2" | "euler_a" | "sde", see ``denoise_latents``; ``log["denoising"]["sampler"]`` and
+        ``["model_evals"]`` say what ran, under the stochastic samplers (``sampler_eta``: euler_a's eta) also ``["eta"]`` and ``["noise_draws"]``.
         ``guidance``, ``guidance_rescale``, ``apg_eta``, ``apg_norm_threshold``, ``apg_momentum``, ``guidance_interval``: see ``denoise_latents``; with any
         of them set, ``log["denoising"]["guidance"]`` is ``self.last_guidance``.
         ``reference_image_path``: reference-image conditioning, see ``denoise_latents``; with it set, ``log["denoising"]["reference"]`` is
@@ -790,7 +815,7 @@ class DiffusionPipeline:
             conditioning, pooled_conditioning, num_steps=num_steps, cfg_weight=cfg_weight,
             latent_size=latent_size, seed=seed, image_path=image_path, denoise=denoise, mask_path=mask_path, block_cache=block_cache,
             sampler=sampler, guidance=guidance, guidance_rescale=guidance_rescale, apg_eta=apg_eta, apg_norm_threshold=apg_norm_threshold,
-            apg_momentum=apg_momentum, guidance_interval=guidance_interval,
+            apg_momentum=apg_momentum, guidance_interval=guidance_interval, **({} if sampler_eta is None else {"sampler_eta": sampler_eta}),
             **({} if reference_image_path is None else {"reference_image_path": reference_image_path}),
             **({} if condition_image_path is None else {"condition_image_path": condition_image_path, "condition_mask_path": condition_mask_path}),
             **({} if skip_layer_guidance is None and skip_layers is None and skip_layer_interval is None else
@@ -1379,12 +1404,14 @@ def _set_rows(model: "CFGDenoiser", lp: _Loop, guided: bool, fork: bool = False)
     return tok, torch.empty_like(tok)
 
 
-def _step_loop(model: "CFGDenoiser", lp: _Loop, plan, grows, guide=None, euler: bool = False, srows=None):
+def _step_loop(model: "CFGDenoiser", lp: _Loop, plan, grows, guide=None, euler: bool = False, srows=None, noise_seeds=None):
     """The host loop behind ``sample_euler`` and ``sample_steps``: per (row, guidance row) one model evaluation -- the engine's head, the policy's
     decision and the chosen tail under the first-block cache -- and one launch of the update, with one device synchronisation per step (the
     reference's mx.eval(x)), which provides iter_time.  ``euler``: the rows are the schedule's Euler rows and the update is dk_euler_cfg_step, the
     reference's statement, instead of the coefficient-row entry.  ``srows`` (``sampler.slg_rows``; None: no row): the evaluations that carry the forked
-    third row group and end in dk_slg_cfg_step.  The operators are looked up on ``ops`` at every call."""
+    third row group and end in dk_slg_cfg_step.  A row with a noise term (``cn != 0``: the stochastic samplers) ends in dk_noisy_cfg_step with the same
+    groups instead, the noise drawn in that launch from ``noise_seeds`` (one Python int per image, uploaded once, here).  The operators are looked up on
+    ``ops`` at every call."""
     from . import ops
     from .sampler import block_cache_rel
     pipe, mm, _, cfg_weight, cfg_on, n_img, policy, x, mask, x_orig, noise, tok, out = lp[:13]
@@ -1398,6 +1425,11 @@ def _step_loop(model: "CFGDenoiser", lp: _Loop, plan, grows, guide=None, euler: 
     if mode == "apg" and beta != 0.0 and any(g.feeds for g in grows):
         mbuf = torch.empty_like(x)  # (never initialised: the first guided row of a stretch does not read it)
     blend = () if mask is None else (x_orig, noise, mask)
+    seeds = None
+    if any(r.cn != 0.0 for r in plan):
+        if noise_seeds is None or len(noise_seeds) != n_img:
+            raise ValueError(f"the plan has rows with a noise term: extra_args['noise_seeds'] must hold one seed per image ({n_img})")
+        seeds = ops.seed_tensor(noise_seeds, x.device)
     n_steps = sum(r.ends_step for r in plan)
     record = {"threshold": getattr(policy, "threshold", None), "computed": [], "skipped": [], "rel": []}
     iter_time = []
@@ -1437,7 +1469,13 @@ def _step_loop(model: "CFGDenoiser", lp: _Loop, plan, grows, guide=None, euler: 
         args = (x, out, tok, n_img, on, pcfg.patch_size, int(pcfg.patchify_via_reshape), r.sigma, r.sigma_next, cfg_weight)
         if not euler:
             args += (hist, (r.cx, r.cd, r.ch, r.hx, r.hd), r.reads_h, r.writes_h)
-        if fork:
+        if r.cn != 0.0:  # (the same groups as the branches below, spelled out as flags)
+            group = dict(guided=True, mode=mode, workspace=gws, **({} if guide is None else dict(
+                rescale=guide["guidance_rescale"], eta=guide["apg_eta"], norm_threshold=guide["apg_norm_threshold"])), momentum=beta,
+                reads_m=mbuf is not None and not g.first, writes_m=mbuf is not None and g.feeds, m=mbuf) if fork or on and mode != "cfg" else {}
+            ops.noisy_cfg_step(*args, cn=r.cn, seeds=seeds, draw=r.draw, slg_scale=lp.forked["scale"] if fork else None, **group,
+                               **dict(zip(("x_orig", "noise", "mask"), blend)))
+        elif fork:
             ops.slg_cfg_step(*args, slg_scale=lp.forked["scale"], mode=mode, workspace=gws, **({} if guide is None else dict(
                 rescale=guide["guidance_rescale"], eta=guide["apg_eta"], norm_threshold=guide["apg_norm_threshold"])), momentum=beta,
                 reads_m=mbuf is not None and not g.first, writes_m=mbuf is not None and g.feeds, m=mbuf, **dict(zip(("x_orig", "noise", "mask"), blend)))
@@ -1501,10 +1539,13 @@ def sample_steps(model: CFGDenoiser, x: Tensor, sigmas, plan, extra_args=None):
     ``model.guidance_record``.
     Skip-layer guidance: ``extra_args["skip_layer_guidance"]`` ({"scale", "layers", "interval"}, ``_skip_layer_options``) gives the evaluations of
     ``sampler.slg_rows`` a third row group, forked inside the engine, and dk_slg_cfg_step as their update; ``_set_rows`` re-prepares the engine where the
-    window begins and ends, and the engine's skip layers are off again when the loop returns or raises.  What ran goes to ``model.skip_layer_record``."""
+    window begins and ends, and the engine's skip layers are off again when the loop returns or raises.  What ran goes to ``model.skip_layer_record``.
+    Stochastic samplers: a plan with noise terms (``step_plan("euler_a" | "sde", ...)``) needs ``extra_args["noise_seeds"]``, one integer in [0, 2^64)
+    per image; its rows end in dk_noisy_cfg_step, which draws the noise in the launch."""
     plan = list(plan)
     guide = None if extra_args is None else extra_args.get("guidance")
     slg = None if extra_args is None else extra_args.get("skip_layer_guidance")
+    seeds = None if extra_args is None else extra_args.get("noise_seeds")
     grows = guidance_rows(plan, None if guide is None else guide["interval"])
     lp = _loop_setup(model, x, sigmas, extra_args, guided=grows[0].guided if grows else True)
     if guide is not None and not lp.cfg_on:
@@ -1525,13 +1566,13 @@ def sample_steps(model: CFGDenoiser, x: Tensor, sigmas, plan, extra_args=None):
         raise ValueError("the plan evaluates the model outside the schedule (or at its last entry): build it with sampler.step_plan on these sigmas")
     if lp.forked is None:
         try:
-            return _step_loop(model, lp, plan, grows, guide)
+            return _step_loop(model, lp, plan, grows, guide, noise_seeds=seeds)
         finally:
             if lp.control is not None:  # (the main engine's taps are off again when the loop returns or raises)
                 lp.mm.set_control_taps(None)
     window = lp.forked["interval"]  # (None, perturbed-attention guidance only: every guided row)
     srows = [bool(g.guided) for g in grows] if window is None else slg_rows(plan, grows, *window)
     try:
-        return _step_loop(model, lp, plan, grows, guide, srows=srows)
+        return _step_loop(model, lp, plan, grows, guide, srows=srows, noise_seeds=seeds)
     finally:
         lp.set_fork(False)

@@ -93,22 +93,40 @@ def max_denoise(sampler, sigmas) -> bool:
 
 # ---- step plans: the update of every model evaluation as a coefficient row (host; no reference counterpart) --------------------------------
 SAMPLERS = ("euler", "heun", "ab2")
+#: the samplers whose rows carry a noise term (cn xi, drawn inside the step launch: "stochastic samplers" below); every name ``step_plan`` takes
+STOCHASTIC_SAMPLERS = ("euler_a", "sde")
+ALL_SAMPLERS = SAMPLERS + STOCHASTIC_SAMPLERS
 
 
 def check_sampler(name) -> str:
     """None -> "euler"; an unknown name raises a ValueError that lists the valid ones"""
     if name is None:
         return "euler"
-    if name not in SAMPLERS:
-        raise ValueError(f"unknown sampler {name!r}: valid samplers are {', '.join(SAMPLERS)}")
+    if name not in ALL_SAMPLERS:
+        raise ValueError(f"unknown sampler {name!r}: valid samplers are {', '.join(ALL_SAMPLERS)}")
     return name
+
+
+def check_sampler_eta(name, eta) -> float:
+    """``sampler_eta`` of a checked sampler name -> the eta of ``euler_a`` (None: 1.0); with any other sampler a value raises, and so does one outside
+    [0, 1] or NaN"""
+    if eta is None:
+        return 1.0
+    if name != "euler_a":
+        raise ValueError(f"sampler_eta belongs to sampler 'euler_a' alone, not to {name!r}")
+    eta = float(eta)
+    if not 0.0 <= eta <= 1.0:
+        raise ValueError(f"sampler_eta must lie in [0, 1], got {eta}")
+    return eta
 
 
 class StepRow(NamedTuple):
     """One model evaluation and the update behind it (dk_lms_cfg_step):  d = (x - den) / sigma,  x' = cx x + cd d + ch H,  H' = hx x + hd d.
     ``index``: which entry of the schedule the model is evaluated at (also the row of the cached modulation table); ``sigma`` = sigmas[index];
     ``sigma_next``: the sigma x' lives at (the masked blend re-noises the known region to it); ``reads_h`` / ``writes_h``: whether the row takes
-    the history buffer / leaves one for a later row; ``ends_step``: x' is the state at the next entry of the schedule."""
+    the history buffer / leaves one for a later row; ``ends_step``: x' is the state at the next entry of the schedule.
+    Stochastic samplers: x' takes one more term, cn xi, xi the image's own standard normals of draw ``draw`` (``philox_normal_reference``); cn == 0
+    (every row of the deterministic samplers, where ``draw`` stays -1): no term, the launch as it was."""
     index: int
     sigma: float
     sigma_next: float
@@ -120,6 +138,8 @@ class StepRow(NamedTuple):
     reads_h: bool
     writes_h: bool
     ends_step: bool
+    cn: float = 0.0
+    draw: int = -1
 
 
 def _row(index, sigma, sigma_next, cd, ch=0.0, reads_h=False, writes_h=False, ends_step=True) -> StepRow:
@@ -129,23 +149,55 @@ def _row(index, sigma, sigma_next, cd, ch=0.0, reads_h=False, writes_h=False, en
                    bool(writes_h), bool(ends_step))
 
 
-def step_plan(name, sigmas) -> List[StepRow]:
+def _noisy_row(index, sigma, sigma_next, cx, cd, cn, draw) -> StepRow:
+    # (a first-order row with its own cx and a noise term; rounded to the kernel's float32 once, like ``_row``)
+    f = lambda v: float(_F(v))  # noqa: E731
+    return StepRow(int(index), f(sigma), f(sigma_next), f(cx), f(cd), 0.0, 0.0, 0.0, False, False, True, f(cn), int(draw))
+
+
+def euler_a_coefficients(sigma, sigma_next, eta):
+    """(sigma_down, cx, cd, cn) of one ancestral step of a rectified flow, in float64 (k-diffusion's sample_euler_ancestral_RF):
+    sigma_down = sigma' (1 + (sigma' / sigma - 1) eta), a = (1 - sigma') / (1 - sigma_down), cx = a, cd = a (sigma_down - sigma),
+    cn = sqrt(sigma'^2 - sigma_down^2 a^2).  sigma_down == 1 (sigma' = 1: a schedule that does not leave pure noise) is refused."""
+    sigma, sigma_next, eta = float(sigma), float(sigma_next), float(eta)
+    down = sigma_next * (1.0 + (sigma_next / sigma - 1.0) * eta)
+    if down == 1.0:
+        raise ValueError(f"euler_a: the step {sigma} -> {sigma_next} has sigma_down = 1: the schedule must leave sigma = 1 after its first entry")
+    a = (1.0 - sigma_next) / (1.0 - down)
+    return down, a, a * (down - sigma), math.sqrt(max(sigma_next * sigma_next - down * down * a * a, 0.0))
+
+
+def step_plan(name, sigmas, eta=None, first_draw: int = 0) -> List[StepRow]:
     """The ordered rows that take x from sigmas[0] to sigmas[-1], computed in float64 from the float32 schedule, with h = sigmas[i+1] - sigmas[i]:
     euler  one row (1, h, 0) per step -- h is exact in float64, so its rounding is the float32 difference dk_euler_cfg_step takes;
     heun   the trapezoid rule: the predictor (1, h, 0) at sigmas[i] leaves H = d, the corrector at sigmas[i+1], evaluated on the predicted
            state, is (1, h/2, -h/2): x + (h/2)(d1 + d2).  The model is never evaluated at sigma = 0: a step that ends there is its Euler row;
     ab2    variable-step Adams-Bashforth 2: the first row is Euler and leaves H = d; later ones are (1, h(1 + w), -h w), w = h / (2 h_prev),
            H = d; a step that ends at sigma = 0 is its Euler row here too.
-    A row writes H only if the next row reads it.  A schedule cut by ``denoise`` starts at its first remaining entry, first-order."""
+    A row writes H only if the next row reads it.  A schedule cut by ``denoise`` starts at its first remaining entry, first-order.
+    The stochastic samplers, first order, one evaluation per step.  A row with a noise term has draw = ``first_draw`` + its index: the whole schedule
+    has draw == index, and a schedule cut by ``denoise`` keeps the draws of the entries it keeps when the caller passes the number of entries cut
+    as ``first_draw`` (the index itself counts from the entries given here: it is also the row of the modulation table).  A row without one -- a step
+    that ends at sigma = 0, every row under eta = 0 -- is the Euler row, draw = -1 like the deterministic samplers' rows.
+    euler_a  ``euler_a_coefficients`` with ``eta`` in [0, 1] (None: 1); eta = 0 gives euler's rows exactly;
+    sde      diffusers' FlowMatchEulerDiscreteScheduler(stochastic_sampling=True): x' = (1 - sigma') den + sigma' xi, i.e. (cx, cd, cn) =
+             (1 - sigma', -(1 - sigma') sigma, sigma').  Every step re-draws all of the noise; at a finite number of steps this does not preserve the
+             marginals of a mean-predicting denoiser (tests/test_stochastic_cpu.py tabulates it).  It is here as the published definition, nothing more."""
     name = check_sampler(name)
+    eta = check_sampler_eta(name, eta)
     s = [float(v) for v in np.asarray(sigmas, dtype=_F)]
     n = len(s) - 1
     rows: List[StepRow] = []
     for i in range(n):
         h = s[i + 1] - s[i]
         last = s[i + 1] == 0.0
-        if name == "euler" or last and name == "heun":
-            rows.append(_row(i, s[i], s[i + 1], h))
+        if name == "euler" or last and name in ("heun", "euler_a", "sde") or name == "euler_a" and eta == 0.0:
+            rows.append(_row(i, s[i], s[i + 1], h))  # (sde at sigma' = 0: (1, -sigma, 0), which is this row)
+        elif name == "euler_a":
+            _, cx, cd, cn = euler_a_coefficients(s[i], s[i + 1], eta)
+            rows.append(_noisy_row(i, s[i], s[i + 1], cx, cd, cn, int(first_draw) + i))
+        elif name == "sde":
+            rows.append(_noisy_row(i, s[i], s[i + 1], 1.0 - s[i + 1], -(1.0 - s[i + 1]) * s[i], s[i + 1], int(first_draw) + i))
         elif name == "heun":
             rows.append(_row(i, s[i], s[i + 1], h, writes_h=True, ends_step=False))
             rows.append(_row(i + 1, s[i + 1], s[i + 1], h / 2, -h / 2, reads_h=True))
@@ -157,6 +209,58 @@ def step_plan(name, sigmas) -> List[StepRow]:
                 w = h / (2.0 * (s[i] - s[i - 1]))
                 rows.append(_row(i, s[i], s[i + 1], h * (1.0 + w), -h * w, reads_h=True, writes_h=feeds))
     return rows
+
+
+# ---- the noise of the stochastic samplers: Philox4x32-10 and Box-Muller, the definition the device function restates (no reference counterpart) -------
+_PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_M32 = 0xFFFFFFFF
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 (Salmon et al., SC'11; Random123's known answers hold): ``counter`` = four and ``key`` = two 32-bit words, each an int or an array
+    of uint64 holding values below 2^32 (arrays broadcast) -> the four output words, of the same kind.  One round:
+    c' = (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)); the key takes its Weyl increments between rounds."""
+    arr = any(isinstance(v, np.ndarray) for v in tuple(counter) + tuple(key))
+    cast = (lambda v: np.asarray(v, dtype=np.uint64)) if arr else int
+    c0, c1, c2, c3 = (cast(v) for v in counter)
+    k0, k1 = (cast(v) for v in key)
+    m0, m1, w0, w1, lo = (cast(v) for v in (_PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1, _M32))
+    sh = cast(32)
+    for _ in range(10):
+        p0, p1 = m0 * c0, m1 * c2  # (below 2^64: exact in uint64)
+        c0, c1, c2, c3 = (p1 >> sh) ^ c1 ^ k0, p1 & lo, (p0 >> sh) ^ c3 ^ k1, p0 & lo
+        k0, k1 = (k0 + w0) & lo, (k1 + w1) & lo
+    return c0, c1, c2, c3
+
+
+def philox_normal_reference(seed, draw, n, stream=0, quad_offset=0) -> np.ndarray:
+    """The ``n`` (a multiple of 4) standard normals of one image, float64: quad q = quad_offset + r // 4 of element r is the Philox block of the counter
+    (q & 0xffffffff, q >> 32, draw, stream) under the key (seed & 0xffffffff, seed >> 32), 0 <= seed < 2^64; a block (o0, o1, o2, o3) gives four
+    normals by Box-Muller on 24-bit uniforms, u = ((o_a >> 8) + 1) 2^-24 in (0, 1], theta = 2 pi (o_b >> 8) 2^-24, z_a = sqrt(-2 ln u) cos theta,
+    z_b = sqrt(-2 ln u) sin theta, with the pairs (o0, o1) -> z0, z1 and (o2, o3) -> z2, z3; element r takes z[r % 4].  ``stream`` 0: step noise."""
+    seed, draw, n, stream, quad_offset = int(seed), int(draw), int(n), int(stream), int(quad_offset)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"the seed must lie in [0, 2^64), got {seed}")
+    if n % 4 != 0 or n < 0:
+        raise ValueError(f"n must be a multiple of 4, got {n}")
+    q = np.arange(n // 4, dtype=np.uint64) + np.uint64(quad_offset)
+    o = philox4x32_10((q & np.uint64(_M32), q >> np.uint64(32), np.uint64(draw & _M32), np.uint64(stream & _M32)), (seed & _M32, seed >> 32))
+    z = np.empty((n // 4, 4), dtype=np.float64)
+    for a in (0, 2):
+        u = ((o[a] >> np.uint64(8)).astype(np.float64) + 1.0) * 2.0 ** -24
+        theta = 2.0 * math.pi * ((o[a + 1] >> np.uint64(8)).astype(np.float64) * 2.0 ** -24)
+        rad = np.sqrt(-2.0 * np.log(u))
+        z[:, a], z[:, a + 1] = rad * np.cos(theta), rad * np.sin(theta)
+    return z.reshape(-1)
+
+
+def stochastic_reference(x, den, row, xi):
+    """One row in float64 numpy: d = (x - den) / sigma, x' = cx x + cd d + cn xi (``row`` a first-order StepRow; ``xi`` shaped like x, ignored where
+    cn == 0)"""
+    x, den = np.asarray(x, dtype=np.float64), np.asarray(den, dtype=np.float64)
+    out = row.cx * x + row.cd * ((x - den) / row.sigma)
+    return out + row.cn * np.asarray(xi, dtype=np.float64) if row.cn != 0.0 else out
 
 
 # ---- guidance modes: how the two predictions of a guided evaluation are combined (no reference counterpart) ---------------------------------

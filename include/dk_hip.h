@@ -519,6 +519,45 @@ int dk_slg_cfg_step_f16(float* x, const void* model_out, int32_t ld_out, void* t
                         float eta, float r, float beta, int32_t reads_m, int32_t writes_m, float* m, void* workspace,
                         size_t workspace_bytes, float slg_scale, void* stream);
 
+/* Stochastic samplers (no reference counterpart; k-diffusion's sample_euler_ancestral_RF and diffusers'
+ * FlowMatchEulerDiscreteScheduler(stochastic_sampling=True) as coefficient rows, sampler.step_plan): the noise is drawn inside the launch.
+ * The generator, defined here and restated on the host by sampler.philox4x32_10 / sampler.philox_normal_reference:
+ *   Philox4x32-10 (Salmon et al., SC'11): multipliers 0xD2511F53, 0xCD9E8D57, key increments 0x9E3779B9, 0xBB67AE85, ten rounds of
+ *     c' = (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0));
+ *   key (seed & 0xffffffff, seed >> 32), seed the image's own; counter (q & 0xffffffff, q >> 32, draw, stream), q = r / 4 with r the
+ *     element's index inside its image, draw the schedule index of the row, stream a use tag (0: step noise; other values are reserved);
+ *   a block (o0, o1, o2, o3) gives four normals by Box-Muller on 24-bit uniforms: u = ((o_a >> 8) + 1) 2^-24 in (0, 1], theta =
+ *     2 pi (o_b >> 8) 2^-24, z_a = sqrt(-2 ln u) cos theta, z_b = sqrt(-2 ln u) sin theta, pairs (o0, o1) -> z0, z1 and (o2, o3) -> z2, z3;
+ *     element r takes z[r % 4].
+ * A value depends on (seed, r, draw, stream) alone: not on the image's place in the batch, on n_img, on CFG or on the element type.
+ *
+ * dk_philox_normal_f32: out f32 [n_img, n_per_img], row j = the normals of seeds[j] (u64 [n_img] on the device) for the quads quad_offset,
+ * quad_offset + 1, ... (quad_offset reaches the counter's second word without a 2^34-element tensor).  n_per_img % 4 == 0; draw, stream >= 0. */
+int dk_philox_normal_f32(float* out, const uint64_t* seeds, int32_t n_img, int64_t n_per_img, int32_t draw, int32_t stream_tag,
+                         uint64_t quad_offset, void* stream);
+/* dk_noisy_cfg_step: dk_slg_cfg_step's argument list, then the flags that entry implies -- guided (0: the guidance group is not read and mode
+ * must be 0; the row may then run with cfg_on = 0, as FLUX does) and slg (0: two row groups, slg_scale is not read) -- and the noise term:
+ *   x' = cx x + cd d [+ ch hist] + cn xi(seeds[img], draw, r),
+ * behind the update and in front of the masked blend; xi is formed in registers by the function dk_philox_normal_f32 runs (stream 0, quad_offset
+ * 0): no noise buffer is read or written, and x' with (cx, cd, cn) = (0, 0, 1) is that operator's output bit for bit, up to the sign of zero.
+ * Every case of the row kernel is reachable: masked, the three modes, the third row group, both element types.  cn == 0 launches exactly what
+ * dk_lms_cfg_step / _masked / dk_guided_cfg_step / dk_slg_cfg_step launch for the same groups -- their kernels, their bits -- and reads neither
+ * seeds nor draw.  Refused with a dk_last_error() text, nothing written: a non-finite cn; cn != 0 with seeds null or draw < 0; Hl * Wl * C not
+ * a multiple of 4; guided == 0 with mode != 0; and whatever the groups' own entries refuse.  _f16: model_out and tokens are fp16. */
+int dk_noisy_cfg_step(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on, int32_t Hl, int32_t Wl,
+                      int32_t C, int32_t p, int32_t reshape_order, float sigma, float cfg_weight, float* hist, float cx, float cd,
+                      float ch, float hx, float hd, float sigma_next, int32_t reads_h, int32_t writes_h, const float* x_orig,
+                      const float* noise, const float* mask, int32_t mask_per_image, int32_t mode, float phi, float eta, float r,
+                      float beta, int32_t reads_m, int32_t writes_m, float* m, void* workspace, size_t workspace_bytes, float slg_scale,
+                      int32_t guided, int32_t slg, float cn, const uint64_t* seeds, int32_t draw, void* stream);
+int dk_noisy_cfg_step_f16(float* x, const void* model_out, int32_t ld_out, void* tokens, int32_t n_img, int32_t cfg_on, int32_t Hl,
+                          int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float sigma, float cfg_weight, float* hist, float cx,
+                          float cd, float ch, float hx, float hd, float sigma_next, int32_t reads_h, int32_t writes_h,
+                          const float* x_orig, const float* noise, const float* mask, int32_t mask_per_image, int32_t mode, float phi,
+                          float eta, float r, float beta, int32_t reads_m, int32_t writes_m, float* m, void* workspace,
+                          size_t workspace_bytes, float slg_scale, int32_t guided, int32_t slg, float cn, const uint64_t* seeds,
+                          int32_t draw, void* stream);
+
 /* Inpainting mask, pixels -> latent cells: mask u8 [n_mask,H,W] (255 = repaint, 0 = keep) -> f32 [n_mask,H/f,W/f],
  * (integer sum of the f x f block) / (f * f * 255) by a true division: an all-0 block gives 0.0f, an all-255 block 1.0f.
  * H and W must be multiples of f (the pipeline passes the VAE's factor, 8). */
