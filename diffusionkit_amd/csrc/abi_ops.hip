@@ -775,13 +775,15 @@ int groupnorm_table_launch(int dtype, const void* x, int B, long HW, int C, int 
                            float* scratch, int n_partial, float* scale_shift, hipStream_t st) {  // (dk_engine.h)
   DK_REQUIRE(gamma && beta && scratch && scale_shift && B > 0 && G > 0 && C % G == 0, "groupnorm table arguments");
   DK_REQUIRE(x != nullptr || n_partial > 0, "either x or the number of partials a conv launch left in scratch");
+  // (the finalisation takes every partial of a conv launch for one 16 x 16-pixel tile: it weighs the pairs by their element counts)
+  DK_REQUIRE(x != nullptr || (long)n_partial * 256 == HW, "partials of a conv launch: one per 16 x 16-pixel tile, n_partial * 256 == HW");
   const int nchunk = x ? gn_nchunk(HW, C) : n_partial;
   float* mean_rstd = scratch + (size_t)B * (nchunk > 1024 ? nchunk : 1024) * 2 * G;
   if (x) {  // the partial sums only: the one finalisation below builds mean / rstd AND the table
     const int rc = DK_EL(dtype, dk_launch_groupnorm_partials)((const bf16_t*)x, B, HW, C, G, scratch, nchunk, st);
     if (rc) return rc;
   }
-  return DK_EL(dtype, dk_launch_groupnorm_finalize)(scratch, nchunk, B, G, (double)HW * (double)(C / G), eps, mean_rstd, (const bf16_t*)gamma,
+  return DK_EL(dtype, dk_launch_groupnorm_finalize)(scratch, nchunk, B, G, HW, eps, mean_rstd, (const bf16_t*)gamma,
                                                     (const bf16_t*)beta, C, scale_shift, st);
 }
 extern "C" int dk_groupnorm_table_bf16(const void* x, int32_t B, int64_t HW, int32_t C, int32_t G, const void* gamma, const void* beta,

@@ -177,7 +177,7 @@ __global__ __launch_bounds__(256, 1) void dk_conv256v4_kernel(ConvHaloParams p) 
       }
     }
   }
-  float ssum[4][8], ssq[4][8];
+  float ssum[4][8], ssq[4][8], spv[8];
 #pragma unroll
   for (int pass = 0; pass < 4; ++pass) {
     const int wn = 2 * wn2 + (pass >> 1), ni = pass & 1;
@@ -206,23 +206,31 @@ __global__ __launch_bounds__(256, 1) void dk_conv256v4_kernel(ConvHaloParams p) 
         for (int e = 0; e < 4; ++e) {
           float v0, v1;
           unpack2bf(sv[e], v0, v1);
+          if (itr == 0) spv[2 * e] = v0, spv[2 * e + 1] = v1;  // the pivot of a channel: this lane's first pixel row
+          v0 -= spv[2 * e], v1 -= spv[2 * e + 1];
           ssum[pass][2 * e] += v0, ssq[pass][2 * e] += v0 * v0;
           ssum[pass][2 * e + 1] += v1, ssq[pass][2 * e + 1] += v1 * v1;
         }
       }
     }
+    if (p.stats_out) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) dk_gn_from_pivot(ssum[pass][e], ssq[pass][e], spv[e], (float)PR);
+    }
   }
   if (p.stats_out) {
-    // this lane's pixel rows -> over the 16 x positions (lane bits 2..5, fixed tree) -> LDS [wave][128 columns][2] -> per group over its
-    // channels and the waves that share its columns (two of a column half; NT = 128: all four), in a fixed order
+    // per channel (sum, M2) of this lane's pixel rows (dk_kernels.h: sums about a pivot, pairs merged pairwise) -> over the 16 x positions
+    // (lane bits 2..5, fixed tree) -> LDS [wave][128 columns][2] -> per group over its channels and the waves that share its columns (two of
+    // a column half; NT = 128: all four), in a fixed order
 #pragma unroll
     for (int pass = 0; pass < 4; ++pass)
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
+        float inv_2n = 0.5f / (float)PR;
 #pragma unroll
         for (int o = 4; o < 64; o <<= 1) {
-          ssum[pass][e] += __shfl_xor(ssum[pass][e], o, 64);
-          ssq[pass][e] += __shfl_xor(ssq[pass][e], o, 64);
+          dk_gn_merge_equal(ssum[pass][e], ssq[pass][e], __shfl_xor(ssum[pass][e], o, 64), __shfl_xor(ssq[pass][e], o, 64), inv_2n);
+          inv_2n *= 0.5f;
         }
       }
     if (rrow == 0) {
@@ -239,20 +247,33 @@ __global__ __launch_bounds__(256, 1) void dk_conv256v4_kernel(ConvHaloParams p) 
     const int cpg = p.O / p.G_out;  // channels per group
     const int gpt = NT / cpg;       // groups of this tile
     if (tid < 2 * gpt) {
+      // the group's cpg * NW pairs hold 16 PR values each (a wave's PR pixel rows of a column): sum = the sum of the sums,
+      // M2 = sum of the M2 + sum (sum_i - sum / pairs)^2 / (16 PR) -- no division in the loop
       const int g = tid >> 1, stat = tid & 1;
-      float a = 0.f;
-      for (int c = 0; c < cpg; ++c) {
+      constexpr int NW = N128 ? 4 : 2;
+      auto pair_at = [&](int c, int m) {
         const int ch = g * cpg + c;  // channel inside the tile: column half ch >> 7 (wave wn2), column ch & 127 of the wave
-        if constexpr (N128) {
-          for (int m = 0; m < 4; ++m)
-            a += *(const __attribute__((address_space(3))) float*)(lds + C4_RED_LDS + ((m * 128 + ch) * 2 + stat) * 4);
-        } else {
-          for (int m = 0; m < 2; ++m)
-            a += *(const __attribute__((address_space(3))) float*)(lds + C4_RED_LDS + ((((m * 2 + (ch >> 7)) * 128) + (ch & 127)) * 2 + stat) * 4);
+        return (unsigned)(C4_RED_LDS + ((N128 ? m * 128 + ch : ((m * 2 + (ch >> 7)) * 128) + (ch & 127)) * 2) * 4);
+      };
+      // one pass: the sums about the first pair's sum (a pivot again: sum (d_i - mean d)^2 = sum d_i^2 - (sum d_i)^2 / pairs)
+      const float s0 = *(const __attribute__((address_space(3))) float*)(lds + pair_at(0, 0));
+      float a = 0.f, m2 = 0.f, dev = 0.f;
+      for (int c = 0; c < cpg; ++c)
+        for (int m = 0; m < NW; ++m) {
+          const unsigned at = pair_at(c, m);
+          const float d = *(const __attribute__((address_space(3))) float*)(lds + at) - s0;
+          a += d;
+          if (stat) {
+            dev = fmaf(d, d, dev);
+            m2 += *(const __attribute__((address_space(3))) float*)(lds + at + 4);
+          }
         }
-      }
+      const float pairs = (float)(cpg * NW);
+      dev -= a * a * (1.0f / pairs);
+      m2 = fmaf(dev < 0.f ? 0.f : dev, 1.0f / (16.0f * (float)PR), m2);
+      a = fmaf(pairs, s0, a);
       const int tiles_img = tiles_x * tiles_y;
-      p.stats_out[(((size_t)b * tiles_img + (pt % tiles_img)) * p.G_out + (n0 / cpg + g)) * 2 + stat] = a;
+      p.stats_out[(((size_t)b * tiles_img + (pt % tiles_img)) * p.G_out + (n0 / cpg + g)) * 2 + stat] = stat ? m2 : a;
     }
   }
 }

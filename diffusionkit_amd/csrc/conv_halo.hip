@@ -25,7 +25,7 @@
 //   (first version, one set of reads per K-tile behind the barrier: 760-915 TFLOP/s; profiles/r03_vae_kernel_stats_halo_v1.md).
 // Optional K extension (x2): the 1x1 conv_shortcut of a channel-changing resnet (vae.py:86-89,98-99) as extra K-tiles over the
 // raw block input (centre tap only, no transform) -- the shortcut never exists as a tensor.
-// Optional statistics of the OUTPUT (stats_out): per workgroup the (sum, sum of squares) of the stored bf16 values per output
+// Optional statistics of the OUTPUT (stats_out): per workgroup the (sum, M2 about the tile's own mean) of the stored bf16 values per output
 // channel group -- the partials dk_gn_finalize_kernel combines for the GroupNorm that reads this tensor next.
 // NT = 16 (IMG): conv_out (3 of 16 columns live) with the clip / uint8 / float image tail of dk_image_post_kernel fused.
 #include "dk_kernels.h"
@@ -417,9 +417,9 @@ __global__ __launch_bounds__(512, 2) void dk_conv_halo_kernel(ConvHaloParams p) 
     // (same wave writes and reads its image: program order + the compiler's lgkmcnt suffice)
     const int rr = lane >> 3, rc = lane & 7;
     const int ocol = n0 + wn * 64 + rc * 8;
-    float ssum[8], ssq[8];
+    float ssum[8], ssq[8], spv[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) ssum[e] = ssq[e] = 0.f;
+    for (int e = 0; e < 8; ++e) ssum[e] = ssq[e] = spv[e] = 0.f;
     // the residual rows of all eight passes up front: one memory latency instead of eight (the compiler cannot move a load of
     // `res` above a store to `y` -- the two may alias for all it knows)
     u32x4 resv[8];
@@ -452,21 +452,25 @@ __global__ __launch_bounds__(512, 2) void dk_conv_halo_kernel(ConvHaloParams p) 
         for (int e = 0; e < 4; ++e) {
           float v0, v1;
           unpack2(sv[e], v0, v1);
+          if (pass == 0) spv[2 * e] = v0, spv[2 * e + 1] = v1;  // the pivot of a channel: this lane's first pixel
+          v0 -= spv[2 * e], v1 -= spv[2 * e + 1];
           ssum[2 * e] += v0, ssq[2 * e] += v0 * v0;
           ssum[2 * e + 1] += v1, ssq[2 * e + 1] += v1 * v1;
         }
       }
     }
     if (p.stats_out) {
-      // per-channel sums of this lane's 8 pixels -> over the 8 row lanes of the wave (lane bits 3..5, fixed tree) -> LDS ->
-      // per-group sums over the 4 waves of a column half and the group's channels, in a fixed order (no atomics: the statistics,
-      // and with them the decoded image, stay bit-reproducible)
+      // per channel (sum, M2) of this lane's 8 pixels (dk_kernels.h: sums about a pivot, pairs merged pairwise) -> over the 8 row lanes of
+      // the wave (lane bits 3..5, fixed tree) -> LDS -> per group over the 4 waves of a column half and the group's channels, in a fixed
+      // order (no atomics: the statistics, and with them the decoded image, stay bit-reproducible)
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
+        dk_gn_from_pivot(ssum[e], ssq[e], spv[e], 8.f);
+        float inv_2n = 1.0f / 16.0f;
 #pragma unroll
         for (int o = 8; o < 64; o <<= 1) {
-          ssum[e] += __shfl_xor(ssum[e], o, 64);
-          ssq[e] += __shfl_xor(ssq[e], o, 64);
+          dk_gn_merge_equal(ssum[e], ssq[e], __shfl_xor(ssum[e], o, 64), __shfl_xor(ssq[e], o, 64), inv_2n);
+          inv_2n *= 0.5f;
         }
       }
       __syncthreads();  // every wave is done with its staging image
@@ -483,15 +487,32 @@ __global__ __launch_bounds__(512, 2) void dk_conv_halo_kernel(ConvHaloParams p) 
       const int cpg = p.O / p.G_out;          // channels per group
       const int gpt = NT / cpg;               // groups of this N-tile
       if (tid < 2 * gpt) {
+        // the group's cpg * WM pairs hold 64 values each (a wave's 64 pixels of a channel): sum = the sum of the sums,
+        // M2 = sum of the M2 + sum (sum_i - sum / pairs)^2 / 64 -- no division in the loop
         const int g = tid >> 1, stat = tid & 1;
-        float a = 0.f;
-        for (int c = 0; c < cpg; ++c) {
+        auto pair_at = [&](int c, int w4) {
           const int ch = g * cpg + c;         // channel inside the N-tile: column half ch >> 6, channel ch & 63 of the half
-          for (int w4 = 0; w4 < WM; ++w4)
-            a += *(const __attribute__((address_space(3))) float*)(lds + (((w4 * WN + (ch >> 6)) * 64 + (ch & 63)) * 2 + stat) * 4);
-        }
+          return (unsigned)((((w4 * WN + (ch >> 6)) * 64 + (ch & 63)) * 2) * 4);
+        };
+        // one pass: the sums about the first pair's sum (a pivot again: sum (d_i - mean d)^2 = sum d_i^2 - (sum d_i)^2 / pairs)
+        const float s0 = *(const __attribute__((address_space(3))) float*)(lds + pair_at(0, 0));
+        float a = 0.f, m2 = 0.f, dev = 0.f;
+        for (int c = 0; c < cpg; ++c)
+          for (int w4 = 0; w4 < WM; ++w4) {
+            const unsigned at = pair_at(c, w4);
+            const float d = *(const __attribute__((address_space(3))) float*)(lds + at) - s0;
+            a += d;
+            if (stat) {
+              dev = fmaf(d, d, dev);
+              m2 += *(const __attribute__((address_space(3))) float*)(lds + at + 4);
+            }
+          }
+        const float pairs = (float)(cpg * WM);
+        dev -= a * a * (1.0f / pairs);
+        m2 = fmaf(dev < 0.f ? 0.f : dev, 1.0f / 64.0f, m2);
+        a = fmaf(pairs, s0, a);
         const int tiles_img = tiles_x * tiles_y;
-        p.stats_out[(((size_t)b * tiles_img + (pt % tiles_img)) * p.G_out + (n0 / cpg + g)) * 2 + stat] = a;
+        p.stats_out[(((size_t)b * tiles_img + (pt % tiles_img)) * p.G_out + (n0 / cpg + g)) * 2 + stat] = stat ? m2 : a;
       }
     }
   }

@@ -351,7 +351,7 @@ struct ConvHaloParams {
   int gn_silu;            // SiLU behind that GroupNorm
   const bf16_t* x2;       // 1x1 shortcut input NHWC [B, H, W, C2] (raw), or null
   int C2;
-  float* stats_out;       // [B][tiles per image][G_out][2] (sum, sum of squares) of the stored output, or null
+  float* stats_out;       // [B][tiles per image][G_out][2] (sum, M2 = sum of squared deviations from the tile's own mean) of the stored output, or null
   int G_out;
   float* img;             // image tail (O <= 4): clip(y / 2 + 0.5) f32 [npix, 3]
   unsigned char* u8;      // ... (x 255) truncated to uint8 [npix, 3]
@@ -363,6 +363,21 @@ struct ConvHaloParams {
   int dtype;
 };
 bool dk_conv_halo_eligible(const ConvHaloParams& p, bool img);
+// GroupNorm statistics travel as (sum, M2) pairs, M2 = the sum of squared deviations from the pair's OWN mean, never as a raw sum of squares:
+// E[x^2] - mean^2 in fp32 loses (mean / sigma)^2 ulps of the variance (1e-4 of it at mean / sigma = 32).  Producers sum deviations from a pivot
+// (a value of the data itself) and convert; pairs of equal size are merged with the pairwise update below; dk_gn_finalize_kernel merges the chunks in fp64.
+// n values summed about the pivot `pv` (s = sum (v - pv), q = sum (v - pv)^2) -> (sum, M2)
+__device__ __forceinline__ void dk_gn_from_pivot(float& s, float& q, float pv, float n) {
+  q -= s * s * (1.0f / n);
+  q = q < 0.f ? 0.f : q;  // (not fmaxf: a NaN stays a NaN)
+  s = fmaf(n, pv, s);
+}
+// (s, m2) of n values <- merged with (sb, mb) of as many: m2 += mb + (s - sb)^2 / 2n (commutative: both partners of a butterfly get the same bits)
+__device__ __forceinline__ void dk_gn_merge_equal(float& s, float& m2, float sb, float mb, float inv_2n) {
+  const float d = s - sb;
+  m2 = (m2 + mb) + d * d * inv_2n;
+  s += sb;
+}
 // conv256v4.hip: the same contract in the one-wave-per-SIMD frame (16 x 16 pixels x 256 channels per workgroup, asm body); no shortcut
 // extension, no image tail.  dk_launch_conv_halo routes to it when dk_conv256v4_wanted (dk_tune_set("conv_v4", 0 | 1 | 2))
 extern int g_dk_conv_v4;

@@ -3,9 +3,10 @@
 int dk_launch_conv_halo(const ConvHaloParams& p, hipStream_t stream);      // conv_halo.hip
 int dk_launch_attention512(const Attn512Params& p, hipStream_t stream);    // attention512.hip
 // ---- vae_ops.hip ----
-// the second pass of the GroupNorm statistics alone: per (batch, group) the partials [B][nchunk][G][2] -> mean / rstd, and
+// the second pass of the GroupNorm statistics alone: per (batch, group) the partials [B][nchunk][G][2] = (sum, M2 about the chunk's own mean)
+// of the chunks of HW pixels (statistics pass: ceil(HW / nchunk) pixels each; conv tiles: 256) -> mean / rstd, and
 // (gamma given) the per-channel table scale_shift [B][2][C]: scale = rstd * gamma, shift = beta - mean * scale
-int dk_launch_groupnorm_finalize(const float* partial, int nchunk, int B, int G, double count, float eps, float* mean_rstd,
+int dk_launch_groupnorm_finalize(const float* partial, int nchunk, int B, int G, long HW, float eps, float* mean_rstd,
                                  const bf16_t* gamma, const bf16_t* beta, int C, float* scale_shift, hipStream_t stream);
 int dk_launch_groupnorm_partials(const bf16_t* x, int B, long HW, int C, int G, float* partial, int nchunk, hipStream_t stream);
 int dk_launch_groupnorm_stats(const bf16_t* x, int B, long HW, int C, int G, float* partial, int nchunk,

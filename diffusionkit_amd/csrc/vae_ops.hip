@@ -8,12 +8,13 @@
 // ---------------------------------------------------------------------------------------------
 // GroupNorm statistics (nn.GroupNorm(pytorch_compatible=True): per (batch, group) mean / variance
 // over H*W*(C/G) elements, fp32).  Pass 1: each workgroup reduces a slab of pixels into per-group
-// (sum, sumsq) partials; pass 2 combines the partials in double precision.
+// (sum, M2) partials, M2 = the sum of squared deviations from the slab's own mean (dk_kernels.h: the sums are taken
+// about a pivot, never as a raw sum of squares); pass 2 merges the partials in double precision.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void dk_gn_partial_kernel(const bf16_t* __restrict__ x, long HW, int C, int G, float* __restrict__ partial,
                                                             int nchunk) {
-  // per-thread (sum, sumsq) of 8 channels, combined in a FIXED order (no atomics: the statistics,
-  // and with them the decoded image, must be bit-reproducible for a fixed seed)
+  // per-thread (sum, sumsq) of 8 channels about the pivot of each channel's group -- the group's first channel at the chunk's first pixel --
+  // combined in a FIXED order (no atomics: the statistics, and with them the decoded image, must be bit-reproducible for a fixed seed)
   __shared__ float red[256 * 16];
   const int tid = threadIdx.x;
   const int chunk = blockIdx.x, b = blockIdx.y;
@@ -23,15 +24,21 @@ __global__ __launch_bounds__(256) void dk_gn_partial_kernel(const bf16_t* __rest
   const int pl = tid / tpp;
   const long per = (HW + nchunk - 1) / nchunk;
   const long p0 = (long)chunk * per, p1 = min(HW, p0 + per);
-  float s[8], q[8];
+  const int cpg = C / G;
+  const bf16_t* piv = x + ((size_t)b * HW + (size_t)(p0 < p1 ? p0 : 0)) * C;  // (an empty trailing chunk reads nothing it uses)
+  float s[8], q[8], pv[8];
 #pragma unroll
-  for (int e = 0; e < 8; ++e) s[e] = q[e] = 0.f;
+  for (int e = 0; e < 8; ++e) {
+    s[e] = q[e] = 0.f;
+    pv[e] = to_f32(piv[(cg * 8 + e) / cpg * cpg]);
+  }
   const bf16_t* base = x + (size_t)b * HW * C + cg * 8;
   auto accumulate = [&](const u32x4 raw) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float a0, a1;
       unpack2(raw[e], a0, a1);
+      a0 -= pv[2 * e], a1 -= pv[2 * e + 1];
       s[2 * e] += a0; q[2 * e] += a0 * a0;
       s[2 * e + 1] += a1; q[2 * e + 1] += a1 * a1;
     }
@@ -55,37 +62,58 @@ __global__ __launch_bounds__(256) void dk_gn_partial_kernel(const bf16_t* __rest
     red[(1 * ppi + pl) * C + cg * 8 + e] = q[e];
   }
   __syncthreads();
-  if (tid < 2 * G) {
-    const int g = tid >> 1, stat = tid & 1, cpg = C / G;
+  if (tid < 2 * G) {  // (2 G is even: the lanes 2 g, 2 g + 1 of a group are both live)
+    const int g = tid >> 1, stat = tid & 1;
     float acc = 0.f;
     for (int pp = 0; pp < ppi; ++pp)
       for (int c = 0; c < cpg; ++c) acc += red[(stat * ppi + pp) * C + g * cpg + c];
-    partial[((size_t)b * nchunk + chunk) * 2 * G + tid] = acc;
+    const float other = __shfl_xor(acc, 1, 64);
+    float sg = stat ? other : acc, qg = stat ? acc : other;
+    if (p0 < p1) dk_gn_from_pivot(sg, qg, to_f32(piv[g * cpg]), (float)((p1 - p0) * cpg));
+    partial[((size_t)b * nchunk + chunk) * 2 * G + tid] = stat ? qg : sg;
   }
 }
 // one workgroup of 256 threads per (batch, group): threads stride over the chunk partials (up to one per 16 x 16 output tile when a
 // fused conv produced them: 4096 at 1024 x 1024), then a fixed-order tree (double) -- wave shuffles, four wave results through LDS
-__global__ __launch_bounds__(256) void dk_gn_finalize_kernel(const float* __restrict__ partial, int nchunk, int G, double count, float eps,
+// Chunk c holds (sum, M2 about its own mean) of its n_c = (pixels of the chunk) * cpg values -- chunk c of the statistics pass covers the pixels
+// [c per, min(HW, (c + 1) per)), per = ceil(HW / nchunk) (trailing chunks may be empty); a conv tile 256 pixels, which the same formula gives --
+// so the group's M2 = sum M2_c + sum n_c (sum_c / n_c - mean)^2, all in fp64.
+__global__ __launch_bounds__(256) void dk_gn_finalize_kernel(const float* __restrict__ partial, int nchunk, int G, long HW, int cpg, float eps,
                                                              float* __restrict__ mean_rstd, const bf16_t* __restrict__ gamma,
                                                              const bf16_t* __restrict__ beta, int C, float* __restrict__ scale_shift) {
-  __shared__ double red[8];
+  __shared__ double red[12];
   const int b = blockIdx.x / G, g = blockIdx.x % G, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  double s = 0.0, q = 0.0;
+  const double count = (double)HW * (double)cpg;
+  const long per = (HW + nchunk - 1) / nchunk;
+  // one pass: the chunk means about chunk 0's (a full chunk; a pivot once more: sum n_c (m_c - mean)^2 = sum n_c d_c^2 - (sum n_c d_c)^2 / count)
+  const float* pg = partial + (size_t)b * nchunk * 2 * G + 2 * g;
+  const double inv_full = 1.0 / ((double)per * (double)cpg);
+  const double m0 = (double)pg[0] * inv_full;
+  double s = 0.0, q = 0.0, t = 0.0;
   for (int c = tid; c < nchunk; c += 256) {
-    s += (double)partial[((size_t)b * nchunk + c) * 2 * G + 2 * g];
-    q += (double)partial[((size_t)b * nchunk + c) * 2 * G + 2 * g + 1];
+    long np = HW - (long)c * per;
+    np = np < 0 ? 0 : np > per ? per : np;
+    if (np == 0) continue;
+    const double nc = (double)np * (double)cpg;
+    const double sc = (double)pg[(size_t)c * 2 * G];
+    const double d = sc * (np == per ? inv_full : 1.0 / nc) - m0;
+    s += sc;
+    q += (double)pg[(size_t)c * 2 * G + 1] + nc * d * d;
+    t += nc * d;
   }
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
+  for (int o = 32; o > 0; o >>= 1) {  // fixed-order tree: wave shuffles, four wave results through LDS
     s += __shfl_xor(s, o, 64);
     q += __shfl_xor(q, o, 64);
+    t += __shfl_xor(t, o, 64);
   }
-  if (lane == 0) red[wave] = s, red[4 + wave] = q;
+  if (lane == 0) red[wave] = s, red[4 + wave] = q, red[8 + wave] = t;
   __syncthreads();
   s = (red[0] + red[1]) + (red[2] + red[3]);
   q = (red[4] + red[5]) + (red[6] + red[7]);
+  t = (red[8] + red[9]) + (red[10] + red[11]);
   const double mean = s / count;
-  double var = q / count - mean * mean;
+  double var = (q - t * t / count) / count;
   if (var < 0.0) var = 0.0;
   const float mf = (float)mean, rf = (float)(1.0 / sqrt(var + (double)eps));
   if (tid == 0) {
@@ -94,7 +122,6 @@ __global__ __launch_bounds__(256) void dk_gn_finalize_kernel(const float* __rest
   }
   if (scale_shift != nullptr) {
     // the per-channel pair dk_gn_apply_kernel builds in LDS (same fp32 expressions), for consumers that apply the norm on load
-    const int cpg = C / G;
     for (int c = tid; c < cpg; c += 256) {
       const int ch = g * cpg + c;
       const float sc = rf * to_f32(gamma[ch]);
@@ -103,15 +130,15 @@ __global__ __launch_bounds__(256) void dk_gn_finalize_kernel(const float* __rest
     }
   }
 }
-int dk_launch_groupnorm_finalize(const float* partial, int nchunk, int B, int G, double count, float eps, float* mean_rstd,
+int dk_launch_groupnorm_finalize(const float* partial, int nchunk, int B, int G, long HW, float eps, float* mean_rstd,
                                  const bf16_t* gamma, const bf16_t* beta, int C, float* scale_shift, hipStream_t stream) {
-  DK_REQUIRE(G >= 1 && nchunk >= 1 && (scale_shift == nullptr || (gamma && beta && C % G == 0)), "groupnorm finalize arguments");
-  hipLaunchKernelGGL(dk_gn_finalize_kernel, dim3(B * G), dim3(256), 0, stream, partial, nchunk, G, count, eps, mean_rstd, gamma, beta, C,
+  DK_REQUIRE(G >= 1 && nchunk >= 1 && HW >= 1 && C % G == 0 && (scale_shift == nullptr || (gamma && beta)), "groupnorm finalize arguments");
+  hipLaunchKernelGGL(dk_gn_finalize_kernel, dim3(B * G), dim3(256), 0, stream, partial, nchunk, G, HW, C / G, eps, mean_rstd, gamma, beta, C,
                      scale_shift);
   DK_CHECK_HIP(hipGetLastError());
   return 0;
 }
-// first pass alone: per (batch row, chunk, group) partial (sum, sum of squares)
+// first pass alone: per (batch row, chunk, group) partial (sum, M2 about the chunk's own mean)
 int dk_launch_groupnorm_partials(const bf16_t* x, int B, long HW, int C, int G, float* partial, int nchunk, hipStream_t stream) {
   DK_REQUIRE(C % 8 == 0 && C / 8 <= 256 && 256 % (C / 8) == 0, "channels must be 8 * 2^k <= 2048");
   DK_REQUIRE(G <= 64 && C % G == 0, "groups");
@@ -125,7 +152,7 @@ int dk_launch_groupnorm_stats(const bf16_t* x, int B, long HW, int C, int G, flo
   // (names in parentheses: no argument-dependent lookup -- hipStream_t would bring the global-scope twin in beside this scope's own)
   const int rc = (dk_launch_groupnorm_partials)(x, B, HW, C, G, partial, nchunk, stream);
   if (rc) return rc;
-  return (dk_launch_groupnorm_finalize)(partial, nchunk, B, G, (double)HW * (double)(C / G), eps, mean_rstd, nullptr, nullptr, C, nullptr, stream);
+  return (dk_launch_groupnorm_finalize)(partial, nchunk, B, G, HW, eps, mean_rstd, nullptr, nullptr, C, nullptr, stream);
 }
 
 // y = [silu]( bf16( (x - mean) * rstd * gamma + beta ) ), evaluated as x * scale[c] + shift[c] with the per-channel

@@ -150,7 +150,7 @@ int dk_conv3x3_bf16(const dk_conv_desc* d, void* stream);
  * GroupNorm (as the per-channel fp32 pair from dk_groupnorm_table_bf16) and the SiLU on the way in -- the normalised tensor is
  * never written.  Optionally: + residual (the block's "+ x", vae.py:100); the 1x1 conv_shortcut of a channel-changing block
  * (vae.py:86-89,98-99) as extra reduction columns over x2 (w = [conv weight | shortcut weight], ldw = 9 C + C2 or more);
- * (sum, sum of squares) partials of the output per channel group for the GroupNorm that reads it next (dk_groupnorm_table_bf16
+ * (sum, M2 about the tile's own mean) partials of the output per channel group for the GroupNorm that reads it next (dk_groupnorm_table_bf16
  * with x == NULL); and, for O <= 4 (conv_out), the clip / uint8 tail of decode_latents_to_image (__init__.py:581-584,525-526).
  * H, W multiples of 16; C (and C2) multiples of 64; O a multiple of 128, or <= 4 with the image tail. */
 typedef struct dk_conv_gn_desc {
@@ -172,7 +172,8 @@ typedef struct dk_conv_gn_desc {
 int dk_conv3x3_gn_bf16(const dk_conv_gn_desc* d, void* stream);
 /* nn.GroupNorm statistics (vae.py:34,72,78,381) as the table dk_conv3x3_gn_bf16 applies: scale = rstd * gamma, shift =
  * beta - mean * scale, fp32 [B, 2, C].  x != NULL: statistics of x (NHWC bf16 [B, HW, C]); x == NULL: from `n_partial` partials
- * per batch row that a dk_conv3x3_gn_bf16 launch left in scratch (layout [B, n_partial, G, 2]).  scratch:
+ * per batch row that a dk_conv3x3_gn_bf16 launch left in scratch (layout [B, n_partial, G, 2]: (sum, M2 about the tile's own mean) of
+ * one 16 x 16-pixel tile each, so n_partial * 256 must equal HW -- anything else is refused).  scratch:
  * dk_groupnorm_scratch_floats(B, G) floats, or B * n_partial * G * 2 + B * G * 2 if that is more. */
 int dk_groupnorm_table_bf16(const void* x, int32_t B, int64_t HW, int32_t C, int32_t G, const void* gamma, const void* beta,
                             float eps, float* scratch, int32_t n_partial, float* scale_shift, void* stream);

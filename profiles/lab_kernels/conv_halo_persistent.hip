@@ -25,6 +25,8 @@
 //   (first version, one set of reads per K-tile behind the barrier: 760-915 TFLOP/s; profiles/r03_vae_kernel_stats_halo_v1.md).
 // Optional K extension (x2): the 1x1 conv_shortcut of a channel-changing resnet (vae.py:86-89,98-99) as extra K-tiles over the
 // raw block input (centre tap only, no transform) -- the shortcut never exists as a tensor.
+// NOTE (lab copy, not built into the library): this copy still writes (sum, sum of squares) partials; the library's conv tails and
+// dk_gn_finalize_kernel have since moved to (sum, M2 about the tile's own mean) pairs (dk_kernels.h) -- port the tail before reviving it.
 // Optional statistics of the OUTPUT (stats_out): per workgroup the (sum, sum of squares) of the stored bf16 values per output
 // channel group -- the partials dk_gn_finalize_kernel combines for the GroupNorm that reads this tensor next.
 // NT = 16 (IMG): conv_out (3 of 16 columns live) with the clip / uint8 / float image tail of dk_image_post_kernel fused.

@@ -497,7 +497,7 @@ def test_conv3x3_gn_footprints(dev, form):
     """norm -> silu -> conv in one launch on conv_halo.hip and on conv256v4.hip (256- and 128-channel tiles, upsample form): the GroupNorm table is built
     from the CLEAN input and only the conv's input is poisoned, so the footprint stays the 3 x 3 neighbourhood; a residual element -> one output
     element, a shortcut input element -> one pixel in all channels; image 1 poisoned -> image 0 bit-identical.
-    Output statistics (one (sum, sum of squares) per image, 16 x 16-pixel tile and group; tile ty * (W / 16) + tx: conv_halo.hip:71-74,
+    Output statistics (one (sum, M2) pair per image, 16 x 16-pixel tile and group; tile ty * (W / 16) + tx: conv_halo.hip:71-74,
     conv256v4.hip:55-58): exactly the entries of the tiles that hold a NaN output pixel are NaN, every other entry is bit-identical."""
     from diffusionkit_amd import ops
     name, dt, v4, (B, H, W, C, O), ups, table, res, C2 = form
