@@ -272,6 +272,9 @@ SIGNATURES = {
     "dk_conv3x3_f16": (_i32, [C.POINTER(dk_conv_desc), _vp]),
     "dk_conv3x3_plan": (_i32, [C.POINTER(dk_conv_desc), C.POINTER(dk_gemm_plan_t)]),
     "dk_conv3x3_plan_f16": (_i32, [C.POINTER(dk_conv_desc), C.POINTER(dk_gemm_plan_t)]),
+    # ... with the K-split workspace of the engines' convs (additive in ABI 5)
+    **{"dk_conv3x3_ws_" + el: (_i32, [C.POINTER(dk_conv_desc), _vp, _sz, _vp]) for el in ("bf16", "f16")},
+    **{"dk_conv3x3_ws_plan" + sfx: (_i32, [C.POINTER(dk_conv_desc), _sz, C.POINTER(dk_gemm_plan_t)]) for sfx in ("", "_f16")},
     "dk_conv3x3_gn_f16": (_i32, [C.POINTER(dk_conv_gn_desc), _vp]),
     "dk_groupnorm_table_f16": (_i32, [_vp, _i32, C.c_int64, _i32, _i32, _vp, _vp, C.c_float, _vp, _i32, _vp, _vp]),
     "dk_groupnorm_f16": (_i32, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _f32, _i32, _vp, _vp]),

@@ -136,6 +136,30 @@ static int conv3x3_plan(int dtype, const dk_conv_desc* d, dk_gemm_plan_t* plan) 
 }
 extern "C" int dk_conv3x3_plan(const dk_conv_desc* d, dk_gemm_plan_t* plan) { return conv3x3_plan(DK_DTYPE_BF16, d, plan); }
 extern "C" int dk_conv3x3_plan_f16(const dk_conv_desc* d, dk_gemm_plan_t* plan) { return conv3x3_plan(DK_DTYPE_F16, d, plan); }
+// The same launches with the K-split workspace the VAE engines attach (VaeRun::conv): the buffer and the rules of dk_gemm_desc.workspace.  A
+// buffer the split could not use is refused -- it never silently runs unsplit.  (plan: only the size is known, the pointer is a made-up aligned one)
+static int conv3x3_ws(int dtype, const dk_conv_desc* d, void* workspace, size_t workspace_bytes, hipStream_t stream, dk_gemm_plan_t* rec) {
+  DK_REQUIRE(workspace != nullptr && ((uintptr_t)workspace & 255) == 0, "conv K-split workspace: 256-byte aligned, not NULL");
+  DK_REQUIRE(workspace_bytes >= dk_gemm_split_workspace_bytes(), "conv K-split workspace too small (dk_gemm_workspace_bytes())");
+  return conv3x3_launch(dtype, d, workspace, stream, rec);
+}
+extern "C" int dk_conv3x3_ws_bf16(const dk_conv_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
+  return conv3x3_ws(DK_DTYPE_BF16, d, workspace, workspace_bytes, S_(stream), nullptr);
+}
+extern "C" int dk_conv3x3_ws_f16(const dk_conv_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
+  return conv3x3_ws(DK_DTYPE_F16, d, workspace, workspace_bytes, S_(stream), nullptr);
+}
+static int conv3x3_ws_plan(int dtype, const dk_conv_desc* d, size_t workspace_bytes, dk_gemm_plan_t* plan) {
+  DK_REQUIRE(plan != nullptr, "null plan");
+  if (workspace_bytes == 0) return conv3x3_launch(dtype, d, nullptr, nullptr, plan);  // (0: none, as dk_attention_plan)
+  return conv3x3_ws(dtype, d, (void*)(uintptr_t)256, workspace_bytes, nullptr, plan);
+}
+extern "C" int dk_conv3x3_ws_plan(const dk_conv_desc* d, size_t workspace_bytes, dk_gemm_plan_t* plan) {
+  return conv3x3_ws_plan(DK_DTYPE_BF16, d, workspace_bytes, plan);
+}
+extern "C" int dk_conv3x3_ws_plan_f16(const dk_conv_desc* d, size_t workspace_bytes, dk_gemm_plan_t* plan) {
+  return conv3x3_ws_plan(DK_DTYPE_F16, d, workspace_bytes, plan);
+}
 
 // Workspace of the stand-alone attention launches (dk_attention_*) of this host thread.  attention5.hip splits the query blocks of a launch's last, partial round of the
 // CUs along the keys where that shortens the round (dk_attention_route, attention.hip: FLUX 1024 x 1024 with four images, 1632 blocks on 256 CUs -- the

@@ -327,6 +327,8 @@ extern "C" int dk_vae_decode(dk_vae* v, const float* latent, int32_t batch, int3
   }
   DK_TRY(R.gn(cur, v->T1, (long)H * W, C, "conv_norm_out", 1));
   bf16_t* raw = raw_bf16 ? (bf16_t*)raw_bf16 : v->Y;
+  // (the conv writes out_channels of the 4 columns per pixel; the fused tail above stores zeros in the rest, so does this one)
+  if (raw_bf16 && cf.out_channels < 4) DK_CHECK_HIP(hipMemsetAsync(raw, 0, (size_t)batch * H * W * 4 * sizeof(bf16_t), st));
   DK_TRY(R.conv(v->T1, raw, H, W, C, cf.out_channels, "conv_out", 0, nullptr, 4));
   DK_TRY(DK_EL(v->dtype, dk_launch_image_post)(raw, 4, image_f32, image_u8, (long)batch * H * W, st));
   return R.rc;

@@ -165,10 +165,11 @@ def zero_page(device) -> Tensor:
 
 
 def conv3x3(x: Tensor, w: Tensor, bias: Optional[Tensor], upsample: bool = False, res: Optional[Tensor] = None,
-            downsample: bool = False) -> Tensor:
+            downsample: bool = False, workspace: Optional[Tensor] = None) -> Tensor:
     """nn.Conv2d k3 on NHWC; w: [O,3,3,C] (or flattened [O, 9C]); C multiple of 64.  Default: stride 1, pad 1
     (``upsample``: over the nearest-x2 view of x); ``downsample``: stride 2 over x padded by one zero row /
-    column at the bottom / right (vae.py:141-143).  bf16 tensors, or all float16 (dk_conv3x3_f16)."""
+    column at the bottom / right (vae.py:141-143).  bf16 tensors, or all float16 (dk_conv3x3_f16).
+    ``workspace``: the K-split scratch (``gemm_workspace``) the VAE engines attach to their convs (dk_conv3x3_ws_bf16 / _f16)."""
     assert not (upsample and downsample)
     lib = _lib.load()
     el = _elem(x.dtype, "conv3x3")
@@ -189,13 +190,17 @@ def conv3x3(x: Tensor, w: Tensor, bias: Optional[Tensor], upsample: bool = False
     d.ldy, d.ldr = ldy, (res.shape[-1] if res is not None else 0)
     d.upsample = 2 if downsample else int(upsample)
     d.epilogue = DK_EPI_RES if res is not None else DK_EPI_BIAS
-    _lib.check(getattr(lib, "dk_conv3x3_" + el)(C.byref(d), _stream()), "dk_conv3x3_" + el)
+    if workspace is not None:
+        _lib.check(getattr(lib, "dk_conv3x3_ws_" + el)(C.byref(d), workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream()),
+                   "dk_conv3x3_ws_" + el)
+    else:
+        _lib.check(getattr(lib, "dk_conv3x3_" + el)(C.byref(d), _stream()), "dk_conv3x3_" + el)
     return y[..., :O]
 
 
 def conv3x3_plan(B: int, H: int, W: int, C_in: int, O: int, upsample: int = 0, dtype=BF, res: bool = False, workspace: int = 0):
-    """dk_conv3x3_plan / dk_conv3x3_plan_f16: the route a ``conv3x3`` call of this OUTPUT size would take (host only, nothing is launched;
-    the pointers are made-up, aligned integers)."""
+    """dk_conv3x3_ws_plan / dk_conv3x3_ws_plan_f16: the route a ``conv3x3`` call of this OUTPUT size would take with a K-split workspace of
+    ``workspace`` bytes (0: none -- dk_conv3x3_plan's answer) (host only, nothing is launched; the pointers are made-up, aligned integers)."""
     d = _lib.dk_conv_desc()
     d.x, d.w, d.y, d.bias, d.zeros = 0x10000, 0x20000, 0x30000, 0x40000, 0x50000
     d.res = 0x60000 if res else None
@@ -204,8 +209,8 @@ def conv3x3_plan(B: int, H: int, W: int, C_in: int, O: int, upsample: int = 0, d
     d.upsample = int(upsample)
     d.epilogue = DK_EPI_RES if res else DK_EPI_BIAS
     plan = _lib.dk_gemm_plan_t()
-    name = "dk_conv3x3_plan" if _elem(dtype, "conv3x3_plan") == "bf16" else "dk_conv3x3_plan_f16"
-    _lib.check(getattr(_lib.load(), name)(C.byref(d), C.byref(plan)), name)
+    name = "dk_conv3x3_ws_plan" if _elem(dtype, "conv3x3_plan") == "bf16" else "dk_conv3x3_ws_plan_f16"
+    _lib.check(getattr(_lib.load(), name)(C.byref(d), int(workspace), C.byref(plan)), name)
     return plan
 
 

@@ -639,6 +639,17 @@ int dk_euler_cfg_step_f16(float* x, const void* model_out, int32_t ld_out, void*
 int dk_conv3x3_f16(const dk_conv_desc* d, void* stream);
 int dk_conv3x3_plan(const dk_conv_desc* d, dk_gemm_plan_t* plan);
 int dk_conv3x3_plan_f16(const dk_conv_desc* d, dk_gemm_plan_t* plan);
+/* dk_conv3x3_bf16 / _f16 with the K-split scratch the VAE engines attach to their 3x3 convs -- additive in ABI 5.  `workspace`: the same buffer
+ * and rules as dk_gemm_desc.workspace (dk_gemm_workspace_bytes() bytes, 256-byte aligned, LAST 4096 bytes zero before the first use; the kernels
+ * leave them zero; one launch at a time may use it).  With it a convolution with O % 256 == 0 whose 256 x 256 tiles fill about half the compute
+ * units (96 .. 128 tiles: an unfused 256-channel stage of a few thousand pixels) runs on gemm256v3.hip's conv form with every tile cut in two
+ * along K; other shapes take the route of dk_conv3x3_bf16.  A NULL, misaligned or short workspace is refused (dk_last_error() names the rule):
+ * the launch never silently runs unsplit.  dk_conv3x3_ws_plan / _plan_f16: dk_gemm_plan of that call for a workspace of workspace_bytes bytes
+ * (0: none -- the answer of dk_conv3x3_plan; a size above 0 that is too small is refused as the launch refuses it). */
+int dk_conv3x3_ws_bf16(const dk_conv_desc* d, void* workspace, size_t workspace_bytes, void* stream);
+int dk_conv3x3_ws_f16(const dk_conv_desc* d, void* workspace, size_t workspace_bytes, void* stream);
+int dk_conv3x3_ws_plan(const dk_conv_desc* d, size_t workspace_bytes, dk_gemm_plan_t* plan);
+int dk_conv3x3_ws_plan_f16(const dk_conv_desc* d, size_t workspace_bytes, dk_gemm_plan_t* plan);
 int dk_conv3x3_gn_f16(const dk_conv_gn_desc* d, void* stream);
 int dk_groupnorm_table_f16(const void* x, int32_t B, int64_t HW, int32_t C, int32_t G, const void* gamma, const void* beta,
                            float eps, float* scratch, int32_t n_partial, float* scale_shift, void* stream);
@@ -967,7 +978,7 @@ size_t dk_vae_workspace_bytes(const dk_vae* v, int32_t batch, int32_t latent_h, 
 /* VAEDecoder.__call__ (vae.py:386-401) + decode_latents_to_image (__init__.py:581-584) +
  * uint8 conversion (__init__.py:525-526).  latent: f32 [B,h,w,16];
  * image_f32: [B,8h,8w,3] in [0,1] or NULL; image_u8: [B,8h,8w,3] or NULL;
- * raw_bf16: decoder output before the clip, [B,8h,8w,4] (3 used) or NULL. */
+ * raw_bf16: decoder output before the clip, [B,8h,8w,4] (3 used, the fourth column is written as zero on every route) or NULL. */
 int dk_vae_decode(dk_vae* v, const float* latent, int32_t batch, int32_t latent_h, int32_t latent_w,
                   float* image_f32, uint8_t* image_u8, void* raw_bf16, void* workspace,
                   size_t workspace_bytes, void* stream);

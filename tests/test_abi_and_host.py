@@ -30,6 +30,11 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, s), f"{s} declared in include/dk_hip.h but not exported"
     assert sorted(_lib.SIGNATURES) == syms
     assert lib.dk_abi_version() == 5
+    # additive in ABI 5: the conv entries that take the K-split workspace, next to the ones they extend
+    for s in ("dk_conv3x3_ws_bf16", "dk_conv3x3_ws_f16", "dk_conv3x3_ws_plan", "dk_conv3x3_ws_plan_f16"):
+        assert s in syms and s.replace("_ws", "") in syms, s
+    integration = open(os.path.join(os.path.dirname(_lib.HEADER_PATH), "..", "INTEGRATION.md")).read()
+    assert "dk_conv3x3_ws_bf16" in integration and "dk_conv3x3_ws_plan" in integration
 
 
 READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"

@@ -11,7 +11,8 @@ import torch
 from diffusionkit_amd import _lib, cli
 from diffusionkit_amd.config import MMDIT_CKPT, VAEDecoderConfig, VAEEncoderConfig, tiny_vae, tiny_vae_encoder
 
-F16_VAE_SYMBOLS = ("dk_vae_set_dtype", "dk_conv3x3_f16", "dk_conv3x3_plan", "dk_conv3x3_plan_f16", "dk_conv3x3_gn_f16", "dk_groupnorm_f16",
+F16_VAE_SYMBOLS = ("dk_vae_set_dtype", "dk_conv3x3_f16", "dk_conv3x3_plan", "dk_conv3x3_plan_f16", "dk_conv3x3_ws_f16", "dk_conv3x3_ws_plan",
+                   "dk_conv3x3_ws_plan_f16", "dk_conv3x3_gn_f16", "dk_groupnorm_f16",
                    "dk_groupnorm_table_f16", "dk_attention_d512_f16", "dk_softmax_rows_f16", "dk_transpose_f16", "dk_latent_sample_f16")
 
 
