@@ -108,6 +108,7 @@ class dk_attention_desc(C.Structure):
         ("scale", C.c_float), ("bias", C.c_void_p), ("bias_head_stride", C.c_int64), ("ldb", C.c_int32),
         ("qn_a", C.c_void_p), ("qn_b", C.c_void_p), ("qn_split", C.c_int32), ("qn_eps", C.c_float), ("q_rope", C.c_void_p),
         ("O8", C.c_void_p), ("O8_scales", C.c_void_p), ("o8_ld", C.c_int32), ("o8_rows", C.c_int64),
+        ("score_bound", C.c_float),
     ]
 
 
@@ -130,7 +131,7 @@ class dk_gemm_plan_t(C.Structure):
 
 
 class dk_attention_plan_t(C.Structure):  # (o8_split is read by dk_attention_plan, the other fields are written)
-    _fields_ = [(n, C.c_int32) for n in ("kernel", "qfuse", "blocks", "whole", "split", "jobs", "merge", "quantize", "launches", "n_cu", "o8_split")]
+    _fields_ = [(n, C.c_int32) for n in ("kernel", "qfuse", "blocks", "whole", "split", "jobs", "merge", "quantize", "launches", "n_cu", "o8_split", "untracked")]
 
 
 # the step entries (dk_euler / dk_lms / dk_guided _cfg_step, their masked and _f16 forms), composed: x, model_out, ld_out, tokens, n_img, cfg_on, Hl, Wl,
@@ -218,6 +219,7 @@ SIGNATURES = {
     "dk_mmdit_bind": (_i32, [_vp, C.c_char_p, _vp]),
     "dk_mmdit_mod_rows": (_i32, [_vp]),
     "dk_mmdit_mod_offset": (_i32, [_vp, _i32, _i32]),
+    "dk_mmdit_score_bound": (_f32, [_vp, _i32, _i32]),
     "dk_mmdit_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32, _i32, _i32]),
     "dk_mmdit_prepare": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
     "dk_mmdit_cache_modulation_params": (_i32, [_vp, _vp, _fp, _i32, _vp]),

@@ -28,7 +28,7 @@ extern "C" int dk_tune_set(const char* key, int32_t value) {
       {"gemm", &g_dk_gemm_mode}, {"gemm_v4", &g_dk_v4_auto}, {"gemm_skew", &g_dk_v4_skew}, {"gemm_mf", &g_dk_v3_mf},
       {"gemm_split", &g_dk_v3_split}, {"gemm_split_min", &g_dk_v3_split_min}, {"gemm_pair_nk", &g_dk_pair_split_nk},
       {"gemm_fuse_k", &g_dk_fuse_k}, {"gemm_fuse_q", &g_dk_fuse_qg}, {"attn", &g_dk_attn_mode}, {"attn_fuse_q", &g_dk_fuse_q},
-      {"attn_split", &g_dk_attn5_split}, {"pitch_min_k", &g_dk_pitch_min_k}, {"conv_halo", &g_dk_conv_halo}, {"conv_v4", &g_dk_conv_v4}};
+      {"attn_split", &g_dk_attn5_split}, {"attn_track", &g_dk_attn5_track}, {"pitch_min_k", &g_dk_pitch_min_k}, {"conv_halo", &g_dk_conv_halo}, {"conv_v4", &g_dk_conv_v4}};
   DK_REQUIRE(key != nullptr, "null key");
   for (const auto& k : knobs)
     if (strcmp(key, k.key) == 0) { *k.knob = value; return 0; }
@@ -197,6 +197,7 @@ static int attn_params_from_desc(int dtype, const dk_attention_desc* d, AttnPara
   p.B = d->B; p.H = d->H; p.S = d->S; p.D = d->D; p.ld = d->ld; p.ldo = d->ldo; p.scale = d->scale;
   p.bias = (const bf16_t*)d->bias; p.bias_head_stride = (long)d->bias_head_stride; p.ldb = d->ldb;
   p.qn_a = (const bf16_t*)d->qn_a; p.qn_b = (const bf16_t*)d->qn_b; p.qn_split = d->qn_split; p.qn_eps = d->qn_eps; p.q_rope = d->q_rope;
+  p.score_bound = d->score_bound;
   p.dtype = dtype;
   if (d->O8 != nullptr) {
     DK_REQUIRE(d->O8_scales != nullptr && d->o8_rows >= (int64_t)d->B * d->S && d->o8_ld >= d->H * d->D && d->o8_ld % 32 == 0,
@@ -223,7 +224,7 @@ static int attention_plan(int dtype, const dk_attention_desc* d, size_t workspac
   }
   AttnRoute r;
   if (const int rc = dk_attention_route(p, workspace_bytes, dk_device_cu_count(), r)) return rc;
-  *plan = dk_attention_plan_t{r.kernel, r.qfuse, r.blocks, r.whole, r.split, r.jobs, r.jobs > 0, r.quantize, r.launches, r.n_cu, p.o8_split};
+  *plan = dk_attention_plan_t{r.kernel, r.qfuse, r.blocks, r.whole, r.split, r.jobs, r.jobs > 0, r.quantize, r.launches, r.n_cu, p.o8_split, r.untracked};
   return 0;
 }
 extern "C" int dk_attention_plan(const dk_attention_desc* d, size_t workspace_bytes, dk_attention_plan_t* plan) {
@@ -241,7 +242,7 @@ static int attention_identity(int dtype, const dk_attention_desc* d, int32_t ide
   if (plan == nullptr) return dk_launch_attention(p, g_attn_ws, S_(stream));
   AttnRoute r;
   if (const int rc = dk_attention_route(p, 0, dk_device_cu_count(), r)) return rc;
-  *plan = dk_attention_plan_t{r.kernel, r.qfuse, r.blocks, r.whole, r.split, r.jobs, r.jobs > 0, r.quantize, r.launches, r.n_cu, 0};
+  *plan = dk_attention_plan_t{r.kernel, r.qfuse, r.blocks, r.whole, r.split, r.jobs, r.jobs > 0, r.quantize, r.launches, r.n_cu, 0, r.untracked};
   return 0;
 }
 extern "C" int dk_attention_identity_bf16(const dk_attention_desc* d, int32_t ident_from, void* stream) {

@@ -19,8 +19,21 @@
 int g_dk_attn_mode = -1;  // dk_tune_set("attn", v): -1 (default) automatic; 4 = dk_attn2 (4 waves); 9 = dk_attn4 (8 waves, D = 128 only);
                           // 10 = dk_attn5 (one wave per SIMD, asm tile loop; D = 128, S % 256 == 0: other shapes fall back to 9)
 int g_dk_attn5_split = -1;  // dk_tune_set("attn_split", v): -1 automatic (needs the workspace), 0 never, 2 .. 4 that many key ranges for the last round's blocks
+int g_dk_attn5_track = -1;  // dk_tune_set("attn_track", v): -1 / 0 automatic (the rule below); 1: the one-wave-per-SIMD kernel always keeps its running row maximum
 
-// Every decision and argument check of one call (AttnRoute, dk_kernels.h): a pure function of its arguments and the two knobs above -- no HIP call.
+// The largest bound on |scale * q.k| (natural units) under which attention5.hip runs its tile loop WITHOUT the running row maximum: 2 B log2(e) <= 64.
+// That body (scripts/gen_attn5.py, program(track=False)) takes the offset m of a row once, from the maximum of the row's first key tile, and forms
+// p = 2^((s - m) log2 e) for every key.  With |s| <= B for every score of the launch, m included:
+//   * s - m <= 2 B, so p <= 2^(2 B log2 e) <= 2^64, and the row sum l <= S * 2^64 < 2^96 for any S < 2^32 -- fp32 holds 2^127, and so does bf16 (same exponent);
+//   * s - m >= -2 B, so no probability falls below 2^-64 (fp32 and bf16 normals reach 2^-126): nothing is flushed that the tracked body would keep,
+//     and l >= the first tile's maximum's own p = 1: the final 1 / l is at most 1;
+//   * the accumulators hold at most l * max|v| < 2^96 * 2^16 for bf16 values below 2^16.
+// softmax does not depend on the offset beyond rounding, so the two bodies agree to the rounding of p (bf16) and of the fp32 sums.  The key-range jobs
+// of a split launch leave their own m per row, and dk_attn5_merge_kernel weights the partials by 2^(m_i - max m) <= 1 as before.
+static constexpr float DK_ATTN5_UNTRACKED_MAX_ARG = 64.0f;
+static constexpr float DK_LOG2E = 1.44269504088896340736f;
+
+// Every decision and argument check of one call (AttnRoute, dk_kernels.h): a pure function of its arguments and the three knobs above -- no HIP call.
 // ws_bytes: size of the caller's region for the partial results of the key-split workgroups (0: none)
 int dk_attention_route(const AttnParams& p, size_t ws_bytes, int n_cu, AttnRoute& r) {
   DK_REQUIRE(p.D == 128 || p.D == 64, "head_dim must be 64 or 128");
@@ -80,6 +93,11 @@ int dk_attention_route(const AttnParams& p, size_t ws_bytes, int n_cu, AttnRoute
     if (ws_bytes < (size_t)tail * r.split * DK_ATTN5_JOB_BYTES) r.split = 1;
     if (r.split > 1) r.whole = r.blocks - tail, r.jobs = tail * r.split;
   }
+  // Kernel 10's body without the running row maximum (the derivation stands at DK_ATTN5_UNTRACKED_MAX_ARG): only for a launch this kernel takes anyway,
+  // with the fused query load (the one instantiation built: every model launch of the bf16 FLUX path), under a bound the caller gave.  No bound, a larger
+  // one (or a NaN), the knob at 1, the plain Q load: the tracked body, as before.
+  DK_REQUIRE(!(p.score_bound < 0.f), "score_bound: a bound on |scale * q.k| is positive (0: unknown)");
+  r.untracked = mode == 10 && r.qfuse && g_dk_attn5_track != 1 && p.score_bound > 0.f && 2.0f * p.score_bound * DK_LOG2E <= DK_ATTN5_UNTRACKED_MAX_ARG;
   // only the D = 128 kernels 9 and 10 write the MX-fp8 copy themselves: the bf16 output of the lean kernel is quantised behind it
   r.quantize = p.O8 == nullptr || mode != 4 ? 0 : p.o8_split != 0 ? 2 : 1;
   r.launches = 1 + (r.jobs > 0) + (r.quantize != 0);

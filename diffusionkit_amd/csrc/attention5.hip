@@ -14,7 +14,9 @@
 //     tile j and the V(j) reads; P(j) V(j) beside the row maxima of S(j+1), the first exponentials of tile j+1, the K(j+2) reads and the
 //     DMA pieces of K(j+3), V(j+2); one barrier per tile;
 //   * the rescale decision of a tile is taken while the previous tile's P.V is still in flight: it records the factor and switches the
-//     exponent offset; accumulators and row sums take the factor once that P.V is complete (scripts/gen_attn5.py, header).
+//     exponent offset; accumulators and row sums take the factor once that P.V is complete (scripts/gen_attn5.py, header);
+//   * launches whose caller bounds the scores (AttnParams::score_bound; the engine: from the QKNorm weights) take a second generated body
+//     without any of that: the offset of a row is the maximum of its first key tile and never moves (attention.hip, dk_attention_route).
 // Shapes: D = 128, S a multiple of 256 with at least 12 key tiles, no score bias (attention4.hip keeps the rest).
 #include "dk_kernels.h"
 
@@ -24,7 +26,9 @@ typedef unsigned int u32x8 __attribute__((ext_vector_type(8)));
 
 #define A5_LDS_BYTES 131072  // four-slot K ring + four-slot V ring
 
-template <bool QFUSE>
+// NT (dk_attention_route: the caller bounds |scale q.k|): the tile loop keeps no running maximum -- attention5_asm_nt.inc.  Built: <QFUSE, false> for
+// both QFUSE, and <true, true>.
+template <bool QFUSE, bool NT>
 __global__ __launch_bounds__(256, 1) void dk_attn5_fwd_kernel(AttnParams p) {
   constexpr int D = 128;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -159,16 +163,32 @@ __global__ __launch_bounds__(256, 1) void dk_attn5_fwd_kernel(AttnParams p) {
 
   f32x16 o[2][4];
   u32x2 lsum, mcv;
-  asm volatile(
-#include "attention5_asm.inc"
-      : "={v[0:15]}"(o[0][0]), "={v[16:31]}"(o[0][1]), "={v[32:47]}"(o[0][2]), "={v[48:63]}"(o[0][3]), "={v[64:79]}"(o[1][0]), "={v[80:95]}"(o[1][1]),
-        "={v[96:111]}"(o[1][2]), "={v[112:127]}"(o[1][3]), "={v[226:227]}"(lsum), "={v[224:225]}"(mcv), "+{v[128:143]}"(qv[0]), "+{v[144:159]}"(qv[1]), "+{v[160:175]}"(qv[2]),
-        "+{v[176:191]}"(qv[3])
-      : [koff] "s"(64 * (int)row_bytes), [voff] "s"(0), [tileb] "s"(64 * (int)row_bytes), [scale] "s"(scale_bits), [ntrip] "s"((nt - 8) / 4), [dbase] "s"(wave * 4096), "{v[238:245]}"(kaddr),
-        "{v[246:247]}"(vaddr), "{v[248:251]}"(dk), "{v[252:255]}"(dv), "{s[40:43]}"(rK), "{s[44:47]}"(rV)
-      :
+#define A5_OUTPUTS                                                                                                                                        \
+  "={v[0:15]}"(o[0][0]), "={v[16:31]}"(o[0][1]), "={v[32:47]}"(o[0][2]), "={v[48:63]}"(o[0][3]), "={v[64:79]}"(o[1][0]), "={v[80:95]}"(o[1][1]),         \
+      "={v[96:111]}"(o[1][2]), "={v[112:127]}"(o[1][3]), "={v[226:227]}"(lsum), "={v[224:225]}"(mcv), "+{v[128:143]}"(qv[0]), "+{v[144:159]}"(qv[1]),     \
+      "+{v[160:175]}"(qv[2]), "+{v[176:191]}"(qv[3])
+#define A5_INPUTS                                                                                                                                         \
+  [koff] "s"(64 * (int)row_bytes), [voff] "s"(0), [tileb] "s"(64 * (int)row_bytes), [scale] "s"(scale_bits), [ntrip] "s"((nt - 8) / 4),                  \
+      [dbase] "s"(wave * 4096), "{v[238:245]}"(kaddr), "{v[246:247]}"(vaddr), "{v[248:251]}"(dk), "{v[252:255]}"(dv), "{s[40:43]}"(rK), "{s[44:47]}"(rV)
+  if constexpr (NT) {  // the body without the running maximum: one exponent offset per row, from the first tile of the key range
+    asm volatile(
+#include "attention5_asm_nt.inc"
+        : A5_OUTPUTS
+        : A5_INPUTS
+        :
 #include "attention5_clobbers.inc"
-  );
+    );
+  } else {
+    asm volatile(
+#include "attention5_asm.inc"
+        : A5_OUTPUTS
+        : A5_INPUTS
+        :
+#include "attention5_clobbers.inc"
+    );
+  }
+#undef A5_OUTPUTS
+#undef A5_INPUTS
 
   // ---- normalise and store: lane owns query q0 + qb*32 + l31, d = dt*32 + 8g + 4hi + {0..3} (attention4.hip's tail, per query block) ----
   // (the block above owns every VGPR: whatever lane-dependent value the tail needs is formed again from a FRESH lane id -- values carried
@@ -306,14 +326,18 @@ int dk_launch_attention5(const AttnParams& p_in, const AttnRoute& r, void* ws, h
   p.a5_ws = r.jobs > 0 ? ws : nullptr;
   static DkDeviceOnce attr_once;
   if (attr_once.first()) {
-    DK_CHECK_HIP(hipFuncSetAttribute((const void*)dk_attn5_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, A5_LDS_BYTES));
-    DK_CHECK_HIP(hipFuncSetAttribute((const void*)dk_attn5_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, A5_LDS_BYTES));
+    DK_CHECK_HIP(hipFuncSetAttribute((const void*)dk_attn5_fwd_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, A5_LDS_BYTES));
+    DK_CHECK_HIP(hipFuncSetAttribute((const void*)dk_attn5_fwd_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, A5_LDS_BYTES));
+    DK_CHECK_HIP(hipFuncSetAttribute((const void*)dk_attn5_fwd_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, A5_LDS_BYTES));
     attr_once.mark();
   }
-  if (r.qfuse)
-    hipLaunchKernelGGL((dk_attn5_fwd_kernel<true>), dim3((unsigned)(r.whole + r.jobs)), dim3(256), A5_LDS_BYTES, stream, p);
+  DK_REQUIRE(!r.untracked || r.qfuse, "attention5: the body without the running maximum is built for the fused query load only");
+  if (r.untracked)
+    hipLaunchKernelGGL((dk_attn5_fwd_kernel<true, true>), dim3((unsigned)(r.whole + r.jobs)), dim3(256), A5_LDS_BYTES, stream, p);
+  else if (r.qfuse)
+    hipLaunchKernelGGL((dk_attn5_fwd_kernel<true, false>), dim3((unsigned)(r.whole + r.jobs)), dim3(256), A5_LDS_BYTES, stream, p);
   else
-    hipLaunchKernelGGL((dk_attn5_fwd_kernel<false>), dim3((unsigned)(r.whole + r.jobs)), dim3(256), A5_LDS_BYTES, stream, p);
+    hipLaunchKernelGGL((dk_attn5_fwd_kernel<false, false>), dim3((unsigned)(r.whole + r.jobs)), dim3(256), A5_LDS_BYTES, stream, p);
   if (r.jobs > 0) hipLaunchKernelGGL(dk_attn5_merge_kernel, dim3((unsigned)((r.blocks - r.whole) * 16)), dim3(256), 0, stream, p, r.jobs);
   return 0;
 }

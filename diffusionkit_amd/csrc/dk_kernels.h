@@ -209,6 +209,12 @@ struct AttnParams {
   int B, H, S, D;
   int ld, ldo;
   float scale;
+  // the caller's bound on |scale * q.k| over the whole launch, in natural units, AFTER the query transform of the Q load; 0: unknown.  A promise,
+  // not checked: attention5.hip runs its tile loop without the running row maximum when the bound admits it (dk_attention_route), and a launch that
+  // breaks the promise can overflow.  The engine derives it from the QKNorm weights (mmdit_engine.hip: dk_score_bound.h).  Only the route reads it.
+  // (It sits in the four bytes of padding between `scale` and the pointer below: the struct is a kernel argument, and a field behind the last one
+  //  would move the hidden arguments of every attention kernel -- this way their code objects stay what they were, static_assert below.)
+  float score_bound = 0.f;
   // optional additive score bias (text encoders: CLIP's causal mask clip.py:83-89, T5's relative-position bias
   // t5.py:61-88): scores = scale * q.k + bias[head * bias_head_stride + q * ldb + k]; ldb a multiple of 64 >= S
   const bf16_t* bias = nullptr;
@@ -246,6 +252,7 @@ struct AttnParams {
   // every key; a query s >= F (image) sees the keys [0, F) and its own key s, nothing else
   int ident_from = 0;
 };
+static_assert(sizeof(AttnParams) == 184 && offsetof(AttnParams, score_bound) == 60, "AttnParams is a kernel argument: its size and offsets are part of every attention kernel's code");
 // The 64-key tiles a 128-query block of identity attention walks, in order: tiles [0, n_lo), then [hi0, hi0 + n_hi).  A block that lies wholly
 // in the image range (q0 >= F) takes the ceil(F / 64) tiles that hold text keys and the tiles that hold its own rows, cut at the end of the
 // sequence -- never the same tile twice: q0 >= F is a multiple of 64, so q0 / 64 >= ceil(F / 64).  A block with a text query walks every tile.
@@ -270,7 +277,7 @@ struct AttnWs {
 constexpr size_t DK_ATTN5_JOB_BYTES = 65536 + 2048;
 
 // What one dk_launch_attention call launches: dk_attention_route (attention.hip) decides it -- and makes every argument check -- from the problem,
-// the bytes of the caller's region, the CU count and the knobs "attn" / "attn_split" alone; the launchers take it as it is, and
+// the bytes of the caller's region, the CU count and the knobs "attn" / "attn_split" / "attn_track" alone; the launchers take it as it is, and
 // dk_attention_plan reports it.  A key split changes the summation order: the route is part of the results.
 struct AttnRoute {
   int kernel;     // in the knob's codes: 4 lean (attention2.hip), 9 phase-alternating (attention4.hip), 10 one wave per SIMD (attention5.hip)
@@ -283,8 +290,9 @@ struct AttnRoute {
   int quantize;   // MX-fp8 copy: 0 none, or the kernel writes it; 1 a quantiser pass follows; 2 the same as two row ranges (o8_split)
   int launches;   // kernel launches of the call
   int n_cu;       // compute units the rules assumed
+  bool untracked;  // kernel 10: the tile loop without the running row maximum (AttnParams::score_bound admits it; knob "attn_track")
 };
-extern int g_dk_attn_mode, g_dk_attn5_split;  // attention.hip
+extern int g_dk_attn_mode, g_dk_attn5_split, g_dk_attn5_track;  // attention.hip
 int dk_attention_route(const AttnParams& p, size_t ws_bytes, int n_cu, AttnRoute& r);
 int dk_launch_attention(const AttnParams& p, AttnWs ws, hipStream_t stream);
 // the kernels' launchers: arguments checked, kernel and split chosen by dk_attention_route

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "dk_engine.h"
+#include "dk_score_bound.h"
 
 int g_dk_fuse_k = 1;  // dk_tune_set("gemm_fuse_k", v): QKNorm + RoPE of the keys inside the q / k / v projection's tail (1, default) or as a separate pass (0)
 int g_dk_fuse_qg = -1;  // dk_tune_set("gemm_fuse_q", v): ... and of the QUERIES there too (1) instead of in the attention kernel's Q load (0); -1 (default): on
@@ -34,12 +35,15 @@ struct StreamW {  // one TransformerBlock's weights (mmdit.py:395-438)
   // MMDiT-X (dk_mmdit_set_dual_attention), image stream of a dual block: the second attention's q | k | v matrix with its FULL bias (attn2's
   // k_proj keeps its bias), its own QKNorm weights and its output projection
   const bf16_t *qkv2_w = nullptr, *qkv2_b = nullptr, *qn2 = nullptr, *kn2 = nullptr, *o2_w = nullptr, *o2_b = nullptr;
+  // max|w| of qn / kn, read once when the weights are resolved (norm_weight_maxima); 0: no such weight, or not bf16 -- no bound (dk_score_bound.h)
+  float qn_max = 0.f, kn_max = 0.f;
 };
 
 struct dk_mmdit {
   dk_mmdit_config cfg;
   std::unordered_map<std::string, const void*> named;
   bool resolved = false;
+  bool norm_max_ready = false;  // StreamW::qn_max / kn_max hold the resolved weights' maxima (norm_weight_maxima)
   // resolved weights
   const bf16_t *xemb_w, *xemb_b, *pos_w, *ctx_w, *ctx_b, *y0_w, *y0_b, *y2_w, *y2_b, *t0_w, *t0_b, *t2_w, *t2_b;
   const bf16_t *adaln_w, *adaln_b, *final_w, *final_b;
@@ -287,6 +291,32 @@ static int resolve_attn2(dk_mmdit* m, const std::string& p, StreamW& w, bool dua
   return 0;
 }
 
+// The QKNorm vectors of every block (D values each) come to the host ONCE per resolved set of weights: what bounds the attention scores of a
+// launch (joint_attention).  Load-time work -- dk_mmdit_bind clears `resolved`, mmdit_resolve clears `norm_max_ready`, and the first prepare
+// behind it comes through here, where its device work begins (resolving alone touches no device).  bf16 engines only (the kernel that uses
+// the bound is bf16 only); the copies are ordered behind whatever `st` holds, the stream the caller prepares on.
+static int norm_weight_maxima(dk_mmdit* m, hipStream_t st) {
+  if (m->norm_max_ready) return 0;
+  std::vector<StreamW*> ws;
+  for (auto* v : {&m->dimg, &m->dtxt, &m->single})
+    for (StreamW& w : *v) {
+      w.qn_max = w.kn_max = 0.f;
+      if (m->dtype == DK_DTYPE_BF16 && w.qn != nullptr && w.kn != nullptr) ws.push_back(&w);
+    }
+  const int D = m->D();
+  std::vector<uint16_t> host(ws.size() * 2 * (size_t)D);
+  for (size_t i = 0; i < ws.size(); ++i) {
+    DK_CHECK_HIP(hipMemcpyAsync(&host[(2 * i) * D], ws[i]->qn, (size_t)D * 2, hipMemcpyDeviceToHost, st));
+    DK_CHECK_HIP(hipMemcpyAsync(&host[(2 * i + 1) * D], ws[i]->kn, (size_t)D * 2, hipMemcpyDeviceToHost, st));
+  }
+  if (!ws.empty()) DK_CHECK_HIP(hipStreamSynchronize(st));
+  std::vector<float> mx(ws.size() * 2);
+  dk_norm_weight_maxima(host.data(), mx.size(), D, mx.data());
+  for (size_t i = 0; i < ws.size(); ++i) ws[i]->qn_max = mx[2 * i], ws[i]->kn_max = mx[2 * i + 1];
+  m->norm_max_ready = true;
+  return 0;
+}
+
 static int mmdit_resolve(dk_mmdit* m) {
   if (m->resolved) return 0;
   const auto& n = m->named;
@@ -338,6 +368,7 @@ static int mmdit_resolve(dk_mmdit* m) {
   }
   for (int i = 0; i < m->cfg.depth_unified; ++i)
     DK_TRY(resolve_stream(m, "unified_transformer_blocks." + std::to_string(i) + ".transformer_block", m->single[i], true, false, m->fp8()));
+  m->norm_max_ready = false;  // (the StreamW records are new: maxima 0, no bound, until norm_weight_maxima has read the weights)
   m->resolved = true;
   return 0;
 }
@@ -438,6 +469,7 @@ extern "C" int dk_mmdit_prepare(dk_mmdit* m, int32_t batch, int32_t latent_h, in
   m->B = batch; m->Hl = latent_h; m->Wl = latent_w; m->S_t = text_len;
   m->S_i = (latent_h / p) * (latent_w / p); m->S_r = m->ref_rows(p); m->S_x = m->S_i + m->S_r; m->S = m->S_t + m->S_x; m->n_t = n_timesteps;
   hipStream_t st = S_(stream);
+  DK_TRY(norm_weight_maxima(m, st));
   if (m->cfg.use_rope) {  // the image at index 0 and, behind it, the reference image's own grid at index 1
     const int seg[6] = {latent_h / p, latent_w / p, 0, m->ref_h / p, m->ref_w / p, 1};
     DK_TRY(dk_launch_rope_table_segments(m->rope, m->S_t, m->S_r > 0 ? 2 : 1, seg, m->cfg.rope_axes_dim, m->cfg.n_rope_axes,
@@ -642,6 +674,10 @@ static bool queries_in_tail(const StreamW& a, const StreamW* b, bool f8) {
 // in the Q load: text rows with wt's weight, image rows with wi's (double block), or all rows with wt's (single block: wi null).
 // O8 / O8_scales / o8_ld: the MX-fp8 copy of the output the fp8 path's next Linear reads (it comes out of the attention kernel or out of a
 // quantiser pass behind it: attention.hip); null on the bf16 path
+// the bound on |scale * q.k| of a block's joint attention from the maxima of its streams' norm weights (0: unknown)
+static float block_score_bound(const StreamW& wt, const StreamW* wi, int D, float scale) {
+  return dk_score_bound(std::max(wt.qn_max, wi ? wi->qn_max : 0.f), std::max(wt.kn_max, wi ? wi->kn_max : 0.f), D, scale);
+}
 static AttnParams joint_attention(const dk_mmdit* m, const BlockCtx& c, bf16_t* O, int ldo, const StreamW& wt, const StreamW* wi,
                                   unsigned char* O8 = nullptr, unsigned char* O8_scales = nullptr, int o8_ld = 0) {
   AttnParams ap;
@@ -652,7 +688,19 @@ static AttnParams joint_attention(const dk_mmdit* m, const BlockCtx& c, bf16_t* 
     ap.qn_a = wt.qn; ap.qn_b = wi ? wi->qn : wt.qn; ap.qn_split = wi ? c.S_t : 0; ap.q_rope = c.rope;
   }
   if (O8 != nullptr) { ap.O8 = O8; ap.O8_scales = O8_scales; ap.o8_ld = o8_ld; ap.o8_nblk = m->nblk; }
+  // Every query and key of the launch is QK-normed -- the keys in the projection's tail or by the separate pass, the queries there or in the Q
+  // load -- whenever the weights exist: the scores are bounded by the weights' maxima (0 without weights: unknown).  The perturbed-attention
+  // launch reuses these parameters on the fork rows (same operands, same bound; its kernel does not read it); the dual-attention launch of
+  // MMDiT-X (D = 64, the lean kernel) passes none.
+  ap.score_bound = block_score_bound(wt, wi, ap.D, ap.scale);
   return ap;
+}
+extern "C" float dk_mmdit_score_bound(const dk_mmdit* m, int32_t kind, int32_t index) {
+  if (m == nullptr || !m->resolved || !m->norm_max_ready || index < 0) return 0.f;
+  const float scale = 1.0f / sqrtf((float)m->D());  // (block_ctx)
+  if (kind == 0 && index < (int)m->dimg.size()) return block_score_bound(m->dtxt[index], &m->dimg[index], m->D(), scale);
+  if (kind == 2 && index < (int)m->single.size()) return block_score_bound(m->single[index], nullptr, m->D(), scale);
+  return 0.f;
 }
 
 // MultiModalTransformerBlock i (mmdit.py:568-675), bf16 Linears.  The two streams run the same Linear shapes on different weights; their

@@ -223,6 +223,10 @@ class MMDiTEngine:
     def mod_offset(self, kind: int, index: int) -> int:
         return self.lib.dk_mmdit_mod_offset(self._h, kind, index)
 
+    def score_bound(self, kind: int, index: int) -> float:
+        """dk_mmdit_score_bound: the bound on |scale q.k| block ``index`` (kind 0 double, 2 single) hands its joint attention launch; 0: unknown"""
+        return float(self.lib.dk_mmdit_score_bound(self._h, kind, index))
+
     # -- reference API ---------------------------------------------------------------------
     def cache_modulation_params(self, pooled_text_embeddings: Tensor, timesteps: Sequence[float]) -> None:
         """MMDiT.cache_modulation_params (mmdit.py:77-180); ``timesteps`` are host floats

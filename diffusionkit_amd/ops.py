@@ -296,11 +296,27 @@ def conv3x3_gn(x: Tensor, w: Tensor, bias: Tensor, gn_table: Optional[Tensor] = 
     return out
 
 
-def attention(qkv: Tensor, H: int, D: int, scale: Optional[float] = None, workspace: Optional[Tensor] = None) -> Tensor:
+def attention(qkv: Tensor, H: int, D: int, scale: Optional[float] = None, workspace: Optional[Tensor] = None,
+              score_bound: Optional[float] = None, qn=None) -> Tensor:
     """SDPA over a token-major [B, S, 3*H*D] projection buffer -> [B, S, H*D].  ``workspace``: lab only (trace buffer of attention4.hip's
-    DK4_TRACE builds, dk_attention_set_workspace for the duration of the call)."""
+    DK4_TRACE builds, dk_attention_set_workspace for the duration of the call).
+    ``score_bound``: the caller's PROMISE that |scale * q.k| <= score_bound for every query / key pair of the call (dk_attention_desc.score_bound: not
+    checked; it lets the one-wave-per-SIMD kernel drop its running row maximum).  ``qn``: (qn_a, qn_b, qn_split[, q_rope]), the query QKNorm (+ RoPE)
+    of the kernel's Q load as ``attention_desc_call`` names them (qn_a / qn_b may be None: RoPE only).  Either one sends the call through
+    dk_attention_desc_bf16."""
     lib = _lib.load()
     _require_cuda(qkv, "qkv", BF)
+    if score_bound is not None or qn is not None:
+        assert workspace is None, "attention: the lab workspace goes with the plain call only"
+        B, S, ld = qkv.shape
+        h = H * D
+        out = torch.empty(B, S, h, dtype=BF, device=qkv.device)
+        kw = dict(q=qkv, k=qkv[:, :, h:], v=qkv[:, :, 2 * h:], out=out, B=B, H=H, S=S, D=D, ld=ld, ldo=h,
+                  scale=scale if scale is not None else 1.0 / math.sqrt(D), score_bound=float(score_bound or 0.0))
+        if qn is not None:
+            kw.update(qn_a=qn[0], qn_b=qn[1], qn_split=int(qn[2]), qn_eps=1e-6, q_rope=qn[3] if len(qn) > 3 else None)
+        attention_desc_call(BF, **kw)
+        return out
     if workspace is None:
         _lib.ensure_attention_workspace(qkv.device)
     B, S, ld = qkv.shape

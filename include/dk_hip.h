@@ -209,6 +209,11 @@ typedef struct dk_attention_desc {
   void* O8_scales;
   int32_t o8_ld;
   int64_t o8_rows; /* rows of the buffer O8 points into (sizes its scale array) */
+  /* The caller's bound on |scale * q.k| over the whole launch (natural units, behind the query transform of the Q load); 0: unknown.  Additive in
+   * ABI 5 (trailing field: zero the descriptor).  A PROMISE, not checked: with 0 < score_bound, 2 * score_bound * log2(e) <= 64, the fused query
+   * load and a launch the one-wave-per-SIMD kernel takes, that kernel's tile loop keeps no running row maximum (dk_attention_plan_t.untracked);
+   * scores beyond the bound can then overflow.  QK-normed operands give the bound from the norm weights: max|w_q| * max|w_k| * sqrt(D) * 1.02. */
+  float score_bound;
 } dk_attention_desc;
 int dk_attention_desc_bf16(const dk_attention_desc* d, void* stream);
 
@@ -243,6 +248,7 @@ typedef struct dk_attention_plan_t {
   int32_t launches;  /* kernel launches the call expands to */
   int32_t n_cu;      /* compute units the rules assumed */
   int32_t o8_split;  /* INPUT, see above */
+  int32_t untracked; /* kernel 10: the tile loop without the running row maximum (d->score_bound admits it and dk_tune_set("attn_track", 1) is not set) */
 } dk_attention_plan_t;
 int dk_attention_plan(const dk_attention_desc* d, size_t workspace_bytes, dk_attention_plan_t* plan);
 
@@ -711,6 +717,11 @@ int dk_mmdit_bind(dk_mmdit* m, const char* name, const void* dev_ptr);
  * (kind 0 image stream of double block i, 1 text stream, 2 single block i, 3 final layer) */
 int dk_mmdit_mod_rows(const dk_mmdit* m);
 int dk_mmdit_mod_offset(const dk_mmdit* m, int32_t kind, int32_t index);
+/* The bound on |scale * q.k| the engine hands the joint attention launch of a block (dk_attention_desc.score_bound): max|w_q| * max|w_k| * sqrt(D) *
+ * 1.02 over the QKNorm weights of the block's streams, read from the device once, in the first dk_mmdit_prepare behind a dk_mmdit_bind.  kind 0:
+ * double block `index` (both streams), 2: single block `index` (the kinds of dk_mmdit_mod_offset).  0: unknown -- no QKNorm weights, not bf16, not
+ * prepared yet, or no such block.  Additive in ABI 5. */
+float dk_mmdit_score_bound(const dk_mmdit* m, int32_t kind, int32_t index);
 
 size_t dk_mmdit_workspace_bytes(const dk_mmdit* m, int32_t batch, int32_t latent_h, int32_t latent_w,
                                 int32_t text_len, int32_t n_timesteps);
@@ -1020,6 +1031,7 @@ int dk_profile_read(int32_t kernel_class, double* total_ms, double* total_flops,
  * tile loop: head_dim 128, S a multiple of 256 and >= 768, falls back to 9 otherwise -- the automatic choice from S = 2048 on, and from
  * S = 1024 for launches of at least three quarters of a round of 256-query blocks);
  * "attn_split": key ranges of the one-wave-per-SIMD kernel's last-round query blocks (-1 automatic, 0 never, 2..4);
+ * "attn_track": 1 = that kernel keeps its running row maximum whatever score_bound a launch carries (-1 / 0 automatic);
  * "attn_fuse_q": 0 = stand-alone query QKNorm + RoPE pass; "conv_halo": 0 = VAE convolutions through the GEMM form;
  * "conv_v4": the fused VAE convolutions with >= 256 output channels on the one-wave-per-SIMD kernel (1 where one image fills the
  * CUs, 0 never, 2 wherever eligible);

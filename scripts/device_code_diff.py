@@ -13,7 +13,12 @@ markdown table row per object; exit status 1 when any differs or exists on one s
 For changes that ADD kernels to an object (A: the parent's build): the object's .text grows, so every function of A's code object is compared on
 its own -- its disassembly (instructions and operands, without addresses) and its block of the notes (argument layout, register counts, LDS /
 scratch) -- against the function of the same name in B.  One row per object with the functions of A that differ or are gone, and the names B adds;
-exit status 1 when a function of A differs or is missing."""
+exit status 1 when a function of A differs or is missing.
+
+    python scripts/device_code_diff.py --kernels --rename OLD=NEW [--rename ...] <build dir A> <build dir B>
+
+... where a kernel template gained a parameter: function OLD of A is compared with function NEW of B (mangled names; the name itself is
+taken out of the notes before they are compared)."""
 import glob
 import hashlib
 import os
@@ -51,6 +56,7 @@ def kernel_code(obj):
         dis = subprocess.check_output([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", "--no-leading-addr", f"{t}/k.co"], text=True)
     blocks = {}
     for b in re.split(r"\n  - \.agpr_count", notes)[1:]:
+        b = b.split("\namdhsa.target")[0]  # (the last kernel's block would carry the trailer of the notes)
         m = re.search(r"\.name:\s+(\S+)", b)
         if m:
             blocks[m.group(1)] = b
@@ -60,12 +66,13 @@ def kernel_code(obj):
         if m:
             cur = m.group(1)
             out[cur] = []
-        elif cur is not None and line.strip():
+        elif cur is not None and line.strip() and line.strip() != "...":  # ("...": the disassembler's mark for the zero padding behind the last function)
             out[cur].append(re.sub(r"//.*$", "", line).strip())
     return {k: (v, blocks.get(k)) for k, v in out.items()}
 
 
-def main_kernels(a, b):
+def main_kernels(a, b, rename=None):
+    rename = rename or {}
     names = sorted({os.path.basename(p) for p in glob.glob(os.path.join(a, "*.o"))})
     print("| object | functions in A | identical in B | different or missing in B | added by B |")
     print("|---|---|---|---|---|")
@@ -80,8 +87,14 @@ def main_kernels(a, b):
             print(f"| {n} | {len(ka)} | 0 | no device code in B | |")
             bad += len(ka)
             continue
-        diff = [k for k in ka if ka[k] != kb.get(k)]
-        added = [k for k in kb if k not in ka]
+        def same(k):
+            k2 = rename.get(k, k)
+            if k2 not in kb:
+                return False
+            (ia, na), (ib, nb) = ka[k], kb[k2]
+            return ia == ib and (na or "").replace(k, "@") == (nb or "").replace(k2, "@")
+        diff = [k for k in ka if not same(k)]
+        added = [k for k in kb if k not in ka and k not in rename.values()]
         print(f"| {n} | {len(ka)} | {len(ka) - len(diff)} | {', '.join(diff) or 'none'} | {len(added)} |")
         bad += len(diff)
     print(f"\n{len(names)} objects, {bad} functions of A with differences")
@@ -113,8 +126,15 @@ def main(a, b):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) == 4 and sys.argv[1] == "--kernels":
-        sys.exit(main_kernels(sys.argv[2], sys.argv[3]))
+    if len(sys.argv) >= 4 and sys.argv[1] == "--kernels":
+        args, ren = sys.argv[2:], {}
+        while len(args) >= 2 and args[0] == "--rename":
+            old, new = args[1].split("=", 1)
+            ren[old] = new
+            args = args[2:]
+        if len(args) != 2:
+            sys.exit(__doc__)
+        sys.exit(main_kernels(args[0], args[1], ren))
     if len(sys.argv) != 3:
         sys.exit(__doc__)
     sys.exit(main(sys.argv[1], sys.argv[2]))

@@ -22,7 +22,8 @@ products and sums included -- are multiplied once, at the head of the next phase
 behind a scalar test of s[56:57]).  Program: a first asm statement with K(0)'s pieces (in front of the query loads), then prologue (K(1..3),
 V(0..2), tile -1 = the scores of tile 0), a four-tile loop (ring slot x score-set parity), eight peeled tiles.
 
-  python scripts/gen_attn5.py            write diffusionkit_amd/csrc/attention5_dma.inc, attention5_asm.inc, attention5_clobbers.inc
+  python scripts/gen_attn5.py            write diffusionkit_amd/csrc/attention5_dma.inc, attention5_asm.inc, attention5_clobbers.inc and
+                                         attention5_asm_nt.inc (program(track=False): the body for bounded scores, one offset per row)
   python scripts/gen_attn5.py --check    also run the instruction-level emulator (4 waves x 64 lanes) against an fp64 softmax(Q K^T) V
 
 v[224:225] mc = running max * c   v[226:227] l   v[228:231] psum[parity][qb]   v[232:233] pend   v[234:237] temporaries
@@ -230,6 +231,16 @@ def rescale_block(label):
     return out
 
 
+def first_max_stream(t):
+    """track=False: the row maxima of the job's first tile (max_stream's chains and cross-half exchange) -> mc = max * c, set ONCE, in the prologue.
+    No decision, no factor: the caller's bound on |scale q.k| keeps every later exponent argument in range (attention.hip, dk_attention_route)."""
+    ms = max_stream(t, 0)
+    units = ms[36:38]
+    for qb in range(2):
+        units.append([I("v_mul_s", f"v_mul_f32 v{MC[qb]}, s51, v{TMP[2 * qb]}", dst=MC[qb], s=51, b=TMP[2 * qb])])
+    return ms[:36] + units
+
+
 class Gaps:
     """the 32 MFMA gaps of a phase (+ one behind the last MFMA): every stream is spread over its window on its own; inside a gap the streams
     are merged round-robin, so that the exponentials of one stream sit between instructions of the others"""
@@ -274,9 +285,10 @@ class Gaps:
         return out
 
 
-def iteration(j, lab, qk=True, pv=True, kread=True, dma_k=True, dma_v=True, mx=True, exp_head=True, landed=True):
+def iteration(j, lab, qk=True, pv=True, kread=True, dma_k=True, dma_v=True, mx=True, exp_head=True, landed=True, track=True):
     """tile j: phase 1 (S(j+1)), barrier, phase 2 (P(j) V(j)).  Flags switch parts off in the prologue / the peeled last iterations.
-    lab: base of this copy's numeric labels (10 per copy)"""
+    lab: base of this copy's numeric labels (10 per copy).  track=False: the exponent offset stays where the prologue (j = -1) put it -- no row
+    maxima, no decision, no pending factor, no rescale block; the first exponentials of tile j + 1 start in the gaps the maxima leave free"""
     p = j & 1
     out, tails = [], []
     if (ABL & 8) and j >= 0:
@@ -287,11 +299,12 @@ def iteration(j, lab, qk=True, pv=True, kread=True, dma_k=True, dma_v=True, mx=T
     if pv:  # the row sums of tile j - 1 are final; a recorded rescale is applied now (P(j - 1) V(j - 1) is complete)
         for qb in range(2):
             head.append(I("v_add", f"v_add_f32 v{L[qb]}, v{L[qb]}, v{PS[p ^ 1][qb]}", dst=L[qb], a=L[qb], b=PS[p ^ 1][qb]))
-        head.append(I("s_cmp_lg64", "s_cmp_lg_u64 s[56:57], 0", a=56))
-        if not (ABL & 2048):
-            head.append(I("cbranch_scc1", f"s_cbranch_scc1 {lab + 8}f", target=f"RESC{lab + 8}"))
-        head.append(I("label", f"{lab + 9}:", name=f"RESCBACK{lab + 8}"))
-        tails.extend(rescale_block(lab + 8))
+        if track:
+            head.append(I("s_cmp_lg64", "s_cmp_lg_u64 s[56:57], 0", a=56))
+            if not (ABL & 2048):
+                head.append(I("cbranch_scc1", f"s_cbranch_scc1 {lab + 8}f", target=f"RESC{lab + 8}"))
+            head.append(I("label", f"{lab + 9}:", name=f"RESCBACK{lab + 8}"))
+            tails.extend(rescale_block(lab + 8))
     qk = qk and not (ABL & 64) and not (ABL & 4096)
     mf1 = [mfma_qk(j + 1, qb, half, kk) for kk in range(8) for half in range(2) for qb in range(2)] if qk else []
     if pv:
@@ -319,9 +332,15 @@ def iteration(j, lab, qk=True, pv=True, kread=True, dma_k=True, dma_v=True, mx=T
     g2 = Gaps()
     pv_m = pv and not (ABL & 64) and not (ABL & 8192)
     mf2 = [mfma_pv(qb, dt, n) for n in range(4) for dt in range(4) for qb in range(2)] if pv_m else []
-    if exp_head and not (ABL & 1):
-        g2.spread(exp_stream(j + 1, [0]), 14, 32)
-    if mx and not (ABL & 2):  # the eight maximum chains over gaps 1 .. 7, then exchange / test + select / factor / pend of the two blocks
+    if exp_head and not (ABL & 1):  # (behind the decision of tile j + 1; without one: from gap 1, where the maxima started to read these scores)
+        g2.spread(exp_stream(j + 1, [0]), 14 if track or j < 0 else 1, 32)
+    if mx and not track:  # the offset of the whole key range, from the first tile's maxima (prologue only)
+        if j < 0:
+            ms = first_max_stream(j + 1)
+            g2.spread(ms[:36], 1, 8)
+            for k, u in enumerate(ms[36:]):
+                g2.put(8 + k, u)
+    elif mx and not (ABL & 2):  # the eight maximum chains over gaps 1 .. 7, then exchange / test + select / factor / pend of the two blocks
         ms = max_stream(j + 1, lab)
         if not (ABL & 128):
             g2.spread(ms[:36], 1, 8)
@@ -351,9 +370,10 @@ def iteration(j, lab, qk=True, pv=True, kread=True, dma_k=True, dma_v=True, mx=T
     return out, tails
 
 
-def program():
+def program(track=True):
     """nt = S / 64 tiles, a multiple of 4, >= 12.  Prologue (K(0..3), V(0..2); iteration -1: the scores of tile 0), a four-tile loop over
-    j = 0 .. nt - 9, eight peeled iterations."""
+    j = 0 .. nt - 9, eight peeled iterations.
+    track=False: the body for launches whose scores are bounded (attention5_asm_nt.inc): the same program without the running maximum."""
     P, tails = [], []
     # ---- block 1 (its own asm statement, in front of the query loads): the DMA pieces of K(0); the loads of the query rows behind them share
     # their round trip.  (All seven prologue tiles in front of the query loads made every workgroup wait for 176 KB: the counter retires in order.)
@@ -371,6 +391,8 @@ def program():
     P.append(I("split", None))
     # ---- block 2
     for d, s in ((48, "%[koff]"), (49, "%[voff]"), (50, "%[tileb]"), (52, "0x40b8aa3b"), (53, "%[ntrip]"), (55, "%[dbase]"), (56, "0"), (57, "0")):  # s52 = 4 * log2(e)
+        if not track and d in (52, 56, 57):
+            continue
         P.append(I("s_mov", f"s_mov_b32 s{d}, {s}", dst=d, src=s))
     pro = []
     for t in range(3):  # K(1) V(0) | K(2) V(1) | K(3) V(2): the order the waits retire them in
@@ -390,14 +412,15 @@ def program():
     for qb in range(2):
         P.append(I("v_movi", f"v_mov_b32 v{MC[qb]}, 0xf149f2ca", dst=MC[qb], imm=0xf149f2ca))  # -1e30
         P.append(I("v_movi", f"v_mov_b32 v{L[qb]}, 0", dst=L[qb], imm=0))
-        P.append(I("v_movi", f"v_mov_b32 v{PEND[qb]}, 1.0", dst=PEND[qb], imm=0x3f800000))
+        if track:
+            P.append(I("v_movi", f"v_mov_b32 v{PEND[qb]}, 1.0", dst=PEND[qb], imm=0x3f800000))
         P.append(I("v_movi", f"v_mov_b32 v{PS[1][qb]}, 0", dst=PS[1][qb], imm=0))
     P.append(need("P0"))
     P.append(BARRIER())
     P.extend(k_reads(0))  # K(0) -> AGPRs
     P.append(wait(lgkm=0))
     # iteration -1: scores of tile 0; behind its barrier: K(1) -> AGPRs, maxima + decision of tile 0, first exponentials, pieces of K(4) and V(3)
-    it, tl = iteration(-1, 100, pv=False)
+    it, tl = iteration(-1, 100, pv=False, track=track)
     P.extend(it)
     tails.extend(tl)
     set_waits(P, resolve(P, []))
@@ -405,7 +428,7 @@ def program():
     def group(j0):
         body, tl = [], []
         for k in range(4):
-            it, t = iteration(j0 + k, 200 + 100 * k)
+            it, t = iteration(j0 + k, 200 + 100 * k, track=track)
             body.extend(it)
             tl.extend(t)
         return body, tl
@@ -419,7 +442,7 @@ def program():
     # peeled: j = nt - 8 + k.  K(j + 5) exists for k <= 2, V(j + 4) for k <= 3, K(j + 2) for k <= 5, tile j + 1 for k <= 6
     pe = []
     for k in range(8):
-        it, tl = iteration(8 + k, 600 + 100 * k, dma_k=k <= 2, dma_v=k <= 3, kread=k <= 5, qk=k <= 6, mx=k <= 6, exp_head=k <= 6, landed=k <= 6)
+        it, tl = iteration(8 + k, 600 + 100 * k, dma_k=k <= 2, dma_v=k <= 3, kread=k <= 5, qk=k <= 6, mx=k <= 6, exp_head=k <= 6, landed=k <= 6, track=track)
         pe.extend(it)
         tails.extend(tl)
     set_waits(pe, resolve(pe, P + ba + bb))
@@ -437,6 +460,19 @@ def program():
 
 CLOBBERS = [f"v{i}" for i in range(192, 224)] + [f"v{i}" for i in range(228, 238)] + [f"a{i}" for i in range(256)] + [f"s{i}" for i in range(48, 58)] + \
            ["m0", "vcc", "scc", "memory"]
+
+
+def emit_nt(csrc):
+    """the body without the running maximum; its first asm statement (K(0)'s pieces) and its clobber list are the tracked body's files"""
+    P = program(track=False)
+    n_mfma = sum(1 for i in P if i.op == "mfma32")
+    k = [i for i, x in enumerate(P) if x.op == "split"][0]
+    P_all, P = P, P[k + 1:]
+    with open(os.path.join(csrc, "attention5_asm_nt.inc"), "w") as f:
+        f.write("// GENERATED by scripts/gen_attn5.py (program(track=False)) -- do not edit; the CPU emulator in that script checks this instruction list.\n")
+        f.write(f"// {len(P)} instructions, {n_mfma} MFMAs (prologue with the ONE exponent offset per row, four-tile loop, eight peeled tiles: no running maximum, no rescale).\n")
+        f.write("\n".join('    "' + ins.text + '\\n"' for ins in P) + "\n")
+    return P_all
 
 
 def emit(csrc):
@@ -463,8 +499,11 @@ if __name__ == "__main__":
     csrc = os.path.join(root, "diffusionkit_amd", "csrc")
     P = emit(csrc)
     print(f"wrote attention5_asm.inc ({len(P)} instructions)")
+    P_nt = emit_nt(csrc)
+    print(f"wrote attention5_asm_nt.inc ({len(P_nt)} instructions)")
     if "--check" in sys.argv:
         import attn5_emu
         ok = attn5_emu.check_all(P, verbose="-v" in sys.argv)
+        ok &= attn5_emu.check_all(P_nt, verbose="-v" in sys.argv, bounded=True)
         print("ALL OK" if ok else "FAILED")
         sys.exit(0 if ok else 1)
