@@ -780,6 +780,9 @@ static int gn_nchunk(long HW, int C) {
 extern "C" size_t dk_groupnorm_scratch_floats(int32_t B, int32_t G) { return (size_t)B * 1024 * 2 * G + (size_t)B * G * 2; }
 int groupnorm_launch(int dtype, const void* x, void* y, int B, long HW, int C, int G, const void* gamma, const void* beta, float eps,
                      int fuse_silu, float* scratch, hipStream_t st) {  // (dk_engine.h)
+  // (dk_launch_groupnorm_apply's bound, asked before the statistics pass: a refused call launches nothing)
+  DK_REQUIRE(C >= 8 && C % 8 == 0, "channels must be 8 * 2^k <= 2048");
+  DK_REQUIRE((double)HW * (C / 8) < 2147483648.0, "one batch row must hold < 2^31 16-byte chunks");
   const int nchunk = gn_nchunk(HW, C);
   float* mean_rstd = scratch + (size_t)B * 1024 * 2 * G;
   int rc = DK_EL(dtype, dk_launch_groupnorm_stats)((const bf16_t*)x, B, HW, C, G, scratch, nchunk, mean_rstd, eps, st);

@@ -23,7 +23,7 @@ import torch
 
 from tests import _footprint as fp
 from tests import _fp8 as f8
-from tests import _fused_cases as fc
+from tests import _op_launches as L
 from tests._util import TOL_SINGLE_OP, rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -81,21 +81,7 @@ def run_family(dev, dt, ops_cpu, ref, cases, launch, what, soft_gate=None, guard
         print(f"[footprint] {what}: soft region of the Q case: {n_soft} elements")
 
 
-def tuned(**knobs):
-    """context manager: ops.tune(key, value) for the block, the defaults afterwards (conv_v4's default is 1)"""
-    from contextlib import contextmanager
-    from diffusionkit_amd import ops
-
-    @contextmanager
-    def cm():
-        try:
-            for k, v in knobs.items():
-                ops.tune(k, v)
-            yield
-        finally:
-            for k in knobs:
-                ops.tune(k, 1 if k == "conv_v4" else -1)
-    return cm()
+tuned = L.tuned  # (ops.tune(key, value) for a block, the defaults afterwards)
 
 
 def ws_flags_zero(ws):
@@ -103,8 +89,7 @@ def ws_flags_zero(ws):
 
 
 # ---- GEMM ---------------------------------------------------------------------------------------------------------------------------
-GEMM_FORMS = [("bf16_128", BF, dict(gemm=128)), ("bf16_v3_mf8", BF, dict(gemm=9, gemm_mf=8)), ("bf16_v3_mf7", BF, dict(gemm=9, gemm_mf=7)),
-              ("bf16_v4", BF, dict(gemm=10)), ("f16_auto", F16, dict(gemm=-1)), ("f16_v3", F16, dict(gemm=9))]
+GEMM_FORMS = L.GEMM_FORMS
 
 
 @pytest.mark.parametrize("epi", ["bias", "gate_res"])
@@ -116,19 +101,13 @@ def test_gemm_joint_buffer_text_stream(dev, form, B, S_t, S_i, epi):
     segment column / element -- the gate's segment map across a tile that straddles two segments included"""
     from diffusionkit_amd import ops
     _, dt, knobs = form
-    h, N, S = 192, 512, S_t + S_i
     ops_cpu, ref, cases = fp.gemm_joint_family(B, S_t, S_i, epi, dt)
     ws = ops.gemm_workspace(dev)
 
+    joint = L.gemm_joint(dt, knobs, B, S_t, S_i, epi)
+
     def launch(v):
-        kw = dict(A=v["att"], W=v["w"], C=v["X"], bias=v["b"], M=B * S_t, N=N, K=h, lda=h, ldc=N, a_seg_len=S_t, a_seg_stride=S, c_seg_len=S_t,
-                  c_seg_stride=S, alpha=1.0, epilogue=ops.DK_EPI_BIAS, workspace=ws.data_ptr(), workspace_bytes=ws.numel())
-        if epi == "gate_res":
-            kw.update(epilogue=ops.DK_EPI_GATE_RES, res=v["X"], ldr=N, r_seg_len=S_t, r_seg_stride=S, gate=v["gate"].data_ptr() + N * 2,
-                      gate_seg_len=S_t, gate_stride=2 * N)
-        with tuned(**knobs):
-            ops.gemm_desc_call(dtype=dt, **kw)
-        return v["X"]
+        return joint(dict(v, ws=ws))
     run_family(dev, dt, ops_cpu, ref, cases, launch, f"gemm {form[0]} {(B, S_t, S_i)} {epi}")
     ws_flags_zero(ws)
 
@@ -143,22 +122,20 @@ def test_gemm_k_split_finisher_adds_the_last_range(dev):
     out, og = fp.guarded(torch.empty(M, N, dtype=BF, device=dev), PAD, SENTINEL)
     plain = {}
 
+    cut, whole = L.gemm_ksplit(1), L.gemm_ksplit(0)
+
     def launch(v):
-        with tuned(gemm=9, gemm_mf=8, gemm_split=1):
-            ops.linear(v["x"], v["w"], v["b"], epilogue=ops.DK_EPI_GATE_RES, gate=v["gate"], res=v["res"], gate_seg_len=M, out=out, workspace=ws)
+        cut(dict(v, out=out, ws=ws))
         if not plain:
-            with tuned(gemm=9, gemm_mf=8, gemm_split=0):
-                plain["y"] = ops.linear(v["x"], v["w"], v["b"], epilogue=ops.DK_EPI_GATE_RES, gate=v["gate"], res=v["res"], gate_seg_len=M, workspace=ws)
+            plain["y"] = whole(dict(v, ws=ws))
             assert not torch.equal(plain["y"], out), "gemm_split 1 was expected to cut the remainder tiles along K (other summation order)"
         return out
     run_family(dev, BF, ops_cpu, ref, cases, launch, "gemm K split", guards=[("out", og)])
     ws_flags_zero(ws)
 
 
-def _fused_launch(call, bufs, ws=None):
-    from diffusionkit_amd import ops
-    with tuned(**call.tune):
-        ops.gemm_fused_call(*fc.resolve(call, lambda name: (ws if name == "ws" else bufs[name]).data_ptr(), ws.numel() if ws is not None else 0))
+def _fused_launch(call, bufs):
+    L.fused(call)(bufs)
 
 
 def test_fused_pair_streams_are_independent(dev):
@@ -274,10 +251,7 @@ def test_gemm_fp8_rows_behind_m_and_row_independence(dev, M):
 
 # ---- attention ------------------------------------------------------------------------------------------------------------------------
 # (id, dtype, knobs, (B, H, S, D), query block of the kernel: attention2.hip QB = NW * 32 = 128, attention4.hip 256, attention5.hip 4 waves x 64)
-ATTN_FORMS = [("lean_100_d64", BF, dict(attn=4), (2, 2, 100, 64), 128), ("lean_129_d128", BF, dict(attn=4), (2, 2, 129, 128), 128),
-              ("alt_129", BF, dict(attn=9), (2, 2, 129, 128), 256), ("alt_250", BF, dict(attn=9), (1, 2, 250, 128), 256),
-              ("wave_768", BF, dict(attn=10), (2, 2, 768, 128), 256), ("wave_key_split_3072", BF, dict(attn=10, attn_split=2), (1, 2, 3072, 128), 256),
-              ("f16_lean_100_d64", F16, dict(), (2, 2, 100, 64), 128)]
+ATTN_FORMS = L.ATTN_FORMS
 
 
 def _attn_gate(dt, QB, D):
@@ -296,16 +270,14 @@ def test_attention_footprints(dev, form):
     out, og = fp.guarded(torch.empty(B, S, h, dtype=dt, device=dev), 8, SENTINEL)
     whole = {}
 
+    run, run_whole = L.attention(dt, knobs, B, H, S, D), L.attention(dt, dict(attn=knobs.get("attn", -1), attn_split=0), B, H, S, D)
+
     def launch(v):
-        base = v["qkv"].data_ptr()
-        kw = dict(q=base, k=base + 2 * h, v=base + 4 * h, B=B, H=H, S=S, D=D, ld=3 * h, ldo=h, scale=1.0 / math.sqrt(D))
         out.fill_(SENTINEL)
-        with tuned(**knobs):
-            ops.attention_desc_call(dtype=dt, out=out, **kw)
+        run(dict(v, out=out))
         if "attn_split" in knobs and not whole:  # (the switch does select the key-split jobs: their partials are rounded to bf16)
             whole["y"] = torch.empty_like(out)
-            with tuned(attn=knobs["attn"], attn_split=0):
-                ops.attention_desc_call(dtype=dt, out=whole["y"], **kw)
+            run_whole(dict(v, out=whole["y"]))
             assert not torch.equal(whole["y"], out), "attn_split did not select the key-split jobs"
         return out
     run_family(dev, dt, ops_cpu, ref, cases, launch, f"attention {name}", soft_gate=_attn_gate(dt, QB, D), guards=[("out", og)])
@@ -343,14 +315,11 @@ def test_attention_q_load_norm_rope_footprint(dev):
     tabd, tg = fp.guarded(tab.to(dev), PAD) if tab is not None else (None, None)
     out, og = fp.guarded(torch.empty(B, S, h, dtype=BF, device=dev), 8, SENTINEL)
 
+    run = L.attention(BF, dict(attn=c["mode"], attn_split=c.get("attn_split", -1)), B, H, S, D, L.attention_q_extra(c))
+
     def launch(v):
-        base = v["qkv"].data_ptr()
         out.fill_(SENTINEL)
-        with tuned(attn=c["mode"], attn_split=c.get("attn_split", -1)):
-            ops.attention_desc_call(q=base, k=base + 2 * h, v=base + 4 * h, out=out, B=B, H=H, S=S, D=D, ld=3 * h, ldo=h, scale=1.0 / math.sqrt(D),
-                                    qn_a=v["qa"] if c["norm"] else None, qn_b=v["qb"] if c["norm"] else None, qn_split=c["split"], qn_eps=fc.KN_EPS,
-                                    q_rope=tabd)
-        return out
+        return run(dict(v, out=out, **({"rope": tabd} if tabd is not None else {})))
     run_family(dev, BF, ops_cpu, ref, [fp.q_head_case(B, H, S, D, QB)], launch, f"attention q load {c['id']}", soft_gate=_attn_gate(BF, QB, D),
                guards=[("out", og)] + ([("rope", tg)] if tg else []))
 
@@ -369,14 +338,13 @@ def test_attention_mx8_copy_footprint(dev):
     out, og = fp.guarded(torch.empty(B, S, h, dtype=BF, device=dev), 8, SENTINEL)
     o8b, o8g = fp.guarded(torch.empty(M, h, dtype=torch.uint8, device=dev), 8, 0xAB)
 
+    copy = L.attention_mx8(c)
+
     def run():
-        base = qkv.data_ptr()
         sc = torch.zeros(ops.mx_scale_bytes(M, h), dtype=torch.uint8, device=dev)
         out.fill_(SENTINEL)
         o8b.fill_(0xAB)
-        with tuned(attn=c["mode"], attn_split=0):
-            ops.attention_desc_call(q=base, k=base + 2 * h, v=base + 4 * h, out=out, O8=o8b, O8_scales=sc, o8_ld=h, o8_rows=M, B=B, H=H, S=S, D=D,
-                                    ld=3 * h, ldo=h, scale=1.0 / math.sqrt(D))
+        copy(dict(qkv=qkv, out=out, o8=o8b, o8_scales=sc))
         return out.clone().cpu(), o8b.clone().cpu().reshape(B, S, h), f8.array_to_scales(sc, M, h).reshape(B, S, h // 32)
     y0, q0, e0 = run()
     for name, idx in case.poison:
@@ -436,27 +404,20 @@ def test_softmax_and_transpose_footprints(dev, dt):
 def test_patchify_and_euler_step_footprints(dev, flux):
     """dk_latent_to_tokens + dk_euler_cfg_step, CFG on: one latent element -> exactly one token feature, in both CFG copies; one model output element ->
     exactly one latent element (and its token feature of the next step's input)"""
-    from diffusionkit_amd import _lib, ops
-    from diffusionkit_amd.engine import _stream
     ops_cpu, ref, (sigma, sigma_next, w), cases = fp.patchify_family(flux)
-    n_img, Hl, Wl, C = ops_cpu["x"].shape
-    p = 2
-    lib = _lib.load()
     tok0, g0 = fp.guarded(torch.empty(ops_cpu["out"].shape, dtype=BF, device=dev), 8, SENTINEL)
     tok, g1 = fp.guarded(torch.empty(ops_cpu["out"].shape, dtype=BF, device=dev), 8, SENTINEL)
 
+    step = L.patchify_step(flux, (sigma, sigma_next, w))
+
     def launch(v):
-        _lib.check(lib.dk_latent_to_tokens(v["x"].data_ptr(), tok0.data_ptr(), n_img, 2, Hl, Wl, C, p, int(flux), _stream()))
-        ops.euler_cfg_step(v["x"], v["out"], tok, n_img, True, p, int(flux), sigma, sigma_next, w)
-        return dict(tok0=tok0, x=v["x"], tok=tok)
+        return step(dict(v, tok0=tok0, tok=tok))
     run_family(dev, BF, ops_cpu, ref, cases, launch, f"patchify flux={flux}", guards=[("tok0", g0), ("tok", g1)], dtypes={"x": torch.float32})
 
 
 # ---- convolutions ------------------------------------------------------------------------------------------------------------------------
 def _conv_launch(ops, form, res):
-    def launch(v):
-        return ops.conv3x3(v["x"], v["w"], v["b"], upsample=form == "up", res=v.get("res") if res else None, downsample=form == "s2")
-    return launch
+    return L.conv(form, res)
 
 
 @pytest.mark.parametrize("form,res", [("plain", False), ("plain", True), ("s2", False), ("up", False)])
@@ -476,20 +437,12 @@ def test_conv3x3_on_256_tile_kernel_footprints(dev, form, shape):
     buffer offsets)"""
     from diffusionkit_amd import ops
     ops_cpu, ref, cases = fp.conv_family(*shape, form, BF, res=form == "plain", tile=8)
-    launch = _conv_launch(ops, form, form == "plain")
-
-    def forced(v):
-        with tuned(gemm=9, gemm_mf=8):
-            return launch(v)
+    forced = L.conv(form, form == "plain", dict(gemm=9, gemm_mf=8))
     run_family(dev, BF, ops_cpu, ref, cases, forced, f"conv3x3 on gemm256v3 {form}")
 
 
 # (id, dtype, conv_v4 knob, (B, H, W, C, O) with H x W the INPUT size, upsample, table, residual, shortcut columns)
-HALO_FORMS = [("halo_table", BF, 0, (2, 16, 16, 64, 128), False, True, False, 0), ("halo_plain_res", BF, 0, (2, 16, 16, 64, 128), False, False, True, 0),
-              ("halo_table_shortcut", BF, 0, (2, 16, 16, 64, 128), False, True, False, 64), ("halo_upsample", BF, 0, (2, 8, 8, 64, 128), True, False, False, 0),
-              ("f16_halo_table_res", F16, 0, (2, 16, 16, 64, 128), False, True, True, 0),
-              ("v4_256_table_res", BF, 2, (2, 32, 48, 128, 256), False, True, True, 0), ("v4_128_table", BF, 2, (2, 32, 48, 128, 128), False, True, False, 0),
-              ("v4_upsample", BF, 2, (2, 16, 24, 128, 256), True, False, False, 0)]
+HALO_FORMS = L.HALO_FORMS
 
 
 @pytest.mark.parametrize("form", HALO_FORMS, ids=lambda f: f[0])
@@ -528,14 +481,7 @@ def test_conv3x3_gn_footprints(dev, form):
             part = torch.stack([fp.tile_mask(per_group[..., g_]) for g_ in range(G)], dim=-1)
             case.hand = dict(y=case.hand, part=part[..., None].expand(*part.shape, 2).clone())
 
-    def launch(v):
-        wk = v["w"].reshape(O, -1)
-        if C2:
-            wk = torch.cat([wk, v["ws"]], dim=1)
-        with tuned(conv_v4=v4):
-            y = ops.conv3x3_gn(v["x"], wk, v["b"], gn_table=tab, silu=True, res=v.get("res"), x2=v.get("x2"), bias2=v.get("bs"),
-                               stats_groups=G if stats else 0, upsample=ups)
-        return dict(y=y[0], part=y[1]) if stats else y
+    launch = L.conv_gn(v4, O, C2, G, stats, ups, tab)
     run_family(dev, dt, ops_cpu, ref, cases, launch, f"conv3x3_gn {name}")
 
 
@@ -553,9 +499,11 @@ def test_conv_out_image_tail_footprints(dev):
     bufs = upload(ops_cpu, dev, BF)
     v = {k: t for k, (t, _) in bufs.items()}
 
+    tail = L.image_tail(tab)
+
     def run():
-        img, u8, raw = ops.conv3x3_gn(v["x"], v["w"].reshape(3, -1), v["b"], gn_table=tab, image=True)
-        return img.clone().cpu(), u8.clone().cpu(), raw.clone().cpu()
+        y = tail(v)
+        return y["img"].clone().cpu(), y["u8"].clone().cpu(), y["raw"].clone().cpu()
     img0, u80, raw0 = run()
     assert bool(torch.isfinite(img0).all())
     for case in cases:
