@@ -258,6 +258,10 @@ SIGNATURES = {
     "dk_mmdit_set_control_taps": (_i32, [_vp, _vp, _i32, _f32]),
     **{"dk_ln_modulate_add_" + el: (_i32, [_vp, _vp, _i32, _f32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
                                            _i32, _f32, _vp]) for el in ("bf16", "f16")},
+    # FLUX ControlNet: the control-net engine of FLUX geometry, the main engine's double- and single-block taps, the one-job joint LayerNorm pass
+    "dk_mmdit_set_flux_control_net": (_i32, [_vp, _i32]),
+    "dk_mmdit_set_flux_control_taps": (_i32, [_vp, _vp, _i32, _i32, _f32]),
+    "dk_ln_modulate_add_joint_bf16": (_i32, [_vp, _i32, _vp, _i32, _f32, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp]),
     "dk_image_mask_out_f32": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "dk_fill_condition_tokens": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "dk_vae_create": (_i32, [C.POINTER(dk_vae_config), C.POINTER(_vp)]),

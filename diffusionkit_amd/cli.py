@@ -117,8 +117,14 @@ def build_parser(model_versions: Sequence[str]) -> argparse.ArgumentParser:
                    help="With --pag-scale: step i of n takes the term iff n START < i < n STOP (default: every guided step).")
     p.add_argument("--controlnet", type=str, default=None, metavar="PATH",
                    help="An SD3 ControlNet in the layout of diffusers' SD3ControlNetModel (the InstantX SD3-medium Canny / Pose / Tile files; SD3 "
-                        "versions only, not Stable Diffusion 3.5 medium): a .safetensors file. Needs --controlnet-image-path. Not together with "
+                        "versions, not Stable Diffusion 3.5 medium) or, with a FLUX version and --controlnet-blocks, a FLUX ControlNet in the layout "
+                        "of diffusers' FluxControlNetModel: a .safetensors file. Needs --controlnet-image-path. Not together with "
                         "--block-cache, --slg-scale, --pag-scale or --fp8. Verified as arithmetic only: the key table has not been run against a real file.")
+    p.add_argument("--controlnet-blocks", type=int, nargs=2, default=None, metavar=("N_DOUBLE", "N_SINGLE"),
+                   help="With --controlnet and a FLUX model version: the ControlNet is a FLUX one in the layout of diffusers' FluxControlNetModel with this "
+                        "many double and single blocks (FLUX ControlNets have no canonical depth; e.g. 5 10). Not together with --fp8, --block-cache, "
+                        "--reference-image-path or --condition. Union-mode and XLabs files are refused. Verified as arithmetic only: the key table "
+                        "has not been run against a real file.")
     p.add_argument("--controlnet-image-path", type=str, default=None, metavar="IMG",
                    help="With --controlnet: the prepared control image (edges, pose, ...). Its sides must equal --height / --width: it is not resized.")
     p.add_argument("--controlnet-scale", type=float, default=None, metavar="S", help="With --controlnet: the scale of the ControlNet's residuals (default 1.0).")
@@ -239,16 +245,28 @@ def resolve(args) -> dict:
         opts = _perturbed_attention_options(*pag, mcfg, "FLUX" in args.model_version, cfg, r.get("block_cache"), r.get("reference_image_path"),
                                             r.get("condition"), r.get("skip_layer_guidance"))
         r.update(pag_scale=opts["scale"], pag_layers=opts["layers"], pag_interval=opts["interval"])
-    cn = {k: getattr(args, k, None) for k in ("controlnet", "controlnet_image_path", "controlnet_scale", "controlnet_interval")}
+    cn = {k: getattr(args, k, None) for k in ("controlnet", "controlnet_image_path", "controlnet_scale", "controlnet_interval", "controlnet_blocks")}
     if any(v is not None for v in cn.values()):  # (keys only when the flags are given)
         from .config import MODEL_CONFIG
         mcfg = r.get("mmdit_config", MODEL_CONFIG[args.model_version])
         if cn["controlnet"] is None:
-            raise ValueError("--controlnet-image-path / --controlnet-scale / --controlnet-interval need --controlnet")
+            raise ValueError("--controlnet-image-path / --controlnet-scale / --controlnet-interval / --controlnet-blocks need --controlnet")
         if cn["controlnet_image_path"] is None:
             raise ValueError("--controlnet needs --controlnet-image-path: the ControlNet was trained to see a control image")
+        blocks = getattr(args, "controlnet_blocks", None)
         if "FLUX" in args.model_version:
-            raise ValueError(f"--controlnet needs an SD3 model version (diffusers' SD3ControlNetModel), not {args.model_version}")
+            if blocks is None:
+                raise ValueError(f"--controlnet without --controlnet-blocks needs an SD3 model version (diffusers' SD3ControlNetModel), not "
+                                 f"{args.model_version}: a FLUX ControlNet (diffusers' FluxControlNetModel) names its depths, --controlnet-blocks N_DOUBLE N_SINGLE")
+            from dataclasses import replace
+            from .config import flux_controlnet_config
+            for key, flag in (("reference_image_path", "--reference-image-path"), ("condition", "--condition")):
+                if r.get(key) is not None:
+                    raise ValueError(f"--controlnet cannot run together with {flag}")
+            r["controlnet_config"] = flux_controlnet_config(int(blocks[0]), int(blocks[1]), replace(mcfg, weight_dtype="bfloat16", fp8_bf16_double_blocks=0))
+        elif blocks is not None:
+            raise ValueError(f"--controlnet-blocks is the FLUX family's (diffusers' FluxControlNetModel), not {args.model_version}'s: an SD3 ControlNet's "
+                             "depth is its preset's")
         if mcfg.dual_attention_blocks > 0:
             raise ValueError(f"--controlnet cannot run with {args.model_version}: its dual attention blocks have no tap form")
         if getattr(args, "fp8", None):
@@ -296,6 +314,8 @@ def main(argv: Optional[Sequence[str]] = None, pipeline_overrides: Optional[dict
         extra["condition"] = r["condition"]
     if "controlnet_ckpt" in r:
         extra["controlnet_ckpt"] = r["controlnet_ckpt"]
+    if "controlnet_config" in r:
+        extra["controlnet_config"] = r["controlnet_config"]
     cond_kw = {key: r[key] for key in ("condition_image_path", "condition_mask_path", *CONTROLNET_KEYS) if key in r}
     sd = pipeline_class(w16=True, shift=r["shift"], use_t5=args.t5, model_version=args.model_version,
                         low_memory_mode=r["low_memory_mode"], a16=True, local_ckpt=checkpoint_dict(args.local_ckpt, args.ckpt),

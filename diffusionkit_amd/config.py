@@ -66,6 +66,11 @@ class MMDiTConfig:
     # ``depth_multimodal`` joint blocks with their own embedders, a second patch embedder for the control image (pos_embed_input) and one
     # Linear(h, h) per block (controlnet_blocks), no final layer; SD3 family only (validate_control_net)
     control_net: bool = False
+    # FLUX ControlNet (the layout of diffusers' FluxControlNetModel; no reference counterpart): this configuration is the ControlNet --
+    # ``depth_multimodal`` double and ``depth_unified`` single blocks with their own embedders, a second patch embedder for the control image
+    # (controlnet_x_embedder), one Linear(h, h) per double block (controlnet_blocks) and per single block (controlnet_single_blocks), no final
+    # layer; FLUX family only (validate_control_net_flux).  ``control_net`` stays the SD3 family's field
+    control_net_flux: bool = False
 
     @property
     def hidden_size(self) -> int:
@@ -105,7 +110,7 @@ class MMDiTConfig:
             skip_txt = (i == self.depth_multimodal - 1) and self.depth_unified < 1
             n += (9 if i < self.dual_attention_blocks else 6) + (2 if skip_txt else 6)
         n += 3 * self.depth_unified
-        n += 0 if self.control_net else 2  # (a ControlNet has no final layer)
+        n += 0 if self.control_net or self.control_net_flux else 2  # (a ControlNet has no final layer)
         return n
 
 
@@ -169,6 +174,33 @@ FLUX_DEV = replace(FLUX_SCHNELL, guidance_embed=True)
 # condition latent's 64 patch features (Fill: + the 8 x 8-unshuffled mask's 256) concatenated to the latent's on the feature axis
 FLUX_FILL_DEV = replace(FLUX_DEV, condition_features=320)
 FLUX_CONTROL_DEV = replace(FLUX_DEV, condition_features=64)
+
+
+def validate_control_net_flux(cfg: MMDiTConfig) -> None:
+    """``control_net_flux`` needs FLUX geometry: RoPE and no learned positional table, at least one double block, bfloat16 activations, no fp8
+    Linears, no dual attention blocks, no condition width, and not ``control_net`` (the SD3 form) at the same time -- the rule
+    dk_mmdit_set_flux_control_net enforces."""
+    if not cfg.control_net_flux:
+        return
+    if cfg.control_net:
+        raise ValueError("control_net_flux and control_net cannot both be set: control_net is the SD3 family's ControlNet")
+    if (cfg.pos_embed_type != PositionalEncoding.PreSDPARope or cfg.depth_multimodal < 1 or cfg.depth_unified < 0
+            or cfg.weight_dtype == "fp8_e4m3" or cfg.activation_dtype != "bfloat16" or cfg.dual_attention_blocks != 0 or cfg.condition_features != 0):
+        raise ValueError("control_net_flux needs the FLUX family: RoPE without a learned positional table, at least one double block, bfloat16 "
+                         "activations, no fp8 Linears, no dual attention blocks and no condition width")
+
+
+def flux_controlnet_config(n_double: int, n_single: int, base: Optional[MMDiTConfig] = None) -> MMDiTConfig:
+    """The FLUX ControlNet with ``n_double`` double and ``n_single`` single blocks for a model like ``base`` (default FLUX_DEV): the model's
+    width, heads, RoPE axes and embedders (the guidance embedding of a guidance-distilled model included), its own depths.  FLUX ControlNets have
+    no canonical depth: the caller names it."""
+    base = FLUX_DEV if base is None else base
+    if n_double < 1 or n_single < 0:
+        raise ValueError(f"a FLUX ControlNet has n_double >= 1 and n_single >= 0 blocks, got ({n_double}, {n_single})")
+    out = replace(base, depth_multimodal=n_double, depth_unified=n_single, hidden_size_override=base.hidden_size, control_net_flux=True,
+                  condition_features=0, weight_dtype="bfloat16", fp8_bf16_double_blocks=0)
+    validate_control_net_flux(out)
+    return out
 
 
 def validate_condition_features(cfg: MMDiTConfig) -> None:
@@ -249,6 +281,14 @@ def tiny_flux(depth_multimodal: int = 2, depth_unified: int = 2, heads: int = 2,
         pooled_text_embed_dim=pooled,
         condition_features=condition_features,
     )
+
+
+def tiny_flux_controlnet(n_double: int = 2, n_single: int = 2, heads: int = 2, head_dim: int = 128, text_dim: int = 256, pooled: int = 64,
+                         guidance_embed: bool = False) -> MMDiTConfig:
+    """FLUX-ControlNet-shaped config for a ``tiny_flux`` model of the same ``heads`` and ``head_dim`` (the widths must agree: the taps are added
+    to its stream); ``n_single`` may be 0."""
+    base = replace(tiny_flux(1, 1, heads, head_dim, text_dim, pooled), guidance_embed=guidance_embed)
+    return flux_controlnet_config(n_double, n_single, base)
 
 
 def tiny_sd3(depth: int = 2, heads: int = 4, text_dim: int = 256, pooled: int = 64,

@@ -370,7 +370,16 @@ extern "C" int dk_ln_modulate_add_f16(void* x, const void* tap, int32_t ldt, flo
                          mod_stride, x_seg_stride, x_seg_stride1, eps, stream);
 }
 
-static int block_probe(int dtype, const void* x, int ldx, int x_seg_len, int x_seg_stride, void* d, const void* d_ref, float* row_partials,
+extern "C" int dk_ln_modulate_add_joint_bf16(void* x, int32_t ldx, const void* tap, int32_t ldt, float s, int32_t tap_seg, int32_t tap_first, void* out,
+                                             int32_t ldo, int32_t M, int32_t h, const void* shift, const void* scale, int32_t mod_stride,
+                                             int32_t mod_seg_len, int32_t x_seg_len, int32_t x_seg_stride, float eps, void* stream) {
+  DK_REQUIRE(M > 0 && h > 0, "bad argument");
+  return dk_launch_ln_modulate_add_joint((bf16_t*)x, ldx, (const bf16_t*)tap, ldt, s, tap_seg, tap_first, (bf16_t*)out, ldo, M, h, (const bf16_t*)shift,
+                                         (const bf16_t*)scale, mod_stride, mod_seg_len > 0 ? mod_seg_len : M, x_seg_len > 0 ? x_seg_len : M, x_seg_stride,
+                                         eps, S_(stream));
+}
+
+static int block_probe(int dtype,const void* x, int ldx, int x_seg_len, int x_seg_stride, void* d, const void* d_ref, float* row_partials,
                        float* probe, int M, int h, int rows_per_batch, void* stream) {
   return DK_EL(dtype, dk_launch_block_probe)((const bf16_t*)x, ldx, x_seg_len, x_seg_stride, (bf16_t*)d, (const bf16_t*)d_ref, row_partials, probe, M, h,
                                              rows_per_batch, S_(stream));

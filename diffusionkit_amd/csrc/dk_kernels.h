@@ -195,6 +195,12 @@ int dk_launch_ln_modulate_mx8(const bf16_t* x, int ldx, int M, int h, const bf16
 int dk_launch_ln_modulate2_mx8(const bf16_t* x0, int M0, const bf16_t* shift0, const bf16_t* scale0, int seg0, const Mx8Out& o0,
                                const bf16_t* x1, int M1, const bf16_t* shift1, const bf16_t* scale1, int seg1, const Mx8Out& o1, int ldx, int h,
                                int mod_stride, int x_seg_stride, float eps, hipStream_t stream);
+// dk_launch_ln_modulate over a joint stream with a residual in front of SOME rows (FLUX ControlNet taps; bf16 only, elementwise.hip): of every
+// tap_seg logical rows the first tap_first are plain, row s >= tap_first of group b becomes round(fmaf(s, tap[b * (tap_seg - tap_first) + s -
+// tap_first], x)) in place first; tap: dense [(M / tap_seg) * (tap_seg - tap_first), ldt]
+int dk_launch_ln_modulate_add_joint(bf16_t* x, int ldx, const bf16_t* tap, int ldt, float s, int tap_seg, int tap_first, bf16_t* out, int ldo, int M,
+                                    int h, const bf16_t* shift, const bf16_t* scale, int mod_stride, int seg_len, int x_seg_len, int x_seg_stride,
+                                    float eps, hipStream_t stream);
 
 // optional HIP-event timing of the dominant kernels (profile.hip); cls: 0 GEMM, 1 conv, 2 attention, 3 fp8 GEMM
 void dk_prof_begin(int cls, double work, hipStream_t st);

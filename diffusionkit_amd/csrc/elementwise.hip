@@ -38,10 +38,13 @@ static_assert(sizeof(LnJob2) % 8 == 0 && alignof(LnJob2) == 8, "job b follows jo
 // row's round trip, x' goes back over x through the row's own resource, and the two reductions and the modulated store run on x' from the
 // same registers.  A job without a tap (the text stream riding in the same launch) has t null: a tap resource of zero bytes, and the add
 // and the write-back are skipped on a wave-uniform test.  The plain and the DUAL instantiations do not see any of this.
+// The tap's row map (FLUX ControlNet taps, dk_mmdit_set_flux_control_taps): of every tseg logical rows the first t0 have no tap (the text rows of
+// a joint stream) and row s >= t0 of group b takes tap row b * (tseg - t0) + (s - t0).  A row without a tap is a job without one, decided per
+// wave: the zero-byte resource, no add, no write-back.  (tseg = M, t0 = 0: row m takes tap row m, the SD3 form.)
 struct LnJobT : LnJob {
   const bf16_t* t;
   float s;
-  int ldt;
+  int ldt, tseg, t0;
 };
 static_assert(sizeof(LnJobT) % 8 == 0 && alignof(LnJobT) == 8, "job b follows job a without padding in the kernarg segment");
 template <bool DUAL, bool ADD = false> struct LnJobOf { typedef LnJob type; };
@@ -75,9 +78,15 @@ __global__ __launch_bounds__(256) void dk_ln_modulate_kernel(typename LnJobOf<DU
   bool tapped = false;
   if constexpr (ADD) {
     tapped = j.t != nullptr;
-    // (a job without a tap: a resource of zero bytes at the row -- every lane reads zeros)
+    size_t trow = 0;
+    if (tapped) {  // (m is wave-uniform, and so is everything here: scalar arithmetic)
+      const int ts = m % j.tseg;
+      tapped = ts >= j.t0;
+      if (tapped) trow = (size_t)((m / j.tseg) * (j.tseg - j.t0) + (ts - j.t0)) * j.ldt;
+    }
+    // (a job or a row without a tap: a resource of zero bytes at the row -- every lane reads zeros, and no tap row is addressed)
     const __amdgpu_buffer_rsrc_t rtap =
-        __builtin_amdgcn_make_buffer_rsrc((void*)(tapped ? j.t + (size_t)m * j.ldt : j.x + xrow), 0, tapped ? h * 2 : 0, 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc((void*)(tapped ? j.t + trow : j.x + xrow), 0, tapped ? h * 2 : 0, 0x00020000);
 #pragma unroll
     for (int i = 0; i < NCH; ++i) rt[i] = __builtin_amdgcn_raw_buffer_load_b128(rtap, (lane + 64 * i) * 16, 0, 0);
   }
@@ -274,10 +283,12 @@ static int launch_ln_jobs_add(const LnJobT& a, const LnJobT& b, int h, float eps
   DK_CHECK_HIP(hipGetLastError());
   return 0;
 }
-static LnJobT ln_job_tap(const LnJob& j, const bf16_t* t, int ldt, float s) {
+// (tseg == 0: every row of the job, row m onto tap row m)
+static LnJobT ln_job_tap(const LnJob& j, const bf16_t* t, int ldt, float s, int tseg = 0, int t0 = 0) {
   LnJobT d;
   static_cast<LnJob&>(d) = j;
   d.t = t; d.s = t ? s : 0.f; d.ldt = t ? ldt : 8;
+  d.tseg = t && tseg > 0 ? tseg : (j.M > 0 ? j.M : 1); d.t0 = t && tseg > 0 ? t0 : 0;
   return d;
 }
 // ... of which the first takes a residual first (ControlNet taps): x0 <- round(x0 + s * tap) in place, row m of the dense [M0, ldt] tap onto
@@ -293,6 +304,23 @@ int dk_launch_ln_modulate2_add(bf16_t* x0, const bf16_t* tap, int ldt, float s, 
   return launch_ln_jobs_add(ln_job_tap(ln_job(x0, ldx, out0, ldo, M0, shift0, scale0, mod_stride, seg0, seg0, x_seg_stride), tap, ldt, s),
                             ln_job_tap(b, nullptr, 0, 0.f), h, eps, stream);
 }
+#ifndef DK_ELEM_F16  // (the FLUX family has no fp16 path)
+// ONE job over a joint stream, of which only some rows take the residual (FLUX ControlNet taps): of every tap_seg logical rows the first tap_first
+// (the text rows) are plain -- neither added to nor written back -- and row s >= tap_first of group b takes row b * (tap_seg - tap_first) +
+// (s - tap_first) of the dense [(M / tap_seg) * (tap_seg - tap_first), ldt] tap; no tap row exists for a text row and none is addressed.
+// tap_first == 0: every row (the final layer's image rows, x at the first image row with x_seg_len = tap_seg = S_i, x_seg_stride = S)
+int dk_launch_ln_modulate_add_joint(bf16_t* x, int ldx, const bf16_t* tap, int ldt, float s, int tap_seg, int tap_first, bf16_t* out, int ldo, int M,
+                                    int h, const bf16_t* shift, const bf16_t* scale, int mod_stride, int seg_len, int x_seg_len, int x_seg_stride,
+                                    float eps, hipStream_t stream) {
+  DK_REQUIRE(x && tap && out && shift && scale && M > 0 && seg_len > 0 && x_seg_len > 0, "ln_modulate_add_joint: null or empty argument");
+  DK_REQUIRE(ldt >= h && ldt % 8 == 0 && ((uintptr_t)tap & 15) == 0, "ln_modulate_add_joint: the tap's rows must be 16-byte aligned and hold h elements");
+  DK_REQUIRE(tap_seg > 0 && tap_first >= 0 && tap_first < tap_seg && M % tap_seg == 0,
+             "ln_modulate_add_joint: the rows are whole groups of tap_seg, of which the first tap_first (fewer than tap_seg) take no tap");
+  const LnJob none = ln_job(nullptr, 8, nullptr, 8, 0, nullptr, nullptr, 8, 1, 1, 0);
+  return launch_ln_jobs_add(ln_job_tap(ln_job(x, ldx, out, ldo, M, shift, scale, mod_stride, seg_len, x_seg_len, x_seg_stride), tap, ldt, s, tap_seg, tap_first),
+                            ln_job_tap(none, nullptr, 0, 0.f), h, eps, stream);
+}
+#endif
 // two row sets (image / text stream) of the same hidden size in one launch
 int dk_launch_ln_modulate2(const bf16_t* x0, bf16_t* out0, int M0, const bf16_t* shift0, const bf16_t* scale0, int seg0, const bf16_t* x1,
                            bf16_t* out1, int M1, const bf16_t* shift1, const bf16_t* scale1, int seg1, int ldx, int ldo, int h,

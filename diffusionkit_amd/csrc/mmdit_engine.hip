@@ -121,8 +121,27 @@ struct dk_mmdit {
   const bf16_t* taps = nullptr;  // [n_taps, B, S_i, h], the caller's
   int n_taps = 0;
   float tap_scale = 0.f;
-  bool tapped() const { return n_taps > 0; }
   int tap_of(int g) const { return (int)((long)g * n_taps / cfg.depth_multimodal); }
+  // FLUX ControlNet (the layout of diffusers' FluxControlNetModel).  control_flux (dk_mmdit_set_flux_control_net, with control_net): the ControlNet
+  // of FLUX geometry -- RoPE, single blocks, controlnet_x_embedder in the place of pos_embed_input, CONDE without positional rows, tap Linears
+  // tap_w / tap_b [0, depth_multimodal) behind the double and [depth_multimodal, +depth_unified) behind the single blocks.  n_dtaps / n_staps
+  // (dk_mmdit_set_flux_control_taps): the MAIN engine's taps [n_dtaps + n_staps, B, S_i, h], double taps first; tap g / ceil(depth / n) behind
+  // block g of each kind, the last block of a kind included
+  bool control_flux = false;
+  const bf16_t *cxe_w = nullptr, *cxe_b = nullptr;
+  int n_dtaps = 0, n_staps = 0;
+  bool flux_tapped() const { return n_dtaps + n_staps > 0; }
+  bool tapped() const { return n_taps > 0 || flux_tapped(); }
+  static int flux_tap_of(int g, int n, int depth) { return g / ((depth + n - 1) / n); }
+  // the tap added behind block g of the global order (in front of whatever reads the image rows next), or null
+  const bf16_t* tap_behind(int g) const {
+    const int nd = cfg.depth_multimodal;
+    const size_t tap = (size_t)B * S_i * cfg.hidden_size;
+    if (g < 0 || !tapped()) return nullptr;
+    if (n_taps > 0) return g < nd - 1 ? taps + (size_t)tap_of(g) * tap : nullptr;  // (SD3: nothing behind the last block)
+    if (g < nd) return n_dtaps > 0 ? taps + (size_t)flux_tap_of(g, n_dtaps, nd) * tap : nullptr;
+    return n_staps > 0 ? taps + (size_t)(n_dtaps + flux_tap_of(g - nd, n_staps, cfg.depth_unified)) * tap : nullptr;
+  }
   // what a call on `stream` hands its launches: this engine's element type and ITS regions (for D = 64 no attention region: unsplit launches)
   LaunchCtx ctx(void* stream) const { return LaunchCtx{S_(stream), dtype, GWS, AttnWs{AWS, AWS_bytes}}; }
   bool fp8() const { return cfg.fp8_linears != 0; }
@@ -338,13 +357,23 @@ static int mmdit_resolve(dk_mmdit* m) {
   DK_TRY(need(n, "final_layer.linear.weight", &m->final_w, m->control_net));
   DK_TRY(need(n, "final_layer.linear.bias", &m->final_b, m->control_net));
   if (m->control_net) {
-    DK_TRY(need(n, "pos_embed_input.proj.weight", &m->cin_w));
-    DK_TRY(need(n, "pos_embed_input.proj.bias", &m->cin_b));
-    m->tap_w.assign(m->cfg.depth_multimodal, nullptr);
-    m->tap_b.assign(m->cfg.depth_multimodal, nullptr);
-    for (int i = 0; i < m->cfg.depth_multimodal; ++i) {
+    if (m->control_flux) {
+      DK_TRY(need(n, "controlnet_x_embedder.proj.weight", &m->cxe_w));
+      DK_TRY(need(n, "controlnet_x_embedder.proj.bias", &m->cxe_b));
+    } else {
+      DK_TRY(need(n, "pos_embed_input.proj.weight", &m->cin_w));
+      DK_TRY(need(n, "pos_embed_input.proj.bias", &m->cin_b));
+    }
+    const int nd = m->cfg.depth_multimodal, ns = m->control_flux ? m->cfg.depth_unified : 0;
+    m->tap_w.assign(nd + ns, nullptr);
+    m->tap_b.assign(nd + ns, nullptr);
+    for (int i = 0; i < nd; ++i) {
       DK_TRY(need(n, "controlnet_blocks." + std::to_string(i) + ".weight", &m->tap_w[i]));
       DK_TRY(need(n, "controlnet_blocks." + std::to_string(i) + ".bias", &m->tap_b[i]));
+    }
+    for (int i = 0; i < ns; ++i) {
+      DK_TRY(need(n, "controlnet_single_blocks." + std::to_string(i) + ".weight", &m->tap_w[nd + i]));
+      DK_TRY(need(n, "controlnet_single_blocks." + std::to_string(i) + ".bias", &m->tap_b[nd + i]));
     }
   }
   if (m->cfg.guidance_embed) {
@@ -492,6 +521,7 @@ extern "C" int dk_mmdit_prepare(dk_mmdit* m, int32_t batch, int32_t latent_h, in
   m->cond_ready = false;
   m->ctrl_ready = false;
   m->taps = nullptr; m->n_taps = 0; m->tap_scale = 0.f;  // (the caller's taps had the previous problem's shape: set again after prepare)
+  m->n_dtaps = m->n_staps = 0;
   m->bc_reset();
   return 0;
 }
@@ -620,8 +650,14 @@ static int mmdit_final_layer(dk_mmdit* m, const bf16_t* mod_step, bf16_t* tokens
   const int h = m->h(), B = m->B, S = m->S, S_t = m->S_t, S_i = m->S_i, F = m->F();
   const int mod_stride = m->mod_rows() * h;
   const bf16_t* mod_fin = mod_step + (size_t)m->mod_offset(3, 0) * h;
-  DK_TRY(DK_EL(L.dtype, dk_launch_ln_modulate)(m->X + (size_t)S_t * h, h, m->XN, h, B * S_i, h, mod_fin, mod_fin + h, mod_stride, S_i, S_i, S,
-                               m->cfg.layer_norm_eps, st));
+  // (FLUX ControlNet taps: the residual behind the last block of the model lands here -- the image rows alone, every one of them tapped)
+  const bf16_t* tap = m->tap_behind(m->cfg.depth_multimodal + m->cfg.depth_unified - 1);
+  if (tap != nullptr)
+    DK_TRY(dk_launch_ln_modulate_add_joint(m->X + (size_t)S_t * h, h, tap, h, m->tap_scale, S_i, 0, m->XN, h, B * S_i, h, mod_fin, mod_fin + h, mod_stride,
+                                           S_i, S_i, S, m->cfg.layer_norm_eps, st));
+  else
+    DK_TRY(DK_EL(L.dtype, dk_launch_ln_modulate)(m->X + (size_t)S_t * h, h, m->XN, h, B * S_i, h, mod_fin, mod_fin + h, mod_stride, S_i, S_i, S,
+                                 m->cfg.layer_norm_eps, st));
   return dk_launch_gemm(Linear(L.dtype, dense(m->XN, h), m->final_w, m->final_b, dense(tokens_out, F), B * S_i, F, h, DK_EPI_BIAS), st);
 }
 
@@ -723,10 +759,10 @@ static int double_block_bf16(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t
   if (dual)
     DK_TRY(DK_EL(L.dtype, dk_launch_ln_modulate2x)(X_img.p, XN_img.p, m->XN2, Mi, mod_img, mod_img + h, mod_img + 6 * h, mod_img + 7 * h, S_i, X_txt.p,
                                                    XN_txt.p, Mt, mod_txt, mod_txt + h, S_t, h, h, h, mod_stride, S, S, cf.layer_norm_eps, st));
-  else if (m->tapped() && i > 0)
-    // ControlNet taps (dk_mmdit_set_control_taps): the residual behind block i - 1 is added here, in front of block i -- the same stream state --
-    // in the pass that reads every image row anyway; the image rows are rewritten in place, the text job is the plain one
-    DK_TRY(DK_EL(L.dtype, dk_launch_ln_modulate2_add)(X_img.p, m->taps + (size_t)m->tap_of(i - 1) * Mi * h, h, m->tap_scale, XN_img.p, Mi, mod_img,
+  else if (m->tap_behind(i - 1) != nullptr)
+    // ControlNet taps (dk_mmdit_set_control_taps / dk_mmdit_set_flux_control_taps): the residual behind block i - 1 is added here, in front of block
+    // i -- the same stream state -- in the pass that reads every image row anyway; the image rows are rewritten in place, the text job is the plain one
+    DK_TRY(DK_EL(L.dtype, dk_launch_ln_modulate2_add)(X_img.p, m->tap_behind(i - 1), h, m->tap_scale, XN_img.p, Mi, mod_img,
                                                       mod_img + h, S_i, X_txt.p, XN_txt.p, Mt, mod_txt, mod_txt + h, S_t, h, h, h, mod_stride, S, S,
                                                       cf.layer_norm_eps, st));
   else
@@ -819,7 +855,12 @@ static int single_block_bf16(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t
   const StreamW& w = m->single[i];
   const bf16_t* mod = block_mod(m, mod_step, 2, i);
   const Rows X = dense(m->X, h), CAT = dense(m->CAT, ldcat);
-  DK_TRY(DK_EL(L.dtype, dk_launch_ln_modulate)(m->X, h, m->XN, h, M, h, mod, mod + h, c.mod_stride, S, M, 0, cf.layer_norm_eps, st));
+  // FLUX ControlNet taps (dk_mmdit_set_flux_control_taps): the residual behind the block in front of this one -- single block i - 1, or the last
+  // double block -- is added to the image rows of the joint stream in this pass; the text rows take the plain path of the same kernel
+  if (const bf16_t* tap = m->tap_behind(cf.depth_multimodal + i - 1))
+    DK_TRY(dk_launch_ln_modulate_add_joint(m->X, h, tap, h, m->tap_scale, S, c.S_t, m->XN, h, M, h, mod, mod + h, c.mod_stride, S, M, 0, cf.layer_norm_eps, st));
+  else
+    DK_TRY(DK_EL(L.dtype, dk_launch_ln_modulate)(m->X, h, m->XN, h, M, h, mod, mod + h, c.mod_stride, S, M, 0, cf.layer_norm_eps, st));
   {  // linear1: [q|k|v] -> QKV, gelu(fc1) -> CAT[:, h:], one pass over the modulated activations
     Linear l1 = Linear(L.dtype, dense(m->XN, h), w.qkv_w, w.qkv_b, dense(m->QKV, 3 * h), M, (3 + r) * h, h, DK_EPI_BIAS).split_ws(L.kws);
     l1.n_split = 3 * h; l1.C2 = m->CAT + h; l1.ldc2 = ldcat; l1.epi2 = DK_EPI_BIAS_GELU;
@@ -990,12 +1031,13 @@ static int mmdit_embed(dk_mmdit* m, const void* tokens_in, const void* text, con
   // (no split workspace; the positional rows repeat per image: one segment of S_i rows, stride 0)
   // (with a condition width: the latent columns of the [h, F + cond_f] weight, and the condition's step-invariant share, CONDE, in the
   // residual slot the positional table leaves free -- one segment per batch row)
-  // (a control-net engine: CONDE = POS + pos_embed_input(control tokens) in the slot of POS -- x_embedder's own [h, F] weight, pitch F)
+  // (a control-net engine: CONDE = POS + pos_embed_input(control tokens) in the slot of POS -- x_embedder's own [h, F] weight, pitch F; of FLUX
+  // geometry: CONDE = controlnet_x_embedder(control tokens), in the slot that a model without a positional table leaves free)
   const bool cond = m->cond_f > 0;
   DK_REQUIRE(!m->control_net || m->ctrl_ready, "a control-net engine needs dk_mmdit_cache_control_image after dk_mmdit_prepare");
   const Rows res = cond || m->control_net ? Rows{m->CONDE, h, S_i, S_i} : Rows{c.use_pos_embed ? m->POS : nullptr, h, S_i, 0};
   DK_TRY(dk_launch_gemm(Linear(L.dtype, dense((const bf16_t*)tokens_in, F), m->xemb_w, m->xemb_b, m->own(m->X, h), B * S_i, h, F,
-                               cond || c.use_pos_embed ? DK_EPI_RES : DK_EPI_BIAS, cond ? F + m->cond_f : 0)
+                               cond || m->control_net || c.use_pos_embed ? DK_EPI_RES : DK_EPI_BIAS, cond ? F + m->cond_f : 0)
                             .gate_res(nullptr, 0, 0, res),
                         st));
   // the reference image's rows behind them: the step-invariant result of dk_mmdit_cache_reference
@@ -1073,6 +1115,25 @@ extern "C" int dk_mmdit_set_control_net(dk_mmdit* m, int32_t on) {
                "a control-net engine cannot have a block cache, skip layers, perturbed attention or control taps of its own");
   }
   m->control_net = on != 0;
+  m->control_flux = false;
+  m->ctrl_ready = false;
+  return 0;
+}
+// the ControlNet of FLUX geometry (diffusers' FluxControlNetModel): double and single blocks, RoPE, no positional table
+extern "C" int dk_mmdit_set_flux_control_net(dk_mmdit* m, int32_t on) {
+  DK_REQUIRE(m != nullptr, "null handle");
+  DK_REQUIRE(m->named.empty() && !m->prepared, "dk_mmdit_set_flux_control_net must precede the first dk_mmdit_bind");
+  if (on) {
+    DK_REQUIRE(m->cfg.use_rope != 0 && m->cfg.use_pos_embed == 0, "a FLUX control-net engine is the FLUX family's: use_rope != 0 and use_pos_embed == 0");
+    DK_REQUIRE(m->cfg.fp8_linears == 0, "a FLUX control-net engine cannot have fp8 Linears");
+    DK_REQUIRE(m->dtype == DK_DTYPE_BF16, "a FLUX control-net engine needs bf16 activations");
+    DK_REQUIRE(m->cfg.depth_multimodal >= 1 && m->cfg.depth_unified >= 0, "a FLUX control-net engine needs at least one double block");
+    DK_REQUIRE(m->n_dual == 0 && m->ref_h == 0 && m->ref_w == 0 && m->cond_f == 0,
+               "a control-net engine cannot have dual attention blocks, a reference grid or a condition width");
+    DK_REQUIRE(!m->bc_on && !m->slg() && !m->perturbed() && !m->tapped(),
+               "a control-net engine cannot have a block cache, skip layers, perturbed attention or control taps of its own");
+  }
+  m->control_net = m->control_flux = on != 0;
   m->ctrl_ready = false;
   return 0;
 }
@@ -1082,11 +1143,15 @@ extern "C" int dk_mmdit_cache_control_image(dk_mmdit* m, const void* ctrl_tokens
   const int h = m->h(), F = m->F(), S_i = m->S_i;
   // pos_embed_input as x_embedder in mmdit_embed (no split workspace) with the positional rows as residual, one launch per batch row: a shared
   // control image gives every batch row the bits a per-image copy of it would
+  // (FLUX geometry: CONDE[b] = controlnet_x_embedder(ctrl_tokens[b]) -- there is no positional table, so no residual operand)
   for (int b = 0; b < m->B; ++b) {
     const bf16_t* src = (const bf16_t*)ctrl_tokens + (per_image ? (size_t)b * S_i * F : 0);
-    DK_TRY(dk_launch_gemm(Linear(m->dtype, dense(src, F), m->cin_w, m->cin_b, dense(m->CONDE + (size_t)b * S_i * h, h), S_i, h, F, DK_EPI_RES)
-                              .gate_res(nullptr, 0, 0, Rows{m->POS, h, S_i, 0}),
-                          S_(stream)));
+    const Rows out = dense(m->CONDE + (size_t)b * S_i * h, h);
+    if (m->control_flux)
+      DK_TRY(dk_launch_gemm(Linear(m->dtype, dense(src, F), m->cxe_w, m->cxe_b, out, S_i, h, F, DK_EPI_BIAS), S_(stream)));
+    else
+      DK_TRY(dk_launch_gemm(Linear(m->dtype, dense(src, F), m->cin_w, m->cin_b, out, S_i, h, F, DK_EPI_RES).gate_res(nullptr, 0, 0, Rows{m->POS, h, S_i, 0}),
+                            S_(stream)));
   }
   m->ctrl_ready = true;
   return 0;
@@ -1094,7 +1159,7 @@ extern "C" int dk_mmdit_cache_control_image(dk_mmdit* m, const void* ctrl_tokens
 extern "C" int dk_mmdit_set_control_taps(dk_mmdit* m, const void* taps, int32_t n_taps, float scale) {
   DK_REQUIRE(m != nullptr, "null handle");
   if (taps == nullptr || n_taps == 0) {
-    m->taps = nullptr; m->n_taps = 0; m->tap_scale = 0.f;
+    m->taps = nullptr; m->n_taps = m->n_dtaps = m->n_staps = 0; m->tap_scale = 0.f;  // (off: taps of either kind)
     return 0;
   }
   DK_REQUIRE(sd3_geometry(m), "control taps are the SD3 family's: use_pos_embed != 0, depth_unified == 0 and fp8_linears == 0");
@@ -1113,10 +1178,46 @@ extern "C" int dk_mmdit_set_control_taps(dk_mmdit* m, const void* taps, int32_t 
   m->taps = (const bf16_t*)taps; m->n_taps = n_taps; m->tap_scale = scale;
   return 0;
 }
+// FLUX taps on the MAIN engine: taps [n_double_taps + n_single_taps, B, S_i, h], the double blocks' first
+extern "C" int dk_mmdit_set_flux_control_taps(dk_mmdit* m, const void* taps, int32_t n_double_taps, int32_t n_single_taps, float scale) {
+  DK_REQUIRE(m != nullptr, "null handle");
+  if (taps == nullptr || (n_double_taps == 0 && n_single_taps == 0)) {
+    m->taps = nullptr; m->n_taps = m->n_dtaps = m->n_staps = 0; m->tap_scale = 0.f;  // (off: taps of either kind)
+    return 0;
+  }
+  const int nd = m->cfg.depth_multimodal, ns = m->cfg.depth_unified;
+  DK_REQUIRE(m->cfg.use_rope != 0 && m->cfg.use_pos_embed == 0, "FLUX control taps are the FLUX family's: use_rope != 0 and use_pos_embed == 0");
+  DK_REQUIRE(m->cfg.fp8_linears == 0, "FLUX control taps cannot be set on an engine with fp8 Linears: the fp8 LayerNorm kernels take no tap");
+  DK_REQUIRE(m->dtype == DK_DTYPE_BF16, "FLUX control taps need bf16 activations");
+  DK_REQUIRE(!m->control_net, "control taps cannot be set on a control-net engine: it writes taps, the main engine reads them");
+  DK_REQUIRE(m->n_taps == 0, "FLUX control taps cannot be set while SD3 control taps are set (dk_mmdit_set_control_taps)");
+  DK_REQUIRE(n_double_taps >= 0 && n_double_taps <= nd, "FLUX control taps: n_double_taps must lie in [0, depth_multimodal]");
+  DK_REQUIRE(n_single_taps >= 0 && n_single_taps <= ns, "FLUX control taps: n_single_taps must lie in [0, depth_unified]");
+  DK_REQUIRE(((uintptr_t)taps & 15) == 0, "control taps must be 16-byte aligned");
+  DK_REQUIRE(m->n_dual == 0, "control taps cannot be set on an engine with dual attention blocks");
+  DK_REQUIRE(!m->bc_on, "FLUX control taps cannot be set while the block cache is on (dk_mmdit_set_block_cache)");
+  DK_REQUIRE(!m->slg() && !m->perturbed(), "control taps cannot be set while skip layers or perturbed attention are set: the fork rows would need taps of their own");
+  DK_REQUIRE(m->ref_h == 0 && m->ref_w == 0, "FLUX control taps cannot be set while a reference grid is set");
+  DK_REQUIRE(m->cond_f == 0, "FLUX control taps cannot be set while a condition width is set");
+  // diffusers' rule in integers: g / ceil(depth / n) must be int(g // np.ceil(depth / n)) in double for every block of the kind
+  for (int kind = 0; kind < 2; ++kind) {
+    const int depth = kind == 0 ? nd : ns, n = kind == 0 ? n_double_taps : n_single_taps;
+    if (n == 0) continue;
+    const double interval = std::ceil((double)depth / (double)n);
+    for (int g = 0; g < depth; ++g) {
+      const int idx = dk_mmdit::flux_tap_of(g, n, depth);
+      DK_REQUIRE(idx == (int)std::floor((double)g / interval) && idx >= 0 && idx < n,
+                 "FLUX control taps: the integer tap index disagrees with int(g // ceil(depth / n))");
+    }
+  }
+  m->taps = (const bf16_t*)taps; m->n_dtaps = n_double_taps; m->n_staps = n_single_taps; m->tap_scale = scale;
+  return 0;
+}
 // what the entries other than dk_mmdit_forward answer while taps are set, and the forward entries on a control-net engine
 static int no_control_taps(const dk_mmdit* m, const char* entry) {
   if (!m->tapped()) return 0;
-  dk_set_error(std::string(entry) + " cannot run while control taps are set (dk_mmdit_set_control_taps): only dk_mmdit_forward adds them");
+  dk_set_error(std::string(entry) + " cannot run while control taps are set (" + (m->flux_tapped() ? "dk_mmdit_set_flux_control_taps" : "dk_mmdit_set_control_taps") +
+               "): only dk_mmdit_forward adds them");
   return -1;
 }
 static int no_control_net(const dk_mmdit* m, const char* entry) {
@@ -1133,7 +1234,9 @@ extern "C" int dk_mmdit_control_forward(dk_mmdit* m, const void* tokens_in, cons
   const int h = m->h(), Mi = m->B * m->S_i;
   const bf16_t* mod_step = m->MOD + (size_t)step_index * m->B * m->mod_rows() * h;
   DK_TRY(mmdit_embed(m, tokens_in, text, L, 0));
-  for (int j = 0; j < m->cfg.depth_multimodal; ++j) {
+  // (FLUX geometry: the single blocks follow in the global order, and behind single block j - depth_multimodal the tap Linear reads the image
+  // rows of the joint stream -- the same segmented rows)
+  for (int j = 0; j < (int)m->tap_w.size(); ++j) {
     DK_TRY(mmdit_blocks(m, mod_step, j, 1, L));
     // taps_out[j] = controlnet_blocks.j(image rows): the segmented rows of the stream in, dense [B S_i, h] out
     DK_TRY(dk_launch_gemm(Linear(L.dtype, m->own(m->X, h), m->tap_w[j], m->tap_b[j], dense((bf16_t*)taps_out + (size_t)j * Mi * h, h), Mi, h, h, DK_EPI_BIAS)

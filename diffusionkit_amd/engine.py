@@ -121,8 +121,27 @@ class MMDiTEngine:
                 if t is None or tuple(t.shape) != (config.hidden_size, cols):
                     raise _lib.DkHipError(f"{name}: a control-net engine needs a [{config.hidden_size}, {cols}] tensor, got "
                                           f"{None if t is None else tuple(t.shape)}")
+        # FLUX ControlNet: the same on FLUX geometry, with tap Linears behind the double and behind the single blocks
+        from .config import validate_control_net_flux
+        try:
+            validate_control_net_flux(config)
+        except ValueError as e:
+            raise _lib.DkHipError(str(e)) from None
+        self.control_net_flux = bool(config.control_net_flux)
+        if self.control_net_flux:
+            _lib.check(self.lib.dk_mmdit_set_flux_control_net(self._h, 1), "dk_mmdit_set_flux_control_net")
+            names = ([("controlnet_x_embedder.proj.weight", config.patch_dim)]
+                     + [(f"controlnet_blocks.{i}.weight", config.hidden_size) for i in range(config.depth_multimodal)]
+                     + [(f"controlnet_single_blocks.{i}.weight", config.hidden_size) for i in range(config.depth_unified)])
+            for name, cols in names:
+                t = packed_weights.get(name)  # (dk_mmdit_bind sees bare pointers: the shapes are checked here)
+                if t is None or tuple(t.shape) != (config.hidden_size, cols):
+                    raise _lib.DkHipError(f"{name}: a FLUX control-net engine needs a [{config.hidden_size}, {cols}] tensor, got "
+                                          f"{None if t is None else tuple(t.shape)}")
+            self.control_net = True  # (what cache_control_image / control_forward ask)
         self._ctrl_cached = False
-        self.control_taps = None  # ``set_control_taps``: (taps tensor, scale), kept alive while the engine reads it; None: off
+        # ``set_control_taps`` / ``set_flux_control_taps``: (taps tensor, scale), kept alive while the engine reads it; None: off
+        self.control_taps = None
         self.weights = packed_weights  # keep the device tensors alive
         for name, t in packed_weights.items():
             want = torch.uint8 if name.endswith(".weight_fp8") else torch.float32 if name.endswith(".wscale") else self.dtype
@@ -296,7 +315,8 @@ class MMDiTEngine:
     def taps_shape(self):
         """[N_c, batch, S_i, h]: what ``control_forward`` of this (control-net) engine writes."""
         b, s_i, _ = self.tokens_shape()
-        return (self.config.depth_multimodal, b, s_i, self.config.hidden_size)
+        n = self.config.depth_multimodal + (self.config.depth_unified if self.control_net_flux else 0)  # (FLUX: the double blocks' taps first)
+        return (n, b, s_i, self.config.hidden_size)
 
     def cache_control_image(self, latent_or_tokens: Tensor, per_image: bool = False) -> None:
         """dk_mmdit_cache_control_image: the VAE-encoded control image, f32 NHWC latent [n, Hl, Wl, C] of the prepared size or its tokens in the
@@ -349,6 +369,29 @@ class MMDiTEngine:
         if taps.dim() != 4 or tuple(taps.shape[1:]) != (b, s_i, self.config.hidden_size):
             raise _lib.DkHipError(f"taps shape {tuple(taps.shape)} != (n, {b}, {s_i}, {self.config.hidden_size})")
         _lib.check(self.lib.dk_mmdit_set_control_taps(self._h, taps.data_ptr(), int(taps.shape[0]), float(scale)), "dk_mmdit_set_control_taps")
+        self.control_taps = (taps, float(scale))
+
+    def set_flux_control_taps(self, taps: Optional[Tensor] = None, n_double_taps: int = 0, scale: float = 1.0) -> None:
+        """dk_mmdit_set_flux_control_taps on the MAIN engine (FLUX family, bf16): ``taps`` [n_double_taps + n_single_taps, batch, S_i, h], the
+        double blocks' taps first -- what a FLUX control-net engine's ``control_forward`` writes, with ``n_double_taps`` its ``depth_multimodal``.
+        Every later ``forward_tokens`` adds ``scale * tap[g // ceil(depth / n)]`` (per kind; diffusers' FluxTransformer2DModel rule) to the image
+        rows behind block g, the last block of each kind included, inside the LayerNorm launch that reads those rows next.  None: off.  Nothing
+        is re-prepared.  ``forward_head`` / ``forward_tail`` / ``run_blocks`` are refused while set."""
+        if taps is None:
+            _lib.check(self.lib.dk_mmdit_set_flux_control_taps(self._h, None, 0, 0, 0.0), "dk_mmdit_set_flux_control_taps")
+            self.control_taps = None
+            return
+        if self._shape is None:
+            raise _lib.DkHipError("set_flux_control_taps() needs prepare() first: the taps' shape is the prepared problem's")
+        _require_cuda(taps, "taps", self.dtype)
+        b, s_i, _ = self.tokens_shape()
+        if taps.dim() != 4 or tuple(taps.shape[1:]) != (b, s_i, self.config.hidden_size):
+            raise _lib.DkHipError(f"taps shape {tuple(taps.shape)} != (n, {b}, {s_i}, {self.config.hidden_size})")
+        n_double_taps = int(n_double_taps)
+        if not 0 <= n_double_taps <= taps.shape[0]:
+            raise _lib.DkHipError(f"n_double_taps = {n_double_taps}: must lie in [0, {taps.shape[0]}], the number of taps")
+        _lib.check(self.lib.dk_mmdit_set_flux_control_taps(self._h, taps.data_ptr(), n_double_taps, int(taps.shape[0]) - n_double_taps, float(scale)),
+                   "dk_mmdit_set_flux_control_taps")
         self.control_taps = (taps, float(scale))
 
     def forward_tokens(self, tokens_in: Tensor, text: Optional[Tensor], step_index: int, tokens_out: Optional[Tensor] = None) -> Tensor:

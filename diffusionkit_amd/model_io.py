@@ -286,12 +286,122 @@ def sd3_controlnet_checkpoint_to_reference(sd: StateDict, cfg: MMDiTConfig) -> S
     return out
 
 
+_FCN_TOP = {"context_embedder": "context_embedder",
+            "time_text_embed.timestep_embedder.linear_1": "t_embedder.mlp.layers.0", "time_text_embed.timestep_embedder.linear_2": "t_embedder.mlp.layers.2",
+            "time_text_embed.text_embedder.linear_1": "y_embedder.mlp.layers.0", "time_text_embed.text_embedder.linear_2": "y_embedder.mlp.layers.2"}
+_FCN_GUIDANCE = {"time_text_embed.guidance_embedder.linear_1": "guidance_in.mlp.layers.0", "time_text_embed.guidance_embedder.linear_2": "guidance_in.mlp.layers.2"}
+_FCN_NORMS = {"attn.norm_q": ("image", "q"), "attn.norm_k": ("image", "k"), "attn.norm_added_q": ("text", "q"), "attn.norm_added_k": ("text", "k")}
+_FCN_SINGLE = {"attn.to_q": "attn.q_proj", "attn.to_k": "attn.k_proj", "attn.to_v": "attn.v_proj", "proj_mlp": "mlp.fc1",
+               "norm.linear": "adaLN_modulation.layers.1"}
+
+
+def flux_controlnet_checkpoint_to_reference(sd: StateDict, cfg: MMDiTConfig) -> StateDict:
+    """The layout of diffusers' ``FluxControlNetModel`` (the InstantX FLUX.1-dev Canny file, the Shakker-Labs files) -> the names of
+    ``weights.synth_mmdit_weights`` for a FLUX control-net configuration (``control_net_flux``).  Written from the published model definition,
+    NOT verified against a real file: no checkpoint and no diffusers installation exist where this was developed.
+      x_embedder / controlnet_x_embedder (Linear p*p*C -> h) -> x_embedder.proj / controlnet_x_embedder.proj as 1x1 convs;  context_embedder;
+      time_text_embed.{timestep,text,guidance}_embedder.linear_{1,2} -> t_embedder / y_embedder / guidance_in (the last only, and necessarily,
+      with ``guidance_embed``);
+      transformer_blocks.i: norm1.linear / norm1_context.linear -> the adaLN Linears (6h rows: shift, scale, gate of attention, then of the MLP
+      -- the engine's row order);  attn.{to_q,to_k,to_v,to_out.0} / attn.{add_q_proj,add_k_proj,add_v_proj,to_add_out} -> the image / text q, k,
+      v, o projections (the k bias is dropped: softmax is invariant to it);  attn.norm_{q,k} / attn.norm_added_{q,k} -> the QKNorm weights;
+      ff / ff_context .net.{0.proj,2} -> mlp.fc1 / fc2;
+      single_transformer_blocks.i: norm.linear -> its adaLN Linear (3h rows: shift, scale, gate);  attn.{to_q,to_k,to_v}, attn.norm_{q,k};
+      proj_mlp -> mlp.fc1;  proj_out [h, h + r h] over [attention | gelu(proj_mlp)] -> attn.o_proj | mlp.fc2 along the input axis, its bias
+      o_proj's (as the BFL loader splits linear2);
+      controlnet_blocks.i / controlnet_single_blocks.i -> the tap Linears.
+    With no single blocks the last double block's text stream ends after attention (nothing reads its result): its to_add_out and ff_context
+    are dropped and its norm1_context keeps the first 2h rows.
+    Refused: a missing or mis-shaped tensor, an unknown key, block counts other than the configuration's, controlnet_mode_embedder (the Union
+    models' extra text token) and input_hint_block (the XLabs layout), each by name."""
+    if not getattr(cfg, "control_net_flux", False):
+        raise CheckpointError("flux_controlnet_checkpoint_to_reference needs a FLUX control-net configuration (control_net_flux=True)")
+    h, r, nd, ns = cfg.hidden_size, cfg.mlp_ratio, cfg.depth_multimodal, cfg.depth_unified
+    for k in sd:
+        if k.startswith("controlnet_mode_embedder"):
+            raise CheckpointError(f"{k}: controlnet_mode_embedder (a Union ControlNet: the control mode rides in as an extra text token) is not built")
+        if k.startswith("input_hint_block"):
+            raise CheckpointError(f"{k}: input_hint_block (the XLabs ControlNet layout: a conv stack over the control image's pixels) is not built")
+
+    def count(prefix):
+        return len({k.split(".")[1] for k in sd if k.startswith(prefix + ".")})
+
+    have = (count("transformer_blocks"), count("single_transformer_blocks"), count("controlnet_blocks"), count("controlnet_single_blocks"))
+    if have != (nd, ns, nd, ns):
+        raise CheckpointError(f"the ControlNet checkpoint holds {have[0]} double and {have[1]} single blocks with {have[2]} controlnet_blocks and "
+                              f"{have[3]} controlnet_single_blocks, the configuration ({nd}, {ns}) of each")
+    out: StateDict = {}
+    for k0, t in sd.items():
+        m = re.fullmatch(r"(.+)\.(weight|bias)", k0)
+        if not m:
+            raise CheckpointError(f"unknown FLUX ControlNet checkpoint key: {k0}")
+        stem, leaf = m.group(1), m.group(2)
+        if stem in ("x_embedder", "controlnet_x_embedder"):
+            if leaf == "weight":
+                if t.dim() != 2 or t.shape[1] != cfg.patch_dim:
+                    raise CheckpointError(f"{k0}: shape {tuple(t.shape)}: [{h}, {cfg.patch_dim}] expected")
+                t = t.reshape(t.shape[0], 1, 1, t.shape[1])
+            out[f"{stem}.proj.{leaf}"] = t
+        elif stem in _FCN_TOP:
+            out[f"{_FCN_TOP[stem]}.{leaf}"] = t
+        elif stem in _FCN_GUIDANCE:
+            if not cfg.guidance_embed:
+                raise CheckpointError(f"{k0}: the checkpoint has a guidance embedder, the configuration has guidance_embed = False")
+            out[f"{_FCN_GUIDANCE[stem]}.{leaf}"] = t
+        elif (m2 := re.fullmatch(r"(controlnet_blocks|controlnet_single_blocks)\.(\d+)", stem)):
+            out[f"{m2.group(1)}.{m2.group(2)}.{leaf}"] = t
+        elif (m2 := re.fullmatch(r"transformer_blocks\.(\d+)\.(.+)", stem)) and (m2.group(2) in _CN_BLOCK or m2.group(2) in _FCN_NORMS):
+            i, part = int(m2.group(1)), m2.group(2)
+            if part in _FCN_NORMS:
+                stream, n = _FCN_NORMS[part]
+                if leaf != "weight":
+                    raise CheckpointError(f"unknown FLUX ControlNet checkpoint key: {k0}")
+                out[f"multimodal_transformer_blocks.{i}.{stream}_transformer_block.qk_norm.{n}_norm.weight"] = t
+                continue
+            stream, part = _CN_BLOCK[part]
+            if part == "attn.k_proj" and leaf == "bias":
+                continue  # (softmax is invariant to it: the reference's model has no k bias, quirk Q9)
+            last_txt = stream == "text" and i == nd - 1 and ns == 0
+            if last_txt and part in ("attn.o_proj", "mlp.fc1", "mlp.fc2"):
+                continue  # (the last text stream's post-attention half: nothing reads its result)
+            if last_txt and part == "adaLN_modulation.layers.1":
+                if t.shape[0] != 6 * h:
+                    raise CheckpointError(f"{k0}: shape {tuple(t.shape)}: {6 * h} rows expected")
+                t = t[:2 * h]
+            out[f"multimodal_transformer_blocks.{i}.{stream}_transformer_block.{part}.{leaf}"] = t
+        elif (m2 := re.fullmatch(r"single_transformer_blocks\.(\d+)\.(.+)", stem)):
+            base, part = f"unified_transformer_blocks.{m2.group(1)}.transformer_block", m2.group(2)
+            if part in _FCN_SINGLE:
+                if part == "attn.to_k" and leaf == "bias":
+                    continue
+                out[f"{base}.{_FCN_SINGLE[part]}.{leaf}"] = t
+            elif part in ("attn.norm_q", "attn.norm_k") and leaf == "weight":
+                out[f"{base}.qk_norm.{part[-1]}_norm.weight"] = t
+            elif part == "proj_out":
+                if leaf == "weight":
+                    if tuple(t.shape) != (h, (1 + r) * h):
+                        raise CheckpointError(f"{k0}: shape {tuple(t.shape)}: [{h}, {(1 + r) * h}] expected")
+                    o, fc2 = torch.split(t, [h, r * h], dim=1)
+                    out[f"{base}.attn.o_proj.weight"], out[f"{base}.mlp.fc2.weight"] = o.contiguous(), fc2.contiguous()
+                else:
+                    out[f"{base}.attn.o_proj.bias"] = t  # (one bias: the fc2 copy is zeroed at run time, quirk Q8)
+            else:
+                raise CheckpointError(f"unknown FLUX ControlNet checkpoint key: {k0}")
+        else:
+            raise CheckpointError(f"unknown FLUX ControlNet checkpoint key: {k0}")
+    _check_mmdit_complete(out, cfg)
+    return out
+
+
 def load_controlnet_checkpoint(src, cfg: MMDiTConfig) -> StateDict:
-    """``src``: a dict already in reference names, a state dict in the diffusers SD3ControlNetModel layout, or a .safetensors path of one."""
+    """``src``: a dict already in reference names, a state dict in the diffusers SD3ControlNetModel layout (FluxControlNetModel's for a
+    ``control_net_flux`` configuration), or a .safetensors path of one."""
     sd = load_safetensors(src) if isinstance(src, str) else dict(src)
     if any(k.startswith("multimodal_transformer_blocks.") for k in sd):
         _check_mmdit_complete(sd, cfg)
         return sd
+    if getattr(cfg, "control_net_flux", False):
+        return flux_controlnet_checkpoint_to_reference(sd, cfg)
     return sd3_controlnet_checkpoint_to_reference(sd, cfg)
 
 

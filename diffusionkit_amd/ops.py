@@ -453,6 +453,33 @@ def ln_modulate_add(x: Tensor, tap: Tensor, s: float, shift: Tensor, scale: Tens
     return (x, out) if x1 is None else (x, out, out1)
 
 
+def ln_modulate_add_joint(x: Tensor, s_t: int, tap: Tensor, s: float, shift: Tensor, scale: Tensor, eps: float = 1e-6):
+    """The LayerNorm pass of a joint stream with a residual tap in front of its image rows (dk_ln_modulate_add_joint_bf16: a single block's
+    LayerNorm behind a FLUX ControlNet tap; the final layer's with ``s_t`` = 0).  x: [B, S, h] bf16 contiguous, the first ``s_t`` rows of every
+    batch row text; tap: [B, S - s_t, h] contiguous -- there are no tap rows for the text rows.  Image rows: x <- round(fmaf(s, tap, x)) IN
+    PLACE (fp32, one rounding); text rows: untouched.  out = ``ln_modulate`` of the rows as they then are.  shift / scale: [B, h] views of one
+    modulation table.  Returns (x, out)."""
+    lib = _lib.load()
+    name = "dk_ln_modulate_add_joint_bf16"
+    _require_cuda(x, "x", BF)
+    if x.dim() != 3 or not x.is_contiguous():
+        raise _lib.DkHipError("x must be a contiguous [B, S, h] tensor")
+    B, S, h = x.shape
+    s_t = int(s_t)
+    if not 0 <= s_t < S:
+        raise _lib.DkHipError(f"s_t = {s_t}: must lie in [0, S = {S})")
+    _require_cuda(tap, "tap", BF)
+    if tuple(tap.shape) != (B, S - s_t, h) or not tap.is_contiguous():
+        raise _lib.DkHipError(f"tap must be a contiguous {(B, S - s_t, h)} tensor, got {tuple(tap.shape)}")
+    for n, t in (("shift", shift), ("scale", scale)):
+        if t.dtype != x.dtype or t.stride(0) != shift.stride(0) or tuple(t.shape) != (B, h) or t.stride(1) != 1:
+            raise _lib.DkHipError(f"{n} must be a [{B}, {h}] {x.dtype} view with the row stride of shift")
+    out = torch.empty(B, S, h, dtype=x.dtype, device=x.device)
+    _lib.check(getattr(lib, name)(x.data_ptr(), h, tap.data_ptr(), h, float(s), S, s_t, out.data_ptr(), h, B * S, h, shift.data_ptr(), scale.data_ptr(),
+                                  shift.stride(0), S, B * S, 0, eps, _stream()), name)
+    return x, out
+
+
 def block_probe(x: Tensor, s_t: int, d: Tensor, d_ref: Optional[Tensor] = None):
     """First-block-cache probe (dk_block_probe_*).  x: the joint stream [B, S, h] behind block 0 (text rows first, ``s_t`` of them per
     batch row; only the image rows are read); d: [B, S - s_t, h], X0's image rows on entry, D_cur = round(x - d) on return; d_ref: the

@@ -301,8 +301,11 @@ class DiffusionPipeline:
         """``controlnet_ckpt`` (SD3 family only): an SD3 ControlNet in the layout of diffusers' SD3ControlNetModel -- a .safetensors path or a state
         dict in that layout, or a dict of reference-named tensors (``weights.synth_mmdit_weights`` of a control-net config) -- built into a second
         ``MMDiTEngine``, ``self.controlnet``; ``controlnet_config``: its configuration (default ``config.SD3_CONTROLNET_6``, in the model's element
-        type).  Every call must then name its ``controlnet_image_path`` (see ``denoise_latents``).  Refused on FLUX, on a model with dual attention
-        blocks (SD3.5-medium) and on an fp8 engine.  Arithmetic parity on synthetic weights only: no ControlNet checkpoint has been run.
+        type).  Every call must then name its ``controlnet_image_path`` (see ``denoise_latents``).  Refused on a model with dual attention
+        blocks (SD3.5-medium) and on an fp8 engine.  On a ``FluxPipeline`` the ControlNet is a FLUX one in the layout of diffusers'
+        FluxControlNetModel (double- and single-block taps) and ``controlnet_config`` is REQUIRED -- ``config.flux_controlnet_config(n_double,
+        n_single)``: FLUX ControlNets have no canonical depth; refused there together with ``condition`` and an fp8 engine, and at the call with a
+        reference image or ``block_cache``.  Arithmetic parity on synthetic weights only: no ControlNet checkpoint has been run.
         ``condition`` (FluxPipeline only): None, "fill" (FLUX.1 Fill) or "control" (FLUX.1 Canny / Depth) -- channel-concatenated conditioning: the
         model's x_embedder is 64 + 320 / 64 + 64 columns wide (``config.FLUX_FILL_DEV`` / ``FLUX_CONTROL_DEV``; a ``mmdit_config`` of the caller's
         gets that width), and every call must name its ``condition_image_path`` (see ``denoise_latents``).
@@ -378,7 +381,9 @@ class DiffusionPipeline:
         from .config import SD3_CONTROLNET_6, validate_control_net
         cfg = self.mmdit_config
         if self._IS_FLUX or cfg.depth_unified > 0:
-            raise ValueError("controlnet_ckpt is the SD3 family's (diffusers' SD3ControlNetModel): FLUX ControlNets have single-block taps and are not built")
+            return _check_flux_controlnet_config(self, controlnet_config)
+        if controlnet_config is not None and getattr(controlnet_config, "control_net_flux", False):
+            raise ValueError("controlnet_config is a FLUX ControlNet's (control_net_flux=True): an SD3 pipeline takes an SD3 ControlNet (control_net=True)")
         if cfg.dual_attention_blocks > 0:
             raise ValueError("controlnet_ckpt cannot be combined with dual attention blocks (SD3.5-medium): the engine adds taps in a plain block's "
                              "LayerNorm launch only")
@@ -642,7 +647,8 @@ class DiffusionPipeline:
         n_seeds = len(seed) if isinstance(seed, (list, tuple)) else 1
         control = _controlnet_options(self, controlnet_image_path, controlnet_scale, controlnet_interval, n_seeds,
                                       (latent_size[0] * 8, latent_size[1] * 8) if image_path is None else read_image_u8(image_path).shape[:2],
-                                      block_cache, slg, pag)  # (raises before any GPU work)
+                                      block_cache, slg, pag, reference_image_path,
+                                      getattr(self, "condition", None) or condition_image_path)  # (raises before any GPU work)
         sampler = check_sampler(sampler)
         eta = check_sampler_eta(sampler, sampler_eta)
         if sampler == "heun" and block_cache is not None:
@@ -689,6 +695,8 @@ class DiffusionPipeline:
             extra_args["perturbed_attention_guidance"] = pag
         if control is not None:
             z = self.latent_format.process_in(self.encode_reference_to_latents(control["pixels"]))
+            if self.controlnet.config.guidance_embed:  # (a guidance-distilled FLUX ControlNet sees the strength the model sees)
+                self.controlnet.guidance = self.mmdit.guidance
             extra_args["controlnet"] = {"engine": self.controlnet, "tokens": self.controlnet.patchify(z.to(torch.float32).contiguous()),
                                         "scale": control["scale"], "interval": control["interval"]}
         self.last_reference = None
@@ -1205,10 +1213,38 @@ def controlnet_step_active(i: int, n: int, interval) -> bool:
     return i / n >= start and (i + 1) / n <= stop
 
 
-def _controlnet_options(pipe, image, scale, interval, n_img, out_hw, block_cache, slg, pag):
+def _check_flux_controlnet_config(pipe, controlnet_config) -> None:
+    """``controlnet_ckpt`` on a FLUX-family pipeline (``DiffusionPipeline._check_controlnet_config``): the configuration is required and must be a
+    FLUX ControlNet's that fits the model; sets ``pipe.controlnet_config``.  Needs no GPU."""
+    from .config import validate_control_net_flux
+    cfg = pipe.mmdit_config
+    if controlnet_config is None:
+        raise ValueError("controlnet_ckpt without a controlnet_config is the SD3 family's preset (config.SD3_CONTROLNET_6, diffusers' SD3ControlNetModel): a "
+                         "FLUX pipeline names its ControlNet's depths, controlnet_config=config.flux_controlnet_config(n_double, n_single) -- FLUX "
+                         "ControlNets (diffusers' FluxControlNetModel) have no canonical depth")
+    if cfg.weight_dtype == "fp8_e4m3":
+        raise ValueError("controlnet_ckpt cannot be combined with an fp8 engine: the fp8 LayerNorm kernels take no tap")
+    if cfg.condition_features != 0 or getattr(pipe, "condition", None) is not None:
+        raise ValueError("controlnet_ckpt cannot be combined with condition= (FLUX.1 Fill / Canny / Depth): the engine carries one kind of image "
+                         "conditioning at a time")
+    if not getattr(controlnet_config, "control_net_flux", False):
+        raise ValueError("controlnet_config must be a FLUX control-net configuration (control_net_flux=True, config.flux_controlnet_config(n_double, "
+                         "n_single)); control_net=True is the SD3 family's")
+    ccfg = controlnet_config
+    validate_control_net_flux(ccfg)
+    if (ccfg.hidden_size != cfg.hidden_size or ccfg.num_heads != cfg.num_heads or ccfg.patch_dim != cfg.patch_dim
+            or ccfg.depth_multimodal > cfg.depth_multimodal or ccfg.depth_unified > cfg.depth_unified):
+        raise ValueError(f"the ControlNet (hidden {ccfg.hidden_size}, {ccfg.num_heads} heads, patch_dim {ccfg.patch_dim}, ({ccfg.depth_multimodal}, "
+                         f"{ccfg.depth_unified}) blocks) does not fit the model (hidden {cfg.hidden_size}, {cfg.num_heads} heads, patch_dim "
+                         f"{cfg.patch_dim}, ({cfg.depth_multimodal}, {cfg.depth_unified}) blocks): the taps are added to its stream")
+    pipe.controlnet_config = ccfg
+
+
+def _controlnet_options(pipe, image, scale, interval, n_img, out_hw, block_cache, slg, pag, reference=None, condition=None):
     """The ControlNet keywords of one call -> None (a pipeline without a ControlNet and no keyword) or {"pixels": uint8 [1 or n_img, H, W, 3],
     "scale", "interval"}.  Refused, each naming its rule: the keywords on a pipeline built without a ControlNet and their absence on one built
-    with it, ``block_cache``, skip-layer and perturbed-attention guidance, a control image of another size than the output."""
+    with it, ``block_cache``, skip-layer and perturbed-attention guidance, a reference image or a condition (the FLUX family's: the engine
+    refuses taps beside either), a control image of another size than the output."""
     has = getattr(pipe, "controlnet", None) is not None
     if not has:
         if image is not None or interval is not None or float(scale) != 1.0:
@@ -1216,6 +1252,10 @@ def _controlnet_options(pipe, image, scale, interval, n_img, out_hw, block_cache
         return None
     if image is None:
         raise ValueError("a pipeline built with a ControlNet needs controlnet_image_path in every call: the ControlNet was trained to see a control image")
+    if reference is not None:
+        raise ValueError("a ControlNet cannot run together with reference_image_path: the reference rows of the stream would need taps of their own")
+    if condition is not None:
+        raise ValueError("a ControlNet cannot run together with a condition (condition_image_path): the engine carries one kind of image conditioning at a time")
     if block_cache is not None:
         raise ValueError("a ControlNet cannot run together with block_cache: the cached effect of blocks 1 .. L-1 would hold another step's taps")
     if slg is not None or pag is not None:
@@ -1453,7 +1493,11 @@ def _step_loop(model: "CFGDenoiser", lp: _Loop, plan, grows, guide=None, euler: 
             if controlnet_step_active(step, n_steps, lp.control["interval"]):
                 lp.control["engine"].control_forward(tok, None, r.index, taps_out=lp.control["taps"])
                 if mm.control_taps is None or mm.control_taps[0] is not lp.control["taps"]:
-                    mm.set_control_taps(lp.control["taps"], lp.control["scale"])
+                    cn = lp.control["engine"]
+                    if cn.control_net_flux:  # (every tap it writes, its double blocks' first; the main engine maps them onto its own depths)
+                        mm.set_flux_control_taps(lp.control["taps"], cn.config.depth_multimodal, lp.control["scale"])
+                    else:
+                        mm.set_control_taps(lp.control["taps"], lp.control["scale"])
                 control_evals += 1
             elif mm.control_taps is not None:
                 mm.set_control_taps(None)

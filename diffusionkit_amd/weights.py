@@ -113,6 +113,15 @@ def synth_mmdit_weights(cfg: MMDiTConfig, seed: int = 1234, device="cpu", dtype=
         for i in range(cfg.depth_multimodal):
             I.linear(f"controlnet_blocks.{i}", h, h)
         return I.out
+    if getattr(cfg, "control_net_flux", False):
+        # FLUX ControlNet: no final layer; the control image's patch embedder and one Linear per double and per single block (drawn, not zero)
+        I.normal("controlnet_x_embedder.proj.weight", (h, 1, 1, cfg.patch_dim))
+        I.normal("controlnet_x_embedder.proj.bias", (h,))
+        for i in range(cfg.depth_multimodal):
+            I.linear(f"controlnet_blocks.{i}", h, h)
+        for i in range(cfg.depth_unified):
+            I.linear(f"controlnet_single_blocks.{i}", h, h)
+        return I.out
     I.linear("final_layer.linear", cfg.patch_dim, h)
     I.linear("final_layer.adaLN_modulation.layers.1", 2 * h, h)
     # MMDiT-X dual-attention blocks (cfg.dual_attention_blocks): the second attention of the image stream -- k_proj WITH its bias -- and rows
@@ -231,7 +240,7 @@ def adaln_order(cfg: MMDiTConfig):
         names.append(f"multimodal_transformer_blocks.{i}.text_transformer_block")
     for i in range(cfg.depth_unified):
         names.append(f"unified_transformer_blocks.{i}.transformer_block")
-    if not getattr(cfg, "control_net", False):  # (a ControlNet has no final layer)
+    if not (getattr(cfg, "control_net", False) or getattr(cfg, "control_net_flux", False)):  # (a ControlNet has no final layer)
         names.append("final_layer")
     return names
 
@@ -271,6 +280,9 @@ def pack_mmdit(cfg: MMDiTConfig, w: Dict[str, Tensor], device, consume: bool = F
     validate_activation_dtype(cfg)
     validate_dual_attention(cfg)
     validate_control_net(cfg)
+    from .config import validate_control_net_flux
+    validate_control_net_flux(cfg)
+    control_flux = bool(getattr(cfg, "control_net_flux", False))
     control_net = bool(getattr(cfg, "control_net", False))
     bf = torch.float16 if cfg.activation_dtype == "float16" else torch.bfloat16
     fp8 = cfg.weight_dtype == "fp8_e4m3"
@@ -323,8 +335,19 @@ def pack_mmdit(cfg: MMDiTConfig, w: Dict[str, Tensor], device, consume: bool = F
               "y_embedder.mlp.layers.2.weight", "y_embedder.mlp.layers.2.bias",
               "t_embedder.mlp.layers.0.weight", "t_embedder.mlp.layers.0.bias",
               "t_embedder.mlp.layers.2.weight", "t_embedder.mlp.layers.2.bias") + (
-                  () if control_net else ("final_layer.linear.weight", "final_layer.linear.bias")):
+                  () if control_net or control_flux else ("final_layer.linear.weight", "final_layer.linear.bias")):
         put(k, get(k))
+    if control_flux:  # the control image's patch embedder, packed as x_embedder is, and the tap Linears of both kinds (dk_mmdit_set_flux_control_net)
+        cw = get("controlnet_x_embedder.proj.weight")
+        if cw.reshape(cw.shape[0], -1).shape[1] != cfg.patch_dim:
+            raise ValueError(f"controlnet_x_embedder.proj.weight {tuple(cw.shape)}: {cfg.patch_dim} input features expected (extra conditioning "
+                             "channels are not supported)")
+        put("controlnet_x_embedder.proj.weight", cw.reshape(cw.shape[0], -1))
+        put("controlnet_x_embedder.proj.bias", get("controlnet_x_embedder.proj.bias"))
+        for kind, n in (("controlnet_blocks", cfg.depth_multimodal), ("controlnet_single_blocks", cfg.depth_unified)):
+            for i in range(n):
+                put(f"{kind}.{i}.weight", get(f"{kind}.{i}.weight"))
+                put(f"{kind}.{i}.bias", get(f"{kind}.{i}.bias"))
     if control_net:  # the control image's patch embedder, packed as x_embedder is, and the tap Linears (dk_mmdit_set_control_net)
         cw = get("pos_embed_input.proj.weight")
         if cw.reshape(cw.shape[0], -1).shape[1] != cfg.patch_dim:

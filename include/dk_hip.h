@@ -385,6 +385,18 @@ int dk_ln_modulate_add_bf16(void* x, const void* tap, int32_t ldt, float s, void
                             int32_t mod_seg_len, const void* x1, void* out1, int32_t M1, const void* shift1, const void* scale1,
                             int32_t mod_seg_len1, int32_t ldx, int32_t ldo, int32_t h, int32_t mod_stride, int32_t x_seg_stride,
                             int32_t x_seg_stride1, float eps, void* stream);
+/* The same pass as ONE job over a joint stream of which only some rows take the residual (FLUX ControlNet taps, see
+ * dk_mmdit_set_flux_control_taps; bf16 only).  Logical row m of the M rows is physical row (m / x_seg_len) * x_seg_stride + m % x_seg_len
+ * of x (x_seg_len <= 0: M, dense); M is a whole number of groups of tap_seg rows.  Of every group the first tap_first rows (0 <= tap_first <
+ * tap_seg: the text rows) are plain -- x is not written there, out is dk_ln_modulate_bf16's -- and row s >= tap_first of group b is first
+ * rewritten in place, x' = round_bf16( fmaf(s, tap[b * (tap_seg - tap_first) + (s - tap_first), :], x) ), out = dk_ln_modulate_bf16 of x'.
+ * tap: dense [(M / tap_seg) * (tap_seg - tap_first), ldt], 16-byte aligned, ldt >= h, ldt % 8 == 0: it has no rows for the plain rows and
+ * nothing is read where they would be.  out: dense [M, ldo]; modulation row m / mod_seg_len at mod_stride elements (mod_seg_len <= 0: M).
+ * The engine's two uses: a single block's LayerNorm (x = X, M = B S, tap_seg = S, tap_first = S_t) and the final layer's (x = X + S_t h,
+ * x_seg_len = tap_seg = S_i, x_seg_stride = S, tap_first = 0).  dk_ln_modulate_add_bf16's job is the map tap_seg = M, tap_first = 0. */
+int dk_ln_modulate_add_joint_bf16(void* x, int32_t ldx, const void* tap, int32_t ldt, float s, int32_t tap_seg, int32_t tap_first, void* out,
+                                  int32_t ldo, int32_t M, int32_t h, const void* shift, const void* scale, int32_t mod_stride,
+                                  int32_t mod_seg_len, int32_t x_seg_len, int32_t x_seg_stride, float eps, void* stream);
 
 /* QKNorm (mmdit.py:754-764) + RoPE.apply (mmdit.py:934-942), in place on the q / k column groups
  * of a token-major QKV buffer.  q_weight/k_weight NULL = no norm; rope_table NULL = no rotation.
@@ -947,6 +959,40 @@ int dk_mmdit_set_control_net(dk_mmdit* m, int32_t on);
 int dk_mmdit_cache_control_image(dk_mmdit* m, const void* ctrl_tokens, int32_t per_image, void* stream);
 int dk_mmdit_control_forward(dk_mmdit* m, const void* tokens_in, const void* text, int32_t step_index, void* taps_out, void* stream);
 int dk_mmdit_set_control_taps(dk_mmdit* m, const void* taps, int32_t n_taps, float scale);
+
+/* ---- FLUX ControlNet (opt-in; the layout of diffusers' FluxControlNetModel, no counterpart in the reference; bf16 only) --------------
+ * The same two engines on FLUX geometry.  The entries above stay the SD3 family's and keep refusing FLUX geometry.
+ *
+ * dk_mmdit_set_flux_control_net(m, on): legal before the first dk_mmdit_bind.  Needs use_rope, no positional table, bf16, no fp8_linears,
+ * depth_multimodal >= 1; depth_unified >= 0.  Such an engine has no final layer (and no modulation rows for one) and additionally binds
+ *   controlnet_x_embedder.proj.{weight,bias}       [h, p*p*C] / [h], packed as x_embedder.proj is
+ *   controlnet_blocks.<j>.{weight,bias}            [h, h] / [h], j < depth_multimodal
+ *   controlnet_single_blocks.<j>.{weight,bias}     [h, h] / [h], j < depth_unified
+ * dk_mmdit_cache_control_image on it computes CONDE[b] = controlnet_x_embedder(ctrl_tokens[b]) once (FLUX has no positional table, so
+ * the slot is free); every dk_mmdit_control_forward's x_embedder launch adds it in its residual epilogue:
+ *   image rows = round( round(x_embedder(tokens)) + round(controlnet_x_embedder(control tokens)) ).
+ * dk_mmdit_control_forward writes depth_multimodal + depth_unified taps, [n, B, S_i, h], double blocks first: behind each double block
+ * the tap Linear reads the image stream, behind each single block the image rows of the joint stream.
+ *
+ * dk_mmdit_set_flux_control_taps(m, taps, n_double_taps, n_single_taps, scale) on the MAIN engine: taps [n_double_taps + n_single_taps,
+ * B, S_i, h] dense bf16, 16-byte aligned, the double blocks' taps first; either count may be 0, each is at most the model's depth of
+ * that kind.  Behind block g of a kind with depth blocks and n taps the image rows take s * tap[g / ceil(depth / n)] (diffusers'
+ * FluxTransformer2DModel: index_block // int(np.ceil(depth / n)); NOT the SD3 rule -- depth 4, n 3 gives 0,0,1,1 here and 0,0,1,2
+ * there), the last block of each kind included.  Every add rides in the LayerNorm launch that reads those rows next, as
+ * x' = round_bf16(fmaf(s, tap, x)) in place:
+ *   behind double g < depth_multimodal - 1     block g + 1's first LayerNorm (dk_ln_modulate_add_bf16)
+ *   behind the last double block               single block 0's LayerNorm, on the image rows of the joint stream
+ *                                              (dk_ln_modulate_add_joint_bf16); the final layer's with depth_unified == 0
+ *   behind single j < depth_unified - 1        single block j + 1's LayerNorm, likewise
+ *   behind the last single block               the final layer's LayerNorm
+ * so a tapped evaluation has the launch count of a plain one.  (NULL, 0, 0, any) is off, the default: every launch and every bit is then
+ * what it is without the feature.  dk_mmdit_prepare switches the taps off.
+ * Refused, with no state changed and an error that names the rule: a geometry other than FLUX's, fp8_linears (the MX-fp8 LayerNorm
+ * kernels take no tap), fp16, a count outside its range, dual attention, a block cache, skip layers, perturbed attention, a reference
+ * grid, a condition width, a control-net engine.  dk_mmdit_forward_head, dk_mmdit_forward_tail and dk_mmdit_run_blocks are refused while
+ * taps are set.  Verified against an fp32 / emulating oracle with synthetic weights (arithmetic parity); no checkpoint has been run. */
+int dk_mmdit_set_flux_control_net(dk_mmdit* m, int32_t on);
+int dk_mmdit_set_flux_control_taps(dk_mmdit* m, const void* taps, int32_t n_double_taps, int32_t n_single_taps, float scale);
 /* Head of step `step_index`: dk_mmdit_forward's embedder launches, block 0 and the probe.  probe_out: device float [batch][2] =
  * (num, den) per batch row; before any computed step den is 0 (and num = sum |D_cur|).  Records a pending head for step_index. */
 int dk_mmdit_forward_head(dk_mmdit* m, const void* tokens_in, const void* text, int32_t step_index, float* probe_out, void* stream);
