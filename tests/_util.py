@@ -39,6 +39,9 @@ def randn(*shape, seed=0, scale=1.0):
 #    +-2^-9 => rel-L2 ~ 1.1e-3; allow 3e-3 for single-op kernels.
 #  - chained ops (block / model level): compared against the fp32 oracle with the bf16-emulating
 #    oracle as yardstick: err(hip, fp32) <= 2 * err(emu, fp32) + 2e-3.
+#  - a whole-tensor gate cannot see a fault confined to a row, a fragment or a tile edge (a dropped key, a zeroed
+#    element, a missing bias on a few columns all stay under 3e-3); the per-element and per-row gates that can are in
+#    tests/_gates.py, proved on mutants in tests/test_gate_power_cpu.py.
 TOL_SINGLE_OP = 3e-3
 
 

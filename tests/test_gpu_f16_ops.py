@@ -10,9 +10,16 @@ import torch
 
 from oracle import mmdit as om
 from oracle.mmdit import Prec
+from tests import _gates as gates
 from tests._util import TOL_SINGLE_OP, max_abs, randn, rel_l2
 
 pytestmark = pytest.mark.gpu
+
+
+def gated(name, ratio):
+    """a per-element / per-row gate of tests/_gates.py (proved on mutants in tests/test_gate_power_cpu.py): worst error / bound, printed, <= 1"""
+    print(f"[gate] {name}: {ratio:.3f}")
+    assert ratio <= 1.0, f"{name}: worst error at {ratio:.3f} of the bound"
 
 F16 = torch.float16
 TOL_F16 = TOL_SINGLE_OP / 8
@@ -87,6 +94,7 @@ def test_gemm128_f16(dev, M, N, K, epi):
     e = rel_l2(ref, y.float())
     print(f"gemm128_f16 {M}x{N}x{K} {epi}: rel_l2 {e:.3e}")
     assert e < TOL_F16
+    gated(f"gemm128_f16 {M}x{N}x{K} {epi}", gates.gemm_gate(y.float().cpu(), x, w, b, F16, epi, res, gate))
 
 
 # ---- gemm256v3: every epilogue, ragged row maps, the half column tile -------------------------------------------------------------------
@@ -125,6 +133,7 @@ def test_gemm256v3_f16(dev, M, seg, stride, N, epi):
     e = rel_l2(ref, got[idx])
     print(f"gemm256v3_f16 M={M} N={N} {epi}: rel_l2 {e:.3e}")
     assert e < TOL_F16
+    gated(f"gemm256v3_f16 M={M} N={N} {epi}", gates.gemm_gate(got[idx], A[idx], w, b, F16, epi, X[idx], gate[torch.arange(M) // seg]))
 
 
 @pytest.mark.parametrize("epi", ["bias", "gate_res"])
@@ -137,6 +146,7 @@ def test_gemm256v3_f16_grouped_image_and_text_pair(dev, epi):
     Xd, Ad = g(X, dev), g(A, dev)
     want = X.clone()
     calls = []
+    gate_args = {}
     for sfx, row0, seg in (("img", S_t, S_i), ("txt", 0, S_t)):
         w, b, gate = rnd(N, K, seed=32 + row0, scale=0.06), rnd(N, seed=33 + row0, scale=0.1), rnd(B, N, seed=34 + row0)
         idx = row0 + seg_rows(B * seg, seg, S)
@@ -148,6 +158,7 @@ def test_gemm256v3_f16_grouped_image_and_text_pair(dev, epi):
         if epi == "gate_res":
             d.update(res=d["C"], ldr=N, r_seg_len=seg, r_seg_stride=S, gate=gd, gate_seg_len=seg, gate_stride=N)
         calls.append((d, idx, (wd, bd, gd)))
+        gate_args[sfx] = (idx, w, b, gate[torch.arange(B * seg) // seg])
     p = ops.gemm_plan({k: (v.data_ptr() if isinstance(v, torch.Tensor) else v) for k, v in calls[0][0].items()},
                       {k: (v.data_ptr() if isinstance(v, torch.Tensor) else v) for k, v in calls[1][0].items()}, dtype=F16)
     assert (p.kernel, p.launches) == (3, 1)  # one grouped launch
@@ -159,6 +170,8 @@ def test_gemm256v3_f16_grouped_image_and_text_pair(dev, epi):
         e = rel_l2(want[idx], got[idx])
         print(f"gemm256v3_f16 pair {epi} M={len(idx)}: rel_l2 {e:.3e}")
         assert e < TOL_F16
+    for sfx, (idx, w, b, gate) in gate_args.items():
+        gated(f"gemm256v3_f16 pair {epi} {sfx}", gates.gemm_gate(got[idx], A[idx], w, b, F16, epi, X[idx], gate))
     assert torch.equal(got[~touched], X[~touched])
 
 
@@ -212,6 +225,7 @@ def test_gemm256v3_f16_k_split(dev):
     ndiff = int((y_ws != y_no).sum())
     print(f"k split f16: split {e_ws:.3e}, whole {e_no:.3e}, {ndiff} of {M * N} elements differ")
     assert e_ws < TOL_F16 and e_no < TOL_F16
+    gated("k split f16, split and whole", gates.gemm_gate([y_ws.float().cpu(), y_no.float().cpu()], x, w, b, F16, rows=gates.row_subset(M, N, K)))
     assert 0 < ndiff < 0.02 * M * N
     assert int(ws[-4096:].sum()) == 0
 
@@ -287,6 +301,7 @@ def test_attention_f16_ragged(dev):
     e = rel_l2(ref, y.float())
     print(f"attention_f16 (2, 3, 333): rel_l2 {e:.3e}")
     assert e < TOL_ATTN_F16
+    gated("attention_f16 (2, 3, 333)", gates.attn_gate(y, qkv, H, D, F16))
 
 
 def test_attention_f16_query_qknorm_in_the_q_load(dev):
@@ -302,6 +317,7 @@ def test_attention_f16_query_qknorm_in_the_q_load(dev):
     e = rel_l2(ref, y.float())
     print(f"attention_f16 (1, 6, 200) fused query norm: rel_l2 {e:.3e}")
     assert e < TOL_ATTN_F16
+    gated("attention_f16 (1, 6, 200) fused query norm", gates.attn_gate(y, torch.cat([qn, qkv[..., h:]], dim=-1), H, D, F16))
 
 
 def test_attention_f16_spiked_key_forces_rescale(dev):
@@ -317,6 +333,7 @@ def test_attention_f16_spiked_key_forces_rescale(dev):
     e = rel_l2(ref, y.float())
     print(f"attention_f16 spiked key: rel_l2 {e:.3e}")
     assert e < TOL_ATTN_F16
+    gated("attention_f16 spiked key", gates.attn_gate(y, qkv, H, D, F16))
 
 
 # ---- elementwise ---------------------------------------------------------------------------------------------------------------------
@@ -331,6 +348,16 @@ def test_ln_modulate_f16(dev, h):
     e = rel_l2(ref, y.float())
     print(f"ln_modulate_f16 h={h}: rel_l2 {e:.3e}")
     assert y.dtype == F16 and e < TOL_F16
+    gated(f"ln_modulate_f16 h={h}", gates.ln_gate(y, x, shift, scale, F16))
+
+
+def test_ln_modulate_f16_large_mean_rows(dev):
+    """h = 2432 = 38 x 64 at mean / sigma 16 (tests/_gates.LN_CASES): rows on which a channel left out of the mean shows; the per-row gate alone"""
+    from diffusionkit_amd import ops
+    case = next(c for c in gates.LN_CASES if c[0] == F16 and len(c) > 5)
+    x, shift, scale = gates.ln_operands(case)
+    y = ops.ln_modulate(g(x, dev), g(shift, dev), g(scale, dev))
+    gated(f"ln_modulate_f16 {case[1:4]} large mean", gates.ln_gate(y, x, shift, scale, F16))
 
 
 def test_qk_norm_rope_f16(dev):
@@ -350,6 +377,7 @@ def test_qk_norm_rope_f16(dev):
     e = rel_l2(ref, got[..., :2 * h])
     print(f"qk_norm_rope_f16: rel_l2 {e:.3e}")
     assert e < TOL_F16
+    gated("qk_norm_rope_f16", gates.qk_gate(got[..., :2 * h], qkv, qw, kw, tab, D, F16))
 
 
 def test_timestep_embedding_f16_out(dev):

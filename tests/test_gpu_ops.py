@@ -9,9 +9,16 @@ import torch
 from oracle import mmdit as om
 from oracle import vae as ov
 from oracle.mmdit import Prec
+from tests import _gates as gates
 from tests._util import BF, TOL_SINGLE_OP, bf16r, max_abs, randn, rel_l2
 
 pytestmark = pytest.mark.gpu
+
+
+def gated(name, ratio):
+    """a per-element / per-row gate of tests/_gates.py (proved on mutants in tests/test_gate_power_cpu.py): worst error / bound, printed, <= 1"""
+    print(f"[gate] {name}: {ratio:.3f}")
+    assert ratio <= 1.0, f"{name}: worst error at {ratio:.3f} of the bound"
 
 
 def g(x, dev):
@@ -33,6 +40,7 @@ def test_gemm_bias(dev, M, N, K):
     assert rel_l2(ref, y.float()) < TOL_SINGLE_OP
     # transpose-detecting: asymmetric problem, and the worst element is within 2 bf16 ulps of the scale
     assert max_abs(ref, y.float()) < 0.02 * float(ref.abs().max()) + 1e-2
+    gated(f"gemm bias {M}x{N}x{K}", gates.gemm_gate(y.float().cpu(), x, w, b, BF, rows=gates.row_subset(M, N, K)))
 
 
 def test_gemm_identity_asymmetric(dev):
@@ -67,6 +75,7 @@ def test_gemm_epilogues(dev, epi):
         y = ops.linear(g(x, dev), g(w, dev), g(b, dev), epilogue=ops.DK_EPI_RES, res=g(res, dev))
         ref = res + acc
     assert rel_l2(ref, y.float()) < TOL_SINGLE_OP
+    gated(f"gemm {epi}", gates.gemm_gate(y.float().cpu(), x, w, b, BF, epi, res, gate.repeat_interleave(S, 0)))
 
 
 def test_gemm_segment_mapping_in_place(dev):
@@ -89,6 +98,8 @@ def test_gemm_segment_mapping_in_place(dev):
     got = Xd.float().cpu()
     assert torch.equal(got[:, :S_t], X[:, :S_t])  # text rows untouched
     assert rel_l2(ref[:, S_t:], got[:, S_t:]) < TOL_SINGLE_OP
+    gated("gemm segment maps, in place", gates.gemm_gate(got[:, S_t:].reshape(-1, h), att[:, S_t:].reshape(-1, h), w, b, BF, "gate_res",
+                                                         X[:, S_t:].reshape(-1, h), gate[:, h:2 * h].repeat_interleave(S_i, 0)))
 
 
 GEMM_MODES = {-1: "automatic choice", 128: "128^2 tiles", 9: "256^2 tiles (16x16x32 MFMA, LDS-DMA ring)",
@@ -123,6 +134,7 @@ def test_gemm_kernel_variants(dev, mode, epi):
         ops.tune("gemm", -1)
     assert rel_l2(ref, y.float()) < TOL_SINGLE_OP, GEMM_MODES[mode]
     assert max_abs(ref, y.float()) < 0.02 * float(ref.abs().max()) + 1e-2
+    gated(f"gemm mode {mode} {epi}", gates.gemm_gate(y.float().cpu(), x, w, b, BF, epi, res, gate.repeat_interleave(S, 0)))
     # the flag region of the K-split workspace must be left zero (flags are reset by their consumer)
     assert int(ws[-4096:].sum()) == 0
 
@@ -159,6 +171,8 @@ def test_gemm_256_half_column_tile(dev, M, N, K, epi, mf):
     y = out[:, :N].float().cpu()
     assert rel_l2(ref, y) < TOL_SINGLE_OP
     assert max_abs(ref, y) < 0.02 * float(ref.abs().max()) + 1e-2
+    gated(f"gemm half column tile {M}x{N}x{K} {epi} mf {mf}",
+          gates.gemm_gate(y, x, w, b, BF, epi, res, gate.repeat_interleave(seg, 0)[:M], rows=gates.row_subset(M, N, K)))
     assert bool((out[:, N:] == 7.0).all())
 
 
@@ -188,6 +202,8 @@ def test_gemm_256_joint_stream_in_place(dev):
         got = Xd.float().cpu()
         assert torch.equal(got[:, :S_t], X[:, :S_t])
         assert rel_l2(ref[:, S_t:], got[:, S_t:]) < TOL_SINGLE_OP, mode
+        gated(f"gemm joint stream, in place, mode {mode}", gates.gemm_gate(got[:, S_t:].reshape(-1, h), att[:, S_t:].reshape(-1, h), w, b, BF, "gate_res",
+                                                                            X[:, S_t:].reshape(-1, h), gate[:, h:2 * h].repeat_interleave(S_i, 0)))
 
 
 @pytest.mark.parametrize("mf", [8, 7, 104])
@@ -229,6 +245,8 @@ def test_gemm_v3_ragged_and_straddling_segments(dev, B, S_t, S_i, epi, mf):
     assert torch.equal(got[:, S_t:], X[:, S_t:])  # rows of the other stream untouched
     assert rel_l2(ref[:, :S_t], got[:, :S_t]) < TOL_SINGLE_OP
     assert max_abs(ref[:, :S_t], got[:, :S_t]) < 0.02 * float(ref.abs().max()) + 1e-2
+    gated(f"gemm ragged segments {epi} mf {mf}", gates.gemm_gate(got[:, :S_t].reshape(-1, N), att[:, :S_t].reshape(-1, h), w, b, BF, epi,
+                                                                X[:, :S_t].reshape(-1, N), gate[:, N:].repeat_interleave(S_t, 0)))
 
 
 @pytest.mark.parametrize("M,N,K", [(4352, 3072, 3072), (224, 256, 64), (449, 512, 192), (4608, 256, 128)])
@@ -247,6 +265,7 @@ def test_gemm_v3_tile_heights_agree(dev, M, N, K):
             ops.tune("gemm", -1)
             ops.tune("gemm_mf", -1)
     assert rel_l2(bf16r(x @ w.t() + b), outs[8].float()) < TOL_SINGLE_OP
+    gated(f"gemm tile heights {M}x{N}x{K}", gates.gemm_gate(outs[8].float().cpu(), x, w, b, BF, rows=gates.row_subset(M, N, K)))
     assert torch.equal(outs[8], outs[7]) and torch.equal(outs[8], outs[-1])
 
 
@@ -281,6 +300,8 @@ def test_gemm_v4_equals_v3(dev, M, N, K, epi, mf):
             ops.tune("gemm_mf", -1)
             ops.tune("gemm_split", -1)
     assert rel_l2(ref, outs[10].float()) < TOL_SINGLE_OP
+    # (each side against fp64; the comparison of the two stays as it is)
+    gated(f"gemm modes 9, 10 {M}x{N}x{K} {epi} mf {mf}", gates.gemm_gate([outs[m_].float().cpu() for m_ in (9, 10)], x, w, b, BF, epi, res, gate, rows=gates.row_subset(M, N, K)))
     assert torch.equal(outs[9], outs[10])
 
 
@@ -301,6 +322,7 @@ def test_conv3x3(dev, B, H, W, C, O, ups, res):
         ref = ref + r
     assert y.shape == ref.shape
     assert rel_l2(ref, y.float()) < TOL_SINGLE_OP
+    gated(f"conv3x3 {(B, H, W, C, O, ups, res)}", gates.conv_gate(y.float().cpu(), x, w, b, BF, "ups" if ups else "plain", r))
 
 
 @pytest.mark.parametrize("B,H,W,C,O,ups,res,mode", [(1, 40, 24, 64, 256, False, False, 9),    # ragged M (960 pixels), forced
@@ -334,6 +356,7 @@ def test_conv3x3_on_256_tile_kernel(dev, B, H, W, C, O, ups, res, mode, mf):
     if res:
         ref = ref + r
     assert rel_l2(ref, y.float()) < TOL_SINGLE_OP
+    gated(f"conv3x3 {(B, H, W, C, O, ups, res)} mf {mf}, 256 and 128 tiles", gates.conv_gate([y.float().cpu(), y128.float().cpu()], x, w, b, BF, "ups" if ups else "plain", r))
     assert max_abs(y128.float(), y.float()) <= 0.02 * float(ref.abs().max()) + 1e-2
     assert float((y128.float() != y.float()).float().mean()) < 0.05
 
@@ -371,6 +394,7 @@ def test_gemm_v3_remainder_split(dev, M, N, K, epi, mf):
         ops.tune("gemm_split", -1)
         ops.tune("gemm_mf", -1)
     assert rel_l2(ref, y.float()) < TOL_SINGLE_OP
+    gated(f"gemm remainder split {M}x{N}x{K} {epi} mf {mf}, split and whole", gates.gemm_gate([y.float().cpu(), y0.float().cpu()], x, w, b, BF, epi, res, gate, rows=gates.row_subset(M, N, K)))
     assert max_abs(y0.float(), y.float()) <= 0.02 * float(ref.abs().max()) + 1e-2  # a bf16 ulp where the summation order differs
     assert float((y0.float() != y.float()).float().mean()) < 0.02
     assert int(ws[-4096:].sum()) == 0
@@ -404,6 +428,7 @@ def test_gemm_small_launch_is_split_automatically(dev, M, N, K, epi, split):
         ops.tune("gemm_split", -1)
     assert rel_l2(ref, y.float()) < TOL_SINGLE_OP
     assert rel_l2(ref, y0.float()) < TOL_SINGLE_OP
+    gated(f"gemm {M}x{N}x{K} {epi}, automatic and split off", gates.gemm_gate([y.float().cpu(), y0.float().cpu()], x, w, b, BF, epi, res, gate, rows=gates.row_subset(M, N, K)))
     if split:
         assert not torch.equal(y0, y), "the launch was expected to be cut along K (other summation order)"
         assert float((y0.float() != y.float()).float().mean()) < 0.05
@@ -423,6 +448,7 @@ def test_conv3x3_stride2_downsample(dev, B, H, W, C, O):
     ref = ov.conv2d_s2_pad_br_nhwc(x, w, b, Prec())
     assert y.shape == ref.shape == (B, H // 2, W // 2, O)
     assert rel_l2(ref, y.float()) < TOL_SINGLE_OP
+    gated(f"conv3x3 stride 2 {(B, H, W, C, O)}", gates.conv_gate(y.float().cpu(), x, w, b, BF, "s2"))
 
 
 def test_latent_sample(dev):
@@ -449,7 +475,9 @@ def test_latent_sample(dev):
                                      (2, 4, 4096 + 589, 64),
                                      # the automatic choice at D = 128, S >= 2048 (phase-alternating kernel): ragged last key tile
                                      # and last query block, two images; a whole number of both
-                                     (2, 3, 2048 + 17, 128), (1, 2, 2304, 128)])
+                                     (2, 3, 2048 + 17, 128), (1, 2, 2304, 128),
+                                     # a ragged last key tile and a ragged last query block in one small launch: a single row carries more of the norm
+                                     (1, 2, 397, 64), (1, 2, 2304 + 17, 128)])
 def test_attention(dev, B, H, S, D):
     from diffusionkit_amd import ops
     h = H * D
@@ -460,11 +488,13 @@ def test_attention(dev, B, H, S, D):
     # P is rounded to bf16 before the PV product and the output once more
     assert rel_l2(ref, y.float()) < 6e-3
     assert max_abs(ref, y.float()) < 0.03
+    gated(f"attention {(B, H, S, D)}", gates.attn_gate(y, qkv, H, D, BF, heads=gates.attn_gate_heads(H, S), images=gates.attn_gate_images(B, S)))
 
 
 @pytest.mark.parametrize("mode", [4, 9])
 @pytest.mark.parametrize("B,H,S,D", [(1, 2, 333, 128), (2, 3, 700, 64), (1, 2, 64, 128), (1, 2, 100, 64), (1, 2, 128, 128), (1, 2, 129, 128), (1, 2, 192, 128), (1, 2, 250, 128), (1, 3, 1088, 128),
-                                     (2, 2, 589 + 64, 64), (1, 2, 64, 64), (1, 2, 128, 64), (1, 2, 129, 64), (1, 2, 192, 64), (1, 3, 1088 + 31, 64)])
+                                     (2, 2, 589 + 64, 64), (1, 2, 64, 64), (1, 2, 128, 64), (1, 2, 129, 64), (1, 2, 192, 64), (1, 3, 1088 + 31, 64),
+                                     (1, 2, 397, 64), (1, 2, 2304 + 17, 128)])
 def test_attention_kernel_variants(dev, mode, B, H, S, D):
     """The attention kernels behind dk_tune_set("attn", mode) (4: the VALU-lean kernel with the deferred rescale, 9: the
     phase-alternating kernel, D = 128; for D = 64 it falls back to the lean kernel) against
@@ -481,6 +511,7 @@ def test_attention_kernel_variants(dev, mode, B, H, S, D):
     ref = om.sdpa(q, k, v, 1.0 / math.sqrt(D), Prec()).transpose(1, 2).reshape(B, S, h)
     assert rel_l2(ref, y.float()) < 6e-3
     assert max_abs(ref, y.float()) < 0.03
+    gated(f"attention mode {mode} {(B, H, S, D)}", gates.attn_gate(y, qkv, H, D, BF))
 
 
 @pytest.mark.parametrize("B,H,S", [(1, 2, 768), (2, 3, 1024), (1, 2, 2304), (1, 24, 4352)])
@@ -503,6 +534,8 @@ def test_attention5_one_wave_per_simd(dev, B, H, S):
     ref = om.sdpa(q, k, v, 1.0 / math.sqrt(D), Prec()).transpose(1, 2).reshape(B, S, hs * D)
     assert rel_l2(ref, outs[10][..., :hs * D].float()) < 6e-3
     assert max_abs(ref, outs[10][..., :hs * D].float()) < 0.03
+    # (each side against fp64; the comparison of the two stays as it is)
+    gated(f"attention modes 9, 10 {(B, H, S)}", gates.attn_gate([outs[9], outs[10]], qkv, H, D, BF, heads=min(hs, gates.attn_gate_heads(H, S))))
     assert max_abs(outs[9].float(), outs[10].float()) < 4e-3  # (same algorithm; the row sums are added in another order)
 
 
@@ -528,6 +561,7 @@ def test_attention5_key_split_of_the_last_round(dev, split):
     q, k, v = (qkv[..., i * h:(i + 1) * h].reshape(B, S, H, D).transpose(1, 2) for i in range(3))
     ref = om.sdpa(q, k, v, 1.0 / math.sqrt(D), Prec()).transpose(1, 2).reshape(B, S, h)
     assert rel_l2(ref, outs[split].float()) < 6e-3
+    gated(f"attention5 key split {split} and unsplit", gates.attn_gate([outs[split], outs[0]], qkv, H, D, BF, family=["attn_split", "attn"]))
     assert not torch.equal(outs[0], outs[split])  # (the switch does select the split launch: the partials are rounded to bf16)
     assert max_abs(outs[0].float(), outs[split].float()) < 0.02 * float(ref.abs().max()) + 4e-3
 
@@ -570,9 +604,10 @@ def test_attention5_spiked_key_forces_rescale(dev):
     finally:
         ops.tune("attn", -1)
     assert rel_l2(ref, y.float()) < 6e-3
+    gated("attention5 spiked keys", gates.attn_gate(y, qkv, H, D, BF))
 
 
-@pytest.mark.parametrize("B,T", [(1, 64), (2, 96), (1, 100), (1, 1000), (2, 4096)])
+@pytest.mark.parametrize("B,T", [(1, 64), (2, 96), (1, 100), (1, 1000), (1, 1000 + 1), (2, 4096)])
 def test_attention_d512_flash(dev, B, T):
     """the VAE mid block's single-head D = 512 attention (vae.py:28-57) on the role-split flash kernel (attention512.hip): ragged
     query blocks and key tiles, two images, against the oracle's SDPA"""
@@ -583,6 +618,7 @@ def test_attention_d512_flash(dev, B, T):
     ref = om.sdpa(q[:, None], k[:, None], v[:, None], 1.0 / math.sqrt(D), Prec())[:, 0]
     assert rel_l2(ref, y.float()) < 6e-3
     assert max_abs(ref, y.float()) < 0.03
+    gated(f"attention D 512 {(B, T)}", gates.d512_gate(y, q, k, v))
 
 
 def test_attention_d512_spiked_key(dev):
@@ -596,6 +632,7 @@ def test_attention_d512_spiked_key(dev):
     assert float(p[7, 250]) > 0.9
     y = ops.attention_d512(g(q, dev), g(k, dev), g(v, dev))
     assert rel_l2(ref, y.float()) < 6e-3
+    gated("attention D 512 spiked key", gates.d512_gate(y, q, k, v))
 
 
 def test_attention_spiked_key_forces_rescale(dev):
@@ -617,6 +654,7 @@ def test_attention_spiked_key_forces_rescale(dev):
         finally:
             ops.tune("attn", -1)
         assert rel_l2(ref, y.float()) < 6e-3, mode
+        gated(f"attention spiked key mode {mode}", gates.attn_gate(y, qkv, H, D, BF))
 
 
 @pytest.mark.parametrize("mode", [4])
@@ -637,6 +675,7 @@ def test_attention_spiked_key_forces_rescale_d64(dev, mode):
     finally:
         ops.tune("attn", -1)
     assert rel_l2(ref, y.float()) < 6e-3
+    gated(f"attention spiked key D 64 mode {mode}", gates.attn_gate(y, qkv, H, D, BF))
 
 
 # ---- normalisation / elementwise ------------------------------------------------------------------
@@ -649,6 +688,16 @@ def test_ln_modulate(dev, B, S, h):
     P = Prec(BF)
     ref = P.r(om.layer_norm(x, 1e-6) * P.r(1.0 + scale[:, None]) + shift[:, None])  # fused batch-1 form
     assert rel_l2(ref, y.float()) < 2e-3
+    gated(f"ln_modulate {(B, S, h)}", gates.ln_gate(y, x, shift, scale, BF))
+
+
+def test_ln_modulate_large_mean_rows(dev):
+    """h = 2432 = 38 x 64 at mean / sigma 16 (tests/_gates.LN_CASES): rows on which a channel left out of the mean shows; the per-row gate alone"""
+    from diffusionkit_amd import ops
+    case = next(c for c in gates.LN_CASES if c[0] == BF and len(c) > 5)
+    x, shift, scale = gates.ln_operands(case)
+    y = ops.ln_modulate(g(x, dev), g(shift, dev), g(scale, dev))
+    gated(f"ln_modulate {case[1:4]} large mean", gates.ln_gate(y, x, shift, scale, BF))
 
 
 @pytest.mark.parametrize("D,norm,rope", [(128, True, True), (64, True, False), (128, False, True)])
@@ -675,6 +724,7 @@ def test_qk_norm_rope(dev, D, norm, rope):
     got = d.float().cpu()
     assert torch.equal(got[..., 2 * h:], qkv[..., 2 * h:])  # v untouched
     assert rel_l2(ref, got) < 2e-3
+    gated(f"qk_norm_rope {(D, norm, rope)}", gates.qk_gate(got[..., :2 * h], qkv, qw if norm else None, kw if norm else None, tab_dev, D, BF))
 
 
 @pytest.mark.parametrize("D", [128, 64])
@@ -692,6 +742,7 @@ def test_qk_norm_rope_key_weight_alone(dev, D):
     got = d.float().cpu()
     assert torch.equal(got[..., :h], qkv[..., :h]) and torch.equal(got[..., 2 * h:], qkv[..., 2 * h:])  # q and v untouched
     assert rel_l2(k, got[..., h:2 * h]) < 2e-3
+    gated(f"qk_norm_rope key weight alone D {D}", gates.qk_gate(got[..., :2 * h], qkv, None, kw, None, D, BF))
     assert not torch.equal(got[..., h:2 * h], qkv[..., h:2 * h])
 
 
@@ -722,6 +773,9 @@ def test_groupnorm(dev, C, G, HW, silu):
     if silu:
         ref = ov.silu(ref, P)
     assert rel_l2(ref, y.float()) < 3e-3
+    gated(f"groupnorm {(C, HW, silu)}", gates.gn_gate(y, x, gamma, beta, G, silu))
+    tab = ops.groupnorm_table(g(x, dev), g(gamma, dev), g(beta, dev), G, 1e-5)
+    gated(f"groupnorm table {(C, HW)}", gates.gn_stats_ratio(tab, x, gamma, beta, G))
 
 
 @pytest.mark.parametrize("B,H,W,C,O,res,sc,gn", [(1, 16, 16, 64, 128, False, 0, True),     # one tile: every border is padding
@@ -759,6 +813,8 @@ def test_conv3x3_gn_halo(dev, B, H, W, C, O, res, sc, gn):
                              x2=g(x2, dev) if sc else None, bias2=g(bs, dev) if sc else None, stats_groups=G)
     assert y.shape == ref.shape
     assert rel_l2(ref, y.float()) < TOL_SINGLE_OP
+    if not gn and not sc:  # (behind a fused GroupNorm the conv's operand is the kernel's own rounding of it: no per-element reference)
+        gated(f"conv halo {(B, H, W, C, O)}", gates.conv_gate(y.float().cpu(), x, w, b, BF, "plain", r))
     # the unfused device path
     actd = ops.groupnorm(xd, g(gamma, dev), g(beta, dev), G, eps, True) if gn else xd
     if sc:
@@ -814,6 +870,8 @@ def test_conv256v4_equals_conv_halo(dev, B, H, W, C, O, res, gn, ups):
             ops.tune("conv_v4", 1)
     y0, y1 = (outs[0][0], outs[2][0]) if sg else (outs[0], outs[2])
     assert rel_l2(ref, y1.float()) < TOL_SINGLE_OP
+    if not gn:  # (each side against fp64; behind a fused GroupNorm the conv's operand is the kernel's own rounding of it: no per-element reference)
+        gated(f"conv halo / conv256v4 {(B, H, W, C, O, ups)}", gates.conv_gate([y0.float().cpu(), y1.float().cpu()], x, w, b, BF, "ups" if ups else "plain", r))
     assert torch.equal(y0, y1)
     if sg:
         assert rel_l2(outs[0][1].double().cpu(), outs[2][1].double().cpu()) < 1e-6
@@ -830,6 +888,7 @@ def test_conv3x3_halo_upsample(dev):
     y = ops.conv3x3_gn(g(x, dev), g(w, dev).reshape(O, -1), g(b, dev), gn_table=None, upsample=True)
     assert y.shape == ref.shape == (B, 2 * Hs, 2 * Ws, O)
     assert rel_l2(ref, y.float()) < TOL_SINGLE_OP
+    gated("conv halo upsample", gates.conv_gate(y.float().cpu(), x, w, b, BF, "ups"))
 
 
 def test_conv_out_image_tail_halo(dev):
