@@ -262,6 +262,11 @@ SIGNATURES = {
     "dk_mmdit_set_flux_control_net": (_i32, [_vp, _i32]),
     "dk_mmdit_set_flux_control_taps": (_i32, [_vp, _vp, _i32, _i32, _f32]),
     "dk_ln_modulate_add_joint_bf16": (_i32, [_vp, _i32, _vp, _i32, _f32, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp]),
+    # FLUX IP-Adapter: the engine's setter / hoist / scale and the decoupled image-prompt attention kernel
+    "dk_mmdit_set_ip_adapter": (_i32, [_vp, _i32, _i32]),
+    "dk_mmdit_cache_ip_tokens": (_i32, [_vp, _vp, _i32, _vp]),
+    "dk_mmdit_set_ip_scale": (_i32, [_vp, _f32]),
+    "dk_ip_attention_bf16": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp]),
     "dk_image_mask_out_f32": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "dk_fill_condition_tokens": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "dk_vae_create": (_i32, [C.POINTER(dk_vae_config), C.POINTER(_vp)]),

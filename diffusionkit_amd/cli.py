@@ -134,6 +134,14 @@ def build_parser(model_versions: Sequence[str]) -> argparse.ArgumentParser:
     p.add_argument("--ckpt", action="append", default=[], metavar="KEY=PATH",
                    help="Further local checkpoint parts (vae_decoder, vae_encoder, clip_l, clip_g, t5, t5_tokenizer, "
                         "tokenizer_l=vocab.json,merges.txt, tokenizer_g=...). Repeatable.")
+    p.add_argument("--ip-adapter", type=str, default=None, metavar="PATH",
+                   help="A FLUX IP-Adapter in XLabs-AI's layout (flux-ip-adapter: 4 tokens from a CLIP ViT-L/14 image embedding, decoupled attention "
+                        "in the double blocks): a .safetensors file; FLUX versions only. Needs --ip-adapter-embeds. Not together with --fp8, "
+                        "--controlnet, --block-cache, --reference-image-path or --condition (the CLI runs FLUX without CFG). The vision tower is not part of this "
+                        "build. Verified as arithmetic only: the key table has not been run against a real file.")
+    p.add_argument("--ip-adapter-embeds", type=str, default=None, metavar="FILE.npy",
+                   help="With --ip-adapter: the prepared CLIP image embedding(s) of the image prompt, a .npy array [768] or [1, 768].")
+    p.add_argument("--ip-adapter-scale", type=float, default=None, metavar="S", help="With --ip-adapter: the scale of the adapter's output (default 1.0).")
     p.add_argument("--fp8", choices=("quality", "speed"), default=None,
                    help="Run the transformer blocks on the fp8 MFMA path (FLUX versions only). quality: the first double-stream "
                         "blocks keep bf16 Linears; speed: every block Linear in fp8.")
@@ -282,12 +290,31 @@ def resolve(args) -> dict:
             r["controlnet_scale"] = cn["controlnet_scale"]
         if cn["controlnet_interval"] is not None:
             r["controlnet_interval"] = tuple(cn["controlnet_interval"])
+    ipa = {k: getattr(args, k, None) for k in ("ip_adapter", "ip_adapter_embeds", "ip_adapter_scale")}
+    if any(v is not None for v in ipa.values()):
+        if ipa["ip_adapter"] is None:
+            raise ValueError("--ip-adapter-embeds / --ip-adapter-scale need --ip-adapter")
+        if ipa["ip_adapter_embeds"] is None:
+            raise ValueError("--ip-adapter needs --ip-adapter-embeds: the prepared image embedding of the image prompt (the vision tower is not built)")
+        if "FLUX" not in args.model_version:
+            raise ValueError(f"--ip-adapter needs a FLUX model version, not {args.model_version}: SD3 and SD3.5 IP-Adapters are not built")
+        if getattr(args, "fp8", None):
+            raise ValueError("--ip-adapter cannot run together with --fp8")
+        for key, flag in (("controlnet_ckpt", "--controlnet"), ("block_cache", "--block-cache"), ("reference_image_path", "--reference-image-path"),
+                          ("condition", "--condition")):
+            if r.get(key) is not None:
+                raise ValueError(f"--ip-adapter cannot run together with {flag}")
+        r["ip_adapter_ckpt"] = ipa["ip_adapter"]
+        r["ip_adapter_image_embeds"] = ipa["ip_adapter_embeds"]
+        if ipa["ip_adapter_scale"] is not None:
+            r["ip_adapter_scale"] = ipa["ip_adapter_scale"]
     return r
 
 
 SKIP_LAYER_KEYS = ("skip_layer_guidance", "skip_layers", "skip_layer_interval")  # keywords of generate_image that ``resolve`` sets together
 PAG_KEYS = ("pag_scale", "pag_layers", "pag_interval")  # the same, perturbed-attention guidance
 CONTROLNET_KEYS = ("controlnet_image_path", "controlnet_scale", "controlnet_interval")  # the same, SD3 ControlNet (the constructor takes controlnet_ckpt)
+IP_ADAPTER_KEYS = ("ip_adapter_image_embeds", "ip_adapter_scale")  # the same, FLUX IP-Adapter (the constructor takes ip_adapter_ckpt)
 # argparse destination -> keyword of generate_image
 GUIDANCE_FLAGS = {"guidance": "guidance", "guidance_rescale": "guidance_rescale", "apg_eta": "apg_eta", "apg_norm_threshold": "apg_norm_threshold",
                   "apg_momentum": "apg_momentum", "guidance_interval": "guidance_interval"}
@@ -316,7 +343,12 @@ def main(argv: Optional[Sequence[str]] = None, pipeline_overrides: Optional[dict
         extra["controlnet_ckpt"] = r["controlnet_ckpt"]
     if "controlnet_config" in r:
         extra["controlnet_config"] = r["controlnet_config"]
-    cond_kw = {key: r[key] for key in ("condition_image_path", "condition_mask_path", *CONTROLNET_KEYS) if key in r}
+    if "ip_adapter_ckpt" in r:
+        extra["ip_adapter_ckpt"] = r["ip_adapter_ckpt"]
+    cond_kw = {key: r[key] for key in ("condition_image_path", "condition_mask_path", *CONTROLNET_KEYS, *IP_ADAPTER_KEYS) if key in r}
+    if "ip_adapter_image_embeds" in cond_kw:  # (the file is read here: generate_image takes arrays)
+        import numpy as np
+        cond_kw["ip_adapter_image_embeds"] = np.load(cond_kw["ip_adapter_image_embeds"], allow_pickle=False)
     sd = pipeline_class(w16=True, shift=r["shift"], use_t5=args.t5, model_version=args.model_version,
                         low_memory_mode=r["low_memory_mode"], a16=True, local_ckpt=checkpoint_dict(args.local_ckpt, args.ckpt),
                         device=args.device, **extra)

@@ -203,6 +203,44 @@ def flux_controlnet_config(n_double: int, n_single: int, base: Optional[MMDiTCon
     return out
 
 
+@dataclass(frozen=True)
+class IPAdapterConfig:
+    """FLUX IP-Adapter (XLabs-AI flux-ip-adapter as diffusers runs it; no reference counterpart): a pipeline-level setting, not part of the model's
+    configuration -- the engine learns ``ip_adapter_tokens`` and ``ip_adapter_dim`` through dk_mmdit_set_ip_adapter.  The projection model maps one
+    image embedding [embed_dim] to ``ip_adapter_tokens`` tokens of ``ip_adapter_dim`` features (Linear, reshape, LayerNorm); every double block of
+    the model owns a to_k_ip / to_v_ip Linear(ip_adapter_dim -> hidden_size)."""
+    ip_adapter_tokens: int = 4
+    ip_adapter_dim: int = 4096
+    embed_dim: int = 768  # CLIP ViT-L/14 image_embeds
+    norm_eps: float = 1e-5
+
+
+FLUX_IP_ADAPTER = IPAdapterConfig()
+
+
+def validate_ip_adapter(cfg: MMDiTConfig, ip: IPAdapterConfig) -> None:
+    """The rule dk_mmdit_set_ip_adapter enforces, in the host's words: the FLUX family with bf16 Linears and activations, head_dim 128, QK-norm, no
+    condition width, not a ControlNet; 1 .. 16 tokens of a width that is a multiple of 64."""
+    if cfg.pos_embed_type != PositionalEncoding.PreSDPARope or cfg.depth_multimodal < 1:
+        raise ValueError("an IP-Adapter needs the FLUX family: RoPE without a learned positional table and at least one double block "
+                         "(SD3 and SD3.5 IP-Adapters are not built)")
+    if cfg.weight_dtype == "fp8_e4m3":
+        raise ValueError("an IP-Adapter cannot be combined with fp8 Linears: the fp8 LayerNorm kernels take no tap")
+    if cfg.activation_dtype != "bfloat16" or cfg.head_dim != 128 or not cfg.use_qk_norm:
+        raise ValueError("an IP-Adapter needs bfloat16 activations, head_dim 128 and QK-norm weights")
+    if cfg.condition_features != 0 or cfg.control_net or cfg.control_net_flux or cfg.dual_attention_blocks != 0:
+        raise ValueError("an IP-Adapter cannot be combined with a condition width, a ControlNet configuration or dual attention blocks")
+    if not 1 <= ip.ip_adapter_tokens <= 16:
+        raise ValueError(f"ip_adapter_tokens = {ip.ip_adapter_tokens}: must lie in [1, 16] (InstantX's 128-token adapters are not built)")
+    if ip.ip_adapter_dim <= 0 or ip.ip_adapter_dim % 64 != 0 or ip.embed_dim <= 0:
+        raise ValueError(f"ip_adapter_dim = {ip.ip_adapter_dim}: must be a positive multiple of 64, with a positive embed_dim")
+
+
+def tiny_ip_adapter(tokens: int = 4, dim: int = 256, embed_dim: int = 64) -> IPAdapterConfig:
+    """IP-Adapter small enough for the CPU oracle beside a ``tiny_flux`` model (whose hidden size its K / V Linears take from the model)."""
+    return IPAdapterConfig(ip_adapter_tokens=tokens, ip_adapter_dim=dim, embed_dim=embed_dim)
+
+
 def validate_condition_features(cfg: MMDiTConfig) -> None:
     """0, or a positive multiple of 64 on a configuration without the learned positional table and with bf16 activations (the rule
     dk_mmdit_set_condition_width enforces)."""

@@ -379,6 +379,13 @@ extern "C" int dk_ln_modulate_add_joint_bf16(void* x, int32_t ldx, const void* t
                                          eps, S_(stream));
 }
 
+extern "C" int dk_ip_attention_bf16(const void* qkv, int32_t ldq, int32_t seg_len, int32_t seg_stride, int32_t first_row, const void* qn, const void* k,
+                                    const void* v, int32_t ldkv, int32_t B, int32_t N, int32_t h, int32_t D, float scale, float eps, void* out,
+                                    void* stream) {
+  return dk_launch_ip_attention((const bf16_t*)qkv, ldq, seg_len, seg_stride, first_row, (const bf16_t*)qn, (const bf16_t*)k, (const bf16_t*)v, ldkv, B, N, h,
+                                D, scale, eps, (bf16_t*)out, S_(stream));
+}
+
 static int block_probe(int dtype,const void* x, int ldx, int x_seg_len, int x_seg_stride, void* d, const void* d_ref, float* row_partials,
                        float* probe, int M, int h, int rows_per_batch, void* stream) {
   return DK_EL(dtype, dk_launch_block_probe)((const bf16_t*)x, ldx, x_seg_len, x_seg_stride, (bf16_t*)d, (const bf16_t*)d_ref, row_partials, probe, M, h,

@@ -202,6 +202,12 @@ int dk_launch_ln_modulate_add_joint(bf16_t* x, int ldx, const bf16_t* tap, int l
                                     int h, const bf16_t* shift, const bf16_t* scale, int mod_stride, int seg_len, int x_seg_len, int x_seg_stride,
                                     float eps, hipStream_t stream);
 
+// decoupled image-prompt attention (FLUX IP-Adapter; bf16, D = 128, 1 <= N <= 16; ip_attention.hip): out [B * seg_len, h] dense = softmax over the N
+// keys K[b] of scale * q_n . k, times V[b]; q_n = the QK-normed, NOT rotated q columns (the first h of ldq) of rows first_row .. + seg_len - 1 of every
+// batch row of qkv [B, seg_stride, ldq]; K, V: [B, N, h] at ldkv elements per row
+int dk_launch_ip_attention(const bf16_t* qkv, int ldq, int seg_len, int seg_stride, int first_row, const bf16_t* qn, const bf16_t* K, const bf16_t* V,
+                           int ldkv, int B, int N, int h, int D, float scale, float eps, bf16_t* out, hipStream_t stream);
+
 // optional HIP-event timing of the dominant kernels (profile.hip); cls: 0 GEMM, 1 conv, 2 attention, 3 fp8 GEMM
 void dk_prof_begin(int cls, double work, hipStream_t st);
 void dk_prof_end(hipStream_t st);

@@ -133,10 +133,23 @@ struct dk_mmdit {
   bool flux_tapped() const { return n_dtaps + n_staps > 0; }
   bool tapped() const { return n_taps > 0 || flux_tapped(); }
   static int flux_tap_of(int g, int n, int depth) { return g / ((depth + n - 1) / n); }
+  // FLUX IP-Adapter (dk_mmdit_set_ip_adapter; include/dk_hip.h): ip_n image-prompt tokens of ip_c features per image.  ipkv_w / ipkv_b: the
+  // adapter's to_k_ip / to_v_ip of every double block as ONE matrix [depth_multimodal * 2h, ip_c] (rows [i 2h, i 2h + h) block i's keys, the next
+  // h its values) and its bias.  IPKV [B * ip_n, depth_multimodal * 2h]: their step-invariant projections (dk_mmdit_cache_ip_tokens) -- block i's
+  // keys of image b at rows b ip_n .., columns i 2h .., its values h columns further.  IP [B * S_i, h]: the adapter's output of the double block
+  // that ran last, added with ip_scale in the LayerNorm launch that reads the image rows next (the tap slot) -- one buffer for all blocks
+  int ip_n = 0, ip_c = 0;
+  const bf16_t *ipkv_w = nullptr, *ipkv_b = nullptr;
+  bf16_t *IPKV = nullptr, *IP = nullptr;
+  bool ip_ready = false;
+  float ip_scale = 0.f;
+  bool ip_active() const { return ip_n > 0 && ip_scale != 0.f; }
+  float tap_s() const { return ip_active() ? ip_scale : tap_scale; }  // (taps and the adapter are never set together)
   // the tap added behind block g of the global order (in front of whatever reads the image rows next), or null
   const bf16_t* tap_behind(int g) const {
     const int nd = cfg.depth_multimodal;
     const size_t tap = (size_t)B * S_i * cfg.hidden_size;
+    if (ip_active()) return g >= 0 && g < nd ? IP : nullptr;  // (the adapter's output behind every double block, nothing behind a single one)
     if (g < 0 || !tapped()) return nullptr;
     if (n_taps > 0) return g < nd - 1 ? taps + (size_t)tap_of(g) * tap : nullptr;  // (SD3: nothing behind the last block)
     if (g < nd) return n_dtaps > 0 ? taps + (size_t)flux_tap_of(g, n_dtaps, nd) * tap : nullptr;
@@ -227,6 +240,7 @@ extern "C" int dk_mmdit_set_dual_attention(dk_mmdit* m, int32_t n_blocks) {
     DK_REQUIRE(m->cfg.depth_unified == 0 && m->cfg.fp8_linears == 0,
                "dual attention blocks are the SD3 family's (MMDiT-X): depth_unified == 0 and fp8_linears == 0");
     DK_REQUIRE(!m->control_net && !m->tapped(), "dual attention blocks cannot be set on a control-net engine or while control taps are set");
+    DK_REQUIRE(m->ip_n == 0, "dual attention blocks cannot be set on an engine with an IP-Adapter (dk_mmdit_set_ip_adapter)");
   }
   m->n_dual = n_blocks;
   m->mod_ready = false;
@@ -397,6 +411,24 @@ static int mmdit_resolve(dk_mmdit* m) {
   }
   for (int i = 0; i < m->cfg.depth_unified; ++i)
     DK_TRY(resolve_stream(m, "unified_transformer_blocks." + std::to_string(i) + ".transformer_block", m->single[i], true, false, m->fp8()));
+  m->ipkv_w = m->ipkv_b = nullptr;
+  if (m->ip_n > 0) {  // the adapter's Linears: bound by their own names, read as one matrix by one GEMM (dk_mmdit_cache_ip_tokens)
+    const size_t hh = (size_t)m->h();
+    for (int i = 0; i < m->cfg.depth_multimodal; ++i) {
+      const std::string b = "ip_adapter." + std::to_string(i);
+      const bf16_t *kw, *kb, *vw, *vb;
+      DK_TRY(need(n, b + ".to_k_ip.weight", &kw));
+      DK_TRY(need(n, b + ".to_k_ip.bias", &kb));
+      DK_TRY(need(n, b + ".to_v_ip.weight", &vw));
+      DK_TRY(need(n, b + ".to_v_ip.bias", &vb));
+      if (i == 0) { m->ipkv_w = kw; m->ipkv_b = kb; }
+      if (kw != m->ipkv_w + (size_t)i * 2 * hh * m->ip_c || vw != kw + hh * m->ip_c || kb != m->ipkv_b + (size_t)i * 2 * hh || vb != kb + hh) {
+        dk_set_error("the IP-Adapter's tensors must be views of one stacked [depth_multimodal * 2h, token_dim] matrix and one [depth_multimodal * 2h] bias, block i's "
+                     "to_k_ip rows at i * 2h and its to_v_ip rows h further: " + b);
+        return -3;
+      }
+    }
+  }
   m->norm_max_ready = false;  // (the StreamW records are new: maxima 0, no bound, until norm_weight_maxima has read the weights)
   m->resolved = true;
   return 0;
@@ -472,6 +504,11 @@ static size_t mmdit_carve(dk_mmdit* m, Carver& c, int B, int Hl, int Wl, int S_t
     m->QKV2 = (bf16_t*)c.take(Mi * 3 * h * 2);
     m->ATT2 = (bf16_t*)c.take(Mi * h * 2);
   }
+  m->IPKV = m->IP = nullptr;
+  if (m->ip_n > 0) {  // (the same: no take without an IP-Adapter)
+    m->IPKV = (bf16_t*)c.take((size_t)m->cfg.depth_multimodal * B * m->ip_n * 2 * h * 2);
+    m->IP = (bf16_t*)c.take((size_t)B * S_i * h * 2);
+  }
   return c.off;
 }
 
@@ -522,6 +559,7 @@ extern "C" int dk_mmdit_prepare(dk_mmdit* m, int32_t batch, int32_t latent_h, in
   m->ctrl_ready = false;
   m->taps = nullptr; m->n_taps = 0; m->tap_scale = 0.f;  // (the caller's taps had the previous problem's shape: set again after prepare)
   m->n_dtaps = m->n_staps = 0;
+  m->ip_ready = false;  // (the cache lives in the workspace that was just carved; the scale stays)
   m->bc_reset();
   return 0;
 }
@@ -533,6 +571,7 @@ extern "C" int dk_mmdit_set_reference_grid(dk_mmdit* m, int32_t ref_latent_h, in
     const int p = m->cfg.patch_size;
     DK_REQUIRE(m->cond_f == 0, "a reference grid and a condition width cannot be set at the same time");
     DK_REQUIRE(!m->control_net && !m->tapped(), "a reference grid cannot be set on a control-net engine or while control taps are set");
+    DK_REQUIRE(m->ip_n == 0, "a reference grid cannot be set on an engine with an IP-Adapter (dk_mmdit_set_ip_adapter)");
     DK_REQUIRE(m->cfg.use_rope, "a reference grid needs RoPE (use_rope = 1, the FLUX family): the reference rows are told from the image rows by their position index");
     DK_REQUIRE(ref_latent_h > 0 && ref_latent_w > 0 && ref_latent_h % p == 0 && ref_latent_w % p == 0,
                "reference latent sides must both be positive multiples of the patch size, or both 0 (off)");
@@ -572,6 +611,7 @@ extern "C" int dk_mmdit_set_condition_width(dk_mmdit* m, int32_t cond_features) 
     DK_REQUIRE(m->cfg.use_pos_embed == 0, "a condition width needs use_pos_embed == 0 (the FLUX family): the residual operand of the x_embedder launch carries the condition's share");
     DK_REQUIRE(m->ref_h == 0 && m->ref_w == 0, "a condition width and a reference grid cannot be set at the same time");
     DK_REQUIRE(m->dtype == DK_DTYPE_BF16, "a condition width needs bf16 activations");
+    DK_REQUIRE(m->ip_n == 0, "a condition width cannot be set on an engine with an IP-Adapter (dk_mmdit_set_ip_adapter)");
     DK_REQUIRE(!m->control_net && !m->tapped(), "a condition width cannot be set on a control-net engine or while control taps are set");
   }
   if (m->cond_f != cond_features) m->prepared = false;  // (another carve: dk_mmdit_prepare must follow)
@@ -653,7 +693,7 @@ static int mmdit_final_layer(dk_mmdit* m, const bf16_t* mod_step, bf16_t* tokens
   // (FLUX ControlNet taps: the residual behind the last block of the model lands here -- the image rows alone, every one of them tapped)
   const bf16_t* tap = m->tap_behind(m->cfg.depth_multimodal + m->cfg.depth_unified - 1);
   if (tap != nullptr)
-    DK_TRY(dk_launch_ln_modulate_add_joint(m->X + (size_t)S_t * h, h, tap, h, m->tap_scale, S_i, 0, m->XN, h, B * S_i, h, mod_fin, mod_fin + h, mod_stride,
+    DK_TRY(dk_launch_ln_modulate_add_joint(m->X + (size_t)S_t * h, h, tap, h, m->tap_s(), S_i, 0, m->XN, h, B * S_i, h, mod_fin, mod_fin + h, mod_stride,
                                            S_i, S_i, S, m->cfg.layer_norm_eps, st));
   else
     DK_TRY(DK_EL(L.dtype, dk_launch_ln_modulate)(m->X + (size_t)S_t * h, h, m->XN, h, B * S_i, h, mod_fin, mod_fin + h, mod_stride, S_i, S_i, S,
@@ -762,7 +802,7 @@ static int double_block_bf16(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t
   else if (m->tap_behind(i - 1) != nullptr)
     // ControlNet taps (dk_mmdit_set_control_taps / dk_mmdit_set_flux_control_taps): the residual behind block i - 1 is added here, in front of block
     // i -- the same stream state -- in the pass that reads every image row anyway; the image rows are rewritten in place, the text job is the plain one
-    DK_TRY(DK_EL(L.dtype, dk_launch_ln_modulate2_add)(X_img.p, m->tap_behind(i - 1), h, m->tap_scale, XN_img.p, Mi, mod_img,
+    DK_TRY(DK_EL(L.dtype, dk_launch_ln_modulate2_add)(X_img.p, m->tap_behind(i - 1), h, m->tap_s(), XN_img.p, Mi, mod_img,
                                                       mod_img + h, S_i, X_txt.p, XN_txt.p, Mt, mod_txt, mod_txt + h, S_t, h, h, h, mod_stride, S, S,
                                                       cf.layer_norm_eps, st));
   else
@@ -780,6 +820,12 @@ static int double_block_bf16(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t
   if (!kf)
     DK_TRY(DK_EL(L.dtype, dk_launch_qk_norm_rope2)(m->QKV + (size_t)S_t * 3 * h, Mi, wi.qn, wi.kn, S_i, S_t, m->QKV, Mt, wt.qn, wt.kn, S_t, 0, 3 * h, 0, h,
                                    cf.num_heads, m->D(), 1e-6f, c.rope, S, st, fuse_q()));
+  // FLUX IP-Adapter (dk_mmdit_set_ip_adapter): the image rows' q columns still hold the raw projection (need_ip_adapter: the attention kernel norms
+  // and rotates in its Q load), which is the operand the published definition attends from once QK-normed.  The output waits in IP for the
+  // LayerNorm launch that reads the image rows next (tap_behind(i)); that launch ran for block i - 1's output before this one overwrites it
+  if (m->ip_active())
+    DK_TRY(dk_launch_ip_attention(m->QKV, 3 * h, S_i, S, S_t, wi.qn, m->IPKV + (size_t)i * 2 * h, m->IPKV + (size_t)i * 2 * h + h, cf.depth_multimodal * 2 * h,
+                                  c.B, m->ip_n, h, m->D(), c.scale, 1e-6f, m->IP, st));
   // attn2's projection on the second modulation, a launch of its own: it has the image job's M and fills the chip as that one does, and the
   // pair above stays the launch of a plain block.  Its QKNorm follows the same switches as the main attention's, without a RoPE table
   const bool kf2 = dual && fuse_k(wi.kn2);
@@ -858,7 +904,7 @@ static int single_block_bf16(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t
   // FLUX ControlNet taps (dk_mmdit_set_flux_control_taps): the residual behind the block in front of this one -- single block i - 1, or the last
   // double block -- is added to the image rows of the joint stream in this pass; the text rows take the plain path of the same kernel
   if (const bf16_t* tap = m->tap_behind(cf.depth_multimodal + i - 1))
-    DK_TRY(dk_launch_ln_modulate_add_joint(m->X, h, tap, h, m->tap_scale, S, c.S_t, m->XN, h, M, h, mod, mod + h, c.mod_stride, S, M, 0, cf.layer_norm_eps, st));
+    DK_TRY(dk_launch_ln_modulate_add_joint(m->X, h, tap, h, m->tap_s(), S, c.S_t, m->XN, h, M, h, mod, mod + h, c.mod_stride, S, M, 0, cf.layer_norm_eps, st));
   else
     DK_TRY(DK_EL(L.dtype, dk_launch_ln_modulate)(m->X, h, m->XN, h, M, h, mod, mod + h, c.mod_stride, S, M, 0, cf.layer_norm_eps, st));
   {  // linear1: [q|k|v] -> QKV, gelu(fc1) -> CAT[:, h:], one pass over the modulated activations
@@ -1061,6 +1107,7 @@ extern "C" int dk_mmdit_set_skip_layers(dk_mmdit* m, const int32_t* blocks, int3
   DK_REQUIRE(m->cfg.depth_unified == 0, "skip layers are the SD3 family's: depth_unified must be 0");
   DK_REQUIRE(m->cfg.fp8_linears == 0, "skip layers cannot be set on an engine with fp8_linears");
   DK_REQUIRE(m->ref_h == 0 && m->ref_w == 0 && m->cond_f == 0, "skip layers cannot be set while a reference grid or a condition width is set");
+  DK_REQUIRE(m->ip_n == 0, "skip layers cannot be set on an engine with an IP-Adapter (dk_mmdit_set_ip_adapter)");
   DK_REQUIRE(!m->perturbed(), "skip layers cannot be set while perturbed attention is set (dk_mmdit_set_perturbed_attention): there is one fork");
   DK_REQUIRE(!m->control_net && !m->tapped(), "skip layers cannot be set on a control-net engine or while control taps are set: the fork rows would need taps of their own");
   std::vector<int32_t> v(blocks, blocks + n_blocks);
@@ -1084,6 +1131,7 @@ extern "C" int dk_mmdit_set_perturbed_attention(dk_mmdit* m, const int32_t* bloc
   DK_REQUIRE(m->cfg.depth_unified == 0, "perturbed attention is the SD3 family's: depth_unified must be 0");
   DK_REQUIRE(m->cfg.fp8_linears == 0, "perturbed attention cannot be set on an engine with fp8_linears");
   DK_REQUIRE(m->ref_h == 0 && m->ref_w == 0 && m->cond_f == 0, "perturbed attention cannot be set while a reference grid or a condition width is set");
+  DK_REQUIRE(m->ip_n == 0, "perturbed attention cannot be set on an engine with an IP-Adapter (dk_mmdit_set_ip_adapter)");
   DK_REQUIRE(!m->slg(), "perturbed attention cannot be set while skip layers are set (dk_mmdit_set_skip_layers): there is one fork");
   DK_REQUIRE(!m->control_net && !m->tapped(), "perturbed attention cannot be set on a control-net engine or while control taps are set: the fork rows would need taps of their own");
   std::vector<int32_t> v(blocks, blocks + n_blocks);
@@ -1128,6 +1176,7 @@ extern "C" int dk_mmdit_set_flux_control_net(dk_mmdit* m, int32_t on) {
     DK_REQUIRE(m->cfg.fp8_linears == 0, "a FLUX control-net engine cannot have fp8 Linears");
     DK_REQUIRE(m->dtype == DK_DTYPE_BF16, "a FLUX control-net engine needs bf16 activations");
     DK_REQUIRE(m->cfg.depth_multimodal >= 1 && m->cfg.depth_unified >= 0, "a FLUX control-net engine needs at least one double block");
+    DK_REQUIRE(m->ip_n == 0, "a FLUX control-net engine cannot have an IP-Adapter (dk_mmdit_set_ip_adapter)");
     DK_REQUIRE(m->n_dual == 0 && m->ref_h == 0 && m->ref_w == 0 && m->cond_f == 0,
                "a control-net engine cannot have dual attention blocks, a reference grid or a condition width");
     DK_REQUIRE(!m->bc_on && !m->slg() && !m->perturbed() && !m->tapped(),
@@ -1191,6 +1240,7 @@ extern "C" int dk_mmdit_set_flux_control_taps(dk_mmdit* m, const void* taps, int
   DK_REQUIRE(m->dtype == DK_DTYPE_BF16, "FLUX control taps need bf16 activations");
   DK_REQUIRE(!m->control_net, "control taps cannot be set on a control-net engine: it writes taps, the main engine reads them");
   DK_REQUIRE(m->n_taps == 0, "FLUX control taps cannot be set while SD3 control taps are set (dk_mmdit_set_control_taps)");
+  DK_REQUIRE(m->ip_n == 0, "FLUX control taps cannot be set on an engine with an IP-Adapter (dk_mmdit_set_ip_adapter): the LayerNorm launch has one tap operand");
   DK_REQUIRE(n_double_taps >= 0 && n_double_taps <= nd, "FLUX control taps: n_double_taps must lie in [0, depth_multimodal]");
   DK_REQUIRE(n_single_taps >= 0 && n_single_taps <= ns, "FLUX control taps: n_single_taps must lie in [0, depth_unified]");
   DK_REQUIRE(((uintptr_t)taps & 15) == 0, "control taps must be 16-byte aligned");
@@ -1245,6 +1295,73 @@ extern "C" int dk_mmdit_control_forward(dk_mmdit* m, const void* tokens_in, cons
   return 0;
 }
 
+// ---- FLUX IP-Adapter (include/dk_hip.h) -------------------------------------------------------------------------------------------------
+extern "C" int dk_mmdit_set_ip_adapter(dk_mmdit* m, int32_t n_tokens, int32_t token_dim) {
+  DK_REQUIRE(m != nullptr, "null handle");
+  DK_REQUIRE(!m->resolved && !m->prepared, "dk_mmdit_set_ip_adapter is legal only before the weights are resolved (the first dk_mmdit_prepare)");
+  if (n_tokens != 0 || token_dim != 0) {
+    DK_REQUIRE(m->cfg.use_rope != 0 && m->cfg.use_pos_embed == 0 && m->cfg.depth_multimodal >= 1,
+               "an IP-Adapter is the FLUX family's: use_rope != 0, use_pos_embed == 0 and at least one double block (SD3 geometry is refused)");
+    DK_REQUIRE(m->cfg.fp8_linears == 0, "an IP-Adapter cannot be set on an engine with fp8 Linears: the fp8 LayerNorm kernels take no tap");
+    DK_REQUIRE(m->dtype == DK_DTYPE_BF16, "an IP-Adapter needs bf16 activations");
+    DK_REQUIRE(m->D() == 128 && m->cfg.use_qk_norm != 0, "an IP-Adapter needs head_dim 128 and QK-norm weights (its queries are the block's QK-normed image queries)");
+    DK_REQUIRE(!m->control_net, "an IP-Adapter cannot be set on a control-net engine");
+    DK_REQUIRE(!m->tapped(), "an IP-Adapter cannot be set while control taps are set: the LayerNorm launch has one tap operand");
+    DK_REQUIRE(!m->bc_on, "an IP-Adapter cannot be set while the block cache is on (dk_mmdit_set_block_cache)");
+    DK_REQUIRE(m->ref_h == 0 && m->ref_w == 0, "an IP-Adapter cannot be set while a reference grid is set");
+    DK_REQUIRE(m->cond_f == 0, "an IP-Adapter cannot be set while a condition width is set");
+    DK_REQUIRE(!m->slg() && !m->perturbed() && m->n_dual == 0, "an IP-Adapter cannot be set with skip layers, perturbed attention or dual attention blocks");
+    DK_REQUIRE(n_tokens >= 1 && n_tokens <= 16, "an IP-Adapter has between 1 and 16 image-prompt tokens per image");
+    DK_REQUIRE(token_dim > 0 && token_dim % 64 == 0 && token_dim <= (1 << 16), "the IP-Adapter's token width must be a positive multiple of 64");
+  }
+  m->ip_n = n_tokens; m->ip_c = token_dim;
+  m->ip_ready = false;
+  return 0;
+}
+extern "C" int dk_mmdit_cache_ip_tokens(dk_mmdit* m, const void* tokens, int32_t per_image, void* stream) {
+  DK_REQUIRE(m && m->prepared && tokens, "prepare must precede cache_ip_tokens");
+  DK_REQUIRE(m->ip_n > 0, "cache_ip_tokens needs an IP-Adapter: dk_mmdit_set_ip_adapter before the first dk_mmdit_prepare");
+  const int N = m->ip_n, Ck = m->ip_c, ldkv = m->cfg.depth_multimodal * 2 * m->h();
+  // every block's keys and values from ONE matrix; one launch per batch row (M = N rows), as the other hoists do: a shared prompt gives every
+  // batch row the bits a per-image copy of it would.  No split workspace.  A previous cache is overwritten
+  for (int b = 0; b < m->B; ++b) {
+    const bf16_t* src = (const bf16_t*)tokens + (per_image ? (size_t)b * N * Ck : 0);
+    DK_TRY(dk_launch_gemm(Linear(m->dtype, dense(src, Ck), m->ipkv_w, m->ipkv_b, dense(m->IPKV + (size_t)b * N * ldkv, ldkv), N, ldkv, Ck, DK_EPI_BIAS), S_(stream)));
+  }
+  m->ip_ready = true;
+  return 0;
+}
+extern "C" int dk_mmdit_set_ip_scale(dk_mmdit* m, float scale) {
+  DK_REQUIRE(m != nullptr, "null handle");
+  if (scale != 0.f) {
+    DK_REQUIRE(m->ip_n > 0, "set_ip_scale needs an IP-Adapter: dk_mmdit_set_ip_adapter before the first dk_mmdit_prepare");
+    DK_REQUIRE(std::isfinite(scale), "the IP-Adapter's scale must be finite");
+    DK_REQUIRE(!m->tapped(), "the IP-Adapter cannot be switched on while control taps are set: the LayerNorm launch has one tap operand");
+  }
+  m->ip_scale = scale;
+  return 0;
+}
+// what the entries other than dk_mmdit_forward answer while the adapter is active (set, with a scale other than 0)
+static int no_ip_adapter(const dk_mmdit* m, const char* entry) {
+  if (!m->ip_active()) return 0;
+  dk_set_error(std::string(entry) + " cannot run while the IP-Adapter is active (dk_mmdit_set_ip_adapter with a scale other than 0): only dk_mmdit_forward runs it");
+  return -1;
+}
+// ... and what dk_mmdit_forward asks before its first launch: the cache, and image queries that stay raw in QKV behind the q / k / v projection
+static int need_ip_adapter(const dk_mmdit* m) {
+  if (!m->ip_active()) return 0;
+  DK_REQUIRE(m->ip_ready, "an engine with an active IP-Adapter needs dk_mmdit_cache_ip_tokens after dk_mmdit_prepare");
+  DK_REQUIRE(fuse_q() != 0, "the IP-Adapter reads the image queries raw from QKV: dk_tune_set(\"attn_fuse_q\", 0) norms and rotates them there in a pass of its own");
+  // (queries_in_tail is what double_block_bf16's launches follow: with the keys' fused tail off -- "gemm_fuse_k" 0 -- "gemm_fuse_q" 1 finishes nothing
+  // and the queries stay raw)
+  for (int i = 0; i < m->cfg.depth_multimodal; ++i)
+    DK_REQUIRE(!queries_in_tail(m->dimg[i], &m->dtxt[i], false),
+               "the IP-Adapter reads the image queries raw from QKV: dk_tune_set(\"gemm_fuse_q\", 1) norms and rotates them in the projection's tail");
+  DK_REQUIRE(!m->tapped() && !m->bc_on && m->S_r == 0 && m->cond_f == 0 && !m->slg() && !m->perturbed() && m->n_dual == 0,
+             "the IP-Adapter cannot run with control taps, a block cache, a reference grid, a condition width, skip layers, perturbed attention or dual attention blocks");
+  return 0;
+}
+
 // The fork of both features: rows [0, live) alone up to block `first`, there the fork rows become a copy of rows [0, fork_rows), and from there on
 // block g runs on the rows [0, rows_of(g)) -- each group of launches is the driver's for its row count
 template <class RowsOf>
@@ -1284,6 +1401,7 @@ extern "C" int dk_mmdit_forward(dk_mmdit* m, const void* tokens_in, const void* 
   const LaunchCtx L = m->ctx(stream);
   const bf16_t* mod_step = m->MOD + (size_t)step_index * m->B * m->mod_rows() * m->h();
   DK_TRY(no_control_net(m, "dk_mmdit_forward"));
+  DK_TRY(need_ip_adapter(m));
   m->bc_pending = -1;  // (a head without its tail is dropped: this call overwrites the stream it left; R / D_ref stay)
   if (m->slg()) return mmdit_forward_forked(m, tokens_in, text, mod_step, (bf16_t*)tokens_out, L);
   if (m->perturbed()) return mmdit_forward_perturbed(m, tokens_in, text, mod_step, (bf16_t*)tokens_out, L);
@@ -1296,6 +1414,7 @@ extern "C" int dk_mmdit_forward(dk_mmdit* m, const void* tokens_in, const void* 
 extern "C" int dk_mmdit_set_block_cache(dk_mmdit* m, int32_t on) {
   DK_REQUIRE(m != nullptr, "null handle");
   if (on) DK_REQUIRE(!m->control_net && !m->tapped(), "the block cache cannot be switched on on a control-net engine or while control taps are set");
+  if (on) DK_REQUIRE(m->ip_n == 0, "the block cache cannot be switched on on an engine with an IP-Adapter (dk_mmdit_set_ip_adapter)");
   if (m->bc_on != (on != 0)) m->prepared = false;  // (another carve: dk_mmdit_prepare must follow)
   m->bc_on = on != 0;
   m->bc_reset();
@@ -1314,6 +1433,7 @@ static int bc_save_img(const dk_mmdit* m, bf16_t* dst, hipStream_t st) {
 }
 extern "C" int dk_mmdit_forward_head(dk_mmdit* m, const void* tokens_in, const void* text, int32_t step_index, float* probe_out, void* stream) {
   DK_REQUIRE(m && m->prepared && m->mod_ready, "prepare + cache_modulation_params must precede forward_head");
+  DK_TRY(no_ip_adapter(m, "dk_mmdit_forward_head"));  // (in front of the block cache's rule: an engine with an adapter can have no block cache)
   DK_REQUIRE(m->bc_on, "forward_head needs the block cache: dk_mmdit_set_block_cache(m, 1) before dk_mmdit_prepare");
   DK_REQUIRE(probe_out != nullptr, "null argument");
   DK_TRY(no_skip_layers(m, "dk_mmdit_forward_head"));
@@ -1335,6 +1455,7 @@ extern "C" int dk_mmdit_forward_head(dk_mmdit* m, const void* tokens_in, const v
 }
 extern "C" int dk_mmdit_forward_tail(dk_mmdit* m, int32_t step_index, int32_t reuse, void* tokens_out, void* stream) {
   DK_REQUIRE(m && m->prepared && m->mod_ready, "prepare + cache_modulation_params must precede forward_tail");
+  DK_TRY(no_ip_adapter(m, "dk_mmdit_forward_tail"));  // (in front of the block cache's rule, as in dk_mmdit_forward_head)
   DK_REQUIRE(m->bc_on && tokens_out != nullptr, "forward_tail needs the block cache and an output");
   DK_TRY(no_skip_layers(m, "dk_mmdit_forward_tail"));
   DK_TRY(no_control_net(m, "dk_mmdit_forward_tail"));
@@ -1368,6 +1489,7 @@ extern "C" int dk_mmdit_run_blocks(dk_mmdit* m, const void* x_in, void* x_out, i
   DK_REQUIRE(x_in && x_out, "null argument");
   DK_TRY(no_skip_layers(m, "dk_mmdit_run_blocks"));
   DK_TRY(no_control_taps(m, "dk_mmdit_run_blocks"));
+  DK_TRY(no_ip_adapter(m, "dk_mmdit_run_blocks"));
   DK_REQUIRE(step_index >= 0 && step_index < m->n_t, "step index out of range");
   const int total = m->cfg.depth_multimodal + m->cfg.depth_unified;
   DK_REQUIRE(first_block >= 0 && n_blocks >= 1 && first_block + n_blocks <= total, "block range outside the model");

@@ -61,6 +61,8 @@ def generate_sharded(pipe, text: str, seeds: Sequence[int], rank: int, world: in
     ``condition_mask_path`` in their list form are cut the same way, and are only passed on when set.  Returns None for a rank without seeds."""
     if getattr(pipe, "controlnet", None) is not None or any(k.startswith("controlnet_") for k in kw):
         raise ValueError("a ControlNet cannot run under multi-GPU sharding: its per-image control images are not cut with the seeds yet")
+    if getattr(pipe, "ip_adapter_config", None) is not None or any(k.startswith("ip_adapter_") for k in kw):
+        raise ValueError("an IP-Adapter cannot run under multi-GPU sharding: its per-image embeddings are not cut with the seeds yet")
     mine = shard_seeds(seeds, rank, world)
     if not mine:
         return None

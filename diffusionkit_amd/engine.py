@@ -40,7 +40,8 @@ def _require_cuda(t: Tensor, name: str, dtype=None):
 class MMDiTEngine:
     """Drop-in for the reference ``MMDiT`` module on the hot path."""
 
-    def __init__(self, config: MMDiTConfig, packed_weights: Dict[str, Tensor]):
+    def __init__(self, config: MMDiTConfig, packed_weights: Dict[str, Tensor], ip_adapter=None):
+        """``ip_adapter``: a ``config.IPAdapterConfig`` when ``packed_weights`` also holds ``weights.pack_ip_adapter``'s tensors (FLUX family)."""
         self.lib = _lib.load()
         self.config = config
         dev0 = next(iter(packed_weights.values())).device
@@ -140,6 +141,23 @@ class MMDiTEngine:
                                           f"{None if t is None else tuple(t.shape)}")
             self.control_net = True  # (what cache_control_image / control_forward ask)
         self._ctrl_cached = False
+        # FLUX IP-Adapter: token count and width before the weights resolve; the stacked K / V matrix is read through bare pointers, so its layout
+        # is checked here
+        self.ip_adapter = ip_adapter
+        self.ip_scale = 0.0
+        self._ip_cached = False
+        if ip_adapter is not None:
+            from .config import validate_ip_adapter
+            try:
+                validate_ip_adapter(config, ip_adapter)
+            except ValueError as e:
+                raise _lib.DkHipError(str(e)) from None
+            nd, hh, cc = config.depth_multimodal, config.hidden_size, ip_adapter.ip_adapter_dim
+            kvw, kvb = packed_weights.get("ip_adapter.kv.weight"), packed_weights.get("ip_adapter.kv.bias")
+            if kvw is None or kvb is None or tuple(kvw.shape) != (nd * 2 * hh, cc) or tuple(kvb.shape) != (nd * 2 * hh,) or not kvw.is_contiguous():
+                raise _lib.DkHipError(f"ip_adapter.kv.weight / .bias: an engine with an IP-Adapter needs the stacked [{nd * 2 * hh}, {cc}] matrix and "
+                                      f"its [{nd * 2 * hh}] bias (weights.pack_ip_adapter)")
+            _lib.check(self.lib.dk_mmdit_set_ip_adapter(self._h, int(ip_adapter.ip_adapter_tokens), int(cc)), "dk_mmdit_set_ip_adapter")
         # ``set_control_taps`` / ``set_flux_control_taps``: (taps tensor, scale), kept alive while the engine reads it; None: off
         self.control_taps = None
         self.weights = packed_weights  # keep the device tensors alive
@@ -225,6 +243,7 @@ class MMDiTEngine:
         self._ref_cached = False
         self._cond_cached = False
         self._ctrl_cached = False
+        self._ip_cached = False
         self.control_taps = None  # (dk_mmdit_prepare switches taps off: their shape was the previous problem's)
 
     @property
@@ -394,6 +413,27 @@ class MMDiTEngine:
                    "dk_mmdit_set_flux_control_taps")
         self.control_taps = (taps, float(scale))
 
+    # -- FLUX IP-Adapter (include/dk_hip.h; no reference counterpart) ----------------------------------------------------------
+    def ip_tokens_shape(self, per_image: bool = True):
+        return (self._shape[0] if per_image else 1, self.ip_adapter.ip_adapter_tokens, self.ip_adapter.ip_adapter_dim)
+
+    def cache_ip_tokens(self, tokens: Tensor, per_image: bool = False) -> None:
+        """dk_mmdit_cache_ip_tokens: the image prompt's tokens (``ip_adapter_project``), bf16 [n, N, C]; n = batch with ``per_image``, else 1 (one
+        prompt for every batch row).  Every double block's keys and values are computed once here; a later call replaces them."""
+        if self._shape is None or self.ip_adapter is None:
+            raise _lib.DkHipError("cache_ip_tokens() needs an engine built with ip_adapter= and prepare() first")
+        _require_cuda(tokens, "image-prompt tokens", self.dtype)
+        if tuple(tokens.shape) != self.ip_tokens_shape(per_image):
+            raise _lib.DkHipError(f"image-prompt tokens shape {tuple(tokens.shape)} != {self.ip_tokens_shape(per_image)}")
+        _lib.check(self.lib.dk_mmdit_cache_ip_tokens(self._h, tokens.data_ptr(), int(bool(per_image)), _stream()), "dk_mmdit_cache_ip_tokens")
+        self._ip_cached = True
+
+    def set_ip_scale(self, scale: float = 0.0) -> None:
+        """dk_mmdit_set_ip_scale: 0 is off (the plain launches and their bits); with another scale every later ``forward_tokens`` adds
+        ``scale * ip_i`` to the image stream behind double block i.  ``forward_head`` / ``forward_tail`` / ``run_blocks`` are refused while on."""
+        _lib.check(self.lib.dk_mmdit_set_ip_scale(self._h, float(scale)), "dk_mmdit_set_ip_scale")
+        self.ip_scale = float(scale)
+
     def forward_tokens(self, tokens_in: Tensor, text: Optional[Tensor], step_index: int, tokens_out: Optional[Tensor] = None) -> Tensor:
         """MMDiT.__call__ between patchify and unpatchify (mmdit.py:188-252).  ``text=None`` uses ``cache_context``'s result."""
         self._check_forward_args(tokens_in, text, step_index)
@@ -494,6 +534,19 @@ class MMDiTEngine:
             text = text.squeeze(2)
         out = self.forward_tokens(tok, text.to(self.dtype).contiguous(), step_index)
         return unpatchify_tokens(out, self.config, lat.shape[1], lat.shape[2])
+
+
+def ip_adapter_project(weights: Dict[str, Tensor], ip, image_embeds: Tensor) -> Tensor:
+    """The IP-Adapter's projection model, once per call, as torch ops on the device: tok = LayerNorm_C(reshape(Linear(E -> N C)(e), [N, C])), affine,
+    rounded to bf16 behind the Linear and behind the norm.  image_embeds: [n, E] -> bf16 [n, N, C] for ``MMDiTEngine.cache_ip_tokens``."""
+    N, Cd = ip.ip_adapter_tokens, ip.ip_adapter_dim
+    w = weights["ip_adapter.proj.weight"]
+    e = image_embeds.to(device=w.device, dtype=torch.bfloat16)
+    if e.dim() != 2 or e.shape[1] != ip.embed_dim:
+        raise _lib.DkHipError(f"image embeddings shape {tuple(image_embeds.shape)} != (n, {ip.embed_dim})")
+    y = torch.nn.functional.linear(e.float(), w.float(), weights["ip_adapter.proj.bias"].float()).to(torch.bfloat16).reshape(e.shape[0], N, Cd)
+    y = torch.nn.functional.layer_norm(y.float(), (Cd,), weights["ip_adapter.norm.weight"].float(), weights["ip_adapter.norm.bias"].float(), ip.norm_eps)
+    return y.to(torch.bfloat16).contiguous()
 
 
 def unpatchify_tokens(tok: Tensor, cfg: MMDiTConfig, hl: int, wl: int) -> Tensor:

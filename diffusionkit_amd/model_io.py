@@ -405,6 +405,58 @@ def load_controlnet_checkpoint(src, cfg: MMDiTConfig) -> StateDict:
     return sd3_controlnet_checkpoint_to_reference(sd, cfg)
 
 
+_IPA_TOP = {"ip_adapter_proj_model.proj": "ip_adapter.proj", "ip_adapter_proj_model.norm": "ip_adapter.norm"}
+
+
+def flux_ip_adapter_checkpoint_to_reference(sd: StateDict, cfg: MMDiTConfig, ip) -> StateDict:
+    """XLabs-AI flux-ip-adapter (``ip_adapter.safetensors``) -> the names of ``weights.synth_ip_adapter_weights``:
+      ip_adapter_proj_model.{proj,norm}.{weight,bias}                                          -> ip_adapter.{proj,norm}.*
+      double_blocks.{i}.processor.ip_adapter_double_stream_{k,v}_proj.{weight,bias}            -> ip_adapter.{i}.to_{k,v}_ip.*
+    UNVERIFIED against a real file: the key table is written from the published definition (no adapter checkpoint and no diffusers installation
+    exist on the development machines).  Any other layout is refused by name: InstantX's (processors on the ``single_blocks`` / 57 blocks, a
+    SigLIP MLP projection with 128 tokens), projection models with MLP layers, diffusers-converted ``to_k_ip`` names."""
+    from .weights import ip_adapter_weight_shapes
+    out: StateDict = {}
+    for k0, t in sd.items():
+        if k0.startswith("single_blocks.") or "single_stream" in k0:
+            raise CheckpointError(f"IP-Adapter checkpoint key {k0}: adapters on the single blocks (InstantX's layout: all 57 blocks, SigLIP, 128 tokens) are "
+                                  "not built; this loader reads XLabs-AI's double-block adapter")
+        if k0.startswith(("image_proj.", "ip_adapter_proj_model.layers", "ip_adapter_proj_model.proj_in", "ip_adapter_proj_model.latents")):
+            raise CheckpointError(f"IP-Adapter checkpoint key {k0}: an MLP / resampler projection model is not built; this loader reads XLabs-AI's "
+                                  "Linear + LayerNorm projection (ip_adapter_proj_model.proj / .norm)")
+        base, _, leaf = k0.rpartition(".")
+        if base in _IPA_TOP and leaf in ("weight", "bias"):
+            out[f"{_IPA_TOP[base]}.{leaf}"] = t
+            continue
+        parts = base.split(".")
+        if (len(parts) == 4 and parts[0] == "double_blocks" and parts[1].isdigit() and parts[2] == "processor" and leaf in ("weight", "bias")
+                and parts[3] in ("ip_adapter_double_stream_k_proj", "ip_adapter_double_stream_v_proj")):
+            i = int(parts[1])
+            if i >= cfg.depth_multimodal:
+                raise CheckpointError(f"IP-Adapter checkpoint key {k0}: the model has {cfg.depth_multimodal} double blocks")
+            out[f"ip_adapter.{i}.to_{parts[3][len('ip_adapter_double_stream_')]}_ip.{leaf}"] = t
+            continue
+        raise CheckpointError(f"unknown IP-Adapter checkpoint key: {k0} (XLabs-AI's layout is read: ip_adapter_proj_model.{{proj,norm}}.*, "
+                              "double_blocks.{i}.processor.ip_adapter_double_stream_{k,v}_proj.*)")
+    want = {k: s for k, s in ip_adapter_weight_shapes(cfg, ip).items() if not (k.endswith("_ip.bias") and k not in out)}  # (biases: when present)
+    _check_against(out, want, "IP-Adapter")
+    return out
+
+
+def load_ip_adapter_checkpoint(src, cfg: MMDiTConfig, ip) -> StateDict:
+    """``src``: a dict already in this project's names (``weights.synth_ip_adapter_weights``), a state dict in XLabs-AI's layout, or a .safetensors
+    path of one."""
+    sd = load_safetensors(src) if isinstance(src, str) else dict(src)
+    if any(k.startswith("ip_adapter.") for k in sd):
+        from .weights import ip_adapter_weight_shapes
+        extra = sorted(set(sd) - set(ip_adapter_weight_shapes(cfg, ip)))
+        if extra:
+            raise CheckpointError(f"unknown IP-Adapter tensors, first: {extra[:3]}")
+        _check_against(sd, {k: s for k, s in ip_adapter_weight_shapes(cfg, ip).items() if not (k.endswith("_ip.bias") and k not in sd)}, "IP-Adapter")
+        return sd
+    return flux_ip_adapter_checkpoint_to_reference(sd, cfg, ip)
+
+
 def _check_mmdit_complete(out: StateDict, cfg: MMDiTConfig) -> None:
     """Every tensor pack_mmdit needs must be present with the right shape (fail loudly, name the key)."""
     from .weights import mmdit_weight_shapes

@@ -480,6 +480,38 @@ def ln_modulate_add_joint(x: Tensor, s_t: int, tap: Tensor, s: float, shift: Ten
     return x, out
 
 
+def ip_attention(qkv: Tensor, s_t: int, qn: Tensor, k: Tensor, v: Tensor, scale: Optional[float] = None, eps: float = 1e-6,
+                 head_dim: int = 128) -> Tensor:
+    """Decoupled image-prompt attention of the FLUX IP-Adapter (dk_ip_attention_bf16).  qkv: bf16 [B, S, 3h] contiguous, the q / k / v
+    projection of a double block with the RAW queries in its first h columns and the first ``s_t`` rows of every batch row text (never
+    read, like the k / v columns).  qn: [head_dim] QK-norm weight.  k, v: [B, N, h] views with unit inner stride and one row pitch (1 <= N
+    <= 16), image b's keys / values.  Returns dense [B * (S - s_t), h]: softmax over the N keys of ``scale`` * q_n . k, times v, per head,
+    q_n the QK-normed (not rotated) queries rounded to bf16."""
+    lib = _lib.load()
+    name = "dk_ip_attention_bf16"
+    _require_cuda(qkv, "qkv", BF)
+    if qkv.dim() != 3 or qkv.shape[2] % 3 != 0:
+        raise _lib.DkHipError("qkv must be a contiguous [B, S, 3h] tensor")
+    B, S, h3 = qkv.shape
+    h, s_t = h3 // 3, int(s_t)
+    if not 0 <= s_t < S:
+        raise _lib.DkHipError(f"s_t = {s_t}: must lie in [0, S = {S})")
+    _require_cuda(qn, "qn", BF)
+    if tuple(qn.shape) != (head_dim,):
+        raise _lib.DkHipError(f"qn must be a [{head_dim}] tensor, got {tuple(qn.shape)}")
+    for n, t in (("k", k), ("v", v)):
+        if not t.is_cuda or t.dtype != BF or t.dim() != 3 or tuple(t.shape) != (B, k.shape[1], h):
+            raise _lib.DkHipError(f"{n} must be a bf16 [{B}, N, {h}] tensor on the GPU, got {tuple(t.shape)}")
+        # (an empty N has no strides to speak of: the library refuses it by name below)
+        if k.shape[1] > 0 and (t.stride(2) != 1 or t.stride(1) != k.stride(1) or (B > 1 and t.stride(0) != k.shape[1] * k.stride(1))):
+            raise _lib.DkHipError(f"{n} must have unit inner stride, k's row pitch and batch rows of N consecutive rows")
+    N = int(k.shape[1])
+    out = torch.empty(B * (S - s_t), h, dtype=BF, device=qkv.device)
+    _lib.check(getattr(lib, name)(qkv.data_ptr(), 3 * h, S - s_t, S, s_t, qn.data_ptr(), k.data_ptr(), v.data_ptr(), k.stride(1), B, N, h, int(head_dim),
+                                  float(1.0 / math.sqrt(head_dim) if scale is None else scale), float(eps), out.data_ptr(), _stream()), name)
+    return out
+
+
 def block_probe(x: Tensor, s_t: int, d: Tensor, d_ref: Optional[Tensor] = None):
     """First-block-cache probe (dk_block_probe_*).  x: the joint stream [B, S, h] behind block 0 (text rows first, ``s_t`` of them per
     batch row; only the image rows are read); d: [B, S - s_t, h], X0's image rows on entry, D_cur = round(x - d) on return; d_ref: the

@@ -297,8 +297,18 @@ class DiffusionPipeline:
         condition: Optional[str] = None,
         controlnet_ckpt=None,
         controlnet_config: Optional[MMDiTConfig] = None,
+        ip_adapter_ckpt=None,
+        ip_adapter_config=None,
     ):
-        """``controlnet_ckpt`` (SD3 family only): an SD3 ControlNet in the layout of diffusers' SD3ControlNetModel -- a .safetensors path or a state
+        """``ip_adapter_ckpt`` (FluxPipeline only): a FLUX IP-Adapter in XLabs-AI's layout (flux-ip-adapter as diffusers'
+        FluxIPAdapterJointAttnProcessor2_0 runs it) -- a .safetensors path or a state dict in that layout, or a dict of the names of
+        ``weights.synth_ip_adapter_weights`` -- bound into the model's engine; ``ip_adapter_config``: a ``config.IPAdapterConfig`` (default
+        ``config.FLUX_IP_ADAPTER``: 4 tokens of 4096 features from a 768-wide CLIP image embedding).  Every call must then name its
+        ``ip_adapter_image_embeds`` (see ``denoise_latents``).  Refused on the SD3 family, on an fp8 engine, together with ``condition`` and with
+        ``controlnet_ckpt`` (the LayerNorm launch has one tap operand).  The CLIP vision tower, several adapters at once, negative image embeds and
+        InstantX's layout are not built.  Written from the published definition, arithmetic parity on synthetic weights only: no adapter
+        checkpoint has been run, and nothing here says anything about image quality.
+        ``controlnet_ckpt`` (SD3 family only): an SD3 ControlNet in the layout of diffusers' SD3ControlNetModel -- a .safetensors path or a state
         dict in that layout, or a dict of reference-named tensors (``weights.synth_mmdit_weights`` of a control-net config) -- built into a second
         ``MMDiTEngine``, ``self.controlnet``; ``controlnet_config``: its configuration (default ``config.SD3_CONTROLNET_6``, in the model's element
         type).  Every call must then name its ``controlnet_image_path`` (see ``denoise_latents``).  Refused on a model with dual attention
@@ -368,6 +378,13 @@ class DiffusionPipeline:
         self._packed_weights = packed_weights  # {"mmdit": ..., "vae_decoder": ...} already in engine layout
         self._text_encoder: Optional[Callable] = None
         self._init_sampler(shift)
+        self.ip_adapter_config, self._ip_adapter_named, self.last_ip_adapter = None, None, None
+        if ip_adapter_ckpt is None and ip_adapter_config is not None:
+            raise ValueError("ip_adapter_config needs ip_adapter_ckpt: there is no IP-Adapter to configure")
+        if ip_adapter_ckpt is not None:
+            _check_ip_adapter_config(self, ip_adapter_config, controlnet_ckpt)  # (before anything is loaded)
+            from .model_io import load_ip_adapter_checkpoint
+            self._ip_adapter_named = dict(load_ip_adapter_checkpoint(ip_adapter_ckpt, self.mmdit_config, self.ip_adapter_config))
         self.controlnet = None
         if controlnet_ckpt is None and controlnet_config is not None:
             raise ValueError("controlnet_config needs controlnet_ckpt: there is no ControlNet to configure")
@@ -415,6 +432,9 @@ class DiffusionPipeline:
         """Builds the MMDiT engine.  ``local_ckpt`` may be a dict of reference-named tensors;
         otherwise seeded synthetic weights are used (no checkpoints exist in this environment)."""
         cfg = self.mmdit_config
+        ipc = getattr(self, "ip_adapter_config", None)
+        if ipc is not None:  # (the adapter's stacked K / V matrix and projection model ride in the model's dict: the engine binds them by name)
+            return self._load_mmdit_with_adapter(cfg, ipc)
         if self._packed_weights is not None and "mmdit" in self._packed_weights:
             self.mmdit = MMDiTEngine(cfg, self._packed_weights["mmdit"])
             return
@@ -425,6 +445,20 @@ class DiffusionPipeline:
         else:
             named = synth_mmdit_weights(cfg, seed=self.weights_seed, device=self._synth_device(cfg.param_count()))
         self.mmdit = MMDiTEngine(cfg, pack_mmdit(cfg, named, self.device, consume=True))
+
+    def _load_mmdit_with_adapter(self, cfg, ipc) -> None:
+        """``load_mmdit`` for a pipeline built with ``ip_adapter_ckpt``: the same sources for the model's weights, the adapter's beside them"""
+        from .weights import pack_ip_adapter
+        if self._packed_weights is not None and "mmdit" in self._packed_weights:
+            packed = dict(self._packed_weights["mmdit"])
+        elif isinstance(self.local_ckpt, dict) and "mmdit" in self.local_ckpt:
+            from .model_io import load_mmdit_checkpoint
+            packed = pack_mmdit(cfg, dict(load_mmdit_checkpoint(self.local_ckpt["mmdit"], cfg)), self.device, consume=True)
+        else:
+            named = synth_mmdit_weights(cfg, seed=self.weights_seed, device=self._synth_device(cfg.param_count()))
+            packed = pack_mmdit(cfg, named, self.device, consume=True)
+        packed.update(pack_ip_adapter(cfg, ipc, self._ip_adapter_named, self.device))
+        self.mmdit = MMDiTEngine(cfg, packed, ip_adapter=ipc)
 
     def _synth_device(self, n_params: int):
         """Seeded synthetic weights come from the CPU generator stream (the one the oracle and the
@@ -552,8 +586,18 @@ class DiffusionPipeline:
         controlnet_image_path=None,
         controlnet_scale: float = 1.0,
         controlnet_interval=None,
+        ip_adapter_image_embeds=None,
+        ip_adapter_scale: float = 1.0,
     ):
-        """``controlnet_image_path`` (a pipeline built with ``controlnet_ckpt``; a path, a PIL image or an array, or a list with one per seed): the
+        """``ip_adapter_image_embeds`` (a pipeline built with ``ip_adapter_ckpt``; an array or tensor [E], [n, E] with n = 1 or one row per seed, or a
+        list with one [E] per seed): the prepared image embedding(s) of the image prompt -- CLIP ViT-L/14 ``image_embeds``, diffusers'
+        ``ip_adapter_image_embeds=``; the vision tower is not part of this build.  They are projected to the adapter's tokens once per call
+        (``engine.ip_adapter_project``), every double block's keys and values are cached (``MMDiTEngine.cache_ip_tokens``), and every model evaluation
+        adds ``ip_adapter_scale`` times the decoupled attention's output behind each double block.  Scale 0 runs the plain launches.  Composes with
+        seed lists, every sampler, img2img and ``mask_path``.  Raises on ``cfg_weight > 0`` (negative image embeds are not built), ``block_cache``,
+        a reference image, on these keywords without an adapter and on their absence with one.  ``self.last_ip_adapter`` = {"scale", "tokens",
+        "images"}, or None.
+        ``controlnet_image_path`` (a pipeline built with ``controlnet_ckpt``; a path, a PIL image or an array, or a list with one per seed): the
         prepared control image (edges, pose, ...) at the OUTPUT size -- never resized, sides multiples of 16 -- VAE-encoded to the posterior's mean (the
         published pipeline samples), put through the latent format's ``process_in`` and patchified.  Every model evaluation of a controlled step first
         runs the ControlNet's engine on the same tokens, both CFG rows included, and the main engine adds ``controlnet_scale`` times its taps
@@ -649,6 +693,7 @@ class DiffusionPipeline:
                                       (latent_size[0] * 8, latent_size[1] * 8) if image_path is None else read_image_u8(image_path).shape[:2],
                                       block_cache, slg, pag, reference_image_path,
                                       getattr(self, "condition", None) or condition_image_path)  # (raises before any GPU work)
+        ip = _ip_adapter_options(self, ip_adapter_image_embeds, ip_adapter_scale, n_seeds, cfg_weight, block_cache, reference_image_path)
         sampler = check_sampler(sampler)
         eta = check_sampler_eta(sampler, sampler_eta)
         if sampler == "heun" and block_cache is not None:
@@ -699,6 +744,12 @@ class DiffusionPipeline:
                 self.controlnet.guidance = self.mmdit.guidance
             extra_args["controlnet"] = {"engine": self.controlnet, "tokens": self.controlnet.patchify(z.to(torch.float32).contiguous()),
                                         "scale": control["scale"], "interval": control["interval"]}
+        self.last_ip_adapter = None
+        if ip is not None:
+            from .engine import ip_adapter_project
+            ipc = self.ip_adapter_config
+            extra_args["ip_adapter"] = {"tokens": ip_adapter_project(self.mmdit.weights, ipc, torch.from_numpy(ip["embeds"])), "scale": ip["scale"]}
+            self.last_ip_adapter = {"scale": ip["scale"], "tokens": ipc.ip_adapter_tokens, "images": int(ip["embeds"].shape[0])}
         self.last_reference = None
         if refs is not None:
             extra_args["reference"] = self.latent_format.process_in(self.encode_reference_to_latents(refs))
@@ -714,16 +765,20 @@ class DiffusionPipeline:
         denoiser = CFGDenoiser(self)
         stochastic = sampler in STOCHASTIC_SAMPLERS
         rows = "euler" if sampler == "euler_a" and eta == 0.0 else sampler  # (eta = 0: euler's rows, and so euler's launches)
-        if rows == "euler" and guide is None and slg is None and pag is None:
-            latent, iter_time = sample_euler(denoiser, x0, sigmas, extra_args=extra_args)
-            evals, draws = len(iter_time), 0
-        else:
-            plan = step_plan(rows, sigmas, eta if rows == "euler_a" else None, first_draw=cut)
-            draws = sum(r.cn != 0.0 for r in plan)
-            if draws:  # (the seeds the start noise was drawn with, one per image)
-                extra_args["noise_seeds"] = [int(s) for s in seeds]
-            latent, iter_time = sample_steps(denoiser, x0, sigmas, plan, extra_args=extra_args)
-            evals = len(plan)
+        try:
+            if rows == "euler" and guide is None and slg is None and pag is None:
+                latent, iter_time = sample_euler(denoiser, x0, sigmas, extra_args=extra_args)
+                evals, draws = len(iter_time), 0
+            else:
+                plan = step_plan(rows, sigmas, eta if rows == "euler_a" else None, first_draw=cut)
+                draws = sum(r.cn != 0.0 for r in plan)
+                if draws:  # (the seeds the start noise was drawn with, one per image)
+                    extra_args["noise_seeds"] = [int(s) for s in seeds]
+                latent, iter_time = sample_steps(denoiser, x0, sigmas, plan, extra_args=extra_args)
+                evals = len(plan)
+        finally:
+            if ip is not None:  # (the engine outlives the call: off again, the plain launches)
+                self.mmdit.set_ip_scale(0.0)
         self.last_sampler = {"sampler": sampler, "model_evals": evals}
         if stochastic:  # (keys of the stochastic samplers alone)
             self.last_sampler.update(eta=eta if sampler == "euler_a" else None, noise_draws=draws)
@@ -771,8 +826,12 @@ class DiffusionPipeline:
         controlnet_image_path=None,
         controlnet_scale: float = 1.0,
         controlnet_interval=None,
+        ip_adapter_image_embeds=None,
+        ip_adapter_scale: float = 1.0,
     ):
-        """``controlnet_image_path``, ``controlnet_scale``, ``controlnet_interval``: SD3 ControlNet, see ``denoise_latents``; with a ControlNet,
+        """``ip_adapter_image_embeds``, ``ip_adapter_scale``: FLUX IP-Adapter, see ``denoise_latents``; ``log["denoising"]["ip_adapter"]`` is
+        ``self.last_ip_adapter``.
+        ``controlnet_image_path``, ``controlnet_scale``, ``controlnet_interval``: SD3 ControlNet, see ``denoise_latents``; with a ControlNet,
         ``log["denoising"]["controlnet"]`` is ``self.last_controlnet``.
         mlx/__init__.py:294-534: returns (PIL.Image, log).  ``mask_path``: inpainting, see ``denoise_latents``; with ``composite`` the pixels
         the mask keeps are pasted back from the input image after decoding (the VAE round trip alone does not reproduce them).
@@ -831,7 +890,9 @@ class DiffusionPipeline:
             **({} if pag_scale is None and pag_layers is None and pag_interval is None else
                {"pag_scale": pag_scale, "pag_layers": pag_layers, "pag_interval": pag_interval}),
             **({} if controlnet_image_path is None and controlnet_interval is None and controlnet_scale == 1.0 and getattr(self, "controlnet", None) is None
-               else {"controlnet_image_path": controlnet_image_path, "controlnet_scale": controlnet_scale, "controlnet_interval": controlnet_interval}))
+               else {"controlnet_image_path": controlnet_image_path, "controlnet_scale": controlnet_scale, "controlnet_interval": controlnet_interval}),
+            **({} if ip_adapter_image_embeds is None and ip_adapter_scale == 1.0 and getattr(self, "ip_adapter_config", None) is None
+               else {"ip_adapter_image_embeds": ip_adapter_image_embeds, "ip_adapter_scale": ip_adapter_scale}))
         torch.cuda.synchronize(dev)
         log["denoising"]["post"] = mem()
         log["peak_memory"] = max(log["peak_memory"], log["denoising"]["post"]["peak_memory"])
@@ -852,6 +913,8 @@ class DiffusionPipeline:
             log["denoising"]["perturbed_attention_guidance"] = self.last_perturbed_attention_guidance
         if self.last_controlnet is not None:
             log["denoising"]["controlnet"] = self.last_controlnet
+        if self.last_ip_adapter is not None:
+            log["denoising"]["ip_adapter"] = self.last_ip_adapter
 
         torch.cuda.reset_peak_memory_stats(dev)
         t0 = time.time()
@@ -1240,6 +1303,70 @@ def _check_flux_controlnet_config(pipe, controlnet_config) -> None:
     pipe.controlnet_config = ccfg
 
 
+def _check_ip_adapter_config(pipe, ip_config, controlnet_ckpt) -> None:
+    """``ip_adapter_ckpt`` on a pipeline: the FLUX family's, one kind of added conditioning at a time; sets ``pipe.ip_adapter_config``.  Needs no GPU."""
+    from .config import FLUX_IP_ADAPTER, IPAdapterConfig, validate_ip_adapter
+    cfg = pipe.mmdit_config
+    if not pipe._IS_FLUX:
+        raise ValueError("ip_adapter_ckpt is the FLUX family's (FluxPipeline): SD3 and SD3.5 IP-Adapters are not built")
+    if cfg.weight_dtype == "fp8_e4m3":
+        raise ValueError("ip_adapter_ckpt cannot be combined with an fp8 engine: the fp8 LayerNorm kernels take no tap")
+    if getattr(pipe, "condition", None) is not None:
+        raise ValueError("ip_adapter_ckpt cannot be combined with condition= (FLUX.1 Fill / Canny / Depth): the engine refuses a condition width beside "
+                         "the adapter")
+    if controlnet_ckpt is not None:
+        raise ValueError("ip_adapter_ckpt cannot be combined with controlnet_ckpt: the LayerNorm launch has one tap operand")
+    ipc = FLUX_IP_ADAPTER if ip_config is None else ip_config
+    if not isinstance(ipc, IPAdapterConfig):
+        raise ValueError(f"ip_adapter_config must be a config.IPAdapterConfig, got {type(ipc).__name__}")
+    validate_ip_adapter(cfg, ipc)
+    pipe.ip_adapter_config = ipc
+
+
+def _ip_adapter_options(pipe, embeds, scale, n_img, cfg_weight, block_cache, reference):
+    """The IP-Adapter keywords of one call -> None (a pipeline without an adapter and no keyword) or {"embeds": f32 [1 or n_img, E], "scale"}.
+    Refused, each naming its rule: the keywords on a pipeline built without an adapter and their absence on one built with it, ``cfg_weight > 0``,
+    ``block_cache``, a reference image, embeddings of another width or count."""
+    ipc = getattr(pipe, "ip_adapter_config", None)
+    if ipc is None:
+        if embeds is not None or float(scale) != 1.0:
+            raise ValueError("ip_adapter_image_embeds / ip_adapter_scale need a pipeline built with an IP-Adapter (ip_adapter_ckpt=)")
+        return None
+    if embeds is None:
+        raise ValueError("a pipeline built with an IP-Adapter needs ip_adapter_image_embeds in every call (ip_adapter_scale=0 switches it off)")
+    if cfg_weight > 0:
+        raise ValueError("an IP-Adapter cannot run with cfg_weight > 0: negative image embeds (true CFG) are not built")
+    if block_cache is not None:
+        raise ValueError("an IP-Adapter cannot run together with block_cache: the engine refuses the block cache beside the adapter")
+    if reference is not None:
+        raise ValueError("an IP-Adapter cannot run together with reference_image_path: the engine refuses a reference grid beside the adapter")
+    scale = float(scale)
+    if not np.isfinite(scale):
+        raise ValueError(f"ip_adapter_scale must be finite, got {scale}")
+    rows = [embeds] if not isinstance(embeds, (list, tuple)) else list(embeds)
+    rows = [np.asarray(r.detach().float().cpu() if isinstance(r, torch.Tensor) else r, dtype=np.float32) for r in rows]
+    e = np.concatenate([r.reshape(1, -1) if r.ndim == 1 else r for r in rows], axis=0)
+    if e.ndim != 2 or e.shape[1] != ipc.embed_dim:
+        raise ValueError(f"ip_adapter_image_embeds must be [E], [n, E] or a list of [E] with E = {ipc.embed_dim}, got {tuple(e.shape)}")
+    if e.shape[0] not in (1, n_img):
+        raise ValueError(f"{e.shape[0]} image embeddings for {n_img} seeds: one for all, or one per seed (several image prompts at once are not built)")
+    if not np.isfinite(e).all():
+        raise ValueError("ip_adapter_image_embeds must be finite")
+    return {"embeds": np.ascontiguousarray(e), "scale": scale}
+
+
+def _cache_ip_adapter(mm, ip: Optional[dict], now: int, n_img: int) -> None:
+    """Behind ``_prepare_rows``: the image prompt's keys and values cached for those rows, shared or per image like ``_cache_reference``, and the scale"""
+    if ip is None:
+        return
+    tok = ip["tokens"]
+    if tok.shape[0] == 1:
+        mm.cache_ip_tokens(tok, per_image=False)
+    else:
+        mm.cache_ip_tokens(tok.repeat(now // n_img, 1, 1).contiguous(), per_image=True)
+    mm.set_ip_scale(ip["scale"])
+
+
 def _controlnet_options(pipe, image, scale, interval, n_img, out_hw, block_cache, slg, pag, reference=None, condition=None):
     """The ControlNet keywords of one call -> None (a pipeline without a ControlNet and no keyword) or {"pixels": uint8 [1 or n_img, H, W, 3],
     "scale", "interval"}.  Refused, each naming its rule: the keywords on a pipeline built without a ControlNet and their absence on one built
@@ -1315,6 +1442,7 @@ class _Loop(NamedTuple):
     # ``extra_args["controlnet"]``: {"engine": the ControlNet's MMDiTEngine, "tokens": the control image's tokens [1 or n_img, S_i, p*p*C], "scale",
     # "interval"} plus "taps", the tensor ``_prepare_control`` allocates for the rows the engines hold; or None
     control: Optional[dict] = None
+    ip: Optional[dict] = None  # ``extra_args["ip_adapter"]``: {"tokens": the image prompt's tokens bf16 [1 or n_img, N, C], "scale"}, or None
 
     @property
     def forked(self) -> Optional[dict]:
@@ -1401,6 +1529,10 @@ def _loop_setup(model: "CFGDenoiser", x: Tensor, sigmas, extra_args, guided: boo
     _cache_condition(mm, condition, now, n_img)
     model.cache_modulation_params(pooled[:now], timesteps)
     mm.cache_context(conditioning[:now])  # context_embedder is step-invariant (the reference recomputes it in every call, mmdit.py:195)
+    ip = extra_args.get("ip_adapter")
+    if ip is not None and (ip["tokens"].dim() != 3 or ip["tokens"].shape[0] not in (1, n_img)):
+        raise ValueError(f"the image-prompt tokens {tuple(ip['tokens'].shape)} do not match {n_img} images: [1 or n_img, N, C]")
+    _cache_ip_adapter(mm, ip, now, n_img)
     control = extra_args.get("controlnet")
     if control is not None:
         control = dict(control)
@@ -1421,7 +1553,7 @@ def _loop_setup(model: "CFGDenoiser", x: Tensor, sigmas, extra_args, guided: boo
         x_orig = noise = None
     tok = mm.patchify(x, dup=2 if cfg_on and guided else 1)
     return _Loop(pipe, mm, sigmas, cfg_weight, cfg_on, n_img, policy, x, mask, x_orig, noise, tok, torch.empty_like(tok), conditioning, pooled, timesteps,
-                 reference, condition, extra_args.get("skip_layer_guidance"), extra_args.get("perturbed_attention_guidance"), control)
+                 reference, condition, extra_args.get("skip_layer_guidance"), extra_args.get("perturbed_attention_guidance"), control, ip)
 
 
 def _set_rows(model: "CFGDenoiser", lp: _Loop, guided: bool, fork: bool = False):
@@ -1437,6 +1569,7 @@ def _set_rows(model: "CFGDenoiser", lp: _Loop, guided: bool, fork: bool = False)
     _cache_condition(lp.mm, lp.condition, now, lp.n_img)
     model.cache_modulation_params(rows(lp.pooled).contiguous(), lp.timesteps)
     lp.mm.cache_context(rows(lp.conditioning).contiguous())
+    _cache_ip_adapter(lp.mm, lp.ip, now, lp.n_img)
     if lp.forked is not None:  # (without the options the engine is never told: its calls are what they were)
         lp.set_fork(fork)
     _prepare_control(lp.control, now, lp.n_img, lp.x.shape[1:3], rows(lp.conditioning).contiguous(), rows(lp.pooled).contiguous(), lp.timesteps)

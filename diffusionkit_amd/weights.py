@@ -143,6 +143,58 @@ def synth_mmdit_weights(cfg: MMDiTConfig, seed: int = 1234, device="cpu", dtype=
     return I.out
 
 
+def synth_ip_adapter_weights(cfg: MMDiTConfig, ip, seed: int = 2468, device="cpu", dtype=torch.bfloat16, shapes_only=False) -> Dict[str, Tensor]:
+    """Random FLUX IP-Adapter weights (``ip``: config.IPAdapterConfig) for the model ``cfg``: the projection model ``ip_adapter.proj`` [N C, E] /
+    ``ip_adapter.norm`` [C] and, per double block, ``ip_adapter.{i}.to_k_ip`` / ``to_v_ip`` [h, C] with biases.  Drawn, not zero: a fresh adapter's
+    zero-initialised Linears would exercise nothing behind them."""
+    I = _Init(device, seed, dtype, shapes_only)
+    N, C, E, h = ip.ip_adapter_tokens, ip.ip_adapter_dim, ip.embed_dim, cfg.hidden_size
+    I.linear("ip_adapter.proj", N * C, E)
+    I.normal("ip_adapter.norm.weight", (C,), mean=1.0)
+    I.normal("ip_adapter.norm.bias", (C,))
+    for i in range(cfg.depth_multimodal):
+        I.linear(f"ip_adapter.{i}.to_k_ip", h, C)
+        I.linear(f"ip_adapter.{i}.to_v_ip", h, C)
+    return I.out
+
+
+def ip_adapter_weight_shapes(cfg: MMDiTConfig, ip) -> Dict[str, tuple]:
+    return synth_ip_adapter_weights(cfg, ip, shapes_only=True)
+
+
+def pack_ip_adapter(cfg: MMDiTConfig, ip, w: Dict[str, Tensor], device) -> Dict[str, Tensor]:
+    """Adapter weights (the names of ``synth_ip_adapter_weights``; the to_*_ip biases optional, zeros when absent) -> what the engine binds: every
+    block's to_k_ip / to_v_ip stacked into ONE bf16 matrix ``ip_adapter.kv.weight`` [depth_multimodal * 2h, C] (block i's key rows at i * 2h, its
+    value rows h further) with ``ip_adapter.kv.bias``, and the per-block names as views of the two (dk_mmdit_cache_ip_tokens reads the stack
+    with one GEMM).  The projection model's tensors pass through: it runs as torch ops on the device (engine.ip_adapter_project)."""
+    from .config import validate_ip_adapter
+    validate_ip_adapter(cfg, ip)
+    shapes = ip_adapter_weight_shapes(cfg, ip)
+    h, C, nd = cfg.hidden_size, ip.ip_adapter_dim, cfg.depth_multimodal
+    for name, shape in shapes.items():
+        if name not in w:
+            if name.endswith("_ip.bias"):
+                continue
+            raise ValueError(f"IP-Adapter tensor missing: {name}")
+        if tuple(w[name].shape) != shape:
+            raise ValueError(f"IP-Adapter tensor {name}: shape {tuple(w[name].shape)}, expected {shape}")
+    dev = torch.device(device)
+    kv_w = torch.empty(nd * 2 * h, C, dtype=torch.bfloat16, device=dev)
+    kv_b = torch.zeros(nd * 2 * h, dtype=torch.bfloat16, device=dev)
+    out = {"ip_adapter.kv.weight": kv_w, "ip_adapter.kv.bias": kv_b}
+    for i in range(nd):
+        for j, leaf in enumerate(("to_k_ip", "to_v_ip")):
+            r0 = (2 * i + j) * h
+            name = f"ip_adapter.{i}.{leaf}"
+            kv_w[r0:r0 + h].copy_(w[name + ".weight"])
+            if name + ".bias" in w:
+                kv_b[r0:r0 + h].copy_(w[name + ".bias"])
+            out[name + ".weight"], out[name + ".bias"] = kv_w[r0:r0 + h], kv_b[r0:r0 + h]
+    for name in ("ip_adapter.proj.weight", "ip_adapter.proj.bias", "ip_adapter.norm.weight", "ip_adapter.norm.bias"):
+        out[name] = w[name].to(device=dev, dtype=torch.bfloat16).contiguous()
+    return out
+
+
 def synth_vae_weights(cfg: VAEDecoderConfig, seed: int = 4321, device="cpu", dtype=torch.bfloat16, shapes_only=False) -> Dict[str, Tensor]:
     """Random weights keyed like the reference VAEDecoder module tree (vae.py:336-384)."""
     I = _Init(device, seed, dtype, shapes_only)

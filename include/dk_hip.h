@@ -993,6 +993,50 @@ int dk_mmdit_set_control_taps(dk_mmdit* m, const void* taps, int32_t n_taps, flo
  * taps are set.  Verified against an fp32 / emulating oracle with synthetic weights (arithmetic parity); no checkpoint has been run. */
 int dk_mmdit_set_flux_control_net(dk_mmdit* m, int32_t on);
 int dk_mmdit_set_flux_control_taps(dk_mmdit* m, const void* taps, int32_t n_double_taps, int32_t n_single_taps, float scale);
+
+/* ---- FLUX IP-Adapter (opt-in; XLabs-AI flux-ip-adapter as diffusers' FluxIPAdapterJointAttnProcessor2_0 runs it, no counterpart in the
+ * reference; bf16 only) -------------------------------------------------------------------------------------------------------------
+ * Decoupled image-prompt attention in the double blocks: behind double block i, after fc2's gated add,
+ *   x_img <- x_img + scale * softmax( q_n K_i^T / sqrt(D) ) V_i          per head, no projection, no gate
+ * with q_n the block's image queries after QK-RMSNorm and BEFORE RoPE, and K_i / V_i = to_k_ip_i / to_v_ip_i of the n_tokens image-prompt
+ * tokens of that batch row ([n_tokens, token_dim]: the adapter's projection of the CLIP image embedding, computed by the caller).  Single
+ * blocks take nothing.
+ *
+ * dk_mmdit_set_ip_adapter(m, n_tokens, token_dim): legal before the weights are resolved (the first dk_mmdit_prepare); (0, 0) is off, the
+ * default: workspace size, carve, every launch and every bit are then what they are without the feature.  1 <= n_tokens <= 16, token_dim a
+ * multiple of 64.  The engine additionally binds, for i < depth_multimodal,
+ *   ip_adapter.<i>.to_k_ip.{weight,bias}, ip_adapter.<i>.to_v_ip.{weight,bias}      [h, token_dim] / [h]
+ * which must be views of ONE matrix [depth_multimodal * 2h, token_dim] (block i's to_k_ip rows at i * 2h, its to_v_ip rows h further) and
+ * ONE bias laid out the same way (weights.py: pack_ip_adapter; a checkpoint without biases binds zeros).  The workspace grows by the K / V
+ * cache [batch * n_tokens, depth_multimodal * 2h] and one output buffer [batch * S_i, h].
+ * dk_mmdit_cache_ip_tokens(m, tokens, per_image, stream): after dk_mmdit_prepare.  tokens bf16 [batch, n_tokens, token_dim] (per_image != 0)
+ * or [1, n_tokens, token_dim] (one prompt for every batch row: one GEMM launch over the stacked matrix per batch row either way, the bits of
+ * a repeated prompt).  Replaces a previous cache; invalidated by dk_mmdit_prepare.
+ * dk_mmdit_set_ip_scale(m, scale): 0 (the default) is off -- the plain launches and their bits.  With another scale every dk_mmdit_forward
+ * runs, behind the q / k / v projection of double block i, ONE more launch (dk_ip_attention_bf16 on the raw image queries that QKV still
+ * holds: the attention kernel norms and rotates in its own Q load) into the output buffer, and the add rides as x' = round_bf16(fmaf(scale,
+ * ip, x)) in the LayerNorm launch that reads the image rows next -- block i + 1's first (dk_ln_modulate_add_bf16), single block 0's or, with
+ * depth_unified == 0, the final layer's (dk_ln_modulate_add_joint_bf16).
+ * Refused, with no state changed and an error that names the rule: SD3 geometry, fp8_linears (the MX-fp8 LayerNorm kernels take no tap),
+ * fp16, a head size other than 128, a control-net engine, control taps (one tap operand per LayerNorm launch), a block cache, a reference
+ * grid, a condition width, skip layers, perturbed attention, dual attention; those setters refuse an engine with an adapter in turn.
+ * dk_mmdit_forward with the adapter active is refused without a cache and under dk_tune_set("attn_fuse_q", 0) or ("gemm_fuse_q", 1), which
+ * leave no raw queries in QKV ("gemm_fuse_q" 1 only while the keys' fused tail is on: with "gemm_fuse_k" 0 it finishes nothing and is accepted);
+ * dk_mmdit_forward_head, dk_mmdit_forward_tail and dk_mmdit_run_blocks are refused while it is active, the first two in front of their own
+ * block-cache rule, so that the adapter's text is what they answer.
+ * Written from the published definition and verified against an fp32 / emulating oracle with synthetic weights (arithmetic parity); no
+ * checkpoint has been run. */
+int dk_mmdit_set_ip_adapter(dk_mmdit* m, int32_t n_tokens, int32_t token_dim);
+int dk_mmdit_cache_ip_tokens(dk_mmdit* m, const void* tokens, int32_t per_image, void* stream);
+int dk_mmdit_set_ip_scale(dk_mmdit* m, float scale);
+/* The kernel behind it, stand-alone.  qkv: bf16 [B, seg_stride, ldq] whose rows hold the raw q projection in their first h columns; the rows
+ * read are first_row .. first_row + seg_len - 1 of every batch row and of those the first h columns -- the other rows (text) and columns (k,
+ * v) are never addressed.  qn: [D] QK-norm weight.  k, v: [B, N, h] at ldkv elements per row.  out: dense [B * seg_len, h]:
+ *   q_n = round_bf16(q * rsqrt(mean_D(q^2) + eps) * qn);  out[b, s, head] = round_bf16( softmax_n(scale * q_n . k[b, n, head]) @ v[b, :, head] )
+ * with the scores, the exact (max-subtracted) softmax and the weighted sum in fp32.  D == 128 and 1 <= N <= 16, anything else is refused by
+ * name; h % 128 == 0; pitches % 8 == 0; 16-byte aligned pointers. */
+int dk_ip_attention_bf16(const void* qkv, int32_t ldq, int32_t seg_len, int32_t seg_stride, int32_t first_row, const void* qn, const void* k,
+                         const void* v, int32_t ldkv, int32_t B, int32_t N, int32_t h, int32_t D, float scale, float eps, void* out, void* stream);
 /* Head of step `step_index`: dk_mmdit_forward's embedder launches, block 0 and the probe.  probe_out: device float [batch][2] =
  * (num, den) per batch row; before any computed step den is 0 (and num = sum |D_cur|).  Records a pending head for step_index. */
 int dk_mmdit_forward_head(dk_mmdit* m, const void* tokens_in, const void* text, int32_t step_index, float* probe_out, void* stream);
