@@ -206,6 +206,10 @@ SIGNATURES = {
     # stochastic samplers: the generator as an operator (out, seeds u64 [n_img], n_img, n_per_img, draw, stream tag, quad_offset; the step entry is
     # dk_noisy_cfg_step above)
     "dk_philox_normal_f32": (_i32, [_vp, _vp, _i32, _i64, _i32, _i32, C.c_uint64, _vp]),
+    # FlowEdit: z, x_src, model_out, ld_out, tokens, zs_out, zt_out, n_img, cfg_on, Hl, Wl, C, p, reshape_order, w_src, w_tar, c, sigma_in, seeds, draw,
+    # prime, stream; and the engine's guidance strength per batch row
+    **{"dk_flowedit_step" + f16: (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp] + [_i32] * 7 + [_f32] * 4 + [_vp, _i32, _i32, _vp]) for f16 in ("", "_f16")},
+    "dk_mmdit_set_guidance_rows": (_i32, [_vp, _fp, _i32]),
     # inpainting: the mask's pixels -> latent cells, the paste-back of the kept pixels
     "dk_mask_to_latent_f32": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "dk_image_composite_u8": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),

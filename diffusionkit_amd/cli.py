@@ -130,6 +130,18 @@ def build_parser(model_versions: Sequence[str]) -> argparse.ArgumentParser:
     p.add_argument("--controlnet-scale", type=float, default=None, metavar="S", help="With --controlnet: the scale of the ControlNet's residuals (default 1.0).")
     p.add_argument("--controlnet-interval", type=float, nargs=2, default=None, metavar=("START", "STOP"),
                    help="With --controlnet: step i of n is controlled iff i / n >= START and (i + 1) / n <= STOP (default: every step).")
+    p.add_argument("--edit-source-prompt", type=str, default=None, metavar="TEXT",
+                   help="FlowEdit (Kulikov et al. 2024): edit --image-path with the plain checkpoint. TEXT describes the image as it is, --prompt what "
+                        "it should become. The defaults of the flags below are the paper's settings as recalled and have not been verified. Not "
+                        "together with --denoise, --mask-path, --block-cache, guidance modes, --slg-scale, --pag-scale, --controlnet, --ip-adapter, "
+                        "--reference-image-path or --condition. Verified as arithmetic only: no trained checkpoint has been run here.")
+    p.add_argument("--edit-steps", type=int, nargs=2, default=None, metavar=("N_MAX", "N_MIN"),
+                   help="With --edit-source-prompt: the edit covers the steps T - N_MAX .. T - N_MIN - 1 of the --steps = T schedule; the last N_MIN steps "
+                        "are ordinary sampling with the target prompt (0 <= N_MIN < N_MAX <= T; default: 33/50 of T for SD3, 24/28 for FLUX, and 0).")
+    p.add_argument("--edit-n-avg", type=int, default=None, metavar="N", help="With --edit-source-prompt: noise draws averaged per step (default 1).")
+    p.add_argument("--edit-source-cfg", type=float, default=None, metavar="W",
+                   help="With --edit-source-prompt: the source side's CFG weight (SD3 versions; --cfg is the target's; default 3.5) or distilled-guidance "
+                        "value (FLUX.1-dev; default 1.5). Refused for FLUX.1-schnell, which has no guidance embedding.")
     p.add_argument("--local-ckpt", default=None, type=str, help="Path to the local mmdit checkpoint.")
     p.add_argument("--ckpt", action="append", default=[], metavar="KEY=PATH",
                    help="Further local checkpoint parts (vae_decoder, vae_encoder, clip_l, clip_g, t5, t5_tokenizer, "
@@ -308,9 +320,37 @@ def resolve(args) -> dict:
         r["ip_adapter_image_embeds"] = ipa["ip_adapter_embeds"]
         if ipa["ip_adapter_scale"] is not None:
             r["ip_adapter_scale"] = ipa["ip_adapter_scale"]
+    ed = {k: getattr(args, k, None) for k in ("edit_source_prompt", "edit_steps", "edit_n_avg", "edit_source_cfg")}
+    if any(v is not None for v in ed.values()):  # (keys only when the flags are given)
+        if ed["edit_source_prompt"] is None:
+            raise ValueError("--edit-steps / --edit-n-avg / --edit-source-cfg need --edit-source-prompt")
+        if args.image_path is None:
+            raise ValueError("--edit-source-prompt needs --image-path: the image to edit")
+        if args.denoise != 0.0:  # (the flag's default: not given)
+            raise ValueError("--edit-source-prompt cannot run together with --denoise: --edit-steps says which part of the schedule the edit covers")
+        for key, flag in (("mask_path", "--mask-path"), ("block_cache", "--block-cache"), ("guidance", "--guidance"),
+                          ("guidance_interval", "--guidance-interval"), ("skip_layer_guidance", "--slg-scale"), ("pag_scale", "--pag-scale"),
+                          ("controlnet_ckpt", "--controlnet"), ("ip_adapter_ckpt", "--ip-adapter"), ("reference_image_path", "--reference-image-path"),
+                          ("condition", "--condition")):
+            if r.get(key) is not None and not (key == "guidance" and r[key] == "cfg"):
+                raise ValueError(f"--edit-source-prompt cannot run together with {flag}")
+        if ed["edit_steps"] is not None:
+            from .sampler import check_flowedit
+            r["edit_steps"] = check_flowedit(args.steps, ed["edit_steps"][0], ed["edit_steps"][1], 1)[:2]
+        if ed["edit_n_avg"] is not None:
+            if ed["edit_n_avg"] < 1:
+                raise ValueError("--edit-n-avg must be at least 1")
+            r["edit_n_avg"] = ed["edit_n_avg"]
+        if ed["edit_source_cfg"] is not None:
+            from .config import MODEL_CONFIG
+            if "FLUX" in args.model_version and not r.get("mmdit_config", MODEL_CONFIG[args.model_version]).guidance_embed:
+                raise ValueError(f"--edit-source-cfg is the source's distilled-guidance value on FLUX: {args.model_version} has no guidance embedding")
+            r["edit_source_cfg"] = ed["edit_source_cfg"]
+        r["edit_source_text"] = ed["edit_source_prompt"]
     return r
 
 
+EDIT_KEYS = ("edit_source_text", "edit_steps", "edit_n_avg", "edit_source_cfg")  # the same, FlowEdit
 SKIP_LAYER_KEYS = ("skip_layer_guidance", "skip_layers", "skip_layer_interval")  # keywords of generate_image that ``resolve`` sets together
 PAG_KEYS = ("pag_scale", "pag_layers", "pag_interval")  # the same, perturbed-attention guidance
 CONTROLNET_KEYS = ("controlnet_image_path", "controlnet_scale", "controlnet_interval")  # the same, SD3 ControlNet (the constructor takes controlnet_ckpt)
@@ -361,9 +401,9 @@ def main(argv: Optional[Sequence[str]] = None, pipeline_overrides: Optional[dict
         logger.info("Benchmark mode: Warming up the models done.")
     image, log = sd.generate_image(args.prompt, cfg_weight=r["cfg"], num_steps=args.steps, seed=args.seed,
                                    negative_text=args.negative_prompt, latent_size=latent_size, image_path=args.image_path,
-                                   denoise=args.denoise, verbose=args.verbose, mask_path=r.get("mask_path"),
+                                   denoise=1.0 if "edit_source_text" in r else args.denoise, verbose=args.verbose, mask_path=r.get("mask_path"),
                                    composite=r.get("composite", True), block_cache=r.get("block_cache"), sampler=r.get("sampler"),
-                                   **{key: r[key] for key in (*GUIDANCE_FLAGS.values(), "reference_image_path", *SKIP_LAYER_KEYS, *PAG_KEYS, "sampler_eta")
+                                   **{key: r[key] for key in (*GUIDANCE_FLAGS.values(), "reference_image_path", *SKIP_LAYER_KEYS, *PAG_KEYS, "sampler_eta", *EDIT_KEYS)
                                       if key in r},
                                    **cond_kw)
     if log["text_encoding"].get("synthetic"):

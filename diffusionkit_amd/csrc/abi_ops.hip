@@ -750,6 +750,40 @@ extern "C" int dk_philox_normal_f32(float* out, const uint64_t* seeds, int32_t n
                                  (unsigned long long)quad_offset, S_(stream));
 }
 
+// FlowEdit: the edit loop's step (elementwise.hip: dk_flowedit_step_kernel).  Every requirement of the launch, then the launcher of the element type.
+static int flowedit_step(int dtype, float* z, const float* x_src, const void* model_out, int ld_out, void* tokens, float* zs_out, float* zt_out,
+                         int n_img, int cfg_on, int Hl, int Wl, int C, int p, int reshape_order, float w_src, float w_tar, float c, float sigma_in,
+                         const uint64_t* seeds, int draw, int prime, void* stream) {
+  DK_REQUIRE(z && x_src && tokens && zt_out && seeds, "null argument (zs_out alone may be null)");
+  DK_REQUIRE(model_out || prime, "model_out is null while the launch reads it (prime = 0)");
+  DK_REQUIRE(n_img > 0 && Hl > 0 && Wl > 0 && C > 0, "n_img and the latent size must be positive");
+  DK_REQUIRE(p > 0 && Hl % p == 0 && Wl % p == 0, "latent size must be divisible by the patch size");
+  DK_REQUIRE(C % 4 == 0, "C must be a multiple of 4: a thread takes the four channels of one Philox block");
+  DK_REQUIRE(prime || (ld_out >= p * p * C && ld_out % 4 == 0), "ld_out must be at least p * p * C and a multiple of 4");
+  const uintptr_t f32s = (uintptr_t)z | (uintptr_t)x_src | (uintptr_t)zs_out | (uintptr_t)zt_out;
+  DK_REQUIRE((f32s & 15) == 0, "z, x_src, zs_out and zt_out must be 16-byte aligned");
+  DK_REQUIRE((((uintptr_t)tokens | (prime ? 0 : (uintptr_t)model_out)) & 7) == 0, "model_out and tokens must be 8-byte aligned");
+  DK_REQUIRE(std::isfinite(w_src) && std::isfinite(w_tar) && std::isfinite(c) && std::isfinite(sigma_in), "w_src, w_tar, c and sigma_in must be finite");
+  DK_REQUIRE(draw >= 0, "draw must not be negative");
+  FlowEditParams s = {};
+  s.z = z, s.x_src = x_src, s.model_out = (const bf16_t*)model_out, s.ld_out = ld_out, s.tok = (bf16_t*)tokens, s.zs_out = zs_out, s.zt_out = zt_out;
+  s.n_img = n_img, s.cfg_on = cfg_on != 0, s.Hl = Hl, s.Wl = Wl, s.C = C, s.p = p, s.reshape_order = reshape_order != 0;
+  s.w_src = w_src, s.w_tar = w_tar, s.c = c, s.sigma_in = sigma_in, s.seeds = (const unsigned long long*)seeds, s.draw = draw, s.prime = prime != 0;
+  return DK_EL(dtype, dk_launch_flowedit_step)(s, S_(stream));
+}
+extern "C" int dk_flowedit_step(float* z, const float* x_src, const void* model_out, int32_t ld_out, void* tokens, float* zs_out, float* zt_out,
+                                int32_t n_img, int32_t cfg_on, int32_t Hl, int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float w_src,
+                                float w_tar, float c, float sigma_in, const uint64_t* seeds, int32_t draw, int32_t prime, void* stream) {
+  return flowedit_step(DK_DTYPE_BF16, z, x_src, model_out, ld_out, tokens, zs_out, zt_out, n_img, cfg_on, Hl, Wl, C, p, reshape_order, w_src, w_tar, c,
+                       sigma_in, seeds, draw, prime, stream);
+}
+extern "C" int dk_flowedit_step_f16(float* z, const float* x_src, const void* model_out, int32_t ld_out, void* tokens, float* zs_out, float* zt_out,
+                                    int32_t n_img, int32_t cfg_on, int32_t Hl, int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float w_src,
+                                    float w_tar, float c, float sigma_in, const uint64_t* seeds, int32_t draw, int32_t prime, void* stream) {
+  return flowedit_step(DK_DTYPE_F16, z, x_src, model_out, ld_out, tokens, zs_out, zt_out, n_img, cfg_on, Hl, Wl, C, p, reshape_order, w_src, w_tar, c,
+                       sigma_in, seeds, draw, prime, stream);
+}
+
 extern "C" int dk_mask_to_latent_f32(const uint8_t* mask, float* out, int32_t n_mask, int32_t H, int32_t W, int32_t f, void* stream) {
   DK_REQUIRE(mask && out, "null argument");
   DK_REQUIRE(n_mask > 0, "n_mask must be positive");

@@ -87,6 +87,25 @@ struct StepParams {
 #endif
 size_t dk_guidance_workspace_size(int n_img, int Hl, int Wl, int C);
 int dk_launch_step(const StepParams& s, hipStream_t stream);
+// FlowEdit (include/dk_hip.h: dk_flowedit_step): z' = z + c (V_tar - V_src) from the rows [src | tar] or [src+ | tar+ | src- | tar-] of model_out
+// (n_img each; prime: not read, z stays), then Zs = (1 - sigma_in) x_src + sigma_in xi and Zt = Zs + (z' - x_src) with xi drawn in the launch
+// (seeds[img], draw, stream tag 1), written in fp32 (zs_out may be null) and as the tokens of the same rows.  One struct for both element types.
+#ifndef DK_FLOWEDIT_PARAMS
+#define DK_FLOWEDIT_PARAMS
+struct FlowEditParams {
+  float* z;
+  const float* x_src;
+  const bf16_t* model_out;
+  int ld_out;
+  bf16_t* tok;
+  float *zs_out, *zt_out;
+  int n_img, cfg_on, Hl, Wl, C, p, reshape_order;
+  float w_src, w_tar, c, sigma_in;
+  const unsigned long long* seeds;
+  int draw, prime;
+};
+#endif
+int dk_launch_flowedit_step(const FlowEditParams& s, hipStream_t stream);
 // first-block cache (include/dk_hip.h): d = round(x - d) over M rows of x through the row map, (num, den) = (sum |d - d_ref|, sum |d_ref|) per
 // row into row_partials [M][2], then per rows_per_batch rows in a fixed order into probe [M / rows_per_batch][2]; d_ref null: read as zeros
 int dk_launch_block_probe(const bf16_t* x, int ldx, int x_seg_len, int x_seg_stride, bf16_t* d, const bf16_t* d_ref, float* row_partials,

@@ -1194,3 +1194,113 @@ int dk_launch_block_residual(bf16_t* x, int ldx, int x_seg_len, int x_seg_stride
   DK_CHECK_HIP(hipGetLastError());
   return 0;
 }
+
+// ---------------------------------------------------------------------------------------------
+// FlowEdit (include/dk_hip.h: dk_flowedit_step; Kulikov et al. 2024; no reference counterpart): the step of an edit loop whose state Z starts at
+// the encoded source image x_src and moves by the difference of two evaluations of the model, one on a noised source Zs with the source prompt
+// and one on Zt = Zs + (Z - x_src) with the target prompt,
+//   Z' = Z + c (V_tar - V_src),   xi = philox_normal(seeds[img], r / 4, draw, stream 1, r % 4),
+//   Zs = (1 - sigma_in) x_src + sigma_in xi,   Zt = Zs + (Z' - x_src),
+// V the model's output itself, under CFG neg + w (pos - neg) with a weight per side.  Batch rows of model_out and tok, n_img each:
+// [src | tar] or [src+ | tar+ | src- | tar-].  prime: model_out is not read and Z is neither changed nor written (the launch that forms the
+// first inputs).  Zs and Zt leave in fp32 (zs_out may be null) and, rounded, as the tokens of the source and target rows -- under CFG of both
+// copies, dk_latent_to_tokens's layout for 2 n_img images.
+// One thread per Philox quad: the four elements r .. r + 3 are four channels of one cell (C % 4 == 0), so the fp32 operands move as 16-byte
+// accesses, the ten rounds run once per quad instead of once per element, and with the SD3 patch order (features (ph, pw, c)) the four
+// features are neighbours too: one 8-byte access per batch row.  FLUX's order (c, ph, pw) spreads them p * p apart: four 2-byte accesses
+// inside one token's row.  Z + c * 0 and Zs + 0 are exact: equal source and target rows with equal weights leave Z's bits, and Z == x_src
+// gives Zt the bits of Zs (but for the sign of a zero).
+// ---------------------------------------------------------------------------------------------
+struct FlowEditArgs {
+  float w_src, w_tar, c, sigma_in;
+  const unsigned long long* seeds;
+  unsigned draw;
+  int prime;
+};
+struct Quad16 {
+  bf16_t v[4];
+};
+// the four features of a quad in batch row `row`: f0, f0 + fs, ...; fs == 1 takes them in one access (8-byte aligned: the launcher's checks)
+__device__ __forceinline__ void flowedit_load(const bf16_t* base, int fs, float* o) {
+  if (fs == 1) {
+    const Quad16 q = *(const Quad16*)__builtin_assume_aligned(base, 8);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = to_f32(q.v[j]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = to_f32(base[j * fs]);
+  }
+}
+__device__ __forceinline__ void flowedit_store(bf16_t* base, int fs, const Quad16& q) {
+  if (fs == 1) {
+    *(Quad16*)__builtin_assume_aligned(base, 8) = q;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) base[j * fs] = q.v[j];
+  }
+}
+__global__ __launch_bounds__(256) void dk_flowedit_step_kernel(float* z, const float* x_src, const bf16_t* model_out, int ld_out, bf16_t* tok,
+                                                               float* zs_out, float* zt_out, int n_img, int cfg_on, int Hl, int Wl, int C, int p,
+                                                               int reshape_order, FlowEditArgs a) {
+  const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long quads_per_img = (long)Hl * Wl * C / 4;
+  if (q >= quads_per_img * n_img) return;
+  const int img = (int)(q / quads_per_img);
+  const long qi = q % quads_per_img;
+  const long i = q * 4;
+  const StepCell k = step_cell(img, qi * 4, Hl, Wl, C, p, reshape_order);  // (of the quad's first element; the other three: the next channels)
+  const int fs = reshape_order ? p * p : 1;
+  const float4 xs = *(const float4*)(x_src + i);
+  float4 zv = *(const float4*)(z + i);
+  float zz[4] = {zv.x, zv.y, zv.z, zv.w};
+  const float xx[4] = {xs.x, xs.y, xs.z, xs.w};
+  if (!a.prime) {
+    const size_t at = ((size_t)img * k.S_i + k.t) * ld_out + k.f, group = (size_t)n_img * k.S_i * ld_out;  // (row b: at + b * group)
+    float vs[4], vt[4];
+    flowedit_load(model_out + at, fs, vs);
+    flowedit_load(model_out + at + group, fs, vt);
+    if (cfg_on) {
+      float ns[4], nt[4];
+      flowedit_load(model_out + at + 2 * group, fs, ns);
+      flowedit_load(model_out + at + 3 * group, fs, nt);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        vs[j] = ns[j] + a.w_src * (vs[j] - ns[j]);
+        vt[j] = nt[j] + a.w_tar * (vt[j] - nt[j]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) zz[j] = zz[j] + a.c * (vt[j] - vs[j]);
+    *(float4*)(z + i) = make_float4(zz[0], zz[1], zz[2], zz[3]);
+  }
+  const unsigned long long seed = a.seeds[img];
+  const float keep = 1.0f - a.sigma_in;
+  float zs[4], zt[4];
+  Quad16 ts, tt;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float xi = philox_normal(seed, (unsigned long long)qi, a.draw, 1u, j);
+    zs[j] = keep * xx[j] + a.sigma_in * xi;
+    zt[j] = zs[j] + (zz[j] - xx[j]);
+    ts.v[j] = from_f32(zs[j]);
+    tt.v[j] = from_f32(zt[j]);
+  }
+  if (zs_out) *(float4*)(zs_out + i) = make_float4(zs[0], zs[1], zs[2], zs[3]);
+  *(float4*)(zt_out + i) = make_float4(zt[0], zt[1], zt[2], zt[3]);
+  const size_t tat = ((size_t)img * k.S_i + k.t) * k.F + k.f, tgroup = (size_t)n_img * k.S_i * k.F;
+  flowedit_store(tok + tat, fs, ts);
+  flowedit_store(tok + tat + tgroup, fs, tt);
+  if (cfg_on) {
+    flowedit_store(tok + tat + 2 * tgroup, fs, ts);
+    flowedit_store(tok + tat + 3 * tgroup, fs, tt);
+  }
+}
+int dk_launch_flowedit_step(const FlowEditParams& s, hipStream_t stream) {
+  const long n_quads = (long)s.n_img * s.Hl * s.Wl * s.C / 4;
+  DK_REQUIRE((n_quads + 255) / 256 <= 0x7fffffffL, "flowedit_step: size");
+  const FlowEditArgs a = {s.w_src, s.w_tar, s.c, s.sigma_in, s.seeds, (unsigned)s.draw, s.prime};
+  hipLaunchKernelGGL(dk_flowedit_step_kernel, dim3((unsigned)((n_quads + 255) / 256)), dim3(256), 0, stream, s.z, s.x_src, s.model_out, s.ld_out, s.tok,
+                     s.zs_out, s.zt_out, s.n_img, s.cfg_on, s.Hl, s.Wl, s.C, s.p, s.reshape_order, a);
+  DK_CHECK_HIP(hipGetLastError());
+  return 0;
+}

@@ -77,6 +77,9 @@ struct dk_mmdit {
   const bf16_t *g0_w = nullptr, *g0_b = nullptr, *g2_w = nullptr, *g2_b = nullptr;
   float guidance = 3.5f;
   bf16_t *gemb = nullptr, *g1 = nullptr, *gvec = nullptr;
+  // ... or one value per batch row (dk_mmdit_set_guidance_rows; empty: the scalar above): 1000 g[b] as the embedding takes it.  The B-row twins of
+  // the scratch rows live in QKV while the table is computed (dk_mmdit_cache_modulation_params): the workspace is the size it was
+  std::vector<float> g_rows;
   // fp8_linears: MX-fp8 activation buffers + their scale side arrays (layout dk_mx_scale_index)
   unsigned char *XN8 = nullptr, *ATT8 = nullptr, *HC8 = nullptr;    // [rows8, h], [rows8, h], max([rows8, ldh8], [rows8, ldcat8])
   unsigned char *SXN = nullptr, *SATT = nullptr, *SHID = nullptr, *SCAT = nullptr;
@@ -219,6 +222,22 @@ extern "C" int dk_mmdit_set_guidance(dk_mmdit* m, float guidance) {
   DK_REQUIRE(m != nullptr, "null handle");
   DK_REQUIRE(m->cfg.guidance_embed, "this configuration has no guidance embedding (guidance_embed = 0)");
   m->guidance = guidance;
+  m->mod_ready = false;
+  return 0;
+}
+extern "C" int dk_mmdit_set_guidance_rows(dk_mmdit* m, const float* g, int32_t n) {
+  DK_REQUIRE(m != nullptr, "null handle");
+  DK_REQUIRE(m->cfg.guidance_embed, "this configuration has no guidance embedding (guidance_embed = 0)");
+  if (g == nullptr || n == 0) {  // back to the scalar of dk_mmdit_set_guidance
+    if (!m->g_rows.empty()) m->mod_ready = false;
+    m->g_rows.clear();
+    return 0;
+  }
+  DK_REQUIRE(m->prepared, "dk_mmdit_prepare must precede dk_mmdit_set_guidance_rows: the rows are those of the prepared batch");
+  DK_REQUIRE(n == m->B, "guidance rows: n must be the prepared batch");
+  for (int b = 0; b < n; ++b) DK_REQUIRE(std::isfinite(g[b]), "guidance rows must be finite");
+  m->g_rows.resize(n);
+  for (int b = 0; b < n; ++b) m->g_rows[b] = 1000.0f * g[b];
   m->mod_ready = false;
   return 0;
 }
@@ -532,6 +551,7 @@ extern "C" int dk_mmdit_prepare(dk_mmdit* m, int32_t batch, int32_t latent_h, in
   Carver c(workspace, workspace_bytes);
   const size_t need_bytes = mmdit_carve(m, c, batch, latent_h, latent_w, text_len, n_timesteps);
   DK_REQUIRE(need_bytes <= workspace_bytes, "workspace too small");
+  m->g_rows.clear();  // (they were the rows of the batch prepared before)
   m->B = batch; m->Hl = latent_h; m->Wl = latent_w; m->S_t = text_len;
   m->S_i = (latent_h / p) * (latent_w / p); m->S_r = m->ref_rows(p); m->S_x = m->S_i + m->S_r; m->S = m->S_t + m->S_x; m->n_t = n_timesteps;
   hipStream_t st = S_(stream);
@@ -655,7 +675,21 @@ extern "C" int dk_mmdit_cache_modulation_params(dk_mmdit* m, const void* pooled,
   DK_TRY(dk_launch_gemm(Linear(dt, dense(m->t1, h), m->t2_w, m->t2_b, dense(m->tvec, h), n, h, h, DK_EPI_BIAS), st));
   DK_TRY(dk_launch_gemm(Linear(dt, dense((const bf16_t*)pooled, P), m->y0_w, m->y0_b, dense(m->y1, h), B, h, P, DK_EPI_BIAS_SILU), st));
   DK_TRY(dk_launch_gemm(Linear(dt, dense(m->y1, h), m->y2_w, m->y2_b, dense(m->yvec, h), B, h, h, DK_EPI_BIAS), st));
-  if (m->cfg.guidance_embed) {
+  if (m->cfg.guidance_embed && !m->g_rows.empty()) {
+    // ... with a value per batch row (dk_mmdit_set_guidance_rows): the same three launches on B rows, and y[b] += g[b] row by row.  Their scratch
+    // -- B values, B embeddings, B hidden rows, B vectors -- is the head of QKV, which no launch reads or writes outside a forward (same stream)
+    const size_t o1 = align_up((size_t)B * 4, 256), o2 = o1 + align_up((size_t)B * Fq * 2, 256), o3 = o2 + align_up((size_t)B * h * 2, 256);
+    DK_REQUIRE(o3 + (size_t)B * h * 2 <= (size_t)B * m->S * 3 * h * 2, "guidance rows: the QKV buffer is too small for their scratch");
+    char* const scratch = (char*)m->QKV;
+    float* const gdev = (float*)scratch;
+    bf16_t *const gemb = (bf16_t*)(scratch + o1), *const g1 = (bf16_t*)(scratch + o2), *const gvec = (bf16_t*)(scratch + o3);
+    DK_CHECK_HIP(hipMemcpyAsync(gdev, m->g_rows.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
+    DK_TRY(DK_EL(dt, dk_launch_timestep_embedding)(gdev, B, 1, Fq, (float)m->cfg.max_period, m->cfg.embed_dtype, gemb, st));
+    DK_TRY(dk_launch_gemm(Linear(dt, dense(gemb, Fq), m->g0_w, m->g0_b, dense(g1, h), B, h, Fq, DK_EPI_BIAS_SILU), st));
+    DK_TRY(dk_launch_gemm(Linear(dt, dense(g1, h), m->g2_w, m->g2_b, dense(gvec, h), B, h, h, DK_EPI_BIAS), st));
+    for (int b = 0; b < B; ++b)
+      DK_TRY(DK_EL(dt, dk_launch_add)(m->yvec + (size_t)b * h, gvec + (size_t)b * h, 1, m->yvec + (size_t)b * h, 1, h, st));
+  } else if (m->cfg.guidance_embed) {
     // FLUX.1-dev guidance embedding (MLPEmbedder, mmdit.py:31-36,945-955): g = guidance_in(timestep_embedding(1000 * guidance)),
     // added to the pooled-text embedding of every batch row, hence to every modulation vector
     const float gt = 1000.0f * m->guidance;

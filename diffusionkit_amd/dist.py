@@ -63,6 +63,8 @@ def generate_sharded(pipe, text: str, seeds: Sequence[int], rank: int, world: in
         raise ValueError("a ControlNet cannot run under multi-GPU sharding: its per-image control images are not cut with the seeds yet")
     if getattr(pipe, "ip_adapter_config", None) is not None or any(k.startswith("ip_adapter_") for k in kw):
         raise ValueError("an IP-Adapter cannot run under multi-GPU sharding: its per-image embeddings are not cut with the seeds yet")
+    if any(k.startswith("edit_") for k in kw):
+        raise ValueError("an edit (edit_source_text) cannot run under multi-GPU sharding: its per-image source images are not cut with the seeds yet")
     mine = shard_seeds(seeds, rank, world)
     if not mine:
         return None

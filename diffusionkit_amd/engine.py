@@ -266,9 +266,12 @@ class MMDiTEngine:
         return float(self.lib.dk_mmdit_score_bound(self._h, kind, index))
 
     # -- reference API ---------------------------------------------------------------------
-    def cache_modulation_params(self, pooled_text_embeddings: Tensor, timesteps: Sequence[float]) -> None:
+    def cache_modulation_params(self, pooled_text_embeddings: Tensor, timesteps: Sequence[float], guidance_rows=None) -> None:
         """MMDiT.cache_modulation_params (mmdit.py:77-180); ``timesteps`` are host floats
-        already rounded to the activation dtype (quirk Q1)."""
+        already rounded to the activation dtype (quirk Q1).
+        ``guidance_rows`` (configurations with ``guidance_embed``; dk_mmdit_set_guidance_rows): one guidance strength per batch row in place of
+        ``self.guidance`` for this table -- FlowEdit evaluates its source and target rows at different values.  None: the scalar, and a table
+        cached without the keyword after one with it is the scalar's again."""
         if self._shape is None:
             raise _lib.DkHipError("prepare() must be called before cache_modulation_params()")
         pooled = pooled_text_embeddings.to(self.dtype).contiguous()
@@ -276,13 +279,32 @@ class MMDiTEngine:
         if pooled.shape != (self._shape[0], self.config.pooled_text_embed_dim):
             raise _lib.DkHipError(f"pooled_text_embeddings shape {tuple(pooled.shape)} != (batch, pooled_dim)")
         ts = [float(t) for t in timesteps]
+        if guidance_rows is not None and not self.config.guidance_embed:
+            raise _lib.DkHipError("guidance_rows needs a configuration with a guidance embedding (guidance_embed)")
         if self.config.guidance_embed:
             _lib.check(self.lib.dk_mmdit_set_guidance(self._h, float(self.guidance)), "dk_mmdit_set_guidance")
+        if guidance_rows is not None:
+            g = [float(v) for v in guidance_rows]
+            if len(g) != self._shape[0]:
+                raise _lib.DkHipError(f"guidance_rows holds {len(g)} values, the prepared batch has {self._shape[0]} rows")
+            _lib.check(self.lib.dk_mmdit_set_guidance_rows(self._h, (C.c_float * len(g))(*g), len(g)), "dk_mmdit_set_guidance_rows")
+            self._guidance_rows_set = True
+        elif getattr(self, "_guidance_rows_set", False):  # (never set: the engine is not told, its calls are what they were)
+            _lib.check(self.lib.dk_mmdit_set_guidance_rows(self._h, None, 0), "dk_mmdit_set_guidance_rows")
+            self._guidance_rows_set = False
         arr = (C.c_float * len(ts))(*ts)
         _lib.check(self.lib.dk_mmdit_cache_modulation_params(self._h, pooled.data_ptr(), arr, len(ts), _stream()),
                    "dk_mmdit_cache_modulation_params")
         self._pooled_keepalive = pooled
         self._n_cached = len(ts)
+
+    def clear_guidance_rows(self) -> None:
+        """Back to the scalar ``self.guidance`` if ``cache_modulation_params(..., guidance_rows=...)`` set per-row values: the table must be cached
+        again before the next forward.  Nothing is called on an engine that never had rows."""
+        if getattr(self, "_guidance_rows_set", False):
+            _lib.check(self.lib.dk_mmdit_set_guidance_rows(self._h, None, 0), "dk_mmdit_set_guidance_rows")
+            self._guidance_rows_set = False
+            self._n_cached = 0
 
     def cache_context(self, text: Tensor) -> None:
         """Step-invariant hoist of ``context_embedder(text)`` (mmdit.py:195): embedded once here, ``forward_tokens(..., None, i)``

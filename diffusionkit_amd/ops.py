@@ -795,6 +795,48 @@ def noisy_cfg_step(x: Tensor, model_out: Tensor, tokens: Tensor, n_img: int, cfg
           slg_scale=0.0 if slg_scale is None else slg_scale, noise_term=(guided, slg_scale is not None, cn, seeds, draw))
 
 
+def flowedit_step(z: Tensor, x_src: Tensor, model_out: Optional[Tensor], tokens: Tensor, zt_out: Tensor, n_img: int, cfg_on: bool, p: int,
+                  reshape_order: int, *, c: float, sigma_in: float, seeds: Tensor, draw: int, w_src: float = 1.0, w_tar: float = 1.0,
+                  zs_out: Optional[Tensor] = None, prime: bool = False) -> None:
+    """dk_flowedit_step / _f16 by the dtype of ``tokens``: the step of the FlowEdit loop (``sampler.flowedit_reference``).  ``z`` f32 [n_img, Hl, Wl,
+    C] takes ``c`` (V_tar - V_src) in place, V the rows of ``model_out`` -- [src | tar], or under ``cfg_on`` [src+ | tar+ | src- | tar-] combined as
+    neg + w (pos - neg) with ``w_src`` / ``w_tar`` -- then Zs = (1 - ``sigma_in``) ``x_src`` + ``sigma_in`` xi and Zt = Zs + (z - ``x_src``) are
+    written to ``zs_out`` (optional) and ``zt_out`` (f32 like z) and, rounded and patchified, to the same rows of ``tokens``.  xi: the normals of
+    ``seeds[img]`` (``seed_tensor``) for draw ``draw`` on stream 1, ``philox_normal(seeds, n, draw, stream=1)``'s values, formed in the launch.
+    ``prime``: ``model_out`` is not read (may be None) and ``z`` stays; the launch that forms the first inputs."""
+    what = "flowedit_step"
+    name = "dk_" + what + ("" if _elem(tokens.dtype, what) == "bf16" else "_f16")
+    rows = (4 if cfg_on else 2) * n_img
+    _require_cuda(z, "z", torch.float32)
+    _require_cuda(tokens, "tokens")
+    if z.dim() != 4 or z.shape[0] != n_img:
+        raise _lib.DkHipError(f"{what}: z {tuple(z.shape)} must be [n_img = {n_img}, Hl, Wl, C]")
+    _, hl, wl, ch = z.shape
+    for n, t in (("x_src", x_src), ("zt_out", zt_out), ("zs_out", zs_out)):
+        if t is None and n == "zs_out":
+            continue
+        _require_cuda(t, n, torch.float32)
+        if t.shape != z.shape:
+            raise _lib.DkHipError(f"{what}: {n} {tuple(t.shape)} must have the latent's shape {tuple(z.shape)}")
+    if hl % p or wl % p:
+        raise _lib.DkHipError(f"{what}: latent size {(hl, wl)} must be divisible by the patch size {p}")
+    s_i, f = (hl // p) * (wl // p), p * p * ch
+    if tuple(tokens.shape) != (rows, s_i, f):
+        raise _lib.DkHipError(f"{what}: tokens {tuple(tokens.shape)} must be [{rows}, {s_i}, {f}]: {'4' if cfg_on else '2'} * n_img batch rows")
+    if model_out is None:
+        if not prime:
+            raise _lib.DkHipError(f"{what}: model_out is None while the launch reads it (prime = False)")
+    else:
+        _require_cuda(model_out, "model_out", tokens.dtype)
+        if model_out.dim() != 3 or tuple(model_out.shape[:2]) != (rows, s_i) or model_out.shape[2] < f:
+            raise _lib.DkHipError(f"{what}: model_out {tuple(model_out.shape)} must be [{rows}, {s_i}, >= {f}]")
+    _require_seeds(seeds, n_img, what)
+    _lib.check(getattr(_lib.load(), name)(z.data_ptr(), x_src.data_ptr(), _ptr(model_out), f if model_out is None else model_out.shape[-1],
+                                          tokens.data_ptr(), _ptr(zs_out), zt_out.data_ptr(), n_img, int(bool(cfg_on)), hl, wl, ch, p, int(reshape_order),
+                                          float(w_src), float(w_tar), float(c), float(sigma_in), seeds.data_ptr(), int(draw), int(bool(prime)), _stream()),
+               name)
+
+
 def mask_to_latent(mask: Tensor, factor: int = 8) -> Tensor:
     """dk_mask_to_latent_f32: uint8 [n_mask, H, W] (or [H, W]) -> f32 [n_mask, H / factor, W / factor], box sum / (factor^2 * 255)."""
     _require_cuda(mask, "mask", torch.uint8)

@@ -15,6 +15,9 @@ step's own launch (dk_euler_cfg_step_masked), and ``generate_image`` pastes the 
 
 Samplers (``sampler=``, keyword-only, no reference counterpart): "euler" (default: the reference's loop, ``sample_euler``), "heun" and "ab2" run
 ``sample_steps`` over the rows of ``sampler.step_plan`` -- one launch of dk_lms_cfg_step (or its masked form) behind every model evaluation.
+FlowEdit (``edit_source_text=``, ``edit_steps=``, ``edit_n_avg=``, ``edit_source_cfg=``, keyword-only, no reference counterpart): text-guided editing
+of ``image_path`` with the plain checkpoint -- ``sample_flowedit``, one launch of dk_flowedit_step behind every model evaluation, the source and the
+target of a draw as batch rows of one evaluation, the noise drawn in the launch.
 The stochastic samplers "euler_a" (``sampler_eta=``) and "sde" are rows with one more term, cn xi: their launch is dk_noisy_cfg_step, which draws xi
 inside the launch from a counter (Philox4x32-10 keyed by the image's own seed), so no noise is drawn on the host, uploaded or stored per step.
 
@@ -588,8 +591,17 @@ class DiffusionPipeline:
         controlnet_interval=None,
         ip_adapter_image_embeds=None,
         ip_adapter_scale: float = 1.0,
+        edit_source_text=None,
+        edit_steps=None,
+        edit_n_avg=None,
+        edit_source_cfg=None,
     ):
-        """``ip_adapter_image_embeds`` (a pipeline built with ``ip_adapter_ckpt``; an array or tensor [E], [n, E] with n = 1 or one row per seed, or a
+        """``edit_source_text`` (FlowEdit, Kulikov et al. 2024; text-guided editing of ``image_path`` with the plain checkpoint): the prompt that
+        describes the source image -- a string, encoded here with ``encode_text``, or an already encoded (conditioning, pooled_conditioning) pair
+        laid out like this call's own -- while ``conditioning`` describes what the image should become.  See ``_denoise_edit`` for ``edit_steps`` =
+        (n_max, n_min), ``edit_n_avg`` and ``edit_source_cfg``, what it composes with and what it refuses.  ``self.last_edit`` says what ran; None
+        without the option, and then every launch and every bit is what it was.
+        ``ip_adapter_image_embeds`` (a pipeline built with ``ip_adapter_ckpt``; an array or tensor [E], [n, E] with n = 1 or one row per seed, or a
         list with one [E] per seed): the prepared image embedding(s) of the image prompt -- CLIP ViT-L/14 ``image_embeds``, diffusers'
         ``ip_adapter_image_embeds=``; the vision tower is not part of this build.  They are projected to the adapter's tokens once per call
         (``engine.ip_adapter_project``), every double block's keys and values are cached (``MMDiTEngine.cache_ip_tokens``), and every model evaluation
@@ -674,6 +686,28 @@ class DiffusionPipeline:
         inpainting and float16.  Raises on FLUX, ``cfg_weight <= 0``, ``block_cache``, an fp8 engine, a reference image, a condition and together
         with skip-layer guidance (there is one fork).  ``self.last_perturbed_attention_guidance`` = {"layers", "scale", "interval", "evals"}, or
         None.  Verified as arithmetic only, on synthetic weights: no checkpoint has been run here."""
+        self.last_edit = None
+        if edit_source_text is None:
+            if edit_steps is not None or edit_n_avg is not None or edit_source_cfg is not None:
+                raise ValueError("edit_steps, edit_n_avg and edit_source_cfg belong to an edit: give edit_source_text, the prompt that describes image_path")
+        else:
+            refused = {"mask_path (inpainting)": mask_path, "block_cache": block_cache,
+                       "a guidance mode other than 'cfg'": None if guidance in (None, "cfg") else guidance, "guidance_interval": guidance_interval,
+                       "skip-layer guidance": next((v for v in (skip_layer_guidance, skip_layers, skip_layer_interval) if v is not None), None),
+                       "perturbed-attention guidance": next((v for v in (pag_scale, pag_layers, pag_interval) if v is not None), None),
+                       "a ControlNet": controlnet_image_path if controlnet_image_path is not None else getattr(self, "controlnet", None),
+                       "an IP-Adapter": ip_adapter_image_embeds if ip_adapter_image_embeds is not None else getattr(self, "ip_adapter_config", None),
+                       "a reference image": reference_image_path,
+                       "channel-concatenated conditioning (condition=)": condition_image_path if condition_image_path is not None
+                       else getattr(self, "condition", None)}
+            for what, value in refused.items():
+                if value is not None:
+                    raise ValueError(_flowedit_refusal(what))
+            if denoise != 1.0:
+                raise ValueError("an edit (edit_source_text) cannot run together with denoise (img2img strength): the edit starts from the image itself, "
+                                 "and edit_steps = (n_max, n_min) says which part of the schedule it covers")
+            return self._denoise_edit(conditioning, pooled_conditioning, num_steps, cfg_weight, seed, image_path, sampler, sampler_eta, edit_source_text,
+                                      edit_steps, edit_n_avg, edit_source_cfg)
         check_condition_args(getattr(self, "condition", None), condition_image_path, condition_mask_path, reference_image_path, self._IS_FLUX)
         if reference_image_path is not None and not self._IS_FLUX:
             raise ValueError(_REFERENCE_NEEDS_ROPE)
@@ -791,6 +825,116 @@ class DiffusionPipeline:
         latent = self.latent_format.process_out(latent)
         return latent, iter_time
 
+    def _denoise_edit(self, conditioning, pooled_conditioning, num_steps, cfg_weight, seed, image_path, sampler, sampler_eta, source, edit_steps,
+                      n_avg, source_cfg):
+        """``denoise_latents`` under ``edit_source_text``: FlowEdit.  ``image_path`` (a path, a PIL image or an array, or a list with one per seed) is
+        VAE-encoded to the posterior's MEAN, as Fill and Kontext take it, and put through ``process_in``: that is x_src, and the latent size is the
+        image's.  Z starts there and takes, for the steps T - n_max .. T - n_min - 1 of the ``num_steps`` = T schedule, (sigma' - sigma) times the
+        mean over ``edit_n_avg`` draws of V(Zt, target) - V(Zs, source), Zs = (1 - sigma) x_src + sigma xi and Zt = Zs + (Z - x_src)
+        (``sample_flowedit``; the definition is ``sampler.flowedit_reference``).  With n_min > 0 one more draw forms Zt at sigmas[T - n_min], and
+        the ordinary loop -- whatever ``sampler`` names -- takes it to sigma 0 with the target conditioning alone.
+        ``edit_steps`` = (n_max, n_min) with 0 <= n_min < n_max <= num_steps; ``edit_n_avg`` >= 1 (default 1).  ``edit_source_cfg``: the source's CFG
+        weight on the SD3 family (``cfg_weight`` is the target's; both must be positive), the source's distilled-guidance value on FLUX.1-dev
+        (``self.mmdit.guidance`` is the target's: the engine then embeds one value per batch row); refused on a FLUX model without a guidance
+        embedding (FLUX.1-schnell).  Defaults, ``sampler.FLOWEDIT_DEFAULTS``, are the paper's settings AS RECALLED and have NOT been verified against
+        the paper or the authors' code: n_max = 33 of T = 50 with source 3.5 / target 13.5 (SD3), n_max = 24 of T = 28 with 1.5 / 5.5 (FLUX.1-dev);
+        without ``edit_steps`` n_max is that share of ``num_steps``, rounded, and n_min 0.
+        The noise is drawn inside the step launch from Philox keyed by each image's seed (stream tag 1; a stochastic sampler in the tail draws
+        on tag 0), so a result depends on its seed alone: a seed list gives each image the bits of its single-seed run.  Composes with seed lists
+        (one image for all seeds, or one per seed), both families, CFG and float16; fp8 engines take the same launches, untested beyond
+        construction.  ``self.last_edit`` = {"n_max", "n_min", "n_avg", "model_evals", "draws", "rows", "source_cfg", "target_cfg",
+        "guidance_rows", "tail_evals"}.  Arithmetic only, on synthetic weights: nothing here says anything about image quality."""
+        from .sampler import FLOWEDIT_DEFAULTS, check_flowedit
+        if image_path is None:
+            raise ValueError("an edit (edit_source_text) needs image_path: the image to edit")
+        family = "flux" if self._IS_FLUX else "sd3"
+        t_ref, nmax_ref, nmin_ref, src_ref, _ = FLOWEDIT_DEFAULTS[family]
+        if edit_steps is None:
+            edit_steps = (max(1, min(int(num_steps), round(num_steps * nmax_ref / t_ref))), nmin_ref)
+        if len(tuple(edit_steps)) != 2:
+            raise ValueError(f"edit_steps must be (n_max, n_min), got {edit_steps!r}")
+        n_max, n_min, n_avg = check_flowedit(num_steps, edit_steps[0], edit_steps[1], 1 if n_avg is None else n_avg)
+        cfg_on = cfg_weight > 0
+        guided_model = bool(self.mmdit_config.guidance_embed)
+        grow_values = None
+        if self._IS_FLUX:
+            if source_cfg is not None and not guided_model:
+                raise ValueError("edit_source_cfg on the FLUX family is the source's distilled-guidance value: this model has no guidance embedding "
+                                 "(FLUX.1-schnell)")
+            w_src = float(cfg_weight)
+            if guided_model:
+                grow_values = (float(src_ref if source_cfg is None else source_cfg), float(self.mmdit.guidance))
+        else:
+            w_src = float(src_ref if source_cfg is None else source_cfg)
+            if not cfg_on or not w_src > 0:
+                raise ValueError("an edit on the SD3 family needs classifier-free guidance on both sides (cfg_weight > 0 and edit_source_cfg > 0)")
+        sampler = check_sampler(sampler)
+        eta = check_sampler_eta(sampler, sampler_eta)
+        seed = int(time.time()) if seed is None else seed
+        seeds = [int(s) for s in (seed if isinstance(seed, (list, tuple)) else [seed])]
+        logger.info(f"Seed: {seeds}")
+        n = len(seeds)
+        images = list(image_path) if isinstance(image_path, (list, tuple)) else [image_path]
+        if len(images) not in (1, n):
+            raise ValueError(f"{len(images)} source images for {n} seeds: give one image, or one per seed")
+        if isinstance(source, str):
+            source = self.encode_text(source, cfg_weight, "")
+        src_c, src_p = source
+        if src_c.dim() == 4:
+            src_c = src_c.squeeze(2)
+        if conditioning.dim() == 4:
+            conditioning = conditioning.squeeze(2)
+        tar_c, tar_p = _tile_conditioning(conditioning, pooled_conditioning, n, cfg_on, self._IS_FLUX)
+        src_c, src_p = _tile_conditioning(src_c, src_p, n, cfg_on, self._IS_FLUX)
+        rows = n * (2 if cfg_on else 1)
+        for what, t in (("conditioning", tar_c), ("edit_source_text", src_c)):
+            if t.shape[0] != rows:
+                raise ValueError(f"{what} has {t.shape[0]} rows for {n} images{' with CFG' if cfg_on else ''}: expected {rows}")
+        if src_c.shape[1:] != tar_c.shape[1:]:
+            raise ValueError(f"the source conditioning {tuple(src_c.shape)} and the target conditioning {tuple(tar_c.shape)} differ in length or width")
+        # [src | tar], or [src+ | tar+ | src- | tar-]: 2 n images whose rows are laid out per image
+        pair = lambda a, b: torch.cat([t.to(self.device) for k in range(0, rows, n) for t in (a[k:k + n], b[k:k + n])], 0)  # noqa: E731
+        x_src = torch.cat([self.latent_format.process_in(self.encode_mean_latents(self.read_image(im))) for im in images], 0)
+        if len(images) == 1 and n > 1:
+            x_src = x_src.expand(n, *x_src.shape[1:])
+        x_src = x_src.to(torch.float32).contiguous()
+        sigmas = self.get_sigmas(self.sampler, num_steps)
+        denoiser = CFGDenoiser(self)
+        extra_args = {"conditioning": pair(src_c, tar_c), "pooled_conditioning": pair(src_p, tar_p), "cfg_weight": cfg_weight, "noise_seeds": seeds,
+                      "edit_source_cfg": w_src}
+        if grow_values is not None:
+            extra_args["edit_guidance_rows"] = [g for _ in range(0, rows, n) for g in grow_values for _ in range(n)]
+        z, zt, iter_time = sample_flowedit(denoiser, x_src, sigmas, n_max, n_min, n_avg, extra_args=extra_args)
+        record = dict(denoiser.flowedit_record, tail_evals=0)
+        latent, evals, draws = z, record["model_evals"], 0
+        stochastic = sampler in STOCHASTIC_SAMPLERS
+        if n_min > 0:  # the paper's "regular sampling" tail: the ordinary loop on the cut schedule, the target rows alone
+            cut = int(num_steps) - n_min
+            tail_args = {"conditioning": tar_c, "pooled_conditioning": tar_p, "cfg_weight": cfg_weight}
+            rows_name = "euler" if sampler == "euler_a" and eta == 0.0 else sampler
+            if rows_name == "euler":
+                latent, tail_time = sample_euler(denoiser, zt, sigmas[cut:], extra_args=tail_args)
+                tail_evals = len(tail_time)
+            else:
+                plan = step_plan(rows_name, sigmas[cut:], eta if rows_name == "euler_a" else None, first_draw=cut)
+                draws = sum(r.cn != 0.0 for r in plan)
+                if draws:
+                    tail_args["noise_seeds"] = seeds
+                latent, tail_time = sample_steps(denoiser, zt, sigmas[cut:], plan, extra_args=tail_args)
+                tail_evals = len(plan)
+            iter_time = iter_time + tail_time
+            evals += tail_evals
+            record.update(tail_evals=tail_evals, model_evals=evals)
+        self.last_edit = record
+        self.last_sampler = {"sampler": sampler, "model_evals": evals}
+        if stochastic:
+            self.last_sampler.update(eta=eta if sampler == "euler_a" else None, noise_draws=draws)
+        self.last_block_cache = None
+        self.last_guidance = dict(_DEFAULT_GUIDANCE, guided_evals=evals if cfg_on else 0, unguided_evals=0 if cfg_on else evals)
+        self.last_skip_layer_guidance = self.last_perturbed_attention_guidance = self.last_controlnet = None
+        self.last_ip_adapter = self.last_reference = self.last_condition = None
+        return self.latent_format.process_out(latent), iter_time
+
     def generate_image(
         self,
         text: str,
@@ -828,8 +972,15 @@ class DiffusionPipeline:
         controlnet_interval=None,
         ip_adapter_image_embeds=None,
         ip_adapter_scale: float = 1.0,
+        edit_source_text=None,
+        edit_steps=None,
+        edit_n_avg=None,
+        edit_source_cfg=None,
     ):
-        """``ip_adapter_image_embeds``, ``ip_adapter_scale``: FLUX IP-Adapter, see ``denoise_latents``; ``log["denoising"]["ip_adapter"]`` is
+        """``edit_source_text``, ``edit_steps``, ``edit_n_avg``, ``edit_source_cfg``: FlowEdit, text-guided editing of ``image_path`` -- ``text`` says
+        what the image should become, ``edit_source_text`` what it shows now; see ``denoise_latents``.  ``log["denoising"]["edit"]`` is
+        ``self.last_edit``.
+        ``ip_adapter_image_embeds``, ``ip_adapter_scale``: FLUX IP-Adapter, see ``denoise_latents``; ``log["denoising"]["ip_adapter"]`` is
         ``self.last_ip_adapter``.
         ``controlnet_image_path``, ``controlnet_scale``, ``controlnet_interval``: SD3 ControlNet, see ``denoise_latents``; with a ControlNet,
         ``log["denoising"]["controlnet"]`` is ``self.last_controlnet``.
@@ -869,6 +1020,7 @@ class DiffusionPipeline:
         }
         t0 = time.time()
         conditioning, pooled_conditioning = self.encode_text(text, cfg_weight, negative_text)
+        edit_source = None if edit_source_text is None else self.encode_text(edit_source_text, cfg_weight, negative_text)
         torch.cuda.synchronize(dev)
         log["text_encoding"]["post"] = mem()
         log["text_encoding"]["time"] = round(time.time() - t0, 3)
@@ -892,7 +1044,9 @@ class DiffusionPipeline:
             **({} if controlnet_image_path is None and controlnet_interval is None and controlnet_scale == 1.0 and getattr(self, "controlnet", None) is None
                else {"controlnet_image_path": controlnet_image_path, "controlnet_scale": controlnet_scale, "controlnet_interval": controlnet_interval}),
             **({} if ip_adapter_image_embeds is None and ip_adapter_scale == 1.0 and getattr(self, "ip_adapter_config", None) is None
-               else {"ip_adapter_image_embeds": ip_adapter_image_embeds, "ip_adapter_scale": ip_adapter_scale}))
+               else {"ip_adapter_image_embeds": ip_adapter_image_embeds, "ip_adapter_scale": ip_adapter_scale}),
+            **({} if edit_source_text is None and edit_steps is None and edit_n_avg is None and edit_source_cfg is None else
+               {"edit_source_text": edit_source, "edit_steps": edit_steps, "edit_n_avg": edit_n_avg, "edit_source_cfg": edit_source_cfg}))
         torch.cuda.synchronize(dev)
         log["denoising"]["post"] = mem()
         log["peak_memory"] = max(log["peak_memory"], log["denoising"]["post"]["peak_memory"])
@@ -915,6 +1069,8 @@ class DiffusionPipeline:
             log["denoising"]["controlnet"] = self.last_controlnet
         if self.last_ip_adapter is not None:
             log["denoising"]["ip_adapter"] = self.last_ip_adapter
+        if self.last_edit is not None:
+            log["denoising"]["edit"] = self.last_edit
 
         torch.cuda.reset_peak_memory_stats(dev)
         t0 = time.time()
@@ -1753,3 +1909,76 @@ def sample_steps(model: CFGDenoiser, x: Tensor, sigmas, plan, extra_args=None):
         return _step_loop(model, lp, plan, grows, guide, srows=srows, noise_seeds=seeds)
     finally:
         lp.set_fork(False)
+
+
+_FLOWEDIT_REFUSED = {
+    "mask": "mask_path (inpainting)", "block_cache": "block_cache", "guidance": "a guidance mode other than 'cfg' or guidance_interval",
+    "skip_layer_guidance": "skip-layer guidance", "perturbed_attention_guidance": "perturbed-attention guidance", "controlnet": "a ControlNet",
+    "ip_adapter": "an IP-Adapter", "reference": "a reference image", "condition": "channel-concatenated conditioning (condition=)"}
+
+
+def _flowedit_refusal(what: str) -> str:
+    return f"an edit (edit_source_text) cannot run together with {what}: the edit loop has its own step launch and its own batch rows"
+
+
+def sample_flowedit(model: CFGDenoiser, x_src: Tensor, sigmas, n_max: int, n_min: int = 0, n_avg: int = 1, extra_args=None):
+    """The edit phase of FlowEdit (Kulikov et al. 2024, "Inversion-Free Text-Based Editing Using Pre-Trained Flow Models"; no reference counterpart;
+    the statement is ``sampler.flowedit_reference``).  ``x_src``: f32 [n_img, h, w, C], the encoded source images after ``process_in``; ``sigmas``:
+    the whole schedule, of which the steps T - n_max .. T - n_min - 1 run here (the first T - n_max run nothing at all).
+    ``extra_args``: ``conditioning`` / ``pooled_conditioning`` laid out per image for 2 n_img images, the source rows first -- [src | tar] x n_img
+    each, and with ``cfg_weight`` > 0 (the TARGET's CFG weight) [src+ | tar+ | src- | tar-]; ``edit_source_cfg``: the source's CFG weight (default:
+    the target's); ``edit_guidance_rows``: one distilled-guidance value per batch row (FLUX.1-dev), or None; ``noise_seeds``: one integer in [0, 2^64)
+    per image.  Every model evaluation runs the source and the target of one draw as batch rows of one ``forward_tokens`` and is followed by one
+    launch of dk_flowedit_step, which updates Z, draws the next noise in registers (Philox stream 1) and writes the next inputs; the prime launch
+    in front forms the first ones.  One device synchronisation per outer step.
+    Returns (Z, Zt, iter_time).  n_min == 0: Z is the result (the last launch forms its inputs at sigma 0, where Zt is Z but for the rounding of
+    x_src + (Z - x_src)).  Otherwise Zt is the state at sigmas[T - n_min] that the ordinary loop
+    (``sample_euler`` / ``sample_steps`` on sigmas[T - n_min:], the target rows alone) takes to sigma 0.  ``model.flowedit_record`` says what ran."""
+    from . import ops
+    from .sampler import flowedit_plan
+    extra_args = {} if extra_args is None else dict(extra_args)
+    for key, what in _FLOWEDIT_REFUSED.items():
+        if extra_args.get(key) is not None:
+            raise ValueError(_flowedit_refusal(what))
+    w_src = extra_args.pop("edit_source_cfg", None)
+    grows = extra_args.pop("edit_guidance_rows", None)
+    seeds = extra_args.pop("noise_seeds", None)
+    plan = flowedit_plan(sigmas, n_max, n_min, n_avg)
+    pipe = model.model
+    x_src = x_src.to(pipe.device, torch.float32).contiguous()
+    n_img = x_src.shape[0]
+    if seeds is None or len(seeds) != n_img:
+        raise ValueError(f"sample_flowedit: extra_args['noise_seeds'] must hold one seed per image ({n_img})")
+    cfg_on = float(extra_args.get("cfg_weight", 7.5)) > 0
+    if not cfg_on and not pipe._IS_FLUX:
+        raise ValueError("an edit on the SD3 family needs classifier-free guidance on both sides (cfg_weight > 0 and edit_source_cfg > 0)")
+    lp = _loop_setup(model, torch.cat([x_src, x_src], 0), sigmas, extra_args)  # (2 n_img images: the source rows and the target rows)
+    mm, pcfg = lp.mm, pipe.mmdit_config
+    w_tar = lp.cfg_weight
+    w_src = w_tar if w_src is None else float(w_src)
+    try:
+        if grows is not None:  # (the table again, with a guidance value per batch row)
+            mm.cache_modulation_params(lp.pooled, lp.timesteps, guidance_rows=grows)
+        z, zt = x_src.clone(), torch.empty_like(x_src)
+        sd = ops.seed_tensor(seeds, x_src.device)
+        tok, out = lp.tok, lp.out
+        iter_time, t0, evals = [], None, 0
+        for r in plan:
+            t0 = time.perf_counter() if t0 is None else t0
+            if not r.prime:
+                mm.forward_tokens(tok, None, r.index, tokens_out=out)
+                evals += 1
+            ops.flowedit_step(z, x_src, None if r.prime else out, tok, zt, n_img, cfg_on, pcfg.patch_size, int(pcfg.patchify_via_reshape), c=r.c,
+                              sigma_in=r.sigma_in, seeds=sd, draw=r.draw, w_src=w_src, w_tar=w_tar, prime=r.prime)
+            if r.ends_step:
+                torch.cuda.synchronize(pipe.device)
+                iter_time.append(round(time.perf_counter() - t0, 3))
+                t0 = None
+    finally:
+        if grows is not None:  # (the engine outlives the call: the scalar again)
+            mm.clear_guidance_rows()
+    model.flowedit_record = {"n_max": int(n_max), "n_min": int(n_min), "n_avg": int(n_avg), "model_evals": evals, "draws": len(plan),
+                             "rows": int(tok.shape[0]), "source_cfg": w_src if cfg_on else None, "target_cfg": w_tar if cfg_on else None,
+                             "guidance_rows": None if grows is None else [float(g) for g in grows]}
+    model.clear_cache()
+    return z, zt, iter_time

@@ -263,6 +263,95 @@ def stochastic_reference(x, den, row, xi):
     return out + row.cn * np.asarray(xi, dtype=np.float64) if row.cn != 0.0 else out
 
 
+# ---- FlowEdit: text-guided editing of an existing image (Kulikov et al. 2024; no reference counterpart) --------------------------------------
+FLOWEDIT_STREAM = 1  # the Philox stream tag of the edit's draws: a stochastic sampler in the tail (tag 0) never repeats one
+# (T, n_max, n_min, source, target) per family: the paper's settings as recalled, NOT verified against the paper or the authors' code.  source /
+# target: the CFG weights (SD3) or the distilled-guidance values (FLUX.1-dev)
+FLOWEDIT_DEFAULTS = {"sd3": (50, 33, 0, 3.5, 13.5), "flux": (28, 24, 0, 1.5, 5.5)}
+
+
+class FlowEditRow(NamedTuple):
+    """One dk_flowedit_step launch.  ``index``: the schedule entry of the model evaluation the launch consumes (``prime``: no evaluation yet, the
+    entry the first inputs are formed for); ``c``: the coefficient on V_tar - V_src, (sigmas[index + 1] - sigmas[index]) / n_avg (prime: 0);
+    ``sigma_in``: the sigma the launch forms the next inputs at; ``draw``: the number of the draw it forms them with; ``next_index``: the schedule
+    entry the next evaluation runs at (the row of the modulation table; past the last evaluation: the entry the edit phase hands on);
+    ``ends_step``: Z is complete for its outer step."""
+    index: int
+    c: float
+    sigma_in: float
+    draw: int
+    prime: bool
+    next_index: int
+    ends_step: bool
+
+
+def check_flowedit(num_steps, n_max, n_min, n_avg):
+    """(n_max, n_min, n_avg) as ints with 0 <= n_min < n_max <= num_steps and n_avg >= 1, else a ValueError that names the rule"""
+    n_max, n_min, n_avg, num_steps = int(n_max), int(n_min), int(n_avg), int(num_steps)
+    if n_min < 0 or n_min >= n_max:
+        raise ValueError(f"edit_steps: n_min must satisfy 0 <= n_min < n_max, got (n_max, n_min) = ({n_max}, {n_min})")
+    if n_max > num_steps:
+        raise ValueError(f"edit_steps: n_max = {n_max} exceeds num_steps = {num_steps}")
+    if n_avg < 1:
+        raise ValueError(f"edit_n_avg must be at least 1, got {n_avg}")
+    return n_max, n_min, n_avg
+
+
+def flowedit_plan(sigmas, n_max, n_min=0, n_avg=1) -> List[FlowEditRow]:
+    """The launches of the edit phase over the descending schedule ``sigmas`` [T + 1]: the prime row, which forms the inputs of the first evaluation
+    at sigmas[T - n_max], then one row per evaluation -- n_avg per outer step i = T - n_max .. T - n_min - 1.  Draw k < n_avg - 1 of a step keeps
+    ``sigma_in`` at sigmas[i]; the last one moves it to sigmas[i + 1], and its launch completes Z for the step.  The inputs of evaluation (i, k) are
+    formed with draw i * n_avg + k: distinct, and a function of the schedule alone.  The last row forms, at sigmas[T - n_min], what the edit
+    hands on: with n_min == 0 that sigma is 0 and the result is Z (Zt is Z but for the rounding of x_src + (Z - x_src)); otherwise Zt is the state the
+    ordinary loop takes to sigma 0.  c is computed in
+    float64 from the float32 schedule and rounded to float32 once."""
+    s = [float(v) for v in np.asarray(sigmas, dtype=_F)]
+    T = len(s) - 1
+    n_max, n_min, n_avg = check_flowedit(T, n_max, n_min, n_avg)
+    f = lambda v: float(_F(v))  # noqa: E731
+    i0 = T - n_max
+    rows = [FlowEditRow(i0, 0.0, f(s[i0]), i0 * n_avg, True, i0, False)]
+    for i in range(i0, T - n_min):
+        for k in range(n_avg):
+            last = k == n_avg - 1
+            nxt, nk = (i + 1, 0) if last else (i, k + 1)
+            rows.append(FlowEditRow(i, f((s[i + 1] - s[i]) / n_avg), f(s[nxt]), nxt * n_avg + nk, False, nxt, last))
+    return rows
+
+
+def flowedit_row_reference(z, x_src, v_src, v_tar, row, xi):
+    """One row in float64 numpy -> (Z', Zs, Zt): Z' = Z + c (V_tar - V_src) (prime: Z), Zs = (1 - sigma_in) x_src + sigma_in xi,
+    Zt = Zs + (Z' - x_src).  ``v_src`` / ``v_tar``: the model's outputs in the latent's layout, already combined under CFG (``cfg_combine``);
+    ignored by a prime row.  ``xi`` shaped like Z."""
+    z, x_src, xi = (np.asarray(v, dtype=np.float64) for v in (z, x_src, xi))
+    if not row.prime:
+        z = z + row.c * (np.asarray(v_tar, dtype=np.float64) - np.asarray(v_src, dtype=np.float64))
+    zs = (1.0 - row.sigma_in) * x_src + row.sigma_in * xi
+    return z, zs, zs + (z - x_src)
+
+
+def cfg_combine(pos, neg, w):
+    """neg + w (pos - neg) in float64: how dk_euler_cfg_step and dk_flowedit_step combine the prompt row and the negative row"""
+    pos, neg = np.asarray(pos, dtype=np.float64), np.asarray(neg, dtype=np.float64)
+    return neg + float(w) * (pos - neg)
+
+
+def flowedit_reference(x_src, sigmas, n_max, n_min, n_avg, velocity, seeds):
+    """The edit phase in float64 numpy.  ``x_src`` [n_img, ...]; ``velocity(zs, zt, sigma, index)`` -> (V_src, V_tar), each shaped like x_src;
+    ``seeds``: one per image, the noise of image j is ``philox_normal_reference(seeds[j], draw, n, stream=1)``.  Returns (Z, Zt) behind the last
+    row: with n_min == 0 Z is the result; otherwise Zt is what the ordinary loop takes from sigmas[T - n_min] to 0."""
+    x_src = np.asarray(x_src, dtype=np.float64)
+    n = int(np.prod(x_src.shape[1:]))
+    z, zs, zt = x_src.copy(), None, None
+    for row in flowedit_plan(sigmas, n_max, n_min, n_avg):
+        v_src = v_tar = None
+        if not row.prime:
+            v_src, v_tar = velocity(zs, zt, float(_F(np.asarray(sigmas, dtype=_F)[row.index])), row.index)
+        xi = np.stack([philox_normal_reference(sd, row.draw, n, FLOWEDIT_STREAM) for sd in seeds]).reshape(x_src.shape)
+        z, zs, zt = flowedit_row_reference(z, x_src, v_src, v_tar, row, xi)
+    return z, zt
+
+
 # ---- guidance modes: how the two predictions of a guided evaluation are combined (no reference counterpart) ---------------------------------
 GUIDANCE = ("cfg", "rescale", "apg")
 

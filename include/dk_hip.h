@@ -577,6 +577,29 @@ int dk_noisy_cfg_step_f16(float* x, const void* model_out, int32_t ld_out, void*
                           size_t workspace_bytes, float slg_scale, int32_t guided, int32_t slg, float cn, const uint64_t* seeds,
                           int32_t draw, void* stream);
 
+/* FlowEdit (Kulikov et al. 2024, "Inversion-Free Text-Based Editing Using Pre-Trained Flow Models"; no reference counterpart): the step of the
+ * edit loop, one launch behind every model evaluation.  z, x_src: f32 [n_img, Hl, Wl, C] (z is read and written; x_src is the encoded source
+ * image).  model_out / tokens: the engine's [prompt x n, negative x n] layout for n = 2 n_img images, the source rows first:
+ *   cfg_on = 0: [src | tar],   cfg_on = 1: [src+ | tar+ | src- | tar-]   (n_img batch rows each).
+ * With V the model's output (under cfg_on, neg + w (pos - neg) with w_src on the source rows and w_tar on the target rows):
+ *   z'  = z + c (V_tar - V_src)                                  c = (sigma_next - sigma) / n_avg
+ *   xi  = the normals of (seeds[img], element r, draw) on stream tag 1, formed in registers by the function dk_philox_normal_f32 runs
+ *   Zs  = (1 - sigma_in) x_src + sigma_in xi,   Zt = Zs + (z' - x_src)
+ * Zs and Zt are written in fp32 to zs_out (may be NULL) and zt_out, and rounded and patchified into the source and target rows of tokens,
+ * under cfg_on into both copies, as dk_latent_to_tokens writes them.  prime = 1: model_out is not read (may be NULL) and z is neither changed
+ * nor written -- the launch that forms the first inputs.  Equal source and target rows with w_src == w_tar leave the bits of z; z == x_src
+ * gives zt_out the bits of zs_out, up to the sign of a zero.  Stream tag 1 keeps the draws apart from those of a stochastic sampler (tag 0).
+ * Refused with a dk_last_error() text, nothing written: a null z, x_src, tokens, zt_out or seeds, or a null model_out without prime; sizes that
+ * are not positive or not divisible by p; C not a multiple of 4; ld_out below p * p * C or not a multiple of 4; z, x_src, zs_out, zt_out not
+ * 16-byte aligned; model_out or tokens not 8-byte aligned; a non-finite w_src, w_tar, c or sigma_in; draw < 0.  _f16: model_out and tokens
+ * are fp16. */
+int dk_flowedit_step(float* z, const float* x_src, const void* model_out, int32_t ld_out, void* tokens, float* zs_out, float* zt_out,
+                     int32_t n_img, int32_t cfg_on, int32_t Hl, int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float w_src, float w_tar,
+                     float c, float sigma_in, const uint64_t* seeds, int32_t draw, int32_t prime, void* stream);
+int dk_flowedit_step_f16(float* z, const float* x_src, const void* model_out, int32_t ld_out, void* tokens, float* zs_out, float* zt_out,
+                         int32_t n_img, int32_t cfg_on, int32_t Hl, int32_t Wl, int32_t C, int32_t p, int32_t reshape_order, float w_src,
+                         float w_tar, float c, float sigma_in, const uint64_t* seeds, int32_t draw, int32_t prime, void* stream);
+
 /* Inpainting mask, pixels -> latent cells: mask u8 [n_mask,H,W] (255 = repaint, 0 = keep) -> f32 [n_mask,H/f,W/f],
  * (integer sum of the f x f block) / (f * f * 255) by a true division: an all-0 block gives 0.0f, an all-255 block 1.0f.
  * H and W must be multiples of f (the pipeline passes the VAE's factor, 8). */
@@ -751,6 +774,13 @@ int dk_mmdit_cache_modulation_params(dk_mmdit* m, const void* pooled, const floa
  * modulation vector -- the published FLUX.1-dev conditioning, which the reference's module tree declares (mmdit.py:31-36)
  * but whose call site (:219-220) it never reaches (quirk Q7). */
 int dk_mmdit_set_guidance(dk_mmdit* m, float guidance);
+/* ... or one strength per batch row (FlowEdit on FLUX.1-dev evaluates its source and target rows at different values): g holds n host floats,
+ * n the prepared batch, so the call follows dk_mmdit_prepare, and a later dk_mmdit_prepare forgets the rows.  The next
+ * dk_mmdit_cache_modulation_params embeds the n values (timestep embedding and the two guidance_in Linears at M = n) and adds row b's vector to
+ * batch row b.  g == NULL or n == 0 returns to the scalar of dk_mmdit_set_guidance; with the rows unset the launches and the table are exactly
+ * the scalar's.  Refused with a dk_last_error() text: a configuration without guidance_embed, an engine not yet prepared, n != batch, a
+ * non-finite value. */
+int dk_mmdit_set_guidance_rows(dk_mmdit* m, const float* g, int32_t n);
 
 /* Element type of the engine: 0 = bfloat16 (default), 1 = float16.  Call after dk_mmdit_create and before the first
  * dk_mmdit_bind.  With 1 every bound weight / bias / table is fp16, every activation buffer holds fp16 (sizes unchanged), and
