@@ -112,6 +112,15 @@ class dk_attention_desc(C.Structure):
     ]
 
 
+class dk_tae_conv_desc(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("skip", C.c_void_p), ("y", C.c_void_p),
+        ("image_f32", C.c_void_p), ("image_u8", C.c_void_p),
+        ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("kind", C.c_int32), ("upsample", C.c_int32), ("relu", C.c_int32),
+        ("scale", C.c_float), ("shift", C.c_float),
+    ]
+
+
 class dk_vae_config(C.Structure):
     _fields_ = [
         ("in_channels", C.c_int32), ("out_channels", C.c_int32), ("block_out_channels", C.c_int32 * 4),
@@ -296,6 +305,14 @@ SIGNATURES = {
     "dk_attention_d512_f16": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_float, _vp, _vp]),
     "dk_softmax_rows_f16": (_i32, [_vp, _i32, _i32, _i32, _vp]),
     "dk_transpose_f16": (_i32, [_vp, _vp, _i32, _i32, _vp]),
+    # tiny latent decoder (TAESD family): the engine and its two operators
+    "dk_tae_create": (_i32, [C.POINTER(_vp)]),
+    "dk_tae_destroy": (None, [_vp]),
+    "dk_tae_bind": (_i32, [_vp, C.c_char_p, _vp]),
+    "dk_tae_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "dk_tae_decode": (_i32, [_vp, _vp, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _sz, _vp]),
+    "dk_tae_block_bf16": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _i32, _i32, _i32, _vp]),
+    "dk_tae_conv_bf16": (_i32, [C.POINTER(dk_tae_conv_desc), _vp]),
     "dk_profile_enable": (_i32, [_i32]),
     "dk_profile_read": (_i32, [_i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "dk_tune_set": (_i32, [C.c_char_p, _i32]),

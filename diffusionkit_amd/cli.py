@@ -154,6 +154,17 @@ def build_parser(model_versions: Sequence[str]) -> argparse.ArgumentParser:
     p.add_argument("--ip-adapter-embeds", type=str, default=None, metavar="FILE.npy",
                    help="With --ip-adapter: the prepared CLIP image embedding(s) of the image prompt, a .npy array [768] or [1, 768].")
     p.add_argument("--ip-adapter-scale", type=float, default=None, metavar="S", help="With --ip-adapter: the scale of the adapter's output (default 1.0).")
+    p.add_argument("--tiny-decoder", type=str, default=None, metavar="PATH",
+                   help="A tiny latent decoder of the TAESD family for 16-channel latents (taesd3_decoder / taef1_decoder .safetensors, published or "
+                        "diffusers key form), or the word synthetic (seeded random weights). Serves --decoder tiny and --preview-dir. Layer list, key "
+                        "table and latent convention are unverified: no such file has been run.")
+    p.add_argument("--decoder", choices=("vae", "tiny"), default=None,
+                   help="Decoder of the final latent: vae (default) or tiny (needs --tiny-decoder; with --mask-path or --condition-mask-path also "
+                        "--no-composite).")
+    p.add_argument("--preview-dir", type=str, default=None, metavar="DIR",
+                   help="Write a preview of the loop's x0 estimate, decoded by the tiny decoder, as DIR/step_%%03d.png after every --preview-every-th "
+                        "step (needs --tiny-decoder; not together with --edit-source-prompt).")
+    p.add_argument("--preview-every", type=int, default=None, metavar="N", help="With --preview-dir: preview every N-th step (default 1).")
     p.add_argument("--fp8", choices=("quality", "speed"), default=None,
                    help="Run the transformer blocks on the fp8 MFMA path (FLUX versions only). quality: the first double-stream "
                         "blocks keep bf16 Linears; speed: every block Linear in fp8.")
@@ -347,7 +358,36 @@ def resolve(args) -> dict:
                 raise ValueError(f"--edit-source-cfg is the source's distilled-guidance value on FLUX: {args.model_version} has no guidance embedding")
             r["edit_source_cfg"] = ed["edit_source_cfg"]
         r["edit_source_text"] = ed["edit_source_prompt"]
+    td = {k: getattr(args, k, None) for k in ("tiny_decoder", "decoder", "preview_dir", "preview_every")}
+    if any(v is not None for v in td.values()):  # (keys only when the flags are given)
+        if td["tiny_decoder"] is None and (td["decoder"] == "tiny" or td["preview_dir"] is not None):
+            raise ValueError("--decoder tiny / --preview-dir need --tiny-decoder: a taesd3 / taef1 decoder file, or the word synthetic")
+        if td["preview_every"] is not None and td["preview_dir"] is None:
+            raise ValueError("--preview-every needs --preview-dir")
+        if td["preview_every"] is not None and td["preview_every"] < 1:
+            raise ValueError("--preview-every must be at least 1")
+        if td["preview_dir"] is not None and "edit_source_text" in r:
+            raise ValueError("--preview-dir cannot run together with --edit-source-prompt")
+        if td["decoder"] == "tiny" and r.get("composite", True) and ("mask_path" in r or "condition_mask_path" in r):
+            raise ValueError("--decoder tiny cannot run together with the paste-back of --mask-path / --condition-mask-path: add --no-composite")
+        if td["tiny_decoder"] is not None:
+            r["tiny_decoder_ckpt"] = td["tiny_decoder"]
+        if td["decoder"] is not None:
+            r["decoder"] = td["decoder"]
+        if td["preview_dir"] is not None:
+            r["preview_dir"], r["preview_every"] = td["preview_dir"], td["preview_every"] or 1
     return r
+
+
+def preview_writer(directory: str):
+    """``preview_callback`` of --preview-dir: step i's uint8 images, stacked vertically like the final image, -> directory/step_%03d.png"""
+    import os
+    from PIL import Image
+    os.makedirs(directory, exist_ok=True)
+
+    def write(step: int, u8) -> None:
+        Image.fromarray(u8.reshape(-1, u8.shape[2], 3).cpu().numpy()).save(os.path.join(directory, "step_%03d.png" % step))
+    return write
 
 
 EDIT_KEYS = ("edit_source_text", "edit_steps", "edit_n_avg", "edit_source_cfg")  # the same, FlowEdit
@@ -385,7 +425,12 @@ def main(argv: Optional[Sequence[str]] = None, pipeline_overrides: Optional[dict
         extra["controlnet_config"] = r["controlnet_config"]
     if "ip_adapter_ckpt" in r:
         extra["ip_adapter_ckpt"] = r["ip_adapter_ckpt"]
+    if "tiny_decoder_ckpt" in r:
+        extra["tiny_decoder_ckpt"] = r["tiny_decoder_ckpt"]
     cond_kw = {key: r[key] for key in ("condition_image_path", "condition_mask_path", *CONTROLNET_KEYS, *IP_ADAPTER_KEYS) if key in r}
+    tiny_kw = {"decoder": r["decoder"]} if "decoder" in r else {}
+    if "preview_dir" in r:
+        tiny_kw.update(preview_every=r["preview_every"], preview_callback=preview_writer(r["preview_dir"]))
     if "ip_adapter_image_embeds" in cond_kw:  # (the file is read here: generate_image takes arrays)
         import numpy as np
         cond_kw["ip_adapter_image_embeds"] = np.load(cond_kw["ip_adapter_image_embeds"], allow_pickle=False)
@@ -405,7 +450,7 @@ def main(argv: Optional[Sequence[str]] = None, pipeline_overrides: Optional[dict
                                    composite=r.get("composite", True), block_cache=r.get("block_cache"), sampler=r.get("sampler"),
                                    **{key: r[key] for key in (*GUIDANCE_FLAGS.values(), "reference_image_path", *SKIP_LAYER_KEYS, *PAG_KEYS, "sampler_eta", *EDIT_KEYS)
                                       if key in r},
-                                   **cond_kw)
+                                   **cond_kw, **tiny_kw)
     if log["text_encoding"].get("synthetic"):
         logger.warning("no text-encoder checkpoints were named (--ckpt clip_l=... t5=...): the conditioning is synthetic")
     image.save(args.output_path)

@@ -417,6 +417,37 @@ def tiny_vae() -> VAEDecoderConfig:
     return VAEDecoderConfig(block_out_channels=(64, 64, 128, 128), layers_per_block=1)
 
 
+@dataclass(frozen=True)
+class TinyDecoderConfig:
+    """The 16-channel tiny latent decoders of the TAESD family (taesd3 for the SD3 latent, taef1 for the FLUX latent): 3x3 convs on 64 channels,
+    ReLU, nearest x 2; no GroupNorm, no attention.  ``layers`` is the decoder's nn.Sequential as recalled from the published taesd.py (index 0 is
+    the clamp 3 tanh(x / 3), index 2 the first ReLU) -- unverified, like the key names built from it (README)."""
+    latent_channels: int = 16
+    width: int = 64
+    out_channels: int = 3
+    # (sequential index, kind): "conv_in" 16 -> 64 bias + ReLU, "block" three biased convs + skip, "up" nearest x 2, "conv" 64 -> 64 no bias,
+    # "conv_out" 64 -> 3 bias
+    layers: Tuple[Tuple[int, str], ...] = ((1, "conv_in"), (3, "block"), (4, "block"), (5, "block"), (6, "up"), (7, "conv"),
+                                           (8, "block"), (9, "block"), (10, "block"), (11, "up"), (12, "conv"),
+                                           (13, "block"), (14, "block"), (15, "block"), (16, "up"), (17, "conv"),
+                                           (18, "block"), (19, "conv_out"))
+
+    def tensor_shapes(self):
+        """name -> shape in the reference layout (conv kernels [O, 3, 3, I])"""
+        c, out = self.width, {}
+        for i, kind in self.layers:
+            if kind == "conv_in":
+                out[f"{i}.weight"], out[f"{i}.bias"] = (c, 3, 3, self.latent_channels), (c,)
+            elif kind == "block":
+                for j in (0, 2, 4):
+                    out[f"{i}.conv.{j}.weight"], out[f"{i}.conv.{j}.bias"] = (c, 3, 3, c), (c,)
+            elif kind == "conv":
+                out[f"{i}.weight"] = (c, 3, 3, c)
+            elif kind == "conv_out":
+                out[f"{i}.weight"], out[f"{i}.bias"] = (self.out_channels, 3, 3, c), (self.out_channels,)
+        return out
+
+
 # reference mlx/__init__.py:37-53
 MMDIT_CKPT = {
     "argmaxinc/mlx-stable-diffusion-3-medium": "argmaxinc/mlx-stable-diffusion-3-medium",

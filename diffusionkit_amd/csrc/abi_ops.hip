@@ -28,7 +28,8 @@ extern "C" int dk_tune_set(const char* key, int32_t value) {
       {"gemm", &g_dk_gemm_mode}, {"gemm_v4", &g_dk_v4_auto}, {"gemm_skew", &g_dk_v4_skew}, {"gemm_mf", &g_dk_v3_mf},
       {"gemm_split", &g_dk_v3_split}, {"gemm_split_min", &g_dk_v3_split_min}, {"gemm_pair_nk", &g_dk_pair_split_nk},
       {"gemm_fuse_k", &g_dk_fuse_k}, {"gemm_fuse_q", &g_dk_fuse_qg}, {"attn", &g_dk_attn_mode}, {"attn_fuse_q", &g_dk_fuse_q},
-      {"attn_split", &g_dk_attn5_split}, {"attn_track", &g_dk_attn5_track}, {"pitch_min_k", &g_dk_pitch_min_k}, {"conv_halo", &g_dk_conv_halo}, {"conv_v4", &g_dk_conv_v4}};
+      {"attn_split", &g_dk_attn5_split}, {"attn_track", &g_dk_attn5_track}, {"pitch_min_k", &g_dk_pitch_min_k}, {"conv_halo", &g_dk_conv_halo}, {"conv_v4", &g_dk_conv_v4},
+      {"tae_block", &g_dk_tae_block}};
   DK_REQUIRE(key != nullptr, "null key");
   for (const auto& k : knobs)
     if (strcmp(key, k.key) == 0) { *k.knob = value; return 0; }

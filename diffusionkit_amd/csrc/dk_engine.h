@@ -1,5 +1,5 @@
 // What the host translation units behind include/dk_hip.h share: abi_ops.hip (the stand-alone operator entries and dk_tune_set),
-// mmdit_engine.hip and vae_engine.hip (the engines that sequence the gfx950 kernels).  Host code only.
+// mmdit_engine.hip, vae_engine.hip and tae_engine.hip (the engines that sequence the gfx950 kernels).  Host code only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,6 +14,7 @@
 extern int g_dk_fuse_k, g_dk_fuse_qg, g_dk_fuse_q;  // mmdit_engine.hip
 extern int g_dk_conv_halo;                          // vae_engine.hip
 extern int g_dk_pitch_min_k;                        // abi_ops.hip
+extern int g_dk_tae_block;                          // tae_engine.hip
 
 static inline hipStream_t S_(void* s) { return (hipStream_t)s; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }

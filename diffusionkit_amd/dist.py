@@ -65,6 +65,9 @@ def generate_sharded(pipe, text: str, seeds: Sequence[int], rank: int, world: in
         raise ValueError("an IP-Adapter cannot run under multi-GPU sharding: its per-image embeddings are not cut with the seeds yet")
     if any(k.startswith("edit_") for k in kw):
         raise ValueError("an edit (edit_source_text) cannot run under multi-GPU sharding: its per-image source images are not cut with the seeds yet")
+    if kw.get("decoder", "vae") != "vae" or any(k.startswith("preview_") for k in kw):
+        raise ValueError("the tiny latent decoder (decoder='tiny', per-step previews) cannot run under multi-GPU sharding: every rank would call "
+                         "the preview callback for its own share of the seeds")
     mine = shard_seeds(seeds, rank, world)
     if not mine:
         return None

@@ -645,6 +645,49 @@ class VAEDecoderEngine:
         return raw[..., :3]
 
 
+class TinyDecoderEngine:
+    """The tiny latent decoder (TAESD family, 16-channel latents) on its own kernels (csrc/tae.hip): previews and an opt-in fast final decode.
+    ``packed_weights`` from ``weights.pack_tae``; bf16 only.  ``scale`` / ``shift``: the latent is read as (x - shift) * scale (1, 0: the
+    denoiser-space latent the step loop holds, as it is)."""
+
+    def __init__(self, packed_weights: Dict[str, Tensor], scale: float = 1.0, shift: float = 0.0):
+        self.lib = _lib.load()
+        self.scale, self.shift = float(scale), float(shift)
+        h = C.c_void_p()
+        _lib.check(self.lib.dk_tae_create(C.byref(h)), "dk_tae_create")
+        self._h = h
+        self.weights = packed_weights
+        for name, t in packed_weights.items():
+            _require_cuda(t, name, torch.bfloat16)
+            _lib.check(self.lib.dk_tae_bind(self._h, name.encode(), t.data_ptr()), f"bind {name}")
+        self._ws = None
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self.lib.dk_tae_destroy(self._h)
+            self._h = None
+
+    def decode(self, x: Tensor, scale: Optional[float] = None, shift: Optional[float] = None):
+        """x: f32 [B,h,w,16] -> (image f32 [B,8h,8w,3] in [0,1], uint8 image), on the current stream.  ``scale`` / ``shift``: this call's
+        affine instead of the engine's."""
+        scale = self.scale if scale is None else float(scale)
+        shift = self.shift if shift is None else float(shift)
+        x = x.to(torch.float32).contiguous()
+        _require_cuda(x, "latent")
+        if x.dim() != 4 or x.shape[-1] != 16:
+            raise _lib.DkHipError(f"tiny decoder: latent must be [B, h, w, 16], got {tuple(x.shape)}")
+        b, h, w, _ = x.shape
+        nbytes = self.lib.dk_tae_workspace_bytes(b, h, w)
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = None
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        img = torch.empty(b, h * 8, w * 8, 3, dtype=torch.float32, device=x.device)
+        u8 = torch.empty(b, h * 8, w * 8, 3, dtype=torch.uint8, device=x.device)
+        _lib.check(self.lib.dk_tae_decode(self._h, x.data_ptr(), b, h, w, scale, shift, img.data_ptr(), u8.data_ptr(),
+                                          self._ws.data_ptr(), self._ws.numel(), _stream()), "dk_tae_decode")
+        return img, u8
+
+
 class VAEEncoderEngine:
     """Drop-in for the reference ``VAEEncoder`` (vae.py:404-467): image in [-1, 1] -> moments.  ``config.dtype`` "float16": fp16 weights,
     activations and moments (the reference runs its encoder in fp32: fp16 is the closer 16-bit form, not its dtype)."""

@@ -700,6 +700,34 @@ def mlx_quantized_checkpoint_to_reference(sd: StateDict, group_size: int = MLX_Q
 # ---------------------------------------------------------------------------------------------
 # entry points used by the pipelines (local_ckpt={"mmdit": path_or_dict, "vae_decoder": path_or_dict})
 # ---------------------------------------------------------------------------------------------
+def taesd_checkpoint_to_reference(src) -> StateDict:
+    """A tiny latent decoder of the TAESD family for 16-channel latents (``taesd3_decoder`` / ``taef1_decoder``) -> the names and layout of
+    ``weights.synth_tae_weights``: keys by sequential index, conv kernels [O, 3, 3, I].  ``src``: a .safetensors path or a state dict, in the
+    published key form ("{i}.weight", "{i}.conv.{j}.bias") or diffusers' AutoencoderTiny form ("decoder.layers.{i}. ...").  Refused, with the
+    reason: a first conv that is not 16-channel (the 4-channel ``taesd`` of SD1 / SDXL), encoder tensors, missing or surplus tensors.  The key
+    table is written from memory of the published files and has not been checked against one (README)."""
+    from .config import TinyDecoderConfig
+    sd = load_safetensors(src) if isinstance(src, str) else dict(src)
+    if any(k.startswith("encoder.") for k in sd):
+        raise ValueError("tiny decoder checkpoint: the file holds encoder tensors (encoder.*); only the decoder half is supported")
+    out: StateDict = {}
+    for k, t in sd.items():
+        name = k[len("decoder.layers."):] if k.startswith("decoder.layers.") else k
+        out[name] = t.permute(0, 2, 3, 1).contiguous() if t.dim() == 4 else t  # PyTorch [O, I, 3, 3] -> [O, 3, 3, I]
+    want = TinyDecoderConfig().tensor_shapes()
+    first = out.get("1.weight")
+    if first is not None and first.dim() == 4 and first.shape[-1] != 16:
+        raise ValueError(f"tiny decoder checkpoint: the first conv takes {first.shape[-1]} latent channels, not 16 -- this is the SD1 / SDXL "
+                         "`taesd`, which is out of scope (taesd3 / taef1 only)")
+    missing, surplus = sorted(set(want) - set(out)), sorted(set(out) - set(want))
+    if missing or surplus:
+        raise ValueError(f"tiny decoder checkpoint: missing {missing[:4]}, unexpected {surplus[:4]} (an encoder file, or another layer list?)")
+    for name, shape in want.items():
+        if tuple(out[name].shape) != tuple(shape):
+            raise ValueError(f"tiny decoder checkpoint: {name} has shape {tuple(out[name].shape)}, expected {tuple(shape)}")
+    return out
+
+
 def load_mmdit_checkpoint(src, cfg: MMDiTConfig) -> StateDict:
     """``src``: a dict already in reference names, a raw checkpoint dict, or a .safetensors path."""
     sd = load_safetensors(src) if isinstance(src, str) else dict(src)

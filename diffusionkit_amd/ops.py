@@ -296,6 +296,72 @@ def conv3x3_gn(x: Tensor, w: Tensor, bias: Tensor, gn_table: Optional[Tensor] = 
     return out
 
 
+TAE_TILE = 16  # output tile (height, width) of the tiny decoder's kernels (csrc/tae.hip)
+
+
+def tae_block(x: Tensor, weights, biases) -> Tensor:
+    """One Block of the tiny latent decoder, ReLU(conv(ReLU(conv(ReLU(conv(x))))) + x), as ONE launch (csrc/tae.hip: dk_tae_block_kernel).
+    ``x`` bf16 [B, H, W, 64]; ``weights``: three [64, 576] (or [64, 3, 3, 64]) tap-major, ``biases``: three [64]."""
+    lib = _lib.load()
+    _require_cuda(x, "x", BF)
+    if x.dim() != 4 or x.shape[-1] != 64 or len(weights) != 3 or len(biases) != 3:
+        raise _lib.DkHipError("tae_block: x [B, H, W, 64], three weights and three biases")
+    ws = [w.reshape(w.shape[0], -1) for w in weights]
+    for i in range(3):
+        _require_cuda(ws[i], f"weights[{i}]", BF)
+        _require_cuda(biases[i], f"biases[{i}]", BF)
+        if tuple(ws[i].shape) != (64, 576) or tuple(biases[i].shape) != (64,):
+            raise _lib.DkHipError("tae_block: weights [64, 576], biases [64]")
+    B, H, W_, _ = x.shape
+    y = torch.empty_like(x)
+    wp = (C.c_void_p * 3)(*[w.data_ptr() for w in ws])
+    bp = (C.c_void_p * 3)(*[b.data_ptr() for b in biases])
+    _lib.check(lib.dk_tae_block_bf16(x.data_ptr(), wp, bp, y.data_ptr(), B, H, W_, _stream()), "dk_tae_block_bf16")
+    return y
+
+
+def tae_conv(x: Tensor, w: Tensor, bias: Optional[Tensor] = None, kind: str = "mid", relu: bool = True, skip: Optional[Tensor] = None,
+             upsample: bool = False, scale: float = 1.0, shift: float = 0.0):
+    """One 3x3 conv of the tiny latent decoder (csrc/tae.hip: dk_tae_conv_kernel).  ``kind`` "first": ``x`` f32 [B, H, W, 16] read as
+    3 tanh((x - shift) scale / 3), ``w`` [64, 160] (weights.pack_tae), bias, ReLU -> bf16 [B, H, W, 64]; "mid": ``x`` bf16 [B, H, W, 64], ``w``
+    [64, 576], optional bias / ReLU / skip / nearest-x2 -> bf16; "last": ``w`` [16, 576], ``bias`` [16] -> (image f32, image u8) [B, H, W, 3]."""
+    lib = _lib.load()
+    kinds = {"first": 0, "mid": 1, "last": 2}
+    if kind not in kinds:
+        raise _lib.DkHipError(f"tae_conv: kind {kind!r} (first | mid | last)")
+    if kind != "mid" and (upsample or skip is not None):
+        raise _lib.DkHipError(f"tae_conv {kind}: upsample and skip belong to kind 'mid'")
+    _require_cuda(x, "x", torch.float32 if kind == "first" else BF)
+    w2 = w.reshape(w.shape[0], -1)
+    _require_cuda(w2, "w", BF)
+    want = {"first": (64, 160), "mid": (64, 576), "last": (16, 576)}[kind]
+    if x.dim() != 4 or x.shape[-1] != (16 if kind == "first" else 64) or tuple(w2.shape) != want:
+        raise _lib.DkHipError(f"tae_conv {kind}: x [B, H, W, {16 if kind == 'first' else 64}], w {want}")
+    for name, t in (("bias", bias), ("skip", skip)):
+        if t is not None:
+            _require_cuda(t, name, BF)
+    if bias is not None and bias.numel() != want[0]:
+        raise _lib.DkHipError(f"tae_conv {kind}: bias [{want[0]}]")
+    B, Hs, Ws, _ = x.shape
+    H, W_ = (Hs * 2, Ws * 2) if upsample else (Hs, Ws)
+    if skip is not None and tuple(skip.shape) != (B, H, W_, 64):
+        raise _lib.DkHipError("tae_conv: skip must have the output's shape")
+    d = _lib.dk_tae_conv_desc()
+    d.x, d.w, d.bias, d.skip = x.data_ptr(), w2.data_ptr(), _ptr(bias), _ptr(skip)
+    d.B, d.H, d.W, d.kind, d.upsample, d.relu = B, H, W_, kinds[kind], int(upsample), int(relu)
+    d.scale, d.shift = scale, shift
+    if kind == "last":
+        img = torch.empty(B, H, W_, 3, dtype=torch.float32, device=x.device)
+        u8 = torch.empty(B, H, W_, 3, dtype=torch.uint8, device=x.device)
+        d.image_f32, d.image_u8 = img.data_ptr(), u8.data_ptr()
+        out = (img, u8)
+    else:
+        out = torch.empty(B, H, W_, 64, dtype=BF, device=x.device)
+        d.y = out.data_ptr()
+    _lib.check(lib.dk_tae_conv_bf16(C.byref(d), _stream()), "dk_tae_conv_bf16")
+    return out
+
+
 def attention(qkv: Tensor, H: int, D: int, scale: Optional[float] = None, workspace: Optional[Tensor] = None,
               score_bound: Optional[float] = None, qn=None) -> Tensor:
     """SDPA over a token-major [B, S, 3*H*D] projection buffer -> [B, S, H*D].  ``workspace``: lab only (trace buffer of attention4.hip's

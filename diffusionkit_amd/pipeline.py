@@ -302,8 +302,15 @@ class DiffusionPipeline:
         controlnet_config: Optional[MMDiTConfig] = None,
         ip_adapter_ckpt=None,
         ip_adapter_config=None,
+        tiny_decoder_ckpt=None,
     ):
-        """``ip_adapter_ckpt`` (FluxPipeline only): a FLUX IP-Adapter in XLabs-AI's layout (flux-ip-adapter as diffusers'
+        """``tiny_decoder_ckpt``: a tiny latent decoder of the TAESD family for 16-channel latents (``taesd3`` for the SD3 latent, ``taef1`` for the FLUX
+        latent) -- a .safetensors path or a state dict as ``model_io.taesd_checkpoint_to_reference`` takes them, or "synthetic" (seeded random weights,
+        ``weights.synth_tae_weights``) -- built into ``self.tiny_decoder`` (``engine.TinyDecoderEngine`` on csrc/tae.hip).  It serves
+        ``generate_image(decoder="tiny")`` and the per-step previews of ``denoise_latents``; without it both are refused.  The decoder is fed the
+        denoiser-space latent (``latent_format.process_out`` undone on its load); that convention, the layer list and the key table are unverified
+        (README).
+        ``ip_adapter_ckpt`` (FluxPipeline only): a FLUX IP-Adapter in XLabs-AI's layout (flux-ip-adapter as diffusers'
         FluxIPAdapterJointAttnProcessor2_0 runs it) -- a .safetensors path or a state dict in that layout, or a dict of the names of
         ``weights.synth_ip_adapter_weights`` -- bound into the model's engine; ``ip_adapter_config``: a ``config.IPAdapterConfig`` (default
         ``config.FLUX_IP_ADAPTER``: 4 tokens of 4096 features from a 768-wide CLIP image embedding).  Every call must then name its
@@ -396,6 +403,9 @@ class DiffusionPipeline:
         self.check_and_load_models()
         if controlnet_ckpt is not None:
             self.load_controlnet(controlnet_ckpt)
+        self.tiny_decoder = None
+        if tiny_decoder_ckpt is not None:
+            self.load_tiny_decoder(tiny_decoder_ckpt)
 
     def _check_controlnet_config(self, controlnet_config) -> None:
         from .config import SD3_CONTROLNET_6, validate_control_net
@@ -424,6 +434,19 @@ class DiffusionPipeline:
         ccfg = self.controlnet_config
         named = dict(load_controlnet_checkpoint(ckpt, ccfg))
         self.controlnet = MMDiTEngine(ccfg, pack_mmdit(ccfg, named, self.device, consume=True))
+
+    def load_tiny_decoder(self, ckpt) -> None:
+        """``self.tiny_decoder`` from ``tiny_decoder_ckpt`` (see the constructor).  Its load undoes ``latent_format.process_out``, so ``decode`` takes
+        the latents ``denoise_latents`` returns; the previews pass scale 1, shift 0 for the loop's own state."""
+        from .engine import TinyDecoderEngine
+        from .weights import pack_tae, synth_tae_weights
+        if isinstance(ckpt, str) and ckpt == "synthetic":
+            named = synth_tae_weights(seed=self.weights_seed + 2)
+        else:
+            from .model_io import taesd_checkpoint_to_reference
+            named = taesd_checkpoint_to_reference(ckpt)
+        self.tiny_decoder = TinyDecoderEngine(pack_tae(named, self.device), scale=self.latent_format.scale_factor,
+                                              shift=self.latent_format.shift_factor)
 
     def _init_sampler(self, shift):
         self.sampler = ModelSamplingDiscreteFlow(shift=shift)
@@ -595,8 +618,17 @@ class DiffusionPipeline:
         edit_steps=None,
         edit_n_avg=None,
         edit_source_cfg=None,
+        preview_every=None,
+        preview_callback=None,
     ):
-        """``edit_source_text`` (FlowEdit, Kulikov et al. 2024; text-guided editing of ``image_path`` with the plain checkpoint): the prompt that
+        """``preview_every`` = N with ``preview_callback`` = f (a pipeline built with ``tiny_decoder_ckpt``): after every N-th step the tiny decoder
+        decodes the loop's x0 estimate on the current stream and ``f(step_index, image_u8)`` is called with the uint8 images [n, 8h, 8w, 3] (a
+        tensor on the device, valid until the next preview).  The estimate is x - sigma v with v taken from the step itself,
+        (sigma' x - sigma x') / (sigma' - sigma) for the state x at the step's sigma and x' at its sigma' -- Euler's own v; the step's effective
+        direction under the second-order samplers, and with the step's noise in it under the stochastic ones.  The loop's state is only read: a run
+        with previews returns the bits of the run without, and the previews' time is not part of ``iter_time``.  Raises without a tiny decoder,
+        with one of the two keywords alone, and with an edit.
+        ``edit_source_text`` (FlowEdit, Kulikov et al. 2024; text-guided editing of ``image_path`` with the plain checkpoint): the prompt that
         describes the source image -- a string, encoded here with ``encode_text``, or an already encoded (conditioning, pooled_conditioning) pair
         laid out like this call's own -- while ``conditioning`` describes what the image should become.  See ``_denoise_edit`` for ``edit_steps`` =
         (n_max, n_min), ``edit_n_avg`` and ``edit_source_cfg``, what it composes with and what it refuses.  ``self.last_edit`` says what ran; None
@@ -687,6 +719,7 @@ class DiffusionPipeline:
         with skip-layer guidance (there is one fork).  ``self.last_perturbed_attention_guidance`` = {"layers", "scale", "interval", "evals"}, or
         None.  Verified as arithmetic only, on synthetic weights: no checkpoint has been run here."""
         self.last_edit = None
+        preview = _preview_options(self, preview_every, preview_callback, edit_source_text)
         if edit_source_text is None:
             if edit_steps is not None or edit_n_avg is not None or edit_source_cfg is not None:
                 raise ValueError("edit_steps, edit_n_avg and edit_source_cfg belong to an edit: give edit_source_text, the prompt that describes image_path")
@@ -797,6 +830,7 @@ class DiffusionPipeline:
         noise_scaled = self.sampler.noise_scaling(np.float32(sigmas[0]), noise, x_T, self.max_denoise(sigmas))
         x0 = torch.from_numpy(np.ascontiguousarray(noise_scaled, dtype=np.float32)).to(self.device)
         denoiser = CFGDenoiser(self)
+        denoiser.preview = preview
         stochastic = sampler in STOCHASTIC_SAMPLERS
         rows = "euler" if sampler == "euler_a" and eta == 0.0 else sampler  # (eta = 0: euler's rows, and so euler's launches)
         try:
@@ -976,8 +1010,15 @@ class DiffusionPipeline:
         edit_steps=None,
         edit_n_avg=None,
         edit_source_cfg=None,
+        decoder: str = "vae",
+        preview_every=None,
+        preview_callback=None,
     ):
-        """``edit_source_text``, ``edit_steps``, ``edit_n_avg``, ``edit_source_cfg``: FlowEdit, text-guided editing of ``image_path`` -- ``text`` says
+        """``decoder``: "vae" (default: every launch and every bit is what it was) or "tiny" -- the final latent is decoded by ``self.tiny_decoder``
+        (a pipeline built with ``tiny_decoder_ckpt``) instead of the VAE; the same image type comes back and ``log["decoding"]["decoder"]`` says
+        which ran.  "tiny" raises without a tiny decoder and together with a ``composite`` paste-back (``mask_path`` or a fill mask: pass
+        ``composite=False``).  ``preview_every`` / ``preview_callback``: per-step previews, see ``denoise_latents``.
+        ``edit_source_text``, ``edit_steps``, ``edit_n_avg``, ``edit_source_cfg``: FlowEdit, text-guided editing of ``image_path`` -- ``text`` says
         what the image should become, ``edit_source_text`` what it shows now; see ``denoise_latents``.  ``log["denoising"]["edit"]`` is
         ``self.last_edit``.
         ``ip_adapter_image_embeds``, ``ip_adapter_scale``: FLUX IP-Adapter, see ``denoise_latents``; ``log["denoising"]["ip_adapter"]`` is
@@ -1002,6 +1043,8 @@ class DiffusionPipeline:
         check_condition_args(getattr(self, "condition", None), condition_image_path, condition_mask_path, reference_image_path, self._IS_FLUX)
         if mask_path is not None and image_path is None:
             raise ValueError("mask_path needs image_path: the mask says which part of that image to keep")
+        _check_decoder(self, decoder, composite and (mask_path is not None or condition_mask_path is not None))
+        _preview_options(self, preview_every, preview_callback, edit_source_text)  # (raises before the text is encoded)
         assert latent_size[0] % 2 == 0, f"Height must be divisible by 16 ({latent_size[0]*8}/16={latent_size[0]/2})"
         assert latent_size[1] % 2 == 0, f"Width must be divisible by 16 ({latent_size[1]*8}/16={latent_size[1]/2})"
         self.check_and_load_models()
@@ -1046,7 +1089,8 @@ class DiffusionPipeline:
             **({} if ip_adapter_image_embeds is None and ip_adapter_scale == 1.0 and getattr(self, "ip_adapter_config", None) is None
                else {"ip_adapter_image_embeds": ip_adapter_image_embeds, "ip_adapter_scale": ip_adapter_scale}),
             **({} if edit_source_text is None and edit_steps is None and edit_n_avg is None and edit_source_cfg is None else
-               {"edit_source_text": edit_source, "edit_steps": edit_steps, "edit_n_avg": edit_n_avg, "edit_source_cfg": edit_source_cfg}))
+               {"edit_source_text": edit_source, "edit_steps": edit_steps, "edit_n_avg": edit_n_avg, "edit_source_cfg": edit_source_cfg}),
+            **({} if preview_every is None and preview_callback is None else {"preview_every": preview_every, "preview_callback": preview_callback}))
         torch.cuda.synchronize(dev)
         log["denoising"]["post"] = mem()
         log["peak_memory"] = max(log["peak_memory"], log["denoising"]["post"]["peak_memory"])
@@ -1075,7 +1119,11 @@ class DiffusionPipeline:
         torch.cuda.reset_peak_memory_stats(dev)
         t0 = time.time()
         log["decoding"]["pre"] = mem()
-        _, u8, _ = self.decoder.decode(latents)
+        if decoder == "tiny":
+            _, u8 = self.tiny_decoder.decode(latents)
+            log["decoding"]["decoder"] = "tiny"
+        else:
+            _, u8, _ = self.decoder.decode(latents)
         if mask_path is not None and composite:
             u8 = self.composite_image(u8, image_path, mask_path)
         elif condition_mask_path is not None and composite:  # (fill: the kept pixels of the condition image, at the size they came in)
@@ -1257,6 +1305,47 @@ class FluxPipeline(DiffusionPipeline):
         if self._text_encoder is not None:
             return self._text_encoder(text, cfg_weight, negative_text)
         return self._synthetic_conditioning(text, 1)
+
+
+_NO_TINY_DECODER = ("needs a tiny latent decoder: build the pipeline with tiny_decoder_ckpt= (a taesd3 / taef1 decoder file, or \"synthetic\"; "
+                    "CLI: --tiny-decoder)")
+
+
+def _check_decoder(pipe, decoder, paste_back: bool) -> None:
+    """``generate_image(decoder=)``, before any GPU work"""
+    if decoder not in ("vae", "tiny"):
+        raise ValueError(f"unknown decoder {decoder!r} (vae | tiny)")
+    if decoder == "tiny":
+        if getattr(pipe, "tiny_decoder", None) is None:
+            raise ValueError("decoder='tiny' " + _NO_TINY_DECODER)
+        if paste_back:
+            raise ValueError("decoder='tiny' cannot run together with the composite paste-back of an inpainting or fill mask (it has been checked "
+                             "against the VAE's images only): pass composite=False (CLI: --no-composite)")
+
+
+def _preview_options(pipe, every, callback, edit=None) -> Optional[dict]:
+    """``preview_every`` / ``preview_callback`` of ``denoise_latents`` -> None or {"every", "callback", "decoder"}; raises before any GPU work"""
+    if every is None and callback is None:
+        return None
+    if every is None or callback is None:
+        raise ValueError("per-step previews take both preview_every=N and preview_callback=f(step_index, image_u8)")
+    if int(every) != every or every < 1:
+        raise ValueError(f"preview_every must be a positive integer, got {every!r}")
+    if getattr(pipe, "tiny_decoder", None) is None:
+        raise ValueError("per-step previews " + _NO_TINY_DECODER)
+    if edit is not None:
+        raise ValueError(_flowedit_refusal("per-step previews"))
+    return {"every": int(every), "callback": callback, "decoder": pipe.tiny_decoder}
+
+
+def _preview(pv: dict, step: int, x_start: Tensor, x: Tensor, sigma: float, sigma_next: float) -> None:
+    """One preview behind step ``step`` (0-based): the x0 estimate x - sigma v, v = (x' - x) / (sigma' - sigma), formed out of place from the state
+    at the step's start and end, decoded in denoiser space (scale 1, shift 0) on the current stream; the device is synchronised behind the
+    callback, so that the preview's time does not fall into the next step's."""
+    x0 = x if sigma_next == sigma else (x_start * float(sigma_next) - x * float(sigma)) / (float(sigma_next) - float(sigma))
+    _, u8 = pv["decoder"].decode(x0, scale=1.0, shift=0.0)
+    pv["callback"](step, u8)
+    torch.cuda.synchronize(x.device)
 
 
 class CFGDenoiser:
@@ -1768,7 +1857,11 @@ def _step_loop(model: "CFGDenoiser", lp: _Loop, plan, grows, guide=None, euler: 
     fork = False  # whether it holds the forked third row group of skip-layer guidance
     srows = [False] * len(plan) if srows is None else srows
     control_evals = 0
+    pv = getattr(model, "preview", None)
+    x_start = sigma_start = None  # the state and sigma at the start of a step that ends in a preview
     for r, g, sl in zip(plan, grows, srows):
+        if pv is not None and t0 is None and (step + 1) % pv["every"] == 0:
+            x_start, sigma_start = x.clone(), r.sigma
         t0 = time.perf_counter() if t0 is None else t0
         if cfg_on and (g.guided != on or sl != fork):
             on, fork = g.guided, sl
@@ -1821,6 +1914,9 @@ def _step_loop(model: "CFGDenoiser", lp: _Loop, plan, grows, guide=None, euler: 
         if r.ends_step:
             torch.cuda.synchronize(pipe.device)
             iter_time.append(round(time.perf_counter() - t0, 3))
+            if x_start is not None:
+                _preview(pv, step, x_start, x, sigma_start, r.sigma_next)
+                x_start = None
             step, t0 = step + 1, None
     if policy is not None:
         model.block_cache_record = record

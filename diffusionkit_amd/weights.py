@@ -469,6 +469,48 @@ def pack_mmdit(cfg: MMDiTConfig, w: Dict[str, Tensor], device, consume: bool = F
     return out
 
 
+def synth_tae_weights(seed: int = 4322, cfg=None) -> Dict[str, Tensor]:
+    """Random bf16 weights of the tiny latent decoder in the reference layout (conv kernels [O, 3, 3, I]), keyed by sequential index
+    (config.TinyDecoderConfig).  He-style gains, so that activations neither die under the ReLUs nor grow through the 34 convs: std
+    sqrt(2 / fan_in) in front of a ReLU, a quarter of that for a Block's last conv (the skip carries the signal, ten Blocks add up), sqrt(1 / fan_in)
+    for the unbiased convs behind the upsamplings; the last conv centres the image at 0.5."""
+    from .config import TinyDecoderConfig
+    cfg = cfg or TinyDecoderConfig()
+    g = torch.Generator().manual_seed(int(seed))
+    out: Dict[str, Tensor] = {}
+    for name, shape in cfg.tensor_shapes().items():
+        t = torch.randn(*shape, generator=g)
+        if name.endswith(".bias"):
+            t = 0.05 * t + (0.5 if name.startswith("19.") else 0.0)
+        else:
+            fan_in = shape[1] * shape[2] * shape[3]
+            gain = 2.0 if (".conv." in name or name.startswith("1.")) else 1.0
+            t = t * (gain / fan_in) ** 0.5
+            if name.endswith(".conv.4.weight"):
+                t = 0.25 * t
+            if name.startswith("19."):
+                t = 0.5 * t
+        out[name] = t.to(torch.bfloat16)
+    return out
+
+
+def pack_tae(w: Dict[str, Tensor], device) -> Dict[str, Tensor]:
+    """Tiny latent decoder: conv weights [O, 3, 3, I] -> bf16 [O, 9 * I]; the first conv's 144 columns zero-padded to 160 (five 32-wide MFMA
+    steps), the last conv's 3 rows (and bias entries) to 16 (one MFMA fragment) -- what dk_tae_bind expects (include/dk_hip.h)."""
+    dev = torch.device(device)
+    out: Dict[str, Tensor] = {}
+    for k, t in w.items():
+        t = t.to(dev).to(torch.bfloat16)
+        if t.dim() == 4:
+            t = t.reshape(t.shape[0], -1)
+            if t.shape[1] % 32:
+                t = torch.nn.functional.pad(t, (0, 32 - t.shape[1] % 32))
+        if t.shape[0] % 16:
+            t = torch.nn.functional.pad(t, (0, 0) * (t.dim() - 1) + (0, 16 - t.shape[0] % 16))
+        out[k] = t.contiguous()
+    return out
+
+
 def pack_vae(cfg, w: Dict[str, Tensor], device) -> Dict[str, Tensor]:
     """Decoder or encoder half: conv weights [O,3,3,I] -> [O, 9*I] (conv_in zero-padded to I = 64), in ``cfg.dtype`` (bfloat16 | float16):
     one rounding from the source tensors."""

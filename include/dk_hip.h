@@ -1131,6 +1131,43 @@ int dk_latent_sample_f16(const void* moments_f16, int32_t ldm, const float* nois
                          int64_t n_pixels, int32_t latent_channels, void* stream);  /* the same on fp16 moments (an fp16 encoder's) */
 
 /* ------------------------------------------------------------------------------------------
+ * Tiny latent decoder (the TAESD family's 16-channel decoders, taesd3 / taef1; no reference counterpart in DiffusionKit).  Written from
+ * memory of the published taesd.py -- layer list, key names and latent convention are unverified, see README.  bf16 only.
+ *   x -> 3 tanh(x / 3); 1: conv3x3(16 -> 64, bias) ReLU; 3-5, 8-10, 13-15, 18: Block; 6, 11, 16: nearest x 2; 7, 12, 17: conv3x3(64 -> 64,
+ *   no bias); 19: conv3x3(64 -> 3, bias); image = clip(out, 0, 1).  Block(x) = ReLU(conv(ReLU(conv(ReLU(conv(x))))) + x), three biased convs.
+ * dk_tae_bind names: "{i}.weight", "{i}.bias", "{i}.conv.{0,2,4}.weight|bias" (the nn.Sequential indices).  Conv weights are bf16, flattened
+ * to [O, 9 * I] tap-major like the VAE's; "1.weight" is [64, 160] (9 * 16 = 144 columns, zero-padded to five 32-wide MFMA steps); "19.weight"
+ * is [16, 576] and "19.bias" [16] (rows / entries 3.. zero).  Biases bf16.
+ * dk_tae_workspace_bytes: three activation buffers [B, 8h, 8w, 64] bf16 (two ping-pong, one intermediate of the chain form); every byte is
+ * written before it is read.  dk_tae_decode: latent f32 [B, h, w, 16], read as (x - shift) * scale (1, 0: the denoiser-space latent as it is);
+ * image_f32 [B, 8h, 8w, 3] in [0, 1] and / or image_u8 (byte = truncation of the bf16-rounded image * 255, dk_vae_decode's rule).  35 launches
+ * (first conv, 10 Blocks as chains of three convs -- the measured faster form; 15 with dk_tune_set("tae_block", 1), one fused launch per Block,
+ * same bits --, 3 upsampling convs, last conv); any h, w >= 1; never allocates.
+ * dk_tae_block_bf16: one Block as ONE launch, x, y bf16 [B, H, W, 64] (two buffers), weights / biases: three pointers each.
+ * dk_tae_conv_bf16: one conv; kind 0 = first (x f32 [B, H, W, 16], clamp and affine on the load, bias, ReLU), 1 = 64 -> 64 (x bf16
+ * [B, H >> upsample, W >> upsample, 64]; bias, skip nullable; out = relu?((acc + bias) + skip)), 2 = last (image tail; y unused).
+ * A Block equals its chain of three kind-1 convs (relu, the last with skip = x) bit for bit: both walk K in the same order.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct dk_tae dk_tae;
+int dk_tae_create(dk_tae** out);
+void dk_tae_destroy(dk_tae* t);
+int dk_tae_bind(dk_tae* t, const char* name, const void* dev_ptr);
+size_t dk_tae_workspace_bytes(int32_t batch, int32_t latent_h, int32_t latent_w);
+int dk_tae_decode(dk_tae* t, const float* latent, int32_t batch, int32_t latent_h, int32_t latent_w, float scale, float shift,
+                  float* image_f32, uint8_t* image_u8, void* workspace, size_t workspace_bytes, void* stream);
+int dk_tae_block_bf16(const void* x, const void* const* weights, const void* const* biases, void* y, int32_t B, int32_t H, int32_t W,
+                      void* stream);
+typedef struct dk_tae_conv_desc {
+  const void *x, *w, *bias, *skip;
+  void* y;
+  float* image_f32;
+  uint8_t* image_u8;
+  int32_t B, H, W, kind, upsample, relu;
+  float scale, shift;
+} dk_tae_conv_desc;
+int dk_tae_conv_bf16(const dk_tae_conv_desc* d, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement hooks (no reference counterpart; the reference times phases with time.time(),
  * mlx/__init__.py:315-530).  When enabled, every bf16 GEMM (class 0), conv (1), attention (2) and fp8 GEMM (3) launch
  * is bracketed by HIP events on its launch stream; dk_profile_read sums elapsed time, algorithmic
@@ -1155,6 +1192,7 @@ int dk_profile_read(int32_t kernel_class, double* total_ms, double* total_flops,
  * "attn_fuse_q": 0 = stand-alone query QKNorm + RoPE pass; "conv_halo": 0 = VAE convolutions through the GEMM form;
  * "conv_v4": the fused VAE convolutions with >= 256 output channels on the one-wave-per-SIMD kernel (1 where one image fills the
  * CUs, 0 never, 2 wherever eligible);
+ * "tae_block": 1 = the tiny decoder's Blocks as one fused launch each instead of chains of three single convs (same bits; -1 / 0: chains);
  * "pitch_min_k": rows of at least this many elements are stored padded (dk_weight_pitch).
  * Returns 0, or -1 for an unknown key. */
 int dk_tune_set(const char* key, int32_t value);
