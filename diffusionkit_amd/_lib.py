@@ -192,6 +192,10 @@ SIGNATURES = {
     "dk_quantize_mx8": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _i64, _i32, _i32, _vp]),
     "dk_ln_modulate_mx8": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _f32, _vp, _i32, _vp, _i64, _i32, _vp]),
     "dk_weight_pitch_fp8": (_i32, [_i32]),
+    "dk_gemm_fp4": (_i32, [C.POINTER(dk_gemm_fp8_desc), _vp, _vp]),
+    "dk_gemm_fp4_fused": (_i32, [C.POINTER(dk_gemm_fp8_desc), C.POINTER(dk_gemm_fp8_side), _vp, C.POINTER(dk_gemm_fp8_desc), C.POINTER(dk_gemm_fp8_side),
+                                 _vp, _vp]),
+    "dk_weight_pitch_fp4": (_i32, [_i32]),
     "dk_mmdit_set_guidance": (_i32, [_vp, _f32]),
     # float16 element type (SD3 family): siblings of the bf16 operators, same descriptors
     "dk_gemm_f16": (_i32, [C.POINTER(dk_gemm_desc), _vp]),

@@ -168,6 +168,11 @@ def build_parser(model_versions: Sequence[str]) -> argparse.ArgumentParser:
     p.add_argument("--fp8", choices=("quality", "speed"), default=None,
                    help="Run the transformer blocks on the fp8 MFMA path (FLUX versions only). quality: the first double-stream "
                         "blocks keep bf16 Linears; speed: every block Linear in fp8.")
+    p.add_argument("--fp4", choices=("quality", "speed"), default=None,
+                   help="Run the transformer blocks with OCP MX-fp4 weights (W4A8 on the same block-scaled MFMA, a quarter of the bf16 weight "
+                        "bytes; FLUX versions only). Same policies as --fp8 (the quality block count was fitted for fp8 and is reused); not "
+                        "together with --fp8, nor with anything --fp8 refuses. Arithmetic verified on synthetic weights only; a 4-bit MLX "
+                        "checkpoint is dequantised and re-quantised, not loaded bit for bit.")
     p.add_argument("--activation-dtype", choices=("bfloat16", "float16"), default="bfloat16",
                    help="Element type of the MMDiT's weights and activations. float16 is the reference's dtype for Stable Diffusion 3 "
                         "(SD3 versions only); the text encoders stay bfloat16, the VAE has --vae-dtype.")
@@ -205,10 +210,15 @@ def resolve(args) -> dict:
     assert width % 16 == 0, f"Width must be divisible by 16 ({width}/16={width/16})"
     r = {"cfg": cfg, "shift": args.shift or SHIFT[args.model_version], "height": height, "width": width,
          "flux": "FLUX" in args.model_version, "low_memory_mode": args.low_memory_mode and not args.benchmark_mode}
+    if getattr(args, "fp8", None) and getattr(args, "fp4", None):
+        raise ValueError("--fp8 and --fp4 cannot run together: one weight format per engine")
     if getattr(args, "fp8", None):
         # (config.fp8_config raises a ValueError for the SD3 geometries: head_dim 64)
         from .config import MODEL_CONFIG, fp8_config
         r["mmdit_config"] = fp8_config(MODEL_CONFIG[args.model_version], args.fp8)
+    if getattr(args, "fp4", None):  # (config.fp4_config: the same geometry rule)
+        from .config import MODEL_CONFIG, fp4_config
+        r["mmdit_config"] = fp4_config(MODEL_CONFIG[args.model_version], args.fp4)
     if getattr(args, "activation_dtype", "bfloat16") != "bfloat16":
         # (config.float16_config raises a ValueError for the FLUX geometries and together with --fp8)
         from .config import MODEL_CONFIG, float16_config
@@ -300,8 +310,8 @@ def resolve(args) -> dict:
                              "depth is its preset's")
         if mcfg.dual_attention_blocks > 0:
             raise ValueError(f"--controlnet cannot run with {args.model_version}: its dual attention blocks have no tap form")
-        if getattr(args, "fp8", None):
-            raise ValueError("--controlnet cannot run together with --fp8")
+        if getattr(args, "fp8", None) or getattr(args, "fp4", None):
+            raise ValueError("--controlnet cannot run together with " + ("--fp8" if getattr(args, "fp8", None) else "--fp4"))
         for key, flag in (("block_cache", "--block-cache"), ("skip_layer_guidance", "--slg-scale"), ("pag_scale", "--pag-scale")):
             if r.get(key) is not None:
                 raise ValueError(f"--controlnet cannot run together with {flag}")
@@ -321,8 +331,8 @@ def resolve(args) -> dict:
             raise ValueError("--ip-adapter needs --ip-adapter-embeds: the prepared image embedding of the image prompt (the vision tower is not built)")
         if "FLUX" not in args.model_version:
             raise ValueError(f"--ip-adapter needs a FLUX model version, not {args.model_version}: SD3 and SD3.5 IP-Adapters are not built")
-        if getattr(args, "fp8", None):
-            raise ValueError("--ip-adapter cannot run together with --fp8")
+        if getattr(args, "fp8", None) or getattr(args, "fp4", None):
+            raise ValueError("--ip-adapter cannot run together with " + ("--fp8" if getattr(args, "fp8", None) else "--fp4"))
         for key, flag in (("controlnet_ckpt", "--controlnet"), ("block_cache", "--block-cache"), ("reference_image_path", "--reference-image-path"),
                           ("condition", "--condition")):
             if r.get(key) is not None:
@@ -413,6 +423,9 @@ def main(argv: Optional[Sequence[str]] = None, pipeline_overrides: Optional[dict
     if args.fp8:  # (a config of the caller's is put on the fp8 path like the model version's own)
         from .config import fp8_config
         extra["mmdit_config"] = fp8_config(extra["mmdit_config"], args.fp8) if extra.get("mmdit_config") is not None else r["mmdit_config"]
+    if getattr(args, "fp4", None):
+        from .config import fp4_config
+        extra["mmdit_config"] = fp4_config(extra["mmdit_config"], args.fp4) if extra.get("mmdit_config") is not None else r["mmdit_config"]
     if "activation_dtype" in r:
         extra["activation_dtype"] = r["activation_dtype"]
     if "vae_dtype" in r:

@@ -46,7 +46,8 @@ class MMDiTConfig:
     # dtype the timestep embedding is evaluated in (reference config.dtype, quirk Q2)
     dtype: str = "bfloat16"
     guidance_embed: bool = False
-    # storage / MFMA dtype of the transformer blocks' Linear weights: "bfloat16", or "fp8_e4m3" (per-output-channel scales,
+    # storage / MFMA dtype of the transformer blocks' Linear weights: "bfloat16", "mxfp4" (OCP MX-fp4 weights, same activation path and rules as
+    # fp8; config.fp4_config), or "fp8_e4m3" (per-output-channel scales,
     # MX-fp8 activations quantised on the fly; FLUX geometry only: head_dim 128, text length a multiple of 128 -- any image token count)
     weight_dtype: str = "bfloat16"
     # fp8 precision policy (only read with weight_dtype = "fp8_e4m3"): the Linears of the first n double-stream blocks stay bf16 --
@@ -131,8 +132,8 @@ def validate_dual_attention(cfg: MMDiTConfig) -> None:
     n = cfg.dual_attention_blocks
     if not (0 <= n <= cfg.depth_multimodal):
         raise ValueError(f"dual_attention_blocks = {n}: must lie in [0, depth_multimodal = {cfg.depth_multimodal}]")
-    if n > 0 and (cfg.depth_unified != 0 or cfg.weight_dtype == "fp8_e4m3"):
-        raise ValueError("dual_attention_blocks needs the SD3 family (MMDiT-X): depth_unified == 0 and no fp8 Linears")
+    if n > 0 and (cfg.depth_unified != 0 or low_bit_name(cfg) is not None):
+        raise ValueError("dual_attention_blocks needs the SD3 family (MMDiT-X): depth_unified == 0 and no fp8 / fp4 Linears")
 
 
 # The InstantX SD3-medium ControlNets (Canny / Pose / Tile; diffusers' SD3ControlNetModel): six joint blocks of SD3-medium's width.  The width is
@@ -141,13 +142,13 @@ SD3_CONTROLNET_6 = replace(SD3_2b, depth_multimodal=6, hidden_size_override=SD3_
 
 
 def validate_control_net(cfg: MMDiTConfig) -> None:
-    """``control_net`` needs SD3 geometry: the learned positional table, depth_unified == 0, no fp8 Linears, no dual attention blocks, no
+    """``control_net`` needs SD3 geometry: the learned positional table, depth_unified == 0, no fp8 / fp4 Linears, no dual attention blocks, no
     condition width (the rule dk_mmdit_set_control_net enforces)."""
     if not cfg.control_net:
         return
-    if (cfg.pos_embed_type != PositionalEncoding.LearnedInputEmbedding or cfg.depth_unified != 0 or cfg.weight_dtype == "fp8_e4m3"
+    if (cfg.pos_embed_type != PositionalEncoding.LearnedInputEmbedding or cfg.depth_unified != 0 or low_bit_name(cfg) is not None
             or cfg.dual_attention_blocks != 0 or cfg.condition_features != 0):
-        raise ValueError("control_net needs the SD3 family: the learned positional table, depth_unified == 0, no fp8 Linears, no dual attention "
+        raise ValueError("control_net needs the SD3 family: the learned positional table, depth_unified == 0, no fp8 / fp4 Linears, no dual attention "
                          "blocks and no condition width")
 
 
@@ -185,9 +186,9 @@ def validate_control_net_flux(cfg: MMDiTConfig) -> None:
     if cfg.control_net:
         raise ValueError("control_net_flux and control_net cannot both be set: control_net is the SD3 family's ControlNet")
     if (cfg.pos_embed_type != PositionalEncoding.PreSDPARope or cfg.depth_multimodal < 1 or cfg.depth_unified < 0
-            or cfg.weight_dtype == "fp8_e4m3" or cfg.activation_dtype != "bfloat16" or cfg.dual_attention_blocks != 0 or cfg.condition_features != 0):
+            or low_bit_name(cfg) is not None or cfg.activation_dtype != "bfloat16" or cfg.dual_attention_blocks != 0 or cfg.condition_features != 0):
         raise ValueError("control_net_flux needs the FLUX family: RoPE without a learned positional table, at least one double block, bfloat16 "
-                         "activations, no fp8 Linears, no dual attention blocks and no condition width")
+                         "activations, no fp8 / fp4 Linears, no dual attention blocks and no condition width")
 
 
 def flux_controlnet_config(n_double: int, n_single: int, base: Optional[MMDiTConfig] = None) -> MMDiTConfig:
@@ -224,8 +225,9 @@ def validate_ip_adapter(cfg: MMDiTConfig, ip: IPAdapterConfig) -> None:
     if cfg.pos_embed_type != PositionalEncoding.PreSDPARope or cfg.depth_multimodal < 1:
         raise ValueError("an IP-Adapter needs the FLUX family: RoPE without a learned positional table and at least one double block "
                          "(SD3 and SD3.5 IP-Adapters are not built)")
-    if cfg.weight_dtype == "fp8_e4m3":
-        raise ValueError("an IP-Adapter cannot be combined with fp8 Linears: the fp8 LayerNorm kernels take no tap")
+    if low_bit_name(cfg):
+        raise ValueError(f"an IP-Adapter cannot be combined with {low_bit_name(cfg)} Linears: the MX-fp8 LayerNorm kernels of the fp8 / fp4 engines "
+                         "take no tap")
     if cfg.activation_dtype != "bfloat16" or cfg.head_dim != 128 or not cfg.use_qk_norm:
         raise ValueError("an IP-Adapter needs bfloat16 activations, head_dim 128 and QK-norm weights")
     if cfg.condition_features != 0 or cfg.control_net or cfg.control_net_flux or cfg.dual_attention_blocks != 0:
@@ -260,6 +262,12 @@ def validate_condition_features(cfg: MMDiTConfig) -> None:
 FLUX_FP8_QUALITY_BLOCKS = 12
 
 
+def low_bit_name(cfg) -> str:
+    """"fp8" / "fp4" for a config whose block Linears run on the block-scaled MFMA (weight_dtype "fp8_e4m3" / "mxfp4"), else None: both engines share
+    the MX-fp8 activation path, so whatever that path cannot take is refused for both, by name"""
+    return {"fp8_e4m3": "fp8", "mxfp4": "fp4"}.get(cfg.weight_dtype)
+
+
 def fp8_config(cfg: MMDiTConfig, policy: str = "quality") -> MMDiTConfig:
     """``cfg`` on the fp8 path (BASELINE.json configs[3]).  policy "quality" (default): the first FLUX_FP8_QUALITY_BLOCKS double-stream blocks keep
     bf16 Linears (>= 35 dB per step, SURVEY.md section 8c iii); "speed": every block Linear in fp8 (31.6 - 32.5 dB per step)."""
@@ -275,8 +283,23 @@ def fp8_config(cfg: MMDiTConfig, policy: str = "quality") -> MMDiTConfig:
     return out
 
 
+def fp4_config(cfg: MMDiTConfig, policy: str = "quality") -> MMDiTConfig:
+    """``cfg`` with OCP MX-fp4 block Linears (W4A8 on the block-scaled MFMA, csrc/gemm256f4.hip): ``fp8_config``'s geometry checks and policies.
+    "quality" keeps the first FLUX_FP8_QUALITY_BLOCKS double-stream blocks in bf16 -- a count that was fitted for fp8, on synthetic weights, and is
+    reused here, not re-fitted: nothing is known about what fp4 needs on a checkpoint.  "speed": every block Linear in fp4."""
+    if policy not in ("quality", "speed"):
+        raise ValueError(f"unknown fp4 policy {policy!r} (quality | speed)")
+    if cfg.head_dim != 128 or cfg.hidden_size % 256 != 0:
+        raise ValueError(f"fp4_config: the fp4 path needs head_dim 128 and hidden_size % 256 == 0 (got {cfg.head_dim}, {cfg.hidden_size}); "
+                         "at run time the text length must be a multiple of 128, the image size is free")
+    n = min(FLUX_FP8_QUALITY_BLOCKS, cfg.depth_multimodal) if policy == "quality" else 0
+    out = replace(cfg, weight_dtype="mxfp4", fp8_bf16_double_blocks=n)
+    validate_fp8_policy(out)
+    return out
+
+
 def validate_activation_dtype(cfg: MMDiTConfig) -> None:
-    """``activation_dtype`` is "bfloat16" or "float16"; float16 is the SD3 family's: head_dim == 64, depth_unified == 0 and no fp8 Linears
+    """``activation_dtype`` is "bfloat16" or "float16"; float16 is the SD3 family's: head_dim == 64, depth_unified == 0 and no fp8 / fp4 Linears
     (the rule dk_mmdit_set_activation_dtype enforces -- the D = 128 attention kernels, the single-stream blocks' fused launches and the fp8 path
     are bf16 only)."""
     if cfg.activation_dtype not in ("bfloat16", "float16"):
@@ -286,8 +309,9 @@ def validate_activation_dtype(cfg: MMDiTConfig) -> None:
     if cfg.head_dim != 64 or cfg.depth_unified != 0:
         raise ValueError(f"activation_dtype float16 needs SD3-family geometry: head_dim == 64 and depth_unified == 0 "
                          f"(got head_dim {cfg.head_dim}, depth_unified {cfg.depth_unified})")
-    if cfg.weight_dtype == "fp8_e4m3":
-        raise ValueError("activation_dtype float16 cannot be combined with weight_dtype fp8_e4m3 (the fp8 path's activations are bf16 / MX-fp8)")
+    if low_bit_name(cfg):
+        raise ValueError(f"activation_dtype float16 cannot be combined with weight_dtype {cfg.weight_dtype} (the {low_bit_name(cfg)} path's "
+                         "activations are bf16 / MX-fp8)")
 
 
 def float16_config(cfg: MMDiTConfig) -> MMDiTConfig:

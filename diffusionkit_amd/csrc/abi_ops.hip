@@ -20,6 +20,9 @@ extern "C" const char* dk_last_error(void) { return g_last_error.c_str(); }
 int g_dk_pitch_min_k = 8192;
 extern "C" int32_t dk_weight_pitch(int32_t k) { return k >= g_dk_pitch_min_k ? k + 64 : k; }
 extern "C" int32_t dk_weight_pitch_fp8(int32_t k) { return k >= g_dk_pitch_min_k ? k + 128 : k; }
+// MX-fp4 weights (gemm256f4.hip): bytes per output channel of the fragment-row layout; the padding rule is dk_weight_pitch_fp8's (a fragment row of
+// 16 channels is 16 pitches long: the same stride pattern over the memory channels, at half the bytes)
+extern "C" int32_t dk_weight_pitch_fp4(int32_t k) { return k >= g_dk_pitch_min_k ? k / 2 + 64 : k / 2; }
 extern "C" size_t dk_mx_scale_bytes(int64_t rows, int32_t k) { return (size_t)((k + 127) / 128) * (size_t)mx_nblk((long)rows) * 512; }
 
 // every knob is defined, with its values and its default, in the file that reads it
@@ -451,6 +454,30 @@ extern "C" int dk_gemm_fp8_fused(const dk_gemm_fp8_desc* d, const dk_gemm_fp8_si
   set_fused(p2, f2);
   if (f2 != nullptr) p2.c2_mx8 = f2->c2_mx8;
   return dk_launch_gemm256f8(p, &p2, S_(stream));
+}
+// the fp8 descriptors with MX-fp4 weights: W in the fragment-row layout, w_block_scales its E8M0 side array (gemm256f4.hip)
+static int gemm_f4_params(const dk_gemm_fp8_desc* d, const dk_gemm_fp8_side* f, const void* w_block_scales, GemmF4Params& p) {
+  if (const int rc = gemm_f8_params_from_desc(d, d->c_mx8 != 0 || (f != nullptr && f->c2_mx8 != 0), p)) return rc;
+  set_fused(p, f);
+  if (f != nullptr) p.c2_mx8 = f->c2_mx8;
+  p.SW = (const unsigned char*)w_block_scales;
+  return 0;
+}
+extern "C" int dk_gemm_fp4(const dk_gemm_fp8_desc* d, const void* w_block_scales, void* stream) {
+  DK_REQUIRE(d != nullptr && w_block_scales != nullptr, "null descriptor / weight block scales");
+  GemmF4Params p;
+  if (const int rc = gemm_f4_params(d, nullptr, w_block_scales, p)) return rc;
+  return dk_launch_gemm256f4(p, nullptr, S_(stream));
+}
+extern "C" int dk_gemm_fp4_fused(const dk_gemm_fp8_desc* d, const dk_gemm_fp8_side* f, const void* w_block_scales, const dk_gemm_fp8_desc* d2,
+                                 const dk_gemm_fp8_side* f2, const void* w_block_scales2, void* stream) {
+  DK_REQUIRE(d != nullptr && w_block_scales != nullptr && (d2 != nullptr || f2 == nullptr) && (d2 == nullptr || w_block_scales2 != nullptr),
+             "null descriptor / weight block scales");
+  GemmF4Params p, p2;
+  if (const int rc = gemm_f4_params(d, f, w_block_scales, p)) return rc;
+  if (d2 == nullptr) return dk_launch_gemm256f4(p, nullptr, S_(stream));
+  if (const int rc = gemm_f4_params(d2, f2, w_block_scales2, p2)) return rc;
+  return dk_launch_gemm256f4(p, &p2, S_(stream));
 }
 extern "C" int dk_quantize_mx8(const void* x, int32_t ldx, int32_t M, int32_t h, void* out, int32_t ldo, void* out_scales, int64_t out_rows,
                                int32_t out_row0, int32_t out_col0, void* stream) {

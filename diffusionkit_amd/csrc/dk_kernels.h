@@ -178,6 +178,22 @@ struct GemmF8Params {
 };
 bool dk_gemm256f8_eligible(const GemmF8Params& p);
 int dk_launch_gemm256f8(const GemmF8Params& p, const GemmF8Params* p2, hipStream_t stream);
+// ---- MX-fp4 GEMM (gemm256f4.hip): the same problem with W as OCP MX-fp4 in the kernel's fragment layout (ldw = bytes per output channel,
+// 16 channels = one fragment row of 16 * ldw bytes) and SW, its E8M0 block scales [N / 64][K / 128][64][4]; SW == nullptr: e4m3 weights, the
+// fp8 kernel's problem (dk_launch_gemm_f8f4 below picks the kernel).  The fp8 kernel's parameter block is a prefix and does not move.
+struct GemmF4Params : GemmF8Params {
+  const unsigned char* SW;
+};
+const char* dk_gemm256f4_refusal(const GemmF4Params& p);  // nullptr: eligible; otherwise the rule the problem breaks
+bool dk_gemm256f4_eligible(const GemmF4Params& p);
+int dk_launch_gemm256f4(const GemmF4Params& p, const GemmF4Params* p2, hipStream_t stream);
+// a Linear of the low-bit block drivers: the fp4 kernel when the problem carries block scales for its weights, else the fp8 kernel
+inline int dk_launch_gemm_f8f4(const GemmF4Params& p, const GemmF4Params* p2, hipStream_t stream) {
+  if (p.SW != nullptr) return dk_launch_gemm256f4(p, p2, stream);
+  if (p2 == nullptr) return dk_launch_gemm256f8(p, nullptr, stream);
+  const GemmF8Params q2 = *p2;
+  return dk_launch_gemm256f8(p, &q2, stream);
+}
 // bf16 rows -> MX-fp8 rows + scales (fp8_ops.hip).  x: [M, h] bf16 through the row map (seg_len, seg_stride); out row m at
 // physical row out_row0 + (m / o_seg_len) * o_seg_stride + m % o_seg_len of the fp8 buffer (pitch ldo bytes, column
 // offset col0, a multiple of 32).  dk_launch_ln_modulate_mx8 = dk_launch_ln_modulate with that output.

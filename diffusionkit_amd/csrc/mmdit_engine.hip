@@ -23,7 +23,8 @@ static bool fuse_qg(const bf16_t* qn, bool f8) { return (g_dk_fuse_qg < 0 ? f8 :
 template <typename P>
 static void set_key_norm(P& p, const bf16_t* kn, const bf16_t* qn, int h, int D, const float* rope, int pos_off, int seg_len) {
   p.kn_w = kn; p.kn_rope = rope; p.kn_col0 = h; p.kn_col1 = 2 * h; p.kn_D = D; p.kn_pos_off = pos_off; p.kn_seg_len = seg_len; p.kn_eps = 1e-6f;
-  if (fuse_qg(qn, std::is_same<P, GemmF8Params>::value)) { p.qn_w = qn; p.qn_col0 = 0; p.qn_col1 = h; }
+  // (the low-bit builders' parameter block is GemmF4Params, a GemmF8Params)
+  if (fuse_qg(qn, std::is_base_of<GemmF8Params, P>::value)) { p.qn_w = qn; p.qn_col0 = 0; p.qn_col1 = h; }
 }
 struct StreamW {  // one TransformerBlock's weights (mmdit.py:395-438)
   const bf16_t *qkv_w = nullptr, *qkv_b = nullptr, *qn = nullptr, *kn = nullptr;
@@ -32,6 +33,8 @@ struct StreamW {  // one TransformerBlock's weights (mmdit.py:395-438)
   // fp8_linears: e4m3 weights + per-output-channel scales instead of the bf16 matrices above (biases stay bf16)
   const unsigned char *qkv_w8 = nullptr, *o_w8 = nullptr, *fc1_w8 = nullptr, *fc2_w8 = nullptr, *l2_w8 = nullptr;
   const float *qkv_ws = nullptr, *o_ws = nullptr, *fc1_ws = nullptr, *fc2_ws = nullptr, *l2_ws = nullptr;
+  // fp8_linears == 2: the *_w8 matrices are MX-fp4 in the fragment layout of gemm256f4.hip and these are their E8M0 block scales (null: e4m3 weights)
+  const unsigned char *qkv_sw = nullptr, *o_sw = nullptr, *fc1_sw = nullptr, *fc2_sw = nullptr, *l2_sw = nullptr;
   // MMDiT-X (dk_mmdit_set_dual_attention), image stream of a dual block: the second attention's q | k | v matrix with its FULL bias (attn2's
   // k_proj keeps its bias), its own QKNorm weights and its output projection
   const bf16_t *qkv2_w = nullptr, *qkv2_b = nullptr, *qn2 = nullptr, *kn2 = nullptr, *o2_w = nullptr, *o2_b = nullptr;
@@ -160,7 +163,8 @@ struct dk_mmdit {
   }
   // what a call on `stream` hands its launches: this engine's element type and ITS regions (for D = 64 no attention region: unsplit launches)
   LaunchCtx ctx(void* stream) const { return LaunchCtx{S_(stream), dtype, GWS, AttnWs{AWS, AWS_bytes}}; }
-  bool fp8() const { return cfg.fp8_linears != 0; }
+  bool fp8() const { return cfg.fp8_linears != 0; }  // the low-bit path: e4m3 (1) or MX-fp4 (2) weights over MX-fp8 activations
+  bool fp4() const { return cfg.fp8_linears == 2; }
   // precision policy: the first n_bf16() double-stream blocks keep bf16 Linears under fp8_linears (global block index = double-block index)
   int n_bf16() const { return fp8() ? (cfg.fp8_bf16_double_blocks < cfg.depth_multimodal ? cfg.fp8_bf16_double_blocks : cfg.depth_multimodal) : 0; }
 
@@ -212,6 +216,7 @@ extern "C" int dk_mmdit_create(const dk_mmdit_config* cfg, dk_mmdit** out) {
     for (int i = 0; i < cfg->n_rope_axes; ++i) half += cfg->rope_axes_dim[i] / 2;
     DK_REQUIRE(half * 2 == D, "rope axes must sum to head_dim");
   }
+  DK_REQUIRE(cfg->fp8_linears >= 0 && cfg->fp8_linears <= 2, "fp8_linears: 0 bf16, 1 e4m3 or 2 MX-fp4 block Linears");
   if (cfg->fp8_linears) DK_REQUIRE(D == 128 && cfg->hidden_size % 256 == 0, "fp8_linears: head_dim 128 and hidden_size a multiple of 256");
   dk_mmdit* m = new dk_mmdit();
   m->cfg = *cfg;
@@ -276,25 +281,29 @@ extern "C" int dk_mmdit_bind(dk_mmdit* m, const char* name, const void* dev_ptr)
 extern "C" int dk_mmdit_mod_rows(const dk_mmdit* m) { return m->mod_rows(); }
 extern "C" int dk_mmdit_mod_offset(const dk_mmdit* m, int32_t kind, int32_t index) { return m->mod_offset(kind, index); }
 
-// the matrix of one Linear: bf16 "<name>.weight", or (fp8_linears) e4m3 "<name>.weight_fp8" + f32 "<name>.wscale"
-static int need_matrix(dk_mmdit* m, bool f8, const std::string& name, const bf16_t** w, const unsigned char** w8, const float** ws) {
+// the matrix of one Linear: bf16 "<name>.weight", or (fp8_linears == 1) e4m3 "<name>.weight_fp8" + f32 "<name>.wscale", or (fp8_linears == 2)
+// MX-fp4 "<name>.weight_fp4" + E8M0 "<name>.wscale4" (both in the kernel's layout, weights.py: pack_mxfp4) + f32 "<name>.wscale"
+static int need_matrix(dk_mmdit* m, bool f8, const std::string& name, const bf16_t** w, const unsigned char** w8, const float** ws,
+                       const unsigned char** sw) {
   if (!f8) return need(m->named, name + ".weight", w);
-  const bf16_t *a = nullptr, *b = nullptr;
-  DK_TRY(need(m->named, name + ".weight_fp8", &a));
+  const bf16_t *a = nullptr, *b = nullptr, *c = nullptr;
+  DK_TRY(need(m->named, name + (m->fp4() ? ".weight_fp4" : ".weight_fp8"), &a));
   DK_TRY(need(m->named, name + ".wscale", &b));
+  if (m->fp4()) DK_TRY(need(m->named, name + ".wscale4", &c));
   *w8 = (const unsigned char*)a;
   *ws = (const float*)b;
+  *sw = (const unsigned char*)c;
   return 0;
 }
 static int resolve_stream(dk_mmdit* m, const std::string& p, StreamW& w, bool single, bool skip_post, bool f8) {
   const auto& n = m->named;
   if (single) {  // fused [q|k|v|fc1] matrix; fc1 views point into it
-    DK_TRY(need_matrix(m, f8, p + ".linear1", &w.qkv_w, &w.qkv_w8, &w.qkv_ws));
+    DK_TRY(need_matrix(m, f8, p + ".linear1", &w.qkv_w, &w.qkv_w8, &w.qkv_ws, &w.qkv_sw));
     DK_TRY(need(n, p + ".linear1.bias", &w.qkv_b));
     if (!f8) w.fc1_w = w.qkv_w + (size_t)3 * m->h() * m->h();
     w.fc1_b = w.qkv_b + 3 * m->h();
   } else {
-    DK_TRY(need_matrix(m, f8, p + ".attn.qkv", &w.qkv_w, &w.qkv_w8, &w.qkv_ws));
+    DK_TRY(need_matrix(m, f8, p + ".attn.qkv", &w.qkv_w, &w.qkv_w8, &w.qkv_ws, &w.qkv_sw));
     DK_TRY(need(n, p + ".attn.qkv.bias", &w.qkv_b));
   }
   if (m->cfg.use_qk_norm) {
@@ -303,16 +312,16 @@ static int resolve_stream(dk_mmdit* m, const std::string& p, StreamW& w, bool si
   }
   if (skip_post) return 0;
   if (!single) {
-    DK_TRY(need_matrix(m, f8, p + ".mlp.fc1", &w.fc1_w, &w.fc1_w8, &w.fc1_ws));
+    DK_TRY(need_matrix(m, f8, p + ".mlp.fc1", &w.fc1_w, &w.fc1_w8, &w.fc1_ws, &w.fc1_sw));
     DK_TRY(need(n, p + ".mlp.fc1.bias", &w.fc1_b));
   }
   if (single) {
-    DK_TRY(need_matrix(m, f8, p + ".linear2", &w.l2_w, &w.l2_w8, &w.l2_ws));
+    DK_TRY(need_matrix(m, f8, p + ".linear2", &w.l2_w, &w.l2_w8, &w.l2_ws, &w.l2_sw));
     DK_TRY(need(n, p + ".linear2.bias", &w.l2_b));
   } else {
-    DK_TRY(need_matrix(m, f8, p + ".attn.o_proj", &w.o_w, &w.o_w8, &w.o_ws));
+    DK_TRY(need_matrix(m, f8, p + ".attn.o_proj", &w.o_w, &w.o_w8, &w.o_ws, &w.o_sw));
     DK_TRY(need(n, p + ".attn.o_proj.bias", &w.o_b));
-    DK_TRY(need_matrix(m, f8, p + ".mlp.fc2", &w.fc2_w, &w.fc2_w8, &w.fc2_ws));
+    DK_TRY(need_matrix(m, f8, p + ".mlp.fc2", &w.fc2_w, &w.fc2_w8, &w.fc2_ws, &w.fc2_sw));
     DK_TRY(need(n, p + ".mlp.fc2.bias", &w.fc2_b));
   }
   return 0;
@@ -956,18 +965,20 @@ static int single_block_bf16(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t
   return dk_launch_gemm(l2, st);
 }
 
-// ---- fp8_linears: the transformer blocks on the fp8 GEMM (gemm256f8.hip) -------------------------------------------------
+// ---- fp8_linears: the transformer blocks on the fp8 GEMM (gemm256f8.hip) or, with MX-fp4 weights, on the fp4 GEMM (gemm256f4.hip) ----
 // A Linear over MX-fp8 activations.  abuf / sa: the fp8 activation buffer and its scale side array (pitch lda bytes); the GEMM
 // reads logical rows through (a_row0, a_seg_len, a_seg_stride): a_row0 a multiple of 128 rows, and either one segment of any length or
 // segments of whole 128-row blocks (dk_gemm256f8_eligible; the row order of mmdit_carve provides it for every token count).
 // Every one carries the engine's split workspace (the K split of small launches).
-static GemmF8Params f8_params(const dk_mmdit* m, const unsigned char* abuf, const unsigned char* sa, int lda, int a_row0, int a_seg_len,
-                              int a_seg_stride, const unsigned char* W, int ldw, const float* ws, const bf16_t* bias, int M, int N, int K,
-                              int epi) {
-  GemmF8Params p;
+// sw: the E8M0 block scales of an MX-fp4 weight (its pitch is dk_weight_pitch_fp4(K), whatever ldw says), or null: e4m3 weights at ldw --
+// dk_launch_gemm_f8f4 picks the kernel from it; everything on the activation side is the same.
+static GemmF4Params f8_params(const dk_mmdit* m, const unsigned char* abuf, const unsigned char* sa, int lda, int a_row0, int a_seg_len,
+                              int a_seg_stride, const unsigned char* W, int ldw, const float* ws, const unsigned char* sw, const bf16_t* bias, int M,
+                              int N, int K, int epi) {
+  GemmF4Params p;
   memset(&p, 0, sizeof(p));
-  p.A = abuf + (size_t)a_row0 * lda; p.SA = sa; p.W = W; p.wscale = ws; p.bias = bias;
-  p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = ldw;
+  p.A = abuf + (size_t)a_row0 * lda; p.SA = sa; p.W = W; p.wscale = ws; p.SW = sw; p.bias = bias;
+  p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = sw != nullptr ? dk_weight_pitch_fp4(K) : ldw;
   p.a_seg_len = a_seg_len; p.a_seg_stride = a_seg_stride; p.a_row0 = a_row0; p.sa_nblk = m->nblk;
   p.epi = epi;
   if (m->GWS) { p.workspace = m->GWS; p.workspace_bytes = dk_gemm_split_workspace_bytes(); }
@@ -998,15 +1009,15 @@ static int double_block_fp8(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t*
                                     S, cf.layer_norm_eps, st));
   const bool kf = keys_in_tail(wi, &wt);
   {
-    GemmF8Params qi = f8_params(m, m->XN8, m->SXN, h, 0, Mi, 0, wi.qkv_w8, h, wi.qkv_ws, wi.qkv_b, Mi, 3 * h, h, DK_EPI_BIAS);
-    GemmF8Params qt = f8_params(m, m->XN8, m->SXN, h, T0, Mt, 0, wt.qkv_w8, h, wt.qkv_ws, wt.qkv_b, Mt, 3 * h, h, DK_EPI_BIAS);
+    GemmF4Params qi = f8_params(m, m->XN8, m->SXN, h, 0, Mi, 0, wi.qkv_w8, h, wi.qkv_ws, wi.qkv_sw, wi.qkv_b, Mi, 3 * h, h, DK_EPI_BIAS);
+    GemmF4Params qt = f8_params(m, m->XN8, m->SXN, h, T0, Mt, 0, wt.qkv_w8, h, wt.qkv_ws, wt.qkv_sw, wt.qkv_b, Mt, 3 * h, h, DK_EPI_BIAS);
     f8_out_bf16(qi, m->img(m->QKV, 3 * h));
     f8_out_bf16(qt, m->txt(m->QKV, 3 * h));
     if (kf) {
       set_key_norm(qi, wi.kn, wi.qn, h, m->D(), c.rope, S_t, S_i);
       set_key_norm(qt, wt.kn, wt.qn, h, m->D(), c.rope, 0, S_t);
     }
-    DK_TRY(dk_launch_gemm256f8(qi, &qt, st));
+    DK_TRY(dk_launch_gemm_f8f4(qi, &qt, st));
   }
   if (!kf)
     DK_TRY(dk_launch_qk_norm_rope2(m->QKV + (size_t)S_t * 3 * h, Mi, wi.qn, wi.kn, S_i, S_t, m->QKV, Mt, wt.qn, wt.kn, S_t, 0, 3 * h, 0, h,
@@ -1016,15 +1027,15 @@ static int double_block_fp8(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t*
   DK_TRY(dk_launch_attention(ap, L.aws, st));
   // post_sdpa (mmdit.py:537-548): residual += gate_attn * o_proj(attn)
   {
-    GemmF8Params oi = c.att_split ? f8_params(m, m->ATT8, m->SATT, h, 0, Mi, 0, wi.o_w8, h, wi.o_ws, wi.o_b, Mi, h, h, DK_EPI_GATE_RES)
-                                  : f8_params(m, m->ATT8, m->SATT, h, S_t, S_i, S, wi.o_w8, h, wi.o_ws, wi.o_b, Mi, h, h, DK_EPI_GATE_RES);
+    GemmF4Params oi = c.att_split ? f8_params(m, m->ATT8, m->SATT, h, 0, Mi, 0, wi.o_w8, h, wi.o_ws, wi.o_sw, wi.o_b, Mi, h, h, DK_EPI_GATE_RES)
+                                  : f8_params(m, m->ATT8, m->SATT, h, S_t, S_i, S, wi.o_w8, h, wi.o_ws, wi.o_sw, wi.o_b, Mi, h, h, DK_EPI_GATE_RES);
     f8_out_bf16(oi, X_img);
     set_gate_res(oi, mod_img + 2 * h, S_i, mod_stride, X_img);
-    GemmF8Params ot = c.att_split ? f8_params(m, m->ATT8, m->SATT, h, T0, Mt, 0, wt.o_w8, h, wt.o_ws, wt.o_b, Mt, h, h, DK_EPI_GATE_RES)
-                                  : f8_params(m, m->ATT8, m->SATT, h, 0, S_t, S, wt.o_w8, h, wt.o_ws, wt.o_b, Mt, h, h, DK_EPI_GATE_RES);
+    GemmF4Params ot = c.att_split ? f8_params(m, m->ATT8, m->SATT, h, T0, Mt, 0, wt.o_w8, h, wt.o_ws, wt.o_sw, wt.o_b, Mt, h, h, DK_EPI_GATE_RES)
+                                  : f8_params(m, m->ATT8, m->SATT, h, 0, S_t, S, wt.o_w8, h, wt.o_ws, wt.o_sw, wt.o_b, Mt, h, h, DK_EPI_GATE_RES);
     f8_out_bf16(ot, X_txt);
     set_gate_res(ot, mod_txt + 2 * h, S_t, mod_stride, X_txt);
-    DK_TRY(dk_launch_gemm256f8(oi, txt_post ? &ot : nullptr, st));
+    DK_TRY(dk_launch_gemm_f8f4(oi, txt_post ? &ot : nullptr, st));
   }
   // residual += gate_mlp * fc2(gelu(fc1(LN-mod(residual)))); the MLP hidden leaves fc1 as MX-fp8
   if (txt_post)
@@ -1032,18 +1043,18 @@ static int double_block_fp8(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t*
                                       c.xn_txt, h, h, mod_stride, S, cf.layer_norm_eps, st));
   else
     DK_TRY(dk_launch_ln_modulate_mx8(X_img.p, h, Mi, h, mod_img + 3 * h, mod_img + 4 * h, mod_stride, S_i, S_i, S, cf.layer_norm_eps, c.xn_img, st));
-  GemmF8Params f1i = f8_params(m, m->XN8, m->SXN, h, 0, Mi, 0, wi.fc1_w8, h, wi.fc1_ws, wi.fc1_b, Mi, r * h, h, DK_EPI_BIAS_GELU);
+  GemmF4Params f1i = f8_params(m, m->XN8, m->SXN, h, 0, Mi, 0, wi.fc1_w8, h, wi.fc1_ws, wi.fc1_sw, wi.fc1_b, Mi, r * h, h, DK_EPI_BIAS_GELU);
   f8_out_hid8(f1i, m, 0);
-  GemmF8Params f2i = f8_params(m, m->HC8, m->SHID, ldh8, 0, Mi, 0, wi.fc2_w8, ldh8, wi.fc2_ws, wi.fc2_b, Mi, h, r * h, DK_EPI_GATE_RES);
+  GemmF4Params f2i = f8_params(m, m->HC8, m->SHID, ldh8, 0, Mi, 0, wi.fc2_w8, ldh8, wi.fc2_ws, wi.fc2_sw, wi.fc2_b, Mi, h, r * h, DK_EPI_GATE_RES);
   f8_out_bf16(f2i, X_img);
   set_gate_res(f2i, mod_img + 5 * h, S_i, mod_stride, X_img);
-  GemmF8Params f1t = f8_params(m, m->XN8, m->SXN, h, T0, Mt, 0, wt.fc1_w8, h, wt.fc1_ws, wt.fc1_b, Mt, r * h, h, DK_EPI_BIAS_GELU);
+  GemmF4Params f1t = f8_params(m, m->XN8, m->SXN, h, T0, Mt, 0, wt.fc1_w8, h, wt.fc1_ws, wt.fc1_sw, wt.fc1_b, Mt, r * h, h, DK_EPI_BIAS_GELU);
   f8_out_hid8(f1t, m, T0);
-  GemmF8Params f2t = f8_params(m, m->HC8, m->SHID, ldh8, T0, Mt, 0, wt.fc2_w8, ldh8, wt.fc2_ws, wt.fc2_b, Mt, h, r * h, DK_EPI_GATE_RES);
+  GemmF4Params f2t = f8_params(m, m->HC8, m->SHID, ldh8, T0, Mt, 0, wt.fc2_w8, ldh8, wt.fc2_ws, wt.fc2_sw, wt.fc2_b, Mt, h, r * h, DK_EPI_GATE_RES);
   f8_out_bf16(f2t, X_txt);
   set_gate_res(f2t, mod_txt + 5 * h, S_t, mod_stride, X_txt);
-  DK_TRY(dk_launch_gemm256f8(f1i, txt_post ? &f1t : nullptr, st));
-  return dk_launch_gemm256f8(f2i, txt_post ? &f2t : nullptr, st);
+  DK_TRY(dk_launch_gemm_f8f4(f1i, txt_post ? &f1t : nullptr, st));
+  return dk_launch_gemm_f8f4(f2i, txt_post ? &f2t : nullptr, st);
 }
 
 // UnifiedTransformerBlock i on the fp8 GEMM
@@ -1056,22 +1067,22 @@ static int single_block_fp8(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t*
   const Rows X = dense(m->X, h);
   DK_TRY(dk_launch_ln_modulate_mx8(m->X, h, M, h, mod, mod + h, c.mod_stride, S, M, 0, cf.layer_norm_eps, c.xn_all, st));
   {  // linear1: [q|k|v] -> QKV (bf16), gelu(fc1) -> CAT8[:, h:] (MX-fp8), one pass over the modulated activations
-    GemmF8Params l1 = f8_params(m, m->XN8, m->SXN, h, 0, M, 0, w.qkv_w8, h, w.qkv_ws, w.qkv_b, M, (3 + r) * h, h, DK_EPI_BIAS);
+    GemmF4Params l1 = f8_params(m, m->XN8, m->SXN, h, 0, M, 0, w.qkv_w8, h, w.qkv_ws, w.qkv_sw, w.qkv_b, M, (3 + r) * h, h, DK_EPI_BIAS);
     f8_out_bf16(l1, dense(m->QKV, 3 * h));
     l1.n_split = 3 * h; l1.C2 = m->HC8 + h; l1.ldc2 = ldcat8; l1.epi2 = DK_EPI_BIAS_GELU; l1.c2_mx8 = 1;
     l1.SC = m->SCAT; l1.sc_nblk = m->nblk; l1.c_row0 = 0; l1.sc_kb0 = h / 32;
     if (keys_in_tail(w, nullptr)) set_key_norm(l1, w.kn, w.qn, h, m->D(), c.rope, 0, S);
-    DK_TRY(dk_launch_gemm256f8(l1, nullptr, st));
+    DK_TRY(dk_launch_gemm_f8f4(l1, nullptr, st));
   }
   if (!keys_in_tail(w, nullptr))
     DK_TRY(dk_launch_qk_norm_rope(m->QKV, 3 * h, 0, h, M, cf.num_heads, m->D(), w.qn, w.kn, 1e-6f, c.rope, S, S, 0, S, st, fuse_q()));
   // (the MX-fp8 copy: the [attn | gelu] operand of linear2, columns [0, h))
   DK_TRY(dk_launch_attention(joint_attention(m, c, m->ATT, h, w, nullptr, m->HC8, m->SCAT, ldcat8), L.aws, st));
   // x += gate * ([attn | gelu] @ [o_proj | fc2]^T + bias)   (one bias: quirk Q8)
-  GemmF8Params l2 = f8_params(m, m->HC8, m->SCAT, ldcat8, 0, M, 0, w.l2_w8, ldcat8, w.l2_ws, w.l2_b, M, h, (1 + r) * h, DK_EPI_GATE_RES);
+  GemmF4Params l2 = f8_params(m, m->HC8, m->SCAT, ldcat8, 0, M, 0, w.l2_w8, ldcat8, w.l2_ws, w.l2_sw, w.l2_b, M, h, (1 + r) * h, DK_EPI_GATE_RES);
   f8_out_bf16(l2, X);
   set_gate_res(l2, mod + 2 * h, S, c.mod_stride, X);
-  return dk_launch_gemm256f8(l2, nullptr, st);
+  return dk_launch_gemm_f8f4(l2, nullptr, st);
 }
 
 // Blocks [first, first + count) of the global order (double blocks 0 .. depth_multimodal - 1, then single blocks) on the joint residual

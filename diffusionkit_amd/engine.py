@@ -66,9 +66,9 @@ class MMDiTEngine:
         c.embed_dtype = _EMBED_DTYPE[config.dtype]
         c.layer_norm_eps = config.layer_norm_eps
         c.guidance_embed = int(config.guidance_embed)
-        if config.weight_dtype not in ("bfloat16", "fp8_e4m3"):
-            raise _lib.DkHipError(f"unknown weight_dtype {config.weight_dtype!r} (bfloat16 | fp8_e4m3)")
-        c.fp8_linears = int(config.weight_dtype == "fp8_e4m3")
+        if config.weight_dtype not in ("bfloat16", "fp8_e4m3", "mxfp4"):
+            raise _lib.DkHipError(f"unknown weight_dtype {config.weight_dtype!r} (bfloat16 | fp8_e4m3 | mxfp4)")
+        c.fp8_linears = {"bfloat16": 0, "fp8_e4m3": 1, "mxfp4": 2}[config.weight_dtype]  # (2: MX-fp4 weights on the fp8 engine's activation path)
         if c.fp8_linears:
             from .config import validate_fp8_policy
             validate_fp8_policy(config)
@@ -162,7 +162,7 @@ class MMDiTEngine:
         self.control_taps = None
         self.weights = packed_weights  # keep the device tensors alive
         for name, t in packed_weights.items():
-            want = torch.uint8 if name.endswith(".weight_fp8") else torch.float32 if name.endswith(".wscale") else self.dtype
+            want = torch.uint8 if name.endswith((".weight_fp8", ".weight_fp4", ".wscale4")) else torch.float32 if name.endswith(".wscale") else self.dtype
             _require_cuda(t, name, want)
             _lib.check(self.lib.dk_mmdit_bind(self._h, name.encode(), t.data_ptr()), f"bind {name}")
         self.guidance = 3.5  # FLUX.1-dev's default distilled-guidance strength; only read when config.guidance_embed
@@ -209,10 +209,11 @@ class MMDiTEngine:
         binds bare pointers, so the layout the packer produced is checked here, where the shapes are still known."""
         h, r = self.config.hidden_size, self.config.mlp_ratio
         for name, t in self.weights.items():
-            fp8 = name.endswith(".weight_fp8")
+            fp8 = name.endswith((".weight_fp8", ".weight_fp4"))
             base = name[:-len(".weight_fp8" if fp8 else ".weight")] if (fp8 or name.endswith(".weight")) else ""
             k = r * h if base.endswith(".mlp.fc2") else (1 + r) * h if base.endswith(".linear2") else 0
-            pitch = (self.lib.dk_weight_pitch_fp8 if fp8 else self.lib.dk_weight_pitch)(k) if k else 0
+            rule = self.lib.dk_weight_pitch_fp4 if name.endswith(".weight_fp4") else self.lib.dk_weight_pitch_fp8 if fp8 else self.lib.dk_weight_pitch
+            pitch = rule(k) if k else 0
             if k and t.shape[1] != pitch:
                 raise _lib.DkHipError(f"{name}: {t.shape[1]} elements per row, the engine expects dk_weight_pitch({k}) = "
                                       f"{pitch} (was the weight packed under a different pitch_min_k?)")

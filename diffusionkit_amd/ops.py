@@ -1038,13 +1038,16 @@ def ln_modulate_mx8(x: Tensor, shift: Tensor, scale: Tensor, mod_seg_len: int = 
 def gemm_fp8(a8: Tensor, a_scales: Tensor, w8: Tensor, w_scale: Tensor, bias: Optional[Tensor] = None, epilogue: int = DK_EPI_BIAS,
              gate: Optional[Tensor] = None, res: Optional[Tensor] = None, gate_seg_len: int = 0, M: Optional[int] = None,
              k: Optional[int] = None, out_mx8: bool = False, workspace: Optional[Tensor] = None, out: Optional[Tensor] = None,
-             out_scales: Optional[Tensor] = None):
+             out_scales: Optional[Tensor] = None, _launch=None):
     """dk_gemm_fp8 over the first M rows / k columns of an MX-fp8 activation buffer a8 [rows, lda] and an e4m3 weight w8 [N, ldw]; any M >= 1 (the
     last 128-row scale block of a8 may be partial).  Returns bf16 [M, N], or with ``out_mx8`` (e4m3 bytes [M, N], scale side array).  ``workspace``
     (ops.gemm_workspace): lets a launch of at most half a round of tiles with a long reduction be cut along K, as the engines do.  ``out`` (and, with
     ``out_mx8``, ``out_scales`` = a side array of ops.mx_scale_bytes(out rows, out pitch)): an output buffer of at least M rows to write rows
     [0, M) of; the other rows are left alone."""
     lib = _lib.load()
+    if _launch is None:  # (ops.gemm_fp4 passes its own entry: the descriptor is the same)
+        def _launch(desc):
+            _lib.check(lib.dk_gemm_fp8(C.byref(desc), _stream()), "dk_gemm_fp8")
     for n, t, dt in (("a8", a8, torch.uint8), ("a_scales", a_scales, torch.uint8), ("w8", w8, torch.uint8), ("w_scale", w_scale, torch.float32)):
         _require_cuda(t, n, dt)
     M = a8.shape[0] if M is None else M
@@ -1076,10 +1079,36 @@ def gemm_fp8(a8: Tensor, a_scales: Tensor, w8: Tensor, w_scale: Tensor, bias: Op
         if sc.numel() < mx_scale_bytes(out.shape[0], out.stride(0)):
             raise ValueError("out_scales is smaller than ops.mx_scale_bytes(out rows, out pitch)")
         d.C, d.ldc, d.c_mx8, d.C_scales, d.c_rows, d.c_row0, d.c_col0 = out.data_ptr(), out.stride(0), 1, sc.data_ptr(), out.shape[0], 0, 0
-        _lib.check(lib.dk_gemm_fp8(C.byref(d), _stream()), "dk_gemm_fp8")
+        _launch(d)
         return out, sc
     if out is None:
         out = torch.empty(M, N, dtype=BF, device=a8.device)
     d.C, d.ldc = out.data_ptr(), out.stride(0)
-    _lib.check(lib.dk_gemm_fp8(C.byref(d), _stream()), "dk_gemm_fp8")
+    _launch(d)
     return out
+
+
+# ---- MX-fp4 weights (include/dk_hip.h: dk_gemm_fp4; weights.quantize_weight_mxfp4 / pack_mxfp4 make the operands) ----
+def weight_pitch_fp4(k: int) -> int:
+    return int(_lib.load().dk_weight_pitch_fp4(k))
+
+
+def gemm_fp4(a8: Tensor, a_scales: Tensor, w4: Tensor, w_block_scales: Tensor, w_scale: Tensor, bias: Optional[Tensor] = None, **kw):
+    """dk_gemm_fp4: ops.gemm_fp8 with an MX-fp4 weight -- w4 uint8 [N, ldw] in the kernel's fragment-row layout and w_block_scales, its E8M0
+    side array (both from weights.pack_mxfp4), w_scale f32 [N].  ``k`` is required when the weight is pitched (the activation buffer's width
+    otherwise).  Every other argument and the results are ops.gemm_fp8's."""
+    _require_cuda(w_block_scales, "w_block_scales", torch.uint8)
+    lib = _lib.load()
+
+    def launch(desc):
+        _lib.check(lib.dk_gemm_fp4(C.byref(desc), w_block_scales.data_ptr(), _stream()), "dk_gemm_fp4")
+    return gemm_fp8(a8, a_scales, w4, w_scale, bias, _launch=launch, **kw)
+
+
+def gemm_fp4_fused_call(d: dict, side: Optional[dict], w_block_scales: Tensor, d2: Optional[dict] = None, side2: Optional[dict] = None,
+                        w_block_scales2: Optional[Tensor] = None) -> None:
+    """dk_gemm_fp4_fused: gemm_fp8_fused_call's forms with MX-fp4 weights and their block-scale side arrays."""
+    a, f = _fill(_lib.dk_gemm_fp8_desc, d), _fill(_lib.dk_gemm_fp8_side, side)
+    b, f2 = _fill(_lib.dk_gemm_fp8_desc, d2), _fill(_lib.dk_gemm_fp8_side, side2)
+    _lib.check(_lib.load().dk_gemm_fp4_fused(_ref(a), _ref(f), w_block_scales.data_ptr(), _ref(b), _ref(f2), _ptr(w_block_scales2), _stream()),
+               "dk_gemm_fp4_fused")

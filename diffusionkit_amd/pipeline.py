@@ -51,7 +51,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .config import (MMDIT_CKPT, MODEL_CONFIG, SKIP_LAYER_GUIDANCE, T5_MAX_LENGTH, MMDiTConfig, VAEDecoderConfig, VAEEncoderConfig)
+from .config import (MMDIT_CKPT, MODEL_CONFIG, SKIP_LAYER_GUIDANCE, T5_MAX_LENGTH, MMDiTConfig, VAEDecoderConfig, VAEEncoderConfig, low_bit_name)
 from .engine import MMDiTEngine, VAEDecoderEngine, VAEEncoderEngine, _stream
 from .sampler import (STOCHASTIC_SAMPLERS, FluxSampler, ModelSamplingDiscreteFlow, check_guidance, check_interval, check_perturbed_attention_guidance,
                       check_sampler, check_sampler_eta, check_skip_layer_guidance, get_sigmas,
@@ -417,8 +417,9 @@ class DiffusionPipeline:
         if cfg.dual_attention_blocks > 0:
             raise ValueError("controlnet_ckpt cannot be combined with dual attention blocks (SD3.5-medium): the engine adds taps in a plain block's "
                              "LayerNorm launch only")
-        if cfg.weight_dtype == "fp8_e4m3":
-            raise ValueError("controlnet_ckpt cannot be combined with an fp8 engine: the taps are added on the bf16 / fp16 path only")
+        if low_bit_name(cfg):
+            name = low_bit_name(cfg)
+            raise ValueError(f"controlnet_ckpt cannot be combined with an {name} engine: the taps are added on the bf16 / fp16 path only")
         ccfg = replace(controlnet_config or SD3_CONTROLNET_6, activation_dtype=cfg.activation_dtype)
         if not ccfg.control_net:
             raise ValueError("controlnet_config must be a control-net configuration (control_net=True, e.g. config.SD3_CONTROLNET_6)")
@@ -1500,8 +1501,9 @@ def _perturbed_attention_options(scale, layers, interval, mmdit_config, is_flux,
                          "CFG rows (PAG without CFG is not built)")
     if block_cache is not None:
         raise ValueError("perturbed-attention guidance cannot run together with block_cache: there is no cache policy for a forked row group yet")
-    if mmdit_config.weight_dtype == "fp8_e4m3":
-        raise ValueError("perturbed-attention guidance cannot run on an fp8 engine: the identity attention has no MX-fp8 output copy")
+    if low_bit_name(mmdit_config):
+        name = low_bit_name(mmdit_config)
+        raise ValueError(f"perturbed-attention guidance cannot run on an {name} engine: the identity attention has no MX-fp8 output copy")
     if reference is not None:
         raise ValueError("perturbed-attention guidance cannot run with a reference image: the forked row group has no reference grid")
     if condition is not None:
@@ -1530,8 +1532,9 @@ def _check_flux_controlnet_config(pipe, controlnet_config) -> None:
         raise ValueError("controlnet_ckpt without a controlnet_config is the SD3 family's preset (config.SD3_CONTROLNET_6, diffusers' SD3ControlNetModel): a "
                          "FLUX pipeline names its ControlNet's depths, controlnet_config=config.flux_controlnet_config(n_double, n_single) -- FLUX "
                          "ControlNets (diffusers' FluxControlNetModel) have no canonical depth")
-    if cfg.weight_dtype == "fp8_e4m3":
-        raise ValueError("controlnet_ckpt cannot be combined with an fp8 engine: the fp8 LayerNorm kernels take no tap")
+    if low_bit_name(cfg):
+        name = low_bit_name(cfg)
+        raise ValueError(f"controlnet_ckpt cannot be combined with an {name} engine: the MX-fp8 LayerNorm kernels of the fp8 / fp4 engines take no tap")
     if cfg.condition_features != 0 or getattr(pipe, "condition", None) is not None:
         raise ValueError("controlnet_ckpt cannot be combined with condition= (FLUX.1 Fill / Canny / Depth): the engine carries one kind of image "
                          "conditioning at a time")
@@ -1554,8 +1557,9 @@ def _check_ip_adapter_config(pipe, ip_config, controlnet_ckpt) -> None:
     cfg = pipe.mmdit_config
     if not pipe._IS_FLUX:
         raise ValueError("ip_adapter_ckpt is the FLUX family's (FluxPipeline): SD3 and SD3.5 IP-Adapters are not built")
-    if cfg.weight_dtype == "fp8_e4m3":
-        raise ValueError("ip_adapter_ckpt cannot be combined with an fp8 engine: the fp8 LayerNorm kernels take no tap")
+    if low_bit_name(cfg):
+        name = low_bit_name(cfg)
+        raise ValueError(f"ip_adapter_ckpt cannot be combined with an {name} engine: the MX-fp8 LayerNorm kernels of the fp8 / fp4 engines take no tap")
     if getattr(pipe, "condition", None) is not None:
         raise ValueError("ip_adapter_ckpt cannot be combined with condition= (FLUX.1 Fill / Canny / Depth): the engine refuses a condition width beside "
                          "the adapter")

@@ -317,14 +317,80 @@ def dequantize_weight_e4m3(q: Tensor, scale: Tensor, k: int = None) -> Tensor:
     return w if k is None else w[:, :k]
 
 
-BLOCK_LINEARS = (".attn.qkv", ".attn.o_proj", ".mlp.fc1", ".mlp.fc2", ".linear1", ".linear2")  # what weight_dtype = "fp8_e4m3" quantises
+E2M1_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # magnitudes of the OCP fp4 codes 0..7; bit 3 is the sign
+
+
+def quantize_weight_mxfp4(w: Tensor):
+    """[N, K] weight (K a multiple of 128) -> (E2M1 codes uint8 [N, K] with values 0..15, E8M0 bytes uint8 [N, K / 32], fp32 wscale [N]): the
+    definition of the OCP MX-fp4 weight format of the W4A8 GEMM (csrc/gemm256f4.hip).
+    wscale[n] = row amax / 6 (1 for an all-zero row).  Per 32-K block of w / wscale the block scale is the smallest power of two s with block
+    amax <= 6 s, decided by exact comparison on the mantissa (never through a rounded 1/6), stored as biased E8M0 clamped to [1, 254]; a zero
+    block takes code 1.  Elements = round-to-nearest-even(block / s) on the E2M1 grid; |block / s| <= 6, so nothing saturates.  fp32 arithmetic
+    on whatever device ``w`` lives on; ``dequantize_weight_mxfp4`` gives back the values the GEMM multiplies with."""
+    wf = w.to(torch.float32)
+    n, k = wf.shape
+    if k % 128 != 0:
+        raise ValueError(f"quantize_weight_mxfp4: K = {k} is not a multiple of 128")
+    amax = wf.abs().amax(dim=1)
+    wscale = torch.where(amax > 0, amax / 6.0, torch.ones_like(amax))
+    x = (wf / wscale[:, None]).view(n, k // 32, 32)
+    m, e = torch.frexp(x.abs().amax(dim=2))  # block amax = m * 2^e, m in [0.5, 1): 6 * 2^(e - 3) = 0.75 * 2^e
+    t = torch.where(m <= 0.75, e - 3, e - 2)
+    e8 = torch.where(m > 0, t + 127, torch.ones_like(t)).clamp_(1, 254)
+    a = torch.ldexp(x.abs(), (127 - e8)[:, :, None])  # exact: a power of two
+    # round to nearest even on the grid: steps of 0.5 below 2, of 1 below 4, of 2 up to 6 (torch.round rounds halves to even, which is the even code)
+    mag = torch.where(a < 2, torch.round(a * 2) / 2, torch.where(a < 4, torch.round(a), torch.round(a / 2) * 2))
+    code = torch.where(mag < 2, mag * 2, torch.where(mag < 4, mag + 2, mag / 2 + 4)).to(torch.uint8)
+    code = code | (((x < 0) & (mag > 0)).to(torch.uint8) << 3)
+    return code.view(n, k), e8.to(torch.uint8), wscale
+
+
+def dequantize_weight_mxfp4(code: Tensor, e8: Tensor, wscale: Tensor) -> Tensor:
+    """fp32 values q * 2^(e - 127) * wscale of a quantised weight (codes [N, K], E8M0 [N, K / 32], wscale [N])."""
+    n, k = code.shape
+    grid = torch.tensor(E2M1_GRID, dtype=torch.float32, device=code.device)
+    q = grid[(code & 7).long()] * torch.where((code & 8) != 0, -1.0, 1.0)
+    q = torch.ldexp(q.view(n, k // 32, 32), (e8.to(torch.int32) - 127)[:, :, None]).view(n, k)
+    return q * wscale.to(torch.float32)[:, None]
+
+
+def pack_mxfp4(code: Tensor, e8: Tensor, pitch: int = None):
+    """(E2M1 codes [N, K], E8M0 [N, K / 32]) -> (uint8 [N, pitch], uint8 [N * K / 32]) in the layout csrc/gemm256f4.hip reads.  N a multiple of
+    64, K of 128; pitch (bytes per output channel, default K / 2) a multiple of 64.
+    Weights: two codes per byte, even K in the low nibble; every 16 output channels are one fragment row of 16 * pitch bytes in which K-tile t
+    (128 K) is 1024 bytes in MFMA lane order -- lane (r, q) = 16 bytes at (q * 16 + r) * 16 = channel r, K [32 q, 32 q + 32) of the tile.
+    Scales: [N / 64][K / 128][lane (r, g)][nf] = channel 64 G + 16 nf + r, K block 4 t + g."""
+    n, k = code.shape
+    pitch = k // 2 if pitch is None else pitch
+    if n % 64 != 0 or k % 128 != 0 or pitch % 64 != 0 or pitch < k // 2:
+        raise ValueError(f"pack_mxfp4: N = {n} (% 64), K = {k} (% 128), pitch = {pitch} (% 64, >= K / 2)")
+    by = code[:, 0::2] | (code[:, 1::2] << 4)  # [N, K / 2]
+    frag = by.view(n // 16, 16, k // 128, 4, 16).permute(0, 2, 3, 1, 4).reshape(n // 16, k * 8)
+    w4 = torch.zeros(n // 16, 16 * pitch, dtype=torch.uint8, device=code.device)
+    w4[:, :k * 8] = frag
+    sw = e8.view(n // 64, 4, 16, k // 128, 4).permute(0, 3, 4, 2, 1).reshape(-1)
+    return w4.view(n, pitch), sw.contiguous()
+
+
+def unpack_mxfp4(w4: Tensor, sw: Tensor, k: int):
+    """inverse of pack_mxfp4: (codes [N, K], E8M0 [N, K / 32]) from the packed bytes"""
+    n, pitch = w4.shape
+    by = w4.reshape(n // 16, 16 * pitch)[:, :k * 8].reshape(n // 16, k // 128, 4, 16, 16).permute(0, 3, 1, 2, 4).reshape(n, k // 2)
+    code = torch.stack([by & 15, by >> 4], dim=2).reshape(n, k)
+    e8 = sw.view(n // 64, k // 128, 4, 16, 4).permute(0, 4, 3, 1, 2).reshape(n, k // 32)
+    return code, e8
+
+
+BLOCK_LINEARS = (".attn.qkv", ".attn.o_proj", ".mlp.fc1", ".mlp.fc2", ".linear1", ".linear2")  # what weight_dtype "fp8_e4m3" / "mxfp4" quantises
 
 
 def pack_mmdit(cfg: MMDiTConfig, w: Dict[str, Tensor], device, consume: bool = False) -> Dict[str, Tensor]:
     """Reference-named weights -> engine tensors (``cfg.activation_dtype``: bf16 by default; contiguous, on ``device``).
     ``consume=True`` pops source tensors as they are packed (halves peak memory at full size).
     With ``cfg.weight_dtype == "fp8_e4m3"`` the Linear matrices of the transformer blocks leave as
-    "<name>.weight_fp8" (uint8 e4m3, rows at dk_weight_pitch_fp8) + "<name>.wscale" (fp32) instead of "<name>.weight"."""
+    "<name>.weight_fp8" (uint8 e4m3, rows at dk_weight_pitch_fp8) + "<name>.wscale" (fp32) instead of "<name>.weight"; with "mxfp4" as
+    "<name>.weight_fp4" (pack_mxfp4 at dk_weight_pitch_fp4) + "<name>.wscale4" (E8M0, kernel layout) + "<name>.wscale".  A source that was itself
+    4-bit (the reference's MLX checkpoints, dequantised by model_io) is RE-quantised here: no bit-preserving load."""
     dev = torch.device(device)
     # element type of every tensor the engine binds: cfg.activation_dtype.  float16: a value from an fp16 or fp32 source is rounded once to fp16,
     # and an fp16 checkpoint tensor reaches the device bit for bit (same names, pitches and fusions)
@@ -337,7 +403,8 @@ def pack_mmdit(cfg: MMDiTConfig, w: Dict[str, Tensor], device, consume: bool = F
     control_flux = bool(getattr(cfg, "control_net_flux", False))
     control_net = bool(getattr(cfg, "control_net", False))
     bf = torch.float16 if cfg.activation_dtype == "float16" else torch.bfloat16
-    fp8 = cfg.weight_dtype == "fp8_e4m3"
+    fp4 = cfg.weight_dtype == "mxfp4"
+    fp8 = cfg.weight_dtype == "fp8_e4m3" or fp4  # (the low-bit path: same Linears, same precision policy)
     out: Dict[str, Tensor] = {}
     get = (lambda k: w.pop(k)) if consume else (lambda k: w[k])
 
@@ -353,6 +420,11 @@ def pack_mmdit(cfg: MMDiTConfig, w: Dict[str, Tensor], device, consume: bool = F
     def put(name, t):
         if is_fp8(name) and name.endswith(".weight") and name[:-len(".weight")].endswith(BLOCK_LINEARS):
             base = name[:-len(".weight")]
+            if fp4:  # OCP MX-fp4 in the kernel's fragment layout + E8M0 block scales + the per-channel scale (the bf16 weight is what gets quantised)
+                code, e8, scale = quantize_weight_mxfp4(t.to(device=dev, dtype=bf))
+                w4, sw = pack_mxfp4(code, e8, int(_lib.load().dk_weight_pitch_fp4(code.shape[1])))
+                out[base + ".weight_fp4"], out[base + ".wscale4"], out[base + ".wscale"] = w4.contiguous(), sw, scale.contiguous()
+                return
             q, scale = quantize_weight_e4m3(t.to(device=dev, dtype=bf))  # the bf16 weight is what gets quantised
             k = q.shape[1]
             pitch = int(_lib.load().dk_weight_pitch_fp8(k))

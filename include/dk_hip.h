@@ -361,6 +361,19 @@ int dk_ln_modulate_mx8(const void* x, int32_t ldx, int32_t M, int32_t h, const v
 /* row pitch in bytes of an fp8 matrix with k columns that is read with a long reduction (k + 128 from 8192 on, see dk_weight_pitch) */
 int32_t dk_weight_pitch_fp8(int32_t k);
 
+/* ---- MX-fp4 weights (W4A8): the fp8 path's Linears with OCP MX-fp4 weights on the same block-scaled MFMA --------------------------
+ * The descriptors are the fp8 ones with three fields read differently: W is E2M1, two elements per byte, in the kernel's fragment-row layout
+ * (uint8 [N, ldw], ldw = dk_weight_pitch_fp4(K) bytes per output channel; diffusionkit_amd/weights.py: pack_mxfp4 writes it,
+ * csrc/gemm256f4.hip documents it), w_scale stays one f32 per output channel, and w_block_scales is the E8M0 side array of the weights, N * K / 32
+ * bytes, 4-byte aligned, in the kernel's layout.  Activations, outputs, epilogues, column split, grouped second problem and K-split workspace
+ * are dk_gemm_fp8's / dk_gemm_fp8_fused's.  Refused by name, nothing launched: K % 128, N % 256, a weight pitch that is no multiple of 64 bytes or
+ * below K / 2, misaligned scale arrays, buffers beyond the 32-bit offsets of the DMA. */
+int dk_gemm_fp4(const dk_gemm_fp8_desc* d, const void* w_block_scales, void* stream);
+int dk_gemm_fp4_fused(const dk_gemm_fp8_desc* d, const dk_gemm_fp8_side* f, const void* w_block_scales, const dk_gemm_fp8_desc* d2,
+                      const dk_gemm_fp8_side* f2, const void* w_block_scales2, void* stream);
+/* bytes per output channel of an MX-fp4 matrix with k columns (k / 2, + 64 from the dk_weight_pitch threshold on) */
+int32_t dk_weight_pitch_fp4(int32_t k);
+
 /* affine_transform + LayerNorm, mmdit.py:958-972, 838-849.
  * out[m,:] = LN(x[m,:]) * (1 + scale[b,:]) + shift[b,:], b = m / mod_seg_len. */
 int dk_ln_modulate_bf16(const void* x, int32_t ldx, void* out, int32_t ldo, int32_t M, int32_t h,
@@ -730,7 +743,10 @@ typedef struct dk_mmdit_config {
    * e4m3 weights ("<name>.weight_fp8" uint8 [N, dk_weight_pitch_fp8(K)] + "<name>.wscale" f32 [N] instead of
    * "<name>.weight") and MX-fp8 activations quantised on the fly (BASELINE.json configs[3]; the reference's counterpart is
    * its 4-bit nn.QuantizedLinear checkpoints, model_io.py:728-734,772-775).  Needs head_dim 128 and a text length that is
-   * one of the multiples of 128; the image token count is free (dk_mmdit_prepare).  0: bf16 weights. */
+   * one of the multiples of 128; the image token count is free (dk_mmdit_prepare).  0: bf16 weights.
+   * 2: the same Linears with OCP MX-fp4 weights on the same MFMA (W4A8): "<name>.weight_fp4" uint8 [N, dk_weight_pitch_fp4(K)] in the fragment
+   * layout of dk_gemm_fp4 + "<name>.wscale4" uint8 [N * K / 32] E8M0 block scales + "<name>.wscale" f32 [N]; activations, buffers, workspace
+   * and every rule that names fp8_linears are those of 1. */
   int32_t fp8_linears;
   /* fp8 precision policy (round 5; only read with fp8_linears): the Linears of the first fp8_bf16_double_blocks double-stream blocks
    * stay bf16 ("<name>.weight", bf16 activations, the bf16 GEMM): errors made in the first blocks travel through all 57 -- measured
