@@ -1,5 +1,6 @@
 """Per-element and per-row gates of the operator parity tests, their fp32 restatements, case lists and mutants (tests/test_gate_power_cpu.py proves
-the gates on the host, tests/test_gpu_ops.py and tests/test_gpu_f16_ops.py apply them to the HIP kernels).  Plain torch, no GPU.
+the gates on the host, tests/test_gpu_ops.py and tests/test_gpu_f16_ops.py apply them to the HIP kernels; tests/test_gpu_fp8.py, tests/test_gpu_fp8_ragged.py
+and tests/test_gpu_fp4.py to the block-scaled GEMMs, with the MX-fp8 output bound of mx8_bound).  Plain torch, no GPU.
 
 A whole-tensor rel-L2 at 3e-3 sits over a bf16 rounding floor of 1.7e-3 and cannot see a fault confined to a row, a fragment or a tile edge.  The gates here
 are local:
@@ -95,11 +96,12 @@ def epilogue_f32(acc, dt, epi, res=None, gate=None):
     return rnd(res + rnd(gate * pre, dt), dt)
 
 
-def epilogue_bound(pre, unit, dt, epi, res=None, gate=None):
+def epilogue_bound(pre, unit, dt, epi, res=None, gate=None, C=None):
     """(ref64, bound) from the fp64 pre-activation and its unit: the error of the pre-activation, sp(pre) + C unit, goes through the epilogue by its
     derivative bound (GELU / SiLU 1.13, gate x by |gate|); every further rounding point adds its spacing, taken at |value| + the error that has reached
-    it (a value pushed over a power of two is rounded on the coarser grid)"""
-    e = spacing(pre.abs() + C_GEMM * unit, dt) + C_GEMM * unit
+    it (a value pushed over a power of two is rounded on the coarser grid).  ``C``: C_GEMM, or C_GEMM_Q for the quantised GEMMs"""
+    C = C_GEMM if C is None else C
+    e = spacing(pre.abs() + C * unit, dt) + C * unit
     if epi == "bias":
         return pre, e
     if epi in ("gelu", "silu"):
@@ -124,10 +126,11 @@ def gemm_ref64(x, w, b):
     return pre, unit
 
 
-def gemm_gate(got, x, w, b, dt, epi="bias", res=None, gate=None, rows=None):
+def gemm_gate(got, x, w, b, dt, epi="bias", res=None, gate=None, rows=None, C=None, where=False):
     """worst |got - ref| / bound of a GEMM output [M, N], or of several (a list: one reference serves them all); ``gate`` already expanded to rows
-    [M, N] or broadcastable [1, N]; ``rows``: the subset"""
+    [M, N] or broadcastable [1, N]; ``rows``: the subset.  ``where``: (worst, (row, column) of it in the whole output)"""
     gots = got if isinstance(got, (list, tuple)) else [got]
+    cols = None
     if rows is not None:
         gots, x = [t[rows] for t in gots], x[rows]
         res = res[rows] if res is not None else None
@@ -138,8 +141,13 @@ def gemm_gate(got, x, w, b, dt, epi="bias", res=None, gate=None, rows=None):
             res = res[:, cols] if res is not None else None
             gate = gate[:, cols] if gate is not None else None
     pre, unit = gemm_ref64(x, w, b)
-    ref, bound = epilogue_bound(pre, unit, dt, epi, res, gate)
-    return max(worst((t.detach().double().cpu() - ref).abs(), bound) for t in gots)
+    ref, bound = epilogue_bound(pre, unit, dt, epi, res, gate, C)
+    if not where:
+        return max(worst((t.detach().double().cpu() - ref).abs(), bound) for t in gots)
+    ratio = torch.stack([(t.detach().double().cpu() - ref).abs() / bound for t in gots]).amax(0)
+    i = int(ratio.argmax())
+    r, c = i // ratio.shape[1], i % ratio.shape[1]
+    return float(ratio.max()), (int(rows[r]) if rows is not None else r, int(cols[c]) if cols is not None else c)
 
 
 def _gemm_case(name, M, N, K, seeds, wscale, bscale, epi="bias", dt=BF, gate_rows=1, ksplit=False):
@@ -274,6 +282,339 @@ class GemmRestatement:
             m["gelu before bias"] = self.m_gelu_before_bias
         if self.c["ksplit"]:
             m["slab omitted"] = self.m_slab_omitted
+        return m
+
+
+# ---- quantised GEMMs: gemm256f8.hip (MX-fp8 x e4m3) and gemm256f4.hip (MX-fp8 x MX-fp4), per element -----------------------------------------------
+# The reference is the fp64 product of the DEQUANTISED operands, so the gate is gemm_gate as it stands.  The kernels multiply element values and block
+# scales inside the MFMA and apply the per-channel wscale in the tail, where the dequantised weight of the reference is fp32(q 2^e wscale): one fp32
+# rounding per weight more than a bf16 GEMM has.  C_GEMM_Q: twice the worst |fp32 restatement - ref64| / unit over QGEMM_CASES, both summation orders
+# (torch's own; K walked in 128-wide K-tiles), wscale and bias applied behind the sum as the tails do.  Measured (test_gate_power_cpu.py::
+# test_qgemm_gate prints them): 3.52e-7 (fp4 "block scales 256x256x256", torch's order; K-tiles 1.59e-7, and 1.79e-7 at K = 640): weight blocks
+# that differ by 2^+-8 leave a few large products to carry the sum.  Every other case stays at or below 8.09e-8 (fp8 "gelu mx8 fc1 512x1024x256",
+# torch's order; K-tiles 6.33e-8 at fp8 256x256x128).  3.52e-7 is more than half of C_GEMM (1.95e-7), so the quantised kernels take their own constant.
+C_GEMM_Q = 7.1e-7
+KT = 128  # K-tile of both kernels; one block scale per 32 K
+
+
+def q_weight(kind, w):
+    """bf16 [N, K] -> (element values fp32 (e4m3 / E2M1), block exponents int32 [N, K / 32] (fp8: zeros, it has no block scale), wscale [N],
+    dequantised fp32 [N, K]) through the product quantisers, as tests/test_gpu_fp8.py and tests/_mxfp4.py build them"""
+    from diffusionkit_amd.weights import dequantize_weight_e4m3, dequantize_weight_mxfp4, quantize_weight_e4m3, quantize_weight_mxfp4
+    if kind == "fp8":
+        qw, ws = quantize_weight_e4m3(w)
+        return qw.view(torch.float8_e4m3fn).float(), torch.zeros(w.shape[0], w.shape[1] // 32, dtype=torch.int32), ws, dequantize_weight_e4m3(qw, ws)
+    code, e8, ws = quantize_weight_mxfp4(w)
+    el = dequantize_weight_mxfp4(code, torch.full_like(e8, 127), torch.ones_like(ws))
+    return el, e8.to(torch.int32) - 127, ws, dequantize_weight_mxfp4(code, e8, ws)
+
+
+def q_scaled(el, eb):
+    """element values x 2^(block exponent): what the MFMA multiplies (exact in fp32)"""
+    n, k = el.shape
+    return torch.ldexp(el.view(n, k // 32, 32), eb[:, :, None]).reshape(n, k)
+
+
+def q_raw(x, wq, order="tiles"):
+    """fp32 sum of the block products without wscale: torch's own order, or K walked in 128-wide K-tiles"""
+    if order == "torch":
+        return x @ wq.t()
+    acc = torch.zeros(x.shape[0], wq.shape[0])
+    for k0 in range(0, x.shape[1], KT):
+        acc += x[:, k0:k0 + KT] @ wq[:, k0:k0 + KT].t()
+    return acc
+
+
+def mx8_bound(ref, e):
+    """bound of an MX-fp8 output, per element on the decoded value: e + q.  ``e``: the bound of the bf16 value the tail forms (epilogue_bound); q: the
+    e4m3 half-spacing (3 mantissa bits, subnormal step 2^-9 below 2^-6) of |ref| + e under the block scale oracle/fp8.py: mx8_encode gives the block
+    (32 columns) -- its rule evaluated on the largest block maximum the bound allows, max(|ref| + e): the exponent is monotone in the maximum, so where
+    amax +- e straddles a change of scale this is the coarser of the two.  q is an exact rounding bound, not a doubled measurement: a correct result
+    may reach e / 2 + q, so the restatement passes this gate at <= 1, not at half the bound"""
+    from oracle import fp8 as o8
+    M, N = ref.shape
+    hi = (ref.abs() + e).reshape(M, N // 32, 32)
+    s = torch.ldexp(torch.ones(M, N // 32, 1, dtype=torch.float64), o8.mx8_scale_exponent(hi.amax(-1, keepdim=True).float()) - 127)
+    _, ex = torch.frexp(hi / s)
+    q = 0.5 * torch.ldexp(s.expand_as(hi), (ex - 1).clamp(min=-6) - 3)
+    return e + q.reshape(M, N)
+
+
+def qgemm_gate(got, x, w, b, epi="bias", res=None, gate=None):
+    """gemm_gate of a quantised GEMM's bf16 output (or of several) on the dequantised operands, the row / column subset taken from the shape ->
+    (worst error / bound, (row, column) of it)"""
+    return gemm_gate(got, x, w, b, BF, epi, res, gate, rows=row_subset(x.shape[0], w.shape[0], w.shape[1]), C=C_GEMM_Q, where=True)
+
+
+def assert_gate(what, worst_at, missed=False):
+    """print a gate's worst error / bound and where it sits, and assert it.  ``missed``: a form on which the kernels are known to leave the bound
+    ("What the kernels miss"): the figure is printed, so that it can be followed in the log, and not asserted"""
+    ratio, at = worst_at
+    print(f"[gate{', not asserted' if missed else ''}] {what}: worst |got - ref64| / bound {ratio:.3f} at {at}")
+    assert missed or ratio <= 1.0, f"{what}: {ratio:.3f} of the per-element bound at {at}"
+
+
+def mx8_gate(got, x, w, b, epi="gelu"):
+    """(worst |decoded MX-fp8 output - ref64| / mx8_bound, (row, column) of it); every row: the MX-fp8 outputs of the tests are small"""
+    pre, unit = gemm_ref64(x, w, b)
+    ref, e = epilogue_bound(pre, unit, BF, epi, C=C_GEMM_Q)
+    ratio = (got.detach().double().cpu() - ref).abs() / mx8_bound(ref, e)
+    i = int(ratio.argmax())
+    return float(ratio.max()), (i // ratio.shape[1], i % ratio.shape[1])
+
+
+def _q_case(name, kind, M, N, K, act, w=None, b=5, epi="bias", res=None, gate=None, win=None, ksplit=False, mx8=False):
+    """act: (seed, rows of the buffer, first row) of tests/_fp8.py fp8_activation, or ("hidden", fc1 case): the MX-fp8 output of that case; w: (seed,
+    scale) or "pattern" (+-2^8 block pattern), default (act seed + 1, 0.02); b: seed or None; res: seed (a buffer of the activation's rows), or
+    ("joint", c_row0, seg, S, B): rows of the joint buffer X (seed 60); gate: (rows of the gate tensor, seed, segment length); win: (N of the whole
+    weight, first column) of a column window"""
+    w = (act[0] + 1, 0.02) if w is None else w
+    return dict(name=f"{kind} {name} {M}x{N}x{K}", kind=kind, M=M, N=N, K=K, act=act, w=w, b=b, epi=epi, res=res, gate=gate, win=win, ksplit=ksplit,
+                mx8=mx8, dt=BF, gate_rows=(M + gate[2] - 1) // gate[2] if gate else 1)
+
+
+def _q_both(kind):
+    """the forms tests/test_gpu_fp8.py and tests/test_gpu_fp4.py share (test_gemm_fp4_tail_forms runs the fp8 tests' forms on the fp4 kernel)"""
+    fc1 = _q_case("gelu mx8 fc1", kind, 512, 1024, 256, (31, 512, 0), b=8, epi="gelu", mx8=True)
+    pairs = [(2, 128, 384)] if kind == "fp8" else [(2, 128, 384), (2, 128, 192), (1, 1, 384)]  # (B, S_t, S_i); fp4: a_row0 = 384, and a text M of 1
+    out = [_q_case("gate_res", kind, 512, 256, 256, (21, 512, 0), res=7, gate=(2, 6, 256), epi="gate_res"), fc1,
+           _q_case("gelu mx8 fc2", kind, 512, 256, 1024, ("hidden", fc1), w=(33, 0.02), b=None),
+           _q_case("column split bf16", kind, 512, 768, 256, (41, 512, 0), b=42, win=(1792, 0)),
+           _q_case("column split mx8", kind, 512, 1024, 256, (41, 512, 0), b=42, epi="gelu", mx8=True, win=(1792, 768)),
+           _q_case("k split 13 K-tiles", kind, 300, 768, 1664, (300 + 768 + 1664, 300, 0), ksplit=True)]
+    out.append(_q_res(out[-1]))
+    for B, S_t, S_i in pairs:
+        Mi, Mt, S = B * S_i, B * S_t, S_t + S_i
+        for seed, row0, M, c_row0, seg in ((52, 0, Mi, S_t, S_i), (54, Mi, Mt, 0, S_t)):
+            for epi in (("bias", "gate_res") if kind == "fp8" else ("gate_res",)):
+                out.append(_q_case(f"pair B={B} {epi} rows {row0}+", kind, M, 512, 256, (51, Mi + Mt, row0), w=(seed, 0.03), b=seed + 1, epi=epi,
+                                   res=("joint", c_row0, seg, S, B) if epi == "gate_res" else None, gate=(B, seed + 10, seg) if epi == "gate_res" else None))
+    return out
+
+
+def _q_res(c):
+    """the gate + residual launch the GPU tests run beside a bias-only one on the same operands: one gate row (seed 6), residual seed 7"""
+    return dict(c, name=c["name"] + " gate_res", epi="gate_res", res=7, gate=(1, 6, c["M"]), gate_rows=1)
+
+
+# (the GPU tests' shapes, seeds and forms.  Of the production-size fp8 launches the list carries 4352 x 3072 x 3072 and one of each K-split form -- the
+# K = 12288 pitched bias launch has the ragged split's N, K and pitch; the ragged-row tests run three epilogues x four M x two N on one small shape
+# and carry every M once)
+QGEMM_CASES = (
+    [_q_case("bias", "fp8", M, N, K, (M + N + K, M, 0)) for M, N, K in ((256, 256, 128), (512, 512, 256), (384, 256, 384), (4352, 3072, 3072))]
+    + [_q_case("auto split", "fp8", 1280, 3072, 15360, (1280 + 3072 + 15360, 1280, 0), epi="gate_res", res=7, gate=(1, 6, 1280), ksplit=True),
+       _q_case("unsplit", "fp8", 1280, 3072, 3072, (1280 + 3072 + 3072, 1280, 0), epi="gate_res", res=7, gate=(1, 6, 1280)),
+       _q_case("ragged split", "fp8", 1208, 3072, 12288, (821, 1208, 0), epi="gate_res", res=7, gate=(1, 6, 1208), ksplit=True)]
+    + _q_both("fp8")
+    + [_q_case(f"ragged {epi}", "fp8", M, N, 384, (801, 384, 0), w=(802 + N, 0.02), b=803, epi=epi, res=804 if epi == "gate_res" else None,
+               gate=(8, 805, M // 2) if epi == "gate_res" else None)
+       for (M, N), epi in zip(((120, 256), (264, 512), (360, 256), (376, 512), (376, 256)), ("gate_res", "gelu", "bias", "gate_res", "gelu"))]
+    + [_q_case("ragged mx8", "fp8", 384, N, 384, (801, 384, 0), w=(812 + N, 0.02), b=813, epi="gelu", mx8=True) for N in (256, 512)]
+    + [_q_case("bias", "fp4", M, N, K, (M + N + K, M, 0))
+       for M, N, K in ((256, 256, 128), (512, 512, 256), (384, 256, 384), (130, 256, 640), (1, 256, 128), (200, 256, 512), (1, 512, 128), (257, 768, 384))]
+    + [_q_case("k split", "fp4", 300, 768, 3072, (300 + 768 + 3072, 300, 0), ksplit=True),
+       _q_case("k split pitched", "fp4", 200, 256, 1024, (200 + 256 + 1024, 200, 0), ksplit=True)]
+    + [_q_case("block scales", "fp4", 256, 256, K, (256 + 256 + K, 256, 0), w="pattern") for K in (256, 640)]
+    + _q_both("fp4"))
+# (every fp4 shape whose bias-only output the kernel misses on an MI355X runs with gate + residual as well, where the gate holds)
+QGEMM_CASES += [_q_res(c) for c in QGEMM_CASES if c["name"].startswith(("fp4 bias 1x512", "fp4 bias 257x", "fp4 bias 130x", "fp4 k split 300x768x3072", "fp4 k split pitched", "fp4 block scales"))]
+
+
+def q_operands(c):
+    """the operands of a case on its row / column subset, as the GPU test draws them"""
+    from oracle import fp8 as o8
+    from tests import _fp8 as f8
+    kind, M, N, K = c["kind"], c["M"], c["N"], c["K"]
+    rows, cols = row_subset(M, N, K), col_subset(M, N, K)
+    idx = torch.arange(M) if rows is None else rows
+    cidx = torch.arange(N) if cols is None else cols
+    assert cols is None or not c["mx8"]  # (an MX-fp8 output needs whole 32-column blocks)
+    if c["act"][0] == "hidden":
+        a = QGemmRestatement(c["act"][1]).out()
+    else:
+        seed, n_rows, row0 = c["act"]
+        a = f8.fp8_activation(n_rows, K, seed)[row0:row0 + M]
+    r0 = (M - 1) // 128 * 128  # first row of the last 128-row scale block
+    qa, ea = o8.mx8_encode(a[idx])
+    o = dict(idx=idx, cidx=cidx, qa=qa.view(torch.float8_e4m3fn).float(), ea=ea.to(torch.int32) - 127, x=f8.mx8_decode(qa, ea), r0=r0,
+             ea_above=o8.mx8_encode(a[r0 - 128:M - 128])[1].to(torch.int32) - 127 if r0 >= 128 else None)
+    n_w, c0 = c["win"] or (N, 0)
+    if c["w"] == "pattern":  # test_gemm_fp4_block_scales_are_applied_per_block
+        kb, n = torch.arange(K)[None, :] // 32, torch.arange(N)[:, None]
+        w = (randn(N, K, seed=77, scale=0.02) * torch.exp2(((kb * 5 + n * 3) % 17 - 8).float())).to(BF)
+    else:
+        w = randn(n_w, K, seed=c["w"][0], scale=c["w"][1]).to(BF)[c0:c0 + N]
+    o["el"], o["eb"], o["ws"], o["w"] = q_weight(kind, w[cidx])
+    o["b"] = randn(n_w, seed=c["b"], scale=0.5)[c0:c0 + N][cidx] if c["b"] is not None else None
+    o["res"] = o["gate"] = None
+    if isinstance(c["res"], tuple):
+        _, c_row0, seg, S, B = c["res"]
+        o["res"] = randn(B * S + 8, N, seed=60)[c_row0 + (idx // seg) * S + idx % seg][:, cidx]
+    elif c["res"] is not None:
+        o["res"] = randn(c["act"][1], N, seed=c["res"])[idx][:, cidx]
+    if c["gate"] is not None:
+        gr, gseed, seg = c["gate"]
+        o["gate"] = randn(gr, N, seed=gseed)[idx // seg][:, cidx]
+    return o
+
+
+class QGemmRestatement(GemmRestatement):
+    """the kernels' own order on a case's row / column subset: K walked in 128-wide K-tiles, the block products (element values x block scales) summed
+    in fp32 without the per-channel wscale, then x wscale[n] and + bias in fp32, then epilogue_f32; an MX-fp8 output through oracle/fp8.py.  ``acc``
+    (what the inherited tail mutants work on) is raw x wscale + bias"""
+
+    def __init__(self, c, order="tiles"):
+        o = q_operands(c)
+        self.c, self.dt, self.epi, self.kind, self.o = c, BF, c["epi"], c["kind"], o
+        self.M, self.N, self.K = c["M"], c["N"], c["K"]
+        self.idx, self.Ns = o["idx"], o["cidx"].numel()
+        self.x, self.w, self.ws, self.res, self.gate = o["x"], o["w"], o["ws"], o["res"], o["gate"]
+        self.b = o["b"] if o["b"] is not None else torch.zeros(self.Ns)
+        self.wq = q_scaled(o["el"], o["eb"])
+        self.raw = q_raw(self.x, self.wq, order)
+        self.acc = self.finish(self.raw)
+        self.pre64, self.unit = gemm_ref64(self.x, self.w, o["b"])
+        self.ref, self.bound = epilogue_bound(self.pre64, self.unit, BF, self.epi, self.res, self.gate, C_GEMM_Q)
+        if c["mx8"]:
+            self.bound = mx8_bound(self.ref, self.bound)
+
+    def finish(self, raw):
+        return raw * self.ws + self.b
+
+    def out(self, acc=None):
+        from oracle import fp8 as o8
+        y = super().out(acc)
+        return o8.mx8_fake_quant(y) if self.c["mx8"] else y
+
+    def unit_error(self, order=None):
+        acc = self.acc if order is None else self.finish(q_raw(self.x, self.wq, order))
+        return float(((acc.double() - self.pre64).abs() / self.unit).max())
+
+    def _with(self, rows, cols, delta):
+        """the output with ``delta`` added to the raw sums of (rows, cols)"""
+        raw = self.raw.clone()
+        raw[rows, cols] += delta
+        return self.out(self.finish(raw))
+
+    def tile(self, t):
+        return slice(t * KT, (t + 1) * KT)
+
+    # -- mutants of the block-scaled loops --
+    def m_w_scale(self, n, kb):
+        """gemm256f4.hip F4_MM's opsel / the SW lane order [N / 64][K / 128][lane (r, g)][nf]: the E8M0 scale of (channel n, K block kb) a binade up;
+        ``n`` a channel, or the same lane and byte of every wave's 64 channels"""
+        k = slice(32 * kb, 32 * kb + 32)
+        return self._with(slice(None), n, self.x[:, k] @ self.wq[n, k].t())
+
+    def m_a_scale_above(self):
+        """dk_mx_scale_index / sa_nblk (a_blk of gemm256f8.hip and gemm256f4.hip): a row of the last 128-row scale block (the first whose scales differ
+        from the row 128 above) multiplied with the scales of that row, the neighbouring scale block's"""
+        o = self.o
+        r = int((self.idx == o["r0"]).nonzero()[0])
+        j = int((o["ea_above"] != o["ea"][r:]).any(dim=1).nonzero()[0])
+        x_bad = torch.ldexp(o["qa"][r + j].view(-1, 32), o["ea_above"][j][:, None]).reshape(-1)
+        return self._with(r + j, slice(None), (x_bad - self.x[r + j]) @ self.wq.t())
+
+    def m_nibbles_swapped(self):
+        """pack_mxfp4 / the fp4 operand fragment ("even K in the low nibble"): even and odd elements of one 32-K block (channel 5, the last block) swapped"""
+        n, k = min(5, self.Ns - 1), slice(self.K - 32, self.K)
+        w_bad = self.wq[n, k].view(16, 2).flip(1).reshape(32)
+        return self._with(slice(None), n, self.x[:, k] @ (w_bad - self.wq[n, k]))
+
+    def _w_from(self, ch_from, t_from, ch, t):
+        """delta of the raw sums of channels ``ch`` when their element values of K-tile t are those of (ch_from, t_from); the block scales stay their own"""
+        w_bad = q_scaled(self.o["el"][ch_from, self.tile(t_from)], self.o["eb"][ch, 4 * t:4 * t + 4])
+        return self.x[:, self.tile(t)] @ (w_bad - self.wq[ch, self.tile(t)]).t()
+
+    def m_next_fragment_row(self):
+        """issue_w's f * 16 * ldw + t * 1024 (gemm256f4.hip; gemm256f8.hip: row n * ldw), which a pitch moves: channels [0, 16) take the element values of
+        the next fragment row, [16, 32), in the last K-tile"""
+        t = self.K // KT - 1
+        return self._with(slice(None), slice(0, 16), self._w_from(slice(16, 32), t, slice(0, 16), t))
+
+    def m_ring_slot_stale(self):
+        """the three-slot weight ring and its hand-counted waits (wo_cur / wo_nxt / wo_nn, F4_TILE_WAIT): K-tile 3, the first wrap, still holds K-tile 0's
+        weights for one wave's 64 channels"""
+        return self._with(slice(None), slice(0, 64), self._w_from(slice(0, 64), 0, slice(0, 64), 3))
+
+    def m_k_tile_dropped(self):
+        """F4_DRIVE / the fp8 kernel's last iteration: the last K-tile missing for one row of the last row tile x 16 columns"""
+        r, t = self.last_tile_row(), self.tile(self.K // KT - 1)
+        return self._with(r, slice(0, 16), -(self.x[r, t] @ self.wq[:16, t].t()))
+
+    def m_slab_omitted(self):
+        """dk_ksplit.h finisher: one producer slab (the last quarter of the K-tiles) never added for the first 256 x 256 tile"""
+        k0 = self.K - max(KT, self.K // 4 // KT * KT)
+        nr, nc = min(TILE, self.idx.numel()), min(TILE, self.Ns)
+        return self._with(slice(0, nr), slice(0, nc), -(self.x[:nr, k0:] @ self.wq[:nc, k0:].t()))
+
+    # -- mutants of the MX-fp8 writer of the tail (dk_gemm_tail.h / dk_mx8_quantize8) --
+    def _encode_last_row(self, exponent):
+        """the decoded last row when block j is encoded with exponent(amax [blocks], j) -> (encoding exponent, decoding exponent)"""
+        from oracle import fp8 as o8
+        y = super().out()
+        v = y[-1].view(-1, 32)
+        enc, dec = exponent(o8.mx8_scale_exponent, v)
+        q = torch.ldexp(v, (127 - enc)[:, None]).clamp(-o8.E4M3_MAX, o8.E4M3_MAX).to(torch.float8_e4m3fn).float()
+        out = self.out()
+        out[-1] = torch.ldexp(q, (dec - 127)[:, None]).reshape(-1)
+        return out
+
+    def m_mx8_scale_of_next_block(self):
+        """the scale store at p.sc_kb0 + (ocol >> 5) under a wrong c_col0 window offset: every block of the last row is read with the scale of the next
+        32-column block (the last with the one before)"""
+        def exponent(rule, v):
+            e = rule(v.abs().amax(-1))
+            return e, torch.cat([e[1:], e[-2:-1]])
+        return self._encode_last_row(exponent)
+
+    def m_mx8_amax_misses_the_largest(self):
+        """dk_mx8_quantize8's amax fold with a lane missing: every block of the last row takes its scale from its second largest magnitude"""
+        def exponent(rule, v):
+            e = rule(v.abs().topk(2, dim=-1).values[:, 1])
+            return e, e
+        return self._encode_last_row(exponent)
+
+    def m_gelu_before_bias(self):
+        from oracle import fp8 as o8
+        out = super().m_gelu_before_bias()
+        if self.c["mx8"]:
+            out[-1] = o8.mx8_fake_quant(out[-1:])[0]
+        return out
+
+    def mutants(self):
+        c, nk = self.c, self.K // KT
+        m = {"last K-tile dropped": self.m_k_tile_dropped, "one element zero": self.m_one_zero, "fragment swapped": self.m_fragment_swapped,
+             "weights of the next fragment row": self.m_next_fragment_row}
+        # (a bias that moves no output of its 3 x 4 corner by eight bf16 spacings -- gate + residual has three roundings -- is not claimed: on the +-2^8 pattern at
+        #  K = 640 with gate + residual the corner's gated products are ~300 and the gated bias ~0.5 -- 1.5 of the bound, not claimed)
+        corner = (slice(-3, None), slice(self.Ns - (self.N % 4 or 4), None))
+        g = self.gate[corner].double() if self.gate is not None else 1.0
+        moved, size = (self.b[corner[1]] * g).abs(), torch.maximum(self.ref[corner].abs(), (self.pre64[corner] * g).abs())  # (the gated product is rounded too)
+        if c["b"] is not None and bool((moved > 8.0 * spacing(size, BF)).any()):
+            m["bias missing"] = self.m_bias_missing
+        if self.epi == "gate_res" and c["gate_rows"] == 2:
+            m["gate row of segment 1"] = self.m_gate_row
+        if self.epi == "gelu":
+            m["gelu before bias"] = self.m_gelu_before_bias
+        if c["ksplit"]:
+            m["slab omitted"] = self.m_slab_omitted
+        if self.kind == "fp4":
+            # (a block 2^-12 and more below the row's largest moves the output by less than bf16's rounding, 2^-9, on any gate: on the +-2^8 pattern
+            #  at K = 256 the last block of the last channel carries 2^-7 where the row's largest carries 2^8 and a binade there is 0.50 of the
+            #  bound; at K = 640 that block carries 2^2)
+            if int(self.o["eb"][-1].max() - self.o["eb"][-1, -1]) < 12:
+                m["w scale x 2 (last channel, last block)"] = lambda: self.m_w_scale(self.Ns - 1, self.K // 32 - 1)
+            for j in (1, 2, 3):  # fragment nf = j (opsel j), lane (r, g) = (j, j) of every wave's 64 channels
+                m[f"w scale x 2 (channels 64 G + {16 * j + j}, block {j})"] = lambda j=j: self.m_w_scale(torch.arange(16 * j + j, self.Ns, 64), j)
+            m["nibbles swapped"] = self.m_nibbles_swapped
+        if self.o["ea_above"] is not None and bool((self.o["ea_above"] != self.o["ea"][int((self.idx == self.o["r0"]).nonzero()[0]):]).any()):
+            m["activation scales of the block above"] = self.m_a_scale_above
+        if nk >= 4:
+            m["ring slot stale"] = self.m_ring_slot_stale
+        if c["mx8"]:
+            m["mx8: scale of the next block"] = self.m_mx8_scale_of_next_block
+            m["mx8: amax misses the largest"] = self.m_mx8_amax_misses_the_largest
         return m
 
 

@@ -404,6 +404,28 @@ def _():
                 outs={"out": ((ROWS8, N), BF)}, ws=("ws", _gemm_ws_bytes()), main_in="a8", main_out="out")
 
 
+@spec("gemm_fp4_bias")
+def _():
+    from diffusionkit_amd import ops
+    from tests import _mxfp4 as f4
+    N, M = 256, 376
+    dev = torch.device("cuda", 0)
+    a8, sa = ops.quantize_mx8(act8().to(dev, BF))
+    w4, sw, wsc, w_dq = f4.weight_operands(fp.rounder(BF)(N, K8, seed=802, scale=0.02).to(BF))
+    bias = fp.rounder(BF)(N, seed=803, scale=0.5)
+    o = dict(a8=a8.cpu(), sa=sa.cpu(), w4=w4, sw=sw, wsc=wsc.float(), bias=bias)
+
+    def launch(v):
+        ops.gemm_fp4(v["a8"], v["sa"], v["w4"], v["sw"], v["wsc"], bias=v["bias"], M=M, k=K8, out=v["out"], workspace=v.get("ws"))
+        return v["out"][:M]
+
+    def ref(q):
+        a = f8.mx8_decode(o["a8"], f8.array_to_scales(o["sa"], ROWS8, K8)).double()[:M]
+        return a @ w_dq.double().t() + q["bias"]
+    return Spec(o, launch, ref, (TOL_SINGLE_OP, None, "test_gpu_fp4.py::test_gemm_fp4_bias"), dtypes={"wsc": torch.float32},
+                outs={"out": ((ROWS8, N), BF)}, ws=("ws", _gemm_ws_bytes()), main_in="a8", main_out="out")
+
+
 def _attention_spec(form):
     name, dt, knobs, (B, H, S, D), QB = form
 

@@ -2,8 +2,12 @@
 
 Gates: a single GEMM against the float64 product of the dequantised operands differs from exact only by the final bf16 rounding (~1e-3):
 rel-L2 < TOL_SINGLE_OP, the project's gate for every single GEMM.  The tail's other forms take the gates of the fp8 tests of the same form
-(tests/test_gpu_fp8.py).  Engine: e_h <= 2 e_e + 2e-3 against the oracle on the same fake-quantised values; what fp4 costs against the
-un-quantised oracle is printed, not gated (random weights say nothing about a checkpoint)."""
+(tests/test_gpu_fp8.py).  Beside every rel-L2 of a GEMM output stands the per-element gate of tests/_gates.py (G.qgemm_gate, G.mx8_gate), proved
+on mutants in tests/test_gate_power_cpu.py::test_qgemm_gate.  Every bias-only shape is also launched with a gate row and a residual in the tail
+on the same operands, where the gate holds on this kernel; on the bias-only, GELU and MX-fp8 outputs the kernel leaves the bound at a few
+elements (tests/test_gpu_fp8.py says where and by how much) and those forms print their figure without asserting it (``missed``).
+Engine: e_h <= 2 e_e + 2e-3 against the oracle on the same fake-quantised values; what fp4 costs against the un-quantised oracle is printed, not
+gated (random weights say nothing about a checkpoint)."""
 from dataclasses import replace
 
 import pytest
@@ -14,32 +18,26 @@ from diffusionkit_amd._lib import DK_EPI_BIAS, DK_EPI_BIAS_GELU, DK_EPI_GATE_RES
 from oracle import fp8 as o8
 from oracle.mmdit import OracleMMDiT, Prec, gelu_erf
 from tests import _fp8 as f8
+from tests import _gates as G
 from tests import _mxfp4 as f4
 from tests._util import BF, TOL_SINGLE_OP, bf16r, psnr, randn, rel_l2
 
 pytestmark = pytest.mark.gpu
 
 
-def _run_bias(dev, M, N, K, w_pitch=None, w=None, **kw):
-    qa, ea, w4, sw, ws, w_dq, a_dq = f4.fp4_problem(M, N, K, seed=M + N + K, w_pitch=w_pitch, w=w)
-    bias = randn(N, seed=5, scale=0.5)
-    rows = (M + 127) // 128 * 128
-    a8 = torch.zeros(rows, K, dtype=torch.uint8)
-    a8[:M] = qa
-    ref = (a_dq.double() @ w_dq.double().t() + bias.double()).float()
-    args = (a8.to(dev), f8.scales_to_array(ea, rows).to(dev), w4.to(dev), sw.to(dev), ws.to(dev))
-    return ref, lambda **extra: ops.gemm_fp4(*args, bias=bias.to(dev, BF), M=M, k=K, **kw, **extra).float().cpu()
-
-
 # one tile and one K-tile (prologue only); two K-tiles (the ON2 = false iterations); three (first steady-state iteration, partial second row tile);
-# five (the three-slot weight ring wraps; last 128-row scale block partial); a single row; a pitched weight (dk_weight_pitch_fp4(K) != K / 2)
+# five (the three-slot weight ring wraps; last 128-row scale block partial); a single row; a pitched weight (dk_weight_pitch_fp4(K) != K / 2);
+# a single row over two column tiles and 257 rows over three: all four `wn` waves, both weight pieces `wave` and `wave + 8`, column tiles 1 and 2
 @pytest.mark.parametrize("M,N,K,w_pitch", [(256, 256, 128, None), (512, 512, 256, None), (384, 256, 384, None), (130, 256, 640, None), (1, 256, 128, None),
-                                           (200, 256, 512, 512 // 2 + 64)])
+                                           (200, 256, 512, 512 // 2 + 64), (1, 512, 128, None), (257, 768, 384, None)])
 def test_gemm_fp4_bias(dev, M, N, K, w_pitch):
-    ref, run = _run_bias(dev, M, N, K, w_pitch)
-    r = rel_l2(ref, run())
+    p = f8.GemmProblem("fp4", dev, M, N, K, w_pitch)
+    y = p.run()
+    r = rel_l2(p.ref, y)
     print(f"[fp4 gemm {M}x{N}x{K}] rel_l2 {r:.3e}")
     assert r < TOL_SINGLE_OP, r
+    p.gate_bias("", y, missed=M > 1)
+    p.gate_res("", p.run_res())
 
 
 def test_gemm_fp4_k_split(dev):
@@ -47,32 +45,48 @@ def test_gemm_fp4_k_split(dev):
     rule's break-even for an all-remainder Linear is 32 saved K-tile steps and this launch saves 18, so the test lowers the `gemm_split_min` knob for
     its launch: the protocol under test is the kernel's, not the break-even.)  Split and unsplit are both inside the gate and differ only by the fp32
     summation order."""
-    ref, run = _run_bias(dev, 300, 768, 3072)
-    wsp = ops.gemm_workspace(dev)
-    y0 = run()
-    wsp[:-4096].zero_()
-    ops.tune("gemm_split_min", 8)
-    try:
-        y = run(workspace=wsp)
-    finally:
-        ops.tune("gemm_split_min", -1)
-    assert rel_l2(ref, y) < TOL_SINGLE_OP and rel_l2(ref, y0) < TOL_SINGLE_OP, (rel_l2(ref, y), rel_l2(ref, y0))
-    # (fp4 x fp8 products have 6 significant bits: most partial sums are exact in fp32 and the two results may agree in every bit, so the cut is
-    #  witnessed by what the producers left in the slabs, not by a difference)
-    assert bool(wsp[:-4096].any()), "the launch was expected to be cut along K (the producers write their accumulators into the workspace)"
-    assert float((y0 != y).float().mean()) < 0.05
-    assert int(wsp[-4096:].sum()) == 0  # the flag region (and the error word) is left zero
+    p = f8.GemmProblem("fp4", dev, 300, 768, 3072)
+    y, y0 = p.k_split(p.run, 8, False)
+    assert rel_l2(p.ref, y) < TOL_SINGLE_OP and rel_l2(p.ref, y0) < TOL_SINGLE_OP, (rel_l2(p.ref, y), rel_l2(p.ref, y0))
+    p.gate_bias("cut and whole", [y, y0], missed=False)
+    p.gate_res("cut and whole", list(p.k_split(p.run_res, 8, False)))
+
+
+@pytest.mark.parametrize("M,N,K,w_pitch", [(300, 768, 1664, None), (200, 256, 1024, 1024 // 2 + 64)])
+def test_gemm_fp4_k_split_short_reductions(dev, M, N, K, w_pitch):
+    """13 K-tiles (finisher 4, producers 3 + 3 + 3), and 8 K-tiles (2 + 2 + 2 + 2) with a pitched weight: the K-tile offsets of the pieces (k0 * 1024
+    into a fragment row, k0 * sa_step and k0 * 256 into the scale arrays) at ranges the long shapes do not produce.  The shared rule would leave
+    launches this short whole (9 and 6 saved K-tile steps), so `gemm_split` is forced beside the lowered `gemm_split_min`.  The fp8 kernel's:
+    tests/test_gpu_fp8.py::test_gemm_fp8_k_split_short_reduction."""
+    p = f8.GemmProblem("fp4", dev, M, N, K, w_pitch)
+    y, y0 = p.k_split(p.run, 0, True)
+    print(f"[fp4 K split {M}x{N}x{K}] rel_l2 cut {rel_l2(p.ref, y):.3e}, whole {rel_l2(p.ref, y0):.3e}; elements that differ {int((y0 != y).sum())}")
+    assert rel_l2(p.ref, y) < TOL_SINGLE_OP and rel_l2(p.ref, y0) < TOL_SINGLE_OP
+    p.gate_bias("cut and whole", [y, y0], missed=w_pitch is not None)
+    p.gate_res("cut and whole", list(p.k_split(p.run_res, 0, True)))
+
+
+def _block_scale_pattern(dev, K):
+    M, N = 256, 256
+    w = randn(N, K, seed=77, scale=0.02)
+    kb, n = torch.arange(K)[None, :] // 32, torch.arange(N)[:, None]
+    w = (w * torch.exp2(((kb * 5 + n * 3) % 17 - 8).float())).to(BF)
+    p = f8.GemmProblem("fp4", dev, M, N, K, w=w)
+    y = p.run()
+    assert rel_l2(p.ref, y) < TOL_SINGLE_OP
+    p.gate_bias("block pattern", y, missed=True)
+    p.gate_res("block pattern", p.run_res())
 
 
 def test_gemm_fp4_block_scales_are_applied_per_block(dev):
     """K blocks that differ by 2^+-8 along one row and across the rows of one 16-channel fragment: a wrong opsel or scale layout fails here and passes
     on a unit-scale weight"""
-    M, N, K = 256, 256, 256
-    w = randn(N, K, seed=77, scale=0.02)
-    kb, n = torch.arange(K)[None, :] // 32, torch.arange(N)[:, None]
-    w = (w * torch.exp2(((kb * 5 + n * 3) % 17 - 8).float())).to(BF)
-    ref, run = _run_bias(dev, M, N, K, w=w)
-    assert rel_l2(ref, run()) < TOL_SINGLE_OP
+    _block_scale_pattern(dev, 256)
+
+
+def test_gemm_fp4_block_scales_when_the_ring_wraps(dev):
+    """the same pattern over five K-tiles: the three-slot weight ring wraps and the scale loads of K-tiles 3 and 4 follow it"""
+    _block_scale_pattern(dev, 640)
 
 
 def _desc(dev, qa, ea, w4, sw, ws, bias, M, N, K, a_row0=0):
@@ -82,7 +96,11 @@ def _desc(dev, qa, ea, w4, sw, ws, bias, M, N, K, a_row0=0):
     return d, keep
 
 
-@pytest.mark.parametrize("form", ["gate_res", "gelu_mx8_chain", "column_split", "grouped_pair"])
+# (B, S_t, S_i) of the grouped pair: the fp8 test's; text rows from activation row 384 (a multiple of 128, not of 256); a text stream of one row
+PAIRS = {"grouped_pair": (2, 128, 384), "grouped_pair_a_row0_384": (2, 128, 192), "grouped_pair_text_m1": (1, 1, 384)}
+
+
+@pytest.mark.parametrize("form", ["gate_res", "gelu_mx8_chain", "column_split"] + list(PAIRS))
 def test_gemm_fp4_tail_forms(dev, form):
     """the shared tail's other forms through this kernel, each against the reference and at the gate of the fp8 test of the same form"""
     if form == "gate_res":
@@ -93,6 +111,7 @@ def test_gemm_fp4_tail_forms(dev, form):
                            epilogue=DK_EPI_GATE_RES, gate=gate.to(dev, BF), res=res.to(dev, BF), gate_seg_len=S)
         ref = res + bf16r(gate.repeat_interleave(S, 0) * bf16r(a_dq @ w_dq.t() + bias))
         assert rel_l2(ref, out.float().cpu()) < TOL_SINGLE_OP
+        G.assert_gate("fp4 gate_res", G.qgemm_gate(out, a_dq, w_dq, bias, "gate_res", res, gate.repeat_interleave(S, 0)))
     elif form == "gelu_mx8_chain":  # fc1 -> GELU -> MX-fp8 (written by the tail) -> fc2
         M, h, r = 512, 256, 4
         qa, ea, w4, sw, ws, w1_dq, a_dq = f4.fp4_problem(M, r * h, h, seed=31)
@@ -102,9 +121,11 @@ def test_gemm_fp4_tail_forms(dev, form):
         want_q, want_e = o8.mx8_encode(gelu_erf(bf16r(a_dq @ w1_dq.t() + b1), Prec(BF)))
         got = f8.mx8_decode(hq.cpu(), f8.array_to_scales(hs.cpu(), M, r * h))
         assert rel_l2(f8.mx8_decode(want_q, want_e), got) < 6e-3
+        G.assert_gate("fp4 gelu -> MX-fp8", G.mx8_gate(got, a_dq, w1_dq, b1))
         w24, sw2, ws2, w2_dq = f4.weight_operands(randn(h, r * h, seed=33, scale=0.02).to(BF))
         out = ops.gemm_fp4(hq, hs, w24.to(dev), sw2.to(dev), ws2.to(dev))
         assert rel_l2(got @ w2_dq.t(), out.float().cpu()) < TOL_SINGLE_OP  # on the hidden values the kernel itself produced
+        G.assert_gate("fp4 fc2 on the MX-fp8 hidden values", G.qgemm_gate(out, got, w2_dq, None), missed=True)
     elif form == "column_split":  # [q | k | v] + bias -> bf16, gelu(fc1 + bias) -> MX-fp8 into a column window of a wider buffer
         M, K, n1, n2, col0, ld8 = 512, 256, 768, 1024, 128, 128 + 1024 + 64
         qa, ea, w4, sw, ws, w_dq, a_dq = f4.fp4_problem(M, n1 + n2, K, seed=41)
@@ -117,12 +138,14 @@ def test_gemm_fp4_tail_forms(dev, form):
         ops.gemm_fp4_fused_call(d, dict(n_split=n1, C2=buf8.data_ptr() + col0, ldc2=ld8, epi2=DK_EPI_BIAS_GELU, c2_mx8=1), keep["sw"])
         acc = a_dq @ w_dq.t() + bias
         assert rel_l2(acc[:, :n1], out[:M].float().cpu()) < TOL_SINGLE_OP and bool((out[M:] == 7.0).all())
+        G.assert_gate("fp4 column split, bf16 half", G.qgemm_gate(out[:M], a_dq, w_dq[:n1], bias[:n1]), missed=True)
         want_q, want_e = o8.mx8_encode(gelu_erf(bf16r(acc[:, n1:]), Prec(BF)))
         got = f8.mx8_decode(buf8[:, col0:col0 + n2].cpu(), f8.array_to_scales(sc.cpu(), M, n2, rows=M, col0=col0))
         assert rel_l2(f8.mx8_decode(want_q, want_e), got) < 6e-3
+        G.assert_gate("fp4 column split, MX-fp8 half", G.mx8_gate(got, a_dq, w_dq[n1:], bias[n1:]))
         assert bool((buf8[:, :col0] == 0xAB).all()) and bool((buf8[:, col0 + n2:] == 0xAB).all())
     else:  # image rows and text rows of one activation buffer in one launch, gate + residual in place in a joint [B, S_t + S_i, N] buffer
-        B, S_t, S_i, N, K = 2, 128, 384, 512, 256
+        (B, S_t, S_i), N, K = PAIRS[form], 512, 256
         Mi, Mt, S = B * S_i, B * S_t, S_t + S_i
         qa, ea, _, _, _, _, a_dq = f4.fp4_problem(Mi + Mt, N, K, seed=51)
         X = randn(B * S + 8, N, seed=60)
@@ -146,6 +169,8 @@ def test_gemm_fp4_tail_forms(dev, form):
             rows = c_row0 + (m // seg) * S + m % seg
             ref = X[rows] + bf16r(gate.repeat_interleave(seg, 0) * bf16r(a_dq[row0:row0 + M] @ w_dq.t() + bias))
             assert rel_l2(ref, got[rows]) < TOL_SINGLE_OP
+            G.assert_gate(f"fp4 {form}, activation row {row0}", G.qgemm_gate(got[rows], a_dq[row0:row0 + M], w_dq, bias, "gate_res", X[rows],
+                                                                           gate.repeat_interleave(seg, 0)))
         assert torch.equal(got[B * S:], bf16r(X[B * S:]))
 
 

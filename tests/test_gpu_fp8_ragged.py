@@ -7,7 +7,8 @@ The fp8 GEMM reads the scales of a wave's 128 rows as one aligned block of the a
   * the engine at image token counts of 120, 360 (two images: the second one's segment starts inside a block) and 195 against the oracle, at the
     gates of test_gpu_fp8.test_mmdit_fp8_tiny, through the lean attention kernel + quantiser pass and through attention4.hip's own MX-fp8 writer;
   * the MX-fp8 copy of the attention output at B * S = 2 * 488 rows.
-Tolerances are those of tests/test_gpu_fp8.py.
+Tolerances are those of tests/test_gpu_fp8.py, the per-element gates of tests/_gates.py beside them; the bias-only, GELU and MX-fp8 outputs print
+their figure without asserting it (``missed``: tests/test_gpu_fp8.py says why).
 """
 import math
 from dataclasses import replace
@@ -20,6 +21,7 @@ from diffusionkit_amd._lib import DK_EPI_BIAS, DK_EPI_BIAS_GELU, DK_EPI_GATE_RES
 from diffusionkit_amd.config import tiny_flux, tiny_sd3
 from diffusionkit_amd.weights import dequantize_weight_e4m3, quantize_weight_e4m3
 from tests import _fp8 as f8
+from tests import _gates as G
 from tests._util import BF, TOL_SINGLE_OP, bf16r, psnr, randn, rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -34,9 +36,14 @@ SENTINEL = 7.0
 @pytest.fixture(scope="module")
 def act(dev):
     """x [384, K] quantised once: (e4m3 bytes, scale side array) on the device"""
-    x = bf16r(randn(ROWS, K, seed=801, scale=1.0))
-    x[:, :K // 2] *= 4.0
-    return ops.quantize_mx8(x.to(dev, BF))
+    return ops.quantize_mx8(f8.fp8_activation(ROWS, K, 801).to(dev, BF))
+
+
+@pytest.fixture(scope="module")
+def act_dq():
+    """the values ``act`` holds, through the oracle's encoder (test_quantize_mx8_bit_exact: the device's bytes and scales are the oracle's)"""
+    from oracle import fp8 as o8
+    return f8.mx8_decode(*o8.mx8_encode(f8.fp8_activation(ROWS, K, 801)))
 
 
 def _weight(N, Kw, seed, dev):
@@ -46,12 +53,13 @@ def _weight(N, Kw, seed, dev):
 
 @pytest.mark.parametrize("N", [256, 512])
 @pytest.mark.parametrize("epi", ["bias", "gelu", "gate_res"])
-def test_gemm_fp8_ragged_rows_are_independent_bf16(dev, act, N, epi):
+def test_gemm_fp8_ragged_rows_are_independent_bf16(dev, act, act_dq, N, epi):
     a8, sa = act
-    w8, ws, _ = _weight(N, K, 802 + N, dev)
-    bias = randn(N, seed=803, scale=0.5).to(dev, BF)
-    res = randn(ROWS, N, seed=804).to(dev, BF)
-    gate = randn(8, N, seed=805).to(dev, BF)  # (two segments of M / 2 rows inside [0, M); the whole-buffer run goes on through the next rows of the gate)
+    w8, ws, w_dq = _weight(N, K, 802 + N, dev)
+    bias_c, res_c, gate_c = randn(N, seed=803, scale=0.5), randn(ROWS, N, seed=804), randn(8, N, seed=805)
+    bias = bias_c.to(dev, BF)
+    res = res_c.to(dev, BF)
+    gate = gate_c.to(dev, BF)  # (two segments of M / 2 rows inside [0, M); the whole-buffer run goes on through the next rows of the gate)
     for M in RAGGED_M:
         kw = dict(bias=bias, k=K)
         if epi == "gelu":
@@ -69,19 +77,25 @@ def test_gemm_fp8_ragged_rows_are_independent_bf16(dev, act, N, epi):
         assert n_diff == 0
         assert bool((out[M:] == SENTINEL).all()), "rows >= M were written"
         assert bool(torch.isfinite(whole.float()).all())
+        g = G.qgemm_gate(out[:M], act_dq[:M], w_dq, bias_c, epi, res_c[:M] if epi == "gate_res" else None,
+                         gate_c.repeat_interleave(M // 2, 0)[:M] if epi == "gate_res" else None)
+        G.assert_gate(f"fp8 ragged bf16 {epi} N={N} M={M}", g, missed=epi == "bias" or (epi == "gelu" and (N, M) not in ((256, 120), (256, 264))))
 
 
 @pytest.mark.parametrize("N", [256, 512])
-def test_gemm_fp8_ragged_mx8_output(dev, act, N):
+def test_gemm_fp8_ragged_mx8_output(dev, act, act_dq, N):
     """fc1 + GELU -> MX-fp8 on M rows: bytes and scales of rows [0, M) are those of the whole-buffer launch, the data rows behind them keep their
     sentinel, and the result is the next GEMM's operand (gated as test_gemm_fp8_gelu_mx8_output_feeds_next_gemm)"""
     a8, sa = act
-    w8, ws, _ = _weight(N, K, 812 + N, dev)
-    bias = randn(N, seed=813, scale=0.5).to(dev, BF)
+    w8, ws, w_dq = _weight(N, K, 812 + N, dev)
+    bias_c = randn(N, seed=813, scale=0.5)
+    bias = bias_c.to(dev, BF)
     w2_8, ws2, w2_dq = _weight(256, N, 814 + N, dev)
     kw = dict(bias=bias, epilogue=DK_EPI_BIAS_GELU, k=K, out_mx8=True)
     whole_q, whole_s = ops.gemm_fp8(a8, sa, w8, ws, M=ROWS, **kw)
     whole_e = f8.array_to_scales(whole_s, ROWS, N)
+    # (rows [0, M) of every ragged launch below are the whole launch's bytes and scales: one gate serves them all)
+    G.assert_gate(f"fp8 ragged mx8 N={N}, gelu -> MX-fp8", G.mx8_gate(f8.mx8_decode(whole_q, whole_e), act_dq, w_dq, bias_c), missed=True)
     for M in RAGGED_M:
         buf = torch.full((ROWS, N), 0xAB, dtype=torch.uint8, device=dev)
         sc = torch.zeros(ops.mx_scale_bytes(ROWS, N), dtype=torch.uint8, device=dev)
@@ -97,6 +111,7 @@ def test_gemm_fp8_ragged_mx8_output(dev, act, N):
         r = rel_l2(hid @ w2_dq.t(), out.float().cpu())
         print(f"[fp8 ragged mx8 N={N} M={M}] next GEMM on the written rows: rel_l2 {r:.3e} (< {TOL_SINGLE_OP})")
         assert out.shape == (M, 256) and r < TOL_SINGLE_OP
+        G.assert_gate(f"fp8 ragged mx8 N={N} M={M}, next GEMM", G.qgemm_gate(out, hid, w2_dq, None), missed=True)
 
 
 def test_gemm_fp8_ragged_launch_is_split_along_k(dev):
@@ -124,6 +139,7 @@ def test_gemm_fp8_ragged_launch_is_split_along_k(dev):
     r, r0 = rel_l2(ref, y.float()), rel_l2(ref, y0.float())
     print(f"[fp8 ragged K split] rel_l2 with the workspace {r:.3e}, without {r0:.3e} (< {TOL_SINGLE_OP})")
     assert r < TOL_SINGLE_OP and r0 < TOL_SINGLE_OP
+    G.assert_gate("fp8 ragged K split, with and without the workspace", G.qgemm_gate([y, y0], a_dq, w_dq, bias, "gate_res", res, gate))
     assert not torch.equal(y0, y), "the launch was expected to be cut along K (other summation order)"
     assert float((y0.float() != y.float()).float().mean()) < 0.05
     assert int(wsp[-4096:].sum()) == 0  # the flag region (and the error word) is left zero

@@ -249,6 +249,91 @@ def test_gemm_fp8_rows_behind_m_and_row_independence(dev, M):
         g_.check(f"gemm_fp8 M={M}: margins of {name}")
 
 
+# ---- MX-fp4 weights -------------------------------------------------------------------------------------------------------------------
+def _fp4_weight(dev, N, pitch=None):
+    """test_gemm_fp8_rows_behind_m_and_row_independence's weight through the MX-fp4 quantiser: (w4, sw, wscale, bias) on the device"""
+    from tests import _mxfp4 as f4
+    w4, sw, wsc, _ = f4.weight_operands(fp.rounder(BF)(N, K8, seed=802, scale=0.02).to(BF), pitch)
+    return w4.to(dev), sw.to(dev), wsc.to(dev), fp.rounder(BF)(N, seed=803, scale=0.5).to(dev, BF)
+
+
+@pytest.mark.parametrize("M", [120, 376])
+def test_gemm_fp4_rows_behind_m_and_row_independence(dev, M):
+    """gemm256f4.hip as test_gemm_fp8_rows_behind_m_and_row_independence: rows >= M of the activation bytes (0x7F) and of their scales (0xFF) poisoned:
+    rows [0, M) bit-identical, rows >= M of the output keep the sentinel; one NaN byte in row M - 1: exactly that row"""
+    from diffusionkit_amd import ops
+    N = 256
+    a8, sa = ops.quantize_mx8(_act8().to(dev, BF))
+    w4, sw, wsc, bias = _fp4_weight(dev, N)
+    (a8g, ag), (sag, sg) = fp.guarded(a8, PAD, 0x7F), fp.guarded(sa, 1, 0xFF)
+    out, og = fp.guarded(torch.empty(ROWS8, N, dtype=BF, device=dev), PAD, SENTINEL)
+
+    def run():
+        out.fill_(SENTINEL)
+        ops.gemm_fp4(a8g, sag, w4, sw, wsc, bias=bias, M=M, k=K8, out=out)
+        assert bool((out[M:] == SENTINEL).all()), "rows >= M were written"
+        return out[:M].clone()
+    clean = run()
+    none = torch.zeros(M, N, dtype=torch.bool)
+    a8g[M:] = 0x7F
+    r = torch.arange(M, ROWS8)[:, None].expand(ROWS8 - M, K8 // 32)
+    kb = torch.arange(K8 // 32)[None, :].expand(ROWS8 - M, K8 // 32)
+    sag[f8.scale_index(r, kb, f8.n_blk128(ROWS8)).reshape(-1).to(dev)] = 0xFF
+    fp.assert_footprint(clean, run(), none, f"gemm_fp4 M={M}: rows >= M poisoned")
+    m = M - 1
+    a8g[m, K8 - 1] = 0x7F
+    one = none.clone()
+    one[m] = True
+    fp.assert_footprint(clean, run(), one, f"gemm_fp4 M={M}: one byte of row {m}")
+    for name, g_ in (("a8", ag), ("scales", sg), ("out", og)):
+        g_.check(f"gemm_fp4 M={M}: margins of {name}")
+
+
+def test_gemm_fp4_weight_scale_footprint(dev):
+    """one E8M0 NaN (0xFF) in the packed block-scale array SW at (channel n, K block kb) -- byte [n / 64][kb / 4][lane (r = n % 16, g = kb % 4)][nf =
+    (n % 64) / 16] of csrc/gemm256f4.hip's layout, restated here -- makes exactly output column n non-finite; every other column is bit-identical"""
+    from diffusionkit_amd import ops
+    N, M = 256, 376
+    a8, sa = ops.quantize_mx8(_act8().to(dev, BF))
+    w4, sw, wsc, bias = _fp4_weight(dev, N)
+    swg, wg = fp.guarded(sw, 1, 0xFF)
+    sw_clean = sw.clone()
+    run = lambda: ops.gemm_fp4(a8, sa, w4, swg, wsc, bias=bias, M=M, k=K8).cpu()  # noqa: E731
+    clean = run()
+    assert bool(torch.isfinite(clean.float()).all())
+    for n in (0, 17, 255):
+        for kb in (0, K8 // 32 - 1):
+            swg.copy_(sw_clean)
+            swg[((((n // 64) * (K8 // 128) + kb // 4) * 4 + kb % 4) * 16 + n % 16) * 4 + (n % 64) // 16] = 0xFF
+            got = run()
+            bad = ~torch.isfinite(got.float())
+            other = torch.ones(N, dtype=torch.bool)
+            other[n] = False
+            assert bool(bad[:, n].all()), f"SW NaN at (channel {n}, block {kb}): {int((~bad[:, n]).sum())} of {M} outputs of column {n} stayed finite"
+            assert not bool(bad[:, other].any()), f"SW NaN at (channel {n}, block {kb}): non-finite outputs in columns {sorted(set(bad.nonzero()[:, 1].tolist()) - {n})[:8]}"
+            assert torch.equal(fp.bits(got)[:, other], fp.bits(clean)[:, other]), f"SW NaN at (channel {n}, block {kb}): other columns differ from the clean run"
+    wg.check("gemm_fp4: margins of the block scales")
+
+
+def test_gemm_fp4_weight_pad_bytes_are_not_read(dev):
+    """a pitched weight (ldw = K / 2 + 64): the pad bytes behind the K / 128 fragments of every fragment row (16 channels x ldw bytes) filled with 0x77
+    leave the output bit-identical.  (E2M1 has no NaN: a pad byte that was read would change values, not poison them.)"""
+    from diffusionkit_amd import ops
+    N, M, pitch = 256, 376, K8 // 2 + 64
+    a8, sa = ops.quantize_mx8(_act8().to(dev, BF))
+    w4, sw, wsc, bias = _fp4_weight(dev, N, pitch)
+    assert w4.shape == (N, pitch)
+    run = lambda: ops.gemm_fp4(a8, sa, w4, sw, wsc, bias=bias, M=M, k=K8).cpu()  # noqa: E731
+    clean = run()
+    assert bool(torch.isfinite(clean.float()).all())
+    rows = w4.view(N // 16, 16 * pitch)
+    assert int(rows[:, K8 * 8:].max()) == 0  # (pack_mxfp4 leaves the pad zero)
+    rows[:, K8 * 8:] = 0x77
+    assert torch.equal(fp.bits(run()), fp.bits(clean)), "the output depends on the pad bytes of a pitched MX-fp4 weight"
+    w4u, swu, _, _ = _fp4_weight(dev, N)
+    assert torch.equal(fp.bits(ops.gemm_fp4(a8, sa, w4u, swu, wsc, bias=bias, M=M, k=K8).cpu()), fp.bits(clean)), "pitched and unpitched weights differ"
+
+
 # ---- attention ------------------------------------------------------------------------------------------------------------------------
 # (id, dtype, knobs, (B, H, S, D), query block of the kernel: attention2.hip QB = NW * 32 = 128, attention4.hip 256, attention5.hip 4 waves x 64)
 ATTN_FORMS = L.ATTN_FORMS
