@@ -112,6 +112,13 @@ def build_parser(model_versions: Sequence[str]) -> argparse.ArgumentParser:
                    help="Perturbed-attention guidance (SD3 versions with --cfg > 0): add S times (prompt prediction - prediction with the attention "
                         "of --pag-layers perturbed: image queries see the text and themselves only). Needs --pag-layers. Not together with "
                         "--slg-scale or --block-cache. Verified as arithmetic only: no checkpoint has been run here.")
+    p.add_argument("--region", action="append", default=None, metavar="X0,Y0,X1,Y1:PROMPT",
+                   help="Regional prompt (FLUX; repeatable, at most 31): PROMPT applies inside the box, in pixels of the output; --prompt is the base prompt.")
+    p.add_argument("--region-mask", action="append", default=None, metavar="PATH:PROMPT",
+                   help="Regional prompt whose region is the non-zero part of a mask image (sampled NEAREST at the centre of every 16 x 16 cell).")
+    p.add_argument("--no-region-base", action="store_true", help="With --region: --prompt is not used; every image token must lie in a region.")
+    p.add_argument("--region-isolate-image", action="store_true",
+                   help="With --no-region-base: image tokens of different regions do not attend to each other.")
     p.add_argument("--pag-layers", type=int, nargs="+", default=None, metavar="BLOCK", help="With --pag-scale: the double blocks whose attention is perturbed.")
     p.add_argument("--pag-interval", type=float, nargs=2, default=None, metavar=("START", "STOP"),
                    help="With --pag-scale: step i of n takes the term iff n START < i < n STOP (default: every guided step).")
@@ -286,6 +293,26 @@ def resolve(args) -> dict:
         opts = _perturbed_attention_options(*pag, mcfg, "FLUX" in args.model_version, cfg, r.get("block_cache"), r.get("reference_image_path"),
                                             r.get("condition"), r.get("skip_layer_guidance"))
         r.update(pag_scale=opts["scale"], pag_layers=opts["layers"], pag_interval=opts["interval"])
+    specs = [(s_, False) for s_ in getattr(args, "region", None) or []] + [(s_, True) for s_ in getattr(args, "region_mask", None) or []]
+    if specs or getattr(args, "no_region_base", False) or getattr(args, "region_isolate_image", False):  # (keys only when the flags are given)
+        from .regional import MAX_REGIONS, parse_region
+        if not specs:
+            raise ValueError("--no-region-base / --region-isolate-image need --region or --region-mask")
+        if "FLUX" not in args.model_version:
+            raise ValueError(f"--region needs a FLUX model version, not {args.model_version}")
+        if len(specs) > MAX_REGIONS:
+            raise ValueError(f"at most {MAX_REGIONS} regions (--region / --region-mask), got {len(specs)}")
+        if getattr(args, "fp8", None) or getattr(args, "fp4", None):
+            raise ValueError("--region cannot run together with " + ("--fp8" if getattr(args, "fp8", None) else "--fp4"))
+        for key, flag in (("block_cache", "--block-cache"), ("reference_image_path", "--reference-image-path"), ("condition", "--condition"),
+                          ("skip_layer_guidance", "--slg-scale"), ("pag_scale", "--pag-scale")):
+            if r.get(key) is not None:
+                raise ValueError(f"--region cannot run together with {flag}")
+        for flag in ("controlnet", "ip_adapter", "edit_source_prompt"):
+            if getattr(args, flag, None) is not None:
+                raise ValueError(f"--region cannot run together with --{flag.replace('_', '-')}")
+        r["regions"] = [parse_region(s_, mask=m) for s_, m in specs]
+        r["region_base"], r["region_isolate_image"] = not args.no_region_base, bool(args.region_isolate_image)
     cn = {k: getattr(args, k, None) for k in ("controlnet", "controlnet_image_path", "controlnet_scale", "controlnet_interval", "controlnet_blocks")}
     if any(v is not None for v in cn.values()):  # (keys only when the flags are given)
         from .config import MODEL_CONFIG
@@ -403,6 +430,7 @@ def preview_writer(directory: str):
 EDIT_KEYS = ("edit_source_text", "edit_steps", "edit_n_avg", "edit_source_cfg")  # the same, FlowEdit
 SKIP_LAYER_KEYS = ("skip_layer_guidance", "skip_layers", "skip_layer_interval")  # keywords of generate_image that ``resolve`` sets together
 PAG_KEYS = ("pag_scale", "pag_layers", "pag_interval")  # the same, perturbed-attention guidance
+REGION_KEYS = ("regions", "region_base", "region_isolate_image")  # the same, regional prompts
 CONTROLNET_KEYS = ("controlnet_image_path", "controlnet_scale", "controlnet_interval")  # the same, SD3 ControlNet (the constructor takes controlnet_ckpt)
 IP_ADAPTER_KEYS = ("ip_adapter_image_embeds", "ip_adapter_scale")  # the same, FLUX IP-Adapter (the constructor takes ip_adapter_ckpt)
 # argparse destination -> keyword of generate_image
@@ -461,7 +489,7 @@ def main(argv: Optional[Sequence[str]] = None, pipeline_overrides: Optional[dict
                                    negative_text=args.negative_prompt, latent_size=latent_size, image_path=args.image_path,
                                    denoise=1.0 if "edit_source_text" in r else args.denoise, verbose=args.verbose, mask_path=r.get("mask_path"),
                                    composite=r.get("composite", True), block_cache=r.get("block_cache"), sampler=r.get("sampler"),
-                                   **{key: r[key] for key in (*GUIDANCE_FLAGS.values(), "reference_image_path", *SKIP_LAYER_KEYS, *PAG_KEYS, "sampler_eta", *EDIT_KEYS)
+                                   **{key: r[key] for key in (*GUIDANCE_FLAGS.values(), "reference_image_path", *SKIP_LAYER_KEYS, *PAG_KEYS, "sampler_eta", *EDIT_KEYS, *REGION_KEYS)
                                       if key in r},
                                    **cond_kw, **tiny_kw)
     if log["text_encoding"].get("synthetic"):

@@ -259,6 +259,27 @@ extern "C" int dk_attention_identity_plan(const dk_attention_desc* d, int32_t id
   DK_REQUIRE(plan != nullptr, "null plan");
   return attention_identity(f16 ? DK_DTYPE_F16 : DK_DTYPE_BF16, d, ident_from, nullptr, plan);
 }
+// group-masked attention (include/dk_hip.h): the descriptor's launch with AttnParams::groups set; every check is dk_attention_route's.  The words are
+// not read here (no device readback): a zero word is the caller's to refuse (ops.attention_groups, the pipeline)
+static int attention_groups(const dk_attention_desc* d, const uint32_t* groups, void* stream, dk_attention_plan_t* plan) {
+  AttnParams p;
+  if (const int rc = attn_params_from_desc(DK_DTYPE_BF16, d, p)) return rc;
+  DK_REQUIRE(groups != nullptr, "group-masked attention: groups missing (use dk_attention_desc_bf16 without a mask)");
+  DK_REQUIRE(((uintptr_t)groups & 3) == 0, "group-masked attention: groups is an array of 32-bit words");
+  p.groups = groups;
+  if (plan == nullptr) return dk_launch_attention(p, g_attn_ws, S_(stream));
+  AttnRoute r;
+  if (const int rc = dk_attention_route(p, 0, dk_device_cu_count(), r)) return rc;
+  *plan = dk_attention_plan_t{r.kernel, r.qfuse, r.blocks, r.whole, r.split, r.jobs, r.jobs > 0, r.quantize, r.launches, r.n_cu, 0, r.untracked};
+  return 0;
+}
+extern "C" int dk_attention_groups_bf16(const dk_attention_desc* d, const uint32_t* groups, void* stream) {
+  return attention_groups(d, groups, stream, nullptr);
+}
+extern "C" int dk_attention_groups_plan(const dk_attention_desc* d, const uint32_t* groups, dk_attention_plan_t* plan) {
+  DK_REQUIRE(plan != nullptr, "null plan");
+  return attention_groups(d, groups, nullptr, plan);
+}
 extern "C" int32_t dk_attention_d512_tp(int32_t T) { return (int32_t)align_up((size_t)(T > 0 ? T : 0), 64); }
 int attention_d512(int dtype, const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int B, int T, int ld, int ldo, float scale,
                    bf16_t* vt, hipStream_t st) {  // (dk_engine.h)

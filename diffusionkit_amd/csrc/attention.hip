@@ -10,6 +10,8 @@
 //
 // Kernels: attention2.hip (VALU-lean, deferred rescale, 4 waves of 32 queries; D = 64, short sequences, and the only one with a score
 // bias) and attention4.hip (the two waves of a SIMD in opposite matrix / vector phases; D = 128, the default on long sequences).
+// The one masked form for D = 128 is attention_group.hip (AttnParams::groups, one group word per token: regional prompts), a kernel of its own that
+// only a launch with group words reaches.
 // Round 5 moved what no default path takes to profiles/lab_kernels/ (README there): the software-pipelined D = 128 kernel with its
 // balanced stream-K-like launch (attention3_pipelined.hip: 908 / 961 / 978 TF against attention4's 1018 / 1053 / 1078 on FLUX B1 /
 // FLUX-dev B1 / FLUX B4), the D = 64 form with two query blocks per wave and the pipelined D = 64 patch (rounds 2-4: all within +-6 %
@@ -40,6 +42,24 @@ int dk_attention_route(const AttnParams& p, size_t ws_bytes, int n_cu, AttnRoute
   DK_REQUIRE(p.S > 0 && p.B > 0 && p.H > 0, "empty attention");
   DK_REQUIRE(p.ld % 8 == 0 && p.ldo % 4 == 0, "row strides must keep 16-byte alignment");
   DK_REQUIRE(n_cu > 0, "compute unit count");
+  if (p.groups != nullptr) {  // group-masked attention (AttnParams::groups): attention_group.hip, whatever the knobs say; nothing below is consulted
+    DK_REQUIRE(p.D == 128, "group-masked attention: head_dim must be 128");
+    DK_REQUIRE(p.dtype == DK_DTYPE_BF16, "group-masked attention: bf16 only (no fp16 form)");
+    DK_REQUIRE(p.bias == nullptr, "group-masked attention: no score bias");
+    DK_REQUIRE(p.O8 == nullptr, "group-masked attention: no MX-fp8 copy of the output");
+    DK_REQUIRE(p.ident_from == 0, "group-masked attention: no identity attention (ident_from) on top");
+    DK_REQUIRE(p.scale > 0.f && p.S <= 65536, "group-masked attention: a positive scale, S <= 65536");
+    DK_REQUIRE((size_t)p.S * p.ld * 2 < (1ull << 32), "one batch row of QKV must span < 4 GiB");
+    r = AttnRoute{};
+    r.kernel = 11;
+    r.n_cu = n_cu;
+    r.qfuse = p.qn_a != nullptr || p.q_rope != nullptr;
+    if (r.qfuse) DK_REQUIRE(p.qn_a == nullptr || p.qn_b != nullptr, "qn_b missing (pass qn_a twice for one weight)");
+    r.blocks = r.whole = (int)((long)p.B * p.H * ((p.S + 127) / 128));  // this kernel's query blocks are 128 rows
+    r.split = 1;  // no key split: skipped tiles leave the blocks uneven, and nothing balances them
+    r.launches = 1;
+    return 0;
+  }
   if (p.ident_from != 0) {  // identity attention (AttnParams::ident_from): attention2.hip's IDENT case, bf16 and fp16
     DK_REQUIRE(p.D == 64, "identity attention: head_dim must be 64");
     DK_REQUIRE(p.bias == nullptr, "identity attention: no score bias");
@@ -120,7 +140,7 @@ int dk_launch_attention(const AttnParams& p_in, AttnWs ws, hipStream_t stream) {
     work = 4.0 * (double)p.B * p.H * (double)tiles * 128.0 * 64.0 * p.D;
   }
   dk_prof_begin(2, work, stream);
-  const int rc = r.kernel == 10 ? dk_launch_attention5(p, r, ws.p, stream) : r.kernel == 9 ? dk_launch_attention4(p, stream) : dk_launch_attention2(p, 4, stream);
+  const int rc = r.kernel == 11 ? dk_launch_attention_group(p, stream) : r.kernel == 10 ? dk_launch_attention5(p, r, ws.p, stream) : r.kernel == 9 ? dk_launch_attention4(p, stream) : dk_launch_attention2(p, 4, stream);
   dk_prof_end(stream);
   if (rc) return rc;
   DK_CHECK_HIP(hipGetLastError());

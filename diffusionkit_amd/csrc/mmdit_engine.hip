@@ -109,6 +109,8 @@ struct dk_mmdit {
   std::vector<int32_t> pag;
   bool perturbed() const { return !pag.empty(); }
   bool perturbed(int g) const { return std::find(pag.begin(), pag.end(), g) != pag.end(); }
+  // regional prompts (dk_mmdit_set_attention_groups): the caller's [B, S] group words of the joint attention of every block, or null (off)
+  const uint32_t* groups = nullptr;
   // first-block cache (dk_mmdit_set_block_cache; include/dk_hip.h): image rows [B * S_i, h] each.  BC_R: X1 at the start of a compute tail, R
   // behind it.  BC_D[bc_cur]: X0 before block 0, D_cur behind the probe; BC_D[1 - bc_cur]: D_ref -- a compute tail swaps the two.
   // BC_ROWS: the probe's (num, den) per image row.  bc_valid: R / D_ref come from a computed step since the last reset; bc_pending: the step
@@ -551,6 +553,7 @@ extern "C" int dk_mmdit_prepare(dk_mmdit* m, int32_t batch, int32_t latent_h, in
                                 int32_t n_timesteps, void* workspace, size_t workspace_bytes, void* stream) {
   DK_REQUIRE(m && workspace, "null argument");
   DK_REQUIRE(batch > 0 && text_len > 0 && n_timesteps > 0, "empty problem");
+  m->groups = nullptr;  // (attention groups are [B, S] of ONE prepared shape: dk_mmdit_set_attention_groups follows every prepare)
   const int p = m->cfg.patch_size;
   DK_REQUIRE(latent_h % p == 0 && latent_w % p == 0, "latent size must be divisible by the patch size");
   DK_TRY(mmdit_resolve(m));
@@ -812,6 +815,7 @@ static AttnParams joint_attention(const dk_mmdit* m, const BlockCtx& c, bf16_t* 
   // launch reuses these parameters on the fork rows (same operands, same bound; its kernel does not read it); the dual-attention launch of
   // MMDiT-X (D = 64, the lean kernel) passes none.
   ap.score_bound = block_score_bound(wt, wi, ap.D, ap.scale);
+  ap.groups = m->groups;  // (null: the launch is what it was; set: attention_group.hip, dk_attention_route)
   return ap;
 }
 extern "C" float dk_mmdit_score_bound(const dk_mmdit* m, int32_t kind, int32_t index) {
@@ -1187,6 +1191,37 @@ extern "C" int dk_mmdit_set_perturbed_attention(dk_mmdit* m, const int32_t* bloc
   m->fork_rows = fork_rows;
   return 0;
 }
+// ---- regional prompts: the group mask of the joint attention (include/dk_hip.h) ------------------------------------------------------------
+// the rules of an engine that carries group words, each named; asked when they are set and again in front of every forward (the other setters
+// do not know of the words)
+static int attention_groups_ok(const dk_mmdit* m) {
+  DK_REQUIRE(m->cfg.depth_unified > 0 && m->cfg.use_pos_embed == 0 && m->D() == 128, "attention groups need the FLUX geometry (single blocks, RoPE, head_dim 128): SD3 / head_dim 64 has no group-masked kernel");
+  DK_REQUIRE(m->cfg.fp8_linears == 0, "attention groups cannot be set on an engine with fp8_linears (the group-masked kernel writes no MX-fp8 copy)");
+  DK_REQUIRE(m->dtype == DK_DTYPE_BF16, "attention groups cannot be set on an engine with fp16 activations");
+  DK_REQUIRE(!m->control_net && !m->tapped(), "attention groups cannot be set on a control-net engine or while control taps are set");
+  DK_REQUIRE(m->ip_n == 0, "attention groups cannot be set on an engine with an IP-Adapter (dk_mmdit_set_ip_adapter)");
+  DK_REQUIRE(m->ref_h == 0 && m->ref_w == 0 && m->cond_f == 0, "attention groups cannot be set while a reference grid or a condition width is set");
+  DK_REQUIRE(!m->bc_on, "attention groups cannot be set on an engine with a block cache (dk_mmdit_set_block_cache)");
+  DK_REQUIRE(!m->slg() && !m->perturbed(), "attention groups cannot be set while skip layers or perturbed attention are set");
+  return 0;
+}
+extern "C" int dk_mmdit_set_attention_groups(dk_mmdit* m, const uint32_t* groups) {
+  DK_REQUIRE(m != nullptr, "null handle");
+  if (groups == nullptr) {
+    m->groups = nullptr;
+    return 0;
+  }
+  DK_REQUIRE(m->prepared, "dk_mmdit_set_attention_groups follows dk_mmdit_prepare (the words are [B, S] of the prepared shape)");
+  DK_REQUIRE(((uintptr_t)groups & 3) == 0, "attention groups: an array of 32-bit words");
+  DK_TRY(attention_groups_ok(m));
+  m->groups = groups;
+  return 0;
+}
+static int no_attention_groups(const dk_mmdit* m, const char* entry) {
+  if (m->groups == nullptr) return 0;
+  dk_set_error(std::string(entry) + " cannot run while attention groups are set (dk_mmdit_set_attention_groups): only dk_mmdit_forward takes them");
+  return -1;
+}
 static int no_skip_layers(const dk_mmdit* m, const char* entry) {
   if (!m->slg() && !m->perturbed()) return 0;
   dk_set_error(std::string(entry) + (m->slg() ? " cannot run while skip layers are set (dk_mmdit_set_skip_layers)" :
@@ -1447,6 +1482,7 @@ extern "C" int dk_mmdit_forward(dk_mmdit* m, const void* tokens_in, const void* 
   const bf16_t* mod_step = m->MOD + (size_t)step_index * m->B * m->mod_rows() * m->h();
   DK_TRY(no_control_net(m, "dk_mmdit_forward"));
   DK_TRY(need_ip_adapter(m));
+  if (m->groups != nullptr) DK_TRY(attention_groups_ok(m));
   m->bc_pending = -1;  // (a head without its tail is dropped: this call overwrites the stream it left; R / D_ref stay)
   if (m->slg()) return mmdit_forward_forked(m, tokens_in, text, mod_step, (bf16_t*)tokens_out, L);
   if (m->perturbed()) return mmdit_forward_perturbed(m, tokens_in, text, mod_step, (bf16_t*)tokens_out, L);
@@ -1482,6 +1518,7 @@ extern "C" int dk_mmdit_forward_head(dk_mmdit* m, const void* tokens_in, const v
   DK_REQUIRE(m->bc_on, "forward_head needs the block cache: dk_mmdit_set_block_cache(m, 1) before dk_mmdit_prepare");
   DK_REQUIRE(probe_out != nullptr, "null argument");
   DK_TRY(no_skip_layers(m, "dk_mmdit_forward_head"));
+  DK_TRY(no_attention_groups(m, "dk_mmdit_forward_head"));
   DK_TRY(no_control_net(m, "dk_mmdit_forward_head"));
   DK_TRY(no_control_taps(m, "dk_mmdit_forward_head"));
   DK_REQUIRE(step_index >= 0 && step_index < m->n_t, "step index out of range");
@@ -1503,6 +1540,7 @@ extern "C" int dk_mmdit_forward_tail(dk_mmdit* m, int32_t step_index, int32_t re
   DK_TRY(no_ip_adapter(m, "dk_mmdit_forward_tail"));  // (in front of the block cache's rule, as in dk_mmdit_forward_head)
   DK_REQUIRE(m->bc_on && tokens_out != nullptr, "forward_tail needs the block cache and an output");
   DK_TRY(no_skip_layers(m, "dk_mmdit_forward_tail"));
+  DK_TRY(no_attention_groups(m, "dk_mmdit_forward_tail"));
   DK_TRY(no_control_net(m, "dk_mmdit_forward_tail"));
   DK_TRY(no_control_taps(m, "dk_mmdit_forward_tail"));
   DK_REQUIRE(m->bc_pending >= 0, "forward_tail needs a pending head: dk_mmdit_forward_head of this step must run first");
@@ -1533,6 +1571,7 @@ extern "C" int dk_mmdit_run_blocks(dk_mmdit* m, const void* x_in, void* x_out, i
   DK_REQUIRE(m && m->prepared && m->mod_ready, "prepare + cache_modulation_params must precede run_blocks");
   DK_REQUIRE(x_in && x_out, "null argument");
   DK_TRY(no_skip_layers(m, "dk_mmdit_run_blocks"));
+  DK_TRY(no_attention_groups(m, "dk_mmdit_run_blocks"));
   DK_TRY(no_control_taps(m, "dk_mmdit_run_blocks"));
   DK_TRY(no_ip_adapter(m, "dk_mmdit_run_blocks"));
   DK_REQUIRE(step_index >= 0 && step_index < m->n_t, "step index out of range");

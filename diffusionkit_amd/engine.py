@@ -174,6 +174,7 @@ class MMDiTEngine:
         self._ref_cached = False
         self.skip_layers, self.fork_rows = (), 0  # ``set_skip_layers``; ((), 0): off
         self.perturbed_attention = ()  # ``set_perturbed_attention``: the blocks; (): off (it shares ``fork_rows``: one of the two at a time)
+        self.attention_groups = None  # ``set_attention_groups``: the [B, S] words on the device; None: off
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -203,6 +204,23 @@ class MMDiTEngine:
         if blocks or self.perturbed_attention:
             self.fork_rows = int(fork_rows)
         self.perturbed_attention = tuple(sorted(blocks))
+
+    def set_attention_groups(self, groups=None) -> None:
+        """dk_mmdit_set_attention_groups (regional prompts, include/dk_hip.h): ``groups`` = the [B, S] group words of the prepared shape, text rows
+        first (``ops.group_words``: a host array is checked for zero words and uploaded, [S] is repeated per batch row); the joint attention of
+        every block then lets query i see key j iff their words share a bit.  ``None``: off.  Set after ``prepare`` (which clears it); takes effect
+        at the next forward.  ``forward_head`` / ``forward_tail`` / ``run_blocks`` are refused while set."""
+        if groups is None:
+            _lib.check(self.lib.dk_mmdit_set_attention_groups(self._h, None), "dk_mmdit_set_attention_groups")
+            self.attention_groups = None
+            return
+        if self._shape is None:
+            raise _lib.DkHipError("set_attention_groups follows prepare (the words are [B, S] of the prepared shape)")
+        from . import ops
+        B, S = self._shape[0], self._shape[3] + self.tokens_shape()[1]
+        g = ops.group_words(groups, B, S, next(iter(self.weights.values())).device)
+        _lib.check(self.lib.dk_mmdit_set_attention_groups(self._h, g.data_ptr()), "dk_mmdit_set_attention_groups")
+        self.attention_groups = g  # (kept alive: the engine reads the caller's memory)
 
     def _check_pitched_weights(self) -> None:
         """The engine reads the long-reduction weights at ``dk_weight_pitch`` elements per row (include/dk_hip.h); the C ABI
@@ -246,6 +264,7 @@ class MMDiTEngine:
         self._ctrl_cached = False
         self._ip_cached = False
         self.control_taps = None  # (dk_mmdit_prepare switches taps off: their shape was the previous problem's)
+        self.attention_groups = None  # (... and the attention groups, for the same reason)
 
     @property
     def batch(self):

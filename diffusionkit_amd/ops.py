@@ -431,6 +431,51 @@ def attention_identity_plan(ident_from: int, dtype=BF, **kw):
     return plan
 
 
+def group_words(groups, B: int, S: int, device) -> Tensor:
+    """The [B, S] group words of ``attention_groups`` as an int32 device tensor (the bit patterns of the uint32 words).  A host array (numpy / CPU
+    tensor, [S] or [B, S]) is checked here -- every word non-zero: a zero word is a token that sees nothing, itself included -- and uploaded; a device
+    tensor is the caller's promise of the same and is taken as it is (the launcher reads no device memory back)."""
+    if isinstance(groups, Tensor) and groups.is_cuda:
+        g = groups
+    else:
+        import numpy as np
+        a = np.ascontiguousarray(groups.numpy() if isinstance(groups, Tensor) else groups).astype(np.uint32, copy=False)
+        if a.ndim == 1:
+            a = np.broadcast_to(a, (B, a.shape[0]))
+        if (a == 0).any():
+            raise ValueError(f"attention groups: {int((a == 0).sum())} zero words (a token must share a bit with itself)")
+        g = torch.from_numpy(np.array(a, dtype=np.uint32, order="C").view(np.int32)).to(device)
+    if g.dtype != torch.int32 or tuple(g.shape) != (B, S) or not g.is_contiguous():
+        raise ValueError(f"attention groups: contiguous int32 [B={B}, S={S}] wanted, got {g.dtype} {tuple(g.shape)}")
+    return g
+
+
+def attention_groups(qkv: Tensor, H: int, groups, D: int = 128, scale: Optional[float] = None, qn=None) -> Tensor:
+    """dk_attention_groups_bf16: ``attention`` over a token-major [B, S, 3*H*D] bf16 buffer under the group mask -- query i sees key j iff
+    groups[b, i] & groups[b, j] != 0 (regional prompts; head_dim 128).  ``groups``: see ``group_words``.  ``qn``: optionally
+    (qn_a, qn_b, qn_split[, q_rope]), the query QKNorm (+ RoPE) of the kernel's Q load, as ``attention_desc_call`` names them."""
+    _require_cuda(qkv, "qkv", BF)
+    B, S, ld = qkv.shape
+    h = H * D
+    g = group_words(groups, B, S, qkv.device)
+    out = torch.empty(B, S, h, dtype=BF, device=qkv.device)
+    kw = dict(q=qkv, k=qkv[:, :, h:], v=qkv[:, :, 2 * h:], out=out, B=B, H=H, S=S, D=D, ld=ld, ldo=h,
+              scale=scale if scale is not None else 1.0 / math.sqrt(D))
+    if qn is not None:
+        kw.update(qn_a=qn[0], qn_b=qn[1], qn_split=int(qn[2]), qn_eps=1e-6, q_rope=qn[3] if len(qn) > 3 else None)
+    d = _fill(_lib.dk_attention_desc, kw)
+    _lib.check(_lib.load().dk_attention_groups_bf16(C.byref(d), g.data_ptr(), _stream()), "dk_attention_groups_bf16")
+    return out
+
+
+def attention_groups_plan(**kw):
+    """dk_attention_groups_plan: what ``attention_groups`` with these dk_attention_desc fields would launch (host only; pointers may be made-up,
+    aligned integers), and every refusal of the launch."""
+    d, plan = _fill(_lib.dk_attention_desc, kw), _lib.dk_attention_plan_t()
+    _lib.check(_lib.load().dk_attention_groups_plan(C.byref(d), 4096, C.byref(plan)), "dk_attention_groups_plan")
+    return plan
+
+
 def ln_modulate(x: Tensor, shift: Tensor, scale: Tensor, eps: float = 1e-6) -> Tensor:
     """x: [B, S, h]; shift/scale: [B, h] -> [B, S, h] (bf16, or all float16)."""
     lib = _lib.load()

@@ -621,8 +621,22 @@ class DiffusionPipeline:
         edit_source_cfg=None,
         preview_every=None,
         preview_callback=None,
+        regions=None,
+        region_base: bool = True,
+        region_isolate_image: bool = False,
     ):
-        """``preview_every`` = N with ``preview_callback`` = f (a pipeline built with ``tiny_decoder_ckpt``): after every N-th step the tiny decoder
+        """``regions`` (regional prompts, FLUX family; None: off, and then every launch and every bit is what it was): a list of
+        {"prompt": str, "box": (x0, y0, x1, y1)} or {"prompt": str, "mask": path | PIL image | array}, at most 31, boxes in pixels of the output.
+        ``conditioning`` is then the token-axis concatenation of the prompts' T5 sequences, each at the same length -- the base prompt's first with
+        ``region_base``, then each region's -- and ``pooled_conditioning`` the base prompt's (the first region's without a base); ``generate_image``
+        builds both.  Every block's joint attention runs under the group mask of ``regional.region_words`` (a region's text sees itself and its
+        image tokens, image tokens see the text of their regions and, through bit 0, the base text and each other; ``region_isolate_image`` with
+        no base: image tokens of different regions do not see each other).  The words are built once per call and repeated per batch row.
+        Raises on an SD3 model, float16 activations, fp8 / fp4 engines, a ControlNet, an IP-Adapter, a reference image, ``condition=``,
+        ``block_cache``, skip-layer and perturbed-attention guidance, an edit, sharding through ``dist.generate_sharded``, more than 31 regions and an image token in no region without a base.
+        ``self.last_regions`` = {"regions", "base", "isolate_image", "text_tokens", "image_tokens"} (image tokens per region), or None.
+        Verified as arithmetic only, on synthetic weights.
+        ``preview_every`` = N with ``preview_callback`` = f (a pipeline built with ``tiny_decoder_ckpt``): after every N-th step the tiny decoder
         decodes the loop's x0 estimate on the current stream and ``f(step_index, image_u8)`` is called with the uint8 images [n, 8h, 8w, 3] (a
         tensor on the device, valid until the next preview).  The estimate is x - sigma v with v taken from the step itself,
         (sigma' x - sigma x') / (sigma' - sigma) for the state x at the step's sigma and x' at its sigma' -- Euler's own v; the step's effective
@@ -731,7 +745,7 @@ class DiffusionPipeline:
                        "perturbed-attention guidance": next((v for v in (pag_scale, pag_layers, pag_interval) if v is not None), None),
                        "a ControlNet": controlnet_image_path if controlnet_image_path is not None else getattr(self, "controlnet", None),
                        "an IP-Adapter": ip_adapter_image_embeds if ip_adapter_image_embeds is not None else getattr(self, "ip_adapter_config", None),
-                       "a reference image": reference_image_path,
+                       "a reference image": reference_image_path, "regional prompts (regions=)": regions,
                        "channel-concatenated conditioning (condition=)": condition_image_path if condition_image_path is not None
                        else getattr(self, "condition", None)}
             for what, value in refused.items():
@@ -754,6 +768,13 @@ class DiffusionPipeline:
             pag = _perturbed_attention_options(pag_scale, pag_layers, pag_interval, self.mmdit_config, self._IS_FLUX, cfg_weight, block_cache,
                                                reference_image_path, getattr(self, "condition", None) or condition_image_path, slg)
         guide = _guidance_options(guidance, guidance_rescale, apg_eta, apg_norm_threshold, apg_momentum, guidance_interval, cfg_weight)
+        self.last_regions = None
+        if regions is not None:  # (raises before any GPU work)
+            _check_regions(self, regions, {"block_cache": block_cache, "skip-layer guidance": slg, "perturbed-attention guidance": pag,
+                                           "a ControlNet": controlnet_image_path if controlnet_image_path is not None else getattr(self, "controlnet", None),
+                                           "an IP-Adapter": ip_adapter_image_embeds if ip_adapter_image_embeds is not None else getattr(self, "ip_adapter_config", None),
+                                           "a reference image": reference_image_path,
+                                           "channel-concatenated conditioning (condition=)": getattr(self, "condition", None) or condition_image_path})
         if mask_path is not None and image_path is None:
             raise ValueError("mask_path needs image_path: the mask says which part of that image to keep")
         n_seeds = len(seed) if isinstance(seed, (list, tuple)) else 1
@@ -800,6 +821,18 @@ class DiffusionPipeline:
             extra_args["noise"] = torch.from_numpy(np.ascontiguousarray(noise, dtype=np.float32)).to(self.device)
         if block_cache is not None:
             extra_args["block_cache"] = block_cache
+        if regions is not None:
+            from . import regional
+            ps = self.mmdit_config.patch_size
+            gh, gw, n_text = x_T.shape[1] // ps, x_T.shape[2] // ps, len(regions) + bool(region_base)
+            if conditioning.shape[-2] % n_text != 0:
+                raise ValueError(f"regions: conditioning holds {conditioning.shape[-2]} text tokens, not a multiple of the {n_text} prompts "
+                                 "(the base prompt's sequence, if any, then each region's, each at the same length)")
+            t_len = conditioning.shape[-2] // n_text
+            words = regional.region_words(regions, gh, gw, t_len, base=bool(region_base), isolate_image=bool(region_isolate_image), cell=8 * ps)
+            extra_args["attention_groups"] = words
+            self.last_regions = {"regions": len(regions), "base": bool(region_base), "isolate_image": bool(region_isolate_image), "text_tokens": t_len,
+                                 "image_tokens": [int(((words[n_text * t_len:] >> (r + 1)) & 1).sum()) for r in range(len(regions))]}
         if guide is not None:
             extra_args["guidance"] = guide
         if slg is not None:
@@ -848,6 +881,8 @@ class DiffusionPipeline:
         finally:
             if ip is not None:  # (the engine outlives the call: off again, the plain launches)
                 self.mmdit.set_ip_scale(0.0)
+            if regions is not None:  # (the same: a later call of the same shape does not prepare again)
+                self.mmdit.set_attention_groups(None)
         self.last_sampler = {"sampler": sampler, "model_evals": evals}
         if stochastic:  # (keys of the stochastic samplers alone)
             self.last_sampler.update(eta=eta if sampler == "euler_a" else None, noise_draws=draws)
@@ -967,7 +1002,7 @@ class DiffusionPipeline:
         self.last_block_cache = None
         self.last_guidance = dict(_DEFAULT_GUIDANCE, guided_evals=evals if cfg_on else 0, unguided_evals=0 if cfg_on else evals)
         self.last_skip_layer_guidance = self.last_perturbed_attention_guidance = self.last_controlnet = None
-        self.last_ip_adapter = self.last_reference = self.last_condition = None
+        self.last_ip_adapter = self.last_reference = self.last_condition = self.last_regions = None
         return self.latent_format.process_out(latent), iter_time
 
     def generate_image(
@@ -1014,8 +1049,15 @@ class DiffusionPipeline:
         decoder: str = "vae",
         preview_every=None,
         preview_callback=None,
+        regions=None,
+        region_base: bool = True,
+        region_isolate_image: bool = False,
     ):
-        """``decoder``: "vae" (default: every launch and every bit is what it was) or "tiny" -- the final latent is decoded by ``self.tiny_decoder``
+        """``regions``, ``region_base``, ``region_isolate_image``: regional prompts, see ``denoise_latents``.  ``text`` is the base prompt (not
+        encoded with ``region_base=False``); each region's prompt is encoded like it and the sequences are concatenated on the token axis (FLUX's
+        text RoPE ids are all zero: no table changes); the pooled vector is the base prompt's, or the first region's.
+        ``log["denoising"]["regions"]`` is ``self.last_regions``.
+        ``decoder``: "vae" (default: every launch and every bit is what it was) or "tiny" -- the final latent is decoded by ``self.tiny_decoder``
         (a pipeline built with ``tiny_decoder_ckpt``) instead of the VAE; the same image type comes back and ``log["decoding"]["decoder"]`` says
         which ran.  "tiny" raises without a tiny decoder and together with a ``composite`` paste-back (``mask_path`` or a fill mask: pass
         ``composite=False``).  ``preview_every`` / ``preview_callback``: per-step previews, see ``denoise_latents``.
@@ -1063,7 +1105,12 @@ class DiffusionPipeline:
             "peak_memory": 0.0,
         }
         t0 = time.time()
-        conditioning, pooled_conditioning = self.encode_text(text, cfg_weight, negative_text)
+        if regions is None:
+            conditioning, pooled_conditioning = self.encode_text(text, cfg_weight, negative_text)
+        else:
+            _check_regions(self, regions, {})  # (raises before the text is encoded)
+            enc = [self.encode_text(t, cfg_weight, negative_text) for t in ([text] if region_base else []) + [r["prompt"] for r in regions]]
+            conditioning, pooled_conditioning = torch.cat([c for c, _ in enc], dim=-2), enc[0][1]
         edit_source = None if edit_source_text is None else self.encode_text(edit_source_text, cfg_weight, negative_text)
         torch.cuda.synchronize(dev)
         log["text_encoding"]["post"] = mem()
@@ -1091,8 +1138,11 @@ class DiffusionPipeline:
                else {"ip_adapter_image_embeds": ip_adapter_image_embeds, "ip_adapter_scale": ip_adapter_scale}),
             **({} if edit_source_text is None and edit_steps is None and edit_n_avg is None and edit_source_cfg is None else
                {"edit_source_text": edit_source, "edit_steps": edit_steps, "edit_n_avg": edit_n_avg, "edit_source_cfg": edit_source_cfg}),
-            **({} if preview_every is None and preview_callback is None else {"preview_every": preview_every, "preview_callback": preview_callback}))
+            **({} if preview_every is None and preview_callback is None else {"preview_every": preview_every, "preview_callback": preview_callback}),
+            **({} if regions is None else {"regions": regions, "region_base": region_base, "region_isolate_image": region_isolate_image}))
         torch.cuda.synchronize(dev)
+        if regions is not None:
+            log["denoising"]["regions"] = self.last_regions
         log["denoising"]["post"] = mem()
         log["peak_memory"] = max(log["peak_memory"], log["denoising"]["post"]["peak_memory"])
         log["denoising"]["time"] = round(time.time() - t0, 3)
@@ -1714,6 +1764,27 @@ def _cache_condition(mm, condition: Optional[Tensor], now: int, n_img: int) -> N
         mm.cache_condition(condition.repeat(now // n_img, 1, 1).contiguous(), per_image=True)
 
 
+def _check_regions(pipe, regions, others: dict) -> None:
+    """The rules of regional prompts (``regions=`` of ``denoise_latents`` / ``generate_image``) that need no GPU, each named; ``others``: what the call
+    combines them with (name -> value, None: absent).  The geometry rules (31 regions, an uncovered image token) are ``regional.region_words``'s."""
+    from . import regional
+    if not pipe._IS_FLUX:
+        raise ValueError("regions (regional prompts) need a FLUX model: the group-masked attention kernel is built for head_dim 128 and the FLUX geometry")
+    if not isinstance(regions, (list, tuple)) or not 1 <= len(regions) <= regional.MAX_REGIONS:
+        raise ValueError(f"regions: a list of 1 to {regional.MAX_REGIONS} regions")
+    for r in regions:
+        if not isinstance(r, dict) or not isinstance(r.get("prompt"), str) or (r.get("box") is None) == (r.get("mask") is None):
+            raise ValueError(f"regions: every region is {{'prompt': str, 'box': (x0, y0, x1, y1)}} or {{'prompt': str, 'mask': path | image | array}}, got {r!r}")
+    cfg = pipe.mmdit_config
+    if cfg.weight_dtype != "bfloat16":
+        raise ValueError("regions cannot run on an fp8 / fp4 engine: the group-masked attention kernel writes no MX-fp8 copy of its output")
+    if pipe.activation_dtype != torch.bfloat16:
+        raise ValueError("regions cannot run with float16 activations: the group-masked attention kernel is bf16")
+    for what, value in others.items():
+        if value is not None:
+            raise ValueError(f"regions (regional prompts) cannot run together with {what}")
+
+
 def _prepare_rows(mm, now: int, latent_hw, text_len: int, n_t: int, reference: Optional[Tensor]) -> None:
     """``MMDiTEngine.prepare`` for ``now`` batch rows, with the reference latent's grid when there is one (none: the engine's grid is turned off)"""
     if reference is None:
@@ -1778,6 +1849,9 @@ def _loop_setup(model: "CFGDenoiser", x: Tensor, sigmas, extra_args, guided: boo
     _cache_condition(mm, condition, now, n_img)
     model.cache_modulation_params(pooled[:now], timesteps)
     mm.cache_context(conditioning[:now])  # context_embedder is step-invariant (the reference recomputes it in every call, mmdit.py:195)
+    model.attention_groups = extra_args.get("attention_groups")  # uint32 [S] of one batch row (regional prompts), or None: the engine is not told
+    if model.attention_groups is not None:
+        mm.set_attention_groups(model.attention_groups)  # (every batch row -- CFG rows, seeds -- repeats it)
     ip = extra_args.get("ip_adapter")
     if ip is not None and (ip["tokens"].dim() != 3 or ip["tokens"].shape[0] not in (1, n_img)):
         raise ValueError(f"the image-prompt tokens {tuple(ip['tokens'].shape)} do not match {n_img} images: [1 or n_img, N, C]")
@@ -1819,6 +1893,8 @@ def _set_rows(model: "CFGDenoiser", lp: _Loop, guided: bool, fork: bool = False)
     model.cache_modulation_params(rows(lp.pooled).contiguous(), lp.timesteps)
     lp.mm.cache_context(rows(lp.conditioning).contiguous())
     _cache_ip_adapter(lp.mm, lp.ip, now, lp.n_img)
+    if getattr(model, "attention_groups", None) is not None:  # (prepare cleared the words: they belong to one prepared shape)
+        lp.mm.set_attention_groups(model.attention_groups)
     if lp.forked is not None:  # (without the options the engine is never told: its calls are what they were)
         lp.set_fork(fork)
     _prepare_control(lp.control, now, lp.n_img, lp.x.shape[1:3], rows(lp.conditioning).contiguous(), rows(lp.pooled).contiguous(), lp.timesteps)

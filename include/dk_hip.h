@@ -237,7 +237,7 @@ int dk_attention_set_workspace(void* workspace, size_t bytes);
  * double blocks: image rows of all batch rows first, the S_t = o8_split text rows of each behind them).  Zero it -- or the whole record -- before
  * the call for the plain order of dk_attention_desc_bf16; it is read only when d->O8 is set. */
 typedef struct dk_attention_plan_t {
-  int32_t kernel;    /* in the codes of dk_tune_set("attn", .): 4 lean kernel, 9 phase-alternating, 10 one wave per SIMD */
+  int32_t kernel;    /* in the codes of dk_tune_set("attn", .): 4 lean kernel, 9 phase-alternating, 10 one wave per SIMD; 11 group-masked (dk_attention_groups_*) */
   int32_t qfuse;     /* QKNorm / RoPE of the queries inside the kernel's Q load */
   int32_t blocks;    /* query blocks of 256 rows: B * H * ceil(S / 256) */
   int32_t whole;     /* kernel 10: blocks that run whole (the others: the launch's last, partial round of the CUs); otherwise = blocks */
@@ -267,6 +267,21 @@ int dk_attention_plan(const dk_attention_desc* d, size_t workspace_bytes, dk_att
 int dk_attention_identity_bf16(const dk_attention_desc* d, int32_t ident_from, void* stream);
 int dk_attention_identity_f16(const dk_attention_desc* d, int32_t ident_from, void* stream);
 int dk_attention_identity_plan(const dk_attention_desc* d, int32_t ident_from, int32_t f16, dk_attention_plan_t* plan);
+
+/* Group-masked attention (additive in ABI 5; no reference counterpart -- training-free regional prompting for diffusion transformers, Chen et al.
+ * 2024, restated from memory of the paper): the descriptor's attention under a mask of one 32-bit word per token.  groups: [B, S] words on the
+ * device, every one non-zero; query i of batch row b sees key j iff groups[b*S + i] & groups[b*S + j] != 0 (every token sees itself).  Regional
+ * prompts with a base prompt: bit 0 on the base text and on every image token, bit r on region r's text and on the image tokens inside region r.
+ * No [S, S] table exists: attention_group.hip (bf16, D = 128; 128-query blocks, 64-key tiles) skips the key tiles a query block shares no bit
+ * with (not loaded), runs the unmasked body where every pair of a wave's 32 queries and the tile is allowed, and masks per element elsewhere: a
+ * disallowed key has probability exactly zero, and neither its K nor its V values reach the query (a NaN there changes no bit of its output).
+ * The fused query load works as in the plain launch.  d->score_bound is not read.
+ * Refused, nothing launched, dk_last_error() names the rule: D != 128; a score bias; an MX-fp8 copy (O8); S > 65536; a scale <= 0.  fp16 has no
+ * entry.  A ZERO WORD IS NOT DETECTED HERE (no device readback): such a row would see nothing; the callers that build the words refuse it on the
+ * host.  The route is kernel 11 -- plan->blocks then counts 128-row blocks, split = 1 -- whatever dk_tune_set("attn", .) says; no workspace is
+ * used.  dk_attention_groups_plan: host only (groups is only checked for NULL), the same checks; plan->o8_split is not read. */
+int dk_attention_groups_bf16(const dk_attention_desc* d, const uint32_t* groups, void* stream);
+int dk_attention_groups_plan(const dk_attention_desc* d, const uint32_t* groups, dk_attention_plan_t* plan);
 
 /* Single-head attention over head_dim 512: the VAE mid block's Attention (vae.py:28-57: softmax((q / sqrt 512) k^T) v over all
  * H * W tokens), flash-style -- the [T, T] score matrix of the reference (537 MB at T = 16384) is never written.  q / k / v / out:
@@ -968,6 +983,18 @@ int dk_mmdit_set_skip_layers(dk_mmdit* m, const int32_t* blocks, int32_t n_block
  * dk_mmdit_forward_tail and dk_mmdit_run_blocks while perturbed attention is set.  Both element types.
  * Verified against an fp32 / emulating oracle with synthetic weights (arithmetic parity); no checkpoint has been run. */
 int dk_mmdit_set_perturbed_attention(dk_mmdit* m, const int32_t* blocks, int32_t n_blocks, int32_t fork_rows);
+
+/* ---- Regional prompts: a group mask on the joint attention of every block (opt-in; FLUX geometry, bf16; no counterpart in the reference) ----
+ * groups: [B, S] 32-bit words on the device in the engine's joint row order (the S_t text rows first), every one non-zero, the caller's until
+ * it is replaced; the joint attention of every double and single block then runs dk_attention_groups_bf16's kernel with them (query i sees
+ * key j iff their words share a bit), and nothing else of the model changes.  NULL, the default: off, every launch and every bit is what it was.
+ * Set AFTER dk_mmdit_prepare (which clears it: the words belong to one prepared shape); takes effect at the next dk_mmdit_forward.  The
+ * attention workspace carve does not change.  The words are not read back: a zero word is the caller's to refuse.
+ * Refused, with no state changed and an error that names the rule (asked again in front of every forward): SD3 geometry / head_dim 64;
+ * fp8_linears; fp16 activations; a control-net engine or control taps; an IP-Adapter; a reference grid or a condition width; the block
+ * cache; skip layers or perturbed attention.  dk_mmdit_forward_head, dk_mmdit_forward_tail and dk_mmdit_run_blocks are refused while set.
+ * Verified against an fp32 oracle with synthetic weights (arithmetic parity); no checkpoint has been run. */
+int dk_mmdit_set_attention_groups(dk_mmdit* m, const uint32_t* groups);
 
 /* ---- SD3 ControlNet (opt-in; the layout of diffusers' SD3ControlNetModel, no counterpart in the reference) ---------------------------
  * Two engines.  The CONTROL-NET engine is an SD3 engine of N_c blocks without a final layer, with a second patch embedder for the
