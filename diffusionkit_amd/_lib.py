@@ -175,6 +175,10 @@ SIGNATURES = {
     # group-masked attention (regional prompts): the descriptor, the [B, S] uint32 words, then the stream -- or the plan
     "dk_attention_groups_bf16": (_i32, [C.POINTER(dk_attention_desc), _vp, _vp]),
     "dk_attention_groups_plan": (_i32, [C.POINTER(dk_attention_desc), _vp, C.POINTER(dk_attention_plan_t)]),
+    # quantised attention (MX-fp8 products): the size query, the descriptor + workspace + bytes + stream -- or bytes + plan
+    "dk_attention_fp8_workspace_bytes": (C.c_size_t, [_i32, _i32, _i32]),
+    "dk_attention_fp8_bf16": (_i32, [C.POINTER(dk_attention_desc), _vp, C.c_size_t, _vp]),
+    "dk_attention_fp8_plan": (_i32, [C.POINTER(dk_attention_desc), C.c_size_t, C.POINTER(dk_attention_plan_t)]),
     "dk_gemm_workspace_bytes": (C.c_size_t, []),
     "dk_attention_workspace_bytes": (C.c_size_t, []),
     "dk_attention_set_workspace": (C.c_int, [C.c_void_p, C.c_size_t]),
@@ -271,6 +275,8 @@ SIGNATURES = {
     "dk_mmdit_set_perturbed_attention": (_i32, [_vp, C.POINTER(_i32), _i32, _i32]),
     # regional prompts: the [B, S] group words of every block's joint attention (NULL: off)
     "dk_mmdit_set_attention_groups": (_i32, [_vp, _vp]),
+    # quantised attention: both products of every block's joint attention in MX-fp8 (before the first prepare)
+    "dk_mmdit_set_attention_fp8": (_i32, [_vp, _i32]),
     **{"dk_ln_modulate_dual_" + el: (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
                                             _i32, _f32, _vp]) for el in ("bf16", "f16")},
     # SD3 ControlNet: the control-net engine's setter / hoist / forward, the main engine's taps, and the LayerNorm pass with a residual tap in front

@@ -183,6 +183,9 @@ def build_parser(model_versions: Sequence[str]) -> argparse.ArgumentParser:
     p.add_argument("--activation-dtype", choices=("bfloat16", "float16"), default="bfloat16",
                    help="Element type of the MMDiT's weights and activations. float16 is the reference's dtype for Stable Diffusion 3 "
                         "(SD3 versions only); the text encoders stay bfloat16, the VAE has --vae-dtype.")
+    p.add_argument("--attention-dtype", choices=("bfloat16", "fp8"), default="bfloat16",
+                   help="Number format of the joint attention's two matrix products. fp8: both on the MX-fp8 MFMA (FLUX versions only; "
+                        "opt-in, slower than the bf16 kernel today and arithmetic-tested on synthetic weights only).")
     p.add_argument("--vae-dtype", choices=("bfloat16", "float16"), default=None,
                    help="Element type of the VAE decoder and (img2img) encoder; default bfloat16. float16 is the reference's decoder dtype "
                         "for Stable Diffusion 3 (not for FLUX); accepted for every model version.")
@@ -231,6 +234,14 @@ def resolve(args) -> dict:
         from .config import MODEL_CONFIG, float16_config
         float16_config(r.get("mmdit_config", MODEL_CONFIG[args.model_version]))
         r["activation_dtype"] = args.activation_dtype
+    if getattr(args, "attention_dtype", "bfloat16") != "bfloat16":
+        # (config.validate_attention_dtype raises a ValueError for the SD3 geometries and together with --activation-dtype float16)
+        from dataclasses import replace
+        from .config import MODEL_CONFIG, validate_attention_dtype
+        acfg = replace(r.get("mmdit_config", MODEL_CONFIG[args.model_version]), attention_dtype="fp8_e4m3",
+                       activation_dtype=r.get("activation_dtype", "bfloat16"))
+        validate_attention_dtype(acfg)
+        r["attention_dtype"] = "fp8_e4m3"
     if getattr(args, "vae_dtype", None) is not None:  # (a key only when the flag is given)
         from .config import validate_vae_dtype
         r["vae_dtype"] = validate_vae_dtype(args.vae_dtype)
@@ -456,6 +467,10 @@ def main(argv: Optional[Sequence[str]] = None, pipeline_overrides: Optional[dict
         extra["mmdit_config"] = fp4_config(extra["mmdit_config"], args.fp4) if extra.get("mmdit_config") is not None else r["mmdit_config"]
     if "activation_dtype" in r:
         extra["activation_dtype"] = r["activation_dtype"]
+    if "attention_dtype" in r:  # (on the caller's config, or the model version's own, behind --fp8 / --fp4)
+        from dataclasses import replace
+        from .config import MODEL_CONFIG
+        extra["mmdit_config"] = replace(extra.get("mmdit_config") or MODEL_CONFIG[args.model_version], attention_dtype=r["attention_dtype"])
     if "vae_dtype" in r:
         extra["vae_dtype"] = r["vae_dtype"]
     if "condition" in r:

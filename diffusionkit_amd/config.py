@@ -59,6 +59,9 @@ class MMDiTConfig:
     # channel-concatenated conditioning (FLUX.1 Fill: 320, Canny / Depth: 64; 0: none): x_embedder.proj.weight has patch_dim + condition_features
     # columns, and a condition token row of that width rides into every model evaluation (MMDiTEngine.cache_condition); FLUX family only
     condition_features: int = 0
+    # number format of the two matrix products of the joint attention: "bfloat16", or "fp8_e4m3" -- both on the MX-fp8 MFMA (csrc/attention_f8.hip,
+    # dk_mmdit_set_attention_fp8; no reference counterpart); FLUX geometry with bf16 activations only (validate_attention_dtype)
+    attention_dtype: str = "bfloat16"
     # MMDiT-X (Stable Diffusion 3.5 medium; no reference counterpart): the first n double blocks carry a second self-attention over the image
     # tokens alone (x_block.attn2), fed by a second modulation of the block's LayerNorm and gated by a ninth adaLN row; SD3 family only
     # (validate_dual_attention)
@@ -296,6 +299,20 @@ def fp4_config(cfg: MMDiTConfig, policy: str = "quality") -> MMDiTConfig:
     out = replace(cfg, weight_dtype="mxfp4", fp8_bf16_double_blocks=n)
     validate_fp8_policy(out)
     return out
+
+
+def validate_attention_dtype(cfg: MMDiTConfig) -> None:
+    """``attention_dtype`` is "bfloat16" or "fp8_e4m3"; fp8_e4m3 needs the FLUX geometry (head_dim 128, single-stream blocks, RoPE) and bf16
+    activations (the rules dk_mmdit_set_attention_fp8 enforces)."""
+    if cfg.attention_dtype not in ("bfloat16", "fp8_e4m3"):
+        raise ValueError(f"unknown attention_dtype {cfg.attention_dtype!r} (bfloat16 | fp8_e4m3)")
+    if cfg.attention_dtype == "bfloat16":
+        return
+    if cfg.activation_dtype != "bfloat16":
+        raise ValueError("attention_dtype fp8_e4m3 cannot be combined with activation_dtype float16 (the quantised kernel reads and writes bf16)")
+    if cfg.head_dim != 128 or cfg.depth_unified == 0 or cfg.pos_embed_type == PositionalEncoding.LearnedInputEmbedding:
+        raise ValueError(f"attention_dtype fp8_e4m3 needs the FLUX geometry: head_dim == 128 (got {cfg.head_dim}), single-stream blocks and RoPE; "
+                         "the SD3 family has no quantised attention kernel")
 
 
 def validate_activation_dtype(cfg: MMDiTConfig) -> None:

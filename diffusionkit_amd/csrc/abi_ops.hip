@@ -280,6 +280,32 @@ extern "C" int dk_attention_groups_plan(const dk_attention_desc* d, const uint32
   DK_REQUIRE(plan != nullptr, "null plan");
   return attention_groups(d, groups, nullptr, plan);
 }
+// quantised attention (include/dk_hip.h): the descriptor's launch with AttnParams::f8_ws set; every check is dk_attention_route's.  The plan entry has
+// no region: it routes with a made-up aligned address of workspace_bytes bytes (nothing is dereferenced on the host)
+static int attention_fp8(const dk_attention_desc* d, void* workspace, size_t workspace_bytes, void* stream, dk_attention_plan_t* plan) {
+  AttnParams p;
+  if (const int rc = attn_params_from_desc(DK_DTYPE_BF16, d, p)) return rc;
+  DK_REQUIRE(workspace != nullptr, "fp8 attention: workspace missing (dk_attention_fp8_workspace_bytes(B, H, S) bytes)");
+  p.f8_ws = workspace;
+  p.f8_ws_bytes = workspace_bytes;
+  if (plan == nullptr) return dk_launch_attention(p, g_attn_ws, S_(stream));
+  if (p.O8 != nullptr) {
+    p.o8_split = plan->o8_split;
+    p.o8_txt_row0 = p.B * (p.S - p.o8_split);
+  }
+  AttnRoute r;
+  if (const int rc = dk_attention_route(p, 0, dk_device_cu_count(), r)) return rc;
+  *plan = dk_attention_plan_t{r.kernel, r.qfuse, r.blocks, r.whole, r.split, r.jobs, r.jobs > 0, r.quantize, r.launches, r.n_cu, p.o8_split, r.untracked};
+  return 0;
+}
+extern "C" size_t dk_attention_fp8_workspace_bytes(int32_t B, int32_t H, int32_t S) { return dk_attention_fp8_ws_bytes(B, H, S); }
+extern "C" int dk_attention_fp8_bf16(const dk_attention_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
+  return attention_fp8(d, workspace, workspace_bytes, stream, nullptr);
+}
+extern "C" int dk_attention_fp8_plan(const dk_attention_desc* d, size_t workspace_bytes, dk_attention_plan_t* plan) {
+  DK_REQUIRE(plan != nullptr, "null plan");
+  return attention_fp8(d, (void*)(uintptr_t)256, workspace_bytes, nullptr, plan);
+}
 extern "C" int32_t dk_attention_d512_tp(int32_t T) { return (int32_t)align_up((size_t)(T > 0 ? T : 0), 64); }
 int attention_d512(int dtype, const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int B, int T, int ld, int ldo, float scale,
                    bf16_t* vt, hipStream_t st) {  // (dk_engine.h)

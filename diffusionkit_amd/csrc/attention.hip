@@ -42,6 +42,31 @@ int dk_attention_route(const AttnParams& p, size_t ws_bytes, int n_cu, AttnRoute
   DK_REQUIRE(p.S > 0 && p.B > 0 && p.H > 0, "empty attention");
   DK_REQUIRE(p.ld % 8 == 0 && p.ldo % 4 == 0, "row strides must keep 16-byte alignment");
   DK_REQUIRE(n_cu > 0, "compute unit count");
+  if (p.f8_ws != nullptr) {  // quantised attention (AttnParams::f8_ws): attention_f8.hip, whatever the knobs say; nothing below is consulted
+    DK_REQUIRE(p.D == 128, "fp8 attention: head_dim must be 128");
+    DK_REQUIRE(p.dtype == DK_DTYPE_BF16, "fp8 attention: bf16 inputs and outputs only (no fp16 form)");
+    DK_REQUIRE(p.bias == nullptr, "fp8 attention: no score bias");
+    DK_REQUIRE(p.ident_from == 0, "fp8 attention: no identity attention (ident_from)");
+    DK_REQUIRE(p.groups == nullptr, "fp8 attention: no attention groups");
+    DK_REQUIRE(p.scale > 0.f, "fp8 attention: a positive scale");
+    DK_REQUIRE(p.S <= 65536, "fp8 attention: S <= 65536");
+    DK_REQUIRE((size_t)p.S * p.ld * 2 < (1ull << 32), "one batch row of QKV must span < 4 GiB");
+    DK_REQUIRE(p.f8_ws_bytes >= dk_attention_fp8_ws_bytes(p.B, p.H, p.S), "fp8 attention: workspace smaller than dk_attention_fp8_workspace_bytes(B, H, S)");
+    DK_REQUIRE(((uintptr_t)p.f8_ws & 15) == 0 && p.ldo % 8 == 0, "fp8 attention: a 16-byte aligned workspace and output rows");
+    DK_REQUIRE(!(p.score_bound < 0.f), "score_bound: a bound on |scale * q.k| is positive (0: unknown)");  // (accepted, not used)
+    if (p.O8 != nullptr && p.o8_split != 0)
+      DK_REQUIRE(p.o8_split > 0 && p.o8_split < p.S && p.o8_txt_row0 >= p.B * (p.S - p.o8_split), "MX-fp8 copy: text rows behind the image rows");
+    r = AttnRoute{};
+    r.kernel = 12;
+    r.n_cu = n_cu;
+    r.qfuse = p.qn_a != nullptr || p.q_rope != nullptr;
+    if (r.qfuse) DK_REQUIRE(p.qn_a == nullptr || p.qn_b != nullptr, "qn_b missing (pass qn_a twice for one weight)");
+    r.blocks = r.whole = (int)((long)p.B * p.H * ((p.S + 127) / 128));  // this kernel's query blocks are 128 rows
+    r.split = 1;
+    r.quantize = p.O8 == nullptr ? 0 : p.o8_split != 0 ? 2 : 1;  // the copy of the output comes from the quantiser pass, as for the lean kernel
+    r.launches = 2 + (r.quantize != 0);                          // pre-pass + attention (+ quantiser)
+    return 0;
+  }
   if (p.groups != nullptr) {  // group-masked attention (AttnParams::groups): attention_group.hip, whatever the knobs say; nothing below is consulted
     DK_REQUIRE(p.D == 128, "group-masked attention: head_dim must be 128");
     DK_REQUIRE(p.dtype == DK_DTYPE_BF16, "group-masked attention: bf16 only (no fp16 form)");
@@ -140,7 +165,7 @@ int dk_launch_attention(const AttnParams& p_in, AttnWs ws, hipStream_t stream) {
     work = 4.0 * (double)p.B * p.H * (double)tiles * 128.0 * 64.0 * p.D;
   }
   dk_prof_begin(2, work, stream);
-  const int rc = r.kernel == 11 ? dk_launch_attention_group(p, stream) : r.kernel == 10 ? dk_launch_attention5(p, r, ws.p, stream) : r.kernel == 9 ? dk_launch_attention4(p, stream) : dk_launch_attention2(p, 4, stream);
+  const int rc = r.kernel == 12 ? dk_launch_attention_f8(p, stream) : r.kernel == 11 ? dk_launch_attention_group(p, stream) : r.kernel == 10 ? dk_launch_attention5(p, r, ws.p, stream) : r.kernel == 9 ? dk_launch_attention4(p, stream) : dk_launch_attention2(p, 4, stream);
   dk_prof_end(stream);
   if (rc) return rc;
   DK_CHECK_HIP(hipGetLastError());

@@ -281,10 +281,15 @@ struct AttnParams {
   int ident_from = 0;
   // group-masked attention (regional prompts; attention_group.hip, D = 128, bf16): null off.  [B, S] words, every one non-zero (the caller's promise: the
   // launcher reads no device memory): query i of batch row b sees key j iff groups[b*S + i] & groups[b*S + j] != 0.  Set: the route is kernel 11
-  // whatever the "attn" knob says.  The last field: every offset in front of it is what it was
+  // whatever the "attn" knob says.
   const uint32_t* groups = nullptr;
+  // quantised attention (attention_f8.hip, D = 128, bf16): null off.  The caller's region for the MX-fp8 copies of K and V that the launch's pre-pass
+  // writes, f8_ws_bytes >= dk_attention_fp8_ws_bytes(B, H, S), 16-byte aligned.  Set: the route is kernel 12 whatever the "attn" knob says.
+  // The last fields: every offset in front of them is what it was
+  void* f8_ws = nullptr;
+  size_t f8_ws_bytes = 0;
 };
-static_assert(sizeof(AttnParams) == 192 && offsetof(AttnParams, groups) == 184 && offsetof(AttnParams, score_bound) == 60, "AttnParams is a kernel argument: its size and offsets are part of every attention kernel's code");
+static_assert(sizeof(AttnParams) == 208 && offsetof(AttnParams, groups) == 184 && offsetof(AttnParams, f8_ws) == 192 && offsetof(AttnParams, score_bound) == 60, "AttnParams is a kernel argument: its size and offsets are part of every attention kernel's code");
 // The 64-key tiles a 128-query block of identity attention walks, in order: tiles [0, n_lo), then [hi0, hi0 + n_hi).  A block that lies wholly
 // in the image range (q0 >= F) takes the ceil(F / 64) tiles that hold text keys and the tiles that hold its own rows, cut at the end of the
 // sequence -- never the same tile twice: q0 >= F is a multiple of 64, so q0 / 64 >= ceil(F / 64).  A block with a text query walks every tile.
@@ -313,7 +318,7 @@ constexpr size_t DK_ATTN5_JOB_BYTES = 65536 + 2048;
 // dk_attention_plan reports it.  A key split changes the summation order: the route is part of the results.
 struct AttnRoute {
   int kernel;     // in the knob's codes: 4 lean (attention2.hip), 9 phase-alternating (attention4.hip), 10 one wave per SIMD (attention5.hip); 11 group-masked
-                  // (attention_group.hip: AttnParams::groups, never the knob)
+                  // (attention_group.hip: AttnParams::groups, never the knob); 12 MX-fp8 products (attention_f8.hip: AttnParams::f8_ws, never the knob)
   bool qfuse;     // QKNorm / RoPE of the queries inside the Q load
   int blocks;     // query blocks of 256 rows, B * H * ceil(S / 256): what the automatic choice counts and kernels 9 and 10 launch per workgroup
   // kernel 10 (otherwise whole = blocks, split = 1, jobs = 0): workgroups 0 .. whole - 1 take whole blocks; each of the blocks - whole others,
@@ -333,6 +338,8 @@ int dk_launch_attention4(const AttnParams& p, hipStream_t stream);             /
 bool dk_attention5_eligible(const AttnParams& p);                              // attention5.hip (one wave per SIMD, asm tile loop; D = 128, S % 256 == 0, no score bias)
 int dk_launch_attention5(const AttnParams& p, const AttnRoute& r, void* ws, hipStream_t stream);
 int dk_launch_attention_group(const AttnParams& p, hipStream_t stream);        // attention_group.hip (AttnParams::groups; D = 128, bf16, no bias / O8 / key split)
+int dk_launch_attention_f8(const AttnParams& p, hipStream_t stream);           // attention_f8.hip (AttnParams::f8_ws; MX-fp8 products, D = 128, bf16 in / out: pre-pass + kernel)
+size_t dk_attention_fp8_ws_bytes(int B, int H, int S);                         // bytes of AttnParams::f8_ws for a launch (host only; 0 for an empty problem)
 
 // ---- single-head D = 512 attention of the VAE's mid block (attention512.hip) -------------------------------
 struct Attn512Params {

@@ -111,6 +111,11 @@ struct dk_mmdit {
   bool perturbed(int g) const { return std::find(pag.begin(), pag.end(), g) != pag.end(); }
   // regional prompts (dk_mmdit_set_attention_groups): the caller's [B, S] group words of the joint attention of every block, or null (off)
   const uint32_t* groups = nullptr;
+  // quantised attention (dk_mmdit_set_attention_fp8): the joint attention of every block on attention_f8.hip; F8WS: its K8 / V8T region, carved
+  // behind everything else (off: no take, the carve is what it was)
+  bool attn_f8 = false;
+  void* F8WS = nullptr;
+  size_t F8WS_bytes = 0;
   // first-block cache (dk_mmdit_set_block_cache; include/dk_hip.h): image rows [B * S_i, h] each.  BC_R: X1 at the start of a compute tail, R
   // behind it.  BC_D[bc_cur]: X0 before block 0, D_cur behind the probe; BC_D[1 - bc_cur]: D_ref -- a compute tail swaps the two.
   // BC_ROWS: the probe's (num, den) per image row.  bc_valid: R / D_ref come from a computed step since the last reset; bc_pending: the step
@@ -539,6 +544,12 @@ static size_t mmdit_carve(dk_mmdit* m, Carver& c, int B, int Hl, int Wl, int S_t
     m->IPKV = (bf16_t*)c.take((size_t)m->cfg.depth_multimodal * B * m->ip_n * 2 * h * 2);
     m->IP = (bf16_t*)c.take((size_t)B * S_i * h * 2);
   }
+  m->F8WS = nullptr;
+  m->F8WS_bytes = 0;
+  if (m->attn_f8) {  // (the same: no take with the option off)
+    m->F8WS_bytes = dk_attention_fp8_ws_bytes(B, m->cfg.num_heads, S);
+    m->F8WS = c.take(m->F8WS_bytes);
+  }
   return c.off;
 }
 
@@ -816,6 +827,7 @@ static AttnParams joint_attention(const dk_mmdit* m, const BlockCtx& c, bf16_t* 
   // MMDiT-X (D = 64, the lean kernel) passes none.
   ap.score_bound = block_score_bound(wt, wi, ap.D, ap.scale);
   ap.groups = m->groups;  // (null: the launch is what it was; set: attention_group.hip, dk_attention_route)
+  if (m->attn_f8) { ap.f8_ws = m->F8WS; ap.f8_ws_bytes = m->F8WS_bytes; }  // (set: attention_f8.hip, route kernel 12)
   return ap;
 }
 extern "C" float dk_mmdit_score_bound(const dk_mmdit* m, int32_t kind, int32_t index) {
@@ -1217,6 +1229,29 @@ extern "C" int dk_mmdit_set_attention_groups(dk_mmdit* m, const uint32_t* groups
   m->groups = groups;
   return 0;
 }
+// ---- quantised attention: both products of the joint attention in MX-fp8 (include/dk_hip.h) -------------------------------------------------
+// the rules of an engine with the option on, each named; asked when it is set and again in front of every forward
+static int attention_fp8_ok(const dk_mmdit* m) {
+  DK_REQUIRE(m->cfg.depth_unified > 0 && m->cfg.use_pos_embed == 0 && m->D() == 128, "fp8 attention needs the FLUX geometry (single blocks, RoPE, head_dim 128): SD3 / head_dim 64 has no quantised kernel");
+  DK_REQUIRE(m->dtype == DK_DTYPE_BF16, "fp8 attention cannot be set on an engine with fp16 activations");
+  DK_REQUIRE(m->groups == nullptr, "fp8 attention cannot run with attention groups (dk_mmdit_set_attention_groups)");
+  DK_REQUIRE(!m->perturbed(), "fp8 attention cannot run with perturbed attention (dk_mmdit_set_perturbed_attention)");
+  DK_REQUIRE(!m->slg(), "fp8 attention cannot run with skip layers (dk_mmdit_set_skip_layers): the fork rows are not in its workspace");
+  DK_REQUIRE(m->ip_n == 0, "fp8 attention cannot be set on an engine with an IP-Adapter (dk_mmdit_set_ip_adapter): its queries are read raw from QKV");
+  return 0;
+}
+extern "C" int dk_mmdit_set_attention_fp8(dk_mmdit* m, int32_t on) {
+  DK_REQUIRE(m != nullptr, "null handle");
+  DK_REQUIRE(!m->resolved && !m->prepared, "dk_mmdit_set_attention_fp8 is legal only before the first dk_mmdit_prepare (the workspace grows by the K8 / V8T region)");
+  if (on) DK_TRY(attention_fp8_ok(m));
+  m->attn_f8 = on != 0;
+  return 0;
+}
+static int no_attention_fp8(const dk_mmdit* m, const char* entry) {
+  if (!m->attn_f8) return 0;
+  dk_set_error(std::string(entry) + " cannot run while fp8 attention is set (dk_mmdit_set_attention_fp8): only dk_mmdit_forward takes it (the block cache has not been shown to compose)");
+  return -1;
+}
 static int no_attention_groups(const dk_mmdit* m, const char* entry) {
   if (m->groups == nullptr) return 0;
   dk_set_error(std::string(entry) + " cannot run while attention groups are set (dk_mmdit_set_attention_groups): only dk_mmdit_forward takes them");
@@ -1483,6 +1518,7 @@ extern "C" int dk_mmdit_forward(dk_mmdit* m, const void* tokens_in, const void* 
   DK_TRY(no_control_net(m, "dk_mmdit_forward"));
   DK_TRY(need_ip_adapter(m));
   if (m->groups != nullptr) DK_TRY(attention_groups_ok(m));
+  if (m->attn_f8) DK_TRY(attention_fp8_ok(m));
   m->bc_pending = -1;  // (a head without its tail is dropped: this call overwrites the stream it left; R / D_ref stay)
   if (m->slg()) return mmdit_forward_forked(m, tokens_in, text, mod_step, (bf16_t*)tokens_out, L);
   if (m->perturbed()) return mmdit_forward_perturbed(m, tokens_in, text, mod_step, (bf16_t*)tokens_out, L);
@@ -1519,6 +1555,7 @@ extern "C" int dk_mmdit_forward_head(dk_mmdit* m, const void* tokens_in, const v
   DK_REQUIRE(probe_out != nullptr, "null argument");
   DK_TRY(no_skip_layers(m, "dk_mmdit_forward_head"));
   DK_TRY(no_attention_groups(m, "dk_mmdit_forward_head"));
+  DK_TRY(no_attention_fp8(m, "dk_mmdit_forward_head"));
   DK_TRY(no_control_net(m, "dk_mmdit_forward_head"));
   DK_TRY(no_control_taps(m, "dk_mmdit_forward_head"));
   DK_REQUIRE(step_index >= 0 && step_index < m->n_t, "step index out of range");
@@ -1541,6 +1578,7 @@ extern "C" int dk_mmdit_forward_tail(dk_mmdit* m, int32_t step_index, int32_t re
   DK_REQUIRE(m->bc_on && tokens_out != nullptr, "forward_tail needs the block cache and an output");
   DK_TRY(no_skip_layers(m, "dk_mmdit_forward_tail"));
   DK_TRY(no_attention_groups(m, "dk_mmdit_forward_tail"));
+  DK_TRY(no_attention_fp8(m, "dk_mmdit_forward_tail"));
   DK_TRY(no_control_net(m, "dk_mmdit_forward_tail"));
   DK_TRY(no_control_taps(m, "dk_mmdit_forward_tail"));
   DK_REQUIRE(m->bc_pending >= 0, "forward_tail needs a pending head: dk_mmdit_forward_head of this step must run first");
@@ -1572,6 +1610,7 @@ extern "C" int dk_mmdit_run_blocks(dk_mmdit* m, const void* x_in, void* x_out, i
   DK_REQUIRE(x_in && x_out, "null argument");
   DK_TRY(no_skip_layers(m, "dk_mmdit_run_blocks"));
   DK_TRY(no_attention_groups(m, "dk_mmdit_run_blocks"));
+  DK_TRY(no_attention_fp8(m, "dk_mmdit_run_blocks"));
   DK_TRY(no_control_taps(m, "dk_mmdit_run_blocks"));
   DK_TRY(no_ip_adapter(m, "dk_mmdit_run_blocks"));
   DK_REQUIRE(step_index >= 0 && step_index < m->n_t, "step index out of range");

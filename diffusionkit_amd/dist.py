@@ -68,6 +68,8 @@ def generate_sharded(pipe, text: str, seeds: Sequence[int], rank: int, world: in
     if kw.get("decoder", "vae") != "vae" or any(k.startswith("preview_") for k in kw):
         raise ValueError("the tiny latent decoder (decoder='tiny', per-step previews) cannot run under multi-GPU sharding: every rank would call "
                          "the preview callback for its own share of the seeds")
+    if getattr(getattr(pipe, "mmdit_config", None), "attention_dtype", "bfloat16") != "bfloat16":
+        raise ValueError("attention_dtype fp8_e4m3 cannot run under multi-GPU sharding: not run with the seeds cut across ranks yet")
     if any(k.startswith("region") for k in kw):
         raise ValueError("regional prompts (regions=) cannot run under multi-GPU sharding: not verified with the seeds cut across ranks yet")
     mine = shard_seeds(seeds, rank, world)

@@ -107,6 +107,15 @@ class MMDiTEngine:
             raise _lib.DkHipError(str(e)) from None
         if config.dual_attention_blocks:
             _lib.check(self.lib.dk_mmdit_set_dual_attention(self._h, int(config.dual_attention_blocks)), "dk_mmdit_set_dual_attention")
+        # quantised attention (attention_dtype = "fp8_e4m3"): before the first prepare, the workspace grows by the K8 / V8T region
+        from .config import validate_attention_dtype
+        try:
+            validate_attention_dtype(config)
+        except ValueError as e:
+            raise _lib.DkHipError(str(e)) from None
+        self.attention_fp8 = False
+        if config.attention_dtype == "fp8_e4m3":
+            self.set_attention_fp8(True)
         # SD3 ControlNet: this engine is the ControlNet (no final layer, a second patch embedder, one tap Linear per block); set before the first bind
         from .config import validate_control_net
         try:
@@ -204,6 +213,13 @@ class MMDiTEngine:
         if blocks or self.perturbed_attention:
             self.fork_rows = int(fork_rows)
         self.perturbed_attention = tuple(sorted(blocks))
+
+    def set_attention_fp8(self, on: bool = True) -> None:
+        """dk_mmdit_set_attention_fp8 (include/dk_hip.h): the joint attention of every double and single block runs both matrix products on the
+        MX-fp8 MFMA (csrc/attention_f8.hip).  Legal until the first ``prepare`` (the workspace grows); FLUX geometry, bf16 activations.
+        ``MMDiTConfig(attention_dtype="fp8_e4m3")`` calls it in the constructor."""
+        _lib.check(self.lib.dk_mmdit_set_attention_fp8(self._h, int(bool(on))), "dk_mmdit_set_attention_fp8")
+        self.attention_fp8 = bool(on)
 
     def set_attention_groups(self, groups=None) -> None:
         """dk_mmdit_set_attention_groups (regional prompts, include/dk_hip.h): ``groups`` = the [B, S] group words of the prepared shape, text rows

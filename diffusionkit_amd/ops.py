@@ -476,6 +476,46 @@ def attention_groups_plan(**kw):
     return plan
 
 
+def attention_fp8_workspace_bytes(B: int, H: int, S: int) -> int:
+    """dk_attention_fp8_workspace_bytes: bytes of the region ``attention_fp8`` keeps the MX-fp8 copies of K and V in (host only)."""
+    return int(_lib.load().dk_attention_fp8_workspace_bytes(B, H, S))
+
+
+def attention_fp8(qkv: Tensor, H: int, D: int = 128, scale: Optional[float] = None, qn=None, workspace: Optional[Tensor] = None,
+                  out: Optional[Tensor] = None) -> Tensor:
+    """dk_attention_fp8_bf16: ``attention`` over a token-major [B, S, 3*H*D] bf16 buffer with both matrix products on the MX-fp8 MFMA (head_dim
+    128; bf16 in and out, the softmax in fp32).  ``qn``: optionally (qn_a, qn_b, qn_split[, q_rope]), as ``attention_groups`` takes them.
+    ``workspace``: a uint8 device tensor of at least ``attention_fp8_workspace_bytes(B, H, S)`` bytes (its content does not matter); None: one
+    of exactly that size is allocated.  ``out``: a [B, S, H*D] bf16 tensor to write into."""
+    _require_cuda(qkv, "qkv", BF)
+    B, S, ld = qkv.shape
+    h = H * D
+    if workspace is None:
+        workspace = torch.empty(attention_fp8_workspace_bytes(B, H, S), dtype=torch.uint8, device=qkv.device)
+    if workspace.dtype != torch.uint8 or not workspace.is_cuda or not workspace.is_contiguous():
+        raise ValueError("attention_fp8: workspace is a contiguous uint8 device tensor")
+    if out is None:
+        out = torch.empty(B, S, h, dtype=BF, device=qkv.device)
+    kw = dict(q=qkv, k=qkv[:, :, h:], v=qkv[:, :, 2 * h:], out=out, B=B, H=H, S=S, D=D, ld=ld, ldo=h,
+              scale=scale if scale is not None else 1.0 / math.sqrt(D))
+    if qn is not None:
+        kw.update(qn_a=qn[0], qn_b=qn[1], qn_split=int(qn[2]), qn_eps=1e-6, q_rope=qn[3] if len(qn) > 3 else None)
+    d = _fill(_lib.dk_attention_desc, kw)
+    _lib.check(_lib.load().dk_attention_fp8_bf16(C.byref(d), workspace.data_ptr(), workspace.numel(), _stream()), "dk_attention_fp8_bf16")
+    return out
+
+
+def attention_fp8_plan(workspace_bytes: Optional[int] = None, o8_split: int = 0, **kw):
+    """dk_attention_fp8_plan: what ``attention_fp8`` with these dk_attention_desc fields would launch (host only; pointers may be made-up, aligned
+    integers), and every refusal of the launch.  ``workspace_bytes``: None = the size query's answer."""
+    d, plan = _fill(_lib.dk_attention_desc, kw), _lib.dk_attention_plan_t()
+    plan.o8_split = o8_split
+    if workspace_bytes is None:
+        workspace_bytes = attention_fp8_workspace_bytes(d.B, d.H, d.S)
+    _lib.check(_lib.load().dk_attention_fp8_plan(C.byref(d), workspace_bytes, C.byref(plan)), "dk_attention_fp8_plan")
+    return plan
+
+
 def ln_modulate(x: Tensor, shift: Tensor, scale: Tensor, eps: float = 1e-6) -> Tensor:
     """x: [B, S, h]; shift/scale: [B, h] -> [B, S, h] (bf16, or all float16)."""
     lib = _lib.load()

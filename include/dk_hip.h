@@ -237,7 +237,7 @@ int dk_attention_set_workspace(void* workspace, size_t bytes);
  * double blocks: image rows of all batch rows first, the S_t = o8_split text rows of each behind them).  Zero it -- or the whole record -- before
  * the call for the plain order of dk_attention_desc_bf16; it is read only when d->O8 is set. */
 typedef struct dk_attention_plan_t {
-  int32_t kernel;    /* in the codes of dk_tune_set("attn", .): 4 lean kernel, 9 phase-alternating, 10 one wave per SIMD; 11 group-masked (dk_attention_groups_*) */
+  int32_t kernel;    /* in the codes of dk_tune_set("attn", .): 4 lean kernel, 9 phase-alternating, 10 one wave per SIMD; 11 group-masked (dk_attention_groups_*); 12 MX-fp8 products (dk_attention_fp8_*) */
   int32_t qfuse;     /* QKNorm / RoPE of the queries inside the kernel's Q load */
   int32_t blocks;    /* query blocks of 256 rows: B * H * ceil(S / 256) */
   int32_t whole;     /* kernel 10: blocks that run whole (the others: the launch's last, partial round of the CUs); otherwise = blocks */
@@ -282,6 +282,24 @@ int dk_attention_identity_plan(const dk_attention_desc* d, int32_t ident_from, i
  * used.  dk_attention_groups_plan: host only (groups is only checked for NULL), the same checks; plan->o8_split is not read. */
 int dk_attention_groups_bf16(const dk_attention_desc* d, const uint32_t* groups, void* stream);
 int dk_attention_groups_plan(const dk_attention_desc* d, const uint32_t* groups, dk_attention_plan_t* plan);
+
+/* Quantised attention (additive in ABI 5; no reference counterpart -- training-free, in the manner of SageAttention, restated from memory of the
+ * paper): the descriptor's attention with BOTH matrix products on the block-scaled MX-fp8 MFMA (e4m3 elements, one E8M0 scale per 32 of the
+ * contraction).  bf16 in, bf16 out, D = 128, any S >= 1; the fused query load (qn_a / qn_b / qn_split / q_rope) works as in the plain launch.
+ * Two launches (attention_f8.hip): a pre-pass writes the keys (one scale per key and 32 of D) and the transposed values (one scale per d and 32
+ * consecutive keys) into `workspace`, the key axis padded to a multiple of 128 with zeros under the scale 2^0 (the workspace needs no clearing,
+ * every byte that is read is written first); the attention kernel quantises the normed / rotated queries, times scale * log2 e, once, keeps the
+ * softmax in fp32 (running maximum, row sum over the fp32 probabilities) and hands P to the second product as e4m3 of p * 2^3.  Nothing is
+ * calibrated and no mean is subtracted from K.  d->O8 set: the MX-fp8 copy comes from the quantiser pass behind the kernel (plan->quantize 1 / 2).
+ * d->score_bound is accepted and not used.
+ * workspace: dk_attention_fp8_workspace_bytes(B, H, S) = B * H * ceil(S / 128) * 128 * 264 bytes (host only), 16-byte aligned, the caller's.
+ * Refused, nothing launched, dk_last_error() names the rule: D != 128; a score bias; a workspace smaller than the size query; S > 65536; a batch
+ * row of QKV of 4 GiB or more; a scale <= 0.  fp16, identity attention and attention groups have no entry (the route refuses them by name).
+ * The route is kernel 12 -- plan->blocks then counts 128-row blocks, split = 1, launches = 2 (+ 1 with O8) -- whatever dk_tune_set("attn", .)
+ * says.  dk_attention_fp8_plan: host only, the same checks with a region of workspace_bytes bytes; plan->o8_split is read when d->O8 is set. */
+size_t dk_attention_fp8_workspace_bytes(int32_t B, int32_t H, int32_t S);
+int dk_attention_fp8_bf16(const dk_attention_desc* d, void* workspace, size_t workspace_bytes, void* stream);
+int dk_attention_fp8_plan(const dk_attention_desc* d, size_t workspace_bytes, dk_attention_plan_t* plan);
 
 /* Single-head attention over head_dim 512: the VAE mid block's Attention (vae.py:28-57: softmax((q / sqrt 512) k^T) v over all
  * H * W tokens), flash-style -- the [T, T] score matrix of the reference (537 MB at T = 16384) is never written.  q / k / v / out:
@@ -995,6 +1013,17 @@ int dk_mmdit_set_perturbed_attention(dk_mmdit* m, const int32_t* blocks, int32_t
  * cache; skip layers or perturbed attention.  dk_mmdit_forward_head, dk_mmdit_forward_tail and dk_mmdit_run_blocks are refused while set.
  * Verified against an fp32 oracle with synthetic weights (arithmetic parity); no checkpoint has been run. */
 int dk_mmdit_set_attention_groups(dk_mmdit* m, const uint32_t* groups);
+
+/* ---- Quantised attention: both products of the joint attention in MX-fp8 (opt-in; FLUX geometry, bf16 activations; no reference counterpart) ----
+ * on != 0: the joint attention of every double and single block runs dk_attention_fp8_bf16's kernels (route kernel 12), on bf16-weight engines
+ * and, through the quantiser pass behind the kernel, on fp8_linears engines; nothing else of the model changes.  0, the default: the workspace
+ * size, its carve, every launch and every bit are what they were.  Legal until the first dk_mmdit_prepare, like dk_mmdit_set_dual_attention:
+ * dk_mmdit_workspace_bytes grows by exactly dk_attention_fp8_workspace_bytes(B, heads, S) (the K8 / V8T region, carved behind everything else).
+ * Refused, with no state changed and an error that names the rule (the last four asked again in front of every forward, where they can arise
+ * later): SD3 geometry / head_dim 64; fp16 activations; attention groups; perturbed attention; skip layers; an IP-Adapter (its queries are
+ * read raw from QKV).  dk_mmdit_forward_head, dk_mmdit_forward_tail and dk_mmdit_run_blocks are refused while set (the block cache has not been
+ * shown to compose).  Verified against an emulating oracle with synthetic weights (arithmetic parity); no checkpoint has been run. */
+int dk_mmdit_set_attention_fp8(dk_mmdit* m, int32_t on);
 
 /* ---- SD3 ControlNet (opt-in; the layout of diffusers' SD3ControlNetModel, no counterpart in the reference) ---------------------------
  * Two engines.  The CONTROL-NET engine is an SD3 engine of N_c blocks without a final layer, with a second patch embedder for the
