@@ -203,6 +203,15 @@ SIGNATURES = {
     "dk_gemm_fp4_fused": (_i32, [C.POINTER(dk_gemm_fp8_desc), C.POINTER(dk_gemm_fp8_side), _vp, C.POINTER(dk_gemm_fp8_desc), C.POINTER(dk_gemm_fp8_side),
                                  _vp, _vp]),
     "dk_weight_pitch_fp4": (_i32, [_i32]),
+    "dk_activation_pitch_fp6": (_i32, [_i32]),
+    "dk_activation_bytes_fp6": (_sz, [_i64, _i32]),
+    "dk_quantize_rows_mx6": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _i64, _i32, _vp]),
+    "dk_ln_modulate_rows_mx6": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _f32, _vp, _i32, _vp, _i64, _i32, _vp]),
+    "dk_gemm_fp4a6": (_i32, [C.POINTER(dk_gemm_fp8_desc), _vp, _vp]),
+    "dk_gemm_fp4a6_plan": (_i32, [C.POINTER(dk_gemm_fp8_desc), C.POINTER(dk_gemm_fp8_side), C.POINTER(dk_gemm_fp8_desc), C.POINTER(dk_gemm_fp8_side),
+                                  C.POINTER(dk_gemm_plan_t)]),
+    "dk_gemm_fp4a6_fused": (_i32, [C.POINTER(dk_gemm_fp8_desc), C.POINTER(dk_gemm_fp8_side), _vp, C.POINTER(dk_gemm_fp8_desc), C.POINTER(dk_gemm_fp8_side),
+                                   _vp, _vp]),
     "dk_mmdit_set_guidance": (_i32, [_vp, _f32]),
     # float16 element type (SD3 family): siblings of the bf16 operators, same descriptors
     "dk_gemm_f16": (_i32, [C.POINTER(dk_gemm_desc), _vp]),
@@ -277,6 +286,7 @@ SIGNATURES = {
     "dk_mmdit_set_attention_groups": (_i32, [_vp, _vp]),
     # quantised attention: both products of every block's joint attention in MX-fp8 (before the first prepare)
     "dk_mmdit_set_attention_fp8": (_i32, [_vp, _i32]),
+    "dk_mmdit_set_activation_fp6": (_i32, [_vp, _i32]),
     **{"dk_ln_modulate_dual_" + el: (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
                                             _i32, _f32, _vp]) for el in ("bf16", "f16")},
     # SD3 ControlNet: the control-net engine's setter / hoist / forward, the main engine's taps, and the LayerNorm pass with a residual tap in front

@@ -180,6 +180,9 @@ def build_parser(model_versions: Sequence[str]) -> argparse.ArgumentParser:
                         "bytes; FLUX versions only). Same policies as --fp8 (the quality block count was fitted for fp8 and is reused); not "
                         "together with --fp8, nor with anything --fp8 refuses. Arithmetic verified on synthetic weights only; a 4-bit MLX "
                         "checkpoint is dequantised and re-quantised, not loaded bit for bit.")
+    p.add_argument("--fp4-activations", choices=("mxfp8", "mxfp6"), default="mxfp8",
+                   help="Activation format in front of qkv / fc1 / linear1 of the --fp4 blocks. mxfp6: OCP E2M3 (W4A6), both operands of the "
+                        "MFMA at 6 bits or fewer; only together with --fp4. Arithmetic verified on synthetic weights only.")
     p.add_argument("--activation-dtype", choices=("bfloat16", "float16"), default="bfloat16",
                    help="Element type of the MMDiT's weights and activations. float16 is the reference's dtype for Stable Diffusion 3 "
                         "(SD3 versions only); the text encoders stay bfloat16, the VAE has --vae-dtype.")
@@ -222,13 +225,15 @@ def resolve(args) -> dict:
          "flux": "FLUX" in args.model_version, "low_memory_mode": args.low_memory_mode and not args.benchmark_mode}
     if getattr(args, "fp8", None) and getattr(args, "fp4", None):
         raise ValueError("--fp8 and --fp4 cannot run together: one weight format per engine")
+    if getattr(args, "fp4_activations", "mxfp8") != "mxfp8" and not getattr(args, "fp4", None):
+        raise ValueError("--fp4-activations mxfp6 needs --fp4: the W4A6 GEMM multiplies MX-fp4 weights only")
     if getattr(args, "fp8", None):
         # (config.fp8_config raises a ValueError for the SD3 geometries: head_dim 64)
         from .config import MODEL_CONFIG, fp8_config
         r["mmdit_config"] = fp8_config(MODEL_CONFIG[args.model_version], args.fp8)
     if getattr(args, "fp4", None):  # (config.fp4_config: the same geometry rule)
         from .config import MODEL_CONFIG, fp4_config
-        r["mmdit_config"] = fp4_config(MODEL_CONFIG[args.model_version], args.fp4)
+        r["mmdit_config"] = fp4_config(MODEL_CONFIG[args.model_version], args.fp4, getattr(args, "fp4_activations", "mxfp8"))
     if getattr(args, "activation_dtype", "bfloat16") != "bfloat16":
         # (config.float16_config raises a ValueError for the FLUX geometries and together with --fp8)
         from .config import MODEL_CONFIG, float16_config
@@ -464,7 +469,7 @@ def main(argv: Optional[Sequence[str]] = None, pipeline_overrides: Optional[dict
         extra["mmdit_config"] = fp8_config(extra["mmdit_config"], args.fp8) if extra.get("mmdit_config") is not None else r["mmdit_config"]
     if getattr(args, "fp4", None):
         from .config import fp4_config
-        extra["mmdit_config"] = fp4_config(extra["mmdit_config"], args.fp4) if extra.get("mmdit_config") is not None else r["mmdit_config"]
+        extra["mmdit_config"] = fp4_config(extra["mmdit_config"], args.fp4, getattr(args, "fp4_activations", "mxfp8")) if extra.get("mmdit_config") is not None else r["mmdit_config"]
     if "activation_dtype" in r:
         extra["activation_dtype"] = r["activation_dtype"]
     if "attention_dtype" in r:  # (on the caller's config, or the model version's own, behind --fp8 / --fp4)

@@ -62,6 +62,9 @@ class MMDiTConfig:
     # number format of the two matrix products of the joint attention: "bfloat16", or "fp8_e4m3" -- both on the MX-fp8 MFMA (csrc/attention_f8.hip,
     # dk_mmdit_set_attention_fp8; no reference counterpart); FLUX geometry with bf16 activations only (validate_attention_dtype)
     attention_dtype: str = "bfloat16"
+    # activation format in front of qkv / fc1 / linear1 of the MX-fp4 blocks: "mxfp8" (default, W4A8) or "mxfp6" (OCP E2M3, W4A6 on
+    # csrc/gemm256f4a6.hip; dk_mmdit_set_activation_fp6); only with weight_dtype "mxfp4" (validate_activation_quant)
+    activation_quant: str = "mxfp8"
     # MMDiT-X (Stable Diffusion 3.5 medium; no reference counterpart): the first n double blocks carry a second self-attention over the image
     # tokens alone (x_block.attn2), fed by a second modulation of the block's LayerNorm and gated by a ninth adaLN row; SD3 family only
     # (validate_dual_attention)
@@ -286,18 +289,28 @@ def fp8_config(cfg: MMDiTConfig, policy: str = "quality") -> MMDiTConfig:
     return out
 
 
-def fp4_config(cfg: MMDiTConfig, policy: str = "quality") -> MMDiTConfig:
+def validate_activation_quant(cfg: MMDiTConfig) -> None:
+    """``activation_quant`` is "mxfp8" or "mxfp6"; mxfp6 needs MX-fp4 block Linears (the rule dk_mmdit_set_activation_fp6 enforces)."""
+    if cfg.activation_quant not in ("mxfp8", "mxfp6"):
+        raise ValueError(f"unknown activation_quant {cfg.activation_quant!r} (mxfp8 | mxfp6)")
+    if cfg.activation_quant == "mxfp6" and cfg.weight_dtype != "mxfp4":
+        raise ValueError(f"activation_quant mxfp6 needs weight_dtype mxfp4 (got {cfg.weight_dtype!r}): the W4A6 GEMM multiplies MX-fp4 weights only")
+
+
+def fp4_config(cfg: MMDiTConfig, policy: str = "quality", activations: str = "mxfp8") -> MMDiTConfig:
     """``cfg`` with OCP MX-fp4 block Linears (W4A8 on the block-scaled MFMA, csrc/gemm256f4.hip): ``fp8_config``'s geometry checks and policies.
     "quality" keeps the first FLUX_FP8_QUALITY_BLOCKS double-stream blocks in bf16 -- a count that was fitted for fp8, on synthetic weights, and is
-    reused here, not re-fitted: nothing is known about what fp4 needs on a checkpoint.  "speed": every block Linear in fp4."""
+    reused here, not re-fitted: nothing is known about what fp4 needs on a checkpoint.  "speed": every block Linear in fp4.
+    ``activations="mxfp6"``: qkv, fc1 and linear1 of the fp4 blocks read MX-fp6 (E2M3) activations (W4A6, ``activation_quant``)."""
     if policy not in ("quality", "speed"):
         raise ValueError(f"unknown fp4 policy {policy!r} (quality | speed)")
     if cfg.head_dim != 128 or cfg.hidden_size % 256 != 0:
         raise ValueError(f"fp4_config: the fp4 path needs head_dim 128 and hidden_size % 256 == 0 (got {cfg.head_dim}, {cfg.hidden_size}); "
                          "at run time the text length must be a multiple of 128, the image size is free")
     n = min(FLUX_FP8_QUALITY_BLOCKS, cfg.depth_multimodal) if policy == "quality" else 0
-    out = replace(cfg, weight_dtype="mxfp4", fp8_bf16_double_blocks=n)
+    out = replace(cfg, weight_dtype="mxfp4", fp8_bf16_double_blocks=n, activation_quant=activations)
     validate_fp8_policy(out)
+    validate_activation_quant(out)
     return out
 
 

@@ -526,6 +526,71 @@ extern "C" int dk_gemm_fp4_fused(const dk_gemm_fp8_desc* d, const dk_gemm_fp8_si
   if (const int rc = gemm_f4_params(d2, f2, w_block_scales2, p2)) return rc;
   return dk_launch_gemm256f4(p, &p2, S_(stream));
 }
+// MX-fp6 activations (W4A6): the fp4 entries with the fragment-ordered E2M3 operand (gemm256f4a6.hip), and its two producers (fp6_ops.hip)
+extern "C" int32_t dk_activation_pitch_fp6(int32_t k) { return k > 0 && k % 128 == 0 ? k / 128 * 96 : 0; }
+extern "C" size_t dk_activation_bytes_fp6(int64_t rows, int32_t k) {
+  return rows > 0 ? (size_t)((rows + 15) / 16 * 16) * (size_t)dk_activation_pitch_fp6(k) : 0;
+}
+static int gemm_f4a6_params(const dk_gemm_fp8_desc* d, const dk_gemm_fp8_side* f, const void* w_block_scales, GemmF4Params& p) {
+  if (const int rc = gemm_f4_params(d, f, w_block_scales, p)) return rc;
+  // (the fp8 default, one segment of ceil(M / 128) * 128 rows, serves here too: a row tile's groups stay inside it)
+  DK_REQUIRE(d->a_rows % 16 == 0 && d->a_rows >= (int64_t)d->a_row0 + d->M,
+             "a_rows is a multiple of 16 (whole fragment rows are read) and rows [a_row0, a_row0 + M) lie inside it");
+  return 0;
+}
+extern "C" int dk_gemm_fp4a6(const dk_gemm_fp8_desc* d, const void* w_block_scales, void* stream) {
+  DK_REQUIRE(d != nullptr && w_block_scales != nullptr, "null descriptor / weight block scales");
+  GemmF4Params p;
+  if (const int rc = gemm_f4a6_params(d, nullptr, w_block_scales, p)) return rc;
+  return dk_launch_gemm256f4a6(p, nullptr, S_(stream));
+}
+extern "C" int dk_gemm_fp4a6_fused(const dk_gemm_fp8_desc* d, const dk_gemm_fp8_side* f, const void* w_block_scales, const dk_gemm_fp8_desc* d2,
+                                   const dk_gemm_fp8_side* f2, const void* w_block_scales2, void* stream) {
+  DK_REQUIRE(d != nullptr && w_block_scales != nullptr && (d2 != nullptr || f2 == nullptr) && (d2 == nullptr || w_block_scales2 != nullptr),
+             "null descriptor / weight block scales");
+  GemmF4Params p, p2;
+  if (const int rc = gemm_f4a6_params(d, f, w_block_scales, p)) return rc;
+  if (d2 == nullptr) return dk_launch_gemm256f4a6(p, nullptr, S_(stream));
+  if (const int rc = gemm_f4a6_params(d2, f2, w_block_scales2, p2)) return rc;
+  return dk_launch_gemm256f4a6(p, &p2, S_(stream));
+}
+// what dk_gemm_fp4a6_fused(d, f, ., d2, f2, .) would launch: host only, the launcher's own route (gemm256f4a6.hip)
+extern "C" int dk_gemm_fp4a6_plan(const dk_gemm_fp8_desc* d, const dk_gemm_fp8_side* f, const dk_gemm_fp8_desc* d2, const dk_gemm_fp8_side* f2,
+                                  dk_gemm_plan_t* plan) {
+  DK_REQUIRE(d != nullptr && plan != nullptr && (d2 != nullptr || f2 == nullptr), "null descriptor / plan");
+  GemmF4Params p, p2;
+  const void* sw = d->W;  // (never read: the block scales only have to be there and 4-byte aligned)
+  if (const int rc = gemm_f4a6_params(d, f, sw, p)) return rc;
+  if (d2 != nullptr)
+    if (const int rc = gemm_f4a6_params(d2, f2, d2->W, p2)) return rc;
+  GemmA6Route r;
+  if (const int rc = dk_gemm256f4a6_route(p, d2 != nullptr ? &p2 : nullptr, r)) return rc;
+  memset(plan, 0, sizeof(*plan));
+  const int tiles = r.tiles_a + r.tiles_b, pieces = r.S > 1 ? r.S : 1;
+  plan->kernel = 46; plan->tile_rows = 256; plan->tiles = tiles; plan->workgroups = tiles * pieces; plan->split_tiles = r.S > 1 ? tiles : 0;
+  plan->k_pieces = pieces; plan->ks = r.ks; plan->n_cu = r.n_cu; plan->launches = 1;
+  return 0;
+}
+static int mx6_out_ok(const void* x, void* out, void* out_scales, int M, int h, int ldo, int64_t out_rows, int out_row0) {
+  DK_REQUIRE(x && out && out_scales && M > 0, "bad argument");
+  DK_REQUIRE(out_row0 >= 0 && out_row0 % 16 == 0 && out_rows % 16 == 0 && (int64_t)out_row0 + M <= out_rows,
+             "rows [out_row0, out_row0 + M) must lie inside the out_rows rows of the output (a multiple of 16: the last group is written whole) and start on a 16-row group");
+  DK_REQUIRE(h % 128 == 0 && ldo >= h / 128 * 96, "a row of the output holds 96 bytes per 128 columns");
+  return 0;
+}
+extern "C" int dk_quantize_rows_mx6(const void* x, int32_t ldx, int32_t M, int32_t h, void* out, int32_t ldo, void* out_scales, int64_t out_rows,
+                                    int32_t out_row0, void* stream) {
+  if (const int rc = mx6_out_ok(x, out, out_scales, M, h, ldo, out_rows, out_row0)) return rc;
+  return dk_launch_quantize_mx6((const bf16_t*)x, ldx, M, 0, M, h, mx8_out(out, out_scales, ldo, (long)out_rows, out_row0, M, 0, 0), S_(stream));
+}
+extern "C" int dk_ln_modulate_rows_mx6(const void* x, int32_t ldx, int32_t M, int32_t h, const void* shift, const void* scale, int32_t mod_stride,
+                                       int32_t mod_seg_len, float eps, void* out, int32_t ldo, void* out_scales, int64_t out_rows,
+                                       int32_t out_row0, void* stream) {
+  if (const int rc = mx6_out_ok(x, out, out_scales, M, h, ldo, out_rows, out_row0)) return rc;
+  return dk_launch_ln_modulate_mx6((const bf16_t*)x, ldx, M, h, (const bf16_t*)shift, (const bf16_t*)scale, mod_stride,
+                                   mod_seg_len > 0 ? mod_seg_len : M, M, 0, eps, mx8_out(out, out_scales, ldo, (long)out_rows, out_row0, M, 0, 0),
+                                   S_(stream));
+}
 extern "C" int dk_quantize_mx8(const void* x, int32_t ldx, int32_t M, int32_t h, void* out, int32_t ldo, void* out_scales, int64_t out_rows,
                                int32_t out_row0, int32_t out_col0, void* stream) {
   DK_REQUIRE(x && out && out_scales && M > 0, "bad argument");

@@ -194,6 +194,17 @@ inline int dk_launch_gemm_f8f4(const GemmF4Params& p, const GemmF4Params* p2, hi
   const GemmF8Params q2 = *p2;
   return dk_launch_gemm256f8(p, &q2, stream);
 }
+// ---- W4A6 GEMM (gemm256f4a6.hip): the MX-fp4 problem with A as MX-fp6 (E2M3) in the fragment order the row quantiser writes (fp6_ops.hip):
+// lda = bytes per activation row (a multiple of 96, >= K / 128 * 96), 16 physical rows = one fragment row of 16 * lda bytes in which K-tile t is
+// 1536 bytes; A points at physical row a_row0's fragment row; SA stays the dk_mx_scale_index side array.  The input may not be an MX-fp8 buffer.
+const char* dk_gemm256f4a6_refusal(const GemmF4Params& p);
+struct GemmA6Route {
+  int tiles_a, tiles_b;  // 256 x 256 tiles of the two problems
+  int S, ks;             // pieces per tile (0: no K split) and K-tiles of a workgroup (the finisher piece of a cut tile)
+  int n_cu;
+};
+int dk_gemm256f4a6_route(const GemmF4Params& p, const GemmF4Params* p2, GemmA6Route& r);  // host only: refusals, tiles and the K split of a launch
+int dk_launch_gemm256f4a6(const GemmF4Params& p, const GemmF4Params* p2, hipStream_t stream);
 // bf16 rows -> MX-fp8 rows + scales (fp8_ops.hip).  x: [M, h] bf16 through the row map (seg_len, seg_stride); out row m at
 // physical row out_row0 + (m / o_seg_len) * o_seg_stride + m % o_seg_len of the fp8 buffer (pitch ldo bytes, column
 // offset col0, a multiple of 32).  dk_launch_ln_modulate_mx8 = dk_launch_ln_modulate with that output.
@@ -209,6 +220,14 @@ int dk_launch_quantize2_mx8(const bf16_t* x0, int x_seg_len0, int M0, const Mx8O
 int dk_launch_ln_modulate_mx8(const bf16_t* x, int ldx, int M, int h, const bf16_t* shift, const bf16_t* scale, int mod_stride, int seg_len,
                               int x_seg_len, int x_seg_stride, float eps, const Mx8Out& o, hipStream_t stream);
 int dk_launch_ln_modulate2_mx8(const bf16_t* x0, int M0, const bf16_t* shift0, const bf16_t* scale0, int seg0, const Mx8Out& o0,
+                               const bf16_t* x1, int M1, const bf16_t* shift1, const bf16_t* scale1, int seg1, const Mx8Out& o1, int ldx, int h,
+                               int mod_stride, int x_seg_stride, float eps, hipStream_t stream);
+// the same two producers with an MX-fp6 output in fragment order (fp6_ops.hip): o.out = the buffer's physical row 0, o.ldo = bytes per row
+// (dk_activation_pitch_fp6), o.col0 a multiple of 128, o.row0 of 16; the rows behind the last one, up to a whole group of 16, are written as zeros
+int dk_launch_quantize_mx6(const bf16_t* x, int ldx, int x_seg_len, int x_seg_stride, int M, int h, const Mx8Out& o, hipStream_t stream);
+int dk_launch_ln_modulate_mx6(const bf16_t* x, int ldx, int M, int h, const bf16_t* shift, const bf16_t* scale, int mod_stride, int seg_len,
+                              int x_seg_len, int x_seg_stride, float eps, const Mx8Out& o, hipStream_t stream);
+int dk_launch_ln_modulate2_mx6(const bf16_t* x0, int M0, const bf16_t* shift0, const bf16_t* scale0, int seg0, const Mx8Out& o0,
                                const bf16_t* x1, int M1, const bf16_t* shift1, const bf16_t* scale1, int seg1, const Mx8Out& o1, int ldx, int h,
                                int mod_stride, int x_seg_stride, float eps, hipStream_t stream);
 // dk_launch_ln_modulate over a joint stream with a residual in front of SOME rows (FLUX ControlNet taps; bf16 only, elementwise.hip): of every

@@ -114,6 +114,10 @@ struct dk_mmdit {
   // quantised attention (dk_mmdit_set_attention_fp8): the joint attention of every block on attention_f8.hip; F8WS: its K8 / V8T region, carved
   // behind everything else (off: no take, the carve is what it was)
   bool attn_f8 = false;
+  // MX-fp6 activations (dk_mmdit_set_activation_fp6): the LN-modulate-quantise launches in front of qkv / fc1 / linear1 of the MX-fp4 blocks write
+  // E2M3 fragments into XN8 (a smaller image of the same buffer: 96 instead of 128 bytes per row and K-tile) and those Linears run gemm256f4a6.hip
+  bool act_fp6 = false;
+  int xn_ld() const { return act_fp6 ? cfg.hidden_size / 128 * 96 : cfg.hidden_size; }  // bytes per row of XN8
   void* F8WS = nullptr;
   size_t F8WS_bytes = 0;
   // first-block cache (dk_mmdit_set_block_cache; include/dk_hip.h): image rows [B * S_i, h] each.  BC_R: X1 at the start of a compute tail, R
@@ -787,9 +791,9 @@ static BlockCtx block_ctx(const dk_mmdit* m, int B) {
   c.X_img = m->img(m->X, c.h); c.X_txt = m->txt(m->X, c.h);
   if (m->fp8()) {
     c.T0 = m->txt0_8; c.R8 = m->rows8; c.att_split = c.S_i % 128 != 0;
-    c.xn_img = mx8_out(m->XN8, m->SXN, c.h, c.R8, 0, c.Mi, 0, 0);
-    c.xn_txt = mx8_out(m->XN8, m->SXN, c.h, c.R8, c.T0, c.Mt, 0, 0);
-    c.xn_all = mx8_out(m->XN8, m->SXN, c.h, c.R8, 0, c.B * c.S, 0, 0);
+    c.xn_img = mx8_out(m->XN8, m->SXN, m->xn_ld(), c.R8, 0, c.Mi, 0, 0);
+    c.xn_txt = mx8_out(m->XN8, m->SXN, m->xn_ld(), c.R8, c.T0, c.Mt, 0, 0);
+    c.xn_all = mx8_out(m->XN8, m->SXN, m->xn_ld(), c.R8, 0, c.B * c.S, 0, 0);
   }
   return c;
 }
@@ -1011,6 +1015,21 @@ static void f8_out_hid8(GemmF8Params& p, const dk_mmdit* m, int c_row0) {
   p.r_seg_len = p.M; p.gate_seg_len = p.M;
 }
 
+// the three launches that differ under MX-fp6 activations (dk_mmdit_set_activation_fp6): the LN-modulate-quantise passes and the Linears they feed
+static int ln_modulate2_xn(const dk_mmdit* m, const bf16_t* x0, int M0, const bf16_t* shift0, const bf16_t* scale0, int seg0, const Mx8Out& o0,
+                           const bf16_t* x1, int M1, const bf16_t* shift1, const bf16_t* scale1, int seg1, const Mx8Out& o1, int ldx, int h,
+                           int mod_stride, int x_seg_stride, float eps, hipStream_t st) {
+  return (m->act_fp6 ? dk_launch_ln_modulate2_mx6 : dk_launch_ln_modulate2_mx8)(x0, M0, shift0, scale0, seg0, o0, x1, M1, shift1, scale1, seg1, o1, ldx, h,
+                                                                                  mod_stride, x_seg_stride, eps, st);
+}
+static int ln_modulate_xn(const dk_mmdit* m, const bf16_t* x, int ldx, int M, int h, const bf16_t* shift, const bf16_t* scale, int mod_stride, int seg_len,
+                          int x_seg_len, int x_seg_stride, float eps, const Mx8Out& o, hipStream_t st) {
+  return (m->act_fp6 ? dk_launch_ln_modulate_mx6 : dk_launch_ln_modulate_mx8)(x, ldx, M, h, shift, scale, mod_stride, seg_len, x_seg_len, x_seg_stride, eps, o, st);
+}
+static int gemm_xn(const dk_mmdit* m, const GemmF4Params& p, const GemmF4Params* p2, hipStream_t st) {
+  return m->act_fp6 ? dk_launch_gemm256f4a6(p, p2, st) : dk_launch_gemm_f8f4(p, p2, st);
+}
+
 // MultiModalTransformerBlock i on the fp8 GEMM: the streams' Linears as pairs of one launch (dk_launch_gemm256f8)
 static int double_block_fp8(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t* mod_step, const LaunchCtx& L) {
   const hipStream_t st = L.st;
@@ -1021,19 +1040,19 @@ static int double_block_fp8(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t*
   const bool txt_post = !m->txt_skipped(i);
   const Rows X_img = c.X_img, X_txt = c.X_txt;
   // pre_sdpa (mmdit.py:440-519): LN-modulate -> MX-fp8, q/k/v projection, QK-norm (+ RoPE)
-  DK_TRY(dk_launch_ln_modulate2_mx8(X_img.p, Mi, mod_img, mod_img + h, S_i, c.xn_img, X_txt.p, Mt, mod_txt, mod_txt + h, S_t, c.xn_txt, h, h, mod_stride,
-                                    S, cf.layer_norm_eps, st));
+  DK_TRY(ln_modulate2_xn(m, X_img.p, Mi, mod_img, mod_img + h, S_i, c.xn_img, X_txt.p, Mt, mod_txt, mod_txt + h, S_t, c.xn_txt, h, h, mod_stride, S,
+                         cf.layer_norm_eps, st));
   const bool kf = keys_in_tail(wi, &wt);
   {
-    GemmF4Params qi = f8_params(m, m->XN8, m->SXN, h, 0, Mi, 0, wi.qkv_w8, h, wi.qkv_ws, wi.qkv_sw, wi.qkv_b, Mi, 3 * h, h, DK_EPI_BIAS);
-    GemmF4Params qt = f8_params(m, m->XN8, m->SXN, h, T0, Mt, 0, wt.qkv_w8, h, wt.qkv_ws, wt.qkv_sw, wt.qkv_b, Mt, 3 * h, h, DK_EPI_BIAS);
+    GemmF4Params qi = f8_params(m, m->XN8, m->SXN, m->xn_ld(), 0, Mi, 0, wi.qkv_w8, h, wi.qkv_ws, wi.qkv_sw, wi.qkv_b, Mi, 3 * h, h, DK_EPI_BIAS);
+    GemmF4Params qt = f8_params(m, m->XN8, m->SXN, m->xn_ld(), T0, Mt, 0, wt.qkv_w8, h, wt.qkv_ws, wt.qkv_sw, wt.qkv_b, Mt, 3 * h, h, DK_EPI_BIAS);
     f8_out_bf16(qi, m->img(m->QKV, 3 * h));
     f8_out_bf16(qt, m->txt(m->QKV, 3 * h));
     if (kf) {
       set_key_norm(qi, wi.kn, wi.qn, h, m->D(), c.rope, S_t, S_i);
       set_key_norm(qt, wt.kn, wt.qn, h, m->D(), c.rope, 0, S_t);
     }
-    DK_TRY(dk_launch_gemm_f8f4(qi, &qt, st));
+    DK_TRY(gemm_xn(m, qi, &qt, st));
   }
   if (!kf)
     DK_TRY(dk_launch_qk_norm_rope2(m->QKV + (size_t)S_t * 3 * h, Mi, wi.qn, wi.kn, S_i, S_t, m->QKV, Mt, wt.qn, wt.kn, S_t, 0, 3 * h, 0, h,
@@ -1055,21 +1074,21 @@ static int double_block_fp8(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t*
   }
   // residual += gate_mlp * fc2(gelu(fc1(LN-mod(residual)))); the MLP hidden leaves fc1 as MX-fp8
   if (txt_post)
-    DK_TRY(dk_launch_ln_modulate2_mx8(X_img.p, Mi, mod_img + 3 * h, mod_img + 4 * h, S_i, c.xn_img, X_txt.p, Mt, mod_txt + 3 * h, mod_txt + 4 * h, S_t,
-                                      c.xn_txt, h, h, mod_stride, S, cf.layer_norm_eps, st));
+    DK_TRY(ln_modulate2_xn(m, X_img.p, Mi, mod_img + 3 * h, mod_img + 4 * h, S_i, c.xn_img, X_txt.p, Mt, mod_txt + 3 * h, mod_txt + 4 * h, S_t, c.xn_txt,
+                           h, h, mod_stride, S, cf.layer_norm_eps, st));
   else
-    DK_TRY(dk_launch_ln_modulate_mx8(X_img.p, h, Mi, h, mod_img + 3 * h, mod_img + 4 * h, mod_stride, S_i, S_i, S, cf.layer_norm_eps, c.xn_img, st));
-  GemmF4Params f1i = f8_params(m, m->XN8, m->SXN, h, 0, Mi, 0, wi.fc1_w8, h, wi.fc1_ws, wi.fc1_sw, wi.fc1_b, Mi, r * h, h, DK_EPI_BIAS_GELU);
+    DK_TRY(ln_modulate_xn(m, X_img.p, h, Mi, h, mod_img + 3 * h, mod_img + 4 * h, mod_stride, S_i, S_i, S, cf.layer_norm_eps, c.xn_img, st));
+  GemmF4Params f1i = f8_params(m, m->XN8, m->SXN, m->xn_ld(), 0, Mi, 0, wi.fc1_w8, h, wi.fc1_ws, wi.fc1_sw, wi.fc1_b, Mi, r * h, h, DK_EPI_BIAS_GELU);
   f8_out_hid8(f1i, m, 0);
   GemmF4Params f2i = f8_params(m, m->HC8, m->SHID, ldh8, 0, Mi, 0, wi.fc2_w8, ldh8, wi.fc2_ws, wi.fc2_sw, wi.fc2_b, Mi, h, r * h, DK_EPI_GATE_RES);
   f8_out_bf16(f2i, X_img);
   set_gate_res(f2i, mod_img + 5 * h, S_i, mod_stride, X_img);
-  GemmF4Params f1t = f8_params(m, m->XN8, m->SXN, h, T0, Mt, 0, wt.fc1_w8, h, wt.fc1_ws, wt.fc1_sw, wt.fc1_b, Mt, r * h, h, DK_EPI_BIAS_GELU);
+  GemmF4Params f1t = f8_params(m, m->XN8, m->SXN, m->xn_ld(), T0, Mt, 0, wt.fc1_w8, h, wt.fc1_ws, wt.fc1_sw, wt.fc1_b, Mt, r * h, h, DK_EPI_BIAS_GELU);
   f8_out_hid8(f1t, m, T0);
   GemmF4Params f2t = f8_params(m, m->HC8, m->SHID, ldh8, T0, Mt, 0, wt.fc2_w8, ldh8, wt.fc2_ws, wt.fc2_sw, wt.fc2_b, Mt, h, r * h, DK_EPI_GATE_RES);
   f8_out_bf16(f2t, X_txt);
   set_gate_res(f2t, mod_txt + 5 * h, S_t, mod_stride, X_txt);
-  DK_TRY(dk_launch_gemm_f8f4(f1i, txt_post ? &f1t : nullptr, st));
+  DK_TRY(gemm_xn(m, f1i, txt_post ? &f1t : nullptr, st));
   return dk_launch_gemm_f8f4(f2i, txt_post ? &f2t : nullptr, st);
 }
 
@@ -1081,14 +1100,14 @@ static int single_block_fp8(dk_mmdit* m, const BlockCtx& c, int i, const bf16_t*
   const StreamW& w = m->single[i];
   const bf16_t* mod = block_mod(m, mod_step, 2, i);
   const Rows X = dense(m->X, h);
-  DK_TRY(dk_launch_ln_modulate_mx8(m->X, h, M, h, mod, mod + h, c.mod_stride, S, M, 0, cf.layer_norm_eps, c.xn_all, st));
+  DK_TRY(ln_modulate_xn(m, m->X, h, M, h, mod, mod + h, c.mod_stride, S, M, 0, cf.layer_norm_eps, c.xn_all, st));
   {  // linear1: [q|k|v] -> QKV (bf16), gelu(fc1) -> CAT8[:, h:] (MX-fp8), one pass over the modulated activations
-    GemmF4Params l1 = f8_params(m, m->XN8, m->SXN, h, 0, M, 0, w.qkv_w8, h, w.qkv_ws, w.qkv_sw, w.qkv_b, M, (3 + r) * h, h, DK_EPI_BIAS);
+    GemmF4Params l1 = f8_params(m, m->XN8, m->SXN, m->xn_ld(), 0, M, 0, w.qkv_w8, h, w.qkv_ws, w.qkv_sw, w.qkv_b, M, (3 + r) * h, h, DK_EPI_BIAS);
     f8_out_bf16(l1, dense(m->QKV, 3 * h));
     l1.n_split = 3 * h; l1.C2 = m->HC8 + h; l1.ldc2 = ldcat8; l1.epi2 = DK_EPI_BIAS_GELU; l1.c2_mx8 = 1;
     l1.SC = m->SCAT; l1.sc_nblk = m->nblk; l1.c_row0 = 0; l1.sc_kb0 = h / 32;
     if (keys_in_tail(w, nullptr)) set_key_norm(l1, w.kn, w.qn, h, m->D(), c.rope, 0, S);
-    DK_TRY(dk_launch_gemm_f8f4(l1, nullptr, st));
+    DK_TRY(gemm_xn(m, l1, nullptr, st));
   }
   if (!keys_in_tail(w, nullptr))
     DK_TRY(dk_launch_qk_norm_rope(m->QKV, 3 * h, 0, h, M, cf.num_heads, m->D(), w.qn, w.kn, 1e-6f, c.rope, S, S, 0, S, st, fuse_q()));
@@ -1245,6 +1264,14 @@ extern "C" int dk_mmdit_set_attention_fp8(dk_mmdit* m, int32_t on) {
   DK_REQUIRE(!m->resolved && !m->prepared, "dk_mmdit_set_attention_fp8 is legal only before the first dk_mmdit_prepare (the workspace grows by the K8 / V8T region)");
   if (on) DK_TRY(attention_fp8_ok(m));
   m->attn_f8 = on != 0;
+  return 0;
+}
+// ---- MX-fp6 activations in front of qkv / fc1 / linear1 of an MX-fp4 engine (include/dk_hip.h) ---------------------------------------------------
+extern "C" int dk_mmdit_set_activation_fp6(dk_mmdit* m, int32_t on) {
+  DK_REQUIRE(m != nullptr, "null handle");
+  DK_REQUIRE(!m->resolved && !m->prepared, "dk_mmdit_set_activation_fp6 is legal only before the first dk_mmdit_prepare");
+  if (on) DK_REQUIRE(m->fp4(), "MX-fp6 activations need an engine with MX-fp4 block Linears (fp8_linears == 2): the W4A6 GEMM has no other weight format");
+  m->act_fp6 = on != 0;
   return 0;
 }
 static int no_attention_fp8(const dk_mmdit* m, const char* entry) {

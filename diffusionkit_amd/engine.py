@@ -116,6 +116,15 @@ class MMDiTEngine:
         self.attention_fp8 = False
         if config.attention_dtype == "fp8_e4m3":
             self.set_attention_fp8(True)
+        # MX-fp6 activations (activation_quant = "mxfp6"): before the first prepare, on an MX-fp4 engine only
+        from .config import validate_activation_quant
+        try:
+            validate_activation_quant(config)
+        except ValueError as e:
+            raise _lib.DkHipError(str(e)) from None
+        self.activation_fp6 = False
+        if config.activation_quant == "mxfp6":
+            self.set_activation_fp6(True)
         # SD3 ControlNet: this engine is the ControlNet (no final layer, a second patch embedder, one tap Linear per block); set before the first bind
         from .config import validate_control_net
         try:
@@ -213,6 +222,13 @@ class MMDiTEngine:
         if blocks or self.perturbed_attention:
             self.fork_rows = int(fork_rows)
         self.perturbed_attention = tuple(sorted(blocks))
+
+    def set_activation_fp6(self, on: bool = True) -> None:
+        """dk_mmdit_set_activation_fp6 (include/dk_hip.h): the LayerNorm-modulate launches in front of qkv, fc1 and linear1 of the MX-fp4 blocks write
+        MX-fp6 (E2M3) fragments and those three Linears run the W4A6 GEMM; o_proj, fc2 and linear2 stay W4A8.  Until the first ``prepare``, on an
+        engine with ``weight_dtype == "mxfp4"`` only; ``MMDiTConfig(activation_quant="mxfp6")`` calls it in the constructor."""
+        _lib.check(self.lib.dk_mmdit_set_activation_fp6(self._h, int(bool(on))), "dk_mmdit_set_activation_fp6")
+        self.activation_fp6 = bool(on)
 
     def set_attention_fp8(self, on: bool = True) -> None:
         """dk_mmdit_set_attention_fp8 (include/dk_hip.h): the joint attention of every double and single block runs both matrix products on the

@@ -1178,16 +1178,70 @@ def weight_pitch_fp4(k: int) -> int:
     return int(_lib.load().dk_weight_pitch_fp4(k))
 
 
-def gemm_fp4(a8: Tensor, a_scales: Tensor, w4: Tensor, w_block_scales: Tensor, w_scale: Tensor, bias: Optional[Tensor] = None, **kw):
+def gemm_fp4(a8: Tensor, a_scales: Tensor, w4: Tensor, w_block_scales: Tensor, w_scale: Tensor, bias: Optional[Tensor] = None,
+             activations: str = "mxfp8", **kw):
     """dk_gemm_fp4: ops.gemm_fp8 with an MX-fp4 weight -- w4 uint8 [N, ldw] in the kernel's fragment-row layout and w_block_scales, its E8M0
     side array (both from weights.pack_mxfp4), w_scale f32 [N].  ``k`` is required when the weight is pitched (the activation buffer's width
-    otherwise).  Every other argument and the results are ops.gemm_fp8's."""
+    otherwise).  Every other argument and the results are ops.gemm_fp8's.
+    ``activations="mxfp6"`` (dk_gemm_fp4a6, W4A6): a8 is the fragment-ordered MX-fp6 buffer of ops.quantize_rows_mx6 / weights.pack_activation_mxfp6
+    ([rows rounded up to 16, pitch] bytes) and ``M`` and ``k`` are required: the buffer's shape says neither."""
     _require_cuda(w_block_scales, "w_block_scales", torch.uint8)
     lib = _lib.load()
+    if activations not in ("mxfp8", "mxfp6"):
+        raise ValueError(f"gemm_fp4: activations must be 'mxfp8' or 'mxfp6', not {activations!r}")
+    if activations == "mxfp6" and (kw.get("M") is None or kw.get("k") is None):
+        raise ValueError("gemm_fp4(activations='mxfp6'): M and k are required")
+    name = "dk_gemm_fp4a6" if activations == "mxfp6" else "dk_gemm_fp4"
 
     def launch(desc):
-        _lib.check(lib.dk_gemm_fp4(C.byref(desc), w_block_scales.data_ptr(), _stream()), "dk_gemm_fp4")
+        _lib.check(getattr(lib, name)(C.byref(desc), w_block_scales.data_ptr(), _stream()), name)
     return gemm_fp8(a8, a_scales, w4, w_scale, bias, _launch=launch, **kw)
+
+
+def gemm_fp4a6_plan(d: dict, side: Optional[dict] = None, d2: Optional[dict] = None, side2: Optional[dict] = None):
+    """dk_gemm_fp4a6_plan: what ``gemm_fp4a6_fused_call`` with these descriptors would launch (host only; pointers may be made-up, aligned
+    integers; ``workspace`` / ``workspace_bytes`` tell the rules that the K split is available)."""
+    a, f = _fill(_lib.dk_gemm_fp8_desc, d), _fill(_lib.dk_gemm_fp8_side, side)
+    b, f2 = _fill(_lib.dk_gemm_fp8_desc, d2), _fill(_lib.dk_gemm_fp8_side, side2)
+    plan = _lib.dk_gemm_plan_t()
+    _lib.check(_lib.load().dk_gemm_fp4a6_plan(_ref(a), _ref(f), _ref(b), _ref(f2), C.byref(plan)), "dk_gemm_fp4a6_plan")
+    return plan
+
+
+def activation_bytes_fp6(rows: int, k: int) -> int:
+    return int(_lib.load().dk_activation_bytes_fp6(rows, k))
+
+
+def quantize_rows_mx6(x: Tensor, shift: Optional[Tensor] = None, scale: Optional[Tensor] = None, mod_seg_len: int = 0, eps: float = 1e-6,
+                      out: Optional[Tensor] = None, scales: Optional[Tensor] = None, out_row0: int = 0):
+    """bf16 [M, h] (h a multiple of 128) -> MX-fp6 activations for ops.gemm_fp4(activations="mxfp6"): (E2M3 bytes uint8 [rows rounded up to 16,
+    96 * h / 128] in the GEMM's fragment order, scale side array uint8 of ops.mx_scale_bytes(rows, h)).  weights.quantize_activation_mxfp6
+    defines the values bit for bit, weights.pack_activation_mxfp6 the order.  With ``shift`` and ``scale`` (dk_ln_modulate_rows_mx6): the rows of
+    dk_ln_modulate_bf16, quantised as they leave.  The rows of the last 16-row group behind row M - 1 are written as zeros."""
+    fused = shift is not None or scale is not None
+    for n, t in (("x", x),) + ((("shift", shift), ("scale", scale)) if fused else ()):
+        _require_cuda(t, n, BF)
+    lib = _lib.load()
+    M, h = x.shape
+    pitch = int(lib.dk_activation_pitch_fp6(h))
+    if pitch == 0:
+        raise ValueError(f"quantize_rows_mx6: h = {h} is not a multiple of 128")
+    if out is None:
+        out = torch.zeros((out_row0 + M + 15) // 16 * 16, pitch, dtype=torch.uint8, device=x.device)
+    if scales is None:
+        scales = torch.zeros(mx_scale_bytes(out.shape[0], h), dtype=torch.uint8, device=x.device)
+    _require_cuda(out, "out", torch.uint8)
+    _require_cuda(scales, "scales", torch.uint8)
+    if out.dim() != 2 or out.shape[0] % 16 != 0 or out.stride(1) != 1 or scales.numel() < mx_scale_bytes(out.shape[0], h):
+        raise ValueError("quantize_rows_mx6: out is [a multiple of 16 rows, pitch] bytes, scales ops.mx_scale_bytes(out rows, h) bytes")
+    if fused:
+        _lib.check(lib.dk_ln_modulate_rows_mx6(x.data_ptr(), x.stride(0), M, h, shift.data_ptr(), scale.data_ptr(), shift.stride(0), mod_seg_len, eps,
+                                               out.data_ptr(), out.stride(0), scales.data_ptr(), out.shape[0], out_row0, _stream()),
+                   "dk_ln_modulate_rows_mx6")
+    else:
+        _lib.check(lib.dk_quantize_rows_mx6(x.data_ptr(), x.stride(0), M, h, out.data_ptr(), out.stride(0), scales.data_ptr(), out.shape[0],
+                                            out_row0, _stream()), "dk_quantize_rows_mx6")
+    return out, scales
 
 
 def gemm_fp4_fused_call(d: dict, side: Optional[dict], w_block_scales: Tensor, d2: Optional[dict] = None, side2: Optional[dict] = None,
@@ -1197,3 +1251,12 @@ def gemm_fp4_fused_call(d: dict, side: Optional[dict], w_block_scales: Tensor, d
     b, f2 = _fill(_lib.dk_gemm_fp8_desc, d2), _fill(_lib.dk_gemm_fp8_side, side2)
     _lib.check(_lib.load().dk_gemm_fp4_fused(_ref(a), _ref(f), w_block_scales.data_ptr(), _ref(b), _ref(f2), _ptr(w_block_scales2), _stream()),
                "dk_gemm_fp4_fused")
+
+
+def gemm_fp4a6_fused_call(d: dict, side: Optional[dict], w_block_scales: Tensor, d2: Optional[dict] = None, side2: Optional[dict] = None,
+                          w_block_scales2: Optional[Tensor] = None) -> None:
+    """dk_gemm_fp4a6_fused: gemm_fp4_fused_call's forms on MX-fp6 activations (A: the fragment-ordered buffer, lda its pitch in bytes)."""
+    a, f = _fill(_lib.dk_gemm_fp8_desc, d), _fill(_lib.dk_gemm_fp8_side, side)
+    b, f2 = _fill(_lib.dk_gemm_fp8_desc, d2), _fill(_lib.dk_gemm_fp8_side, side2)
+    _lib.check(_lib.load().dk_gemm_fp4a6_fused(_ref(a), _ref(f), w_block_scales.data_ptr(), _ref(b), _ref(f2), _ptr(w_block_scales2), _stream()),
+               "dk_gemm_fp4a6_fused")

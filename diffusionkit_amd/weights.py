@@ -381,6 +381,94 @@ def unpack_mxfp4(w4: Tensor, sw: Tensor, k: int):
     return code, e8
 
 
+E2M3_MAX = 7.5
+_INV_E2M3_MAX_BITS = 0x3E088889  # fp32 nearest to 1 / 7.5; the kernel multiplies by the same bit pattern (csrc/fp6_ops.hip)
+
+
+def _e2m3_round(a: Tensor) -> Tensor:
+    """non-negative fp32 magnitudes -> E2M3 magnitude codes 0..31 (uint8): round to nearest even on the OCP grid -- steps of 0.125 below 2 (the
+    subnormals and the first binade), 0.25 below 4, 0.5 up to 7.5 -- saturating at 7.5 (code 31).  torch.round rounds halves to the even integer,
+    which is the even code."""
+    a = a.clamp(max=8.0)
+    mag = torch.where(a < 2, torch.round(a * 8) / 8, torch.where(a < 4, torch.round(a * 4) / 4, torch.round(a * 2) / 2)).clamp_(max=E2M3_MAX)
+    return torch.where(mag < 2, mag * 8, torch.where(mag < 4, mag * 4 + 8, mag * 2 + 16)).to(torch.uint8)
+
+
+def quantize_activation_mxfp6(x: Tensor):
+    """[M, K] activations (K a multiple of 32) -> (E2M3 codes uint8 [M, K] with values 0..63, E8M0 bytes uint8 [M, K / 32]): the definition of the
+    MX-fp6 activation format of the W4A6 GEMM (csrc/gemm256f4a6.hip); the row quantiser kernel (csrc/fp6_ops.hip) is held to it bit for bit.
+    Element: OCP E2M3 -- bit 5 the sign, two exponent bits (bias 1), three mantissa bits; subnormal step 0.125, largest magnitude 7.5, no Inf, no NaN.
+    Scale: the MX-fp8 row quantiser's rule (dk_mx8_quantize8) with 7.5 in the place of 448: biased exponent e = ceil(log2(amax / 7.5)) + 127
+    evaluated on the fp32 bit pattern of amax * fp32(1 / 7.5), clamped to [1, 254] -- an all-zero block takes e = 1, as there.  The rounded
+    reciprocal can leave the block maximum one last-place unit above 7.5, which rounds to 7.5.  Elements = RNE(x * 2^(127 - e)) on the E2M3
+    grid, saturating at +-7.5; a result of magnitude zero carries no sign.  e = 254 makes every element 0 (the kernels' 2^(127 - 254) is 0).
+    Non-finite inputs: a block that holds an Inf or a NaN takes scale byte 0xFF (the E8M0 NaN: the block is NaN in every product) and codes 0 --
+    E2M3 itself cannot say it.  fp32 arithmetic on whatever device ``x`` lives on."""
+    xf = x.to(torch.float32)
+    m, k = xf.shape
+    if k % 32 != 0:
+        raise ValueError(f"quantize_activation_mxfp6: K = {k} is not a multiple of 32")
+    xb = xf.view(m, k // 32, 32)
+    bad = ~torch.isfinite(xb).all(dim=2, keepdim=True)
+    amax = torch.where(bad, torch.zeros_like(xb[..., :1]), xb.abs().amax(dim=2, keepdim=True))
+    t = amax * torch.tensor(_INV_E2M3_MAX_BITS, dtype=torch.int32, device=x.device).view(torch.float32)
+    e = ((t.view(torch.int32) + 0x7FFFFF) >> 23).clamp(1, 254)
+    a = torch.ldexp(torch.where(bad | (e == 254), torch.zeros_like(xb), xb.abs()), 127 - e)
+    code = _e2m3_round(a)
+    code = code | (((xb < 0) & (code > 0)).to(torch.uint8) << 5)
+    code = torch.where(bad, torch.zeros_like(code), code)
+    e8 = torch.where(bad, torch.full_like(e, 255), e)
+    return code.view(m, k), e8.view(m, k // 32).to(torch.uint8)
+
+
+def dequantize_activation_mxfp6(code: Tensor, e8: Tensor) -> Tensor:
+    """fp32 values q * 2^(e - 127) of MX-fp6 activations (codes [M, K], E8M0 [M, K / 32]); a block with scale byte 0xFF is NaN"""
+    m, k = code.shape
+    c = (code & 31).to(torch.float32)
+    q = torch.where(c < 8, c * 0.125, torch.ldexp(1.0 + (c % 8) / 8.0, (c.to(torch.int32) >> 3) - 1))
+    q = torch.where((code & 32) != 0, -q, q).view(m, k // 32, 32)
+    out = torch.ldexp(q, (e8.to(torch.int32) - 127)[:, :, None])
+    return torch.where((e8 == 255)[:, :, None], torch.full_like(out, float("nan")), out).view(m, k)
+
+
+def activation_pitch_fp6(k: int) -> int:
+    """bytes per row of a fragment-ordered MX-fp6 activation buffer with k columns (k a multiple of 128): 96 per K-tile"""
+    return k // 128 * 96
+
+
+def pack_activation_mxfp6(code: Tensor, pitch: int = None) -> Tensor:
+    """E2M3 codes [M, K] (K a multiple of 128) -> uint8 [ceil(M / 16) * 16, pitch] in the layout csrc/gemm256f4a6.hip reads -- the activation-side
+    mirror of pack_mxfp4.  32 codes of a (row, 32-K block) are 24 bytes, code e in bits [6 e, 6 e + 6) little-endian (profiles/mxfp6_probe.log).
+    Every 16 rows are one fragment row of 16 * pitch bytes in which K-tile t (128 K) is 1536 bytes: first the leading 16 bytes of every MFMA lane
+    at (q * 16 + r) * 16, then the trailing 8 at 1024 + (q * 16 + r) * 8, lane (r, q) = row r, K [32 q, 32 q + 32) of the tile -- so a lane's
+    operand is one aligned 16-byte and one aligned 8-byte LDS read, both linear over the wave.  Rows past M are zero."""
+    m, k = code.shape
+    pitch = activation_pitch_fp6(k) if pitch is None else pitch
+    if k % 128 != 0 or pitch % 96 != 0 or pitch < activation_pitch_fp6(k):
+        raise ValueError(f"pack_activation_mxfp6: K = {k} (% 128), pitch = {pitch} (% 96, >= K / 128 * 96)")
+    g = (m + 15) // 16
+    c = torch.zeros(g * 16, k, dtype=torch.int32, device=code.device)
+    c[:m] = code.to(torch.int32)
+    c = c.view(g * 16, k // 4, 4)
+    by = torch.stack([c[..., 0] | (c[..., 1] << 6), (c[..., 1] >> 2) | (c[..., 2] << 4), (c[..., 2] >> 4) | (c[..., 3] << 2)], dim=2) & 0xFF
+    by = by.to(torch.uint8).view(g, 16, k // 128, 4, 24).permute(0, 2, 3, 1, 4)  # [G, t, q, r, 24]
+    frag = torch.cat([by[..., :16].reshape(g, k // 128, 1024), by[..., 16:].reshape(g, k // 128, 512)], dim=2)
+    out = torch.zeros(g, 16 * pitch, dtype=torch.uint8, device=code.device)
+    out[:, :k // 128 * 1536] = frag.reshape(g, -1)
+    return out.view(g * 16, pitch)
+
+
+def unpack_activation_mxfp6(a6: Tensor, m: int, k: int) -> Tensor:
+    """inverse of pack_activation_mxfp6: the codes [m, k] of a fragment-ordered buffer"""
+    rows, pitch = a6.shape
+    g, nt = rows // 16, k // 128
+    frag = a6.reshape(g, 16 * pitch)[:, :nt * 1536].reshape(g, nt, 1536)
+    by = torch.cat([frag[..., :1024].reshape(g, nt, 4, 16, 16), frag[..., 1024:].reshape(g, nt, 4, 16, 8)], dim=4)  # [G, t, q, r, 24]
+    by = by.permute(0, 3, 1, 2, 4).reshape(g * 16, k // 4, 3).to(torch.int32)
+    c = torch.stack([by[..., 0], (by[..., 0] >> 6) | (by[..., 1] << 2), (by[..., 1] >> 4) | (by[..., 2] << 4), by[..., 2] >> 2], dim=2) & 63
+    return c.to(torch.uint8).view(g * 16, k)[:m]
+
+
 BLOCK_LINEARS = (".attn.qkv", ".attn.o_proj", ".mlp.fc1", ".mlp.fc2", ".linear1", ".linear2")  # what weight_dtype "fp8_e4m3" / "mxfp4" quantises
 
 

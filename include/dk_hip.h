@@ -407,6 +407,32 @@ int dk_gemm_fp4_fused(const dk_gemm_fp8_desc* d, const dk_gemm_fp8_side* f, cons
 /* bytes per output channel of an MX-fp4 matrix with k columns (k / 2, + 64 from the dk_weight_pitch threshold on) */
 int32_t dk_weight_pitch_fp4(int32_t k);
 
+/* ---- MX-fp6 activations (W4A6): MX-fp4 weights against OCP E2M3 activations, both operands of the block-scaled MFMA at 6 bits or fewer ------
+ * The activation operand is written by the two row quantisers below and read by nothing but dk_gemm_fp4a6: E2M3 elements, 32 of a (row, 32-K
+ * block) packed into 24 bytes, in the GEMM's fragment order (diffusionkit_amd/weights.py: quantize_activation_mxfp6 defines the format bit for bit,
+ * pack_activation_mxfp6 the order).  A buffer of `rows` rows and k columns (k % 128 == 0) is dk_activation_bytes_fp6(rows, k) bytes -- rows rounded
+ * up to 16, dk_activation_pitch_fp6(k) = 96 * k / 128 bytes each -- 16-byte aligned; its E8M0 scales are a dk_mx_scale_bytes(rows, k) side array,
+ * as for MX-fp8.  The quantisers write rows [out_row0, out_row0 + M) (out_row0 % 16 == 0) and zeros into the rest of the last 16-row group.
+ * dk_gemm_fp4a6 / _fused are dk_gemm_fp4 / _fused with that operand: d->A points at the fragment row of physical row d->a_row0, d->lda is the pitch
+ * in bytes; weights, outputs, epilogues, column split, grouped second problem and K-split workspace do not change. */
+int32_t dk_activation_pitch_fp6(int32_t k);
+size_t dk_activation_bytes_fp6(int64_t rows, int32_t k);
+int dk_quantize_rows_mx6(const void* x, int32_t ldx, int32_t M, int32_t h, void* out, int32_t ldo, void* out_scales, int64_t out_rows,
+                         int32_t out_row0, void* stream);
+int dk_ln_modulate_rows_mx6(const void* x, int32_t ldx, int32_t M, int32_t h, const void* shift, const void* scale, int32_t mod_stride,
+                            int32_t mod_seg_len, float eps, void* out, int32_t ldo, void* out_scales, int64_t out_rows, int32_t out_row0,
+                            void* stream);
+int dk_gemm_fp4a6(const dk_gemm_fp8_desc* d, const void* w_block_scales, void* stream);
+int dk_gemm_fp4a6_fused(const dk_gemm_fp8_desc* d, const dk_gemm_fp8_side* f, const void* w_block_scales, const dk_gemm_fp8_desc* d2,
+                        const dk_gemm_fp8_side* f2, const void* w_block_scales2, void* stream);
+/* What dk_gemm_fp4a6_fused(d, f, ., d2, f2, .) WOULD launch on the current device (f, d2, f2 may be NULL), read from the launcher's own route: host
+ * only, no kernel runs, pointers are not dereferenced (NULL-ness and alignment are looked at; `workspace` non-NULL, dk_gemm_workspace_bytes()
+ * large and 256-byte aligned tells the rules that the K split is available), 256 compute units without a GPU.  kernel = 46 (this kernel),
+ * tile_rows = 256, tiles, workgroups = tiles * k_pieces, split_tiles (all of them or none: a launch of at most half a round of tiles with a long
+ * reduction is cut), k_pieces, ks in K-tiles of 128 elements (the finisher piece of a cut tile), n_cu, launches = 1.  Refusals are the launch's. */
+int dk_gemm_fp4a6_plan(const dk_gemm_fp8_desc* d, const dk_gemm_fp8_side* f, const dk_gemm_fp8_desc* d2, const dk_gemm_fp8_side* f2,
+                       dk_gemm_plan_t* plan);
+
 /* affine_transform + LayerNorm, mmdit.py:958-972, 838-849.
  * out[m,:] = LN(x[m,:]) * (1 + scale[b,:]) + shift[b,:], b = m / mod_seg_len. */
 int dk_ln_modulate_bf16(const void* x, int32_t ldx, void* out, int32_t ldo, int32_t M, int32_t h,
@@ -1024,6 +1050,13 @@ int dk_mmdit_set_attention_groups(dk_mmdit* m, const uint32_t* groups);
  * read raw from QKV).  dk_mmdit_forward_head, dk_mmdit_forward_tail and dk_mmdit_run_blocks are refused while set (the block cache has not been
  * shown to compose).  Verified against an emulating oracle with synthetic weights (arithmetic parity); no checkpoint has been run. */
 int dk_mmdit_set_attention_fp8(dk_mmdit* m, int32_t on);
+/* MX-fp6 activations (W4A6) on an MX-fp4 engine (fp8_linears == 2), legal until the first dk_mmdit_prepare.  on != 0: the LayerNorm-modulate
+ * launches in front of qkv / fc1 of the double blocks and linear1 of the single blocks write MX-fp6 (E2M3) fragments (dk_ln_modulate_rows_mx6's
+ * kernel) into the buffer the MX-fp8 rows use -- the fp6 image is smaller, the workspace and its carve do not change -- and those Linears run
+ * dk_gemm_fp4a6's kernel; o_proj, fc2 and linear2 stay W4A8, the bf16 blocks of the precision policy are untouched.  Off, the default: every
+ * launch and every bit are what they were.  Refused by name: an engine without MX-fp4 block Linears (so everything fp8_linears == 2 refuses), a
+ * call after dk_mmdit_prepare. */
+int dk_mmdit_set_activation_fp6(dk_mmdit* m, int32_t on);
 
 /* ---- SD3 ControlNet (opt-in; the layout of diffusers' SD3ControlNetModel, no counterpart in the reference) ---------------------------
  * Two engines.  The CONTROL-NET engine is an SD3 engine of N_c blocks without a final layer, with a second patch embedder for the
